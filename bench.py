@@ -2,8 +2,8 @@
 """bench.py -- output Mpixels/s of the Lanczos resample hot path on N MI355X (one process per GPU).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5|c1] [--shard frames|strips]
-                    [--pattern gradient|noise|blocks|dark] [--mode lsb1|exact] [--frames F] [--regions R]
-                    [--no-cpu-baseline] [--no-extras] [--exchange] [--settle-s SECONDS]
+                    [--pattern gradient|noise|blocks|dark] [--mode lsb1|exact] [--frames F] [--settle-s SECONDS]
+                    [--dump-outputs DIR] [--full [--regions R] [--no-cpu-baseline] [--no-extras] [--exchange] [--planar-path]]
 
 A "step" is ONE pass of the fused resample over a batch of F distinct synthetic frames that are already
 resident in HBM (F = 32 by default for config 2; the steps cycle through R input / output sets whose inputs add up to more
@@ -17,20 +17,28 @@ the environment) it is a rank.  The work shards with NO data-path collective:
     with an input halo (lanczos_strip_input_rows); rank r resamples strip r of each of the F frames: strong scaling.
 Rank 0 prints one JSON line.
 
-Timing: W untimed warm-up steps, then R regions (default 5) of EXACTLY K steps each, every region bracketed by a
-barrier + torch.cuda.synchronize() on both sides and reduced with MAX over ranks; `ms_per_step` and `value` are the
-MEDIAN region (median of >= 5 repeats); all regions are listed under "timing".
+Timing: --settle-s of untimed launches and W untimed warm-up steps, then ONE region of EXACTLY K steps, bracketed by a
+barrier + torch.cuda.synchronize() on both sides and reduced with MAX over ranks: `ms_per_step` = region / K, `value` =
+output pixels of the K steps / region.
 
-roofline (whole step, not one kernel): achieved = algorithmic bytes per step (input + output bytes of the F frames,
+--dump-outputs DIR: after the timed steps, what the last one computed (its output batch) goes to DIR/*.npy as float32,
+48 MiB at most (see dump_outputs).  The inputs are seeded: the same arguments give the same inputs on every run.
+
+A plain run does only the above and prints the headline line.  --full adds everything else, after the headline and its
+dump: the roofline passes, R more timed regions of K steps (--regions, default 5; SURVEY.md 8d: median of >= 5 repeats,
+listed under "timing", never `value`), the other patterns / modes / batches / configs, the PCIe-inclusive host path, the
+multi-rank exchange legs, the CPU baseline with its parity check, and the PMC traffic figure.
+
+roofline (--full; whole step, not one kernel): achieved = algorithmic bytes per step (input + output bytes of the F frames,
 SURVEY.md 8d) / average device time of one step, measured with HIP events on the launch stream by the library
 (lanczos_timing_*: from before the marching kernel to after the in-place-prefix kernel, so both kernels and the gap
 between them are inside).  `kernel_us` / `prefix_kernel_us` split it.  `traffic` is the PMC figure
 (profiles/traffic.json, written by scripts/round_profile.sh) only if it was collected for this exact workload AND
 this exact kernel source (fingerprint of lanczos-hls_amd/csrc); otherwise null.
 
-cpu_baseline = the reference's own software path (oracle/_ref, full_TB.h:29-96 compiled where it lay; kind
-"reference") when that build travelled with the repo, else the CPU restatement (oracle/, kind "port"); timed on this
-host on a bounded sample, rank 0, N = 1 only.
+cpu_baseline (--full) = the reference's own software path (oracle/_ref, full_TB.h:29-96 compiled where it lay; kind
+"reference") when that build is present, else the CPU restatement (oracle/, kind "port"); timed on this host on a bounded
+sample, rank 0, N = 1 only.
 """
 import argparse
 import hashlib
@@ -156,34 +164,45 @@ def cpu_baseline(frame_np, cfg, gpu_out_np):
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=50, help="timed steps (K): one region of exactly K steps")
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--regions", type=int, default=5, help="timed regions of K steps each; the median is reported")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (float32, a fixed sample of at most 48 MiB)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every side measurement (roofline, repeat regions, other patterns / modes / "
+                         "batches / configs, host path, exchange legs, CPU baseline)")
+    ap.add_argument("--regions", type=int, default=5,
+                    help="--full: timed regions of K steps run after the headline, listed with their median (not `value`)")
     ap.add_argument("--settle-s", type=float, default=0.25,
                     help="seconds of untimed launches before the warm-up steps (device clock ramp); 0 disables")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--shard", default="auto", choices=["auto", "frames", "strips"])
     ap.add_argument("--pattern", default="gradient",
                     help="headline input: gradient (natural-image-like, SURVEY.md 8d), noise (worst case for the "
-                         "integer-phase fix-ups), blocks, dark; the others are reported under other_patterns")
+                         "integer-phase fix-ups), blocks, dark; the others are reported under other_patterns (--full)")
     ap.add_argument("--mode", default="lsb1", choices=["lsb1", "exact"])
     ap.add_argument("--rotate", type=int, default=0,
                     help="distinct input/output batch sets the steps cycle through (default: as many as it takes for the inputs "
                          "touched between two uses of a set to exceed twice the 256 MiB Infinity Cache; 1 = the same batch every step)")
     ap.add_argument("--frames", type=int, default=0, help="frames per GPU per step (default: 32, c5: 8)")
     ap.add_argument("--kernel", default="auto", choices=["auto", "generic", "fast"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip other_patterns / host path / c5 strip leg (profiling runs: only the headline launches)")
+                    help="--full: skip other_patterns / host path / c5 strip leg")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse the multi-rank path)")
     ap.add_argument("--same-device", action="store_true",
                     help="rehearsal only: every rank uses cuda:0 (needs --backend gloo)")
     ap.add_argument("--planar-path", action="store_true",
-                    help="also time planar-in / planar-out frames (device layout conversion either side), reported separately")
+                    help="--full: also time planar-in / planar-out frames (device layout conversion either side), reported separately")
     ap.add_argument("--exchange", action="store_true",
-                    help="also time root scatter/gather of the frames over RCCL (N > 1), reported separately")
-    return ap.parse_args()
+                    help="--full: also time root scatter/gather of the frames over RCCL (N > 1), reported separately")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if (args.planar_path or args.exchange) and not args.full:
+        ap.error("--planar-path and --exchange are side measurements: add --full")
+    return args
 
 
 def launch_ranks(args):
@@ -281,6 +300,36 @@ def device_step_times(ctx, torch, wl, n):
     return main_ms / launches / 1e3, prefix_ms / launches / 1e3, launches
 
 
+DUMP_SAMPLES = 12 * 2**20   # --dump-outputs: 12 Mi float32 samples (48 MiB) over all ranks
+DUMP_SEED = 20251016
+
+
+def dump_outputs(torch, wl, out_dir, rank, world):
+    """--dump-outputs DIR: what the last step handed its caller -- the output batch it wrote (wl.y: frames x rows x out_w x
+    channels of uint8 / uint16 samples) -- as float32 sample values, DUMP_SAMPLES at most over all ranks:
+      output_head.npy    (rows, out_w, channels): the first rows of frame 0 (a third of the budget), whole width
+      output_sample.npy  (n,): the batch at sorted flat indices drawn from numpy default_rng(DUMP_SEED) (the rest)
+    Rank r > 0 of a multi-rank run writes the same names with the suffix _rank<r>."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    y = wl.y
+
+    def host_f32(t):
+        if t.dtype == torch.int16:   # the bit pattern of uint16
+            t = t.to(torch.int32) & 0xFFFF
+        return t.to(torch.float32).cpu().numpy()
+
+    budget = DUMP_SAMPLES // max(world, 1)
+    row = y.shape[2] * y.shape[3]
+    head_rows = max(1, min(y.shape[1], budget // 3 // row))
+    flat = y.reshape(-1)
+    n = flat.numel()
+    idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=min(n, budget - head_rows * row)))
+    suffix = f"_rank{rank}" if rank > 0 else ""
+    np.save(os.path.join(out_dir, f"output_head{suffix}.npy"), host_f32(y[0, :head_rows]))
+    np.save(os.path.join(out_dir, f"output_sample{suffix}.npy"), host_f32(flat[torch.from_numpy(idx).to(y.device)]))
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
@@ -372,25 +421,32 @@ def main():
             torch.cuda.synchronize()
 
     settle(wl, args.settle_s)
+    # The settling runs for a time, not a step count: restart the set cycle, so that the same arguments always leave the
+    # last timed step on the same set, (W + K - 1) mod R (what --dump-outputs writes).
+    wl.n = 0
     for _ in range(args.warmup):
         wl.step()
 
-    # Pass A (never part of `value`): K steps between one pair of HIP events on the launch stream -> roofline; then K steps
-    # with the library's per-kernel events -> how the step splits into its kernels.
-    step_s = device_batch_time(torch, wl, args.steps)
-    main_s, prefix_s, launches = device_step_times(ctx, torch, wl, args.steps)
-
-    # Pass B (the timed regions): R x exactly K steps, no instrumentation.  (Replaying one captured step as a HIP
-    # graph was measured too: 0.144-0.150 ms per step against 0.114 ms of plain launches.)
-    regions = [timed_region(wl, args.steps) for _ in range(max(args.regions, 1))]
-    elapsed = sorted(regions)[len(regions) // 2]
-
+    # The headline: one region of exactly K steps, no instrumentation.  (Replaying one captured step as a HIP graph was
+    # measured too: 0.144-0.150 ms per step against 0.114 ms of plain launches.)
+    elapsed = timed_region(wl, args.steps)
+    if args.dump_outputs:
+        dump_outputs(torch, wl, args.dump_outputs, rank, world)
     total_pix_step = sum_over_ranks(float(wl.out_pix))
     value = total_pix_step * args.steps / elapsed / 1e6
-    achieved = wl.alg_bytes / step_s / 1e9 if step_s > 0 else 0.0   # whole step: every kernel + the gaps between them
+
+    regions = []
+    if args.full:
+        # Pass A (never part of `value`): K steps between one pair of HIP events on the launch stream -> roofline; then K
+        # steps with the library's per-kernel events -> how the step splits into its kernels.
+        step_s = device_batch_time(torch, wl, args.steps)
+        main_s, prefix_s, launches = device_step_times(ctx, torch, wl, args.steps)
+        achieved = wl.alg_bytes / step_s / 1e9 if step_s > 0 else 0.0   # whole step: every kernel + the gaps between them
+        # Pass B: R more regions of exactly K steps, no instrumentation (the spread of the headline's measurement)
+        regions = [timed_region(wl, args.steps) for _ in range(max(args.regions, 1))]
 
     extra = {}
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # the other synthetic generators of SURVEY.md 8(d), same launch shape, fewer steps, WHOLE-step device time
         others = {}
         for pat in ("noise", "gradient", "blocks"):
@@ -449,7 +505,7 @@ def main():
                                               "roofline_frac": round(wl.alg_bytes / s_1 / 1e9 / HBM_PEAK_GBS, 4),
                                               "note": "input resident in the 256 MiB Infinity Cache between steps; not the headline"}
 
-    if rank == 0 and world == 1 and not args.no_extras and args.config == "c2":
+    if args.full and rank == 0 and world == 1 and not args.no_extras and args.config == "c2":
         # BASELINE configs 3 and 5 beside the headline (whole-step device time, inputs cycled past the Infinity Cache like the
         # headline's), and the headline's workload at twice the batch: same kernels, same method, fewer steps
         others_cfg = {}
@@ -469,7 +525,7 @@ def main():
             torch.cuda.empty_cache()
         extra["other_configs"] = others_cfg
 
-    if args.exchange and dist is not None and shard == "frames":
+    if args.full and args.exchange and dist is not None and shard == "frames":
         # root-inclusive figure: rank 0 scatters every rank's input frames and gathers the outputs (RCCL)
         reps = 3
         xin = [torch.empty_like(wl.x) for _ in range(world)] if rank == 0 else None
@@ -485,7 +541,7 @@ def main():
         extra["root_scatter_gather"] = {"value": round(total_pix_step * reps / dt / 1e6, 1),
                                         "unit": "Mpix/s", "note": "rank 0 scatters inputs / gathers outputs over RCCL"}
 
-    if dist is not None and shard == "strips":
+    if args.full and dist is not None and shard == "strips":
         # config 5, root-inclusive: every rank sends its output strips to rank 0 (one exchange step)
         reps = 3
         yout = None
@@ -509,7 +565,7 @@ def main():
         extra["root_gather_inclusive"] = {"value": round(total_pix_step * reps / dt / 1e6, 1), "unit": "Mpix/s",
                                           "note": "compute + every rank's output strips sent to rank 0 (RCCL send/recv)"}
 
-    if dist is not None and args.config != "c5" and not args.no_extras:
+    if args.full and dist is not None and args.config != "c5" and not args.no_extras:
         # BASELINE config 5 beside the headline: ONE 8K RGBA16 frame set cut into N row strips (tile sharding)
         c5 = CONFIGS["c5"]
         f5 = 2
@@ -527,7 +583,7 @@ def main():
             "algorithmic_bytes_per_step_all_ranks": int(bytes5)}
         del w5
 
-    if args.planar_path and rank == 0:
+    if args.full and args.planar_path and rank == 0:
         # Callers that hold the reference's planar img[C][H][W] arrays (full_TB.h:20-21): planar -> interleaved,
         # resample, interleaved -> planar, all on the device.  Reported beside the headline, never `value`.
         d = wl.full
@@ -548,7 +604,7 @@ def main():
                                 "note": "planar in -> planar out on the device",
                                 "equals_interleaved_result": bool(torch.equal(yp, y.permute(0, 3, 1, 2)))}
 
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         # PCIe-inclusive rate: host buffers in, host buffers out, through the pipelined lanczos_resample_host.
         # Never `value` (inputs must be resident in HBM for that); DESIGN.md quotes this figure.
         d = wl.full
@@ -570,7 +626,7 @@ def main():
         pin_out.close()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import numpy as np
         wl.step()
         torch.cuda.synchronize()
@@ -584,14 +640,15 @@ def main():
     # FETCH_SIZE doubled per MI355X_MICROARCH.md) and committed under profiles/.  bench.py cannot run the profiler on
     # itself, so it reports that figure ONLY for this exact workload and this exact kernel source; otherwise null.
     traffic = None
-    try:
-        with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
-            tj = json.load(f)
-        ent = tj.get(f"{args.config}:{frames}:{args.pattern}:{args.mode}")
-        if ent and ent.get("csrc_fingerprint") == csrc_fingerprint() and world == 1:
-            traffic = ent["total_bytes_per_step"]
-    except Exception:
-        traffic = None
+    if args.full:
+        try:
+            with open(os.path.join(ROOT, "profiles", "traffic.json")) as f:
+                tj = json.load(f)
+            ent = tj.get(f"{args.config}:{frames}:{args.pattern}:{args.mode}")
+            if ent and ent.get("csrc_fingerprint") == csrc_fingerprint() and world == 1:
+                traffic = ent["total_bytes_per_step"]
+        except Exception:
+            traffic = None
 
     if rank == 0:
         par = (f"{frames} frames per GPU per step over {world} GPU(s)" if shard == "frames" else
@@ -605,21 +662,26 @@ def main():
             "config": {"workload": desc_txt, "frames_per_step_per_gpu": frames, "batch_sets_cycled": wl.rotate, "pattern": args.pattern,
                        "parity_mode": args.mode, "kernel": {1: "generic", 2: "fast"}.get(ctx.last_kernel(), "?"),
                        "settle_s_untimed": args.settle_s, "parallelism": par + ", no data-path collective"},
-            "timing": {"regions": len(regions), "steps_per_region": args.steps, "statistic": "median",
-                       "ms_per_step_all_regions": [round(r / args.steps * 1e3, 4) for r in regions]},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "scope": "whole step on rank 0 (every kernel of the step + the gaps), one HIP-event pair around K steps "
-                                  "on the launch stream; kernel_us / prefix_kernel_us: per-kernel events of a second pass",
-                         "step_us": round(step_s * 1e6, 2), "kernel_us": round(main_s * 1e6, 2),
-                         "prefix_kernel_us": round(prefix_s * 1e6, 2),
-                         "frac_from_ms_per_step": round(wl.alg_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
-                         "algorithmic_bytes_per_step": wl.alg_bytes, "steps_timed": launches},
-            "cpu_baseline": cpu,
+            "timing": {"regions": 1, "steps_per_region": args.steps, "statistic": "one region of exactly K steps"},
         }
-        line.update(extra)
-        if "same_batch_every_step" in extra:   # rounds 1 / 2a quoted this figure (inputs served by the Infinity Cache)
-            line["roofline"]["frac_same_batch_every_step"] = extra["same_batch_every_step"]["roofline_frac"]
+        if args.full:
+            line["timing"]["repeat_regions"] = {
+                "ms_per_step_all_regions": [round(r / args.steps * 1e3, 4) for r in regions],
+                "median_ms_per_step": round(sorted(regions)[len(regions) // 2] / args.steps * 1e3, 4),
+                "note": f"{len(regions)} more regions of K steps after the headline; not part of value"}
+            line["roofline"] = {
+                "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                "scope": "whole step on rank 0 (every kernel of the step + the gaps), one HIP-event pair around K steps "
+                         "on the launch stream; kernel_us / prefix_kernel_us: per-kernel events of a second pass",
+                "step_us": round(step_s * 1e6, 2), "kernel_us": round(main_s * 1e6, 2),
+                "prefix_kernel_us": round(prefix_s * 1e6, 2),
+                "frac_from_ms_per_step": round(wl.alg_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
+                "algorithmic_bytes_per_step": wl.alg_bytes, "steps_timed": launches}
+            line["cpu_baseline"] = cpu
+            line.update(extra)
+            if "same_batch_every_step" in extra:   # rounds 1 / 2a quoted this figure (inputs served by the Infinity Cache)
+                line["roofline"]["frac_same_batch_every_step"] = extra["same_batch_every_step"]["roofline_frac"]
         print(json.dumps(line), flush=True)
     ctx.close()
     if dist is not None:

@@ -9,5 +9,5 @@ if [ -z "$lib" ] || ! python3 -c "import ctypes,sys; l=ctypes.CDLL(sys.argv[1]);
   echo "$0: set LANCZOS_LIB to a build made with EXTRA=-DLZ_PROFILE_BITS (make -C lanczos-hls_amd variant VARIANT=prof EXTRA=-DLZ_PROFILE_BITS)" >&2; exit 2
 fi
 for skip in $skips; do
-  LANCZOS_DEBUG_SKIP=$skip python bench.py --steps 10 --warmup 2 --no-cpu-baseline "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('skip=$skip', d['config']['pattern'], 'kernel_us', d['roofline']['kernel_us'])"
+  LANCZOS_DEBUG_SKIP=$skip python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('skip=$skip', d['config']['pattern'], 'kernel_us', d['roofline']['kernel_us'])"
 done

@@ -1,7 +1,7 @@
 #!/usr/bin/env bash
 # scripts/round_profile.sh <tag> [config] [extra bench args...] -- on the GPU box: one round's evidence for one
 # workload, written under gpurun_out/<tag>/ (copy what should be judged into profiles/):
-#   bench.json            python3 bench.py --config <config> ...        -- the line the driver also produces
+#   bench.json            python3 bench.py --full --config <config> ... -- the full benchmark line (roofline, side figures)
 #   stats/                rocprofv3 --kernel-trace --stats of the same command (headline launches only)
 #   pmc_fetch/ pmc_write/ separate --pmc passes (FETCH_SIZE ; WRITE_SIZE) for the HBM traffic figure
 #   summary.json          per-kernel average durations + traffic per step (+ the csrc fingerprint it belongs to)
@@ -11,7 +11,7 @@ set -uo pipefail
 tag="${1:-round}"; cfg="${2:-c2}"; shift; shift || true
 extra=("$@")
 out="$PWD/gpurun_out/$tag"; mkdir -p "$out"; export TMPDIR=/tmp
-python3 bench.py --config "$cfg" "${extra[@]}" > "$out/bench.json" 2> "$out/bench.err"; echo "bench rc=$?"
+python3 bench.py --full --config "$cfg" "${extra[@]}" > "$out/bench.json" 2> "$out/bench.err"; echo "bench rc=$?"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -o t -- python3 bench.py --config "$cfg" --no-cpu-baseline --no-extras "${extra[@]}" > "$out/bench_under_rocprof.json" 2> "$out/stats.err"; echo "stats rc=$?"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -o p -- python3 bench.py --config "$cfg" --no-cpu-baseline --no-extras --steps 5 --warmup 1 --regions 1 --settle-s 0 "${extra[@]}" > /dev/null 2> "$out/pmc_fetch.err"; echo "fetch rc=$?"
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out/pmc_write" -o p -- python3 bench.py --config "$cfg" --no-cpu-baseline --no-extras --steps 5 --warmup 1 --regions 1 --settle-s 0 "${extra[@]}" > /dev/null 2> "$out/pmc_write.err"; echo "write rc=$?"

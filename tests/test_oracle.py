@@ -5,7 +5,8 @@ Pins, strongest first:
      (oracle/_ref, full_TB.h:29-96) for small shapes x {noise, dark} inputs
   2. tests/golden/kat_digests.json  -- FNV-1a-64 digests of the reference output for medium/large
      shapes, including the five digests recorded in SURVEY.md 8(c)
-  3. oracle/_ref live, when it has been built in this container (skipped on the GPU box)
+  3. tests/golden/live_reference_digests.json -- digests of oracle/_ref's outputs on four inputs per shape, and
+     oracle/_ref itself, sample for sample, where it has been built
 """
 import json
 import math
@@ -86,22 +87,42 @@ def test_survey_kat_full_size():
         assert got == d["survey_8c"][shape] == d["digests"][shape + ":noise"]
 
 
-def test_against_live_reference_build():
-    cases = [r for r in O.ref_configs() if r[2] * r[3] <= 1000 * 600]
-    built = [r for r in cases if os.path.exists(O.ref_so_path(*r))]
-    if not built:
-        pytest.skip("oracle/_ref not built here (make -C oracle ref needs /root/reference)")
+LIVE_DIGESTS = os.path.join(GOLD, "live_reference_digests.json")
+
+
+def live_cases():
+    """Every shape of oracle/ref_configs.txt up to 1000x600 output, four planar inputs each (one rng stream over all shapes,
+    so the inputs do not depend on which reference builds exist).  Yields (key, cfg, name, img)."""
     rng = np.random.default_rng(7)
-    for (iw, ih, ow, oh, sn, sd, a, c) in built:
+    for (iw, ih, ow, oh, sn, sd, a, c) in O.ref_configs():
+        if ow * oh > 1000 * 600:
+            continue
         cfg = O.cfg(iw, ih, ow, oh, c, a, sn, sd)
-        for img in (rng.integers(0, 256, (c, ih, iw), dtype=np.uint8),
-                    rng.integers(0, 40, (c, ih, iw), dtype=np.uint8),
-                    np.full((c, ih, iw), 255, np.uint8),
-                    ((np.add.outer(np.arange(ih), np.arange(iw)) // 4 % 2) * 255).astype(np.uint8)[None]
-                    .repeat(c, 0)):
-            ref = O.ref_expected_planar_u8(cfg, img)
-            got = O.expected_planar_u8(cfg, img)
-            assert np.array_equal(got, ref), (iw, ih, ow, oh, sn, sd, a, c)
+        shape = f"{iw}x{ih}_{ow}x{oh}_{sn}-{sd}_a{a}_c{c}"
+        imgs = {"noise": rng.integers(0, 256, (c, ih, iw), dtype=np.uint8),
+                "dark": rng.integers(0, 40, (c, ih, iw), dtype=np.uint8),
+                "white": np.full((c, ih, iw), 255, np.uint8),
+                "checker": ((np.add.outer(np.arange(ih), np.arange(iw)) // 4 % 2) * 255).astype(np.uint8)[None]
+                .repeat(c, 0)}
+        for name, img in imgs.items():
+            yield f"{shape}:{name}", cfg, name, img
+
+
+def test_against_live_reference_build():
+    """The restatement against the reference's compiled lines (oracle/_ref): digest for digest against the reference outputs
+    recorded in tests/golden/live_reference_digests.json (tests/golden/make_live_digests.py), and sample for sample against
+    oracle/_ref itself where that build exists."""
+    with open(LIVE_DIGESTS) as f:
+        want = json.load(f)["digests"]
+    seen = 0
+    for key, cfg, _, img in live_cases():
+        got = O.expected_planar_u8(cfg, img)
+        assert f"{O.fnv1a64(got):016x}" == want[key], key
+        ref = O.ref_expected_planar_u8(cfg, img)   # None where oracle/_ref was not built
+        if ref is not None:
+            assert np.array_equal(got, ref), key
+        seen += 1
+    assert seen == len(want) >= 60
 
 
 def test_double_to_uint8_truncates():
