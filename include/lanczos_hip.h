@@ -42,7 +42,8 @@ extern "C" {
 
 #define LANCZOS_OK 0
 #define LANCZOS_ERR_BAD_ARG 1      /* null pointer, non-positive size, out != in*N/D, a or channels unsupported */
-#define LANCZOS_ERR_UNSUPPORTED 2  /* valid request this build cannot run (scale < 1; a row strip that starts inside the in-place prefix rows) */
+#define LANCZOS_ERR_UNSUPPORTED 2  /* valid request this build cannot run (scale < 1; a row strip that starts inside the in-place prefix rows).
+                                     Resizes to any size, downscaling included: lanczos_resize_* below */
 #define LANCZOS_ERR_NO_DEVICE 3    /* no HIP device / device index out of range */
 #define LANCZOS_ERR_HIP 4          /* a HIP runtime call failed; see lanczos_last_hip_error() */
 #define LANCZOS_ERR_NOMEM 5
@@ -67,6 +68,9 @@ extern "C" {
 #define LANCZOS_KERNEL_GENERIC 1  /* table-driven, any rational scale > 1, f64 throughout (always exact) */
 #define LANCZOS_KERNEL_FAST 2     /* specialised: integer scale, LDS-staged tiles, f32 taps + exact fallback */
 #define LANCZOS_KERNEL_HLS 3      /* LANCZOS_MODE_HLS: V-then-H with de-ringing clamps, f64 */
+#define LANCZOS_KERNEL_RESIZE_FUSED 4     /* lanczos_resize_*: one launch, H pass into an LDS row ring, V pass from it */
+#define LANCZOS_KERNEL_RESIZE_TWO_PASS 5  /* lanczos_resize_*: H kernel into scratch, V kernel from it (any tap count);
+                                             also a resize that changes one axis only, or none */
 
 typedef struct lanczos_ctx lanczos_ctx; /* opaque: device, stream, cached tap tables, staging buffers */
 
@@ -190,6 +194,52 @@ int lanczos_multi_exchange_selftest(lanczos_multi* m, int messages, size_t bytes
 int lanczos_device_alloc(int device, void** p, size_t bytes);
 int lanczos_device_free(int device, void* p);
 int lanczos_device_copy(int device, void* dst, const void* src, size_t bytes, int to_device);
+
+/* ---- resize to any size (Pillow's contract, NOT the reference's) ----
+ * lanczos_desc above follows the reference's software model and only upscales by one N/D on both axes.  The resize entry
+ * points below take any output size per axis, downscaling included, and produce what Pillow's
+ * Image.resize((out_w, out_h), Image.LANCZOS) produces, byte for byte (a = 3 is Pillow's LANCZOS; a = 2 and 4 use the same
+ * recipe with that a).  Per axis, with scale = in / out, fs = max(scale, 1), support = a * fs:
+ *   output o reads inputs [first, first + count) around centre (o + 0.5) * scale with weights L((i - centre + 0.5) / fs),
+ *   L(x) = sinc(x) sinc(x / a) on [-a, a), normalised to sum 1 and rounded to 22-bit fixed point (host, double);
+ *   acc = 2^21 + sum(sample * coeff) in int32, result = clamp(acc >> 22, 0, 255).
+ * The horizontal pass runs first into an 8-bit intermediate; a pass whose axis keeps its size is skipped (as Pillow does).
+ * Channels are independent: 8-bit interleaved samples, 1, 3 or 4 channels.  Four channels give Pillow's result on RGBX /
+ * RGBa data; Pillow's RGBA mode premultiplies alpha inside resize -- a caller who wants that result premultiplies (and
+ * afterwards un-premultiplies) the data itself. */
+typedef struct lanczos_resize_desc {
+    int32_t in_w, in_h;     /* 1..65535 each */
+    int32_t out_w, out_h;   /* 1..65535 each, independent of the input size and of each other */
+    int32_t channels;       /* 1, 3 or 4, interleaved, 8-bit samples */
+    int32_t a;              /* 2, 3 or 4 (3 = Pillow's LANCZOS) */
+    int32_t reserved[2];    /* must be 0 */
+} lanczos_resize_desc;
+
+/* forced path of lanczos_resize_force (tests and A/B runs only) */
+#define LANCZOS_RESIZE_AUTO 0
+#define LANCZOS_RESIZE_FUSED 1     /* LANCZOS_ERR_UNSUPPORTED where the fused kernel cannot run the shape */
+#define LANCZOS_RESIZE_TWO_PASS 2
+
+/* host only, no GPU needed */
+int lanczos_resize_desc_init(lanczos_resize_desc* d, int in_w, int in_h, int out_w, int out_h, int channels, int a);
+int lanczos_resize_validate(const lanczos_resize_desc* d);   /* LANCZOS_ERR_BAD_ARG: size, channels, a or reserved */
+/* Fixed-point tables of one axis (0 = horizontal, 1 = vertical): output o reads inputs first[o] .. first[o] + count[o] - 1
+ * with coeffs[o * ksize + i] (i < count[o]; zero beyond).  *ksize = 2 * ceil(support) + 1.  With first, count and coeffs all
+ * NULL only *ksize is returned; otherwise all three must hold out (and out * ksize) elements. */
+int lanczos_resize_taps_host(const lanczos_resize_desc* d, int axis, int32_t* first, int32_t* count, int32_t* coeffs,
+                             int* ksize);
+/* Device buffers, asynchronous on `stream` (NULL = the default stream), frames at d_in + f * in_frame_stride and
+ * d_out + f * out_frame_stride (bytes; 0 = tightly packed), as lanczos_resample_device.  The first call of an axis shape
+ * builds its tables and uploads them before it returns (a blocking copy on a private stream, so that the cached tables are
+ * valid whether or not the caller's stream is being captured into a graph and whether or not that graph is ever replayed).
+ * The two-pass path keeps its intermediate in context scratch: one stream at a time per context, and a captured graph
+ * must not outlive its context. */
+int lanczos_resize_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const void* d_in, void* d_out, int frames,
+                          size_t in_frame_stride, size_t out_frame_stride, void* stream);
+/* Host buffers, `frames` frames back to back; synchronous (copy in -> resize -> copy out on the context's stream). */
+int lanczos_resize_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const void* in, void* out, int frames);
+/* LANCZOS_RESIZE_AUTO / _FUSED / _TWO_PASS: tests and A/B runs only (lanczos_force_kernel does not affect resizes). */
+int lanczos_resize_force(lanczos_ctx* ctx, int path);
 
 /* ---- measurement / introspection ---- */
 /* When enabled, every lanczos_resample_device call brackets its main kernel with HIP events on the

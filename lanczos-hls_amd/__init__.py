@@ -23,6 +23,8 @@ LIB_PATH = os.environ.get("LANCZOS_LIB") or os.path.join(_HERE, "liblanczos_hip.
 OK, ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_HIP, ERR_NOMEM, ERR_RCCL = range(7)   # include/lanczos_hip.h:43-49
 MODE_LSB1, MODE_EXACT, MODE_HLS = 0, 1, 2
 KERNEL_NONE, KERNEL_GENERIC, KERNEL_FAST, KERNEL_HLS = 0, 1, 2, 3
+KERNEL_RESIZE_FUSED, KERNEL_RESIZE_TWO_PASS = 4, 5
+RESIZE_AUTO, RESIZE_FUSED, RESIZE_TWO_PASS = 0, 1, 2   # lanczos_resize_force
 
 # every symbol include/lanczos_hip.h declares (tests check the library exports exactly these)
 ABI_SYMBOLS = [
@@ -38,6 +40,8 @@ ABI_SYMBOLS = [
     "lanczos_multi_devices", "lanczos_resample_multi_host", "lanczos_resample_multi_root",
     "lanczos_multi_last_error", "lanczos_multi_exchange_plan", "lanczos_multi_exchange_selftest", "lanczos_device_alloc", "lanczos_device_free",
     "lanczos_device_copy",
+    "lanczos_resize_desc_init", "lanczos_resize_validate", "lanczos_resize_taps_host", "lanczos_resize_device",
+    "lanczos_resize_host", "lanczos_resize_force",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
 
@@ -59,6 +63,16 @@ class Desc(ctypes.Structure):
         ("a", ctypes.c_int32), ("mode", ctypes.c_int32),
         ("out_row0", ctypes.c_int32), ("out_rows", ctypes.c_int32),
         ("reserved", ctypes.c_int32 * 3),
+    ]
+
+
+class ResizeDesc(ctypes.Structure):
+    """lanczos_resize_desc -- resize to any size with Pillow's Lanczos contract (include/lanczos_hip.h)."""
+    _fields_ = [
+        ("in_w", ctypes.c_int32), ("in_h", ctypes.c_int32),
+        ("out_w", ctypes.c_int32), ("out_h", ctypes.c_int32),
+        ("channels", ctypes.c_int32), ("a", ctypes.c_int32),
+        ("reserved", ctypes.c_int32 * 2),
     ]
 
 
@@ -127,6 +141,13 @@ def _lib():
         L.lanczos_resample_multi_host.argtypes = [c_void_p, PD, c_void_p, c_void_p, c_int, c_int]
         L.lanczos_resample_multi_root.argtypes = [c_void_p, PD, c_void_p, c_void_p, c_int, c_int,
                                                   ctypes.POINTER(c_double), ctypes.POINTER(c_double)]
+        PRD = ctypes.POINTER(ResizeDesc)
+        L.lanczos_resize_desc_init.argtypes = [PRD] + [c_int] * 6
+        L.lanczos_resize_validate.argtypes = [PRD]
+        L.lanczos_resize_taps_host.argtypes = [PRD, c_int, c_void_p, c_void_p, c_void_p, PI]
+        L.lanczos_resize_device.argtypes = [c_void_p, PRD, c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p]
+        L.lanczos_resize_host.argtypes = [c_void_p, PRD, c_void_p, c_void_p, c_int]
+        L.lanczos_resize_force.argtypes = [c_void_p, c_int]
         L.lanczos_strerror.restype = ctypes.c_char_p
         L.lanczos_version.argtypes = []
         L.lanczos_version.restype = ctypes.c_char_p
@@ -180,6 +201,28 @@ def taps_host(desc, axis):
     _check(_lib().lanczos_taps_host(ctypes.byref(desc), axis, first.ctypes.data, w.ctypes.data),
            "lanczos_taps_host")
     return first, w
+
+
+def resize_desc(in_w, in_h, out_w, out_h, channels, a=3):
+    """A validated lanczos_resize_desc (Pillow's contract: any output size, downscaling included)."""
+    d = ResizeDesc()
+    _check(_lib().lanczos_resize_desc_init(ctypes.byref(d), in_w, in_h, out_w, out_h, channels, a),
+           "lanczos_resize_desc_init")
+    return d
+
+
+def resize_taps_host(desc, axis):
+    """Fixed-point tables of one axis (0 = horizontal, 1 = vertical): (first[out], count[out], coeffs[out][ksize]) int32."""
+    ks = ctypes.c_int()
+    _check(_lib().lanczos_resize_taps_host(ctypes.byref(desc), axis, None, None, None, ctypes.byref(ks)),
+           "lanczos_resize_taps_host")
+    n = desc.out_w if axis == 0 else desc.out_h
+    first = np.empty(n, dtype=np.int32)
+    count = np.empty(n, dtype=np.int32)
+    coeffs = np.empty((n, ks.value), dtype=np.int32)
+    _check(_lib().lanczos_resize_taps_host(ctypes.byref(desc), axis, first.ctypes.data, count.ctypes.data,
+                                           coeffs.ctypes.data, ctypes.byref(ks)), "lanczos_resize_taps_host")
+    return first, count, coeffs
 
 
 class PinnedArray:
@@ -289,6 +332,33 @@ class Context:
     def resample_planar_device(self, desc, d_in_planar, d_out_planar, frames, stream=None):
         _check(_lib().lanczos_resample_planar_device(self._h, ctypes.byref(desc), d_in_planar, d_out_planar, frames,
                                                      stream), "lanczos_resample_planar_device")
+
+    # -- resize to any size (Pillow's contract, lanczos_resize_*)
+    def resize(self, img, out_w, out_h, a=3):
+        """img: uint8 [H][W], [H][W][C] or [F][H][W][C] -> the same layout at out_h x out_w, bytes identical to Pillow's
+        Image.resize((out_w, out_h), Image.LANCZOS) for a = 3 (RGBX semantics for four channels: no premultiplication)."""
+        img = np.ascontiguousarray(img)
+        if img.dtype != np.uint8 or img.ndim not in (2, 3, 4):
+            raise LanczosError(ERR_BAD_ARG, "resize: expected a uint8 [H][W], [H][W][C] or [F][H][W][C] array")
+        x = img.reshape(img.shape + (1,)) if img.ndim == 2 else img
+        x = x if x.ndim == 4 else x[None]
+        f, h, w, c = x.shape
+        d = resize_desc(w, h, out_w, out_h, c, a)
+        out = np.empty((f, out_h, out_w, c), dtype=np.uint8)
+        _check(_lib().lanczos_resize_host(self._h, ctypes.byref(d), x.ctypes.data, out.ctypes.data, f),
+               "lanczos_resize_host")
+        if img.ndim == 2:
+            return out[0, :, :, 0]
+        return out if img.ndim == 4 else out[0]
+
+    def resize_device(self, desc, d_in, d_out, frames, in_frame_stride=0, out_frame_stride=0, stream=None):
+        """Device pointers, asynchronous on `stream` (None = the default stream)."""
+        _check(_lib().lanczos_resize_device(self._h, ctypes.byref(desc), d_in, d_out, frames, in_frame_stride,
+                                            out_frame_stride, stream), "lanczos_resize_device")
+
+    def resize_force(self, path):
+        """RESIZE_AUTO / RESIZE_FUSED / RESIZE_TWO_PASS (tests and A/B runs)."""
+        _check(_lib().lanczos_resize_force(self._h, path), "lanczos_resize_force")
 
     def timing_enable(self, on=True):
         _check(_lib().lanczos_timing_enable(self._h, 1 if on else 0), "lanczos_timing_enable")

@@ -24,6 +24,7 @@
 #include "lanczos_generic.hpp"
 #include "lanczos_hls.hpp"
 #include "lanczos_rational.hpp"
+#include "lanczos_resize.hpp"
 #include "lanczos_kernels_common.hpp"
 #include "lanczos_taps.hpp"
 
@@ -87,6 +88,7 @@ struct lanczos_ctx {
     void* planar_in = nullptr;
     void* planar_out = nullptr;
     size_t planar_in_bytes = 0, planar_out_bytes = 0;
+    lz::ResizeState* resize = nullptr;   // lanczos_resize_* (lanczos_resize.hip), created on first use
 };
 #ifdef LZ_PROFILE_BITS
 static constexpr size_t kStampBytes = 16384 * 8 * 6 * 8;
@@ -505,6 +507,7 @@ int lanczos_destroy(lanczos_ctx* ctx) {
     ctx->wg_tabs.release_all();
     for (auto& kv : ctx->plans) free_plan(kv.second);
     ctx->plans.clear();
+    delete ctx->resize;
 #ifdef LZ_PROFILE_BITS
     if (ctx->stamp_buf) {
         diag_report(ctx, stderr);
@@ -1003,6 +1006,71 @@ int lanczos_resample_planar_device(lanczos_ctx* ctx, const lanczos_desc* d, cons
     if (rc != LANCZOS_OK) return rc;
     return lanczos_interleaved_to_planar_device(ctx, ctx->planar_out, d_out_planar, d->out_w, d->out_h, d->channels,
                                                 d->bytes_per_sample, frames, stream);
+}
+
+// ---- resize to any size (Pillow's contract; lanczos_resize.hip) ------------------------------------------------------
+int lanczos_resize_desc_init(lanczos_resize_desc* d, int in_w, int in_h, int out_w, int out_h, int channels, int a) {
+    if (!d) return LANCZOS_ERR_BAD_ARG;
+    memset(d, 0, sizeof(*d));
+    d->in_w = in_w, d->in_h = in_h, d->out_w = out_w, d->out_h = out_h, d->channels = channels, d->a = a;
+    return lz::resize_validate(d);
+}
+
+int lanczos_resize_validate(const lanczos_resize_desc* d) { return lz::resize_validate(d); }
+
+int lanczos_resize_taps_host(const lanczos_resize_desc* d, int axis, int32_t* first, int32_t* count, int32_t* coeffs,
+                             int* ksize) {
+    int rc = lz::resize_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    if (!ksize || (axis != 0 && axis != 1)) return LANCZOS_ERR_BAD_ARG;
+    const int in_n = axis == 0 ? d->in_w : d->in_h, out_n = axis == 0 ? d->out_w : d->out_h;
+    *ksize = lz::resize_ksize(in_n, out_n, d->a);
+    if (!first && !count && !coeffs) return LANCZOS_OK;
+    if (!first || !count || !coeffs) return LANCZOS_ERR_BAD_ARG;
+    lz::ResizeAxisHost t;
+    if (!lz::resize_build_axis(in_n, out_n, d->a, &t)) return LANCZOS_ERR_UNSUPPORTED;
+    memcpy(first, t.first.data(), t.first.size() * sizeof(int32_t));
+    memcpy(count, t.count.data(), t.count.size() * sizeof(int32_t));
+    memcpy(coeffs, t.coeffs.data(), t.coeffs.size() * sizeof(int32_t));
+    return LANCZOS_OK;
+}
+
+static int resize_state(lanczos_ctx* ctx) {
+    if (!ctx->resize) ctx->resize = new (std::nothrow) lz::ResizeState();
+    return ctx->resize ? LANCZOS_OK : LANCZOS_ERR_NOMEM;
+}
+
+int lanczos_resize_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const void* d_in, void* d_out, int frames,
+                          size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    int rc = lz::resize_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
+    // NULL = the legacy default stream, as lanczos_resample_device
+    return lz::resize_device(ctx->resize, d, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
+                             &ctx->last_kernel, &ctx->last_hip);
+}
+
+int lanczos_resize_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const void* in, void* out, int frames) {
+    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    int rc = lz::resize_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->stream) return LANCZOS_ERR_HIP;
+    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
+    return lz::resize_host(ctx->resize, d, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip);
+}
+
+int lanczos_resize_force(lanczos_ctx* ctx, int path) {
+    if (!ctx || path < LANCZOS_RESIZE_AUTO || path > LANCZOS_RESIZE_TWO_PASS) return LANCZOS_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    int rc = resize_state(ctx);
+    if (rc != LANCZOS_OK) return rc;
+    ctx->resize->force = path;
+    return LANCZOS_OK;
 }
 
 int lanczos_u8(lanczos_ctx* ctx, const uint8_t* in, int in_w, int in_h, int channels, uint8_t* out, int out_w,

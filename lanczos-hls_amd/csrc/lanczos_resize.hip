@@ -1,0 +1,619 @@
+// lanczos_resize.hip -- resize to any size, downscaling included, with Pillow's Lanczos contract (include/lanczos_hip.h,
+// lanczos_resize_*).  Host tap tables in 22-bit fixed point, their per-context cache, and two kernel paths:
+//
+//   fused     k_rs_fused: a workgroup owns a strip of output columns (all channels) of one frame and a chunk of its output
+//             rows.  It marches down the rows in blocks of kRsOB: the input rows the block's vertical taps need are staged
+//             in LDS (buffer loads, range-checked zero fill), the horizontal pass turns them into clipped u8 rows of an LDS
+//             ring, and the vertical pass reads the ring and stores the block's output rows.  Horizontal coefficients stay in
+//             registers for the whole march (a thread keeps one output column); vertical ones are workgroup-uniform scalar
+//             loads.
+//   two-pass  k_rs_h writes the u8 intermediate (in_h x out_w x C per frame) to context scratch, k_rs_v reads it: any tap
+//             count.  It also serves a resize that changes one axis only (one kernel) -- as Pillow, a pass whose axis keeps
+//             its size is skipped.
+//
+// Arithmetic is Pillow's and exact by construction: acc = 2^21 + sum(sample * coeff) in int32 with 24-bit multiplies
+// (|coeff| < 2^23 and 255 * sum|coeff| + 2^21 < 2^31, checked when a table is built), result clamp(acc >> 22, 0, 255).
+#include "lanczos_resize.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+
+namespace lz {
+
+// ---- host tables -------------------------------------------------------------------------------------------------
+
+int resize_validate(const lanczos_resize_desc* d) {
+    if (!d) return LANCZOS_ERR_BAD_ARG;
+    const int sizes[4] = {d->in_w, d->in_h, d->out_w, d->out_h};
+    for (int s : sizes)
+        if (s < 1 || s > kResizeMaxSize) return LANCZOS_ERR_BAD_ARG;
+    if (d->channels != 1 && d->channels != 3 && d->channels != 4) return LANCZOS_ERR_BAD_ARG;
+    if (d->a < 2 || d->a > 4) return LANCZOS_ERR_BAD_ARG;
+    if (d->reserved[0] != 0 || d->reserved[1] != 0) return LANCZOS_ERR_BAD_ARG;
+    return LANCZOS_OK;
+}
+
+// Pillow's sinc_filter / lanczos_filter with a as a parameter (libm sin, double)
+static double rs_sinc(double x) {
+    if (x == 0.0) return 1.0;
+    x = x * M_PI;
+    return sin(x) / x;
+}
+static double rs_filter(double x, int a) {
+    if (-a <= x && x < a) return rs_sinc(x) * rs_sinc(x / a);
+    return 0.0;
+}
+
+int resize_ksize(int in_n, int out_n, int a) {
+    const double scale = (double)in_n / out_n;
+    const double fs = scale > 1.0 ? scale : 1.0;
+    return (int)ceil(a * fs) * 2 + 1;
+}
+
+bool resize_build_axis(int in_n, int out_n, int a, ResizeAxisHost* t) {
+    const double scale = (double)in_n / out_n;
+    const double fs = scale > 1.0 ? scale : 1.0;
+    const double support = a * fs;
+    const double ss = 1.0 / fs;
+    const int ksize = (int)ceil(support) * 2 + 1;
+    t->in_n = in_n, t->out_n = out_n, t->a = a, t->ksize = ksize;
+    t->first.assign(out_n, 0);
+    t->count.assign(out_n, 0);
+    t->coeffs.assign((size_t)out_n * ksize, 0);
+    std::vector<double> w(ksize);
+    bool ok = true;
+    for (int o = 0; o < out_n; o++) {
+        const double center = (o + 0.5) * scale;
+        int xmin = (int)(center - support + 0.5);
+        if (xmin < 0) xmin = 0;
+        int xmax = (int)(center + support + 0.5);
+        if (xmax > in_n) xmax = in_n;
+        const int n = xmax - xmin;
+        double ww = 0.0;
+        for (int i = 0; i < n; i++) {
+            w[i] = rs_filter((i + xmin - center + 0.5) * ss, a);
+            ww += w[i];
+        }
+        int32_t* k = &t->coeffs[(size_t)o * ksize];
+        long long abs_sum = 0;
+        for (int i = 0; i < n; i++) {
+            const double v = ww != 0.0 ? w[i] / ww : w[i];
+            k[i] = v < 0 ? (int32_t)(-0.5 + v * (1 << kResizePrecision)) : (int32_t)(0.5 + v * (1 << kResizePrecision));
+            if (k[i] <= -(1 << 23) || k[i] >= (1 << 23)) ok = false;
+            abs_sum += k[i] < 0 ? -(long long)k[i] : k[i];
+        }
+        if (255 * abs_sum + (1 << (kResizePrecision - 1)) >= (1ll << 31)) ok = false;
+        t->first[o] = xmin;
+        t->count[o] = n;
+    }
+    return ok;
+}
+
+// ---- kernels -----------------------------------------------------------------------------------------------------
+
+constexpr int kRsThreads = 256;
+constexpr int kRsOB = 8;                 // output rows per march step of the fused kernel
+constexpr int kRsFusedMaxLds = 80 * 1024;   // at least two fused workgroups per CU (160 KiB of LDS)
+constexpr int kRsRowsPerChunkMin = 4 * kRsOB;
+constexpr int kRsTargetWgs = 2048;
+constexpr int kRsLoadBatch = 16;   // staging loads in flight per thread
+
+__device__ __forceinline__ int rs_mad(int sample, int coeff, int acc) { return __mul24(sample, coeff) + acc; }
+__device__ __forceinline__ uint32_t rs_clip8(int acc) { return (uint32_t)min(max(acc >> kResizePrecision, 0), 255); }
+
+// one pass of the two-pass path: `n_cols` samples per output row, `rows` output rows, frames in blockIdx.z
+struct RsPass {
+    const uint8_t* src;
+    uint8_t* dst;
+    unsigned long long src_fs, dst_fs;   // frame strides (bytes)
+    unsigned long long src_pitch, dst_pitch;
+    int n_cols, channels;
+    const int32_t *first, *count, *coeffs;
+    int ksize;
+};
+
+// horizontal: output sample x = o * C + c of row blockIdx.y
+__global__ __launch_bounds__(kRsThreads) void k_rs_h(RsPass p) {
+    const int x = blockIdx.x * kRsThreads + threadIdx.x;
+    if (x >= p.n_cols) return;
+    const int o = x / p.channels, c = x - o * p.channels;
+    const uint8_t* src = p.src + blockIdx.z * p.src_fs + blockIdx.y * p.src_pitch + c;
+    const int f = p.first[o], n = p.count[o];
+    const int32_t* k = p.coeffs + (size_t)o * p.ksize;
+    int acc = 1 << (kResizePrecision - 1);
+#pragma unroll 8
+    for (int i = 0; i < n; i++) acc = rs_mad(src[(size_t)(f + i) * p.channels], k[i], acc);
+    p.dst[blockIdx.z * p.dst_fs + blockIdx.y * p.dst_pitch + x] = (uint8_t)rs_clip8(acc);
+}
+
+// vertical: output row o = blockIdx.y, sample column x (coefficients uniform over the workgroup)
+__global__ __launch_bounds__(kRsThreads) void k_rs_v(RsPass p) {
+    const int x = blockIdx.x * kRsThreads + threadIdx.x;
+    if (x >= p.n_cols) return;
+    const int o = blockIdx.y;
+    const int f = p.first[o], n = p.count[o];
+    const int32_t* k = p.coeffs + (size_t)o * p.ksize;
+    const uint8_t* src = p.src + blockIdx.z * p.src_fs + (size_t)f * p.src_pitch + x;
+    int acc = 1 << (kResizePrecision - 1);
+#pragma unroll 8
+    for (int i = 0; i < n; i++) acc = rs_mad(src[(size_t)i * p.src_pitch], k[i], acc);
+    p.dst[blockIdx.z * p.dst_fs + o * p.dst_pitch + x] = (uint8_t)rs_clip8(acc);
+}
+
+struct RsFused {
+    const uint8_t* in;
+    uint8_t* out;
+    unsigned long long in_fs, out_fs;
+    int in_pitch, out_pitch, in_h, out_w, out_h;
+    const int32_t *hf, *hc, *hk;
+    int hks;
+    const int32_t *vf, *vc, *vk;
+    int vks;
+    int strips, rows_per_chunk;   // grid.x = strips * chunks, grid.y = frames
+    int ring_rows, stage_rows, stage_dw;
+};
+
+template <int C>
+struct RsStrip {
+    static constexpr int SW = C == 4 ? 64 : 256;   // output pixels per strip: ring rows of 256 / 768 / 256 bytes
+    static constexpr int RL = kRsThreads / SW;    // input rows per horizontal round
+    static constexpr int RDW = SW * C / 4;        // ring row in dwords
+    static constexpr int WPR = RDW / 64;          // waves per ring row in the vertical pass
+};
+
+template <int C, int K>
+__global__ __launch_bounds__(kRsThreads) void k_rs_fused(RsFused g) {
+    using S = RsStrip<C>;
+    constexpr int SW = S::SW, RL = S::RL, RDW = S::RDW, WPR = S::WPR;
+    constexpr int NE = (K * C + 3) / 4;   // dwords of one horizontal window
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    uint32_t* ring = lds;                        // [ring_rows][RDW]
+    uint32_t* stage = lds + g.ring_rows * RDW;   // [stage_rows][stage_dw]
+    uint8_t* ring8 = (uint8_t*)ring;
+
+    const int tid = threadIdx.x;
+    const int strip = blockIdx.x % g.strips, chunk = blockIdx.x / g.strips;
+    const int x0 = strip * SW;
+    const int sw = min(SW, g.out_w - x0);
+    const int xs = g.hf[x0];   // first input pixel of the strip's span
+
+    // horizontal: this thread's output column for the whole march, its coefficients in registers
+    const int px = tid % SW, rl = tid / SW;
+    int kh[K];
+    int hoffb;
+    {
+        const int p = x0 + min(px, sw - 1);
+        const int n = px < sw ? g.hc[p] : 0;
+        hoffb = (g.hf[p] - xs) * C;
+#pragma unroll
+        for (int k = 0; k < K; k++) kh[k] = k < n ? g.hk[(size_t)p * g.hks + k] : 0;
+    }
+
+    const uint8_t* fin = g.in + blockIdx.y * g.in_fs;
+    // dword-aligned base and range: the bytes in front of the frame and behind its end that share a dword with it (same
+    // page) are read but only ever multiplied by zero coefficients; everything further out reads as 0
+    const int delta = (int)((uintptr_t)fin & 3);
+    const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint8_t*>(fin - delta), 0, (unsigned)((delta + g.in_h * g.in_pitch + 3) & ~3), 0x00020000);
+    uint8_t* fout = g.out + blockIdx.y * g.out_fs;
+    const __amdgpu_buffer_rsrc_t orsrc =
+        __builtin_amdgcn_make_buffer_rsrc(fout, 0, (unsigned)(g.out_h * g.out_pitch), 0x00020000);
+    const bool out_aligned = (((uintptr_t)fout | (unsigned)g.out_pitch | (unsigned)(x0 * C)) & 3) == 0;
+    const int valid_bytes = sw * C;
+
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+    const int o_begin = chunk * g.rows_per_chunk;
+    const int o_end = min(o_begin + g.rows_per_chunk, g.out_h);
+    const float inv_sd = 1.0f / (float)g.stage_dw;
+    int hi = g.vf[o_begin];   // next input row to produce
+    for (int o0 = o_begin; o0 < o_end; o0 += kRsOB) {
+        const int nob = min(kRsOB, o_end - o0);
+        const int lo = g.vf[o0];
+        const int need = g.vf[o0 + nob - 1] + g.vc[o0 + nob - 1];
+        if (hi < lo) hi = lo;
+        while (hi < need) {
+            const int nr = min(g.stage_rows, need - hi);
+            // kRsLoadBatch loads in flight per thread before the first LDS write (one HBM latency per batch, not per dword)
+            const int total = nr * g.stage_dw;
+            for (int u0 = tid; u0 < total; u0 += kRsLoadBatch * kRsThreads) {
+                uint32_t v[kRsLoadBatch];
+#pragma unroll
+                for (int b = 0; b < kRsLoadBatch; b++) {
+                    const int u = u0 + b * kRsThreads;
+                    int r = (int)((float)u * inv_sd);   // u / stage_dw, corrected below (u < 2^20)
+                    r -= r * g.stage_dw > u;
+                    r += (r + 1) * g.stage_dw <= u;
+                    const int off = delta + (hi + r) * g.in_pitch + xs * C;
+                    v[b] = u < total ? __builtin_amdgcn_raw_buffer_load_b32(irsrc, (off & ~3) + 4 * (u - r * g.stage_dw), 0, 0)
+                                     : 0u;
+                }
+#pragma unroll
+                for (int b = 0; b < kRsLoadBatch; b++)
+                    if (u0 + b * kRsThreads < total) stage[u0 + b * kRsThreads] = v[b];
+            }
+            __syncthreads();
+            for (int j = rl; j < nr; j += RL) {
+                const int pos = ((delta + (hi + j) * g.in_pitch + xs * C) & 3) + hoffb;
+                const uint32_t* srow = stage + j * g.stage_dw + (pos >> 2);
+                const unsigned sh = pos & 3;
+                uint32_t dw[NE + 1];
+#pragma unroll
+                for (int t = 0; t <= NE; t++) dw[t] = srow[t];
+                int acc[C];
+#pragma unroll
+                for (int c = 0; c < C; c++) acc[c] = 1 << (kResizePrecision - 1);
+#pragma unroll
+                for (int t = 0; t < NE; t++) {
+                    const uint32_t e = __builtin_amdgcn_alignbyte(dw[t + 1], dw[t], sh);
+#pragma unroll
+                    for (int b = 0; b < 4; b++) {
+                        const int idx = t * 4 + b;
+                        if (idx < K * C) acc[idx % C] = rs_mad((int)((e >> (8 * b)) & 255u), kh[idx / C], acc[idx % C]);
+                    }
+                }
+                uint8_t* rrow = ring8 + ((hi + j) % g.ring_rows) * (RDW * 4) + px * C;
+#pragma unroll
+                for (int c = 0; c < C; c++) rrow[c] = (uint8_t)rs_clip8(acc[c]);
+            }
+            __syncthreads();
+            hi += nr;
+        }
+        // vertical: one output row per wave (WPR waves per row), coefficients uniform
+        for (int q = wave; q < nob * WPR; q += kRsThreads / 64) {
+            const int r = q / WPR;
+            const int o = o0 + r;
+            const int dcol = (q - r * WPR) * 64 + lane;
+            const int f = g.vf[o], n = g.vc[o];
+            const int32_t* kv = g.vk + (size_t)o * g.vks;
+            int slot = f % g.ring_rows;
+            int a0 = 1 << (kResizePrecision - 1), a1 = a0, a2 = a0, a3 = a0;
+#pragma unroll 4
+            for (int i = 0; i < n; i++) {
+                const int k = kv[i];
+                const uint32_t w = ring[slot * RDW + dcol];
+                a0 = rs_mad((int)(w & 255u), k, a0);
+                a1 = rs_mad((int)((w >> 8) & 255u), k, a1);
+                a2 = rs_mad((int)((w >> 16) & 255u), k, a2);
+                a3 = rs_mad((int)(w >> 24), k, a3);
+                if (++slot == g.ring_rows) slot = 0;
+            }
+            const int b0 = dcol * 4;
+            if (b0 < valid_bytes) {
+                const int row_off = o * g.out_pitch + x0 * C + b0;
+                const uint32_t packed = rs_clip8(a0) | (rs_clip8(a1) << 8) | (rs_clip8(a2) << 16) | (rs_clip8(a3) << 24);
+                if (out_aligned && b0 + 4 <= valid_bytes) {
+                    __builtin_amdgcn_raw_buffer_store_b32(packed, orsrc, row_off, 0, 0);
+                } else {
+                    for (int b = 0; b < 4 && b0 + b < valid_bytes; b++)
+                        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(packed >> (8 * b)), orsrc, row_off + b, 0, 0);
+                }
+            }
+        }
+    }
+}
+
+// horizontal tap counts with a fused instance (a request runs on the smallest one >= its ksize, zero-padded)
+#define LZ_RS_BUCKETS(X) X(7) X(9) X(11) X(13) X(17) X(25)
+
+static int rs_bucket(int ksize) {
+    int k = 0;
+#define X(KB) \
+    if (!k && ksize <= KB) k = KB;
+    LZ_RS_BUCKETS(X)
+#undef X
+    return k;
+}
+
+// ---- host side: cache, planning, launch ---------------------------------------------------------------------------
+
+static bool rs_capturing(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+}
+
+// a block that launches on `streams` may still read: freed by a later call once they have drained.  A stream that is being
+// captured gets no event (it would become a graph node): such a block waits for the final reap behind a device-wide sync.
+static void rs_retire(RetireList& rl, void* p, const std::vector<hipStream_t>& streams) {
+    std::vector<hipStream_t> live;
+    bool captured = false;
+    for (hipStream_t s : streams) {
+        if (rs_capturing(s)) captured = true;
+        else live.push_back(s);
+    }
+    rl.retire({p}, {}, live);
+    if (captured) rl.list.back().unrecorded = true;
+}
+
+ResizeState::~ResizeState() {   // the owner has drained the device
+    retired.reap(true);
+    for (ResizeAxis* a : axes) {
+        (void)hipFree(a->dev);
+        delete a;
+    }
+    for (void* p : kept) (void)hipFree(p);
+    if (scratch) (void)hipFree(scratch);
+    if (stage_in) (void)hipFree(stage_in);
+    if (stage_out) (void)hipFree(stage_out);
+    if (upload) (void)hipStreamDestroy(upload);
+}
+
+// The tables of one axis shape, built and uploaded on first use.  The upload is eager: a copy on the private stream and a
+// wait for it, so an entry is valid from the moment it is cached -- also when the caller's stream is being captured
+// (a copy queued on it would only run when the graph is replayed, perhaps never).
+static int rs_axis(ResizeState* st, int in_n, int out_n, int a, ResizeAxis** out, int* last_hip) {
+    for (size_t i = 0; i < st->axes.size(); i++) {
+        ResizeAxis* ax = st->axes[i];
+        if (ax->key[0] == in_n && ax->key[1] == out_n && ax->key[2] == a) {
+            st->axes.erase(st->axes.begin() + i);
+            st->axes.push_back(ax);   // most recent last
+            *out = ax;
+            return LANCZOS_OK;
+        }
+    }
+    st->retired.reap(false);
+    ResizeAxis* ax = new (std::nothrow) ResizeAxis();
+    if (!ax) return LANCZOS_ERR_NOMEM;
+    ax->key[0] = in_n, ax->key[1] = out_n, ax->key[2] = a;
+    if (!resize_build_axis(in_n, out_n, a, &ax->host)) {
+        delete ax;
+        return LANCZOS_ERR_UNSUPPORTED;
+    }
+    const ResizeAxisHost& h = ax->host;
+    std::vector<int32_t> block((size_t)2 * h.out_n + h.coeffs.size());
+    memcpy(block.data(), h.first.data(), (size_t)h.out_n * 4);
+    memcpy(block.data() + h.out_n, h.count.data(), (size_t)h.out_n * 4);
+    memcpy(block.data() + 2 * (size_t)h.out_n, h.coeffs.data(), h.coeffs.size() * 4);
+    hipError_t e = hipSuccess;
+    if (!st->upload) e = hipStreamCreateWithFlags(&st->upload, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc((void**)&ax->dev, block.size() * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(ax->dev, block.data(), block.size() * 4, hipMemcpyHostToDevice, st->upload);
+    if (e == hipSuccess) e = hipStreamSynchronize(st->upload);
+    if (e != hipSuccess) {
+        *last_hip = (int)e;
+        if (ax->dev) (void)hipFree(ax->dev);   // nothing else has seen the block
+        delete ax;
+        return LANCZOS_ERR_HIP;
+    }
+    if (st->axes.size() >= ResizeState::kMaxAxes) {   // bounded: the least recently used shape goes once its launches drained
+        ResizeAxis* old = st->axes.front();
+        rs_retire(st->retired, old->dev, old->streams);
+        delete old;
+        st->axes.erase(st->axes.begin());
+    }
+    st->axes.push_back(ax);
+    *out = ax;
+    return LANCZOS_OK;
+}
+
+// context scratch of at least `bytes`.  A block a captured launch used may still be named by a live graph: it is kept until
+// the context goes instead of being freed when a larger one replaces it.
+static int rs_scratch(ResizeState* st, size_t bytes, hipStream_t stream, bool capturing, int* last_hip) {
+    if (st->scratch_bytes < bytes) {
+        if (st->scratch) {
+            if (st->scratch_captured) st->kept.push_back(st->scratch);
+            else rs_retire(st->retired, st->scratch, st->scratch_streams);
+        }
+        st->scratch = nullptr;
+        st->scratch_bytes = 0;
+        st->scratch_captured = false;
+        st->scratch_streams.clear();
+        hipError_t e = hipMalloc(&st->scratch, bytes);
+        if (e != hipSuccess) {
+            *last_hip = (int)e;
+            st->scratch = nullptr;
+            return LANCZOS_ERR_HIP;
+        }
+        st->scratch_bytes = bytes;
+    }
+    if (capturing) st->scratch_captured = true;
+    else note_stream(st->scratch_streams, stream);
+    return LANCZOS_OK;
+}
+
+// the fused kernel's launch shape for this request (false: it cannot run it)
+struct RsFusedPlan {
+    int K = 0, strips = 0, rows_per_chunk = 0, chunks = 0, ring_rows = 0, stage_rows = 0, stage_dw = 0;
+    size_t lds = 0;
+};
+static bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H, const ResizeAxisHost& V, int frames,
+                          RsFusedPlan* fp) {
+    if (d->in_w == d->out_w || d->in_h == d->out_h) return false;   // one pass only: nothing to fuse
+    if ((long long)d->in_w * d->in_h * d->channels + 4 >= (1ll << 31)) return false;   // 32-bit buffer offsets
+    if ((long long)d->out_w * d->out_h * d->channels >= (1ll << 31)) return false;
+    fp->K = rs_bucket(H.ksize);
+    if (!fp->K) return false;
+    const int C = d->channels;
+    const int SW = C == 4 ? RsStrip<4>::SW : RsStrip<1>::SW;
+    const int NE = (fp->K * C + 3) / 4;
+    fp->strips = (d->out_w + SW - 1) / SW;
+    int span_dw = 0;
+    for (int s = 0; s < fp->strips; s++) {
+        const int x0 = s * SW, x1 = std::min(d->out_w, x0 + SW) - 1;
+        const int hoffb = (H.first[x1] - H.first[x0]) * C;
+        span_dw = std::max(span_dw, ((3 + hoffb) >> 2) + NE + 1);
+    }
+    fp->stage_dw = span_dw;
+    int ring = 1;
+    for (int o0 = 0; o0 < d->out_h; o0 += kRsOB) {
+        const int last = std::min(o0 + kRsOB, d->out_h) - 1;
+        ring = std::max(ring, V.first[last] + V.count[last] - V.first[o0]);
+    }
+    fp->ring_rows = ring;
+    const double scale_v = (double)d->in_h / d->out_h;
+    fp->stage_rows = std::min(16, (int)ceil(kRsOB * scale_v) + 1);
+    auto lds = [&]() { return (size_t)ring * SW * C + (size_t)fp->stage_rows * fp->stage_dw * 4; };
+    while (lds() > (size_t)kRsFusedMaxLds && fp->stage_rows > 4) fp->stage_rows--;   // wide spans: fewer rows per staging
+    fp->lds = lds();
+    if (fp->lds > (size_t)kRsFusedMaxLds) return false;
+    // row chunks: enough workgroups to fill the chip, each chunk a whole number of march steps
+    int rpc = (d->out_h + kRsOB - 1) / kRsOB * kRsOB;
+    const long long base = (long long)fp->strips * frames;
+    while (base * ((d->out_h + rpc - 1) / rpc) < kRsTargetWgs && rpc > kRsRowsPerChunkMin)
+        rpc = std::max(kRsRowsPerChunkMin, (rpc / 2 + kRsOB - 1) / kRsOB * kRsOB);
+    fp->rows_per_chunk = rpc;
+    fp->chunks = (d->out_h + rpc - 1) / rpc;
+    return (long long)fp->strips * fp->chunks < (1ll << 31);
+}
+
+static hipError_t rs_launch_fused(const lanczos_resize_desc* d, const RsFusedPlan& fp, const ResizeAxis* H,
+                                  const ResizeAxis* V, const uint8_t* in, uint8_t* out, size_t in_fs, size_t out_fs, int frames,
+                                  hipStream_t stream) {
+    RsFused g{};
+    g.in_pitch = d->in_w * d->channels;
+    g.out_pitch = d->out_w * d->channels;
+    g.in_h = d->in_h, g.out_w = d->out_w, g.out_h = d->out_h;
+    g.in_fs = in_fs, g.out_fs = out_fs;
+    g.hf = H->first(), g.hc = H->count(), g.hk = H->coeffs(), g.hks = H->host.ksize;
+    g.vf = V->first(), g.vc = V->count(), g.vk = V->coeffs(), g.vks = V->host.ksize;
+    g.strips = fp.strips, g.rows_per_chunk = fp.rows_per_chunk;
+    g.ring_rows = fp.ring_rows, g.stage_rows = fp.stage_rows, g.stage_dw = fp.stage_dw;
+    for (int f0 = 0; f0 < frames; f0 += 65535) {
+        const int nf = std::min(65535, frames - f0);
+        g.in = in + (size_t)f0 * in_fs;
+        g.out = out + (size_t)f0 * out_fs;
+        const dim3 grid(fp.strips * fp.chunks, nf);
+        bool launched = false;
+#define X(KB)                                                                                                         \
+    if (!launched && fp.K == KB) {                                                                                    \
+        if (d->channels == 1) hipLaunchKernelGGL((k_rs_fused<1, KB>), grid, dim3(kRsThreads), fp.lds, stream, g);     \
+        else if (d->channels == 3) hipLaunchKernelGGL((k_rs_fused<3, KB>), grid, dim3(kRsThreads), fp.lds, stream, g); \
+        else hipLaunchKernelGGL((k_rs_fused<4, KB>), grid, dim3(kRsThreads), fp.lds, stream, g);                      \
+        launched = true;                                                                                              \
+    }
+        LZ_RS_BUCKETS(X)
+#undef X
+        if (!launched) return hipErrorInvalidValue;
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+static hipError_t rs_launch_pass(bool horizontal, const RsPass& p0, int rows, int frames, hipStream_t stream) {
+    RsPass p = p0;
+    for (int f0 = 0; f0 < frames; f0 += 65535) {
+        const int nf = std::min(65535, frames - f0);
+        p.src = p0.src + (size_t)f0 * p0.src_fs;
+        p.dst = p0.dst + (size_t)f0 * p0.dst_fs;
+        const dim3 grid((p.n_cols + kRsThreads - 1) / kRsThreads, rows, nf);
+        if (horizontal) hipLaunchKernelGGL(k_rs_h, grid, dim3(kRsThreads), 0, stream, p);
+        else hipLaunchKernelGGL(k_rs_v, grid, dim3(kRsThreads), 0, stream, p);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_in, void* d_out, int frames,
+                  size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream, int* last_kernel, int* last_hip) {
+    const int C = d->channels;
+    const size_t in_frame = (size_t)d->in_w * d->in_h * C, out_frame = (size_t)d->out_w * d->out_h * C;
+    const size_t in_fs = in_frame_stride ? in_frame_stride : in_frame;
+    const size_t out_fs = out_frame_stride ? out_frame_stride : out_frame;
+    if (in_fs < in_frame || out_fs < out_frame) return LANCZOS_ERR_BAD_ARG;
+    const uint8_t* in = (const uint8_t*)d_in;
+    uint8_t* out = (uint8_t*)d_out;
+    const bool capturing = rs_capturing(stream);
+    const bool need_h = d->in_w != d->out_w, need_v = d->in_h != d->out_h;
+
+    ResizeAxis *H = nullptr, *V = nullptr;
+    int rc;
+    if (need_h && (rc = rs_axis(st, d->in_w, d->out_w, d->a, &H, last_hip)) != LANCZOS_OK) return rc;
+    if (need_v && (rc = rs_axis(st, d->in_h, d->out_h, d->a, &V, last_hip)) != LANCZOS_OK) return rc;
+    for (ResizeAxis* ax : {H, V})
+        if (ax && !capturing) note_stream(ax->streams, stream);
+
+    RsFusedPlan fp;
+    const bool fused_ok = need_h && need_v && rs_fused_plan(d, H->host, V->host, frames, &fp);
+    if (st->force == LANCZOS_RESIZE_FUSED && !fused_ok) return LANCZOS_ERR_UNSUPPORTED;
+    const bool fused = fused_ok && st->force != LANCZOS_RESIZE_TWO_PASS;
+    hipError_t e = hipSuccess;
+    if (fused) {
+        e = rs_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream);
+        *last_kernel = LANCZOS_KERNEL_RESIZE_FUSED;
+    } else if (!need_h && !need_v) {   // Pillow returns a copy
+        e = hipMemcpy2DAsync(out, out_fs, in, in_fs, in_frame, frames, hipMemcpyDeviceToDevice, stream);
+        *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
+    } else {
+        RsPass ph{}, pv{};
+        if (need_h) {
+            ph.src = in, ph.src_fs = in_fs, ph.src_pitch = (size_t)d->in_w * C;
+            ph.n_cols = d->out_w * C, ph.channels = C;
+            ph.first = H->first(), ph.count = H->count(), ph.coeffs = H->coeffs(), ph.ksize = H->host.ksize;
+            ph.dst_pitch = (size_t)d->out_w * C;
+            if (need_v) {
+                rc = rs_scratch(st, (size_t)frames * d->in_h * d->out_w * C, stream, capturing, last_hip);
+                if (rc != LANCZOS_OK) return rc;
+                ph.dst = (uint8_t*)st->scratch, ph.dst_fs = (size_t)d->in_h * d->out_w * C;
+            } else {
+                ph.dst = out, ph.dst_fs = out_fs;
+            }
+            e = rs_launch_pass(true, ph, d->in_h, frames, stream);
+        }
+        if (e == hipSuccess && need_v) {
+            pv.src = need_h ? ph.dst : in;
+            pv.src_fs = need_h ? ph.dst_fs : in_fs;
+            pv.src_pitch = (size_t)d->out_w * C;
+            pv.dst = out, pv.dst_fs = out_fs, pv.dst_pitch = (size_t)d->out_w * C;
+            pv.n_cols = d->out_w * C, pv.channels = C;
+            pv.first = V->first(), pv.count = V->count(), pv.coeffs = V->coeffs(), pv.ksize = V->host.ksize;
+            e = rs_launch_pass(false, pv, d->out_h, frames, stream);
+        }
+        *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
+    }
+    if (capturing) {   // a live graph may name these tables: they stay until the context goes
+        for (ResizeAxis* ax : {H, V})
+            if (ax) {
+                auto it = std::find(st->axes.begin(), st->axes.end(), ax);
+                if (it != st->axes.end()) {
+                    st->kept.push_back(ax->dev);
+                    ax->dev = nullptr;
+                    st->axes.erase(it);
+                    delete ax;
+                }
+            }
+    }
+    if (e != hipSuccess) {
+        *last_hip = (int)e;
+        return LANCZOS_ERR_HIP;
+    }
+    return LANCZOS_OK;
+}
+
+int resize_host(ResizeState* st, const lanczos_resize_desc* d, const void* in, void* out, int frames, hipStream_t stream,
+                int* last_kernel, int* last_hip) {
+    const size_t in_bytes = (size_t)d->in_w * d->in_h * d->channels * frames;
+    const size_t out_bytes = (size_t)d->out_w * d->out_h * d->channels * frames;
+    auto grow = [&](void** p, size_t* have, size_t need) -> hipError_t {
+        if (*have >= need) return hipSuccess;
+        if (*p) {
+            rs_retire(st->retired, *p, {stream});
+            *p = nullptr;
+            *have = 0;
+        }
+        const hipError_t e = hipMalloc(p, need);
+        if (e == hipSuccess) *have = need;
+        else *p = nullptr;
+        return e;
+    };
+    hipError_t e = grow(&st->stage_in, &st->stage_in_bytes, in_bytes);
+    if (e == hipSuccess) e = grow(&st->stage_out, &st->stage_out_bytes, out_bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(st->stage_in, in, in_bytes, hipMemcpyHostToDevice, stream);
+    int rc = LANCZOS_OK;
+    if (e == hipSuccess) {
+        rc = resize_device(st, d, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip);
+        if (rc == LANCZOS_OK) e = hipMemcpyAsync(out, st->stage_out, out_bytes, hipMemcpyDeviceToHost, stream);
+    }
+    const hipError_t es = hipStreamSynchronize(stream);   // nothing stays in flight on the caller's buffers
+    if (rc != LANCZOS_OK) return rc;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        *last_hip = (int)e;
+        return LANCZOS_ERR_HIP;
+    }
+    return LANCZOS_OK;
+}
+
+}  // namespace lz

@@ -1,0 +1,67 @@
+// lanczos_resize.hpp -- resize to any size with Pillow's Lanczos contract (include/lanczos_hip.h, lanczos_resize_*):
+// host tap tables, their per-context cache, and the entry points lanczos_api.hip forwards to.  The kernels live in
+// lanczos_resize.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "../../include/lanczos_hip.h"
+#include "lanczos_cache.hpp"
+
+namespace lz {
+
+constexpr int kResizePrecision = 22;   // Pillow's PRECISION_BITS for 8-bit samples (32 - 8 - 2)
+constexpr int kResizeMaxSize = 65535;
+
+int resize_validate(const lanczos_resize_desc* d);
+
+// Fixed-point tables of one axis, computed on the host in double exactly as Pillow's precompute_coeffs +
+// normalize_coeffs_8bpc do.  Returns false if a coefficient or an accumulator could leave the ranges the kernels rely on
+// (|coeff| < 2^23 for the 24-bit multiply, 255 * sum|coeff| + 2^21 < 2^31); no shape met so far does.
+struct ResizeAxisHost {
+    int in_n = 0, out_n = 0, a = 0, ksize = 0;
+    std::vector<int32_t> first, count, coeffs;   // [out_n], [out_n], [out_n][ksize]
+};
+int resize_ksize(int in_n, int out_n, int a);
+bool resize_build_axis(int in_n, int out_n, int a, ResizeAxisHost* t);
+
+// One axis shape on the device: first | count | coeffs in one block.
+struct ResizeAxis {
+    int key[3] = {0, 0, 0};   // in, out, a
+    ResizeAxisHost host;
+    int32_t* dev = nullptr;
+    const int32_t* first() const { return dev; }
+    const int32_t* count() const { return dev + host.out_n; }
+    const int32_t* coeffs() const { return dev + 2 * (size_t)host.out_n; }
+    std::vector<hipStream_t> streams;   // streams whose launches read this block (retirement)
+};
+
+// What a context keeps for its resizes.  Callers serialise per context (ctx->mu).
+struct ResizeState {
+    static constexpr size_t kMaxAxes = 32;   // bounded: the least recently used axis shape is retired at the 33rd
+    std::vector<ResizeAxis*> axes;           // least recently used first
+    RetireList retired;
+    hipStream_t upload = nullptr;            // private stream of the eager table uploads
+    int force = LANCZOS_RESIZE_AUTO;
+    // intermediate of the two-pass path (in_h x out_w x C per frame)
+    void* scratch = nullptr;
+    size_t scratch_bytes = 0;
+    bool scratch_captured = false;           // used by a captured launch: a live graph may still hold it
+    std::vector<hipStream_t> scratch_streams;
+    std::vector<void*> kept;                 // scratch blocks replaced while a graph may hold them: freed at destruction
+    // staging of lanczos_resize_host
+    void* stage_in = nullptr;
+    void* stage_out = nullptr;
+    size_t stage_in_bytes = 0, stage_out_bytes = 0;
+    ~ResizeState();
+};
+
+// The entry points (ctx->mu held, device set).  *last_kernel / *last_hip as in lanczos_ctx.
+int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_in, void* d_out, int frames,
+                  size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream, int* last_kernel, int* last_hip);
+int resize_host(ResizeState* st, const lanczos_resize_desc* d, const void* in, void* out, int frames, hipStream_t stream,
+                int* last_kernel, int* last_hip);
+
+}  // namespace lz

@@ -4,6 +4,9 @@
  *
  *   lanczos_upscale <in.(png|ppm|pgm)> <out.(png|ppm|pgm)> [--scale N[/D]] [--a A] [--channels C]
  *                   [--exact | --hls] [--device D] [--repeat K]
+ *   lanczos_upscale <in> <out> --size WxH [--a A] [--channels C] [--device D] [--repeat K]
+ *                   (resize to any size, downscaling included, through lanczos_resize_host: Pillow's Image.resize with
+ *                   LANCZOS, not the reference's model; refuses --scale, --exact, --hls and the multi-device flags)
  *                   [--devices 0-7 | 0,2,5] [--frames F] [--split frames|rows] [--root]   (several GPUs of one node, plain C:
  *                   the image is replicated into a batch of F frames and the batch -- or every frame's rows -- is split
  *                   over the devices by lanczos_resample_multi_host; the first result frame is written.  --root: the batch
@@ -30,12 +33,61 @@ static int ends_with(const char* s, const char* suf) {
     return n >= m && strcmp(s + n - m, suf) == 0;
 }
 
+static double ms_since(const struct timespec* t0) {
+    struct timespec t1;
+    clock_gettime(CLOCK_MONOTONIC, &t1);
+    return (t1.tv_sec - t0->tv_sec) * 1e3 + (t1.tv_nsec - t0->tv_nsec) / 1e6;
+}
+
+/* --size WxH: one frame through lanczos_resize_host */
+static int resize_main(const char* out_path, const uint8_t* img, int width, int height, int channels, int out_w, int out_h,
+                       int a, int device, int repeat) {
+    lanczos_resize_desc d;
+    int rc = lanczos_resize_desc_init(&d, width, height, out_w, out_h, channels, a);
+    if (rc != LANCZOS_OK) {
+        printf("Cannot resize %i x %i to %i x %i: %s.\n", width, height, out_w, out_h, lanczos_strerror(rc));
+        return EXIT_FAILURE;
+    }
+    printf("Resize %d x %d -> %d x %d, a = %d\n", width, height, out_w, out_h, a);
+    uint8_t* out = (uint8_t*)malloc((size_t)out_w * out_h * channels);
+    lanczos_ctx* ctx = NULL;
+    rc = lanczos_create(&ctx, device);
+    if (rc != LANCZOS_OK || !out) {
+        printf("Cannot use the GPU: %s\n", lanczos_strerror(rc));
+        return EXIT_FAILURE;
+    }
+    struct timespec t0;
+    clock_gettime(CLOCK_MONOTONIC, &t0);
+    for (int k = 0; k < repeat && rc == LANCZOS_OK; k++) rc = lanczos_resize_host(ctx, &d, img, out, 1);
+    if (rc != LANCZOS_OK) {
+        printf("lanczos_resize failed: %s (hip error %d)\n", lanczos_strerror(rc), lanczos_last_hip_error(ctx));
+        return EXIT_FAILURE;
+    }
+    const double ms = ms_since(&t0) / repeat;
+    printf("%dx%d->%dx%d_%d: %.3f ms per frame incl. PCIe copies (%.1f Mpix/s), kernel family %d\n", width, height, out_w,
+           out_h, a, ms, out_w * (double)out_h / ms / 1e3, lanczos_last_kernel(ctx));
+    const int ok = ends_with(out_path, ".png") ? lz_image_write_png(out_path, out_w, out_h, channels, out, out_w * channels)
+                                               : lz_image_write_pnm(out_path, out_w, out_h, channels, out, out_w * channels);
+    lanczos_destroy(ctx);
+    free(out);
+    if (!ok) {
+        printf("Could not write %s\n", out_path);
+        return EXIT_FAILURE;
+    }
+    return 0;
+}
+
 int main(int argc, char* argv[]) {
     const char *in_path = NULL, *out_path = NULL;
     int scale_n = 2, scale_d = 1, a = 3, want_channels = 3, exact = 0, hls = 0, device = 0, repeat = 1;
     int devices[64], n_devices = 0, frames = 1, split = LANCZOS_SPLIT_FRAMES, root = 0;
+    int size_w = 0, size_h = 0, have_size = 0, upscale_only = 0; /* upscale_only: a flag --size cannot go with */
     for (int i = 1; i < argc; i++) {
-        if (!strcmp(argv[i], "--scale") && i + 1 < argc) {
+        if (!strcmp(argv[i], "--size") && i + 1 < argc) {
+            have_size = 1;
+            if (sscanf(argv[++i], "%dx%d", &size_w, &size_h) != 2) size_w = size_h = 0;
+        } else if (!strcmp(argv[i], "--scale") && i + 1 < argc) {
+            upscale_only = 1;
             scale_d = 1;
             if (sscanf(argv[++i], "%d/%d", &scale_n, &scale_d) < 1) scale_n = 0;
         } else if (!strcmp(argv[i], "--a") && i + 1 < argc) {
@@ -48,15 +100,21 @@ int main(int argc, char* argv[]) {
             repeat = atoi(argv[++i]);
         } else if (!strcmp(argv[i], "--exact")) {
             exact = 1;
+            upscale_only = 1;
         } else if (!strcmp(argv[i], "--hls")) {
             hls = 1;
+            upscale_only = 1;
         } else if (!strcmp(argv[i], "--root")) {
             root = 1;
+            upscale_only = 1;
         } else if (!strcmp(argv[i], "--frames") && i + 1 < argc) {
+            upscale_only = 1;
             frames = atoi(argv[++i]);
         } else if (!strcmp(argv[i], "--split") && i + 1 < argc) {
+            upscale_only = 1;
             split = !strcmp(argv[++i], "rows") ? LANCZOS_SPLIT_ROWS : LANCZOS_SPLIT_FRAMES;
         } else if (!strcmp(argv[i], "--devices") && i + 1 < argc) { /* "0-7" or "0,2,5" */
+            upscale_only = 1;
             const char* p = argv[++i];
             int lo, hi;
             if (sscanf(p, "%d-%d", &lo, &hi) == 2) {
@@ -76,9 +134,16 @@ int main(int argc, char* argv[]) {
     }
     if (!in_path || !out_path) {
         fprintf(stderr, "usage: %s <in.png|ppm> <out.png|ppm> [--scale N[/D]] [--a A] [--channels C] [--exact|--hls] "
-                        "[--device D] [--repeat K] [--devices 0-7|0,2,5] [--frames F] [--split frames|rows] [--root]\n", argv[0]);
+                        "[--device D] [--repeat K] [--devices 0-7|0,2,5] [--frames F] [--split frames|rows] [--root]\n"
+                        "       %s <in.png|ppm> <out.png|ppm> --size WxH [--a A] [--channels C] [--device D] [--repeat K]\n",
+                argv[0], argv[0]);
         return EXIT_FAILURE;
     }
+    if (have_size && upscale_only) {
+        fprintf(stderr, "--size cannot be combined with --scale, --exact, --hls, --devices, --frames, --split or --root\n");
+        return EXIT_FAILURE;
+    }
+    if (repeat < 1) repeat = 1;
     printf("Running full TB (%s)\n", lanczos_version());  /* main.cpp:16 */
 
     int width = 0, height = 0, channels = 0;
@@ -86,6 +151,11 @@ int main(int argc, char* argv[]) {
     if (img == NULL) { /* full_TB.h:110-113 */
         printf("Image was not loaded successfully.\n");
         return EXIT_FAILURE;
+    }
+    if (have_size) {
+        const int rc = resize_main(out_path, img, width, height, want_channels, size_w, size_h, a, device, repeat);
+        lz_image_free(img);
+        return rc;
     }
     lanczos_desc d;
     int rc = lanczos_desc_init(&d, width, height, want_channels, 1, scale_n, scale_d, a);
