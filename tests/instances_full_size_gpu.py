@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """tests/instances_full_size_gpu.py -- every marching-kernel instance (lanczos_fast.hpp LZ_FAST_CONFIGS: 35 sample-type / channel /
 scale / a combinations) at a 4K-class output size, both parity modes, against the CPU oracle (test infrastructure, not collected
-by pytest: minutes of CPU time).  The pytest suite covers the same instances at 160 x 45; this run exercises them with full
+by pytest: minutes of CPU time).  LSB1 outputs go through the per-sample contract of tests/lsb1_check.py.  The pytest suite covers the same instances at 160 x 45; this run exercises them with full
 workgroup tables (every table mode, hundreds of ticks per chunk, the register budgets of round 4).  Two frames per call, so
 that a launch holds more than one (strip, frame) pair per XCD.  Exit code 1 on any mismatch."""
 import os
@@ -16,6 +16,7 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 import lanczos_hls_amd as L  # noqa: E402
+import lsb1_check as LC  # noqa: E402
 import oracle_lib as O  # noqa: E402
 import patterns as P  # noqa: E402
 
@@ -47,10 +48,16 @@ def main():
             for i in range(2):
                 d = np.abs(got[i].astype(np.int32) - want[i].astype(np.int32))
                 ok = d.max() == 0 if mode == L.MODE_EXACT else d.max() <= 1
+                why = ""
+                if ok and mode == L.MODE_LSB1:
+                    try:
+                        LC.check(frames[i], s, 1, a, got[i], L.KERNEL_FAST, f"{dt.__name__} C{c} {s}x a={a} frame {i}", threads=16)
+                    except AssertionError as e:
+                        ok, why = False, str(e)
                 n += 1
                 if not ok:
                     bad += 1
-                    print(f"MISMATCH {dt.__name__} C{c} {s}x a={a} mode {mode} frame {i}: max |diff| {d.max()}, {np.count_nonzero(d if mode == L.MODE_EXACT else d > 1)} samples", flush=True)
+                    print(f"MISMATCH {dt.__name__} C{c} {s}x a={a} mode {mode} frame {i}: max |diff| {d.max()}, {np.count_nonzero(d if mode == L.MODE_EXACT else d > 1)} samples {why}", flush=True)
         print(f"{dt.__name__} C{c} {s}x a={a} {w}x{h}->{w * s}x{h * s}: ok ({time.time() - t0:.0f} s)", flush=True)
     print(f"instances at full size: {len(cases)} instances x 2 modes x 2 frames = {n} comparisons, {bad} failures")
     return 1 if bad else 0

@@ -1,0 +1,42 @@
+"""Child process of test_parity_gpu.py::test_production_switches_change_no_result (not collected by pytest): the library reads
+its environment switches once per process (csrc/lanczos_env.hpp), so every switch is tried in a fresh process.  Runs the
+requests of SWITCH_REQUESTS in both parity modes and writes the outputs to the .npz named on the command line."""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import lanczos_hls_amd as L  # noqa: E402
+import patterns as P  # noqa: E402
+
+# name -> (frames, sn, sd, a): a config 2 batch (k_march, prefix rows riding or in front), a periodic rational scale (k_ratp;
+# k_rat under LANCZOS_NO_RATP) and a deep in-place prefix (K = 99: k_prefix / k_prefix_stream behind k_rat)
+SWITCH_REQUESTS = {
+    "config2_batch": (lambda: np.stack([P.noise(1080, 1920, 3, seed=1), P.dark_noise(1080, 1920, 3, seed=2)]), 2, 1, 3),
+    "rational_3_2": (lambda: P.noise(270, 480, 3, seed=3)[None], 3, 2, 3),
+    "deep_prefix_33_32": (lambda: P.noise(160, 128, 3, seed=31)[None], 33, 32, 3),
+}
+
+
+def main(out_path):
+    ctx = L.Context(0)
+    res = {}
+    try:
+        for name, (gen, sn, sd, a) in SWITCH_REQUESTS.items():
+            frames = gen()
+            for mode, tag in ((L.MODE_EXACT, "exact"), (L.MODE_LSB1, "lsb1")):
+                res[f"{name}:{tag}"] = ctx.resample(frames, sn, sd, a, mode)
+                res[f"{name}:{tag}:kernel"] = np.array(ctx.last_kernel())
+    finally:
+        ctx.close()
+    np.savez(out_path, **res)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1]))

@@ -27,6 +27,17 @@ class OracleCfg(ctypes.Structure):
     ]
 
 
+class ExplainStats(ctypes.Structure):
+    """oracle_explain_stats (oracle/lanczos_oracle.h)"""
+    _fields_ = [
+        ("samples", ctypes.c_uint64), ("equal", ctypes.c_uint64), ("plus1", ctypes.c_uint64),
+        ("unexplained", ctypes.c_uint64), ("window", ctypes.c_uint64), ("int_flips", ctypes.c_uint64),
+        ("int_row_samples", ctypes.c_uint64), ("max_plus1_gap", ctypes.c_double), ("inplace_rows", ctypes.c_int),
+        ("first_o", ctypes.c_int), ("first_x", ctypes.c_int), ("first_c", ctypes.c_int), ("first_kind", ctypes.c_int),
+        ("first_got", ctypes.c_longlong), ("first_v", ctypes.c_double),
+    ]
+
+
 _lib = None
 
 
@@ -39,7 +50,7 @@ def build_oracle():
 def lib():
     global _lib
     if _lib is None:
-        srcs = [os.path.join(ORACLE_DIR, n) for n in ("lanczos_oracle.c", "lanczos_hls_model.c", "lanczos_hls_model.h")]
+        srcs = [os.path.join(ORACLE_DIR, n) for n in ("lanczos_oracle.c", "lanczos_oracle.h", "lanczos_hls_model.c", "lanczos_hls_model.h")]
         if (not os.path.exists(ORACLE_SO)) or any(os.path.getmtime(s) > os.path.getmtime(ORACLE_SO) for s in srcs):
             build_oracle()
         L = ctypes.CDLL(ORACLE_SO)
@@ -70,6 +81,15 @@ def lib():
         L.oracle_hls_weight.argtypes = [ctypes.c_int] * 5
         L.oracle_lcg_fill_u16.restype = None
         L.oracle_lcg_fill_u16.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32]
+        for name in ("oracle_hpass_hwc_u8", "oracle_hpass_hwc_u16"):
+            f = getattr(L, name)
+            f.restype = ctypes.c_int
+            f.argtypes = [P, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        for name in ("oracle_explain_hwc_u8", "oracle_explain_hwc_u16"):
+            f = getattr(L, name)
+            f.restype = ctypes.c_int
+            f.argtypes = [P, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_int,
+                          ctypes.POINTER(ExplainStats), ctypes.c_void_p, ctypes.c_int]
         _lib = L
     return _lib
 
@@ -122,6 +142,33 @@ def expected_hwc_u16(c, img, threads=1):
     rc = lib().oracle_expected_hwc_u16(ctypes.byref(c), img.ctypes.data, out.ctypes.data, threads)
     assert rc == 0, rc
     return out
+
+
+def hpass_hwc(c, img, threads=1):
+    """The reference's truncated H intermediate T: [IN_H][OUT_W][C] (full_TB.h:83-87)."""
+    img = np.ascontiguousarray(img)
+    assert img.shape == (c.in_h, c.in_w, c.channels) and img.dtype in (np.uint8, np.uint16)
+    T = np.empty((c.in_h, c.out_w, c.channels), dtype=img.dtype)
+    fn = lib().oracle_hpass_hwc_u8 if img.dtype == np.uint8 else lib().oracle_hpass_hwc_u16
+    rc = fn(ctypes.byref(c), img.ctypes.data, T.ctypes.data, threads)
+    assert rc == 0, rc
+    return T
+
+
+def explain_hwc(c, img, got, delta, copies_int_rows, threads=1, want_ref=False):
+    """oracle_explain_hwc_*: per-sample classification of `got` against the reference's f64 vertical sums.
+    Returns (ExplainStats, reference output or None)."""
+    img = np.ascontiguousarray(img)
+    got = np.ascontiguousarray(got)
+    assert img.shape == (c.in_h, c.in_w, c.channels) and img.dtype in (np.uint8, np.uint16)
+    assert got.shape == (c.out_h, c.out_w, c.channels) and got.dtype == img.dtype, (got.shape, got.dtype)
+    ref = np.empty_like(got) if want_ref else None
+    st = ExplainStats()
+    fn = lib().oracle_explain_hwc_u8 if img.dtype == np.uint8 else lib().oracle_explain_hwc_u16
+    rc = fn(ctypes.byref(c), img.ctypes.data, got.ctypes.data, float(delta), int(bool(copies_int_rows)), ctypes.byref(st),
+            ref.ctypes.data if want_ref else None, threads)
+    assert rc == 0, rc
+    return st, ref
 
 
 def hls_expected_hwc(c, img, threads=1, bit_precision=0):

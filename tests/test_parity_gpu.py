@@ -2,7 +2,9 @@
 
   * golden fixtures (reference outputs) and known-answer digests: bit-exact in EXACT mode
   * oracle on seeded synthetic frames (noise / dark / gradient / blocks): EXACT mode bit-exact;
-    default LSB1 mode within +-1 LSB per sample (the tolerance BASELINE.json's north_star states)
+    default LSB1 mode within +-1 LSB per sample (the tolerance BASELINE.json's north_star states) AND per sample within the
+    mode's stated contract (tests/lsb1_check.py: +1 only where the reference's f64 sum lies within delta below a store
+    boundary, integer-phase rows copies of the H intermediate, prefix rows and k_generic bit-exact)
   * edge cases the reference's loop bounds imply: tiny images (every tap range clipped), a = 2/3/4,
     1/3/4 channels, non-integer scales, the in-place prefix rows, strips, batches, u16
 """
@@ -13,6 +15,7 @@ import numpy as np
 import pytest
 
 import lanczos_hls_amd as L
+import lsb1_check as LC
 import oracle_lib as O
 import patterns as P
 
@@ -43,14 +46,24 @@ def _oracle(img, sn, sd, a, threads=8):
     return O.expected_hwc_u8(cfg, img, threads)
 
 
-def _cmp(got, want, mode, what):
+def _cmp(got, want, mode, what, req=None):
+    """EXACT: bit-identical.  LSB1: within 1 LSB, and `req` = (img, sn, sd, a, kernel family) must be given: the sample-by-sample
+    contract of tests/lsb1_check.py is checked on top."""
     assert got.shape == want.shape and got.dtype == want.dtype, what
     diff = np.abs(got.astype(np.int64) - want.astype(np.int64))
     if mode == L.MODE_EXACT:
         assert diff.max() == 0, f"{what}: {np.count_nonzero(diff)} samples differ, max {diff.max()}"
     else:
         assert diff.max() <= 1, f"{what}: max |diff| {diff.max()} > 1 LSB"
+        assert req is not None, f"{what}: an LSB1 comparison needs the request for the per-sample check"
+        img, sn, sd, a, family = req
+        LC.check(img, sn, sd, a, got, family, what)
     return int(np.count_nonzero(diff))
+
+
+def _req(ctx, img, sn, sd, a):
+    """The request of the last call on ctx, with the kernel family that served it."""
+    return (img, sn, sd, a, ctx.last_kernel())
 
 
 @pytest.mark.parametrize("family", [L.KERNEL_GENERIC, L.KERNEL_NONE])
@@ -67,7 +80,11 @@ def test_golden_fixtures(ctx, family, mode):
             img = np.ascontiguousarray(z[k + ":in"].transpose(1, 2, 0))      # planar -> stb layout
             want = np.ascontiguousarray(z[k + ":out"].transpose(1, 2, 0))
             got = ctx.resample(img, sn, sd, a, mode)
-            _cmp(got, want, mode, k)
+            fam = ctx.last_kernel()
+            if family == L.KERNEL_GENERIC:
+                assert fam == L.KERNEL_GENERIC, k
+                _cmp(got, want, L.MODE_EXACT, k + " (k_generic: bit-exact in every mode)")
+            _cmp(got, want, mode, k, (img, sn, sd, a, fam))
     finally:
         ctx.force_kernel(L.KERNEL_NONE)
 
@@ -116,7 +133,7 @@ def test_oracle_parity_medium(ctx, pattern, mode):
         img = P.ALL_U8[pattern](h, w, c)
         want = _oracle(img, sn, sd, a)
         got = ctx.resample(img, sn, sd, a, mode)
-        _cmp(got, want, mode, f"{pattern} {w}x{h}x{c} {sn}/{sd} a={a}")
+        _cmp(got, want, mode, f"{pattern} {w}x{h}x{c} {sn}/{sd} a={a}", _req(ctx, img, sn, sd, a))
         want_family = L.KERNEL_FAST if _fast_expected(w, c, sn, sd) else L.KERNEL_GENERIC
         assert ctx.last_kernel() == want_family, (w, h, c, sn, sd, a, ctx.last_kernel())
 
@@ -138,7 +155,7 @@ def test_every_integer_scale_instance(ctx, mode):
                       (P.noise(h, w, c, seed=seed, dtype=np.uint16) >> (8 if pat == "dark" else 0)).astype(np.uint16)
                 want = _oracle(img, s, 1, a)
                 got = ctx.resample(img, s, 1, a, mode)
-                _cmp(got, want, mode, f"{dt.__name__} c={c} {s}x a={a} {w}x{h} {pat}")
+                _cmp(got, want, mode, f"{dt.__name__} c={c} {s}x a={a} {w}x{h} {pat}", _req(ctx, img, s, 1, a))
                 assert ctx.last_kernel() == L.KERNEL_FAST, (dt.__name__, c, s, a, w)
 
 
@@ -165,7 +182,7 @@ def test_sixteen_bit_exact_mode_split_weight_chains(ctx):
                 want = _oracle(img, 2, 1, a)
                 for mode in (L.MODE_EXACT, L.MODE_LSB1):
                     got = ctx.resample(img, 2, 1, a, mode)
-                    _cmp(got, want, mode, f"uint16 c={c} a={a} {name}")
+                    _cmp(got, want, mode, f"uint16 c={c} a={a} {name}", _req(ctx, img, 2, 1, a))
                     assert ctx.last_kernel() == L.KERNEL_FAST
 
 
@@ -185,11 +202,11 @@ def test_rational_scales_fast_kernel(ctx, pattern, mode):
         img = P.ALL_U8[pattern](h, w, c)
         want = _oracle(img, sn, sd, a)
         got = ctx.resample(img, sn, sd, a, mode)
-        _cmp(got, want, mode, f"{pattern} {w}x{h}x{c} {sn}/{sd} a={a}")
+        _cmp(got, want, mode, f"{pattern} {w}x{h}x{c} {sn}/{sd} a={a}", _req(ctx, img, sn, sd, a))
         assert ctx.last_kernel() == L.KERNEL_FAST, (w, h, c, sn, sd, a)
     img16 = P.noise(60, 96, 4, seed=77, dtype=np.uint16)
     got = ctx.resample(img16, 3, 2, 3, mode)
-    _cmp(got, _oracle(img16, 3, 2, 3), mode, "u16 3/2")
+    _cmp(got, _oracle(img16, 3, 2, 3), mode, "u16 3/2", _req(ctx, img16, 3, 2, 3))
     assert ctx.last_kernel() == L.KERNEL_FAST
 
 
@@ -227,6 +244,8 @@ def test_rational_fast_kernel_known_answer_and_speed(ctx):
         assert ctx.last_kernel() == L.KERNEL_FAST
         diff = (outs[L.KERNEL_GENERIC].to(torch.int16) - outs[L.KERNEL_NONE].to(torch.int16)).abs()
         assert int(diff.max()) <= 1                                   # LSB1 against the always-exact kernel
+        _cmp(outs[L.KERNEL_NONE][0].cpu().numpy(), outs[L.KERNEL_GENERIC][0].cpu().numpy(), L.MODE_LSB1, f"rational {sn}/{sd} frame 0",
+             (x[0].cpu().numpy(), sn, sd, 3, L.KERNEL_FAST))
         print(f"rational {sn}/{sd}: generic {times[L.KERNEL_GENERIC] * 1e6:.1f} us, fast {times[L.KERNEL_NONE] * 1e6:.1f} us per 4 frames")
         assert times[L.KERNEL_GENERIC] / times[L.KERNEL_NONE] >= (4.0 if (sn, sd) == (4, 3) else 4.6), (sn, sd, times)
 
@@ -241,7 +260,8 @@ def test_scales_close_to_one_deep_inplace_prefix(ctx):
         assert K == (a - 1) * sn // (sn - sd) + 1
         want = _oracle(img, sn, sd, a)
         for mode in (L.MODE_EXACT, L.MODE_LSB1):
-            _cmp(ctx.resample(img, sn, sd, a, mode), want, mode, f"deep prefix {sn}/{sd} K={K}")
+            got = ctx.resample(img, sn, sd, a, mode)
+            _cmp(got, want, mode, f"deep prefix {sn}/{sd} K={K}", _req(ctx, img, sn, sd, a))
     # S = 1: every sample on an integer phase, the in-place pass one recurrence over the whole height per column
     # (full_TB.h:67-77) -- the output is the input except where the double noise of the ~1e-17 taps flips a dark sample
     for (w, h, c, a, gen) in [(64, 48, 3, 3, P.dark_noise), (40, 200, 1, 3, P.dark_noise), (33, 21, 4, 4, P.noise), (96, 64, 3, 2, P.noise)]:
@@ -249,7 +269,8 @@ def test_scales_close_to_one_deep_inplace_prefix(ctx):
         want = _oracle(img, 4, 4, a)                # reduced to 1/1 by the gcd, like lanczos.h:110
         assert want.shape == img.shape
         for mode in (L.MODE_EXACT, L.MODE_LSB1):
-            _cmp(ctx.resample(img, 4, 4, a, mode), want, mode, f"S=1 {w}x{h}x{c} a={a}")
+            got = ctx.resample(img, 4, 4, a, mode)
+            _cmp(got, want, mode, f"S=1 {w}x{h}x{c} a={a}", _req(ctx, img, 4, 4, a))
     assert (_oracle(P.dark_noise(48, 64, 3, seed=5), 1, 1, 3) != P.dark_noise(48, 64, 3, seed=5)).any()   # (the quirk is exercised)
     # Deeper than the row arrays of k_prefix: the streaming form of the recurrence (k_prefix_stream, rings of 24 rows).  S = 1 at 4K
     # height and 1025/1024 (K = 2 * 1025 + 1 > the frame height: every output row reads written rows) -- both shapes have
@@ -262,7 +283,8 @@ def test_scales_close_to_one_deep_inplace_prefix(ctx):
         want = _oracle(img, sn, sd, a)
         assert want.shape == (d.out_h, d.out_w, c)
         for mode in (L.MODE_EXACT, L.MODE_LSB1):
-            _cmp(ctx.resample(img, sn, sd, a, mode), want, mode, f"streamed prefix {sn}/{sd} {w}x{h}x{c} a={a} K={L.inplace_rows(d)}")
+            got = ctx.resample(img, sn, sd, a, mode)
+            _cmp(got, want, mode, f"streamed prefix {sn}/{sd} {w}x{h}x{c} a={a} K={L.inplace_rows(d)}", _req(ctx, img, sn, sd, a))
     with pytest.raises(L.LanczosError) as e:       # S < 1: refused (the reference itself is out of bounds there)
         ctx.resample(P.noise(16, 16, 3), 3, 4, 3)
     assert e.value.code == L.ERR_UNSUPPORTED
@@ -277,7 +299,7 @@ def test_tiny_images_all_taps_clipped(ctx):
         want = _oracle(img, sn, sd, a, threads=1)
         for mode in (L.MODE_EXACT, L.MODE_LSB1):
             got = ctx.resample(img, sn, sd, a, mode)
-            _cmp(got, want, mode, f"tiny {w}x{h}x{c} {sn}/{sd} a={a}")
+            _cmp(got, want, mode, f"tiny {w}x{h}x{c} {sn}/{sd} a={a}", _req(ctx, img, sn, sd, a))
 
 
 def test_extreme_values_saturate_like_the_reference(ctx):
@@ -398,7 +420,7 @@ def test_u16_matches_the_templated_checker(ctx):
         got = ctx.resample(img, sn, sd, a, L.MODE_EXACT)
         _cmp(got, want, L.MODE_EXACT, f"u16 {w}x{h}x{c}")
         got = ctx.resample(img, sn, sd, a, L.MODE_LSB1)
-        _cmp(got, want, L.MODE_LSB1, f"u16 {w}x{h}x{c}")
+        _cmp(got, want, L.MODE_LSB1, f"u16 {w}x{h}x{c}", _req(ctx, img, sn, sd, a))
 
 
 def test_reference_call_shape_and_errors(ctx):
@@ -440,11 +462,11 @@ def test_full_size_config2_against_oracle(ctx, pattern):
     want = _oracle(img, 2, 1, 3, threads=32)
     for mode in (L.MODE_LSB1, L.MODE_EXACT):
         got = ctx.resample(img, 2, 1, 3, mode)
-        _cmp(got, want, mode, f"full-size {pattern}")
+        _cmp(got, want, mode, f"full-size {pattern}", _req(ctx, img, 2, 1, 3))
     # the same frames inside a batch of 3 on the device-pointer path the benchmark uses
     batch = np.stack([img, P.noise(1080, 1920, 3, seed=3), img[::-1].copy()])
     got = ctx.resample(batch, 2, 1, 3, L.MODE_LSB1)
-    _cmp(got[0], want, L.MODE_LSB1, f"full-size {pattern} in a batch")
+    _cmp(got[0], want, L.MODE_LSB1, f"full-size {pattern} in a batch", _req(ctx, img, 2, 1, 3))
 
 
 @pytest.mark.parametrize("shape", [(1920, 1080, 3, 2, 1, 3, 16), (1920, 1080, 3, 2, 1, 3, 32), (1920, 1080, 3, 2, 1, 3, 24),
@@ -467,7 +489,7 @@ def test_benchmark_batches_every_frame(ctx, shape):
     for i in range(1, frames):
         assert np.array_equal(exact[i], exact[0]), f"EXACT: frame {i} of {frames} differs from frame 0"
     fast = ctx.resample(batch, sn, sd, a, L.MODE_LSB1)
-    assert np.abs(fast[0].astype(np.int16) - exact[0].astype(np.int16)).max() <= 1
+    _cmp(fast[0], exact[0], L.MODE_LSB1, f"batch of {frames}, frame 0", _req(ctx, img, sn, sd, a))
     for i in range(1, frames):
         assert np.array_equal(fast[i], fast[0]), f"LSB1: frame {i} of {frames} differs from frame 0"
 
@@ -515,7 +537,7 @@ def test_full_size_config5_batch_every_frame(ctx):
     for i in range(1, 4):
         assert np.array_equal(got[i], got[0]), f"EXACT: frame {i} differs from frame 0"
     fast = ctx.resample(batch, sn, sd, a, L.MODE_LSB1)
-    assert np.abs(fast[0].astype(np.int32) - got[0].astype(np.int32)).max() <= 1
+    _cmp(fast[0], got[0], L.MODE_LSB1, "config 5 batch, frame 0", _req(ctx, frame, sn, sd, a))
     for i in range(1, 4):
         assert np.array_equal(fast[i], fast[0]), f"LSB1: frame {i} differs from frame 0"
 
@@ -531,7 +553,7 @@ def test_full_size_config5_against_oracle(ctx):
     want = _oracle(img, sn, sd, a, threads=min(os.cpu_count() or 8, 64))
     for mode in (L.MODE_EXACT, L.MODE_LSB1):
         got = ctx.resample(img, sn, sd, a, mode)
-        _cmp(got, want, mode, "full-size config 5")
+        _cmp(got, want, mode, "full-size config 5", _req(ctx, img, sn, sd, a))
         assert ctx.last_kernel() == L.KERNEL_FAST
 
 
@@ -559,6 +581,9 @@ def test_full_size_config5_as_8_row_strips(ctx):
             y_strips[540 * i:540 * (i + 1)] = yout
         torch.cuda.synchronize()
         assert torch.equal(y_strips, y_whole), f"mode {mode}: strips differ from the whole frame"
+        if mode == L.MODE_LSB1:   # (EXACT: the digest test pins the whole-frame bytes)
+            whole = y_whole.cpu().numpy().view(np.uint16)
+            LC.check(img, sn, sd, a, whole, L.KERNEL_FAST, "config 5 as 8 row strips, LSB1", threads=16)
 
 
 def test_full_size_config3_against_oracle(ctx):
@@ -566,7 +591,8 @@ def test_full_size_config3_against_oracle(ctx):
     img = P.gradient_noise(720, 1280, 3)
     want = _oracle(img, 3, 1, 3, threads=32)
     for mode in (L.MODE_LSB1, L.MODE_EXACT):
-        _cmp(ctx.resample(img, 3, 1, 3, mode), want, mode, "full-size config 3")
+        got = ctx.resample(img, 3, 1, 3, mode)
+        _cmp(got, want, mode, "full-size config 3", _req(ctx, img, 3, 1, 3))
 
 
 def test_device_path_is_ordered_behind_the_default_stream(ctx):
@@ -587,7 +613,8 @@ def test_device_path_is_ordered_behind_the_default_stream(ctx):
         torch.cuda.synchronize()
         for f in (0, 7):
             want = O.expected_hwc_u8(cfg, x[f].cpu().numpy(), 8)
-            _cmp(y[f].cpu().numpy(), want, L.MODE_LSB1, f"default-stream ordering rep {rep} frame {f}")
+            _cmp(y[f].cpu().numpy(), want, L.MODE_LSB1, f"default-stream ordering rep {rep} frame {f}",
+                 _req(ctx, x[f].cpu().numpy(), 2, 1, 3))
 
 
 def test_host_path_pipeline_with_pinned_buffers(ctx):
@@ -694,7 +721,7 @@ def test_frame_strides_and_kernel_families(ctx, pad_in, pad_out):
         got = d_out.cpu().numpy()
         for f in range(frames):
             g = got[f * out_stride:f * out_stride + out_fb].reshape(d.out_h, d.out_w, c)
-            _cmp(g, want[f], mode, f"frame {f} pads {pad_in}/{pad_out}")
+            _cmp(g, want[f], mode, f"frame {f} pads {pad_in}/{pad_out}", _req(ctx, imgs[f], sn, 1, a))
             assert np.all(got[f * out_stride + out_fb:(f + 1) * out_stride] == 0x5A), "padding between frames was written"
 
 
@@ -719,8 +746,8 @@ def test_prefix_rows_ride_or_run_separately(ctx):
             torch.cuda.synchronize()
             got = y.cpu().numpy()
             for f in (0, frames // 2, frames - 1):
-                _cmp(got[f], want, mode, f"{frames} frames, frame {f}")
-                assert np.array_equal(got[f][:k], want[:k]) or mode == L.MODE_LSB1
+                _cmp(got[f], want, mode, f"{frames} frames, frame {f}", _req(ctx, img, sn, 1, a))
+                assert np.array_equal(got[f][:k], want[:k])      # the prefix kernels are f64 in every mode
 
 
 def test_first_use_of_a_shape_inside_stream_capture():
@@ -750,16 +777,93 @@ def test_first_use_of_a_shape_inside_stream_capture():
             assert int(y.max()) == 0                          # captured, not run
             g.replay()
             torch.cuda.synchronize()
-            _cmp(y.cpu().numpy(), want, mode, f"graph replay, mode {mode}")
+            _cmp(y.cpu().numpy(), want, mode, f"graph replay, mode {mode}", (img, 2, 1, d.a, c.last_kernel()))
             x.copy_(torch.from_numpy(img2))                   # the graph holds pointers, not data
             g.replay()
             torch.cuda.synchronize()
-            _cmp(y.cpu().numpy(), _oracle(img2, 2, 1, d.a), mode, f"second replay, mode {mode}")
+            _cmp(y.cpu().numpy(), _oracle(img2, 2, 1, d.a), mode, f"second replay, mode {mode}", (img2, 2, 1, d.a, c.last_kernel()))
             # and the plan / table the capture created serve an ordinary call afterwards
             y.zero_()
             c.resample_device(d, x.data_ptr(), y.data_ptr(), 1, stream=torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
-            _cmp(y.cpu().numpy(), _oracle(img2, 2, 1, d.a), mode, f"plain call after capture, mode {mode}")
+            _cmp(y.cpu().numpy(), _oracle(img2, 2, 1, d.a), mode, f"plain call after capture, mode {mode}", _req(c, img2, 2, 1, d.a))
             del g
     finally:
         c.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The LSB1 contract at full size (tests/lsb1_check.py), with coverage asserted: the window population (samples whose reference
+# sum lies within delta of a store boundary: where the biased floor decides) and the integer-phase flips of the H pass (where
+# the fix-up lists decide) must be clearly non-zero, so that the check was exercised and not passed over.
+
+
+def _c5_gradient():
+    w, h, c = C5[:3]
+    y, x = np.mgrid[0:h, 0:w]
+    base = ((x * 65535 // w + y * 65535 // h) // 2).astype(np.int64)
+    nz = (O.lcg_u16(h * w * c, 99).reshape(h, w, c) >> 6).astype(np.int64)
+    return np.clip(base[..., None] + nz, 0, 65535).astype(np.uint16)
+
+
+FULL_LSB1 = {
+    "config2": ((1920, 1080, 3, 2, 3), {"noise": lambda: P.noise(1080, 1920, 3, seed=1), "dark": lambda: P.dark_noise(1080, 1920, 3),
+                                        "gradient": lambda: P.gradient_noise(1080, 1920, 3)}),
+    "config3": ((1280, 720, 3, 3, 3), {"noise": lambda: P.noise(720, 1280, 3, seed=1), "dark": lambda: P.dark_noise(720, 1280, 3),
+                                       "gradient": lambda: P.gradient_noise(720, 1280, 3)}),
+    "config5": ((3840, 2160, 4, 2, 4), {"noise": _c5_frame, "gradient": _c5_gradient}),
+}
+
+
+@pytest.mark.parametrize("config,pattern", [(k, p) for k, (_, gens) in FULL_LSB1.items() for p in gens])
+def test_full_size_lsb1_contract(ctx, config, pattern):
+    (w, h, c, s, a), gens = FULL_LSB1[config]
+    img = gens[pattern]()
+    got = ctx.resample(img, s, 1, a, L.MODE_LSB1)
+    assert ctx.last_kernel() == L.KERNEL_FAST
+    r = LC.check(img, s, 1, a, got, L.KERNEL_FAST, f"{config} {pattern} LSB1")
+    print(f"{config} {pattern}: +1 fraction {r['plus1_fraction']:.3e} ({r['plus1']} of {r['samples']}), window {r['window']}, "
+          f"integer-phase flips {r['int_flips']}, integer-row samples {r['int_row_samples']}, largest +1 gap "
+          f"{r['max_plus1_gap']:.3g} (delta {r['delta']:g})")
+    assert r["window"] >= 1000 and r["int_row_samples"] >= w * c * 100
+    if pattern != "gradient":
+        assert r["int_flips"] >= 100
+
+
+def _run_switch_child(tmp_path, name, env_extra):
+    import subprocess
+    import sys
+    out = str(tmp_path / f"{name}.npz")
+    env = dict(os.environ)
+    for k in ("LANCZOS_TILE_KERNEL", "LANCZOS_NO_RATP", "LANCZOS_SEPARATE_PREFIX", "LANCZOS_MARCH_SEGS", "LANCZOS_MARCH_WGS",
+              "LANCZOS_RANK_WEIGHTS"):
+        env.pop(k, None)
+    env.update(env_extra)
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(__file__), "lsb1_env_child.py"), out], env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, f"{name}: exit {r.returncode}\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}"
+    return np.load(out)
+
+
+def test_production_switches_change_no_result(tmp_path):
+    """none of the production switches changes a result.  Each in a fresh child process (the environment is
+    read once per process), one at a time: EXACT identical to the reference, LSB1 within its contract, and the switches that
+    only re-partition the work give LSB1 bytes identical to the default run."""
+    import lsb1_env_child as E
+    reqs = {name: (gen(), sn, sd, a) for name, (gen, sn, sd, a) in E.SWITCH_REQUESTS.items()}
+    want = {name: [_oracle(f, sn, sd, a, threads=16) for f in frames] for name, (frames, sn, sd, a) in reqs.items()}
+    base = _run_switch_child(tmp_path, "default", {})
+    partition_only = {"LANCZOS_SEPARATE_PREFIX", "LANCZOS_MARCH_SEGS", "LANCZOS_MARCH_WGS", "LANCZOS_RANK_WEIGHTS"}
+    for var, val in [("LANCZOS_TILE_KERNEL", "1"), ("LANCZOS_NO_RATP", "1"), ("LANCZOS_SEPARATE_PREFIX", "1"),
+                     ("LANCZOS_MARCH_SEGS", "0"), ("LANCZOS_MARCH_SEGS", "1"), ("LANCZOS_MARCH_WGS", "7"),
+                     ("LANCZOS_RANK_WEIGHTS", "0"), (None, None)]:
+        res = base if var is None else _run_switch_child(tmp_path, f"{var}_{val}", {var: val})
+        tag = "default" if var is None else f"{var}={val}"
+        for name, (frames, sn, sd, a) in reqs.items():
+            exact, lsb1 = res[f"{name}:exact"], res[f"{name}:lsb1"]
+            fam = int(res[f"{name}:lsb1:kernel"])
+            for i in range(len(frames)):
+                _cmp(exact[i], want[name][i], L.MODE_EXACT, f"{tag} {name} frame {i}")
+                _cmp(lsb1[i], want[name][i], L.MODE_LSB1, f"{tag} {name} frame {i}", (frames[i], sn, sd, a, fam))
+            if var in partition_only:
+                assert np.array_equal(lsb1, base[f"{name}:lsb1"]), f"{tag}: {name} LSB1 bytes differ from the default run"
