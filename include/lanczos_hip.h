@@ -228,6 +228,17 @@ int lanczos_resize_validate(const lanczos_resize_desc* d);   /* LANCZOS_ERR_BAD_
  * NULL only *ksize is returned; otherwise all three must hold out (and out * ksize) elements. */
 int lanczos_resize_taps_host(const lanczos_resize_desc* d, int axis, int32_t* first, int32_t* count, int32_t* coeffs,
                              int* ksize);
+/* Diagnostic: what lanczos_resize_device would launch for this request and `frames` frames under LANCZOS_RESIZE_AUTO (the
+ * launch itself plans with the same function).  fused = 0: the two-pass path (one axis keeps its size, more horizontal
+ * taps than the widest fused instance has, the LDS row ring does not fit 80 KiB, or a frame of 2^31 bytes or more); the
+ * other fields are then 0.  fused = 1: the fused kernel instance with K horizontal taps on a grid of strips x chunks
+ * workgroups per frame; a workgroup marches down rows_per_chunk output rows in blocks of 8 with an LDS ring of ring_rows
+ * rows and a staging area of stage_rows input rows of stage_dw dwords; lds_bytes is their sum. */
+typedef struct lanczos_resize_plan {
+    int32_t fused;
+    int32_t K, strips, rows_per_chunk, chunks, ring_rows, stage_rows, stage_dw, lds_bytes;
+} lanczos_resize_plan;
+int lanczos_resize_plan_host(const lanczos_resize_desc* d, int frames, lanczos_resize_plan* out);
 /* Device buffers, asynchronous on `stream` (NULL = the default stream), frames at d_in + f * in_frame_stride and
  * d_out + f * out_frame_stride (bytes; 0 = tightly packed), as lanczos_resample_device.  The first call of an axis shape
  * builds its tables and uploads them before it returns (a blocking copy on a private stream, so that the cached tables are

@@ -41,7 +41,7 @@ ABI_SYMBOLS = [
     "lanczos_multi_last_error", "lanczos_multi_exchange_plan", "lanczos_multi_exchange_selftest", "lanczos_device_alloc", "lanczos_device_free",
     "lanczos_device_copy",
     "lanczos_resize_desc_init", "lanczos_resize_validate", "lanczos_resize_taps_host", "lanczos_resize_device",
-    "lanczos_resize_host", "lanczos_resize_force",
+    "lanczos_resize_host", "lanczos_resize_force", "lanczos_resize_plan_host",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
 
@@ -74,6 +74,12 @@ class ResizeDesc(ctypes.Structure):
         ("channels", ctypes.c_int32), ("a", ctypes.c_int32),
         ("reserved", ctypes.c_int32 * 2),
     ]
+
+
+class ResizePlan(ctypes.Structure):
+    """lanczos_resize_plan -- what lanczos_resize_device would launch (lanczos_resize_plan_host, diagnostic)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("fused", "K", "strips", "rows_per_chunk", "chunks", "ring_rows", "stage_rows",
+                                              "stage_dw", "lds_bytes")]
 
 
 _LIB = None
@@ -148,6 +154,7 @@ def _lib():
         L.lanczos_resize_device.argtypes = [c_void_p, PRD, c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p]
         L.lanczos_resize_host.argtypes = [c_void_p, PRD, c_void_p, c_void_p, c_int]
         L.lanczos_resize_force.argtypes = [c_void_p, c_int]
+        L.lanczos_resize_plan_host.argtypes = [PRD, c_int, ctypes.POINTER(ResizePlan)]
         L.lanczos_strerror.restype = ctypes.c_char_p
         L.lanczos_version.argtypes = []
         L.lanczos_version.restype = ctypes.c_char_p
@@ -223,6 +230,13 @@ def resize_taps_host(desc, axis):
     _check(_lib().lanczos_resize_taps_host(ctypes.byref(desc), axis, first.ctypes.data, count.ctypes.data,
                                            coeffs.ctypes.data, ctypes.byref(ks)), "lanczos_resize_taps_host")
     return first, count, coeffs
+
+
+def resize_plan_host(desc, frames=1):
+    """The launch plan of a resize under RESIZE_AUTO (no GPU needed): a ResizePlan, fused = 0 for the two-pass path."""
+    p = ResizePlan()
+    _check(_lib().lanczos_resize_plan_host(ctypes.byref(desc), frames, ctypes.byref(p)), "lanczos_resize_plan_host")
+    return p
 
 
 class PinnedArray:

@@ -44,7 +44,9 @@ struct Plan {
     void* dev_block = nullptr;  // one allocation behind `dev`
     void* host_block = nullptr; // page-locked source of the asynchronous upload (alive as long as the plan: a captured graph replays the copy)
     hipEvent_t uploaded = nullptr;       // recorded behind the upload ...
-    hipStream_t upload_stream = nullptr; // ... on this stream (the stream of the plan's first call)
+    hipStream_t upload_stream = nullptr; // ... on this stream (the stream of the plan's first call); neither where that stream
+                                         // was being captured: the upload was eager and is complete
+    bool captured = false;               // a captured call has used the tables: a live graph may name them
     lz::FastConsts fast{};      // phase weights etc. for the specialised kernels
     bool fast_ok = false;
     lz::RatHost rat;            // rational scales: per-index f32 weights, integer-phase flags (k_rat)
@@ -62,6 +64,7 @@ struct lanczos_ctx {
     std::map<PlanKey, Plan*> plans;
     lz::LruOrder<PlanKey> plan_order;  // the cache is bounded (kMaxPlans): the least recently used plan is retired
     lz::RetireList retired_plans;
+    std::vector<void*> kept_dev, kept_host;   // blocks of evicted plans a live graph may still name: freed by lanczos_destroy
     std::mutex mu;
     int last_kernel = LANCZOS_KERNEL_NONE;
     int last_hip = 0;
@@ -117,8 +120,13 @@ void free_plan(Plan* p) {   // nothing in flight reads it any more
 }
 
 // The plan of a shape: tap tables built on the host, uploaded ONCE, asynchronously, on the stream of the first call that needs
-// them (page-locked source, no device-wide wait: the entry points stay asynchronous on the caller's stream and can be captured
-// into a graph in relaxed capture mode; calls on other streams wait for the upload by event).
+// them (page-locked source, no device-wide wait: the entry points stay asynchronous on the caller's stream; calls on other
+// streams wait for the upload by event).  A stream that is being captured into a graph (relaxed capture mode: the first call
+// allocates) would turn the copy and the event into graph nodes that run only when the graph is replayed, perhaps never, while
+// the plan is cached as valid: there the upload is eager instead -- a copy on the context's private upload stream and a wait
+// for it, no event -- so an eager call of the shape before any replay reads complete tables.  Nothing is recorded on, queried
+// from or waited for on a capturing stream.  Tables a captured call has used are not freed when the LRU evicts their plan
+// (the graph may be replayed later): they move to kept_* until lanczos_destroy.
 int get_plan(lanczos_ctx* ctx, const lanczos_desc* d, hipStream_t stream, Plan** out) {
     PlanKey key;
     memset(&key, 0, sizeof(key));
@@ -129,9 +137,15 @@ int get_plan(lanczos_ctx* ctx, const lanczos_desc* d, hipStream_t stream, Plan**
     if (it != ctx->plans.end()) {
         Plan* p = it->second;
         ctx->plan_order.touch(key);
-        if (stream != p->upload_stream && hipEventQuery(p->uploaded) != hipSuccess)
-            LZ_HIP(ctx, hipStreamWaitEvent(stream, p->uploaded, 0));  // another stream: behind the upload
-        lz::note_stream(p->streams, stream);
+        if (lz::stream_capturing(stream)) {
+            // (an upload still in flight on another stream is waited for here: the graph gets no node for it)
+            if (p->uploaded && hipEventQuery(p->uploaded) != hipSuccess) LZ_HIP(ctx, hipEventSynchronize(p->uploaded));
+            p->captured = true;
+        } else {
+            if (p->uploaded && stream != p->upload_stream && hipEventQuery(p->uploaded) != hipSuccess)
+                LZ_HIP(ctx, hipStreamWaitEvent(stream, p->uploaded, 0));  // another stream: behind the upload
+            lz::note_stream(p->streams, stream);
+        }
         *out = p;
         return LANCZOS_OK;
     }
@@ -143,7 +157,12 @@ int get_plan(lanczos_ctx* ctx, const lanczos_desc* d, hipStream_t stream, Plan**
         auto io = ctx->plans.find(old);
         if (io != ctx->plans.end()) {
             Plan* q = io->second;
-            ctx->retired_plans.retire({q->dev_block}, {q->host_block}, q->streams);
+            if (q->captured) {
+                ctx->kept_dev.push_back(q->dev_block);
+                ctx->kept_host.push_back(q->host_block);
+            } else {
+                ctx->retired_plans.retire({q->dev_block}, {q->host_block}, q->streams);
+            }
             if (q->uploaded) (void)hipEventDestroy(q->uploaded);
             delete q;
             ctx->plans.erase(io);
@@ -211,25 +230,32 @@ int get_plan(lanczos_ctx* ctx, const lanczos_desc* d, hipStream_t stream, Plan**
     memcpy(host.data() + off_vf, p->V.first.data(), (size_t)d->out_h * 4);
     memcpy(host.data() + off_hw, p->H.w.data(), (size_t)d->out_w * taps * 8);
     memcpy(host.data() + off_vw, p->V.w.data(), (size_t)d->out_h * taps * 8);
+    const bool capturing = lz::stream_capturing(stream);   // hipStreamIsCapturing: the upload below must not become a graph node
+    hipStream_t up = stream;
     e = hipMalloc(&p->dev_block, total);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->uploaded, hipEventDisableTiming);
+    if (e == hipSuccess && capturing) e = ctx->wg_tabs.eager_stream(&up);
+    if (e == hipSuccess && !capturing) e = hipEventCreateWithFlags(&p->uploaded, hipEventDisableTiming);
     if (e != hipSuccess) {
         ctx->last_hip = (int)e;
         free_plan(p);
         return LANCZOS_ERR_HIP;
     }
-    e = hipMemcpyAsync(p->dev_block, p->host_block, total, hipMemcpyHostToDevice, stream);  // stream-ordered in front of the first launch
-    if (e == hipSuccess) e = hipEventRecord(p->uploaded, stream);
+    e = hipMemcpyAsync(p->dev_block, p->host_block, total, hipMemcpyHostToDevice, up);  // stream-ordered in front of the first launch
+    if (e == hipSuccess) e = capturing ? hipStreamSynchronize(up) : hipEventRecord(p->uploaded, stream);
     if (e != hipSuccess) {
         // the copy may have been queued: its two blocks go through the retire list, not straight back to the allocator
         ctx->last_hip = (int)e;
-        ctx->retired_plans.retire({p->dev_block}, {p->host_block}, {stream});
+        ctx->retired_plans.retire({p->dev_block}, {p->host_block}, {up});
         if (p->uploaded) (void)hipEventDestroy(p->uploaded);
         delete p;
         return LANCZOS_ERR_HIP;
     }
-    p->upload_stream = stream;
-    p->streams.push_back(stream);
+    if (capturing) {
+        p->captured = true;   // complete: no event, no upload stream to stay behind
+    } else {
+        p->upload_stream = stream;
+        p->streams.push_back(stream);
+    }
     uint8_t* b = (uint8_t*)p->dev_block;
     p->dev.h_first = (const int32_t*)(b + off_hf);
     p->dev.v_first = (const int32_t*)(b + off_vf);
@@ -507,6 +533,8 @@ int lanczos_destroy(lanczos_ctx* ctx) {
     ctx->wg_tabs.release_all();
     for (auto& kv : ctx->plans) free_plan(kv.second);
     ctx->plans.clear();
+    for (void* p : ctx->kept_dev) (void)hipFree(p);
+    for (void* p : ctx->kept_host) (void)hipHostFree(p);
     delete ctx->resize;
 #ifdef LZ_PROFILE_BITS
     if (ctx->stamp_buf) {
@@ -1033,6 +1061,13 @@ int lanczos_resize_taps_host(const lanczos_resize_desc* d, int axis, int32_t* fi
     memcpy(count, t.count.data(), t.count.size() * sizeof(int32_t));
     memcpy(coeffs, t.coeffs.data(), t.coeffs.size() * sizeof(int32_t));
     return LANCZOS_OK;
+}
+
+int lanczos_resize_plan_host(const lanczos_resize_desc* d, int frames, lanczos_resize_plan* out) {
+    int rc = lz::resize_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    if (frames < 1 || !out) return LANCZOS_ERR_BAD_ARG;
+    return lz::resize_plan_host(d, frames, out);
 }
 
 static int resize_state(lanczos_ctx* ctx) {

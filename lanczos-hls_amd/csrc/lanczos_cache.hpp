@@ -69,6 +69,11 @@ struct RetireList {
     }
     ~RetireList() { reap(true); }
 };
+// true while `s` is being captured into a graph (and when that cannot be told): work queued on it now does not run now
+inline bool stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+}
 inline void note_stream(std::vector<hipStream_t>& v, hipStream_t s) {
     if (std::find(v.begin(), v.end(), s) == v.end()) v.push_back(s);
 }
@@ -96,6 +101,12 @@ struct LruOrder {
 // device copies of the workgroup tables a context has used (callers serialise per context).  A table is built once per launch
 // shape into page-locked memory and uploaded asynchronously on the stream of its first launch; launches on other streams wait
 // for that upload by event.  Bounded: the least recently used shape is retired when the 65th arrives.
+//
+// Stream capture: a copy queued on a stream that is being captured becomes a graph node and moves nothing until the graph is
+// replayed -- perhaps never -- so a table first needed by a captured launch goes up eagerly instead: a copy on the cache's
+// private stream and a wait for it.  The item is valid from the moment it is cached and carries no `uploaded` event (nothing is
+// ever recorded on, queried from or waited for on a capturing stream).  A table a captured launch has used may be named by a
+// live graph: eviction moves its blocks to `kept`, which only release_all() frees -- a graph must not outlive its context.
 template <typename Entry>
 struct WgTabCacheT {
     static constexpr size_t kMaxItems = 64;
@@ -105,12 +116,40 @@ struct WgTabCacheT {
         Entry* host = nullptr;             // page-locked source of the upload (stays valid while the copy is in flight)
         int n = 0, segs = 1;
         bool balanced = false;
-        hipEvent_t uploaded = nullptr;     // recorded behind the upload
+        hipEvent_t uploaded = nullptr;     // recorded behind the upload; none where the upload was eager (complete)
         hipStream_t upload_stream = nullptr;
-        std::vector<hipStream_t> streams;  // streams this shape was uploaded / launched on
+        std::vector<hipStream_t> streams;  // streams this shape was uploaded / launched on (not captured ones)
+        bool captured = false;             // a captured launch has used it
     };
     std::vector<Item> items;               // least recently used first
     RetireList retired;
+    std::vector<void*> kept_dev, kept_host;   // blocks of evicted items a live graph may still name
+    hipStream_t eager = nullptr;              // private stream of the eager uploads, created on first need
+    hipError_t eager_stream(hipStream_t* s) {
+        hipError_t e = hipSuccess;
+        if (!eager) e = hipStreamCreateWithFlags(&eager, hipStreamNonBlocking);
+        *s = eager;
+        return e;
+    }
+    // every use of an item by a launch on `stream` goes through here: orders the launch behind the upload and remembers what
+    // has to drain before the item's blocks may go
+    hipError_t use(Item* it, hipStream_t stream) {
+        if (stream_capturing(stream)) {
+            // (an upload still in flight on another stream is waited for here: the graph gets no node for it)
+            if (it->uploaded && hipEventQuery(it->uploaded) != hipSuccess) {
+                const hipError_t e = hipEventSynchronize(it->uploaded);
+                if (e != hipSuccess) return e;
+            }
+            it->captured = true;
+            return hipSuccess;
+        }
+        if (it->uploaded && stream != it->upload_stream && hipEventQuery(it->uploaded) != hipSuccess) {
+            const hipError_t e = hipStreamWaitEvent(stream, it->uploaded, 0);  // another stream: behind the upload
+            if (e != hipSuccess) return e;
+        }
+        note_stream(it->streams, stream);
+        return hipSuccess;
+    }
     // set by every march_launch (query or launch): the batch size this kernel instance runs best at for this frame width -- the
     // largest one whose (strip, frame) pairs, cut in two chunks each, fill ONE resident round of workgroups with rank-aware
     // shares (config 2: 32 frames = 960 workgroups on 1 024 slots).  Larger batches are faster as several launches of this size
@@ -130,8 +169,8 @@ struct WgTabCacheT {
             }
         return nullptr;
     }
-    // uploads `tab` on `stream` and returns the new item (nullptr + *err on failure).  Pointers to items are valid until the
-    // next insert().
+    // uploads `tab` on `stream` (eagerly on the private stream if `stream` is being captured) and returns the new item
+    // (nullptr + *err on failure).  Pointers to items are valid until the next insert().
     Item* insert(const long long (&key)[8], const std::vector<Entry>& tab, int n, int segs, bool balanced, hipStream_t stream,
                  hipError_t* err) {
         retired.reap(false);
@@ -139,23 +178,34 @@ struct WgTabCacheT {
         memcpy(it.key, key, sizeof(key));
         it.n = n, it.segs = segs, it.balanced = balanced;
         const size_t bytes = sizeof(Entry) * tab.size();
-        hipError_t e = hipMalloc((void**)&it.dev, bytes);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&it.host, bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&it.uploaded, hipEventDisableTiming);
-        if (e == hipSuccess) {
-            memcpy(it.host, tab.data(), bytes);
-            e = hipMemcpyAsync(it.dev, it.host, bytes, hipMemcpyHostToDevice, stream);  // stream-ordered in front of the first launch
-        }
-        if (e == hipSuccess) e = hipEventRecord(it.uploaded, stream);
+        const bool capturing = stream_capturing(stream);   // hipStreamIsCapturing: the upload below must not become a graph node
+        hipStream_t up = stream;
+        hipError_t e = capturing ? eager_stream(&up) : hipSuccess;
         if (e != hipSuccess) {
-            // the copy may have been queued: nothing it touches is freed before that stream has drained
-            if (it.uploaded) (void)hipEventDestroy(it.uploaded);
-            retired.retire({it.dev}, {it.host}, {stream});
             *err = e;
             return nullptr;
         }
-        it.upload_stream = stream;
-        it.streams.push_back(stream);   // the upload itself reads `host` and writes `dev` on this stream
+        e = hipMalloc((void**)&it.dev, bytes);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&it.host, bytes, hipHostMallocDefault);
+        if (e == hipSuccess && !capturing) e = hipEventCreateWithFlags(&it.uploaded, hipEventDisableTiming);
+        if (e == hipSuccess) {
+            memcpy(it.host, tab.data(), bytes);
+            e = hipMemcpyAsync(it.dev, it.host, bytes, hipMemcpyHostToDevice, up);  // stream-ordered in front of the first launch
+        }
+        if (e == hipSuccess) e = capturing ? hipStreamSynchronize(up) : hipEventRecord(it.uploaded, stream);
+        if (e != hipSuccess) {
+            // the copy may have been queued: nothing it touches is freed before that stream has drained
+            if (it.uploaded) (void)hipEventDestroy(it.uploaded);
+            retired.retire({it.dev}, {it.host}, {up});
+            *err = e;
+            return nullptr;
+        }
+        if (capturing) {
+            it.captured = true;             // complete: no event, no upload stream to stay behind
+        } else {
+            it.upload_stream = stream;
+            it.streams.push_back(stream);   // the upload itself reads `host` and writes `dev` on this stream
+        }
         if (items.size() >= kMaxItems) drop(0);  // bounded: the least recently used shape goes (freed once its launches have drained)
         items.push_back(it);
         *err = hipSuccess;
@@ -163,7 +213,12 @@ struct WgTabCacheT {
     }
     void drop(size_t i) {
         Item& it = items[i];
-        retired.retire({it.dev}, {it.host}, it.streams);
+        if (it.captured) {
+            kept_dev.push_back(it.dev);
+            kept_host.push_back(it.host);
+        } else {
+            retired.retire({it.dev}, {it.host}, it.streams);
+        }
         if (it.uploaded) (void)hipEventDestroy(it.uploaded);
         items.erase(items.begin() + i);
     }
@@ -177,6 +232,12 @@ struct WgTabCacheT {
             if (it.uploaded) (void)hipEventDestroy(it.uploaded);
         }
         items.clear();
+        for (void* p : kept_dev) (void)hipFree(p);
+        for (void* p : kept_host) (void)hipHostFree(p);
+        kept_dev.clear();
+        kept_host.clear();
+        if (eager) (void)hipStreamDestroy(eager);
+        eager = nullptr;
     }
     ~WgTabCacheT() { release_all(); }
 };

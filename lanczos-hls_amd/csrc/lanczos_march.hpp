@@ -1538,15 +1538,14 @@ inline hipError_t march_launch_t(const lanczos_desc& d, const FrameGeom& g_in, c
             fprintf(stderr, "lanczos: k_march table: %d workgroups x %d segment(s) for %d strips x %d frames, rows [%d, %d): %s shares\n", item->n,
                     item->segs, strips, g.frames, m_lo, m_hi, item->balanced ? "rank-aware" : "equal");
     }
-    if (stream != item->upload_stream && hipEventQuery(item->uploaded) != hipSuccess) {
-        hipError_t e = hipStreamWaitEvent(stream, item->uploaded, 0);  // another stream: behind the upload
+    {
+        const hipError_t e = cache->use(item, stream);   // behind the upload
         if (e != hipSuccess) return e;
     }
     g.wg_tab = item->dev;
     g.wg_segs = item->segs;
     g.wg_per_frame = 0;
     g.n_main = item->n;
-    note_stream(item->streams, stream);
     dim3 grid(g.n_main + g.prefix_blocks_per_frame * g.frames);
     if (*prefix_fused) {
         if (exact) march_kernel_launch<T, C, S, A, true, false, true>(grid, dim3(K::NT), K::LDS_BYTES, stream, g, t, fc);

@@ -308,18 +308,13 @@ static int rs_bucket(int ksize) {
 
 // ---- host side: cache, planning, launch ---------------------------------------------------------------------------
 
-static bool rs_capturing(hipStream_t s) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-}
-
 // a block that launches on `streams` may still read: freed by a later call once they have drained.  A stream that is being
 // captured gets no event (it would become a graph node): such a block waits for the final reap behind a device-wide sync.
 static void rs_retire(RetireList& rl, void* p, const std::vector<hipStream_t>& streams) {
     std::vector<hipStream_t> live;
     bool captured = false;
     for (hipStream_t s : streams) {
-        if (rs_capturing(s)) captured = true;
+        if (stream_capturing(s)) captured = true;
         else live.push_back(s);
     }
     rl.retire({p}, {}, live);
@@ -413,12 +408,8 @@ static int rs_scratch(ResizeState* st, size_t bytes, hipStream_t stream, bool ca
 }
 
 // the fused kernel's launch shape for this request (false: it cannot run it)
-struct RsFusedPlan {
-    int K = 0, strips = 0, rows_per_chunk = 0, chunks = 0, ring_rows = 0, stage_rows = 0, stage_dw = 0;
-    size_t lds = 0;
-};
-static bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H, const ResizeAxisHost& V, int frames,
-                          RsFusedPlan* fp) {
+bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H, const ResizeAxisHost& V, int frames,
+                   RsFusedPlan* fp) {
     if (d->in_w == d->out_w || d->in_h == d->out_h) return false;   // one pass only: nothing to fuse
     if ((long long)d->in_w * d->in_h * d->channels + 4 >= (1ll << 31)) return false;   // 32-bit buffer offsets
     if ((long long)d->out_w * d->out_h * d->channels >= (1ll << 31)) return false;
@@ -455,6 +446,21 @@ static bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H,
     fp->rows_per_chunk = rpc;
     fp->chunks = (d->out_h + rpc - 1) / rpc;
     return (long long)fp->strips * fp->chunks < (1ll << 31);
+}
+
+int resize_plan_host(const lanczos_resize_desc* d, int frames, lanczos_resize_plan* out) {
+    memset(out, 0, sizeof(*out));
+    if (d->in_w == d->out_w || d->in_h == d->out_h) return LANCZOS_OK;   // as resize_device: no table for such an axis
+    ResizeAxisHost H, V;
+    if (!resize_build_axis(d->in_w, d->out_w, d->a, &H) || !resize_build_axis(d->in_h, d->out_h, d->a, &V))
+        return LANCZOS_ERR_UNSUPPORTED;
+    RsFusedPlan fp;
+    if (!rs_fused_plan(d, H, V, frames, &fp)) return LANCZOS_OK;
+    out->fused = 1;
+    out->K = fp.K, out->strips = fp.strips, out->rows_per_chunk = fp.rows_per_chunk, out->chunks = fp.chunks;
+    out->ring_rows = fp.ring_rows, out->stage_rows = fp.stage_rows, out->stage_dw = fp.stage_dw;
+    out->lds_bytes = (int32_t)fp.lds;
+    return LANCZOS_OK;
 }
 
 static hipError_t rs_launch_fused(const lanczos_resize_desc* d, const RsFusedPlan& fp, const ResizeAxis* H,
@@ -515,7 +521,7 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_i
     if (in_fs < in_frame || out_fs < out_frame) return LANCZOS_ERR_BAD_ARG;
     const uint8_t* in = (const uint8_t*)d_in;
     uint8_t* out = (uint8_t*)d_out;
-    const bool capturing = rs_capturing(stream);
+    const bool capturing = stream_capturing(stream);
     const bool need_h = d->in_w != d->out_w, need_v = d->in_h != d->out_h;
 
     ResizeAxis *H = nullptr, *V = nullptr;

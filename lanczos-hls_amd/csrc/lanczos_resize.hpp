@@ -27,6 +27,16 @@ struct ResizeAxisHost {
 int resize_ksize(int in_n, int out_n, int a);
 bool resize_build_axis(int in_n, int out_n, int a, ResizeAxisHost* t);
 
+// The fused kernel's launch shape for a request (false: it cannot run it).  H and V are the tables of the two axes, both of
+// which change size.  lanczos_resize_device plans with it; lanczos_resize_plan_host reports what it returns.
+struct RsFusedPlan {
+    int K = 0, strips = 0, rows_per_chunk = 0, chunks = 0, ring_rows = 0, stage_rows = 0, stage_dw = 0;
+    size_t lds = 0;
+};
+bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H, const ResizeAxisHost& V, int frames,
+                   RsFusedPlan* fp);
+int resize_plan_host(const lanczos_resize_desc* d, int frames, lanczos_resize_plan* out);
+
 // One axis shape on the device: first | count | coeffs in one block.
 struct ResizeAxis {
     int key[3] = {0, 0, 0};   // in, out, a

@@ -4,7 +4,8 @@
 // The handful of HIP calls the header makes are replaced by a small model of streams: work queued on a stream (an asynchronous
 // copy, an event record) completes only when the test drains that stream, and the model objects to
 //   * freeing a block that a queued copy still reads or writes (the round-3 harness crash: DESIGN.md 9),
-//   * freeing a block twice, leaking one, recording on a destroyed stream (reported as an error code, as HIP does).
+//   * freeing a block twice, leaking one, recording on a destroyed stream (reported as an error code, as HIP does),
+//   * queueing a copy, an event record or a wait on a stream that is being captured into a graph.
 // Round 3's verdict asked for exactly this: create -> many shapes -> destroy of the cache + RetireList with stubbed events.
 #include <cstdint>
 #include <cstdio>
@@ -19,6 +20,7 @@ typedef int hipError_t;
 static const hipError_t hipSuccess = 0, hipErrorNotReady = 600, hipErrorInvalidValue = 1, hipErrorOutOfMemory = 2;
 struct StubStream {
     bool alive = true;
+    bool capturing = false;                                // work queued now would become graph nodes: nothing may be queued
     std::vector<int> pending_events;                       // ids of events recorded and not yet reached
     std::vector<std::pair<const void*, const void*>> copies;  // (dst, src) of copies queued and not yet done
 };
@@ -28,7 +30,8 @@ struct StubEvent {
 };
 typedef StubStream* hipStream_t;
 typedef StubEvent* hipEvent_t;
-static const unsigned hipEventDisableTiming = 2, hipHostMallocDefault = 0;
+static const unsigned hipEventDisableTiming = 2, hipHostMallocDefault = 0, hipStreamNonBlocking = 1;
+enum hipStreamCaptureStatus { hipStreamCaptureStatusNone = 0, hipStreamCaptureStatusActive = 1 };
 enum hipMemcpyKind { hipMemcpyHostToDevice = 1 };
 
 static std::set<void*> g_dev, g_host;
@@ -92,6 +95,7 @@ static hipError_t hipEventDestroy(hipEvent_t e) {
 }
 static hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
     if (!s || !s->alive) return hipErrorInvalidValue;   // a stream the caller has destroyed
+    if (s->capturing) violation("hipEventRecord on a capturing stream");
     e->recorded = true;
     e->done = false;
     s->pending_events.push_back(e->id);
@@ -112,6 +116,7 @@ static hipError_t hipEventSynchronize(hipEvent_t e) {
 static hipError_t hipMemcpyAsync(void* dst, const void* src, size_t n, hipMemcpyKind, hipStream_t s) {
     if (g_copies++ == g_fail_copy_at) return hipErrorInvalidValue;
     if (!s || !s->alive) return hipErrorInvalidValue;
+    if (s->capturing) violation("hipMemcpyAsync on a capturing stream");
     (void)n;
     s->copies.push_back({dst, src});   // the bytes move when the stream is drained
     return hipSuccess;
@@ -129,6 +134,33 @@ static void drain(hipStream_t s) {
 static hipStream_t new_stream() {
     g_streams.push_back(new StubStream());
     return g_streams.back();
+}
+static int g_private_streams = 0;
+static hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
+    *s = new_stream();
+    g_private_streams++;
+    return hipSuccess;
+}
+static hipError_t hipStreamDestroy(hipStream_t s) {
+    if (!s->alive) violation("hipStreamDestroy of a dead stream");
+    drain(s);
+    s->alive = false;
+    g_private_streams--;
+    return hipSuccess;
+}
+static hipError_t hipStreamSynchronize(hipStream_t s) {
+    if (s->capturing) violation("hipStreamSynchronize of a capturing stream");
+    drain(s);
+    return hipSuccess;
+}
+static hipError_t hipStreamIsCapturing(hipStream_t s, hipStreamCaptureStatus* cs) {
+    *cs = s && s->capturing ? hipStreamCaptureStatusActive : hipStreamCaptureStatusNone;
+    return hipSuccess;
+}
+static hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
+    if (s->capturing) violation("hipStreamWaitEvent on a capturing stream");
+    if (!g_events.count(e->id)) violation("hipStreamWaitEvent on a dead event");
+    return hipSuccess;
 }
 
 #define LZ_CACHE_TEST_STUBS
@@ -251,6 +283,39 @@ int main() {
         }
         c.drop(0);
         drain(s1);   // (release_all's precondition: the owner has drained the device)
+    }
+    EXPECT(g_dev.empty() && g_host.empty() && g_events.empty());
+    {   // 8. first use while the stream is being captured: the table goes up eagerly on the private stream and is complete when
+        // insert() returns, nothing is queued on the capturing stream, and eviction keeps the blocks for the live graph
+        Cache c;
+        long long k[8];
+        std::vector<Entry> tab(5, Entry{0, 0, 0, 1});
+        hipError_t e;
+        hipStream_t cap = new_stream();
+        cap->capturing = true;
+        make_key(k, 1);
+        Cache::Item* it = c.insert(k, tab, 5, 1, true, cap, &e);
+        EXPECT(it && e == hipSuccess && it->captured && !it->uploaded && !it->upload_stream && it->streams.empty());
+        EXPECT(it && !in_flight(it->dev) && c.eager && c.eager != cap && g_private_streams == 1);
+        void* dev = it ? it->dev : nullptr;
+        cap->capturing = false;
+        EXPECT(it && c.use(it, s1) == hipSuccess && it->streams.size() == 1);   // eager use: no event to wait for
+        make_key(k, 2);                                                       // uploaded eagerly on s1, still in flight, then captured
+        it = c.insert(k, tab, 5, 1, true, s1, &e);
+        EXPECT(it && it->uploaded && !it->captured && in_flight(it->dev));
+        cap->capturing = true;
+        EXPECT(it && c.use(it, cap) == hipSuccess && it->captured && !in_flight(it->dev) && it->streams.size() == 1);
+        cap->capturing = false;
+        for (int shape = 100; shape < 100 + (int)Cache::kMaxItems; shape++) {  // both evicted: kept, not retired
+            make_key(k, shape);
+            EXPECT(c.insert(k, tab, 5, 1, true, s1, &e) != nullptr);
+        }
+        EXPECT(c.kept_dev.size() == 2 && c.kept_host.size() == 2 && c.retired.list.empty());
+        drain(s1);
+        c.retired.reap(false);
+        EXPECT(g_dev.count(dev));                           // a replay may still read it
+        c.release_all();
+        EXPECT(c.kept_dev.empty() && !c.eager && g_private_streams == 0);
     }
     EXPECT(g_dev.empty() && g_host.empty() && g_events.empty());
     {   // 7. recency order of the plan cache

@@ -792,6 +792,64 @@ def test_first_use_of_a_shape_inside_stream_capture():
         c.close()
 
 
+@pytest.mark.parametrize("mode", [L.MODE_EXACT, L.MODE_LSB1])
+@pytest.mark.parametrize("sn,sd", [(2, 1), (3, 2)])
+def test_first_use_inside_capture_then_eager_before_replay(sn, sd, mode):
+    """The tap tables and the workgroup table of a shape first used inside stream capture are valid at once (they go up
+    eagerly on a private stream; a copy queued on the capturing stream would run only at a replay): an eager call BEFORE any
+    replay gives the right samples, the graph replays afterwards, also after an eager call of another shape, and a graph
+    that is dropped without ever being replayed leaves a usable plan behind.  2/1 is served by k_march, 3/2 by k_rat."""
+    import torch
+    c = L.Context(0)
+    try:
+        w, h, a = 120, 76 + 2 * mode + sd, 3                 # shapes no other test of this module uses
+        img, img2 = P.gradient_noise(h, w, 3, seed=15), P.noise(h, w, 3, seed=16)
+        d = L.make_desc(w, h, 3, sn, sd, a, 1, mode)
+        x = torch.from_numpy(img).cuda()
+        y = torch.zeros((d.out_h, d.out_w, 3), dtype=torch.uint8, device="cuda")
+        g = torch.cuda.CUDAGraph()
+        s = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        with torch.cuda.graph(g, stream=s, capture_error_mode="relaxed"):
+            c.resample_device(d, x.data_ptr(), y.data_ptr(), 1, stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        assert int(y.max()) == 0                              # captured, not run
+        y2 = torch.zeros_like(y)
+        c.resample_device(d, x.data_ptr(), y2.data_ptr(), 1, stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        assert c.last_kernel() == L.KERNEL_FAST
+        _cmp(y2.cpu().numpy(), _oracle(img, sn, sd, a), mode, "eager call before any replay", _req(c, img, sn, sd, a))
+        assert int(y.max()) == 0
+        x.copy_(torch.from_numpy(img2))
+        g.replay()
+        torch.cuda.synchronize()
+        _cmp(y.cpu().numpy(), _oracle(img2, sn, sd, a), mode, "replay", _req(c, img2, sn, sd, a))
+        other = P.noise(50, 88, 3, seed=17)                   # another shape, eagerly
+        _cmp(c.resample(other, sn, sd, a, mode), _oracle(other, sn, sd, a), mode, "other shape", _req(c, other, sn, sd, a))
+        x.copy_(torch.from_numpy(img))
+        y.zero_()
+        g.replay()
+        torch.cuda.synchronize()
+        _cmp(y.cpu().numpy(), _oracle(img, sn, sd, a), mode, "replay after other work", _req(c, img, sn, sd, a))
+        del g
+        # a graph that is never replayed
+        img3 = P.gradient_noise(h + 2, w, 3, seed=18)
+        d3 = L.make_desc(w, h + 2, 3, sn, sd, a, 1, mode)
+        x3 = torch.from_numpy(img3).cuda()
+        y3 = torch.zeros((d3.out_h, d3.out_w, 3), dtype=torch.uint8, device="cuda")
+        g3 = torch.cuda.CUDAGraph()
+        torch.cuda.synchronize()
+        with torch.cuda.graph(g3, stream=s, capture_error_mode="relaxed"):
+            c.resample_device(d3, x3.data_ptr(), y3.data_ptr(), 1, stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        del g3
+        c.resample_device(d3, x3.data_ptr(), y3.data_ptr(), 1, stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        _cmp(y3.cpu().numpy(), _oracle(img3, sn, sd, a), mode, "eager call after a dropped graph", _req(c, img3, sn, sd, a))
+    finally:
+        c.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # The LSB1 contract at full size (tests/lsb1_check.py), with coverage asserted: the window population (samples whose reference
 # sum lies within delta of a store boundary: where the biased floor decides) and the integer-phase flips of the H pass (where

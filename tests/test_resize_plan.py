@@ -1,0 +1,182 @@
+"""CPU-only checks of the fused resize kernel's launch plan (lanczos_resize_plan_host, the same function the launch uses).
+
+The invariants are written from the axis tables (lanczos_resize_taps_host, pinned to the numpy model and to Pillow by
+tests/test_resize_host.py) and from the march the kernel documents (csrc/lanczos_resize.hip), not from the planner's
+formulas:
+
+  * a workgroup owns a strip of SW output columns (256; 64 for four channels) and a chunk of `rows_per_chunk` output rows,
+    and marches down the chunk in blocks of 8 rows.  The rows a block's vertical taps read, first[o0] ..
+    first[last] + count[last] - 1, live in an LDS ring of `ring_rows` rows, slot = row % ring_rows;
+  * input rows are staged `stage_rows` at a time, `stage_dw` dwords each, from the dword that holds the strip's first
+    input byte; a thread reads NE + 1 dwords, NE = (K * C + 3) / 4, from dword (align + (first[p] - first[x0]) * C) >> 2 of
+    the staged row, align = the byte offset of the strip's first input byte in its dword (0..3);
+  * K is the smallest horizontal tap count with an instance that is >= ksize; LDS = ring + staging <= 80 KiB.
+"""
+import numpy as np
+import pytest
+
+import lanczos_hls_amd as L
+
+SWEEP = [1, 2, 3, 5, 7, 16, 17, 40, 97, 160, 333, 1000, 1080, 1920, 3840]   # tests/test_resize_host.py's
+BUCKETS = (7, 9, 11, 13, 17, 25)
+LDS_MAX = 80 * 1024
+OB = 8                       # output rows per march block
+BIG = (65535, 32768, 60000, 30000)   # 3 and 4 channels: a frame of 2^31 bytes or more
+
+_TABLES = {}
+
+
+def tables(in_n, out_n, a):
+    """(first, count, ksize) of one axis from the library's host tables."""
+    key = (in_n, out_n, a)
+    if key not in _TABLES:
+        d = L.resize_desc(in_n, 1, out_n, 1, 1, a)
+        f, c, k = L.resize_taps_host(d, 0)
+        _TABLES[key] = (f.astype(np.int64), c.astype(np.int64), k.shape[1])
+    return _TABLES[key]
+
+
+def strip_width(channels):
+    return 64 if channels == 4 else 256
+
+
+def min_ring_rows(vf, vc, out_h):
+    """The most input rows any block of 8 output rows (from row 0) reads."""
+    o0 = np.arange(0, out_h, OB)
+    last = np.minimum(o0 + OB, out_h) - 1
+    return int((vf[last] + vc[last] - vf[o0]).max())
+
+
+def min_stage_dw(hf, out_w, channels, k):
+    """Dwords of a staged row that the widest strip reads at the worst alignment: last index + 1."""
+    sw = strip_width(channels)
+    ne = (k * channels + 3) // 4
+    x0 = np.arange(0, out_w, sw)
+    x1 = np.minimum(x0 + sw, out_w) - 1
+    return int((((3 + (hf[x1] - hf[x0]) * channels) >> 2) + ne).max()) + 1
+
+
+def two_pass_reasons(in_w, in_h, out_w, out_h, channels, a):
+    """Why the fused kernel cannot run a request (csrc/lanczos_resize.hip), each computed from the request and
+    its tables alone: [] means it can."""
+    reasons = []
+    if in_w == out_w or in_h == out_h:
+        return ["axis"]                       # one pass only (or a copy): nothing to fuse, and no table for that axis
+    if in_w * in_h * channels + 4 >= 2 ** 31 or out_w * out_h * channels >= 2 ** 31:
+        reasons.append("bytes")               # 32-bit buffer offsets
+    hf, hc, hks = tables(in_w, out_w, a)
+    vf, vc, _ = tables(in_h, out_h, a)
+    k = next((b for b in BUCKETS if b >= hks), 0)
+    if not k:
+        reasons.append("bucket")              # no instance with that many horizontal taps
+    else:
+        ring = min_ring_rows(vf, vc, out_h) * strip_width(channels) * channels
+        if ring + 4 * min_stage_dw(hf, out_w, channels, k) * 4 > LDS_MAX:
+            reasons.append("lds")             # the ring and the smallest staging (4 rows) do not fit
+    return reasons
+
+
+def check_plan(shape, channels, a, frames):
+    """Asserts every invariant of the plan of one request; returns 'fused' or the first reason for two-pass."""
+    in_w, in_h, out_w, out_h = shape
+    what = (shape, channels, a, frames)
+    p = L.resize_plan_host(L.resize_desc(in_w, in_h, out_w, out_h, channels, a), frames)
+    reasons = two_pass_reasons(in_w, in_h, out_w, out_h, channels, a)
+    if not p.fused:
+        assert reasons, what
+        assert (p.K, p.strips, p.rows_per_chunk, p.chunks, p.ring_rows, p.stage_rows, p.stage_dw, p.lds_bytes) == (0,) * 8
+        return reasons[0]
+    assert not reasons or reasons == ["lds"] and p.stage_rows < 4, (what, reasons)
+    assert in_w != out_w and in_h != out_h, what
+    hf, hc, hks = tables(in_w, out_w, a)
+    vf, vc, _ = tables(in_h, out_h, a)
+    sw = strip_width(channels)
+    assert p.K >= hks and p.K in BUCKETS and not any(hks <= b < p.K for b in BUCKETS), (what, p.K, hks)
+    assert (hc <= p.K).all(), what
+    assert p.strips == -(-out_w // sw), what
+    assert p.lds_bytes == p.ring_rows * sw * channels + p.stage_rows * p.stage_dw * 4, what
+    assert p.lds_bytes <= LDS_MAX, what
+    # chunks
+    rpc = p.rows_per_chunk
+    assert rpc > 0 and rpc % OB == 0, (what, rpc)
+    assert p.chunks * rpc >= out_h and (p.chunks - 1) * rpc < out_h, (what, rpc, p.chunks)
+    # ring: every block of every chunk.  The tables must be monotone for the block's first and last row to bound it.
+    assert (np.diff(vf) >= 0).all() and (np.diff(vf + vc) >= 0).all(), what
+    for c in range(p.chunks):
+        o_end = min((c + 1) * rpc, out_h)
+        o0 = np.arange(c * rpc, o_end, OB)
+        last = np.minimum(o0 + OB, o_end) - 1
+        span = vf[last] + vc[last] - vf[o0]
+        assert int(span.max()) <= p.ring_rows, (what, c, int(span.max()), p.ring_rows)
+    # staging: every strip, every output column of it, every alignment
+    assert (np.diff(hf) >= 0).all(), what
+    ne = (p.K * channels + 3) // 4
+    x = np.arange(out_w)
+    hoffb = (hf - hf[x // sw * sw]) * channels
+    for align in range(4):
+        last_dw = ((align + hoffb) >> 2) + ne
+        assert int(last_dw.max()) < p.stage_dw, (what, align, int(last_dw.max()), p.stage_dw)
+    assert p.stage_rows >= 1, what
+    assert p.stage_rows * p.stage_dw + 16 * 256 < 2 ** 20, what   # the staging loop's float division is exact below 2^20
+    return "fused"
+
+
+def sweep_shapes():
+    """Every (in, out) pair of SWEEP x SWEEP as the horizontal axis and as the vertical axis, each with three partners."""
+    pairs = [(i, o) for i in SWEEP for o in SWEEP if i * o <= 4_000_000]
+    n = len(pairs)
+    shapes = []
+    for k, (iw, ow) in enumerate(pairs):
+        for step in (1, 71, 149):
+            ih, oh = pairs[(k * step + 5 * step) % n]
+            shapes.append((iw, ih, ow, oh))
+    shapes.append(BIG)
+    return shapes
+
+
+@pytest.mark.parametrize("channels", [1, 3, 4])
+@pytest.mark.parametrize("a", [2, 3, 4])
+def test_plan_invariants_over_the_sweep(channels, a):
+    """661 shapes (every SWEEP x SWEEP pair as the horizontal and as the vertical axis, and one frame of 2^31 bytes or more)
+    x frames in {1, 32}: 1322 plans per (channels, a).  How they plan (first reason that holds, in the order axis, bytes,
+    bucket, lds):
+
+        C a | fused  axis  bytes  bucket  lds
+        1 2 |   644   164      0     388  126
+        1 3 |   606   164      0     424  128
+        1 4 |   566   164      0     470  122
+        3 2 |   590   164      2     388  178
+        3 3 |   556   164      2     424  176
+        3 4 |   522   164      2     470  164
+        4 2 |   642   164      2     388  126
+        4 3 |   604   164      2     424  128
+        4 4 |   564   164      2     470  122
+
+    (one channel: 65535 x 32768 stays below 2^31 bytes, so `bytes` cannot occur there.)  Every outcome must occur, so that no
+    branch of the planner leaves the sweep unnoticed."""
+    shapes = sweep_shapes()
+    hs = {(s[0], s[2]) for s in shapes}
+    vs = {(s[1], s[3]) for s in shapes}
+    want = {(i, o) for i in SWEEP for o in SWEEP if i * o <= 4_000_000}
+    assert want <= hs and want <= vs
+    counts = {}
+    for shape in shapes:
+        for frames in (1, 32):
+            r = check_plan(shape, channels, a, frames)
+            counts[r] = counts.get(r, 0) + 1
+    print(f"C={channels} a={a}: {counts}")
+    outcomes = {"fused", "axis", "bucket", "lds"} | ({"bytes"} if channels > 1 else set())
+    assert set(counts) == outcomes, counts
+
+
+def test_plan_query_validation():
+    import ctypes
+    lib = L._lib()
+    p = L.ResizePlan()
+    d = L.resize_desc(64, 48, 20, 100, 3, 3)
+    assert lib.lanczos_resize_plan_host(ctypes.byref(d), 1, ctypes.byref(p)) == L.OK and p.fused == 1
+    assert lib.lanczos_resize_plan_host(ctypes.byref(d), 0, ctypes.byref(p)) == L.ERR_BAD_ARG
+    assert lib.lanczos_resize_plan_host(ctypes.byref(d), 1, None) == L.ERR_BAD_ARG
+    assert lib.lanczos_resize_plan_host(None, 1, ctypes.byref(p)) == L.ERR_BAD_ARG
+    d.channels = 2
+    assert lib.lanczos_resize_plan_host(ctypes.byref(d), 1, ctypes.byref(p)) == L.ERR_BAD_ARG
