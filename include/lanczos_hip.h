@@ -205,15 +205,22 @@ int lanczos_device_copy(int device, void* dst, const void* src, size_t bytes, in
  *   acc = 2^21 + sum(sample * coeff) in int32, result = clamp(acc >> 22, 0, 255).
  * The horizontal pass runs first into an 8-bit intermediate; a pass whose axis keeps its size is skipped (as Pillow does).
  * Channels are independent: 8-bit interleaved samples, 1, 3 or 4 channels.  Four channels give Pillow's result on RGBX /
- * RGBa data; Pillow's RGBA mode premultiplies alpha inside resize -- a caller who wants that result premultiplies (and
- * afterwards un-premultiplies) the data itself. */
+ * RGBa data.  With LANCZOS_RESIZE_ALPHA in the flag word they give Pillow's result in mode RGBA instead (channel 3 is
+ * straight alpha), byte for byte, inside the same kernels -- no extra launch and no extra pass over memory:
+ *   every input pixel is premultiplied: t = c * A + 128, c' = ((t >> 8) + t) >> 8 for its three colour samples c, alpha A
+ *   as it is; both passes run on the premultiplied four channels, alpha filtered like any other channel; every output
+ *   pixel with resized alpha A keeps its colour samples if A is 0 or 255 and otherwise gets c = min(255, 255 * c' / A)
+ *   (truncating; c' > A occurs where the filter rings).  A resize that changes neither axis is a plain copy, flag or not. */
 typedef struct lanczos_resize_desc {
     int32_t in_w, in_h;     /* 1..65535 each */
     int32_t out_w, out_h;   /* 1..65535 each, independent of the input size and of each other */
     int32_t channels;       /* 1, 3 or 4, interleaved, 8-bit samples */
     int32_t a;              /* 2, 3 or 4 (3 = Pillow's LANCZOS) */
-    int32_t reserved[2];    /* must be 0 */
+    int32_t reserved[2];    /* reserved[0]: flags, 0 or LANCZOS_RESIZE_ALPHA; reserved[1]: must be 0 */
 } lanczos_resize_desc;
+
+/* flag of lanczos_resize_desc.reserved[0]: channel 3 is straight alpha (Pillow's RGBA mode); channels must be 4 */
+#define LANCZOS_RESIZE_ALPHA 1
 
 /* forced path of lanczos_resize_force (tests and A/B runs only) */
 #define LANCZOS_RESIZE_AUTO 0
@@ -222,7 +229,11 @@ typedef struct lanczos_resize_desc {
 
 /* host only, no GPU needed */
 int lanczos_resize_desc_init(lanczos_resize_desc* d, int in_w, int in_h, int out_w, int out_h, int channels, int a);
-int lanczos_resize_validate(const lanczos_resize_desc* d);   /* LANCZOS_ERR_BAD_ARG: size, channels, a or reserved */
+/* the same with the flag word (lanczos_resize_desc_init gives 0) */
+int lanczos_resize_desc_init_ex(lanczos_resize_desc* d, int in_w, int in_h, int out_w, int out_h, int channels, int a,
+                                int flags);
+/* LANCZOS_ERR_BAD_ARG: size, channels, a, a flag other than LANCZOS_RESIZE_ALPHA, that flag without four channels */
+int lanczos_resize_validate(const lanczos_resize_desc* d);
 /* Fixed-point tables of one axis (0 = horizontal, 1 = vertical): output o reads inputs first[o] .. first[o] + count[o] - 1
  * with coeffs[o * ksize + i] (i < count[o]; zero beyond).  *ksize = 2 * ceil(support) + 1.  With first, count and coeffs all
  * NULL only *ksize is returned; otherwise all three must hold out (and out * ksize) elements. */

@@ -25,6 +25,7 @@ MODE_LSB1, MODE_EXACT, MODE_HLS = 0, 1, 2
 KERNEL_NONE, KERNEL_GENERIC, KERNEL_FAST, KERNEL_HLS = 0, 1, 2, 3
 KERNEL_RESIZE_FUSED, KERNEL_RESIZE_TWO_PASS = 4, 5
 RESIZE_AUTO, RESIZE_FUSED, RESIZE_TWO_PASS = 0, 1, 2   # lanczos_resize_force
+RESIZE_ALPHA = 1   # flag of lanczos_resize_desc.reserved[0]: channel 3 of 4 is straight alpha (Pillow's RGBA mode)
 
 # every symbol include/lanczos_hip.h declares (tests check the library exports exactly these)
 ABI_SYMBOLS = [
@@ -40,7 +41,7 @@ ABI_SYMBOLS = [
     "lanczos_multi_devices", "lanczos_resample_multi_host", "lanczos_resample_multi_root",
     "lanczos_multi_last_error", "lanczos_multi_exchange_plan", "lanczos_multi_exchange_selftest", "lanczos_device_alloc", "lanczos_device_free",
     "lanczos_device_copy",
-    "lanczos_resize_desc_init", "lanczos_resize_validate", "lanczos_resize_taps_host", "lanczos_resize_device",
+    "lanczos_resize_desc_init", "lanczos_resize_desc_init_ex", "lanczos_resize_validate", "lanczos_resize_taps_host", "lanczos_resize_device",
     "lanczos_resize_host", "lanczos_resize_force", "lanczos_resize_plan_host",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
@@ -149,6 +150,7 @@ def _lib():
                                                   ctypes.POINTER(c_double), ctypes.POINTER(c_double)]
         PRD = ctypes.POINTER(ResizeDesc)
         L.lanczos_resize_desc_init.argtypes = [PRD] + [c_int] * 6
+        L.lanczos_resize_desc_init_ex.argtypes = [PRD] + [c_int] * 7
         L.lanczos_resize_validate.argtypes = [PRD]
         L.lanczos_resize_taps_host.argtypes = [PRD, c_int, c_void_p, c_void_p, c_void_p, PI]
         L.lanczos_resize_device.argtypes = [c_void_p, PRD, c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p]
@@ -210,11 +212,12 @@ def taps_host(desc, axis):
     return first, w
 
 
-def resize_desc(in_w, in_h, out_w, out_h, channels, a=3):
-    """A validated lanczos_resize_desc (Pillow's contract: any output size, downscaling included)."""
+def resize_desc(in_w, in_h, out_w, out_h, channels, a=3, alpha=False):
+    """A validated lanczos_resize_desc (Pillow's contract: any output size, downscaling included).  alpha: the fourth of
+    four channels is straight alpha, resized as Pillow's mode RGBA (premultiplied inside the kernels)."""
     d = ResizeDesc()
-    _check(_lib().lanczos_resize_desc_init(ctypes.byref(d), in_w, in_h, out_w, out_h, channels, a),
-           "lanczos_resize_desc_init")
+    _check(_lib().lanczos_resize_desc_init_ex(ctypes.byref(d), in_w, in_h, out_w, out_h, channels, a,
+                                              RESIZE_ALPHA if alpha else 0), "lanczos_resize_desc_init_ex")
     return d
 
 
@@ -348,16 +351,18 @@ class Context:
                                                      stream), "lanczos_resample_planar_device")
 
     # -- resize to any size (Pillow's contract, lanczos_resize_*)
-    def resize(self, img, out_w, out_h, a=3):
+    def resize(self, img, out_w, out_h, a=3, alpha=False):
         """img: uint8 [H][W], [H][W][C] or [F][H][W][C] -> the same layout at out_h x out_w, bytes identical to Pillow's
-        Image.resize((out_w, out_h), Image.LANCZOS) for a = 3 (RGBX semantics for four channels: no premultiplication)."""
+        Image.resize((out_w, out_h), Image.LANCZOS) for a = 3.  Four channels: mode RGBX (independent channels) by default,
+        mode RGBA (straight alpha in the last channel, premultiplied inside the kernels) with alpha=True; alpha=True with any
+        other channel count raises LanczosError(ERR_BAD_ARG)."""
         img = np.ascontiguousarray(img)
         if img.dtype != np.uint8 or img.ndim not in (2, 3, 4):
             raise LanczosError(ERR_BAD_ARG, "resize: expected a uint8 [H][W], [H][W][C] or [F][H][W][C] array")
         x = img.reshape(img.shape + (1,)) if img.ndim == 2 else img
         x = x if x.ndim == 4 else x[None]
         f, h, w, c = x.shape
-        d = resize_desc(w, h, out_w, out_h, c, a)
+        d = resize_desc(w, h, out_w, out_h, c, a, alpha)
         out = np.empty((f, out_h, out_w, c), dtype=np.uint8)
         _check(_lib().lanczos_resize_host(self._h, ctypes.byref(d), x.ctypes.data, out.ctypes.data, f),
                "lanczos_resize_host")

@@ -1044,6 +1044,15 @@ int lanczos_resize_desc_init(lanczos_resize_desc* d, int in_w, int in_h, int out
     return lz::resize_validate(d);
 }
 
+int lanczos_resize_desc_init_ex(lanczos_resize_desc* d, int in_w, int in_h, int out_w, int out_h, int channels, int a,
+                                int flags) {
+    if (!d) return LANCZOS_ERR_BAD_ARG;
+    memset(d, 0, sizeof(*d));
+    d->in_w = in_w, d->in_h = in_h, d->out_w = out_w, d->out_h = out_h, d->channels = channels, d->a = a;
+    d->reserved[0] = flags;
+    return lz::resize_validate(d);
+}
+
 int lanczos_resize_validate(const lanczos_resize_desc* d) { return lz::resize_validate(d); }
 
 int lanczos_resize_taps_host(const lanczos_resize_desc* d, int axis, int32_t* first, int32_t* count, int32_t* coeffs,

@@ -11,9 +11,15 @@
 //             count.  It also serves a resize that changes one axis only (one kernel) -- as Pillow, a pass whose axis keeps
 //             its size is skipped.
 //
+// LANCZOS_RESIZE_ALPHA (four channels, Pillow's RGBA mode): both paths premultiply the colour samples by alpha where they
+// read the frame and divide alpha out where they write it (lanczos_alpha.hpp), k_rs_fused<4, K, true> and k_rs_h_alpha /
+// k_rs_v_alpha; tables, plan and scratch are those of the same request without the flag.
+//
 // Arithmetic is Pillow's and exact by construction: acc = 2^21 + sum(sample * coeff) in int32 with 24-bit multiplies
 // (|coeff| < 2^23 and 255 * sum|coeff| + 2^21 < 2^31, checked when a table is built), result clamp(acc >> 22, 0, 255).
 #include "lanczos_resize.hpp"
+
+#include "lanczos_alpha.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -31,7 +37,8 @@ int resize_validate(const lanczos_resize_desc* d) {
         if (s < 1 || s > kResizeMaxSize) return LANCZOS_ERR_BAD_ARG;
     if (d->channels != 1 && d->channels != 3 && d->channels != 4) return LANCZOS_ERR_BAD_ARG;
     if (d->a < 2 || d->a > 4) return LANCZOS_ERR_BAD_ARG;
-    if (d->reserved[0] != 0 || d->reserved[1] != 0) return LANCZOS_ERR_BAD_ARG;
+    if ((d->reserved[0] & ~LANCZOS_RESIZE_ALPHA) != 0 || d->reserved[1] != 0) return LANCZOS_ERR_BAD_ARG;
+    if ((d->reserved[0] & LANCZOS_RESIZE_ALPHA) && d->channels != 4) return LANCZOS_ERR_BAD_ARG;
     return LANCZOS_OK;
 }
 
@@ -142,6 +149,58 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_v(RsPass p) {
     p.dst[blockIdx.z * p.dst_fs + o * p.dst_pitch + x] = (uint8_t)rs_clip8(acc);
 }
 
+// LANCZOS_RESIZE_ALPHA on the two-pass path: one thread per four-channel pixel, so that a colour sample has its alpha next
+// to it.  The horizontal kernel premultiplies what it reads; with UN (no vertical pass follows) it also divides alpha out
+// of what it writes, otherwise the intermediate holds premultiplied pixels.  The vertical kernel divides alpha out of what
+// it writes; with PRE (no horizontal pass ran) it premultiplies what it reads.  Frames may start at any byte: byte accesses.
+__device__ __forceinline__ uint32_t rs_load_px(const uint8_t* p) {
+    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+}
+__device__ __forceinline__ void rs_store_px(uint8_t* p, uint32_t v) {
+#pragma unroll
+    for (int b = 0; b < 4; b++) p[b] = (uint8_t)(v >> (8 * b));
+}
+__device__ __forceinline__ void rs_mad_px(uint32_t px, int k, int (&acc)[4]) {
+#pragma unroll
+    for (int b = 0; b < 4; b++) acc[b] = rs_mad((int)((px >> (8 * b)) & 255u), k, acc[b]);
+}
+__device__ __forceinline__ uint32_t rs_clip_px(const int (&acc)[4]) {
+    return rs_clip8(acc[0]) | (rs_clip8(acc[1]) << 8) | (rs_clip8(acc[2]) << 16) | (rs_clip8(acc[3]) << 24);
+}
+
+template <bool UN>
+__global__ __launch_bounds__(kRsThreads) void k_rs_h_alpha(RsPass p) {
+    const int o = blockIdx.x * kRsThreads + threadIdx.x;   // output pixel of row blockIdx.y (n_cols counts samples)
+    if (o * 4 >= p.n_cols) return;
+    const int f = p.first[o], n = p.count[o];
+    const uint8_t* src = p.src + blockIdx.z * p.src_fs + blockIdx.y * p.src_pitch + (size_t)f * 4;
+    const int32_t* k = p.coeffs + (size_t)o * p.ksize;
+    int acc[4] = {1 << (kResizePrecision - 1), 1 << (kResizePrecision - 1), 1 << (kResizePrecision - 1),
+                  1 << (kResizePrecision - 1)};
+#pragma unroll 4
+    for (int i = 0; i < n; i++) rs_mad_px(rs_premul_px(rs_load_px(src + (size_t)i * 4)), k[i], acc);
+    const uint32_t px = rs_clip_px(acc);
+    rs_store_px(p.dst + blockIdx.z * p.dst_fs + blockIdx.y * p.dst_pitch + (size_t)o * 4, UN ? rs_unpremul_px(px) : px);
+}
+
+template <bool PRE>
+__global__ __launch_bounds__(kRsThreads) void k_rs_v_alpha(RsPass p) {
+    const int x = blockIdx.x * kRsThreads + threadIdx.x;   // pixel column
+    if (x * 4 >= p.n_cols) return;
+    const int o = blockIdx.y;
+    const int f = p.first[o], n = p.count[o];
+    const int32_t* k = p.coeffs + (size_t)o * p.ksize;
+    const uint8_t* src = p.src + blockIdx.z * p.src_fs + (size_t)f * p.src_pitch + (size_t)x * 4;
+    int acc[4] = {1 << (kResizePrecision - 1), 1 << (kResizePrecision - 1), 1 << (kResizePrecision - 1),
+                  1 << (kResizePrecision - 1)};
+#pragma unroll 4
+    for (int i = 0; i < n; i++) {
+        const uint32_t px = rs_load_px(src + (size_t)i * p.src_pitch);
+        rs_mad_px(PRE ? rs_premul_px(px) : px, k[i], acc);
+    }
+    rs_store_px(p.dst + blockIdx.z * p.dst_fs + o * p.dst_pitch + (size_t)x * 4, rs_unpremul_px(rs_clip_px(acc)));
+}
+
 struct RsFused {
     const uint8_t* in;
     uint8_t* out;
@@ -163,8 +222,13 @@ struct RsStrip {
     static constexpr int WPR = RDW / 64;          // waves per ring row in the vertical pass
 };
 
-template <int C, int K>
+// ALPHA (LANCZOS_RESIZE_ALPHA, C == 4): the staging loads premultiply, once per staged pixel and not once per window that
+// reads it, and the vertical pass divides alpha out where it packs its dword, which for four channels is one pixel.  For
+// that the staged dwords are pixels: a frame base that is no dword multiple (every row then starts `delta` bytes into a
+// dword, the row pitch being one) is shifted out while staging, and the horizontal pass reads its window unshifted.
+template <int C, int K, bool ALPHA = false>
 __global__ __launch_bounds__(kRsThreads) void k_rs_fused(RsFused g) {
+    static_assert(!ALPHA || C == 4, "alpha is the fourth of four channels");
     using S = RsStrip<C>;
     constexpr int SW = S::SW, RL = S::RL, RDW = S::RDW, WPR = S::WPR;
     constexpr int NE = (K * C + 3) / 4;   // dwords of one horizontal window
@@ -219,6 +283,8 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(RsFused g) {
             const int total = nr * g.stage_dw;
             for (int u0 = tid; u0 < total; u0 += kRsLoadBatch * kRsThreads) {
                 uint32_t v[kRsLoadBatch];
+                uint32_t vn[ALPHA ? kRsLoadBatch : 1];   // ALPHA, delta != 0: the dword behind v[b], the rest of its pixel
+                (void)vn;
 #pragma unroll
                 for (int b = 0; b < kRsLoadBatch; b++) {
                     const int u = u0 + b * kRsThreads;
@@ -226,21 +292,28 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(RsFused g) {
                     r -= r * g.stage_dw > u;
                     r += (r + 1) * g.stage_dw <= u;
                     const int off = delta + (hi + r) * g.in_pitch + xs * C;
-                    v[b] = u < total ? __builtin_amdgcn_raw_buffer_load_b32(irsrc, (off & ~3) + 4 * (u - r * g.stage_dw), 0, 0)
-                                     : 0u;
+                    const int at = (off & ~3) + 4 * (u - r * g.stage_dw);
+                    v[b] = u < total ? __builtin_amdgcn_raw_buffer_load_b32(irsrc, at, 0, 0) : 0u;
+                    if constexpr (ALPHA)
+                        vn[b] = delta != 0 && u < total ? __builtin_amdgcn_raw_buffer_load_b32(irsrc, at + 4, 0, 0) : 0u;
                 }
 #pragma unroll
                 for (int b = 0; b < kRsLoadBatch; b++)
-                    if (u0 + b * kRsThreads < total) stage[u0 + b * kRsThreads] = v[b];
+                    if (u0 + b * kRsThreads < total) {
+                        if constexpr (ALPHA)
+                            stage[u0 + b * kRsThreads] = rs_premul_px(__builtin_amdgcn_alignbyte(vn[b], v[b], (unsigned)delta));
+                        else
+                            stage[u0 + b * kRsThreads] = v[b];
+                    }
             }
             __syncthreads();
             for (int j = rl; j < nr; j += RL) {
-                const int pos = ((delta + (hi + j) * g.in_pitch + xs * C) & 3) + hoffb;
+                const int pos = (ALPHA ? 0 : (delta + (hi + j) * g.in_pitch + xs * C) & 3) + hoffb;
                 const uint32_t* srow = stage + j * g.stage_dw + (pos >> 2);
-                const unsigned sh = pos & 3;
+                const unsigned sh = ALPHA ? 0u : pos & 3;   // ALPHA: the staged dwords are pixels
                 uint32_t dw[NE + 1];
 #pragma unroll
-                for (int t = 0; t <= NE; t++) dw[t] = srow[t];
+                for (int t = 0; t <= NE; t++) dw[t] = !ALPHA || t < NE ? srow[t] : 0u;
                 int acc[C];
 #pragma unroll
                 for (int c = 0; c < C; c++) acc[c] = 1 << (kResizePrecision - 1);
@@ -282,7 +355,8 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(RsFused g) {
             const int b0 = dcol * 4;
             if (b0 < valid_bytes) {
                 const int row_off = o * g.out_pitch + x0 * C + b0;
-                const uint32_t packed = rs_clip8(a0) | (rs_clip8(a1) << 8) | (rs_clip8(a2) << 16) | (rs_clip8(a3) << 24);
+                uint32_t packed = rs_clip8(a0) | (rs_clip8(a1) << 8) | (rs_clip8(a2) << 16) | (rs_clip8(a3) << 24);
+                if constexpr (ALPHA) packed = rs_unpremul_px(packed);
                 if (out_aligned && b0 + 4 <= valid_bytes) {
                     __builtin_amdgcn_raw_buffer_store_b32(packed, orsrc, row_off, 0, 0);
                 } else {
@@ -466,6 +540,7 @@ int resize_plan_host(const lanczos_resize_desc* d, int frames, lanczos_resize_pl
 static hipError_t rs_launch_fused(const lanczos_resize_desc* d, const RsFusedPlan& fp, const ResizeAxis* H,
                                   const ResizeAxis* V, const uint8_t* in, uint8_t* out, size_t in_fs, size_t out_fs, int frames,
                                   hipStream_t stream) {
+    const bool alpha = (d->reserved[0] & LANCZOS_RESIZE_ALPHA) != 0;
     RsFused g{};
     g.in_pitch = d->in_w * d->channels;
     g.out_pitch = d->out_w * d->channels;
@@ -485,6 +560,7 @@ static hipError_t rs_launch_fused(const lanczos_resize_desc* d, const RsFusedPla
     if (!launched && fp.K == KB) {                                                                                    \
         if (d->channels == 1) hipLaunchKernelGGL((k_rs_fused<1, KB>), grid, dim3(kRsThreads), fp.lds, stream, g);     \
         else if (d->channels == 3) hipLaunchKernelGGL((k_rs_fused<3, KB>), grid, dim3(kRsThreads), fp.lds, stream, g); \
+        else if (alpha) hipLaunchKernelGGL((k_rs_fused<4, KB, true>), grid, dim3(kRsThreads), fp.lds, stream, g);     \
         else hipLaunchKernelGGL((k_rs_fused<4, KB>), grid, dim3(kRsThreads), fp.lds, stream, g);                      \
         launched = true;                                                                                              \
     }
@@ -497,14 +573,21 @@ static hipError_t rs_launch_fused(const lanczos_resize_desc* d, const RsFusedPla
     return hipSuccess;
 }
 
-static hipError_t rs_launch_pass(bool horizontal, const RsPass& p0, int rows, int frames, hipStream_t stream) {
+// alpha: the LANCZOS_RESIZE_ALPHA kernels (a thread per pixel); `only`: the other pass does not run
+static hipError_t rs_launch_pass(bool horizontal, const RsPass& p0, int rows, int frames, hipStream_t stream,
+                                 bool alpha = false, bool only = false) {
     RsPass p = p0;
     for (int f0 = 0; f0 < frames; f0 += 65535) {
         const int nf = std::min(65535, frames - f0);
         p.src = p0.src + (size_t)f0 * p0.src_fs;
         p.dst = p0.dst + (size_t)f0 * p0.dst_fs;
-        const dim3 grid((p.n_cols + kRsThreads - 1) / kRsThreads, rows, nf);
-        if (horizontal) hipLaunchKernelGGL(k_rs_h, grid, dim3(kRsThreads), 0, stream, p);
+        const int n_threads = alpha ? p.n_cols / 4 : p.n_cols;
+        const dim3 grid((n_threads + kRsThreads - 1) / kRsThreads, rows, nf);
+        if (alpha && horizontal && only) hipLaunchKernelGGL(k_rs_h_alpha<true>, grid, dim3(kRsThreads), 0, stream, p);
+        else if (alpha && horizontal) hipLaunchKernelGGL(k_rs_h_alpha<false>, grid, dim3(kRsThreads), 0, stream, p);
+        else if (alpha && only) hipLaunchKernelGGL(k_rs_v_alpha<true>, grid, dim3(kRsThreads), 0, stream, p);
+        else if (alpha) hipLaunchKernelGGL(k_rs_v_alpha<false>, grid, dim3(kRsThreads), 0, stream, p);
+        else if (horizontal) hipLaunchKernelGGL(k_rs_h, grid, dim3(kRsThreads), 0, stream, p);
         else hipLaunchKernelGGL(k_rs_v, grid, dim3(kRsThreads), 0, stream, p);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
@@ -523,6 +606,7 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_i
     uint8_t* out = (uint8_t*)d_out;
     const bool capturing = stream_capturing(stream);
     const bool need_h = d->in_w != d->out_w, need_v = d->in_h != d->out_h;
+    const bool alpha = (d->reserved[0] & LANCZOS_RESIZE_ALPHA) != 0;
 
     ResizeAxis *H = nullptr, *V = nullptr;
     int rc;
@@ -539,7 +623,7 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_i
     if (fused) {
         e = rs_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream);
         *last_kernel = LANCZOS_KERNEL_RESIZE_FUSED;
-    } else if (!need_h && !need_v) {   // Pillow returns a copy
+    } else if (!need_h && !need_v) {   // Pillow returns a copy (also of RGBA: no premultiply round trip)
         e = hipMemcpy2DAsync(out, out_fs, in, in_fs, in_frame, frames, hipMemcpyDeviceToDevice, stream);
         *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
     } else {
@@ -556,7 +640,7 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_i
             } else {
                 ph.dst = out, ph.dst_fs = out_fs;
             }
-            e = rs_launch_pass(true, ph, d->in_h, frames, stream);
+            e = rs_launch_pass(true, ph, d->in_h, frames, stream, alpha, !need_v);
         }
         if (e == hipSuccess && need_v) {
             pv.src = need_h ? ph.dst : in;
@@ -565,7 +649,7 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_i
             pv.dst = out, pv.dst_fs = out_fs, pv.dst_pitch = (size_t)d->out_w * C;
             pv.n_cols = d->out_w * C, pv.channels = C;
             pv.first = V->first(), pv.count = V->count(), pv.coeffs = V->coeffs(), pv.ksize = V->host.ksize;
-            e = rs_launch_pass(false, pv, d->out_h, frames, stream);
+            e = rs_launch_pass(false, pv, d->out_h, frames, stream, alpha, !need_h);
         }
         *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
     }

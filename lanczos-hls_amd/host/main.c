@@ -4,9 +4,11 @@
  *
  *   lanczos_upscale <in.(png|ppm|pgm)> <out.(png|ppm|pgm)> [--scale N[/D]] [--a A] [--channels C]
  *                   [--exact | --hls] [--device D] [--repeat K]
- *   lanczos_upscale <in> <out> --size WxH [--a A] [--channels C] [--device D] [--repeat K]
+ *   lanczos_upscale <in> <out> --size WxH [--a A] [--channels C | --alpha] [--device D] [--repeat K]
  *                   (resize to any size, downscaling included, through lanczos_resize_host: Pillow's Image.resize with
- *                   LANCZOS, not the reference's model; refuses --scale, --exact, --hls and the multi-device flags)
+ *                   LANCZOS, not the reference's model; refuses --scale, --exact, --hls and the multi-device flags.
+ *                   --alpha: four channels, the fourth straight alpha, resized as Pillow's mode RGBA and written as an
+ *                   RGBA PNG; needs --size, --channels 4 if --channels is given, and a .png output)
  *                   [--devices 0-7 | 0,2,5] [--frames F] [--split frames|rows] [--root]   (several GPUs of one node, plain C:
  *                   the image is replicated into a batch of F frames and the batch -- or every frame's rows -- is split
  *                   over the devices by lanczos_resample_multi_host; the first result frame is written.  --root: the batch
@@ -41,14 +43,14 @@ static double ms_since(const struct timespec* t0) {
 
 /* --size WxH: one frame through lanczos_resize_host */
 static int resize_main(const char* out_path, const uint8_t* img, int width, int height, int channels, int out_w, int out_h,
-                       int a, int device, int repeat) {
+                       int a, int alpha, int device, int repeat) {
     lanczos_resize_desc d;
-    int rc = lanczos_resize_desc_init(&d, width, height, out_w, out_h, channels, a);
+    int rc = lanczos_resize_desc_init_ex(&d, width, height, out_w, out_h, channels, a, alpha ? LANCZOS_RESIZE_ALPHA : 0);
     if (rc != LANCZOS_OK) {
         printf("Cannot resize %i x %i to %i x %i: %s.\n", width, height, out_w, out_h, lanczos_strerror(rc));
         return EXIT_FAILURE;
     }
-    printf("Resize %d x %d -> %d x %d, a = %d\n", width, height, out_w, out_h, a);
+    printf("Resize %d x %d -> %d x %d, a = %d%s\n", width, height, out_w, out_h, a, alpha ? ", straight alpha" : "");
     uint8_t* out = (uint8_t*)malloc((size_t)out_w * out_h * channels);
     lanczos_ctx* ctx = NULL;
     rc = lanczos_create(&ctx, device);
@@ -82,6 +84,7 @@ int main(int argc, char* argv[]) {
     int scale_n = 2, scale_d = 1, a = 3, want_channels = 3, exact = 0, hls = 0, device = 0, repeat = 1;
     int devices[64], n_devices = 0, frames = 1, split = LANCZOS_SPLIT_FRAMES, root = 0;
     int size_w = 0, size_h = 0, have_size = 0, upscale_only = 0; /* upscale_only: a flag --size cannot go with */
+    int alpha = 0, have_channels = 0;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--size") && i + 1 < argc) {
             have_size = 1;
@@ -94,6 +97,9 @@ int main(int argc, char* argv[]) {
             a = atoi(argv[++i]);
         } else if (!strcmp(argv[i], "--channels") && i + 1 < argc) {
             want_channels = atoi(argv[++i]);
+            have_channels = 1;
+        } else if (!strcmp(argv[i], "--alpha")) {
+            alpha = 1;
         } else if (!strcmp(argv[i], "--device") && i + 1 < argc) {
             device = atoi(argv[++i]);
         } else if (!strcmp(argv[i], "--repeat") && i + 1 < argc) {
@@ -135,13 +141,21 @@ int main(int argc, char* argv[]) {
     if (!in_path || !out_path) {
         fprintf(stderr, "usage: %s <in.png|ppm> <out.png|ppm> [--scale N[/D]] [--a A] [--channels C] [--exact|--hls] "
                         "[--device D] [--repeat K] [--devices 0-7|0,2,5] [--frames F] [--split frames|rows] [--root]\n"
-                        "       %s <in.png|ppm> <out.png|ppm> --size WxH [--a A] [--channels C] [--device D] [--repeat K]\n",
+                        "       %s <in.png|ppm> <out.png|ppm> --size WxH [--a A] [--channels C | --alpha] [--device D] "
+                        "[--repeat K]\n",
                 argv[0], argv[0]);
         return EXIT_FAILURE;
     }
     if (have_size && upscale_only) {
         fprintf(stderr, "--size cannot be combined with --scale, --exact, --hls, --devices, --frames, --split or --root\n");
         return EXIT_FAILURE;
+    }
+    if (alpha) {
+        if (!have_size || (have_channels && want_channels != 4) || !ends_with(out_path, ".png")) {
+            fprintf(stderr, "--alpha needs --size, four channels (no --channels other than 4) and a .png output\n");
+            return EXIT_FAILURE;
+        }
+        want_channels = 4;
     }
     if (repeat < 1) repeat = 1;
     printf("Running full TB (%s)\n", lanczos_version());  /* main.cpp:16 */
@@ -153,7 +167,7 @@ int main(int argc, char* argv[]) {
         return EXIT_FAILURE;
     }
     if (have_size) {
-        const int rc = resize_main(out_path, img, width, height, want_channels, size_w, size_h, a, device, repeat);
+        const int rc = resize_main(out_path, img, width, height, want_channels, size_w, size_h, a, alpha, device, repeat);
         lz_image_free(img);
         return rc;
     }

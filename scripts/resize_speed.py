@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """resize_speed.py -- speed of the resize-to-any-size entry (lanczos_resize_device) on one MI355X.
 
-    python scripts/resize_speed.py [--steps K] [--warmup W] [--rounds R] [--only W1,W3] [--pillow]
+    python scripts/resize_speed.py [--steps K] [--warmup W] [--rounds R] [--only W1,W3,A1] [--routes rgbx,three_step]
+                                   [--pillow]
 
 One JSON line per (workload, path).  Discipline as bench.py's: the frames are resident in HBM and the steps cycle through
 enough input / output sets that the inputs of one cycle exceed twice the 256 MiB Infinity Cache (no step finds its input
@@ -13,6 +14,15 @@ of all paths are compared byte for byte.
   mpix_per_s     output pixels per second
   hbm_frac       compulsory bytes (F * (input + output frame bytes)) / step time / 8 TB/s
   kernel         family that served the call (lanczos_last_kernel: 4 fused, 5 two-pass)
+
+A1 and A4 are W1's and W4's shapes with four channels, straight alpha in the last (Pillow's mode RGBA).  They time three
+routes under RESIZE_AUTO, alternating region by region like the paths above:
+  rgbx        the four channels filtered independently (no alpha semantics: the floor of what the kernel costs)
+  alpha       LANCZOS_RESIZE_ALPHA: premultiply and un-premultiply inside the resize kernel
+  three_step  what a caller had to do without the flag: premultiply with torch elementwise operations, the rgbx resize,
+              un-premultiply with torch elementwise operations, the same integer formulas, all on the same stream
+Before timing, frame 0 of `alpha` and of `three_step` are compared byte for byte.  --routes selects routes (a build without
+the flag runs rgbx,three_step).
 
 --pillow adds Pillow's single-core time of one frame of each workload (if Pillow imports; else "not available").
 """
@@ -38,6 +48,11 @@ WORKLOADS = {   # name: (in_w, in_h, out_w, out_h, channels, a, frames)
     "W4": (1920, 1080, 3840, 2160, 3, 3, 32),
     "W5": (3840, 2160, 160, 90, 3, 3, 32),
 }
+RGBA_WORKLOADS = {   # W1's and W4's shapes, four channels
+    "A1": (3840, 2160, 1920, 1080, 4, 3, 32),
+    "A4": (1920, 1080, 3840, 2160, 4, 3, 32),
+}
+ROUTES = ("rgbx", "alpha", "three_step")
 PATHS = {"auto": L.RESIZE_AUTO, "fused": L.RESIZE_FUSED, "two_pass": L.RESIZE_TWO_PASS}
 
 
@@ -109,12 +124,91 @@ def run(name, spec, args, ctx, torch):
     torch.cuda.empty_cache()
 
 
+def premultiply(torch, x):
+    """x: uint8 [N][4], straight alpha -> premultiplied (t = c * A + 128, c' = ((t >> 8) + t) >> 8)."""
+    v = x.to(torch.int32)
+    t = v[:, :3] * v[:, 3:] + 128
+    out = x.clone()
+    out[:, :3] = ((t >> 8) + t) >> 8
+    return out
+
+
+def unpremultiply(torch, y, out):
+    """y: uint8 [N][4] premultiplied -> `out` with straight alpha (A in {0, 255}: copy; else min(255, 255 * c' // A))."""
+    v = y.to(torch.int32)
+    c, a = v[:, :3], v[:, 3:]
+    q = torch.clamp(torch.div(255 * c, a.clamp(min=1), rounding_mode="floor"), max=255)
+    out.copy_(y)
+    out[:, :3] = torch.where((a == 0) | (a == 255), c, q)
+    return out
+
+
+def run_rgba(name, spec, args, ctx, torch):
+    iw, ih, ow, oh, c, a, f = spec
+    in_fb, out_fb = iw * ih * c, ow * oh * c
+    sets = max(2, -(-2 * 256 * 2 ** 20 // (f * in_fb)) + 1)
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    xs = [torch.randint(0, 256, (f * in_fb,), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(sets)]
+    ys = [torch.empty(f * out_fb, dtype=torch.uint8, device="cuda") for _ in range(sets)]
+    tmp = torch.empty(f * out_fb, dtype=torch.uint8, device="cuda")   # three_step: the premultiplied result
+    routes = [r for r in ROUTES if r in args.routes.split(",")]
+    d_rgbx = L.resize_desc(iw, ih, ow, oh, c, a)
+    d_alpha = L.resize_desc(iw, ih, ow, oh, c, a, alpha=True) if "alpha" in routes else None
+    stream = torch.cuda.current_stream()
+    s = stream.cuda_stream
+    ctx.resize_force(L.RESIZE_AUTO)
+
+    def step(route, i):
+        if route == "rgbx":
+            ctx.resize_device(d_rgbx, xs[i].data_ptr(), ys[i].data_ptr(), f, 0, 0, s)
+        elif route == "alpha":
+            ctx.resize_device(d_alpha, xs[i].data_ptr(), ys[i].data_ptr(), f, 0, 0, s)
+        else:
+            pre = premultiply(torch, xs[i].view(-1, 4))
+            ctx.resize_device(d_rgbx, pre.data_ptr(), tmp.data_ptr(), f, 0, 0, s)
+            unpremultiply(torch, tmp.view(-1, 4), ys[i].view(-1, 4))
+
+    first = {}
+    for route in routes:
+        step(route, 0)
+        torch.cuda.synchronize()
+        first[route] = (ys[0][:out_fb].cpu().numpy(), ctx.last_kernel())
+    if "alpha" in first and "three_step" in first and not np.array_equal(first["alpha"][0], first["three_step"][0]):
+        raise SystemExit(f"{name}: the alpha route differs from the three-step route")
+    times = {r: [] for r in routes}
+    for route in routes:
+        for k in range(args.warmup):
+            step(route, k % sets)
+    torch.cuda.synchronize()
+    for r in range(args.rounds):
+        for route in routes:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for k in range(args.steps):
+                step(route, (r * args.steps + k) % sets)
+            e1.record(stream)
+            e1.synchronize()
+            times[route].append(e0.elapsed_time(e1) * 1e3 / args.steps)
+    for route in routes:
+        us = statistics.median(times[route])
+        line = {"workload": name, "shape": f"{iw}x{ih}->{ow}x{oh} C{c} a{a}", "frames": f, "route": route,
+                "kernel": first[route][1], "us_per_step": round(us, 2),
+                "us_all_regions": [round(v, 2) for v in times[route]], "mpix_per_s": round(f * ow * oh / us, 1),
+                "hbm_frac": round(f * (in_fb + out_fb) / (us * 1e-6) / HBM_BPS, 4), "compulsory_bytes": f * (in_fb + out_fb),
+                "input_sets_cycled": sets, "steps": args.steps, "rounds": args.rounds, "lib": os.path.basename(L.LIB_PATH),
+                "measured": True}
+        print(json.dumps(line), flush=True)
+    del xs, ys, tmp
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--only", default="W1,W2,W3,W4,W5")
+    ap.add_argument("--only", default="W1,W2,W3,W4,W5,A1,A4")
+    ap.add_argument("--routes", default=",".join(ROUTES))
     ap.add_argument("--pillow", action="store_true")
     args = ap.parse_args()
     import torch
@@ -122,7 +216,10 @@ def main():
         raise SystemExit("resize_speed.py needs a GPU")
     ctx = L.Context(0)
     for name in args.only.split(","):
-        run(name, WORKLOADS[name], args, ctx, torch)
+        if name in RGBA_WORKLOADS:
+            run_rgba(name, RGBA_WORKLOADS[name], args, ctx, torch)
+        else:
+            run(name, WORKLOADS[name], args, ctx, torch)
     ctx.close()
 
 
