@@ -210,17 +210,34 @@ int lanczos_device_copy(int device, void* dst, const void* src, size_t bytes, in
  *   every input pixel is premultiplied: t = c * A + 128, c' = ((t >> 8) + t) >> 8 for its three colour samples c, alpha A
  *   as it is; both passes run on the premultiplied four channels, alpha filtered like any other channel; every output
  *   pixel with resized alpha A keeps its colour samples if A is 0 or 255 and otherwise gets c = min(255, 255 * c' / A)
- *   (truncating; c' > A occurs where the filter rings).  A resize that changes neither axis is a plain copy, flag or not. */
+ *   (truncating; c' > A occurs where the filter rings).  A resize that changes neither axis is a plain copy, flag or not.
+ *
+ * With LANCZOS_RESIZE_U16 in the flag word the samples are native-endian uint16_t (1, 3 or 4 interleaved channels) and the
+ * result is what Pillow produces in mode I;16, byte for byte, every channel resized as an independent I;16 plane.  Pillow
+ * does not use the fixed-point recipe there.  The tap geometry (first, count, the weights and their normalisation) is the
+ * one above, but the coefficients stay double and one pass computes, per output sample,
+ *   ss = 0.0; for i ascending: ss = ss + (double)sample[first + i] * k[i]    -- an IEEE multiply and an IEEE add, no FMA;
+ *   v = (int)(ss < 0 ? ss - 0.5 : ss + 0.5)                                  -- truncating;
+ *   stored = lo | hi << 8 with lo = clip8(v % 256) (C's %: the sign of v) and hi = clip8(v >> 8), clip8 to 0 .. 255.
+ * That store is Pillow's, quirk included: a negative v stores 0, but a v above 65535 stores 0xFF00 | (v & 255), NOT 65535:
+ * the low byte wraps.  It is no corner: Lanczos overshoots at every hard edge of a full-range image.  The horizontal pass
+ * runs first into a 16-bit intermediate stored that way; a pass whose axis keeps its size is skipped, a resize that changes
+ * neither axis is a plain copy.  The bytes are those of a Pillow build whose compiler does not contract the multiply and
+ * the add into an FMA (the x86-64 wheels; checked against 12.2.0).  Frame strides stay in bytes; base pointers and strides
+ * of a 16-bit request must be even.  Pillow has no 16-bit RGBA: LANCZOS_RESIZE_U16 | LANCZOS_RESIZE_ALPHA is refused. */
 typedef struct lanczos_resize_desc {
     int32_t in_w, in_h;     /* 1..65535 each */
     int32_t out_w, out_h;   /* 1..65535 each, independent of the input size and of each other */
-    int32_t channels;       /* 1, 3 or 4, interleaved, 8-bit samples */
+    int32_t channels;       /* 1, 3 or 4, interleaved; 8-bit samples, 16-bit with LANCZOS_RESIZE_U16 */
     int32_t a;              /* 2, 3 or 4 (3 = Pillow's LANCZOS) */
-    int32_t reserved[2];    /* reserved[0]: flags, 0 or LANCZOS_RESIZE_ALPHA; reserved[1]: must be 0 */
+    int32_t reserved[2];    /* reserved[0]: flags, 0, LANCZOS_RESIZE_ALPHA or LANCZOS_RESIZE_U16; reserved[1]: must be 0 */
 } lanczos_resize_desc;
 
 /* flag of lanczos_resize_desc.reserved[0]: channel 3 is straight alpha (Pillow's RGBA mode); channels must be 4 */
 #define LANCZOS_RESIZE_ALPHA 1
+/* flag of lanczos_resize_desc.reserved[0]: samples are native-endian uint16_t (Pillow's I;16 arithmetic, see above); not
+ * together with LANCZOS_RESIZE_ALPHA */
+#define LANCZOS_RESIZE_U16 4
 
 /* forced path of lanczos_resize_force (tests and A/B runs only) */
 #define LANCZOS_RESIZE_AUTO 0
@@ -232,19 +249,25 @@ int lanczos_resize_desc_init(lanczos_resize_desc* d, int in_w, int in_h, int out
 /* the same with the flag word (lanczos_resize_desc_init gives 0) */
 int lanczos_resize_desc_init_ex(lanczos_resize_desc* d, int in_w, int in_h, int out_w, int out_h, int channels, int a,
                                 int flags);
-/* LANCZOS_ERR_BAD_ARG: size, channels, a, a flag other than LANCZOS_RESIZE_ALPHA, that flag without four channels */
+/* LANCZOS_ERR_BAD_ARG: size, channels, a, a flag word other than 0, LANCZOS_RESIZE_ALPHA or LANCZOS_RESIZE_U16,
+ * LANCZOS_RESIZE_ALPHA without four channels */
 int lanczos_resize_validate(const lanczos_resize_desc* d);
 /* Fixed-point tables of one axis (0 = horizontal, 1 = vertical): output o reads inputs first[o] .. first[o] + count[o] - 1
  * with coeffs[o * ksize + i] (i < count[o]; zero beyond).  *ksize = 2 * ceil(support) + 1.  With first, count and coeffs all
  * NULL only *ksize is returned; otherwise all three must hold out (and out * ksize) elements. */
 int lanczos_resize_taps_host(const lanczos_resize_desc* d, int axis, int32_t* first, int32_t* count, int32_t* coeffs,
                              int* ksize);
+/* The double tables of the 16-bit path, same shapes and rules: first and count are those of lanczos_resize_taps_host,
+ * coeffs[o * ksize + i] is the normalised weight itself.  Neither function looks at LANCZOS_RESIZE_U16. */
+int lanczos_resize_taps_f64_host(const lanczos_resize_desc* d, int axis, int32_t* first, int32_t* count, double* coeffs,
+                                 int* ksize);
 /* Diagnostic: what lanczos_resize_device would launch for this request and `frames` frames under LANCZOS_RESIZE_AUTO (the
  * launch itself plans with the same function).  fused = 0: the two-pass path (one axis keeps its size, more horizontal
  * taps than the widest fused instance has, the LDS row ring does not fit 80 KiB, or a frame of 2^31 bytes or more); the
  * other fields are then 0.  fused = 1: the fused kernel instance with K horizontal taps on a grid of strips x chunks
  * workgroups per frame; a workgroup marches down rows_per_chunk output rows in blocks of 8 with an LDS ring of ring_rows
- * rows and a staging area of stage_rows input rows of stage_dw dwords; lds_bytes is their sum. */
+ * rows and a staging area of stage_rows input rows of stage_dw dwords; lds_bytes is their sum.  A 16-bit request has ring
+ * and staging rows of 2-byte samples and narrower strips, so it meets the 80 KiB condition at smaller reductions. */
 typedef struct lanczos_resize_plan {
     int32_t fused;
     int32_t K, strips, rows_per_chunk, chunks, ring_rows, stage_rows, stage_dw, lds_bytes;

@@ -26,6 +26,7 @@ KERNEL_NONE, KERNEL_GENERIC, KERNEL_FAST, KERNEL_HLS = 0, 1, 2, 3
 KERNEL_RESIZE_FUSED, KERNEL_RESIZE_TWO_PASS = 4, 5
 RESIZE_AUTO, RESIZE_FUSED, RESIZE_TWO_PASS = 0, 1, 2   # lanczos_resize_force
 RESIZE_ALPHA = 1   # flag of lanczos_resize_desc.reserved[0]: channel 3 of 4 is straight alpha (Pillow's RGBA mode)
+RESIZE_U16 = 4     # flag of lanczos_resize_desc.reserved[0]: native-endian uint16 samples (Pillow's I;16 arithmetic)
 
 # every symbol include/lanczos_hip.h declares (tests check the library exports exactly these)
 ABI_SYMBOLS = [
@@ -41,7 +42,8 @@ ABI_SYMBOLS = [
     "lanczos_multi_devices", "lanczos_resample_multi_host", "lanczos_resample_multi_root",
     "lanczos_multi_last_error", "lanczos_multi_exchange_plan", "lanczos_multi_exchange_selftest", "lanczos_device_alloc", "lanczos_device_free",
     "lanczos_device_copy",
-    "lanczos_resize_desc_init", "lanczos_resize_desc_init_ex", "lanczos_resize_validate", "lanczos_resize_taps_host", "lanczos_resize_device",
+    "lanczos_resize_desc_init", "lanczos_resize_desc_init_ex", "lanczos_resize_validate", "lanczos_resize_taps_host",
+    "lanczos_resize_taps_f64_host", "lanczos_resize_device",
     "lanczos_resize_host", "lanczos_resize_force", "lanczos_resize_plan_host",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
@@ -153,6 +155,7 @@ def _lib():
         L.lanczos_resize_desc_init_ex.argtypes = [PRD] + [c_int] * 7
         L.lanczos_resize_validate.argtypes = [PRD]
         L.lanczos_resize_taps_host.argtypes = [PRD, c_int, c_void_p, c_void_p, c_void_p, PI]
+        L.lanczos_resize_taps_f64_host.argtypes = [PRD, c_int, c_void_p, c_void_p, c_void_p, PI]
         L.lanczos_resize_device.argtypes = [c_void_p, PRD, c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p]
         L.lanczos_resize_host.argtypes = [c_void_p, PRD, c_void_p, c_void_p, c_int]
         L.lanczos_resize_force.argtypes = [c_void_p, c_int]
@@ -212,12 +215,16 @@ def taps_host(desc, axis):
     return first, w
 
 
-def resize_desc(in_w, in_h, out_w, out_h, channels, a=3, alpha=False):
+def resize_desc(in_w, in_h, out_w, out_h, channels, a=3, alpha=False, bits=8):
     """A validated lanczos_resize_desc (Pillow's contract: any output size, downscaling included).  alpha: the fourth of
-    four channels is straight alpha, resized as Pillow's mode RGBA (premultiplied inside the kernels)."""
+    four channels is straight alpha, resized as Pillow's mode RGBA (premultiplied inside the kernels).  bits: 8, or 16 for
+    uint16 samples resized as Pillow's mode I;16 (double accumulation, Pillow's wrapping store); not with alpha."""
+    if bits not in (8, 16):
+        raise LanczosError(ERR_BAD_ARG, "resize_desc: bits must be 8 or 16")
     d = ResizeDesc()
-    _check(_lib().lanczos_resize_desc_init_ex(ctypes.byref(d), in_w, in_h, out_w, out_h, channels, a,
-                                              RESIZE_ALPHA if alpha else 0), "lanczos_resize_desc_init_ex")
+    flags = (RESIZE_ALPHA if alpha else 0) | (RESIZE_U16 if bits == 16 else 0)
+    _check(_lib().lanczos_resize_desc_init_ex(ctypes.byref(d), in_w, in_h, out_w, out_h, channels, a, flags),
+           "lanczos_resize_desc_init_ex")
     return d
 
 
@@ -232,6 +239,21 @@ def resize_taps_host(desc, axis):
     coeffs = np.empty((n, ks.value), dtype=np.int32)
     _check(_lib().lanczos_resize_taps_host(ctypes.byref(desc), axis, first.ctypes.data, count.ctypes.data,
                                            coeffs.ctypes.data, ctypes.byref(ks)), "lanczos_resize_taps_host")
+    return first, count, coeffs
+
+
+def resize_taps_f64_host(desc, axis):
+    """Double tables of one axis, what 16-bit requests run on: (first[out] int32, count[out] int32, coeffs[out][ksize]
+    float64); first and count are those of resize_taps_host."""
+    ks = ctypes.c_int()
+    _check(_lib().lanczos_resize_taps_f64_host(ctypes.byref(desc), axis, None, None, None, ctypes.byref(ks)),
+           "lanczos_resize_taps_f64_host")
+    n = desc.out_w if axis == 0 else desc.out_h
+    first = np.empty(n, dtype=np.int32)
+    count = np.empty(n, dtype=np.int32)
+    coeffs = np.empty((n, ks.value), dtype=np.float64)
+    _check(_lib().lanczos_resize_taps_f64_host(ctypes.byref(desc), axis, first.ctypes.data, count.ctypes.data,
+                                               coeffs.ctypes.data, ctypes.byref(ks)), "lanczos_resize_taps_f64_host")
     return first, count, coeffs
 
 
@@ -352,18 +374,19 @@ class Context:
 
     # -- resize to any size (Pillow's contract, lanczos_resize_*)
     def resize(self, img, out_w, out_h, a=3, alpha=False):
-        """img: uint8 [H][W], [H][W][C] or [F][H][W][C] -> the same layout at out_h x out_w, bytes identical to Pillow's
-        Image.resize((out_w, out_h), Image.LANCZOS) for a = 3.  Four channels: mode RGBX (independent channels) by default,
-        mode RGBA (straight alpha in the last channel, premultiplied inside the kernels) with alpha=True; alpha=True with any
-        other channel count raises LanczosError(ERR_BAD_ARG)."""
+        """img: uint8 or uint16 [H][W], [H][W][C] or [F][H][W][C] -> the same layout and dtype at out_h x out_w, bytes
+        identical to Pillow's Image.resize((out_w, out_h), Image.LANCZOS) for a = 3.  Four channels: mode RGBX (independent
+        channels) by default, mode RGBA (straight alpha in the last channel, premultiplied inside the kernels) with
+        alpha=True; alpha=True with any other channel count raises LanczosError(ERR_BAD_ARG).  uint16: every channel as
+        Pillow resizes an I;16 plane (a sum above 65535 stores 0xFF00 | low byte, as Pillow does); not with alpha."""
         img = np.ascontiguousarray(img)
-        if img.dtype != np.uint8 or img.ndim not in (2, 3, 4):
-            raise LanczosError(ERR_BAD_ARG, "resize: expected a uint8 [H][W], [H][W][C] or [F][H][W][C] array")
+        if img.dtype not in (np.uint8, np.uint16) or img.ndim not in (2, 3, 4):
+            raise LanczosError(ERR_BAD_ARG, "resize: expected a uint8 or uint16 [H][W], [H][W][C] or [F][H][W][C] array")
         x = img.reshape(img.shape + (1,)) if img.ndim == 2 else img
         x = x if x.ndim == 4 else x[None]
         f, h, w, c = x.shape
-        d = resize_desc(w, h, out_w, out_h, c, a, alpha)
-        out = np.empty((f, out_h, out_w, c), dtype=np.uint8)
+        d = resize_desc(w, h, out_w, out_h, c, a, alpha, 8 * img.dtype.itemsize)
+        out = np.empty((f, out_h, out_w, c), dtype=img.dtype)
         _check(_lib().lanczos_resize_host(self._h, ctypes.byref(d), x.ctypes.data, out.ctypes.data, f),
                "lanczos_resize_host")
         if img.ndim == 2:

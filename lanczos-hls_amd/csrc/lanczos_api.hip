@@ -1072,6 +1072,23 @@ int lanczos_resize_taps_host(const lanczos_resize_desc* d, int axis, int32_t* fi
     return LANCZOS_OK;
 }
 
+int lanczos_resize_taps_f64_host(const lanczos_resize_desc* d, int axis, int32_t* first, int32_t* count, double* coeffs,
+                                 int* ksize) {
+    int rc = lz::resize_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    if (!ksize || (axis != 0 && axis != 1)) return LANCZOS_ERR_BAD_ARG;
+    const int in_n = axis == 0 ? d->in_w : d->in_h, out_n = axis == 0 ? d->out_w : d->out_h;
+    *ksize = lz::resize_ksize(in_n, out_n, d->a);
+    if (!first && !count && !coeffs) return LANCZOS_OK;
+    if (!first || !count || !coeffs) return LANCZOS_ERR_BAD_ARG;
+    lz::ResizeAxisHost t;
+    lz::resize_build_axis(in_n, out_n, d->a, &t, true);
+    memcpy(first, t.first.data(), t.first.size() * sizeof(int32_t));
+    memcpy(count, t.count.data(), t.count.size() * sizeof(int32_t));
+    memcpy(coeffs, t.coeffs64.data(), t.coeffs64.size() * sizeof(double));
+    return LANCZOS_OK;
+}
+
 int lanczos_resize_plan_host(const lanczos_resize_desc* d, int frames, lanczos_resize_plan* out) {
     int rc = lz::resize_validate(d);
     if (rc != LANCZOS_OK) return rc;

@@ -15,6 +15,9 @@
 // read the frame and divide alpha out where they write it (lanczos_alpha.hpp), k_rs_fused<4, K, true> and k_rs_h_alpha /
 // k_rs_v_alpha; tables, plan and scratch are those of the same request without the flag.
 //
+// LANCZOS_RESIZE_U16 (16-bit samples, Pillow's I;16): the same tap geometry with double coefficients and Pillow's double
+// accumulation; tables, cache, planning and dispatch are here, the kernels in lanczos_resize16.hip.
+//
 // Arithmetic is Pillow's and exact by construction: acc = 2^21 + sum(sample * coeff) in int32 with 24-bit multiplies
 // (|coeff| < 2^23 and 255 * sum|coeff| + 2^21 < 2^31, checked when a table is built), result clamp(acc >> 22, 0, 255).
 #include "lanczos_resize.hpp"
@@ -37,7 +40,8 @@ int resize_validate(const lanczos_resize_desc* d) {
         if (s < 1 || s > kResizeMaxSize) return LANCZOS_ERR_BAD_ARG;
     if (d->channels != 1 && d->channels != 3 && d->channels != 4) return LANCZOS_ERR_BAD_ARG;
     if (d->a < 2 || d->a > 4) return LANCZOS_ERR_BAD_ARG;
-    if ((d->reserved[0] & ~LANCZOS_RESIZE_ALPHA) != 0 || d->reserved[1] != 0) return LANCZOS_ERR_BAD_ARG;
+    if ((d->reserved[0] & ~(LANCZOS_RESIZE_ALPHA | LANCZOS_RESIZE_U16)) != 0 || d->reserved[1] != 0) return LANCZOS_ERR_BAD_ARG;
+    if ((d->reserved[0] & LANCZOS_RESIZE_ALPHA) && (d->reserved[0] & LANCZOS_RESIZE_U16)) return LANCZOS_ERR_BAD_ARG;
     if ((d->reserved[0] & LANCZOS_RESIZE_ALPHA) && d->channels != 4) return LANCZOS_ERR_BAD_ARG;
     return LANCZOS_OK;
 }
@@ -59,7 +63,7 @@ int resize_ksize(int in_n, int out_n, int a) {
     return (int)ceil(a * fs) * 2 + 1;
 }
 
-bool resize_build_axis(int in_n, int out_n, int a, ResizeAxisHost* t) {
+bool resize_build_axis(int in_n, int out_n, int a, ResizeAxisHost* t, bool f64) {
     const double scale = (double)in_n / out_n;
     const double fs = scale > 1.0 ? scale : 1.0;
     const double support = a * fs;
@@ -68,7 +72,8 @@ bool resize_build_axis(int in_n, int out_n, int a, ResizeAxisHost* t) {
     t->in_n = in_n, t->out_n = out_n, t->a = a, t->ksize = ksize;
     t->first.assign(out_n, 0);
     t->count.assign(out_n, 0);
-    t->coeffs.assign((size_t)out_n * ksize, 0);
+    t->coeffs.assign(f64 ? 0 : (size_t)out_n * ksize, 0);
+    t->coeffs64.assign(f64 ? (size_t)out_n * ksize : 0, 0.0);
     std::vector<double> w(ksize);
     bool ok = true;
     for (int o = 0; o < out_n; o++) {
@@ -83,6 +88,13 @@ bool resize_build_axis(int in_n, int out_n, int a, ResizeAxisHost* t) {
             w[i] = rs_filter((i + xmin - center + 0.5) * ss, a);
             ww += w[i];
         }
+        t->first[o] = xmin;
+        t->count[o] = n;
+        if (f64) {
+            double* k64 = &t->coeffs64[(size_t)o * ksize];
+            for (int i = 0; i < n; i++) k64[i] = ww != 0.0 ? w[i] / ww : w[i];
+            continue;
+        }
         int32_t* k = &t->coeffs[(size_t)o * ksize];
         long long abs_sum = 0;
         for (int i = 0; i < n; i++) {
@@ -92,20 +104,15 @@ bool resize_build_axis(int in_n, int out_n, int a, ResizeAxisHost* t) {
             abs_sum += k[i] < 0 ? -(long long)k[i] : k[i];
         }
         if (255 * abs_sum + (1 << (kResizePrecision - 1)) >= (1ll << 31)) ok = false;
-        t->first[o] = xmin;
-        t->count[o] = n;
     }
     return ok;
 }
 
 // ---- kernels -----------------------------------------------------------------------------------------------------
 
-constexpr int kRsThreads = 256;
-constexpr int kRsOB = 8;                 // output rows per march step of the fused kernel
 constexpr int kRsFusedMaxLds = 80 * 1024;   // at least two fused workgroups per CU (160 KiB of LDS)
 constexpr int kRsRowsPerChunkMin = 4 * kRsOB;
 constexpr int kRsTargetWgs = 2048;
-constexpr int kRsLoadBatch = 16;   // staging loads in flight per thread
 
 __device__ __forceinline__ int rs_mad(int sample, int coeff, int acc) { return __mul24(sample, coeff) + acc; }
 __device__ __forceinline__ uint32_t rs_clip8(int acc) { return (uint32_t)min(max(acc >> kResizePrecision, 0), 255); }
@@ -216,7 +223,7 @@ struct RsFused {
 
 template <int C>
 struct RsStrip {
-    static constexpr int SW = C == 4 ? 64 : 256;   // output pixels per strip: ring rows of 256 / 768 / 256 bytes
+    static constexpr int SW = rs_strip_width(C, false);   // output pixels per strip
     static constexpr int RL = kRsThreads / SW;    // input rows per horizontal round
     static constexpr int RDW = SW * C / 4;        // ring row in dwords
     static constexpr int WPR = RDW / 64;          // waves per ring row in the vertical pass
@@ -411,10 +418,10 @@ ResizeState::~ResizeState() {   // the owner has drained the device
 // The tables of one axis shape, built and uploaded on first use.  The upload is eager: a copy on the private stream and a
 // wait for it, so an entry is valid from the moment it is cached -- also when the caller's stream is being captured
 // (a copy queued on it would only run when the graph is replayed, perhaps never).
-static int rs_axis(ResizeState* st, int in_n, int out_n, int a, ResizeAxis** out, int* last_hip) {
+static int rs_axis(ResizeState* st, int in_n, int out_n, int a, bool f64, ResizeAxis** out, int* last_hip) {
     for (size_t i = 0; i < st->axes.size(); i++) {
         ResizeAxis* ax = st->axes[i];
-        if (ax->key[0] == in_n && ax->key[1] == out_n && ax->key[2] == a) {
+        if (ax->key[0] == in_n && ax->key[1] == out_n && ax->key[2] == a && ax->key[3] == (int)f64) {
             st->axes.erase(st->axes.begin() + i);
             st->axes.push_back(ax);   // most recent last
             *out = ax;
@@ -424,16 +431,17 @@ static int rs_axis(ResizeState* st, int in_n, int out_n, int a, ResizeAxis** out
     st->retired.reap(false);
     ResizeAxis* ax = new (std::nothrow) ResizeAxis();
     if (!ax) return LANCZOS_ERR_NOMEM;
-    ax->key[0] = in_n, ax->key[1] = out_n, ax->key[2] = a;
-    if (!resize_build_axis(in_n, out_n, a, &ax->host)) {
+    ax->key[0] = in_n, ax->key[1] = out_n, ax->key[2] = a, ax->key[3] = (int)f64;
+    if (!resize_build_axis(in_n, out_n, a, &ax->host, f64)) {
         delete ax;
         return LANCZOS_ERR_UNSUPPORTED;
     }
     const ResizeAxisHost& h = ax->host;
-    std::vector<int32_t> block((size_t)2 * h.out_n + h.coeffs.size());
+    std::vector<int32_t> block((size_t)2 * h.out_n + h.coeffs.size() + 2 * h.coeffs64.size());
     memcpy(block.data(), h.first.data(), (size_t)h.out_n * 4);
     memcpy(block.data() + h.out_n, h.count.data(), (size_t)h.out_n * 4);
-    memcpy(block.data() + 2 * (size_t)h.out_n, h.coeffs.data(), h.coeffs.size() * 4);
+    if (f64) memcpy(block.data() + 2 * (size_t)h.out_n, h.coeffs64.data(), h.coeffs64.size() * 8);
+    else memcpy(block.data() + 2 * (size_t)h.out_n, h.coeffs.data(), h.coeffs.size() * 4);
     hipError_t e = hipSuccess;
     if (!st->upload) e = hipStreamCreateWithFlags(&st->upload, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipMalloc((void**)&ax->dev, block.size() * 4);
@@ -485,12 +493,13 @@ static int rs_scratch(ResizeState* st, size_t bytes, hipStream_t stream, bool ca
 bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H, const ResizeAxisHost& V, int frames,
                    RsFusedPlan* fp) {
     if (d->in_w == d->out_w || d->in_h == d->out_h) return false;   // one pass only: nothing to fuse
-    if ((long long)d->in_w * d->in_h * d->channels + 4 >= (1ll << 31)) return false;   // 32-bit buffer offsets
-    if ((long long)d->out_w * d->out_h * d->channels >= (1ll << 31)) return false;
-    fp->K = rs_bucket(H.ksize);
+    const bool u16 = resize_u16(d);
+    const int C = d->channels * (u16 ? 2 : 1);   // bytes per pixel
+    if ((long long)d->in_w * d->in_h * C + 4 >= (1ll << 31)) return false;   // 32-bit buffer offsets
+    if ((long long)d->out_w * d->out_h * C >= (1ll << 31)) return false;
+    fp->K = u16 ? rs16_bucket(H.ksize) : rs_bucket(H.ksize);
     if (!fp->K) return false;
-    const int C = d->channels;
-    const int SW = C == 4 ? RsStrip<4>::SW : RsStrip<1>::SW;
+    const int SW = rs_strip_width(d->channels, u16);
     const int NE = (fp->K * C + 3) / 4;
     fp->strips = (d->out_w + SW - 1) / SW;
     int span_dw = 0;
@@ -526,7 +535,8 @@ int resize_plan_host(const lanczos_resize_desc* d, int frames, lanczos_resize_pl
     memset(out, 0, sizeof(*out));
     if (d->in_w == d->out_w || d->in_h == d->out_h) return LANCZOS_OK;   // as resize_device: no table for such an axis
     ResizeAxisHost H, V;
-    if (!resize_build_axis(d->in_w, d->out_w, d->a, &H) || !resize_build_axis(d->in_h, d->out_h, d->a, &V))
+    const bool u16 = resize_u16(d);
+    if (!resize_build_axis(d->in_w, d->out_w, d->a, &H, u16) || !resize_build_axis(d->in_h, d->out_h, d->a, &V, u16))
         return LANCZOS_ERR_UNSUPPORTED;
     RsFusedPlan fp;
     if (!rs_fused_plan(d, H, V, frames, &fp)) return LANCZOS_OK;
@@ -598,10 +608,13 @@ static hipError_t rs_launch_pass(bool horizontal, const RsPass& p0, int rows, in
 int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_in, void* d_out, int frames,
                   size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream, int* last_kernel, int* last_hip) {
     const int C = d->channels;
-    const size_t in_frame = (size_t)d->in_w * d->in_h * C, out_frame = (size_t)d->out_w * d->out_h * C;
+    const bool u16 = resize_u16(d);
+    const size_t B = u16 ? 2 : 1;   // bytes per sample
+    const size_t in_frame = (size_t)d->in_w * d->in_h * C * B, out_frame = (size_t)d->out_w * d->out_h * C * B;
     const size_t in_fs = in_frame_stride ? in_frame_stride : in_frame;
     const size_t out_fs = out_frame_stride ? out_frame_stride : out_frame;
     if (in_fs < in_frame || out_fs < out_frame) return LANCZOS_ERR_BAD_ARG;
+    if (u16 && (((uintptr_t)d_in | (uintptr_t)d_out | in_fs | out_fs) & 1) != 0) return LANCZOS_ERR_BAD_ARG;
     const uint8_t* in = (const uint8_t*)d_in;
     uint8_t* out = (uint8_t*)d_out;
     const bool capturing = stream_capturing(stream);
@@ -610,8 +623,8 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_i
 
     ResizeAxis *H = nullptr, *V = nullptr;
     int rc;
-    if (need_h && (rc = rs_axis(st, d->in_w, d->out_w, d->a, &H, last_hip)) != LANCZOS_OK) return rc;
-    if (need_v && (rc = rs_axis(st, d->in_h, d->out_h, d->a, &V, last_hip)) != LANCZOS_OK) return rc;
+    if (need_h && (rc = rs_axis(st, d->in_w, d->out_w, d->a, u16, &H, last_hip)) != LANCZOS_OK) return rc;
+    if (need_v && (rc = rs_axis(st, d->in_h, d->out_h, d->a, u16, &V, last_hip)) != LANCZOS_OK) return rc;
     for (ResizeAxis* ax : {H, V})
         if (ax && !capturing) note_stream(ax->streams, stream);
 
@@ -621,10 +634,30 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_i
     const bool fused = fused_ok && st->force != LANCZOS_RESIZE_TWO_PASS;
     hipError_t e = hipSuccess;
     if (fused) {
-        e = rs_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream);
+        e = u16 ? rs16_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream)
+                : rs_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream);
         *last_kernel = LANCZOS_KERNEL_RESIZE_FUSED;
     } else if (!need_h && !need_v) {   // Pillow returns a copy (also of RGBA: no premultiply round trip)
         e = hipMemcpy2DAsync(out, out_fs, in, in_fs, in_frame, frames, hipMemcpyDeviceToDevice, stream);
+        *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
+    } else if (u16) {
+        const uint8_t* mid = in;   // what the vertical pass reads
+        size_t mid_fs = in_fs;
+        if (need_h) {
+            uint8_t* dst = out;
+            size_t dst_fs = out_fs;
+            if (need_v) {
+                rc = rs_scratch(st, (size_t)frames * d->in_h * d->out_w * C * 2, stream, capturing, last_hip);
+                if (rc != LANCZOS_OK) return rc;
+                dst = (uint8_t*)st->scratch, dst_fs = (size_t)d->in_h * d->out_w * C * 2;
+            }
+            e = rs16_launch_pass(true, H, C, in, in_fs, (size_t)d->in_w * C, dst, dst_fs, (size_t)d->out_w * C, d->out_w * C,
+                                 d->in_h, frames, stream);
+            mid = dst, mid_fs = dst_fs;
+        }
+        if (e == hipSuccess && need_v)
+            e = rs16_launch_pass(false, V, C, mid, mid_fs, (size_t)d->out_w * C, out, out_fs, (size_t)d->out_w * C,
+                                 d->out_w * C, d->out_h, frames, stream);
         *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
     } else {
         RsPass ph{}, pv{};
@@ -674,8 +707,10 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_i
 
 int resize_host(ResizeState* st, const lanczos_resize_desc* d, const void* in, void* out, int frames, hipStream_t stream,
                 int* last_kernel, int* last_hip) {
-    const size_t in_bytes = (size_t)d->in_w * d->in_h * d->channels * frames;
-    const size_t out_bytes = (size_t)d->out_w * d->out_h * d->channels * frames;
+    const size_t B = resize_u16(d) ? 2 : 1;
+    if (B == 2 && (((uintptr_t)in | (uintptr_t)out) & 1) != 0) return LANCZOS_ERR_BAD_ARG;
+    const size_t in_bytes = (size_t)d->in_w * d->in_h * d->channels * B * frames;
+    const size_t out_bytes = (size_t)d->out_w * d->out_h * d->channels * B * frames;
     auto grow = [&](void** p, size_t* have, size_t need) -> hipError_t {
         if (*have >= need) return hipSuccess;
         if (*p) {

@@ -1,6 +1,6 @@
 // lanczos_resize.hpp -- resize to any size with Pillow's Lanczos contract (include/lanczos_hip.h, lanczos_resize_*):
 // host tap tables, their per-context cache, and the entry points lanczos_api.hip forwards to.  The kernels live in
-// lanczos_resize.hip.
+// lanczos_resize.hip; those of 16-bit requests (LANCZOS_RESIZE_U16, double coefficients) in lanczos_resize16.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,9 +23,21 @@ int resize_validate(const lanczos_resize_desc* d);
 struct ResizeAxisHost {
     int in_n = 0, out_n = 0, a = 0, ksize = 0;
     std::vector<int32_t> first, count, coeffs;   // [out_n], [out_n], [out_n][ksize]
+    std::vector<double> coeffs64;                // [out_n][ksize]: the 16-bit path's tables, which have no `coeffs`
 };
 int resize_ksize(int in_n, int out_n, int a);
-bool resize_build_axis(int in_n, int out_n, int a, ResizeAxisHost* t);
+// f64: the tables of the 16-bit path instead -- the normalised weights as they are (Pillow's precompute_coeffs alone),
+// in coeffs64; always true.
+bool resize_build_axis(int in_n, int out_n, int a, ResizeAxisHost* t, bool f64 = false);
+
+inline bool resize_u16(const lanczos_resize_desc* d) { return (d->reserved[0] & LANCZOS_RESIZE_U16) != 0; }
+
+// launch geometry both translation units share
+constexpr int kRsThreads = 256;
+constexpr int kRsOB = 8;             // output rows per march step of the fused kernels
+constexpr int kRsLoadBatch = 16;     // staging loads in flight per thread
+// output pixels per strip of the fused kernels: ring rows of 256 / 768 / 256 bytes (8-bit), 256 / 768 / 512 bytes (16-bit)
+constexpr int rs_strip_width(int channels, bool u16) { return channels == 4 ? 64 : u16 ? 128 : 256; }
 
 // The fused kernel's launch shape for a request (false: it cannot run it).  H and V are the tables of the two axes, both of
 // which change size.  lanczos_resize_device plans with it; lanczos_resize_plan_host reports what it returns.
@@ -37,14 +49,16 @@ bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H, const 
                    RsFusedPlan* fp);
 int resize_plan_host(const lanczos_resize_desc* d, int frames, lanczos_resize_plan* out);
 
-// One axis shape on the device: first | count | coeffs in one block.
+// One axis shape on the device: first | count | coeffs in one block (int32 coefficients, or double ones for 16-bit samples:
+// the two int32 arrays in front of them keep those 8-byte aligned).
 struct ResizeAxis {
-    int key[3] = {0, 0, 0};   // in, out, a
+    int key[4] = {0, 0, 0, 0};   // in, out, a, double coefficients
     ResizeAxisHost host;
     int32_t* dev = nullptr;
     const int32_t* first() const { return dev; }
     const int32_t* count() const { return dev + host.out_n; }
     const int32_t* coeffs() const { return dev + 2 * (size_t)host.out_n; }
+    const double* coeffs64() const { return (const double*)(dev + 2 * (size_t)host.out_n); }
     std::vector<hipStream_t> streams;   // streams whose launches read this block (retirement)
 };
 
@@ -55,7 +69,7 @@ struct ResizeState {
     RetireList retired;
     hipStream_t upload = nullptr;            // private stream of the eager table uploads
     int force = LANCZOS_RESIZE_AUTO;
-    // intermediate of the two-pass path (in_h x out_w x C per frame)
+    // intermediate of the two-pass path (in_h x out_w x C samples per frame)
     void* scratch = nullptr;
     size_t scratch_bytes = 0;
     bool scratch_captured = false;           // used by a captured launch: a live graph may still hold it
@@ -73,5 +87,16 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_i
                   size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream, int* last_kernel, int* last_hip);
 int resize_host(ResizeState* st, const lanczos_resize_desc* d, const void* in, void* out, int frames, hipStream_t stream,
                 int* last_kernel, int* last_hip);
+
+// 16-bit requests (lanczos_resize16.hip): the tap count of the smallest fused instance that holds ksize (0: none), and the
+// launches.
+// Pitches are those of tightly packed rows; frame strides in bytes.
+int rs16_bucket(int ksize);
+hipError_t rs16_launch_fused(const lanczos_resize_desc* d, const RsFusedPlan& fp, const ResizeAxis* H, const ResizeAxis* V,
+                             const uint8_t* in, uint8_t* out, size_t in_fs, size_t out_fs, int frames, hipStream_t stream);
+// one pass of the two-pass path over `rows` rows of `n_cols` samples: src / dst row pitches in samples
+hipError_t rs16_launch_pass(bool horizontal, const ResizeAxis* ax, int channels, const uint8_t* src, size_t src_fs,
+                            size_t src_pitch, uint8_t* dst, size_t dst_fs, size_t dst_pitch, int n_cols, int rows, int frames,
+                            hipStream_t stream);
 
 }  // namespace lz

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """resize_speed.py -- speed of the resize-to-any-size entry (lanczos_resize_device) on one MI355X.
 
-    python scripts/resize_speed.py [--steps K] [--warmup W] [--rounds R] [--only W1,W3,A1] [--routes rgbx,three_step]
+    python scripts/resize_speed.py [--steps K] [--warmup W] [--rounds R] [--only W1,W3,A1,U1] [--routes rgbx,three_step]
                                    [--pillow]
 
 One JSON line per (workload, path).  Discipline as bench.py's: the frames are resident in HBM and the steps cycle through
@@ -24,7 +24,11 @@ routes under RESIZE_AUTO, alternating region by region like the paths above:
 Before timing, frame 0 of `alpha` and of `three_step` are compared byte for byte.  --routes selects routes (a build without
 the flag runs rgbx,three_step).
 
---pillow adds Pillow's single-core time of one frame of each workload (if Pillow imports; else "not available").
+U1 and U4 are W1's and W4's shapes with 16-bit samples (LANCZOS_RESIZE_U16, Pillow's mode I;16): the same three paths, the
+same discipline, twice the compulsory bytes.
+
+--pillow adds Pillow's single-core time of one frame of each workload (if Pillow imports; else "not available"); for U1 and
+U4 that is the time of one I;16 plane (a frame has three).
 """
 import argparse
 import json
@@ -48,6 +52,10 @@ WORKLOADS = {   # name: (in_w, in_h, out_w, out_h, channels, a, frames)
     "W4": (1920, 1080, 3840, 2160, 3, 3, 32),
     "W5": (3840, 2160, 160, 90, 3, 3, 32),
 }
+U16_WORKLOADS = {   # W1's and W4's shapes, 16-bit samples
+    "U1": (3840, 2160, 1920, 1080, 3, 3, 32),
+    "U4": (1920, 1080, 3840, 2160, 3, 3, 32),
+}
 RGBA_WORKLOADS = {   # W1's and W4's shapes, four channels
     "A1": (3840, 2160, 1920, 1080, 4, 3, 32),
     "A4": (1920, 1080, 3840, 2160, 4, 3, 32),
@@ -56,15 +64,15 @@ ROUTES = ("rgbx", "alpha", "three_step")
 PATHS = {"auto": L.RESIZE_AUTO, "fused": L.RESIZE_FUSED, "two_pass": L.RESIZE_TWO_PASS}
 
 
-def run(name, spec, args, ctx, torch):
+def run(name, spec, args, ctx, torch, bits=8):
     iw, ih, ow, oh, c, a, f = spec
-    in_fb, out_fb = iw * ih * c, ow * oh * c
+    in_fb, out_fb = iw * ih * c * bits // 8, ow * oh * c * bits // 8   # frame bytes
     step_in = f * in_fb
     sets = max(2, -(-2 * 256 * 2 ** 20 // step_in) + 1)
     gen = torch.Generator(device="cuda").manual_seed(7)
     xs = [torch.randint(0, 256, (f * in_fb,), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(sets)]
     ys = [torch.empty(f * out_fb, dtype=torch.uint8, device="cuda") for _ in range(sets)]
-    d = L.resize_desc(iw, ih, ow, oh, c, a)
+    d = L.resize_desc(iw, ih, ow, oh, c, a, bits=bits)
     stream = torch.cuda.current_stream()
     s = stream.cuda_stream
     paths, ref = {}, None
@@ -103,23 +111,28 @@ def run(name, spec, args, ctx, torch):
     ctx.resize_force(L.RESIZE_AUTO)
     for pn, (p, fam) in paths.items():
         us = statistics.median(times[pn])
-        line = {"workload": name, "shape": f"{iw}x{ih}->{ow}x{oh} C{c} a{a}", "frames": f, "path": pn, "kernel": fam,
+        line = {"workload": name, "shape": f"{iw}x{ih}->{ow}x{oh} C{c} a{a} u{bits}", "frames": f, "path": pn, "kernel": fam,
                 "us_per_step": round(us, 2), "us_all_regions": [round(v, 2) for v in times[pn]],
                 "mpix_per_s": round(f * ow * oh / us, 1), "hbm_frac": round(f * (in_fb + out_fb) / (us * 1e-6) / HBM_BPS, 4),
                 "compulsory_bytes": f * (in_fb + out_fb), "input_sets_cycled": sets, "steps": args.steps,
-                "rounds": args.rounds, "measured": True}
+                "rounds": args.rounds, "lib": os.path.basename(L.LIB_PATH), "measured": True}
         print(json.dumps(line), flush=True)
     if args.pillow:
+        key = "pillow_single_core_ms_per_frame" if bits == 8 else "pillow_single_core_ms_per_I16_plane"
         try:
             from PIL import Image
-            img = Image.frombytes("RGB", (iw, ih), xs[0][:in_fb].cpu().numpy().tobytes())
+            raw = xs[0][:in_fb].cpu().numpy()
+            if bits == 8:
+                img = Image.frombytes("RGB", (iw, ih), raw.tobytes())
+            else:
+                img = Image.fromarray(np.ascontiguousarray(raw.view(np.uint16).reshape(ih, iw, c)[:, :, 0]))
             img.resize((ow, oh), Image.LANCZOS)
             t0 = time.perf_counter()
             img.resize((ow, oh), Image.LANCZOS)
             ms = (time.perf_counter() - t0) * 1e3
-            print(json.dumps({"workload": name, "pillow_single_core_ms_per_frame": round(ms, 2), "measured": True}))
+            print(json.dumps({"workload": name, key: round(ms, 2), "measured": True}))
         except ImportError:
-            print(json.dumps({"workload": name, "pillow_single_core_ms_per_frame": "not available"}))
+            print(json.dumps({"workload": name, key: "not available"}))
     del xs, ys
     torch.cuda.empty_cache()
 
@@ -207,7 +220,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--only", default="W1,W2,W3,W4,W5,A1,A4")
+    ap.add_argument("--only", default="W1,W2,W3,W4,W5,A1,A4,U1,U4")
     ap.add_argument("--routes", default=",".join(ROUTES))
     ap.add_argument("--pillow", action="store_true")
     args = ap.parse_args()
@@ -218,6 +231,8 @@ def main():
     for name in args.only.split(","):
         if name in RGBA_WORKLOADS:
             run_rgba(name, RGBA_WORKLOADS[name], args, ctx, torch)
+        elif name in U16_WORKLOADS:
+            run(name, U16_WORKLOADS[name], args, ctx, torch, bits=16)
         else:
             run(name, WORKLOADS[name], args, ctx, torch)
     ctx.close()
