@@ -286,6 +286,83 @@ int lanczos_resize_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const vo
 /* LANCZOS_RESIZE_AUTO / _FUSED / _TWO_PASS: tests and A/B runs only (lanczos_force_kernel does not affect resizes). */
 int lanczos_resize_force(lanczos_ctx* ctx, int path);
 
+/* ---- resize from a source box and with reducing_gap (the other two arguments of Pillow's Image.resize) ----
+ * The _ex entry points take a lanczos_resize_opts beside the descriptor; NULL is the call without it, and the entry points
+ * above forward to them with NULL.
+ *
+ * box = (x0, y0, x1, y1) in source pixels, fractions allowed, 0 <= x0 < x1 <= in_w and 0 <= y0 < y1 <= in_h.  Per axis with
+ * (b0, b1): both are rounded to float (Pillow's C takes float box[4]) and their difference is taken in float,
+ *   scale = (double)(float)(b1f - b0f) / out,  centre = (double)b0f + (o + 0.5) * scale,
+ * and everything else -- fs, support, ksize, first = max(int(centre - support + 0.5), 0), the end min(int(centre + support
+ * + 0.5), in), weights, normalisation, the 22-bit rounding or the double tables of 16-bit requests -- is the recipe above.
+ * first indexes the WHOLE source axis and is clipped to the whole source, not to the box: pixels outside the box contribute
+ * near its edges.  A pass runs iff out != in || b0f != 0 || b1f != in, so a sub-pixel shift at equal size runs the pass; with
+ * both axes idle the call is the plain copy.  Every sample type takes a box (8-bit, LANCZOS_RESIZE_ALPHA, LANCZOS_RESIZE_U16).
+ * The two-pass path produces only the intermediate rows the vertical taps read, and sizes its scratch by them.
+ *
+ * reducing_gap = g (0 = none, otherwise g >= 1; below 1 or NaN: LANCZOS_ERR_BAD_ARG), as Image.resize(..., reducing_gap=g):
+ * all in double on the caller's box, before anything is rounded to float,
+ *   fx = int((x1 - x0) / out_w / g) or 1, fy likewise; both 1: the plain box resize.  Otherwise, with s = a - 0.5,
+ *   sx = s * (x1 - x0) / out_w, sy likewise, the safe box is
+ *   rb = (max(0, int(x0 - sx)), max(0, int(y0 - sy)), min(in_w, ceil(x1 + sx)), min(in_h, ceil(y1 + sy)));
+ *   the source is reduced by (fx, fy) over rb (lanczos_reduce_*, below) and the REDUCED frame is resized with the box
+ *   ((x0 - rb0) / fx, (y0 - rb1) / fy, (x1 - rb0) / fx, (y1 - rb1) / fy) (divided in double, rounded to float after).
+ * The result is Pillow's for the same arguments; it is NOT the resize without a gap (it differs from it in general).
+ * Pillow silently drops reducing_gap in mode RGBA and raises for I;16, so neither has an oracle: a gap together with
+ * LANCZOS_RESIZE_ALPHA or LANCZOS_RESIZE_U16 is LANCZOS_ERR_BAD_ARG.  fx * fy >= 65536: LANCZOS_ERR_UNSUPPORTED.
+ * The reduced frames live in context scratch under the rules of the two-pass intermediate (one stream at a time per context;
+ * a captured launch pins the block; a captured graph must not outlive its context). */
+typedef struct lanczos_resize_opts {
+    double box[4];        /* x0, y0, x1, y1 */
+    double reducing_gap;  /* 0 = none */
+    int32_t reserved[4];  /* must be 0 */
+} lanczos_resize_opts;
+/* the full box of `d` and no gap: the request without options */
+int lanczos_resize_opts_init(lanczos_resize_opts* o, const lanczos_resize_desc* d);
+/* as lanczos_resize_taps_host / _taps_f64_host.  With a gap that reduces, the tables are those of the inner resize (of the
+ * reduced frame with the box after reduction): *ksize and the first[] range follow the reduced axis. */
+int lanczos_resize_taps_host_ex(const lanczos_resize_desc* d, const lanczos_resize_opts* o, int axis, int32_t* first,
+                                int32_t* count, int32_t* coeffs, int* ksize);
+int lanczos_resize_taps_f64_host_ex(const lanczos_resize_desc* d, const lanczos_resize_opts* o, int axis, int32_t* first,
+                                    int32_t* count, double* coeffs, int* ksize);
+/* Diagnostic: how a request with options resolves (the launch resolves with the same function).  fx = fy = 1: no reduction;
+ * safe_box is then (0, 0, in_w, in_h), the reduced size the source's and inner_box the caller's box.  pass_h / pass_v: whether
+ * the inner resize runs that pass.  mid_row0 / mid_rows: the rows of the (reduced) source the horizontal pass of the two-pass
+ * path produces, which is what its scratch holds per frame (mid_rows x out_w pixels); 0 / 0 unless both passes run.  inner:
+ * the plan of the inner resize, as lanczos_resize_plan_host reports it. */
+typedef struct lanczos_resize_plan_ex {
+    int32_t fx, fy;
+    int32_t safe_box[4];
+    int32_t reduced_w, reduced_h;
+    int32_t pass_h, pass_v;
+    int32_t mid_row0, mid_rows;
+    double inner_box[4];
+    lanczos_resize_plan inner;
+} lanczos_resize_plan_ex;
+int lanczos_resize_plan_host_ex(const lanczos_resize_desc* d, const lanczos_resize_opts* o, int frames,
+                                lanczos_resize_plan_ex* out);
+int lanczos_resize_device_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* d_in,
+                             void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream);
+int lanczos_resize_host_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* in,
+                           void* out, int frames);
+
+/* ---- reduce by whole factors (Pillow's Image.reduce((fx, fy), box), an exact integer box average) ----
+ * 8-bit, 1, 3 or 4 independent interleaved channels.  box = (x0, y0, x1, y1), integers with 0 <= x0 < x1 <= in_w and the same
+ * for y; NULL = the whole frame.  The output is ceil((x1 - x0) / fx) x ceil((y1 - y0) / fy) pixels, tightly packed rows.
+ * Output pixel (ox, oy) covers source columns x0 + ox * fx .. min(x0 + (ox + 1) * fx, x1) - 1 and the rows likewise: the last
+ * column and row of blocks may be ragged and then divide by their own pixel count d, in uint32:
+ *   out = ((sum + d / 2) * m(d)) >> 24,  m(d) = floor(2^24 / d)
+ * (what Pillow's single-precision 4294967296.0f / (256 * d) gives for every d < 65536).  fx * fy >= 65536 and frames of 2^31
+ * bytes or more: LANCZOS_ERR_UNSUPPORTED.  Pillow refuses I;16 here; there is no 16-bit and no alpha-aware reduce. */
+int lanczos_reduce_size(int in_w, int in_h, int fx, int fy, const int32_t* box, int* out_w, int* out_h);   /* host only */
+/* Device buffers, asynchronous on `stream`; frame strides in bytes, 0 = tightly packed; the base may be any byte address. */
+int lanczos_reduce_device(lanczos_ctx* ctx, int in_w, int in_h, int channels, int fx, int fy, const int32_t* box,
+                          const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride,
+                          void* stream);
+/* Host buffers, `frames` frames back to back; synchronous. */
+int lanczos_reduce_host(lanczos_ctx* ctx, int in_w, int in_h, int channels, int fx, int fy, const int32_t* box,
+                        const void* in, void* out, int frames);
+
 /* ---- measurement / introspection ---- */
 /* When enabled, every lanczos_resample_device call brackets its main kernel with HIP events on the
  * launch stream. lanczos_timing_read synchronises, returns and resets the sums. */

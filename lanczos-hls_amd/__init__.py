@@ -45,6 +45,9 @@ ABI_SYMBOLS = [
     "lanczos_resize_desc_init", "lanczos_resize_desc_init_ex", "lanczos_resize_validate", "lanczos_resize_taps_host",
     "lanczos_resize_taps_f64_host", "lanczos_resize_device",
     "lanczos_resize_host", "lanczos_resize_force", "lanczos_resize_plan_host",
+    "lanczos_resize_opts_init", "lanczos_resize_taps_host_ex", "lanczos_resize_taps_f64_host_ex",
+    "lanczos_resize_plan_host_ex", "lanczos_resize_device_ex", "lanczos_resize_host_ex",
+    "lanczos_reduce_size", "lanczos_reduce_device", "lanczos_reduce_host",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
 
@@ -83,6 +86,20 @@ class ResizePlan(ctypes.Structure):
     """lanczos_resize_plan -- what lanczos_resize_device would launch (lanczos_resize_plan_host, diagnostic)."""
     _fields_ = [(n, ctypes.c_int32) for n in ("fused", "K", "strips", "rows_per_chunk", "chunks", "ring_rows", "stage_rows",
                                               "stage_dw", "lds_bytes")]
+
+
+class ResizeOpts(ctypes.Structure):
+    """lanczos_resize_opts -- the source box and reducing_gap of a resize (Pillow's other two arguments)."""
+    _fields_ = [("box", ctypes.c_double * 4), ("reducing_gap", ctypes.c_double), ("reserved", ctypes.c_int32 * 4)]
+
+
+class ResizePlanEx(ctypes.Structure):
+    """lanczos_resize_plan_ex -- how a request with options resolves (lanczos_resize_plan_host_ex, diagnostic)."""
+    _fields_ = [("fx", ctypes.c_int32), ("fy", ctypes.c_int32), ("safe_box", ctypes.c_int32 * 4),
+                ("reduced_w", ctypes.c_int32), ("reduced_h", ctypes.c_int32),
+                ("pass_h", ctypes.c_int32), ("pass_v", ctypes.c_int32),
+                ("mid_row0", ctypes.c_int32), ("mid_rows", ctypes.c_int32),
+                ("inner_box", ctypes.c_double * 4), ("inner", ResizePlan)]
 
 
 _LIB = None
@@ -160,6 +177,23 @@ def _lib():
         L.lanczos_resize_host.argtypes = [c_void_p, PRD, c_void_p, c_void_p, c_int]
         L.lanczos_resize_force.argtypes = [c_void_p, c_int]
         L.lanczos_resize_plan_host.argtypes = [PRD, c_int, ctypes.POINTER(ResizePlan)]
+        PRO = ctypes.POINTER(ResizeOpts)
+        L.lanczos_strerror.restype = ctypes.c_char_p
+        L.lanczos_version.argtypes = []
+        L.lanczos_version.restype = ctypes.c_char_p
+        if os.environ.get("LANCZOS_LIB") and not hasattr(L, "lanczos_resize_opts_init"):
+            _LIB = L   # an older build of the ABI (A/B runs): everything up to here is there, box / gap / reduce are not
+            return _LIB
+        L.lanczos_resize_opts_init.argtypes = [PRO, PRD]
+        L.lanczos_resize_taps_host_ex.argtypes = [PRD, PRO, c_int, c_void_p, c_void_p, c_void_p, PI]
+        L.lanczos_resize_taps_f64_host_ex.argtypes = [PRD, PRO, c_int, c_void_p, c_void_p, c_void_p, PI]
+        L.lanczos_resize_plan_host_ex.argtypes = [PRD, PRO, c_int, ctypes.POINTER(ResizePlanEx)]
+        L.lanczos_resize_device_ex.argtypes = [c_void_p, PRD, PRO, c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p]
+        L.lanczos_resize_host_ex.argtypes = [c_void_p, PRD, PRO, c_void_p, c_void_p, c_int]
+        L.lanczos_reduce_size.argtypes = [c_int] * 4 + [c_void_p, PI, PI]
+        L.lanczos_reduce_device.argtypes = [c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_int, c_size_t,
+                                                                      c_size_t, c_void_p]
+        L.lanczos_reduce_host.argtypes = [c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_int]
         L.lanczos_strerror.restype = ctypes.c_char_p
         L.lanczos_version.argtypes = []
         L.lanczos_version.restype = ctypes.c_char_p
@@ -228,40 +262,90 @@ def resize_desc(in_w, in_h, out_w, out_h, channels, a=3, alpha=False, bits=8):
     return d
 
 
-def resize_taps_host(desc, axis):
-    """Fixed-point tables of one axis (0 = horizontal, 1 = vertical): (first[out], count[out], coeffs[out][ksize]) int32."""
+def resize_opts(desc, box=None, reducing_gap=None):
+    """A lanczos_resize_opts for `desc`: box = (x0, y0, x1, y1) in source pixels (None = the whole frame), reducing_gap as
+    Pillow's Image.resize takes it (None = none).  Validated where it is used."""
+    o = ResizeOpts()
+    _check(_lib().lanczos_resize_opts_init(ctypes.byref(o), ctypes.byref(desc)), "lanczos_resize_opts_init")
+    if box is not None:
+        if len(box) != 4:
+            raise LanczosError(ERR_BAD_ARG, "resize_opts: box is (x0, y0, x1, y1)")
+        for i in range(4):
+            o.box[i] = float(box[i])
+    if reducing_gap is not None:
+        # 0 means "none" in the C struct; a caller who passes 0 gets what Pillow gives for it, an error
+        o.reducing_gap = float(reducing_gap) if float(reducing_gap) != 0.0 else float("nan")
+    return o
+
+
+def _opts_ref(desc, box, reducing_gap, opts):
+    if opts is None and (box is not None or reducing_gap is not None):
+        opts = resize_opts(desc, box, reducing_gap)
+    return ctypes.byref(opts) if opts is not None else None
+
+
+def resize_taps_host(desc, axis, box=None, reducing_gap=None, opts=None):
+    """Fixed-point tables of one axis (0 = horizontal, 1 = vertical): (first[out], count[out], coeffs[out][ksize]) int32.
+    With a box and / or a gap (or a ready ResizeOpts) the tables of the resize that remains: lanczos_resize_taps_host_ex."""
     ks = ctypes.c_int()
-    _check(_lib().lanczos_resize_taps_host(ctypes.byref(desc), axis, None, None, None, ctypes.byref(ks)),
-           "lanczos_resize_taps_host")
+    if box is None and reducing_gap is None and opts is None:
+        fn = lambda *a: _lib().lanczos_resize_taps_host(ctypes.byref(desc), axis, *a)
+    else:
+        ref = _opts_ref(desc, box, reducing_gap, opts)
+        fn = lambda *a: _lib().lanczos_resize_taps_host_ex(ctypes.byref(desc), ref, axis, *a)
+    _check(fn(None, None, None, ctypes.byref(ks)), "lanczos_resize_taps_host")
     n = desc.out_w if axis == 0 else desc.out_h
     first = np.empty(n, dtype=np.int32)
     count = np.empty(n, dtype=np.int32)
     coeffs = np.empty((n, ks.value), dtype=np.int32)
-    _check(_lib().lanczos_resize_taps_host(ctypes.byref(desc), axis, first.ctypes.data, count.ctypes.data,
-                                           coeffs.ctypes.data, ctypes.byref(ks)), "lanczos_resize_taps_host")
+    _check(fn(first.ctypes.data, count.ctypes.data, coeffs.ctypes.data, ctypes.byref(ks)), "lanczos_resize_taps_host")
     return first, count, coeffs
 
 
-def resize_taps_f64_host(desc, axis):
+def resize_taps_f64_host(desc, axis, box=None, reducing_gap=None, opts=None):
     """Double tables of one axis, what 16-bit requests run on: (first[out] int32, count[out] int32, coeffs[out][ksize]
-    float64); first and count are those of resize_taps_host."""
+    float64); first and count are those of resize_taps_host.  box / reducing_gap / opts as resize_taps_host."""
     ks = ctypes.c_int()
-    _check(_lib().lanczos_resize_taps_f64_host(ctypes.byref(desc), axis, None, None, None, ctypes.byref(ks)),
-           "lanczos_resize_taps_f64_host")
+    if box is None and reducing_gap is None and opts is None:
+        fn = lambda *a: _lib().lanczos_resize_taps_f64_host(ctypes.byref(desc), axis, *a)
+    else:
+        ref = _opts_ref(desc, box, reducing_gap, opts)
+        fn = lambda *a: _lib().lanczos_resize_taps_f64_host_ex(ctypes.byref(desc), ref, axis, *a)
+    _check(fn(None, None, None, ctypes.byref(ks)), "lanczos_resize_taps_f64_host")
     n = desc.out_w if axis == 0 else desc.out_h
     first = np.empty(n, dtype=np.int32)
     count = np.empty(n, dtype=np.int32)
     coeffs = np.empty((n, ks.value), dtype=np.float64)
-    _check(_lib().lanczos_resize_taps_f64_host(ctypes.byref(desc), axis, first.ctypes.data, count.ctypes.data,
-                                               coeffs.ctypes.data, ctypes.byref(ks)), "lanczos_resize_taps_f64_host")
+    _check(fn(first.ctypes.data, count.ctypes.data, coeffs.ctypes.data, ctypes.byref(ks)), "lanczos_resize_taps_f64_host")
     return first, count, coeffs
 
 
-def resize_plan_host(desc, frames=1):
-    """The launch plan of a resize under RESIZE_AUTO (no GPU needed): a ResizePlan, fused = 0 for the two-pass path."""
-    p = ResizePlan()
-    _check(_lib().lanczos_resize_plan_host(ctypes.byref(desc), frames, ctypes.byref(p)), "lanczos_resize_plan_host")
+def resize_plan_host(desc, frames=1, box=None, reducing_gap=None, opts=None):
+    """The launch plan of a resize under RESIZE_AUTO (no GPU needed): a ResizePlan, fused = 0 for the two-pass path.  With a
+    box and / or a gap (or a ready ResizeOpts): a ResizePlanEx -- the reduction (fx, fy, safe_box, reduced_w / reduced_h), the
+    box that remains (inner_box), the passes that run, the rows of the two-pass intermediate, and the inner ResizePlan."""
+    if box is None and reducing_gap is None and opts is None:
+        p = ResizePlan()
+        _check(_lib().lanczos_resize_plan_host(ctypes.byref(desc), frames, ctypes.byref(p)), "lanczos_resize_plan_host")
+        return p
+    p = ResizePlanEx()
+    _check(_lib().lanczos_resize_plan_host_ex(ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts), frames,
+                                              ctypes.byref(p)), "lanczos_resize_plan_host_ex")
     return p
+
+
+def _factor_pair(factor):
+    fx, fy = (factor, factor) if isinstance(factor, (int, np.integer)) else factor
+    return int(fx), int(fy)
+
+
+def reduce_size(in_w, in_h, factor, box=None):
+    """(out_w, out_h) of a reduce by `factor` (an int or (fx, fy)) over the integer box (None = the whole frame)."""
+    fx, fy = _factor_pair(factor)
+    b = (ctypes.c_int32 * 4)(*[int(v) for v in box]) if box is not None else None
+    w, h = ctypes.c_int(), ctypes.c_int()
+    _check(_lib().lanczos_reduce_size(in_w, in_h, fx, fy, b, ctypes.byref(w), ctypes.byref(h)), "lanczos_reduce_size")
+    return w.value, h.value
 
 
 class PinnedArray:
@@ -373,8 +457,12 @@ class Context:
                                                      stream), "lanczos_resample_planar_device")
 
     # -- resize to any size (Pillow's contract, lanczos_resize_*)
-    def resize(self, img, out_w, out_h, a=3, alpha=False):
-        """img: uint8 or uint16 [H][W], [H][W][C] or [F][H][W][C] -> the same layout and dtype at out_h x out_w, bytes
+    def resize(self, img, out_w, out_h, a=3, alpha=False, box=None, reducing_gap=None):
+        """box = (x0, y0, x1, y1): resize that (sub-pixel) region of the source, as Image.resize(..., box=box); pixels
+        outside it still contribute near its edges.  reducing_gap = g >= 1: first reduce by whole factors (an exact box
+        average), then resize what is left, as Image.resize(..., reducing_gap=g) -- Pillow's bytes for the same arguments, not
+        those of the resize without a gap; 8-bit without alpha only (ERR_BAD_ARG otherwise, as there is no oracle).
+        img: uint8 or uint16 [H][W], [H][W][C] or [F][H][W][C] -> the same layout and dtype at out_h x out_w, bytes
         identical to Pillow's Image.resize((out_w, out_h), Image.LANCZOS) for a = 3.  Four channels: mode RGBX (independent
         channels) by default, mode RGBA (straight alpha in the last channel, premultiplied inside the kernels) with
         alpha=True; alpha=True with any other channel count raises LanczosError(ERR_BAD_ARG).  uint16: every channel as
@@ -387,16 +475,57 @@ class Context:
         f, h, w, c = x.shape
         d = resize_desc(w, h, out_w, out_h, c, a, alpha, 8 * img.dtype.itemsize)
         out = np.empty((f, out_h, out_w, c), dtype=img.dtype)
-        _check(_lib().lanczos_resize_host(self._h, ctypes.byref(d), x.ctypes.data, out.ctypes.data, f),
-               "lanczos_resize_host")
+        if box is None and reducing_gap is None:
+            _check(_lib().lanczos_resize_host(self._h, ctypes.byref(d), x.ctypes.data, out.ctypes.data, f),
+                   "lanczos_resize_host")
+        else:
+            _check(_lib().lanczos_resize_host_ex(self._h, ctypes.byref(d), _opts_ref(d, box, reducing_gap, None),
+                                                 x.ctypes.data, out.ctypes.data, f), "lanczos_resize_host_ex")
         if img.ndim == 2:
             return out[0, :, :, 0]
         return out if img.ndim == 4 else out[0]
 
-    def resize_device(self, desc, d_in, d_out, frames, in_frame_stride=0, out_frame_stride=0, stream=None):
-        """Device pointers, asynchronous on `stream` (None = the default stream)."""
-        _check(_lib().lanczos_resize_device(self._h, ctypes.byref(desc), d_in, d_out, frames, in_frame_stride,
-                                            out_frame_stride, stream), "lanczos_resize_device")
+    def resize_device(self, desc, d_in, d_out, frames, in_frame_stride=0, out_frame_stride=0, stream=None, box=None,
+                      reducing_gap=None, opts=None):
+        """Device pointers, asynchronous on `stream` (None = the default stream).  box / reducing_gap / opts as
+        resize_taps_host."""
+        if box is None and reducing_gap is None and opts is None:
+            _check(_lib().lanczos_resize_device(self._h, ctypes.byref(desc), d_in, d_out, frames, in_frame_stride,
+                                                out_frame_stride, stream), "lanczos_resize_device")
+        else:
+            _check(_lib().lanczos_resize_device_ex(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
+                                                   d_in, d_out, frames, in_frame_stride, out_frame_stride, stream),
+                   "lanczos_resize_device_ex")
+
+    # -- reduce by whole factors (Pillow's Image.reduce, lanczos_reduce_*)
+    def reduce(self, img, factor, box=None):
+        """img: uint8 [H][W], [H][W][C] or [F][H][W][C] -> the same layout reduced by `factor` (an int or (fx, fy)) over the
+        integer box (x0, y0, x1, y1) (None = the whole frame): bytes identical to Pillow's Image.reduce(factor, box)."""
+        img = np.ascontiguousarray(img)
+        if img.dtype == np.uint16:
+            raise LanczosError(ERR_BAD_ARG, "reduce: 8-bit samples only (Pillow refuses I;16 as well)")
+        if img.dtype != np.uint8 or img.ndim not in (2, 3, 4):
+            raise LanczosError(ERR_BAD_ARG, "reduce: expected a uint8 [H][W], [H][W][C] or [F][H][W][C] array")
+        x = img.reshape(img.shape + (1,)) if img.ndim == 2 else img
+        x = x if x.ndim == 4 else x[None]
+        f, h, w, c = x.shape
+        fx, fy = _factor_pair(factor)
+        ow, oh = reduce_size(w, h, (fx, fy), box)
+        b = (ctypes.c_int32 * 4)(*[int(v) for v in box]) if box is not None else None
+        out = np.empty((f, oh, ow, c), dtype=np.uint8)
+        _check(_lib().lanczos_reduce_host(self._h, w, h, c, fx, fy, b, x.ctypes.data, out.ctypes.data, f),
+               "lanczos_reduce_host")
+        if img.ndim == 2:
+            return out[0, :, :, 0]
+        return out if img.ndim == 4 else out[0]
+
+    def reduce_device(self, in_w, in_h, channels, factor, d_in, d_out, frames, box=None, in_frame_stride=0,
+                      out_frame_stride=0, stream=None):
+        """Device pointers, asynchronous on `stream`; the output is reduce_size(in_w, in_h, factor, box) pixels per frame."""
+        fx, fy = _factor_pair(factor)
+        b = (ctypes.c_int32 * 4)(*[int(v) for v in box]) if box is not None else None
+        _check(_lib().lanczos_reduce_device(self._h, in_w, in_h, channels, fx, fy, b, d_in, d_out, frames, in_frame_stride,
+                                            out_frame_stride, stream), "lanczos_reduce_device")
 
     def resize_force(self, path):
         """RESIZE_AUTO / RESIZE_FUSED / RESIZE_TWO_PASS (tests and A/B runs)."""

@@ -1055,45 +1055,72 @@ int lanczos_resize_desc_init_ex(lanczos_resize_desc* d, int in_w, int in_h, int 
 
 int lanczos_resize_validate(const lanczos_resize_desc* d) { return lz::resize_validate(d); }
 
-int lanczos_resize_taps_host(const lanczos_resize_desc* d, int axis, int32_t* first, int32_t* count, int32_t* coeffs,
-                             int* ksize) {
+int lanczos_resize_opts_init(lanczos_resize_opts* o, const lanczos_resize_desc* d) {
+    if (!o) return LANCZOS_ERR_BAD_ARG;
+    memset(o, 0, sizeof(*o));
+    int rc = lz::resize_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    o->box[2] = d->in_w, o->box[3] = d->in_h;
+    return LANCZOS_OK;
+}
+
+// the tables of one axis of the resize that remains once the options are resolved
+static int resize_taps_any(const lanczos_resize_desc* d, const lanczos_resize_opts* o, int axis, int32_t* first,
+                           int32_t* count, void* coeffs, int* ksize, bool f64) {
     int rc = lz::resize_validate(d);
     if (rc != LANCZOS_OK) return rc;
     if (!ksize || (axis != 0 && axis != 1)) return LANCZOS_ERR_BAD_ARG;
-    const int in_n = axis == 0 ? d->in_w : d->in_h, out_n = axis == 0 ? d->out_w : d->out_h;
-    *ksize = lz::resize_ksize(in_n, out_n, d->a);
+    lz::RsResolved r;
+    if ((rc = lz::resize_resolve(d, o, &r)) != LANCZOS_OK) return rc;
+    const int in_n = axis == 0 ? r.inner.in_w : r.inner.in_h, out_n = axis == 0 ? d->out_w : d->out_h;
+    const lz::RsSpan span = axis == 0 ? r.h : r.v;
+    *ksize = lz::resize_ksize(in_n, out_n, d->a, span);
     if (!first && !count && !coeffs) return LANCZOS_OK;
     if (!first || !count || !coeffs) return LANCZOS_ERR_BAD_ARG;
     lz::ResizeAxisHost t;
-    if (!lz::resize_build_axis(in_n, out_n, d->a, &t)) return LANCZOS_ERR_UNSUPPORTED;
+    if (!lz::resize_build_axis(in_n, out_n, d->a, span, &t, f64)) return LANCZOS_ERR_UNSUPPORTED;
     memcpy(first, t.first.data(), t.first.size() * sizeof(int32_t));
     memcpy(count, t.count.data(), t.count.size() * sizeof(int32_t));
-    memcpy(coeffs, t.coeffs.data(), t.coeffs.size() * sizeof(int32_t));
+    if (f64) memcpy(coeffs, t.coeffs64.data(), t.coeffs64.size() * sizeof(double));
+    else memcpy(coeffs, t.coeffs.data(), t.coeffs.size() * sizeof(int32_t));
     return LANCZOS_OK;
+}
+
+int lanczos_resize_taps_host_ex(const lanczos_resize_desc* d, const lanczos_resize_opts* o, int axis, int32_t* first,
+                                int32_t* count, int32_t* coeffs, int* ksize) {
+    return resize_taps_any(d, o, axis, first, count, coeffs, ksize, false);
+}
+
+int lanczos_resize_taps_f64_host_ex(const lanczos_resize_desc* d, const lanczos_resize_opts* o, int axis, int32_t* first,
+                                    int32_t* count, double* coeffs, int* ksize) {
+    return resize_taps_any(d, o, axis, first, count, coeffs, ksize, true);
+}
+
+int lanczos_resize_taps_host(const lanczos_resize_desc* d, int axis, int32_t* first, int32_t* count, int32_t* coeffs,
+                             int* ksize) {
+    return lanczos_resize_taps_host_ex(d, nullptr, axis, first, count, coeffs, ksize);
 }
 
 int lanczos_resize_taps_f64_host(const lanczos_resize_desc* d, int axis, int32_t* first, int32_t* count, double* coeffs,
                                  int* ksize) {
-    int rc = lz::resize_validate(d);
-    if (rc != LANCZOS_OK) return rc;
-    if (!ksize || (axis != 0 && axis != 1)) return LANCZOS_ERR_BAD_ARG;
-    const int in_n = axis == 0 ? d->in_w : d->in_h, out_n = axis == 0 ? d->out_w : d->out_h;
-    *ksize = lz::resize_ksize(in_n, out_n, d->a);
-    if (!first && !count && !coeffs) return LANCZOS_OK;
-    if (!first || !count || !coeffs) return LANCZOS_ERR_BAD_ARG;
-    lz::ResizeAxisHost t;
-    lz::resize_build_axis(in_n, out_n, d->a, &t, true);
-    memcpy(first, t.first.data(), t.first.size() * sizeof(int32_t));
-    memcpy(count, t.count.data(), t.count.size() * sizeof(int32_t));
-    memcpy(coeffs, t.coeffs64.data(), t.coeffs64.size() * sizeof(double));
-    return LANCZOS_OK;
+    return lanczos_resize_taps_f64_host_ex(d, nullptr, axis, first, count, coeffs, ksize);
 }
 
-int lanczos_resize_plan_host(const lanczos_resize_desc* d, int frames, lanczos_resize_plan* out) {
+int lanczos_resize_plan_host_ex(const lanczos_resize_desc* d, const lanczos_resize_opts* o, int frames,
+                                lanczos_resize_plan_ex* out) {
     int rc = lz::resize_validate(d);
     if (rc != LANCZOS_OK) return rc;
     if (frames < 1 || !out) return LANCZOS_ERR_BAD_ARG;
-    return lz::resize_plan_host(d, frames, out);
+    return lz::resize_plan_host(d, o, frames, out);
+}
+
+int lanczos_resize_plan_host(const lanczos_resize_desc* d, int frames, lanczos_resize_plan* out) {
+    if (!out) return LANCZOS_ERR_BAD_ARG;
+    lanczos_resize_plan_ex ex;
+    const int rc = lanczos_resize_plan_host_ex(d, nullptr, frames, &ex);
+    if (rc == LANCZOS_OK) *out = ex.inner;
+    else memset(out, 0, sizeof(*out));
+    return rc;
 }
 
 static int resize_state(lanczos_ctx* ctx) {
@@ -1101,8 +1128,8 @@ static int resize_state(lanczos_ctx* ctx) {
     return ctx->resize ? LANCZOS_OK : LANCZOS_ERR_NOMEM;
 }
 
-int lanczos_resize_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const void* d_in, void* d_out, int frames,
-                          size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+int lanczos_resize_device_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* d_in,
+                             void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
     if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
     int rc = lz::resize_validate(d);
     if (rc != LANCZOS_OK) return rc;
@@ -1110,11 +1137,17 @@ int lanczos_resize_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const 
     LZ_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
     // NULL = the legacy default stream, as lanczos_resample_device
-    return lz::resize_device(ctx->resize, d, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
+    return lz::resize_device(ctx->resize, d, o, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
                              &ctx->last_kernel, &ctx->last_hip);
 }
 
-int lanczos_resize_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const void* in, void* out, int frames) {
+int lanczos_resize_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const void* d_in, void* d_out, int frames,
+                          size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+    return lanczos_resize_device_ex(ctx, d, nullptr, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+}
+
+int lanczos_resize_host_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* in,
+                           void* out, int frames) {
     if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
     int rc = lz::resize_validate(d);
     if (rc != LANCZOS_OK) return rc;
@@ -1122,7 +1155,43 @@ int lanczos_resize_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const vo
     LZ_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->stream) return LANCZOS_ERR_HIP;
     if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
-    return lz::resize_host(ctx->resize, d, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip);
+    return lz::resize_host(ctx->resize, d, o, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip);
+}
+
+int lanczos_resize_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const void* in, void* out, int frames) {
+    return lanczos_resize_host_ex(ctx, d, nullptr, in, out, frames);
+}
+
+int lanczos_reduce_size(int in_w, int in_h, int fx, int fy, const int32_t* box, int* out_w, int* out_h) {
+    if (!out_w || !out_h) return LANCZOS_ERR_BAD_ARG;
+    int rb[4];
+    const int rc = lz::reduce_validate(in_w, in_h, 1, fx, fy, box, rb);
+    if (rc != LANCZOS_OK) return rc;
+    *out_w = (rb[2] - rb[0] + fx - 1) / fx, *out_h = (rb[3] - rb[1] + fy - 1) / fy;
+    return LANCZOS_OK;
+}
+
+int lanczos_reduce_device(lanczos_ctx* ctx, int in_w, int in_h, int channels, int fx, int fy, const int32_t* box,
+                          const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride,
+                          void* stream) {
+    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = resize_state(ctx);
+    if (rc != LANCZOS_OK) return rc;
+    return lz::reduce_device(ctx->resize, in_w, in_h, channels, fx, fy, box, d_in, d_out, frames, in_frame_stride,
+                             out_frame_stride, (hipStream_t)stream, &ctx->last_hip);
+}
+
+int lanczos_reduce_host(lanczos_ctx* ctx, int in_w, int in_h, int channels, int fx, int fy, const int32_t* box,
+                        const void* in, void* out, int frames) {
+    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->stream) return LANCZOS_ERR_HIP;
+    int rc = resize_state(ctx);
+    if (rc != LANCZOS_OK) return rc;
+    return lz::reduce_host(ctx->resize, in_w, in_h, channels, fx, fy, box, in, out, frames, ctx->stream, &ctx->last_hip);
 }
 
 int lanczos_resize_force(lanczos_ctx* ctx, int path) {

@@ -7,8 +7,8 @@
 //             ring, and the vertical pass reads the ring and stores the block's output rows.  Horizontal coefficients stay in
 //             registers for the whole march (a thread keeps one output column); vertical ones are workgroup-uniform scalar
 //             loads.
-//   two-pass  k_rs_h writes the u8 intermediate (in_h x out_w x C per frame) to context scratch, k_rs_v reads it: any tap
-//             count.  It also serves a resize that changes one axis only (one kernel) -- as Pillow, a pass whose axis keeps
+//   two-pass  k_rs_h writes the u8 intermediate (the rows the vertical taps read x out_w x C per frame) to context scratch,
+//             k_rs_v reads it: any tap count.  It also serves a resize that changes one axis only (one kernel) -- as Pillow, a pass whose axis keeps
 //             its size is skipped.
 //
 // LANCZOS_RESIZE_ALPHA (four channels, Pillow's RGBA mode): both paths premultiply the colour samples by alpha where they
@@ -17,6 +17,10 @@
 //
 // LANCZOS_RESIZE_U16 (16-bit samples, Pillow's I;16): the same tap geometry with double coefficients and Pillow's double
 // accumulation; tables, cache, planning and dispatch are here, the kernels in lanczos_resize16.hip.
+//
+// A source box (lanczos_resize_opts) only changes the tables: an axis is built over a span of the source given as two floats,
+// `first` still indexes the whole axis, and the kernels are the ones above.  reducing_gap puts lanczos_reduce.hip in front:
+// reduce into context scratch, then the resize of the reduced frames with the box that remains (resize_resolve).
 //
 // Arithmetic is Pillow's and exact by construction: acc = 2^21 + sum(sample * coeff) in int32 with 24-bit multiplies
 // (|coeff| < 2^23 and 255 * sum|coeff| + 2^21 < 2^31, checked when a table is built), result clamp(acc >> 22, 0, 255).
@@ -57,19 +61,23 @@ static double rs_filter(double x, int a) {
     return 0.0;
 }
 
-int resize_ksize(int in_n, int out_n, int a) {
-    const double scale = (double)in_n / out_n;
+// the extent of a span is taken in float, as Pillow's C does with its float box[4]; for the whole axis it is in_n exactly
+static double rs_span_scale(RsSpan s, int out_n) { return (double)(float)(s.b1 - s.b0) / out_n; }
+
+int resize_ksize(int in_n, int out_n, int a, RsSpan s) {
+    (void)in_n;
+    const double scale = rs_span_scale(s, out_n);
     const double fs = scale > 1.0 ? scale : 1.0;
     return (int)ceil(a * fs) * 2 + 1;
 }
 
-bool resize_build_axis(int in_n, int out_n, int a, ResizeAxisHost* t, bool f64) {
-    const double scale = (double)in_n / out_n;
+bool resize_build_axis(int in_n, int out_n, int a, RsSpan s, ResizeAxisHost* t, bool f64) {
+    const double scale = rs_span_scale(s, out_n);
     const double fs = scale > 1.0 ? scale : 1.0;
     const double support = a * fs;
     const double ss = 1.0 / fs;
     const int ksize = (int)ceil(support) * 2 + 1;
-    t->in_n = in_n, t->out_n = out_n, t->a = a, t->ksize = ksize;
+    t->in_n = in_n, t->out_n = out_n, t->a = a, t->ksize = ksize, t->scale = scale;
     t->first.assign(out_n, 0);
     t->count.assign(out_n, 0);
     t->coeffs.assign(f64 ? 0 : (size_t)out_n * ksize, 0);
@@ -77,7 +85,7 @@ bool resize_build_axis(int in_n, int out_n, int a, ResizeAxisHost* t, bool f64) 
     std::vector<double> w(ksize);
     bool ok = true;
     for (int o = 0; o < out_n; o++) {
-        const double center = (o + 0.5) * scale;
+        const double center = (double)s.b0 + (o + 0.5) * scale;
         int xmin = (int)(center - support + 0.5);
         if (xmin < 0) xmin = 0;
         int xmax = (int)(center + support + 0.5);
@@ -106,6 +114,53 @@ bool resize_build_axis(int in_n, int out_n, int a, ResizeAxisHost* t, bool f64) 
         if (255 * abs_sum + (1 << (kResizePrecision - 1)) >= (1ll << 31)) ok = false;
     }
     return ok;
+}
+
+// Options -> the reduction in front of the resize and the resize that remains (include/lanczos_hip.h).  The gap arithmetic is
+// Pillow's Python, in double on the caller's box; only the inner box is rounded to float.
+int resize_resolve(const lanczos_resize_desc* d, const lanczos_resize_opts* o, RsResolved* r) {
+    *r = RsResolved();
+    r->inner = *d;
+    r->rb[2] = d->in_w, r->rb[3] = d->in_h;
+    double box[4] = {0.0, 0.0, (double)d->in_w, (double)d->in_h};
+    double gap = 0.0;
+    if (o) {
+        for (int i = 0; i < 4; i++) {
+            if (o->reserved[i] != 0 || !std::isfinite(o->box[i])) return LANCZOS_ERR_BAD_ARG;
+            box[i] = o->box[i];
+        }
+        if (!(box[0] >= 0.0 && box[0] < box[2] && box[2] <= d->in_w)) return LANCZOS_ERR_BAD_ARG;
+        if (!(box[1] >= 0.0 && box[1] < box[3] && box[3] <= d->in_h)) return LANCZOS_ERR_BAD_ARG;
+        gap = o->reducing_gap;
+        if (gap != 0.0 && !(gap >= 1.0)) return LANCZOS_ERR_BAD_ARG;   // NaN included
+        // Pillow drops the gap in mode RGBA and refuses it for I;16: no oracle for either
+        if (gap != 0.0 && (d->reserved[0] & (LANCZOS_RESIZE_ALPHA | LANCZOS_RESIZE_U16))) return LANCZOS_ERR_BAD_ARG;
+    }
+    if (gap != 0.0) {
+        const double ex = (box[2] - box[0]) / d->out_w / gap, ey = (box[3] - box[1]) / d->out_h / gap;
+        const long long fx = ex >= 1.0 ? (long long)ex : 1, fy = ey >= 1.0 ? (long long)ey : 1;
+        if (fx > 1 || fy > 1) {
+            if (fx * fy >= 65536) return LANCZOS_ERR_UNSUPPORTED;
+            const double sup = d->a - 0.5;
+            const double sx = sup * ((box[2] - box[0]) / d->out_w), sy = sup * ((box[3] - box[1]) / d->out_h);
+            r->rb[0] = std::max(0, (int)(box[0] - sx));
+            r->rb[1] = std::max(0, (int)(box[1] - sy));
+            r->rb[2] = (int)std::min((double)d->in_w, ceil(box[2] + sx));
+            r->rb[3] = (int)std::min((double)d->in_h, ceil(box[3] + sy));
+            r->fx = (int)fx, r->fy = (int)fy;
+            r->inner.in_w = (r->rb[2] - r->rb[0] + r->fx - 1) / r->fx;
+            r->inner.in_h = (r->rb[3] - r->rb[1] + r->fy - 1) / r->fy;
+            box[0] = (box[0] - r->rb[0]) / r->fx, box[2] = (box[2] - r->rb[0]) / r->fx;
+            box[1] = (box[1] - r->rb[1]) / r->fy, box[3] = (box[3] - r->rb[1]) / r->fy;
+        }
+    }
+    for (int i = 0; i < 4; i++) r->inner_box[i] = box[i];
+    r->h = RsSpan{(float)box[0], (float)box[2]};
+    r->v = RsSpan{(float)box[1], (float)box[3]};
+    if (!(r->h.b0 < r->h.b1) || !(r->v.b0 < r->v.b1)) return LANCZOS_ERR_BAD_ARG;   // empty once rounded to float
+    r->need_h = rs_axis_runs(r->inner.in_w, r->inner.out_w, r->h);
+    r->need_v = rs_axis_runs(r->inner.in_h, r->inner.out_h, r->v);
+    return LANCZOS_OK;
 }
 
 // ---- kernels -----------------------------------------------------------------------------------------------------
@@ -409,7 +464,8 @@ ResizeState::~ResizeState() {   // the owner has drained the device
         delete a;
     }
     for (void* p : kept) (void)hipFree(p);
-    if (scratch) (void)hipFree(scratch);
+    if (scratch.p) (void)hipFree(scratch.p);
+    if (reduced.p) (void)hipFree(reduced.p);
     if (stage_in) (void)hipFree(stage_in);
     if (stage_out) (void)hipFree(stage_out);
     if (upload) (void)hipStreamDestroy(upload);
@@ -418,10 +474,14 @@ ResizeState::~ResizeState() {   // the owner has drained the device
 // The tables of one axis shape, built and uploaded on first use.  The upload is eager: a copy on the private stream and a
 // wait for it, so an entry is valid from the moment it is cached -- also when the caller's stream is being captured
 // (a copy queued on it would only run when the graph is replayed, perhaps never).
-static int rs_axis(ResizeState* st, int in_n, int out_n, int a, bool f64, ResizeAxis** out, int* last_hip) {
+static int rs_axis(ResizeState* st, int in_n, int out_n, int a, RsSpan span, bool f64, ResizeAxis** out, int* last_hip) {
+    uint32_t bits[2];
+    memcpy(&bits[0], &span.b0, 4);
+    memcpy(&bits[1], &span.b1, 4);
     for (size_t i = 0; i < st->axes.size(); i++) {
         ResizeAxis* ax = st->axes[i];
-        if (ax->key[0] == in_n && ax->key[1] == out_n && ax->key[2] == a && ax->key[3] == (int)f64) {
+        if (ax->key[0] == in_n && ax->key[1] == out_n && ax->key[2] == a && ax->key[3] == (int)f64 &&
+            ax->span_bits[0] == bits[0] && ax->span_bits[1] == bits[1]) {
             st->axes.erase(st->axes.begin() + i);
             st->axes.push_back(ax);   // most recent last
             *out = ax;
@@ -432,7 +492,8 @@ static int rs_axis(ResizeState* st, int in_n, int out_n, int a, bool f64, Resize
     ResizeAxis* ax = new (std::nothrow) ResizeAxis();
     if (!ax) return LANCZOS_ERR_NOMEM;
     ax->key[0] = in_n, ax->key[1] = out_n, ax->key[2] = a, ax->key[3] = (int)f64;
-    if (!resize_build_axis(in_n, out_n, a, &ax->host, f64)) {
+    ax->span_bits[0] = bits[0], ax->span_bits[1] = bits[1];
+    if (!resize_build_axis(in_n, out_n, a, span, &ax->host, f64)) {
         delete ax;
         return LANCZOS_ERR_UNSUPPORTED;
     }
@@ -466,33 +527,33 @@ static int rs_axis(ResizeState* st, int in_n, int out_n, int a, bool f64, Resize
 
 // context scratch of at least `bytes`.  A block a captured launch used may still be named by a live graph: it is kept until
 // the context goes instead of being freed when a larger one replaces it.
-static int rs_scratch(ResizeState* st, size_t bytes, hipStream_t stream, bool capturing, int* last_hip) {
-    if (st->scratch_bytes < bytes) {
-        if (st->scratch) {
-            if (st->scratch_captured) st->kept.push_back(st->scratch);
-            else rs_retire(st->retired, st->scratch, st->scratch_streams);
+static int rs_scratch(ResizeState* st, ResizeState::Block* blk, size_t bytes, hipStream_t stream, bool capturing,
+                      int* last_hip) {
+    if (blk->bytes < bytes) {
+        if (blk->p) {
+            if (blk->captured) st->kept.push_back(blk->p);
+            else rs_retire(st->retired, blk->p, blk->streams);
         }
-        st->scratch = nullptr;
-        st->scratch_bytes = 0;
-        st->scratch_captured = false;
-        st->scratch_streams.clear();
-        hipError_t e = hipMalloc(&st->scratch, bytes);
+        blk->p = nullptr;
+        blk->bytes = 0;
+        blk->captured = false;
+        blk->streams.clear();
+        hipError_t e = hipMalloc(&blk->p, bytes);
         if (e != hipSuccess) {
             *last_hip = (int)e;
-            st->scratch = nullptr;
+            blk->p = nullptr;
             return LANCZOS_ERR_HIP;
         }
-        st->scratch_bytes = bytes;
+        blk->bytes = bytes;
     }
-    if (capturing) st->scratch_captured = true;
-    else note_stream(st->scratch_streams, stream);
+    if (capturing) blk->captured = true;
+    else note_stream(blk->streams, stream);
     return LANCZOS_OK;
 }
 
-// the fused kernel's launch shape for this request (false: it cannot run it)
+// the fused kernel's launch shape for this request, both of whose passes run (false: it cannot run it)
 bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H, const ResizeAxisHost& V, int frames,
                    RsFusedPlan* fp) {
-    if (d->in_w == d->out_w || d->in_h == d->out_h) return false;   // one pass only: nothing to fuse
     const bool u16 = resize_u16(d);
     const int C = d->channels * (u16 ? 2 : 1);   // bytes per pixel
     if ((long long)d->in_w * d->in_h * C + 4 >= (1ll << 31)) return false;   // 32-bit buffer offsets
@@ -515,7 +576,7 @@ bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H, const 
         ring = std::max(ring, V.first[last] + V.count[last] - V.first[o0]);
     }
     fp->ring_rows = ring;
-    const double scale_v = (double)d->in_h / d->out_h;
+    const double scale_v = V.scale;
     fp->stage_rows = std::min(16, (int)ceil(kRsOB * scale_v) + 1);
     auto lds = [&]() { return (size_t)ring * SW * C + (size_t)fp->stage_rows * fp->stage_dw * 4; };
     while (lds() > (size_t)kRsFusedMaxLds && fp->stage_rows > 4) fp->stage_rows--;   // wide spans: fewer rows per staging
@@ -531,19 +592,30 @@ bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H, const 
     return (long long)fp->strips * fp->chunks < (1ll << 31);
 }
 
-int resize_plan_host(const lanczos_resize_desc* d, int frames, lanczos_resize_plan* out) {
+int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o, int frames, lanczos_resize_plan_ex* out) {
     memset(out, 0, sizeof(*out));
-    if (d->in_w == d->out_w || d->in_h == d->out_h) return LANCZOS_OK;   // as resize_device: no table for such an axis
-    ResizeAxisHost H, V;
+    RsResolved r;
+    const int rc = resize_resolve(d, o, &r);
+    if (rc != LANCZOS_OK) return rc;
+    out->fx = r.fx, out->fy = r.fy;
+    for (int i = 0; i < 4; i++) out->safe_box[i] = r.rb[i], out->inner_box[i] = r.inner_box[i];
+    out->reduced_w = r.inner.in_w, out->reduced_h = r.inner.in_h;
+    out->pass_h = r.need_h, out->pass_v = r.need_v;
     const bool u16 = resize_u16(d);
-    if (!resize_build_axis(d->in_w, d->out_w, d->a, &H, u16) || !resize_build_axis(d->in_h, d->out_h, d->a, &V, u16))
-        return LANCZOS_ERR_UNSUPPORTED;
+    ResizeAxisHost H, V;
+    if (r.need_v) {
+        if (!resize_build_axis(r.inner.in_h, r.inner.out_h, d->a, r.v, &V, u16)) return LANCZOS_ERR_UNSUPPORTED;
+        if (r.need_h) rs_mid_rows(V, &out->mid_row0, &out->mid_rows);
+    }
+    if (!r.need_h || !r.need_v) return LANCZOS_OK;   // as resize_device: no table for an idle axis, nothing to fuse
+    if (!resize_build_axis(r.inner.in_w, r.inner.out_w, d->a, r.h, &H, u16)) return LANCZOS_ERR_UNSUPPORTED;
     RsFusedPlan fp;
-    if (!rs_fused_plan(d, H, V, frames, &fp)) return LANCZOS_OK;
-    out->fused = 1;
-    out->K = fp.K, out->strips = fp.strips, out->rows_per_chunk = fp.rows_per_chunk, out->chunks = fp.chunks;
-    out->ring_rows = fp.ring_rows, out->stage_rows = fp.stage_rows, out->stage_dw = fp.stage_dw;
-    out->lds_bytes = (int32_t)fp.lds;
+    if (!rs_fused_plan(&r.inner, H, V, frames, &fp)) return LANCZOS_OK;
+    lanczos_resize_plan* in = &out->inner;
+    in->fused = 1;
+    in->K = fp.K, in->strips = fp.strips, in->rows_per_chunk = fp.rows_per_chunk, in->chunks = fp.chunks;
+    in->ring_rows = fp.ring_rows, in->stage_rows = fp.stage_rows, in->stage_dw = fp.stage_dw;
+    in->lds_bytes = (int32_t)fp.lds;
     return LANCZOS_OK;
 }
 
@@ -605,26 +677,22 @@ static hipError_t rs_launch_pass(bool horizontal, const RsPass& p0, int rows, in
     return hipSuccess;
 }
 
-int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_in, void* d_out, int frames,
-                  size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream, int* last_kernel, int* last_hip) {
+// the resize that remains once the options are resolved: `d` describes the frames at `in` (the caller's, or the reduced
+// ones), sh / sv are the source spans of its two axes
+static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh, RsSpan sv, const uint8_t* in, uint8_t* out,
+                        int frames, size_t in_fs, size_t out_fs, hipStream_t stream, int* last_kernel, int* last_hip) {
     const int C = d->channels;
     const bool u16 = resize_u16(d);
     const size_t B = u16 ? 2 : 1;   // bytes per sample
-    const size_t in_frame = (size_t)d->in_w * d->in_h * C * B, out_frame = (size_t)d->out_w * d->out_h * C * B;
-    const size_t in_fs = in_frame_stride ? in_frame_stride : in_frame;
-    const size_t out_fs = out_frame_stride ? out_frame_stride : out_frame;
-    if (in_fs < in_frame || out_fs < out_frame) return LANCZOS_ERR_BAD_ARG;
-    if (u16 && (((uintptr_t)d_in | (uintptr_t)d_out | in_fs | out_fs) & 1) != 0) return LANCZOS_ERR_BAD_ARG;
-    const uint8_t* in = (const uint8_t*)d_in;
-    uint8_t* out = (uint8_t*)d_out;
+    const size_t in_frame = (size_t)d->in_w * d->in_h * C * B;
     const bool capturing = stream_capturing(stream);
-    const bool need_h = d->in_w != d->out_w, need_v = d->in_h != d->out_h;
+    const bool need_h = rs_axis_runs(d->in_w, d->out_w, sh), need_v = rs_axis_runs(d->in_h, d->out_h, sv);
     const bool alpha = (d->reserved[0] & LANCZOS_RESIZE_ALPHA) != 0;
 
     ResizeAxis *H = nullptr, *V = nullptr;
     int rc;
-    if (need_h && (rc = rs_axis(st, d->in_w, d->out_w, d->a, u16, &H, last_hip)) != LANCZOS_OK) return rc;
-    if (need_v && (rc = rs_axis(st, d->in_h, d->out_h, d->a, u16, &V, last_hip)) != LANCZOS_OK) return rc;
+    if (need_h && (rc = rs_axis(st, d->in_w, d->out_w, d->a, sh, u16, &H, last_hip)) != LANCZOS_OK) return rc;
+    if (need_v && (rc = rs_axis(st, d->in_h, d->out_h, d->a, sv, u16, &V, last_hip)) != LANCZOS_OK) return rc;
     for (ResizeAxis* ax : {H, V})
         if (ax && !capturing) note_stream(ax->streams, stream);
 
@@ -632,6 +700,13 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_i
     const bool fused_ok = need_h && need_v && rs_fused_plan(d, H->host, V->host, frames, &fp);
     if (st->force == LANCZOS_RESIZE_FUSED && !fused_ok) return LANCZOS_ERR_UNSUPPORTED;
     const bool fused = fused_ok && st->force != LANCZOS_RESIZE_TWO_PASS;
+    // two passes: the horizontal one produces the rows the vertical taps read and no others, mid_rows of them from source
+    // row mid_row0 on, and the scratch holds exactly those; the vertical pass indexes it through a base mid_row0 rows in
+    // front of it, which it never dereferences below the block (its first tap is row mid_row0)
+    int mid_row0 = 0, mid_rows = d->in_h;
+    if (need_h && need_v) rs_mid_rows(V->host, &mid_row0, &mid_rows);
+    const size_t mid_pitch = (size_t)d->out_w * C * B, mid_fs = (size_t)mid_rows * mid_pitch;
+    const size_t in_pitch = (size_t)d->in_w * C * B;
     hipError_t e = hipSuccess;
     if (fused) {
         e = u16 ? rs16_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream)
@@ -642,44 +717,44 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_i
         *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
     } else if (u16) {
         const uint8_t* mid = in;   // what the vertical pass reads
-        size_t mid_fs = in_fs;
+        size_t v_fs = in_fs;
         if (need_h) {
             uint8_t* dst = out;
             size_t dst_fs = out_fs;
             if (need_v) {
-                rc = rs_scratch(st, (size_t)frames * d->in_h * d->out_w * C * 2, stream, capturing, last_hip);
+                rc = rs_scratch(st, &st->scratch, (size_t)frames * mid_fs, stream, capturing, last_hip);
                 if (rc != LANCZOS_OK) return rc;
-                dst = (uint8_t*)st->scratch, dst_fs = (size_t)d->in_h * d->out_w * C * 2;
+                dst = (uint8_t*)st->scratch.p, dst_fs = mid_fs;
             }
-            e = rs16_launch_pass(true, H, C, in, in_fs, (size_t)d->in_w * C, dst, dst_fs, (size_t)d->out_w * C, d->out_w * C,
-                                 d->in_h, frames, stream);
-            mid = dst, mid_fs = dst_fs;
+            e = rs16_launch_pass(true, H, C, in + (size_t)mid_row0 * in_pitch, in_fs, (size_t)d->in_w * C, dst, dst_fs,
+                                 (size_t)d->out_w * C, d->out_w * C, mid_rows, frames, stream);
+            mid = (const uint8_t*)((uintptr_t)dst - (uintptr_t)((size_t)mid_row0 * mid_pitch)), v_fs = dst_fs;
         }
         if (e == hipSuccess && need_v)
-            e = rs16_launch_pass(false, V, C, mid, mid_fs, (size_t)d->out_w * C, out, out_fs, (size_t)d->out_w * C,
+            e = rs16_launch_pass(false, V, C, mid, v_fs, (size_t)d->out_w * C, out, out_fs, (size_t)d->out_w * C,
                                  d->out_w * C, d->out_h, frames, stream);
         *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
     } else {
         RsPass ph{}, pv{};
         if (need_h) {
-            ph.src = in, ph.src_fs = in_fs, ph.src_pitch = (size_t)d->in_w * C;
+            ph.src = in + (size_t)mid_row0 * in_pitch, ph.src_fs = in_fs, ph.src_pitch = in_pitch;
             ph.n_cols = d->out_w * C, ph.channels = C;
             ph.first = H->first(), ph.count = H->count(), ph.coeffs = H->coeffs(), ph.ksize = H->host.ksize;
-            ph.dst_pitch = (size_t)d->out_w * C;
+            ph.dst_pitch = mid_pitch;
             if (need_v) {
-                rc = rs_scratch(st, (size_t)frames * d->in_h * d->out_w * C, stream, capturing, last_hip);
+                rc = rs_scratch(st, &st->scratch, (size_t)frames * mid_fs, stream, capturing, last_hip);
                 if (rc != LANCZOS_OK) return rc;
-                ph.dst = (uint8_t*)st->scratch, ph.dst_fs = (size_t)d->in_h * d->out_w * C;
+                ph.dst = (uint8_t*)st->scratch.p, ph.dst_fs = mid_fs;
             } else {
                 ph.dst = out, ph.dst_fs = out_fs;
             }
-            e = rs_launch_pass(true, ph, d->in_h, frames, stream, alpha, !need_v);
+            e = rs_launch_pass(true, ph, mid_rows, frames, stream, alpha, !need_v);
         }
         if (e == hipSuccess && need_v) {
-            pv.src = need_h ? ph.dst : in;
+            pv.src = need_h ? (const uint8_t*)((uintptr_t)ph.dst - (uintptr_t)((size_t)mid_row0 * mid_pitch)) : in;
             pv.src_fs = need_h ? ph.dst_fs : in_fs;
-            pv.src_pitch = (size_t)d->out_w * C;
-            pv.dst = out, pv.dst_fs = out_fs, pv.dst_pitch = (size_t)d->out_w * C;
+            pv.src_pitch = mid_pitch;
+            pv.dst = out, pv.dst_fs = out_fs, pv.dst_pitch = mid_pitch;
             pv.n_cols = d->out_w * C, pv.channels = C;
             pv.first = V->first(), pv.count = V->count(), pv.coeffs = V->coeffs(), pv.ksize = V->host.ksize;
             e = rs_launch_pass(false, pv, d->out_h, frames, stream, alpha, !need_h);
@@ -705,30 +780,108 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_i
     return LANCZOS_OK;
 }
 
-int resize_host(ResizeState* st, const lanczos_resize_desc* d, const void* in, void* out, int frames, hipStream_t stream,
-                int* last_kernel, int* last_hip) {
+int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* d_in, void* d_out,
+                  int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream, int* last_kernel,
+                  int* last_hip) {
+    RsResolved r;
+    int rc = resize_resolve(d, o, &r);
+    if (rc != LANCZOS_OK) return rc;
+    const int C = d->channels;
+    const size_t B = resize_u16(d) ? 2 : 1;   // bytes per sample
+    const size_t in_frame = (size_t)d->in_w * d->in_h * C * B, out_frame = (size_t)d->out_w * d->out_h * C * B;
+    const size_t in_fs = in_frame_stride ? in_frame_stride : in_frame;
+    const size_t out_fs = out_frame_stride ? out_frame_stride : out_frame;
+    if (in_fs < in_frame || out_fs < out_frame) return LANCZOS_ERR_BAD_ARG;
+    if (B == 2 && (((uintptr_t)d_in | (uintptr_t)d_out | in_fs | out_fs) & 1) != 0) return LANCZOS_ERR_BAD_ARG;
+    const uint8_t* in = (const uint8_t*)d_in;
+    if (r.reduces()) {   // reducing_gap: reduce into context scratch, then resize the reduced frames
+        int rb[4];
+        const int32_t box[4] = {r.rb[0], r.rb[1], r.rb[2], r.rb[3]};
+        if ((rc = reduce_validate(d->in_w, d->in_h, C, r.fx, r.fy, box, rb)) != LANCZOS_OK) return rc;
+        const size_t red_fs = (size_t)r.inner.in_w * r.inner.in_h * C;
+        rc = rs_scratch(st, &st->reduced, (size_t)frames * red_fs, stream, stream_capturing(stream), last_hip);
+        if (rc != LANCZOS_OK) return rc;
+        const hipError_t e = reduce_launch(in, (uint8_t*)st->reduced.p, d->in_w, C, r.fx, r.fy, rb, frames, in_fs, red_fs, stream);
+        if (e != hipSuccess) {
+            *last_hip = (int)e;
+            return LANCZOS_ERR_HIP;
+        }
+        return resize_inner(st, &r.inner, r.h, r.v, (const uint8_t*)st->reduced.p, (uint8_t*)d_out, frames, red_fs, out_fs,
+                            stream, last_kernel, last_hip);
+    }
+    return resize_inner(st, d, r.h, r.v, in, (uint8_t*)d_out, frames, in_fs, out_fs, stream, last_kernel, last_hip);
+}
+
+// staging buffers of the host entry points (resize and reduce)
+static hipError_t rs_grow_stage(ResizeState* st, void** p, size_t* have, size_t need, hipStream_t stream) {
+    if (*have >= need) return hipSuccess;
+    if (*p) {
+        rs_retire(st->retired, *p, {stream});
+        *p = nullptr;
+        *have = 0;
+    }
+    const hipError_t e = hipMalloc(p, need);
+    if (e == hipSuccess) *have = need;
+    else *p = nullptr;
+    return e;
+}
+
+int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* in, void* out,
+                int frames, hipStream_t stream, int* last_kernel, int* last_hip) {
     const size_t B = resize_u16(d) ? 2 : 1;
     if (B == 2 && (((uintptr_t)in | (uintptr_t)out) & 1) != 0) return LANCZOS_ERR_BAD_ARG;
     const size_t in_bytes = (size_t)d->in_w * d->in_h * d->channels * B * frames;
     const size_t out_bytes = (size_t)d->out_w * d->out_h * d->channels * B * frames;
-    auto grow = [&](void** p, size_t* have, size_t need) -> hipError_t {
-        if (*have >= need) return hipSuccess;
-        if (*p) {
-            rs_retire(st->retired, *p, {stream});
-            *p = nullptr;
-            *have = 0;
-        }
-        const hipError_t e = hipMalloc(p, need);
-        if (e == hipSuccess) *have = need;
-        else *p = nullptr;
-        return e;
-    };
-    hipError_t e = grow(&st->stage_in, &st->stage_in_bytes, in_bytes);
-    if (e == hipSuccess) e = grow(&st->stage_out, &st->stage_out_bytes, out_bytes);
+    hipError_t e = rs_grow_stage(st, &st->stage_in, &st->stage_in_bytes, in_bytes, stream);
+    if (e == hipSuccess) e = rs_grow_stage(st, &st->stage_out, &st->stage_out_bytes, out_bytes, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(st->stage_in, in, in_bytes, hipMemcpyHostToDevice, stream);
     int rc = LANCZOS_OK;
     if (e == hipSuccess) {
-        rc = resize_device(st, d, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip);
+        rc = resize_device(st, d, o, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip);
+        if (rc == LANCZOS_OK) e = hipMemcpyAsync(out, st->stage_out, out_bytes, hipMemcpyDeviceToHost, stream);
+    }
+    const hipError_t es = hipStreamSynchronize(stream);   // nothing stays in flight on the caller's buffers
+    if (rc != LANCZOS_OK) return rc;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        *last_hip = (int)e;
+        return LANCZOS_ERR_HIP;
+    }
+    return LANCZOS_OK;
+}
+
+int reduce_device(ResizeState* st, int in_w, int in_h, int channels, int fx, int fy, const int32_t* box, const void* d_in,
+                  void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream, int* last_hip) {
+    (void)st;
+    int rb[4];
+    const int rc = reduce_validate(in_w, in_h, channels, fx, fy, box, rb);
+    if (rc != LANCZOS_OK) return rc;
+    const size_t in_frame = (size_t)in_w * in_h * channels;
+    const size_t out_frame = (size_t)((rb[2] - rb[0] + fx - 1) / fx) * ((rb[3] - rb[1] + fy - 1) / fy) * channels;
+    const size_t in_fs = in_frame_stride ? in_frame_stride : in_frame;
+    const size_t out_fs = out_frame_stride ? out_frame_stride : out_frame;
+    if (in_fs < in_frame || out_fs < out_frame) return LANCZOS_ERR_BAD_ARG;
+    const hipError_t e = reduce_launch((const uint8_t*)d_in, (uint8_t*)d_out, in_w, channels, fx, fy, rb, frames, in_fs, out_fs,
+                                       stream);
+    if (e != hipSuccess) {
+        *last_hip = (int)e;
+        return LANCZOS_ERR_HIP;
+    }
+    return LANCZOS_OK;
+}
+
+int reduce_host(ResizeState* st, int in_w, int in_h, int channels, int fx, int fy, const int32_t* box, const void* in,
+                void* out, int frames, hipStream_t stream, int* last_hip) {
+    int rb[4];
+    int rc = reduce_validate(in_w, in_h, channels, fx, fy, box, rb);
+    if (rc != LANCZOS_OK) return rc;
+    const size_t in_bytes = (size_t)in_w * in_h * channels * frames;
+    const size_t out_bytes = (size_t)((rb[2] - rb[0] + fx - 1) / fx) * ((rb[3] - rb[1] + fy - 1) / fy) * channels * frames;
+    hipError_t e = rs_grow_stage(st, &st->stage_in, &st->stage_in_bytes, in_bytes, stream);
+    if (e == hipSuccess) e = rs_grow_stage(st, &st->stage_out, &st->stage_out_bytes, out_bytes, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(st->stage_in, in, in_bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) {
+        rc = reduce_device(st, in_w, in_h, channels, fx, fy, box, st->stage_in, st->stage_out, frames, 0, 0, stream, last_hip);
         if (rc == LANCZOS_OK) e = hipMemcpyAsync(out, st->stage_out, out_bytes, hipMemcpyDeviceToHost, stream);
     }
     const hipError_t es = hipStreamSynchronize(stream);   // nothing stays in flight on the caller's buffers

@@ -22,13 +22,39 @@ int resize_validate(const lanczos_resize_desc* d);
 // (|coeff| < 2^23 for the 24-bit multiply, 255 * sum|coeff| + 2^21 < 2^31); no shape met so far does.
 struct ResizeAxisHost {
     int in_n = 0, out_n = 0, a = 0, ksize = 0;
+    double scale = 1.0;                          // source pixels per output pixel: the box's extent / out_n
     std::vector<int32_t> first, count, coeffs;   // [out_n], [out_n], [out_n][ksize]
     std::vector<double> coeffs64;                // [out_n][ksize]: the 16-bit path's tables, which have no `coeffs`
 };
-int resize_ksize(int in_n, int out_n, int a);
+// The source interval of one axis as Pillow's C sees it: both ends rounded to float.  The whole axis is (0, in_n).
+struct RsSpan {
+    float b0 = 0.0f, b1 = 0.0f;
+};
+inline RsSpan rs_full_span(int in_n) { return RsSpan{0.0f, (float)in_n}; }
+// the pass rule: an axis runs its pass iff it changes size or its span is not the whole axis
+inline bool rs_axis_runs(int in_n, int out_n, RsSpan s) { return out_n != in_n || s.b0 != 0.0f || s.b1 != (float)in_n; }
+int resize_ksize(int in_n, int out_n, int a, RsSpan s);
 // f64: the tables of the 16-bit path instead -- the normalised weights as they are (Pillow's precompute_coeffs alone),
 // in coeffs64; always true.
-bool resize_build_axis(int in_n, int out_n, int a, ResizeAxisHost* t, bool f64 = false);
+bool resize_build_axis(int in_n, int out_n, int a, RsSpan s, ResizeAxisHost* t, bool f64 = false);
+
+// A request with its options resolved (lanczos_resize_opts; NULL = the full box, no gap): the reduction in front of the
+// resize, if any, and the resize that remains -- `inner` is the caller's descriptor, or one whose source is the reduced frame.
+struct RsResolved {
+    int fx = 1, fy = 1;
+    int rb[4] = {0, 0, 0, 0};   // the safe box the reduction covers (the whole frame without one)
+    lanczos_resize_desc inner{};
+    double inner_box[4] = {0, 0, 0, 0};
+    RsSpan h, v;                // inner_box rounded to float, per axis
+    bool need_h = false, need_v = false;
+    bool reduces() const { return fx > 1 || fy > 1; }
+};
+int resize_resolve(const lanczos_resize_desc* d, const lanczos_resize_opts* o, RsResolved* r);
+// the rows of the inner source the horizontal pass of the two-pass path produces: what the vertical taps read
+inline void rs_mid_rows(const ResizeAxisHost& V, int* row0, int* rows) {
+    *row0 = V.first.front();
+    *rows = V.first.back() + V.count.back() - *row0;
+}
 
 inline bool resize_u16(const lanczos_resize_desc* d) { return (d->reserved[0] & LANCZOS_RESIZE_U16) != 0; }
 
@@ -47,12 +73,13 @@ struct RsFusedPlan {
 };
 bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H, const ResizeAxisHost& V, int frames,
                    RsFusedPlan* fp);
-int resize_plan_host(const lanczos_resize_desc* d, int frames, lanczos_resize_plan* out);
+int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o, int frames, lanczos_resize_plan_ex* out);
 
 // One axis shape on the device: first | count | coeffs in one block (int32 coefficients, or double ones for 16-bit samples:
 // the two int32 arrays in front of them keep those 8-byte aligned).
 struct ResizeAxis {
     int key[4] = {0, 0, 0, 0};   // in, out, a, double coefficients
+    uint32_t span_bits[2] = {0, 0};   // the bit patterns of the span's two floats: two boxes over one (in, out, a) are two entries
     ResizeAxisHost host;
     int32_t* dev = nullptr;
     const int32_t* first() const { return dev; }
@@ -69,11 +96,15 @@ struct ResizeState {
     RetireList retired;
     hipStream_t upload = nullptr;            // private stream of the eager table uploads
     int force = LANCZOS_RESIZE_AUTO;
-    // intermediate of the two-pass path (in_h x out_w x C samples per frame)
-    void* scratch = nullptr;
-    size_t scratch_bytes = 0;
-    bool scratch_captured = false;           // used by a captured launch: a live graph may still hold it
-    std::vector<hipStream_t> scratch_streams;
+    // a block of context scratch that grows on demand
+    struct Block {
+        void* p = nullptr;
+        size_t bytes = 0;
+        bool captured = false;               // used by a captured launch: a live graph may still hold it
+        std::vector<hipStream_t> streams;
+    };
+    Block scratch;                           // intermediate of the two-pass path (the rows the vertical taps read x out_w x C)
+    Block reduced;                           // the reduced frames of a request with reducing_gap, tightly packed
     std::vector<void*> kept;                 // scratch blocks replaced while a graph may hold them: freed at destruction
     // staging of lanczos_resize_host
     void* stage_in = nullptr;
@@ -83,10 +114,21 @@ struct ResizeState {
 };
 
 // The entry points (ctx->mu held, device set).  *last_kernel / *last_hip as in lanczos_ctx.
-int resize_device(ResizeState* st, const lanczos_resize_desc* d, const void* d_in, void* d_out, int frames,
-                  size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream, int* last_kernel, int* last_hip);
-int resize_host(ResizeState* st, const lanczos_resize_desc* d, const void* in, void* out, int frames, hipStream_t stream,
-                int* last_kernel, int* last_hip);
+int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* d_in, void* d_out,
+                  int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream, int* last_kernel,
+                  int* last_hip);
+int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* in, void* out,
+                int frames, hipStream_t stream, int* last_kernel, int* last_hip);
+
+// Reduce by whole factors (lanczos_reduce.hip): Pillow's Image.reduce over an integer box, 8-bit.  Arguments validated by
+// reduce_validate; the output rows are tightly packed.
+int reduce_validate(int in_w, int in_h, int channels, int fx, int fy, const int32_t* box, int rb[4]);
+hipError_t reduce_launch(const uint8_t* in, uint8_t* out, int in_w, int channels, int fx, int fy, const int rb[4], int frames,
+                         size_t in_fs, size_t out_fs, hipStream_t stream);
+int reduce_device(ResizeState* st, int in_w, int in_h, int channels, int fx, int fy, const int32_t* box, const void* d_in,
+                  void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream, int* last_hip);
+int reduce_host(ResizeState* st, int in_w, int in_h, int channels, int fx, int fy, const int32_t* box, const void* in,
+                void* out, int frames, hipStream_t stream, int* last_hip);
 
 // 16-bit requests (lanczos_resize16.hip): the tap count of the smallest fused instance that holds ksize (0: none), and the
 // launches.

@@ -4,11 +4,14 @@
  *
  *   lanczos_upscale <in.(png|ppm|pgm)> <out.(png|ppm|pgm)> [--scale N[/D]] [--a A] [--channels C]
  *                   [--exact | --hls] [--device D] [--repeat K]
- *   lanczos_upscale <in> <out> --size WxH [--a A] [--channels C | --alpha] [--device D] [--repeat K]
+ *   lanczos_upscale <in> <out> --size WxH [--box x0,y0,x1,y1] [--reducing-gap G] [--a A] [--channels C | --alpha]
+ *                   [--device D] [--repeat K]
  *                   (resize to any size, downscaling included, through lanczos_resize_host: Pillow's Image.resize with
  *                   LANCZOS, not the reference's model; refuses --scale, --exact, --hls and the multi-device flags.
  *                   --alpha: four channels, the fourth straight alpha, resized as Pillow's mode RGBA and written as an
- *                   RGBA PNG; needs --size, --channels 4 if --channels is given, and a .png output)
+ *                   RGBA PNG; needs --size, --channels 4 if --channels is given, and a .png output.
+ *                   --box: resize that region of the source (source pixels, fractions allowed), Image.resize's box;
+ *                   --reducing-gap G >= 1: reduce by whole factors first, Image.resize's reducing_gap; not with --alpha)
  *                   [--devices 0-7 | 0,2,5] [--frames F] [--split frames|rows] [--root]   (several GPUs of one node, plain C:
  *                   the image is replicated into a batch of F frames and the batch -- or every frame's rows -- is split
  *                   over the devices by lanczos_resample_multi_host; the first result frame is written.  --root: the batch
@@ -43,14 +46,26 @@ static double ms_since(const struct timespec* t0) {
 
 /* --size WxH: one frame through lanczos_resize_host */
 static int resize_main(const char* out_path, const uint8_t* img, int width, int height, int channels, int out_w, int out_h,
-                       int a, int alpha, int device, int repeat) {
+                       int a, int alpha, int device, int repeat, const double* box, double gap) {
     lanczos_resize_desc d;
+    lanczos_resize_opts o;
+    lanczos_resize_plan_ex plan;
     int rc = lanczos_resize_desc_init_ex(&d, width, height, out_w, out_h, channels, a, alpha ? LANCZOS_RESIZE_ALPHA : 0);
+    if (rc == LANCZOS_OK) rc = lanczos_resize_opts_init(&o, &d);
+    if (rc == LANCZOS_OK) {
+        if (box) memcpy(o.box, box, sizeof(o.box));
+        o.reducing_gap = gap;
+        rc = lanczos_resize_plan_host_ex(&d, &o, 1, &plan); /* validates the box and the gap */
+    }
     if (rc != LANCZOS_OK) {
         printf("Cannot resize %i x %i to %i x %i: %s.\n", width, height, out_w, out_h, lanczos_strerror(rc));
         return EXIT_FAILURE;
     }
     printf("Resize %d x %d -> %d x %d, a = %d%s\n", width, height, out_w, out_h, a, alpha ? ", straight alpha" : "");
+    if (box) printf("Box %g,%g,%g,%g\n", o.box[0], o.box[1], o.box[2], o.box[3]);
+    if (plan.fx > 1 || plan.fy > 1)
+        printf("Reduce by %d x %d over %d,%d,%d,%d to %d x %d first\n", plan.fx, plan.fy, plan.safe_box[0], plan.safe_box[1],
+               plan.safe_box[2], plan.safe_box[3], plan.reduced_w, plan.reduced_h);
     uint8_t* out = (uint8_t*)malloc((size_t)out_w * out_h * channels);
     lanczos_ctx* ctx = NULL;
     rc = lanczos_create(&ctx, device);
@@ -60,7 +75,7 @@ static int resize_main(const char* out_path, const uint8_t* img, int width, int 
     }
     struct timespec t0;
     clock_gettime(CLOCK_MONOTONIC, &t0);
-    for (int k = 0; k < repeat && rc == LANCZOS_OK; k++) rc = lanczos_resize_host(ctx, &d, img, out, 1);
+    for (int k = 0; k < repeat && rc == LANCZOS_OK; k++) rc = lanczos_resize_host_ex(ctx, &d, &o, img, out, 1);
     if (rc != LANCZOS_OK) {
         printf("lanczos_resize failed: %s (hip error %d)\n", lanczos_strerror(rc), lanczos_last_hip_error(ctx));
         return EXIT_FAILURE;
@@ -84,11 +99,18 @@ int main(int argc, char* argv[]) {
     int scale_n = 2, scale_d = 1, a = 3, want_channels = 3, exact = 0, hls = 0, device = 0, repeat = 1;
     int devices[64], n_devices = 0, frames = 1, split = LANCZOS_SPLIT_FRAMES, root = 0;
     int size_w = 0, size_h = 0, have_size = 0, upscale_only = 0; /* upscale_only: a flag --size cannot go with */
-    int alpha = 0, have_channels = 0;
+    int alpha = 0, have_channels = 0, have_box = 0, have_gap = 0;
+    double box[4] = {0, 0, 0, 0}, gap = 0.0;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--size") && i + 1 < argc) {
             have_size = 1;
             if (sscanf(argv[++i], "%dx%d", &size_w, &size_h) != 2) size_w = size_h = 0;
+        } else if (!strcmp(argv[i], "--box") && i + 1 < argc) {
+            char tail;
+            have_box = sscanf(argv[++i], "%lf,%lf,%lf,%lf%c", &box[0], &box[1], &box[2], &box[3], &tail) == 4 ? 1 : -1;
+        } else if (!strcmp(argv[i], "--reducing-gap") && i + 1 < argc) {
+            char tail;
+            have_gap = sscanf(argv[++i], "%lf%c", &gap, &tail) == 1 && gap >= 1.0 ? 1 : -1;
         } else if (!strcmp(argv[i], "--scale") && i + 1 < argc) {
             upscale_only = 1;
             scale_d = 1;
@@ -141,13 +163,25 @@ int main(int argc, char* argv[]) {
     if (!in_path || !out_path) {
         fprintf(stderr, "usage: %s <in.png|ppm> <out.png|ppm> [--scale N[/D]] [--a A] [--channels C] [--exact|--hls] "
                         "[--device D] [--repeat K] [--devices 0-7|0,2,5] [--frames F] [--split frames|rows] [--root]\n"
-                        "       %s <in.png|ppm> <out.png|ppm> --size WxH [--a A] [--channels C | --alpha] [--device D] "
-                        "[--repeat K]\n",
+                        "       %s <in.png|ppm> <out.png|ppm> --size WxH [--box x0,y0,x1,y1] [--reducing-gap G] [--a A] "
+                        "[--channels C | --alpha] [--device D] [--repeat K]\n",
                 argv[0], argv[0]);
         return EXIT_FAILURE;
     }
     if (have_size && upscale_only) {
         fprintf(stderr, "--size cannot be combined with --scale, --exact, --hls, --devices, --frames, --split or --root\n");
+        return EXIT_FAILURE;
+    }
+    if (have_box < 0) {
+        fprintf(stderr, "--box takes four numbers, x0,y0,x1,y1 in source pixels\n");
+        return EXIT_FAILURE;
+    }
+    if (have_gap < 0) {
+        fprintf(stderr, "--reducing-gap takes a number of at least 1\n");
+        return EXIT_FAILURE;
+    }
+    if ((have_box || have_gap) && !have_size) {
+        fprintf(stderr, "--box and --reducing-gap need --size\n");
         return EXIT_FAILURE;
     }
     if (alpha) {
@@ -167,7 +201,8 @@ int main(int argc, char* argv[]) {
         return EXIT_FAILURE;
     }
     if (have_size) {
-        const int rc = resize_main(out_path, img, width, height, want_channels, size_w, size_h, a, alpha, device, repeat);
+        const int rc = resize_main(out_path, img, width, height, want_channels, size_w, size_h, a, alpha, device, repeat,
+                                   have_box ? box : NULL, have_gap ? gap : 0.0);
         lz_image_free(img);
         return rc;
     }

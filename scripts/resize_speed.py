@@ -27,6 +27,17 @@ the flag runs rgbx,three_step).
 U1 and U4 are W1's and W4's shapes with 16-bit samples (LANCZOS_RESIZE_U16, Pillow's mode I;16): the same three paths, the
 same discipline, twice the compulsory bytes.
 
+R5 is W5's shape (3840x2160 -> 160x90, 32 frames) with reducing_gap: routes `plain` (W5 as it is: two-pass, 145 vertical
+taps), `gap2` and `gap3` (reduce 12x12 / 8x8 into context scratch, then the fused kernel), `reduce12` (lanczos_reduce_device
+12x12 alone) and `copy` (a device-to-device copy of the same source bytes, which moves twice what the reduction moves),
+alternating region by region.  The bytes of gap2 / gap3 are NOT those of plain: they are Pillow's for that gap.
+
+B1 / B2 are a fractional 1280x720-ish box out of 7680x4320 (8 frames) to 1920x1080 / 640x360: `boxed_auto` and
+`boxed_two_pass` on the whole frames against `tight_auto` and `tight_two_pass`, the same resize of a tightly packed copy of
+the crop region padded by the support (its box is the boxed one shifted by whole pixels; a float rounds the two
+differently, so the bytes are compared between the paths of each, not between boxed and tight).  R5, B1 and B2 run on
+request (--only R5,B1,B2); they need a build with lanczos_resize_device_ex.
+
 --pillow adds Pillow's single-core time of one frame of each workload (if Pillow imports; else "not available"); for U1 and
 U4 that is the time of one I;16 plane (a frame has three).
 """
@@ -215,6 +226,118 @@ def run_rgba(name, spec, args, ctx, torch):
     torch.cuda.empty_cache()
 
 
+def run_routes(name, shape, f, routes, in_bytes, out_bytes, args, ctx, torch, check=()):
+    """routes: {route: step(i)} alternating region by region; check: pairs of routes whose frame-0 outputs must agree
+    (each step(i) returns the tensor it wrote)."""
+    stream = torch.cuda.current_stream()
+    first = {}
+    for rn, step in routes.items():
+        y = step(0)
+        torch.cuda.synchronize()
+        first[rn] = (y.cpu().numpy().copy(), ctx.last_kernel())
+    for a, b in check:
+        if not np.array_equal(first[a][0], first[b][0]):
+            raise SystemExit(f"{name}: route {a} differs from route {b}")
+    times = {rn: [] for rn in routes}
+    for rn, step in routes.items():
+        for k in range(args.warmup):
+            step(k)
+    torch.cuda.synchronize()
+    for r in range(args.rounds):
+        for rn, step in routes.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for k in range(args.steps):
+                step(r * args.steps + k)
+            e1.record(stream)
+            e1.synchronize()
+            times[rn].append(e0.elapsed_time(e1) * 1e3 / args.steps)
+    for rn in routes:
+        us = statistics.median(times[rn])
+        line = {"workload": name, "shape": shape, "frames": f, "route": rn, "kernel": first[rn][1],
+                "us_per_step": round(us, 2), "us_all_regions": [round(v, 2) for v in times[rn]],
+                "hbm_frac": round((in_bytes[rn] + out_bytes[rn]) / (us * 1e-6) / HBM_BPS, 4),
+                "compulsory_bytes": in_bytes[rn] + out_bytes[rn], "steps": args.steps, "rounds": args.rounds,
+                "lib": os.path.basename(L.LIB_PATH), "measured": True}
+        print(json.dumps(line), flush=True)
+
+
+def run_gap(name, args, ctx, torch):
+    iw, ih, ow, oh, c, a, f = WORKLOADS["W5"]
+    in_fb, out_fb = iw * ih * c, ow * oh * c
+    sets = max(2, -(-2 * 256 * 2 ** 20 // (f * in_fb)) + 1)
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    xs = [torch.randint(0, 256, (f * in_fb,), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(sets)]
+    ys = [torch.empty(f * out_fb, dtype=torch.uint8, device="cuda") for _ in range(sets)]
+    rw, rh = L.reduce_size(iw, ih, 12)
+    red = torch.empty(f * rw * rh * c, dtype=torch.uint8, device="cuda")
+    cp = torch.empty(f * in_fb, dtype=torch.uint8, device="cuda")
+    d = L.resize_desc(iw, ih, ow, oh, c, a)
+    opts = {g: L.resize_opts(d, reducing_gap=g) for g in (2.0, 3.0)}
+    s = torch.cuda.current_stream().cuda_stream
+    ctx.resize_force(L.RESIZE_AUTO)
+
+    def resize(o):
+        def step(i):
+            ctx.resize_device(d, xs[i % sets].data_ptr(), ys[i % sets].data_ptr(), f, 0, 0, s, opts=o)
+            return ys[i % sets][:out_fb]
+        return step
+
+    def reduce12(i):
+        ctx.reduce_device(iw, ih, c, 12, xs[i % sets].data_ptr(), red.data_ptr(), f, stream=s)
+        return red[:rw * rh * c]
+
+    def copy(i):
+        cp.copy_(xs[i % sets])
+        return cp[:out_fb]
+
+    routes = {"plain": resize(None), "gap2": resize(opts[2.0]), "gap3": resize(opts[3.0]), "reduce12": reduce12, "copy": copy}
+    inb = {rn: f * in_fb for rn in routes}
+    outb = {"plain": f * out_fb, "gap2": f * out_fb, "gap3": f * out_fb, "reduce12": f * rw * rh * c, "copy": f * in_fb}
+    run_routes(name, f"{iw}x{ih}->{ow}x{oh} C{c} a{a}", f, routes, inb, outb, args, ctx, torch)
+    del xs, ys, red, cp
+    torch.cuda.empty_cache()
+
+
+def run_box(name, out, args, ctx, torch):
+    iw, ih, c, a, f = 7680, 4320, 3, 3, 8
+    ow, oh = out
+    box = (3000.3, 1700.6, 4281.1, 2420.2)
+    padx, pady = int(a * max(1.0, (box[2] - box[0]) / ow)) + 2, int(a * max(1.0, (box[3] - box[1]) / oh)) + 2
+    cx0, cy0 = int(box[0]) - padx, int(box[1]) - pady
+    cx1, cy1 = int(box[2]) + 1 + padx, int(box[3]) + 1 + pady
+    cw, ch = cx1 - cx0, cy1 - cy0
+    tbox = (box[0] - cx0, box[1] - cy0, box[2] - cx0, box[3] - cy0)
+    in_fb, out_fb, crop_fb = iw * ih * c, ow * oh * c, cw * ch * c
+    sets = 3   # 8 frames of 8K are 796 MB: every step's source region is far behind the Infinity Cache by its next use
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    xs = [torch.randint(0, 256, (f, ih, iw, c), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(sets)]
+    ts = [x[:, cy0:cy1, cx0:cx1].contiguous() for x in xs]
+    ys = [torch.empty(f * out_fb, dtype=torch.uint8, device="cuda") for _ in range(sets)]
+    d, dt = L.resize_desc(iw, ih, ow, oh, c, a), L.resize_desc(cw, ch, ow, oh, c, a)
+    o, ot = L.resize_opts(d, box=box), L.resize_opts(dt, box=tbox)
+    s = torch.cuda.current_stream().cuda_stream
+
+    def mk(desc, opt, src, path):
+        def step(i):
+            ctx.resize_force(path)
+            ctx.resize_device(desc, src[i % sets].data_ptr(), ys[i % sets].data_ptr(), f, 0, 0, s, opts=opt)
+            return ys[i % sets][:out_fb]
+        return step
+
+    routes = {"boxed_auto": mk(d, o, xs, L.RESIZE_AUTO), "tight_auto": mk(dt, ot, ts, L.RESIZE_AUTO),
+              "boxed_two_pass": mk(d, o, xs, L.RESIZE_TWO_PASS), "tight_two_pass": mk(dt, ot, ts, L.RESIZE_TWO_PASS)}
+    inb = {rn: f * crop_fb for rn in routes}
+    outb = {rn: f * out_fb for rn in routes}
+    # the tight box is the boxed one shifted by whole pixels, which a float rounds differently: bytes are compared between
+    # the two paths of each, not between boxed and tight
+    run_routes(name, f"box {box} of {iw}x{ih}->{ow}x{oh} C{c} a{a}; tight {cw}x{ch}", f, routes, inb, outb, args, ctx, torch,
+               check=(("boxed_auto", "boxed_two_pass"), ("tight_auto", "tight_two_pass")))
+    ctx.resize_force(L.RESIZE_AUTO)
+    del xs, ts, ys
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -229,7 +352,11 @@ def main():
         raise SystemExit("resize_speed.py needs a GPU")
     ctx = L.Context(0)
     for name in args.only.split(","):
-        if name in RGBA_WORKLOADS:
+        if name == "R5":
+            run_gap(name, args, ctx, torch)
+        elif name in ("B1", "B2"):
+            run_box(name, (1920, 1080) if name == "B1" else (640, 360), args, ctx, torch)
+        elif name in RGBA_WORKLOADS:
             run_rgba(name, RGBA_WORKLOADS[name], args, ctx, torch)
         elif name in U16_WORKLOADS:
             run(name, U16_WORKLOADS[name], args, ctx, torch, bits=16)
