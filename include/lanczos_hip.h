@@ -369,6 +369,30 @@ int lanczos_reduce_host(lanczos_ctx* ctx, int in_w, int in_h, int channels, int 
 int lanczos_timing_enable(lanczos_ctx* ctx, int on);
 int lanczos_timing_read(lanczos_ctx* ctx, int* launches, double* main_kernel_ms, double* prefix_kernel_ms);
 int lanczos_last_kernel(const lanczos_ctx* ctx);
+/* How the last upscale call (lanczos_resample_device / _host / _planar_device) on the context was launched -- finer than the
+ * family of lanczos_last_kernel, for tests and A/B runs.  One int: LANCZOS_ROUTE_MAIN(r) is the main kernel,
+ * LANCZOS_ROUTE_PREFIX(r) how the in-place prefix rows [0, K) were produced, LANCZOS_ROUTE_LAUNCHES(r) the number of launches the
+ * call went out as (1 unless lanczos_resample_device split an oversized batch; lanczos_resample_host counts the launches of its
+ * pipeline's groups).  Main kernel and prefix route are those of the LAST launch; LANCZOS_ROUTE_PREFIX_SEEN(r) has bit
+ * (1 << route) set for every prefix route any launch of the call took.  0 (all fields "none") after a resize, reduce or layout
+ * call, after a call that failed before its first launch, and on a new context. */
+int lanczos_last_route(const lanczos_ctx* ctx);
+#define LANCZOS_ROUTE_MAIN(r) ((r) & 0xf)
+#define LANCZOS_ROUTE_PREFIX(r) (((r) >> 4) & 0xf)
+#define LANCZOS_ROUTE_PREFIX_SEEN(r) (((r) >> 8) & 0xff)
+#define LANCZOS_ROUTE_LAUNCHES(r) (((r) >> 16) & 0x7fff)
+#define LANCZOS_ROUTE_MAIN_NONE 0     /* no main launch: a strip from row 0 that ends inside the prefix rows (k_march only) */
+#define LANCZOS_ROUTE_MAIN_MARCH 1    /* k_march: integer scales, rows and frame strides 16-byte multiples */
+#define LANCZOS_ROUTE_MAIN_TILE 2     /* k_fast, the tile-per-workgroup kernel: the other integer scales, LANCZOS_TILE_KERNEL=1 */
+#define LANCZOS_ROUTE_MAIN_RATP 3     /* k_ratp: exactly periodic rational scales */
+#define LANCZOS_ROUTE_MAIN_RAT 4      /* k_rat: the other rational scales, LANCZOS_NO_RATP=1 */
+#define LANCZOS_ROUTE_MAIN_GENERIC 5  /* k_generic */
+#define LANCZOS_ROUTE_MAIN_HLS 6      /* k_hls */
+#define LANCZOS_ROUTE_PREFIX_NONE 0      /* no prefix rows in the call: K = 0, a strip below them, LANCZOS_MODE_HLS */
+#define LANCZOS_ROUTE_PREFIX_RIDING 1    /* extra workgroups at the end of the k_march grid */
+#define LANCZOS_ROUTE_PREFIX_FRONT 2     /* k_prefix_reg (registers only) in front of k_march */
+#define LANCZOS_ROUTE_PREFIX_BEHIND 3    /* k_prefix (LDS row arrays) behind the main kernel */
+#define LANCZOS_ROUTE_PREFIX_STREAMED 4  /* k_prefix_stream (LDS rings, any depth) behind the main kernel */
 int lanczos_last_hip_error(const lanczos_ctx* ctx);
 /* Force a kernel family for A/B tests: LANCZOS_KERNEL_NONE (auto), _GENERIC or _FAST. */
 int lanczos_force_kernel(lanczos_ctx* ctx, int family);

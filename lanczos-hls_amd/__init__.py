@@ -10,6 +10,7 @@ the reference's testbench:
 There is NO CPU fallback: if the shared library is missing or no GPU is present the calls raise.
 Nothing here imports anything under oracle/.
 """
+import collections
 import ctypes
 import os
 import subprocess
@@ -24,6 +25,11 @@ OK, ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_HIP, ERR_NOMEM, ERR_RCCL = 
 MODE_LSB1, MODE_EXACT, MODE_HLS = 0, 1, 2
 KERNEL_NONE, KERNEL_GENERIC, KERNEL_FAST, KERNEL_HLS = 0, 1, 2, 3
 KERNEL_RESIZE_FUSED, KERNEL_RESIZE_TWO_PASS = 4, 5
+# lanczos_last_route: the main kernel and the route of the in-place prefix rows (include/lanczos_hip.h LANCZOS_ROUTE_*)
+ROUTE_MAIN_NONE, ROUTE_MAIN_MARCH, ROUTE_MAIN_TILE, ROUTE_MAIN_RATP, ROUTE_MAIN_RAT, ROUTE_MAIN_GENERIC, ROUTE_MAIN_HLS = range(7)
+ROUTE_PREFIX_NONE, ROUTE_PREFIX_RIDING, ROUTE_PREFIX_FRONT, ROUTE_PREFIX_BEHIND, ROUTE_PREFIX_STREAMED = range(5)
+ROUTE_MAIN_NAMES = ("none", "march", "tile", "ratp", "rat", "generic", "hls")
+ROUTE_PREFIX_NAMES = ("none", "riding", "front", "behind", "streamed")
 RESIZE_AUTO, RESIZE_FUSED, RESIZE_TWO_PASS = 0, 1, 2   # lanczos_resize_force
 RESIZE_ALPHA = 1   # flag of lanczos_resize_desc.reserved[0]: channel 3 of 4 is straight alpha (Pillow's RGBA mode)
 RESIZE_U16 = 4     # flag of lanczos_resize_desc.reserved[0]: native-endian uint16 samples (Pillow's I;16 arithmetic)
@@ -36,7 +42,7 @@ ABI_SYMBOLS = [
     "lanczos_resample_host",
     "lanczos_resample_device", "lanczos_planar_to_interleaved_device", "lanczos_interleaved_to_planar_device",
     "lanczos_resample_planar_device", "lanczos_u8", "lanczos_timing_enable", "lanczos_timing_read",
-    "lanczos_last_kernel", "lanczos_last_hip_error", "lanczos_force_kernel", "lanczos_strerror",
+    "lanczos_last_kernel", "lanczos_last_route", "lanczos_last_hip_error", "lanczos_force_kernel", "lanczos_strerror",
     "lanczos_version",
     "lanczos_partition_frames", "lanczos_partition_rows", "lanczos_multi_create", "lanczos_multi_destroy",
     "lanczos_multi_devices", "lanczos_resample_multi_host", "lanczos_resample_multi_root",
@@ -50,6 +56,15 @@ ABI_SYMBOLS = [
     "lanczos_reduce_size", "lanczos_reduce_device", "lanczos_reduce_host",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
+
+
+class Route(collections.namedtuple("Route", "main prefix launches prefix_seen")):
+    """lanczos_last_route, unpacked: ROUTE_MAIN_* and ROUTE_PREFIX_* of the last launch of the call, the number of launches,
+    and the set of ROUTE_PREFIX_* that any launch of the call took."""
+
+    def __str__(self):
+        seen = "+".join(ROUTE_PREFIX_NAMES[r] for r in sorted(self.prefix_seen))
+        return f"{ROUTE_MAIN_NAMES[self.main]}+{ROUTE_PREFIX_NAMES[self.prefix]} x{self.launches} (prefix routes seen: {seen})"
 
 
 class LanczosError(RuntimeError):
@@ -157,6 +172,8 @@ def _lib():
         L.lanczos_timing_read.argtypes = [c_void_p, PI, ctypes.POINTER(c_double), ctypes.POINTER(c_double)]
         L.lanczos_last_kernel.argtypes = [c_void_p]
         L.lanczos_last_hip_error.argtypes = [c_void_p]
+        if hasattr(L, "lanczos_last_route"):   # (an older build loaded through LANCZOS_LIB has none)
+            L.lanczos_last_route.argtypes = [c_void_p]
         L.lanczos_force_kernel.argtypes = [c_void_p, c_int]
         L.lanczos_strerror.argtypes = [c_int]
         L.lanczos_partition_frames.argtypes = [c_int, c_int, c_int, PI, PI]
@@ -542,6 +559,12 @@ class Context:
 
     def last_kernel(self):
         return _lib().lanczos_last_kernel(self._h)
+
+    def last_route(self):
+        """How the last upscale call was launched: a Route (main kernel, prefix route, launches, prefix routes seen)."""
+        r = _lib().lanczos_last_route(self._h)
+        seen = (r >> 8) & 0xff
+        return Route(r & 0xf, (r >> 4) & 0xf, (r >> 16) & 0x7fff, frozenset(i for i in range(8) if seen >> i & 1))
 
     def force_kernel(self, family):
         _check(_lib().lanczos_force_kernel(self._h, family), "lanczos_force_kernel")

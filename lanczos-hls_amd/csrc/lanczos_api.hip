@@ -67,6 +67,9 @@ struct lanczos_ctx {
     std::vector<void*> kept_dev, kept_host;   // blocks of evicted plans a live graph may still name: freed by lanczos_destroy
     std::mutex mu;
     int last_kernel = LANCZOS_KERNEL_NONE;
+    int last_route = 0;      // lanczos_last_route: main kernel, prefix route and launch count of the last upscale call
+    int route_launches = 0;  // launches of the call in flight (reset by the entry points, counted where a launch is issued)
+    int route_seen = 0;      // prefix routes of those launches, one bit each
     int last_hip = 0;
     int force = LANCZOS_KERNEL_NONE;
     // staging for lanczos_resample_host
@@ -111,6 +114,15 @@ namespace {
             return LANCZOS_ERR_HIP;                        \
         }                                                  \
     } while (0)
+
+// lanczos_last_route: an upscale entry point starts a call with route_begin; every launch of the call reports itself with
+// route_launch at the point where it is issued
+void route_begin(lanczos_ctx* ctx) { ctx->last_route = ctx->route_launches = ctx->route_seen = 0; }
+void route_launch(lanczos_ctx* ctx, int main_kernel, int prefix_route) {
+    if (ctx->route_launches < 0x7fff) ctx->route_launches++;
+    ctx->route_seen |= 1 << prefix_route;
+    ctx->last_route = main_kernel | prefix_route << 4 | ctx->route_seen << 8 | ctx->route_launches << 16;
+}
 
 void free_plan(Plan* p) {   // nothing in flight reads it any more
     if (p->dev_block) (void)hipFree(p->dev_block);
@@ -592,6 +604,7 @@ int lanczos_timing_read(lanczos_ctx* ctx, int* launches, double* main_kernel_ms,
 }
 
 int lanczos_last_kernel(const lanczos_ctx* ctx) { return ctx ? ctx->last_kernel : LANCZOS_KERNEL_NONE; }
+int lanczos_last_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_route : 0; }
 int lanczos_last_hip_error(const lanczos_ctx* ctx) { return ctx ? ctx->last_hip : 0; }
 
 int lanczos_force_kernel(lanczos_ctx* ctx, int family) {
@@ -720,6 +733,7 @@ static int resample_device_locked(lanczos_ctx* ctx, const lanczos_desc* d, const
             hipLaunchKernelGGL(lz::k_hls<uint16_t>, grid, dim3(lz::kHlsThreads), 0, stream, g, p->dev);
         LZ_HIP(ctx, hipGetLastError());
         ctx->last_kernel = LANCZOS_KERNEL_HLS;
+        route_launch(ctx, LANCZOS_ROUTE_MAIN_HLS, LANCZOS_ROUTE_PREFIX_NONE);
         if (ev0) {  // one kernel: all of it is "main"
             LZ_HIP(ctx, hipEventRecord(ev1, stream));
             LZ_HIP(ctx, hipEventRecord(ev2, stream));
@@ -729,10 +743,12 @@ static int resample_device_locked(lanczos_ctx* ctx, const lanczos_desc* d, const
         return LANCZOS_OK;
     }
     bool prefix_front = false;  // the prefix rows went out on this stream in FRONT of the main kernel (register-only kernel)
+    int route_main = LANCZOS_ROUTE_MAIN_NONE;   // what lanczos_last_route reports: set where each launch is issued
     if (use_fast) {
         hipError_t e;
         if (lz::env().tile_kernel || !lz::march_supports(g)) {  // LANCZOS_TILE_KERNEL=1: the tile-per-workgroup kernel (A/B measurements)
             e = lz::fast_launch(*d, g, p->dev, p->fast, stream);
+            route_main = LANCZOS_ROUTE_MAIN_TILE;
         } else {
             lz::FrameGeom gm = g;
             if (!in_split) {   // (with timing on, every sub-launch commits its own event triple: what is timed is what is shipped)
@@ -778,6 +794,8 @@ static int resample_device_locked(lanczos_ctx* ctx, const lanczos_desc* d, const
                 e = hipSuccess;
             }
             if (e == hipSuccess) e = lz::march_launch(*d, gm, p->dev, p->fast, stream, &prefix_fused, &ctx->wg_tabs);
+            // (march_launch issues nothing for a strip that ends inside the prefix rows: its y_lo >= y_hi)
+            route_main = row0 + rows <= g.skip_rows ? LANCZOS_ROUTE_MAIN_NONE : LANCZOS_ROUTE_MAIN_MARCH;
         }
         if (e != hipSuccess) {
             ctx->last_hip = (int)e;
@@ -791,6 +809,7 @@ static int resample_device_locked(lanczos_ctx* ctx, const lanczos_desc* d, const
             return LANCZOS_ERR_HIP;
         }
         ctx->last_kernel = LANCZOS_KERNEL_FAST;
+        route_main = LANCZOS_ROUTE_MAIN_RATP;
     } else if (use_rat) {
         const int row_bytes = d->out_w * d->channels * d->bytes_per_sample;
         const int tiles_x = (row_bytes + lz::kRatTileRowBytes - 1) / lz::kRatTileRowBytes;
@@ -814,6 +833,7 @@ static int resample_device_locked(lanczos_ctx* ctx, const lanczos_desc* d, const
 #undef LZ_RAT
         LZ_HIP(ctx, hipGetLastError());
         ctx->last_kernel = LANCZOS_KERNEL_FAST;
+        route_main = LANCZOS_ROUTE_MAIN_RAT;
     } else {
         const int samples_w = d->out_w * d->channels;
         const int tiles_x = (samples_w + lz::kGenTileW - 1) / lz::kGenTileW;
@@ -825,7 +845,9 @@ static int resample_device_locked(lanczos_ctx* ctx, const lanczos_desc* d, const
             hipLaunchKernelGGL(lz::k_generic<uint16_t>, grid, dim3(lz::kGenTileW), 0, stream, g, p->dev);
         LZ_HIP(ctx, hipGetLastError());
         ctx->last_kernel = LANCZOS_KERNEL_GENERIC;
+        route_main = LANCZOS_ROUTE_MAIN_GENERIC;
     }
+    int route_prefix = prefix_fused ? LANCZOS_ROUTE_PREFIX_RIDING : (prefix_front ? LANCZOS_ROUTE_PREFIX_FRONT : LANCZOS_ROUTE_PREFIX_NONE);
     if (ev1 && !prefix_front) LZ_HIP(ctx, hipEventRecord(ev1, stream));  // start..middle = the main kernel
 
     if (has_prefix && !prefix_fused && !prefix_front) {
@@ -838,6 +860,7 @@ static int resample_device_locked(lanczos_ctx* ctx, const lanczos_desc* d, const
         dim3 grid((samples_w + bw - 1) / bw, frames);
 #define LZ_PREFIX_STREAM(T, TAPS) \
     hipLaunchKernelGGL((lz::k_prefix_stream<T, TAPS>), grid, dim3(128), 0, stream, g, p->dev, p->prefix.K, p->prefix.M)
+        route_prefix = streamed ? LANCZOS_ROUTE_PREFIX_STREAMED : LANCZOS_ROUTE_PREFIX_BEHIND;
         if (streamed) {
             if (d->bytes_per_sample == 1) {
                 if (d->a == 2) LZ_PREFIX_STREAM(uint8_t, 4);
@@ -865,6 +888,7 @@ static int resample_device_locked(lanczos_ctx* ctx, const lanczos_desc* d, const
 #undef LZ_PREFIX_STREAM
         LZ_HIP(ctx, hipGetLastError());
     }
+    route_launch(ctx, route_main, route_prefix);
     if (ev2) {
         LZ_HIP(ctx, hipEventRecord(ev2, stream));
         ctx->ev_prefix_first[ctx->ev_used / 3] = prefix_front ? 1 : 0;
@@ -879,6 +903,7 @@ int lanczos_resample_device(lanczos_ctx* ctx, const lanczos_desc* d, const void*
     int rc = lz::validate(d);
     if (rc != LANCZOS_OK) return rc;
     std::lock_guard<std::mutex> lock(ctx->mu);
+    route_begin(ctx);
     return resample_device_locked(ctx, d, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream_v);
 }
 
@@ -906,6 +931,7 @@ int lanczos_resample_host(lanczos_ctx* ctx, const lanczos_desc* d, const void* i
     std::lock_guard<std::mutex> lock(ctx->mu);
     LZ_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->stream) return LANCZOS_ERR_HIP;
+    route_begin(ctx);
     Plan* p = nullptr;
     rc = get_plan(ctx, d, ctx->stream, &p);   // (the pipeline's resample calls run on the context's stream)
     if (rc != LANCZOS_OK) return rc;
@@ -982,6 +1008,7 @@ static int layout_call(lanczos_ctx* ctx, bool to_interleaved, const void* src, v
     if (h > 65535 || frames > 65535) return LANCZOS_ERR_UNSUPPORTED;
     std::lock_guard<std::mutex> lock(ctx->mu);
     LZ_HIP(ctx, hipSetDevice(ctx->device));
+    route_begin(ctx);
     LZ_HIP(ctx, lz::layout_launch(to_interleaved, src, dst, w, h, channels, bytes_per_sample, frames, (hipStream_t)stream));
     return LANCZOS_OK;
 }
@@ -1032,8 +1059,11 @@ int lanczos_resample_planar_device(lanczos_ctx* ctx, const lanczos_desc* d, cons
     whole.out_rows = 0;
     rc = lanczos_resample_device(ctx, &whole, ctx->planar_in, ctx->planar_out, frames, 0, 0, stream);
     if (rc != LANCZOS_OK) return rc;
-    return lanczos_interleaved_to_planar_device(ctx, ctx->planar_out, d_out_planar, d->out_w, d->out_h, d->channels,
-                                                d->bytes_per_sample, frames, stream);
+    const int route = ctx->last_route;   // (the layout call behind it reports none: the planar call reports its resample)
+    rc = lanczos_interleaved_to_planar_device(ctx, ctx->planar_out, d_out_planar, d->out_w, d->out_h, d->channels,
+                                              d->bytes_per_sample, frames, stream);
+    if (rc == LANCZOS_OK) ctx->last_route = route;
+    return rc;
 }
 
 // ---- resize to any size (Pillow's contract; lanczos_resize.hip) ------------------------------------------------------
@@ -1136,6 +1166,7 @@ int lanczos_resize_device_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, con
     std::lock_guard<std::mutex> lock(ctx->mu);
     LZ_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
+    route_begin(ctx);
     // NULL = the legacy default stream, as lanczos_resample_device
     return lz::resize_device(ctx->resize, d, o, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
                              &ctx->last_kernel, &ctx->last_hip);
@@ -1155,6 +1186,7 @@ int lanczos_resize_host_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, const
     LZ_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->stream) return LANCZOS_ERR_HIP;
     if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
+    route_begin(ctx);
     return lz::resize_host(ctx->resize, d, o, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip);
 }
 
@@ -1179,6 +1211,7 @@ int lanczos_reduce_device(lanczos_ctx* ctx, int in_w, int in_h, int channels, in
     LZ_HIP(ctx, hipSetDevice(ctx->device));
     int rc = resize_state(ctx);
     if (rc != LANCZOS_OK) return rc;
+    route_begin(ctx);
     return lz::reduce_device(ctx->resize, in_w, in_h, channels, fx, fy, box, d_in, d_out, frames, in_frame_stride,
                              out_frame_stride, (hipStream_t)stream, &ctx->last_hip);
 }
@@ -1191,6 +1224,7 @@ int lanczos_reduce_host(lanczos_ctx* ctx, int in_w, int in_h, int channels, int 
     if (!ctx->stream) return LANCZOS_ERR_HIP;
     int rc = resize_state(ctx);
     if (rc != LANCZOS_OK) return rc;
+    route_begin(ctx);
     return lz::reduce_host(ctx->resize, in_w, in_h, channels, fx, fy, box, in, out, frames, ctx->stream, &ctx->last_hip);
 }
 

@@ -15,7 +15,7 @@ import lanczos_hls_amd as L  # noqa: E402
 import patterns as P  # noqa: E402
 
 # name -> (frames, sn, sd, a): a config 2 batch (k_march, prefix rows riding or in front), a periodic rational scale (k_ratp;
-# k_rat under LANCZOS_NO_RATP) and a deep in-place prefix (K = 99: k_prefix / k_prefix_stream behind k_rat)
+# k_rat under LANCZOS_NO_RATP) and a deep in-place prefix (K = 67: k_prefix behind k_rat)
 SWITCH_REQUESTS = {
     "config2_batch": (lambda: np.stack([P.noise(1080, 1920, 3, seed=1), P.dark_noise(1080, 1920, 3, seed=2)]), 2, 1, 3),
     "rational_3_2": (lambda: P.noise(270, 480, 3, seed=3)[None], 3, 2, 3),
@@ -32,6 +32,8 @@ def main(out_path):
             for mode, tag in ((L.MODE_EXACT, "exact"), (L.MODE_LSB1, "lsb1")):
                 res[f"{name}:{tag}"] = ctx.resample(frames, sn, sd, a, mode)
                 res[f"{name}:{tag}:kernel"] = np.array(ctx.last_kernel())
+                r = ctx.last_route()
+                res[f"{name}:{tag}:route"] = np.array([r.main, r.prefix, r.launches])
     finally:
         ctx.close()
     np.savez(out_path, **res)

@@ -148,8 +148,9 @@ def test_every_integer_scale_instance(ctx, mode):
     cases += [(np.uint16, c, s, a) for c in (3, 4) for s in (2, 3) for a in (3, 4)]
     for (dt, c, s, a) in cases:
         bps = np.dtype(dt).itemsize
-        for (w, h) in ((160, 45), (148, 37)):   # 160*c*bps is a 16-byte multiple for every case; 148 is not (but dword rows)
-            assert (w * c * bps) % 16 == (0 if w == 160 else (w * c * bps) % 16)
+        # 160*c*bps is a 16-byte multiple for every case; 148 is not for 1 and 3 channels, 149 is not for 4 (dword rows all)
+        for (w, h) in ((160, 45), (149 if c == 4 else 148, 37)):
+            assert ((w * c * bps) % 16 == 0) == (w == 160) and (w * s * c * bps) % 4 == 0
             for pat, seed in (("dark", 3), ("noise", 4)):
                 img = (P.dark_noise(h, w, c, seed=seed) if pat == "dark" else P.noise(h, w, c, seed=seed)) if dt == np.uint8 else \
                       (P.noise(h, w, c, seed=seed, dtype=np.uint16) >> (8 if pat == "dark" else 0)).astype(np.uint16)
@@ -157,6 +158,9 @@ def test_every_integer_scale_instance(ctx, mode):
                 got = ctx.resample(img, s, 1, a, mode)
                 _cmp(got, want, mode, f"{dt.__name__} c={c} {s}x a={a} {w}x{h} {pat}", _req(ctx, img, s, 1, a))
                 assert ctx.last_kernel() == L.KERNEL_FAST, (dt.__name__, c, s, a, w)
+                r = ctx.last_route()   # one frame: the prefix rows ride on k_march; behind the tile kernel they are k_prefix's
+                assert (r.main, r.prefix, r.launches) == ((L.ROUTE_MAIN_MARCH, L.ROUTE_PREFIX_RIDING, 1) if w == 160 else
+                                                          (L.ROUTE_MAIN_TILE, L.ROUTE_PREFIX_BEHIND, 1)), (dt.__name__, c, s, a, w, str(r))
 
 
 def test_sixteen_bit_exact_mode_split_weight_chains(ctx):
@@ -193,6 +197,11 @@ RATIONAL_SHAPES = [
 ]
 
 
+# the instances of k_ratp (lanczos_rational.hpp LZ_RATP_CONFIGS): (bytes per sample, channels, N, D, a)
+RATP_INSTANCES = {(1, 3, 4, 3, 3), (1, 3, 3, 2, 3), (1, 3, 5, 2, 3), (1, 3, 5, 4, 3), (1, 4, 4, 3, 3), (1, 4, 3, 2, 3), (1, 1, 4, 3, 3),
+                  (1, 1, 3, 2, 3), (1, 3, 4, 3, 2), (1, 3, 3, 2, 2), (2, 4, 3, 2, 3)}
+
+
 @pytest.mark.parametrize("mode", [L.MODE_EXACT, L.MODE_LSB1])
 @pytest.mark.parametrize("pattern", ["noise", "dark", "gradient", "blocks"])
 def test_rational_scales_fast_kernel(ctx, pattern, mode):
@@ -204,10 +213,16 @@ def test_rational_scales_fast_kernel(ctx, pattern, mode):
         got = ctx.resample(img, sn, sd, a, mode)
         _cmp(got, want, mode, f"{pattern} {w}x{h}x{c} {sn}/{sd} a={a}", _req(ctx, img, sn, sd, a))
         assert ctx.last_kernel() == L.KERNEL_FAST, (w, h, c, sn, sd, a)
+        assert ctx.last_route().main in (L.ROUTE_MAIN_RATP, L.ROUTE_MAIN_RAT), (w, h, c, sn, sd, a, str(ctx.last_route()))
+        if (1, c, sn, sd, a) not in RATP_INSTANCES:       # no k_ratp instance: the per-index kernel
+            assert ctx.last_route().main == L.ROUTE_MAIN_RAT, (w, h, c, sn, sd, a)
+        elif min(w, h) >= 64:                             # (frames of a few periods only are left to k_rat)
+            assert ctx.last_route().main == L.ROUTE_MAIN_RATP, (w, h, c, sn, sd, a)
     img16 = P.noise(60, 96, 4, seed=77, dtype=np.uint16)
     got = ctx.resample(img16, 3, 2, 3, mode)
     _cmp(got, _oracle(img16, 3, 2, 3), mode, "u16 3/2", _req(ctx, img16, 3, 2, 3))
     assert ctx.last_kernel() == L.KERNEL_FAST
+    assert (2, 4, 3, 2, 3) in RATP_INSTANCES and ctx.last_route().main == L.ROUTE_MAIN_RATP   # (the one 16-bit instance)
 
 
 def test_rational_fast_kernel_known_answer_and_speed(ctx):
@@ -262,6 +277,9 @@ def test_scales_close_to_one_deep_inplace_prefix(ctx):
         for mode in (L.MODE_EXACT, L.MODE_LSB1):
             got = ctx.resample(img, sn, sd, a, mode)
             _cmp(got, want, mode, f"deep prefix {sn}/{sd} K={K}", _req(ctx, img, sn, sd, a))
+            r = ctx.last_route()   # M + M2 rows of 32 columns or more fit the LDS at all four depths: k_prefix, behind k_rat
+            main = L.ROUTE_MAIN_RAT if (d.out_w * c) % 4 == 0 else L.ROUTE_MAIN_GENERIC   # (65 samples per row: k_generic)
+            assert (r.main, r.prefix) == (main, L.ROUTE_PREFIX_BEHIND), (sn, sd, str(r))
     # S = 1: every sample on an integer phase, the in-place pass one recurrence over the whole height per column
     # (full_TB.h:67-77) -- the output is the input except where the double noise of the ~1e-17 taps flips a dark sample
     for (w, h, c, a, gen) in [(64, 48, 3, 3, P.dark_noise), (40, 200, 1, 3, P.dark_noise), (33, 21, 4, 4, P.noise), (96, 64, 3, 2, P.noise)]:
@@ -271,6 +289,8 @@ def test_scales_close_to_one_deep_inplace_prefix(ctx):
         for mode in (L.MODE_EXACT, L.MODE_LSB1):
             got = ctx.resample(img, 4, 4, a, mode)
             _cmp(got, want, mode, f"S=1 {w}x{h}x{c} a={a}", _req(ctx, img, 4, 4, a))
+            r = ctx.last_route()
+            assert (r.main, r.prefix) == (L.ROUTE_MAIN_GENERIC, L.ROUTE_PREFIX_BEHIND), (w, h, str(r))
     assert (_oracle(P.dark_noise(48, 64, 3, seed=5), 1, 1, 3) != P.dark_noise(48, 64, 3, seed=5)).any()   # (the quirk is exercised)
     # Deeper than the row arrays of k_prefix: the streaming form of the recurrence (k_prefix_stream, rings of 24 rows).  S = 1 at 4K
     # height and 1025/1024 (K = 2 * 1025 + 1 > the frame height: every output row reads written rows) -- both shapes have
@@ -285,6 +305,9 @@ def test_scales_close_to_one_deep_inplace_prefix(ctx):
         for mode in (L.MODE_EXACT, L.MODE_LSB1):
             got = ctx.resample(img, sn, sd, a, mode)
             _cmp(got, want, mode, f"streamed prefix {sn}/{sd} {w}x{h}x{c} a={a} K={L.inplace_rows(d)}", _req(ctx, img, sn, sd, a))
+            r = ctx.last_route()   # (257/256 at 1200 rows of 8-bit samples: 1040 rows of 32 columns still fit, k_prefix serves it)
+            assert r.main == (L.ROUTE_MAIN_GENERIC if sn == sd else L.ROUTE_MAIN_RAT), (sn, sd, str(r))
+            assert r.prefix == (L.ROUTE_PREFIX_BEHIND if (sn, sd) == (257, 256) else L.ROUTE_PREFIX_STREAMED), (sn, sd, str(r))
     with pytest.raises(L.LanczosError) as e:       # S < 1: refused (the reference itself is out of bounds there)
         ctx.resample(P.noise(16, 16, 3), 3, 4, 3)
     assert e.value.code == L.ERR_UNSUPPORTED
@@ -718,6 +741,9 @@ def test_frame_strides_and_kernel_families(ctx, pad_in, pad_out):
         ctx.resample_device(d, d_in.data_ptr(), d_out.data_ptr(), frames, in_stride, out_stride,
                             torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
+        r = ctx.last_route()   # five frames: the prefix rows ride on k_march, k_prefix runs behind the tile kernel
+        assert (r.main, r.prefix) == ((L.ROUTE_MAIN_MARCH, L.ROUTE_PREFIX_RIDING) if in_stride % 16 == 0 else
+                                      (L.ROUTE_MAIN_TILE, L.ROUTE_PREFIX_BEHIND)), (pad_in, pad_out, str(r))
         got = d_out.cpu().numpy()
         for f in range(frames):
             g = got[f * out_stride:f * out_stride + out_fb].reshape(d.out_h, d.out_w, c)
@@ -744,6 +770,9 @@ def test_prefix_rows_ride_or_run_separately(ctx):
             y.zero_()
             ctx.resample_device(d, x.data_ptr(), y.data_ptr(), frames, 0, 0, torch.cuda.current_stream().cuda_stream)
             torch.cuda.synchronize()
+            r = ctx.last_route()
+            assert (r.main, r.prefix, r.launches) == (L.ROUTE_MAIN_MARCH, L.ROUTE_PREFIX_FRONT if frames == 96 else L.ROUTE_PREFIX_RIDING, 1), \
+                (frames, str(r))
             got = y.cpu().numpy()
             for f in (0, frames // 2, frames - 1):
                 _cmp(got[f], want, mode, f"{frames} frames, frame {f}", _req(ctx, img, sn, 1, a))
@@ -798,11 +827,11 @@ def test_first_use_inside_capture_then_eager_before_replay(sn, sd, mode):
     """The tap tables and the workgroup table of a shape first used inside stream capture are valid at once (they go up
     eagerly on a private stream; a copy queued on the capturing stream would run only at a replay): an eager call BEFORE any
     replay gives the right samples, the graph replays afterwards, also after an eager call of another shape, and a graph
-    that is dropped without ever being replayed leaves a usable plan behind.  2/1 is served by k_march, 3/2 by k_rat."""
+    that is dropped without ever being replayed leaves a usable plan behind.  2/1 is served by k_march, 3/2 by k_ratp."""
     import torch
     c = L.Context(0)
     try:
-        w, h, a = 120, 76 + 2 * mode + sd, 3                 # shapes no other test of this module uses
+        w, h, a = 128, 76 + 2 * mode + sd, 3                 # shapes no other test of this module uses; 16-byte rows: k_march
         img, img2 = P.gradient_noise(h, w, 3, seed=15), P.noise(h, w, 3, seed=16)
         d = L.make_desc(w, h, 3, sn, sd, a, 1, mode)
         x = torch.from_numpy(img).cuda()
@@ -818,6 +847,8 @@ def test_first_use_inside_capture_then_eager_before_replay(sn, sd, mode):
         c.resample_device(d, x.data_ptr(), y2.data_ptr(), 1, stream=torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         assert c.last_kernel() == L.KERNEL_FAST
+        r = c.last_route()
+        assert (r.main, r.prefix) == ((L.ROUTE_MAIN_MARCH, L.ROUTE_PREFIX_RIDING) if sd == 1 else (L.ROUTE_MAIN_RATP, L.ROUTE_PREFIX_BEHIND)), str(r)
         _cmp(y2.cpu().numpy(), _oracle(img, sn, sd, a), mode, "eager call before any replay", _req(c, img, sn, sd, a))
         assert int(y.max()) == 0
         x.copy_(torch.from_numpy(img2))
@@ -920,6 +951,17 @@ def test_production_switches_change_no_result(tmp_path):
         for name, (frames, sn, sd, a) in reqs.items():
             exact, lsb1 = res[f"{name}:exact"], res[f"{name}:lsb1"]
             fam = int(res[f"{name}:lsb1:kernel"])
+            for mtag in ("exact", "lsb1"):   # what each switch changed, and nothing else
+                main, prefix = (int(v) for v in res[f"{name}:{mtag}:route"][:2])
+                want_route = {"config2_batch": (L.ROUTE_MAIN_MARCH, L.ROUTE_PREFIX_RIDING), "rational_3_2": (L.ROUTE_MAIN_RATP, L.ROUTE_PREFIX_BEHIND),
+                              "deep_prefix_33_32": (L.ROUTE_MAIN_RAT, L.ROUTE_PREFIX_BEHIND)}[name]
+                if var == "LANCZOS_TILE_KERNEL" and name == "config2_batch":
+                    want_route = (L.ROUTE_MAIN_TILE, L.ROUTE_PREFIX_BEHIND)
+                if var == "LANCZOS_NO_RATP" and name == "rational_3_2":
+                    want_route = (L.ROUTE_MAIN_RAT, L.ROUTE_PREFIX_BEHIND)
+                if var == "LANCZOS_SEPARATE_PREFIX" and name == "config2_batch":
+                    want_route = (L.ROUTE_MAIN_MARCH, L.ROUTE_PREFIX_BEHIND)
+                assert (main, prefix) == want_route, f"{tag} {name} {mtag}: route {main}+{prefix}, expected {want_route}"
             for i in range(len(frames)):
                 _cmp(exact[i], want[name][i], L.MODE_EXACT, f"{tag} {name} frame {i}")
                 _cmp(lsb1[i], want[name][i], L.MODE_LSB1, f"{tag} {name} frame {i}", (frames[i], sn, sd, a, fam))
