@@ -224,13 +224,29 @@ int lanczos_device_copy(int device, void* dst, const void* src, size_t bytes, in
  * runs first into a 16-bit intermediate stored that way; a pass whose axis keeps its size is skipped, a resize that changes
  * neither axis is a plain copy.  The bytes are those of a Pillow build whose compiler does not contract the multiply and
  * the add into an FMA (the x86-64 wheels; checked against 12.2.0).  Frame strides stay in bytes; base pointers and strides
- * of a 16-bit request must be even.  Pillow has no 16-bit RGBA: LANCZOS_RESIZE_U16 | LANCZOS_RESIZE_ALPHA is refused. */
+ * of a 16-bit request must be even.  Pillow has no 16-bit RGBA: LANCZOS_RESIZE_U16 | LANCZOS_RESIZE_ALPHA is refused.
+ *
+ * With LANCZOS_RESIZE_F32 in the flag word the samples are IEEE float (1, 3 or 4 interleaved channels) and the result is what
+ * Pillow produces in mode F, bit for bit, every channel resized as an independent F plane.  Tap geometry and coefficients
+ * are exactly those of the 16-bit path (lanczos_resize_taps_f64_host / _ex), and one pass computes, per output sample,
+ *   ss = 0.0; for i = 0 .. count - 1 ascending: ss = ss + (double)sample[first + i] * k[i]   -- IEEE multiply, IEEE add, no FMA;
+ *   stored = (float)ss, rounded to nearest even.
+ * No clamp and no rounding to integer: a sum beyond FLT_MAX stores +-inf, a sum in the float denormal range stores the
+ * denormal (nothing is flushed, on load or on store), a tiny negative sum stores -0.0.  Exactly `count` taps are multiplied:
+ * a tap inside the window whose weight happens to be 0.0 is multiplied (a non-finite sample there gives NaN, as in Pillow),
+ * a sample outside the window never is, however the kernels pad their loops.  Output NaNs sit exactly where Pillow's sit;
+ * their sign and payload are not part of the contract (x86 and the GPU produce different default NaNs).  The horizontal pass
+ * runs first into a float intermediate stored that way; a pass whose axis keeps its size (idle box) is skipped, and a
+ * request with no pass is a plain copy.  There is no float alpha: the flag combines with no other flag.  Base pointers and
+ * frame strides (still in bytes) must be multiples of 4.  A source box works; reducing_gap does not (LANCZOS_ERR_BAD_ARG), and
+ * lanczos_reduce_* takes no floats: Pillow does reduce mode F, but its float box average is no double sum in row-major order
+ * and its summation order has not been pinned down -- not built rather than guessed. */
 typedef struct lanczos_resize_desc {
     int32_t in_w, in_h;     /* 1..65535 each */
     int32_t out_w, out_h;   /* 1..65535 each, independent of the input size and of each other */
-    int32_t channels;       /* 1, 3 or 4, interleaved; 8-bit samples, 16-bit with LANCZOS_RESIZE_U16 */
+    int32_t channels;       /* 1, 3 or 4, interleaved; 8-bit samples, 16-bit with LANCZOS_RESIZE_U16, float with LANCZOS_RESIZE_F32 */
     int32_t a;              /* 2, 3 or 4 (3 = Pillow's LANCZOS) */
-    int32_t reserved[2];    /* reserved[0]: flags, 0, LANCZOS_RESIZE_ALPHA or LANCZOS_RESIZE_U16; reserved[1]: must be 0 */
+    int32_t reserved[2];    /* reserved[0]: flags, 0 or one of LANCZOS_RESIZE_ALPHA / _U16 / _F32; reserved[1]: must be 0 */
 } lanczos_resize_desc;
 
 /* flag of lanczos_resize_desc.reserved[0]: channel 3 is straight alpha (Pillow's RGBA mode); channels must be 4 */
@@ -238,6 +254,8 @@ typedef struct lanczos_resize_desc {
 /* flag of lanczos_resize_desc.reserved[0]: samples are native-endian uint16_t (Pillow's I;16 arithmetic, see above); not
  * together with LANCZOS_RESIZE_ALPHA */
 #define LANCZOS_RESIZE_U16 4
+/* flag of lanczos_resize_desc.reserved[0]: samples are float (Pillow's mode F arithmetic, see above); with no other flag */
+#define LANCZOS_RESIZE_F32 16
 
 /* forced path of lanczos_resize_force (tests and A/B runs only) */
 #define LANCZOS_RESIZE_AUTO 0
@@ -249,16 +267,17 @@ int lanczos_resize_desc_init(lanczos_resize_desc* d, int in_w, int in_h, int out
 /* the same with the flag word (lanczos_resize_desc_init gives 0) */
 int lanczos_resize_desc_init_ex(lanczos_resize_desc* d, int in_w, int in_h, int out_w, int out_h, int channels, int a,
                                 int flags);
-/* LANCZOS_ERR_BAD_ARG: size, channels, a, a flag word other than 0, LANCZOS_RESIZE_ALPHA or LANCZOS_RESIZE_U16,
- * LANCZOS_RESIZE_ALPHA without four channels */
+/* LANCZOS_ERR_BAD_ARG: size, channels, a, a flag word other than 0, LANCZOS_RESIZE_ALPHA, LANCZOS_RESIZE_U16 or
+ * LANCZOS_RESIZE_F32, LANCZOS_RESIZE_ALPHA without four channels */
 int lanczos_resize_validate(const lanczos_resize_desc* d);
 /* Fixed-point tables of one axis (0 = horizontal, 1 = vertical): output o reads inputs first[o] .. first[o] + count[o] - 1
  * with coeffs[o * ksize + i] (i < count[o]; zero beyond).  *ksize = 2 * ceil(support) + 1.  With first, count and coeffs all
  * NULL only *ksize is returned; otherwise all three must hold out (and out * ksize) elements. */
 int lanczos_resize_taps_host(const lanczos_resize_desc* d, int axis, int32_t* first, int32_t* count, int32_t* coeffs,
                              int* ksize);
-/* The double tables of the 16-bit path, same shapes and rules: first and count are those of lanczos_resize_taps_host,
- * coeffs[o * ksize + i] is the normalised weight itself.  Neither function looks at LANCZOS_RESIZE_U16. */
+/* The double tables of the 16-bit and float paths, same shapes and rules: first and count are those of
+ * lanczos_resize_taps_host, coeffs[o * ksize + i] is the normalised weight itself.  Neither function looks at
+ * LANCZOS_RESIZE_U16 or LANCZOS_RESIZE_F32. */
 int lanczos_resize_taps_f64_host(const lanczos_resize_desc* d, int axis, int32_t* first, int32_t* count, double* coeffs,
                                  int* ksize);
 /* Diagnostic: what lanczos_resize_device would launch for this request and `frames` frames under LANCZOS_RESIZE_AUTO (the
@@ -267,7 +286,8 @@ int lanczos_resize_taps_f64_host(const lanczos_resize_desc* d, int axis, int32_t
  * other fields are then 0.  fused = 1: the fused kernel instance with K horizontal taps on a grid of strips x chunks
  * workgroups per frame; a workgroup marches down rows_per_chunk output rows in blocks of 8 with an LDS ring of ring_rows
  * rows and a staging area of stage_rows input rows of stage_dw dwords; lds_bytes is their sum.  A 16-bit request has ring
- * and staging rows of 2-byte samples and narrower strips, so it meets the 80 KiB condition at smaller reductions. */
+ * and staging rows of 2-byte samples and narrower strips, so it meets the 80 KiB condition at smaller reductions; a float
+ * request has rows of 4-byte samples in strips of 128 (one channel) or 64 pixels and meets it at smaller ones still. */
 typedef struct lanczos_resize_plan {
     int32_t fused;
     int32_t K, strips, rows_per_chunk, chunks, ring_rows, stage_rows, stage_dw, lds_bytes;
@@ -297,7 +317,7 @@ int lanczos_resize_force(lanczos_ctx* ctx, int path);
  * + 0.5), in), weights, normalisation, the 22-bit rounding or the double tables of 16-bit requests -- is the recipe above.
  * first indexes the WHOLE source axis and is clipped to the whole source, not to the box: pixels outside the box contribute
  * near its edges.  A pass runs iff out != in || b0f != 0 || b1f != in, so a sub-pixel shift at equal size runs the pass; with
- * both axes idle the call is the plain copy.  Every sample type takes a box (8-bit, LANCZOS_RESIZE_ALPHA, LANCZOS_RESIZE_U16).
+ * both axes idle the call is the plain copy.  Every sample type takes a box (8-bit, LANCZOS_RESIZE_ALPHA, _U16, _F32).
  * The two-pass path produces only the intermediate rows the vertical taps read, and sizes its scratch by them.
  *
  * reducing_gap = g (0 = none, otherwise g >= 1; below 1 or NaN: LANCZOS_ERR_BAD_ARG), as Image.resize(..., reducing_gap=g):
@@ -309,7 +329,8 @@ int lanczos_resize_force(lanczos_ctx* ctx, int path);
  *   ((x0 - rb0) / fx, (y0 - rb1) / fy, (x1 - rb0) / fx, (y1 - rb1) / fy) (divided in double, rounded to float after).
  * The result is Pillow's for the same arguments; it is NOT the resize without a gap (it differs from it in general).
  * Pillow silently drops reducing_gap in mode RGBA and raises for I;16, so neither has an oracle: a gap together with
- * LANCZOS_RESIZE_ALPHA or LANCZOS_RESIZE_U16 is LANCZOS_ERR_BAD_ARG.  fx * fy >= 65536: LANCZOS_ERR_UNSUPPORTED.
+ * LANCZOS_RESIZE_ALPHA or LANCZOS_RESIZE_U16 is LANCZOS_ERR_BAD_ARG, and so is one with LANCZOS_RESIZE_F32 (not built, see
+ * above).  fx * fy >= 65536: LANCZOS_ERR_UNSUPPORTED.
  * The reduced frames live in context scratch under the rules of the two-pass intermediate (one stream at a time per context;
  * a captured launch pins the block; a captured graph must not outlive its context). */
 typedef struct lanczos_resize_opts {
@@ -353,7 +374,7 @@ int lanczos_resize_host_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, const
  * column and row of blocks may be ragged and then divide by their own pixel count d, in uint32:
  *   out = ((sum + d / 2) * m(d)) >> 24,  m(d) = floor(2^24 / d)
  * (what Pillow's single-precision 4294967296.0f / (256 * d) gives for every d < 65536).  fx * fy >= 65536 and frames of 2^31
- * bytes or more: LANCZOS_ERR_UNSUPPORTED.  Pillow refuses I;16 here; there is no 16-bit and no alpha-aware reduce. */
+ * bytes or more: LANCZOS_ERR_UNSUPPORTED.  Pillow refuses I;16 here; there is no 16-bit, no float and no alpha-aware reduce. */
 int lanczos_reduce_size(int in_w, int in_h, int fx, int fy, const int32_t* box, int* out_w, int* out_h);   /* host only */
 /* Device buffers, asynchronous on `stream`; frame strides in bytes, 0 = tightly packed; the base may be any byte address. */
 int lanczos_reduce_device(lanczos_ctx* ctx, int in_w, int in_h, int channels, int fx, int fy, const int32_t* box,

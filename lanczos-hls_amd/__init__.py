@@ -33,6 +33,7 @@ ROUTE_PREFIX_NAMES = ("none", "riding", "front", "behind", "streamed")
 RESIZE_AUTO, RESIZE_FUSED, RESIZE_TWO_PASS = 0, 1, 2   # lanczos_resize_force
 RESIZE_ALPHA = 1   # flag of lanczos_resize_desc.reserved[0]: channel 3 of 4 is straight alpha (Pillow's RGBA mode)
 RESIZE_U16 = 4     # flag of lanczos_resize_desc.reserved[0]: native-endian uint16 samples (Pillow's I;16 arithmetic)
+RESIZE_F32 = 16    # flag of lanczos_resize_desc.reserved[0]: float samples (Pillow's mode F arithmetic); with no other flag
 
 # every symbol include/lanczos_hip.h declares (tests check the library exports exactly these)
 ABI_SYMBOLS = [
@@ -266,14 +267,15 @@ def taps_host(desc, axis):
     return first, w
 
 
-def resize_desc(in_w, in_h, out_w, out_h, channels, a=3, alpha=False, bits=8):
+def resize_desc(in_w, in_h, out_w, out_h, channels, a=3, alpha=False, bits=8, f32=False):
     """A validated lanczos_resize_desc (Pillow's contract: any output size, downscaling included).  alpha: the fourth of
     four channels is straight alpha, resized as Pillow's mode RGBA (premultiplied inside the kernels).  bits: 8, or 16 for
-    uint16 samples resized as Pillow's mode I;16 (double accumulation, Pillow's wrapping store); not with alpha."""
+    uint16 samples resized as Pillow's mode I;16 (double accumulation, Pillow's wrapping store); not with alpha.  f32: float
+    samples resized as Pillow's mode F (double accumulation, stored as float, no clamp); not with alpha or bits=16."""
     if bits not in (8, 16):
         raise LanczosError(ERR_BAD_ARG, "resize_desc: bits must be 8 or 16")
     d = ResizeDesc()
-    flags = (RESIZE_ALPHA if alpha else 0) | (RESIZE_U16 if bits == 16 else 0)
+    flags = (RESIZE_ALPHA if alpha else 0) | (RESIZE_U16 if bits == 16 else 0) | (RESIZE_F32 if f32 else 0)
     _check(_lib().lanczos_resize_desc_init_ex(ctypes.byref(d), in_w, in_h, out_w, out_h, channels, a, flags),
            "lanczos_resize_desc_init_ex")
     return d
@@ -320,7 +322,7 @@ def resize_taps_host(desc, axis, box=None, reducing_gap=None, opts=None):
 
 
 def resize_taps_f64_host(desc, axis, box=None, reducing_gap=None, opts=None):
-    """Double tables of one axis, what 16-bit requests run on: (first[out] int32, count[out] int32, coeffs[out][ksize]
+    """Double tables of one axis, what 16-bit and float requests run on: (first[out] int32, count[out] int32, coeffs[out][ksize]
     float64); first and count are those of resize_taps_host.  box / reducing_gap / opts as resize_taps_host."""
     ks = ctypes.c_int()
     if box is None and reducing_gap is None and opts is None:
@@ -497,6 +499,29 @@ class Context:
                    "lanczos_resize_host")
         else:
             _check(_lib().lanczos_resize_host_ex(self._h, ctypes.byref(d), _opts_ref(d, box, reducing_gap, None),
+                                                 x.ctypes.data, out.ctypes.data, f), "lanczos_resize_host_ex")
+        if img.ndim == 2:
+            return out[0, :, :, 0]
+        return out if img.ndim == 4 else out[0]
+
+    def resize_f32(self, img, out_w, out_h, a=3, box=None):
+        """img: float32 [H][W], [H][W][C] or [F][H][W][C] (C = 1, 3 or 4) -> the same layout at out_h x out_w, every channel
+        bit for bit what Pillow's Image.resize((out_w, out_h), Image.LANCZOS, box) gives for it as a mode F plane (a = 3):
+        double accumulation over exactly the window's taps, stored as float -- no clamp, inf on overflow, denormals kept, NaN
+        where Pillow has NaN.  box as Context.resize.  No alpha and no reducing_gap for floats."""
+        img = np.ascontiguousarray(img)
+        if img.dtype != np.float32 or img.ndim not in (2, 3, 4):
+            raise LanczosError(ERR_BAD_ARG, "resize_f32: expected a float32 [H][W], [H][W][C] or [F][H][W][C] array")
+        x = img.reshape(img.shape + (1,)) if img.ndim == 2 else img
+        x = x if x.ndim == 4 else x[None]
+        f, h, w, c = x.shape
+        d = resize_desc(w, h, out_w, out_h, c, a, f32=True)
+        out = np.empty((f, out_h, out_w, c), dtype=np.float32)
+        if box is None:
+            _check(_lib().lanczos_resize_host(self._h, ctypes.byref(d), x.ctypes.data, out.ctypes.data, f),
+                   "lanczos_resize_host")
+        else:
+            _check(_lib().lanczos_resize_host_ex(self._h, ctypes.byref(d), _opts_ref(d, box, None, None),
                                                  x.ctypes.data, out.ctypes.data, f), "lanczos_resize_host_ex")
         if img.ndim == 2:
             return out[0, :, :, 0]

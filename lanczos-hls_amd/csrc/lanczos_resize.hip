@@ -18,6 +18,9 @@
 // LANCZOS_RESIZE_U16 (16-bit samples, Pillow's I;16): the same tap geometry with double coefficients and Pillow's double
 // accumulation; tables, cache, planning and dispatch are here, the kernels in lanczos_resize16.hip.
 //
+// LANCZOS_RESIZE_F32 (float samples, Pillow's mode F): the double tables and cache entries of the 16-bit path, a float
+// intermediate and no clamp; the kernels are in lanczos_resize32.hip.
+//
 // A source box (lanczos_resize_opts) only changes the tables: an axis is built over a span of the source given as two floats,
 // `first` still indexes the whole axis, and the kernels are the ones above.  reducing_gap puts lanczos_reduce.hip in front:
 // reduce into context scratch, then the resize of the reduced frames with the box that remains (resize_resolve).
@@ -44,8 +47,10 @@ int resize_validate(const lanczos_resize_desc* d) {
         if (s < 1 || s > kResizeMaxSize) return LANCZOS_ERR_BAD_ARG;
     if (d->channels != 1 && d->channels != 3 && d->channels != 4) return LANCZOS_ERR_BAD_ARG;
     if (d->a < 2 || d->a > 4) return LANCZOS_ERR_BAD_ARG;
-    if ((d->reserved[0] & ~(LANCZOS_RESIZE_ALPHA | LANCZOS_RESIZE_U16)) != 0 || d->reserved[1] != 0) return LANCZOS_ERR_BAD_ARG;
+    constexpr int kFlags = LANCZOS_RESIZE_ALPHA | LANCZOS_RESIZE_U16 | LANCZOS_RESIZE_F32;
+    if ((d->reserved[0] & ~kFlags) != 0 || d->reserved[1] != 0) return LANCZOS_ERR_BAD_ARG;
     if ((d->reserved[0] & LANCZOS_RESIZE_ALPHA) && (d->reserved[0] & LANCZOS_RESIZE_U16)) return LANCZOS_ERR_BAD_ARG;
+    if ((d->reserved[0] & LANCZOS_RESIZE_F32) && d->reserved[0] != LANCZOS_RESIZE_F32) return LANCZOS_ERR_BAD_ARG;
     if ((d->reserved[0] & LANCZOS_RESIZE_ALPHA) && d->channels != 4) return LANCZOS_ERR_BAD_ARG;
     return LANCZOS_OK;
 }
@@ -133,8 +138,10 @@ int resize_resolve(const lanczos_resize_desc* d, const lanczos_resize_opts* o, R
         if (!(box[1] >= 0.0 && box[1] < box[3] && box[3] <= d->in_h)) return LANCZOS_ERR_BAD_ARG;
         gap = o->reducing_gap;
         if (gap != 0.0 && !(gap >= 1.0)) return LANCZOS_ERR_BAD_ARG;   // NaN included
-        // Pillow drops the gap in mode RGBA and refuses it for I;16: no oracle for either
-        if (gap != 0.0 && (d->reserved[0] & (LANCZOS_RESIZE_ALPHA | LANCZOS_RESIZE_U16))) return LANCZOS_ERR_BAD_ARG;
+        // Pillow drops the gap in mode RGBA and refuses it for I;16: no oracle for either.  It does reduce mode F, but the
+        // summation order of its float box average is not pinned down: not built
+        if (gap != 0.0 && (d->reserved[0] & (LANCZOS_RESIZE_ALPHA | LANCZOS_RESIZE_U16 | LANCZOS_RESIZE_F32)))
+            return LANCZOS_ERR_BAD_ARG;
     }
     if (gap != 0.0) {
         const double ex = (box[2] - box[0]) / d->out_w / gap, ey = (box[3] - box[1]) / d->out_h / gap;
@@ -278,7 +285,7 @@ struct RsFused {
 
 template <int C>
 struct RsStrip {
-    static constexpr int SW = rs_strip_width(C, false);   // output pixels per strip
+    static constexpr int SW = rs_strip_width(C, 1);   // output pixels per strip
     static constexpr int RL = kRsThreads / SW;    // input rows per horizontal round
     static constexpr int RDW = SW * C / 4;        // ring row in dwords
     static constexpr int WPR = RDW / 64;          // waves per ring row in the vertical pass
@@ -554,13 +561,13 @@ static int rs_scratch(ResizeState* st, ResizeState::Block* blk, size_t bytes, hi
 // the fused kernel's launch shape for this request, both of whose passes run (false: it cannot run it)
 bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H, const ResizeAxisHost& V, int frames,
                    RsFusedPlan* fp) {
-    const bool u16 = resize_u16(d);
-    const int C = d->channels * (u16 ? 2 : 1);   // bytes per pixel
+    const int bps = resize_bps(d);
+    const int C = d->channels * bps;   // bytes per pixel
     if ((long long)d->in_w * d->in_h * C + 4 >= (1ll << 31)) return false;   // 32-bit buffer offsets
     if ((long long)d->out_w * d->out_h * C >= (1ll << 31)) return false;
-    fp->K = u16 ? rs16_bucket(H.ksize) : rs_bucket(H.ksize);
+    fp->K = bps > 1 ? rs16_bucket(H.ksize) : rs_bucket(H.ksize);
     if (!fp->K) return false;
-    const int SW = rs_strip_width(d->channels, u16);
+    const int SW = rs_strip_width(d->channels, bps);
     const int NE = (fp->K * C + 3) / 4;
     fp->strips = (d->out_w + SW - 1) / SW;
     int span_dw = 0;
@@ -601,7 +608,7 @@ int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o,
     for (int i = 0; i < 4; i++) out->safe_box[i] = r.rb[i], out->inner_box[i] = r.inner_box[i];
     out->reduced_w = r.inner.in_w, out->reduced_h = r.inner.in_h;
     out->pass_h = r.need_h, out->pass_v = r.need_v;
-    const bool u16 = resize_u16(d);
+    const bool u16 = resize_bps(d) > 1;   // the double tables
     ResizeAxisHost H, V;
     if (r.need_v) {
         if (!resize_build_axis(r.inner.in_h, r.inner.out_h, d->a, r.v, &V, u16)) return LANCZOS_ERR_UNSUPPORTED;
@@ -682,8 +689,9 @@ static hipError_t rs_launch_pass(bool horizontal, const RsPass& p0, int rows, in
 static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh, RsSpan sv, const uint8_t* in, uint8_t* out,
                         int frames, size_t in_fs, size_t out_fs, hipStream_t stream, int* last_kernel, int* last_hip) {
     const int C = d->channels;
-    const bool u16 = resize_u16(d);
-    const size_t B = u16 ? 2 : 1;   // bytes per sample
+    const size_t B = (size_t)resize_bps(d);   // bytes per sample
+    const bool f32 = B == 4;
+    const bool u16 = B > 1;   // samples wider than a byte: the double tables and the kernels of their own translation units
     const size_t in_frame = (size_t)d->in_w * d->in_h * C * B;
     const bool capturing = stream_capturing(stream);
     const bool need_h = rs_axis_runs(d->in_w, d->out_w, sh), need_v = rs_axis_runs(d->in_h, d->out_h, sv);
@@ -709,13 +717,15 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     const size_t in_pitch = (size_t)d->in_w * C * B;
     hipError_t e = hipSuccess;
     if (fused) {
-        e = u16 ? rs16_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream)
-                : rs_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream);
+        e = f32   ? rs32_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream)
+            : u16 ? rs16_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream)
+                  : rs_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream);
         *last_kernel = LANCZOS_KERNEL_RESIZE_FUSED;
     } else if (!need_h && !need_v) {   // Pillow returns a copy (also of RGBA: no premultiply round trip)
         e = hipMemcpy2DAsync(out, out_fs, in, in_fs, in_frame, frames, hipMemcpyDeviceToDevice, stream);
         *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
     } else if (u16) {
+        const auto launch_pass = f32 ? rs32_launch_pass : rs16_launch_pass;
         const uint8_t* mid = in;   // what the vertical pass reads
         size_t v_fs = in_fs;
         if (need_h) {
@@ -726,13 +736,13 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
                 if (rc != LANCZOS_OK) return rc;
                 dst = (uint8_t*)st->scratch.p, dst_fs = mid_fs;
             }
-            e = rs16_launch_pass(true, H, C, in + (size_t)mid_row0 * in_pitch, in_fs, (size_t)d->in_w * C, dst, dst_fs,
-                                 (size_t)d->out_w * C, d->out_w * C, mid_rows, frames, stream);
+            e = launch_pass(true, H, C, in + (size_t)mid_row0 * in_pitch, in_fs, (size_t)d->in_w * C, dst, dst_fs,
+                            (size_t)d->out_w * C, d->out_w * C, mid_rows, frames, stream);
             mid = (const uint8_t*)((uintptr_t)dst - (uintptr_t)((size_t)mid_row0 * mid_pitch)), v_fs = dst_fs;
         }
         if (e == hipSuccess && need_v)
-            e = rs16_launch_pass(false, V, C, mid, v_fs, (size_t)d->out_w * C, out, out_fs, (size_t)d->out_w * C,
-                                 d->out_w * C, d->out_h, frames, stream);
+            e = launch_pass(false, V, C, mid, v_fs, (size_t)d->out_w * C, out, out_fs, (size_t)d->out_w * C, d->out_w * C,
+                            d->out_h, frames, stream);
         *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
     } else {
         RsPass ph{}, pv{};
@@ -787,12 +797,12 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_r
     int rc = resize_resolve(d, o, &r);
     if (rc != LANCZOS_OK) return rc;
     const int C = d->channels;
-    const size_t B = resize_u16(d) ? 2 : 1;   // bytes per sample
+    const size_t B = (size_t)resize_bps(d);   // bytes per sample
     const size_t in_frame = (size_t)d->in_w * d->in_h * C * B, out_frame = (size_t)d->out_w * d->out_h * C * B;
     const size_t in_fs = in_frame_stride ? in_frame_stride : in_frame;
     const size_t out_fs = out_frame_stride ? out_frame_stride : out_frame;
     if (in_fs < in_frame || out_fs < out_frame) return LANCZOS_ERR_BAD_ARG;
-    if (B == 2 && (((uintptr_t)d_in | (uintptr_t)d_out | in_fs | out_fs) & 1) != 0) return LANCZOS_ERR_BAD_ARG;
+    if ((((uintptr_t)d_in | (uintptr_t)d_out | in_fs | out_fs) & (B - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
     const uint8_t* in = (const uint8_t*)d_in;
     if (r.reduces()) {   // reducing_gap: reduce into context scratch, then resize the reduced frames
         int rb[4];
@@ -828,8 +838,8 @@ static hipError_t rs_grow_stage(ResizeState* st, void** p, size_t* have, size_t 
 
 int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* in, void* out,
                 int frames, hipStream_t stream, int* last_kernel, int* last_hip) {
-    const size_t B = resize_u16(d) ? 2 : 1;
-    if (B == 2 && (((uintptr_t)in | (uintptr_t)out) & 1) != 0) return LANCZOS_ERR_BAD_ARG;
+    const size_t B = (size_t)resize_bps(d);
+    if ((((uintptr_t)in | (uintptr_t)out) & (B - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
     const size_t in_bytes = (size_t)d->in_w * d->in_h * d->channels * B * frames;
     const size_t out_bytes = (size_t)d->out_w * d->out_h * d->channels * B * frames;
     hipError_t e = rs_grow_stage(st, &st->stage_in, &st->stage_in_bytes, in_bytes, stream);

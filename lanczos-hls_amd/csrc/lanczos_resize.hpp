@@ -1,6 +1,7 @@
 // lanczos_resize.hpp -- resize to any size with Pillow's Lanczos contract (include/lanczos_hip.h, lanczos_resize_*):
 // host tap tables, their per-context cache, and the entry points lanczos_api.hip forwards to.  The kernels live in
-// lanczos_resize.hip; those of 16-bit requests (LANCZOS_RESIZE_U16, double coefficients) in lanczos_resize16.hip.
+// lanczos_resize.hip; those of 16-bit requests (LANCZOS_RESIZE_U16, double coefficients) in lanczos_resize16.hip and those of
+// float requests (LANCZOS_RESIZE_F32, the same double tables) in lanczos_resize32.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,7 +25,7 @@ struct ResizeAxisHost {
     int in_n = 0, out_n = 0, a = 0, ksize = 0;
     double scale = 1.0;                          // source pixels per output pixel: the box's extent / out_n
     std::vector<int32_t> first, count, coeffs;   // [out_n], [out_n], [out_n][ksize]
-    std::vector<double> coeffs64;                // [out_n][ksize]: the 16-bit path's tables, which have no `coeffs`
+    std::vector<double> coeffs64;                // [out_n][ksize]: the 16-bit and float paths' tables, which have no `coeffs`
 };
 // The source interval of one axis as Pillow's C sees it: both ends rounded to float.  The whole axis is (0, in_n).
 struct RsSpan {
@@ -57,13 +58,19 @@ inline void rs_mid_rows(const ResizeAxisHost& V, int* row0, int* rows) {
 }
 
 inline bool resize_u16(const lanczos_resize_desc* d) { return (d->reserved[0] & LANCZOS_RESIZE_U16) != 0; }
+inline bool resize_f32(const lanczos_resize_desc* d) { return (d->reserved[0] & LANCZOS_RESIZE_F32) != 0; }
+// bytes per sample: 1, 2 (LANCZOS_RESIZE_U16) or 4 (LANCZOS_RESIZE_F32); samples wider than a byte run on the double tables
+inline int resize_bps(const lanczos_resize_desc* d) { return resize_f32(d) ? 4 : resize_u16(d) ? 2 : 1; }
 
 // launch geometry both translation units share
 constexpr int kRsThreads = 256;
 constexpr int kRsOB = 8;             // output rows per march step of the fused kernels
 constexpr int kRsLoadBatch = 16;     // staging loads in flight per thread
-// output pixels per strip of the fused kernels: ring rows of 256 / 768 / 256 bytes (8-bit), 256 / 768 / 512 bytes (16-bit)
-constexpr int rs_strip_width(int channels, bool u16) { return channels == 4 ? 64 : u16 ? 128 : 256; }
+// output pixels per strip of the fused kernels by channels and bytes per sample: ring rows of 256 / 768 / 256 bytes (8-bit),
+// 256 / 768 / 512 bytes (16-bit), 512 / 768 / 1024 bytes (float)
+constexpr int rs_strip_width(int channels, int bps) {
+    return bps == 4 ? (channels == 1 ? 128 : 64) : channels == 4 ? 64 : bps == 2 ? 128 : 256;
+}
 
 // The fused kernel's launch shape for a request (false: it cannot run it).  H and V are the tables of the two axes, both of
 // which change size.  lanczos_resize_device plans with it; lanczos_resize_plan_host reports what it returns.
@@ -138,6 +145,14 @@ hipError_t rs16_launch_fused(const lanczos_resize_desc* d, const RsFusedPlan& fp
                              const uint8_t* in, uint8_t* out, size_t in_fs, size_t out_fs, int frames, hipStream_t stream);
 // one pass of the two-pass path over `rows` rows of `n_cols` samples: src / dst row pitches in samples
 hipError_t rs16_launch_pass(bool horizontal, const ResizeAxis* ax, int channels, const uint8_t* src, size_t src_fs,
+                            size_t src_pitch, uint8_t* dst, size_t dst_fs, size_t dst_pitch, int n_cols, int rows, int frames,
+                            hipStream_t stream);
+
+// float requests (lanczos_resize32.hip): the same two launches with 4-byte samples; the fused instances have the tap counts of
+// rs16_bucket
+hipError_t rs32_launch_fused(const lanczos_resize_desc* d, const RsFusedPlan& fp, const ResizeAxis* H, const ResizeAxis* V,
+                             const uint8_t* in, uint8_t* out, size_t in_fs, size_t out_fs, int frames, hipStream_t stream);
+hipError_t rs32_launch_pass(bool horizontal, const ResizeAxis* ax, int channels, const uint8_t* src, size_t src_fs,
                             size_t src_pitch, uint8_t* dst, size_t dst_fs, size_t dst_pitch, int n_cols, int rows, int frames,
                             hipStream_t stream);
 

@@ -88,7 +88,7 @@ struct Rs16Fused {
 
 template <int C>
 struct Rs16Strip {
-    static constexpr int SW = rs_strip_width(C, true);   // output pixels per strip
+    static constexpr int SW = rs_strip_width(C, 2);   // output pixels per strip
     static constexpr int RL = kRsThreads / SW;           // input rows per horizontal round
     static constexpr int RDW = SW * C / 2;               // ring row in dwords (two samples each)
     static constexpr int WPR = RDW / 64;                 // waves per ring row in the vertical pass

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """resize_speed.py -- speed of the resize-to-any-size entry (lanczos_resize_device) on one MI355X.
 
-    python scripts/resize_speed.py [--steps K] [--warmup W] [--rounds R] [--only W1,W3,A1,U1] [--routes rgbx,three_step]
+    python scripts/resize_speed.py [--steps K] [--warmup W] [--rounds R] [--only W1,W3,A1,U1,F1] [--routes rgbx,three_step]
                                    [--pillow]
 
 One JSON line per (workload, path).  Discipline as bench.py's: the frames are resident in HBM and the steps cycle through
@@ -27,6 +27,9 @@ the flag runs rgbx,three_step).
 U1 and U4 are W1's and W4's shapes with 16-bit samples (LANCZOS_RESIZE_U16, Pillow's mode I;16): the same three paths, the
 same discipline, twice the compulsory bytes.
 
+F1 and F4 are W1's and W4's shapes with float samples (LANCZOS_RESIZE_F32, Pillow's mode F; uniform [0, 1) inputs): the same
+three paths, four times the compulsory bytes.  They run on request (--only F1,F4) and need a build with the flag.
+
 R5 is W5's shape (3840x2160 -> 160x90, 32 frames) with reducing_gap: routes `plain` (W5 as it is: two-pass, 145 vertical
 taps), `gap2` and `gap3` (reduce 12x12 / 8x8 into context scratch, then the fused kernel), `reduce12` (lanczos_reduce_device
 12x12 alone) and `copy` (a device-to-device copy of the same source bytes, which moves twice what the reduction moves),
@@ -39,7 +42,7 @@ differently, so the bytes are compared between the paths of each, not between bo
 request (--only R5,B1,B2); they need a build with lanczos_resize_device_ex.
 
 --pillow adds Pillow's single-core time of one frame of each workload (if Pillow imports; else "not available"); for U1 and
-U4 that is the time of one I;16 plane (a frame has three).
+U4 that is the time of one I;16 plane (a frame has three), for F1 and F4 that of one F plane.
 """
 import argparse
 import json
@@ -67,6 +70,10 @@ U16_WORKLOADS = {   # W1's and W4's shapes, 16-bit samples
     "U1": (3840, 2160, 1920, 1080, 3, 3, 32),
     "U4": (1920, 1080, 3840, 2160, 3, 3, 32),
 }
+F32_WORKLOADS = {   # W1's and W4's shapes, float samples
+    "F1": (3840, 2160, 1920, 1080, 3, 3, 32),
+    "F4": (1920, 1080, 3840, 2160, 3, 3, 32),
+}
 RGBA_WORKLOADS = {   # W1's and W4's shapes, four channels
     "A1": (3840, 2160, 1920, 1080, 4, 3, 32),
     "A4": (1920, 1080, 3840, 2160, 4, 3, 32),
@@ -81,9 +88,14 @@ def run(name, spec, args, ctx, torch, bits=8):
     step_in = f * in_fb
     sets = max(2, -(-2 * 256 * 2 ** 20 // step_in) + 1)
     gen = torch.Generator(device="cuda").manual_seed(7)
-    xs = [torch.randint(0, 256, (f * in_fb,), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(sets)]
+    if bits == 32:
+        xs = [torch.rand(f * in_fb // 4, dtype=torch.float32, device="cuda", generator=gen).view(torch.uint8)
+              for _ in range(sets)]
+        d = L.resize_desc(iw, ih, ow, oh, c, a, f32=True)
+    else:
+        xs = [torch.randint(0, 256, (f * in_fb,), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(sets)]
+        d = L.resize_desc(iw, ih, ow, oh, c, a, bits=bits)
     ys = [torch.empty(f * out_fb, dtype=torch.uint8, device="cuda") for _ in range(sets)]
-    d = L.resize_desc(iw, ih, ow, oh, c, a, bits=bits)
     stream = torch.cuda.current_stream()
     s = stream.cuda_stream
     paths, ref = {}, None
@@ -129,14 +141,16 @@ def run(name, spec, args, ctx, torch, bits=8):
                 "rounds": args.rounds, "lib": os.path.basename(L.LIB_PATH), "measured": True}
         print(json.dumps(line), flush=True)
     if args.pillow:
-        key = "pillow_single_core_ms_per_frame" if bits == 8 else "pillow_single_core_ms_per_I16_plane"
+        key = {8: "pillow_single_core_ms_per_frame", 16: "pillow_single_core_ms_per_I16_plane",
+               32: "pillow_single_core_ms_per_F_plane"}[bits]
         try:
             from PIL import Image
             raw = xs[0][:in_fb].cpu().numpy()
             if bits == 8:
                 img = Image.frombytes("RGB", (iw, ih), raw.tobytes())
             else:
-                img = Image.fromarray(np.ascontiguousarray(raw.view(np.uint16).reshape(ih, iw, c)[:, :, 0]))
+                img = Image.fromarray(np.ascontiguousarray(raw.view(np.uint16 if bits == 16 else np.float32)
+                                                           .reshape(ih, iw, c)[:, :, 0]))
             img.resize((ow, oh), Image.LANCZOS)
             t0 = time.perf_counter()
             img.resize((ow, oh), Image.LANCZOS)
@@ -360,6 +374,8 @@ def main():
             run_rgba(name, RGBA_WORKLOADS[name], args, ctx, torch)
         elif name in U16_WORKLOADS:
             run(name, U16_WORKLOADS[name], args, ctx, torch, bits=16)
+        elif name in F32_WORKLOADS:
+            run(name, F32_WORKLOADS[name], args, ctx, torch, bits=32)
         else:
             run(name, WORKLOADS[name], args, ctx, torch)
     ctx.close()
