@@ -71,6 +71,7 @@ extern "C" {
 #define LANCZOS_KERNEL_RESIZE_FUSED 4     /* lanczos_resize_*: one launch, H pass into an LDS row ring, V pass from it */
 #define LANCZOS_KERNEL_RESIZE_TWO_PASS 5  /* lanczos_resize_*: H kernel into scratch, V kernel from it (any tap count);
                                              also a resize that changes one axis only, or none */
+#define LANCZOS_KERNEL_RESIZE_NEAREST 6   /* lanczos_resize_* with LANCZOS_FILTER_NEAREST: one gather launch, no tables of weights */
 
 typedef struct lanczos_ctx lanczos_ctx; /* opaque: device, stream, cached tap tables, staging buffers */
 
@@ -245,8 +246,9 @@ typedef struct lanczos_resize_desc {
     int32_t in_w, in_h;     /* 1..65535 each */
     int32_t out_w, out_h;   /* 1..65535 each, independent of the input size and of each other */
     int32_t channels;       /* 1, 3 or 4, interleaved; 8-bit samples, 16-bit with LANCZOS_RESIZE_U16, float with LANCZOS_RESIZE_F32 */
-    int32_t a;              /* 2, 3 or 4 (3 = Pillow's LANCZOS) */
-    int32_t reserved[2];    /* reserved[0]: flags, 0 or one of LANCZOS_RESIZE_ALPHA / _U16 / _F32; reserved[1]: must be 0 */
+    int32_t a;              /* 2, 3 or 4 (3 = Pillow's LANCZOS); 3 with any filter other than LANCZOS_FILTER_LANCZOS */
+    int32_t reserved[2];    /* reserved[0]: flags, 0 or one of LANCZOS_RESIZE_ALPHA / _U16 / _F32, and the filter in bits
+                               8..11 (LANCZOS_RESIZE_FILTER); reserved[1]: must be 0 */
 } lanczos_resize_desc;
 
 /* flag of lanczos_resize_desc.reserved[0]: channel 3 is straight alpha (Pillow's RGBA mode); channels must be 4 */
@@ -256,6 +258,41 @@ typedef struct lanczos_resize_desc {
 #define LANCZOS_RESIZE_U16 4
 /* flag of lanczos_resize_desc.reserved[0]: samples are float (Pillow's mode F arithmetic, see above); with no other flag */
 #define LANCZOS_RESIZE_F32 16
+
+/* The filter (Image.resize's `resample` argument) sits in bits 8..11 of lanczos_resize_desc.reserved[0] and combines with the
+ * flags above exactly as those combine with each other.  0 is Lanczos with the descriptor's a; every other filter needs
+ * a == 3 (one canonical descriptor per request), values 6..15 are LANCZOS_ERR_BAD_ARG.
+ *
+ * The weighted filters change two things of the recipe above and nothing else: the support S that stands where a stands
+ * (support = S * fs, ksize = 2 * ceil(support) + 1, the safe box of reducing_gap uses S - 0.5) and the weight w(x) of the
+ * argument x = (i + first - centre + 0.5) / fs, all in double without contraction, Pillow's functions as they are written:
+ *   BOX       S = 0.5  w = 1 if -0.5 < x <= 0.5 (on the signed x: the interval is not symmetric), else 0
+ *   BILINEAR  S = 1    x = |x|; w = 1 - x if x < 1, else 0
+ *   HAMMING   S = 1    x = |x|; w = 1 if x == 0, 0 if x >= 1, else with x = x * pi: sin(x) / x * (0.54f + 0.46f * cos(x)) --
+ *                      the two constants are FLOAT literals widened to double (0.54000002145767211914..., not 0.54)
+ *   BICUBIC   S = 2    x = |x|; with a = -0.5: ((a + 2) x - (a + 3)) x x + 1 if x < 1, (((x - 5) x + 8) x - 4) a if x < 2, else 0
+ * Normalisation, the 22-bit rounding, the double tables of 16-bit and float requests, pass skipping, the premultiplied alpha
+ * path, the I;16 store and the float rule that exactly `count` taps are multiplied are those of Lanczos.
+ *
+ * LANCZOS_FILTER_NEAREST has no weights.  Per axis, with the span (b0f, b1f) rounded to float as above,
+ *   step = (double)(float)(b1f - b0f) / out;  xo = (double)b0f + step * 0.5;
+ *   for o = 0 .. out - 1 in order: idx[o] = (int)xo; xo += step          -- a RUNNING SUM, not b0f + (o + 0.5) * step
+ * and out[y][x] = in[idx_v[y]][idx_h[x]], whole pixels: with LANCZOS_RESIZE_ALPHA nothing is premultiplied.  One launch
+ * gathers both axes (LANCZOS_KERNEL_RESIZE_NEAREST; no intermediate, no context scratch); equal sizes with the full box are the
+ * plain copy.  The tables functions report *ksize = 1, count = 1, first = idx and the coefficient 1.0 (2^22 in fixed point);
+ * the plan reports fused = 0.  Pillow ignores reducing_gap for NEAREST: a non-zero gap is LANCZOS_ERR_BAD_ARG.  An index
+ * outside the source (it cannot happen for a box inside the frame) is LANCZOS_ERR_UNSUPPORTED.
+ * LANCZOS_FILTER_NEAREST | LANCZOS_RESIZE_U16 is LANCZOS_ERR_UNSUPPORTED: Pillow sends I;16 through its generic transform, whose
+ * indices are computed by direct multiplication and differ from the running sum's (8-bit and float frames take the path
+ * above, checked against Pillow 12.2.0). */
+#define LANCZOS_FILTER_LANCZOS 0
+#define LANCZOS_FILTER_BOX 1
+#define LANCZOS_FILTER_BILINEAR 2
+#define LANCZOS_FILTER_HAMMING 3
+#define LANCZOS_FILTER_BICUBIC 4
+#define LANCZOS_FILTER_NEAREST 5
+#define LANCZOS_RESIZE_FILTER(f) ((f) << 8)
+#define LANCZOS_RESIZE_FILTER_OF(flags) (((flags) >> 8) & 15)
 
 /* forced path of lanczos_resize_force (tests and A/B runs only) */
 #define LANCZOS_RESIZE_AUTO 0
@@ -267,8 +304,12 @@ int lanczos_resize_desc_init(lanczos_resize_desc* d, int in_w, int in_h, int out
 /* the same with the flag word (lanczos_resize_desc_init gives 0) */
 int lanczos_resize_desc_init_ex(lanczos_resize_desc* d, int in_w, int in_h, int out_w, int out_h, int channels, int a,
                                 int flags);
-/* LANCZOS_ERR_BAD_ARG: size, channels, a, a flag word other than 0, LANCZOS_RESIZE_ALPHA, LANCZOS_RESIZE_U16 or
- * LANCZOS_RESIZE_F32, LANCZOS_RESIZE_ALPHA without four channels */
+/* the same with a filter: a = 3, reserved[0] = flags | LANCZOS_RESIZE_FILTER(filter); `flags` carries no filter bits */
+int lanczos_resize_desc_init_filter(lanczos_resize_desc* d, int in_w, int in_h, int out_w, int out_h, int channels,
+                                    int filter, int flags);
+/* LANCZOS_ERR_BAD_ARG: size, channels, a, a flag word whose flags are other than 0, LANCZOS_RESIZE_ALPHA, LANCZOS_RESIZE_U16 or
+ * LANCZOS_RESIZE_F32, LANCZOS_RESIZE_ALPHA without four channels, a filter above LANCZOS_FILTER_NEAREST, a != 3 with a filter
+ * other than LANCZOS_FILTER_LANCZOS.  LANCZOS_ERR_UNSUPPORTED: LANCZOS_FILTER_NEAREST with LANCZOS_RESIZE_U16 */
 int lanczos_resize_validate(const lanczos_resize_desc* d);
 /* Fixed-point tables of one axis (0 = horizontal, 1 = vertical): output o reads inputs first[o] .. first[o] + count[o] - 1
  * with coeffs[o * ksize + i] (i < count[o]; zero beyond).  *ksize = 2 * ceil(support) + 1.  With first, count and coeffs all
@@ -303,7 +344,8 @@ int lanczos_resize_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const 
                           size_t in_frame_stride, size_t out_frame_stride, void* stream);
 /* Host buffers, `frames` frames back to back; synchronous (copy in -> resize -> copy out on the context's stream). */
 int lanczos_resize_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const void* in, void* out, int frames);
-/* LANCZOS_RESIZE_AUTO / _FUSED / _TWO_PASS: tests and A/B runs only (lanczos_force_kernel does not affect resizes). */
+/* LANCZOS_RESIZE_AUTO / _FUSED / _TWO_PASS: tests and A/B runs only (lanczos_force_kernel does not affect resizes).
+ * LANCZOS_FILTER_NEAREST has one path: forced _FUSED is LANCZOS_ERR_UNSUPPORTED for it, forced _TWO_PASS changes nothing. */
 int lanczos_resize_force(lanczos_ctx* ctx, int path);
 
 /* ---- resize from a source box and with reducing_gap (the other two arguments of Pillow's Image.resize) ----

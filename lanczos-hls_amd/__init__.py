@@ -24,7 +24,7 @@ LIB_PATH = os.environ.get("LANCZOS_LIB") or os.path.join(_HERE, "liblanczos_hip.
 OK, ERR_BAD_ARG, ERR_UNSUPPORTED, ERR_NO_DEVICE, ERR_HIP, ERR_NOMEM, ERR_RCCL = range(7)   # include/lanczos_hip.h:43-49
 MODE_LSB1, MODE_EXACT, MODE_HLS = 0, 1, 2
 KERNEL_NONE, KERNEL_GENERIC, KERNEL_FAST, KERNEL_HLS = 0, 1, 2, 3
-KERNEL_RESIZE_FUSED, KERNEL_RESIZE_TWO_PASS = 4, 5
+KERNEL_RESIZE_FUSED, KERNEL_RESIZE_TWO_PASS, KERNEL_RESIZE_NEAREST = 4, 5, 6
 # lanczos_last_route: the main kernel and the route of the in-place prefix rows (include/lanczos_hip.h LANCZOS_ROUTE_*)
 ROUTE_MAIN_NONE, ROUTE_MAIN_MARCH, ROUTE_MAIN_TILE, ROUTE_MAIN_RATP, ROUTE_MAIN_RAT, ROUTE_MAIN_GENERIC, ROUTE_MAIN_HLS = range(7)
 ROUTE_PREFIX_NONE, ROUTE_PREFIX_RIDING, ROUTE_PREFIX_FRONT, ROUTE_PREFIX_BEHIND, ROUTE_PREFIX_STREAMED = range(5)
@@ -34,6 +34,9 @@ RESIZE_AUTO, RESIZE_FUSED, RESIZE_TWO_PASS = 0, 1, 2   # lanczos_resize_force
 RESIZE_ALPHA = 1   # flag of lanczos_resize_desc.reserved[0]: channel 3 of 4 is straight alpha (Pillow's RGBA mode)
 RESIZE_U16 = 4     # flag of lanczos_resize_desc.reserved[0]: native-endian uint16 samples (Pillow's I;16 arithmetic)
 RESIZE_F32 = 16    # flag of lanczos_resize_desc.reserved[0]: float samples (Pillow's mode F arithmetic); with no other flag
+# the filter of a resize (Image.resize's `resample`), bits 8..11 of lanczos_resize_desc.reserved[0]
+FILTER_LANCZOS, FILTER_BOX, FILTER_BILINEAR, FILTER_HAMMING, FILTER_BICUBIC, FILTER_NEAREST = range(6)
+FILTER_NAMES = ("lanczos", "box", "bilinear", "hamming", "bicubic", "nearest")
 
 # every symbol include/lanczos_hip.h declares (tests check the library exports exactly these)
 ABI_SYMBOLS = [
@@ -49,7 +52,7 @@ ABI_SYMBOLS = [
     "lanczos_multi_devices", "lanczos_resample_multi_host", "lanczos_resample_multi_root",
     "lanczos_multi_last_error", "lanczos_multi_exchange_plan", "lanczos_multi_exchange_selftest", "lanczos_device_alloc", "lanczos_device_free",
     "lanczos_device_copy",
-    "lanczos_resize_desc_init", "lanczos_resize_desc_init_ex", "lanczos_resize_validate", "lanczos_resize_taps_host",
+    "lanczos_resize_desc_init", "lanczos_resize_desc_init_ex", "lanczos_resize_desc_init_filter", "lanczos_resize_validate", "lanczos_resize_taps_host",
     "lanczos_resize_taps_f64_host", "lanczos_resize_device",
     "lanczos_resize_host", "lanczos_resize_force", "lanczos_resize_plan_host",
     "lanczos_resize_opts_init", "lanczos_resize_taps_host_ex", "lanczos_resize_taps_f64_host_ex",
@@ -212,6 +215,8 @@ def _lib():
         L.lanczos_reduce_device.argtypes = [c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_int, c_size_t,
                                                                       c_size_t, c_void_p]
         L.lanczos_reduce_host.argtypes = [c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_int]
+        if hasattr(L, "lanczos_resize_desc_init_filter"):   # (an older build loaded through LANCZOS_LIB has only Lanczos)
+            L.lanczos_resize_desc_init_filter.argtypes = [PRD] + [c_int] * 7
         L.lanczos_strerror.restype = ctypes.c_char_p
         L.lanczos_version.argtypes = []
         L.lanczos_version.restype = ctypes.c_char_p
@@ -267,17 +272,35 @@ def taps_host(desc, axis):
     return first, w
 
 
-def resize_desc(in_w, in_h, out_w, out_h, channels, a=3, alpha=False, bits=8, f32=False):
+def filter_code(filter):
+    """FILTER_* of a filter given by name ("lanczos", "box", "bilinear", "hamming", "bicubic", "nearest") or as FILTER_*."""
+    if isinstance(filter, str):
+        if filter.lower() not in FILTER_NAMES:
+            raise LanczosError(ERR_BAD_ARG, f"unknown filter {filter!r}: one of {', '.join(FILTER_NAMES)}")
+        return FILTER_NAMES.index(filter.lower())
+    return int(filter)
+
+
+def resize_desc(in_w, in_h, out_w, out_h, channels, a=3, alpha=False, bits=8, f32=False, filter=FILTER_LANCZOS):
     """A validated lanczos_resize_desc (Pillow's contract: any output size, downscaling included).  alpha: the fourth of
     four channels is straight alpha, resized as Pillow's mode RGBA (premultiplied inside the kernels).  bits: 8, or 16 for
     uint16 samples resized as Pillow's mode I;16 (double accumulation, Pillow's wrapping store); not with alpha.  f32: float
-    samples resized as Pillow's mode F (double accumulation, stored as float, no clamp); not with alpha or bits=16."""
+    samples resized as Pillow's mode F (double accumulation, stored as float, no clamp); not with alpha or bits=16.
+    filter: Image.resize's `resample`, a name or FILTER_*; every filter but Lanczos needs a == 3 (ERR_BAD_ARG otherwise), and
+    "nearest" gathers whole pixels (no premultiply with alpha; ERR_UNSUPPORTED with bits=16)."""
     if bits not in (8, 16):
         raise LanczosError(ERR_BAD_ARG, "resize_desc: bits must be 8 or 16")
     d = ResizeDesc()
     flags = (RESIZE_ALPHA if alpha else 0) | (RESIZE_U16 if bits == 16 else 0) | (RESIZE_F32 if f32 else 0)
-    _check(_lib().lanczos_resize_desc_init_ex(ctypes.byref(d), in_w, in_h, out_w, out_h, channels, a, flags),
-           "lanczos_resize_desc_init_ex")
+    f = filter_code(filter)
+    if f == FILTER_LANCZOS:
+        _check(_lib().lanczos_resize_desc_init_ex(ctypes.byref(d), in_w, in_h, out_w, out_h, channels, a, flags),
+               "lanczos_resize_desc_init_ex")
+        return d
+    if a != 3:
+        raise LanczosError(ERR_BAD_ARG, "resize_desc: a filter other than Lanczos takes a = 3")
+    _check(_lib().lanczos_resize_desc_init_filter(ctypes.byref(d), in_w, in_h, out_w, out_h, channels, f, flags),
+           "lanczos_resize_desc_init_filter")
     return d
 
 
@@ -476,8 +499,11 @@ class Context:
                                                      stream), "lanczos_resample_planar_device")
 
     # -- resize to any size (Pillow's contract, lanczos_resize_*)
-    def resize(self, img, out_w, out_h, a=3, alpha=False, box=None, reducing_gap=None):
-        """box = (x0, y0, x1, y1): resize that (sub-pixel) region of the source, as Image.resize(..., box=box); pixels
+    def resize(self, img, out_w, out_h, a=3, alpha=False, box=None, reducing_gap=None, filter=FILTER_LANCZOS):
+        """filter: Image.resize's `resample` as a name ("lanczos", "box", "bilinear", "hamming", "bicubic", "nearest") or
+        FILTER_*; bytes identical to Pillow's for that filter.  Every filter but Lanczos needs a == 3; "nearest" takes no
+        reducing_gap and no uint16 frames, and copies RGBA pixels whole.
+        box = (x0, y0, x1, y1): resize that (sub-pixel) region of the source, as Image.resize(..., box=box); pixels
         outside it still contribute near its edges.  reducing_gap = g >= 1: first reduce by whole factors (an exact box
         average), then resize what is left, as Image.resize(..., reducing_gap=g) -- Pillow's bytes for the same arguments, not
         those of the resize without a gap; 8-bit without alpha only (ERR_BAD_ARG otherwise, as there is no oracle).
@@ -492,7 +518,7 @@ class Context:
         x = img.reshape(img.shape + (1,)) if img.ndim == 2 else img
         x = x if x.ndim == 4 else x[None]
         f, h, w, c = x.shape
-        d = resize_desc(w, h, out_w, out_h, c, a, alpha, 8 * img.dtype.itemsize)
+        d = resize_desc(w, h, out_w, out_h, c, a, alpha, 8 * img.dtype.itemsize, filter=filter)
         out = np.empty((f, out_h, out_w, c), dtype=img.dtype)
         if box is None and reducing_gap is None:
             _check(_lib().lanczos_resize_host(self._h, ctypes.byref(d), x.ctypes.data, out.ctypes.data, f),
@@ -504,8 +530,9 @@ class Context:
             return out[0, :, :, 0]
         return out if img.ndim == 4 else out[0]
 
-    def resize_f32(self, img, out_w, out_h, a=3, box=None):
-        """img: float32 [H][W], [H][W][C] or [F][H][W][C] (C = 1, 3 or 4) -> the same layout at out_h x out_w, every channel
+    def resize_f32(self, img, out_w, out_h, a=3, box=None, filter=FILTER_LANCZOS):
+        """filter as Context.resize.
+        img: float32 [H][W], [H][W][C] or [F][H][W][C] (C = 1, 3 or 4) -> the same layout at out_h x out_w, every channel
         bit for bit what Pillow's Image.resize((out_w, out_h), Image.LANCZOS, box) gives for it as a mode F plane (a = 3):
         double accumulation over exactly the window's taps, stored as float -- no clamp, inf on overflow, denormals kept, NaN
         where Pillow has NaN.  box as Context.resize.  No alpha and no reducing_gap for floats."""
@@ -515,7 +542,7 @@ class Context:
         x = img.reshape(img.shape + (1,)) if img.ndim == 2 else img
         x = x if x.ndim == 4 else x[None]
         f, h, w, c = x.shape
-        d = resize_desc(w, h, out_w, out_h, c, a, f32=True)
+        d = resize_desc(w, h, out_w, out_h, c, a, f32=True, filter=filter)
         out = np.empty((f, out_h, out_w, c), dtype=np.float32)
         if box is None:
             _check(_lib().lanczos_resize_host(self._h, ctypes.byref(d), x.ctypes.data, out.ctypes.data, f),
@@ -528,9 +555,14 @@ class Context:
         return out if img.ndim == 4 else out[0]
 
     def resize_device(self, desc, d_in, d_out, frames, in_frame_stride=0, out_frame_stride=0, stream=None, box=None,
-                      reducing_gap=None, opts=None):
+                      reducing_gap=None, opts=None, filter=None):
         """Device pointers, asynchronous on `stream` (None = the default stream).  box / reducing_gap / opts as
-        resize_taps_host."""
+        resize_taps_host.  The filter is the descriptor's (resize_desc(..., filter=)); filter= (a name or FILTER_*) runs
+        the same request with that filter instead."""
+        if filter is not None:
+            d = ResizeDesc.from_buffer_copy(desc)
+            d.reserved[0] = (d.reserved[0] & ~(15 << 8)) | (filter_code(filter) << 8)
+            desc = d
         if box is None and reducing_gap is None and opts is None:
             _check(_lib().lanczos_resize_device(self._h, ctypes.byref(desc), d_in, d_out, frames, in_frame_stride,
                                                 out_frame_stride, stream), "lanczos_resize_device")

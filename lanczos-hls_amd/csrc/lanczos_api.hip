@@ -1083,6 +1083,16 @@ int lanczos_resize_desc_init_ex(lanczos_resize_desc* d, int in_w, int in_h, int 
     return lz::resize_validate(d);
 }
 
+int lanczos_resize_desc_init_filter(lanczos_resize_desc* d, int in_w, int in_h, int out_w, int out_h, int channels,
+                                    int filter, int flags) {
+    if (!d) return LANCZOS_ERR_BAD_ARG;
+    memset(d, 0, sizeof(*d));
+    d->in_w = in_w, d->in_h = in_h, d->out_w = out_w, d->out_h = out_h, d->channels = channels, d->a = 3;
+    if (filter < 0 || filter > 15 || (flags & LANCZOS_RESIZE_FILTER(15)) != 0) return LANCZOS_ERR_BAD_ARG;
+    d->reserved[0] = flags | LANCZOS_RESIZE_FILTER(filter);
+    return lz::resize_validate(d);
+}
+
 int lanczos_resize_validate(const lanczos_resize_desc* d) { return lz::resize_validate(d); }
 
 int lanczos_resize_opts_init(lanczos_resize_opts* o, const lanczos_resize_desc* d) {
@@ -1104,11 +1114,12 @@ static int resize_taps_any(const lanczos_resize_desc* d, const lanczos_resize_op
     if ((rc = lz::resize_resolve(d, o, &r)) != LANCZOS_OK) return rc;
     const int in_n = axis == 0 ? r.inner.in_w : r.inner.in_h, out_n = axis == 0 ? d->out_w : d->out_h;
     const lz::RsSpan span = axis == 0 ? r.h : r.v;
-    *ksize = lz::resize_ksize(in_n, out_n, d->a, span);
+    const int filter = lz::resize_filter(d);
+    *ksize = lz::resize_ksize(in_n, out_n, d->a, filter, span);
     if (!first && !count && !coeffs) return LANCZOS_OK;
     if (!first || !count || !coeffs) return LANCZOS_ERR_BAD_ARG;
     lz::ResizeAxisHost t;
-    if (!lz::resize_build_axis(in_n, out_n, d->a, span, &t, f64)) return LANCZOS_ERR_UNSUPPORTED;
+    if (!lz::resize_build_axis(in_n, out_n, d->a, filter, span, &t, f64)) return LANCZOS_ERR_UNSUPPORTED;
     memcpy(first, t.first.data(), t.first.size() * sizeof(int32_t));
     memcpy(count, t.count.data(), t.count.size() * sizeof(int32_t));
     if (f64) memcpy(coeffs, t.coeffs64.data(), t.coeffs64.size() * sizeof(double));

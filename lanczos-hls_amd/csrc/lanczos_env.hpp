@@ -17,6 +17,7 @@ struct Env {
     int march_segs = -1;           // LANCZOS_MARCH_SEGS=0     never the one-workgroup-per-slot table (mode A); >0: always
     std::string rank_weights;      // LANCZOS_RANK_WEIGHTS="w0:w1:w2:w3/v0:v1:v2" slot speeds of the rank-aware shares; "0": equal shares
     bool has_rank_weights = false;
+    bool rs_no_small_buckets = false;  // LANCZOS_RS_NO_SMALL_BUCKETS=1  resizes with fewer than 7 horizontal taps on the 7-tap fused instance (A/B runs)
 #ifdef LZ_PROFILE_BITS
     int debug_skip = 0;            // LANCZOS_DEBUG_SKIP=bits  ablation bits of the kernels (results are then wrong)
     bool stamp = false;            // LANCZOS_STAMP=1          k_march<u8,3,2,3> with s_memtime stamps + residency census
@@ -36,6 +37,7 @@ inline const Env& env() {
         v.march_wgs = num("LANCZOS_MARCH_WGS", 0);
         v.march_segs = num("LANCZOS_MARCH_SEGS", -1);
         if (const char* s = std::getenv("LANCZOS_RANK_WEIGHTS")) v.rank_weights = s, v.has_rank_weights = true;
+        v.rs_no_small_buckets = flag("LANCZOS_RS_NO_SMALL_BUCKETS");
 #ifdef LZ_PROFILE_BITS
         v.debug_skip = num("LANCZOS_DEBUG_SKIP", 0);
         v.stamp = flag("LANCZOS_STAMP");

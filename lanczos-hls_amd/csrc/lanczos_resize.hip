@@ -30,6 +30,7 @@
 #include "lanczos_resize.hpp"
 
 #include "lanczos_alpha.hpp"
+#include "lanczos_env.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -48,10 +49,15 @@ int resize_validate(const lanczos_resize_desc* d) {
     if (d->channels != 1 && d->channels != 3 && d->channels != 4) return LANCZOS_ERR_BAD_ARG;
     if (d->a < 2 || d->a > 4) return LANCZOS_ERR_BAD_ARG;
     constexpr int kFlags = LANCZOS_RESIZE_ALPHA | LANCZOS_RESIZE_U16 | LANCZOS_RESIZE_F32;
-    if ((d->reserved[0] & ~kFlags) != 0 || d->reserved[1] != 0) return LANCZOS_ERR_BAD_ARG;
+    if ((d->reserved[0] & ~(kFlags | LANCZOS_RESIZE_FILTER(15))) != 0 || d->reserved[1] != 0) return LANCZOS_ERR_BAD_ARG;
+    const int filter = resize_filter(d);
+    if (filter > LANCZOS_FILTER_NEAREST) return LANCZOS_ERR_BAD_ARG;
+    if (filter != LANCZOS_FILTER_LANCZOS && d->a != 3) return LANCZOS_ERR_BAD_ARG;   // one descriptor per request
     if ((d->reserved[0] & LANCZOS_RESIZE_ALPHA) && (d->reserved[0] & LANCZOS_RESIZE_U16)) return LANCZOS_ERR_BAD_ARG;
-    if ((d->reserved[0] & LANCZOS_RESIZE_F32) && d->reserved[0] != LANCZOS_RESIZE_F32) return LANCZOS_ERR_BAD_ARG;
+    if ((d->reserved[0] & LANCZOS_RESIZE_F32) && (d->reserved[0] & kFlags) != LANCZOS_RESIZE_F32) return LANCZOS_ERR_BAD_ARG;
     if ((d->reserved[0] & LANCZOS_RESIZE_ALPHA) && d->channels != 4) return LANCZOS_ERR_BAD_ARG;
+    // Pillow resizes I;16 with NEAREST through its generic transform: other indices than the running sum's.  Not built
+    if (filter == LANCZOS_FILTER_NEAREST && (d->reserved[0] & LANCZOS_RESIZE_U16)) return LANCZOS_ERR_UNSUPPORTED;
     return LANCZOS_OK;
 }
 
@@ -65,24 +71,75 @@ static double rs_filter(double x, int a) {
     if (-a <= x && x < a) return rs_sinc(x) * rs_sinc(x / a);
     return 0.0;
 }
+// Pillow's box_filter, bilinear_filter, hamming_filter and bicubic_filter, operation for operation
+static double rs_box(double x) { return x > -0.5 && x <= 0.5 ? 1.0 : 0.0; }
+static double rs_bilinear(double x) {
+    if (x < 0.0) x = -x;
+    return x < 1.0 ? 1.0 - x : 0.0;
+}
+static double rs_hamming(double x) {
+    if (x < 0.0) x = -x;
+    if (x == 0.0) return 1.0;
+    if (x >= 1.0) return 0.0;
+    x = x * M_PI;
+    return sin(x) / x * (0.54f + 0.46f * cos(x));   // float literals, widened: Pillow's bytes depend on it
+}
+static double rs_bicubic(double x) {
+    constexpr double a = -0.5;
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
+static double rs_weight(double x, int a, int filter) {
+    switch (filter) {
+        case LANCZOS_FILTER_BOX: return rs_box(x);
+        case LANCZOS_FILTER_BILINEAR: return rs_bilinear(x);
+        case LANCZOS_FILTER_HAMMING: return rs_hamming(x);
+        case LANCZOS_FILTER_BICUBIC: return rs_bicubic(x);
+        default: return rs_filter(x, a);
+    }
+}
 
 // the extent of a span is taken in float, as Pillow's C does with its float box[4]; for the whole axis it is in_n exactly
 static double rs_span_scale(RsSpan s, int out_n) { return (double)(float)(s.b1 - s.b0) / out_n; }
 
-int resize_ksize(int in_n, int out_n, int a, RsSpan s) {
+int resize_ksize(int in_n, int out_n, int a, int filter, RsSpan s) {
     (void)in_n;
+    if (filter == LANCZOS_FILTER_NEAREST) return 1;
     const double scale = rs_span_scale(s, out_n);
     const double fs = scale > 1.0 ? scale : 1.0;
-    return (int)ceil(a * fs) * 2 + 1;
+    return (int)ceil(rs_filter_support(filter, a) * fs) * 2 + 1;
 }
 
-bool resize_build_axis(int in_n, int out_n, int a, RsSpan s, ResizeAxisHost* t, bool f64) {
+// LANCZOS_FILTER_NEAREST: Pillow's ImagingScaleAffine steps through the source with a running sum
+static bool rs_build_nearest(int in_n, int out_n, RsSpan s, ResizeAxisHost* t, bool f64) {
+    const double step = rs_span_scale(s, out_n);
+    t->ksize = 1, t->scale = step;
+    t->first.assign(out_n, 0);
+    t->count.assign(out_n, 1);
+    t->coeffs.assign(f64 ? 0 : (size_t)out_n, 1 << kResizePrecision);
+    t->coeffs64.assign(f64 ? (size_t)out_n : 0, 1.0);
+    bool ok = true;
+    double xo = (double)s.b0 + step * 0.5;
+    for (int o = 0; o < out_n; o++) {
+        const int i = xo < 0.0 ? -1 : (int)xo;
+        if (i < 0 || i >= in_n) ok = false;   // Pillow leaves such a pixel untouched; no box inside the frame gets here
+        t->first[o] = std::min(std::max(i, 0), in_n - 1);
+        xo += step;
+    }
+    return ok;
+}
+
+bool resize_build_axis(int in_n, int out_n, int a, int filter, RsSpan s, ResizeAxisHost* t, bool f64) {
+    t->in_n = in_n, t->out_n = out_n, t->a = a, t->filter = filter;
+    if (filter == LANCZOS_FILTER_NEAREST) return rs_build_nearest(in_n, out_n, s, t, f64);
     const double scale = rs_span_scale(s, out_n);
     const double fs = scale > 1.0 ? scale : 1.0;
-    const double support = a * fs;
+    const double support = rs_filter_support(filter, a) * fs;
     const double ss = 1.0 / fs;
     const int ksize = (int)ceil(support) * 2 + 1;
-    t->in_n = in_n, t->out_n = out_n, t->a = a, t->ksize = ksize, t->scale = scale;
+    t->ksize = ksize, t->scale = scale;
     t->first.assign(out_n, 0);
     t->count.assign(out_n, 0);
     t->coeffs.assign(f64 ? 0 : (size_t)out_n * ksize, 0);
@@ -98,7 +155,7 @@ bool resize_build_axis(int in_n, int out_n, int a, RsSpan s, ResizeAxisHost* t, 
         const int n = xmax - xmin;
         double ww = 0.0;
         for (int i = 0; i < n; i++) {
-            w[i] = rs_filter((i + xmin - center + 0.5) * ss, a);
+            w[i] = rs_weight((i + xmin - center + 0.5) * ss, a, filter);
             ww += w[i];
         }
         t->first[o] = xmin;
@@ -142,13 +199,14 @@ int resize_resolve(const lanczos_resize_desc* d, const lanczos_resize_opts* o, R
         // summation order of its float box average is not pinned down: not built
         if (gap != 0.0 && (d->reserved[0] & (LANCZOS_RESIZE_ALPHA | LANCZOS_RESIZE_U16 | LANCZOS_RESIZE_F32)))
             return LANCZOS_ERR_BAD_ARG;
+        if (gap != 0.0 && resize_nearest(d)) return LANCZOS_ERR_BAD_ARG;   // Pillow drops it there as well
     }
     if (gap != 0.0) {
         const double ex = (box[2] - box[0]) / d->out_w / gap, ey = (box[3] - box[1]) / d->out_h / gap;
         const long long fx = ex >= 1.0 ? (long long)ex : 1, fy = ey >= 1.0 ? (long long)ey : 1;
         if (fx > 1 || fy > 1) {
             if (fx * fy >= 65536) return LANCZOS_ERR_UNSUPPORTED;
-            const double sup = d->a - 0.5;
+            const double sup = rs_filter_support(resize_filter(d), d->a) - 0.5;
             const double sx = sup * ((box[2] - box[0]) / d->out_w), sy = sup * ((box[3] - box[1]) / d->out_h);
             r->rb[0] = std::max(0, (int)(box[0] - sx));
             r->rb[1] = std::max(0, (int)(box[1] - sy));
@@ -437,11 +495,14 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(RsFused g) {
     }
 }
 
-// horizontal tap counts with a fused instance (a request runs on the smallest one >= its ksize, zero-padded)
-#define LZ_RS_BUCKETS(X) X(7) X(9) X(11) X(13) X(17) X(25)
+// horizontal tap counts with a fused instance (a request runs on the smallest one >= its ksize, zero-padded).  3 and 5 serve
+// the upscales of the short filters (box and bilinear: ksize 3, bicubic: 5) and only them: a Lanczos request keeps the
+// instance it always had (a = 2 upscales, ksize 5, run on 7).  LANCZOS_RS_NO_SMALL_BUCKETS=1 pads the short filters to 7 too
+#define LZ_RS_BUCKETS(X) X(3) X(5) X(7) X(9) X(11) X(13) X(17) X(25)
 
-static int rs_bucket(int ksize) {
+static int rs_bucket(int ksize, bool small) {
     int k = 0;
+    if ((!small || env().rs_no_small_buckets) && ksize < 7) ksize = 7;
 #define X(KB) \
     if (!k && ksize <= KB) k = KB;
     LZ_RS_BUCKETS(X)
@@ -481,14 +542,15 @@ ResizeState::~ResizeState() {   // the owner has drained the device
 // The tables of one axis shape, built and uploaded on first use.  The upload is eager: a copy on the private stream and a
 // wait for it, so an entry is valid from the moment it is cached -- also when the caller's stream is being captured
 // (a copy queued on it would only run when the graph is replayed, perhaps never).
-static int rs_axis(ResizeState* st, int in_n, int out_n, int a, RsSpan span, bool f64, ResizeAxis** out, int* last_hip) {
+static int rs_axis(ResizeState* st, int in_n, int out_n, int a, int filter, RsSpan span, bool f64, ResizeAxis** out,
+                   int* last_hip) {
     uint32_t bits[2];
     memcpy(&bits[0], &span.b0, 4);
     memcpy(&bits[1], &span.b1, 4);
     for (size_t i = 0; i < st->axes.size(); i++) {
         ResizeAxis* ax = st->axes[i];
         if (ax->key[0] == in_n && ax->key[1] == out_n && ax->key[2] == a && ax->key[3] == (int)f64 &&
-            ax->span_bits[0] == bits[0] && ax->span_bits[1] == bits[1]) {
+            ax->key[4] == filter && ax->span_bits[0] == bits[0] && ax->span_bits[1] == bits[1]) {
             st->axes.erase(st->axes.begin() + i);
             st->axes.push_back(ax);   // most recent last
             *out = ax;
@@ -498,9 +560,9 @@ static int rs_axis(ResizeState* st, int in_n, int out_n, int a, RsSpan span, boo
     st->retired.reap(false);
     ResizeAxis* ax = new (std::nothrow) ResizeAxis();
     if (!ax) return LANCZOS_ERR_NOMEM;
-    ax->key[0] = in_n, ax->key[1] = out_n, ax->key[2] = a, ax->key[3] = (int)f64;
+    ax->key[0] = in_n, ax->key[1] = out_n, ax->key[2] = a, ax->key[3] = (int)f64, ax->key[4] = filter;
     ax->span_bits[0] = bits[0], ax->span_bits[1] = bits[1];
-    if (!resize_build_axis(in_n, out_n, a, span, &ax->host, f64)) {
+    if (!resize_build_axis(in_n, out_n, a, filter, span, &ax->host, f64)) {
         delete ax;
         return LANCZOS_ERR_UNSUPPORTED;
     }
@@ -565,7 +627,8 @@ bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H, const 
     const int C = d->channels * bps;   // bytes per pixel
     if ((long long)d->in_w * d->in_h * C + 4 >= (1ll << 31)) return false;   // 32-bit buffer offsets
     if ((long long)d->out_w * d->out_h * C >= (1ll << 31)) return false;
-    fp->K = bps > 1 ? rs16_bucket(H.ksize) : rs_bucket(H.ksize);
+    const bool small = resize_filter(d) != LANCZOS_FILTER_LANCZOS;   // the instances with 3 and 5 taps
+    fp->K = bps > 1 ? rs16_bucket(H.ksize, small) : rs_bucket(H.ksize, small);
     if (!fp->K) return false;
     const int SW = rs_strip_width(d->channels, bps);
     const int NE = (fp->K * C + 3) / 4;
@@ -609,13 +672,15 @@ int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o,
     out->reduced_w = r.inner.in_w, out->reduced_h = r.inner.in_h;
     out->pass_h = r.need_h, out->pass_v = r.need_v;
     const bool u16 = resize_bps(d) > 1;   // the double tables
+    const int filter = resize_filter(d);
+    if (filter == LANCZOS_FILTER_NEAREST) return LANCZOS_OK;   // one gather launch: no intermediate, nothing to fuse
     ResizeAxisHost H, V;
     if (r.need_v) {
-        if (!resize_build_axis(r.inner.in_h, r.inner.out_h, d->a, r.v, &V, u16)) return LANCZOS_ERR_UNSUPPORTED;
+        if (!resize_build_axis(r.inner.in_h, r.inner.out_h, d->a, filter, r.v, &V, u16)) return LANCZOS_ERR_UNSUPPORTED;
         if (r.need_h) rs_mid_rows(V, &out->mid_row0, &out->mid_rows);
     }
     if (!r.need_h || !r.need_v) return LANCZOS_OK;   // as resize_device: no table for an idle axis, nothing to fuse
-    if (!resize_build_axis(r.inner.in_w, r.inner.out_w, d->a, r.h, &H, u16)) return LANCZOS_ERR_UNSUPPORTED;
+    if (!resize_build_axis(r.inner.in_w, r.inner.out_w, d->a, filter, r.h, &H, u16)) return LANCZOS_ERR_UNSUPPORTED;
     RsFusedPlan fp;
     if (!rs_fused_plan(&r.inner, H, V, frames, &fp)) return LANCZOS_OK;
     lanczos_resize_plan* in = &out->inner;
@@ -696,16 +761,21 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     const bool capturing = stream_capturing(stream);
     const bool need_h = rs_axis_runs(d->in_w, d->out_w, sh), need_v = rs_axis_runs(d->in_h, d->out_h, sv);
     const bool alpha = (d->reserved[0] & LANCZOS_RESIZE_ALPHA) != 0;
+    const int filter = resize_filter(d);
+    // the gather reads both index tables, also that of an axis that keeps its size (the identity) -- unless both do
+    const bool nearest = filter == LANCZOS_FILTER_NEAREST && (need_h || need_v);
 
     ResizeAxis *H = nullptr, *V = nullptr;
     int rc;
-    if (need_h && (rc = rs_axis(st, d->in_w, d->out_w, d->a, sh, u16, &H, last_hip)) != LANCZOS_OK) return rc;
-    if (need_v && (rc = rs_axis(st, d->in_h, d->out_h, d->a, sv, u16, &V, last_hip)) != LANCZOS_OK) return rc;
+    if ((need_h || nearest) && (rc = rs_axis(st, d->in_w, d->out_w, d->a, filter, sh, u16, &H, last_hip)) != LANCZOS_OK)
+        return rc;
+    if ((need_v || nearest) && (rc = rs_axis(st, d->in_h, d->out_h, d->a, filter, sv, u16, &V, last_hip)) != LANCZOS_OK)
+        return rc;
     for (ResizeAxis* ax : {H, V})
         if (ax && !capturing) note_stream(ax->streams, stream);
 
     RsFusedPlan fp;
-    const bool fused_ok = need_h && need_v && rs_fused_plan(d, H->host, V->host, frames, &fp);
+    const bool fused_ok = !nearest && need_h && need_v && rs_fused_plan(d, H->host, V->host, frames, &fp);
     if (st->force == LANCZOS_RESIZE_FUSED && !fused_ok) return LANCZOS_ERR_UNSUPPORTED;
     const bool fused = fused_ok && st->force != LANCZOS_RESIZE_TWO_PASS;
     // two passes: the horizontal one produces the rows the vertical taps read and no others, mid_rows of them from source
@@ -721,6 +791,10 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
             : u16 ? rs16_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream)
                   : rs_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream);
         *last_kernel = LANCZOS_KERNEL_RESIZE_FUSED;
+    } else if (nearest) {
+        e = rs_nearest_launch(in, out, d->in_w, d->out_w, d->out_h, C, (int)B, H->first(), V->first(), frames, in_fs, out_fs,
+                              stream);
+        *last_kernel = LANCZOS_KERNEL_RESIZE_NEAREST;
     } else if (!need_h && !need_v) {   // Pillow returns a copy (also of RGBA: no premultiply round trip)
         e = hipMemcpy2DAsync(out, out_fs, in, in_fs, in_frame, frames, hipMemcpyDeviceToDevice, stream);
         *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;

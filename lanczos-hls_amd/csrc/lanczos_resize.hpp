@@ -1,7 +1,9 @@
 // lanczos_resize.hpp -- resize to any size with Pillow's Lanczos contract (include/lanczos_hip.h, lanczos_resize_*):
 // host tap tables, their per-context cache, and the entry points lanczos_api.hip forwards to.  The kernels live in
 // lanczos_resize.hip; those of 16-bit requests (LANCZOS_RESIZE_U16, double coefficients) in lanczos_resize16.hip and those of
-// float requests (LANCZOS_RESIZE_F32, the same double tables) in lanczos_resize32.hip.
+// float requests (LANCZOS_RESIZE_F32, the same double tables) in lanczos_resize32.hip.  The filter of a request
+// (LANCZOS_RESIZE_FILTER) only changes the tables; LANCZOS_FILTER_NEAREST has index tables and a kernel of its own
+// (lanczos_resize_nearest.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,7 +24,7 @@ int resize_validate(const lanczos_resize_desc* d);
 // normalize_coeffs_8bpc do.  Returns false if a coefficient or an accumulator could leave the ranges the kernels rely on
 // (|coeff| < 2^23 for the 24-bit multiply, 255 * sum|coeff| + 2^21 < 2^31); no shape met so far does.
 struct ResizeAxisHost {
-    int in_n = 0, out_n = 0, a = 0, ksize = 0;
+    int in_n = 0, out_n = 0, a = 0, filter = 0, ksize = 0;
     double scale = 1.0;                          // source pixels per output pixel: the box's extent / out_n
     std::vector<int32_t> first, count, coeffs;   // [out_n], [out_n], [out_n][ksize]
     std::vector<double> coeffs64;                // [out_n][ksize]: the 16-bit and float paths' tables, which have no `coeffs`
@@ -34,10 +36,17 @@ struct RsSpan {
 inline RsSpan rs_full_span(int in_n) { return RsSpan{0.0f, (float)in_n}; }
 // the pass rule: an axis runs its pass iff it changes size or its span is not the whole axis
 inline bool rs_axis_runs(int in_n, int out_n, RsSpan s) { return out_n != in_n || s.b0 != 0.0f || s.b1 != (float)in_n; }
-int resize_ksize(int in_n, int out_n, int a, RsSpan s);
+// the filter of a request (LANCZOS_FILTER_*) and the support S of its weight function, which stands where Lanczos has a
+inline int resize_filter(const lanczos_resize_desc* d) { return LANCZOS_RESIZE_FILTER_OF(d->reserved[0]); }
+inline bool resize_nearest(const lanczos_resize_desc* d) { return resize_filter(d) == LANCZOS_FILTER_NEAREST; }
+inline double rs_filter_support(int filter, int a) {
+    return filter == LANCZOS_FILTER_BOX ? 0.5 : filter == LANCZOS_FILTER_BICUBIC ? 2.0 : filter == LANCZOS_FILTER_LANCZOS ? (double)a : 1.0;
+}
+int resize_ksize(int in_n, int out_n, int a, int filter, RsSpan s);
 // f64: the tables of the 16-bit path instead -- the normalised weights as they are (Pillow's precompute_coeffs alone),
-// in coeffs64; always true.
-bool resize_build_axis(int in_n, int out_n, int a, RsSpan s, ResizeAxisHost* t, bool f64 = false);
+// in coeffs64; always true.  LANCZOS_FILTER_NEAREST: first = Pillow's source index of every output (a running sum), count = 1,
+// ksize = 1, the coefficient 2^22 or 1.0; false if an index leaves the source.
+bool resize_build_axis(int in_n, int out_n, int a, int filter, RsSpan s, ResizeAxisHost* t, bool f64 = false);
 
 // A request with its options resolved (lanczos_resize_opts; NULL = the full box, no gap): the reduction in front of the
 // resize, if any, and the resize that remains -- `inner` is the caller's descriptor, or one whose source is the reduced frame.
@@ -85,7 +94,7 @@ int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o,
 // One axis shape on the device: first | count | coeffs in one block (int32 coefficients, or double ones for 16-bit samples:
 // the two int32 arrays in front of them keep those 8-byte aligned).
 struct ResizeAxis {
-    int key[4] = {0, 0, 0, 0};   // in, out, a, double coefficients
+    int key[5] = {0, 0, 0, 0, 0};   // in, out, a, double coefficients, filter
     uint32_t span_bits[2] = {0, 0};   // the bit patterns of the span's two floats: two boxes over one (in, out, a) are two entries
     ResizeAxisHost host;
     int32_t* dev = nullptr;
@@ -137,10 +146,10 @@ int reduce_device(ResizeState* st, int in_w, int in_h, int channels, int fx, int
 int reduce_host(ResizeState* st, int in_w, int in_h, int channels, int fx, int fy, const int32_t* box, const void* in,
                 void* out, int frames, hipStream_t stream, int* last_hip);
 
-// 16-bit requests (lanczos_resize16.hip): the tap count of the smallest fused instance that holds ksize (0: none), and the
-// launches.
+// 16-bit requests (lanczos_resize16.hip): the tap count of the smallest fused instance that holds ksize (0: none; small: the
+// instances with 3 and 5 taps count, which they do for every filter but Lanczos), and the launches.
 // Pitches are those of tightly packed rows; frame strides in bytes.
-int rs16_bucket(int ksize);
+int rs16_bucket(int ksize, bool small);
 hipError_t rs16_launch_fused(const lanczos_resize_desc* d, const RsFusedPlan& fp, const ResizeAxis* H, const ResizeAxis* V,
                              const uint8_t* in, uint8_t* out, size_t in_fs, size_t out_fs, int frames, hipStream_t stream);
 // one pass of the two-pass path over `rows` rows of `n_cols` samples: src / dst row pitches in samples
@@ -155,5 +164,11 @@ hipError_t rs32_launch_fused(const lanczos_resize_desc* d, const RsFusedPlan& fp
 hipError_t rs32_launch_pass(bool horizontal, const ResizeAxis* ax, int channels, const uint8_t* src, size_t src_fs,
                             size_t src_pitch, uint8_t* dst, size_t dst_fs, size_t dst_pitch, int n_cols, int rows, int frames,
                             hipStream_t stream);
+
+// LANCZOS_FILTER_NEAREST (lanczos_resize_nearest.hip): out[y][x] = in[vidx[y]][hidx[x]] for pixels of `channels` samples of
+// `bps` bytes (1 or 4), one launch.  hidx / vidx are device tables of out_w / out_h source indices, all inside the source.
+hipError_t rs_nearest_launch(const uint8_t* in, uint8_t* out, int in_w, int out_w, int out_h, int channels, int bps,
+                             const int32_t* hidx, const int32_t* vidx, int frames, size_t in_fs, size_t out_fs,
+                             hipStream_t stream);
 
 }  // namespace lz

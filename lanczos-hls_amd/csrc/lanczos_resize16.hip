@@ -17,6 +17,8 @@
 // adds +0.0, which leaves the sum and its rounding as they were.  u16 -> f64 is exact.
 #include "lanczos_resize.hpp"
 
+#include "lanczos_env.hpp"
+
 #include <algorithm>
 
 namespace lz {
@@ -224,10 +226,11 @@ __global__ __launch_bounds__(kRsThreads) void k_rs16_fused(Rs16Fused g) {
 }
 
 // horizontal tap counts with a fused instance (a request runs on the smallest one >= its ksize, zero-padded)
-#define LZ_RS16_BUCKETS(X) X(7) X(9) X(11) X(13) X(17) X(25)
+#define LZ_RS16_BUCKETS(X) X(3) X(5) X(7) X(9) X(11) X(13) X(17) X(25)
 
-int rs16_bucket(int ksize) {
+int rs16_bucket(int ksize, bool small) {
     int k = 0;
+    if ((!small || env().rs_no_small_buckets) && ksize < 7) ksize = 7;   // 3 and 5: the short filters only (lanczos_resize.hip)
 #define X(KB) \
     if (!k && ksize <= KB) k = KB;
     LZ_RS16_BUCKETS(X)

@@ -223,7 +223,7 @@ hipError_t rs32_launch_fused(const lanczos_resize_desc* d, const RsFusedPlan& fp
         else hipLaunchKernelGGL((k_rs32_fused<4, KB>), grid, dim3(kRsThreads), fp.lds, stream, g);                      \
         launched = true;                                                                                                \
     }
-        X(7) X(9) X(11) X(13) X(17) X(25)   // the buckets of rs16_bucket
+        X(3) X(5) X(7) X(9) X(11) X(13) X(17) X(25)   // the buckets of rs16_bucket
 #undef X
         if (!launched) return hipErrorInvalidValue;
         const hipError_t e = hipGetLastError();

@@ -1,0 +1,100 @@
+// lanczos_resize_nearest.hip -- the kernel of LANCZOS_FILTER_NEAREST: Pillow's Image.resize(size, Image.NEAREST, box)
+// (include/lanczos_hip.h).  There is no arithmetic: out[y][x] = in[vidx[y]][hidx[x]] with two index tables the
+// host builds with Pillow's running sum (resize_build_axis) and caches like the tap tables of an axis.
+//
+//   k_rs_nearest<B, C>  pixels of C samples of B bytes (1 or 4: 8-bit and float frames; pixel sizes 1, 3, 4, 12 and 16 bytes).
+//                One launch gathers both axes: a workgroup owns 256 dwords of one output row of one frame (blockIdx.x,
+//                .y, .z).  The source row is workgroup-uniform (one scalar load of vidx).  A thread owns one dword of the
+//                output row's ADDRESS grid -- the dwords as memory aligns them, wherever the row starts -- gathers the
+//                samples that fall into it (a load per sample; four byte loads, or one dword load for an aligned 4-byte
+//                pixel) and stores it packed: a wave writes 256 contiguous bytes whatever the pixel size is, and a 3-byte
+//                pixel costs no byte stores.  Only the dwords a row shares with its neighbours (a row pitch or a base that
+//                is no dword multiple) go out sample by sample.
+//
+// Loads and stores are plain global accesses with 64-bit addresses: frames of any size, bases at any sample boundary.  Every
+// index is checked on the host to lie inside the source before a table is cached, and a store is predicated on its sample
+// lying inside the row.
+#include "lanczos_resize.hpp"
+
+#include <algorithm>
+#include <type_traits>
+
+namespace lz {
+
+struct NnArgs {
+    const uint8_t* in;
+    uint8_t* out;
+    unsigned long long in_fs, out_fs;   // frame strides (bytes)
+    unsigned in_pitch, out_pitch;       // bytes of a source row, of an output row
+    int n_samples;                      // samples of an output row: out_w * C
+    const int32_t *hidx, *vidx;
+};
+
+template <int B, int C>
+__global__ __launch_bounds__(kRsThreads) void k_rs_nearest(NnArgs g) {
+    static_assert(B == 1 || B == 4, "8-bit and float samples");
+    using T = typename std::conditional<B == 1, uint8_t, uint32_t>::type;
+    constexpr int SPD = 4 / B;   // samples per dword
+    const int oy = blockIdx.y;
+    const uint8_t* srow = g.in + blockIdx.z * g.in_fs + (size_t)g.vidx[oy] * g.in_pitch;
+    uint8_t* orow = g.out + blockIdx.z * g.out_fs + (size_t)oy * g.out_pitch;
+    const int a0 = (int)((uintptr_t)orow & 3) / B;      // samples of the row's first dword that lie in front of the row
+    const int q = blockIdx.x * kRsThreads + threadIdx.x;   // dword of the row's address grid
+    const int s0 = q * SPD - a0;                         // its first sample
+    if (s0 >= g.n_samples) return;
+    const bool whole = s0 >= 0 && s0 + SPD <= g.n_samples;
+    uint32_t packed = 0u;
+    if (B == 1 && C == 4 && whole && a0 == 0 && ((uintptr_t)srow & 3) == 0) {   // the dword is pixel q
+        packed = *(const uint32_t*)(srow + (size_t)g.hidx[q] * 4);
+    } else {
+#pragma unroll
+        for (int j = 0; j < SPD; j++) {
+            const int s = s0 + j;
+            if (s < 0 || s >= g.n_samples) continue;
+            const int px = s / C, c = s - px * C;
+            packed |= (uint32_t)((const T*)srow)[g.hidx[px] * C + c] << (8 * B * j);
+        }
+    }
+    if (whole) {
+        *(uint32_t*)(orow + (ptrdiff_t)s0 * B) = packed;   // (orow - a0 * B) + 4 * q: aligned
+    } else {
+#pragma unroll
+        for (int j = 0; j < SPD; j++)
+            if (s0 + j >= 0 && s0 + j < g.n_samples) ((T*)orow)[s0 + j] = (T)(packed >> (8 * B * j));
+    }
+}
+
+hipError_t rs_nearest_launch(const uint8_t* in, uint8_t* out, int in_w, int out_w, int out_h, int channels, int bps,
+                             const int32_t* hidx, const int32_t* vidx, int frames, size_t in_fs, size_t out_fs,
+                             hipStream_t stream) {
+    NnArgs g{};
+    g.in_fs = in_fs, g.out_fs = out_fs;
+    g.in_pitch = (unsigned)in_w * channels * bps, g.out_pitch = (unsigned)out_w * channels * bps;
+    g.n_samples = out_w * channels;
+    g.hidx = hidx, g.vidx = vidx;
+    const int spd = 4 / bps;
+    const int ndw = (g.n_samples + 2 * (spd - 1)) / spd;   // dwords of the address grid a row can touch, misaligned start included
+    for (int f0 = 0; f0 < frames; f0 += 65535) {
+        const int nf = std::min(65535, frames - f0);
+        g.in = in + (size_t)f0 * in_fs;
+        g.out = out + (size_t)f0 * out_fs;
+        const dim3 grid((ndw + kRsThreads - 1) / kRsThreads, out_h, nf);
+#define LZ_NN_LAUNCH(BB)                                                                                  \
+    if (channels == 1) hipLaunchKernelGGL((k_rs_nearest<BB, 1>), grid, dim3(kRsThreads), 0, stream, g);      \
+    else if (channels == 3) hipLaunchKernelGGL((k_rs_nearest<BB, 3>), grid, dim3(kRsThreads), 0, stream, g); \
+    else hipLaunchKernelGGL((k_rs_nearest<BB, 4>), grid, dim3(kRsThreads), 0, stream, g);
+        if (bps == 1) {
+            LZ_NN_LAUNCH(1)
+        } else if (bps == 4) {
+            LZ_NN_LAUNCH(4)
+        } else {
+            return hipErrorInvalidValue;
+        }
+#undef LZ_NN_LAUNCH
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace lz

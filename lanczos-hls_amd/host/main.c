@@ -4,14 +4,16 @@
  *
  *   lanczos_upscale <in.(png|ppm|pgm)> <out.(png|ppm|pgm)> [--scale N[/D]] [--a A] [--channels C]
  *                   [--exact | --hls] [--device D] [--repeat K]
- *   lanczos_upscale <in> <out> --size WxH [--box x0,y0,x1,y1] [--reducing-gap G] [--a A] [--channels C | --alpha]
- *                   [--device D] [--repeat K]
+ *   lanczos_upscale <in> <out> --size WxH [--filter box|bilinear|hamming|bicubic|nearest|lanczos] [--box x0,y0,x1,y1]
+ *                   [--reducing-gap G] [--a A] [--channels C | --alpha] [--device D] [--repeat K]
  *                   (resize to any size, downscaling included, through lanczos_resize_host: Pillow's Image.resize with
  *                   LANCZOS, not the reference's model; refuses --scale, --exact, --hls and the multi-device flags.
  *                   --alpha: four channels, the fourth straight alpha, resized as Pillow's mode RGBA and written as an
  *                   RGBA PNG; needs --size, --channels 4 if --channels is given, and a .png output.
  *                   --box: resize that region of the source (source pixels, fractions allowed), Image.resize's box;
- *                   --reducing-gap G >= 1: reduce by whole factors first, Image.resize's reducing_gap; not with --alpha)
+ *                   --reducing-gap G >= 1: reduce by whole factors first, Image.resize's reducing_gap; not with --alpha;
+ *                   --filter: Image.resize's resample, default lanczos; every other filter needs a = 3, nearest takes no
+ *                   --reducing-gap)
  *                   [--devices 0-7 | 0,2,5] [--frames F] [--split frames|rows] [--root]   (several GPUs of one node, plain C:
  *                   the image is replicated into a batch of F frames and the batch -- or every frame's rows -- is split
  *                   over the devices by lanczos_resample_multi_host; the first result frame is written.  --root: the batch
@@ -44,13 +46,16 @@ static double ms_since(const struct timespec* t0) {
     return (t1.tv_sec - t0->tv_sec) * 1e3 + (t1.tv_nsec - t0->tv_nsec) / 1e6;
 }
 
+static const char* const filter_names[6] = {"lanczos", "box", "bilinear", "hamming", "bicubic", "nearest"}; /* LANCZOS_FILTER_* */
+
 /* --size WxH: one frame through lanczos_resize_host */
 static int resize_main(const char* out_path, const uint8_t* img, int width, int height, int channels, int out_w, int out_h,
-                       int a, int alpha, int device, int repeat, const double* box, double gap) {
+                       int a, int alpha, int filter, int device, int repeat, const double* box, double gap) {
     lanczos_resize_desc d;
     lanczos_resize_opts o;
     lanczos_resize_plan_ex plan;
-    int rc = lanczos_resize_desc_init_ex(&d, width, height, out_w, out_h, channels, a, alpha ? LANCZOS_RESIZE_ALPHA : 0);
+    int rc = lanczos_resize_desc_init_ex(&d, width, height, out_w, out_h, channels, a,
+                                         (alpha ? LANCZOS_RESIZE_ALPHA : 0) | LANCZOS_RESIZE_FILTER(filter));
     if (rc == LANCZOS_OK) rc = lanczos_resize_opts_init(&o, &d);
     if (rc == LANCZOS_OK) {
         if (box) memcpy(o.box, box, sizeof(o.box));
@@ -62,6 +67,7 @@ static int resize_main(const char* out_path, const uint8_t* img, int width, int 
         return EXIT_FAILURE;
     }
     printf("Resize %d x %d -> %d x %d, a = %d%s\n", width, height, out_w, out_h, a, alpha ? ", straight alpha" : "");
+    if (filter != LANCZOS_FILTER_LANCZOS) printf("Filter %s\n", filter_names[filter]);
     if (box) printf("Box %g,%g,%g,%g\n", o.box[0], o.box[1], o.box[2], o.box[3]);
     if (plan.fx > 1 || plan.fy > 1)
         printf("Reduce by %d x %d over %d,%d,%d,%d to %d x %d first\n", plan.fx, plan.fy, plan.safe_box[0], plan.safe_box[1],
@@ -99,7 +105,7 @@ int main(int argc, char* argv[]) {
     int scale_n = 2, scale_d = 1, a = 3, want_channels = 3, exact = 0, hls = 0, device = 0, repeat = 1;
     int devices[64], n_devices = 0, frames = 1, split = LANCZOS_SPLIT_FRAMES, root = 0;
     int size_w = 0, size_h = 0, have_size = 0, upscale_only = 0; /* upscale_only: a flag --size cannot go with */
-    int alpha = 0, have_channels = 0, have_box = 0, have_gap = 0;
+    int alpha = 0, have_channels = 0, have_box = 0, have_gap = 0, filter = LANCZOS_FILTER_LANCZOS, have_filter = 0;
     double box[4] = {0, 0, 0, 0}, gap = 0.0;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--size") && i + 1 < argc) {
@@ -111,6 +117,11 @@ int main(int argc, char* argv[]) {
         } else if (!strcmp(argv[i], "--reducing-gap") && i + 1 < argc) {
             char tail;
             have_gap = sscanf(argv[++i], "%lf%c", &gap, &tail) == 1 && gap >= 1.0 ? 1 : -1;
+        } else if (!strcmp(argv[i], "--filter") && i + 1 < argc) {
+            have_filter = -1;
+            i++;
+            for (int f = 0; f < 6; f++)
+                if (!strcmp(argv[i], filter_names[f])) filter = f, have_filter = 1;
         } else if (!strcmp(argv[i], "--scale") && i + 1 < argc) {
             upscale_only = 1;
             scale_d = 1;
@@ -163,7 +174,8 @@ int main(int argc, char* argv[]) {
     if (!in_path || !out_path) {
         fprintf(stderr, "usage: %s <in.png|ppm> <out.png|ppm> [--scale N[/D]] [--a A] [--channels C] [--exact|--hls] "
                         "[--device D] [--repeat K] [--devices 0-7|0,2,5] [--frames F] [--split frames|rows] [--root]\n"
-                        "       %s <in.png|ppm> <out.png|ppm> --size WxH [--box x0,y0,x1,y1] [--reducing-gap G] [--a A] "
+                        "       %s <in.png|ppm> <out.png|ppm> --size WxH [--filter box|bilinear|hamming|bicubic|nearest|lanczos] "
+                        "[--box x0,y0,x1,y1] [--reducing-gap G] [--a A] "
                         "[--channels C | --alpha] [--device D] [--repeat K]\n",
                 argv[0], argv[0]);
         return EXIT_FAILURE;
@@ -184,6 +196,10 @@ int main(int argc, char* argv[]) {
         fprintf(stderr, "--box and --reducing-gap need --size\n");
         return EXIT_FAILURE;
     }
+    if (have_filter < 0 || (have_filter && !have_size)) {
+        fprintf(stderr, "--filter takes box, bilinear, hamming, bicubic, nearest or lanczos, and needs --size\n");
+        return EXIT_FAILURE;
+    }
     if (alpha) {
         if (!have_size || (have_channels && want_channels != 4) || !ends_with(out_path, ".png")) {
             fprintf(stderr, "--alpha needs --size, four channels (no --channels other than 4) and a .png output\n");
@@ -201,7 +217,7 @@ int main(int argc, char* argv[]) {
         return EXIT_FAILURE;
     }
     if (have_size) {
-        const int rc = resize_main(out_path, img, width, height, want_channels, size_w, size_h, a, alpha, device, repeat,
+        const int rc = resize_main(out_path, img, width, height, want_channels, size_w, size_h, a, alpha, filter, device, repeat,
                                    have_box ? box : NULL, have_gap ? gap : 0.0);
         lz_image_free(img);
         return rc;

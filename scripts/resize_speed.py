@@ -27,6 +27,11 @@ the flag runs rgbx,three_step).
 U1 and U4 are W1's and W4's shapes with 16-bit samples (LANCZOS_RESIZE_U16, Pillow's mode I;16): the same three paths, the
 same discipline, twice the compulsory bytes.
 
+C1, C4 (bicubic), L1, L4 (bilinear) and N1, N4 (nearest) are W1's and W4's shapes with Pillow's other filters (--only C1,C4,...;
+a build with LANCZOS_RESIZE_FILTER).  LANCZOS_RS_NO_SMALL_BUCKETS=1 in the environment pads the short filters' upscales to the
+7-tap fused instance (the A/B of the 3- and 5-tap instances).  N1 and N4 also time a device-to-device copy of the output's
+bytes on the same stream and print the ratio.
+
 F1 and F4 are W1's and W4's shapes with float samples (LANCZOS_RESIZE_F32, Pillow's mode F; uniform [0, 1) inputs): the same
 three paths, four times the compulsory bytes.  They run on request (--only F1,F4) and need a build with the flag.
 
@@ -78,11 +83,15 @@ RGBA_WORKLOADS = {   # W1's and W4's shapes, four channels
     "A1": (3840, 2160, 1920, 1080, 4, 3, 32),
     "A4": (1920, 1080, 3840, 2160, 4, 3, 32),
 }
+FILTER_WORKLOADS = {   # W1's and W4's shapes with Pillow's other filters: name: (workload, filter)
+    "C1": ("W1", "bicubic"), "C4": ("W4", "bicubic"), "L1": ("W1", "bilinear"), "L4": ("W4", "bilinear"),
+    "N4": ("W4", "nearest"), "N1": ("W1", "nearest"),   # nearest: also timed against a device-to-device copy of the output
+}
 ROUTES = ("rgbx", "alpha", "three_step")
 PATHS = {"auto": L.RESIZE_AUTO, "fused": L.RESIZE_FUSED, "two_pass": L.RESIZE_TWO_PASS}
 
 
-def run(name, spec, args, ctx, torch, bits=8):
+def run(name, spec, args, ctx, torch, bits=8, filt="lanczos"):
     iw, ih, ow, oh, c, a, f = spec
     in_fb, out_fb = iw * ih * c * bits // 8, ow * oh * c * bits // 8   # frame bytes
     step_in = f * in_fb
@@ -94,7 +103,7 @@ def run(name, spec, args, ctx, torch, bits=8):
         d = L.resize_desc(iw, ih, ow, oh, c, a, f32=True)
     else:
         xs = [torch.randint(0, 256, (f * in_fb,), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(sets)]
-        d = L.resize_desc(iw, ih, ow, oh, c, a, bits=bits)
+        d = L.resize_desc(iw, ih, ow, oh, c, a, bits=bits, filter=filt)
     ys = [torch.empty(f * out_fb, dtype=torch.uint8, device="cuda") for _ in range(sets)]
     stream = torch.cuda.current_stream()
     s = stream.cuda_stream
@@ -132,9 +141,24 @@ def run(name, spec, args, ctx, torch, bits=8):
             e1.synchronize()
             times[pn].append(e0.elapsed_time(e1) * 1e3 / args.steps)
     ctx.resize_force(L.RESIZE_AUTO)
+    if filt == "nearest":   # the yardstick of a gather: hipMemcpyAsync device to device of the output's bytes, same stream
+        paths = {"auto": paths["auto"]}   # one kernel whatever is forced
+        copies = []
+        for r in range(args.rounds):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for k in range(args.steps):
+                ys[(k + 1) % sets].copy_(ys[k % sets], non_blocking=True)
+            e1.record(stream)
+            e1.synchronize()
+            copies.append(e0.elapsed_time(e1) * 1e3 / args.steps)
+        print(json.dumps({"workload": name, "d2d_copy_of_output_us": round(statistics.median(copies), 2),
+                          "nearest_over_copy": round(statistics.median(times["auto"]) / statistics.median(copies), 3),
+                          "bytes": f * out_fb, "measured": True}), flush=True)
     for pn, (p, fam) in paths.items():
         us = statistics.median(times[pn])
-        line = {"workload": name, "shape": f"{iw}x{ih}->{ow}x{oh} C{c} a{a} u{bits}", "frames": f, "path": pn, "kernel": fam,
+        line = {"workload": name, "shape": f"{iw}x{ih}->{ow}x{oh} C{c} a{a} u{bits}" + ("" if filt == "lanczos" else " " + filt),
+                "frames": f, "path": pn, "kernel": fam, "small_buckets": os.environ.get("LANCZOS_RS_NO_SMALL_BUCKETS", "0") in ("", "0"),
                 "us_per_step": round(us, 2), "us_all_regions": [round(v, 2) for v in times[pn]],
                 "mpix_per_s": round(f * ow * oh / us, 1), "hbm_frac": round(f * (in_fb + out_fb) / (us * 1e-6) / HBM_BPS, 4),
                 "compulsory_bytes": f * (in_fb + out_fb), "input_sets_cycled": sets, "steps": args.steps,
@@ -376,6 +400,8 @@ def main():
             run(name, U16_WORKLOADS[name], args, ctx, torch, bits=16)
         elif name in F32_WORKLOADS:
             run(name, F32_WORKLOADS[name], args, ctx, torch, bits=32)
+        elif name in FILTER_WORKLOADS:
+            run(name, WORKLOADS[FILTER_WORKLOADS[name][0]], args, ctx, torch, filt=FILTER_WORKLOADS[name][1])
         else:
             run(name, WORKLOADS[name], args, ctx, torch)
     ctx.close()
