@@ -296,8 +296,11 @@ typedef struct lanczos_resize_desc {
 
 /* forced path of lanczos_resize_force (tests and A/B runs only) */
 #define LANCZOS_RESIZE_AUTO 0
-#define LANCZOS_RESIZE_FUSED 1     /* LANCZOS_ERR_UNSUPPORTED where the fused kernel cannot run the shape */
+#define LANCZOS_RESIZE_FUSED 1     /* LANCZOS_ERR_UNSUPPORTED where the fused kernel cannot run the shape, and for a tensor
+                                      request whose float frame spans 2^31 bytes or more */
 #define LANCZOS_RESIZE_TWO_PASS 2
+#define LANCZOS_RESIZE_CONVERT 3   /* the resize as AUTO plans it; a tensor request takes the converted route (the A/B of the
+                                      fused tensor epilogue); a byte request runs as under AUTO */
 
 /* host only, no GPU needed */
 int lanczos_resize_desc_init(lanczos_resize_desc* d, int in_w, int in_h, int out_w, int out_h, int channels, int a);
@@ -344,7 +347,7 @@ int lanczos_resize_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const 
                           size_t in_frame_stride, size_t out_frame_stride, void* stream);
 /* Host buffers, `frames` frames back to back; synchronous (copy in -> resize -> copy out on the context's stream). */
 int lanczos_resize_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const void* in, void* out, int frames);
-/* LANCZOS_RESIZE_AUTO / _FUSED / _TWO_PASS: tests and A/B runs only (lanczos_force_kernel does not affect resizes).
+/* LANCZOS_RESIZE_AUTO / _FUSED / _TWO_PASS / _CONVERT: tests and A/B runs only (lanczos_force_kernel does not affect resizes).
  * LANCZOS_FILTER_NEAREST has one path: forced _FUSED is LANCZOS_ERR_UNSUPPORTED for it, forced _TWO_PASS changes nothing. */
 int lanczos_resize_force(lanczos_ctx* ctx, int path);
 
@@ -408,6 +411,55 @@ int lanczos_resize_device_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, con
                              void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream);
 int lanczos_resize_host_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* in,
                            void* out, int frames);
+
+/* ---- resize 8-bit frames straight into a float tensor (PIL.Image.resize -> ToTensor() -> Normalize(mean, std)) ----
+ * A tensor request is the byte request plus a table and an output layout:
+ *   out[f][c * chan_stride + y * row_stride + x * pix_stride] = lut[c * 256 + P(f, y, x, c)]
+ * where P(f, y, x, c) is exactly the byte lanczos_resize_device_ex stores for the same descriptor and options: every filter,
+ * box, reducing_gap, LANCZOS_RESIZE_ALPHA, and the plain copy where no pass runs.  out is float, strides count floats, frame f
+ * starts out_frame_stride BYTES behind frame f - 1.  CHW is (out_h * out_w, out_w, 1), HWC is (1, out_w * channels, channels);
+ * padded rows or planes and a slice of a larger tensor are larger strides.  Floats the contract does not name are not written.
+ * Table entries are copied as 32-bit words and nothing is computed on them: NaN payloads and -0.0 arrive unchanged.  An 8-bit
+ * sample has 256 values, so any per-channel pointwise map is such a table, and one built with IEEE float operations repeats
+ * torch's result bit for bit: lanczos_tensor_lut_normalize builds that of ToTensor() + Normalize().
+ * d_lut is a device pointer to channels * 256 floats which the caller owns.  The kernels read it WHEN THEY RUN, not when the
+ * call is made: it must stay allocated until they have run, and a replayed graph sees the table's contents of that moment.
+ * Routes (lanczos_last_tensor_route): where the byte request runs the fused kernel and a float frame spans less than 2^31
+ * bytes, the fused kernel's vertical pass stores the floats itself (LANCZOS_TENSOR_FUSED; LANCZOS_RESIZE_ALPHA included) --
+ * a tensor request is fused exactly when lanczos_resize_plan_host(_ex) says the byte request is, on the same plan.  Every
+ * other request (two passes, one pass, LANCZOS_FILTER_NEAREST, the plain copy, forced LANCZOS_RESIZE_TWO_PASS, larger float
+ * frames) writes its bytes to context scratch and one conversion launch follows (LANCZOS_TENSOR_CONVERTED); that scratch
+ * lives under the rules of the two-pass intermediate (one stream at a time per context; a captured launch pins the block; a
+ * captured graph must not outlive its context).  lanczos_last_kernel reports the resize kernel as for the byte request. */
+typedef struct lanczos_tensor_out {
+    const float* d_lut;     /* device: channels * 256 floats, lut[c * 256 + v]; read when the kernels run */
+    int64_t chan_stride, row_stride, pix_stride;   /* in floats, each > 0 */
+    int32_t reserved[4];    /* must be 0 */
+} lanczos_tensor_out;
+#define LANCZOS_TENSOR_FUSED 1      /* the resize kernel wrote the floats itself */
+#define LANCZOS_TENSOR_CONVERTED 2  /* the bytes went to context scratch and a conversion launch followed */
+/* LANCZOS_ERR_BAD_ARG: what lanczos_resize_validate refuses, a null t or table, a stride <= 0 (or above 2^40), non-zero
+ * reserved words, strides under which two (c, y, x) share an address -- sorted by stride, each stride must be at least the
+ * previous stride times its extent (an axis of extent 1 takes no part).  LANCZOS_ERR_UNSUPPORTED: LANCZOS_RESIZE_U16 or
+ * LANCZOS_RESIZE_F32 (a table per 16-bit value and float inputs are out of scope). */
+int lanczos_resize_tensor_validate(const lanczos_resize_desc* d, const lanczos_tensor_out* t);
+/* Host only: lut[c * 256 + v] = ((float)v / 255.0f - mean[c]) / std[c], in float with IEEE division and no contraction --
+ * bit for bit torch's uint8.to(float32).div(255).sub(mean).div(std).  mean == NULL is 0 and std == NULL is 1, so NULL, NULL is
+ * plain ToTensor().  channels: 1, 3 or 4. */
+int lanczos_tensor_lut_normalize(int channels, const float* mean, const float* std, float* lut);
+/* As lanczos_resize_device_ex (opts may be NULL) with float frames at d_out.  Further LANCZOS_ERR_BAD_ARG: d_out or
+ * out_frame_stride no multiple of 4, out_frame_stride (bytes; 0 = the frame's extent) smaller than the frame's extent
+ * ((channels - 1) * chan_stride + (out_h - 1) * row_stride + (out_w - 1) * pix_stride + 1 floats). */
+int lanczos_resize_tensor_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                 const lanczos_tensor_out* t, const void* d_in, void* d_out, int frames,
+                                 size_t in_frame_stride, size_t out_frame_stride, void* stream);
+/* Host buffers and a HOST table in t->d_lut; `frames` input frames back to back, float frames one extent apart; synchronous.
+ * Floats of `out` the strides do not name keep their contents. */
+int lanczos_resize_tensor_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                               const lanczos_tensor_out* t, const void* in, void* out, int frames);
+/* 0 if the last call on the context was no tensor call (or failed before its launches), else LANCZOS_TENSOR_FUSED or
+ * LANCZOS_TENSOR_CONVERTED */
+int lanczos_last_tensor_route(const lanczos_ctx* ctx);
 
 /* ---- reduce by whole factors (Pillow's Image.reduce((fx, fy), box), an exact integer box average) ----
  * 8-bit, 1, 3 or 4 independent interleaved channels.  box = (x0, y0, x1, y1), integers with 0 <= x0 < x1 <= in_w and the same

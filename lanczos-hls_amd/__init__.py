@@ -30,13 +30,14 @@ ROUTE_MAIN_NONE, ROUTE_MAIN_MARCH, ROUTE_MAIN_TILE, ROUTE_MAIN_RATP, ROUTE_MAIN_
 ROUTE_PREFIX_NONE, ROUTE_PREFIX_RIDING, ROUTE_PREFIX_FRONT, ROUTE_PREFIX_BEHIND, ROUTE_PREFIX_STREAMED = range(5)
 ROUTE_MAIN_NAMES = ("none", "march", "tile", "ratp", "rat", "generic", "hls")
 ROUTE_PREFIX_NAMES = ("none", "riding", "front", "behind", "streamed")
-RESIZE_AUTO, RESIZE_FUSED, RESIZE_TWO_PASS = 0, 1, 2   # lanczos_resize_force
+RESIZE_AUTO, RESIZE_FUSED, RESIZE_TWO_PASS, RESIZE_CONVERT = 0, 1, 2, 3   # lanczos_resize_force
 RESIZE_ALPHA = 1   # flag of lanczos_resize_desc.reserved[0]: channel 3 of 4 is straight alpha (Pillow's RGBA mode)
 RESIZE_U16 = 4     # flag of lanczos_resize_desc.reserved[0]: native-endian uint16 samples (Pillow's I;16 arithmetic)
 RESIZE_F32 = 16    # flag of lanczos_resize_desc.reserved[0]: float samples (Pillow's mode F arithmetic); with no other flag
 # the filter of a resize (Image.resize's `resample`), bits 8..11 of lanczos_resize_desc.reserved[0]
 FILTER_LANCZOS, FILTER_BOX, FILTER_BILINEAR, FILTER_HAMMING, FILTER_BICUBIC, FILTER_NEAREST = range(6)
 FILTER_NAMES = ("lanczos", "box", "bilinear", "hamming", "bicubic", "nearest")
+TENSOR_FUSED, TENSOR_CONVERTED = 1, 2   # lanczos_last_tensor_route: who wrote the floats of the last tensor call
 
 # every symbol include/lanczos_hip.h declares (tests check the library exports exactly these)
 ABI_SYMBOLS = [
@@ -58,6 +59,8 @@ ABI_SYMBOLS = [
     "lanczos_resize_opts_init", "lanczos_resize_taps_host_ex", "lanczos_resize_taps_f64_host_ex",
     "lanczos_resize_plan_host_ex", "lanczos_resize_device_ex", "lanczos_resize_host_ex",
     "lanczos_reduce_size", "lanczos_reduce_device", "lanczos_reduce_host",
+    "lanczos_resize_tensor_validate", "lanczos_tensor_lut_normalize", "lanczos_resize_tensor_device",
+    "lanczos_resize_tensor_host", "lanczos_last_tensor_route",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
 
@@ -119,6 +122,13 @@ class ResizePlanEx(ctypes.Structure):
                 ("pass_h", ctypes.c_int32), ("pass_v", ctypes.c_int32),
                 ("mid_row0", ctypes.c_int32), ("mid_rows", ctypes.c_int32),
                 ("inner_box", ctypes.c_double * 4), ("inner", ResizePlan)]
+
+
+class TensorOut(ctypes.Structure):
+    """lanczos_tensor_out -- the table and the float layout of a tensor request: out[c * chan_stride + y * row_stride +
+    x * pix_stride] = lut[c * 256 + byte], strides in floats."""
+    _fields_ = [("d_lut", ctypes.c_void_p), ("chan_stride", ctypes.c_int64), ("row_stride", ctypes.c_int64),
+                ("pix_stride", ctypes.c_int64), ("reserved", ctypes.c_int32 * 4)]
 
 
 _LIB = None
@@ -217,6 +227,14 @@ def _lib():
         L.lanczos_reduce_host.argtypes = [c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_int]
         if hasattr(L, "lanczos_resize_desc_init_filter"):   # (an older build loaded through LANCZOS_LIB has only Lanczos)
             L.lanczos_resize_desc_init_filter.argtypes = [PRD] + [c_int] * 7
+        if hasattr(L, "lanczos_resize_tensor_device"):   # (nor has it the tensor entry)
+            PTO = ctypes.POINTER(TensorOut)
+            L.lanczos_resize_tensor_validate.argtypes = [PRD, PTO]
+            L.lanczos_tensor_lut_normalize.argtypes = [c_int, c_void_p, c_void_p, c_void_p]
+            L.lanczos_resize_tensor_device.argtypes = [c_void_p, PRD, PRO, PTO, c_void_p, c_void_p, c_int, c_size_t, c_size_t,
+                                                       c_void_p]
+            L.lanczos_resize_tensor_host.argtypes = [c_void_p, PRD, PRO, PTO, c_void_p, c_void_p, c_int]
+            L.lanczos_last_tensor_route.argtypes = [c_void_p]
         L.lanczos_strerror.restype = ctypes.c_char_p
         L.lanczos_version.argtypes = []
         L.lanczos_version.restype = ctypes.c_char_p
@@ -374,6 +392,48 @@ def resize_plan_host(desc, frames=1, box=None, reducing_gap=None, opts=None):
     _check(_lib().lanczos_resize_plan_host_ex(ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts), frames,
                                               ctypes.byref(p)), "lanczos_resize_plan_host_ex")
     return p
+
+
+def normalize_lut(channels, mean=None, std=None):
+    """The table of ToTensor() + Normalize(mean, std) as float32 [channels][256]: ((float)v / 255 - mean[c]) / std[c] in IEEE
+    float, bit for bit torch's uint8.to(float32).div(255).sub(mean).div(std).  mean=None is 0, std=None is 1."""
+    def arr(v, what):
+        if v is None:
+            return None
+        a = np.asarray(v, dtype=np.float32)
+        if a.shape not in ((), (channels,)):
+            raise LanczosError(ERR_BAD_ARG, f"normalize_lut: {what} is one value, or one per channel")
+        return np.ascontiguousarray(np.broadcast_to(a, (channels,)))
+    m, s = arr(mean, "mean"), arr(std, "std")
+    lut = np.empty((channels, 256), dtype=np.float32)
+    _check(_lib().lanczos_tensor_lut_normalize(channels, m.ctypes.data if m is not None else None,
+                                               s.ctypes.data if s is not None else None, lut.ctypes.data),
+           "lanczos_tensor_lut_normalize")
+    return lut
+
+
+def tensor_strides(layout, out_w, out_h, channels):
+    """(chan_stride, row_stride, pix_stride) in floats of a tightly packed "chw" or "hwc" frame."""
+    if layout == "chw":
+        return out_h * out_w, out_w, 1
+    if layout == "hwc":
+        return 1, out_w * channels, channels
+    raise LanczosError(ERR_BAD_ARG, f"unknown layout {layout!r}: chw or hwc")
+
+
+def tensor_out(d_lut, strides):
+    """A TensorOut: d_lut a pointer to channels * 256 floats (device memory for the device entry), strides =
+    (chan_stride, row_stride, pix_stride) in floats.  Validated where it is used (resize_tensor_validate)."""
+    t = TensorOut()
+    t.d_lut = d_lut
+    t.chan_stride, t.row_stride, t.pix_stride = (int(v) for v in strides)
+    return t
+
+
+def resize_tensor_validate(desc, t):
+    """lanczos_resize_tensor_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the request is refused."""
+    _check(_lib().lanczos_resize_tensor_validate(ctypes.byref(desc), ctypes.byref(t) if t is not None else None),
+           "lanczos_resize_tensor_validate")
 
 
 def _factor_pair(factor):
@@ -571,6 +631,50 @@ class Context:
                                                    d_in, d_out, frames, in_frame_stride, out_frame_stride, stream),
                    "lanczos_resize_device_ex")
 
+    # -- resize straight into a float tensor (PIL.Image.resize -> ToTensor() -> Normalize(), lanczos_resize_tensor_*)
+    def resize_tensor(self, img, out_w, out_h, mean=None, std=None, lut=None, layout="chw", a=3, alpha=False, box=None,
+                      reducing_gap=None, filter=FILTER_LANCZOS):
+        """img: uint8 [H][W], [H][W][C] or [F][H][W][C] as Context.resize takes it -> float32 [F][C][H][W] (layout="chw") or
+        [F][H][W][C] ("hwc"), the frame axis dropped as resize drops it: lut[c][byte] of the bytes Context.resize returns for
+        the same arguments.  lut: float32 [C][256], moved bit for bit; None = normalize_lut(C, mean, std), with which the
+        result is bit for bit torch.from_numpy(bytes).permute(2, 0, 1).float().div(255).sub(mean).div(std)."""
+        img = np.ascontiguousarray(img)
+        if img.dtype != np.uint8 or img.ndim not in (2, 3, 4):
+            raise LanczosError(ERR_BAD_ARG, "resize_tensor: expected a uint8 [H][W], [H][W][C] or [F][H][W][C] array")
+        x = img.reshape(img.shape + (1,)) if img.ndim == 2 else img
+        x = x if x.ndim == 4 else x[None]
+        f, h, w, c = x.shape
+        d = resize_desc(w, h, out_w, out_h, c, a, alpha, filter=filter)
+        if lut is None:
+            lut = normalize_lut(c, mean, std)
+        elif mean is not None or std is not None:
+            raise LanczosError(ERR_BAD_ARG, "resize_tensor: a table or mean / std, not both")
+        lut = np.ascontiguousarray(lut)
+        if lut.dtype != np.float32 or lut.size != c * 256:
+            raise LanczosError(ERR_BAD_ARG, f"resize_tensor: the table is float32 [{c}][256]")
+        t = tensor_out(lut.ctypes.data, tensor_strides(layout, out_w, out_h, c))
+        out = np.empty((f, c, out_h, out_w) if layout == "chw" else (f, out_h, out_w, c), dtype=np.float32)
+        _check(_lib().lanczos_resize_tensor_host(self._h, ctypes.byref(d), _opts_ref(d, box, reducing_gap, None),
+                                                 ctypes.byref(t), x.ctypes.data, out.ctypes.data, f),
+               "lanczos_resize_tensor_host")
+        return out if img.ndim == 4 else out[0]
+
+    def resize_tensor_device(self, desc, d_in, d_out, frames, d_lut, strides, in_frame_stride=0, out_frame_stride=0,
+                             stream=None, box=None, reducing_gap=None, opts=None):
+        """Device pointers, asynchronous on `stream`: uint8 frames at d_in -> float frames at d_out, out_frame_stride in BYTES
+        (0 = one frame's extent).  d_lut: device pointer to channels * 256 floats, read when the kernels run (a replayed
+        graph sees its contents of that moment).  strides = (chan_stride, row_stride, pix_stride) in floats, e.g.
+        tensor_strides("chw", ...), or a ready TensorOut (d_lut then unused).  box / reducing_gap / opts as resize_device."""
+        t = strides if isinstance(strides, TensorOut) else tensor_out(d_lut, strides)
+        _check(_lib().lanczos_resize_tensor_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
+                                                   ctypes.byref(t), d_in, d_out, frames, in_frame_stride, out_frame_stride,
+                                                   stream), "lanczos_resize_tensor_device")
+
+    def last_tensor_route(self):
+        """TENSOR_FUSED (the resize kernel stored the floats), TENSOR_CONVERTED (bytes to scratch, then a conversion launch),
+        or 0 if the last call on the context was no tensor call."""
+        return _lib().lanczos_last_tensor_route(self._h)
+
     # -- reduce by whole factors (Pillow's Image.reduce, lanczos_reduce_*)
     def reduce(self, img, factor, box=None):
         """img: uint8 [H][W], [H][W][C] or [F][H][W][C] -> the same layout reduced by `factor` (an int or (fx, fy)) over the
@@ -602,7 +706,8 @@ class Context:
                                             out_frame_stride, stream), "lanczos_reduce_device")
 
     def resize_force(self, path):
-        """RESIZE_AUTO / RESIZE_FUSED / RESIZE_TWO_PASS (tests and A/B runs)."""
+        """RESIZE_AUTO / RESIZE_FUSED / RESIZE_TWO_PASS (tests and A/B runs); RESIZE_CONVERT: as AUTO, but a tensor request takes
+        the converted route."""
         _check(_lib().lanczos_resize_force(self._h, path), "lanczos_resize_force")
 
     def timing_enable(self, on=True):

@@ -67,6 +67,7 @@ struct lanczos_ctx {
     std::vector<void*> kept_dev, kept_host;   // blocks of evicted plans a live graph may still name: freed by lanczos_destroy
     std::mutex mu;
     int last_kernel = LANCZOS_KERNEL_NONE;
+    int last_tensor_route = 0;   // lanczos_last_tensor_route: LANCZOS_TENSOR_* of the last call, 0 unless it was a tensor call
     int last_route = 0;      // lanczos_last_route: main kernel, prefix route and launch count of the last upscale call
     int route_launches = 0;  // launches of the call in flight (reset by the entry points, counted where a launch is issued)
     int route_seen = 0;      // prefix routes of those launches, one bit each
@@ -117,7 +118,7 @@ namespace {
 
 // lanczos_last_route: an upscale entry point starts a call with route_begin; every launch of the call reports itself with
 // route_launch at the point where it is issued
-void route_begin(lanczos_ctx* ctx) { ctx->last_route = ctx->route_launches = ctx->route_seen = 0; }
+void route_begin(lanczos_ctx* ctx) { ctx->last_route = ctx->route_launches = ctx->route_seen = ctx->last_tensor_route = 0; }
 void route_launch(lanczos_ctx* ctx, int main_kernel, int prefix_route) {
     if (ctx->route_launches < 0x7fff) ctx->route_launches++;
     ctx->route_seen |= 1 << prefix_route;
@@ -1205,6 +1206,50 @@ int lanczos_resize_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const vo
     return lanczos_resize_host_ex(ctx, d, nullptr, in, out, frames);
 }
 
+int lanczos_resize_tensor_validate(const lanczos_resize_desc* d, const lanczos_tensor_out* t) {
+    return lz::tensor_validate(d, t);
+}
+
+int lanczos_tensor_lut_normalize(int channels, const float* mean, const float* std, float* lut) {
+    if ((channels != 1 && channels != 3 && channels != 4) || !lut) return LANCZOS_ERR_BAD_ARG;
+    lz::tensor_lut_normalize(channels, mean, std, lut);
+    return LANCZOS_OK;
+}
+
+int lanczos_resize_tensor_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                 const lanczos_tensor_out* t, const void* d_in, void* d_out, int frames,
+                                 size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    int rc = lz::tensor_validate(d, t);
+    if (rc != LANCZOS_OK) return rc;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
+    route_begin(ctx);
+    lz::RsTensorCall tc;
+    tc.t = t, tc.extent_bytes = lz::tensor_extent_bytes(d, t);
+    rc = lz::resize_device(ctx->resize, d, opts, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
+                           &ctx->last_kernel, &ctx->last_hip, &tc);
+    ctx->last_tensor_route = tc.route;
+    return rc;
+}
+
+int lanczos_resize_tensor_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                               const lanczos_tensor_out* t, const void* in, void* out, int frames) {
+    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    int rc = lz::tensor_validate(d, t);
+    if (rc != LANCZOS_OK) return rc;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->stream) return LANCZOS_ERR_HIP;
+    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
+    route_begin(ctx);
+    return lz::resize_tensor_host(ctx->resize, d, opts, t, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip,
+                                  &ctx->last_tensor_route);
+}
+
+int lanczos_last_tensor_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_tensor_route : 0; }
+
 int lanczos_reduce_size(int in_w, int in_h, int fx, int fy, const int32_t* box, int* out_w, int* out_h) {
     if (!out_w || !out_h) return LANCZOS_ERR_BAD_ARG;
     int rb[4];
@@ -1240,7 +1285,7 @@ int lanczos_reduce_host(lanczos_ctx* ctx, int in_w, int in_h, int channels, int 
 }
 
 int lanczos_resize_force(lanczos_ctx* ctx, int path) {
-    if (!ctx || path < LANCZOS_RESIZE_AUTO || path > LANCZOS_RESIZE_TWO_PASS) return LANCZOS_ERR_BAD_ARG;
+    if (!ctx || path < LANCZOS_RESIZE_AUTO || path > LANCZOS_RESIZE_CONVERT) return LANCZOS_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lock(ctx->mu);
     int rc = resize_state(ctx);
     if (rc != LANCZOS_OK) return rc;

@@ -30,6 +30,7 @@
 #include "lanczos_resize.hpp"
 
 #include "lanczos_alpha.hpp"
+#include "lanczos_resize_fused.hpp"
 #include "lanczos_env.hpp"
 
 #include <algorithm>
@@ -234,9 +235,6 @@ constexpr int kRsFusedMaxLds = 80 * 1024;   // at least two fused workgroups per
 constexpr int kRsRowsPerChunkMin = 4 * kRsOB;
 constexpr int kRsTargetWgs = 2048;
 
-__device__ __forceinline__ int rs_mad(int sample, int coeff, int acc) { return __mul24(sample, coeff) + acc; }
-__device__ __forceinline__ uint32_t rs_clip8(int acc) { return (uint32_t)min(max(acc >> kResizePrecision, 0), 255); }
-
 // one pass of the two-pass path: `n_cols` samples per output row, `rows` output rows, frames in blockIdx.z
 struct RsPass {
     const uint8_t* src;
@@ -328,177 +326,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_v_alpha(RsPass p) {
     rs_store_px(p.dst + blockIdx.z * p.dst_fs + o * p.dst_pitch + (size_t)x * 4, rs_unpremul_px(rs_clip_px(acc)));
 }
 
-struct RsFused {
-    const uint8_t* in;
-    uint8_t* out;
-    unsigned long long in_fs, out_fs;
-    int in_pitch, out_pitch, in_h, out_w, out_h;
-    const int32_t *hf, *hc, *hk;
-    int hks;
-    const int32_t *vf, *vc, *vk;
-    int vks;
-    int strips, rows_per_chunk;   // grid.x = strips * chunks, grid.y = frames
-    int ring_rows, stage_rows, stage_dw;
-};
-
-template <int C>
-struct RsStrip {
-    static constexpr int SW = rs_strip_width(C, 1);   // output pixels per strip
-    static constexpr int RL = kRsThreads / SW;    // input rows per horizontal round
-    static constexpr int RDW = SW * C / 4;        // ring row in dwords
-    static constexpr int WPR = RDW / 64;          // waves per ring row in the vertical pass
-};
-
-// ALPHA (LANCZOS_RESIZE_ALPHA, C == 4): the staging loads premultiply, once per staged pixel and not once per window that
-// reads it, and the vertical pass divides alpha out where it packs its dword, which for four channels is one pixel.  For
-// that the staged dwords are pixels: a frame base that is no dword multiple (every row then starts `delta` bytes into a
-// dword, the row pitch being one) is shifted out while staging, and the horizontal pass reads its window unshifted.
-template <int C, int K, bool ALPHA = false>
-__global__ __launch_bounds__(kRsThreads) void k_rs_fused(RsFused g) {
-    static_assert(!ALPHA || C == 4, "alpha is the fourth of four channels");
-    using S = RsStrip<C>;
-    constexpr int SW = S::SW, RL = S::RL, RDW = S::RDW, WPR = S::WPR;
-    constexpr int NE = (K * C + 3) / 4;   // dwords of one horizontal window
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
-    uint32_t* ring = lds;                        // [ring_rows][RDW]
-    uint32_t* stage = lds + g.ring_rows * RDW;   // [stage_rows][stage_dw]
-    uint8_t* ring8 = (uint8_t*)ring;
-
-    const int tid = threadIdx.x;
-    const int strip = blockIdx.x % g.strips, chunk = blockIdx.x / g.strips;
-    const int x0 = strip * SW;
-    const int sw = min(SW, g.out_w - x0);
-    const int xs = g.hf[x0];   // first input pixel of the strip's span
-
-    // horizontal: this thread's output column for the whole march, its coefficients in registers
-    const int px = tid % SW, rl = tid / SW;
-    int kh[K];
-    int hoffb;
-    {
-        const int p = x0 + min(px, sw - 1);
-        const int n = px < sw ? g.hc[p] : 0;
-        hoffb = (g.hf[p] - xs) * C;
-#pragma unroll
-        for (int k = 0; k < K; k++) kh[k] = k < n ? g.hk[(size_t)p * g.hks + k] : 0;
-    }
-
-    const uint8_t* fin = g.in + blockIdx.y * g.in_fs;
-    // dword-aligned base and range: the bytes in front of the frame and behind its end that share a dword with it (same
-    // page) are read but only ever multiplied by zero coefficients; everything further out reads as 0
-    const int delta = (int)((uintptr_t)fin & 3);
-    const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(fin - delta), 0, (unsigned)((delta + g.in_h * g.in_pitch + 3) & ~3), 0x00020000);
-    uint8_t* fout = g.out + blockIdx.y * g.out_fs;
-    const __amdgpu_buffer_rsrc_t orsrc =
-        __builtin_amdgcn_make_buffer_rsrc(fout, 0, (unsigned)(g.out_h * g.out_pitch), 0x00020000);
-    const bool out_aligned = (((uintptr_t)fout | (unsigned)g.out_pitch | (unsigned)(x0 * C)) & 3) == 0;
-    const int valid_bytes = sw * C;
-
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-    const int o_begin = chunk * g.rows_per_chunk;
-    const int o_end = min(o_begin + g.rows_per_chunk, g.out_h);
-    const float inv_sd = 1.0f / (float)g.stage_dw;
-    int hi = g.vf[o_begin];   // next input row to produce
-    for (int o0 = o_begin; o0 < o_end; o0 += kRsOB) {
-        const int nob = min(kRsOB, o_end - o0);
-        const int lo = g.vf[o0];
-        const int need = g.vf[o0 + nob - 1] + g.vc[o0 + nob - 1];
-        if (hi < lo) hi = lo;
-        while (hi < need) {
-            const int nr = min(g.stage_rows, need - hi);
-            // kRsLoadBatch loads in flight per thread before the first LDS write (one HBM latency per batch, not per dword)
-            const int total = nr * g.stage_dw;
-            for (int u0 = tid; u0 < total; u0 += kRsLoadBatch * kRsThreads) {
-                uint32_t v[kRsLoadBatch];
-                uint32_t vn[ALPHA ? kRsLoadBatch : 1];   // ALPHA, delta != 0: the dword behind v[b], the rest of its pixel
-                (void)vn;
-#pragma unroll
-                for (int b = 0; b < kRsLoadBatch; b++) {
-                    const int u = u0 + b * kRsThreads;
-                    int r = (int)((float)u * inv_sd);   // u / stage_dw, corrected below (u < 2^20)
-                    r -= r * g.stage_dw > u;
-                    r += (r + 1) * g.stage_dw <= u;
-                    const int off = delta + (hi + r) * g.in_pitch + xs * C;
-                    const int at = (off & ~3) + 4 * (u - r * g.stage_dw);
-                    v[b] = u < total ? __builtin_amdgcn_raw_buffer_load_b32(irsrc, at, 0, 0) : 0u;
-                    if constexpr (ALPHA)
-                        vn[b] = delta != 0 && u < total ? __builtin_amdgcn_raw_buffer_load_b32(irsrc, at + 4, 0, 0) : 0u;
-                }
-#pragma unroll
-                for (int b = 0; b < kRsLoadBatch; b++)
-                    if (u0 + b * kRsThreads < total) {
-                        if constexpr (ALPHA)
-                            stage[u0 + b * kRsThreads] = rs_premul_px(__builtin_amdgcn_alignbyte(vn[b], v[b], (unsigned)delta));
-                        else
-                            stage[u0 + b * kRsThreads] = v[b];
-                    }
-            }
-            __syncthreads();
-            for (int j = rl; j < nr; j += RL) {
-                const int pos = (ALPHA ? 0 : (delta + (hi + j) * g.in_pitch + xs * C) & 3) + hoffb;
-                const uint32_t* srow = stage + j * g.stage_dw + (pos >> 2);
-                const unsigned sh = ALPHA ? 0u : pos & 3;   // ALPHA: the staged dwords are pixels
-                uint32_t dw[NE + 1];
-#pragma unroll
-                for (int t = 0; t <= NE; t++) dw[t] = !ALPHA || t < NE ? srow[t] : 0u;
-                int acc[C];
-#pragma unroll
-                for (int c = 0; c < C; c++) acc[c] = 1 << (kResizePrecision - 1);
-#pragma unroll
-                for (int t = 0; t < NE; t++) {
-                    const uint32_t e = __builtin_amdgcn_alignbyte(dw[t + 1], dw[t], sh);
-#pragma unroll
-                    for (int b = 0; b < 4; b++) {
-                        const int idx = t * 4 + b;
-                        if (idx < K * C) acc[idx % C] = rs_mad((int)((e >> (8 * b)) & 255u), kh[idx / C], acc[idx % C]);
-                    }
-                }
-                uint8_t* rrow = ring8 + ((hi + j) % g.ring_rows) * (RDW * 4) + px * C;
-#pragma unroll
-                for (int c = 0; c < C; c++) rrow[c] = (uint8_t)rs_clip8(acc[c]);
-            }
-            __syncthreads();
-            hi += nr;
-        }
-        // vertical: one output row per wave (WPR waves per row), coefficients uniform
-        for (int q = wave; q < nob * WPR; q += kRsThreads / 64) {
-            const int r = q / WPR;
-            const int o = o0 + r;
-            const int dcol = (q - r * WPR) * 64 + lane;
-            const int f = g.vf[o], n = g.vc[o];
-            const int32_t* kv = g.vk + (size_t)o * g.vks;
-            int slot = f % g.ring_rows;
-            int a0 = 1 << (kResizePrecision - 1), a1 = a0, a2 = a0, a3 = a0;
-#pragma unroll 4
-            for (int i = 0; i < n; i++) {
-                const int k = kv[i];
-                const uint32_t w = ring[slot * RDW + dcol];
-                a0 = rs_mad((int)(w & 255u), k, a0);
-                a1 = rs_mad((int)((w >> 8) & 255u), k, a1);
-                a2 = rs_mad((int)((w >> 16) & 255u), k, a2);
-                a3 = rs_mad((int)(w >> 24), k, a3);
-                if (++slot == g.ring_rows) slot = 0;
-            }
-            const int b0 = dcol * 4;
-            if (b0 < valid_bytes) {
-                const int row_off = o * g.out_pitch + x0 * C + b0;
-                uint32_t packed = rs_clip8(a0) | (rs_clip8(a1) << 8) | (rs_clip8(a2) << 16) | (rs_clip8(a3) << 24);
-                if constexpr (ALPHA) packed = rs_unpremul_px(packed);
-                if (out_aligned && b0 + 4 <= valid_bytes) {
-                    __builtin_amdgcn_raw_buffer_store_b32(packed, orsrc, row_off, 0, 0);
-                } else {
-                    for (int b = 0; b < 4 && b0 + b < valid_bytes; b++)
-                        __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(packed >> (8 * b)), orsrc, row_off + b, 0, 0);
-                }
-            }
-        }
-    }
-}
-
-// horizontal tap counts with a fused instance (a request runs on the smallest one >= its ksize, zero-padded).  3 and 5 serve
-// the upscales of the short filters (box and bilinear: ksize 3, bicubic: 5) and only them: a Lanczos request keeps the
-// instance it always had (a = 2 upscales, ksize 5, run on 7).  LANCZOS_RS_NO_SMALL_BUCKETS=1 pads the short filters to 7 too
-#define LZ_RS_BUCKETS(X) X(3) X(5) X(7) X(9) X(11) X(13) X(17) X(25)
+// k_rs_fused, its launch arguments and its tap-count buckets (LZ_RS_BUCKETS): lanczos_resize_fused.hpp
 
 static int rs_bucket(int ksize, bool small) {
     int k = 0;
@@ -534,6 +362,7 @@ ResizeState::~ResizeState() {   // the owner has drained the device
     for (void* p : kept) (void)hipFree(p);
     if (scratch.p) (void)hipFree(scratch.p);
     if (reduced.p) (void)hipFree(reduced.p);
+    if (tensor_bytes.p) (void)hipFree(tensor_bytes.p);
     if (stage_in) (void)hipFree(stage_in);
     if (stage_out) (void)hipFree(stage_out);
     if (upload) (void)hipStreamDestroy(upload);
@@ -751,8 +580,11 @@ static hipError_t rs_launch_pass(bool horizontal, const RsPass& p0, int rows, in
 
 // the resize that remains once the options are resolved: `d` describes the frames at `in` (the caller's, or the reduced
 // ones), sh / sv are the source spans of its two axes
+// tc: a tensor request, `out` / `out_fs` then being the float frames.  Where the fused kernel runs it stores them itself;
+// everything else writes its bytes to context scratch and k_rs_to_tensor follows
 static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh, RsSpan sv, const uint8_t* in, uint8_t* out,
-                        int frames, size_t in_fs, size_t out_fs, hipStream_t stream, int* last_kernel, int* last_hip) {
+                        int frames, size_t in_fs, size_t out_fs, hipStream_t stream, int* last_kernel, int* last_hip,
+                        RsTensorCall* tc) {
     const int C = d->channels;
     const size_t B = (size_t)resize_bps(d);   // bytes per sample
     const bool f32 = B == 4;
@@ -778,6 +610,18 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     const bool fused_ok = !nearest && need_h && need_v && rs_fused_plan(d, H->host, V->host, frames, &fp);
     if (st->force == LANCZOS_RESIZE_FUSED && !fused_ok) return LANCZOS_ERR_UNSUPPORTED;
     const bool fused = fused_ok && st->force != LANCZOS_RESIZE_TWO_PASS;
+    // 32-bit buffer offsets into the float frame: a larger one is converted, and refused where the fused kernel is forced
+    const bool t_fits = tc && tc->extent_bytes < ((size_t)1 << 31);
+    if (tc && st->force == LANCZOS_RESIZE_FUSED && !t_fits) return LANCZOS_ERR_UNSUPPORTED;
+    const bool t_fused = fused && t_fits && st->force != LANCZOS_RESIZE_CONVERT;
+    uint8_t* const t_out = out;
+    const size_t t_fs = out_fs;
+    if (tc && !t_fused) {
+        const size_t bytes_fs = ((size_t)d->out_w * d->out_h * C + 3) & ~(size_t)3;
+        rc = rs_scratch(st, &st->tensor_bytes, (size_t)frames * bytes_fs, stream, capturing, last_hip);
+        if (rc != LANCZOS_OK) return rc;
+        out = (uint8_t*)st->tensor_bytes.p, out_fs = bytes_fs;
+    }
     // two passes: the horizontal one produces the rows the vertical taps read and no others, mid_rows of them from source
     // row mid_row0 on, and the scratch holds exactly those; the vertical pass indexes it through a base mid_row0 rows in
     // front of it, which it never dereferences below the block (its first tap is row mid_row0)
@@ -787,9 +631,10 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     const size_t in_pitch = (size_t)d->in_w * C * B;
     hipError_t e = hipSuccess;
     if (fused) {
-        e = f32   ? rs32_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream)
-            : u16 ? rs16_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream)
-                  : rs_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream);
+        e = t_fused ? rs_tensor_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, *tc, stream)
+            : f32   ? rs32_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream)
+            : u16   ? rs16_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream)
+                    : rs_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream);
         *last_kernel = LANCZOS_KERNEL_RESIZE_FUSED;
     } else if (nearest) {
         e = rs_nearest_launch(in, out, d->in_w, d->out_w, d->out_h, C, (int)B, H->first(), V->first(), frames, in_fs, out_fs,
@@ -845,6 +690,11 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
         }
         *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
     }
+    if (tc) {
+        if (!t_fused && e == hipSuccess)
+            e = rs_to_tensor_launch(out, out_fs, t_out, t_fs, d->out_w, d->out_h, C, *tc->t, frames, stream);
+        tc->route = t_fused ? LANCZOS_TENSOR_FUSED : LANCZOS_TENSOR_CONVERTED;
+    }
     if (capturing) {   // a live graph may name these tables: they stay until the context goes
         for (ResizeAxis* ax : {H, V})
             if (ax) {
@@ -866,17 +716,19 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
 
 int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* d_in, void* d_out,
                   int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream, int* last_kernel,
-                  int* last_hip) {
+                  int* last_hip, RsTensorCall* tc) {
     RsResolved r;
     int rc = resize_resolve(d, o, &r);
     if (rc != LANCZOS_OK) return rc;
     const int C = d->channels;
     const size_t B = (size_t)resize_bps(d);   // bytes per sample
-    const size_t in_frame = (size_t)d->in_w * d->in_h * C * B, out_frame = (size_t)d->out_w * d->out_h * C * B;
+    const size_t in_frame = (size_t)d->in_w * d->in_h * C * B;
+    const size_t out_frame = tc ? tc->extent_bytes : (size_t)d->out_w * d->out_h * C * B;
     const size_t in_fs = in_frame_stride ? in_frame_stride : in_frame;
     const size_t out_fs = out_frame_stride ? out_frame_stride : out_frame;
     if (in_fs < in_frame || out_fs < out_frame) return LANCZOS_ERR_BAD_ARG;
     if ((((uintptr_t)d_in | (uintptr_t)d_out | in_fs | out_fs) & (B - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
+    if (tc && (((uintptr_t)d_out | out_fs) & 3) != 0) return LANCZOS_ERR_BAD_ARG;   // float frames
     const uint8_t* in = (const uint8_t*)d_in;
     if (r.reduces()) {   // reducing_gap: reduce into context scratch, then resize the reduced frames
         int rb[4];
@@ -891,9 +743,9 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_r
             return LANCZOS_ERR_HIP;
         }
         return resize_inner(st, &r.inner, r.h, r.v, (const uint8_t*)st->reduced.p, (uint8_t*)d_out, frames, red_fs, out_fs,
-                            stream, last_kernel, last_hip);
+                            stream, last_kernel, last_hip, tc);
     }
-    return resize_inner(st, d, r.h, r.v, in, (uint8_t*)d_out, frames, in_fs, out_fs, stream, last_kernel, last_hip);
+    return resize_inner(st, d, r.h, r.v, in, (uint8_t*)d_out, frames, in_fs, out_fs, stream, last_kernel, last_hip, tc);
 }
 
 // staging buffers of the host entry points (resize and reduce)
@@ -922,6 +774,41 @@ int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_res
     int rc = LANCZOS_OK;
     if (e == hipSuccess) {
         rc = resize_device(st, d, o, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip);
+        if (rc == LANCZOS_OK) e = hipMemcpyAsync(out, st->stage_out, out_bytes, hipMemcpyDeviceToHost, stream);
+    }
+    const hipError_t es = hipStreamSynchronize(stream);   // nothing stays in flight on the caller's buffers
+    if (rc != LANCZOS_OK) return rc;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) {
+        *last_hip = (int)e;
+        return LANCZOS_ERR_HIP;
+    }
+    return LANCZOS_OK;
+}
+
+// The table rides behind the input frames in the input staging block.  The float frames go up before they come back, so that
+// the words of `out` the strides leave out keep what they held.
+int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_tensor_out* t,
+                       const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip, int* route) {
+    if (((uintptr_t)out & 3) != 0) return LANCZOS_ERR_BAD_ARG;
+    RsTensorCall tc;
+    tc.extent_bytes = tensor_extent_bytes(d, t);
+    const size_t in_bytes = (size_t)d->in_w * d->in_h * d->channels * frames;
+    const size_t lut_at = (in_bytes + 255) & ~(size_t)255, lut_bytes = (size_t)d->channels * 256 * sizeof(float);
+    const size_t out_bytes = tc.extent_bytes * frames;
+    hipError_t e = rs_grow_stage(st, &st->stage_in, &st->stage_in_bytes, lut_at + lut_bytes, stream);
+    if (e == hipSuccess) e = rs_grow_stage(st, &st->stage_out, &st->stage_out_bytes, out_bytes, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(st->stage_in, in, in_bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync((uint8_t*)st->stage_in + lut_at, t->d_lut, lut_bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(st->stage_out, out, out_bytes, hipMemcpyHostToDevice, stream);
+    int rc = LANCZOS_OK;
+    if (e == hipSuccess) {
+        lanczos_tensor_out dev = *t;
+        dev.d_lut = (const float*)((const uint8_t*)st->stage_in + lut_at);
+        tc.t = &dev;
+        rc = resize_device(st, d, o, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip, &tc);
+        *route = tc.route;
         if (rc == LANCZOS_OK) e = hipMemcpyAsync(out, st->stage_out, out_bytes, hipMemcpyDeviceToHost, stream);
     }
     const hipError_t es = hipStreamSynchronize(stream);   // nothing stays in flight on the caller's buffers

@@ -121,6 +121,7 @@ struct ResizeState {
     };
     Block scratch;                           // intermediate of the two-pass path (the rows the vertical taps read x out_w x C)
     Block reduced;                           // the reduced frames of a request with reducing_gap, tightly packed
+    Block tensor_bytes;                      // the byte result of a tensor request on the converted route (k_rs_to_tensor reads it)
     std::vector<void*> kept;                 // scratch blocks replaced while a graph may hold them: freed at destruction
     // staging of lanczos_resize_host
     void* stage_in = nullptr;
@@ -129,10 +130,32 @@ struct ResizeState {
     ~ResizeState();
 };
 
-// The entry points (ctx->mu held, device set).  *last_kernel / *last_hip as in lanczos_ctx.
+// A tensor request (lanczos_tensor_out, lanczos_resize_tensor.hip): d_out and out_frame_stride of resize_device are then those
+// of the float frames.  route: out, LANCZOS_TENSOR_FUSED or LANCZOS_TENSOR_CONVERTED once the launches are out.
+struct RsTensorCall {
+    const lanczos_tensor_out* t = nullptr;   // validated (tensor_validate)
+    size_t extent_bytes = 0;                 // of one float frame: from its first float to its last
+    int route = 0;
+};
+int tensor_validate(const lanczos_resize_desc* d, const lanczos_tensor_out* t);
+size_t tensor_extent_bytes(const lanczos_resize_desc* d, const lanczos_tensor_out* t);
+void tensor_lut_normalize(int channels, const float* mean, const float* std, float* lut);
+// the TENSOR instances of k_rs_fused (every K bucket x C = 1, 3, 4 and alpha); `out` / `out_fs`: the float frames
+hipError_t rs_tensor_launch_fused(const lanczos_resize_desc* d, const RsFusedPlan& fp, const ResizeAxis* H, const ResizeAxis* V,
+                                  const uint8_t* in, uint8_t* out, size_t in_fs, size_t out_fs, int frames,
+                                  const RsTensorCall& tc, hipStream_t stream);
+// k_rs_to_tensor: tightly packed interleaved bytes (frames `src_fs` apart, base and stride dword multiples, readable up to the
+// next dword multiple behind each frame) -> strided floats through the table
+hipError_t rs_to_tensor_launch(const uint8_t* src, size_t src_fs, uint8_t* out, size_t out_fs, int w, int h, int channels,
+                               const lanczos_tensor_out& t, int frames, hipStream_t stream);
+
+// The entry points (ctx->mu held, device set).  *last_kernel / *last_hip as in lanczos_ctx.  tc: a tensor request (NULL: bytes)
 int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* d_in, void* d_out,
                   int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream, int* last_kernel,
-                  int* last_hip);
+                  int* last_hip, RsTensorCall* tc = nullptr);
+// host table (t->d_lut) and host buffers, float frames tensor_extent_bytes apart; synchronous
+int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_tensor_out* t,
+                       const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip, int* route);
 int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* in, void* out,
                 int frames, hipStream_t stream, int* last_kernel, int* last_hip);
 

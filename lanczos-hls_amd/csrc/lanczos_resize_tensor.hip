@@ -1,0 +1,170 @@
+// lanczos_resize_tensor.hip -- 8-bit resizes that leave as float tensors (include/lanczos_hip.h, lanczos_tensor_out;
+// DESIGN.md 4.5): out[c * cs + y * rs + x * ps] = lut[c][P(y, x, c)], P the byte lanczos_resize_device_ex stores.  The table
+// entries are moved as 32-bit words, never computed on.  Two kernels:
+//
+//   fused      the TENSOR instances of k_rs_fused (lanczos_resize_fused.hpp): the vertical pass stores the floats itself.  A
+//              tensor request runs them exactly where the byte request runs the fused kernel, on the same plan.
+//   converted  k_rs_to_tensor behind any other resize (two passes, one pass, nearest, the plain copy, a float frame of 2^31
+//              bytes or more): the bytes go to context scratch, tightly packed, and one streaming launch turns them into floats.
+//
+// The validation of a request and the table of ToTensor + Normalize are here as well.
+#include "lanczos_resize_fused.hpp"
+
+#include <algorithm>
+
+namespace lz {
+
+// ---- host: validation, the normalisation table --------------------------------------------------------------------
+
+size_t tensor_extent_bytes(const lanczos_resize_desc* d, const lanczos_tensor_out* t) {
+    return (size_t)((d->channels - 1) * t->chan_stride + (d->out_h - 1) * t->row_stride + (d->out_w - 1) * t->pix_stride + 1) *
+           sizeof(float);
+}
+
+int tensor_validate(const lanczos_resize_desc* d, const lanczos_tensor_out* t) {
+    const int rc = resize_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    if (!t || !t->d_lut) return LANCZOS_ERR_BAD_ARG;
+    for (int32_t r : t->reserved)
+        if (r != 0) return LANCZOS_ERR_BAD_ARG;
+    // a table per 16-bit value and float inputs are out of scope
+    if (d->reserved[0] & (LANCZOS_RESIZE_U16 | LANCZOS_RESIZE_F32)) return LANCZOS_ERR_UNSUPPORTED;
+    struct Dim {
+        int64_t stride, extent;
+    } dims[3] = {{t->chan_stride, d->channels}, {t->row_stride, d->out_h}, {t->pix_stride, d->out_w}};
+    constexpr int64_t kMaxStride = (int64_t)1 << 40;   // stride x extent stays far inside int64
+    for (const Dim& m : dims)
+        if (m.stride <= 0 || m.stride > kMaxStride) return LANCZOS_ERR_BAD_ARG;
+    // no two (c, y, x) share an address: by rising stride, each stride covers the whole extent of the one before.  An axis of
+    // extent 1 never moves, so its stride takes no part
+    std::sort(dims, dims + 3, [](const Dim& a, const Dim& b) { return a.stride < b.stride; });
+    int64_t covered = 1;   // floats the axes so far span
+    for (const Dim& m : dims) {
+        if (m.extent == 1) continue;
+        if (m.stride < covered) return LANCZOS_ERR_BAD_ARG;
+        covered = m.stride * m.extent;
+    }
+    return LANCZOS_OK;
+}
+
+// ToTensor() then Normalize(mean, std), operation for operation in float: this translation unit is built with
+// -ffp-contract=off, and the divisions are IEEE divisions (no reciprocal)
+void tensor_lut_normalize(int channels, const float* mean, const float* std, float* lut) {
+    for (int c = 0; c < channels; c++) {
+        const float m = mean ? mean[c] : 0.0f, s = std ? std[c] : 1.0f;
+        for (int v = 0; v < 256; v++) lut[c * 256 + v] = ((float)v / 255.0f - m) / s;
+    }
+}
+
+// ---- kernels --------------------------------------------------------------------------------------------------------
+
+struct RsToTensor {
+    const uint8_t* src;
+    uint8_t* out;
+    unsigned long long src_fs, out_fs;   // frame strides (bytes)
+    unsigned long long frame_bytes;      // samples of one frame
+    unsigned pitch;                      // samples of one row
+    const uint32_t* lut;
+    long long cs, rs, ps;
+};
+
+constexpr int kToTensorBlock = 4 * kRsThreads;   // samples per workgroup: one dword load per thread
+
+// A thread loads one dword of the frame (coalesced, rows tightly packed, so the frame is one run of bytes) and the wave
+// exchanges its 64 dwords as the fused epilogue does: in round r lane i stores sample 64 r + i of the wave's 256.  Addresses
+// are 64-bit; the row of the workgroup's first sample costs one division per thread, a 64-bit one only for frames of 4 GiB.
+template <int C>
+__global__ __launch_bounds__(kRsThreads) void k_rs_to_tensor(RsToTensor g) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long base = (unsigned long long)blockIdx.x * kToTensorBlock;
+    const uint8_t* fsrc = g.src + blockIdx.y * g.src_fs;
+    const unsigned long long mine = base + 4ull * tid;
+    const uint32_t dw = mine < g.frame_bytes ? *(const uint32_t*)(fsrc + mine) : 0u;
+    unsigned long long y0;
+    unsigned rem0;
+    if (g.frame_bytes <= 0xffffffffull) {
+        const unsigned q = (unsigned)base / g.pitch;
+        y0 = q, rem0 = (unsigned)base - q * g.pitch;
+    } else {
+        y0 = base / g.pitch, rem0 = (unsigned)(base - y0 * g.pitch);
+    }
+    uint32_t* fout = (uint32_t*)(g.out + blockIdx.y * g.out_fs);
+#pragma unroll
+    for (int rr = 0; rr < 4; rr++) {
+        const uint32_t w = (uint32_t)__shfl((int)dw, 16 * rr + (lane >> 2), 64);
+        const unsigned local = (unsigned)(wave * 256 + 64 * rr + lane);
+        if (base + local < g.frame_bytes) {
+            unsigned rem = rem0 + local;   // pitch and the block are below 2^19 samples
+            const unsigned dy = rem / g.pitch;
+            rem -= dy * g.pitch;
+            const unsigned x = rem / C, c = rem - x * C;
+            const uint32_t v = g.lut[c * 256 + ((w >> (8 * (lane & 3))) & 255u)];
+            fout[(long long)c * g.cs + (long long)(y0 + dy) * g.rs + (long long)x * g.ps] = v;
+        }
+    }
+}
+
+hipError_t rs_to_tensor_launch(const uint8_t* src, size_t src_fs, uint8_t* out, size_t out_fs, int w, int h, int channels,
+                               const lanczos_tensor_out& t, int frames, hipStream_t stream) {
+    RsToTensor g{};
+    g.src_fs = src_fs, g.out_fs = out_fs;
+    g.frame_bytes = (unsigned long long)w * h * channels;
+    g.pitch = (unsigned)(w * channels);
+    g.lut = (const uint32_t*)t.d_lut;
+    g.cs = t.chan_stride, g.rs = t.row_stride, g.ps = t.pix_stride;
+    const unsigned blocks = (unsigned)((g.frame_bytes + kToTensorBlock - 1) / kToTensorBlock);   // at most 2^24
+    for (int f0 = 0; f0 < frames; f0 += 65535) {
+        const int nf = std::min(65535, frames - f0);
+        g.src = src + (size_t)f0 * src_fs;
+        g.out = out + (size_t)f0 * out_fs;
+        const dim3 grid(blocks, nf);
+        if (channels == 1) hipLaunchKernelGGL(k_rs_to_tensor<1>, grid, dim3(kRsThreads), 0, stream, g);
+        else if (channels == 3) hipLaunchKernelGGL(k_rs_to_tensor<3>, grid, dim3(kRsThreads), 0, stream, g);
+        else hipLaunchKernelGGL(k_rs_to_tensor<4>, grid, dim3(kRsThreads), 0, stream, g);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+hipError_t rs_tensor_launch_fused(const lanczos_resize_desc* d, const RsFusedPlan& fp, const ResizeAxis* H, const ResizeAxis* V,
+                                  const uint8_t* in, uint8_t* out, size_t in_fs, size_t out_fs, int frames,
+                                  const RsTensorCall& tc, hipStream_t stream) {
+    const bool alpha = (d->reserved[0] & LANCZOS_RESIZE_ALPHA) != 0;
+    RsFusedTensor g{};
+    g.in_pitch = d->in_w * d->channels;
+    g.out_pitch = d->out_w * d->channels;
+    g.in_h = d->in_h, g.out_w = d->out_w, g.out_h = d->out_h;
+    g.in_fs = in_fs, g.out_fs = out_fs;
+    g.hf = H->first(), g.hc = H->count(), g.hk = H->coeffs(), g.hks = H->host.ksize;
+    g.vf = V->first(), g.vc = V->count(), g.vk = V->coeffs(), g.vks = V->host.ksize;
+    g.strips = fp.strips, g.rows_per_chunk = fp.rows_per_chunk;
+    g.ring_rows = fp.ring_rows, g.stage_rows = fp.stage_rows, g.stage_dw = fp.stage_dw;
+    g.lut = (const uint32_t*)tc.t->d_lut;
+    g.cs = (int)tc.t->chan_stride, g.rs = (int)tc.t->row_stride, g.ps = (int)tc.t->pix_stride;   // extent below 2^31 bytes
+    g.extent_bytes = (unsigned)tc.extent_bytes;
+    for (int f0 = 0; f0 < frames; f0 += 65535) {
+        const int nf = std::min(65535, frames - f0);
+        g.in = in + (size_t)f0 * in_fs;
+        g.out = out + (size_t)f0 * out_fs;
+        const dim3 grid(fp.strips * fp.chunks, nf);
+        bool launched = false;
+#define X(KB)                                                                                                                  \
+    if (!launched && fp.K == KB) {                                                                                             \
+        if (d->channels == 1) hipLaunchKernelGGL((k_rs_fused<1, KB, false, true>), grid, dim3(kRsThreads), fp.lds, stream, g); \
+        else if (d->channels == 3)                                                                                             \
+            hipLaunchKernelGGL((k_rs_fused<3, KB, false, true>), grid, dim3(kRsThreads), fp.lds, stream, g);                   \
+        else if (alpha) hipLaunchKernelGGL((k_rs_fused<4, KB, true, true>), grid, dim3(kRsThreads), fp.lds, stream, g);        \
+        else hipLaunchKernelGGL((k_rs_fused<4, KB, false, true>), grid, dim3(kRsThreads), fp.lds, stream, g);                  \
+        launched = true;                                                                                                       \
+    }
+        LZ_RS_BUCKETS(X)
+#undef X
+        if (!launched) return hipErrorInvalidValue;
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace lz

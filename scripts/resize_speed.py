@@ -2,7 +2,7 @@
 """resize_speed.py -- speed of the resize-to-any-size entry (lanczos_resize_device) on one MI355X.
 
     python scripts/resize_speed.py [--steps K] [--warmup W] [--rounds R] [--only W1,W3,A1,U1,F1] [--routes rgbx,three_step]
-                                   [--pillow]
+                                   [--pillow] [--parent-lib PATH]
 
 One JSON line per (workload, path).  Discipline as bench.py's: the frames are resident in HBM and the steps cycle through
 enough input / output sets that the inputs of one cycle exceed twice the 256 MiB Infinity Cache (no step finds its input
@@ -45,6 +45,17 @@ B1 / B2 are a fractional 1280x720-ish box out of 7680x4320 (8 frames) to 1920x10
 the crop region padded by the support (its box is the boxed one shifted by whole pixels; a float rounds the two
 differently, so the bytes are compared between the paths of each, not between boxed and tight).  R5, B1 and B2 run on
 request (--only R5,B1,B2); they need a build with lanczos_resize_device_ex.
+
+T1, T2, T4 and TP are tensor workloads (lanczos_resize_tensor_device: 8-bit frames resized straight into normalised float
+tensors; --only T1,T2,T4,TP; a build with the entry): T1 is W1's shape to CHW, T2 the same to HWC, T4 W4's shape to CHW, TP a
+preprocessing shape, 256 frames of 500x375 -> 224x224 from a centred 375x375 box, to CHW.  Routes, alternating region by region:
+  fused         the tensor call under RESIZE_AUTO: the fused kernel stores the floats
+  converted     the same call under RESIZE_CONVERT: the same byte resize into context scratch, then k_rs_to_tensor
+  bytes_torch   the byte resize, then uint8 -> .permute().float().div(255).sub(mean).div(std) with torch on the same stream
+  bytes         the byte resize alone
+  parent_bytes  the byte resize alone on another build of the library (--parent-lib PATH: the parent commit's)
+  copy          a device-to-device copy of one step's float output: the floor of what the extra bytes cost
+Frame 0 of fused and converted are compared bit for bit before timing; a last line gives the ratios.
 
 --pillow adds Pillow's single-core time of one frame of each workload (if Pillow imports; else "not available"); for U1 and
 U4 that is the time of one I;16 plane (a frame has three), for F1 and F4 that of one F plane.
@@ -298,6 +309,110 @@ def run_routes(name, shape, f, routes, in_bytes, out_bytes, args, ctx, torch, ch
                 "compulsory_bytes": in_bytes[rn] + out_bytes[rn], "steps": args.steps, "rounds": args.rounds,
                 "lib": os.path.basename(L.LIB_PATH), "measured": True}
         print(json.dumps(line), flush=True)
+    return {rn: statistics.median(times[rn]) for rn in routes}
+
+
+TENSOR_WORKLOADS = {   # name: (in_w, in_h, out_w, out_h, channels, frames, layout, box)
+    "T1": (3840, 2160, 1920, 1080, 3, 32, "chw", None),
+    "T2": (3840, 2160, 1920, 1080, 3, 32, "hwc", None),
+    "T4": (1920, 1080, 3840, 2160, 3, 32, "chw", None),
+    "TP": (500, 375, 224, 224, 3, 256, "chw", (62.5, 0.0, 437.5, 375.0)),
+}
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
+
+
+class ParentLib:
+    """The byte resize of another build of the C ABI (the parent commit's), loaded beside this one."""
+
+    def __init__(self, path):
+        import ctypes
+        self.lib = ctypes.CDLL(path)
+        self.h = ctypes.c_void_p()
+        self.lib.lanczos_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int]
+        self.lib.lanczos_resize_device_ex.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t,
+                                                      ctypes.c_void_p]
+        self.lib.lanczos_destroy.argtypes = [ctypes.c_void_p]
+        if self.lib.lanczos_create(ctypes.byref(self.h), 0) != 0:
+            raise SystemExit(f"{path}: lanczos_create failed")
+        self.byref = ctypes.byref
+
+    def resize_device(self, d, d_in, d_out, frames, stream, opts=None):
+        rc = self.lib.lanczos_resize_device_ex(self.h, self.byref(d), self.byref(opts) if opts is not None else None, d_in,
+                                               d_out, frames, 0, 0, stream)
+        if rc != 0:
+            raise SystemExit(f"parent lanczos_resize_device_ex: {rc}")
+
+    def close(self):
+        self.lib.lanczos_destroy(self.h)
+
+
+def run_tensor(name, args, ctx, torch, parent):
+    iw, ih, ow, oh, c, f, layout, box = TENSOR_WORKLOADS[name]
+    in_fb, out_fb = iw * ih * c, ow * oh * c
+    sets = max(2, -(-2 * 256 * 2 ** 20 // (f * in_fb)) + 1)
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    xs = [torch.randint(0, 256, (f * in_fb,), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(sets)]
+    ys = [torch.empty(f * out_fb, dtype=torch.float32, device="cuda") for _ in range(sets)]
+    tmp = torch.empty(f * out_fb, dtype=torch.uint8, device="cuda")
+    d = L.resize_desc(iw, ih, ow, oh, c)
+    opts = L.resize_opts(d, box=box) if box else None
+    lut = torch.from_numpy(L.normalize_lut(c, IMAGENET_MEAN, IMAGENET_STD)).cuda()
+    st = L.tensor_strides(layout, ow, oh, c)
+    shape = (1, c, 1, 1) if layout == "chw" else (1, 1, 1, c)
+    mean = torch.tensor(IMAGENET_MEAN, device="cuda").view(shape)
+    std = torch.tensor(IMAGENET_STD, device="cuda").view(shape)
+    s = torch.cuda.current_stream().cuda_stream
+    seen = {}
+
+    def tensor(path):
+        def step(i):
+            ctx.resize_force(path)
+            ctx.resize_tensor_device(d, xs[i % sets].data_ptr(), ys[i % sets].data_ptr(), f, lut.data_ptr(), st, stream=s,
+                                     opts=opts)
+            seen[path] = ctx.last_tensor_route()
+            return ys[i % sets][:out_fb].view(torch.int32)
+        return step
+
+    def bytes_(i):
+        ctx.resize_force(L.RESIZE_AUTO)
+        ctx.resize_device(d, xs[i % sets].data_ptr(), tmp.data_ptr(), f, 0, 0, s, opts=opts)
+        return tmp[:out_fb]
+
+    def bytes_torch(i):
+        bytes_(i)
+        t = tmp.view(f, oh, ow, c)
+        t = t.permute(0, 3, 1, 2) if layout == "chw" else t
+        return t.float().div(255).sub(mean).div(std).contiguous().view(-1)[:out_fb].view(torch.int32)
+
+    def parent_bytes(i):
+        parent.resize_device(d, xs[i % sets].data_ptr(), tmp.data_ptr(), f, s, opts)
+        return tmp[:out_fb]
+
+    def copy(i):
+        ys[(i + 1) % sets].copy_(ys[i % sets], non_blocking=True)
+        return ys[(i + 1) % sets][:out_fb].view(torch.int32)
+
+    routes = {"fused": tensor(L.RESIZE_AUTO), "converted": tensor(L.RESIZE_CONVERT), "bytes_torch": bytes_torch, "bytes": bytes_}
+    if parent is not None:
+        routes["parent_bytes"] = parent_bytes
+    routes["copy"] = copy
+    inb = {rn: f * in_fb for rn in routes}
+    outb = {rn: 4 * f * out_fb for rn in routes}
+    outb["bytes"] = outb["parent_bytes"] = f * out_fb
+    inb["copy"] = 4 * f * out_fb
+    us = run_routes(name, f"{iw}x{ih}->{ow}x{oh} C{c} {layout}" + (f" box {box}" if box else ""), f, routes, inb, outb, args,
+                    ctx, torch, check=(("fused", "converted"),))
+    ctx.resize_force(L.RESIZE_AUTO)
+    if (seen[L.RESIZE_AUTO], seen[L.RESIZE_CONVERT]) != (L.TENSOR_FUSED, L.TENSOR_CONVERTED):
+        raise SystemExit(f"{name}: routes {seen}")
+    base = us.get("parent_bytes", us["bytes"])
+    print(json.dumps({"workload": name, "fused_over_converted": round(us["fused"] / us["converted"], 3),
+                      "fused_over_bytes_torch": round(us["fused"] / us["bytes_torch"], 3),
+                      "fused_minus_byte_resize_us": round(us["fused"] - base, 2), "byte_resize": "parent" if parent else "this build",
+                      "copy_of_float_output_us": round(us["copy"], 2), "measured": True}), flush=True)
+    del xs, ys, tmp
+    torch.cuda.empty_cache()
 
 
 def run_gap(name, args, ctx, torch):
@@ -384,13 +499,17 @@ def main():
     ap.add_argument("--only", default="W1,W2,W3,W4,W5,A1,A4,U1,U4")
     ap.add_argument("--routes", default=",".join(ROUTES))
     ap.add_argument("--pillow", action="store_true")
+    ap.add_argument("--parent-lib", default=None, help="another build of liblanczos_hip.so for the parent_bytes route of T*")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("resize_speed.py needs a GPU")
     ctx = L.Context(0)
+    parent = ParentLib(args.parent_lib) if args.parent_lib else None
     for name in args.only.split(","):
-        if name == "R5":
+        if name in TENSOR_WORKLOADS:
+            run_tensor(name, args, ctx, torch, parent)
+        elif name == "R5":
             run_gap(name, args, ctx, torch)
         elif name in ("B1", "B2"):
             run_box(name, (1920, 1080) if name == "B1" else (640, 360), args, ctx, torch)
@@ -404,6 +523,8 @@ def main():
             run(name, WORKLOADS[FILTER_WORKLOADS[name][0]], args, ctx, torch, filt=FILTER_WORKLOADS[name][1])
         else:
             run(name, WORKLOADS[name], args, ctx, torch)
+    if parent is not None:
+        parent.close()
     ctx.close()
 
 
