@@ -1,32 +1,30 @@
-// lanczos_resize.hip -- resize to any size, downscaling included, with Pillow's Lanczos contract (include/lanczos_hip.h,
-// lanczos_resize_*).  Host tap tables in 22-bit fixed point, their per-context cache, and two kernel paths:
+// lanczos_resize.hip -- resize to any size, downscaling included, with Pillow's contract (include/lanczos_hip.h,
+// lanczos_resize_*).  Host tap tables, their per-context cache, planning, dispatch and the host entry points.
+// The kernels are templates over the sample width (RsSample<BPS>, lanczos_resize_fused.hpp); there are two paths:
 //
 //   fused     k_rs_fused: a workgroup owns a strip of output columns (all channels) of one frame and a chunk of its output
 //             rows.  It marches down the rows in blocks of kRsOB: the input rows the block's vertical taps need are staged
-//             in LDS (buffer loads, range-checked zero fill), the horizontal pass turns them into clipped u8 rows of an LDS
-//             ring, and the vertical pass reads the ring and stores the block's output rows.  Horizontal coefficients stay in
-//             registers for the whole march (a thread keeps one output column); vertical ones are workgroup-uniform scalar
-//             loads.
-//   two-pass  k_rs_h writes the u8 intermediate (the rows the vertical taps read x out_w x C per frame) to context scratch,
-//             k_rs_v reads it: any tap count.  It also serves a resize that changes one axis only (one kernel) -- as Pillow, a pass whose axis keeps
-//             its size is skipped.
+//             in LDS (buffer loads, range-checked zero fill), the horizontal pass turns them into rows of an LDS ring, stored
+//             as Pillow stores its intermediate, and the vertical pass reads the ring and stores the block's output rows.
+//             Horizontal coefficients stay in registers for the whole march (a thread keeps one output column); vertical
+//             ones are workgroup-uniform scalar loads.  This file compiles the 8-bit instances that store bytes.
+//   two-pass  k_rs_pass_h writes the intermediate (the rows the vertical taps read x out_w x C per frame) to context
+//             scratch, k_rs_pass_v reads it: any tap count, every sample width, all compiled here.  It also serves a resize
+//             that changes one axis only (one kernel) -- as Pillow, a pass whose axis keeps its size is skipped.
 //
 // LANCZOS_RESIZE_ALPHA (four channels, Pillow's RGBA mode): both paths premultiply the colour samples by alpha where they
-// read the frame and divide alpha out where they write it (lanczos_alpha.hpp), k_rs_fused<4, K, true> and k_rs_h_alpha /
-// k_rs_v_alpha; tables, plan and scratch are those of the same request without the flag.
+// read the frame and divide alpha out where they write it (lanczos_alpha.hpp), the ALPHA instances of k_rs_fused and
+// k_rs_h_alpha / k_rs_v_alpha; tables, plan and scratch are those of the same request without the flag.
 //
-// LANCZOS_RESIZE_U16 (16-bit samples, Pillow's I;16): the same tap geometry with double coefficients and Pillow's double
-// accumulation; tables, cache, planning and dispatch are here, the kernels in lanczos_resize16.hip.
-//
-// LANCZOS_RESIZE_F32 (float samples, Pillow's mode F): the double tables and cache entries of the 16-bit path, a float
-// intermediate and no clamp; the kernels are in lanczos_resize32.hip.
+// LANCZOS_RESIZE_U16 (16-bit samples, Pillow's I;16) and LANCZOS_RESIZE_F32 (float samples, Pillow's mode F): the same tap
+// geometry with double coefficients (one set of tables and cache entries for both) and Pillow's double accumulation; a u16 or
+// float intermediate.  Their fused instances are compiled by lanczos_resize16.hip and lanczos_resize32.hip.
 //
 // A source box (lanczos_resize_opts) only changes the tables: an axis is built over a span of the source given as two floats,
 // `first` still indexes the whole axis, and the kernels are the ones above.  reducing_gap puts lanczos_reduce.hip in front:
 // reduce into context scratch, then the resize of the reduced frames with the box that remains (resize_resolve).
 //
-// Arithmetic is Pillow's and exact by construction: acc = 2^21 + sum(sample * coeff) in int32 with 24-bit multiplies
-// (|coeff| < 2^23 and 255 * sum|coeff| + 2^21 < 2^31, checked when a table is built), result clamp(acc >> 22, 0, 255).
+// The arithmetic is Pillow's and exact by construction; RsSample<BPS> says how for each width.
 #include "lanczos_resize.hpp"
 
 #include "lanczos_alpha.hpp"
@@ -235,45 +233,6 @@ constexpr int kRsFusedMaxLds = 80 * 1024;   // at least two fused workgroups per
 constexpr int kRsRowsPerChunkMin = 4 * kRsOB;
 constexpr int kRsTargetWgs = 2048;
 
-// one pass of the two-pass path: `n_cols` samples per output row, `rows` output rows, frames in blockIdx.z
-struct RsPass {
-    const uint8_t* src;
-    uint8_t* dst;
-    unsigned long long src_fs, dst_fs;   // frame strides (bytes)
-    unsigned long long src_pitch, dst_pitch;
-    int n_cols, channels;
-    const int32_t *first, *count, *coeffs;
-    int ksize;
-};
-
-// horizontal: output sample x = o * C + c of row blockIdx.y
-__global__ __launch_bounds__(kRsThreads) void k_rs_h(RsPass p) {
-    const int x = blockIdx.x * kRsThreads + threadIdx.x;
-    if (x >= p.n_cols) return;
-    const int o = x / p.channels, c = x - o * p.channels;
-    const uint8_t* src = p.src + blockIdx.z * p.src_fs + blockIdx.y * p.src_pitch + c;
-    const int f = p.first[o], n = p.count[o];
-    const int32_t* k = p.coeffs + (size_t)o * p.ksize;
-    int acc = 1 << (kResizePrecision - 1);
-#pragma unroll 8
-    for (int i = 0; i < n; i++) acc = rs_mad(src[(size_t)(f + i) * p.channels], k[i], acc);
-    p.dst[blockIdx.z * p.dst_fs + blockIdx.y * p.dst_pitch + x] = (uint8_t)rs_clip8(acc);
-}
-
-// vertical: output row o = blockIdx.y, sample column x (coefficients uniform over the workgroup)
-__global__ __launch_bounds__(kRsThreads) void k_rs_v(RsPass p) {
-    const int x = blockIdx.x * kRsThreads + threadIdx.x;
-    if (x >= p.n_cols) return;
-    const int o = blockIdx.y;
-    const int f = p.first[o], n = p.count[o];
-    const int32_t* k = p.coeffs + (size_t)o * p.ksize;
-    const uint8_t* src = p.src + blockIdx.z * p.src_fs + (size_t)f * p.src_pitch + x;
-    int acc = 1 << (kResizePrecision - 1);
-#pragma unroll 8
-    for (int i = 0; i < n; i++) acc = rs_mad(src[(size_t)i * p.src_pitch], k[i], acc);
-    p.dst[blockIdx.z * p.dst_fs + o * p.dst_pitch + x] = (uint8_t)rs_clip8(acc);
-}
-
 // LANCZOS_RESIZE_ALPHA on the two-pass path: one thread per four-channel pixel, so that a colour sample has its alpha next
 // to it.  The horizontal kernel premultiplies what it reads; with UN (no vertical pass follows) it also divides alpha out
 // of what it writes, otherwise the intermediate holds premultiplied pixels.  The vertical kernel divides alpha out of what
@@ -287,14 +246,15 @@ __device__ __forceinline__ void rs_store_px(uint8_t* p, uint32_t v) {
 }
 __device__ __forceinline__ void rs_mad_px(uint32_t px, int k, int (&acc)[4]) {
 #pragma unroll
-    for (int b = 0; b < 4; b++) acc[b] = rs_mad((int)((px >> (8 * b)) & 255u), k, acc[b]);
+    for (int b = 0; b < 4; b++) acc[b] = RsSample<1>::mad(RsSample<1>::get(px, b), k, acc[b]);
 }
 __device__ __forceinline__ uint32_t rs_clip_px(const int (&acc)[4]) {
-    return rs_clip8(acc[0]) | (rs_clip8(acc[1]) << 8) | (rs_clip8(acc[2]) << 16) | (rs_clip8(acc[3]) << 24);
+    using S = RsSample<1>;
+    return S::store(acc[0]) | (S::store(acc[1]) << 8) | (S::store(acc[2]) << 16) | (S::store(acc[3]) << 24);
 }
 
 template <bool UN>
-__global__ __launch_bounds__(kRsThreads) void k_rs_h_alpha(RsPass p) {
+__global__ __launch_bounds__(kRsThreads) void k_rs_h_alpha(RsPass<int32_t> p) {
     const int o = blockIdx.x * kRsThreads + threadIdx.x;   // output pixel of row blockIdx.y (n_cols counts samples)
     if (o * 4 >= p.n_cols) return;
     const int f = p.first[o], n = p.count[o];
@@ -309,7 +269,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_h_alpha(RsPass p) {
 }
 
 template <bool PRE>
-__global__ __launch_bounds__(kRsThreads) void k_rs_v_alpha(RsPass p) {
+__global__ __launch_bounds__(kRsThreads) void k_rs_v_alpha(RsPass<int32_t> p) {
     const int x = blockIdx.x * kRsThreads + threadIdx.x;   // pixel column
     if (x * 4 >= p.n_cols) return;
     const int o = blockIdx.y;
@@ -326,8 +286,11 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_v_alpha(RsPass p) {
     rs_store_px(p.dst + blockIdx.z * p.dst_fs + o * p.dst_pitch + (size_t)x * 4, rs_unpremul_px(rs_clip_px(acc)));
 }
 
-// k_rs_fused, its launch arguments and its tap-count buckets (LZ_RS_BUCKETS): lanczos_resize_fused.hpp
+// the 8-bit instances of k_rs_fused that store bytes
+template hipError_t rs_launch_fused<1, false>(const RsFusedLaunch&);
 
+// the tap count of the smallest fused instance that holds ksize (0: none; small: the instances with 3 and 5 taps count, which
+// they do for every filter but Lanczos)
 static int rs_bucket(int ksize, bool small) {
     int k = 0;
     if ((!small || env().rs_no_small_buckets) && ksize < 7) ksize = 7;
@@ -457,7 +420,7 @@ bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H, const 
     if ((long long)d->in_w * d->in_h * C + 4 >= (1ll << 31)) return false;   // 32-bit buffer offsets
     if ((long long)d->out_w * d->out_h * C >= (1ll << 31)) return false;
     const bool small = resize_filter(d) != LANCZOS_FILTER_LANCZOS;   // the instances with 3 and 5 taps
-    fp->K = bps > 1 ? rs16_bucket(H.ksize, small) : rs_bucket(H.ksize, small);
+    fp->K = rs_bucket(H.ksize, small);
     if (!fp->K) return false;
     const int SW = rs_strip_width(d->channels, bps);
     const int NE = (fp->K * C + 3) / 4;
@@ -520,62 +483,36 @@ int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o,
     return LANCZOS_OK;
 }
 
-static hipError_t rs_launch_fused(const lanczos_resize_desc* d, const RsFusedPlan& fp, const ResizeAxis* H,
-                                  const ResizeAxis* V, const uint8_t* in, uint8_t* out, size_t in_fs, size_t out_fs, int frames,
-                                  hipStream_t stream) {
-    const bool alpha = (d->reserved[0] & LANCZOS_RESIZE_ALPHA) != 0;
-    RsFused g{};
-    g.in_pitch = d->in_w * d->channels;
-    g.out_pitch = d->out_w * d->channels;
-    g.in_h = d->in_h, g.out_w = d->out_w, g.out_h = d->out_h;
-    g.in_fs = in_fs, g.out_fs = out_fs;
-    g.hf = H->first(), g.hc = H->count(), g.hk = H->coeffs(), g.hks = H->host.ksize;
-    g.vf = V->first(), g.vc = V->count(), g.vk = V->coeffs(), g.vks = V->host.ksize;
-    g.strips = fp.strips, g.rows_per_chunk = fp.rows_per_chunk;
-    g.ring_rows = fp.ring_rows, g.stage_rows = fp.stage_rows, g.stage_dw = fp.stage_dw;
-    for (int f0 = 0; f0 < frames; f0 += 65535) {
-        const int nf = std::min(65535, frames - f0);
-        g.in = in + (size_t)f0 * in_fs;
-        g.out = out + (size_t)f0 * out_fs;
-        const dim3 grid(fp.strips * fp.chunks, nf);
-        bool launched = false;
-#define X(KB)                                                                                                         \
-    if (!launched && fp.K == KB) {                                                                                    \
-        if (d->channels == 1) hipLaunchKernelGGL((k_rs_fused<1, KB>), grid, dim3(kRsThreads), fp.lds, stream, g);     \
-        else if (d->channels == 3) hipLaunchKernelGGL((k_rs_fused<3, KB>), grid, dim3(kRsThreads), fp.lds, stream, g); \
-        else if (alpha) hipLaunchKernelGGL((k_rs_fused<4, KB, true>), grid, dim3(kRsThreads), fp.lds, stream, g);     \
-        else hipLaunchKernelGGL((k_rs_fused<4, KB>), grid, dim3(kRsThreads), fp.lds, stream, g);                      \
-        launched = true;                                                                                              \
-    }
-        LZ_RS_BUCKETS(X)
-#undef X
-        if (!launched) return hipErrorInvalidValue;
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-// alpha: the LANCZOS_RESIZE_ALPHA kernels (a thread per pixel); `only`: the other pass does not run
-static hipError_t rs_launch_pass(bool horizontal, const RsPass& p0, int rows, int frames, hipStream_t stream,
-                                 bool alpha = false, bool only = false) {
-    RsPass p = p0;
-    for (int f0 = 0; f0 < frames; f0 += 65535) {
-        const int nf = std::min(65535, frames - f0);
-        p.src = p0.src + (size_t)f0 * p0.src_fs;
-        p.dst = p0.dst + (size_t)f0 * p0.dst_fs;
-        const int n_threads = alpha ? p.n_cols / 4 : p.n_cols;
-        const dim3 grid((n_threads + kRsThreads - 1) / kRsThreads, rows, nf);
-        if (alpha && horizontal && only) hipLaunchKernelGGL(k_rs_h_alpha<true>, grid, dim3(kRsThreads), 0, stream, p);
-        else if (alpha && horizontal) hipLaunchKernelGGL(k_rs_h_alpha<false>, grid, dim3(kRsThreads), 0, stream, p);
-        else if (alpha && only) hipLaunchKernelGGL(k_rs_v_alpha<true>, grid, dim3(kRsThreads), 0, stream, p);
-        else if (alpha) hipLaunchKernelGGL(k_rs_v_alpha<false>, grid, dim3(kRsThreads), 0, stream, p);
-        else if (horizontal) hipLaunchKernelGGL(k_rs_h, grid, dim3(kRsThreads), 0, stream, p);
-        else hipLaunchKernelGGL(k_rs_v, grid, dim3(kRsThreads), 0, stream, p);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+// One pass of the two-pass path over `rows` rows of `n_cols` samples of `bps` bytes; src / dst row pitches in samples, frame
+// strides in bytes.  alpha: the LANCZOS_RESIZE_ALPHA kernels (8-bit, a thread per pixel); `only`: the other pass does not run
+static hipError_t rs_launch_pass(int bps, bool horizontal, const ResizeAxis* ax, int channels, const uint8_t* src, size_t src_fs,
+                                 size_t src_pitch, uint8_t* dst, size_t dst_fs, size_t dst_pitch, int n_cols, int rows, int frames,
+                                 hipStream_t stream, bool alpha, bool only) {
+    if (alpha && bps != 1) return hipErrorInvalidValue;
+    auto run = [&](auto sample) {
+        using S = decltype(sample);
+        RsPass<typename S::coeff_t> p{};
+        p.src_fs = src_fs, p.dst_fs = dst_fs, p.src_pitch = src_pitch, p.dst_pitch = dst_pitch;
+        p.n_cols = n_cols, p.channels = channels;
+        p.first = ax->first(), p.count = ax->count(), p.coeffs = ax->coeffs<typename S::coeff_t>(), p.ksize = ax->host.ksize;
+        void (*kern)(RsPass<typename S::coeff_t>) = horizontal ? k_rs_pass_h<S> : k_rs_pass_v<S>;
+        if constexpr (S::BPS == 1) {   // alpha is 8-bit only (checked above)
+            if (alpha && horizontal) kern = only ? k_rs_h_alpha<true> : k_rs_h_alpha<false>;
+            else if (alpha) kern = only ? k_rs_v_alpha<true> : k_rs_v_alpha<false>;
+        }
+        for (int f0 = 0; f0 < frames; f0 += 65535) {
+            const int nf = std::min(65535, frames - f0);
+            p.src = src + (size_t)f0 * src_fs;
+            p.dst = dst + (size_t)f0 * dst_fs;
+            const int n_threads = alpha ? n_cols / 4 : n_cols;
+            const dim3 grid((n_threads + kRsThreads - 1) / kRsThreads, rows, nf);
+            hipLaunchKernelGGL(kern, grid, dim3(kRsThreads), 0, stream, p);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    };
+    return bps == 4 ? run(RsSample<4>()) : bps == 2 ? run(RsSample<2>()) : run(RsSample<1>());
 }
 
 // the resize that remains once the options are resolved: `d` describes the frames at `in` (the caller's, or the reduced
@@ -588,7 +525,7 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     const int C = d->channels;
     const size_t B = (size_t)resize_bps(d);   // bytes per sample
     const bool f32 = B == 4;
-    const bool u16 = B > 1;   // samples wider than a byte: the double tables and the kernels of their own translation units
+    const bool u16 = B > 1;   // samples wider than a byte: the double tables
     const size_t in_frame = (size_t)d->in_w * d->in_h * C * B;
     const bool capturing = stream_capturing(stream);
     const bool need_h = rs_axis_runs(d->in_w, d->out_w, sh), need_v = rs_axis_runs(d->in_h, d->out_h, sv);
@@ -631,10 +568,11 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     const size_t in_pitch = (size_t)d->in_w * C * B;
     hipError_t e = hipSuccess;
     if (fused) {
-        e = t_fused ? rs_tensor_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, *tc, stream)
-            : f32   ? rs32_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream)
-            : u16   ? rs16_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream)
-                    : rs_launch_fused(d, fp, H, V, in, out, in_fs, out_fs, frames, stream);
+        const RsFusedLaunch c{d, &fp, H, V, in, out, in_fs, out_fs, frames, tc, stream};
+        e = t_fused ? rs_launch_fused<1, true>(c)
+            : f32   ? rs_launch_fused<4, false>(c)
+            : u16   ? rs_launch_fused<2, false>(c)
+                    : rs_launch_fused<1, false>(c);
         *last_kernel = LANCZOS_KERNEL_RESIZE_FUSED;
     } else if (nearest) {
         e = rs_nearest_launch(in, out, d->in_w, d->out_w, d->out_h, C, (int)B, H->first(), V->first(), frames, in_fs, out_fs,
@@ -643,8 +581,8 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     } else if (!need_h && !need_v) {   // Pillow returns a copy (also of RGBA: no premultiply round trip)
         e = hipMemcpy2DAsync(out, out_fs, in, in_fs, in_frame, frames, hipMemcpyDeviceToDevice, stream);
         *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
-    } else if (u16) {
-        const auto launch_pass = f32 ? rs32_launch_pass : rs16_launch_pass;
+    } else {
+        const int in_cols = d->in_w * C, out_cols = d->out_w * C;   // samples of a row
         const uint8_t* mid = in;   // what the vertical pass reads
         size_t v_fs = in_fs;
         if (need_h) {
@@ -655,39 +593,13 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
                 if (rc != LANCZOS_OK) return rc;
                 dst = (uint8_t*)st->scratch.p, dst_fs = mid_fs;
             }
-            e = launch_pass(true, H, C, in + (size_t)mid_row0 * in_pitch, in_fs, (size_t)d->in_w * C, dst, dst_fs,
-                            (size_t)d->out_w * C, d->out_w * C, mid_rows, frames, stream);
+            e = rs_launch_pass((int)B, true, H, C, in + (size_t)mid_row0 * in_pitch, in_fs, in_cols, dst, dst_fs, out_cols,
+                               out_cols, mid_rows, frames, stream, alpha, !need_v);
             mid = (const uint8_t*)((uintptr_t)dst - (uintptr_t)((size_t)mid_row0 * mid_pitch)), v_fs = dst_fs;
         }
         if (e == hipSuccess && need_v)
-            e = launch_pass(false, V, C, mid, v_fs, (size_t)d->out_w * C, out, out_fs, (size_t)d->out_w * C, d->out_w * C,
-                            d->out_h, frames, stream);
-        *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
-    } else {
-        RsPass ph{}, pv{};
-        if (need_h) {
-            ph.src = in + (size_t)mid_row0 * in_pitch, ph.src_fs = in_fs, ph.src_pitch = in_pitch;
-            ph.n_cols = d->out_w * C, ph.channels = C;
-            ph.first = H->first(), ph.count = H->count(), ph.coeffs = H->coeffs(), ph.ksize = H->host.ksize;
-            ph.dst_pitch = mid_pitch;
-            if (need_v) {
-                rc = rs_scratch(st, &st->scratch, (size_t)frames * mid_fs, stream, capturing, last_hip);
-                if (rc != LANCZOS_OK) return rc;
-                ph.dst = (uint8_t*)st->scratch.p, ph.dst_fs = mid_fs;
-            } else {
-                ph.dst = out, ph.dst_fs = out_fs;
-            }
-            e = rs_launch_pass(true, ph, mid_rows, frames, stream, alpha, !need_v);
-        }
-        if (e == hipSuccess && need_v) {
-            pv.src = need_h ? (const uint8_t*)((uintptr_t)ph.dst - (uintptr_t)((size_t)mid_row0 * mid_pitch)) : in;
-            pv.src_fs = need_h ? ph.dst_fs : in_fs;
-            pv.src_pitch = mid_pitch;
-            pv.dst = out, pv.dst_fs = out_fs, pv.dst_pitch = mid_pitch;
-            pv.n_cols = d->out_w * C, pv.channels = C;
-            pv.first = V->first(), pv.count = V->count(), pv.coeffs = V->coeffs(), pv.ksize = V->host.ksize;
-            e = rs_launch_pass(false, pv, d->out_h, frames, stream, alpha, !need_h);
-        }
+            e = rs_launch_pass((int)B, false, V, C, mid, v_fs, out_cols, out, out_fs, out_cols, out_cols, d->out_h, frames,
+                               stream, alpha, !need_h);
         *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
     }
     if (tc) {
@@ -762,18 +674,26 @@ static hipError_t rs_grow_stage(ResizeState* st, void** p, size_t* have, size_t 
     return e;
 }
 
-int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* in, void* out,
-                int frames, hipStream_t stream, int* last_kernel, int* last_hip) {
-    const size_t B = (size_t)resize_bps(d);
-    if ((((uintptr_t)in | (uintptr_t)out) & (B - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
-    const size_t in_bytes = (size_t)d->in_w * d->in_h * d->channels * B * frames;
-    const size_t out_bytes = (size_t)d->out_w * d->out_h * d->channels * B * frames;
-    hipError_t e = rs_grow_stage(st, &st->stage_in, &st->stage_in_bytes, in_bytes, stream);
+// What the host entry points share: both staging blocks grown, the input copied up, `call` (the device entry on the staged
+// blocks; it returns a LANCZOS_ status), the output copied down and the stream drained.  A tensor request has more to upload:
+// its table, `table_at` bytes into the input block, and the output block starts as a copy of `out` (out_up)
+struct RsStagedExtra {
+    const void* table = nullptr;
+    size_t table_at = 0, table_bytes = 0;
+    bool out_up = false;
+};
+template <class F>
+static int rs_staged_call(ResizeState* st, const void* in, size_t in_bytes, void* out, size_t out_bytes, const RsStagedExtra& x,
+                          hipStream_t stream, int* last_hip, F&& call) {
+    hipError_t e = rs_grow_stage(st, &st->stage_in, &st->stage_in_bytes, std::max(in_bytes, x.table_at + x.table_bytes), stream);
     if (e == hipSuccess) e = rs_grow_stage(st, &st->stage_out, &st->stage_out_bytes, out_bytes, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(st->stage_in, in, in_bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && x.table)
+        e = hipMemcpyAsync((uint8_t*)st->stage_in + x.table_at, x.table, x.table_bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && x.out_up) e = hipMemcpyAsync(st->stage_out, out, out_bytes, hipMemcpyHostToDevice, stream);
     int rc = LANCZOS_OK;
     if (e == hipSuccess) {
-        rc = resize_device(st, d, o, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip);
+        rc = call();
         if (rc == LANCZOS_OK) e = hipMemcpyAsync(out, st->stage_out, out_bytes, hipMemcpyDeviceToHost, stream);
     }
     const hipError_t es = hipStreamSynchronize(stream);   // nothing stays in flight on the caller's buffers
@@ -786,6 +706,17 @@ int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_res
     return LANCZOS_OK;
 }
 
+int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* in, void* out,
+                int frames, hipStream_t stream, int* last_kernel, int* last_hip) {
+    const size_t B = (size_t)resize_bps(d);
+    if ((((uintptr_t)in | (uintptr_t)out) & (B - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
+    const size_t in_bytes = (size_t)d->in_w * d->in_h * d->channels * B * frames;
+    const size_t out_bytes = (size_t)d->out_w * d->out_h * d->channels * B * frames;
+    return rs_staged_call(st, in, in_bytes, out, out_bytes, {}, stream, last_hip, [&] {
+        return resize_device(st, d, o, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip);
+    });
+}
+
 // The table rides behind the input frames in the input staging block.  The float frames go up before they come back, so that
 // the words of `out` the strides leave out keep what they held.
 int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_tensor_out* t,
@@ -794,31 +725,17 @@ int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanc
     RsTensorCall tc;
     tc.extent_bytes = tensor_extent_bytes(d, t);
     const size_t in_bytes = (size_t)d->in_w * d->in_h * d->channels * frames;
-    const size_t lut_at = (in_bytes + 255) & ~(size_t)255, lut_bytes = (size_t)d->channels * 256 * sizeof(float);
-    const size_t out_bytes = tc.extent_bytes * frames;
-    hipError_t e = rs_grow_stage(st, &st->stage_in, &st->stage_in_bytes, lut_at + lut_bytes, stream);
-    if (e == hipSuccess) e = rs_grow_stage(st, &st->stage_out, &st->stage_out_bytes, out_bytes, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(st->stage_in, in, in_bytes, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync((uint8_t*)st->stage_in + lut_at, t->d_lut, lut_bytes, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(st->stage_out, out, out_bytes, hipMemcpyHostToDevice, stream);
-    int rc = LANCZOS_OK;
-    if (e == hipSuccess) {
+    RsStagedExtra x;
+    x.table = t->d_lut, x.table_at = (in_bytes + 255) & ~(size_t)255, x.table_bytes = (size_t)d->channels * 256 * sizeof(float);
+    x.out_up = true;
+    return rs_staged_call(st, in, in_bytes, out, tc.extent_bytes * frames, x, stream, last_hip, [&] {
         lanczos_tensor_out dev = *t;
-        dev.d_lut = (const float*)((const uint8_t*)st->stage_in + lut_at);
+        dev.d_lut = (const float*)((const uint8_t*)st->stage_in + x.table_at);
         tc.t = &dev;
-        rc = resize_device(st, d, o, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip, &tc);
+        const int rc = resize_device(st, d, o, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip, &tc);
         *route = tc.route;
-        if (rc == LANCZOS_OK) e = hipMemcpyAsync(out, st->stage_out, out_bytes, hipMemcpyDeviceToHost, stream);
-    }
-    const hipError_t es = hipStreamSynchronize(stream);   // nothing stays in flight on the caller's buffers
-    if (rc != LANCZOS_OK) return rc;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) {
-        *last_hip = (int)e;
-        return LANCZOS_ERR_HIP;
-    }
-    return LANCZOS_OK;
+        return rc;
+    });
 }
 
 int reduce_device(ResizeState* st, int in_w, int in_h, int channels, int fx, int fy, const int32_t* box, const void* d_in,
@@ -848,21 +765,9 @@ int reduce_host(ResizeState* st, int in_w, int in_h, int channels, int fx, int f
     if (rc != LANCZOS_OK) return rc;
     const size_t in_bytes = (size_t)in_w * in_h * channels * frames;
     const size_t out_bytes = (size_t)((rb[2] - rb[0] + fx - 1) / fx) * ((rb[3] - rb[1] + fy - 1) / fy) * channels * frames;
-    hipError_t e = rs_grow_stage(st, &st->stage_in, &st->stage_in_bytes, in_bytes, stream);
-    if (e == hipSuccess) e = rs_grow_stage(st, &st->stage_out, &st->stage_out_bytes, out_bytes, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(st->stage_in, in, in_bytes, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) {
-        rc = reduce_device(st, in_w, in_h, channels, fx, fy, box, st->stage_in, st->stage_out, frames, 0, 0, stream, last_hip);
-        if (rc == LANCZOS_OK) e = hipMemcpyAsync(out, st->stage_out, out_bytes, hipMemcpyDeviceToHost, stream);
-    }
-    const hipError_t es = hipStreamSynchronize(stream);   // nothing stays in flight on the caller's buffers
-    if (rc != LANCZOS_OK) return rc;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) {
-        *last_hip = (int)e;
-        return LANCZOS_ERR_HIP;
-    }
-    return LANCZOS_OK;
+    return rs_staged_call(st, in, in_bytes, out, out_bytes, {}, stream, last_hip, [&] {
+        return reduce_device(st, in_w, in_h, channels, fx, fy, box, st->stage_in, st->stage_out, frames, 0, 0, stream, last_hip);
+    });
 }
 
 }  // namespace lz

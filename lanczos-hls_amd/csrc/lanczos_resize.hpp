@@ -1,9 +1,9 @@
-// lanczos_resize.hpp -- resize to any size with Pillow's Lanczos contract (include/lanczos_hip.h, lanczos_resize_*):
-// host tap tables, their per-context cache, and the entry points lanczos_api.hip forwards to.  The kernels live in
-// lanczos_resize.hip; those of 16-bit requests (LANCZOS_RESIZE_U16, double coefficients) in lanczos_resize16.hip and those of
-// float requests (LANCZOS_RESIZE_F32, the same double tables) in lanczos_resize32.hip.  The filter of a request
-// (LANCZOS_RESIZE_FILTER) only changes the tables; LANCZOS_FILTER_NEAREST has index tables and a kernel of its own
-// (lanczos_resize_nearest.hip).
+// lanczos_resize.hpp -- resize to any size with Pillow's contract (include/lanczos_hip.h, lanczos_resize_*): host tap tables,
+// their per-context cache, and the entry points lanczos_api.hip forwards to.  Tables, cache, planning and dispatch are in
+// lanczos_resize.hip.  The kernels are written once for 8-bit, 16-bit (LANCZOS_RESIZE_U16) and float (LANCZOS_RESIZE_F32)
+// samples in lanczos_resize_fused.hpp; the fused instances are compiled by lanczos_resize.hip (8-bit), lanczos_resize_tensor.hip
+// (8-bit into float tensors), lanczos_resize16.hip and lanczos_resize32.hip.  The filter of a request (LANCZOS_RESIZE_FILTER)
+// only changes the tables; LANCZOS_FILTER_NEAREST has index tables and a kernel of its own (lanczos_resize_nearest.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -71,7 +71,7 @@ inline bool resize_f32(const lanczos_resize_desc* d) { return (d->reserved[0] & 
 // bytes per sample: 1, 2 (LANCZOS_RESIZE_U16) or 4 (LANCZOS_RESIZE_F32); samples wider than a byte run on the double tables
 inline int resize_bps(const lanczos_resize_desc* d) { return resize_f32(d) ? 4 : resize_u16(d) ? 2 : 1; }
 
-// launch geometry both translation units share
+// launch geometry the translation units share
 constexpr int kRsThreads = 256;
 constexpr int kRsOB = 8;             // output rows per march step of the fused kernels
 constexpr int kRsLoadBatch = 16;     // staging loads in flight per thread
@@ -100,8 +100,8 @@ struct ResizeAxis {
     int32_t* dev = nullptr;
     const int32_t* first() const { return dev; }
     const int32_t* count() const { return dev + host.out_n; }
-    const int32_t* coeffs() const { return dev + 2 * (size_t)host.out_n; }
-    const double* coeffs64() const { return (const double*)(dev + 2 * (size_t)host.out_n); }
+    template <class KT>   // int32_t, or double for the tables of samples wider than a byte (key[3])
+    const KT* coeffs() const { return (const KT*)(dev + 2 * (size_t)host.out_n); }
     std::vector<hipStream_t> streams;   // streams whose launches read this block (retirement)
 };
 
@@ -140,10 +140,6 @@ struct RsTensorCall {
 int tensor_validate(const lanczos_resize_desc* d, const lanczos_tensor_out* t);
 size_t tensor_extent_bytes(const lanczos_resize_desc* d, const lanczos_tensor_out* t);
 void tensor_lut_normalize(int channels, const float* mean, const float* std, float* lut);
-// the TENSOR instances of k_rs_fused (every K bucket x C = 1, 3, 4 and alpha); `out` / `out_fs`: the float frames
-hipError_t rs_tensor_launch_fused(const lanczos_resize_desc* d, const RsFusedPlan& fp, const ResizeAxis* H, const ResizeAxis* V,
-                                  const uint8_t* in, uint8_t* out, size_t in_fs, size_t out_fs, int frames,
-                                  const RsTensorCall& tc, hipStream_t stream);
 // k_rs_to_tensor: tightly packed interleaved bytes (frames `src_fs` apart, base and stride dword multiples, readable up to the
 // next dword multiple behind each frame) -> strided floats through the table
 hipError_t rs_to_tensor_launch(const uint8_t* src, size_t src_fs, uint8_t* out, size_t out_fs, int w, int h, int channels,
@@ -169,24 +165,21 @@ int reduce_device(ResizeState* st, int in_w, int in_h, int channels, int fx, int
 int reduce_host(ResizeState* st, int in_w, int in_h, int channels, int fx, int fy, const int32_t* box, const void* in,
                 void* out, int frames, hipStream_t stream, int* last_hip);
 
-// 16-bit requests (lanczos_resize16.hip): the tap count of the smallest fused instance that holds ksize (0: none; small: the
-// instances with 3 and 5 taps count, which they do for every filter but Lanczos), and the launches.
-// Pitches are those of tightly packed rows; frame strides in bytes.
-int rs16_bucket(int ksize, bool small);
-hipError_t rs16_launch_fused(const lanczos_resize_desc* d, const RsFusedPlan& fp, const ResizeAxis* H, const ResizeAxis* V,
-                             const uint8_t* in, uint8_t* out, size_t in_fs, size_t out_fs, int frames, hipStream_t stream);
-// one pass of the two-pass path over `rows` rows of `n_cols` samples: src / dst row pitches in samples
-hipError_t rs16_launch_pass(bool horizontal, const ResizeAxis* ax, int channels, const uint8_t* src, size_t src_fs,
-                            size_t src_pitch, uint8_t* dst, size_t dst_fs, size_t dst_pitch, int n_cols, int rows, int frames,
-                            hipStream_t stream);
-
-// float requests (lanczos_resize32.hip): the same two launches with 4-byte samples; the fused instances have the tap counts of
-// rs16_bucket
-hipError_t rs32_launch_fused(const lanczos_resize_desc* d, const RsFusedPlan& fp, const ResizeAxis* H, const ResizeAxis* V,
-                             const uint8_t* in, uint8_t* out, size_t in_fs, size_t out_fs, int frames, hipStream_t stream);
-hipError_t rs32_launch_pass(bool horizontal, const ResizeAxis* ax, int channels, const uint8_t* src, size_t src_fs,
-                            size_t src_pitch, uint8_t* dst, size_t dst_fs, size_t dst_pitch, int n_cols, int rows, int frames,
-                            hipStream_t stream);
+// One request for the fused kernel, k_rs_fused<RsSample<BPS>, C, K, ALPHA, TENSOR> (lanczos_resize_fused.hpp): the instance
+// is that of d's channels and alpha flag and of the plan's K.  Frame strides in bytes.
+struct RsFusedLaunch {
+    const lanczos_resize_desc* d;
+    const RsFusedPlan* fp;
+    const ResizeAxis *H, *V;
+    const uint8_t* in;
+    uint8_t* out;
+    size_t in_fs, out_fs;
+    int frames;
+    const RsTensorCall* tc;   // TENSOR: `out` / `out_fs` are the float frames
+    hipStream_t stream;
+};
+template <int BPS, bool TENSOR>
+hipError_t rs_launch_fused(const RsFusedLaunch& c);
 
 // LANCZOS_FILTER_NEAREST (lanczos_resize_nearest.hip): out[y][x] = in[vidx[y]][hidx[x]] for pixels of `channels` samples of
 // `bps` bytes (1 or 4), one launch.  hidx / vidx are device tables of out_w / out_h source indices, all inside the source.

@@ -1,71 +1,205 @@
-// lanczos_resize_fused.hpp -- k_rs_fused, the fused kernel of 8-bit resizes (lanczos_resize.hip describes the march), as a
-// template two translation units instantiate: lanczos_resize.hip the instances that store bytes, lanczos_resize_tensor.hip
-// those whose vertical pass stores floats through a table instead (TENSOR; include/lanczos_hip.h, lanczos_tensor_out).
+// lanczos_resize_fused.hpp -- the resize kernels, written once for the three sample widths (lanczos_resize.hip describes the
+// two paths):
+//
+//   RsSample<BPS>   what a sample width brings: its types, Pillow's multiply-add and store.  These are the specification of
+//                   the bytes; everything below only moves samples around.
+//   k_rs_pass_h/_v  the two-pass kernels, one thread per output sample (instantiated in lanczos_resize.hip).
+//   k_rs_fused      the fused kernel, and rs_launch_fused, which fills its arguments and picks the instance.  Four
+//                   translation units instantiate them side by side: lanczos_resize.hip (8-bit, bytes out),
+//                   lanczos_resize_tensor.hip (8-bit, floats out through a table: TENSOR), lanczos_resize16.hip and
+//                   lanczos_resize32.hip.
 #pragma once
 #include "lanczos_alpha.hpp"
 #include "lanczos_resize.hpp"
 
+#include <algorithm>
+#include <type_traits>
+
 namespace lz {
 
-__device__ __forceinline__ int rs_mad(int sample, int coeff, int acc) { return __mul24(sample, coeff) + acc; }
-__device__ __forceinline__ uint32_t rs_clip8(int acc) { return (uint32_t)min(max(acc >> kResizePrecision, 0), 255); }
+// ---- the sample policies ---------------------------------------------------------------------------------------------
+//
+// elem_t: a sample in memory; word_t: the unsigned type of its width; coeff_t / acc_t: a coefficient and a running sum;
+// kAcc0: the sum before the first tap; SPD: samples per dword; kPassUnroll: the tap loop's unroll factor in the two-pass
+// kernels; get(w, i): sample i of a dword; mad(sample, k, acc): one tap; store(acc): the sample Pillow stores, in the low
+// bits of a word.
+template <int BPS>
+struct RsSample;
 
+// 8-bit: acc = 2^21 + sum(sample * coeff) in int32 with 24-bit multiplies (|coeff| < 2^23 and 255 * sum|coeff| + 2^21 < 2^31,
+// checked when a table is built), result clamp(acc >> 22, 0, 255).  Integer sums: tap order and zero-padded taps change nothing.
+template <>
+struct RsSample<1> {
+    using elem_t = uint8_t;
+    using word_t = uint8_t;
+    using coeff_t = int32_t;
+    using acc_t = int;
+    static constexpr int BPS = 1, SPD = 4, kPassUnroll = 8;
+    static constexpr int kAcc0 = 1 << (kResizePrecision - 1);
+    static __device__ __forceinline__ int get(uint32_t w, int i) { return (int)((w >> (8 * i)) & 255u); }
+    static __device__ __forceinline__ int mad(int sample, int coeff, int acc) { return __mul24(sample, coeff) + acc; }
+    static __device__ __forceinline__ uint32_t store(int acc) { return (uint32_t)min(max(acc >> kResizePrecision, 0), 255); }
+};
+
+// 16-bit (Pillow's I;16) accumulates in double, tap by tap: ss = ss + (double)sample * k.  The bytes follow from three
+// things.  (1) The multiply and the add round separately: every tap goes through mad, spelled with __dmul_rn / __dadd_rn,
+// which the compiler never contracts (the build also passes -ffp-contract=off); the ISA of the wide-sample kernels holds no
+// v_fma_f64.  (2) One chain per sample in ascending tap order: no tree, no split sums.  (3) A padded tap multiplies a finite
+// sample by 0.0 and adds +0.0, which leaves the sum and its rounding as they were.  u16 -> f64 is exact.
+template <>
+struct RsSample<2> {
+    using elem_t = uint16_t;
+    using word_t = uint16_t;
+    using coeff_t = double;
+    using acc_t = double;
+    static constexpr int BPS = 2, SPD = 2, kPassUnroll = 4;
+    static constexpr double kAcc0 = 0.0;
+    static __device__ __forceinline__ uint32_t get(uint32_t w, int i) { return (w >> (16 * i)) & 0xffffu; }
+    static __device__ __forceinline__ double mad(uint32_t sample, double k, double ss) {
+        return __dadd_rn(ss, __dmul_rn((double)sample, k));
+    }
+    // Pillow's ROUND_UP and its two CLIP8 stores: v < 0 stores 0, v > 65535 stores 0xFF00 | (v & 255) -- the low byte wraps
+    static __device__ __forceinline__ uint32_t store(double ss) {
+        const int v = (int)(ss < 0.0 ? __dadd_rn(ss, -0.5) : __dadd_rn(ss, 0.5));
+        return v < 0 ? 0u : (uint32_t)(min(v >> 8, 255) << 8 | (v & 255));
+    }
+};
+
+// float (Pillow's mode F) accumulates in double like 16-bit and stores (float)ss.  The bits follow from four things.  (1) and
+// (2) as above.  (3) Exactly `count` taps are multiplied.  A float next to the window may be inf or NaN, and inf * 0.0 is
+// NaN, so the 16-bit padding (a neighbouring sample times +0.0) is not harmless here: the unrolled horizontal loop of the fused
+// kernel selects on tap < count -- never on the coefficient, since a zero weight inside Pillow's window is multiplied there
+// too -- and every other loop runs to count.  Staged dwords beyond the frame read as 0 and are never multiplied either.
+// (4) Denormals survive: samples travel as dwords, and float <-> double conversions and the double arithmetic run with the
+// kernel mode's denormal bits set (FP_DENORM = 3 for both fields of the MODE register, the compiler's default: the build
+// passes no flush flag).
+template <>
+struct RsSample<4> {
+    using elem_t = float;
+    using word_t = uint32_t;
+    using coeff_t = double;
+    using acc_t = double;
+    static constexpr int BPS = 4, SPD = 1, kPassUnroll = 4;
+    static constexpr double kAcc0 = 0.0;
+    static __device__ __forceinline__ float get(uint32_t w, int) { return __uint_as_float(w); }
+    static __device__ __forceinline__ double mad(float sample, double k, double ss) {
+        return __dadd_rn(ss, __dmul_rn((double)sample, k));
+    }
+    static __device__ __forceinline__ uint32_t store(double ss) { return __float_as_uint(__double2float_rn(ss)); }
+};
+
+// ---- two-pass path ---------------------------------------------------------------------------------------------------
+
+// one pass: `n_cols` samples per output row, `rows` output rows, frames in blockIdx.z
+template <class KT>
+struct RsPass {
+    const uint8_t* src;
+    uint8_t* dst;
+    unsigned long long src_fs, dst_fs;         // frame strides (bytes)
+    unsigned long long src_pitch, dst_pitch;   // row pitches (samples)
+    int n_cols, channels;
+    const int32_t *first, *count;
+    const KT* coeffs;
+    int ksize;
+};
+
+// horizontal: output sample x = o * C + c of row blockIdx.y
+template <class S>
+__global__ __launch_bounds__(kRsThreads) void k_rs_pass_h(RsPass<typename S::coeff_t> p) {
+    const int x = blockIdx.x * kRsThreads + threadIdx.x;
+    if (x >= p.n_cols) return;
+    const int o = x / p.channels, c = x - o * p.channels;
+    const typename S::elem_t* src = (const typename S::elem_t*)(p.src + blockIdx.z * p.src_fs) + blockIdx.y * p.src_pitch + c;
+    const int f = p.first[o], n = p.count[o];
+    const typename S::coeff_t* k = p.coeffs + (size_t)o * p.ksize;
+    typename S::acc_t acc = S::kAcc0;
+#pragma unroll S::kPassUnroll
+    for (int i = 0; i < n; i++) acc = S::mad(src[(size_t)(f + i) * p.channels], k[i], acc);
+    ((typename S::word_t*)(p.dst + blockIdx.z * p.dst_fs))[blockIdx.y * p.dst_pitch + x] = (typename S::word_t)S::store(acc);
+}
+
+// vertical: output row o = blockIdx.y, sample column x (coefficients uniform over the workgroup)
+template <class S>
+__global__ __launch_bounds__(kRsThreads) void k_rs_pass_v(RsPass<typename S::coeff_t> p) {
+    const int x = blockIdx.x * kRsThreads + threadIdx.x;
+    if (x >= p.n_cols) return;
+    const int o = blockIdx.y;
+    const int f = p.first[o], n = p.count[o];
+    const typename S::coeff_t* k = p.coeffs + (size_t)o * p.ksize;
+    const typename S::elem_t* src = (const typename S::elem_t*)(p.src + blockIdx.z * p.src_fs) + (size_t)f * p.src_pitch + x;
+    typename S::acc_t acc = S::kAcc0;
+#pragma unroll S::kPassUnroll
+    for (int i = 0; i < n; i++) acc = S::mad(src[(size_t)i * p.src_pitch], k[i], acc);
+    ((typename S::word_t*)(p.dst + blockIdx.z * p.dst_fs))[o * p.dst_pitch + x] = (typename S::word_t)S::store(acc);
+}
+
+// ---- fused path ------------------------------------------------------------------------------------------------------
+
+template <class KT>
 struct RsFused {
     const uint8_t* in;
     uint8_t* out;
     unsigned long long in_fs, out_fs;
-    int in_pitch, out_pitch, in_h, out_w, out_h;
-    const int32_t *hf, *hc, *hk;
+    int in_pitch, out_pitch, in_h, out_w, out_h;   // pitches in bytes
+    const int32_t *hf, *hc;
+    const KT* hk;
     int hks;
-    const int32_t *vf, *vc, *vk;
+    const int32_t *vf, *vc;
+    const KT* vk;
     int vks;
     int strips, rows_per_chunk;   // grid.x = strips * chunks, grid.y = frames
     int ring_rows, stage_rows, stage_dw;
 };
 // TENSOR instances: `out` / `out_fs` of RsFused are the float frames and their stride in bytes
-struct RsFusedTensor : RsFused {
+struct RsFusedTensor : RsFused<int32_t> {
     const uint32_t* lut;     // [C][256] words, read when the kernel runs
     int cs, rs, ps;          // channel, row and pixel strides in floats
     unsigned extent_bytes;   // of one float frame, below 2^31
 };
-template <bool TENSOR>
-struct RsFusedArg {
-    using type = RsFused;
-};
-template <>
-struct RsFusedArg<true> {
-    using type = RsFusedTensor;
-};
 
-template <int C>
+template <int C, int BPS>
 struct RsStrip {
-    static constexpr int SW = rs_strip_width(C, 1);   // output pixels per strip
-    static constexpr int RL = kRsThreads / SW;    // input rows per horizontal round
-    static constexpr int RDW = SW * C / 4;        // ring row in dwords
-    static constexpr int WPR = RDW / 64;          // waves per ring row in the vertical pass
+    static constexpr int SW = rs_strip_width(C, BPS);   // output pixels per strip
+    static constexpr int RL = kRsThreads / SW;          // input rows per horizontal round
+    static constexpr int RDW = SW * C * BPS / 4;        // ring row in dwords
+    static constexpr int WPR = RDW / 64;                // waves per ring row in the vertical pass
 };
 
-// ALPHA (LANCZOS_RESIZE_ALPHA, C == 4): the staging loads premultiply, once per staged pixel and not once per window that
-// reads it, and the vertical pass divides alpha out where it packs its dword, which for four channels is one pixel.  For
+// The march.  Input rows are staged in LDS as the dwords they come in; the horizontal pass turns them into rows of an LDS
+// ring, stored as Pillow stores the intermediate; the vertical pass reads the ring, a lane owning one dword of the row (S::SPD
+// samples).  A thread keeps one output column and its K coefficients in registers for the whole march (2 VGPRs per tap where
+// they are doubles); the vertical coefficients are workgroup-uniform scalar loads.
+//
+// Float frames start on a dword and have dword pitches (checked by the caller), so a staged dword is a sample: there is no
+// `delta`, no shift, and the window is read tap by tap with the select RsSample<4> asks for.
+//
+// ALPHA (LANCZOS_RESIZE_ALPHA, C == 4, 8-bit): the staging loads premultiply, once per staged pixel and not once per window
+// that reads it, and the vertical pass divides alpha out where it packs its dword, which for four channels is one pixel.  For
 // that the staged dwords are pixels: a frame base that is no dword multiple (every row then starts `delta` bytes into a
 // dword, the row pitch being one) is shifted out while staging, and the horizontal pass reads its window unshifted.
 //
-// TENSOR (lanczos_tensor_out): the vertical pass stores lut[c][byte] as a float at c * cs + y * rs + x * ps of the float frame
-// instead of the byte.  A lane holds four consecutive samples of the interleaved row, so a store of them as they lie would
+// TENSOR (lanczos_tensor_out, 8-bit): the vertical pass stores lut[c][byte] as a float at c * cs + y * rs + x * ps of the float
+// frame instead of the byte.  A lane holds four consecutive samples of the interleaved row, so a store of them as they lie would
 // put 16 bytes between neighbouring lanes; the wave's 64 dwords are exchanged instead (four ds_bpermute) so that in round r
 // lane i has sample 64 r + i of the wave's 256: neighbouring lanes store neighbouring samples, whole 256-byte runs where the
 // layout is interleaved or has one channel, runs of every C-th lane per plane where it is planar.  The table is read from
 // global memory through the vector cache (1 to 4 KiB, resident after the first rows): LDS and the plan stay the byte kernel's.
-template <int C, int K, bool ALPHA = false, bool TENSOR = false>
-__global__ __launch_bounds__(kRsThreads) void k_rs_fused(typename RsFusedArg<TENSOR>::type g) {
+template <class S, int C, int K, bool ALPHA = false, bool TENSOR = false>
+__global__ __launch_bounds__(kRsThreads) void k_rs_fused(
+    std::conditional_t<TENSOR, RsFusedTensor, RsFused<typename S::coeff_t>> g) {
     static_assert(!ALPHA || C == 4, "alpha is the fourth of four channels");
-    using S = RsStrip<C>;
-    constexpr int SW = S::SW, RL = S::RL, RDW = S::RDW, WPR = S::WPR;
-    constexpr int NE = (K * C + 3) / 4;   // dwords of one horizontal window
+    static_assert((!ALPHA && !TENSOR) || S::BPS == 1, "alpha and tensor output are 8-bit");
+    using acc_t = typename S::acc_t;
+    using word_t = typename S::word_t;
+    using St = RsStrip<C, S::BPS>;
+    constexpr int SW = St::SW, RL = St::RL, RDW = St::RDW, WPR = St::WPR;
+    constexpr int BPS = S::BPS, SPD = S::SPD;
+    constexpr int CB = C * BPS;                        // bytes per pixel
+    constexpr int NE = (K * C + SPD - 1) / SPD;        // dwords of one horizontal window
+    constexpr bool kDwordSamples = BPS == 4;           // a sample is a dword: nothing to align
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     uint32_t* ring = lds;                        // [ring_rows][RDW]
     uint32_t* stage = lds + g.ring_rows * RDW;   // [stage_rows][stage_dw]
-    uint8_t* ring8 = (uint8_t*)ring;
 
     const int tid = threadIdx.x;
     const int strip = blockIdx.x % g.strips, chunk = blockIdx.x / g.strips;
@@ -73,30 +207,31 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(typename RsFusedArg<TEN
     const int sw = min(SW, g.out_w - x0);
     const int xs = g.hf[x0];   // first input pixel of the strip's span
 
-    // horizontal: this thread's output column for the whole march, its coefficients in registers
+    // horizontal: this thread's output column for the whole march, its coefficients in registers; nh taps are its window
     const int px = tid % SW, rl = tid / SW;
-    int kh[K];
-    int hoffb;
+    typename S::coeff_t kh[K];
+    int hoff, nh;   // the window's offset into the strip's span: bytes, dwords where a sample is one
     {
         const int p = x0 + min(px, sw - 1);
-        const int n = px < sw ? g.hc[p] : 0;
-        hoffb = (g.hf[p] - xs) * C;
+        nh = px < sw ? g.hc[p] : 0;
+        hoff = (g.hf[p] - xs) * (kDwordSamples ? C : CB);
 #pragma unroll
-        for (int k = 0; k < K; k++) kh[k] = k < n ? g.hk[(size_t)p * g.hks + k] : 0;
+        for (int k = 0; k < K; k++) kh[k] = k < nh ? g.hk[(size_t)p * g.hks + k] : 0;
     }
 
     const uint8_t* fin = g.in + blockIdx.y * g.in_fs;
     // dword-aligned base and range: the bytes in front of the frame and behind its end that share a dword with it (same
     // page) are read but only ever multiplied by zero coefficients; everything further out reads as 0
-    const int delta = (int)((uintptr_t)fin & 3);
+    const int delta = kDwordSamples ? 0 : (int)((uintptr_t)fin & 3);
     const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(fin - delta), 0, (unsigned)((delta + g.in_h * g.in_pitch + 3) & ~3), 0x00020000);
+        const_cast<uint8_t*>(fin - delta), 0,
+        kDwordSamples ? (unsigned)(g.in_h * g.in_pitch) : (unsigned)((delta + g.in_h * g.in_pitch + 3) & ~3), 0x00020000);
     uint8_t* fout = g.out + blockIdx.y * g.out_fs;
     unsigned out_bytes = (unsigned)(g.out_h * g.out_pitch);
     if constexpr (TENSOR) out_bytes = g.extent_bytes;
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(fout, 0, out_bytes, 0x00020000);
-    const bool out_aligned = (((uintptr_t)fout | (unsigned)g.out_pitch | (unsigned)(x0 * C)) & 3) == 0;
-    const int valid_bytes = sw * C;
+    const bool out_aligned = (((uintptr_t)fout | (unsigned)g.out_pitch | (unsigned)(x0 * CB)) & 3) == 0;
+    const int valid_bytes = sw * (kDwordSamples ? C : CB);   // of the strip's row; dwords where a sample is one
 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int o_begin = chunk * g.rows_per_chunk;
@@ -122,8 +257,13 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(typename RsFusedArg<TEN
                     int r = (int)((float)u * inv_sd);   // u / stage_dw, corrected below (u < 2^20)
                     r -= r * g.stage_dw > u;
                     r += (r + 1) * g.stage_dw <= u;
-                    const int off = delta + (hi + r) * g.in_pitch + xs * C;
-                    const int at = (off & ~3) + 4 * (u - r * g.stage_dw);
+                    int at;
+                    if constexpr (kDwordSamples) {
+                        at = (hi + r) * g.in_pitch + 4 * (xs * C + u - r * g.stage_dw);
+                    } else {
+                        const int off = delta + (hi + r) * g.in_pitch + xs * CB;
+                        at = (off & ~3) + 4 * (u - r * g.stage_dw);
+                    }
                     v[b] = u < total ? __builtin_amdgcn_raw_buffer_load_b32(irsrc, at, 0, 0) : 0u;
                     if constexpr (ALPHA)
                         vn[b] = delta != 0 && u < total ? __builtin_amdgcn_raw_buffer_load_b32(irsrc, at + 4, 0, 0) : 0u;
@@ -139,57 +279,73 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(typename RsFusedArg<TEN
             }
             __syncthreads();
             for (int j = rl; j < nr; j += RL) {
-                const int pos = (ALPHA ? 0 : (delta + (hi + j) * g.in_pitch + xs * C) & 3) + hoffb;
-                const uint32_t* srow = stage + j * g.stage_dw + (pos >> 2);
-                const unsigned sh = ALPHA ? 0u : pos & 3;   // ALPHA: the staged dwords are pixels
-                uint32_t dw[NE + 1];
+                acc_t acc[C];
 #pragma unroll
-                for (int t = 0; t <= NE; t++) dw[t] = !ALPHA || t < NE ? srow[t] : 0u;
-                int acc[C];
+                for (int c = 0; c < C; c++) acc[c] = S::kAcc0;
+                if constexpr (kDwordSamples) {
+                    const uint32_t* srow = stage + j * g.stage_dw + hoff;
 #pragma unroll
-                for (int c = 0; c < C; c++) acc[c] = 1 << (kResizePrecision - 1);
+                    for (int k = 0; k < K; k++) {
 #pragma unroll
-                for (int t = 0; t < NE; t++) {
-                    const uint32_t e = __builtin_amdgcn_alignbyte(dw[t + 1], dw[t], sh);
+                        for (int c = 0; c < C; c++) {
+                            const acc_t ss = S::mad(S::get(srow[k * C + c], 0), kh[k], acc[c]);
+                            acc[c] = k < nh ? ss : acc[c];   // a select on the tap count: the sum of a tap past it is dropped
+                        }
+                    }
+                } else {
+                    const int pos = (ALPHA ? 0 : (delta + (hi + j) * g.in_pitch + xs * CB) & 3) + hoff;
+                    const uint32_t* srow = stage + j * g.stage_dw + (pos >> 2);
+                    const unsigned sh = ALPHA ? 0u : pos & 3;   // ALPHA: the staged dwords are pixels
+                    uint32_t dw[NE + 1];
 #pragma unroll
-                    for (int b = 0; b < 4; b++) {
-                        const int idx = t * 4 + b;
-                        if (idx < K * C) acc[idx % C] = rs_mad((int)((e >> (8 * b)) & 255u), kh[idx / C], acc[idx % C]);
+                    for (int t = 0; t <= NE; t++) dw[t] = !ALPHA || t < NE ? srow[t] : 0u;
+#pragma unroll
+                    for (int t = 0; t < NE; t++) {
+                        const uint32_t e = __builtin_amdgcn_alignbyte(dw[t + 1], dw[t], sh);
+#pragma unroll
+                        for (int b = 0; b < SPD; b++) {
+                            const int idx = t * SPD + b;   // sample of the window: tap idx / C of channel idx % C, ascending
+                            if (idx < K * C) acc[idx % C] = S::mad(S::get(e, b), kh[idx / C], acc[idx % C]);
+                        }
                     }
                 }
-                uint8_t* rrow = ring8 + ((hi + j) % g.ring_rows) * (RDW * 4) + px * C;
+                word_t* rrow = (word_t*)ring + ((hi + j) % g.ring_rows) * (RDW * SPD) + px * C;
 #pragma unroll
-                for (int c = 0; c < C; c++) rrow[c] = (uint8_t)rs_clip8(acc[c]);
+                for (int c = 0; c < C; c++) rrow[c] = (word_t)S::store(acc[c]);
             }
             __syncthreads();
             hi += nr;
         }
-        // vertical: one output row per wave (WPR waves per row), coefficients uniform
+        // vertical: one output row per wave (WPR waves per row), coefficients uniform, SPD samples per lane
         for (int q = wave; q < nob * WPR; q += kRsThreads / 64) {
             const int r = q / WPR;
             const int o = o0 + r;
             const int dcol = (q - r * WPR) * 64 + lane;
             const int f = g.vf[o], n = g.vc[o];
-            const int32_t* kv = g.vk + (size_t)o * g.vks;
+            const typename S::coeff_t* kv = g.vk + (size_t)o * g.vks;
             int slot = f % g.ring_rows;
-            int a0 = 1 << (kResizePrecision - 1), a1 = a0, a2 = a0, a3 = a0;
+            // SPD of the four sums are used.  Named sums and the packing below written out per width, not an array and
+            // loops over it: from those the compiler orders the sums' registers otherwise, and for 8-bit it then packs with
+            // the v_ashr_pk_u8_i32 that the TENSOR branch speaks of.  With the array, and the 8-bit pack kept from that
+            // instruction by hand, every instance had the same registers and occupancy but another schedule, and the 4K
+            // workloads measured 0.25 to 0.5 % slower (8-bit and float, three channels, halving and doubling)
+            [[maybe_unused]] acc_t a0 = S::kAcc0, a1 = a0, a2 = a0, a3 = a0;
 #pragma unroll 4
             for (int i = 0; i < n; i++) {
-                const int k = kv[i];
+                const typename S::coeff_t k = kv[i];
                 const uint32_t w = ring[slot * RDW + dcol];
-                a0 = rs_mad((int)(w & 255u), k, a0);
-                a1 = rs_mad((int)((w >> 8) & 255u), k, a1);
-                a2 = rs_mad((int)((w >> 16) & 255u), k, a2);
-                a3 = rs_mad((int)(w >> 24), k, a3);
+                a0 = S::mad(S::get(w, 0), k, a0);
+                if constexpr (SPD > 1) a1 = S::mad(S::get(w, 1), k, a1);
+                if constexpr (SPD > 2) a2 = S::mad(S::get(w, 2), k, a2), a3 = S::mad(S::get(w, 3), k, a3);
                 if (++slot == g.ring_rows) slot = 0;
             }
-            const int b0 = dcol * 4;
+            const int b0 = kDwordSamples ? dcol : dcol * 4;   // the lane's place in the strip's row, as valid_bytes counts
             if constexpr (TENSOR) {
                 // the dword is put together with v_perm_b32, not with shifts: followed by the exchange below, the shifted form
                 // is compiled to v_ashr_pk_u8_i32, whose 16-bit result leaves the upper half of its register as it was while
                 // the code behind it takes that half for zero (seen on the device: bytes 2 and 3 with bits of a0 in them)
-                uint32_t packed = __builtin_amdgcn_perm(rs_clip8(a1), rs_clip8(a0), 0x0c0c0400u) |
-                                  __builtin_amdgcn_perm(rs_clip8(a3), rs_clip8(a2), 0x04000c0cu);
+                uint32_t packed = __builtin_amdgcn_perm(S::store(a1), S::store(a0), 0x0c0c0400u) |
+                                  __builtin_amdgcn_perm(S::store(a3), S::store(a2), 0x04000c0cu);
                 if constexpr (ALPHA) packed = rs_unpremul_px(packed);
                 const int wb = b0 - lane * 4;   // the wave's first sample of the strip's row
 #pragma unroll
@@ -203,23 +359,100 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(typename RsFusedArg<TEN
                     }
                 }
             } else if (b0 < valid_bytes) {
-                const int row_off = o * g.out_pitch + x0 * C + b0;
-                uint32_t packed = rs_clip8(a0) | (rs_clip8(a1) << 8) | (rs_clip8(a2) << 16) | (rs_clip8(a3) << 24);
+                const int row_off = o * g.out_pitch + (kDwordSamples ? 4 * (x0 * C + dcol) : x0 * CB + b0);
+                uint32_t packed;   // the dword of the lane's stored samples
+                if constexpr (SPD == 4) packed = S::store(a0) | (S::store(a1) << 8) | (S::store(a2) << 16) | (S::store(a3) << 24);
+                else if constexpr (SPD == 2) packed = S::store(a0) | (S::store(a1) << 16);
+                else packed = S::store(a0);
                 if constexpr (ALPHA) packed = rs_unpremul_px(packed);
-                if (out_aligned && b0 + 4 <= valid_bytes) {
+                if (kDwordSamples || (out_aligned && b0 + 4 <= valid_bytes)) {
                     __builtin_amdgcn_raw_buffer_store_b32(packed, orsrc, row_off, 0, 0);
-                } else {
+                } else if constexpr (BPS == 1) {
                     for (int b = 0; b < 4 && b0 + b < valid_bytes; b++)
                         __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(packed >> (8 * b)), orsrc, row_off + b, 0, 0);
+                } else if constexpr (BPS == 2) {
+                    __builtin_amdgcn_raw_buffer_store_b16((uint16_t)S::store(a0), orsrc, row_off, 0, 0);
+                    if (b0 + 2 < valid_bytes) __builtin_amdgcn_raw_buffer_store_b16((uint16_t)S::store(a1), orsrc, row_off + 2, 0, 0);
                 }
             }
         }
     }
 }
 
-// horizontal tap counts with a fused instance (a request runs on the smallest one >= its ksize, zero-padded).  3 and 5 serve
-// the upscales of the short filters (box and bilinear: ksize 3, bicubic: 5) and only them: a Lanczos request keeps the
-// instance it always had (a = 2 upscales, ksize 5, run on 7).  LANCZOS_RS_NO_SMALL_BUCKETS=1 pads the short filters to 7 too
+// horizontal tap counts with a fused instance (a request runs on the smallest one >= its ksize, zero-padded), for every
+// sample width.  3 and 5 serve the upscales of the short filters (box and bilinear: ksize 3, bicubic: 5) and only them: a
+// Lanczos request keeps the instance it always had (a = 2 upscales, ksize 5, run on 7).  LANCZOS_RS_NO_SMALL_BUCKETS=1 pads
+// the short filters to 7 too
 #define LZ_RS_BUCKETS(X) X(3) X(5) X(7) X(9) X(11) X(13) X(17) X(25)
+
+// f(C, K, ALPHA) as std::integral_constants for the instance of a request; false: there is none
+template <class F>
+bool rs_dispatch_instance(int channels, int K, bool alpha, F&& f) {
+    auto with_k = [&](auto kb) {
+        if (channels == 1) f(std::integral_constant<int, 1>(), kb, std::false_type());
+        else if (channels == 3) f(std::integral_constant<int, 3>(), kb, std::false_type());
+        else if (alpha) f(std::integral_constant<int, 4>(), kb, std::true_type());
+        else f(std::integral_constant<int, 4>(), kb, std::false_type());
+    };
+#define X(KB)                                          \
+    if (K == KB) {                                     \
+        with_k(std::integral_constant<int, KB>());     \
+        return true;                                   \
+    }
+    LZ_RS_BUCKETS(X)
+#undef X
+    return false;
+}
+
+// the launch arguments of a request, all but the frame pointers
+template <class KT>
+void rs_fill_fused(RsFused<KT>* g, const RsFusedLaunch& c) {
+    const lanczos_resize_desc* d = c.d;
+    g->in_pitch = d->in_w * d->channels * resize_bps(d);
+    g->out_pitch = d->out_w * d->channels * resize_bps(d);
+    g->in_h = d->in_h, g->out_w = d->out_w, g->out_h = d->out_h;
+    g->in_fs = c.in_fs, g->out_fs = c.out_fs;
+    g->hf = c.H->first(), g->hc = c.H->count(), g->hk = c.H->coeffs<KT>(), g->hks = c.H->host.ksize;
+    g->vf = c.V->first(), g->vc = c.V->count(), g->vk = c.V->coeffs<KT>(), g->vks = c.V->host.ksize;
+    g->strips = c.fp->strips, g->rows_per_chunk = c.fp->rows_per_chunk;
+    g->ring_rows = c.fp->ring_rows, g->stage_rows = c.fp->stage_rows, g->stage_dw = c.fp->stage_dw;
+}
+
+template <int BPS, bool TENSOR>
+hipError_t rs_launch_fused(const RsFusedLaunch& c) {
+    using S = RsSample<BPS>;
+    const bool alpha = (c.d->reserved[0] & LANCZOS_RESIZE_ALPHA) != 0;
+    const RsFusedPlan& fp = *c.fp;
+    std::conditional_t<TENSOR, RsFusedTensor, RsFused<typename S::coeff_t>> g{};
+    rs_fill_fused(&g, c);
+    if constexpr (TENSOR) {
+        g.lut = (const uint32_t*)c.tc->t->d_lut;
+        g.cs = (int)c.tc->t->chan_stride, g.rs = (int)c.tc->t->row_stride, g.ps = (int)c.tc->t->pix_stride;   // extent below 2^31 bytes
+        g.extent_bytes = (unsigned)c.tc->extent_bytes;
+    }
+    for (int f0 = 0; f0 < c.frames; f0 += 65535) {
+        const int nf = std::min(65535, c.frames - f0);
+        g.in = c.in + (size_t)f0 * c.in_fs;
+        g.out = c.out + (size_t)f0 * c.out_fs;
+        const dim3 grid(fp.strips * fp.chunks, nf);
+        bool launched = false;
+        rs_dispatch_instance(c.d->channels, fp.K, alpha, [&](auto ch, auto k, auto a) {
+            if constexpr (!decltype(a)::value || BPS == 1) {   // alpha is 8-bit only (resize_validate)
+                hipLaunchKernelGGL((k_rs_fused<S, decltype(ch)::value, decltype(k)::value, decltype(a)::value, TENSOR>), grid,
+                                   dim3(kRsThreads), fp.lds, c.stream, g);
+                launched = true;
+            }
+        });
+        if (!launched) return hipErrorInvalidValue;
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+// each is instantiated, with its kernels, by the translation unit named at the head of this file
+extern template hipError_t rs_launch_fused<1, false>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<1, true>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<2, false>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<4, false>(const RsFusedLaunch&);
 
 }  // namespace lz

@@ -127,44 +127,7 @@ hipError_t rs_to_tensor_launch(const uint8_t* src, size_t src_fs, uint8_t* out, 
     return hipSuccess;
 }
 
-hipError_t rs_tensor_launch_fused(const lanczos_resize_desc* d, const RsFusedPlan& fp, const ResizeAxis* H, const ResizeAxis* V,
-                                  const uint8_t* in, uint8_t* out, size_t in_fs, size_t out_fs, int frames,
-                                  const RsTensorCall& tc, hipStream_t stream) {
-    const bool alpha = (d->reserved[0] & LANCZOS_RESIZE_ALPHA) != 0;
-    RsFusedTensor g{};
-    g.in_pitch = d->in_w * d->channels;
-    g.out_pitch = d->out_w * d->channels;
-    g.in_h = d->in_h, g.out_w = d->out_w, g.out_h = d->out_h;
-    g.in_fs = in_fs, g.out_fs = out_fs;
-    g.hf = H->first(), g.hc = H->count(), g.hk = H->coeffs(), g.hks = H->host.ksize;
-    g.vf = V->first(), g.vc = V->count(), g.vk = V->coeffs(), g.vks = V->host.ksize;
-    g.strips = fp.strips, g.rows_per_chunk = fp.rows_per_chunk;
-    g.ring_rows = fp.ring_rows, g.stage_rows = fp.stage_rows, g.stage_dw = fp.stage_dw;
-    g.lut = (const uint32_t*)tc.t->d_lut;
-    g.cs = (int)tc.t->chan_stride, g.rs = (int)tc.t->row_stride, g.ps = (int)tc.t->pix_stride;   // extent below 2^31 bytes
-    g.extent_bytes = (unsigned)tc.extent_bytes;
-    for (int f0 = 0; f0 < frames; f0 += 65535) {
-        const int nf = std::min(65535, frames - f0);
-        g.in = in + (size_t)f0 * in_fs;
-        g.out = out + (size_t)f0 * out_fs;
-        const dim3 grid(fp.strips * fp.chunks, nf);
-        bool launched = false;
-#define X(KB)                                                                                                                  \
-    if (!launched && fp.K == KB) {                                                                                             \
-        if (d->channels == 1) hipLaunchKernelGGL((k_rs_fused<1, KB, false, true>), grid, dim3(kRsThreads), fp.lds, stream, g); \
-        else if (d->channels == 3)                                                                                             \
-            hipLaunchKernelGGL((k_rs_fused<3, KB, false, true>), grid, dim3(kRsThreads), fp.lds, stream, g);                   \
-        else if (alpha) hipLaunchKernelGGL((k_rs_fused<4, KB, true, true>), grid, dim3(kRsThreads), fp.lds, stream, g);        \
-        else hipLaunchKernelGGL((k_rs_fused<4, KB, false, true>), grid, dim3(kRsThreads), fp.lds, stream, g);                  \
-        launched = true;                                                                                                       \
-    }
-        LZ_RS_BUCKETS(X)
-#undef X
-        if (!launched) return hipErrorInvalidValue;
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
+// the TENSOR instances of k_rs_fused: every tap-count bucket x C = 1, 3, 4 and alpha
+template hipError_t rs_launch_fused<1, true>(const RsFusedLaunch&);
 
 }  // namespace lz

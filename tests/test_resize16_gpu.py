@@ -110,7 +110,7 @@ H_KSIZE = {5: (2, 200), 7: (3, 200), 9: (4, 200), 11: (3, 392), 13: (3, 496), 15
 
 
 def test_every_fused_instance(ctx):
-    """k_rs16_fused<C, K> for every C in {1, 3, 4} and K in {7, 9, 11, 13, 17, 25}, at both edges of the buckets, a = 2, 3, 4,
+    """k_rs_fused<RsSample<2>, C, K> for every C in {1, 3, 4} and K in {7, 9, 11, 13, 17, 25}, at both edges of the buckets, a = 2, 3, 4,
     each with a vertical upscale and a vertical reduction, against the model on all three paths."""
     ow, ih = 261, 60
     seen = set()

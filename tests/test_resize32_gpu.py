@@ -140,7 +140,7 @@ def _hks(iw, ow, a):
 
 
 def test_every_fused_instance(ctx):
-    """k_rs32_fused<C, K> for every C in {1, 3, 4} and K in {7, 9, 11, 13, 17, 25}, at both edges of the buckets, a = 2, 3, 4,
+    """k_rs_fused<RsSample<4>, C, K> for every C in {1, 3, 4} and K in {7, 9, 11, 13, 17, 25}, at both edges of the buckets, a = 2, 3, 4,
     each with a vertical upscale (67 rows: more than one chunk of 32, ragged 8-row steps) and a vertical reduction, against
     the model on all three paths.  Below a bucket's K the padded taps meet real neighbours: the frames carry inf and NaN."""
     ow, ih = 261, 60

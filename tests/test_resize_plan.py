@@ -180,3 +180,28 @@ def test_plan_query_validation():
     assert lib.lanczos_resize_plan_host(None, 1, ctypes.byref(p)) == L.ERR_BAD_ARG
     d.channels = 2
     assert lib.lanczos_resize_plan_host(ctypes.byref(d), 1, ctypes.byref(p)) == L.ERR_BAD_ARG
+
+
+# horizontal ksize -> (filter, a, in_w) at out_w = 261 (tests/test_resize*_gpu.py's instance shapes), and the tap count of the
+# fused instance it runs on (0: two passes).  A box or bilinear upscale has 3 taps and a bicubic one 5, and only they run on
+# the instances of 3 and 5; a Lanczos request pads to 7 at least, and 27 taps are more than any instance holds.
+H_KSIZE_K = [(3, "box", 3, 200, 3), (3, "bilinear", 3, 200, 3), (5, "bicubic", 3, 200, 5), (5, "lanczos", 2, 200, 7),
+             (7, "lanczos", 3, 200, 7), (9, "lanczos", 4, 200, 9), (11, "lanczos", 3, 392, 11), (13, "lanczos", 3, 496, 13),
+             (15, "lanczos", 3, 574, 17), (17, "lanczos", 4, 496, 17), (19, "lanczos", 3, 757, 25), (21, "lanczos", 3, 835, 25),
+             (23, "lanczos", 3, 913, 25), (25, "lanczos", 3, 1018, 25), (27, "lanczos", 3, 1100, 0)]
+
+
+@pytest.mark.parametrize("channels", [1, 3, 4])
+def test_one_bucket_list_for_every_sample_width(channels):
+    """The 8-bit, LANCZOS_RESIZE_U16 and LANCZOS_RESIZE_F32 descriptor of one shape run on the fused instance of the same tap
+    count, or all three on two passes: horizontal ksize 3, 5, ..., 27 over the filters that reach them."""
+    assert [r[0] for r in H_KSIZE_K if r[1] == "lanczos"] == list(range(5, 28, 2))
+    ow, ih, oh = 261, 60, 67
+    for hk, filt, a, iw, want in H_KSIZE_K:
+        widths = {"u8": dict(), "u16": dict(bits=16), "f32": dict(f32=True)}
+        assert L.resize_taps_host(L.resize_desc(iw, 1, ow, 1, 1, a, filter=filt), 0)[2].shape[1] == hk   # the public query
+        got = {}
+        for name, kw in widths.items():
+            p = L.resize_plan_host(L.resize_desc(iw, ih, ow, oh, channels, a, filter=filt, **kw))
+            got[name] = p.K if p.fused else 0
+        assert got == {"u8": want, "u16": want, "f32": want}, (hk, filt, a, got)
