@@ -4,7 +4,9 @@ strides on a non-default stream, first use inside stream capture, and the CLI.  
 edges of the fused march, saturating content, more than 65 535 frames and the bounded axis cache are covered on small frames
 (the numpy model is the cost), with the coverage asserted through the plan query (lanczos_resize_plan_host).
 
-TODO: frames of 2 GiB and more (the 32-bit-offset fallback to two-pass) are not run here: the numpy model is too slow for one."""
+Frames of 2 GiB and more (the 32-bit-offset fallback to two-pass), the largest frames the fused kernel accepts, frame strides
+of 4 GiB and the launchers this file's 65 537 frames do not reach are run by tests/test_resize_wide_addresses_gpu.py, against a
+reference that applies the numpy models to the window of the source a request reads (tests/resize_window_model.py)."""
 import os
 import struct
 import subprocess

@@ -152,8 +152,9 @@ def test_plan_invariants_over_the_sweep(channels, a):
         4 3 |   604   164      2     424  128
         4 4 |   564   164      2     470  122
 
-    (one channel: 65535 x 32768 stays below 2^31 bytes, so `bytes` cannot occur there.)  Every outcome must occur, so that no
-    branch of the planner leaves the sweep unnoticed."""
+    (one channel: 65535 x 32768 stays below 2^31 bytes, so `bytes` does not occur there in this sweep.  It can occur: at
+    65535 x 32769, which test_frames_at_the_2_gib_edge plans.)  Every outcome must occur, so that no branch of the planner
+    leaves the sweep unnoticed."""
     shapes = sweep_shapes()
     hs = {(s[0], s[2]) for s in shapes}
     vs = {(s[1], s[3]) for s in shapes}
@@ -205,3 +206,70 @@ def test_one_bucket_list_for_every_sample_width(channels):
             p = L.resize_plan_host(L.resize_desc(iw, ih, ow, oh, channels, a, filter=filt, **kw))
             got[name] = p.K if p.fused else 0
         assert got == {"u8": want, "u16": want, "f32": want}, (hk, filt, a, got)
+
+
+# ---- the 2^31-byte edge, beyond the sweep -----------------------------------------------------------------------------------
+# (name, in_w, in_h, channels, descriptor keywords, bytes per sample): frames of 2^31 bytes or more, two of them through the
+# sample width alone.  tests/test_resize_wide_addresses_gpu.py runs them.
+FRAMES_2GIB = [("u8c1", 65535, 32769, 1, {}, 1), ("u8c4", 32768, 16385, 4, {}, 1), ("rgba", 32768, 16385, 4, {"alpha": True}, 1),
+               ("u16c3", 32768, 10923, 3, {"bits": 16}, 2), ("f32c3", 16384, 10923, 3, {"f32": True}, 4)]
+OUT_EDGE = (173, 131)
+
+
+def corner_box(in_w, in_h):
+    """about 197 x 149 source pixels in the bottom-right corner, fractional on every side"""
+    return (in_w - 200.25, in_h - 150.5, in_w - 3.0, in_h - 1.75)
+
+
+def largest_fused_frame(bytes_per_pixel):
+    """(in_w, in_h) with the most bytes the fused kernel admits (in_w * in_h * bytes_per_pixel + 4 < 2^31), both sides in
+    1024 .. 65535: a short search over the heights."""
+    limit = (2 ** 31 - 5) // bytes_per_pixel
+    best = (0, 0, 0)
+    for h in range(1024, 65536):
+        w = min(65535, limit // h)
+        if w >= 1024 and w * h > best[0]:
+            best = (w * h, w, h)
+    return best[1], best[2]
+
+
+def frames_below_2gib():
+    """(name, in_w, in_h, channels, descriptor keywords, bytes per sample) of the largest frames the fused kernel accepts"""
+    return [("u8c4", 32766, 16385, 4, {}, 1), ("rgba", 32766, 16385, 4, {"alpha": True}, 1), ("u8c1", 65535, 32768, 1, {}, 1),
+            ("u16c3",) + largest_fused_frame(6) + (3, {"bits": 16}, 2), ("f32c3",) + largest_fused_frame(12) + (3, {"f32": True}, 4)]
+
+
+def bytes_reason(in_w, in_h, out_w, out_h, channels, bps):
+    """the `bytes` reason of two_pass_reasons for any sample width"""
+    return in_w * in_h * channels * bps + 4 >= 2 ** 31 or out_w * out_h * channels * bps >= 2 ** 31
+
+
+def test_frames_at_the_2_gib_edge():
+    """What the sweep cannot reach.  A frame of 2^31 bytes or more plans two passes for the `bytes` reason and no other: with
+    the corner box the taps are few and the ring small, and the largest frame below the limit -- the same request but for a
+    row, a column or a few of them -- plans fused.  That holds for one channel too (65535 x 32769, as input and as output), and
+    for 16-bit and float frames, which cross 2^31 bytes through the sample width."""
+    ow, oh = OUT_EDGE
+    for name, iw, ih, c, kw, bps in FRAMES_2GIB:
+        d = L.resize_desc(iw, ih, ow, oh, c, **kw)
+        assert iw * ih * c * bps >= 2 ** 31 and bytes_reason(iw, ih, ow, oh, c, bps), name
+        p = L.resize_plan_host(d, 1, box=corner_box(iw, ih))
+        assert p.pass_h and p.pass_v and not p.inner.fused and p.mid_rows == 153, (name, p.mid_rows)
+        assert (p.inner.K, p.inner.strips, p.inner.lds_bytes) == (0, 0, 0), name
+    for name, iw, ih, c, kw, bps in frames_below_2gib():
+        assert 2 ** 31 - 32768 <= iw * ih * c * bps <= 2 ** 31 - 5 and not bytes_reason(iw, ih, ow, oh, c, bps), (name, iw, ih)
+        for w in (ow, 261):
+            d = L.resize_desc(iw, ih, w, oh, c, **kw)
+            p = L.resize_plan_host(d, 1, box=corner_box(iw, ih))
+            hks = L.resize_taps_host(d, 0, box=corner_box(iw, ih))[2].shape[1]      # 9 taps down to 173, 7 up to 261
+            assert hks == (9 if w == ow else 7)
+            assert p.pass_h and p.pass_v and p.inner.fused and p.inner.K == hks, (name, w, p.inner.K)
+    assert largest_fused_frame(6) == (57404, 6235) and largest_fused_frame(12) == (54610, 3277)
+    # the whole frame, no box: 65535 x 32769 as a one-channel input, through check_plan like the sweep's shapes
+    assert "bytes" in two_pass_reasons(65535, 32769, 60000, 30000, 1, 3)
+    assert not L.resize_plan_host(L.resize_desc(65535, 32769, 60000, 30000, 1, 3), 1).fused
+    assert check_plan((65535, 32768, 60000, 30000), 1, 3, 1) == "fused"
+    # ... and as a one-channel output: an upscale of 7 taps whose ring is a few rows -- `bytes` is the only reason
+    assert two_pass_reasons(40, 30, 65535, 32769, 1, 3) == ["bytes"]
+    assert check_plan((40, 30, 65535, 32769), 1, 3, 1) == "bytes"
+    assert check_plan((40, 30, 65535, 32768), 1, 3, 1) == "fused"
