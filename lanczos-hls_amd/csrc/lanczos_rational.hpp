@@ -600,11 +600,19 @@ inline void ratp_prepare(const lanczos_desc& d, const AxisTaps& H, const AxisTap
         if (ax->out_n > N * (a + 2) && ax->in_n > 2 * a + D + 2) ref_ax = ax;
     if (!ref_ax) return;
     for (int i = 0; i < 8 * kMaxTaps; i++) p->phase_w[i] = 0.0f;
-    const int o_ref = N * (a + 1);   // an interior period: every tap in range
+    // The weights of a phase, from build_axis's own expression at the period that starts at o_ref but WITHOUT its clipping: on
+    // an axis of 2a + D + 3 input samples that period's last taps lie beyond the frame, the table holds zeros there, and a
+    // phase table read from it sent every such frame to k_rat through the deviation below.  Where the taps are in range the
+    // values are the table's, bit for bit.
+    const int o_ref = N * (a + 1);
+    const double SCALE = (double)N / D;
+    auto w_ref = [&](int o, int k) {
+        const double x = (double)o / SCALE;
+        return kernel(x - ((int)std::floor(x) - a + 1 + k), a);
+    };
     for (int ph = 0; ph < N; ph++)   // phases above N/2 are the mirror images of those below (what the kernel reads)
         for (int k = 0; k < taps; k++)
-            p->phase_w[ph * kMaxTaps + k] = ph <= N / 2 ? (float)ref_ax->w[(size_t)(o_ref + ph) * taps + k]
-                                                        : (float)ref_ax->w[(size_t)(o_ref + N - ph) * taps + (taps - 1 - k)];
+            p->phase_w[ph * kMaxTaps + k] = ph <= N / 2 ? (float)w_ref(o_ref + ph, k) : (float)w_ref(o_ref + N - ph, taps - 1 - k);
     double dev = 0;
     auto check = [&](const AxisTaps& ax, const std::vector<uint8_t>& fl) {
         for (int o = 0; o < ax.out_n; o++) {

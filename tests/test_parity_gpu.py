@@ -197,16 +197,20 @@ RATIONAL_SHAPES = [
 ]
 
 
-# the instances of k_ratp (lanczos_rational.hpp LZ_RATP_CONFIGS): (bytes per sample, channels, N, D, a)
-RATP_INSTANCES = {(1, 3, 4, 3, 3), (1, 3, 3, 2, 3), (1, 3, 5, 2, 3), (1, 3, 5, 4, 3), (1, 4, 4, 3, 3), (1, 4, 3, 2, 3), (1, 1, 4, 3, 3),
-                  (1, 1, 3, 2, 3), (1, 3, 4, 3, 2), (1, 3, 3, 2, 2), (2, 4, 3, 2, 3)}
+# the instances of k_ratp (lanczos_rational.hpp LZ_RATP_CONFIGS) as (bytes per sample, channels, N, D, a): tests/ratp_cfg.py
+# holds the one list, tests/test_rational_instances.py compares it with the header
+from ratp_cfg import RATP_INSTANCES  # noqa: E402
 
 
 @pytest.mark.parametrize("mode", [L.MODE_EXACT, L.MODE_LSB1])
 @pytest.mark.parametrize("pattern", ["noise", "dark", "gradient", "blocks"])
 def test_rational_scales_fast_kernel(ctx, pattern, mode):
     """4/3, 3/2, 5/2, 5/3, 7/4: the reference reduces SCALE_N/SCALE_D with gcd (lanczos.h:108-114) and evaluates
-    x = xx / SCALE in double; the f32 tile kernel follows its per-index taps."""
+    x = xx / SCALE in double; k_rat follows its per-index taps, k_ratp serves the frames the host found periodic.
+    Of k_ratp's 11 instances these shapes reach three -- (u8, C, N, D, a) = (3, 4, 3, 3) at 300 x 200 and 1200 x 40, (3, 3, 2, 3)
+    at 256 x 120, (1, 3, 2, 3) at 64 x 300 -- and the 16-bit tail a fourth, (u16, 4, 3, 2, 3); of k_rat's six (sample type, a)
+    pairs they reach uint8 with a = 2, 3, 4.  Every instance of both families, in both modes, on multi-tile ragged frames, in
+    strips and in strided batches: tests/test_rational_instances_gpu.py."""
     for (w, h, c, sn, sd, a) in RATIONAL_SHAPES:
         img = P.ALL_U8[pattern](h, w, c)
         want = _oracle(img, sn, sd, a)
