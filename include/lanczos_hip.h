@@ -461,6 +461,43 @@ int lanczos_resize_tensor_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, c
  * LANCZOS_TENSOR_CONVERTED */
 int lanczos_last_tensor_route(const lanczos_ctx* ctx);
 
+/* ---- ... into a bfloat16 or float16 tensor (the pipeline above followed by .to(torch.bfloat16) / .to(torch.float16)) ----
+ * lanczos_resize_tensor_*'s contract with "float" read as "16-bit element":
+ *   out[f][c * chan_stride + y * row_stride + x * pix_stride] = lut[c * 256 + P(f, y, x, c)]
+ * with out and lut of 16-bit words, strides in ELEMENTS (2 bytes) and P the byte of the byte request.  The words are moved and
+ * never computed on, so one entry serves bfloat16, float16 and any other 16-bit pointwise map of an 8-bit sample; zeros,
+ * subnormals, NaN and inf patterns arrive unchanged.  A table of float32 entries rounded to nearest-even
+ * (lanczos_tensor_lut_convert16) gives what torch's cast of the float32 tensor gives, bit for bit.  Elements the strides do not
+ * name are not written: a 16-bit neighbour of a stored element keeps its contents.  The table's lifetime, the overlap rule,
+ * the stride cap, the routes (fused where the byte request is and an element frame spans less than 2^31 bytes, else converted),
+ * lanczos_last_tensor_route, lanczos_last_kernel, lanczos_resize_force and the scratch and capture rules are the float
+ * entry's.  The element width has a struct of its own since lanczos_tensor_out's reserved words must be 0. */
+typedef struct lanczos_tensor16_out {
+    const uint16_t* d_lut;  /* device: channels * 256 16-bit words, lut[c * 256 + v]; read when the kernels run */
+    int64_t chan_stride, row_stride, pix_stride;   /* in ELEMENTS (2 bytes), each > 0 */
+    int32_t reserved[4];    /* must be 0 */
+} lanczos_tensor16_out;
+#define LANCZOS_TENSOR_BF16 1   /* formats of the two table functions; a request carries none */
+#define LANCZOS_TENSOR_F16 2
+/* as lanczos_resize_tensor_validate */
+int lanczos_resize_tensor16_validate(const lanczos_resize_desc* d, const lanczos_tensor16_out* t);
+/* Host only: n float32 values to words of `format`, round to nearest, ties to even, as torch's CPU cast.  bfloat16:
+ * (bits + 0x7FFF + ((bits >> 16) & 1)) >> 16.  float16: IEEE binary16, subnormals kept, overflow to +-inf.  A NaN becomes
+ * some NaN of the format.  LANCZOS_ERR_BAD_ARG: a NULL pointer, n < 0, an unknown format. */
+int lanczos_tensor_lut_convert16(const float* in, int n, int format, uint16_t* out);
+/* Host only: lanczos_tensor_lut_normalize followed by lanczos_tensor_lut_convert16 --
+ * uint8.to(float32).div(255).sub(mean).div(std).to(bfloat16 or float16), bit for bit. */
+int lanczos_tensor16_lut_normalize(int channels, const float* mean, const float* std, int format, uint16_t* lut);
+/* As lanczos_resize_tensor_device with 16-bit frames at d_out: d_out and out_frame_stride (bytes) are multiples of 2, the
+ * frame's extent is ((channels - 1) * chan_stride + (out_h - 1) * row_stride + (out_w - 1) * pix_stride + 1) * 2 bytes. */
+int lanczos_resize_tensor16_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                   const lanczos_tensor16_out* t, const void* d_in, void* d_out, int frames,
+                                   size_t in_frame_stride, size_t out_frame_stride, void* stream);
+/* As lanczos_resize_tensor_host: a HOST table in t->d_lut, 16-bit frames one extent apart; synchronous.  Elements of `out` the
+ * strides do not name keep their contents. */
+int lanczos_resize_tensor16_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                 const lanczos_tensor16_out* t, const void* in, void* out, int frames);
+
 /* ---- reduce by whole factors (Pillow's Image.reduce((fx, fy), box), an exact integer box average) ----
  * 8-bit, 1, 3 or 4 independent interleaved channels.  box = (x0, y0, x1, y1), integers with 0 <= x0 < x1 <= in_w and the same
  * for y; NULL = the whole frame.  The output is ceil((x1 - x0) / fx) x ceil((y1 - y0) / fy) pixels, tightly packed rows.

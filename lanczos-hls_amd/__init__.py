@@ -38,6 +38,8 @@ RESIZE_F32 = 16    # flag of lanczos_resize_desc.reserved[0]: float samples (Pil
 FILTER_LANCZOS, FILTER_BOX, FILTER_BILINEAR, FILTER_HAMMING, FILTER_BICUBIC, FILTER_NEAREST = range(6)
 FILTER_NAMES = ("lanczos", "box", "bilinear", "hamming", "bicubic", "nearest")
 TENSOR_FUSED, TENSOR_CONVERTED = 1, 2   # lanczos_last_tensor_route: who wrote the floats of the last tensor call
+TENSOR_BF16, TENSOR_F16 = 1, 2          # the formats of lanczos_tensor_lut_convert16 / lanczos_tensor16_lut_normalize
+_TENSOR16_FORMATS = {"bfloat16": TENSOR_BF16, "float16": TENSOR_F16}
 
 # every symbol include/lanczos_hip.h declares (tests check the library exports exactly these)
 ABI_SYMBOLS = [
@@ -61,6 +63,8 @@ ABI_SYMBOLS = [
     "lanczos_reduce_size", "lanczos_reduce_device", "lanczos_reduce_host",
     "lanczos_resize_tensor_validate", "lanczos_tensor_lut_normalize", "lanczos_resize_tensor_device",
     "lanczos_resize_tensor_host", "lanczos_last_tensor_route",
+    "lanczos_resize_tensor16_validate", "lanczos_tensor_lut_convert16", "lanczos_tensor16_lut_normalize",
+    "lanczos_resize_tensor16_device", "lanczos_resize_tensor16_host",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
 
@@ -129,6 +133,12 @@ class TensorOut(ctypes.Structure):
     x * pix_stride] = lut[c * 256 + byte], strides in floats."""
     _fields_ = [("d_lut", ctypes.c_void_p), ("chan_stride", ctypes.c_int64), ("row_stride", ctypes.c_int64),
                 ("pix_stride", ctypes.c_int64), ("reserved", ctypes.c_int32 * 4)]
+
+
+class TensorOut16(ctypes.Structure):
+    """lanczos_tensor16_out -- TensorOut for 16-bit elements (bfloat16 or float16 words): the table is channels * 256 16-bit
+    words, strides in elements."""
+    _fields_ = TensorOut._fields_
 
 
 _LIB = None
@@ -235,6 +245,14 @@ def _lib():
                                                        c_void_p]
             L.lanczos_resize_tensor_host.argtypes = [c_void_p, PRD, PRO, PTO, c_void_p, c_void_p, c_int]
             L.lanczos_last_tensor_route.argtypes = [c_void_p]
+        if hasattr(L, "lanczos_resize_tensor16_device"):   # (nor the 16-bit one)
+            PTO16 = ctypes.POINTER(TensorOut16)
+            L.lanczos_resize_tensor16_validate.argtypes = [PRD, PTO16]
+            L.lanczos_tensor_lut_convert16.argtypes = [c_void_p, c_int, c_int, c_void_p]
+            L.lanczos_tensor16_lut_normalize.argtypes = [c_int, c_void_p, c_void_p, c_int, c_void_p]
+            L.lanczos_resize_tensor16_device.argtypes = [c_void_p, PRD, PRO, PTO16, c_void_p, c_void_p, c_int, c_size_t,
+                                                         c_size_t, c_void_p]
+            L.lanczos_resize_tensor16_host.argtypes = [c_void_p, PRD, PRO, PTO16, c_void_p, c_void_p, c_int]
         L.lanczos_strerror.restype = ctypes.c_char_p
         L.lanczos_version.argtypes = []
         L.lanczos_version.restype = ctypes.c_char_p
@@ -394,9 +412,32 @@ def resize_plan_host(desc, frames=1, box=None, reducing_gap=None, opts=None):
     return p
 
 
-def normalize_lut(channels, mean=None, std=None):
+def _tensor16_format(dtype, what):
+    if dtype not in _TENSOR16_FORMATS:
+        raise LanczosError(ERR_BAD_ARG, f"{what}: dtype is 'float32', 'bfloat16' or 'float16', not {dtype!r}")
+    return _TENSOR16_FORMATS[dtype]
+
+
+def _tensor16_array(words, dtype):
+    """the words of a 16-bit table or tensor as the caller sees them: np.float16, or the bfloat16 patterns as np.uint16"""
+    return words.view(np.float16) if dtype == "float16" else words
+
+
+def lut_convert16(array, dtype):
+    """float32 values -> "bfloat16" (np.uint16 holding the patterns: numpy has no bfloat16) or "float16" (np.float16) of the
+    same shape, rounded to nearest-even as torch's .to(torch.bfloat16) / .to(torch.float16) rounds on the CPU."""
+    a = np.ascontiguousarray(array, dtype=np.float32)
+    out = np.empty(a.shape, dtype=np.uint16)
+    _check(_lib().lanczos_tensor_lut_convert16(a.ctypes.data, a.size, _tensor16_format(dtype, "lut_convert16"),
+                                               out.ctypes.data), "lanczos_tensor_lut_convert16")
+    return _tensor16_array(out, dtype)
+
+
+def normalize_lut(channels, mean=None, std=None, dtype="float32"):
     """The table of ToTensor() + Normalize(mean, std) as float32 [channels][256]: ((float)v / 255 - mean[c]) / std[c] in IEEE
-    float, bit for bit torch's uint8.to(float32).div(255).sub(mean).div(std).  mean=None is 0, std=None is 1."""
+    float, bit for bit torch's uint8.to(float32).div(255).sub(mean).div(std).  mean=None is 0, std=None is 1.
+    dtype="bfloat16" / "float16": that table rounded as lut_convert16 rounds it (np.uint16 patterns / np.float16), bit for bit
+    torch's .to(torch.bfloat16) / .to(torch.float16) of the float32 result."""
     def arr(v, what):
         if v is None:
             return None
@@ -405,6 +446,13 @@ def normalize_lut(channels, mean=None, std=None):
             raise LanczosError(ERR_BAD_ARG, f"normalize_lut: {what} is one value, or one per channel")
         return np.ascontiguousarray(np.broadcast_to(a, (channels,)))
     m, s = arr(mean, "mean"), arr(std, "std")
+    if dtype != "float32":
+        lut = np.empty((channels, 256), dtype=np.uint16)
+        _check(_lib().lanczos_tensor16_lut_normalize(channels, m.ctypes.data if m is not None else None,
+                                                     s.ctypes.data if s is not None else None,
+                                                     _tensor16_format(dtype, "normalize_lut"), lut.ctypes.data),
+               "lanczos_tensor16_lut_normalize")
+        return _tensor16_array(lut, dtype)
     lut = np.empty((channels, 256), dtype=np.float32)
     _check(_lib().lanczos_tensor_lut_normalize(channels, m.ctypes.data if m is not None else None,
                                                s.ctypes.data if s is not None else None, lut.ctypes.data),
@@ -413,7 +461,7 @@ def normalize_lut(channels, mean=None, std=None):
 
 
 def tensor_strides(layout, out_w, out_h, channels):
-    """(chan_stride, row_stride, pix_stride) in floats of a tightly packed "chw" or "hwc" frame."""
+    """(chan_stride, row_stride, pix_stride) in elements of a tightly packed "chw" or "hwc" frame."""
     if layout == "chw":
         return out_h * out_w, out_w, 1
     if layout == "hwc":
@@ -428,6 +476,21 @@ def tensor_out(d_lut, strides):
     t.d_lut = d_lut
     t.chan_stride, t.row_stride, t.pix_stride = (int(v) for v in strides)
     return t
+
+
+def tensor16_out(d_lut, strides):
+    """A TensorOut16: d_lut a pointer to channels * 256 16-bit words (device memory for the device entry), strides =
+    (chan_stride, row_stride, pix_stride) in elements.  Validated where it is used (resize_tensor16_validate)."""
+    t = TensorOut16()
+    t.d_lut = d_lut
+    t.chan_stride, t.row_stride, t.pix_stride = (int(v) for v in strides)
+    return t
+
+
+def resize_tensor16_validate(desc, t):
+    """lanczos_resize_tensor16_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the request is refused."""
+    _check(_lib().lanczos_resize_tensor16_validate(ctypes.byref(desc), ctypes.byref(t) if t is not None else None),
+           "lanczos_resize_tensor16_validate")
 
 
 def resize_tensor_validate(desc, t):
@@ -633,11 +696,18 @@ class Context:
 
     # -- resize straight into a float tensor (PIL.Image.resize -> ToTensor() -> Normalize(), lanczos_resize_tensor_*)
     def resize_tensor(self, img, out_w, out_h, mean=None, std=None, lut=None, layout="chw", a=3, alpha=False, box=None,
-                      reducing_gap=None, filter=FILTER_LANCZOS):
+                      reducing_gap=None, filter=FILTER_LANCZOS, dtype="float32"):
         """img: uint8 [H][W], [H][W][C] or [F][H][W][C] as Context.resize takes it -> float32 [F][C][H][W] (layout="chw") or
         [F][H][W][C] ("hwc"), the frame axis dropped as resize drops it: lut[c][byte] of the bytes Context.resize returns for
         the same arguments.  lut: float32 [C][256], moved bit for bit; None = normalize_lut(C, mean, std), with which the
-        result is bit for bit torch.from_numpy(bytes).permute(2, 0, 1).float().div(255).sub(mean).div(std)."""
+        result is bit for bit torch.from_numpy(bytes).permute(2, 0, 1).float().div(255).sub(mean).div(std).
+        dtype="float16" returns np.float16 and dtype="bfloat16" np.uint16 holding the bfloat16 patterns (numpy has no
+        bfloat16; torch.from_numpy(a.view(np.int16)).view(torch.bfloat16) is the tensor), with normalize_lut(..., dtype=)
+        bit for bit the float32 pipeline followed by .to(torch.float16) / .to(torch.bfloat16).  lut is then uint16 or float16
+        [C][256], moved bit for bit."""
+        wide = dtype == "float32"
+        if not wide:
+            _tensor16_format(dtype, "resize_tensor")
         img = np.ascontiguousarray(img)
         if img.dtype != np.uint8 or img.ndim not in (2, 3, 4):
             raise LanczosError(ERR_BAD_ARG, "resize_tensor: expected a uint8 [H][W], [H][W][C] or [F][H][W][C] array")
@@ -646,25 +716,44 @@ class Context:
         f, h, w, c = x.shape
         d = resize_desc(w, h, out_w, out_h, c, a, alpha, filter=filter)
         if lut is None:
-            lut = normalize_lut(c, mean, std)
+            lut = normalize_lut(c, mean, std, dtype)
         elif mean is not None or std is not None:
             raise LanczosError(ERR_BAD_ARG, "resize_tensor: a table or mean / std, not both")
         lut = np.ascontiguousarray(lut)
-        if lut.dtype != np.float32 or lut.size != c * 256:
-            raise LanczosError(ERR_BAD_ARG, f"resize_tensor: the table is float32 [{c}][256]")
-        t = tensor_out(lut.ctypes.data, tensor_strides(layout, out_w, out_h, c))
-        out = np.empty((f, c, out_h, out_w) if layout == "chw" else (f, out_h, out_w, c), dtype=np.float32)
-        _check(_lib().lanczos_resize_tensor_host(self._h, ctypes.byref(d), _opts_ref(d, box, reducing_gap, None),
-                                                 ctypes.byref(t), x.ctypes.data, out.ctypes.data, f),
-               "lanczos_resize_tensor_host")
+        if lut.dtype not in ((np.float32,) if wide else (np.uint16, np.float16)) or lut.size != c * 256:
+            raise LanczosError(ERR_BAD_ARG, f"resize_tensor: the table is {'float32' if wide else 'uint16 or float16'} [{c}][256]")
+        strides = tensor_strides(layout, out_w, out_h, c)
+        shape = (f, c, out_h, out_w) if layout == "chw" else (f, out_h, out_w, c)
+        opts = _opts_ref(d, box, reducing_gap, None)
+        if wide:
+            t = tensor_out(lut.ctypes.data, strides)
+            out = np.empty(shape, dtype=np.float32)
+            _check(_lib().lanczos_resize_tensor_host(self._h, ctypes.byref(d), opts, ctypes.byref(t), x.ctypes.data,
+                                                     out.ctypes.data, f), "lanczos_resize_tensor_host")
+        else:
+            t = tensor16_out(lut.ctypes.data, strides)
+            out = np.empty(shape, dtype=np.uint16)
+            _check(_lib().lanczos_resize_tensor16_host(self._h, ctypes.byref(d), opts, ctypes.byref(t), x.ctypes.data,
+                                                       out.ctypes.data, f), "lanczos_resize_tensor16_host")
+            out = _tensor16_array(out, dtype)
         return out if img.ndim == 4 else out[0]
 
     def resize_tensor_device(self, desc, d_in, d_out, frames, d_lut, strides, in_frame_stride=0, out_frame_stride=0,
-                             stream=None, box=None, reducing_gap=None, opts=None):
+                             stream=None, box=None, reducing_gap=None, opts=None, dtype="float32"):
         """Device pointers, asynchronous on `stream`: uint8 frames at d_in -> float frames at d_out, out_frame_stride in BYTES
         (0 = one frame's extent).  d_lut: device pointer to channels * 256 floats, read when the kernels run (a replayed
         graph sees its contents of that moment).  strides = (chan_stride, row_stride, pix_stride) in floats, e.g.
-        tensor_strides("chw", ...), or a ready TensorOut (d_lut then unused).  box / reducing_gap / opts as resize_device."""
+        tensor_strides("chw", ...), or a ready TensorOut (d_lut then unused).  box / reducing_gap / opts as resize_device.
+        dtype="bfloat16" / "float16" (or a ready TensorOut16): 16-bit elements at d_out and in the table, strides in
+        elements, d_out and out_frame_stride multiples of 2."""
+        if isinstance(strides, TensorOut16) or dtype != "float32":
+            if not isinstance(strides, TensorOut16):
+                _tensor16_format(dtype, "resize_tensor_device")
+            t = strides if isinstance(strides, TensorOut16) else tensor16_out(d_lut, strides)
+            _check(_lib().lanczos_resize_tensor16_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
+                                                         ctypes.byref(t), d_in, d_out, frames, in_frame_stride,
+                                                         out_frame_stride, stream), "lanczos_resize_tensor16_device")
+            return
         t = strides if isinstance(strides, TensorOut) else tensor_out(d_lut, strides)
         _check(_lib().lanczos_resize_tensor_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
                                                    ctypes.byref(t), d_in, d_out, frames, in_frame_stride, out_frame_stride,

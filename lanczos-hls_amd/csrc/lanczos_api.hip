@@ -1206,8 +1206,47 @@ int lanczos_resize_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const vo
     return lanczos_resize_host_ex(ctx, d, nullptr, in, out, frames);
 }
 
+// The float and the 16-bit tensor entries are one request (lz::RsTensorOut) with another element width
+extern "C++" {
+template <class T>
+static int tensor_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts, const T* t, int elem,
+                         const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    lz::RsTensorCall tc;
+    int rc = lz::tensor_validate(d, t, elem, &tc.t);
+    if (rc != LANCZOS_OK) return rc;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
+    route_begin(ctx);
+    tc.extent_bytes = lz::tensor_extent_bytes(d, tc.t);
+    rc = lz::resize_device(ctx->resize, d, opts, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
+                           &ctx->last_kernel, &ctx->last_hip, &tc);
+    ctx->last_tensor_route = tc.route;
+    return rc;
+}
+
+template <class T>
+static int tensor_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts, const T* t, int elem,
+                       const void* in, void* out, int frames) {
+    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    lz::RsTensorOut lay;
+    int rc = lz::tensor_validate(d, t, elem, &lay);
+    if (rc != LANCZOS_OK) return rc;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->stream) return LANCZOS_ERR_HIP;
+    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
+    route_begin(ctx);
+    return lz::resize_tensor_host(ctx->resize, d, opts, lay, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip,
+                                  &ctx->last_tensor_route);
+}
+
+}   // extern "C++"
+
 int lanczos_resize_tensor_validate(const lanczos_resize_desc* d, const lanczos_tensor_out* t) {
-    return lz::tensor_validate(d, t);
+    lz::RsTensorOut lay;
+    return lz::tensor_validate(d, t, 4, &lay);
 }
 
 int lanczos_tensor_lut_normalize(int channels, const float* mean, const float* std, float* lut) {
@@ -1219,33 +1258,39 @@ int lanczos_tensor_lut_normalize(int channels, const float* mean, const float* s
 int lanczos_resize_tensor_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                  const lanczos_tensor_out* t, const void* d_in, void* d_out, int frames,
                                  size_t in_frame_stride, size_t out_frame_stride, void* stream) {
-    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    int rc = lz::tensor_validate(d, t);
-    if (rc != LANCZOS_OK) return rc;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    LZ_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
-    route_begin(ctx);
-    lz::RsTensorCall tc;
-    tc.t = t, tc.extent_bytes = lz::tensor_extent_bytes(d, t);
-    rc = lz::resize_device(ctx->resize, d, opts, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
-                           &ctx->last_kernel, &ctx->last_hip, &tc);
-    ctx->last_tensor_route = tc.route;
-    return rc;
+    return tensor_device(ctx, d, opts, t, 4, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
 }
 
 int lanczos_resize_tensor_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                const lanczos_tensor_out* t, const void* in, void* out, int frames) {
-    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    int rc = lz::tensor_validate(d, t);
-    if (rc != LANCZOS_OK) return rc;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    LZ_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->stream) return LANCZOS_ERR_HIP;
-    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
-    route_begin(ctx);
-    return lz::resize_tensor_host(ctx->resize, d, opts, t, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip,
-                                  &ctx->last_tensor_route);
+    return tensor_host(ctx, d, opts, t, 4, in, out, frames);
+}
+
+int lanczos_resize_tensor16_validate(const lanczos_resize_desc* d, const lanczos_tensor16_out* t) {
+    lz::RsTensorOut lay;
+    return lz::tensor_validate(d, t, 2, &lay);
+}
+
+int lanczos_tensor_lut_convert16(const float* in, int n, int format, uint16_t* out) {
+    if (!in || !out || n < 0) return LANCZOS_ERR_BAD_ARG;
+    return lz::tensor_lut_convert16(in, n, format, out) ? LANCZOS_OK : LANCZOS_ERR_BAD_ARG;
+}
+
+int lanczos_tensor16_lut_normalize(int channels, const float* mean, const float* std, int format, uint16_t* lut) {
+    float f[4 * 256];
+    const int rc = lanczos_tensor_lut_normalize(channels, mean, std, lut ? f : nullptr);
+    return rc != LANCZOS_OK ? rc : lanczos_tensor_lut_convert16(f, channels * 256, format, lut);
+}
+
+int lanczos_resize_tensor16_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                   const lanczos_tensor16_out* t, const void* d_in, void* d_out, int frames,
+                                   size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+    return tensor_device(ctx, d, opts, t, 2, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+}
+
+int lanczos_resize_tensor16_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                 const lanczos_tensor16_out* t, const void* in, void* out, int frames) {
+    return tensor_host(ctx, d, opts, t, 2, in, out, frames);
 }
 
 int lanczos_last_tensor_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_tensor_route : 0; }

@@ -287,7 +287,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_v_alpha(RsPass<int32_t> p) {
 }
 
 // the 8-bit instances of k_rs_fused that store bytes
-template hipError_t rs_launch_fused<1, false>(const RsFusedLaunch&);
+template hipError_t rs_launch_fused<1, 0>(const RsFusedLaunch&);
 
 // the tap count of the smallest fused instance that holds ksize (0: none; small: the instances with 3 and 5 taps count, which
 // they do for every filter but Lanczos)
@@ -517,7 +517,7 @@ static hipError_t rs_launch_pass(int bps, bool horizontal, const ResizeAxis* ax,
 
 // the resize that remains once the options are resolved: `d` describes the frames at `in` (the caller's, or the reduced
 // ones), sh / sv are the source spans of its two axes
-// tc: a tensor request, `out` / `out_fs` then being the float frames.  Where the fused kernel runs it stores them itself;
+// tc: a tensor request, `out` / `out_fs` then being the element frames.  Where the fused kernel runs it stores them itself;
 // everything else writes its bytes to context scratch and k_rs_to_tensor follows
 static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh, RsSpan sv, const uint8_t* in, uint8_t* out,
                         int frames, size_t in_fs, size_t out_fs, hipStream_t stream, int* last_kernel, int* last_hip,
@@ -547,7 +547,7 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     const bool fused_ok = !nearest && need_h && need_v && rs_fused_plan(d, H->host, V->host, frames, &fp);
     if (st->force == LANCZOS_RESIZE_FUSED && !fused_ok) return LANCZOS_ERR_UNSUPPORTED;
     const bool fused = fused_ok && st->force != LANCZOS_RESIZE_TWO_PASS;
-    // 32-bit buffer offsets into the float frame: a larger one is converted, and refused where the fused kernel is forced
+    // 32-bit buffer offsets into the element frame: a larger one is converted, and refused where the fused kernel is forced
     const bool t_fits = tc && tc->extent_bytes < ((size_t)1 << 31);
     if (tc && st->force == LANCZOS_RESIZE_FUSED && !t_fits) return LANCZOS_ERR_UNSUPPORTED;
     const bool t_fused = fused && t_fits && st->force != LANCZOS_RESIZE_CONVERT;
@@ -569,10 +569,10 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     hipError_t e = hipSuccess;
     if (fused) {
         const RsFusedLaunch c{d, &fp, H, V, in, out, in_fs, out_fs, frames, tc, stream};
-        e = t_fused ? rs_launch_fused<1, true>(c)
-            : f32   ? rs_launch_fused<4, false>(c)
-            : u16   ? rs_launch_fused<2, false>(c)
-                    : rs_launch_fused<1, false>(c);
+        e = t_fused ? (tc->t.elem == 2 ? rs_launch_fused<1, 2>(c) : rs_launch_fused<1, 4>(c))
+            : f32   ? rs_launch_fused<4, 0>(c)
+            : u16   ? rs_launch_fused<2, 0>(c)
+                    : rs_launch_fused<1, 0>(c);
         *last_kernel = LANCZOS_KERNEL_RESIZE_FUSED;
     } else if (nearest) {
         e = rs_nearest_launch(in, out, d->in_w, d->out_w, d->out_h, C, (int)B, H->first(), V->first(), frames, in_fs, out_fs,
@@ -604,7 +604,7 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     }
     if (tc) {
         if (!t_fused && e == hipSuccess)
-            e = rs_to_tensor_launch(out, out_fs, t_out, t_fs, d->out_w, d->out_h, C, *tc->t, frames, stream);
+            e = rs_to_tensor_launch(out, out_fs, t_out, t_fs, d->out_w, d->out_h, C, tc->t, frames, stream);
         tc->route = t_fused ? LANCZOS_TENSOR_FUSED : LANCZOS_TENSOR_CONVERTED;
     }
     if (capturing) {   // a live graph may name these tables: they stay until the context goes
@@ -640,7 +640,7 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_r
     const size_t out_fs = out_frame_stride ? out_frame_stride : out_frame;
     if (in_fs < in_frame || out_fs < out_frame) return LANCZOS_ERR_BAD_ARG;
     if ((((uintptr_t)d_in | (uintptr_t)d_out | in_fs | out_fs) & (B - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
-    if (tc && (((uintptr_t)d_out | out_fs) & 3) != 0) return LANCZOS_ERR_BAD_ARG;   // float frames
+    if (tc && (((uintptr_t)d_out | out_fs) & (size_t)(tc->t.elem - 1)) != 0) return LANCZOS_ERR_BAD_ARG;   // element frames
     const uint8_t* in = (const uint8_t*)d_in;
     if (r.reduces()) {   // reducing_gap: reduce into context scratch, then resize the reduced frames
         int rb[4];
@@ -717,21 +717,20 @@ int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_res
     });
 }
 
-// The table rides behind the input frames in the input staging block.  The float frames go up before they come back, so that
-// the words of `out` the strides leave out keep what they held.
-int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_tensor_out* t,
+// The table rides behind the input frames in the input staging block.  The element frames go up before they come back, so
+// that the elements of `out` the strides leave out keep what they held.
+int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const RsTensorOut& t,
                        const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip, int* route) {
-    if (((uintptr_t)out & 3) != 0) return LANCZOS_ERR_BAD_ARG;
+    if (((uintptr_t)out & (uintptr_t)(t.elem - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
     RsTensorCall tc;
+    tc.t = t;
     tc.extent_bytes = tensor_extent_bytes(d, t);
     const size_t in_bytes = (size_t)d->in_w * d->in_h * d->channels * frames;
     RsStagedExtra x;
-    x.table = t->d_lut, x.table_at = (in_bytes + 255) & ~(size_t)255, x.table_bytes = (size_t)d->channels * 256 * sizeof(float);
+    x.table = t.d_lut, x.table_at = (in_bytes + 255) & ~(size_t)255, x.table_bytes = (size_t)d->channels * 256 * t.elem;
     x.out_up = true;
     return rs_staged_call(st, in, in_bytes, out, tc.extent_bytes * frames, x, stream, last_hip, [&] {
-        lanczos_tensor_out dev = *t;
-        dev.d_lut = (const float*)((const uint8_t*)st->stage_in + x.table_at);
-        tc.t = &dev;
+        tc.t.d_lut = (const uint8_t*)st->stage_in + x.table_at;
         const int rc = resize_device(st, d, o, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip, &tc);
         *route = tc.route;
         return rc;

@@ -2,7 +2,8 @@
 // their per-context cache, and the entry points lanczos_api.hip forwards to.  Tables, cache, planning and dispatch are in
 // lanczos_resize.hip.  The kernels are written once for 8-bit, 16-bit (LANCZOS_RESIZE_U16) and float (LANCZOS_RESIZE_F32)
 // samples in lanczos_resize_fused.hpp; the fused instances are compiled by lanczos_resize.hip (8-bit), lanczos_resize_tensor.hip
-// (8-bit into float tensors), lanczos_resize16.hip and lanczos_resize32.hip.  The filter of a request (LANCZOS_RESIZE_FILTER)
+// (8-bit into float tensors), lanczos_resize_tensor16.hip (8-bit into bfloat16 / float16 tensors), lanczos_resize16.hip and
+// lanczos_resize32.hip.  The filter of a request (LANCZOS_RESIZE_FILTER)
 // only changes the tables; LANCZOS_FILTER_NEAREST has index tables and a kernel of its own (lanczos_resize_nearest.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -130,27 +131,43 @@ struct ResizeState {
     ~ResizeState();
 };
 
-// A tensor request (lanczos_tensor_out, lanczos_resize_tensor.hip): d_out and out_frame_stride of resize_device are then those
-// of the float frames.  route: out, LANCZOS_TENSOR_FUSED or LANCZOS_TENSOR_CONVERTED once the launches are out.
+// The table and the layout of a tensor request, whatever its element: lanczos_tensor_out (elem 4, floats) and
+// lanczos_tensor16_out (elem 2, bfloat16 or float16 words) are both this.  Strides in elements.
+struct RsTensorOut {
+    const void* d_lut = nullptr;   // channels * 256 elements
+    int64_t chan_stride = 0, row_stride = 0, pix_stride = 0;
+    int elem = 4;                  // bytes of an element
+};
+// A tensor request (lanczos_resize_tensor.hip): d_out and out_frame_stride of resize_device are then those of the element
+// frames.  route: out, LANCZOS_TENSOR_FUSED or LANCZOS_TENSOR_CONVERTED once the launches are out.
 struct RsTensorCall {
-    const lanczos_tensor_out* t = nullptr;   // validated (tensor_validate)
-    size_t extent_bytes = 0;                 // of one float frame: from its first float to its last
+    RsTensorOut t;             // validated (tensor_validate)
+    size_t extent_bytes = 0;   // of one element frame: from its first element to its last
     int route = 0;
 };
-int tensor_validate(const lanczos_resize_desc* d, const lanczos_tensor_out* t);
-size_t tensor_extent_bytes(const lanczos_resize_desc* d, const lanczos_tensor_out* t);
+// t NULL: the caller passed no struct; reserved: its four words
+int tensor_validate(const lanczos_resize_desc* d, const RsTensorOut* t, const int32_t* reserved);
+// the request of either public struct (T): *lay is filled where there is one
+template <class T>
+int tensor_validate(const lanczos_resize_desc* d, const T* t, int elem, RsTensorOut* lay) {
+    if (t) *lay = RsTensorOut{t->d_lut, t->chan_stride, t->row_stride, t->pix_stride, elem};
+    return tensor_validate(d, t ? lay : nullptr, t ? t->reserved : nullptr);
+}
+size_t tensor_extent_bytes(const lanczos_resize_desc* d, const RsTensorOut& t);
 void tensor_lut_normalize(int channels, const float* mean, const float* std, float* lut);
+// float32 -> bfloat16 (LANCZOS_TENSOR_BF16) or float16 (LANCZOS_TENSOR_F16) words, round to nearest even; false: no such format
+bool tensor_lut_convert16(const float* in, int n, int format, uint16_t* out);
 // k_rs_to_tensor: tightly packed interleaved bytes (frames `src_fs` apart, base and stride dword multiples, readable up to the
-// next dword multiple behind each frame) -> strided floats through the table
+// next dword multiple behind each frame) -> strided elements through the table
 hipError_t rs_to_tensor_launch(const uint8_t* src, size_t src_fs, uint8_t* out, size_t out_fs, int w, int h, int channels,
-                               const lanczos_tensor_out& t, int frames, hipStream_t stream);
+                               const RsTensorOut& t, int frames, hipStream_t stream);
 
 // The entry points (ctx->mu held, device set).  *last_kernel / *last_hip as in lanczos_ctx.  tc: a tensor request (NULL: bytes)
 int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* d_in, void* d_out,
                   int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream, int* last_kernel,
                   int* last_hip, RsTensorCall* tc = nullptr);
-// host table (t->d_lut) and host buffers, float frames tensor_extent_bytes apart; synchronous
-int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_tensor_out* t,
+// host table (t.d_lut) and host buffers, element frames tensor_extent_bytes apart; synchronous
+int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const RsTensorOut& t,
                        const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip, int* route);
 int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* in, void* out,
                 int frames, hipStream_t stream, int* last_kernel, int* last_hip);
@@ -175,10 +192,10 @@ struct RsFusedLaunch {
     uint8_t* out;
     size_t in_fs, out_fs;
     int frames;
-    const RsTensorCall* tc;   // TENSOR: `out` / `out_fs` are the float frames
+    const RsTensorCall* tc;   // TENSOR: `out` / `out_fs` are the element frames
     hipStream_t stream;
 };
-template <int BPS, bool TENSOR>
+template <int BPS, int TENSOR>   // TENSOR: bytes of a stored table element, 0 where the samples themselves are stored
 hipError_t rs_launch_fused(const RsFusedLaunch& c);
 
 // LANCZOS_FILTER_NEAREST (lanczos_resize_nearest.hip): out[y][x] = in[vidx[y]][hidx[x]] for pixels of `channels` samples of

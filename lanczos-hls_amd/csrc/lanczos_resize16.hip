@@ -6,6 +6,6 @@
 
 namespace lz {
 
-template hipError_t rs_launch_fused<2, false>(const RsFusedLaunch&);
+template hipError_t rs_launch_fused<2, 0>(const RsFusedLaunch&);
 
 }  // namespace lz

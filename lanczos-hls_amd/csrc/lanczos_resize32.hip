@@ -6,6 +6,6 @@
 
 namespace lz {
 
-template hipError_t rs_launch_fused<4, false>(const RsFusedLaunch&);
+template hipError_t rs_launch_fused<4, 0>(const RsFusedLaunch&);
 
 }  // namespace lz

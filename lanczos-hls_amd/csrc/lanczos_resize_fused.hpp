@@ -4,10 +4,10 @@
 //   RsSample<BPS>   what a sample width brings: its types, Pillow's multiply-add and store.  These are the specification of
 //                   the bytes; everything below only moves samples around.
 //   k_rs_pass_h/_v  the two-pass kernels, one thread per output sample (instantiated in lanczos_resize.hip).
-//   k_rs_fused      the fused kernel, and rs_launch_fused, which fills its arguments and picks the instance.  Four
+//   k_rs_fused      the fused kernel, and rs_launch_fused, which fills its arguments and picks the instance.  Five
 //                   translation units instantiate them side by side: lanczos_resize.hip (8-bit, bytes out),
-//                   lanczos_resize_tensor.hip (8-bit, floats out through a table: TENSOR), lanczos_resize16.hip and
-//                   lanczos_resize32.hip.
+//                   lanczos_resize_tensor.hip (8-bit, floats out through a table: TENSOR = 4), lanczos_resize_tensor16.hip
+//                   (8-bit, 16-bit elements out through a table: TENSOR = 2), lanczos_resize16.hip and lanczos_resize32.hip.
 #pragma once
 #include "lanczos_alpha.hpp"
 #include "lanczos_resize.hpp"
@@ -150,11 +150,11 @@ struct RsFused {
     int strips, rows_per_chunk;   // grid.x = strips * chunks, grid.y = frames
     int ring_rows, stage_rows, stage_dw;
 };
-// TENSOR instances: `out` / `out_fs` of RsFused are the float frames and their stride in bytes
+// TENSOR instances: `out` / `out_fs` of RsFused are the element frames and their stride in bytes
 struct RsFusedTensor : RsFused<int32_t> {
-    const uint32_t* lut;     // [C][256] words, read when the kernel runs
-    int cs, rs, ps;          // channel, row and pixel strides in floats
-    unsigned extent_bytes;   // of one float frame, below 2^31
+    const uint32_t* lut;     // [C][256] words of TENSOR bytes each, read when the kernel runs
+    int cs, rs, ps;          // channel, row and pixel strides in elements
+    unsigned extent_bytes;   // of one element frame, below 2^31
 };
 
 template <int C, int BPS>
@@ -184,9 +184,12 @@ struct RsStrip {
 // lane i has sample 64 r + i of the wave's 256: neighbouring lanes store neighbouring samples, whole 256-byte runs where the
 // layout is interleaved or has one channel, runs of every C-th lane per plane where it is planar.  The table is read from
 // global memory through the vector cache (1 to 4 KiB, resident after the first rows): LDS and the plan stay the byte kernel's.
-template <class S, int C, int K, bool ALPHA = false, bool TENSOR = false>
+// TENSOR is the width of the stored element in bytes: 4 (floats, lanczos_tensor_out), 2 (bfloat16 or float16 words,
+// lanczos_tensor16_out: the table is of 16-bit words and the store a 16-bit one, everything else the same), 0: bytes out.
+template <class S, int C, int K, bool ALPHA = false, int TENSOR = 0>
 __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
-    std::conditional_t<TENSOR, RsFusedTensor, RsFused<typename S::coeff_t>> g) {
+    std::conditional_t<TENSOR != 0, RsFusedTensor, RsFused<typename S::coeff_t>> g) {
+    static_assert(TENSOR == 0 || TENSOR == 2 || TENSOR == 4, "bytes, 16-bit elements or floats out");
     static_assert(!ALPHA || C == 4, "alpha is the fourth of four channels");
     static_assert((!ALPHA && !TENSOR) || S::BPS == 1, "alpha and tensor output are 8-bit");
     using acc_t = typename S::acc_t;
@@ -354,8 +357,12 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
                     const int j = wb + 64 * rr + lane;
                     if (j < valid_bytes) {
                         const int xo = j / C, c = j - xo * C;
-                        const uint32_t v = g.lut[c * 256 + (int)((w >> (8 * (lane & 3))) & 255u)];
-                        __builtin_amdgcn_raw_buffer_store_b32(v, orsrc, (c * g.cs + o * g.rs + (x0 + xo) * g.ps) * 4, 0, 0);
+                        const int at = c * 256 + (int)((w >> (8 * (lane & 3))) & 255u);
+                        const int to = c * g.cs + o * g.rs + (x0 + xo) * g.ps;
+                        if constexpr (TENSOR == 2)
+                            __builtin_amdgcn_raw_buffer_store_b16(((const uint16_t*)g.lut)[at], orsrc, to * 2, 0, 0);
+                        else
+                            __builtin_amdgcn_raw_buffer_store_b32(g.lut[at], orsrc, to * 4, 0, 0);
                     }
                 }
             } else if (b0 < valid_bytes) {
@@ -418,16 +425,16 @@ void rs_fill_fused(RsFused<KT>* g, const RsFusedLaunch& c) {
     g->ring_rows = c.fp->ring_rows, g->stage_rows = c.fp->stage_rows, g->stage_dw = c.fp->stage_dw;
 }
 
-template <int BPS, bool TENSOR>
+template <int BPS, int TENSOR>
 hipError_t rs_launch_fused(const RsFusedLaunch& c) {
     using S = RsSample<BPS>;
     const bool alpha = (c.d->reserved[0] & LANCZOS_RESIZE_ALPHA) != 0;
     const RsFusedPlan& fp = *c.fp;
-    std::conditional_t<TENSOR, RsFusedTensor, RsFused<typename S::coeff_t>> g{};
+    std::conditional_t<TENSOR != 0, RsFusedTensor, RsFused<typename S::coeff_t>> g{};
     rs_fill_fused(&g, c);
-    if constexpr (TENSOR) {
-        g.lut = (const uint32_t*)c.tc->t->d_lut;
-        g.cs = (int)c.tc->t->chan_stride, g.rs = (int)c.tc->t->row_stride, g.ps = (int)c.tc->t->pix_stride;   // extent below 2^31 bytes
+    if constexpr (TENSOR != 0) {
+        g.lut = (const uint32_t*)c.tc->t.d_lut;
+        g.cs = (int)c.tc->t.chan_stride, g.rs = (int)c.tc->t.row_stride, g.ps = (int)c.tc->t.pix_stride;   // extent below 2^31 bytes
         g.extent_bytes = (unsigned)c.tc->extent_bytes;
     }
     for (int f0 = 0; f0 < c.frames; f0 += 65535) {
@@ -450,9 +457,10 @@ hipError_t rs_launch_fused(const RsFusedLaunch& c) {
     return hipSuccess;
 }
 // each is instantiated, with its kernels, by the translation unit named at the head of this file
-extern template hipError_t rs_launch_fused<1, false>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<1, true>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<2, false>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<4, false>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<1, 0>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<1, 4>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<1, 2>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<2, 0>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<4, 0>(const RsFusedLaunch&);
 
 }  // namespace lz

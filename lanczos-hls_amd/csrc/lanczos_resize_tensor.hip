@@ -1,32 +1,35 @@
-// lanczos_resize_tensor.hip -- 8-bit resizes that leave as float tensors (include/lanczos_hip.h, lanczos_tensor_out;
-// DESIGN.md 4.5): out[c * cs + y * rs + x * ps] = lut[c][P(y, x, c)], P the byte lanczos_resize_device_ex stores.  The table
-// entries are moved as 32-bit words, never computed on.  Two kernels:
+// lanczos_resize_tensor.hip -- 8-bit resizes that leave as float, bfloat16 or float16 tensors (include/lanczos_hip.h,
+// lanczos_tensor_out and lanczos_tensor16_out): out[c * cs + y * rs + x * ps] = lut[c][P(y, x, c)], P the byte
+// lanczos_resize_device_ex stores.  The table entries are moved as 32-bit or 16-bit words, never computed on.  Two kernels:
 //
-//   fused      the TENSOR instances of k_rs_fused (lanczos_resize_fused.hpp): the vertical pass stores the floats itself.  A
-//              tensor request runs them exactly where the byte request runs the fused kernel, on the same plan.
-//   converted  k_rs_to_tensor behind any other resize (two passes, one pass, nearest, the plain copy, a float frame of 2^31
-//              bytes or more): the bytes go to context scratch, tightly packed, and one streaming launch turns them into floats.
+//   fused      the TENSOR instances of k_rs_fused (lanczos_resize_fused.hpp): the vertical pass stores the elements itself.  A
+//              tensor request runs them exactly where the byte request runs the fused kernel, on the same plan.  Those that
+//              store floats are instantiated here, those that store 16-bit elements in lanczos_resize_tensor16.hip.
+//   converted  k_rs_to_tensor behind any other resize (two passes, one pass, nearest, the plain copy, an element frame of 2^31
+//              bytes or more): the bytes go to context scratch, tightly packed, and one streaming launch turns them into
+//              elements (k_rs_to_tensor<C, uint16_t> is the k_rs_to_tensor16 of the documents).
 //
-// The validation of a request and the table of ToTensor + Normalize are here as well.
+// The validation of a request, the table of ToTensor + Normalize and its rounding to 16 bits are here as well.
 #include "lanczos_resize_fused.hpp"
 
 #include <algorithm>
+#include <cstring>
 
 namespace lz {
 
 // ---- host: validation, the normalisation table --------------------------------------------------------------------
 
-size_t tensor_extent_bytes(const lanczos_resize_desc* d, const lanczos_tensor_out* t) {
-    return (size_t)((d->channels - 1) * t->chan_stride + (d->out_h - 1) * t->row_stride + (d->out_w - 1) * t->pix_stride + 1) *
-           sizeof(float);
+size_t tensor_extent_bytes(const lanczos_resize_desc* d, const RsTensorOut& t) {
+    return (size_t)((d->channels - 1) * t.chan_stride + (d->out_h - 1) * t.row_stride + (d->out_w - 1) * t.pix_stride + 1) *
+           (size_t)t.elem;
 }
 
-int tensor_validate(const lanczos_resize_desc* d, const lanczos_tensor_out* t) {
+int tensor_validate(const lanczos_resize_desc* d, const RsTensorOut* t, const int32_t* reserved) {
     const int rc = resize_validate(d);
     if (rc != LANCZOS_OK) return rc;
     if (!t || !t->d_lut) return LANCZOS_ERR_BAD_ARG;
-    for (int32_t r : t->reserved)
-        if (r != 0) return LANCZOS_ERR_BAD_ARG;
+    for (int i = 0; i < 4; i++)
+        if (reserved[i] != 0) return LANCZOS_ERR_BAD_ARG;
     // a table per 16-bit value and float inputs are out of scope
     if (d->reserved[0] & (LANCZOS_RESIZE_U16 | LANCZOS_RESIZE_F32)) return LANCZOS_ERR_UNSUPPORTED;
     struct Dim {
@@ -38,7 +41,7 @@ int tensor_validate(const lanczos_resize_desc* d, const lanczos_tensor_out* t) {
     // no two (c, y, x) share an address: by rising stride, each stride covers the whole extent of the one before.  An axis of
     // extent 1 never moves, so its stride takes no part
     std::sort(dims, dims + 3, [](const Dim& a, const Dim& b) { return a.stride < b.stride; });
-    int64_t covered = 1;   // floats the axes so far span
+    int64_t covered = 1;   // elements the axes so far span
     for (const Dim& m : dims) {
         if (m.extent == 1) continue;
         if (m.stride < covered) return LANCZOS_ERR_BAD_ARG;
@@ -56,6 +59,42 @@ void tensor_lut_normalize(int channels, const float* mean, const float* std, flo
     }
 }
 
+// Round to nearest, ties to even, on the bits, as a CPU cast does.  bfloat16 is the upper half-word of the float: half a unit
+// less one, plus the unit bit, carries into it (and on into the exponent, up to inf).  float16 re-biases the exponent (127 ->
+// 15) and rounds the 13 bits that go the same way, which carries a full mantissa into the exponent and the largest exponent
+// into inf; below 2^-14 the result is the integer nearest to value * 2^24, a subnormal (or 0, or 2^-14 itself).  A NaN stays a
+// quiet NaN of its sign.
+static uint16_t bf16_word(uint32_t b) {
+    if ((b & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((b >> 16) | 0x7fc0u);
+    return (uint16_t)((b + 0x7fffu + ((b >> 16) & 1u)) >> 16);
+}
+static uint16_t f16_word(uint32_t b) {
+    const uint32_t sign = (b >> 16) & 0x8000u;
+    b &= 0x7fffffffu;
+    if (b > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);
+    if (b >= 0x38800000u) {   // 2^-14 and up: a normal float16, or inf
+        uint32_t v = b - 0x38000000u;
+        v += 0xfffu + ((v >> 13) & 1u);
+        return (uint16_t)(sign | std::min(v >> 13, 0x7c00u));
+    }
+    const uint32_t shift = 126u - (b >> 23);   // value * 2^24 = mantissa >> shift, shift 14 and up
+    if (shift > 24u) return (uint16_t)sign;    // below 2^-25: nearer to 0 than to the smallest subnormal
+    const uint32_t m = (b & 0x7fffffu) | 0x800000u;
+    uint32_t h = m >> shift;
+    const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1u);
+    h += rem > half || (rem == half && (h & 1u));
+    return (uint16_t)(sign | h);
+}
+bool tensor_lut_convert16(const float* in, int n, int format, uint16_t* out) {
+    if (format != LANCZOS_TENSOR_BF16 && format != LANCZOS_TENSOR_F16) return false;
+    for (int i = 0; i < n; i++) {
+        uint32_t b;
+        std::memcpy(&b, in + i, 4);
+        out[i] = format == LANCZOS_TENSOR_BF16 ? bf16_word(b) : f16_word(b);
+    }
+    return true;
+}
+
 // ---- kernels --------------------------------------------------------------------------------------------------------
 
 struct RsToTensor {
@@ -64,7 +103,7 @@ struct RsToTensor {
     unsigned long long src_fs, out_fs;   // frame strides (bytes)
     unsigned long long frame_bytes;      // samples of one frame
     unsigned pitch;                      // samples of one row
-    const uint32_t* lut;
+    const void* lut;   // words of the stored element's width
     long long cs, rs, ps;
 };
 
@@ -73,7 +112,8 @@ constexpr int kToTensorBlock = 4 * kRsThreads;   // samples per workgroup: one d
 // A thread loads one dword of the frame (coalesced, rows tightly packed, so the frame is one run of bytes) and the wave
 // exchanges its 64 dwords as the fused epilogue does: in round r lane i stores sample 64 r + i of the wave's 256.  Addresses
 // are 64-bit; the row of the workgroup's first sample costs one division per thread, a 64-bit one only for frames of 4 GiB.
-template <int C>
+// E is the word of a stored element: uint32_t for floats, uint16_t for bfloat16 and float16.
+template <int C, class E>
 __global__ __launch_bounds__(kRsThreads) void k_rs_to_tensor(RsToTensor g) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const unsigned long long base = (unsigned long long)blockIdx.x * kToTensorBlock;
@@ -88,7 +128,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_to_tensor(RsToTensor g) {
     } else {
         y0 = base / g.pitch, rem0 = (unsigned)(base - y0 * g.pitch);
     }
-    uint32_t* fout = (uint32_t*)(g.out + blockIdx.y * g.out_fs);
+    E* fout = (E*)(g.out + blockIdx.y * g.out_fs);
 #pragma unroll
     for (int rr = 0; rr < 4; rr++) {
         const uint32_t w = (uint32_t)__shfl((int)dw, 16 * rr + (lane >> 2), 64);
@@ -98,36 +138,37 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_to_tensor(RsToTensor g) {
             const unsigned dy = rem / g.pitch;
             rem -= dy * g.pitch;
             const unsigned x = rem / C, c = rem - x * C;
-            const uint32_t v = g.lut[c * 256 + ((w >> (8 * (lane & 3))) & 255u)];
+            const E v = ((const E*)g.lut)[c * 256 + ((w >> (8 * (lane & 3))) & 255u)];
             fout[(long long)c * g.cs + (long long)(y0 + dy) * g.rs + (long long)x * g.ps] = v;
         }
     }
 }
 
 hipError_t rs_to_tensor_launch(const uint8_t* src, size_t src_fs, uint8_t* out, size_t out_fs, int w, int h, int channels,
-                               const lanczos_tensor_out& t, int frames, hipStream_t stream) {
+                               const RsTensorOut& t, int frames, hipStream_t stream) {
     RsToTensor g{};
     g.src_fs = src_fs, g.out_fs = out_fs;
     g.frame_bytes = (unsigned long long)w * h * channels;
     g.pitch = (unsigned)(w * channels);
-    g.lut = (const uint32_t*)t.d_lut;
+    g.lut = t.d_lut;
     g.cs = t.chan_stride, g.rs = t.row_stride, g.ps = t.pix_stride;
     const unsigned blocks = (unsigned)((g.frame_bytes + kToTensorBlock - 1) / kToTensorBlock);   // at most 2^24
+    void (*kern)(RsToTensor);
+    if (t.elem == 2) kern = channels == 1 ? k_rs_to_tensor<1, uint16_t> : channels == 3 ? k_rs_to_tensor<3, uint16_t> : k_rs_to_tensor<4, uint16_t>;
+    else kern = channels == 1 ? k_rs_to_tensor<1, uint32_t> : channels == 3 ? k_rs_to_tensor<3, uint32_t> : k_rs_to_tensor<4, uint32_t>;
     for (int f0 = 0; f0 < frames; f0 += 65535) {
         const int nf = std::min(65535, frames - f0);
         g.src = src + (size_t)f0 * src_fs;
         g.out = out + (size_t)f0 * out_fs;
         const dim3 grid(blocks, nf);
-        if (channels == 1) hipLaunchKernelGGL(k_rs_to_tensor<1>, grid, dim3(kRsThreads), 0, stream, g);
-        else if (channels == 3) hipLaunchKernelGGL(k_rs_to_tensor<3>, grid, dim3(kRsThreads), 0, stream, g);
-        else hipLaunchKernelGGL(k_rs_to_tensor<4>, grid, dim3(kRsThreads), 0, stream, g);
+        hipLaunchKernelGGL(kern, grid, dim3(kRsThreads), 0, stream, g);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-// the TENSOR instances of k_rs_fused: every tap-count bucket x C = 1, 3, 4 and alpha
-template hipError_t rs_launch_fused<1, true>(const RsFusedLaunch&);
+// the instances of k_rs_fused that store floats: every tap-count bucket x C = 1, 3, 4 and alpha
+template hipError_t rs_launch_fused<1, 4>(const RsFusedLaunch&);
 
 }  // namespace lz

@@ -57,6 +57,14 @@ preprocessing shape, 256 frames of 500x375 -> 224x224 from a centred 375x375 box
   copy          a device-to-device copy of one step's float output: the floor of what the extra bytes cost
 Frame 0 of fused and converted are compared bit for bit before timing; a last line gives the ratios.
 
+T1h, T2h, T4h and TPh are T1, T2, T4 and TP to bfloat16 (lanczos_resize_tensor16_device; --only T1h,T2h,T4h,TPh).  Routes:
+  fused         the 16-bit tensor call under RESIZE_AUTO: the fused kernel stores the bfloat16 words
+  converted     the same call under RESIZE_CONVERT: the byte resize into context scratch, then k_rs_to_tensor16
+  f32_cast      the float32 tensor call (fused) followed by torch's .to(torch.bfloat16) on the same stream: what the 16-bit
+                entry replaces
+  f32           the float32 tensor call alone
+Frame 0 of fused, converted and f32_cast are compared bit for bit before timing; a last line gives the ratios.
+
 --pillow adds Pillow's single-core time of one frame of each workload (if Pillow imports; else "not available"); for U1 and
 U4 that is the time of one I;16 plane (a frame has three), for F1 and F4 that of one F plane.
 """
@@ -415,6 +423,58 @@ def run_tensor(name, args, ctx, torch, parent):
     torch.cuda.empty_cache()
 
 
+def run_tensor16(name, args, ctx, torch):
+    iw, ih, ow, oh, c, f, layout, box = TENSOR_WORKLOADS[name[:-1]]
+    in_fb, out_fb = iw * ih * c, ow * oh * c
+    sets = max(2, -(-2 * 256 * 2 ** 20 // (f * in_fb)) + 1)
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    xs = [torch.randint(0, 256, (f * in_fb,), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(sets)]
+    ys = [torch.empty(f * out_fb, dtype=torch.bfloat16, device="cuda") for _ in range(sets)]
+    wide = [torch.empty(f * out_fb, dtype=torch.float32, device="cuda") for _ in range(sets)]
+    d = L.resize_desc(iw, ih, ow, oh, c)
+    opts = L.resize_opts(d, box=box) if box else None
+    lut = torch.from_numpy(L.normalize_lut(c, IMAGENET_MEAN, IMAGENET_STD)).cuda()
+    lut16 = torch.from_numpy(L.normalize_lut(c, IMAGENET_MEAN, IMAGENET_STD, dtype="bfloat16").view(np.int16)).cuda()
+    st = L.tensor_strides(layout, ow, oh, c)
+    s = torch.cuda.current_stream().cuda_stream
+    seen = {}
+
+    def tensor16(path):
+        def step(i):
+            ctx.resize_force(path)
+            ctx.resize_tensor_device(d, xs[i % sets].data_ptr(), ys[i % sets].data_ptr(), f, lut16.data_ptr(), st, stream=s,
+                                     opts=opts, dtype="bfloat16")
+            seen[path] = ctx.last_tensor_route()
+            return ys[i % sets][:out_fb].view(torch.int16)
+        return step
+
+    def f32(i):
+        ctx.resize_force(L.RESIZE_AUTO)
+        ctx.resize_tensor_device(d, xs[i % sets].data_ptr(), wide[i % sets].data_ptr(), f, lut.data_ptr(), st, stream=s,
+                                 opts=opts)
+        return wide[i % sets][:out_fb].view(torch.int32)
+
+    def f32_cast(i):
+        f32(i)
+        return wide[i % sets].to(torch.bfloat16)[:out_fb].view(torch.int16)
+
+    routes = {"fused": tensor16(L.RESIZE_AUTO), "converted": tensor16(L.RESIZE_CONVERT), "f32_cast": f32_cast, "f32": f32}
+    inb = {rn: f * in_fb for rn in routes}
+    outb = {rn: 2 * f * out_fb for rn in routes}
+    outb["f32"] = 4 * f * out_fb
+    us = run_routes(name, f"{iw}x{ih}->{ow}x{oh} C{c} {layout} bfloat16" + (f" box {box}" if box else ""), f, routes, inb, outb,
+                    args, ctx, torch, check=(("fused", "converted"), ("fused", "f32_cast")))
+    ctx.resize_force(L.RESIZE_AUTO)
+    if (seen[L.RESIZE_AUTO], seen[L.RESIZE_CONVERT]) != (L.TENSOR_FUSED, L.TENSOR_CONVERTED):
+        raise SystemExit(f"{name}: routes {seen}")
+    print(json.dumps({"workload": name, "fused_over_f32_cast": round(us["fused"] / us["f32_cast"], 3),
+                      "converted_over_f32_cast": round(us["converted"] / us["f32_cast"], 3),
+                      "fused_over_converted": round(us["fused"] / us["converted"], 3),
+                      "fused_over_f32": round(us["fused"] / us["f32"], 3), "measured": True}), flush=True)
+    del xs, ys, wide
+    torch.cuda.empty_cache()
+
+
 def run_gap(name, args, ctx, torch):
     iw, ih, ow, oh, c, a, f = WORKLOADS["W5"]
     in_fb, out_fb = iw * ih * c, ow * oh * c
@@ -509,6 +569,8 @@ def main():
     for name in args.only.split(","):
         if name in TENSOR_WORKLOADS:
             run_tensor(name, args, ctx, torch, parent)
+        elif name.endswith("h") and name[:-1] in TENSOR_WORKLOADS:
+            run_tensor16(name, args, ctx, torch)
         elif name == "R5":
             run_gap(name, args, ctx, torch)
         elif name in ("B1", "B2"):
