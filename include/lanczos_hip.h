@@ -498,6 +498,77 @@ int lanczos_resize_tensor16_device(lanczos_ctx* ctx, const lanczos_resize_desc* 
 int lanczos_resize_tensor16_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                  const lanczos_tensor16_out* t, const void* in, void* out, int frames);
 
+/* ---- resize and crop in one call: compute only a window of the output (Image.resize(...).crop(window)) ----
+ * A window is (x0, y0, w, h) in OUTPUT pixels of the full request (descriptor and options): 0 <= x0, 1 <= w, x0 + w <= out_w
+ * and the same for y.  A windowed call stores a tightly packed w x h frame whose sample (x, y, c) is exactly what the same
+ * call without a window stores at (x0 + x, y0 + y, c) -- every sample type (8-bit, LANCZOS_RESIZE_ALPHA, _U16, _F32), every
+ * filter (LANCZOS_FILTER_NEAREST included), every source box, reducing_gap, and both tensor element widths.  Nothing outside
+ * that frame is written, and the result depends only on the source pixels the window's outputs read
+ * (lanczos_resize_window_source; a kernel may load a few more inside the frame and drop them).  It
+ * is exact by construction: the kernels of the full request run on slices of its tables (first, count and coeffs from output x0
+ * or y0 on), which stay cached under the full axes -- a centre crop and the full resize of one shape share their tables.
+ * The source `box` is no substitute: its corners are rounded to float and `first` is clipped against the source, not against
+ * the output grid, so a box over "the same region" gives other bytes than the crop of the full resize.
+ * Whether an axis runs its pass is decided by the FULL request, as without a window: an axis that keeps its size is only
+ * cropped, and with both axes idle the call is a crop copy (one launch for any frame count; RGBA is not premultiplied, as in
+ * the plain copy).  A NULL window, or the whole output, is the call without one: same route, same bytes -- the entry points
+ * without a window forward with NULL.  One window per call, the same for every frame of the batch.
+ * Planning follows the window: the fused plan is that of a w x h output (a window the fused kernel cannot run -- see
+ * lanczos_resize_plan -- takes the two-pass path, and forced LANCZOS_RESIZE_FUSED is then LANCZOS_ERR_UNSUPPORTED); the
+ * two-pass path computes only the intermediate rows the window's vertical taps read, w pixels wide; a horizontal pass alone
+ * runs the window's h rows, a vertical pass alone the window's w columns.  lanczos_last_kernel and lanczos_last_tensor_route
+ * report as for the full request's route family.  The capture and scratch rules are those of the call without a window.
+ * With a reducing_gap that reduces, the reduction still covers the whole safe box (restricting it to the window is not built):
+ * the window only applies to the resize of the reduced frames.
+ * Tensor calls: the strides describe the window's C x h x w frame -- the overlap rule, the frame's extent, the minimum of
+ * out_frame_stride and the 2^31-byte limit of the fused tensor route all use w and h, not out_w and out_h. */
+typedef struct lanczos_resize_window {
+    int32_t x0, y0, w, h;
+    int32_t reserved[4];  /* must be 0 */
+} lanczos_resize_window;
+/* the whole output of `d` */
+int lanczos_resize_window_init(lanczos_resize_window* win, const lanczos_resize_desc* d);
+/* Host only.  LANCZOS_ERR_BAD_ARG: what lanczos_resize_validate refuses, a window outside the output, w or h below 1, non-zero
+ * reserved words.  win NULL = the whole output. */
+int lanczos_resize_window_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win);
+/* Host only: rect = (x0, y0, x1, y1), integers, half open -- the source rectangle the windowed request's result depends on.  Per axis: one
+ * that runs reads the union of [first[o], first[o] + count[o]) over the window's outputs o (lanczos_resize_taps_host_ex; for
+ * LANCZOS_FILTER_NEAREST the smallest index to the largest + 1); an idle axis reads the window's own range.  With a reducing_gap
+ * that reduces, rect is the safe box (lanczos_resize_plan_ex.safe_box) whatever the window. */
+int lanczos_resize_window_source(const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                                 int32_t rect[4]);
+/* lanczos_resize_plan_host_ex for the windowed request: mid_row0 / mid_rows are the rows the window's vertical taps read, and
+ * inner is the fused plan of a w x h output.  The whole output gives what lanczos_resize_plan_host_ex gives. */
+int lanczos_resize_window_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                                    int frames, lanczos_resize_plan_ex* out);
+/* As lanczos_resize_device_ex / lanczos_resize_host_ex (o and win may be NULL) with output frames of w x h pixels:
+ * out_frame_stride 0 is w * h * channels samples, a smaller one is LANCZOS_ERR_BAD_ARG. */
+int lanczos_resize_window_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
+                                 const lanczos_resize_window* win, const void* d_in, void* d_out, int frames,
+                                 size_t in_frame_stride, size_t out_frame_stride, void* stream);
+int lanczos_resize_window_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
+                               const lanczos_resize_window* win, const void* in, void* out, int frames);
+/* as lanczos_resize_tensor_validate / lanczos_resize_tensor16_validate for a frame of the window's extent */
+int lanczos_resize_tensor_window_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win,
+                                          const lanczos_tensor_out* t);
+int lanczos_resize_tensor16_window_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win,
+                                            const lanczos_tensor16_out* t);
+/* as the tensor entry points above, element frames of the window's extent:
+ * ((channels - 1) * chan_stride + (h - 1) * row_stride + (w - 1) * pix_stride + 1) elements */
+int lanczos_resize_tensor_window_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                        const lanczos_resize_window* win, const lanczos_tensor_out* t, const void* d_in,
+                                        void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream);
+int lanczos_resize_tensor_window_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                      const lanczos_resize_window* win, const lanczos_tensor_out* t, const void* in, void* out,
+                                      int frames);
+int lanczos_resize_tensor16_window_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                          const lanczos_resize_window* win, const lanczos_tensor16_out* t, const void* d_in,
+                                          void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride,
+                                          void* stream);
+int lanczos_resize_tensor16_window_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                        const lanczos_resize_window* win, const lanczos_tensor16_out* t, const void* in,
+                                        void* out, int frames);
+
 /* ---- reduce by whole factors (Pillow's Image.reduce((fx, fy), box), an exact integer box average) ----
  * 8-bit, 1, 3 or 4 independent interleaved channels.  box = (x0, y0, x1, y1), integers with 0 <= x0 < x1 <= in_w and the same
  * for y; NULL = the whole frame.  The output is ceil((x1 - x0) / fx) x ceil((y1 - y0) / fy) pixels, tightly packed rows.

@@ -65,6 +65,11 @@ ABI_SYMBOLS = [
     "lanczos_resize_tensor_host", "lanczos_last_tensor_route",
     "lanczos_resize_tensor16_validate", "lanczos_tensor_lut_convert16", "lanczos_tensor16_lut_normalize",
     "lanczos_resize_tensor16_device", "lanczos_resize_tensor16_host",
+    "lanczos_resize_window_init", "lanczos_resize_window_validate", "lanczos_resize_window_source",
+    "lanczos_resize_window_plan_host", "lanczos_resize_window_device", "lanczos_resize_window_host",
+    "lanczos_resize_tensor_window_validate", "lanczos_resize_tensor16_window_validate",
+    "lanczos_resize_tensor_window_device", "lanczos_resize_tensor_window_host",
+    "lanczos_resize_tensor16_window_device", "lanczos_resize_tensor16_window_host",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
 
@@ -126,6 +131,12 @@ class ResizePlanEx(ctypes.Structure):
                 ("pass_h", ctypes.c_int32), ("pass_v", ctypes.c_int32),
                 ("mid_row0", ctypes.c_int32), ("mid_rows", ctypes.c_int32),
                 ("inner_box", ctypes.c_double * 4), ("inner", ResizePlan)]
+
+
+class ResizeWindow(ctypes.Structure):
+    """lanczos_resize_window -- the window (x0, y0, w, h) of the output, in output pixels, that a call computes and stores."""
+    _fields_ = [("x0", ctypes.c_int32), ("y0", ctypes.c_int32), ("w", ctypes.c_int32), ("h", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 4)]
 
 
 class TensorOut(ctypes.Structure):
@@ -253,6 +264,23 @@ def _lib():
             L.lanczos_resize_tensor16_device.argtypes = [c_void_p, PRD, PRO, PTO16, c_void_p, c_void_p, c_int, c_size_t,
                                                          c_size_t, c_void_p]
             L.lanczos_resize_tensor16_host.argtypes = [c_void_p, PRD, PRO, PTO16, c_void_p, c_void_p, c_int]
+        if hasattr(L, "lanczos_resize_window_device"):   # (nor the window of the output)
+            PRW = ctypes.POINTER(ResizeWindow)
+            L.lanczos_resize_window_init.argtypes = [PRW, PRD]
+            L.lanczos_resize_window_validate.argtypes = [PRD, PRW]
+            L.lanczos_resize_window_source.argtypes = [PRD, PRO, PRW, c_void_p]
+            L.lanczos_resize_window_plan_host.argtypes = [PRD, PRO, PRW, c_int, ctypes.POINTER(ResizePlanEx)]
+            L.lanczos_resize_window_device.argtypes = [c_void_p, PRD, PRO, PRW, c_void_p, c_void_p, c_int, c_size_t, c_size_t,
+                                                       c_void_p]
+            L.lanczos_resize_window_host.argtypes = [c_void_p, PRD, PRO, PRW, c_void_p, c_void_p, c_int]
+            L.lanczos_resize_tensor_window_validate.argtypes = [PRD, PRW, PTO]
+            L.lanczos_resize_tensor16_window_validate.argtypes = [PRD, PRW, PTO16]
+            L.lanczos_resize_tensor_window_device.argtypes = [c_void_p, PRD, PRO, PRW, PTO, c_void_p, c_void_p, c_int, c_size_t,
+                                                              c_size_t, c_void_p]
+            L.lanczos_resize_tensor_window_host.argtypes = [c_void_p, PRD, PRO, PRW, PTO, c_void_p, c_void_p, c_int]
+            L.lanczos_resize_tensor16_window_device.argtypes = [c_void_p, PRD, PRO, PRW, PTO16, c_void_p, c_void_p, c_int,
+                                                                c_size_t, c_size_t, c_void_p]
+            L.lanczos_resize_tensor16_window_host.argtypes = [c_void_p, PRD, PRO, PRW, PTO16, c_void_p, c_void_p, c_int]
         L.lanczos_strerror.restype = ctypes.c_char_p
         L.lanczos_version.argtypes = []
         L.lanczos_version.restype = ctypes.c_char_p
@@ -412,6 +440,54 @@ def resize_plan_host(desc, frames=1, box=None, reducing_gap=None, opts=None):
     return p
 
 
+def resize_window(desc, window=None):
+    """A validated ResizeWindow for `desc`: window = (x0, y0, w, h) in output pixels of the full request, inside its output
+    (ERR_BAD_ARG otherwise); None = the whole output.  A ready ResizeWindow is validated and returned."""
+    if isinstance(window, ResizeWindow):
+        win = window
+    else:
+        win = ResizeWindow()
+        _check(_lib().lanczos_resize_window_init(ctypes.byref(win), ctypes.byref(desc)), "lanczos_resize_window_init")
+        if window is not None:
+            if len(window) != 4:
+                raise LanczosError(ERR_BAD_ARG, "resize_window: window is (x0, y0, w, h)")
+            win.x0, win.y0, win.w, win.h = (int(v) for v in window)
+    _check(_lib().lanczos_resize_window_validate(ctypes.byref(desc), ctypes.byref(win)), "lanczos_resize_window_validate")
+    return win
+
+
+def _window_ref(desc, window):
+    return ctypes.byref(resize_window(desc, window)) if window is not None else None
+
+
+def resize_window_source(desc, window=None, box=None, reducing_gap=None, opts=None):
+    """(x0, y0, x1, y1), half open: the source rectangle the windowed request reads (lanczos_resize_window_source).  With a
+    reducing_gap that reduces it is the safe box, whatever the window."""
+    rect = (ctypes.c_int32 * 4)()
+    _check(_lib().lanczos_resize_window_source(ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
+                                               _window_ref(desc, window), rect), "lanczos_resize_window_source")
+    return tuple(rect)
+
+
+def resize_window_plan_host(desc, window=None, frames=1, box=None, reducing_gap=None, opts=None):
+    """The ResizePlanEx of the windowed request (no GPU needed): mid_row0 / mid_rows are the rows the window's vertical taps
+    read, inner is the fused plan of a w x h output.  The whole output gives resize_plan_host's ResizePlanEx."""
+    p = ResizePlanEx()
+    _check(_lib().lanczos_resize_window_plan_host(ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
+                                                  _window_ref(desc, window), frames, ctypes.byref(p)),
+           "lanczos_resize_window_plan_host")
+    return p
+
+
+def center_window(out_w, out_h, w, h):
+    """The window (x0, y0, w, h) torchvision's CenterCrop((h, w)) takes out of an out_h x out_w image: the origin is
+    int(round((out - crop) / 2.0)) per axis with Python's round (a tie goes to the even integer).  A crop larger than the
+    output raises ERR_BAD_ARG: CenterCrop would pad there, which is no window."""
+    if not (1 <= w <= out_w and 1 <= h <= out_h):
+        raise LanczosError(ERR_BAD_ARG, f"center_window: a {w} x {h} crop of a {out_w} x {out_h} output")
+    return int(round((out_w - w) / 2.0)), int(round((out_h - h) / 2.0)), int(w), int(h)
+
+
 def _tensor16_format(dtype, what):
     if dtype not in _TENSOR16_FORMATS:
         raise LanczosError(ERR_BAD_ARG, f"{what}: dtype is 'float32', 'bfloat16' or 'float16', not {dtype!r}")
@@ -487,16 +563,26 @@ def tensor16_out(d_lut, strides):
     return t
 
 
-def resize_tensor16_validate(desc, t):
-    """lanczos_resize_tensor16_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the request is refused."""
-    _check(_lib().lanczos_resize_tensor16_validate(ctypes.byref(desc), ctypes.byref(t) if t is not None else None),
-           "lanczos_resize_tensor16_validate")
+def resize_tensor16_validate(desc, t, window=None):
+    """lanczos_resize_tensor16_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the request is refused.
+    window: the strides describe that window's frame (lanczos_resize_tensor16_window_validate)."""
+    tp = ctypes.byref(t) if t is not None else None
+    if window is None:
+        _check(_lib().lanczos_resize_tensor16_validate(ctypes.byref(desc), tp), "lanczos_resize_tensor16_validate")
+    else:
+        _check(_lib().lanczos_resize_tensor16_window_validate(ctypes.byref(desc), _window_ref(desc, window), tp),
+               "lanczos_resize_tensor16_window_validate")
 
 
-def resize_tensor_validate(desc, t):
-    """lanczos_resize_tensor_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the request is refused."""
-    _check(_lib().lanczos_resize_tensor_validate(ctypes.byref(desc), ctypes.byref(t) if t is not None else None),
-           "lanczos_resize_tensor_validate")
+def resize_tensor_validate(desc, t, window=None):
+    """lanczos_resize_tensor_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the request is refused.
+    window: the strides describe that window's frame (lanczos_resize_tensor_window_validate)."""
+    tp = ctypes.byref(t) if t is not None else None
+    if window is None:
+        _check(_lib().lanczos_resize_tensor_validate(ctypes.byref(desc), tp), "lanczos_resize_tensor_validate")
+    else:
+        _check(_lib().lanczos_resize_tensor_window_validate(ctypes.byref(desc), _window_ref(desc, window), tp),
+               "lanczos_resize_tensor_window_validate")
 
 
 def _factor_pair(factor):
@@ -622,8 +708,11 @@ class Context:
                                                      stream), "lanczos_resample_planar_device")
 
     # -- resize to any size (Pillow's contract, lanczos_resize_*)
-    def resize(self, img, out_w, out_h, a=3, alpha=False, box=None, reducing_gap=None, filter=FILTER_LANCZOS):
-        """filter: Image.resize's `resample` as a name ("lanczos", "box", "bilinear", "hamming", "bicubic", "nearest") or
+    def resize(self, img, out_w, out_h, a=3, alpha=False, box=None, reducing_gap=None, filter=FILTER_LANCZOS, window=None):
+        """window = (x0, y0, w, h) in output pixels: compute and return only that window of the out_h x out_w result, [h][w]
+        instead of [out_h][out_w] -- exactly Image.resize(...).crop((x0, y0, x0 + w, y0 + h)), without computing the rest
+        (center_window gives torchvision's CenterCrop).
+        filter: Image.resize's `resample` as a name ("lanczos", "box", "bilinear", "hamming", "bicubic", "nearest") or
         FILTER_*; bytes identical to Pillow's for that filter.  Every filter but Lanczos needs a == 3; "nearest" takes no
         reducing_gap and no uint16 frames, and copies RGBA pixels whole.
         box = (x0, y0, x1, y1): resize that (sub-pixel) region of the source, as Image.resize(..., box=box); pixels
@@ -642,8 +731,13 @@ class Context:
         x = x if x.ndim == 4 else x[None]
         f, h, w, c = x.shape
         d = resize_desc(w, h, out_w, out_h, c, a, alpha, 8 * img.dtype.itemsize, filter=filter)
-        out = np.empty((f, out_h, out_w, c), dtype=img.dtype)
-        if box is None and reducing_gap is None:
+        win = resize_window(d, window)
+        out = np.empty((f, win.h, win.w, c), dtype=img.dtype)
+        if window is not None:
+            _check(_lib().lanczos_resize_window_host(self._h, ctypes.byref(d), _opts_ref(d, box, reducing_gap, None),
+                                                     ctypes.byref(win), x.ctypes.data, out.ctypes.data, f),
+                   "lanczos_resize_window_host")
+        elif box is None and reducing_gap is None:
             _check(_lib().lanczos_resize_host(self._h, ctypes.byref(d), x.ctypes.data, out.ctypes.data, f),
                    "lanczos_resize_host")
         else:
@@ -653,8 +747,8 @@ class Context:
             return out[0, :, :, 0]
         return out if img.ndim == 4 else out[0]
 
-    def resize_f32(self, img, out_w, out_h, a=3, box=None, filter=FILTER_LANCZOS):
-        """filter as Context.resize.
+    def resize_f32(self, img, out_w, out_h, a=3, box=None, filter=FILTER_LANCZOS, window=None):
+        """filter and window as Context.resize.
         img: float32 [H][W], [H][W][C] or [F][H][W][C] (C = 1, 3 or 4) -> the same layout at out_h x out_w, every channel
         bit for bit what Pillow's Image.resize((out_w, out_h), Image.LANCZOS, box) gives for it as a mode F plane (a = 3):
         double accumulation over exactly the window's taps, stored as float -- no clamp, inf on overflow, denormals kept, NaN
@@ -666,8 +760,13 @@ class Context:
         x = x if x.ndim == 4 else x[None]
         f, h, w, c = x.shape
         d = resize_desc(w, h, out_w, out_h, c, a, f32=True, filter=filter)
-        out = np.empty((f, out_h, out_w, c), dtype=np.float32)
-        if box is None:
+        win = resize_window(d, window)
+        out = np.empty((f, win.h, win.w, c), dtype=np.float32)
+        if window is not None:
+            _check(_lib().lanczos_resize_window_host(self._h, ctypes.byref(d), _opts_ref(d, box, None, None),
+                                                     ctypes.byref(win), x.ctypes.data, out.ctypes.data, f),
+                   "lanczos_resize_window_host")
+        elif box is None:
             _check(_lib().lanczos_resize_host(self._h, ctypes.byref(d), x.ctypes.data, out.ctypes.data, f),
                    "lanczos_resize_host")
         else:
@@ -678,15 +777,20 @@ class Context:
         return out if img.ndim == 4 else out[0]
 
     def resize_device(self, desc, d_in, d_out, frames, in_frame_stride=0, out_frame_stride=0, stream=None, box=None,
-                      reducing_gap=None, opts=None, filter=None):
+                      reducing_gap=None, opts=None, filter=None, window=None):
         """Device pointers, asynchronous on `stream` (None = the default stream).  box / reducing_gap / opts as
         resize_taps_host.  The filter is the descriptor's (resize_desc(..., filter=)); filter= (a name or FILTER_*) runs
-        the same request with that filter instead."""
+        the same request with that filter instead.  window = (x0, y0, w, h) or a ResizeWindow: the frames at d_out are that
+        window of the output, w x h pixels tightly packed (out_frame_stride 0 = one such frame)."""
         if filter is not None:
             d = ResizeDesc.from_buffer_copy(desc)
             d.reserved[0] = (d.reserved[0] & ~(15 << 8)) | (filter_code(filter) << 8)
             desc = d
-        if box is None and reducing_gap is None and opts is None:
+        if window is not None:
+            _check(_lib().lanczos_resize_window_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
+                                                       _window_ref(desc, window), d_in, d_out, frames, in_frame_stride,
+                                                       out_frame_stride, stream), "lanczos_resize_window_device")
+        elif box is None and reducing_gap is None and opts is None:
             _check(_lib().lanczos_resize_device(self._h, ctypes.byref(desc), d_in, d_out, frames, in_frame_stride,
                                                 out_frame_stride, stream), "lanczos_resize_device")
         else:
@@ -696,8 +800,9 @@ class Context:
 
     # -- resize straight into a float tensor (PIL.Image.resize -> ToTensor() -> Normalize(), lanczos_resize_tensor_*)
     def resize_tensor(self, img, out_w, out_h, mean=None, std=None, lut=None, layout="chw", a=3, alpha=False, box=None,
-                      reducing_gap=None, filter=FILTER_LANCZOS, dtype="float32"):
-        """img: uint8 [H][W], [H][W][C] or [F][H][W][C] as Context.resize takes it -> float32 [F][C][H][W] (layout="chw") or
+                      reducing_gap=None, filter=FILTER_LANCZOS, dtype="float32", window=None):
+        """window = (x0, y0, w, h): only that window of the output, [F][C][h][w] or [F][h][w][C] (as Context.resize).
+        img: uint8 [H][W], [H][W][C] or [F][H][W][C] as Context.resize takes it -> float32 [F][C][H][W] (layout="chw") or
         [F][H][W][C] ("hwc"), the frame axis dropped as resize drops it: lut[c][byte] of the bytes Context.resize returns for
         the same arguments.  lut: float32 [C][256], moved bit for bit; None = normalize_lut(C, mean, std), with which the
         result is bit for bit torch.from_numpy(bytes).permute(2, 0, 1).float().div(255).sub(mean).div(std).
@@ -722,42 +827,67 @@ class Context:
         lut = np.ascontiguousarray(lut)
         if lut.dtype not in ((np.float32,) if wide else (np.uint16, np.float16)) or lut.size != c * 256:
             raise LanczosError(ERR_BAD_ARG, f"resize_tensor: the table is {'float32' if wide else 'uint16 or float16'} [{c}][256]")
-        strides = tensor_strides(layout, out_w, out_h, c)
-        shape = (f, c, out_h, out_w) if layout == "chw" else (f, out_h, out_w, c)
+        win = resize_window(d, window)
+        strides = tensor_strides(layout, win.w, win.h, c)
+        shape = (f, c, win.h, win.w) if layout == "chw" else (f, win.h, win.w, c)
         opts = _opts_ref(d, box, reducing_gap, None)
+        wref = ctypes.byref(win) if window is not None else None
         if wide:
             t = tensor_out(lut.ctypes.data, strides)
             out = np.empty(shape, dtype=np.float32)
-            _check(_lib().lanczos_resize_tensor_host(self._h, ctypes.byref(d), opts, ctypes.byref(t), x.ctypes.data,
-                                                     out.ctypes.data, f), "lanczos_resize_tensor_host")
+            if wref is None:
+                _check(_lib().lanczos_resize_tensor_host(self._h, ctypes.byref(d), opts, ctypes.byref(t), x.ctypes.data,
+                                                         out.ctypes.data, f), "lanczos_resize_tensor_host")
+            else:
+                _check(_lib().lanczos_resize_tensor_window_host(self._h, ctypes.byref(d), opts, wref, ctypes.byref(t),
+                                                                x.ctypes.data, out.ctypes.data, f),
+                       "lanczos_resize_tensor_window_host")
         else:
             t = tensor16_out(lut.ctypes.data, strides)
             out = np.empty(shape, dtype=np.uint16)
-            _check(_lib().lanczos_resize_tensor16_host(self._h, ctypes.byref(d), opts, ctypes.byref(t), x.ctypes.data,
-                                                       out.ctypes.data, f), "lanczos_resize_tensor16_host")
+            if wref is None:
+                _check(_lib().lanczos_resize_tensor16_host(self._h, ctypes.byref(d), opts, ctypes.byref(t), x.ctypes.data,
+                                                           out.ctypes.data, f), "lanczos_resize_tensor16_host")
+            else:
+                _check(_lib().lanczos_resize_tensor16_window_host(self._h, ctypes.byref(d), opts, wref, ctypes.byref(t),
+                                                                  x.ctypes.data, out.ctypes.data, f),
+                       "lanczos_resize_tensor16_window_host")
             out = _tensor16_array(out, dtype)
         return out if img.ndim == 4 else out[0]
 
     def resize_tensor_device(self, desc, d_in, d_out, frames, d_lut, strides, in_frame_stride=0, out_frame_stride=0,
-                             stream=None, box=None, reducing_gap=None, opts=None, dtype="float32"):
+                             stream=None, box=None, reducing_gap=None, opts=None, dtype="float32", window=None):
         """Device pointers, asynchronous on `stream`: uint8 frames at d_in -> float frames at d_out, out_frame_stride in BYTES
         (0 = one frame's extent).  d_lut: device pointer to channels * 256 floats, read when the kernels run (a replayed
         graph sees its contents of that moment).  strides = (chan_stride, row_stride, pix_stride) in floats, e.g.
         tensor_strides("chw", ...), or a ready TensorOut (d_lut then unused).  box / reducing_gap / opts as resize_device.
         dtype="bfloat16" / "float16" (or a ready TensorOut16): 16-bit elements at d_out and in the table, strides in
-        elements, d_out and out_frame_stride multiples of 2."""
+        elements, d_out and out_frame_stride multiples of 2.  window = (x0, y0, w, h) or a ResizeWindow: the element frames
+        are that window of the output, and the strides describe its C x h x w frame (tensor_strides(layout, w, h, C))."""
+        oref = _opts_ref(desc, box, reducing_gap, opts)
+        wref = _window_ref(desc, window)
         if isinstance(strides, TensorOut16) or dtype != "float32":
             if not isinstance(strides, TensorOut16):
                 _tensor16_format(dtype, "resize_tensor_device")
             t = strides if isinstance(strides, TensorOut16) else tensor16_out(d_lut, strides)
-            _check(_lib().lanczos_resize_tensor16_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
-                                                         ctypes.byref(t), d_in, d_out, frames, in_frame_stride,
-                                                         out_frame_stride, stream), "lanczos_resize_tensor16_device")
+            if wref is None:
+                _check(_lib().lanczos_resize_tensor16_device(self._h, ctypes.byref(desc), oref, ctypes.byref(t), d_in, d_out,
+                                                             frames, in_frame_stride, out_frame_stride, stream),
+                       "lanczos_resize_tensor16_device")
+            else:
+                _check(_lib().lanczos_resize_tensor16_window_device(self._h, ctypes.byref(desc), oref, wref, ctypes.byref(t),
+                                                                    d_in, d_out, frames, in_frame_stride, out_frame_stride,
+                                                                    stream), "lanczos_resize_tensor16_window_device")
             return
         t = strides if isinstance(strides, TensorOut) else tensor_out(d_lut, strides)
-        _check(_lib().lanczos_resize_tensor_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
-                                                   ctypes.byref(t), d_in, d_out, frames, in_frame_stride, out_frame_stride,
-                                                   stream), "lanczos_resize_tensor_device")
+        if wref is None:
+            _check(_lib().lanczos_resize_tensor_device(self._h, ctypes.byref(desc), oref, ctypes.byref(t), d_in, d_out, frames,
+                                                       in_frame_stride, out_frame_stride, stream),
+                   "lanczos_resize_tensor_device")
+        else:
+            _check(_lib().lanczos_resize_tensor_window_device(self._h, ctypes.byref(desc), oref, wref, ctypes.byref(t), d_in,
+                                                              d_out, frames, in_frame_stride, out_frame_stride, stream),
+                   "lanczos_resize_tensor_window_device")
 
     def last_tensor_route(self):
         """TENSOR_FUSED (the resize kernel stored the floats), TENSOR_CONVERTED (bytes to scratch, then a conversion launch),

@@ -1148,12 +1148,41 @@ int lanczos_resize_taps_f64_host(const lanczos_resize_desc* d, int axis, int32_t
     return lanczos_resize_taps_f64_host_ex(d, nullptr, axis, first, count, coeffs, ksize);
 }
 
-int lanczos_resize_plan_host_ex(const lanczos_resize_desc* d, const lanczos_resize_opts* o, int frames,
-                                lanczos_resize_plan_ex* out) {
+int lanczos_resize_window_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                                    int frames, lanczos_resize_plan_ex* out) {
     int rc = lz::resize_validate(d);
     if (rc != LANCZOS_OK) return rc;
     if (frames < 1 || !out) return LANCZOS_ERR_BAD_ARG;
-    return lz::resize_plan_host(d, o, frames, out);
+    return lz::resize_plan_host(d, o, win, frames, out);
+}
+
+int lanczos_resize_plan_host_ex(const lanczos_resize_desc* d, const lanczos_resize_opts* o, int frames,
+                                lanczos_resize_plan_ex* out) {
+    return lanczos_resize_window_plan_host(d, o, nullptr, frames, out);
+}
+
+int lanczos_resize_window_init(lanczos_resize_window* win, const lanczos_resize_desc* d) {
+    if (!win) return LANCZOS_ERR_BAD_ARG;
+    memset(win, 0, sizeof(*win));
+    const int rc = lz::resize_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    win->w = d->out_w, win->h = d->out_h;
+    return LANCZOS_OK;
+}
+
+int lanczos_resize_window_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win) {
+    const int rc = lz::resize_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    lz::RsWindow w;
+    return lz::resize_window_resolve(d, win, &w);
+}
+
+int lanczos_resize_window_source(const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                                 int32_t rect[4]) {
+    const int rc = lz::resize_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    if (!rect) return LANCZOS_ERR_BAD_ARG;
+    return lz::resize_window_source(d, o, win, rect);
 }
 
 int lanczos_resize_plan_host(const lanczos_resize_desc* d, int frames, lanczos_resize_plan* out) {
@@ -1170,8 +1199,9 @@ static int resize_state(lanczos_ctx* ctx) {
     return ctx->resize ? LANCZOS_OK : LANCZOS_ERR_NOMEM;
 }
 
-int lanczos_resize_device_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* d_in,
-                             void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+int lanczos_resize_window_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
+                                 const lanczos_resize_window* win, const void* d_in, void* d_out, int frames,
+                                 size_t in_frame_stride, size_t out_frame_stride, void* stream) {
     if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
     int rc = lz::resize_validate(d);
     if (rc != LANCZOS_OK) return rc;
@@ -1180,8 +1210,13 @@ int lanczos_resize_device_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, con
     if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
     route_begin(ctx);
     // NULL = the legacy default stream, as lanczos_resample_device
-    return lz::resize_device(ctx->resize, d, o, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
+    return lz::resize_device(ctx->resize, d, o, win, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
                              &ctx->last_kernel, &ctx->last_hip);
+}
+
+int lanczos_resize_device_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* d_in,
+                             void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+    return lanczos_resize_window_device(ctx, d, o, nullptr, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
 }
 
 int lanczos_resize_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const void* d_in, void* d_out, int frames,
@@ -1189,8 +1224,8 @@ int lanczos_resize_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const 
     return lanczos_resize_device_ex(ctx, d, nullptr, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
 }
 
-int lanczos_resize_host_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* in,
-                           void* out, int frames) {
+int lanczos_resize_window_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
+                               const lanczos_resize_window* win, const void* in, void* out, int frames) {
     if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
     int rc = lz::resize_validate(d);
     if (rc != LANCZOS_OK) return rc;
@@ -1199,7 +1234,12 @@ int lanczos_resize_host_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, const
     if (!ctx->stream) return LANCZOS_ERR_HIP;
     if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
     route_begin(ctx);
-    return lz::resize_host(ctx->resize, d, o, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip);
+    return lz::resize_host(ctx->resize, d, o, win, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip);
+}
+
+int lanczos_resize_host_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* in,
+                           void* out, int frames) {
+    return lanczos_resize_window_host(ctx, d, o, nullptr, in, out, frames);
 }
 
 int lanczos_resize_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const void* in, void* out, int frames) {
@@ -1209,44 +1249,51 @@ int lanczos_resize_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const vo
 // The float and the 16-bit tensor entries are one request (lz::RsTensorOut) with another element width
 extern "C++" {
 template <class T>
-static int tensor_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts, const T* t, int elem,
-                         const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+static int tensor_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                         const lanczos_resize_window* win, const T* t, int elem, const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
     if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
     lz::RsTensorCall tc;
-    int rc = lz::tensor_validate(d, t, elem, &tc.t);
+    int rc = lz::tensor_validate(d, win, t, elem, &tc.t);
     if (rc != LANCZOS_OK) return rc;
     std::lock_guard<std::mutex> lock(ctx->mu);
     LZ_HIP(ctx, hipSetDevice(ctx->device));
     if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
     route_begin(ctx);
-    tc.extent_bytes = lz::tensor_extent_bytes(d, tc.t);
-    rc = lz::resize_device(ctx->resize, d, opts, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
+    lz::RsWindow w;
+    (void)lz::resize_window_resolve(d, win, &w);   // validated above
+    tc.extent_bytes = lz::tensor_extent_bytes(d, w, tc.t);
+    rc = lz::resize_device(ctx->resize, d, opts, win, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
                            &ctx->last_kernel, &ctx->last_hip, &tc);
     ctx->last_tensor_route = tc.route;
     return rc;
 }
 
 template <class T>
-static int tensor_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts, const T* t, int elem,
-                       const void* in, void* out, int frames) {
+static int tensor_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                       const lanczos_resize_window* win, const T* t, int elem, const void* in, void* out, int frames) {
     if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
     lz::RsTensorOut lay;
-    int rc = lz::tensor_validate(d, t, elem, &lay);
+    int rc = lz::tensor_validate(d, win, t, elem, &lay);
     if (rc != LANCZOS_OK) return rc;
     std::lock_guard<std::mutex> lock(ctx->mu);
     LZ_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->stream) return LANCZOS_ERR_HIP;
     if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
     route_begin(ctx);
-    return lz::resize_tensor_host(ctx->resize, d, opts, lay, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip,
+    return lz::resize_tensor_host(ctx->resize, d, opts, win, lay, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip,
                                   &ctx->last_tensor_route);
 }
 
 }   // extern "C++"
 
-int lanczos_resize_tensor_validate(const lanczos_resize_desc* d, const lanczos_tensor_out* t) {
+int lanczos_resize_tensor_window_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win,
+                                          const lanczos_tensor_out* t) {
     lz::RsTensorOut lay;
-    return lz::tensor_validate(d, t, 4, &lay);
+    return lz::tensor_validate(d, win, t, 4, &lay);
+}
+
+int lanczos_resize_tensor_validate(const lanczos_resize_desc* d, const lanczos_tensor_out* t) {
+    return lanczos_resize_tensor_window_validate(d, nullptr, t);
 }
 
 int lanczos_tensor_lut_normalize(int channels, const float* mean, const float* std, float* lut) {
@@ -1258,17 +1305,34 @@ int lanczos_tensor_lut_normalize(int channels, const float* mean, const float* s
 int lanczos_resize_tensor_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                  const lanczos_tensor_out* t, const void* d_in, void* d_out, int frames,
                                  size_t in_frame_stride, size_t out_frame_stride, void* stream) {
-    return tensor_device(ctx, d, opts, t, 4, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+    return tensor_device(ctx, d, opts, nullptr, t, 4, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+}
+
+int lanczos_resize_tensor_window_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                        const lanczos_resize_window* win, const lanczos_tensor_out* t, const void* d_in,
+                                        void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+    return tensor_device(ctx, d, opts, win, t, 4, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
 }
 
 int lanczos_resize_tensor_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                const lanczos_tensor_out* t, const void* in, void* out, int frames) {
-    return tensor_host(ctx, d, opts, t, 4, in, out, frames);
+    return tensor_host(ctx, d, opts, nullptr, t, 4, in, out, frames);
+}
+
+int lanczos_resize_tensor_window_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                      const lanczos_resize_window* win, const lanczos_tensor_out* t, const void* in, void* out,
+                                      int frames) {
+    return tensor_host(ctx, d, opts, win, t, 4, in, out, frames);
+}
+
+int lanczos_resize_tensor16_window_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win,
+                                            const lanczos_tensor16_out* t) {
+    lz::RsTensorOut lay;
+    return lz::tensor_validate(d, win, t, 2, &lay);
 }
 
 int lanczos_resize_tensor16_validate(const lanczos_resize_desc* d, const lanczos_tensor16_out* t) {
-    lz::RsTensorOut lay;
-    return lz::tensor_validate(d, t, 2, &lay);
+    return lanczos_resize_tensor16_window_validate(d, nullptr, t);
 }
 
 int lanczos_tensor_lut_convert16(const float* in, int n, int format, uint16_t* out) {
@@ -1285,12 +1349,25 @@ int lanczos_tensor16_lut_normalize(int channels, const float* mean, const float*
 int lanczos_resize_tensor16_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                    const lanczos_tensor16_out* t, const void* d_in, void* d_out, int frames,
                                    size_t in_frame_stride, size_t out_frame_stride, void* stream) {
-    return tensor_device(ctx, d, opts, t, 2, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+    return tensor_device(ctx, d, opts, nullptr, t, 2, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+}
+
+int lanczos_resize_tensor16_window_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                          const lanczos_resize_window* win, const lanczos_tensor16_out* t, const void* d_in,
+                                          void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride,
+                                          void* stream) {
+    return tensor_device(ctx, d, opts, win, t, 2, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
 }
 
 int lanczos_resize_tensor16_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                  const lanczos_tensor16_out* t, const void* in, void* out, int frames) {
-    return tensor_host(ctx, d, opts, t, 2, in, out, frames);
+    return tensor_host(ctx, d, opts, nullptr, t, 2, in, out, frames);
+}
+
+int lanczos_resize_tensor16_window_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                        const lanczos_resize_window* win, const lanczos_tensor16_out* t, const void* in,
+                                        void* out, int frames) {
+    return tensor_host(ctx, d, opts, win, t, 2, in, out, frames);
 }
 
 int lanczos_last_tensor_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_tensor_route : 0; }

@@ -24,6 +24,11 @@
 // `first` still indexes the whole axis, and the kernels are the ones above.  reducing_gap puts lanczos_reduce.hip in front:
 // reduce into context scratch, then the resize of the reduced frames with the box that remains (resize_resolve).
 //
+// A window of the output (lanczos_resize_window) changes no table and no kernel: the tables stay those of the full axes, cached
+// under the full axes' keys, and every launch gets them from the window's first output on, with the window's extent as its
+// output size.  Plan, scratch and output strides follow the window.  Only the request that changes neither axis has device
+// code of its own for it, the crop copy k_rs_crop (lanczos_resize_nearest.hip).
+//
 // The arithmetic is Pillow's and exact by construction; RsSample<BPS> says how for each width.
 #include "lanczos_resize.hpp"
 
@@ -227,6 +232,52 @@ int resize_resolve(const lanczos_resize_desc* d, const lanczos_resize_opts* o, R
     return LANCZOS_OK;
 }
 
+int resize_window_resolve(const lanczos_resize_desc* d, const lanczos_resize_window* win, RsWindow* w) {
+    *w = RsWindow{0, 0, d->out_w, d->out_h};
+    if (!win) return LANCZOS_OK;
+    for (int32_t r : win->reserved)
+        if (r != 0) return LANCZOS_ERR_BAD_ARG;
+    if (win->x0 < 0 || win->w < 1 || win->w > d->out_w || win->x0 > d->out_w - win->w) return LANCZOS_ERR_BAD_ARG;
+    if (win->y0 < 0 || win->h < 1 || win->h > d->out_h || win->y0 > d->out_h - win->h) return LANCZOS_ERR_BAD_ARG;
+    *w = RsWindow{win->x0, win->y0, win->w, win->h};
+    return LANCZOS_OK;
+}
+
+// An axis that runs reads the union of its outputs' tap ranges (an index per output for LANCZOS_FILTER_NEAREST, whose count
+// is 1); an idle one is only cropped.  With a gap that reduces, the reduction covers the whole safe box whatever the window.
+int resize_window_source(const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                         int32_t rect[4]) {
+    RsResolved r;
+    RsWindow w;
+    int rc = resize_resolve(d, o, &r);
+    if (rc == LANCZOS_OK) rc = resize_window_resolve(d, win, &w);
+    if (rc != LANCZOS_OK) return rc;
+    if (r.reduces()) {
+        for (int i = 0; i < 4; i++) rect[i] = r.rb[i];
+        return LANCZOS_OK;
+    }
+    const struct {
+        bool runs;
+        int in_n, out_n, o0, n;
+        RsSpan span;
+    } axes[2] = {{r.need_h, d->in_w, d->out_w, w.x0, w.w, r.h}, {r.need_v, d->in_h, d->out_h, w.y0, w.h, r.v}};
+    for (int ax = 0; ax < 2; ax++) {
+        int lo = axes[ax].o0, hi = axes[ax].o0 + axes[ax].n;
+        if (axes[ax].runs) {
+            ResizeAxisHost t;
+            if (!resize_build_axis(axes[ax].in_n, axes[ax].out_n, d->a, resize_filter(d), axes[ax].span, &t, resize_bps(d) > 1))
+                return LANCZOS_ERR_UNSUPPORTED;
+            lo = axes[ax].in_n, hi = 0;
+            for (int i = axes[ax].o0; i < axes[ax].o0 + axes[ax].n; i++) {
+                lo = std::min(lo, t.first[i]);
+                hi = std::max(hi, t.first[i] + t.count[i]);
+            }
+        }
+        rect[ax] = lo, rect[ax + 2] = hi;
+    }
+    return LANCZOS_OK;
+}
+
 // ---- kernels -----------------------------------------------------------------------------------------------------
 
 constexpr int kRsFusedMaxLds = 80 * 1024;   // at least two fused workgroups per CU (160 KiB of LDS)
@@ -412,29 +463,30 @@ static int rs_scratch(ResizeState* st, ResizeState::Block* blk, size_t bytes, hi
     return LANCZOS_OK;
 }
 
-// the fused kernel's launch shape for this request, both of whose passes run (false: it cannot run it)
-bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H, const ResizeAxisHost& V, int frames,
-                   RsFusedPlan* fp) {
+// the fused kernel's launch shape for this request, both of whose passes run (false: it cannot run it).  The output is that
+// of the two views, a window of d's
+bool rs_fused_plan(const lanczos_resize_desc* d, const RsAxisView& H, const RsAxisView& V, int frames, RsFusedPlan* fp) {
     const int bps = resize_bps(d);
     const int C = d->channels * bps;   // bytes per pixel
+    const int out_w = H.n, out_h = V.n;
     if ((long long)d->in_w * d->in_h * C + 4 >= (1ll << 31)) return false;   // 32-bit buffer offsets
-    if ((long long)d->out_w * d->out_h * C >= (1ll << 31)) return false;
+    if ((long long)out_w * out_h * C >= (1ll << 31)) return false;
     const bool small = resize_filter(d) != LANCZOS_FILTER_LANCZOS;   // the instances with 3 and 5 taps
     fp->K = rs_bucket(H.ksize, small);
     if (!fp->K) return false;
     const int SW = rs_strip_width(d->channels, bps);
     const int NE = (fp->K * C + 3) / 4;
-    fp->strips = (d->out_w + SW - 1) / SW;
+    fp->strips = (out_w + SW - 1) / SW;
     int span_dw = 0;
     for (int s = 0; s < fp->strips; s++) {
-        const int x0 = s * SW, x1 = std::min(d->out_w, x0 + SW) - 1;
+        const int x0 = s * SW, x1 = std::min(out_w, x0 + SW) - 1;
         const int hoffb = (H.first[x1] - H.first[x0]) * C;
         span_dw = std::max(span_dw, ((3 + hoffb) >> 2) + NE + 1);
     }
     fp->stage_dw = span_dw;
     int ring = 1;
-    for (int o0 = 0; o0 < d->out_h; o0 += kRsOB) {
-        const int last = std::min(o0 + kRsOB, d->out_h) - 1;
+    for (int o0 = 0; o0 < out_h; o0 += kRsOB) {
+        const int last = std::min(o0 + kRsOB, out_h) - 1;
         ring = std::max(ring, V.first[last] + V.count[last] - V.first[o0]);
     }
     fp->ring_rows = ring;
@@ -445,19 +497,22 @@ bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H, const 
     fp->lds = lds();
     if (fp->lds > (size_t)kRsFusedMaxLds) return false;
     // row chunks: enough workgroups to fill the chip, each chunk a whole number of march steps
-    int rpc = (d->out_h + kRsOB - 1) / kRsOB * kRsOB;
+    int rpc = (out_h + kRsOB - 1) / kRsOB * kRsOB;
     const long long base = (long long)fp->strips * frames;
-    while (base * ((d->out_h + rpc - 1) / rpc) < kRsTargetWgs && rpc > kRsRowsPerChunkMin)
+    while (base * ((out_h + rpc - 1) / rpc) < kRsTargetWgs && rpc > kRsRowsPerChunkMin)
         rpc = std::max(kRsRowsPerChunkMin, (rpc / 2 + kRsOB - 1) / kRsOB * kRsOB);
     fp->rows_per_chunk = rpc;
-    fp->chunks = (d->out_h + rpc - 1) / rpc;
+    fp->chunks = (out_h + rpc - 1) / rpc;
     return (long long)fp->strips * fp->chunks < (1ll << 31);
 }
 
-int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o, int frames, lanczos_resize_plan_ex* out) {
+int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win, int frames,
+                     lanczos_resize_plan_ex* out) {
     memset(out, 0, sizeof(*out));
     RsResolved r;
-    const int rc = resize_resolve(d, o, &r);
+    RsWindow w;
+    int rc = resize_resolve(d, o, &r);
+    if (rc == LANCZOS_OK) rc = resize_window_resolve(d, win, &w);
     if (rc != LANCZOS_OK) return rc;
     out->fx = r.fx, out->fy = r.fy;
     for (int i = 0; i < 4; i++) out->safe_box[i] = r.rb[i], out->inner_box[i] = r.inner_box[i];
@@ -469,12 +524,12 @@ int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o,
     ResizeAxisHost H, V;
     if (r.need_v) {
         if (!resize_build_axis(r.inner.in_h, r.inner.out_h, d->a, filter, r.v, &V, u16)) return LANCZOS_ERR_UNSUPPORTED;
-        if (r.need_h) rs_mid_rows(V, &out->mid_row0, &out->mid_rows);
+        if (r.need_h) rs_mid_rows(rs_axis_view(V, w.y0, w.h), &out->mid_row0, &out->mid_rows);
     }
     if (!r.need_h || !r.need_v) return LANCZOS_OK;   // as resize_device: no table for an idle axis, nothing to fuse
     if (!resize_build_axis(r.inner.in_w, r.inner.out_w, d->a, filter, r.h, &H, u16)) return LANCZOS_ERR_UNSUPPORTED;
     RsFusedPlan fp;
-    if (!rs_fused_plan(&r.inner, H, V, frames, &fp)) return LANCZOS_OK;
+    if (!rs_fused_plan(&r.inner, rs_axis_view(H, w.x0, w.w), rs_axis_view(V, w.y0, w.h), frames, &fp)) return LANCZOS_OK;
     lanczos_resize_plan* in = &out->inner;
     in->fused = 1;
     in->K = fp.K, in->strips = fp.strips, in->rows_per_chunk = fp.rows_per_chunk, in->chunks = fp.chunks;
@@ -484,8 +539,9 @@ int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o,
 }
 
 // One pass of the two-pass path over `rows` rows of `n_cols` samples of `bps` bytes; src / dst row pitches in samples, frame
-// strides in bytes.  alpha: the LANCZOS_RESIZE_ALPHA kernels (8-bit, a thread per pixel); `only`: the other pass does not run
-static hipError_t rs_launch_pass(int bps, bool horizontal, const ResizeAxis* ax, int channels, const uint8_t* src, size_t src_fs,
+// strides in bytes.  alpha: the LANCZOS_RESIZE_ALPHA kernels (8-bit, a thread per pixel); `only`: the other pass does not run.
+// o0: the output of the axis the pass starts at (a window); the kernels count their outputs from it
+static hipError_t rs_launch_pass(int bps, bool horizontal, const ResizeAxis* ax, int o0, int channels, const uint8_t* src, size_t src_fs,
                                  size_t src_pitch, uint8_t* dst, size_t dst_fs, size_t dst_pitch, int n_cols, int rows, int frames,
                                  hipStream_t stream, bool alpha, bool only) {
     if (alpha && bps != 1) return hipErrorInvalidValue;
@@ -494,7 +550,9 @@ static hipError_t rs_launch_pass(int bps, bool horizontal, const ResizeAxis* ax,
         RsPass<typename S::coeff_t> p{};
         p.src_fs = src_fs, p.dst_fs = dst_fs, p.src_pitch = src_pitch, p.dst_pitch = dst_pitch;
         p.n_cols = n_cols, p.channels = channels;
-        p.first = ax->first(), p.count = ax->count(), p.coeffs = ax->coeffs<typename S::coeff_t>(), p.ksize = ax->host.ksize;
+        p.ksize = ax->host.ksize;
+        p.first = ax->first() + o0, p.count = ax->count() + o0;
+        p.coeffs = ax->coeffs<typename S::coeff_t>() + (size_t)o0 * p.ksize;
         void (*kern)(RsPass<typename S::coeff_t>) = horizontal ? k_rs_pass_h<S> : k_rs_pass_v<S>;
         if constexpr (S::BPS == 1) {   // alpha is 8-bit only (checked above)
             if (alpha && horizontal) kern = only ? k_rs_h_alpha<true> : k_rs_h_alpha<false>;
@@ -519,9 +577,11 @@ static hipError_t rs_launch_pass(int bps, bool horizontal, const ResizeAxis* ax,
 // ones), sh / sv are the source spans of its two axes
 // tc: a tensor request, `out` / `out_fs` then being the element frames.  Where the fused kernel runs it stores them itself;
 // everything else writes its bytes to context scratch and k_rs_to_tensor follows
-static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh, RsSpan sv, const uint8_t* in, uint8_t* out,
-                        int frames, size_t in_fs, size_t out_fs, hipStream_t stream, int* last_kernel, int* last_hip,
-                        RsTensorCall* tc) {
+// win: the window of d's output that is stored, as a tightly packed win.w x win.h frame.  The passes that run and the tables
+// are those of the full request; plan, scratch and every launch are the window's
+static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh, RsSpan sv, const RsWindow& win,
+                        const uint8_t* in, uint8_t* out, int frames, size_t in_fs, size_t out_fs, hipStream_t stream,
+                        int* last_kernel, int* last_hip, RsTensorCall* tc) {
     const int C = d->channels;
     const size_t B = (size_t)resize_bps(d);   // bytes per sample
     const bool f32 = B == 4;
@@ -544,7 +604,8 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
         if (ax && !capturing) note_stream(ax->streams, stream);
 
     RsFusedPlan fp;
-    const bool fused_ok = !nearest && need_h && need_v && rs_fused_plan(d, H->host, V->host, frames, &fp);
+    const bool fused_ok = !nearest && need_h && need_v &&
+                          rs_fused_plan(d, rs_axis_view(H->host, win.x0, win.w), rs_axis_view(V->host, win.y0, win.h), frames, &fp);
     if (st->force == LANCZOS_RESIZE_FUSED && !fused_ok) return LANCZOS_ERR_UNSUPPORTED;
     const bool fused = fused_ok && st->force != LANCZOS_RESIZE_TWO_PASS;
     // 32-bit buffer offsets into the element frame: a larger one is converted, and refused where the fused kernel is forced
@@ -554,7 +615,7 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     uint8_t* const t_out = out;
     const size_t t_fs = out_fs;
     if (tc && !t_fused) {
-        const size_t bytes_fs = ((size_t)d->out_w * d->out_h * C + 3) & ~(size_t)3;
+        const size_t bytes_fs = ((size_t)win.w * win.h * C + 3) & ~(size_t)3;
         rc = rs_scratch(st, &st->tensor_bytes, (size_t)frames * bytes_fs, stream, capturing, last_hip);
         if (rc != LANCZOS_OK) return rc;
         out = (uint8_t*)st->tensor_bytes.p, out_fs = bytes_fs;
@@ -562,27 +623,32 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     // two passes: the horizontal one produces the rows the vertical taps read and no others, mid_rows of them from source
     // row mid_row0 on, and the scratch holds exactly those; the vertical pass indexes it through a base mid_row0 rows in
     // front of it, which it never dereferences below the block (its first tap is row mid_row0)
-    int mid_row0 = 0, mid_rows = d->in_h;
-    if (need_h && need_v) rs_mid_rows(V->host, &mid_row0, &mid_rows);
-    const size_t mid_pitch = (size_t)d->out_w * C * B, mid_fs = (size_t)mid_rows * mid_pitch;
+    // (a horizontal pass alone runs the window's rows, which are the source's)
+    int mid_row0 = win.y0, mid_rows = win.h;
+    if (need_h && need_v) rs_mid_rows(rs_axis_view(V->host, win.y0, win.h), &mid_row0, &mid_rows);
+    const size_t mid_pitch = (size_t)win.w * C * B, mid_fs = (size_t)mid_rows * mid_pitch;
     const size_t in_pitch = (size_t)d->in_w * C * B;
     hipError_t e = hipSuccess;
     if (fused) {
-        const RsFusedLaunch c{d, &fp, H, V, in, out, in_fs, out_fs, frames, tc, stream};
+        const RsFusedLaunch c{d, win, &fp, H, V, in, out, in_fs, out_fs, frames, tc, stream};
         e = t_fused ? (tc->t.elem == 2 ? rs_launch_fused<1, 2>(c) : rs_launch_fused<1, 4>(c))
             : f32   ? rs_launch_fused<4, 0>(c)
             : u16   ? rs_launch_fused<2, 0>(c)
                     : rs_launch_fused<1, 0>(c);
         *last_kernel = LANCZOS_KERNEL_RESIZE_FUSED;
     } else if (nearest) {
-        e = rs_nearest_launch(in, out, d->in_w, d->out_w, d->out_h, C, (int)B, H->first(), V->first(), frames, in_fs, out_fs,
-                              stream);
+        e = rs_nearest_launch(in, out, d->in_w, win.w, win.h, C, (int)B, H->first() + win.x0, V->first() + win.y0, frames, in_fs,
+                              out_fs, stream);
         *last_kernel = LANCZOS_KERNEL_RESIZE_NEAREST;
-    } else if (!need_h && !need_v) {   // Pillow returns a copy (also of RGBA: no premultiply round trip)
-        e = hipMemcpy2DAsync(out, out_fs, in, in_fs, in_frame, frames, hipMemcpyDeviceToDevice, stream);
+    } else if (!need_h && !need_v) {   // Pillow returns a copy (also of RGBA: no premultiply round trip); a window crops it
+        if (win.whole(d))
+            e = hipMemcpy2DAsync(out, out_fs, in, in_fs, in_frame, frames, hipMemcpyDeviceToDevice, stream);
+        else
+            e = rs_crop_launch(in + (size_t)win.y0 * in_pitch + (size_t)win.x0 * C * B, out, in_pitch, (size_t)win.w * C * B,
+                               win.h, frames, in_fs, out_fs, stream);
         *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
     } else {
-        const int in_cols = d->in_w * C, out_cols = d->out_w * C;   // samples of a row
+        const int in_cols = d->in_w * C, out_cols = win.w * C;   // samples of a row
         const uint8_t* mid = in;   // what the vertical pass reads
         size_t v_fs = in_fs;
         if (need_h) {
@@ -593,18 +659,20 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
                 if (rc != LANCZOS_OK) return rc;
                 dst = (uint8_t*)st->scratch.p, dst_fs = mid_fs;
             }
-            e = rs_launch_pass((int)B, true, H, C, in + (size_t)mid_row0 * in_pitch, in_fs, in_cols, dst, dst_fs, out_cols,
-                               out_cols, mid_rows, frames, stream, alpha, !need_v);
+            e = rs_launch_pass((int)B, true, H, win.x0, C, in + (size_t)mid_row0 * in_pitch, in_fs, in_cols, dst, dst_fs,
+                               out_cols, out_cols, mid_rows, frames, stream, alpha, !need_v);
             mid = (const uint8_t*)((uintptr_t)dst - (uintptr_t)((size_t)mid_row0 * mid_pitch)), v_fs = dst_fs;
+        } else {
+            mid = in + (size_t)win.x0 * C * B;   // the vertical pass alone: the window's columns of the source's full rows
         }
         if (e == hipSuccess && need_v)
-            e = rs_launch_pass((int)B, false, V, C, mid, v_fs, out_cols, out, out_fs, out_cols, out_cols, d->out_h, frames,
-                               stream, alpha, !need_h);
+            e = rs_launch_pass((int)B, false, V, win.y0, C, mid, v_fs, need_h ? out_cols : in_cols, out, out_fs, out_cols,
+                               out_cols, win.h, frames, stream, alpha, !need_h);
         *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
     }
     if (tc) {
         if (!t_fused && e == hipSuccess)
-            e = rs_to_tensor_launch(out, out_fs, t_out, t_fs, d->out_w, d->out_h, C, tc->t, frames, stream);
+            e = rs_to_tensor_launch(out, out_fs, t_out, t_fs, win.w, win.h, C, tc->t, frames, stream);
         tc->route = t_fused ? LANCZOS_TENSOR_FUSED : LANCZOS_TENSOR_CONVERTED;
     }
     if (capturing) {   // a live graph may name these tables: they stay until the context goes
@@ -626,16 +694,18 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     return LANCZOS_OK;
 }
 
-int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* d_in, void* d_out,
-                  int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream, int* last_kernel,
-                  int* last_hip, RsTensorCall* tc) {
+int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                  const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream,
+                  int* last_kernel, int* last_hip, RsTensorCall* tc) {
     RsResolved r;
+    RsWindow w;
     int rc = resize_resolve(d, o, &r);
+    if (rc == LANCZOS_OK) rc = resize_window_resolve(d, win, &w);
     if (rc != LANCZOS_OK) return rc;
     const int C = d->channels;
     const size_t B = (size_t)resize_bps(d);   // bytes per sample
     const size_t in_frame = (size_t)d->in_w * d->in_h * C * B;
-    const size_t out_frame = tc ? tc->extent_bytes : (size_t)d->out_w * d->out_h * C * B;
+    const size_t out_frame = tc ? tc->extent_bytes : (size_t)w.w * w.h * C * B;
     const size_t in_fs = in_frame_stride ? in_frame_stride : in_frame;
     const size_t out_fs = out_frame_stride ? out_frame_stride : out_frame;
     if (in_fs < in_frame || out_fs < out_frame) return LANCZOS_ERR_BAD_ARG;
@@ -654,10 +724,10 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_r
             *last_hip = (int)e;
             return LANCZOS_ERR_HIP;
         }
-        return resize_inner(st, &r.inner, r.h, r.v, (const uint8_t*)st->reduced.p, (uint8_t*)d_out, frames, red_fs, out_fs,
+        return resize_inner(st, &r.inner, r.h, r.v, w, (const uint8_t*)st->reduced.p, (uint8_t*)d_out, frames, red_fs, out_fs,
                             stream, last_kernel, last_hip, tc);
     }
-    return resize_inner(st, d, r.h, r.v, in, (uint8_t*)d_out, frames, in_fs, out_fs, stream, last_kernel, last_hip, tc);
+    return resize_inner(st, d, r.h, r.v, w, in, (uint8_t*)d_out, frames, in_fs, out_fs, stream, last_kernel, last_hip, tc);
 }
 
 // staging buffers of the host entry points (resize and reduce)
@@ -706,32 +776,39 @@ static int rs_staged_call(ResizeState* st, const void* in, size_t in_bytes, void
     return LANCZOS_OK;
 }
 
-int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* in, void* out,
-                int frames, hipStream_t stream, int* last_kernel, int* last_hip) {
+int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip) {
     const size_t B = (size_t)resize_bps(d);
     if ((((uintptr_t)in | (uintptr_t)out) & (B - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
+    RsWindow w;
+    const int rc = resize_window_resolve(d, win, &w);
+    if (rc != LANCZOS_OK) return rc;
     const size_t in_bytes = (size_t)d->in_w * d->in_h * d->channels * B * frames;
-    const size_t out_bytes = (size_t)d->out_w * d->out_h * d->channels * B * frames;
+    const size_t out_bytes = (size_t)w.w * w.h * d->channels * B * frames;
     return rs_staged_call(st, in, in_bytes, out, out_bytes, {}, stream, last_hip, [&] {
-        return resize_device(st, d, o, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip);
+        return resize_device(st, d, o, win, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip);
     });
 }
 
 // The table rides behind the input frames in the input staging block.  The element frames go up before they come back, so
 // that the elements of `out` the strides leave out keep what they held.
-int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const RsTensorOut& t,
-                       const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip, int* route) {
+int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
+                       const lanczos_resize_window* win, const RsTensorOut& t, const void* in, void* out, int frames,
+                       hipStream_t stream, int* last_kernel, int* last_hip, int* route) {
     if (((uintptr_t)out & (uintptr_t)(t.elem - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
+    RsWindow w;
+    const int wrc = resize_window_resolve(d, win, &w);
+    if (wrc != LANCZOS_OK) return wrc;
     RsTensorCall tc;
     tc.t = t;
-    tc.extent_bytes = tensor_extent_bytes(d, t);
+    tc.extent_bytes = tensor_extent_bytes(d, w, t);
     const size_t in_bytes = (size_t)d->in_w * d->in_h * d->channels * frames;
     RsStagedExtra x;
     x.table = t.d_lut, x.table_at = (in_bytes + 255) & ~(size_t)255, x.table_bytes = (size_t)d->channels * 256 * t.elem;
     x.out_up = true;
     return rs_staged_call(st, in, in_bytes, out, tc.extent_bytes * frames, x, stream, last_hip, [&] {
         tc.t.d_lut = (const uint8_t*)st->stage_in + x.table_at;
-        const int rc = resize_device(st, d, o, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip, &tc);
+        const int rc = resize_device(st, d, o, win, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip, &tc);
         *route = tc.route;
         return rc;
     });

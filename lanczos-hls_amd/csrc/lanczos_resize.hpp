@@ -61,11 +61,32 @@ struct RsResolved {
     bool reduces() const { return fx > 1 || fy > 1; }
 };
 int resize_resolve(const lanczos_resize_desc* d, const lanczos_resize_opts* o, RsResolved* r);
-// the rows of the inner source the horizontal pass of the two-pass path produces: what the vertical taps read
-inline void rs_mid_rows(const ResizeAxisHost& V, int* row0, int* rows) {
-    *row0 = V.first.front();
-    *rows = V.first.back() + V.count.back() - *row0;
+
+// A window of the output (lanczos_resize_window), resolved: NULL is the whole output.  A windowed request runs the kernels of
+// the full request on slices of its tables -- outputs x0 .. x0 + w of the horizontal axis, y0 .. y0 + h of the vertical one --
+// so its sample (x, y) is the full request's (x0 + x, y0 + y) by construction.
+struct RsWindow {
+    int x0 = 0, y0 = 0, w = 0, h = 0;
+    bool whole(const lanczos_resize_desc* d) const { return x0 == 0 && y0 == 0 && w == d->out_w && h == d->out_h; }
+};
+int resize_window_resolve(const lanczos_resize_desc* d, const lanczos_resize_window* win, RsWindow* w);
+// `n` outputs of an axis from output `o0` on: what planning reads of the tables
+struct RsAxisView {
+    const int32_t *first, *count;
+    int n, ksize;
+    double scale;
+};
+inline RsAxisView rs_axis_view(const ResizeAxisHost& t, int o0, int n) {
+    return RsAxisView{t.first.data() + o0, t.count.data() + o0, n, t.ksize, t.scale};
 }
+// the rows of the inner source the horizontal pass of the two-pass path produces: what the vertical taps of V's outputs read
+inline void rs_mid_rows(const RsAxisView& V, int* row0, int* rows) {
+    *row0 = V.first[0];
+    *rows = V.first[V.n - 1] + V.count[V.n - 1] - *row0;
+}
+// the source rectangle (x0, y0, x1, y1) a windowed request's result depends on (lanczos_resize_window_source)
+int resize_window_source(const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                         int32_t rect[4]);
 
 inline bool resize_u16(const lanczos_resize_desc* d) { return (d->reserved[0] & LANCZOS_RESIZE_U16) != 0; }
 inline bool resize_f32(const lanczos_resize_desc* d) { return (d->reserved[0] & LANCZOS_RESIZE_F32) != 0; }
@@ -83,14 +104,15 @@ constexpr int rs_strip_width(int channels, int bps) {
 }
 
 // The fused kernel's launch shape for a request (false: it cannot run it).  H and V are the tables of the two axes, both of
-// which change size.  lanczos_resize_device plans with it; lanczos_resize_plan_host reports what it returns.
+// which run, cut to the window: the output is H.n x V.n pixels (d's out_w / out_h are not read).  lanczos_resize_device plans
+// with it; lanczos_resize_plan_host reports what it returns.
 struct RsFusedPlan {
     int K = 0, strips = 0, rows_per_chunk = 0, chunks = 0, ring_rows = 0, stage_rows = 0, stage_dw = 0;
     size_t lds = 0;
 };
-bool rs_fused_plan(const lanczos_resize_desc* d, const ResizeAxisHost& H, const ResizeAxisHost& V, int frames,
-                   RsFusedPlan* fp);
-int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o, int frames, lanczos_resize_plan_ex* out);
+bool rs_fused_plan(const lanczos_resize_desc* d, const RsAxisView& H, const RsAxisView& V, int frames, RsFusedPlan* fp);
+int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win, int frames,
+                     lanczos_resize_plan_ex* out);
 
 // One axis shape on the device: first | count | coeffs in one block (int32 coefficients, or double ones for 16-bit samples:
 // the two int32 arrays in front of them keep those 8-byte aligned).
@@ -145,15 +167,17 @@ struct RsTensorCall {
     size_t extent_bytes = 0;   // of one element frame: from its first element to its last
     int route = 0;
 };
-// t NULL: the caller passed no struct; reserved: its four words
-int tensor_validate(const lanczos_resize_desc* d, const RsTensorOut* t, const int32_t* reserved);
+// t NULL: the caller passed no struct; reserved: its four words.  The frame the strides describe is the window's (win NULL:
+// the whole output)
+int tensor_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const RsTensorOut* t,
+                    const int32_t* reserved);
 // the request of either public struct (T): *lay is filled where there is one
 template <class T>
-int tensor_validate(const lanczos_resize_desc* d, const T* t, int elem, RsTensorOut* lay) {
+int tensor_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const T* t, int elem, RsTensorOut* lay) {
     if (t) *lay = RsTensorOut{t->d_lut, t->chan_stride, t->row_stride, t->pix_stride, elem};
-    return tensor_validate(d, t ? lay : nullptr, t ? t->reserved : nullptr);
+    return tensor_validate(d, win, t ? lay : nullptr, t ? t->reserved : nullptr);
 }
-size_t tensor_extent_bytes(const lanczos_resize_desc* d, const RsTensorOut& t);
+size_t tensor_extent_bytes(const lanczos_resize_desc* d, const RsWindow& win, const RsTensorOut& t);
 void tensor_lut_normalize(int channels, const float* mean, const float* std, float* lut);
 // float32 -> bfloat16 (LANCZOS_TENSOR_BF16) or float16 (LANCZOS_TENSOR_F16) words, round to nearest even; false: no such format
 bool tensor_lut_convert16(const float* in, int n, int format, uint16_t* out);
@@ -162,15 +186,17 @@ bool tensor_lut_convert16(const float* in, int n, int format, uint16_t* out);
 hipError_t rs_to_tensor_launch(const uint8_t* src, size_t src_fs, uint8_t* out, size_t out_fs, int w, int h, int channels,
                                const RsTensorOut& t, int frames, hipStream_t stream);
 
-// The entry points (ctx->mu held, device set).  *last_kernel / *last_hip as in lanczos_ctx.  tc: a tensor request (NULL: bytes)
-int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* d_in, void* d_out,
-                  int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream, int* last_kernel,
-                  int* last_hip, RsTensorCall* tc = nullptr);
+// The entry points (ctx->mu held, device set).  *last_kernel / *last_hip as in lanczos_ctx.  tc: a tensor request (NULL: bytes).
+// win: the window of the output that is computed and stored, tightly packed (NULL: the whole output)
+int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                  const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream,
+                  int* last_kernel, int* last_hip, RsTensorCall* tc = nullptr);
 // host table (t.d_lut) and host buffers, element frames tensor_extent_bytes apart; synchronous
-int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const RsTensorOut& t,
-                       const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip, int* route);
-int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* in, void* out,
-                int frames, hipStream_t stream, int* last_kernel, int* last_hip);
+int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
+                       const lanczos_resize_window* win, const RsTensorOut& t, const void* in, void* out, int frames,
+                       hipStream_t stream, int* last_kernel, int* last_hip, int* route);
+int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip);
 
 // Reduce by whole factors (lanczos_reduce.hip): Pillow's Image.reduce over an integer box, 8-bit.  Arguments validated by
 // reduce_validate; the output rows are tightly packed.
@@ -183,9 +209,11 @@ int reduce_host(ResizeState* st, int in_w, int in_h, int channels, int fx, int f
                 void* out, int frames, hipStream_t stream, int* last_hip);
 
 // One request for the fused kernel, k_rs_fused<RsSample<BPS>, C, K, ALPHA, TENSOR> (lanczos_resize_fused.hpp): the instance
-// is that of d's channels and alpha flag and of the plan's K.  Frame strides in bytes.
+// is that of d's channels and alpha flag and of the plan's K.  Frame strides in bytes.  The kernel gets the tables from the
+// window's first outputs on and the window's extent as its output size; the plan is that of the window.
 struct RsFusedLaunch {
     const lanczos_resize_desc* d;
+    RsWindow win;
     const RsFusedPlan* fp;
     const ResizeAxis *H, *V;
     const uint8_t* in;
@@ -203,5 +231,9 @@ hipError_t rs_launch_fused(const RsFusedLaunch& c);
 hipError_t rs_nearest_launch(const uint8_t* in, uint8_t* out, int in_w, int out_w, int out_h, int channels, int bps,
                              const int32_t* hidx, const int32_t* vidx, int frames, size_t in_fs, size_t out_fs,
                              hipStream_t stream);
+// The crop of a resize that changes neither axis (k_rs_crop, beside the gather): `rows` rows of `row_bytes` bytes from `in`
+// (the window's first byte; rows in_pitch bytes apart) to tightly packed rows at `out`, every frame in one launch.
+hipError_t rs_crop_launch(const uint8_t* in, uint8_t* out, size_t in_pitch, size_t row_bytes, int rows, int frames,
+                          size_t in_fs, size_t out_fs, hipStream_t stream);
 
 }  // namespace lz

@@ -415,12 +415,14 @@ bool rs_dispatch_instance(int channels, int K, bool alpha, F&& f) {
 template <class KT>
 void rs_fill_fused(RsFused<KT>* g, const RsFusedLaunch& c) {
     const lanczos_resize_desc* d = c.d;
+    const RsWindow& w = c.win;   // the kernel's output is the window: its tables start at the window's first outputs
     g->in_pitch = d->in_w * d->channels * resize_bps(d);
-    g->out_pitch = d->out_w * d->channels * resize_bps(d);
-    g->in_h = d->in_h, g->out_w = d->out_w, g->out_h = d->out_h;
+    g->out_pitch = w.w * d->channels * resize_bps(d);
+    g->in_h = d->in_h, g->out_w = w.w, g->out_h = w.h;
     g->in_fs = c.in_fs, g->out_fs = c.out_fs;
-    g->hf = c.H->first(), g->hc = c.H->count(), g->hk = c.H->coeffs<KT>(), g->hks = c.H->host.ksize;
-    g->vf = c.V->first(), g->vc = c.V->count(), g->vk = c.V->coeffs<KT>(), g->vks = c.V->host.ksize;
+    g->hks = c.H->host.ksize, g->vks = c.V->host.ksize;
+    g->hf = c.H->first() + w.x0, g->hc = c.H->count() + w.x0, g->hk = c.H->coeffs<KT>() + (size_t)w.x0 * g->hks;
+    g->vf = c.V->first() + w.y0, g->vc = c.V->count() + w.y0, g->vk = c.V->coeffs<KT>() + (size_t)w.y0 * g->vks;
     g->strips = c.fp->strips, g->rows_per_chunk = c.fp->rows_per_chunk;
     g->ring_rows = c.fp->ring_rows, g->stage_rows = c.fp->stage_rows, g->stage_dw = c.fp->stage_dw;
 }

@@ -11,6 +11,14 @@
 //                pixel costs no byte stores.  Only the dwords a row shares with its neighbours (a row pitch or a base that
 //                is no dword multiple) go out sample by sample.
 //
+//   k_rs_crop    the window of a resize that changes neither axis (lanczos_resize_window with both passes idle): a copy of
+//                the window's rows into a tightly packed frame, for samples of any width (bytes are moved, never looked at:
+//                RGBA is not premultiplied, as in the plain copy).  As in the gather, a thread owns one dword of the stored
+//                row's ADDRESS grid and stores it whole -- a wave writes 256 contiguous bytes whatever the alignment of the two
+//                frames, also for an 8-bit source with an odd row pitch -- and loads it as one dword where the source lies
+//                on a dword as well, else as four bytes; only the dwords a row shares with its neighbours go out byte by
+//                byte.  The thread walks the frames from blockIdx.z in steps of the grid's depth: any frame count is one launch.
+//
 // Loads and stores are plain global accesses with 64-bit addresses: frames of any size, bases at any sample boundary.  Every
 // index is checked on the host to lie inside the source before a table is cached, and a store is predicated on its sample
 // lying inside the row.
@@ -95,6 +103,49 @@ hipError_t rs_nearest_launch(const uint8_t* in, uint8_t* out, int in_w, int out_
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+struct CropArgs {
+    const uint8_t* in;   // the window's first byte of frame 0
+    uint8_t* out;
+    unsigned long long in_fs, out_fs;         // frame strides (bytes)
+    unsigned long long in_pitch, out_pitch;   // bytes of a source row, of a stored row
+    int row_bytes;                            // of a stored row: at most 65535 pixels of 16 bytes
+    int frames;
+};
+
+__global__ __launch_bounds__(kRsThreads) void k_rs_crop(CropArgs g) {
+    const int q = blockIdx.x * kRsThreads + threadIdx.x;   // dword of the stored row's address grid
+    const unsigned long long y = blockIdx.y;
+    for (int f = blockIdx.z; f < g.frames; f += gridDim.z) {
+        const uint8_t* srow = g.in + f * g.in_fs + y * g.in_pitch;
+        uint8_t* orow = g.out + f * g.out_fs + y * g.out_pitch;
+        const int s0 = q * 4 - (int)((uintptr_t)orow & 3);   // the dword's first byte of the row
+        if (s0 >= g.row_bytes) continue;
+        if (s0 >= 0 && s0 + 4 <= g.row_bytes) {
+            const uint8_t* s = srow + s0;
+            const uint32_t v = ((uintptr_t)s & 3) == 0 ? *(const uint32_t*)s
+                                                      : (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16) | ((uint32_t)s[3] << 24);
+            *(uint32_t*)(orow + s0) = v;   // (orow - its offset in the dword) + 4 * q: aligned
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+                if (s0 + j >= 0 && s0 + j < g.row_bytes) orow[s0 + j] = srow[s0 + j];
+        }
+    }
+}
+
+hipError_t rs_crop_launch(const uint8_t* in, uint8_t* out, size_t in_pitch, size_t row_bytes, int rows, int frames,
+                          size_t in_fs, size_t out_fs, hipStream_t stream) {
+    CropArgs g{};
+    g.in = in, g.out = out;
+    g.in_fs = in_fs, g.out_fs = out_fs;
+    g.in_pitch = in_pitch, g.out_pitch = row_bytes;
+    g.row_bytes = (int)row_bytes, g.frames = frames;
+    const int ndw = ((int)row_bytes + 6) / 4;   // dwords of the address grid a row can touch, a misaligned start included
+    const dim3 grid((ndw + kRsThreads - 1) / kRsThreads, rows, std::min(frames, 65535));
+    hipLaunchKernelGGL(k_rs_crop, grid, dim3(kRsThreads), 0, stream, g);
+    return hipGetLastError();
 }
 
 }  // namespace lz

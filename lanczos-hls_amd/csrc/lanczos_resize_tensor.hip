@@ -19,14 +19,17 @@ namespace lz {
 
 // ---- host: validation, the normalisation table --------------------------------------------------------------------
 
-size_t tensor_extent_bytes(const lanczos_resize_desc* d, const RsTensorOut& t) {
-    return (size_t)((d->channels - 1) * t.chan_stride + (d->out_h - 1) * t.row_stride + (d->out_w - 1) * t.pix_stride + 1) *
+size_t tensor_extent_bytes(const lanczos_resize_desc* d, const RsWindow& win, const RsTensorOut& t) {
+    return (size_t)((d->channels - 1) * t.chan_stride + (win.h - 1) * t.row_stride + (win.w - 1) * t.pix_stride + 1) *
            (size_t)t.elem;
 }
 
-int tensor_validate(const lanczos_resize_desc* d, const RsTensorOut* t, const int32_t* reserved) {
-    const int rc = resize_validate(d);
+int tensor_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const RsTensorOut* t,
+                    const int32_t* reserved) {
+    int rc = resize_validate(d);
     if (rc != LANCZOS_OK) return rc;
+    RsWindow w;   // the frame the strides describe
+    if ((rc = resize_window_resolve(d, win, &w)) != LANCZOS_OK) return rc;
     if (!t || !t->d_lut) return LANCZOS_ERR_BAD_ARG;
     for (int i = 0; i < 4; i++)
         if (reserved[i] != 0) return LANCZOS_ERR_BAD_ARG;
@@ -34,7 +37,7 @@ int tensor_validate(const lanczos_resize_desc* d, const RsTensorOut* t, const in
     if (d->reserved[0] & (LANCZOS_RESIZE_U16 | LANCZOS_RESIZE_F32)) return LANCZOS_ERR_UNSUPPORTED;
     struct Dim {
         int64_t stride, extent;
-    } dims[3] = {{t->chan_stride, d->channels}, {t->row_stride, d->out_h}, {t->pix_stride, d->out_w}};
+    } dims[3] = {{t->chan_stride, d->channels}, {t->row_stride, w.h}, {t->pix_stride, w.w}};
     constexpr int64_t kMaxStride = (int64_t)1 << 40;   // stride x extent stays far inside int64
     for (const Dim& m : dims)
         if (m.stride <= 0 || m.stride > kMaxStride) return LANCZOS_ERR_BAD_ARG;

@@ -5,7 +5,7 @@
  *   lanczos_upscale <in.(png|ppm|pgm)> <out.(png|ppm|pgm)> [--scale N[/D]] [--a A] [--channels C]
  *                   [--exact | --hls] [--device D] [--repeat K]
  *   lanczos_upscale <in> <out> --size WxH [--filter box|bilinear|hamming|bicubic|nearest|lanczos] [--box x0,y0,x1,y1]
- *                   [--reducing-gap G] [--a A] [--channels C | --alpha] [--device D] [--repeat K]
+ *                   [--reducing-gap G] [--window x0,y0,w,h] [--a A] [--channels C | --alpha] [--device D] [--repeat K]
  *                   (resize to any size, downscaling included, through lanczos_resize_host: Pillow's Image.resize with
  *                   LANCZOS, not the reference's model; refuses --scale, --exact, --hls and the multi-device flags.
  *                   --alpha: four channels, the fourth straight alpha, resized as Pillow's mode RGBA and written as an
@@ -13,7 +13,9 @@
  *                   --box: resize that region of the source (source pixels, fractions allowed), Image.resize's box;
  *                   --reducing-gap G >= 1: reduce by whole factors first, Image.resize's reducing_gap; not with --alpha;
  *                   --filter: Image.resize's resample, default lanczos; every other filter needs a = 3, nearest takes no
- *                   --reducing-gap)
+ *                   --reducing-gap;
+ *                   --window: compute and write only that window of the WxH output (output pixels), a w x h image:
+ *                   Image.resize(...).crop((x0, y0, x0 + w, y0 + h)) through lanczos_resize_window_host)
  *                   [--devices 0-7 | 0,2,5] [--frames F] [--split frames|rows] [--root]   (several GPUs of one node, plain C:
  *                   the image is replicated into a batch of F frames and the batch -- or every frame's rows -- is split
  *                   over the devices by lanczos_resample_multi_host; the first result frame is written.  --root: the batch
@@ -50,9 +52,10 @@ static const char* const filter_names[6] = {"lanczos", "box", "bilinear", "hammi
 
 /* --size WxH: one frame through lanczos_resize_host */
 static int resize_main(const char* out_path, const uint8_t* img, int width, int height, int channels, int out_w, int out_h,
-                       int a, int alpha, int filter, int device, int repeat, const double* box, double gap) {
+                       int a, int alpha, int filter, int device, int repeat, const double* box, double gap, const int* window) {
     lanczos_resize_desc d;
     lanczos_resize_opts o;
+    lanczos_resize_window win;
     lanczos_resize_plan_ex plan;
     int rc = lanczos_resize_desc_init_ex(&d, width, height, out_w, out_h, channels, a,
                                          (alpha ? LANCZOS_RESIZE_ALPHA : 0) | LANCZOS_RESIZE_FILTER(filter));
@@ -60,7 +63,11 @@ static int resize_main(const char* out_path, const uint8_t* img, int width, int 
     if (rc == LANCZOS_OK) {
         if (box) memcpy(o.box, box, sizeof(o.box));
         o.reducing_gap = gap;
-        rc = lanczos_resize_plan_host_ex(&d, &o, 1, &plan); /* validates the box and the gap */
+        rc = lanczos_resize_window_init(&win, &d);
+    }
+    if (rc == LANCZOS_OK) {
+        if (window) win.x0 = window[0], win.y0 = window[1], win.w = window[2], win.h = window[3];
+        rc = lanczos_resize_window_plan_host(&d, &o, &win, 1, &plan); /* validates the box, the gap and the window */
     }
     if (rc != LANCZOS_OK) {
         printf("Cannot resize %i x %i to %i x %i: %s.\n", width, height, out_w, out_h, lanczos_strerror(rc));
@@ -72,7 +79,13 @@ static int resize_main(const char* out_path, const uint8_t* img, int width, int 
     if (plan.fx > 1 || plan.fy > 1)
         printf("Reduce by %d x %d over %d,%d,%d,%d to %d x %d first\n", plan.fx, plan.fy, plan.safe_box[0], plan.safe_box[1],
                plan.safe_box[2], plan.safe_box[3], plan.reduced_w, plan.reduced_h);
-    uint8_t* out = (uint8_t*)malloc((size_t)out_w * out_h * channels);
+    if (window) {
+        int32_t rect[4] = {0, 0, 0, 0};
+        (void)lanczos_resize_window_source(&d, &o, &win, rect);
+        printf("Window %d,%d,%d,%d of the output, from source pixels %d,%d to %d,%d\n", win.x0, win.y0, win.w, win.h, rect[0],
+               rect[1], rect[2], rect[3]);
+    }
+    uint8_t* out = (uint8_t*)malloc((size_t)win.w * win.h * channels);
     lanczos_ctx* ctx = NULL;
     rc = lanczos_create(&ctx, device);
     if (rc != LANCZOS_OK || !out) {
@@ -81,16 +94,16 @@ static int resize_main(const char* out_path, const uint8_t* img, int width, int 
     }
     struct timespec t0;
     clock_gettime(CLOCK_MONOTONIC, &t0);
-    for (int k = 0; k < repeat && rc == LANCZOS_OK; k++) rc = lanczos_resize_host_ex(ctx, &d, &o, img, out, 1);
+    for (int k = 0; k < repeat && rc == LANCZOS_OK; k++) rc = lanczos_resize_window_host(ctx, &d, &o, &win, img, out, 1);
     if (rc != LANCZOS_OK) {
         printf("lanczos_resize failed: %s (hip error %d)\n", lanczos_strerror(rc), lanczos_last_hip_error(ctx));
         return EXIT_FAILURE;
     }
     const double ms = ms_since(&t0) / repeat;
     printf("%dx%d->%dx%d_%d: %.3f ms per frame incl. PCIe copies (%.1f Mpix/s), kernel family %d\n", width, height, out_w,
-           out_h, a, ms, out_w * (double)out_h / ms / 1e3, lanczos_last_kernel(ctx));
-    const int ok = ends_with(out_path, ".png") ? lz_image_write_png(out_path, out_w, out_h, channels, out, out_w * channels)
-                                               : lz_image_write_pnm(out_path, out_w, out_h, channels, out, out_w * channels);
+           out_h, a, ms, win.w * (double)win.h / ms / 1e3, lanczos_last_kernel(ctx));
+    const int ok = ends_with(out_path, ".png") ? lz_image_write_png(out_path, win.w, win.h, channels, out, win.w * channels)
+                                               : lz_image_write_pnm(out_path, win.w, win.h, channels, out, win.w * channels);
     lanczos_destroy(ctx);
     free(out);
     if (!ok) {
@@ -107,6 +120,7 @@ int main(int argc, char* argv[]) {
     int size_w = 0, size_h = 0, have_size = 0, upscale_only = 0; /* upscale_only: a flag --size cannot go with */
     int alpha = 0, have_channels = 0, have_box = 0, have_gap = 0, filter = LANCZOS_FILTER_LANCZOS, have_filter = 0;
     double box[4] = {0, 0, 0, 0}, gap = 0.0;
+    int window[4] = {0, 0, 0, 0}, have_window = 0;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--size") && i + 1 < argc) {
             have_size = 1;
@@ -114,6 +128,9 @@ int main(int argc, char* argv[]) {
         } else if (!strcmp(argv[i], "--box") && i + 1 < argc) {
             char tail;
             have_box = sscanf(argv[++i], "%lf,%lf,%lf,%lf%c", &box[0], &box[1], &box[2], &box[3], &tail) == 4 ? 1 : -1;
+        } else if (!strcmp(argv[i], "--window") && i + 1 < argc) {
+            char tail;
+            have_window = sscanf(argv[++i], "%d,%d,%d,%d%c", &window[0], &window[1], &window[2], &window[3], &tail) == 4 ? 1 : -1;
         } else if (!strcmp(argv[i], "--reducing-gap") && i + 1 < argc) {
             char tail;
             have_gap = sscanf(argv[++i], "%lf%c", &gap, &tail) == 1 && gap >= 1.0 ? 1 : -1;
@@ -175,7 +192,7 @@ int main(int argc, char* argv[]) {
         fprintf(stderr, "usage: %s <in.png|ppm> <out.png|ppm> [--scale N[/D]] [--a A] [--channels C] [--exact|--hls] "
                         "[--device D] [--repeat K] [--devices 0-7|0,2,5] [--frames F] [--split frames|rows] [--root]\n"
                         "       %s <in.png|ppm> <out.png|ppm> --size WxH [--filter box|bilinear|hamming|bicubic|nearest|lanczos] "
-                        "[--box x0,y0,x1,y1] [--reducing-gap G] [--a A] "
+                        "[--box x0,y0,x1,y1] [--reducing-gap G] [--window x0,y0,w,h] [--a A] "
                         "[--channels C | --alpha] [--device D] [--repeat K]\n",
                 argv[0], argv[0]);
         return EXIT_FAILURE;
@@ -194,6 +211,10 @@ int main(int argc, char* argv[]) {
     }
     if ((have_box || have_gap) && !have_size) {
         fprintf(stderr, "--box and --reducing-gap need --size\n");
+        return EXIT_FAILURE;
+    }
+    if (have_window < 0 || (have_window && !have_size)) {
+        fprintf(stderr, "--window takes four integers, x0,y0,w,h in pixels of the --size output, and needs --size\n");
         return EXIT_FAILURE;
     }
     if (have_filter < 0 || (have_filter && !have_size)) {
@@ -218,7 +239,7 @@ int main(int argc, char* argv[]) {
     }
     if (have_size) {
         const int rc = resize_main(out_path, img, width, height, want_channels, size_w, size_h, a, alpha, filter, device, repeat,
-                                   have_box ? box : NULL, have_gap ? gap : 0.0);
+                                   have_box ? box : NULL, have_gap ? gap : 0.0, have_window ? window : NULL);
         lz_image_free(img);
         return rc;
     }

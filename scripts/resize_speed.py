@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """resize_speed.py -- speed of the resize-to-any-size entry (lanczos_resize_device) on one MI355X.
 
-    python scripts/resize_speed.py [--steps K] [--warmup W] [--rounds R] [--only W1,W3,A1,U1,F1] [--routes rgbx,three_step]
+    python scripts/resize_speed.py [--steps K] [--warmup W] [--rounds R] [--only W1,W3,A1,U1,F1,WIN1] [--routes rgbx,three_step]
                                    [--pillow] [--parent-lib PATH]
 
 One JSON line per (workload, path).  Discipline as bench.py's: the frames are resident in HBM and the steps cycle through
@@ -64,6 +64,16 @@ T1h, T2h, T4h and TPh are T1, T2, T4 and TP to bfloat16 (lanczos_resize_tensor16
                 entry replaces
   f32           the float32 tensor call alone
 Frame 0 of fused, converted and f32_cast are compared bit for bit before timing; a last line gives the ratios.
+
+WIN1, WIN1h, WIN2 and WINC are resize-and-crop workloads (a window of the output, lanczos_resize_window_device; --only
+WIN1,WIN1h,WIN2,WINC; a build with the entry).  WIN1: 256 frames of 500x375 RGB8 -> 341x256, window center_window(341, 256, 224, 224), bytes out.  WIN1h:
+the same into normalised bfloat16 CHW.  WIN2: 32 frames of 3840x2160 -> 1920x1080, window the centre 1280x720.  WINC: 256 frames of 341x256 at their own size (neither
+axis runs: the full call is the plain copy, the windowed one the crop copy k_rs_crop), window the centre 224x224.  Routes:
+  windowed      the call with the window: only the window's pixels are computed and stored
+  full_slice    the full call, then torch's slice of the window and .contiguous() on the same stream: what the window replaces
+  full          the full call alone
+  parent_full   the full call alone on another build of the library (--parent-lib PATH: the parent commit's)
+Frame 0 of windowed and full_slice are compared byte for byte before timing; a last line gives the ratios and the two plans.
 
 --pillow adds Pillow's single-core time of one frame of each workload (if Pillow imports; else "not available"); for U1 and
 U4 that is the time of one I;16 plane (a frame has three), for F1 and F4 that of one F plane.
@@ -340,10 +350,18 @@ class ParentLib:
         self.lib.lanczos_resize_device_ex.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                       ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t,
                                                       ctypes.c_void_p]
+        if hasattr(self.lib, "lanczos_resize_tensor16_device"):
+            self.lib.lanczos_resize_tensor16_device.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_int, ctypes.c_size_t,
+                                                                                        ctypes.c_size_t, ctypes.c_void_p]
         self.lib.lanczos_destroy.argtypes = [ctypes.c_void_p]
         if self.lib.lanczos_create(ctypes.byref(self.h), 0) != 0:
             raise SystemExit(f"{path}: lanczos_create failed")
         self.byref = ctypes.byref
+
+    def resize_tensor16_device(self, d, t, d_in, d_out, frames, stream):
+        rc = self.lib.lanczos_resize_tensor16_device(self.h, self.byref(d), None, self.byref(t), d_in, d_out, frames, 0, 0, stream)
+        if rc != 0:
+            raise SystemExit(f"parent lanczos_resize_tensor16_device: {rc}")
 
     def resize_device(self, d, d_in, d_out, frames, stream, opts=None):
         rc = self.lib.lanczos_resize_device_ex(self.h, self.byref(d), self.byref(opts) if opts is not None else None, d_in,
@@ -475,6 +493,89 @@ def run_tensor16(name, args, ctx, torch):
     torch.cuda.empty_cache()
 
 
+WINDOW_WORKLOADS = {   # name: (in_w, in_h, out_w, out_h, channels, frames, crop (w, h) taken from the centre, bfloat16 CHW out)
+    "WIN1": (500, 375, 341, 256, 3, 256, (224, 224), False),
+    "WIN1h": (500, 375, 341, 256, 3, 256, (224, 224), True),
+    "WIN2": (3840, 2160, 1920, 1080, 3, 32, (1280, 720), False),
+    "WINC": (341, 256, 341, 256, 3, 256, (224, 224), False),   # neither axis runs: the crop copy against torch's slice
+}
+
+
+def run_window(name, args, ctx, torch, parent):
+    iw, ih, ow, oh, c, f, crop, half = WINDOW_WORKLOADS[name]
+    window = L.center_window(ow, oh, *crop)
+    x0, y0, w, h = window
+    in_fb, out_fb, win_fb = iw * ih * c, ow * oh * c, w * h * c
+    sets = max(2, -(-2 * 256 * 2 ** 20 // (f * in_fb)) + 1)
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    dt = torch.bfloat16 if half else torch.uint8
+    xs = [torch.randint(0, 256, (f * in_fb,), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(sets)]
+    ys = [torch.empty(f * win_fb, dtype=dt, device="cuda") for _ in range(sets)]      # windowed results
+    fulls = [torch.empty(f * out_fb, dtype=dt, device="cuda") for _ in range(sets)]   # full results
+    d = L.resize_desc(iw, ih, ow, oh, c)
+    win = L.resize_window(d, window)
+    s = torch.cuda.current_stream().cuda_stream
+    ctx.resize_force(L.RESIZE_AUTO)
+    if half:
+        lut16 = torch.from_numpy(L.normalize_lut(c, IMAGENET_MEAN, IMAGENET_STD, dtype="bfloat16").view(np.int16)).cuda()
+        t_win = L.tensor16_out(lut16.data_ptr(), L.tensor_strides("chw", w, h, c))
+        t_full = L.tensor16_out(lut16.data_ptr(), L.tensor_strides("chw", ow, oh, c))
+    bits = (lambda y: y.view(torch.int16)) if half else (lambda y: y)
+
+    def windowed(i):
+        if half:
+            ctx.resize_tensor_device(d, xs[i % sets].data_ptr(), ys[i % sets].data_ptr(), f, None, t_win, stream=s, window=win)
+        else:
+            ctx.resize_device(d, xs[i % sets].data_ptr(), ys[i % sets].data_ptr(), f, 0, 0, s, window=win)
+        return bits(ys[i % sets][:win_fb])
+
+    def full(i):
+        if half:
+            ctx.resize_tensor_device(d, xs[i % sets].data_ptr(), fulls[i % sets].data_ptr(), f, None, t_full, stream=s)
+        else:
+            ctx.resize_device(d, xs[i % sets].data_ptr(), fulls[i % sets].data_ptr(), f, 0, 0, s)
+        return bits(fulls[i % sets][:out_fb])
+
+    def full_slice(i):
+        full(i)
+        if half:
+            t = fulls[i % sets].view(f, c, oh, ow)[:, :, y0:y0 + h, x0:x0 + w]
+        else:
+            t = fulls[i % sets].view(f, oh, ow, c)[:, y0:y0 + h, x0:x0 + w]
+        return bits(t.contiguous().view(-1)[:win_fb])
+
+    def parent_full(i):
+        if half:
+            parent.resize_tensor16_device(d, t_full, xs[i % sets].data_ptr(), fulls[i % sets].data_ptr(), f, s)
+        else:
+            parent.resize_device(d, xs[i % sets].data_ptr(), fulls[i % sets].data_ptr(), f, s)
+        return bits(fulls[i % sets][:out_fb])
+
+    routes = {"windowed": windowed, "full_slice": full_slice, "full": full}
+    if parent is not None:
+        routes["parent_full"] = parent_full
+    e = 2 if half else 1
+    rect = L.resize_window_source(d, win)
+    inb = {rn: f * in_fb for rn in routes}
+    inb["windowed"] = f * (rect[2] - rect[0]) * (rect[3] - rect[1]) * c
+    outb = {rn: e * f * out_fb for rn in routes}
+    outb["windowed"] = e * f * win_fb
+    outb["full_slice"] = e * f * (out_fb + 2 * win_fb)
+    us = run_routes(name, f"{iw}x{ih}->{ow}x{oh} C{c} window {window}" + (" bfloat16 chw" if half else ""), f, routes, inb, outb,
+                    args, ctx, torch, check=(("windowed", "full_slice"),))
+    pw, pf = L.resize_window_plan_host(d, win, f), L.resize_window_plan_host(d, None, f)
+    plan = lambda p: {"fused": p.inner.fused, "K": p.inner.K, "strips": p.inner.strips, "chunks": p.inner.chunks,
+                      "rows_per_chunk": p.inner.rows_per_chunk, "mid_rows": p.mid_rows}
+    print(json.dumps({"workload": name, "windowed_over_full_slice": round(us["windowed"] / us["full_slice"], 3),
+                      "windowed_over_full": round(us["windowed"] / us["full"], 3),
+                      "windowed_over_parent_full": round(us["windowed"] / us["parent_full"], 3) if parent else None,
+                      "full_over_parent_full": round(us["full"] / us["parent_full"], 3) if parent else None,
+                      "pixels_full_over_window": round(ow * oh / (w * h), 3), "source_rect": rect,
+                      "plan_windowed": plan(pw), "plan_full": plan(pf), "measured": True}), flush=True)
+    del xs, ys, fulls
+    torch.cuda.empty_cache()
+
+
 def run_gap(name, args, ctx, torch):
     iw, ih, ow, oh, c, a, f = WORKLOADS["W5"]
     in_fb, out_fb = iw * ih * c, ow * oh * c
@@ -559,7 +660,8 @@ def main():
     ap.add_argument("--only", default="W1,W2,W3,W4,W5,A1,A4,U1,U4")
     ap.add_argument("--routes", default=",".join(ROUTES))
     ap.add_argument("--pillow", action="store_true")
-    ap.add_argument("--parent-lib", default=None, help="another build of liblanczos_hip.so for the parent_bytes route of T*")
+    ap.add_argument("--parent-lib", default=None,
+                    help="another build of liblanczos_hip.so for the parent_bytes route of T* and the parent_full route of WIN*")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -567,7 +669,9 @@ def main():
     ctx = L.Context(0)
     parent = ParentLib(args.parent_lib) if args.parent_lib else None
     for name in args.only.split(","):
-        if name in TENSOR_WORKLOADS:
+        if name in WINDOW_WORKLOADS:
+            run_window(name, args, ctx, torch, parent)
+        elif name in TENSOR_WORKLOADS:
             run_tensor(name, args, ctx, torch, parent)
         elif name.endswith("h") and name[:-1] in TENSOR_WORKLOADS:
             run_tensor16(name, args, ctx, torch)
