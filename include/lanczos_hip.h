@@ -617,6 +617,28 @@ int lanczos_last_route(const lanczos_ctx* ctx);
 #define LANCZOS_ROUTE_PREFIX_BEHIND 3    /* k_prefix (LDS row arrays) behind the main kernel */
 #define LANCZOS_ROUTE_PREFIX_STREAMED 4  /* k_prefix_stream (LDS rings, any depth) behind the main kernel */
 int lanczos_last_hip_error(const lanczos_ctx* ctx);
+/* The workgroup table of the last k_march launch of the last upscale call on the context (the table decides which rows of which
+ * (strip, frame) pair every marching workgroup computes; for tests and A/B runs).  `entries`, if not NULL, receives up to
+ * `capacity` int32 quadruples (frame, strip, m_b, m_e) in table order -- workgroup-major, info->segs entries per workgroup,
+ * m_b >= m_e: an empty segment -- where [m_b, m_e) are the input rows m = floor(y / scale) whose output rows the segment stores.
+ * Returns the number of quadruples the table holds (info->workgroups * info->segs), or a negative LANCZOS_ERR_*.  All of `info`
+ * is zero and 0 is returned where the last call launched no k_march, after a resize, reduce or layout call and on a new
+ * context, as for lanczos_last_route.  Host data only: the call touches neither a stream nor the device. */
+typedef struct lanczos_march_table_info {
+    int32_t workgroups;   /* marching workgroups of the launch (riding prefix workgroups not counted) */
+    int32_t segs;         /* table entries per workgroup */
+    int32_t mode;         /* LANCZOS_MARCH_TABLE_* : which branch of the builder made the table */
+    int32_t rank_aware;   /* 1: shares weighted by the slots' speeds, 0: equal chunks */
+    int32_t strips, frames;
+    int32_t m_lo, m_hi;   /* the rows the table shares out */
+    int32_t wg_per_cu;    /* resident marching workgroups per CU the table was laid out for */
+    int32_t cus;
+    int32_t reserved[6];
+} lanczos_march_table_info;
+#define LANCZOS_MARCH_TABLE_NONE 0
+#define LANCZOS_MARCH_TABLE_A 1   /* one workgroup per CU slot, a share may run across (strip, frame) pairs */
+#define LANCZOS_MARCH_TABLE_B 2   /* whole chunks of one pair, one segment per workgroup */
+int lanczos_last_march_table(const lanczos_ctx* ctx, lanczos_march_table_info* info, int32_t* entries, int capacity);
 /* Force a kernel family for A/B tests: LANCZOS_KERNEL_NONE (auto), _GENERIC or _FAST. */
 int lanczos_force_kernel(lanczos_ctx* ctx, int family);
 const char* lanczos_strerror(int code);

@@ -49,7 +49,7 @@ ABI_SYMBOLS = [
     "lanczos_resample_host",
     "lanczos_resample_device", "lanczos_planar_to_interleaved_device", "lanczos_interleaved_to_planar_device",
     "lanczos_resample_planar_device", "lanczos_u8", "lanczos_timing_enable", "lanczos_timing_read",
-    "lanczos_last_kernel", "lanczos_last_route", "lanczos_last_hip_error", "lanczos_force_kernel", "lanczos_strerror",
+    "lanczos_last_kernel", "lanczos_last_route", "lanczos_last_march_table", "lanczos_last_hip_error", "lanczos_force_kernel", "lanczos_strerror",
     "lanczos_version",
     "lanczos_partition_frames", "lanczos_partition_rows", "lanczos_multi_create", "lanczos_multi_destroy",
     "lanczos_multi_devices", "lanczos_resample_multi_host", "lanczos_resample_multi_root",
@@ -81,6 +81,23 @@ class Route(collections.namedtuple("Route", "main prefix launches prefix_seen"))
     def __str__(self):
         seen = "+".join(ROUTE_PREFIX_NAMES[r] for r in sorted(self.prefix_seen))
         return f"{ROUTE_MAIN_NAMES[self.main]}+{ROUTE_PREFIX_NAMES[self.prefix]} x{self.launches} (prefix routes seen: {seen})"
+
+
+MARCH_TABLE_NONE, MARCH_TABLE_A, MARCH_TABLE_B = 0, 1, 2   # lanczos_march_table_info.mode
+
+
+class MarchTableInfoC(ctypes.Structure):   # include/lanczos_hip.h: lanczos_march_table_info
+    _fields_ = [(n, ctypes.c_int32) for n in ("workgroups", "segs", "mode", "rank_aware", "strips", "frames", "m_lo", "m_hi",
+                                               "wg_per_cu", "cus")] + [("reserved", ctypes.c_int32 * 6)]
+
+
+class MarchTableInfo(collections.namedtuple("MarchTableInfo", "workgroups segs mode rank_aware strips frames m_lo m_hi wg_per_cu cus")):
+    """lanczos_last_march_table's info: the shape of the workgroup table the last k_march launch used (mode: MARCH_TABLE_*)."""
+
+    def __str__(self):
+        return (f"mode {'-AB'[self.mode]}, {'rank-aware' if self.rank_aware else 'equal'}: {self.workgroups} workgroups x {self.segs} "
+                f"segment(s) for {self.strips} strips x {self.frames} frames, rows [{self.m_lo}, {self.m_hi}), "
+                f"{self.wg_per_cu} workgroups/CU x {self.cus} CUs")
 
 
 class LanczosError(RuntimeError):
@@ -209,6 +226,8 @@ def _lib():
         L.lanczos_last_hip_error.argtypes = [c_void_p]
         if hasattr(L, "lanczos_last_route"):   # (an older build loaded through LANCZOS_LIB has none)
             L.lanczos_last_route.argtypes = [c_void_p]
+        if hasattr(L, "lanczos_last_march_table"):
+            L.lanczos_last_march_table.argtypes = [c_void_p, ctypes.POINTER(MarchTableInfoC), ctypes.POINTER(ctypes.c_int32), c_int]
         L.lanczos_force_kernel.argtypes = [c_void_p, c_int]
         L.lanczos_strerror.argtypes = [c_int]
         L.lanczos_partition_frames.argtypes = [c_int, c_int, c_int, PI, PI]
@@ -946,6 +965,20 @@ class Context:
         r = _lib().lanczos_last_route(self._h)
         seen = (r >> 8) & 0xff
         return Route(r & 0xf, (r >> 4) & 0xf, (r >> 16) & 0x7fff, frozenset(i for i in range(8) if seen >> i & 1))
+
+    def last_march_table(self):
+        """The workgroup table of the last k_march launch of the last upscale call: (MarchTableInfo, int32 array
+        [workgroups][segs][4] of (frame, strip, m_b, m_e); m_b >= m_e: an empty segment).  All zero, and an empty array, where
+        that call launched no k_march."""
+        info = MarchTableInfoC()
+        n = _lib().lanczos_last_march_table(self._h, ctypes.byref(info), None, 0)
+        if n < 0:
+            raise LanczosError(-n, "lanczos_last_march_table")
+        tab = np.zeros((info.workgroups, info.segs, 4), np.int32)
+        if n:
+            assert n == info.workgroups * info.segs
+            _lib().lanczos_last_march_table(self._h, ctypes.byref(info), tab.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n)
+        return MarchTableInfo(*(getattr(info, f) for f in MarchTableInfo._fields)), tab
 
     def force_kernel(self, family):
         _check(_lib().lanczos_force_kernel(self._h, family), "lanczos_force_kernel")

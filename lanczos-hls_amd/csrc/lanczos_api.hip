@@ -118,7 +118,10 @@ namespace {
 
 // lanczos_last_route: an upscale entry point starts a call with route_begin; every launch of the call reports itself with
 // route_launch at the point where it is issued
-void route_begin(lanczos_ctx* ctx) { ctx->last_route = ctx->route_launches = ctx->route_seen = ctx->last_tensor_route = 0; }
+void route_begin(lanczos_ctx* ctx) {
+    ctx->last_route = ctx->route_launches = ctx->route_seen = ctx->last_tensor_route = 0;
+    ctx->wg_tabs.last_valid = false;   // lanczos_last_march_table: no k_march launch in this call yet
+}
 void route_launch(lanczos_ctx* ctx, int main_kernel, int prefix_route) {
     if (ctx->route_launches < 0x7fff) ctx->route_launches++;
     ctx->route_seen |= 1 << prefix_route;
@@ -608,6 +611,28 @@ int lanczos_last_kernel(const lanczos_ctx* ctx) { return ctx ? ctx->last_kernel 
 int lanczos_last_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_route : 0; }
 int lanczos_last_hip_error(const lanczos_ctx* ctx) { return ctx ? ctx->last_hip : 0; }
 
+// Host data only (the item's page-locked source block): no stream, no device.  Like the other last_* reports it is read between
+// the context's calls, by the thread that made them.
+int lanczos_last_march_table(const lanczos_ctx* ctx, lanczos_march_table_info* info, int32_t* entries, int capacity) {
+    if (!ctx || !info || capacity < 0) return -LANCZOS_ERR_BAD_ARG;
+    memset(info, 0, sizeof(*info));
+    const lz::WgTabCache::Item* it = ctx->wg_tabs.last();
+    if (!it) return 0;
+    info->workgroups = it->n;
+    info->segs = it->segs;
+    info->mode = it->mode_a ? LANCZOS_MARCH_TABLE_A : LANCZOS_MARCH_TABLE_B;
+    info->rank_aware = it->balanced ? 1 : 0;
+    info->strips = (int32_t)it->key[1], info->frames = (int32_t)it->key[2];
+    info->m_lo = (int32_t)it->key[3], info->m_hi = (int32_t)it->key[4];
+    info->wg_per_cu = (int32_t)it->key[5], info->cus = (int32_t)it->key[6];
+    const int total = it->n * it->segs;
+    if (entries) {
+        static_assert(sizeof(lz::WgEntry) == 4 * sizeof(int32_t), "a table entry is four int32");
+        memcpy(entries, it->host, sizeof(lz::WgEntry) * (size_t)(capacity < total ? capacity : total));
+    }
+    return total;
+}
+
 int lanczos_force_kernel(lanczos_ctx* ctx, int family) {
     if (!ctx || family < LANCZOS_KERNEL_NONE || family > LANCZOS_KERNEL_FAST) return LANCZOS_ERR_BAD_ARG;  // (_HLS follows the mode)
     ctx->force = family;
@@ -1061,9 +1086,15 @@ int lanczos_resample_planar_device(lanczos_ctx* ctx, const lanczos_desc* d, cons
     rc = lanczos_resample_device(ctx, &whole, ctx->planar_in, ctx->planar_out, frames, 0, 0, stream);
     if (rc != LANCZOS_OK) return rc;
     const int route = ctx->last_route;   // (the layout call behind it reports none: the planar call reports its resample)
+    long long table_key[8];
+    memcpy(table_key, ctx->wg_tabs.last_key, sizeof(table_key));
+    const bool table_valid = ctx->wg_tabs.last_valid;
     rc = lanczos_interleaved_to_planar_device(ctx, ctx->planar_out, d_out_planar, d->out_w, d->out_h, d->channels,
                                               d->bytes_per_sample, frames, stream);
-    if (rc == LANCZOS_OK) ctx->last_route = route;
+    if (rc == LANCZOS_OK) {
+        ctx->last_route = route;
+        if (table_valid) ctx->wg_tabs.note_last(table_key);
+    }
     return rc;
 }
 

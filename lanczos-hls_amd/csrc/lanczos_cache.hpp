@@ -116,6 +116,7 @@ struct WgTabCacheT {
         Entry* host = nullptr;             // page-locked source of the upload (stays valid while the copy is in flight)
         int n = 0, segs = 1;
         bool balanced = false;
+        bool mode_a = false;               // march_build_table's branch: one workgroup per CU slot (A) or whole chunks (B)
         hipEvent_t uploaded = nullptr;     // recorded behind the upload; none where the upload was eager (complete)
         hipStream_t upload_stream = nullptr;
         std::vector<hipStream_t> streams;  // streams this shape was uploaded / launched on (not captured ones)
@@ -160,6 +161,20 @@ struct WgTabCacheT {
     // pref_frames followed by the rest (32 + 16 frames: 207 + 113 us)
     int max_one_round_frames = 0;
     int wg_per_cu = 0;   // resident marching workgroups per CU of the instance the last query was about
+    // lanczos_last_march_table: the shape of the last k_march launch (march_launch_t notes it where it launches, the entry points
+    // clear it when a call begins).  A key, not a pointer: items move on every insert.
+    long long last_key[8] = {};
+    bool last_valid = false;
+    void note_last(const long long (&key)[8]) {
+        memcpy(last_key, key, sizeof(key));
+        last_valid = true;
+    }
+    const Item* last() const {   // (no recency update: a report is not a use)
+        if (!last_valid) return nullptr;
+        for (const Item& it : items)
+            if (memcmp(it.key, last_key, sizeof(last_key)) == 0) return &it;
+        return nullptr;
+    }
 
     Item* find(const long long (&key)[8]) {
         for (size_t i = 0; i < items.size(); i++)
@@ -172,11 +187,11 @@ struct WgTabCacheT {
     // uploads `tab` on `stream` (eagerly on the private stream if `stream` is being captured) and returns the new item
     // (nullptr + *err on failure).  Pointers to items are valid until the next insert().
     Item* insert(const long long (&key)[8], const std::vector<Entry>& tab, int n, int segs, bool balanced, hipStream_t stream,
-                 hipError_t* err) {
+                 hipError_t* err, bool mode_a = false) {
         retired.reap(false);
         Item it;
         memcpy(it.key, key, sizeof(key));
-        it.n = n, it.segs = segs, it.balanced = balanced;
+        it.n = n, it.segs = segs, it.balanced = balanced, it.mode_a = mode_a;
         const size_t bytes = sizeof(Entry) * tab.size();
         const bool capturing = stream_capturing(stream);   // hipStreamIsCapturing: the upload below must not become a graph node
         hipStream_t up = stream;

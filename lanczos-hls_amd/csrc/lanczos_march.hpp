@@ -1268,7 +1268,8 @@ inline int march_align_rows(int rows, int ms, int taps) {
 }
 
 // Fills `tab` ([block id][segs]) for `strips` x `frames` pairs whose rows [m_lo, m_hi) are shared out among the marching
-// workgroups.  Returns the number of marching workgroups; *segs_out = table entries per workgroup.
+// workgroups.  Returns the number of marching workgroups; *segs_out = table entries per workgroup, *mode_a_out (if asked for) =
+// which of the two branches below built the table.
 //   mode A (large batches): exactly one workgroup per CU slot.  The pairs are dealt to the XCDs in consecutive runs (neighbouring
 //     strips share an L2); inside an XCD the pairs' rows form one line that is cut into consecutive shares proportional to
 //     the slots' speeds.  A share may run from one pair into the next: up to 3 segments, cuts moved off pair boundaries'
@@ -1276,7 +1277,8 @@ inline int march_align_rows(int rows, int ms, int taps) {
 //   mode B: whole chunks (one segment), equal, or -- one resident round of >= 2 chunks per pair -- fast slots paired with
 //     slow ones and the pair's rows split by speed.
 inline int march_build_table(std::vector<WgEntry>& tab, int* segs_out, int strips, int frames, int m_lo, int m_hi, int ms, int taps,
-                             int nb, int cus, int nwaves, bool* balanced_out) {
+                             int nb, int cus, int nwaves, bool* balanced_out, bool* mode_a_out = nullptr) {
+    if (mode_a_out) *mode_a_out = false;
     const int m_rows = m_hi - m_lo, slots = nb * cus, pairs = strips * frames;
     const int nx = 8, cu_x = cus / nx > 0 ? cus / nx : 1;
     const MarchSlotSpeed sp = march_slot_speed(nb, nwaves);
@@ -1353,6 +1355,7 @@ inline int march_build_table(std::vector<WgEntry>& tab, int* segs_out, int strip
             for (size_t k = 0; k < share[b].size(); k++) tab[(size_t)b * max_segs + k] = share[b][k];
         *segs_out = max_segs;
         *balanced_out = true;
+        if (mode_a_out) *mode_a_out = true;
         return n;
     }
     // ---------------------------------------------------------------- mode B
@@ -1529,15 +1532,16 @@ inline hipError_t march_launch_t(const lanczos_desc& d, const FrameGeom& g_in, c
     if (!item) {
         std::vector<WgEntry> tab;
         int segs = 1;
-        bool balanced = false;
-        const int n = march_build_table(tab, &segs, strips, g.frames, m_lo, m_hi, K::MS, K::TAPS, nb, cus, K::NWAVES, &balanced);
+        bool balanced = false, mode_a = false;
+        const int n = march_build_table(tab, &segs, strips, g.frames, m_lo, m_hi, K::MS, K::TAPS, nb, cus, K::NWAVES, &balanced, &mode_a);
         hipError_t e = hipSuccess;
-        item = cache->insert(key, tab, n, segs, balanced, stream, &e);
+        item = cache->insert(key, tab, n, segs, balanced, stream, &e, mode_a);
         if (!item) return e;
         if (env().verbose)
-            fprintf(stderr, "lanczos: k_march table: %d workgroups x %d segment(s) for %d strips x %d frames, rows [%d, %d): %s shares\n", item->n,
-                    item->segs, strips, g.frames, m_lo, m_hi, item->balanced ? "rank-aware" : "equal");
+            fprintf(stderr, "lanczos: k_march table: mode %c, %d workgroups x %d segment(s) for %d strips x %d frames, rows [%d, %d): %s shares\n",
+                    item->mode_a ? 'A' : 'B', item->n, item->segs, strips, g.frames, m_lo, m_hi, item->balanced ? "rank-aware" : "equal");
     }
+    cache->note_last(key);   // lanczos_last_march_table
     {
         const hipError_t e = cache->use(item, stream);   // behind the upload
         if (e != hipSuccess) return e;

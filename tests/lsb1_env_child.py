@@ -1,6 +1,7 @@
 """Child process of test_parity_gpu.py::test_production_switches_change_no_result (not collected by pytest): the library reads
 its environment switches once per process (csrc/lanczos_env.hpp), so every switch is tried in a fresh process.  Runs the
-requests of SWITCH_REQUESTS in both parity modes and writes the outputs to the .npz named on the command line."""
+requests of SWITCH_REQUESTS in both parity modes and writes the outputs, the routes and the reported k_march workgroup tables to the
+.npz named on the command line."""
 import os
 import sys
 
@@ -34,6 +35,9 @@ def main(out_path):
                 res[f"{name}:{tag}:kernel"] = np.array(ctx.last_kernel())
                 r = ctx.last_route()
                 res[f"{name}:{tag}:route"] = np.array([r.main, r.prefix, r.launches])
+                info, tab = ctx.last_march_table()   # of the call's last launch; all zero where that was no k_march
+                res[f"{name}:{tag}:table_info"] = np.array(info)
+                res[f"{name}:{tag}:table"] = tab
     finally:
         ctx.close()
     np.savez(out_path, **res)

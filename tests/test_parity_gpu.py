@@ -551,19 +551,30 @@ def test_full_size_config5_digest(ctx):
 
 
 def test_full_size_config5_batch_every_frame(ctx):
-    """Config 5 as a batch of 4 identical frames (PARITY UNPINNED BY THE REFERENCE, as above): this launch shape takes the
-    marching kernel's table mode A -- one workgroup per CU slot, shares that run from one (strip, frame) pair into the next
-    (lanczos_march.hpp: march_build_table).  Every frame must equal frame 0 and frame 0 the committed digest."""
+    """Config 5 as a batch of 4 identical frames (PARITY UNPINNED BY THE REFERENCE, as above): the host entry sends them out as two
+    launches of two frames, and this launch shape (120 (strip, frame) pairs, two 8-wave workgroups per CU: no rank-aware
+    shares) takes the marching kernel's table mode A -- one workgroup per CU slot, shares that run from one pair into the next
+    (lanczos_march.hpp: march_build_table) -- which the reported table must confirm in both modes.  Every frame must equal
+    frame 0 and frame 0 the committed digest."""
+    import march_table_cfg as M
     with open(os.path.join(GOLD, "kat_digests_u16.json")) as f:
         kat = json.load(f)["digests"]
     w, h, c, sn, sd, a = C5
     frame = _c5_frame()
     batch = np.ascontiguousarray(np.broadcast_to(frame, (4,) + frame.shape))
+    def mode_a(tag):
+        info, tab = ctx.last_march_table()
+        assert info.mode == L.MARCH_TABLE_A and info.workgroups == info.wg_per_cu * info.cus, f"{tag}: {info}"
+        assert not M.partition_errors(info, tab), f"{tag}: {M.partition_errors(info, tab)}"
+        sm = M.summary(info, tab)
+        assert sm["strip_changes"] >= 1, f"{tag}: no share runs from one strip into the next: {M.describe(info, tab)}"
     got = ctx.resample(batch, sn, sd, a, L.MODE_EXACT)
+    mode_a("EXACT")
     assert f"{O.fnv1a64(got[0]):016x}" == kat["3840x2160_7680x4320_2-1_a4_c4"]
     for i in range(1, 4):
         assert np.array_equal(got[i], got[0]), f"EXACT: frame {i} differs from frame 0"
     fast = ctx.resample(batch, sn, sd, a, L.MODE_LSB1)
+    mode_a("LSB1")
     _cmp(fast[0], got[0], L.MODE_LSB1, "config 5 batch, frame 0", _req(ctx, frame, sn, sd, a))
     for i in range(1, 4):
         assert np.array_equal(fast[i], fast[0]), f"LSB1: frame {i} differs from frame 0"
@@ -941,8 +952,12 @@ def _run_switch_child(tmp_path, name, env_extra):
 def test_production_switches_change_no_result(tmp_path):
     """none of the production switches changes a result.  Each in a fresh child process (the environment is
     read once per process), one at a time: EXACT identical to the reference, LSB1 within its contract, and the switches that
-    only re-partition the work give LSB1 bytes identical to the default run."""
+    only re-partition the work give LSB1 bytes identical to the default run.  The workgroup table every run reports for the
+    config 2 batch partitions its launch and has the shape the switch asks for.  The two 1080p frames go out as two launches of
+    one frame, 15 (strip, frame) pairs each: mode A needs 64 pairs, so LANCZOS_MARCH_SEGS=1 cannot reach it here and every run
+    reports mode B (tests/test_march_table_gpu.py forces mode A on batches that admit it)."""
     import lsb1_env_child as E
+    import march_table_cfg as M
     reqs = {name: (gen(), sn, sd, a) for name, (gen, sn, sd, a) in E.SWITCH_REQUESTS.items()}
     want = {name: [_oracle(f, sn, sd, a, threads=16) for f in frames] for name, (frames, sn, sd, a) in reqs.items()}
     base = _run_switch_child(tmp_path, "default", {})
@@ -966,6 +981,17 @@ def test_production_switches_change_no_result(tmp_path):
                 if var == "LANCZOS_SEPARATE_PREFIX" and name == "config2_batch":
                     want_route = (L.ROUTE_MAIN_MARCH, L.ROUTE_PREFIX_BEHIND)
                 assert (main, prefix) == want_route, f"{tag} {name} {mtag}: route {main}+{prefix}, expected {want_route}"
+                info, tab = M.Info(*(int(v) for v in res[f"{name}:{mtag}:table_info"])), res[f"{name}:{mtag}:table"]
+                if main != L.ROUTE_MAIN_MARCH:
+                    assert tuple(info) == (0,) * 10 and tab.size == 0, f"{tag} {name} {mtag}: a table reported without k_march: {info}"
+                    continue
+                assert not M.partition_errors(info, tab), f"{tag} {name} {mtag}: {M.partition_errors(info, tab)}"
+                assert (info.mode, info.segs, info.strips, info.frames, info.m_lo, info.m_hi) == (L.MARCH_TABLE_B, 1, 15, 1, 2, 1080), \
+                    f"{tag} {name} {mtag}: {M.describe(info, tab)}"
+                if tag == "LANCZOS_MARCH_WGS=7":      # seven workgroups for 15 pairs: one chunk per pair
+                    assert info.workgroups == 15 and not info.rank_aware, f"{tag} {name} {mtag}: {M.describe(info, tab)}"
+                if tag == "LANCZOS_RANK_WEIGHTS=0":
+                    assert not info.rank_aware, f"{tag} {name} {mtag}: {M.describe(info, tab)}"
             for i in range(len(frames)):
                 _cmp(exact[i], want[name][i], L.MODE_EXACT, f"{tag} {name} frame {i}")
                 _cmp(lsb1[i], want[name][i], L.MODE_LSB1, f"{tag} {name} frame {i}", (frames[i], sn, sd, a, fam))
