@@ -7,6 +7,11 @@
     boundary, integer-phase rows copies of the H intermediate, prefix rows and k_generic bit-exact)
   * edge cases the reference's loop bounds imply: tiny images (every tap range clipped), a = 2/3/4,
     1/3/4 channels, non-integer scales, the in-place prefix rows, strips, batches, u16
+  * per-instance coverage lives in modules of its own: every k_ratp / k_rat instance in tests/test_rational_instances_gpu.py, every
+    k_fast tile-kernel instance (whole on contents that steer its FIXUP worklist, in row strips, in batches with strides off
+    16 bytes) and both k_generic kernels (in strips and strided batches, 16-bit samples forced) in
+    tests/test_fast_instances_gpu.py; test_every_integer_scale_instance below stays as the one-frame pass over both the marching
+    and the tile kernel
 """
 import json
 import os
