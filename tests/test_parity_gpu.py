@@ -10,8 +10,9 @@
   * per-instance coverage lives in modules of its own: every k_ratp / k_rat instance in tests/test_rational_instances_gpu.py, every
     k_fast tile-kernel instance (whole on contents that steer its FIXUP worklist, in row strips, in batches with strides off
     16 bytes) and both k_generic kernels (in strips and strided batches, 16-bit samples forced) in
-    tests/test_fast_instances_gpu.py; test_every_integer_scale_instance below stays as the one-frame pass over both the marching
-    and the tile kernel
+    tests/test_fast_instances_gpu.py, every k_march instance on contents that steer its fix-up worklist and its f64 redo rows in
+    tests/test_march_fixup_gpu.py (what each content reaches: tests/test_march_fixup_cfg.py, no GPU);
+    test_every_integer_scale_instance below stays as the one-frame pass over both the marching and the tile kernel
 """
 import json
 import os
