@@ -569,6 +569,60 @@ int lanczos_resize_tensor16_window_host(lanczos_ctx* ctx, const lanczos_resize_d
                                         const lanczos_resize_window* win, const lanczos_tensor16_out* t, const void* in,
                                         void* out, int frames);
 
+/* ---- tensor outputs with a channel map and per-frame flips (BGR -> RGB, RGBA -> RGB, RandomHorizontalFlip) ----
+ * One entry point for every tensor request: the element width is a field and the window an optional argument.  With (w, h)
+ * the extent of the window (of the whole output when win is NULL), P(f, y, x, c) the byte lanczos_resize_window_device stores
+ * for the same descriptor, options and window, and m_f = (flip ^ d_flip[f]) & 3 (d_flip NULL: flip & 3):
+ *   out[f][oc * chan_stride + Y * row_stride + X * pix_stride] = lut[oc * 256 + P(f, y, x, src_channel[oc])]
+ *   X = (m_f & 1) ? w - 1 - x : x        Y = (m_f & 2) ? h - 1 - y : y
+ * The table is indexed by the OUTPUT channel: mean / std of lanczos_tensor_lut_normalize are given in output order.  The map is
+ * injective: it reorders and drops channels and cannot replicate them (a stride-0 expand on the caller's side does that).  A
+ * source channel that no oc names is not stored anywhere.  With LANCZOS_RESIZE_ALPHA the colour samples are un-premultiplied
+ * as in the byte request whether or not alpha itself is kept: RGBA -> RGB with alpha is Pillow's resize in mode RGBA followed
+ * by .convert("RGB").  Flips mirror inside the frame: the set of addresses written per frame does not depend on them.
+ * The overlap rule, the frame's extent, the minimum out_frame_stride and the 2^31-byte limit of the fused route are those of
+ * the tensor entries above with `channels` read as out_channels and "element" as elem_bytes: the extent is
+ * (out_channels - 1) * chan_stride + (h - 1) * row_stride + (w - 1) * pix_stride + 1 elements.  Elements the strides do not
+ * name are not written, 16-bit neighbours included; words are moved and never computed on.  d_lut and d_flip live as d_lut
+ * does above: both are read WHEN THE KERNELS RUN, and a replayed graph sees their contents of that moment.  Bits 2..7 of a
+ * d_flip byte are ignored (device memory cannot be validated).
+ * A view with elem_bytes 4, out_channels == channels, the identity in src_channel, flip 0 and d_flip NULL is
+ * lanczos_resize_tensor_window_device: the same words on the same route and the same kernels; with elem_bytes 2 it is
+ * lanczos_resize_tensor16_window_device.  Routes: a view is LANCZOS_TENSOR_FUSED exactly when
+ * lanczos_resize_window_plan_host says the byte request is fused and the element frame spans less than 2^31 bytes, else
+ * LANCZOS_TENSOR_CONVERTED; lanczos_last_tensor_route, lanczos_last_kernel and lanczos_resize_force (LANCZOS_RESIZE_CONVERT
+ * included) apply as above.  Byte, 16-bit-sample and float-sample outputs have no map and no flips. */
+typedef struct lanczos_tensor_view {
+    const void* d_lut;        /* out_channels * 256 elements of elem_bytes each, lut[oc * 256 + v]; read when the kernels run */
+    int64_t chan_stride, row_stride, pix_stride;   /* in elements, each > 0 */
+    int32_t elem_bytes;       /* 4 (float32 words) or 2 (bfloat16 / float16 words) */
+    int32_t out_channels;     /* 1 .. d->channels */
+    int32_t src_channel[4];   /* src_channel[oc] < d->channels for oc < out_channels, pairwise distinct; the rest must be 0 */
+    int32_t flip;             /* bit 0: mirror x, bit 1: mirror y -- applied to every frame */
+    const uint8_t* d_flip;    /* NULL, or one byte per frame (same bits), XORed with `flip`; read when the kernels run */
+    int32_t reserved[4];      /* must be 0 */
+} lanczos_tensor_view;
+/* the identity over every channel, CHW strides of d's whole output, no flips, d_lut NULL.  LANCZOS_ERR_BAD_ARG: a null v, what
+ * lanczos_resize_validate refuses, elem_bytes other than 2 or 4 */
+int lanczos_tensor_view_init(lanczos_tensor_view* v, const lanczos_resize_desc* d, int elem_bytes);
+/* Host only.  LANCZOS_ERR_BAD_ARG: everything lanczos_resize_tensor_window_validate refuses (the overlap rule under the
+ * out_channels extents), elem_bytes other than 2 or 4, out_channels outside 1 .. channels, a src_channel out of range, a
+ * duplicate or a non-zero one beyond out_channels, flip outside 0 .. 3, non-zero reserved words.  LANCZOS_ERR_UNSUPPORTED:
+ * LANCZOS_RESIZE_U16 or LANCZOS_RESIZE_F32. */
+int lanczos_resize_tensor_view_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win,
+                                        const lanczos_tensor_view* v);
+/* As lanczos_resize_tensor_window_device (opts and win may be NULL): d_lut and d_flip are device pointers.  Further
+ * LANCZOS_ERR_BAD_ARG: d_out or out_frame_stride (bytes; 0 = the frame's extent) no multiple of elem_bytes, a frame stride
+ * below the extent. */
+int lanczos_resize_tensor_view_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                      const lanczos_resize_window* win, const lanczos_tensor_view* v, const void* d_in,
+                                      void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream);
+/* Host buffers, a HOST table in v->d_lut and a HOST flip array (`frames` bytes, or NULL) in v->d_flip; element frames one
+ * extent apart; synchronous.  Elements of `out` the strides do not name keep their contents. */
+int lanczos_resize_tensor_view_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                    const lanczos_resize_window* win, const lanczos_tensor_view* v, const void* in, void* out,
+                                    int frames);
+
 /* ---- reduce by whole factors (Pillow's Image.reduce((fx, fy), box), an exact integer box average) ----
  * 8-bit, 1, 3 or 4 independent interleaved channels.  box = (x0, y0, x1, y1), integers with 0 <= x0 < x1 <= in_w and the same
  * for y; NULL = the whole frame.  The output is ceil((x1 - x0) / fx) x ceil((y1 - y0) / fy) pixels, tightly packed rows.

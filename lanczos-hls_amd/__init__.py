@@ -70,6 +70,8 @@ ABI_SYMBOLS = [
     "lanczos_resize_tensor_window_validate", "lanczos_resize_tensor16_window_validate",
     "lanczos_resize_tensor_window_device", "lanczos_resize_tensor_window_host",
     "lanczos_resize_tensor16_window_device", "lanczos_resize_tensor16_window_host",
+    "lanczos_tensor_view_init", "lanczos_resize_tensor_view_validate", "lanczos_resize_tensor_view_device",
+    "lanczos_resize_tensor_view_host",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
 
@@ -168,6 +170,19 @@ class TensorOut16(ctypes.Structure):
     words, strides in elements."""
     _fields_ = TensorOut._fields_
 
+
+class TensorView(ctypes.Structure):
+    """lanczos_tensor_view -- a tensor request of either element width with a channel map and flips:
+    out[oc * chan_stride + Y * row_stride + X * pix_stride] = lut[oc * 256 + byte of source channel src_channel[oc]], X and Y
+    mirrored per frame by bits 0 and 1 of flip ^ d_flip[f]."""
+    _fields_ = [("d_lut", ctypes.c_void_p), ("chan_stride", ctypes.c_int64), ("row_stride", ctypes.c_int64),
+                ("pix_stride", ctypes.c_int64), ("elem_bytes", ctypes.c_int32), ("out_channels", ctypes.c_int32),
+                ("src_channel", ctypes.c_int32 * 4), ("flip", ctypes.c_int32), ("d_flip", ctypes.c_void_p),
+                ("reserved", ctypes.c_int32 * 4)]
+
+
+FLIP_H, FLIP_V = 1, 2   # the bits of lanczos_tensor_view.flip and of a d_flip byte
+_FLIP_NAMES = {None: 0, "": 0, "h": FLIP_H, "v": FLIP_V, "hv": FLIP_H | FLIP_V, "vh": FLIP_H | FLIP_V}
 
 _LIB = None
 
@@ -300,6 +315,13 @@ def _lib():
             L.lanczos_resize_tensor16_window_device.argtypes = [c_void_p, PRD, PRO, PRW, PTO16, c_void_p, c_void_p, c_int,
                                                                 c_size_t, c_size_t, c_void_p]
             L.lanczos_resize_tensor16_window_host.argtypes = [c_void_p, PRD, PRO, PRW, PTO16, c_void_p, c_void_p, c_int]
+        if hasattr(L, "lanczos_resize_tensor_view_device"):   # (nor the view)
+            PTV = ctypes.POINTER(TensorView)
+            L.lanczos_tensor_view_init.argtypes = [PTV, PRD, c_int]
+            L.lanczos_resize_tensor_view_validate.argtypes = [PRD, PRW, PTV]
+            L.lanczos_resize_tensor_view_device.argtypes = [c_void_p, PRD, PRO, PRW, PTV, c_void_p, c_void_p, c_int, c_size_t,
+                                                            c_size_t, c_void_p]
+            L.lanczos_resize_tensor_view_host.argtypes = [c_void_p, PRD, PRO, PRW, PTV, c_void_p, c_void_p, c_int]
         L.lanczos_strerror.restype = ctypes.c_char_p
         L.lanczos_version.argtypes = []
         L.lanczos_version.restype = ctypes.c_char_p
@@ -582,6 +604,42 @@ def tensor16_out(d_lut, strides):
     return t
 
 
+def tensor_view_init(desc, elem_bytes=4):
+    """lanczos_tensor_view_init: the identity over every channel, CHW strides of the whole output, no flips, d_lut NULL."""
+    v = TensorView()
+    _check(_lib().lanczos_tensor_view_init(ctypes.byref(v), ctypes.byref(desc), elem_bytes), "lanczos_tensor_view_init")
+    return v
+
+
+def tensor_view(d_lut, strides, elem_bytes=4, channels_out=(0, 1, 2), flip=0, d_flip=None):
+    """A TensorView: d_lut a pointer to len(channels_out) * 256 elements of elem_bytes (4: float32, 2: bfloat16 / float16
+    words), indexed by the OUTPUT channel; strides = (chan_stride, row_stride, pix_stride) in elements; channels_out the
+    source channel of every output channel, e.g. (2, 1, 0) or (0, 1, 2) of an RGBA frame; flip FLIP_H | FLIP_V bits (or "h",
+    "v", "hv") for every frame; d_flip a pointer to one such byte per frame, XORed with flip, or None.  Both pointers are
+    device memory for the device entry.  Validated where it is used (resize_tensor_view_validate)."""
+    v = TensorView()
+    v.d_lut = d_lut
+    v.chan_stride, v.row_stride, v.pix_stride = (int(x) for x in strides)
+    v.elem_bytes = int(elem_bytes)
+    src = [int(c) for c in channels_out]
+    if len(src) > 4:
+        raise LanczosError(ERR_BAD_ARG, "tensor_view: at most four output channels")
+    v.out_channels = len(src)
+    for oc, sc in enumerate(src):
+        v.src_channel[oc] = sc
+    v.flip = _FLIP_NAMES[flip] if flip in _FLIP_NAMES else int(flip)
+    v.d_flip = d_flip
+    return v
+
+
+def resize_tensor_view_validate(desc, v, window=None):
+    """lanczos_resize_tensor_view_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the view is refused.
+    window: the strides describe that window's frame."""
+    _check(_lib().lanczos_resize_tensor_view_validate(ctypes.byref(desc), _window_ref(desc, window),
+                                                      ctypes.byref(v) if v is not None else None),
+           "lanczos_resize_tensor_view_validate")
+
+
 def resize_tensor16_validate(desc, t, window=None):
     """lanczos_resize_tensor16_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the request is refused.
     window: the strides describe that window's frame (lanczos_resize_tensor16_window_validate)."""
@@ -819,8 +877,14 @@ class Context:
 
     # -- resize straight into a float tensor (PIL.Image.resize -> ToTensor() -> Normalize(), lanczos_resize_tensor_*)
     def resize_tensor(self, img, out_w, out_h, mean=None, std=None, lut=None, layout="chw", a=3, alpha=False, box=None,
-                      reducing_gap=None, filter=FILTER_LANCZOS, dtype="float32", window=None):
-        """window = (x0, y0, w, h): only that window of the output, [F][C][h][w] or [F][h][w][C] (as Context.resize).
+                      reducing_gap=None, filter=FILTER_LANCZOS, dtype="float32", window=None, channels_out=None, flip=None):
+        """channels_out: a tuple of source channel indices, one per channel of the result -- (2, 1, 0) turns BGR into RGB,
+        (0, 1, 2) on an RGBA frame drops alpha (with alpha=True the colours are un-premultiplied first, Pillow's resize in mode
+        RGBA then .convert("RGB")); distinct indices, no replication.  The result then has len(channels_out) channels, and the
+        table (lut, or mean / std) is [len(channels_out)][256] in OUTPUT order.  flip: None, "h", "v", "hv", or an integer
+        array with one entry per frame (bit 0 mirrors x, bit 1 mirrors y: torch's .flip(-1) / .flip(-2) of that frame).  With
+        neither keyword the call is what it was (lanczos_resize_tensor_*); with either it is lanczos_resize_tensor_view_host.
+        window = (x0, y0, w, h): only that window of the output, [F][C][h][w] or [F][h][w][C] (as Context.resize).
         img: uint8 [H][W], [H][W][C] or [F][H][W][C] as Context.resize takes it -> float32 [F][C][H][W] (layout="chw") or
         [F][H][W][C] ("hwc"), the frame axis dropped as resize drops it: lut[c][byte] of the bytes Context.resize returns for
         the same arguments.  lut: float32 [C][256], moved bit for bit; None = normalize_lut(C, mean, std), with which the
@@ -839,8 +903,19 @@ class Context:
         x = x if x.ndim == 4 else x[None]
         f, h, w, c = x.shape
         d = resize_desc(w, h, out_w, out_h, c, a, alpha, filter=filter)
+        view = channels_out is not None or flip is not None
+        if channels_out is not None:
+            channels_out = tuple(int(v) for v in channels_out)
+            if not 1 <= len(channels_out) <= c:
+                raise LanczosError(ERR_BAD_ARG, f"resize_tensor: channels_out names 1 to {c} source channels")
+            c = len(channels_out)
         if lut is None:
-            lut = normalize_lut(c, mean, std, dtype)
+            if c == 2:   # lanczos_tensor_lut_normalize builds 1, 3 or 4 channels: two rows of one
+                m, s = (None if v is None else np.broadcast_to(np.asarray(v, dtype=np.float32), (2,)) for v in (mean, std))
+                lut = np.concatenate([normalize_lut(1, None if m is None else m[k], None if s is None else s[k], dtype)
+                                      for k in range(2)])
+            else:
+                lut = normalize_lut(c, mean, std, dtype)
         elif mean is not None or std is not None:
             raise LanczosError(ERR_BAD_ARG, "resize_tensor: a table or mean / std, not both")
         lut = np.ascontiguousarray(lut)
@@ -851,7 +926,23 @@ class Context:
         shape = (f, c, win.h, win.w) if layout == "chw" else (f, win.h, win.w, c)
         opts = _opts_ref(d, box, reducing_gap, None)
         wref = ctypes.byref(win) if window is not None else None
-        if wide:
+        if view:
+            flips = None
+            if flip is not None and not isinstance(flip, str):
+                flips = np.ascontiguousarray(flip)
+                if flips.shape != (f,) or flips.dtype.kind not in "iub" or ((flips < 0) | (flips > 3)).any():
+                    raise LanczosError(ERR_BAD_ARG, f"resize_tensor: flip is 'h', 'v', 'hv' or {f} integers 0 .. 3, one per frame")
+                flips = flips.astype(np.uint8)
+            elif flip not in _FLIP_NAMES:
+                raise LanczosError(ERR_BAD_ARG, f"resize_tensor: flip is 'h', 'v', 'hv' or one integer per frame, not {flip!r}")
+            v = tensor_view(lut.ctypes.data, strides, 4 if wide else 2,
+                            channels_out if channels_out is not None else tuple(range(c)),
+                            0 if flips is not None else flip, flips.ctypes.data if flips is not None else None)
+            out = np.empty(shape, dtype=np.float32 if wide else np.uint16)
+            _check(_lib().lanczos_resize_tensor_view_host(self._h, ctypes.byref(d), opts, wref, ctypes.byref(v), x.ctypes.data,
+                                                          out.ctypes.data, f), "lanczos_resize_tensor_view_host")
+            out = out if wide else _tensor16_array(out, dtype)
+        elif wide:
             t = tensor_out(lut.ctypes.data, strides)
             out = np.empty(shape, dtype=np.float32)
             if wref is None:
@@ -875,8 +966,13 @@ class Context:
         return out if img.ndim == 4 else out[0]
 
     def resize_tensor_device(self, desc, d_in, d_out, frames, d_lut, strides, in_frame_stride=0, out_frame_stride=0,
-                             stream=None, box=None, reducing_gap=None, opts=None, dtype="float32", window=None):
-        """Device pointers, asynchronous on `stream`: uint8 frames at d_in -> float frames at d_out, out_frame_stride in BYTES
+                             stream=None, box=None, reducing_gap=None, opts=None, dtype="float32", window=None,
+                             channels_out=None, flip=None, d_flip=None):
+        """channels_out / flip as Context.resize_tensor (flip: None, "h", "v", "hv" or FLIP_* bits, for every frame); d_flip: a
+        device pointer to one byte per frame, XORed with flip and read when the kernels run.  With any of the three, or a ready
+        TensorView as `strides`, the call is lanczos_resize_tensor_view_device: the table at d_lut is [len(channels_out)][256]
+        in output order and the strides describe a frame of that many channels.
+        Device pointers, asynchronous on `stream`: uint8 frames at d_in -> float frames at d_out, out_frame_stride in BYTES
         (0 = one frame's extent).  d_lut: device pointer to channels * 256 floats, read when the kernels run (a replayed
         graph sees its contents of that moment).  strides = (chan_stride, row_stride, pix_stride) in floats, e.g.
         tensor_strides("chw", ...), or a ready TensorOut (d_lut then unused).  box / reducing_gap / opts as resize_device.
@@ -885,6 +981,18 @@ class Context:
         are that window of the output, and the strides describe its C x h x w frame (tensor_strides(layout, w, h, C))."""
         oref = _opts_ref(desc, box, reducing_gap, opts)
         wref = _window_ref(desc, window)
+        if isinstance(strides, TensorView) or channels_out is not None or flip is not None or d_flip is not None:
+            if isinstance(strides, TensorView):
+                v = strides
+            else:
+                if dtype != "float32":
+                    _tensor16_format(dtype, "resize_tensor_device")
+                v = tensor_view(d_lut, strides, 4 if dtype == "float32" else 2,
+                                channels_out if channels_out is not None else tuple(range(desc.channels)), flip or 0, d_flip)
+            _check(_lib().lanczos_resize_tensor_view_device(self._h, ctypes.byref(desc), oref, wref, ctypes.byref(v), d_in,
+                                                            d_out, frames, in_frame_stride, out_frame_stride, stream),
+                   "lanczos_resize_tensor_view_device")
+            return
         if isinstance(strides, TensorOut16) or dtype != "float32":
             if not isinstance(strides, TensorOut16):
                 _tensor16_format(dtype, "resize_tensor_device")

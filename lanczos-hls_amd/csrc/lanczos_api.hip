@@ -1279,19 +1279,17 @@ int lanczos_resize_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const vo
 
 // The float and the 16-bit tensor entries are one request (lz::RsTensorOut) with another element width
 extern "C++" {
-template <class T>
-static int tensor_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
-                         const lanczos_resize_window* win, const T* t, int elem, const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
-    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    lz::RsTensorCall tc;
-    int rc = lz::tensor_validate(d, win, t, elem, &tc.t);
-    if (rc != LANCZOS_OK) return rc;
+// what follows the validation of a device request (tc.t filled)
+static int tensor_device_run(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                             const lanczos_resize_window* win, lz::RsTensorCall& tc, const void* d_in, void* d_out, int frames,
+                             size_t in_frame_stride, size_t out_frame_stride, void* stream) {
     std::lock_guard<std::mutex> lock(ctx->mu);
     LZ_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
+    int rc = resize_state(ctx);
+    if (rc != LANCZOS_OK) return rc;
     route_begin(ctx);
     lz::RsWindow w;
-    (void)lz::resize_window_resolve(d, win, &w);   // validated above
+    (void)lz::resize_window_resolve(d, win, &w);   // validated by the caller
     tc.extent_bytes = lz::tensor_extent_bytes(d, w, tc.t);
     rc = lz::resize_device(ctx->resize, d, opts, win, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
                            &ctx->last_kernel, &ctx->last_hip, &tc);
@@ -1300,19 +1298,36 @@ static int tensor_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const l
 }
 
 template <class T>
+static int tensor_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                         const lanczos_resize_window* win, const T* t, int elem, const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    lz::RsTensorCall tc;
+    const int rc = lz::tensor_validate(d, win, t, elem, &tc.t);
+    if (rc != LANCZOS_OK) return rc;
+    return tensor_device_run(ctx, d, opts, win, tc, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+}
+
+// ... and of a host request (lay filled)
+static int tensor_host_run(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                           const lanczos_resize_window* win, const lz::RsTensorOut& lay, const void* in, void* out, int frames) {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->stream) return LANCZOS_ERR_HIP;
+    const int rc = resize_state(ctx);
+    if (rc != LANCZOS_OK) return rc;
+    route_begin(ctx);
+    return lz::resize_tensor_host(ctx->resize, d, opts, win, lay, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip,
+                                  &ctx->last_tensor_route);
+}
+
+template <class T>
 static int tensor_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                        const lanczos_resize_window* win, const T* t, int elem, const void* in, void* out, int frames) {
     if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
     lz::RsTensorOut lay;
-    int rc = lz::tensor_validate(d, win, t, elem, &lay);
+    const int rc = lz::tensor_validate(d, win, t, elem, &lay);
     if (rc != LANCZOS_OK) return rc;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    LZ_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->stream) return LANCZOS_ERR_HIP;
-    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
-    route_begin(ctx);
-    return lz::resize_tensor_host(ctx->resize, d, opts, win, lay, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip,
-                                  &ctx->last_tensor_route);
+    return tensor_host_run(ctx, d, opts, win, lay, in, out, frames);
 }
 
 }   // extern "C++"
@@ -1399,6 +1414,43 @@ int lanczos_resize_tensor16_window_host(lanczos_ctx* ctx, const lanczos_resize_d
                                         const lanczos_resize_window* win, const lanczos_tensor16_out* t, const void* in,
                                         void* out, int frames) {
     return tensor_host(ctx, d, opts, win, t, 2, in, out, frames);
+}
+
+int lanczos_tensor_view_init(lanczos_tensor_view* v, const lanczos_resize_desc* d, int elem_bytes) {
+    if (!v || (elem_bytes != 2 && elem_bytes != 4)) return LANCZOS_ERR_BAD_ARG;
+    const int rc = lz::resize_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    *v = lanczos_tensor_view{};
+    v->chan_stride = (int64_t)d->out_h * d->out_w, v->row_stride = d->out_w, v->pix_stride = 1;
+    v->elem_bytes = elem_bytes, v->out_channels = d->channels;
+    for (int c = 0; c < d->channels; c++) v->src_channel[c] = c;
+    return LANCZOS_OK;
+}
+
+int lanczos_resize_tensor_view_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win,
+                                        const lanczos_tensor_view* v) {
+    lz::RsTensorOut lay;
+    return lz::tensor_view_validate(d, win, v, &lay);
+}
+
+int lanczos_resize_tensor_view_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                      const lanczos_resize_window* win, const lanczos_tensor_view* v, const void* d_in,
+                                      void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    lz::RsTensorCall tc;
+    const int rc = lz::tensor_view_validate(d, win, v, &tc.t);
+    if (rc != LANCZOS_OK) return rc;
+    return tensor_device_run(ctx, d, opts, win, tc, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+}
+
+int lanczos_resize_tensor_view_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                    const lanczos_resize_window* win, const lanczos_tensor_view* v, const void* in, void* out,
+                                    int frames) {
+    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    lz::RsTensorOut lay;
+    const int rc = lz::tensor_view_validate(d, win, v, &lay);
+    if (rc != LANCZOS_OK) return rc;
+    return tensor_host_run(ctx, d, opts, win, lay, in, out, frames);
 }
 
 int lanczos_last_tensor_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_tensor_route : 0; }

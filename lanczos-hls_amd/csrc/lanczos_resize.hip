@@ -631,7 +631,8 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     hipError_t e = hipSuccess;
     if (fused) {
         const RsFusedLaunch c{d, win, &fp, H, V, in, out, in_fs, out_fs, frames, tc, stream};
-        e = t_fused ? (tc->t.elem == 2 ? rs_launch_fused<1, 2>(c) : rs_launch_fused<1, 4>(c))
+        e = t_fused && tc->t.mapped ? (tc->t.elem == 2 ? rs_launch_fused<1, 2 + kRsMapped>(c) : rs_launch_fused<1, 4 + kRsMapped>(c))
+            : t_fused ? (tc->t.elem == 2 ? rs_launch_fused<1, 2>(c) : rs_launch_fused<1, 4>(c))
             : f32   ? rs_launch_fused<4, 0>(c)
             : u16   ? rs_launch_fused<2, 0>(c)
                     : rs_launch_fused<1, 0>(c);
@@ -746,20 +747,26 @@ static hipError_t rs_grow_stage(ResizeState* st, void** p, size_t* have, size_t 
 
 // What the host entry points share: both staging blocks grown, the input copied up, `call` (the device entry on the staged
 // blocks; it returns a LANCZOS_ status), the output copied down and the stream drained.  A tensor request has more to upload:
-// its table, `table_at` bytes into the input block, and the output block starts as a copy of `out` (out_up)
+// its table, `table_at` bytes into the input block (a view's flip array rides behind it, `flips_at` bytes in), and the output
+// block starts as a copy of `out` (out_up)
 struct RsStagedExtra {
     const void* table = nullptr;
     size_t table_at = 0, table_bytes = 0;
+    const void* flips = nullptr;
+    size_t flips_at = 0, flips_bytes = 0;
     bool out_up = false;
 };
 template <class F>
 static int rs_staged_call(ResizeState* st, const void* in, size_t in_bytes, void* out, size_t out_bytes, const RsStagedExtra& x,
                           hipStream_t stream, int* last_hip, F&& call) {
-    hipError_t e = rs_grow_stage(st, &st->stage_in, &st->stage_in_bytes, std::max(in_bytes, x.table_at + x.table_bytes), stream);
+    const size_t in_need = std::max({in_bytes, x.table_at + x.table_bytes, x.flips_at + x.flips_bytes});
+    hipError_t e = rs_grow_stage(st, &st->stage_in, &st->stage_in_bytes, in_need, stream);
     if (e == hipSuccess) e = rs_grow_stage(st, &st->stage_out, &st->stage_out_bytes, out_bytes, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(st->stage_in, in, in_bytes, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess && x.table)
         e = hipMemcpyAsync((uint8_t*)st->stage_in + x.table_at, x.table, x.table_bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && x.flips)
+        e = hipMemcpyAsync((uint8_t*)st->stage_in + x.flips_at, x.flips, x.flips_bytes, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess && x.out_up) e = hipMemcpyAsync(st->stage_out, out, out_bytes, hipMemcpyHostToDevice, stream);
     int rc = LANCZOS_OK;
     if (e == hipSuccess) {
@@ -790,8 +797,8 @@ int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_res
     });
 }
 
-// The table rides behind the input frames in the input staging block.  The element frames go up before they come back, so
-// that the elements of `out` the strides leave out keep what they held.
+// The table rides behind the input frames in the input staging block, and behind it the flip array of a view.  The element
+// frames go up before they come back, so that the elements of `out` the strides leave out keep what they held.
 int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
                        const lanczos_resize_window* win, const RsTensorOut& t, const void* in, void* out, int frames,
                        hipStream_t stream, int* last_kernel, int* last_hip, int* route) {
@@ -804,10 +811,12 @@ int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanc
     tc.extent_bytes = tensor_extent_bytes(d, w, t);
     const size_t in_bytes = (size_t)d->in_w * d->in_h * d->channels * frames;
     RsStagedExtra x;
-    x.table = t.d_lut, x.table_at = (in_bytes + 255) & ~(size_t)255, x.table_bytes = (size_t)d->channels * 256 * t.elem;
+    x.table = t.d_lut, x.table_at = (in_bytes + 255) & ~(size_t)255, x.table_bytes = (size_t)t.out_channels * 256 * t.elem;
+    if (t.d_flip) x.flips = t.d_flip, x.flips_at = x.table_at + x.table_bytes, x.flips_bytes = (size_t)frames;
     x.out_up = true;
     return rs_staged_call(st, in, in_bytes, out, tc.extent_bytes * frames, x, stream, last_hip, [&] {
         tc.t.d_lut = (const uint8_t*)st->stage_in + x.table_at;
+        if (t.d_flip) tc.t.d_flip = (const uint8_t*)st->stage_in + x.flips_at;
         const int rc = resize_device(st, d, o, win, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip, &tc);
         *route = tc.route;
         return rc;

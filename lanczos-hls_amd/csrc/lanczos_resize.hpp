@@ -2,7 +2,8 @@
 // their per-context cache, and the entry points lanczos_api.hip forwards to.  Tables, cache, planning and dispatch are in
 // lanczos_resize.hip.  The kernels are written once for 8-bit, 16-bit (LANCZOS_RESIZE_U16) and float (LANCZOS_RESIZE_F32)
 // samples in lanczos_resize_fused.hpp; the fused instances are compiled by lanczos_resize.hip (8-bit), lanczos_resize_tensor.hip
-// (8-bit into float tensors), lanczos_resize_tensor16.hip (8-bit into bfloat16 / float16 tensors), lanczos_resize16.hip and
+// (8-bit into float tensors), lanczos_resize_tensor16.hip (8-bit into bfloat16 / float16 tensors), lanczos_resize_tensor_view.hip
+// and lanczos_resize_tensor16_view.hip (the same two through a channel map and flips), lanczos_resize16.hip and
 // lanczos_resize32.hip.  The filter of a request (LANCZOS_RESIZE_FILTER)
 // only changes the tables; LANCZOS_FILTER_NEAREST has index tables and a kernel of its own (lanczos_resize_nearest.hip).
 #pragma once
@@ -153,12 +154,27 @@ struct ResizeState {
     ~ResizeState();
 };
 
-// The table and the layout of a tensor request, whatever its element: lanczos_tensor_out (elem 4, floats) and
-// lanczos_tensor16_out (elem 2, bfloat16 or float16 words) are both this.  Strides in elements.
+// The table and the layout of a tensor request, whatever its element: lanczos_tensor_out (elem 4, floats),
+// lanczos_tensor16_out (elem 2, bfloat16 or float16 words) and lanczos_tensor_view (either, with a channel map and flips) are
+// all this.  Strides in elements.
 struct RsTensorOut {
-    const void* d_lut = nullptr;   // channels * 256 elements
+    const void* d_lut = nullptr;   // out_channels * 256 elements
     int64_t chan_stride = 0, row_stride = 0, pix_stride = 0;
     int elem = 4;                  // bytes of an element
+    // the view: output channel oc is source channel src_channel[oc].  out_channels 0 stands for every channel in its place
+    // (the two structs without a map); tensor_validate fills it in
+    int out_channels = 0;
+    int src_channel[4] = {0, 0, 0, 0};
+    int flip = 0;                      // bit 0: mirror x, bit 1: mirror y, every frame
+    const uint8_t* d_flip = nullptr;   // one byte per frame, XORed with flip; read when the kernels run
+    // set by tensor_validate: false where the view is the identity without flips, which runs the kernels without a map
+    bool mapped = false;
+    // dst[c] in byte c: the output channel source channel c goes to, 255 where none does
+    unsigned dst_of_src() const {
+        unsigned dst = 0xffffffffu;
+        for (int oc = 0; oc < out_channels; oc++) dst = (dst & ~(255u << (8 * src_channel[oc]))) | ((unsigned)oc << (8 * src_channel[oc]));
+        return dst;
+    }
 };
 // A tensor request (lanczos_resize_tensor.hip): d_out and out_frame_stride of resize_device are then those of the element
 // frames.  route: out, LANCZOS_TENSOR_FUSED or LANCZOS_TENSOR_CONVERTED once the launches are out.
@@ -168,21 +184,24 @@ struct RsTensorCall {
     int route = 0;
 };
 // t NULL: the caller passed no struct; reserved: its four words.  The frame the strides describe is the window's (win NULL:
-// the whole output)
-int tensor_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const RsTensorOut* t,
-                    const int32_t* reserved);
-// the request of either public struct (T): *lay is filled where there is one
+// the whole output).  On LANCZOS_OK t->out_channels, src_channel and mapped are resolved
+int tensor_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, RsTensorOut* t, const int32_t* reserved);
+// the request of either public struct without a map (T): *lay is filled where there is one
 template <class T>
 int tensor_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const T* t, int elem, RsTensorOut* lay) {
     if (t) *lay = RsTensorOut{t->d_lut, t->chan_stride, t->row_stride, t->pix_stride, elem};
     return tensor_validate(d, win, t ? lay : nullptr, t ? t->reserved : nullptr);
 }
+// ... and of lanczos_tensor_view
+int tensor_view_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_tensor_view* v,
+                         RsTensorOut* lay);
 size_t tensor_extent_bytes(const lanczos_resize_desc* d, const RsWindow& win, const RsTensorOut& t);
 void tensor_lut_normalize(int channels, const float* mean, const float* std, float* lut);
 // float32 -> bfloat16 (LANCZOS_TENSOR_BF16) or float16 (LANCZOS_TENSOR_F16) words, round to nearest even; false: no such format
 bool tensor_lut_convert16(const float* in, int n, int format, uint16_t* out);
 // k_rs_to_tensor: tightly packed interleaved bytes (frames `src_fs` apart, base and stride dword multiples, readable up to the
 // next dword multiple behind each frame) -> strided elements through the table
+// (t.mapped: through the channel map and the frames' flips)
 hipError_t rs_to_tensor_launch(const uint8_t* src, size_t src_fs, uint8_t* out, size_t out_fs, int w, int h, int channels,
                                const RsTensorOut& t, int frames, hipStream_t stream);
 
@@ -191,7 +210,8 @@ hipError_t rs_to_tensor_launch(const uint8_t* src, size_t src_fs, uint8_t* out, 
 int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
                   const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream,
                   int* last_kernel, int* last_hip, RsTensorCall* tc = nullptr);
-// host table (t.d_lut) and host buffers, element frames tensor_extent_bytes apart; synchronous
+// host table (t.d_lut), host flip array (t.d_flip, or NULL) and host buffers, element frames tensor_extent_bytes apart;
+// synchronous
 int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
                        const lanczos_resize_window* win, const RsTensorOut& t, const void* in, void* out, int frames,
                        hipStream_t stream, int* last_kernel, int* last_hip, int* route);
@@ -223,7 +243,10 @@ struct RsFusedLaunch {
     const RsTensorCall* tc;   // TENSOR: `out` / `out_fs` are the element frames
     hipStream_t stream;
 };
-template <int BPS, int TENSOR>   // TENSOR: bytes of a stored table element, 0 where the samples themselves are stored
+// TENSOR: bytes of a stored table element, 0 where the samples themselves are stored; + kRsMapped: through the channel map and
+// the flips of the request (RsTensorOut::mapped)
+constexpr int kRsMapped = 8;
+template <int BPS, int TENSOR>
 hipError_t rs_launch_fused(const RsFusedLaunch& c);
 
 // LANCZOS_FILTER_NEAREST (lanczos_resize_nearest.hip): out[y][x] = in[vidx[y]][hidx[x]] for pixels of `channels` samples of

@@ -4,10 +4,12 @@
 //   RsSample<BPS>   what a sample width brings: its types, Pillow's multiply-add and store.  These are the specification of
 //                   the bytes; everything below only moves samples around.
 //   k_rs_pass_h/_v  the two-pass kernels, one thread per output sample (instantiated in lanczos_resize.hip).
-//   k_rs_fused      the fused kernel, and rs_launch_fused, which fills its arguments and picks the instance.  Five
+//   k_rs_fused      the fused kernel, and rs_launch_fused, which fills its arguments and picks the instance.  Seven
 //                   translation units instantiate them side by side: lanczos_resize.hip (8-bit, bytes out),
 //                   lanczos_resize_tensor.hip (8-bit, floats out through a table: TENSOR = 4), lanczos_resize_tensor16.hip
-//                   (8-bit, 16-bit elements out through a table: TENSOR = 2), lanczos_resize16.hip and lanczos_resize32.hip.
+//                   (8-bit, 16-bit elements out through a table: TENSOR = 2), lanczos_resize_tensor_view.hip and
+//                   lanczos_resize_tensor16_view.hip (the same two through a channel map and flips: TENSOR + kRsMapped),
+//                   lanczos_resize16.hip and lanczos_resize32.hip.
 #pragma once
 #include "lanczos_alpha.hpp"
 #include "lanczos_resize.hpp"
@@ -156,6 +158,17 @@ struct RsFusedTensor : RsFused<int32_t> {
     int cs, rs, ps;          // channel, row and pixel strides in elements
     unsigned extent_bytes;   // of one element frame, below 2^31
 };
+// ... + kRsMapped: lut is [out_channels][256], indexed by the output channel.  A struct of its own: with these fields behind
+// RsFusedTensor's the argument loads of the instances without a map were merged otherwise, and their registers moved
+struct RsFusedTensorMap : RsFusedTensor {
+    unsigned dst;            // byte c: the output channel of source channel c, 255 where it is dropped
+    int flip;                // bit 0: mirror x, bit 1: mirror y
+    const uint8_t* d_flip;   // NULL, or one byte per frame of the launch, XORed with flip; read when the kernel runs
+};
+// the argument of k_rs_fused<..., TENSOR> for coefficients KT
+template <int TENSOR, class KT>
+using RsFusedArgs = std::conditional_t<(TENSOR & kRsMapped) != 0, RsFusedTensorMap,
+                                       std::conditional_t<TENSOR != 0, RsFusedTensor, RsFused<KT>>>;
 
 template <int C, int BPS>
 struct RsStrip {
@@ -186,10 +199,17 @@ struct RsStrip {
 // global memory through the vector cache (1 to 4 KiB, resident after the first rows): LDS and the plan stay the byte kernel's.
 // TENSOR is the width of the stored element in bytes: 4 (floats, lanczos_tensor_out), 2 (bfloat16 or float16 words,
 // lanczos_tensor16_out: the table is of 16-bit words and the store a 16-bit one, everything else the same), 0: bytes out.
+//
+// TENSOR + kRsMapped (lanczos_tensor_view with a channel map or flips; instances of their own, the ones above are as they
+// were): the lane's channel c becomes dst[c], four byte fields of one scalar, and a channel no output names stores nothing.  A
+// flip negates a stride and moves the base to the matching corner of the frame -- both computed once per workgroup from one
+// uniform byte load -- so every offset stays inside [0, extent) and the buffer resource is the same.
 template <class S, int C, int K, bool ALPHA = false, int TENSOR = 0>
 __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
-    std::conditional_t<TENSOR != 0, RsFusedTensor, RsFused<typename S::coeff_t>> g) {
-    static_assert(TENSOR == 0 || TENSOR == 2 || TENSOR == 4, "bytes, 16-bit elements or floats out");
+    RsFusedArgs<TENSOR, typename S::coeff_t> g) {
+    constexpr int EB = TENSOR & ~kRsMapped;   // bytes of a stored element
+    constexpr bool MAPPED = (TENSOR & kRsMapped) != 0;
+    static_assert((EB == 0 && !MAPPED) || EB == 2 || EB == 4, "bytes, 16-bit elements or floats out");
     static_assert(!ALPHA || C == 4, "alpha is the fourth of four channels");
     static_assert((!ALPHA && !TENSOR) || S::BPS == 1, "alpha and tensor output are 8-bit");
     using acc_t = typename S::acc_t;
@@ -235,6 +255,13 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(fout, 0, out_bytes, 0x00020000);
     const bool out_aligned = (((uintptr_t)fout | (unsigned)g.out_pitch | (unsigned)(x0 * CB)) & 3) == 0;
     const int valid_bytes = sw * (kDwordSamples ? C : CB);   // of the strip's row; dwords where a sample is one
+    // MAPPED: the frame's flips turned into a base and two signed strides (elements)
+    [[maybe_unused]] int t_base = 0, t_rs = 0, t_ps = 0;
+    if constexpr (MAPPED) {
+        const int m = g.flip ^ (g.d_flip ? __builtin_amdgcn_readfirstlane((int)g.d_flip[blockIdx.y]) : 0);
+        t_rs = (m & 2) ? -g.rs : g.rs, t_ps = (m & 1) ? -g.ps : g.ps;
+        t_base = ((m & 2) ? (g.out_h - 1) * g.rs : 0) + ((m & 1) ? (g.out_w - 1) * g.ps : 0);
+    }
 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int o_begin = chunk * g.rows_per_chunk;
@@ -357,12 +384,24 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
                     const int j = wb + 64 * rr + lane;
                     if (j < valid_bytes) {
                         const int xo = j / C, c = j - xo * C;
-                        const int at = c * 256 + (int)((w >> (8 * (lane & 3))) & 255u);
-                        const int to = c * g.cs + o * g.rs + (x0 + xo) * g.ps;
-                        if constexpr (TENSOR == 2)
-                            __builtin_amdgcn_raw_buffer_store_b16(((const uint16_t*)g.lut)[at], orsrc, to * 2, 0, 0);
-                        else
-                            __builtin_amdgcn_raw_buffer_store_b32(g.lut[at], orsrc, to * 4, 0, 0);
+                        if constexpr (MAPPED) {
+                            const int oc = (int)((g.dst >> (8 * c)) & 255u);
+                            if (oc < 4) {
+                                const int at = oc * 256 + (int)((w >> (8 * (lane & 3))) & 255u);
+                                const int to = t_base + oc * g.cs + o * t_rs + (x0 + xo) * t_ps;
+                                if constexpr (EB == 2)
+                                    __builtin_amdgcn_raw_buffer_store_b16(((const uint16_t*)g.lut)[at], orsrc, to * 2, 0, 0);
+                                else
+                                    __builtin_amdgcn_raw_buffer_store_b32(g.lut[at], orsrc, to * 4, 0, 0);
+                            }
+                        } else {
+                            const int at = c * 256 + (int)((w >> (8 * (lane & 3))) & 255u);
+                            const int to = c * g.cs + o * g.rs + (x0 + xo) * g.ps;
+                            if constexpr (EB == 2)
+                                __builtin_amdgcn_raw_buffer_store_b16(((const uint16_t*)g.lut)[at], orsrc, to * 2, 0, 0);
+                            else
+                                __builtin_amdgcn_raw_buffer_store_b32(g.lut[at], orsrc, to * 4, 0, 0);
+                        }
                     }
                 }
             } else if (b0 < valid_bytes) {
@@ -432,17 +471,19 @@ hipError_t rs_launch_fused(const RsFusedLaunch& c) {
     using S = RsSample<BPS>;
     const bool alpha = (c.d->reserved[0] & LANCZOS_RESIZE_ALPHA) != 0;
     const RsFusedPlan& fp = *c.fp;
-    std::conditional_t<TENSOR != 0, RsFusedTensor, RsFused<typename S::coeff_t>> g{};
+    RsFusedArgs<TENSOR, typename S::coeff_t> g{};
     rs_fill_fused(&g, c);
     if constexpr (TENSOR != 0) {
         g.lut = (const uint32_t*)c.tc->t.d_lut;
         g.cs = (int)c.tc->t.chan_stride, g.rs = (int)c.tc->t.row_stride, g.ps = (int)c.tc->t.pix_stride;   // extent below 2^31 bytes
         g.extent_bytes = (unsigned)c.tc->extent_bytes;
     }
+    if constexpr ((TENSOR & kRsMapped) != 0) g.dst = c.tc->t.dst_of_src(), g.flip = c.tc->t.flip & 3;
     for (int f0 = 0; f0 < c.frames; f0 += 65535) {
         const int nf = std::min(65535, c.frames - f0);
         g.in = c.in + (size_t)f0 * c.in_fs;
         g.out = c.out + (size_t)f0 * c.out_fs;
+        if constexpr ((TENSOR & kRsMapped) != 0) g.d_flip = c.tc->t.d_flip ? c.tc->t.d_flip + f0 : nullptr;   // a byte per frame
         const dim3 grid(fp.strips * fp.chunks, nf);
         bool launched = false;
         rs_dispatch_instance(c.d->channels, fp.K, alpha, [&](auto ch, auto k, auto a) {
@@ -462,6 +503,8 @@ hipError_t rs_launch_fused(const RsFusedLaunch& c) {
 extern template hipError_t rs_launch_fused<1, 0>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<1, 4>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<1, 2>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<1, 4 + kRsMapped>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<1, 2 + kRsMapped>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<2, 0>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<4, 0>(const RsFusedLaunch&);
 

@@ -1,13 +1,15 @@
 // lanczos_resize_tensor.hip -- 8-bit resizes that leave as float, bfloat16 or float16 tensors (include/lanczos_hip.h,
-// lanczos_tensor_out and lanczos_tensor16_out): out[c * cs + y * rs + x * ps] = lut[c][P(y, x, c)], P the byte
-// lanczos_resize_device_ex stores.  The table entries are moved as 32-bit or 16-bit words, never computed on.  Two kernels:
+// lanczos_tensor_out, lanczos_tensor16_out and lanczos_tensor_view): out[c * cs + y * rs + x * ps] =
+// lut[c][P(y, x, c)], P the byte lanczos_resize_device_ex stores; a view also maps the channels and mirrors frames.  The table entries are moved as 32-bit or 16-bit words, never computed on.  Two kernels:
 //
 //   fused      the TENSOR instances of k_rs_fused (lanczos_resize_fused.hpp): the vertical pass stores the elements itself.  A
 //              tensor request runs them exactly where the byte request runs the fused kernel, on the same plan.  Those that
-//              store floats are instantiated here, those that store 16-bit elements in lanczos_resize_tensor16.hip.
+//              store floats are instantiated here, those that store 16-bit elements in lanczos_resize_tensor16.hip, those of
+//              a view with a map or flips in lanczos_resize_tensor_view.hip and lanczos_resize_tensor16_view.hip.
 //   converted  k_rs_to_tensor behind any other resize (two passes, one pass, nearest, the plain copy, an element frame of 2^31
 //              bytes or more): the bytes go to context scratch, tightly packed, and one streaming launch turns them into
-//              elements (k_rs_to_tensor<C, uint16_t> is the k_rs_to_tensor16 of the documents).
+//              elements (k_rs_to_tensor<C, uint16_t> is the k_rs_to_tensor16 of the documents; k_rs_to_tensor_map is the
+//              form with a channel map and flips).
 //
 // The validation of a request, the table of ToTensor + Normalize and its rounding to 16 bits are here as well.
 #include "lanczos_resize_fused.hpp"
@@ -20,12 +22,12 @@ namespace lz {
 // ---- host: validation, the normalisation table --------------------------------------------------------------------
 
 size_t tensor_extent_bytes(const lanczos_resize_desc* d, const RsWindow& win, const RsTensorOut& t) {
-    return (size_t)((d->channels - 1) * t.chan_stride + (win.h - 1) * t.row_stride + (win.w - 1) * t.pix_stride + 1) *
+    const int oc = t.out_channels ? t.out_channels : d->channels;
+    return (size_t)((oc - 1) * t.chan_stride + (win.h - 1) * t.row_stride + (win.w - 1) * t.pix_stride + 1) *
            (size_t)t.elem;
 }
 
-int tensor_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const RsTensorOut* t,
-                    const int32_t* reserved) {
+int tensor_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, RsTensorOut* t, const int32_t* reserved) {
     int rc = resize_validate(d);
     if (rc != LANCZOS_OK) return rc;
     RsWindow w;   // the frame the strides describe
@@ -33,11 +35,27 @@ int tensor_validate(const lanczos_resize_desc* d, const lanczos_resize_window* w
     if (!t || !t->d_lut) return LANCZOS_ERR_BAD_ARG;
     for (int i = 0; i < 4; i++)
         if (reserved[i] != 0) return LANCZOS_ERR_BAD_ARG;
+    // the channel map: out_channels 0 is every channel in its place.  Injective, and nothing set behind out_channels
+    if (t->elem != 2 && t->elem != 4) return LANCZOS_ERR_BAD_ARG;
+    if (t->out_channels == 0) {
+        t->out_channels = d->channels;
+        for (int c = 0; c < 4; c++) t->src_channel[c] = c < d->channels ? c : 0;
+    }
+    if (t->out_channels < 1 || t->out_channels > d->channels || (t->flip & ~3) != 0) return LANCZOS_ERR_BAD_ARG;
+    bool identity = t->out_channels == d->channels;
+    for (int oc = 0; oc < 4; oc++) {
+        const int sc = t->src_channel[oc];
+        if (oc >= t->out_channels ? sc != 0 : (sc < 0 || sc >= d->channels)) return LANCZOS_ERR_BAD_ARG;
+        for (int k = 0; k < oc && oc < t->out_channels; k++)
+            if (t->src_channel[k] == sc) return LANCZOS_ERR_BAD_ARG;
+        if (oc < t->out_channels && sc != oc) identity = false;
+    }
+    t->mapped = !identity || t->flip != 0 || t->d_flip != nullptr;
     // a table per 16-bit value and float inputs are out of scope
     if (d->reserved[0] & (LANCZOS_RESIZE_U16 | LANCZOS_RESIZE_F32)) return LANCZOS_ERR_UNSUPPORTED;
     struct Dim {
         int64_t stride, extent;
-    } dims[3] = {{t->chan_stride, d->channels}, {t->row_stride, w.h}, {t->pix_stride, w.w}};
+    } dims[3] = {{t->chan_stride, t->out_channels}, {t->row_stride, w.h}, {t->pix_stride, w.w}};
     constexpr int64_t kMaxStride = (int64_t)1 << 40;   // stride x extent stays far inside int64
     for (const Dim& m : dims)
         if (m.stride <= 0 || m.stride > kMaxStride) return LANCZOS_ERR_BAD_ARG;
@@ -51,6 +69,21 @@ int tensor_validate(const lanczos_resize_desc* d, const lanczos_resize_window* w
         covered = m.stride * m.extent;
     }
     return LANCZOS_OK;
+}
+
+int tensor_view_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_tensor_view* v,
+                         RsTensorOut* lay) {
+    if (v) {
+        *lay = RsTensorOut{v->d_lut, v->chan_stride, v->row_stride, v->pix_stride, v->elem_bytes, v->out_channels};
+        for (int c = 0; c < 4; c++) lay->src_channel[c] = v->src_channel[c];
+        lay->flip = v->flip, lay->d_flip = v->d_flip;
+        // 0 channels is no view (and stands for "all of them" inside): refused here, once the descriptor has been looked at
+        if (v->out_channels == 0) {
+            const int rc = resize_validate(d);
+            return rc != LANCZOS_OK ? rc : LANCZOS_ERR_BAD_ARG;
+        }
+    }
+    return tensor_validate(d, win, v ? lay : nullptr, v ? v->reserved : nullptr);
 }
 
 // ToTensor() then Normalize(mean, std), operation for operation in float: this translation unit is built with
@@ -109,6 +142,13 @@ struct RsToTensor {
     const void* lut;   // words of the stored element's width
     long long cs, rs, ps;
 };
+// ... with a channel map and flips: lut is [out_channels][256]
+struct RsToTensorMap : RsToTensor {
+    unsigned dst;            // byte c: the output channel of source channel c, 255 where it is dropped
+    int flip;                // bit 0: mirror x, bit 1: mirror y
+    const uint8_t* d_flip;   // NULL, or one byte per frame of the launch, XORed with flip; read when the kernel runs
+    int w, h;                // pixels of a frame
+};
 
 constexpr int kToTensorBlock = 4 * kRsThreads;   // samples per workgroup: one dword load per thread
 
@@ -147,24 +187,71 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_to_tensor(RsToTensor g) {
     }
 }
 
+// The same with a channel map and flips, as the fused epilogue's mapped form has them: channel c goes to dst[c] or nowhere,
+// and the frame's flips are a base and two signed strides, worked out once per workgroup from one uniform byte load.  A kernel
+// of its own and not a branch of the one above: shared through an inlined body, the instances above came out of the compiler
+// with another schedule than they had.
+template <int C, class E>
+__global__ __launch_bounds__(kRsThreads) void k_rs_to_tensor_map(RsToTensorMap g) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long base = (unsigned long long)blockIdx.x * kToTensorBlock;
+    const uint8_t* fsrc = g.src + blockIdx.y * g.src_fs;
+    const unsigned long long mine = base + 4ull * tid;
+    const uint32_t dw = mine < g.frame_bytes ? *(const uint32_t*)(fsrc + mine) : 0u;
+    unsigned long long y0;
+    unsigned rem0;
+    if (g.frame_bytes <= 0xffffffffull) {
+        const unsigned q = (unsigned)base / g.pitch;
+        y0 = q, rem0 = (unsigned)base - q * g.pitch;
+    } else {
+        y0 = base / g.pitch, rem0 = (unsigned)(base - y0 * g.pitch);
+    }
+    E* fout = (E*)(g.out + blockIdx.y * g.out_fs);
+    const int m = g.flip ^ (g.d_flip ? __builtin_amdgcn_readfirstlane((int)g.d_flip[blockIdx.y]) : 0);
+    const long long t_rs = (m & 2) ? -g.rs : g.rs, t_ps = (m & 1) ? -g.ps : g.ps;
+    const long long t_base = ((m & 2) ? (g.h - 1) * g.rs : 0) + ((m & 1) ? (g.w - 1) * g.ps : 0);
+#pragma unroll
+    for (int rr = 0; rr < 4; rr++) {
+        const uint32_t w = (uint32_t)__shfl((int)dw, 16 * rr + (lane >> 2), 64);
+        const unsigned local = (unsigned)(wave * 256 + 64 * rr + lane);
+        if (base + local < g.frame_bytes) {
+            unsigned rem = rem0 + local;   // pitch and the block are below 2^19 samples
+            const unsigned dy = rem / g.pitch;
+            rem -= dy * g.pitch;
+            const unsigned x = rem / C, c = rem - x * C;
+            const unsigned oc = (g.dst >> (8 * c)) & 255u;
+            if (oc < 4) {
+                const E v = ((const E*)g.lut)[oc * 256 + ((w >> (8 * (lane & 3))) & 255u)];
+                fout[t_base + (long long)oc * g.cs + (long long)(y0 + dy) * t_rs + (long long)x * t_ps] = v;
+            }
+        }
+    }
+}
+
 hipError_t rs_to_tensor_launch(const uint8_t* src, size_t src_fs, uint8_t* out, size_t out_fs, int w, int h, int channels,
                                const RsTensorOut& t, int frames, hipStream_t stream) {
-    RsToTensor g{};
+    RsToTensorMap g{};
     g.src_fs = src_fs, g.out_fs = out_fs;
     g.frame_bytes = (unsigned long long)w * h * channels;
     g.pitch = (unsigned)(w * channels);
     g.lut = t.d_lut;
     g.cs = t.chan_stride, g.rs = t.row_stride, g.ps = t.pix_stride;
+    g.dst = t.dst_of_src(), g.flip = t.flip & 3, g.w = w, g.h = h;
     const unsigned blocks = (unsigned)((g.frame_bytes + kToTensorBlock - 1) / kToTensorBlock);   // at most 2^24
     void (*kern)(RsToTensor);
     if (t.elem == 2) kern = channels == 1 ? k_rs_to_tensor<1, uint16_t> : channels == 3 ? k_rs_to_tensor<3, uint16_t> : k_rs_to_tensor<4, uint16_t>;
     else kern = channels == 1 ? k_rs_to_tensor<1, uint32_t> : channels == 3 ? k_rs_to_tensor<3, uint32_t> : k_rs_to_tensor<4, uint32_t>;
+    void (*kern_map)(RsToTensorMap);
+    if (t.elem == 2) kern_map = channels == 1 ? k_rs_to_tensor_map<1, uint16_t> : channels == 3 ? k_rs_to_tensor_map<3, uint16_t> : k_rs_to_tensor_map<4, uint16_t>;
+    else kern_map = channels == 1 ? k_rs_to_tensor_map<1, uint32_t> : channels == 3 ? k_rs_to_tensor_map<3, uint32_t> : k_rs_to_tensor_map<4, uint32_t>;
     for (int f0 = 0; f0 < frames; f0 += 65535) {
         const int nf = std::min(65535, frames - f0);
         g.src = src + (size_t)f0 * src_fs;
         g.out = out + (size_t)f0 * out_fs;
+        g.d_flip = t.d_flip ? t.d_flip + f0 : nullptr;   // a byte per frame
         const dim3 grid(blocks, nf);
-        hipLaunchKernelGGL(kern, grid, dim3(kRsThreads), 0, stream, g);
+        if (t.mapped) hipLaunchKernelGGL(kern_map, grid, dim3(kRsThreads), 0, stream, g);
+        else hipLaunchKernelGGL(kern, grid, dim3(kRsThreads), 0, stream, static_cast<const RsToTensor&>(g));
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -75,6 +75,17 @@ axis runs: the full call is the plain copy, the windowed one the crop copy k_rs_
   parent_full   the full call alone on another build of the library (--parent-lib PATH: the parent commit's)
 Frame 0 of windowed and full_slice are compared byte for byte before timing; a last line gives the ratios and the two plans.
 
+V1, V1h, VW and VWh are tensor views (a channel map and per-frame flips, lanczos_resize_tensor_view_device; --only V1,V1h,VW,VWh;
+a build with the entry), all to normalised CHW with the table in output order.  V1: T1's shape, BGR -> RGB, every other frame
+mirrored horizontally through d_flip, float32; V1h: the same to bfloat16.  VW: 256 RGBA frames (alpha set) of 500x375 -> 341x256,
+window center_window(341, 256, 224, 224), alpha dropped, float32; VWh: the same to bfloat16.  Routes:
+  view            the view under RESIZE_AUTO: the mapped fused instances store the elements
+  view_converted  the view under RESIZE_CONVERT: the byte resize into context scratch, then k_rs_to_tensor_map
+  tensor_torch    the tensor call without a map, then torch's t[:, [2, 1, 0]] / t[:, :3], torch.where(flip, t.flip(-1), t) and
+                  .contiguous() on the same stream: what the view replaces
+  tensor          the tensor call without a map alone
+Frame 0 of view, view_converted and tensor_torch are compared bit for bit before timing; a last line gives the ratios.
+
 --pillow adds Pillow's single-core time of one frame of each workload (if Pillow imports; else "not available"); for U1 and
 U4 that is the time of one I;16 plane (a frame has three), for F1 and F4 that of one F plane.
 """
@@ -576,6 +587,89 @@ def run_window(name, args, ctx, torch, parent):
     torch.cuda.empty_cache()
 
 
+VIEW_WORKLOADS = {   # name: (in_w, in_h, out_w, out_h, channels, alpha, frames, crop (w, h) from the centre or None, channels_out, per-frame flips, bfloat16)
+    "V1": (3840, 2160, 1920, 1080, 3, False, 32, None, (2, 1, 0), True, False),      # T1's shape, BGR -> RGB, every other frame mirrored
+    "V1h": (3840, 2160, 1920, 1080, 3, False, 32, None, (2, 1, 0), True, True),
+    "VW": (500, 375, 341, 256, 4, True, 256, (224, 224), (0, 1, 2), False, False),   # WIN1's shape on RGBA frames, alpha dropped
+    "VWh": (500, 375, 341, 256, 4, True, 256, (224, 224), (0, 1, 2), False, True),
+}
+
+
+def run_view(name, args, ctx, torch):
+    """A tensor view (channel map, per-frame flips) against what it replaces -- the tensor call without one followed by torch's
+    index / where(flip) / .contiguous() on the same stream -- and against that tensor call alone.  CHW, the ImageNet table in
+    output order."""
+    iw, ih, ow, oh, c, alpha, f, crop, src, flips, half = VIEW_WORKLOADS[name]
+    window = L.center_window(ow, oh, *crop) if crop else None
+    w, h = (window[2], window[3]) if window else (ow, oh)
+    oc = len(src)
+    in_fb, full_fb, view_fb = iw * ih * c, w * h * c, w * h * oc
+    sets = max(2, -(-2 * 256 * 2 ** 20 // (f * in_fb)) + 1)
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    dt = torch.bfloat16 if half else torch.float32
+    dtype = "bfloat16" if half else "float32"
+    xs = [torch.randint(0, 256, (f * in_fb,), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(sets)]
+    ys = [torch.empty(f * view_fb, dtype=dt, device="cuda") for _ in range(sets)]    # the view's results
+    fulls = [torch.empty(f * full_fb, dtype=dt, device="cuda") for _ in range(sets)]   # every source channel, unflipped
+    d = L.resize_desc(iw, ih, ow, oh, c, alpha=alpha)
+    win = L.resize_window(d, window) if window else None
+    # the table in output order, and the same rows in source order for the call without a map (a dropped channel gets zeros)
+    lut_out = L.normalize_lut(oc, IMAGENET_MEAN[:oc], IMAGENET_STD[:oc], dtype=dtype)
+    lut_src = np.zeros((c, 256), dtype=lut_out.dtype)
+    for o, sc in enumerate(src):
+        lut_src[sc] = lut_out[o]
+    as_dev = lambda a: torch.from_numpy(a.view(np.int16) if half else a).cuda()
+    d_out, d_src = as_dev(lut_out), as_dev(lut_src)
+    fl = np.array([k & 1 for k in range(f)], dtype=np.uint8) if flips else None
+    d_flip = torch.from_numpy(fl).cuda() if flips else None
+    mask = torch.from_numpy(fl.astype(bool)).cuda().view(f, 1, 1, 1) if flips else None
+    index = torch.tensor(src, device="cuda")
+    st_view, st_full = L.tensor_strides("chw", w, h, oc), L.tensor_strides("chw", w, h, c)
+    s = torch.cuda.current_stream().cuda_stream
+    bits = (lambda y: y.view(torch.int16)) if half else (lambda y: y.view(torch.int32))
+    seen = {}
+
+    def view(path):
+        def step(i):
+            ctx.resize_force(path)
+            ctx.resize_tensor_device(d, xs[i % sets].data_ptr(), ys[i % sets].data_ptr(), f, d_out.data_ptr(), st_view, stream=s,
+                                     dtype=dtype, window=win, channels_out=src, d_flip=d_flip.data_ptr() if flips else None)
+            seen[path] = ctx.last_tensor_route()
+            return bits(ys[i % sets][:view_fb])
+        return step
+
+    def tensor(i):
+        ctx.resize_force(L.RESIZE_AUTO)
+        ctx.resize_tensor_device(d, xs[i % sets].data_ptr(), fulls[i % sets].data_ptr(), f, d_src.data_ptr(), st_full, stream=s,
+                                 dtype=dtype, window=win)
+        return bits(fulls[i % sets][:full_fb])
+
+    def tensor_torch(i):
+        tensor(i)
+        t = fulls[i % sets].view(f, c, h, w)
+        t = t[:, :oc] if src == tuple(range(oc)) else t[:, index]
+        if flips:
+            t = torch.where(mask, t.flip(-1), t)
+        return bits(t.contiguous().view(-1)[:view_fb])
+
+    routes = {"view": view(L.RESIZE_AUTO), "view_converted": view(L.RESIZE_CONVERT), "tensor_torch": tensor_torch, "tensor": tensor}
+    e = 2 if half else 4
+    inb = {rn: f * in_fb for rn in routes}
+    outb = {rn: e * f * view_fb for rn in routes}
+    outb["tensor"] = e * f * full_fb
+    us = run_routes(name, f"{iw}x{ih}->{ow}x{oh} C{c}{' alpha' if alpha else ''} -> channels {src}" +
+                    (f" window {window}" if window else "") + (" flips 0,1,0,1.." if flips else "") + f" chw {dtype}", f, routes,
+                    inb, outb, args, ctx, torch, check=(("view", "view_converted"), ("view", "tensor_torch")))
+    ctx.resize_force(L.RESIZE_AUTO)
+    if (seen[L.RESIZE_AUTO], seen[L.RESIZE_CONVERT]) != (L.TENSOR_FUSED, L.TENSOR_CONVERTED):
+        raise SystemExit(f"{name}: routes {seen}")
+    print(json.dumps({"workload": name, "view_over_tensor_torch": round(us["view"] / us["tensor_torch"], 3),
+                      "view_over_tensor": round(us["view"] / us["tensor"], 3),
+                      "view_over_view_converted": round(us["view"] / us["view_converted"], 3), "measured": True}), flush=True)
+    del xs, ys, fulls
+    torch.cuda.empty_cache()
+
+
 def run_gap(name, args, ctx, torch):
     iw, ih, ow, oh, c, a, f = WORKLOADS["W5"]
     in_fb, out_fb = iw * ih * c, ow * oh * c
@@ -671,6 +765,8 @@ def main():
     for name in args.only.split(","):
         if name in WINDOW_WORKLOADS:
             run_window(name, args, ctx, torch, parent)
+        elif name in VIEW_WORKLOADS:
+            run_view(name, args, ctx, torch)
         elif name in TENSOR_WORKLOADS:
             run_tensor(name, args, ctx, torch, parent)
         elif name.endswith("h") and name[:-1] in TENSOR_WORKLOADS:
