@@ -623,6 +623,52 @@ int lanczos_resize_tensor_view_host(lanczos_ctx* ctx, const lanczos_resize_desc*
                                     const lanczos_resize_window* win, const lanczos_tensor_view* v, const void* in, void* out,
                                     int frames);
 
+/* ---- tensor outputs with a crop origin per frame (Resize -> RandomCrop -> RandomHorizontalFlip -> ToTensor -> Normalize) ----
+ * A tensor view whose window has one size (w, h) for the whole batch and an origin per frame, read from device memory when the
+ * kernels run.  With P_full(f, y, x, c) the byte lanczos_resize_device_ex stores for the same descriptor and options WITHOUT a
+ * window, m_f the flip bits of lanczos_tensor_view and (x0_f, y0_f) frame f's origin after clamping:
+ *   out[f][oc * chan_stride + Y * row_stride + X * pix_stride] = lut[oc * 256 + P_full(f, y0_f + y, x0_f + x, src_channel[oc])]
+ *   X = (m_f & 1) ? w - 1 - x : x        Y = (m_f & 2) ? h - 1 - y : y                            0 <= x < w, 0 <= y < h
+ *   x0_f = min(max(d_origin[2 f], 0), out_w - w)        y0_f = min(max(d_origin[2 f + 1], 0), out_h - h)
+ * Exact by construction, as a window is.  Everything else is lanczos_tensor_view's contract with (w, h) as the frame: every
+ * filter, box and reducing_gap, LANCZOS_RESIZE_ALPHA, both element widths, the overlap rule, the extent, elements the strides
+ * do not name left untouched, the 2^31-byte limit of the fused route.  d_origin lives as d_lut and d_flip do: it is read WHEN
+ * THE KERNELS RUN, and a replayed graph follows its contents of that moment.  THE CLAMP IS PART OF THE CONTRACT and of the
+ * kernels: device memory cannot be validated, and an origin outside the output would index the tap tables out of range.
+ * Routes: LANCZOS_TENSOR_FUSED exactly when lanczos_resize_crops_plan_host says fused -- its plan holds for every origin, which
+ * the plan of the window at one origin does not -- and the element frame spans less than 2^31 bytes.  Every other request
+ * (two passes, one pass, LANCZOS_FILTER_NEAREST, a plan that does not fit, forced LANCZOS_RESIZE_TWO_PASS / _CONVERT) is
+ * LANCZOS_TENSOR_CONVERTED: the bytes of the WHOLE output go to context scratch and one launch gathers every frame's window
+ * from it; a request that changes neither axis gathers from the caller's frames, with no scratch and no copy (RandomCrop +
+ * flip + ToTensor + Normalize of frames already at size).  Forced LANCZOS_RESIZE_FUSED is LANCZOS_ERR_UNSUPPORTED where the
+ * crops plan is not fused.  lanczos_last_tensor_route and lanczos_last_kernel report as for a view. */
+typedef struct lanczos_resize_crops {
+    int32_t w, h;               /* 1..out_w, 1..out_h: the size of every frame's window */
+    const int32_t* d_origin;    /* `frames` pairs (x0, y0) in output pixels of the full request; 4-byte aligned */
+    int32_t reserved[4];        /* must be 0 */
+} lanczos_resize_crops;
+/* Host only; d_origin is not read.  LANCZOS_ERR_BAD_ARG: what lanczos_resize_validate refuses, a null struct, w or h below 1
+ * or above the output, a null or misaligned d_origin, non-zero reserved words. */
+int lanczos_resize_crops_validate(const lanczos_resize_desc* d, const lanczos_resize_crops* crops);
+/* lanczos_resize_plan_host_ex for a crops request; d_origin is not read.  inner.ring_rows and inner.stage_dw are the largest
+ * lanczos_resize_window_plan_host reports for the window (x0, y0, w, h) over every legal origin, stage_rows and lds_bytes
+ * follow from them, and K, strips, rows_per_chunk and chunks are the window's at any origin.  fused = 0 where those maxima do
+ * not fit, even if the window at some origins would.  mid_row0 / mid_rows are the whole output's. */
+int lanczos_resize_crops_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                   const lanczos_resize_crops* crops, int frames, lanczos_resize_plan_ex* out);
+/* Host only: lanczos_resize_crops_validate, then lanczos_resize_tensor_view_validate with (w, h) as the frame. */
+int lanczos_resize_tensor_crops_validate(const lanczos_resize_desc* d, const lanczos_resize_crops* crops,
+                                         const lanczos_tensor_view* v);
+/* As lanczos_resize_tensor_view_device with (w, h) as the frame; d_lut, d_flip and d_origin are device pointers. */
+int lanczos_resize_tensor_crops_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                       const lanczos_resize_crops* crops, const lanczos_tensor_view* v, const void* d_in,
+                                       void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream);
+/* Host buffers, a HOST table, a HOST flip array and HOST origins (`frames` pairs in crops->d_origin); synchronous.  An origin
+ * outside [0, out_w - w] x [0, out_h - h] is LANCZOS_ERR_BAD_ARG here: the host array can be validated, so it is not clamped. */
+int lanczos_resize_tensor_crops_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                     const lanczos_resize_crops* crops, const lanczos_tensor_view* v, const void* in, void* out,
+                                     int frames);
+
 /* ---- reduce by whole factors (Pillow's Image.reduce((fx, fy), box), an exact integer box average) ----
  * 8-bit, 1, 3 or 4 independent interleaved channels.  box = (x0, y0, x1, y1), integers with 0 <= x0 < x1 <= in_w and the same
  * for y; NULL = the whole frame.  The output is ceil((x1 - x0) / fx) x ceil((y1 - y0) / fy) pixels, tightly packed rows.

@@ -72,6 +72,8 @@ ABI_SYMBOLS = [
     "lanczos_resize_tensor16_window_device", "lanczos_resize_tensor16_window_host",
     "lanczos_tensor_view_init", "lanczos_resize_tensor_view_validate", "lanczos_resize_tensor_view_device",
     "lanczos_resize_tensor_view_host",
+    "lanczos_resize_crops_validate", "lanczos_resize_crops_plan_host", "lanczos_resize_tensor_crops_validate",
+    "lanczos_resize_tensor_crops_device", "lanczos_resize_tensor_crops_host",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
 
@@ -179,6 +181,12 @@ class TensorView(ctypes.Structure):
                 ("pix_stride", ctypes.c_int64), ("elem_bytes", ctypes.c_int32), ("out_channels", ctypes.c_int32),
                 ("src_channel", ctypes.c_int32 * 4), ("flip", ctypes.c_int32), ("d_flip", ctypes.c_void_p),
                 ("reserved", ctypes.c_int32 * 4)]
+
+
+class ResizeCrops(ctypes.Structure):
+    """lanczos_resize_crops -- one window size (w, h) for every frame and a pointer to `frames` pairs (x0, y0) of int32, the
+    window's origin per frame in output pixels of the full request; read, and clamped into the output, when the kernels run."""
+    _fields_ = [("w", ctypes.c_int32), ("h", ctypes.c_int32), ("d_origin", ctypes.c_void_p), ("reserved", ctypes.c_int32 * 4)]
 
 
 FLIP_H, FLIP_V = 1, 2   # the bits of lanczos_tensor_view.flip and of a d_flip byte
@@ -322,6 +330,14 @@ def _lib():
             L.lanczos_resize_tensor_view_device.argtypes = [c_void_p, PRD, PRO, PRW, PTV, c_void_p, c_void_p, c_int, c_size_t,
                                                             c_size_t, c_void_p]
             L.lanczos_resize_tensor_view_host.argtypes = [c_void_p, PRD, PRO, PRW, PTV, c_void_p, c_void_p, c_int]
+        if hasattr(L, "lanczos_resize_tensor_crops_device"):   # (nor a crop origin per frame)
+            PRC = ctypes.POINTER(ResizeCrops)
+            L.lanczos_resize_crops_validate.argtypes = [PRD, PRC]
+            L.lanczos_resize_crops_plan_host.argtypes = [PRD, PRO, PRC, c_int, ctypes.POINTER(ResizePlanEx)]
+            L.lanczos_resize_tensor_crops_validate.argtypes = [PRD, PRC, PTV]
+            L.lanczos_resize_tensor_crops_device.argtypes = [c_void_p, PRD, PRO, PRC, PTV, c_void_p, c_void_p, c_int, c_size_t,
+                                                             c_size_t, c_void_p]
+            L.lanczos_resize_tensor_crops_host.argtypes = [c_void_p, PRD, PRO, PRC, PTV, c_void_p, c_void_p, c_int]
         L.lanczos_strerror.restype = ctypes.c_char_p
         L.lanczos_version.argtypes = []
         L.lanczos_version.restype = ctypes.c_char_p
@@ -517,6 +533,39 @@ def resize_window_plan_host(desc, window=None, frames=1, box=None, reducing_gap=
     _check(_lib().lanczos_resize_window_plan_host(ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
                                                   _window_ref(desc, window), frames, ctypes.byref(p)),
            "lanczos_resize_window_plan_host")
+    return p
+
+
+def resize_crops(w, h, d_origin):
+    """A ResizeCrops: every frame stores the w x h window of its resize whose origin is its pair (x0, y0) of the int32 array
+    at d_origin (device memory for the device entry, 4-byte aligned), clamped so that the window lies inside the output.
+    Validated where it is used (resize_crops_validate)."""
+    c = ResizeCrops()
+    c.w, c.h, c.d_origin = int(w), int(h), d_origin
+    return c
+
+
+def resize_crops_validate(desc, crops, view=None):
+    """lanczos_resize_crops_validate, or with a TensorView lanczos_resize_tensor_crops_validate (the view's strides describe the
+    w x h frame): raises LanczosError where the request is refused."""
+    cp = ctypes.byref(crops) if crops is not None else None
+    if view is None:
+        _check(_lib().lanczos_resize_crops_validate(ctypes.byref(desc), cp), "lanczos_resize_crops_validate")
+    else:
+        _check(_lib().lanczos_resize_tensor_crops_validate(ctypes.byref(desc), cp, ctypes.byref(view)),
+               "lanczos_resize_tensor_crops_validate")
+
+
+def resize_crops_plan_host(desc, crops, frames=1, box=None, reducing_gap=None, opts=None):
+    """The ResizePlanEx of a crops request (no GPU needed; d_origin is not read): inner.ring_rows and inner.stage_dw are the
+    largest resize_window_plan_host reports for (x0, y0, w, h) over every origin inside the output, and inner.fused is 0 where
+    those do not fit.  crops: a ResizeCrops or (w, h)."""
+    if not isinstance(crops, ResizeCrops):
+        dummy = (ctypes.c_int32 * 2)()
+        crops = resize_crops(crops[0], crops[1], ctypes.addressof(dummy))
+    p = ResizePlanEx()
+    _check(_lib().lanczos_resize_crops_plan_host(ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
+                                                 ctypes.byref(crops), frames, ctypes.byref(p)), "lanczos_resize_crops_plan_host")
     return p
 
 
@@ -877,8 +926,12 @@ class Context:
 
     # -- resize straight into a float tensor (PIL.Image.resize -> ToTensor() -> Normalize(), lanczos_resize_tensor_*)
     def resize_tensor(self, img, out_w, out_h, mean=None, std=None, lut=None, layout="chw", a=3, alpha=False, box=None,
-                      reducing_gap=None, filter=FILTER_LANCZOS, dtype="float32", window=None, channels_out=None, flip=None):
-        """channels_out: a tuple of source channel indices, one per channel of the result -- (2, 1, 0) turns BGR into RGB,
+                      reducing_gap=None, filter=FILTER_LANCZOS, dtype="float32", window=None, channels_out=None, flip=None,
+                      crop=None, origins=None):
+        """crop=(w, h) with origins=[(x0, y0), ...], one pair per frame: frame f of the result is the w x h window of its
+        resize at origins[f] (Resize -> RandomCrop; lanczos_resize_tensor_crops_host, which refuses an origin outside the
+        output).  channels_out and flip apply as below; not together with window.
+        channels_out: a tuple of source channel indices, one per channel of the result -- (2, 1, 0) turns BGR into RGB,
         (0, 1, 2) on an RGBA frame drops alpha (with alpha=True the colours are un-premultiplied first, Pillow's resize in mode
         RGBA then .convert("RGB")); distinct indices, no replication.  The result then has len(channels_out) channels, and the
         table (lut, or mean / std) is [len(channels_out)][256] in OUTPUT order.  flip: None, "h", "v", "hv", or an integer
@@ -921,6 +974,16 @@ class Context:
         lut = np.ascontiguousarray(lut)
         if lut.dtype not in ((np.float32,) if wide else (np.uint16, np.float16)) or lut.size != c * 256:
             raise LanczosError(ERR_BAD_ARG, f"resize_tensor: the table is {'float32' if wide else 'uint16 or float16'} [{c}][256]")
+        if (crop is None) != (origins is None) or (crop is not None and window is not None):
+            raise LanczosError(ERR_BAD_ARG, "resize_tensor: crop= and origins= come together, and not with window=")
+        org = None
+        if crop is not None:
+            org = np.ascontiguousarray(origins)
+            if len(crop) != 2 or org.shape != (f, 2) or org.dtype.kind not in "iu":
+                raise LanczosError(ERR_BAD_ARG, f"resize_tensor: crop is (w, h) and origins {f} integer pairs (x0, y0)")
+            org = org.astype(np.int32)
+            window = (0, 0, int(crop[0]), int(crop[1]))   # the frame the strides describe
+            view = True
         win = resize_window(d, window)
         strides = tensor_strides(layout, win.w, win.h, c)
         shape = (f, c, win.h, win.w) if layout == "chw" else (f, win.h, win.w, c)
@@ -939,8 +1002,14 @@ class Context:
                             channels_out if channels_out is not None else tuple(range(c)),
                             0 if flips is not None else flip, flips.ctypes.data if flips is not None else None)
             out = np.empty(shape, dtype=np.float32 if wide else np.uint16)
-            _check(_lib().lanczos_resize_tensor_view_host(self._h, ctypes.byref(d), opts, wref, ctypes.byref(v), x.ctypes.data,
-                                                          out.ctypes.data, f), "lanczos_resize_tensor_view_host")
+            if org is not None:
+                cr = resize_crops(win.w, win.h, org.ctypes.data)
+                _check(_lib().lanczos_resize_tensor_crops_host(self._h, ctypes.byref(d), opts, ctypes.byref(cr), ctypes.byref(v),
+                                                               x.ctypes.data, out.ctypes.data, f),
+                       "lanczos_resize_tensor_crops_host")
+            else:
+                _check(_lib().lanczos_resize_tensor_view_host(self._h, ctypes.byref(d), opts, wref, ctypes.byref(v), x.ctypes.data,
+                                                              out.ctypes.data, f), "lanczos_resize_tensor_view_host")
             out = out if wide else _tensor16_array(out, dtype)
         elif wide:
             t = tensor_out(lut.ctypes.data, strides)
@@ -967,8 +1036,11 @@ class Context:
 
     def resize_tensor_device(self, desc, d_in, d_out, frames, d_lut, strides, in_frame_stride=0, out_frame_stride=0,
                              stream=None, box=None, reducing_gap=None, opts=None, dtype="float32", window=None,
-                             channels_out=None, flip=None, d_flip=None):
-        """channels_out / flip as Context.resize_tensor (flip: None, "h", "v", "hv" or FLIP_* bits, for every frame); d_flip: a
+                             channels_out=None, flip=None, d_flip=None, crop=None, d_origin=None):
+        """crop=(w, h) with d_origin, a device pointer to `frames` int32 pairs (x0, y0) (or crop a ready ResizeCrops): every
+        frame stores the w x h window of its resize at its own origin, read and clamped into the output when the kernels run
+        (lanczos_resize_tensor_crops_device).  The strides describe the C x h x w frame; not together with window.
+        channels_out / flip as Context.resize_tensor (flip: None, "h", "v", "hv" or FLIP_* bits, for every frame); d_flip: a
         device pointer to one byte per frame, XORed with flip and read when the kernels run.  With any of the three, or a ready
         TensorView as `strides`, the call is lanczos_resize_tensor_view_device: the table at d_lut is [len(channels_out)][256]
         in output order and the strides describe a frame of that many channels.
@@ -980,8 +1052,12 @@ class Context:
         elements, d_out and out_frame_stride multiples of 2.  window = (x0, y0, w, h) or a ResizeWindow: the element frames
         are that window of the output, and the strides describe its C x h x w frame (tensor_strides(layout, w, h, C))."""
         oref = _opts_ref(desc, box, reducing_gap, opts)
+        if crop is not None and window is not None:
+            raise LanczosError(ERR_BAD_ARG, "resize_tensor_device: crop= or window=, not both")
+        if (crop is None or not isinstance(crop, ResizeCrops)) and (crop is None) != (d_origin is None):
+            raise LanczosError(ERR_BAD_ARG, "resize_tensor_device: crop=(w, h) and d_origin= come together")
         wref = _window_ref(desc, window)
-        if isinstance(strides, TensorView) or channels_out is not None or flip is not None or d_flip is not None:
+        if crop is not None or isinstance(strides, TensorView) or channels_out is not None or flip is not None or d_flip is not None:
             if isinstance(strides, TensorView):
                 v = strides
             else:
@@ -989,6 +1065,12 @@ class Context:
                     _tensor16_format(dtype, "resize_tensor_device")
                 v = tensor_view(d_lut, strides, 4 if dtype == "float32" else 2,
                                 channels_out if channels_out is not None else tuple(range(desc.channels)), flip or 0, d_flip)
+            if crop is not None:
+                cr = crop if isinstance(crop, ResizeCrops) else resize_crops(crop[0], crop[1], d_origin)
+                _check(_lib().lanczos_resize_tensor_crops_device(self._h, ctypes.byref(desc), oref, ctypes.byref(cr), ctypes.byref(v),
+                                                                 d_in, d_out, frames, in_frame_stride, out_frame_stride, stream),
+                       "lanczos_resize_tensor_crops_device")
+                return
             _check(_lib().lanczos_resize_tensor_view_device(self._h, ctypes.byref(desc), oref, wref, ctypes.byref(v), d_in,
                                                             d_out, frames, in_frame_stride, out_frame_stride, stream),
                    "lanczos_resize_tensor_view_device")

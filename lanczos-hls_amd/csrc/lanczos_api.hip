@@ -1309,7 +1309,8 @@ static int tensor_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const l
 
 // ... and of a host request (lay filled)
 static int tensor_host_run(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
-                           const lanczos_resize_window* win, const lz::RsTensorOut& lay, const void* in, void* out, int frames) {
+                           const lanczos_resize_window* win, const lz::RsTensorOut& lay, const void* in, void* out, int frames,
+                           const int32_t* origins = nullptr) {
     std::lock_guard<std::mutex> lock(ctx->mu);
     LZ_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->stream) return LANCZOS_ERR_HIP;
@@ -1317,7 +1318,7 @@ static int tensor_host_run(lanczos_ctx* ctx, const lanczos_resize_desc* d, const
     if (rc != LANCZOS_OK) return rc;
     route_begin(ctx);
     return lz::resize_tensor_host(ctx->resize, d, opts, win, lay, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip,
-                                  &ctx->last_tensor_route);
+                                  &ctx->last_tensor_route, origins);
 }
 
 template <class T>
@@ -1451,6 +1452,63 @@ int lanczos_resize_tensor_view_host(lanczos_ctx* ctx, const lanczos_resize_desc*
     const int rc = lz::tensor_view_validate(d, win, v, &lay);
     if (rc != LANCZOS_OK) return rc;
     return tensor_host_run(ctx, d, opts, win, lay, in, out, frames);
+}
+
+int lanczos_resize_crops_validate(const lanczos_resize_desc* d, const lanczos_resize_crops* crops) {
+    return lz::resize_crops_validate(d, crops);
+}
+
+int lanczos_resize_crops_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_crops* crops,
+                                   int frames, lanczos_resize_plan_ex* out) {
+    const int rc = lz::resize_crops_validate(d, crops);
+    if (rc != LANCZOS_OK) return rc;
+    if (frames < 1 || !out) return LANCZOS_ERR_BAD_ARG;
+    return lz::resize_plan_host(d, o, nullptr, frames, out, crops);
+}
+
+extern "C++" {
+// a crops request is a view whose frame is the window (0, 0, w, h): validated as one, *win filled
+static int tensor_crops_validate(const lanczos_resize_desc* d, const lanczos_resize_crops* crops, const lanczos_tensor_view* v,
+                                 lanczos_resize_window* win, lz::RsTensorOut* lay) {
+    const int rc = lz::resize_crops_validate(d, crops);
+    if (rc != LANCZOS_OK) return rc;
+    *win = lanczos_resize_window{0, 0, crops->w, crops->h, {0, 0, 0, 0}};
+    return lz::tensor_view_validate(d, win, v, lay);
+}
+}   // extern "C++"
+
+int lanczos_resize_tensor_crops_validate(const lanczos_resize_desc* d, const lanczos_resize_crops* crops,
+                                         const lanczos_tensor_view* v) {
+    lanczos_resize_window win;
+    lz::RsTensorOut lay;
+    return tensor_crops_validate(d, crops, v, &win, &lay);
+}
+
+int lanczos_resize_tensor_crops_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                       const lanczos_resize_crops* crops, const lanczos_tensor_view* v, const void* d_in,
+                                       void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    lanczos_resize_window win;
+    lz::RsTensorCall tc;
+    const int rc = tensor_crops_validate(d, crops, v, &win, &tc.t);
+    if (rc != LANCZOS_OK) return rc;
+    tc.d_origin = crops->d_origin;
+    return tensor_device_run(ctx, d, opts, &win, tc, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+}
+
+int lanczos_resize_tensor_crops_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                     const lanczos_resize_crops* crops, const lanczos_tensor_view* v, const void* in, void* out,
+                                     int frames) {
+    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    lanczos_resize_window win;
+    lz::RsTensorOut lay;
+    const int rc = tensor_crops_validate(d, crops, v, &win, &lay);
+    if (rc != LANCZOS_OK) return rc;
+    for (int f = 0; f < frames; f++) {   // a host array can be validated: nothing is clamped here
+        const int32_t x0 = crops->d_origin[2 * f], y0 = crops->d_origin[2 * f + 1];
+        if (x0 < 0 || x0 > d->out_w - crops->w || y0 < 0 || y0 > d->out_h - crops->h) return LANCZOS_ERR_BAD_ARG;
+    }
+    return tensor_host_run(ctx, d, opts, &win, lay, in, out, frames, crops->d_origin);
 }
 
 int lanczos_last_tensor_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_tensor_route : 0; }

@@ -29,6 +29,11 @@
 // output size.  Plan, scratch and output strides follow the window.  Only the request that changes neither axis has device
 // code of its own for it, the crop copy k_rs_crop (lanczos_resize_nearest.hip).
 //
+// A crop origin per frame (lanczos_resize_crops, tensor requests only) is a window whose size is known here and whose origin
+// only the kernels see: the fused plan is the largest over every origin (rs_fused_plan_crops), the crops instances of k_rs_fused
+// move their table pointers by the frame's origin, and every other route resizes the whole output and lets
+// k_rs_to_tensor_crops gather the windows (lanczos_resize_tensor_crops.hip).
+//
 // The arithmetic is Pillow's and exact by construction; RsSample<BPS> says how for each width.
 #include "lanczos_resize.hpp"
 
@@ -463,12 +468,34 @@ static int rs_scratch(ResizeState* st, ResizeState::Block* blk, size_t bytes, hi
     return LANCZOS_OK;
 }
 
-// the fused kernel's launch shape for this request, both of whose passes run (false: it cannot run it).  The output is that
-// of the two views, a window of d's
-bool rs_fused_plan(const lanczos_resize_desc* d, const RsAxisView& H, const RsAxisView& V, int frames, RsFusedPlan* fp) {
+// The two sizes of the plan that depend on where a window lies.  stage_dw: the dwords of a staged row, the widest span of
+// source bytes one of the window's strips reads.  ring_rows: the most intermediate rows a march step of kRsOB output rows
+// reads; the steps start every kRsOB rows from the window's first (chunks are whole steps) and the last one may be short.
+static int rs_plan_stage_dw(const RsAxisView& H, int x_at, int w, int SW, int C, int NE) {
+    int span_dw = 0;
+    for (int x0 = 0; x0 < w; x0 += SW) {
+        const int x1 = std::min(w, x0 + SW) - 1;
+        const int hoffb = (H.first[x_at + x1] - H.first[x_at + x0]) * C;
+        span_dw = std::max(span_dw, ((3 + hoffb) >> 2) + NE + 1);
+    }
+    return span_dw;
+}
+static int rs_plan_ring_rows(const RsAxisView& V, int y_at, int h) {
+    int ring = 1;
+    for (int o0 = 0; o0 < h; o0 += kRsOB) {
+        const int last = std::min(o0 + kRsOB, h) - 1;
+        ring = std::max(ring, V.first[y_at + last] + V.count[y_at + last] - V.first[y_at + o0]);
+    }
+    return ring;
+}
+
+// The fused kernel's launch shape for a w x h window of the output of H x V whose origin is any of nx x ny places from the
+// views' first outputs on: stage_dw and ring_rows are the largest any of them needs.  One place is the window itself.
+static bool rs_fused_plan_at(const lanczos_resize_desc* d, const RsAxisView& H, const RsAxisView& V, int w, int h, int nx, int ny,
+                             int frames, RsFusedPlan* fp) {
     const int bps = resize_bps(d);
     const int C = d->channels * bps;   // bytes per pixel
-    const int out_w = H.n, out_h = V.n;
+    const int out_w = w, out_h = h;
     if ((long long)d->in_w * d->in_h * C + 4 >= (1ll << 31)) return false;   // 32-bit buffer offsets
     if ((long long)out_w * out_h * C >= (1ll << 31)) return false;
     const bool small = resize_filter(d) != LANCZOS_FILTER_LANCZOS;   // the instances with 3 and 5 taps
@@ -477,18 +504,10 @@ bool rs_fused_plan(const lanczos_resize_desc* d, const RsAxisView& H, const RsAx
     const int SW = rs_strip_width(d->channels, bps);
     const int NE = (fp->K * C + 3) / 4;
     fp->strips = (out_w + SW - 1) / SW;
-    int span_dw = 0;
-    for (int s = 0; s < fp->strips; s++) {
-        const int x0 = s * SW, x1 = std::min(out_w, x0 + SW) - 1;
-        const int hoffb = (H.first[x1] - H.first[x0]) * C;
-        span_dw = std::max(span_dw, ((3 + hoffb) >> 2) + NE + 1);
-    }
-    fp->stage_dw = span_dw;
+    fp->stage_dw = 0;
+    for (int x = 0; x < nx; x++) fp->stage_dw = std::max(fp->stage_dw, rs_plan_stage_dw(H, x, out_w, SW, C, NE));
     int ring = 1;
-    for (int o0 = 0; o0 < out_h; o0 += kRsOB) {
-        const int last = std::min(o0 + kRsOB, out_h) - 1;
-        ring = std::max(ring, V.first[last] + V.count[last] - V.first[o0]);
-    }
+    for (int y = 0; y < ny; y++) ring = std::max(ring, rs_plan_ring_rows(V, y, out_h));
     fp->ring_rows = ring;
     const double scale_v = V.scale;
     fp->stage_rows = std::min(16, (int)ceil(kRsOB * scale_v) + 1);
@@ -506,8 +525,32 @@ bool rs_fused_plan(const lanczos_resize_desc* d, const RsAxisView& H, const RsAx
     return (long long)fp->strips * fp->chunks < (1ll << 31);
 }
 
+// the fused kernel's launch shape for this request, both of whose passes run (false: it cannot run it).  The output is that
+// of the two views, a window of d's
+bool rs_fused_plan(const lanczos_resize_desc* d, const RsAxisView& H, const RsAxisView& V, int frames, RsFusedPlan* fp) {
+    return rs_fused_plan_at(d, H, V, H.n, V.n, 1, 1, frames, fp);
+}
+
+// ... and for a w x h window at any origin inside the output of the two views, which are the full axes: brute force over the
+// origins of each axis, a few hundred at most times a handful of strips or march steps
+bool rs_fused_plan_crops(const lanczos_resize_desc* d, const RsAxisView& H, const RsAxisView& V, int w, int h, int frames,
+                         RsFusedPlan* fp) {
+    return rs_fused_plan_at(d, H, V, w, h, H.n - w + 1, V.n - h + 1, frames, fp);
+}
+
+int resize_crops_validate(const lanczos_resize_desc* d, const lanczos_resize_crops* c) {
+    const int rc = resize_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    if (!c || !c->d_origin) return LANCZOS_ERR_BAD_ARG;
+    for (int32_t r : c->reserved)
+        if (r != 0) return LANCZOS_ERR_BAD_ARG;
+    if (c->w < 1 || c->w > d->out_w || c->h < 1 || c->h > d->out_h) return LANCZOS_ERR_BAD_ARG;
+    if (((uintptr_t)c->d_origin & 3) != 0) return LANCZOS_ERR_BAD_ARG;
+    return LANCZOS_OK;
+}
+
 int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win, int frames,
-                     lanczos_resize_plan_ex* out) {
+                     lanczos_resize_plan_ex* out, const lanczos_resize_crops* crops) {
     memset(out, 0, sizeof(*out));
     RsResolved r;
     RsWindow w;
@@ -529,7 +572,9 @@ int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o,
     if (!r.need_h || !r.need_v) return LANCZOS_OK;   // as resize_device: no table for an idle axis, nothing to fuse
     if (!resize_build_axis(r.inner.in_w, r.inner.out_w, d->a, filter, r.h, &H, u16)) return LANCZOS_ERR_UNSUPPORTED;
     RsFusedPlan fp;
-    if (!rs_fused_plan(&r.inner, rs_axis_view(H, w.x0, w.w), rs_axis_view(V, w.y0, w.h), frames, &fp)) return LANCZOS_OK;
+    if (crops ? !rs_fused_plan_crops(&r.inner, rs_axis_view(H, 0, H.out_n), rs_axis_view(V, 0, V.out_n), crops->w, crops->h, frames, &fp)
+              : !rs_fused_plan(&r.inner, rs_axis_view(H, w.x0, w.w), rs_axis_view(V, w.y0, w.h), frames, &fp))
+        return LANCZOS_OK;
     lanczos_resize_plan* in = &out->inner;
     in->fused = 1;
     in->K = fp.K, in->strips = fp.strips, in->rows_per_chunk = fp.rows_per_chunk, in->chunks = fp.chunks;
@@ -579,7 +624,10 @@ static hipError_t rs_launch_pass(int bps, bool horizontal, const ResizeAxis* ax,
 // everything else writes its bytes to context scratch and k_rs_to_tensor follows
 // win: the window of d's output that is stored, as a tightly packed win.w x win.h frame.  The passes that run and the tables
 // are those of the full request; plan, scratch and every launch are the window's
-static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh, RsSpan sv, const RsWindow& win,
+// tc->d_origin (a crop origin per frame): win is (0, 0, w, h).  The fused kernel runs on the plan that holds for every origin;
+// everything else resizes the whole output into context scratch and k_rs_to_tensor_crops gathers each frame's window from it --
+// or from the caller's frames where no pass runs
+static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh, RsSpan sv, const RsWindow& win_in,
                         const uint8_t* in, uint8_t* out, int frames, size_t in_fs, size_t out_fs, hipStream_t stream,
                         int* last_kernel, int* last_hip, RsTensorCall* tc) {
     const int C = d->channels;
@@ -603,18 +651,30 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     for (ResizeAxis* ax : {H, V})
         if (ax && !capturing) note_stream(ax->streams, stream);
 
+    const bool crops = tc && tc->d_origin;
+    RsWindow win = win_in;
     RsFusedPlan fp;
-    const bool fused_ok = !nearest && need_h && need_v &&
-                          rs_fused_plan(d, rs_axis_view(H->host, win.x0, win.w), rs_axis_view(V->host, win.y0, win.h), frames, &fp);
+    bool fused_ok = !nearest && need_h && need_v &&
+                    (crops ? rs_fused_plan_crops(d, rs_axis_view(H->host, 0, d->out_w), rs_axis_view(V->host, 0, d->out_h), win.w, win.h,
+                                                 frames, &fp)
+                           : rs_fused_plan(d, rs_axis_view(H->host, win.x0, win.w), rs_axis_view(V->host, win.y0, win.h), frames, &fp));
     if (st->force == LANCZOS_RESIZE_FUSED && !fused_ok) return LANCZOS_ERR_UNSUPPORTED;
-    const bool fused = fused_ok && st->force != LANCZOS_RESIZE_TWO_PASS;
+    bool fused = fused_ok && st->force != LANCZOS_RESIZE_TWO_PASS;
     // 32-bit buffer offsets into the element frame: a larger one is converted, and refused where the fused kernel is forced
     const bool t_fits = tc && tc->extent_bytes < ((size_t)1 << 31);
     if (tc && st->force == LANCZOS_RESIZE_FUSED && !t_fits) return LANCZOS_ERR_UNSUPPORTED;
     const bool t_fused = fused && t_fits && st->force != LANCZOS_RESIZE_CONVERT;
     uint8_t* const t_out = out;
     const size_t t_fs = out_fs;
-    if (tc && !t_fused) {
+    const bool crops_gather = crops && !t_fused;
+    const bool crops_direct = crops_gather && !nearest && !need_h && !need_v;   // no pass runs: the caller's frames are the bytes
+    if (crops_gather) {   // the bytes of the whole output, by the plan of the whole output
+        win = RsWindow{0, 0, d->out_w, d->out_h};
+        fused_ok = !nearest && need_h && need_v &&
+                   rs_fused_plan(d, rs_axis_view(H->host, 0, win.w), rs_axis_view(V->host, 0, win.h), frames, &fp);
+        fused = fused_ok && st->force != LANCZOS_RESIZE_TWO_PASS;
+    }
+    if (tc && !t_fused && !crops_direct) {
         const size_t bytes_fs = ((size_t)win.w * win.h * C + 3) & ~(size_t)3;
         rc = rs_scratch(st, &st->tensor_bytes, (size_t)frames * bytes_fs, stream, capturing, last_hip);
         if (rc != LANCZOS_OK) return rc;
@@ -631,7 +691,9 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     hipError_t e = hipSuccess;
     if (fused) {
         const RsFusedLaunch c{d, win, &fp, H, V, in, out, in_fs, out_fs, frames, tc, stream};
-        e = t_fused && tc->t.mapped ? (tc->t.elem == 2 ? rs_launch_fused<1, 2 + kRsMapped>(c) : rs_launch_fused<1, 4 + kRsMapped>(c))
+        e = t_fused && crops ? (tc->t.elem == 2 ? rs_launch_fused<1, 2 + kRsMapped + kRsCrops>(c)
+                                                : rs_launch_fused<1, 4 + kRsMapped + kRsCrops>(c))
+            : t_fused && tc->t.mapped ? (tc->t.elem == 2 ? rs_launch_fused<1, 2 + kRsMapped>(c) : rs_launch_fused<1, 4 + kRsMapped>(c))
             : t_fused ? (tc->t.elem == 2 ? rs_launch_fused<1, 2>(c) : rs_launch_fused<1, 4>(c))
             : f32   ? rs_launch_fused<4, 0>(c)
             : u16   ? rs_launch_fused<2, 0>(c)
@@ -642,7 +704,9 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
                               out_fs, stream);
         *last_kernel = LANCZOS_KERNEL_RESIZE_NEAREST;
     } else if (!need_h && !need_v) {   // Pillow returns a copy (also of RGBA: no premultiply round trip); a window crops it
-        if (win.whole(d))
+        if (crops_direct)
+            ;   // nothing to copy: the gather below reads the caller's frames
+        else if (win.whole(d))
             e = hipMemcpy2DAsync(out, out_fs, in, in_fs, in_frame, frames, hipMemcpyDeviceToDevice, stream);
         else
             e = rs_crop_launch(in + (size_t)win.y0 * in_pitch + (size_t)win.x0 * C * B, out, in_pitch, (size_t)win.w * C * B,
@@ -672,7 +736,13 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
         *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
     }
     if (tc) {
-        if (!t_fused && e == hipSuccess)
+        if (crops_direct)
+            e = rs_to_tensor_crops_launch(in, in_fs, in_pitch, d->in_w, d->in_h, t_out, t_fs, win_in.w, win_in.h, C, tc->t,
+                                          tc->d_origin, frames, stream);
+        else if (crops_gather && e == hipSuccess)
+            e = rs_to_tensor_crops_launch(out, out_fs, (size_t)win.w * C, win.w, win.h, t_out, t_fs, win_in.w, win_in.h, C, tc->t,
+                                          tc->d_origin, frames, stream);
+        else if (!t_fused && e == hipSuccess)
             e = rs_to_tensor_launch(out, out_fs, t_out, t_fs, win.w, win.h, C, tc->t, frames, stream);
         tc->route = t_fused ? LANCZOS_TENSOR_FUSED : LANCZOS_TENSOR_CONVERTED;
     }
@@ -754,12 +824,14 @@ struct RsStagedExtra {
     size_t table_at = 0, table_bytes = 0;
     const void* flips = nullptr;
     size_t flips_at = 0, flips_bytes = 0;
+    const void* origins = nullptr;   // of a lanczos_resize_crops request, behind the flips on a dword
+    size_t origins_at = 0, origins_bytes = 0;
     bool out_up = false;
 };
 template <class F>
 static int rs_staged_call(ResizeState* st, const void* in, size_t in_bytes, void* out, size_t out_bytes, const RsStagedExtra& x,
                           hipStream_t stream, int* last_hip, F&& call) {
-    const size_t in_need = std::max({in_bytes, x.table_at + x.table_bytes, x.flips_at + x.flips_bytes});
+    const size_t in_need = std::max({in_bytes, x.table_at + x.table_bytes, x.flips_at + x.flips_bytes, x.origins_at + x.origins_bytes});
     hipError_t e = rs_grow_stage(st, &st->stage_in, &st->stage_in_bytes, in_need, stream);
     if (e == hipSuccess) e = rs_grow_stage(st, &st->stage_out, &st->stage_out_bytes, out_bytes, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(st->stage_in, in, in_bytes, hipMemcpyHostToDevice, stream);
@@ -767,6 +839,8 @@ static int rs_staged_call(ResizeState* st, const void* in, size_t in_bytes, void
         e = hipMemcpyAsync((uint8_t*)st->stage_in + x.table_at, x.table, x.table_bytes, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess && x.flips)
         e = hipMemcpyAsync((uint8_t*)st->stage_in + x.flips_at, x.flips, x.flips_bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && x.origins)
+        e = hipMemcpyAsync((uint8_t*)st->stage_in + x.origins_at, x.origins, x.origins_bytes, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess && x.out_up) e = hipMemcpyAsync(st->stage_out, out, out_bytes, hipMemcpyHostToDevice, stream);
     int rc = LANCZOS_OK;
     if (e == hipSuccess) {
@@ -801,7 +875,7 @@ int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_res
 // frames go up before they come back, so that the elements of `out` the strides leave out keep what they held.
 int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
                        const lanczos_resize_window* win, const RsTensorOut& t, const void* in, void* out, int frames,
-                       hipStream_t stream, int* last_kernel, int* last_hip, int* route) {
+                       hipStream_t stream, int* last_kernel, int* last_hip, int* route, const int32_t* origins) {
     if (((uintptr_t)out & (uintptr_t)(t.elem - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
     RsWindow w;
     const int wrc = resize_window_resolve(d, win, &w);
@@ -813,10 +887,15 @@ int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanc
     RsStagedExtra x;
     x.table = t.d_lut, x.table_at = (in_bytes + 255) & ~(size_t)255, x.table_bytes = (size_t)t.out_channels * 256 * t.elem;
     if (t.d_flip) x.flips = t.d_flip, x.flips_at = x.table_at + x.table_bytes, x.flips_bytes = (size_t)frames;
+    if (origins) {
+        x.origins = origins, x.origins_bytes = (size_t)frames * 8;
+        x.origins_at = (x.table_at + x.table_bytes + x.flips_bytes + 3) & ~(size_t)3;
+    }
     x.out_up = true;
     return rs_staged_call(st, in, in_bytes, out, tc.extent_bytes * frames, x, stream, last_hip, [&] {
         tc.t.d_lut = (const uint8_t*)st->stage_in + x.table_at;
         if (t.d_flip) tc.t.d_flip = (const uint8_t*)st->stage_in + x.flips_at;
+        if (origins) tc.d_origin = (const int32_t*)((const uint8_t*)st->stage_in + x.origins_at);
         const int rc = resize_device(st, d, o, win, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip, &tc);
         *route = tc.route;
         return rc;

@@ -3,7 +3,8 @@
 // lanczos_resize.hip.  The kernels are written once for 8-bit, 16-bit (LANCZOS_RESIZE_U16) and float (LANCZOS_RESIZE_F32)
 // samples in lanczos_resize_fused.hpp; the fused instances are compiled by lanczos_resize.hip (8-bit), lanczos_resize_tensor.hip
 // (8-bit into float tensors), lanczos_resize_tensor16.hip (8-bit into bfloat16 / float16 tensors), lanczos_resize_tensor_view.hip
-// and lanczos_resize_tensor16_view.hip (the same two through a channel map and flips), lanczos_resize16.hip and
+// and lanczos_resize_tensor16_view.hip (the same two through a channel map and flips), lanczos_resize_tensor_crops.hip and
+// lanczos_resize_tensor16_crops.hip (those with a crop origin per frame), lanczos_resize16.hip and
 // lanczos_resize32.hip.  The filter of a request (LANCZOS_RESIZE_FILTER)
 // only changes the tables; LANCZOS_FILTER_NEAREST has index tables and a kernel of its own (lanczos_resize_nearest.hip).
 #pragma once
@@ -112,8 +113,18 @@ struct RsFusedPlan {
     size_t lds = 0;
 };
 bool rs_fused_plan(const lanczos_resize_desc* d, const RsAxisView& H, const RsAxisView& V, int frames, RsFusedPlan* fp);
+// The plan of a w x h window whose origin is only known when the kernel runs (lanczos_resize_crops).  H and V are the full
+// axes.  K, strips, rows_per_chunk and chunks depend on the window's size alone; stage_dw is the largest over every x origin
+// and ring_rows the largest over every y origin of what rs_fused_plan computes for the window there; stage_rows and lds follow
+// from those by its rule.  false where that does not fit, even if the window at some origins would
+bool rs_fused_plan_crops(const lanczos_resize_desc* d, const RsAxisView& H, const RsAxisView& V, int w, int h, int frames,
+                         RsFusedPlan* fp);
+// crops: the plan of a request with a crop origin per frame (win is then NULL; mid_row0 / mid_rows are the whole output's,
+// which the converted route resizes)
 int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win, int frames,
-                     lanczos_resize_plan_ex* out);
+                     lanczos_resize_plan_ex* out, const lanczos_resize_crops* crops = nullptr);
+// a crop size per request: 1..out_w x 1..out_h, origins given, reserved words 0
+int resize_crops_validate(const lanczos_resize_desc* d, const lanczos_resize_crops* c);
 
 // One axis shape on the device: first | count | coeffs in one block (int32 coefficients, or double ones for 16-bit samples:
 // the two int32 arrays in front of them keep those 8-byte aligned).
@@ -182,6 +193,9 @@ struct RsTensorCall {
     RsTensorOut t;             // validated (tensor_validate)
     size_t extent_bytes = 0;   // of one element frame: from its first element to its last
     int route = 0;
+    // lanczos_resize_crops: a pair (x0, y0) per frame, read and clamped when the kernels run.  The window of the call is then
+    // (0, 0, w, h), the size of every frame's crop
+    const int32_t* d_origin = nullptr;
 };
 // t NULL: the caller passed no struct; reserved: its four words.  The frame the strides describe is the window's (win NULL:
 // the whole output).  On LANCZOS_OK t->out_channels, src_channel and mapped are resolved
@@ -204,6 +218,11 @@ bool tensor_lut_convert16(const float* in, int n, int format, uint16_t* out);
 // (t.mapped: through the channel map and the frames' flips)
 hipError_t rs_to_tensor_launch(const uint8_t* src, size_t src_fs, uint8_t* out, size_t out_fs, int w, int h, int channels,
                                const RsTensorOut& t, int frames, hipStream_t stream);
+// k_rs_to_tensor_crops (lanczos_resize_tensor_crops.hip): frame f's w x h window at its clamped origin of interleaved byte frames
+// of src_w x src_h pixels (rows src_pitch bytes apart, any alignment) -> strided elements through the map, flips and table
+hipError_t rs_to_tensor_crops_launch(const uint8_t* src, size_t src_fs, size_t src_pitch, int src_w, int src_h, uint8_t* out,
+                                     size_t out_fs, int w, int h, int channels, const RsTensorOut& t, const int32_t* d_origin,
+                                     int frames, hipStream_t stream);
 
 // The entry points (ctx->mu held, device set).  *last_kernel / *last_hip as in lanczos_ctx.  tc: a tensor request (NULL: bytes).
 // win: the window of the output that is computed and stored, tightly packed (NULL: the whole output)
@@ -211,10 +230,10 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_r
                   const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream,
                   int* last_kernel, int* last_hip, RsTensorCall* tc = nullptr);
 // host table (t.d_lut), host flip array (t.d_flip, or NULL) and host buffers, element frames tensor_extent_bytes apart;
-// synchronous
+// synchronous.  origins: NULL, or the host array of a lanczos_resize_crops request (win is then (0, 0, w, h))
 int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
                        const lanczos_resize_window* win, const RsTensorOut& t, const void* in, void* out, int frames,
-                       hipStream_t stream, int* last_kernel, int* last_hip, int* route);
+                       hipStream_t stream, int* last_kernel, int* last_hip, int* route, const int32_t* origins = nullptr);
 int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
                 const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip);
 
@@ -246,6 +265,8 @@ struct RsFusedLaunch {
 // TENSOR: bytes of a stored table element, 0 where the samples themselves are stored; + kRsMapped: through the channel map and
 // the flips of the request (RsTensorOut::mapped)
 constexpr int kRsMapped = 8;
+// + kRsCrops: a window origin per frame, read when the kernel runs (RsTensorCall::d_origin); the tables are the full axes'
+constexpr int kRsCrops = 16;
 template <int BPS, int TENSOR>
 hipError_t rs_launch_fused(const RsFusedLaunch& c);
 

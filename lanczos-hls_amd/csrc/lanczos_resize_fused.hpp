@@ -9,7 +9,8 @@
 //                   lanczos_resize_tensor.hip (8-bit, floats out through a table: TENSOR = 4), lanczos_resize_tensor16.hip
 //                   (8-bit, 16-bit elements out through a table: TENSOR = 2), lanczos_resize_tensor_view.hip and
 //                   lanczos_resize_tensor16_view.hip (the same two through a channel map and flips: TENSOR + kRsMapped),
-//                   lanczos_resize16.hip and lanczos_resize32.hip.
+//                   lanczos_resize_tensor_crops.hip and lanczos_resize_tensor16_crops.hip (those with a crop origin per frame:
+//                   TENSOR + kRsMapped + kRsCrops), lanczos_resize16.hip and lanczos_resize32.hip.
 #pragma once
 #include "lanczos_alpha.hpp"
 #include "lanczos_resize.hpp"
@@ -165,10 +166,18 @@ struct RsFusedTensorMap : RsFusedTensor {
     int flip;                // bit 0: mirror x, bit 1: mirror y
     const uint8_t* d_flip;   // NULL, or one byte per frame of the launch, XORed with flip; read when the kernel runs
 };
+// ... + kRsCrops: the tables are those of the full axes and every frame has a window origin of its own.  Again a struct of its
+// own, for the reason above
+struct RsFusedTensorCrops : RsFusedTensorMap {
+    const int32_t* d_origin;   // a pair (x0, y0) per frame of the launch, in output pixels of the full request; read when the
+                               // kernel runs and clamped to [0, max_x0] x [0, max_y0]
+    int max_x0, max_y0;        // the full output's size less the window's
+};
 // the argument of k_rs_fused<..., TENSOR> for coefficients KT
 template <int TENSOR, class KT>
-using RsFusedArgs = std::conditional_t<(TENSOR & kRsMapped) != 0, RsFusedTensorMap,
-                                       std::conditional_t<TENSOR != 0, RsFusedTensor, RsFused<KT>>>;
+using RsFusedArgs = std::conditional_t<
+    (TENSOR & kRsCrops) != 0, RsFusedTensorCrops,
+    std::conditional_t<(TENSOR & kRsMapped) != 0, RsFusedTensorMap, std::conditional_t<TENSOR != 0, RsFusedTensor, RsFused<KT>>>>;
 
 template <int C, int BPS>
 struct RsStrip {
@@ -204,12 +213,20 @@ struct RsStrip {
 // were): the lane's channel c becomes dst[c], four byte fields of one scalar, and a channel no output names stores nothing.  A
 // flip negates a stride and moves the base to the matching corner of the frame -- both computed once per workgroup from one
 // uniform byte load -- so every offset stays inside [0, extent) and the buffer resource is the same.
+//
+// TENSOR + kRsMapped + kRsCrops (lanczos_resize_crops; instances of their own again): out_w x out_h is the crop every frame
+// stores and the tables are the full axes'.  A workgroup loads its frame's origin with two uniform loads, clamps it so that the
+// crop lies inside the full output -- device memory cannot be validated, and the tables end there -- and moves its six table
+// pointers by it: from there on it is the kernel of the window at that origin.  The plan is the largest over every origin
+// (rs_fused_plan_crops), so staging rows and ring hold whichever the frame has.
 template <class S, int C, int K, bool ALPHA = false, int TENSOR = 0>
 __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
     RsFusedArgs<TENSOR, typename S::coeff_t> g) {
-    constexpr int EB = TENSOR & ~kRsMapped;   // bytes of a stored element
+    constexpr int EB = TENSOR & ~(kRsMapped | kRsCrops);   // bytes of a stored element
     constexpr bool MAPPED = (TENSOR & kRsMapped) != 0;
+    constexpr bool CROPS = (TENSOR & kRsCrops) != 0;
     static_assert((EB == 0 && !MAPPED) || EB == 2 || EB == 4, "bytes, 16-bit elements or floats out");
+    static_assert(!CROPS || MAPPED, "a crop origin per frame comes with the mapped epilogue");
     static_assert(!ALPHA || C == 4, "alpha is the fourth of four channels");
     static_assert((!ALPHA && !TENSOR) || S::BPS == 1, "alpha and tensor output are 8-bit");
     using acc_t = typename S::acc_t;
@@ -225,6 +242,13 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
     uint32_t* stage = lds + g.ring_rows * RDW;   // [stage_rows][stage_dw]
 
     const int tid = threadIdx.x;
+    if constexpr (CROPS) {   // the frame's origin, clamped: the tables from there on are the window's
+        const int ox = __builtin_amdgcn_readfirstlane(g.d_origin[2 * blockIdx.y]);
+        const int oy = __builtin_amdgcn_readfirstlane(g.d_origin[2 * blockIdx.y + 1]);
+        const int cx = min(max(ox, 0), g.max_x0), cy = min(max(oy, 0), g.max_y0);
+        g.hf += cx, g.hc += cx, g.hk += (size_t)cx * g.hks;
+        g.vf += cy, g.vc += cy, g.vk += (size_t)cy * g.vks;
+    }
     const int strip = blockIdx.x % g.strips, chunk = blockIdx.x / g.strips;
     const int x0 = strip * SW;
     const int sw = min(SW, g.out_w - x0);
@@ -479,11 +503,13 @@ hipError_t rs_launch_fused(const RsFusedLaunch& c) {
         g.extent_bytes = (unsigned)c.tc->extent_bytes;
     }
     if constexpr ((TENSOR & kRsMapped) != 0) g.dst = c.tc->t.dst_of_src(), g.flip = c.tc->t.flip & 3;
+    if constexpr ((TENSOR & kRsCrops) != 0) g.max_x0 = c.d->out_w - c.win.w, g.max_y0 = c.d->out_h - c.win.h;
     for (int f0 = 0; f0 < c.frames; f0 += 65535) {
         const int nf = std::min(65535, c.frames - f0);
         g.in = c.in + (size_t)f0 * c.in_fs;
         g.out = c.out + (size_t)f0 * c.out_fs;
         if constexpr ((TENSOR & kRsMapped) != 0) g.d_flip = c.tc->t.d_flip ? c.tc->t.d_flip + f0 : nullptr;   // a byte per frame
+        if constexpr ((TENSOR & kRsCrops) != 0) g.d_origin = c.tc->d_origin + 2 * (size_t)f0;                  // a pair per frame
         const dim3 grid(fp.strips * fp.chunks, nf);
         bool launched = false;
         rs_dispatch_instance(c.d->channels, fp.K, alpha, [&](auto ch, auto k, auto a) {
@@ -505,6 +531,8 @@ extern template hipError_t rs_launch_fused<1, 4>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<1, 2>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<1, 4 + kRsMapped>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<1, 2 + kRsMapped>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<1, 4 + kRsMapped + kRsCrops>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<1, 2 + kRsMapped + kRsCrops>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<2, 0>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<4, 0>(const RsFusedLaunch&);
 

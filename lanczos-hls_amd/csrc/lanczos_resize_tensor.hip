@@ -5,7 +5,9 @@
 //   fused      the TENSOR instances of k_rs_fused (lanczos_resize_fused.hpp): the vertical pass stores the elements itself.  A
 //              tensor request runs them exactly where the byte request runs the fused kernel, on the same plan.  Those that
 //              store floats are instantiated here, those that store 16-bit elements in lanczos_resize_tensor16.hip, those of
-//              a view with a map or flips in lanczos_resize_tensor_view.hip and lanczos_resize_tensor16_view.hip.
+//              a view with a map or flips in lanczos_resize_tensor_view.hip and lanczos_resize_tensor16_view.hip, those of a
+//              request with a crop origin per frame in lanczos_resize_tensor_crops.hip and lanczos_resize_tensor16_crops.hip
+//              (with their converter, k_rs_to_tensor_crops).
 //   converted  k_rs_to_tensor behind any other resize (two passes, one pass, nearest, the plain copy, an element frame of 2^31
 //              bytes or more): the bytes go to context scratch, tightly packed, and one streaming launch turns them into
 //              elements (k_rs_to_tensor<C, uint16_t> is the k_rs_to_tensor16 of the documents; k_rs_to_tensor_map is the

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """resize_speed.py -- speed of the resize-to-any-size entry (lanczos_resize_device) on one MI355X.
 
-    python scripts/resize_speed.py [--steps K] [--warmup W] [--rounds R] [--only W1,W3,A1,U1,F1,WIN1] [--routes rgbx,three_step]
+    python scripts/resize_speed.py [--steps K] [--warmup W] [--rounds R] [--only W1,W3,A1,U1,F1,WIN1,RC1] [--routes rgbx,three_step]
                                    [--pillow] [--parent-lib PATH]
 
 One JSON line per (workload, path).  Discipline as bench.py's: the frames are resident in HBM and the steps cycle through
@@ -85,6 +85,24 @@ window center_window(341, 256, 224, 224), alpha dropped, float32; VWh: the same 
                   .contiguous() on the same stream: what the view replaces
   tensor          the tensor call without a map alone
 Frame 0 of view, view_converted and tensor_torch are compared bit for bit before timing; a last line gives the ratios.
+
+RC1, RC1h and RCC are crops workloads (a tensor view with a crop origin per frame, lanczos_resize_tensor_crops_device; --only
+RC1,RC1h,RCC; a build with the entry): Resize -> RandomCrop(224) -> RandomHorizontalFlip -> ToTensor -> Normalize in one call, to
+normalised CHW.  RC1: 256 frames of 500x375 RGB8 -> 341x256, a seeded random 224x224 origin per frame, every other frame mirrored,
+float32; RC1h: the same to bfloat16.  RCC: 256 frames of 256x256 kept at size (no pass runs: the gather reads the caller's
+frames), random 224x224 crops, float32.  Routes:
+  crops            the call under RESIZE_AUTO
+  crops_converted  the call under RESIZE_CONVERT: the byte resize of the whole output into context scratch, then
+                   k_rs_to_tensor_crops (RCC: the same launch as `crops`)
+  full_gather      what the call replaces: the view call on the FULL output, then torch's gather of every frame's window with the
+                   mirror folded into its column indices (index tensors built outside the timed region).  The gather is the
+                   fastest of four that were timed on RC1's tensors (float32 / bfloat16 µs): rows by index_select then columns by
+                   torch.gather 299 / 250, torch.gather over rows then over columns with expanded indices 312 / 235 -- the first
+                   is used for float32, the second for bfloat16 --, one advanced-indexing expression t[f, c, y, x] 598 / 578, a
+                   loop of 256 slice copies 2 818 / 2 784
+  window_center    the view call with the centred uniform window and the same flips: the same pixel count on the existing
+                   kernels, the floor
+Frame 0 of crops, crops_converted and full_gather are compared bit for bit before timing; a last line gives the ratios.
 
 --pillow adds Pillow's single-core time of one frame of each workload (if Pillow imports; else "not available"); for U1 and
 U4 that is the time of one I;16 plane (a frame has three), for F1 and F4 that of one F plane.
@@ -670,6 +688,92 @@ def run_view(name, args, ctx, torch):
     torch.cuda.empty_cache()
 
 
+CROPS_WORKLOADS = {   # name: (in_w, in_h, out_w, out_h, channels, frames, crop (w, h), bfloat16)
+    "RC1": (500, 375, 341, 256, 3, 256, (224, 224), False),
+    "RC1h": (500, 375, 341, 256, 3, 256, (224, 224), True),
+    "RCC": (256, 256, 256, 256, 3, 256, (224, 224), False),
+}
+
+
+def run_crops(name, args, ctx, torch):
+    """A crop origin per frame against the view call on the full output plus torch's gather, against the centred uniform window
+    (the floor) and against its own converted route."""
+    iw, ih, ow, oh, c, f, (w, h), half = CROPS_WORKLOADS[name]
+    in_fb, full_fb, crop_fb = iw * ih * c, ow * oh * c, w * h * c
+    sets = max(2, -(-2 * 256 * 2 ** 20 // (f * in_fb)) + 1)
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    dt = torch.bfloat16 if half else torch.float32
+    dtype = "bfloat16" if half else "float32"
+    xs = [torch.randint(0, 256, (f * in_fb,), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(sets)]
+    ys = [torch.empty(f * crop_fb, dtype=dt, device="cuda") for _ in range(sets)]
+    fulls = [torch.empty(f * full_fb, dtype=dt, device="cuda") for _ in range(sets)]
+    d = L.resize_desc(iw, ih, ow, oh, c)
+    lut = L.normalize_lut(c, IMAGENET_MEAN[:c], IMAGENET_STD[:c], dtype=dtype)
+    d_lut = torch.from_numpy(lut.view(np.int16) if half else lut).cuda()
+    rng = np.random.default_rng(11)
+    org = np.stack([rng.integers(0, ow - w + 1, f), rng.integers(0, oh - h + 1, f)], axis=1).astype(np.int32)
+    fl = np.array([k & 1 for k in range(f)], dtype=np.uint8)
+    d_org, d_flip = torch.from_numpy(org).cuda(), torch.from_numpy(fl).cuda()
+    # the gather's index tensors: the rows of every frame and its (mirrored where the frame is) columns
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    cols = org[:, :1] + np.where(fl[:, None] == 1, np.arange(w)[::-1][None], np.arange(w)[None])
+    rows = org[:, 1:] + np.arange(h)[None]
+    g_y, g_x = dev(rows).view(f, 1, h, 1).expand(f, c, h, ow), dev(cols).view(f, 1, 1, w).expand(f, c, h, w)
+    row_of = dev((np.arange(f)[:, None, None] * c + np.arange(c)[None, :, None]) * oh + rows[:, None, :]).view(-1)
+    g_x2 = g_x.reshape(f * c * h, w)
+    win = L.resize_window(d, L.center_window(ow, oh, w, h))
+    st_crop, st_full = L.tensor_strides("chw", w, h, c), L.tensor_strides("chw", ow, oh, c)
+    s = torch.cuda.current_stream().cuda_stream
+    bits = (lambda y: y.view(torch.int16)) if half else (lambda y: y.view(torch.int32))
+    src = tuple(range(c))
+    seen = {}
+
+    def crops(path):
+        def step(i):
+            ctx.resize_force(path)
+            ctx.resize_tensor_device(d, xs[i % sets].data_ptr(), ys[i % sets].data_ptr(), f, d_lut.data_ptr(), st_crop, stream=s,
+                                     dtype=dtype, channels_out=src, d_flip=d_flip.data_ptr(), crop=(w, h), d_origin=d_org.data_ptr())
+            seen[path] = ctx.last_tensor_route()
+            return bits(ys[i % sets][:crop_fb])
+        return step
+
+    def full_gather(i):
+        ctx.resize_force(L.RESIZE_AUTO)
+        ctx.resize_tensor_device(d, xs[i % sets].data_ptr(), fulls[i % sets].data_ptr(), f, d_lut.data_ptr(), st_full, stream=s,
+                                 dtype=dtype, channels_out=src)
+        if half:
+            t = fulls[i % sets].view(f, c, oh, ow).gather(2, g_y).gather(3, g_x)
+        else:
+            t = fulls[i % sets].view(f * c * oh, ow).index_select(0, row_of).gather(1, g_x2)
+        return bits(t.view(-1)[:crop_fb])
+
+    def window_center(i):
+        ctx.resize_force(L.RESIZE_AUTO)
+        ctx.resize_tensor_device(d, xs[i % sets].data_ptr(), ys[i % sets].data_ptr(), f, d_lut.data_ptr(), st_crop, stream=s,
+                                 dtype=dtype, window=win, channels_out=src, d_flip=d_flip.data_ptr())
+        return bits(ys[i % sets][:crop_fb])
+
+    routes = {"crops": crops(L.RESIZE_AUTO), "crops_converted": crops(L.RESIZE_CONVERT), "full_gather": full_gather,
+              "window_center": window_center}
+    e = 2 if half else 4
+    inb = {rn: f * in_fb for rn in routes}
+    outb = {rn: e * f * crop_fb for rn in routes}
+    us = run_routes(name, f"{iw}x{ih}->{ow}x{oh} C{c} random {w}x{h} crops, flips 0,1,0,1.. chw {dtype}", f, routes, inb, outb,
+                    args, ctx, torch, check=(("crops", "crops_converted"), ("crops", "full_gather")))
+    ctx.resize_force(L.RESIZE_AUTO)
+    plan = L.resize_crops_plan_host(d, (w, h), f).inner
+    if seen[L.RESIZE_CONVERT] != L.TENSOR_CONVERTED or seen[L.RESIZE_AUTO] != (L.TENSOR_FUSED if plan.fused else L.TENSOR_CONVERTED):
+        raise SystemExit(f"{name}: routes {seen}")
+    print(json.dumps({"workload": name, "crops_over_full_gather": round(us["crops"] / us["full_gather"], 3),
+                      "crops_over_window_center": round(us["crops"] / us["window_center"], 3),
+                      "crops_over_crops_converted": round(us["crops"] / us["crops_converted"], 3),
+                      "auto_route": seen[L.RESIZE_AUTO],
+                      "plan": {k: getattr(plan, k) for k in ("fused", "K", "strips", "chunks", "ring_rows", "stage_rows", "stage_dw",
+                                                             "lds_bytes")}, "measured": True}), flush=True)
+    del xs, ys, fulls
+    torch.cuda.empty_cache()
+
+
 def run_gap(name, args, ctx, torch):
     iw, ih, ow, oh, c, a, f = WORKLOADS["W5"]
     in_fb, out_fb = iw * ih * c, ow * oh * c
@@ -765,6 +869,8 @@ def main():
     for name in args.only.split(","):
         if name in WINDOW_WORKLOADS:
             run_window(name, args, ctx, torch, parent)
+        elif name in CROPS_WORKLOADS:
+            run_crops(name, args, ctx, torch)
         elif name in VIEW_WORKLOADS:
             run_view(name, args, ctx, torch)
         elif name in TENSOR_WORKLOADS:
