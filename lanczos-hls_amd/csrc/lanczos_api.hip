@@ -573,6 +573,7 @@ int lanczos_destroy(lanczos_ctx* ctx) {
 
 int lanczos_timing_enable(lanczos_ctx* ctx, int on) {
     if (!ctx) return LANCZOS_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(ctx->mu);
     ctx->timing = on != 0;
     return LANCZOS_OK;
 }
@@ -635,6 +636,7 @@ int lanczos_last_march_table(const lanczos_ctx* ctx, lanczos_march_table_info* i
 
 int lanczos_force_kernel(lanczos_ctx* ctx, int family) {
     if (!ctx || family < LANCZOS_KERNEL_NONE || family > LANCZOS_KERNEL_FAST) return LANCZOS_ERR_BAD_ARG;  // (_HLS follows the mode)
+    std::lock_guard<std::mutex> lock(ctx->mu);
     ctx->force = family;
     return LANCZOS_OK;
 }
@@ -1026,12 +1028,19 @@ int lanczos_resample_host(lanczos_ctx* ctx, const lanczos_desc* d, const void* i
 }
 
 // ---- planar <-> interleaved (full_TB.h:127-138, 146-165) --------------------------------------------------------
-static int layout_call(lanczos_ctx* ctx, bool to_interleaved, const void* src, void* dst, int w, int h, int channels,
-                       int bytes_per_sample, int frames, void* stream) {
-    if (!ctx || !src || !dst || w <= 0 || h <= 0 || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+static int layout_check(const void* src, const void* dst, int w, int h, int channels, int bytes_per_sample, int frames) {
+    if (!src || !dst || w <= 0 || h <= 0 || frames <= 0) return LANCZOS_ERR_BAD_ARG;
     if ((channels != 1 && channels != 3 && channels != 4) || (bytes_per_sample != 1 && bytes_per_sample != 2))
         return LANCZOS_ERR_BAD_ARG;
     if (h > 65535 || frames > 65535) return LANCZOS_ERR_UNSUPPORTED;
+    return LANCZOS_OK;
+}
+
+static int layout_call(lanczos_ctx* ctx, bool to_interleaved, const void* src, void* dst, int w, int h, int channels,
+                       int bytes_per_sample, int frames, void* stream) {
+    if (!ctx) return LANCZOS_ERR_BAD_ARG;
+    const int rc = layout_check(src, dst, w, h, channels, bytes_per_sample, frames);
+    if (rc != LANCZOS_OK) return rc;
     std::lock_guard<std::mutex> lock(ctx->mu);
     LZ_HIP(ctx, hipSetDevice(ctx->device));
     route_begin(ctx);
@@ -1051,51 +1060,52 @@ int lanczos_interleaved_to_planar_device(lanczos_ctx* ctx, const void* d_interle
 
 // img_in[C][IN_H][IN_W] -> img_out[C][OUT_H][OUT_W], the arrays lanczos_expected() works on (full_TB.h:20-21,79-96).
 // Whole frames only.  The interleaved scratch frames belong to the context: calls on one context must follow each
-// other in stream order (one stream at a time).
+// other in stream order (one stream at a time).  The lock is held from the growth of the scratch frames to the last of the
+// three launches: a second thread's call on the same context and stream can neither replace the frames nor write its own
+// pixels into them between this call's launches.
 int lanczos_resample_planar_device(lanczos_ctx* ctx, const lanczos_desc* d, const void* d_in_planar, void* d_out_planar,
                                    int frames, void* stream) {
     if (!ctx || !d_in_planar || !d_out_planar || frames <= 0) return LANCZOS_ERR_BAD_ARG;
     int rc = lz::validate(d);
     if (rc != LANCZOS_OK) return rc;
     if (d->out_rows != 0 && !(d->out_row0 == 0 && d->out_rows == d->out_h)) return LANCZOS_ERR_UNSUPPORTED;
-    const size_t in_bytes = lanczos_in_frame_bytes(d) * frames, out_bytes = lanczos_out_frame_bytes(d) * frames;
-    {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        LZ_HIP(ctx, hipSetDevice(ctx->device));
-        if (ctx->planar_in_bytes < in_bytes) {
-            if (ctx->planar_in) (void)hipFree(ctx->planar_in);
-            ctx->planar_in = nullptr;
-            ctx->planar_in_bytes = 0;
-            LZ_HIP(ctx, hipMalloc(&ctx->planar_in, in_bytes));
-            ctx->planar_in_bytes = in_bytes;
-        }
-        if (ctx->planar_out_bytes < out_bytes) {
-            if (ctx->planar_out) (void)hipFree(ctx->planar_out);
-            ctx->planar_out = nullptr;
-            ctx->planar_out_bytes = 0;
-            LZ_HIP(ctx, hipMalloc(&ctx->planar_out, out_bytes));
-            ctx->planar_out_bytes = out_bytes;
-        }
-    }
-    rc = lanczos_planar_to_interleaved_device(ctx, d_in_planar, ctx->planar_in, d->in_w, d->in_h, d->channels,
-                                              d->bytes_per_sample, frames, stream);
+    rc = layout_check(d_in_planar, d_out_planar, d->in_w, d->in_h, d->channels, d->bytes_per_sample, frames);
+    if (rc == LANCZOS_OK) rc = layout_check(d_in_planar, d_out_planar, d->out_w, d->out_h, d->channels, d->bytes_per_sample, frames);
     if (rc != LANCZOS_OK) return rc;
+    const size_t in_bytes = lanczos_in_frame_bytes(d) * frames, out_bytes = lanczos_out_frame_bytes(d) * frames;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    route_begin(ctx);
+    if (ctx->planar_in_bytes < in_bytes) {
+        if (ctx->planar_in) (void)hipFree(ctx->planar_in);
+        ctx->planar_in = nullptr;
+        ctx->planar_in_bytes = 0;
+        LZ_HIP(ctx, hipMalloc(&ctx->planar_in, in_bytes));
+        ctx->planar_in_bytes = in_bytes;
+    }
+    if (ctx->planar_out_bytes < out_bytes) {
+        if (ctx->planar_out) (void)hipFree(ctx->planar_out);
+        ctx->planar_out = nullptr;
+        ctx->planar_out_bytes = 0;
+        LZ_HIP(ctx, hipMalloc(&ctx->planar_out, out_bytes));
+        ctx->planar_out_bytes = out_bytes;
+    }
+    LZ_HIP(ctx, lz::layout_launch(true, d_in_planar, ctx->planar_in, d->in_w, d->in_h, d->channels, d->bytes_per_sample, frames,
+                                  (hipStream_t)stream));
     lanczos_desc whole = *d;
     whole.out_row0 = 0;
     whole.out_rows = 0;
-    rc = lanczos_resample_device(ctx, &whole, ctx->planar_in, ctx->planar_out, frames, 0, 0, stream);
+    rc = resample_device_locked(ctx, &whole, ctx->planar_in, ctx->planar_out, frames, 0, 0, stream);
     if (rc != LANCZOS_OK) return rc;
-    const int route = ctx->last_route;   // (the layout call behind it reports none: the planar call reports its resample)
-    long long table_key[8];
-    memcpy(table_key, ctx->wg_tabs.last_key, sizeof(table_key));
-    const bool table_valid = ctx->wg_tabs.last_valid;
-    rc = lanczos_interleaved_to_planar_device(ctx, ctx->planar_out, d_out_planar, d->out_w, d->out_h, d->channels,
-                                              d->bytes_per_sample, frames, stream);
-    if (rc == LANCZOS_OK) {
-        ctx->last_route = route;
-        if (table_valid) ctx->wg_tabs.note_last(table_key);
+    // (the report of the call is that of its resample: the layout launches add nothing to it)
+    const hipError_t e = lz::layout_launch(false, ctx->planar_out, d_out_planar, d->out_w, d->out_h, d->channels, d->bytes_per_sample,
+                                           frames, (hipStream_t)stream);
+    if (e != hipSuccess) {
+        route_begin(ctx);
+        ctx->last_hip = (int)e;
+        return LANCZOS_ERR_HIP;
     }
-    return rc;
+    return LANCZOS_OK;
 }
 
 // ---- resize to any size (Pillow's contract; lanczos_resize.hip) ------------------------------------------------------
