@@ -299,7 +299,8 @@ typedef struct lanczos_resize_desc {
 #define LANCZOS_RESIZE_FUSED 1     /* LANCZOS_ERR_UNSUPPORTED where the fused kernel cannot run the shape, and for a tensor
                                       request whose float frame spans 2^31 bytes or more */
 #define LANCZOS_RESIZE_TWO_PASS 2
-#define LANCZOS_RESIZE_CONVERT 3   /* the resize as AUTO plans it; a tensor request takes the converted route (the A/B of the
+#define LANCZOS_RESIZE_CONVERT 3   /* the resize as AUTO plans it; a source layout takes LANCZOS_SOURCE_PACKED (the A/B of the direct
+                                    * staging) and a tensor request takes the converted route (the A/B of the
                                       fused tensor epilogue); a byte request runs as under AUTO */
 
 /* host only, no GPU needed */
@@ -668,6 +669,75 @@ int lanczos_resize_tensor_crops_device(lanczos_ctx* ctx, const lanczos_resize_de
 int lanczos_resize_tensor_crops_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                      const lanczos_resize_crops* crops, const lanczos_tensor_view* v, const void* in, void* out,
                                      int frames);
+
+/* ---- resize from planar (CHW) and row-pitched sources without a repack ----
+ * Every entry above reads `channels` interleaved samples with tightly packed rows.  A source layout beside the descriptor says
+ * where the samples lie instead: sample (y, x, c) of frame f is at byte
+ *   f * in_frame_stride + c * chan_stride + y * row_stride + x * pix_stride
+ * of d_in (B = bytes per sample, C = channels).  Two shapes are accepted:
+ *   interleaved, pitched   pix_stride = C * B, chan_stride = B, row_stride >= in_w * C * B and a multiple of B.  Every sample
+ *                          type (8-bit, LANCZOS_RESIZE_ALPHA, _U16, _F32); a float source keeps its multiple-of-4 rule for base
+ *                          and strides, a 16-bit one its multiple-of-2 rule.
+ *   planar                 pix_stride = 1, row_stride >= in_w, chan_stride >= (in_h - 1) * row_stride + in_w.  8-bit samples
+ *                          only, LANCZOS_RESIZE_ALPHA included; base and strides may have any residue.  One channel, planar,
+ *                          is the interleaved shape.  A planar _U16 or _F32 source is LANCZOS_ERR_UNSUPPORTED: those types
+ *                          resize every channel as an independent plane, so such a source already is frames * C one-channel
+ *                          frames (channels = 1, in_frame_stride = chan_stride) for the entries above.
+ * Everything else, and a non-zero reserved word, is LANCZOS_ERR_BAD_ARG: no negative strides, no layout per frame.
+ * in_frame_stride = 0 is the layout's own extent: in_h * row_stride (interleaved), channels * chan_stride (planar); a non-zero
+ * stride below that extent is LANCZOS_ERR_BAD_ARG.
+ * THE CONTRACT: the result is what the entry without a source stores for the same descriptor, options, window, view and crops
+ * when it is given the tightly packed interleaved copy of the source -- byte for byte, word for word, nothing else written.
+ * The same tables and arithmetic run; only the place a source byte is fetched from changes.  No byte outside [frame base
+ * rounded down to a dword, frame end rounded up to a dword) is read, and bytes the layout does not name never reach a result.
+ * The frame END is: planar, the last byte the layout names (the padding behind the last row of the last plane is never read);
+ * interleaved, base + in_h * row_stride -- the fused kernel's range check covers whole pitched rows, so EVERY frame, the last
+ * one included, must hold its full in_h * row_stride bytes.  A region that starts x0 pixels into the rows of a larger surface and
+ * ends in the surface's last row passes the surface's end by x0 * C * B bytes: the allocation has to cover them (they never
+ * reach a result).
+ * Routes (lanczos_last_source_route): LANCZOS_SOURCE_DIRECT, the resize kernel reads the caller's memory -- the fused kernel,
+ * for a pitched interleaved source of any sample type (with a window, a view or crops) and for a planar 8-bit source of 3 or 4
+ * channels (bytes out or a tensor; planar instances of their own, lanczos_resize_source*.hip); a tightly packed interleaved
+ * source is DIRECT on every route, being the call without a source.  LANCZOS_SOURCE_PACKED, everything else: the two-pass
+ * kernels, one pass, LANCZOS_FILTER_NEAREST, the copies, reducing_gap, oversize frames, a planar source with crops (and a
+ * LANCZOS_RESIZE_ALPHA one whose row pitch is no multiple of 4 with crops), forced LANCZOS_RESIZE_TWO_PASS, and any source that
+ * is not tightly packed under forced LANCZOS_RESIZE_CONVERT (the A/B of the direct staging): one streaming
+ * launch (k_rs_pack_source) gathers the frames tightly packed into context scratch and the request runs on that block.  The
+ * block lives as the other scratch of a context does: one stream at a time per context, and a captured launch pins it. */
+typedef struct lanczos_resize_source {
+    int64_t row_stride, chan_stride;   /* bytes */
+    int32_t pix_stride;                /* bytes */
+    int32_t reserved[3];               /* must be 0 */
+} lanczos_resize_source;
+#define LANCZOS_SOURCE_INTERLEAVED 0
+#define LANCZOS_SOURCE_PLANAR 1
+#define LANCZOS_SOURCE_DIRECT 1
+#define LANCZOS_SOURCE_PACKED 2
+/* Host only: the tight layout of that kind for d's source frame. */
+int lanczos_resize_source_init(lanczos_resize_source* src, const lanczos_resize_desc* d, int layout);
+/* Host only.  NULL validates as the call without a source does. */
+int lanczos_resize_source_validate(const lanczos_resize_desc* d, const lanczos_resize_source* src);
+/* lanczos_resize_window_device with a source layout (src NULL: exactly that call). */
+int lanczos_resize_source_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                 const lanczos_resize_window* win, const lanczos_resize_source* src, const void* d_in,
+                                 void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream);
+/* lanczos_resize_tensor_view_device (crops NULL) or lanczos_resize_tensor_crops_device (win NULL) with a source layout; win
+ * together with crops is LANCZOS_ERR_BAD_ARG.  src NULL: exactly those calls. */
+int lanczos_resize_tensor_source_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                        const lanczos_resize_window* win, const lanczos_resize_crops* crops,
+                                        const lanczos_resize_source* src, const lanczos_tensor_view* v, const void* d_in,
+                                        void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream);
+/* Host buffers: `frames` frames back to back in the described layout (the layout's own extent apart); synchronous.  Otherwise as
+ * lanczos_resize_window_host and lanczos_resize_tensor_view_host / lanczos_resize_tensor_crops_host. */
+int lanczos_resize_source_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                               const lanczos_resize_window* win, const lanczos_resize_source* src, const void* in, void* out,
+                               int frames);
+int lanczos_resize_tensor_source_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                      const lanczos_resize_window* win, const lanczos_resize_crops* crops,
+                                      const lanczos_resize_source* src, const lanczos_tensor_view* v, const void* in, void* out,
+                                      int frames);
+/* LANCZOS_SOURCE_DIRECT / LANCZOS_SOURCE_PACKED of the last call that had a source and returned LANCZOS_OK, 0 before any. */
+int lanczos_last_source_route(const lanczos_ctx* ctx);
 
 /* ---- reduce by whole factors (Pillow's Image.reduce((fx, fy), box), an exact integer box average) ----
  * 8-bit, 1, 3 or 4 independent interleaved channels.  box = (x0, y0, x1, y1), integers with 0 <= x0 < x1 <= in_w and the same

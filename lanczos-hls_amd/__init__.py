@@ -40,6 +40,8 @@ FILTER_NAMES = ("lanczos", "box", "bilinear", "hamming", "bicubic", "nearest")
 TENSOR_FUSED, TENSOR_CONVERTED = 1, 2   # lanczos_last_tensor_route: who wrote the floats of the last tensor call
 TENSOR_BF16, TENSOR_F16 = 1, 2          # the formats of lanczos_tensor_lut_convert16 / lanczos_tensor16_lut_normalize
 _TENSOR16_FORMATS = {"bfloat16": TENSOR_BF16, "float16": TENSOR_F16}
+SOURCE_INTERLEAVED, SOURCE_PLANAR = 0, 1   # the layouts of lanczos_resize_source_init
+SOURCE_DIRECT, SOURCE_PACKED = 1, 2        # lanczos_last_source_route: who read the source of the last call that had one
 
 # every symbol include/lanczos_hip.h declares (tests check the library exports exactly these)
 ABI_SYMBOLS = [
@@ -74,6 +76,9 @@ ABI_SYMBOLS = [
     "lanczos_resize_tensor_view_host",
     "lanczos_resize_crops_validate", "lanczos_resize_crops_plan_host", "lanczos_resize_tensor_crops_validate",
     "lanczos_resize_tensor_crops_device", "lanczos_resize_tensor_crops_host",
+    "lanczos_resize_source_init", "lanczos_resize_source_validate", "lanczos_resize_source_device",
+    "lanczos_resize_tensor_source_device", "lanczos_resize_source_host", "lanczos_resize_tensor_source_host",
+    "lanczos_last_source_route",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
 
@@ -187,6 +192,13 @@ class ResizeCrops(ctypes.Structure):
     """lanczos_resize_crops -- one window size (w, h) for every frame and a pointer to `frames` pairs (x0, y0) of int32, the
     window's origin per frame in output pixels of the full request; read, and clamped into the output, when the kernels run."""
     _fields_ = [("w", ctypes.c_int32), ("h", ctypes.c_int32), ("d_origin", ctypes.c_void_p), ("reserved", ctypes.c_int32 * 4)]
+
+
+class ResizeSource(ctypes.Structure):
+    """lanczos_resize_source -- where the samples of a source frame lie: sample (y, x, c) at byte c * chan_stride +
+    y * row_stride + x * pix_stride of its frame.  Interleaved with pitched rows, or planar (8-bit)."""
+    _fields_ = [("row_stride", ctypes.c_int64), ("chan_stride", ctypes.c_int64), ("pix_stride", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 3)]
 
 
 FLIP_H, FLIP_V = 1, 2   # the bits of lanczos_tensor_view.flip and of a d_flip byte
@@ -338,6 +350,17 @@ def _lib():
             L.lanczos_resize_tensor_crops_device.argtypes = [c_void_p, PRD, PRO, PRC, PTV, c_void_p, c_void_p, c_int, c_size_t,
                                                              c_size_t, c_void_p]
             L.lanczos_resize_tensor_crops_host.argtypes = [c_void_p, PRD, PRO, PRC, PTV, c_void_p, c_void_p, c_int]
+        if hasattr(L, "lanczos_resize_source_device"):   # (nor a source layout)
+            PRS = ctypes.POINTER(ResizeSource)
+            L.lanczos_resize_source_init.argtypes = [PRS, PRD, c_int]
+            L.lanczos_resize_source_validate.argtypes = [PRD, PRS]
+            L.lanczos_resize_source_device.argtypes = [c_void_p, PRD, PRO, PRW, PRS, c_void_p, c_void_p, c_int, c_size_t, c_size_t,
+                                                       c_void_p]
+            L.lanczos_resize_tensor_source_device.argtypes = [c_void_p, PRD, PRO, PRW, PRC, PRS, PTV, c_void_p, c_void_p, c_int,
+                                                              c_size_t, c_size_t, c_void_p]
+            L.lanczos_resize_source_host.argtypes = [c_void_p, PRD, PRO, PRW, PRS, c_void_p, c_void_p, c_int]
+            L.lanczos_resize_tensor_source_host.argtypes = [c_void_p, PRD, PRO, PRW, PRC, PRS, PTV, c_void_p, c_void_p, c_int]
+            L.lanczos_last_source_route.argtypes = [c_void_p]
         L.lanczos_strerror.restype = ctypes.c_char_p
         L.lanczos_version.argtypes = []
         L.lanczos_version.restype = ctypes.c_char_p
@@ -567,6 +590,40 @@ def resize_crops_plan_host(desc, crops, frames=1, box=None, reducing_gap=None, o
     _check(_lib().lanczos_resize_crops_plan_host(ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
                                                  ctypes.byref(crops), frames, ctypes.byref(p)), "lanczos_resize_crops_plan_host")
     return p
+
+
+def resize_source(desc, layout="planar", row_stride=None, chan_stride=None):
+    """A ResizeSource for `desc`: layout "planar" (N x C x H x W bytes, what torchvision.io.decode_jpeg(device=) returns) or
+    "interleaved"; row_stride / chan_stride in bytes replace the tight layout's (pitched rows, padded planes).  Validated where it
+    is used (resize_source_validate); a ready ResizeSource is returned as it is."""
+    if isinstance(layout, ResizeSource):
+        return layout
+    kinds = {"interleaved": SOURCE_INTERLEAVED, "planar": SOURCE_PLANAR}
+    if layout not in kinds:
+        raise LanczosError(ERR_BAD_ARG, f"resize_source: layout is 'planar' or 'interleaved', not {layout!r}")
+    s = ResizeSource()
+    _check(_lib().lanczos_resize_source_init(ctypes.byref(s), ctypes.byref(desc), kinds[layout]), "lanczos_resize_source_init")
+    if row_stride is not None:
+        if chan_stride is None and layout == "planar":   # the planes stay back to back
+            chan_stride = int(row_stride) * desc.in_h
+        s.row_stride = int(row_stride)
+    if chan_stride is not None:
+        s.chan_stride = int(chan_stride)
+    return s
+
+
+def resize_source_validate(desc, source):
+    """lanczos_resize_source_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the layout is refused."""
+    _check(_lib().lanczos_resize_source_validate(ctypes.byref(desc), ctypes.byref(source) if source is not None else None),
+           "lanczos_resize_source_validate")
+
+
+def _planar_frames(img, what):
+    """uint8 (C, H, W) or (N, C, H, W) -> a contiguous (N, C, H, W) array"""
+    img = np.ascontiguousarray(img)
+    if img.dtype != np.uint8 or img.ndim not in (3, 4):
+        raise LanczosError(ERR_BAD_ARG, f"{what}: planar=True takes a uint8 [C][H][W] or [F][C][H][W] array")
+    return img if img.ndim == 4 else img[None]
 
 
 def center_window(out_w, out_h, w, h):
@@ -834,8 +891,12 @@ class Context:
                                                      stream), "lanczos_resample_planar_device")
 
     # -- resize to any size (Pillow's contract, lanczos_resize_*)
-    def resize(self, img, out_w, out_h, a=3, alpha=False, box=None, reducing_gap=None, filter=FILTER_LANCZOS, window=None):
-        """window = (x0, y0, w, h) in output pixels: compute and return only that window of the out_h x out_w result, [h][w]
+    def resize(self, img, out_w, out_h, a=3, alpha=False, box=None, reducing_gap=None, filter=FILTER_LANCZOS, window=None,
+               planar=False):
+        """planar=True: img is uint8 [C][H][W] or [F][C][H][W] (planes, as a decoder or a torch stage leaves them) and is read
+        as it lies (lanczos_resize_source_host); the result is interleaved as ever, [h][w][C] or [F][h][w][C], the bytes of the
+        same call on img moved to [H][W][C].
+        window = (x0, y0, w, h) in output pixels: compute and return only that window of the out_h x out_w result, [h][w]
         instead of [out_h][out_w] -- exactly Image.resize(...).crop((x0, y0, x0 + w, y0 + h)), without computing the rest
         (center_window gives torchvision's CenterCrop).
         filter: Image.resize's `resample` as a name ("lanczos", "box", "bilinear", "hamming", "bicubic", "nearest") or
@@ -850,6 +911,17 @@ class Context:
         channels) by default, mode RGBA (straight alpha in the last channel, premultiplied inside the kernels) with
         alpha=True; alpha=True with any other channel count raises LanczosError(ERR_BAD_ARG).  uint16: every channel as
         Pillow resizes an I;16 plane (a sum above 65535 stores 0xFF00 | low byte, as Pillow does); not with alpha."""
+        if planar:
+            x = _planar_frames(img, "resize")
+            f, c, h, w = x.shape
+            d = resize_desc(w, h, out_w, out_h, c, a, alpha, filter=filter)
+            win = resize_window(d, window)
+            out = np.empty((f, win.h, win.w, c), dtype=np.uint8)
+            _check(_lib().lanczos_resize_source_host(self._h, ctypes.byref(d), _opts_ref(d, box, reducing_gap, None),
+                                                     ctypes.byref(win) if window is not None else None,
+                                                     ctypes.byref(resize_source(d, "planar")), x.ctypes.data, out.ctypes.data, f),
+                   "lanczos_resize_source_host")
+            return out if np.ndim(img) == 4 else out[0]
         img = np.ascontiguousarray(img)
         if img.dtype not in (np.uint8, np.uint16) or img.ndim not in (2, 3, 4):
             raise LanczosError(ERR_BAD_ARG, "resize: expected a uint8 or uint16 [H][W], [H][W][C] or [F][H][W][C] array")
@@ -903,8 +975,10 @@ class Context:
         return out if img.ndim == 4 else out[0]
 
     def resize_device(self, desc, d_in, d_out, frames, in_frame_stride=0, out_frame_stride=0, stream=None, box=None,
-                      reducing_gap=None, opts=None, filter=None, window=None):
-        """Device pointers, asynchronous on `stream` (None = the default stream).  box / reducing_gap / opts as
+                      reducing_gap=None, opts=None, filter=None, window=None, source=None):
+        """source: a ResizeSource (resize_source) saying where the samples of the frames at d_in lie -- planar, or interleaved
+        with pitched rows; in_frame_stride 0 is then that layout's extent (lanczos_resize_source_device).
+        Device pointers, asynchronous on `stream` (None = the default stream).  box / reducing_gap / opts as
         resize_taps_host.  The filter is the descriptor's (resize_desc(..., filter=)); filter= (a name or FILTER_*) runs
         the same request with that filter instead.  window = (x0, y0, w, h) or a ResizeWindow: the frames at d_out are that
         window of the output, w x h pixels tightly packed (out_frame_stride 0 = one such frame)."""
@@ -912,7 +986,11 @@ class Context:
             d = ResizeDesc.from_buffer_copy(desc)
             d.reserved[0] = (d.reserved[0] & ~(15 << 8)) | (filter_code(filter) << 8)
             desc = d
-        if window is not None:
+        if source is not None:
+            _check(_lib().lanczos_resize_source_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
+                                                       _window_ref(desc, window), ctypes.byref(source), d_in, d_out, frames,
+                                                       in_frame_stride, out_frame_stride, stream), "lanczos_resize_source_device")
+        elif window is not None:
             _check(_lib().lanczos_resize_window_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
                                                        _window_ref(desc, window), d_in, d_out, frames, in_frame_stride,
                                                        out_frame_stride, stream), "lanczos_resize_window_device")
@@ -927,8 +1005,10 @@ class Context:
     # -- resize straight into a float tensor (PIL.Image.resize -> ToTensor() -> Normalize(), lanczos_resize_tensor_*)
     def resize_tensor(self, img, out_w, out_h, mean=None, std=None, lut=None, layout="chw", a=3, alpha=False, box=None,
                       reducing_gap=None, filter=FILTER_LANCZOS, dtype="float32", window=None, channels_out=None, flip=None,
-                      crop=None, origins=None):
-        """crop=(w, h) with origins=[(x0, y0), ...], one pair per frame: frame f of the result is the w x h window of its
+                      crop=None, origins=None, planar=False):
+        """planar=True: img is uint8 [C][H][W] or [F][C][H][W] and is read as it lies (lanczos_resize_tensor_source_host); the
+        result is that of the same call on img moved to [H][W][C].
+        crop=(w, h) with origins=[(x0, y0), ...], one pair per frame: frame f of the result is the w x h window of its
         resize at origins[f] (Resize -> RandomCrop; lanczos_resize_tensor_crops_host, which refuses an origin outside the
         output).  channels_out and flip apply as below; not together with window.
         channels_out: a tuple of source channel indices, one per channel of the result -- (2, 1, 0) turns BGR into RGB,
@@ -949,14 +1029,19 @@ class Context:
         wide = dtype == "float32"
         if not wide:
             _tensor16_format(dtype, "resize_tensor")
-        img = np.ascontiguousarray(img)
-        if img.dtype != np.uint8 or img.ndim not in (2, 3, 4):
-            raise LanczosError(ERR_BAD_ARG, "resize_tensor: expected a uint8 [H][W], [H][W][C] or [F][H][W][C] array")
-        x = img.reshape(img.shape + (1,)) if img.ndim == 2 else img
-        x = x if x.ndim == 4 else x[None]
-        f, h, w, c = x.shape
+        if planar:
+            x = _planar_frames(img, "resize_tensor")
+            f, c, h, w = x.shape
+            img = x if np.ndim(img) == 4 else x[0]
+        else:
+            img = np.ascontiguousarray(img)
+            if img.dtype != np.uint8 or img.ndim not in (2, 3, 4):
+                raise LanczosError(ERR_BAD_ARG, "resize_tensor: expected a uint8 [H][W], [H][W][C] or [F][H][W][C] array")
+            x = img.reshape(img.shape + (1,)) if img.ndim == 2 else img
+            x = x if x.ndim == 4 else x[None]
+            f, h, w, c = x.shape
         d = resize_desc(w, h, out_w, out_h, c, a, alpha, filter=filter)
-        view = channels_out is not None or flip is not None
+        view = planar or channels_out is not None or flip is not None
         if channels_out is not None:
             channels_out = tuple(int(v) for v in channels_out)
             if not 1 <= len(channels_out) <= c:
@@ -1002,7 +1087,14 @@ class Context:
                             channels_out if channels_out is not None else tuple(range(c)),
                             0 if flips is not None else flip, flips.ctypes.data if flips is not None else None)
             out = np.empty(shape, dtype=np.float32 if wide else np.uint16)
-            if org is not None:
+            if planar:
+                cr = resize_crops(win.w, win.h, org.ctypes.data) if org is not None else None
+                _check(_lib().lanczos_resize_tensor_source_host(self._h, ctypes.byref(d), opts, None if cr is not None else wref,
+                                                                ctypes.byref(cr) if cr is not None else None,
+                                                                ctypes.byref(resize_source(d, "planar")), ctypes.byref(v),
+                                                                x.ctypes.data, out.ctypes.data, f),
+                       "lanczos_resize_tensor_source_host")
+            elif org is not None:
                 cr = resize_crops(win.w, win.h, org.ctypes.data)
                 _check(_lib().lanczos_resize_tensor_crops_host(self._h, ctypes.byref(d), opts, ctypes.byref(cr), ctypes.byref(v),
                                                                x.ctypes.data, out.ctypes.data, f),
@@ -1036,8 +1128,10 @@ class Context:
 
     def resize_tensor_device(self, desc, d_in, d_out, frames, d_lut, strides, in_frame_stride=0, out_frame_stride=0,
                              stream=None, box=None, reducing_gap=None, opts=None, dtype="float32", window=None,
-                             channels_out=None, flip=None, d_flip=None, crop=None, d_origin=None):
-        """crop=(w, h) with d_origin, a device pointer to `frames` int32 pairs (x0, y0) (or crop a ready ResizeCrops): every
+                             channels_out=None, flip=None, d_flip=None, crop=None, d_origin=None, source=None):
+        """source: a ResizeSource (resize_source) for the frames at d_in, as Context.resize_device; the request then runs as a
+        view (lanczos_resize_tensor_source_device), a ready TensorOut / TensorOut16 as `strides` included.
+        crop=(w, h) with d_origin, a device pointer to `frames` int32 pairs (x0, y0) (or crop a ready ResizeCrops): every
         frame stores the w x h window of its resize at its own origin, read and clamped into the output when the kernels run
         (lanczos_resize_tensor_crops_device).  The strides describe the C x h x w frame; not together with window.
         channels_out / flip as Context.resize_tensor (flip: None, "h", "v", "hv" or FLIP_* bits, for every frame); d_flip: a
@@ -1057,7 +1151,11 @@ class Context:
         if (crop is None or not isinstance(crop, ResizeCrops)) and (crop is None) != (d_origin is None):
             raise LanczosError(ERR_BAD_ARG, "resize_tensor_device: crop=(w, h) and d_origin= come together")
         wref = _window_ref(desc, window)
-        if crop is not None or isinstance(strides, TensorView) or channels_out is not None or flip is not None or d_flip is not None:
+        if source is not None and isinstance(strides, (TensorOut, TensorOut16)):   # the same request as a view
+            t = strides
+            strides = tensor_view(t.d_lut, (t.chan_stride, t.row_stride, t.pix_stride), 2 if isinstance(t, TensorOut16) else 4,
+                                  tuple(range(desc.channels)))
+        if source is not None or crop is not None or isinstance(strides, TensorView) or channels_out is not None or flip is not None or d_flip is not None:
             if isinstance(strides, TensorView):
                 v = strides
             else:
@@ -1065,6 +1163,13 @@ class Context:
                     _tensor16_format(dtype, "resize_tensor_device")
                 v = tensor_view(d_lut, strides, 4 if dtype == "float32" else 2,
                                 channels_out if channels_out is not None else tuple(range(desc.channels)), flip or 0, d_flip)
+            if source is not None:
+                cr = None if crop is None else crop if isinstance(crop, ResizeCrops) else resize_crops(crop[0], crop[1], d_origin)
+                _check(_lib().lanczos_resize_tensor_source_device(self._h, ctypes.byref(desc), oref, wref,
+                                                                  ctypes.byref(cr) if cr is not None else None, ctypes.byref(source),
+                                                                  ctypes.byref(v), d_in, d_out, frames, in_frame_stride,
+                                                                  out_frame_stride, stream), "lanczos_resize_tensor_source_device")
+                return
             if crop is not None:
                 cr = crop if isinstance(crop, ResizeCrops) else resize_crops(crop[0], crop[1], d_origin)
                 _check(_lib().lanczos_resize_tensor_crops_device(self._h, ctypes.byref(desc), oref, ctypes.byref(cr), ctypes.byref(v),
@@ -1102,6 +1207,11 @@ class Context:
         """TENSOR_FUSED (the resize kernel stored the floats), TENSOR_CONVERTED (bytes to scratch, then a conversion launch),
         or 0 if the last call on the context was no tensor call."""
         return _lib().lanczos_last_tensor_route(self._h)
+
+    def last_source_route(self):
+        """SOURCE_DIRECT (the resize kernel read the source as it lies), SOURCE_PACKED (one launch gathered it tightly packed
+        into context scratch first), of the last call on the context that had a source layout; 0 before any."""
+        return _lib().lanczos_last_source_route(self._h)
 
     # -- reduce by whole factors (Pillow's Image.reduce, lanczos_reduce_*)
     def reduce(self, img, factor, box=None):

@@ -68,6 +68,7 @@ struct lanczos_ctx {
     std::mutex mu;
     int last_kernel = LANCZOS_KERNEL_NONE;
     int last_tensor_route = 0;   // lanczos_last_tensor_route: LANCZOS_TENSOR_* of the last call, 0 unless it was a tensor call
+    int last_source_route = 0;   // lanczos_last_source_route: LANCZOS_SOURCE_* of the last call that had a source layout
     int last_route = 0;      // lanczos_last_route: main kernel, prefix route and launch count of the last upscale call
     int route_launches = 0;  // launches of the call in flight (reset by the entry points, counted where a launch is issued)
     int route_seen = 0;      // prefix routes of those launches, one bit each
@@ -1292,7 +1293,7 @@ extern "C++" {
 // what follows the validation of a device request (tc.t filled)
 static int tensor_device_run(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                              const lanczos_resize_window* win, lz::RsTensorCall& tc, const void* d_in, void* d_out, int frames,
-                             size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+                             size_t in_frame_stride, size_t out_frame_stride, void* stream, lz::RsSourceCall* sc = nullptr) {
     std::lock_guard<std::mutex> lock(ctx->mu);
     LZ_HIP(ctx, hipSetDevice(ctx->device));
     int rc = resize_state(ctx);
@@ -1302,8 +1303,9 @@ static int tensor_device_run(lanczos_ctx* ctx, const lanczos_resize_desc* d, con
     (void)lz::resize_window_resolve(d, win, &w);   // validated by the caller
     tc.extent_bytes = lz::tensor_extent_bytes(d, w, tc.t);
     rc = lz::resize_device(ctx->resize, d, opts, win, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
-                           &ctx->last_kernel, &ctx->last_hip, &tc);
+                           &ctx->last_kernel, &ctx->last_hip, &tc, sc);
     ctx->last_tensor_route = tc.route;
+    if (rc == LANCZOS_OK && sc && sc->route) ctx->last_source_route = sc->route;   // a refused or failed call leaves it
     return rc;
 }
 
@@ -1320,15 +1322,17 @@ static int tensor_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const l
 // ... and of a host request (lay filled)
 static int tensor_host_run(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                            const lanczos_resize_window* win, const lz::RsTensorOut& lay, const void* in, void* out, int frames,
-                           const int32_t* origins = nullptr) {
+                           const int32_t* origins = nullptr, lz::RsSourceCall* sc = nullptr) {
     std::lock_guard<std::mutex> lock(ctx->mu);
     LZ_HIP(ctx, hipSetDevice(ctx->device));
     if (!ctx->stream) return LANCZOS_ERR_HIP;
-    const int rc = resize_state(ctx);
+    int rc = resize_state(ctx);
     if (rc != LANCZOS_OK) return rc;
     route_begin(ctx);
-    return lz::resize_tensor_host(ctx->resize, d, opts, win, lay, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip,
-                                  &ctx->last_tensor_route, origins);
+    rc = lz::resize_tensor_host(ctx->resize, d, opts, win, lay, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip,
+                                &ctx->last_tensor_route, origins, sc);
+    if (rc == LANCZOS_OK && sc && sc->route) ctx->last_source_route = sc->route;   // a refused or failed call leaves it
+    return rc;
 }
 
 template <class T>
@@ -1522,6 +1526,113 @@ int lanczos_resize_tensor_crops_host(lanczos_ctx* ctx, const lanczos_resize_desc
 }
 
 int lanczos_last_tensor_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_tensor_route : 0; }
+
+// ---- a source layout beside the descriptor (lanczos_resize_source.hip) -------------------------------------------------
+int lanczos_resize_source_init(lanczos_resize_source* src, const lanczos_resize_desc* d, int layout) {
+    if (!src || (layout != LANCZOS_SOURCE_INTERLEAVED && layout != LANCZOS_SOURCE_PLANAR)) return LANCZOS_ERR_BAD_ARG;
+    const int rc = lz::resize_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    const int64_t B = lz::resize_bps(d);
+    *src = lanczos_resize_source{};
+    if (layout == LANCZOS_SOURCE_PLANAR) {
+        if (B != 1) return LANCZOS_ERR_UNSUPPORTED;
+        src->row_stride = d->in_w, src->chan_stride = (int64_t)d->in_w * d->in_h, src->pix_stride = 1;
+    } else {
+        src->row_stride = (int64_t)d->in_w * d->channels * B, src->chan_stride = B, src->pix_stride = (int32_t)(d->channels * B);
+    }
+    return LANCZOS_OK;
+}
+
+int lanczos_resize_source_validate(const lanczos_resize_desc* d, const lanczos_resize_source* src) {
+    const int rc = lz::resize_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    lz::RsSource s;
+    return lz::resize_source_resolve(d, src, &s);
+}
+
+int lanczos_resize_source_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
+                                 const lanczos_resize_window* win, const lanczos_resize_source* src, const void* d_in,
+                                 void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+    if (!src) return lanczos_resize_window_device(ctx, d, o, win, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    int rc = lz::resize_validate(d);
+    lz::RsSourceCall sc;
+    if (rc == LANCZOS_OK) rc = lz::resize_source_resolve(d, src, &sc.s);
+    if (rc != LANCZOS_OK) return rc;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
+    route_begin(ctx);
+    rc = lz::resize_device(ctx->resize, d, o, win, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
+                           &ctx->last_kernel, &ctx->last_hip, nullptr, &sc);
+    if (rc == LANCZOS_OK && sc.route) ctx->last_source_route = sc.route;   // a refused or failed call leaves it
+    return rc;
+}
+
+int lanczos_resize_source_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
+                               const lanczos_resize_window* win, const lanczos_resize_source* src, const void* in, void* out,
+                               int frames) {
+    if (!src) return lanczos_resize_window_host(ctx, d, o, win, in, out, frames);
+    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    int rc = lz::resize_validate(d);
+    lz::RsSourceCall sc;
+    if (rc == LANCZOS_OK) rc = lz::resize_source_resolve(d, src, &sc.s);
+    if (rc != LANCZOS_OK) return rc;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->stream) return LANCZOS_ERR_HIP;
+    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
+    route_begin(ctx);
+    rc = lz::resize_host(ctx->resize, d, o, win, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip, &sc);
+    if (rc == LANCZOS_OK && sc.route) ctx->last_source_route = sc.route;   // a refused or failed call leaves it
+    return rc;
+}
+
+int lanczos_resize_tensor_source_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                        const lanczos_resize_window* win, const lanczos_resize_crops* crops,
+                                        const lanczos_resize_source* src, const lanczos_tensor_view* v, const void* d_in,
+                                        void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+    if (win && crops) return LANCZOS_ERR_BAD_ARG;
+    if (!src)
+        return crops ? lanczos_resize_tensor_crops_device(ctx, d, opts, crops, v, d_in, d_out, frames, in_frame_stride,
+                                                          out_frame_stride, stream)
+                     : lanczos_resize_tensor_view_device(ctx, d, opts, win, v, d_in, d_out, frames, in_frame_stride,
+                                                         out_frame_stride, stream);
+    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    lanczos_resize_window cw;
+    lz::RsTensorCall tc;
+    lz::RsSourceCall sc;
+    int rc = crops ? tensor_crops_validate(d, crops, v, &cw, &tc.t) : lz::tensor_view_validate(d, win, v, &tc.t);
+    if (rc == LANCZOS_OK) rc = lz::resize_source_resolve(d, src, &sc.s);
+    if (rc != LANCZOS_OK) return rc;
+    if (crops) tc.d_origin = crops->d_origin;
+    return tensor_device_run(ctx, d, opts, crops ? &cw : win, tc, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream, &sc);
+}
+
+int lanczos_resize_tensor_source_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                      const lanczos_resize_window* win, const lanczos_resize_crops* crops,
+                                      const lanczos_resize_source* src, const lanczos_tensor_view* v, const void* in, void* out,
+                                      int frames) {
+    if (win && crops) return LANCZOS_ERR_BAD_ARG;
+    if (!src)
+        return crops ? lanczos_resize_tensor_crops_host(ctx, d, opts, crops, v, in, out, frames)
+                     : lanczos_resize_tensor_view_host(ctx, d, opts, win, v, in, out, frames);
+    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    lanczos_resize_window cw;
+    lz::RsTensorOut lay;
+    lz::RsSourceCall sc;
+    int rc = crops ? tensor_crops_validate(d, crops, v, &cw, &lay) : lz::tensor_view_validate(d, win, v, &lay);
+    if (rc == LANCZOS_OK) rc = lz::resize_source_resolve(d, src, &sc.s);
+    if (rc != LANCZOS_OK) return rc;
+    if (crops)
+        for (int f = 0; f < frames; f++) {   // as lanczos_resize_tensor_crops_host: a host array is validated, not clamped
+            const int32_t x0 = crops->d_origin[2 * f], y0 = crops->d_origin[2 * f + 1];
+            if (x0 < 0 || x0 > d->out_w - crops->w || y0 < 0 || y0 > d->out_h - crops->h) return LANCZOS_ERR_BAD_ARG;
+        }
+    return tensor_host_run(ctx, d, opts, crops ? &cw : win, lay, in, out, frames, crops ? crops->d_origin : nullptr, &sc);
+}
+
+int lanczos_last_source_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_source_route : 0; }
 
 int lanczos_reduce_size(int in_w, int in_h, int fx, int fy, const int32_t* box, int* out_w, int* out_h) {
     if (!out_w || !out_h) return LANCZOS_ERR_BAD_ARG;

@@ -34,6 +34,11 @@
 // move their table pointers by the frame's origin, and every other route resizes the whole output and lets
 // k_rs_to_tensor_crops gather the windows (lanczos_resize_tensor_crops.hip).
 //
+// A source layout (lanczos_resize_source: planar frames, pitched rows) changes where a source byte is fetched from and nothing
+// else: the fused kernel reads such frames as they lie (a pitch is one of its arguments; planar frames have staging loads and
+// instances of their own, lanczos_resize_source*.hip), every other route gets them packed into context scratch by
+// k_rs_pack_source first (lanczos_resize_source.hip).
+//
 // The arithmetic is Pillow's and exact by construction; RsSample<BPS> says how for each width.
 #include "lanczos_resize.hpp"
 
@@ -382,6 +387,7 @@ ResizeState::~ResizeState() {   // the owner has drained the device
     if (scratch.p) (void)hipFree(scratch.p);
     if (reduced.p) (void)hipFree(reduced.p);
     if (tensor_bytes.p) (void)hipFree(tensor_bytes.p);
+    if (packed.p) (void)hipFree(packed.p);
     if (stage_in) (void)hipFree(stage_in);
     if (stage_out) (void)hipFree(stage_out);
     if (upload) (void)hipStreamDestroy(upload);
@@ -492,11 +498,13 @@ static int rs_plan_ring_rows(const RsAxisView& V, int y_at, int h) {
 // The fused kernel's launch shape for a w x h window of the output of H x V whose origin is any of nx x ny places from the
 // views' first outputs on: stage_dw and ring_rows are the largest any of them needs.  One place is the window itself.
 static bool rs_fused_plan_at(const lanczos_resize_desc* d, const RsAxisView& H, const RsAxisView& V, int w, int h, int nx, int ny,
-                             int frames, RsFusedPlan* fp) {
+                             int frames, RsFusedPlan* fp, size_t src_extent) {
     const int bps = resize_bps(d);
     const int C = d->channels * bps;   // bytes per pixel
     const int out_w = w, out_h = h;
-    if ((long long)d->in_w * d->in_h * C + 4 >= (1ll << 31)) return false;   // 32-bit buffer offsets
+    // 32-bit buffer offsets, into the frame as the kernel addresses it: a pitched or planar source has its own extent
+    if (src_extent >= ((size_t)1 << 31)) return false;
+    if ((src_extent ? (long long)src_extent : (long long)d->in_w * d->in_h * C) + 4 >= (1ll << 31)) return false;
     if ((long long)out_w * out_h * C >= (1ll << 31)) return false;
     const bool small = resize_filter(d) != LANCZOS_FILTER_LANCZOS;   // the instances with 3 and 5 taps
     fp->K = rs_bucket(H.ksize, small);
@@ -527,15 +535,16 @@ static bool rs_fused_plan_at(const lanczos_resize_desc* d, const RsAxisView& H, 
 
 // the fused kernel's launch shape for this request, both of whose passes run (false: it cannot run it).  The output is that
 // of the two views, a window of d's
-bool rs_fused_plan(const lanczos_resize_desc* d, const RsAxisView& H, const RsAxisView& V, int frames, RsFusedPlan* fp) {
-    return rs_fused_plan_at(d, H, V, H.n, V.n, 1, 1, frames, fp);
+bool rs_fused_plan(const lanczos_resize_desc* d, const RsAxisView& H, const RsAxisView& V, int frames, RsFusedPlan* fp,
+                   size_t src_extent) {
+    return rs_fused_plan_at(d, H, V, H.n, V.n, 1, 1, frames, fp, src_extent);
 }
 
 // ... and for a w x h window at any origin inside the output of the two views, which are the full axes: brute force over the
 // origins of each axis, a few hundred at most times a handful of strips or march steps
 bool rs_fused_plan_crops(const lanczos_resize_desc* d, const RsAxisView& H, const RsAxisView& V, int w, int h, int frames,
-                         RsFusedPlan* fp) {
-    return rs_fused_plan_at(d, H, V, w, h, H.n - w + 1, V.n - h + 1, frames, fp);
+                         RsFusedPlan* fp, size_t src_extent) {
+    return rs_fused_plan_at(d, H, V, w, h, H.n - w + 1, V.n - h + 1, frames, fp, src_extent);
 }
 
 int resize_crops_validate(const lanczos_resize_desc* d, const lanczos_resize_crops* c) {
@@ -627,9 +636,33 @@ static hipError_t rs_launch_pass(int bps, bool horizontal, const ResizeAxis* ax,
 // tc->d_origin (a crop origin per frame): win is (0, 0, w, h).  The fused kernel runs on the plan that holds for every origin;
 // everything else resizes the whole output into context scratch and k_rs_to_tensor_crops gathers each frame's window from it --
 // or from the caller's frames where no pass runs
+// sc: the frames at `in` lie in that layout, which is not the tight one (the tight one is no source at all).  Where the fused
+// kernel runs and has the staging for it, it reads them as they lie (LANCZOS_SOURCE_DIRECT); everything else gets them packed
+// into context scratch first (rs_pack_source) and is then the request it always was
 static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh, RsSpan sv, const RsWindow& win_in,
                         const uint8_t* in, uint8_t* out, int frames, size_t in_fs, size_t out_fs, hipStream_t stream,
-                        int* last_kernel, int* last_hip, RsTensorCall* tc) {
+                        int* last_kernel, int* last_hip, RsTensorCall* tc, RsSourceCall* sc = nullptr);
+
+// the PACKED route of a source: `frames` frames at *in, in layout s, gathered tightly packed into the context's block; *in and
+// *in_fs then name that block
+static int rs_pack_source(ResizeState* st, const lanczos_resize_desc* d, const RsSource& s, const uint8_t** in, size_t* in_fs,
+                          int frames, hipStream_t stream, int* last_hip) {
+    const size_t fs = ((size_t)d->in_w * d->in_h * d->channels * resize_bps(d) + 3) & ~(size_t)3;
+    const int rc = rs_scratch(st, &st->packed, (size_t)frames * fs, stream, stream_capturing(stream), last_hip);
+    if (rc != LANCZOS_OK) return rc;
+    const hipError_t e = rs_pack_source_launch(*in, *in_fs, s, (uint8_t*)st->packed.p, fs, d->in_w, d->in_h, d->channels,
+                                               resize_bps(d), frames, stream);
+    if (e != hipSuccess) {
+        *last_hip = (int)e;
+        return LANCZOS_ERR_HIP;
+    }
+    *in = (const uint8_t*)st->packed.p, *in_fs = fs;
+    return LANCZOS_OK;
+}
+
+static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh, RsSpan sv, const RsWindow& win_in,
+                        const uint8_t* in, uint8_t* out, int frames, size_t in_fs, size_t out_fs, hipStream_t stream,
+                        int* last_kernel, int* last_hip, RsTensorCall* tc, RsSourceCall* sc) {
     const int C = d->channels;
     const size_t B = (size_t)resize_bps(d);   // bytes per sample
     const bool f32 = B == 4;
@@ -654,10 +687,23 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     const bool crops = tc && tc->d_origin;
     RsWindow win = win_in;
     RsFusedPlan fp;
-    bool fused_ok = !nearest && need_h && need_v &&
-                    (crops ? rs_fused_plan_crops(d, rs_axis_view(H->host, 0, d->out_w), rs_axis_view(V->host, 0, d->out_h), win.w, win.h,
-                                                 frames, &fp)
-                           : rs_fused_plan(d, rs_axis_view(H->host, win.x0, win.w), rs_axis_view(V->host, win.y0, win.h), frames, &fp));
+    // the source as the fused kernel would read it: a planar one needs the instances, which crops have none of, and AUTO's leave
+    const RsSource* src = sc ? &sc->s : nullptr;
+    // ALPHA stages whole pixels and shifts them by the frame's residue: rows whose pitch is no dword multiple need the instances
+    // that shift by the row's, which crops have none of either
+    const bool rowshift = src && !src->planar && alpha && (src->row_stride & 3) != 0;
+    if (src && (st->force == LANCZOS_RESIZE_CONVERT || st->force == LANCZOS_RESIZE_TWO_PASS || (rowshift && crops) ||
+                (src->planar && (crops || (st->force == LANCZOS_RESIZE_AUTO && !kRsPlanarAutoDirect)))))
+        src = nullptr;
+    auto plan = [&](size_t extent) {
+        return !nearest && need_h && need_v &&
+               (crops ? rs_fused_plan_crops(d, rs_axis_view(H->host, 0, d->out_w), rs_axis_view(V->host, 0, d->out_h), win.w, win.h,
+                                            frames, &fp, extent)
+                      : rs_fused_plan(d, rs_axis_view(H->host, win.x0, win.w), rs_axis_view(V->host, win.y0, win.h), frames, &fp,
+                                      extent));
+    };
+    bool fused_ok = src ? plan(src->extent) : false;
+    if (!fused_ok) src = nullptr, fused_ok = plan(0);   // no source, or one the kernel cannot address: the packed frame's plan
     if (st->force == LANCZOS_RESIZE_FUSED && !fused_ok) return LANCZOS_ERR_UNSUPPORTED;
     bool fused = fused_ok && st->force != LANCZOS_RESIZE_TWO_PASS;
     // 32-bit buffer offsets into the element frame: a larger one is converted, and refused where the fused kernel is forced
@@ -667,6 +713,11 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     uint8_t* const t_out = out;
     const size_t t_fs = out_fs;
     const bool crops_gather = crops && !t_fused;
+    if (sc) {
+        if (crops_gather || !fused) src = nullptr;   // the fused kernel alone reads a source as it lies
+        sc->route = src ? LANCZOS_SOURCE_DIRECT : LANCZOS_SOURCE_PACKED;
+        if (!src && (rc = rs_pack_source(st, d, sc->s, &in, &in_fs, frames, stream, last_hip)) != LANCZOS_OK) return rc;
+    }
     const bool crops_direct = crops_gather && !nearest && !need_h && !need_v;   // no pass runs: the caller's frames are the bytes
     if (crops_gather) {   // the bytes of the whole output, by the plan of the whole output
         win = RsWindow{0, 0, d->out_w, d->out_h};
@@ -690,8 +741,14 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     const size_t in_pitch = (size_t)d->in_w * C * B;
     hipError_t e = hipSuccess;
     if (fused) {
-        const RsFusedLaunch c{d, win, &fp, H, V, in, out, in_fs, out_fs, frames, tc, stream};
-        e = t_fused && crops ? (tc->t.elem == 2 ? rs_launch_fused<1, 2 + kRsMapped + kRsCrops>(c)
+        const RsFusedLaunch c{d, win, &fp, H, V, in, out, in_fs, out_fs, frames, tc, stream, src};
+        e = src && src->planar ? (!t_fused           ? rs_launch_fused<1, kRsPlanar>(c)
+                                  : tc->t.elem == 2 ? rs_launch_fused<1, 2 + kRsMapped + kRsPlanar>(c)
+                                                    : rs_launch_fused<1, 4 + kRsMapped + kRsPlanar>(c))
+            : src && rowshift  ? (!t_fused           ? rs_launch_fused<1, kRsRowShift>(c)
+                                  : tc->t.elem == 2 ? rs_launch_fused<1, 2 + kRsMapped + kRsRowShift>(c)
+                                                    : rs_launch_fused<1, 4 + kRsMapped + kRsRowShift>(c))
+            : t_fused && crops ? (tc->t.elem == 2 ? rs_launch_fused<1, 2 + kRsMapped + kRsCrops>(c)
                                                 : rs_launch_fused<1, 4 + kRsMapped + kRsCrops>(c))
             : t_fused && tc->t.mapped ? (tc->t.elem == 2 ? rs_launch_fused<1, 2 + kRsMapped>(c) : rs_launch_fused<1, 4 + kRsMapped>(c))
             : t_fused ? (tc->t.elem == 2 ? rs_launch_fused<1, 2>(c) : rs_launch_fused<1, 4>(c))
@@ -767,7 +824,7 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
 
 int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
                   const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream,
-                  int* last_kernel, int* last_hip, RsTensorCall* tc) {
+                  int* last_kernel, int* last_hip, RsTensorCall* tc, RsSourceCall* sc) {
     RsResolved r;
     RsWindow w;
     int rc = resize_resolve(d, o, &r);
@@ -775,7 +832,8 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_r
     if (rc != LANCZOS_OK) return rc;
     const int C = d->channels;
     const size_t B = (size_t)resize_bps(d);   // bytes per sample
-    const size_t in_frame = (size_t)d->in_w * d->in_h * C * B;
+    if (sc && sc->s.tight) sc->route = LANCZOS_SOURCE_DIRECT, sc = nullptr;   // the call without a source
+    const size_t in_frame = sc ? sc->s.extent : (size_t)d->in_w * d->in_h * C * B;
     const size_t out_frame = tc ? tc->extent_bytes : (size_t)w.w * w.h * C * B;
     const size_t in_fs = in_frame_stride ? in_frame_stride : in_frame;
     const size_t out_fs = out_frame_stride ? out_frame_stride : out_frame;
@@ -783,6 +841,11 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_r
     if ((((uintptr_t)d_in | (uintptr_t)d_out | in_fs | out_fs) & (B - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
     if (tc && (((uintptr_t)d_out | out_fs) & (size_t)(tc->t.elem - 1)) != 0) return LANCZOS_ERR_BAD_ARG;   // element frames
     const uint8_t* in = (const uint8_t*)d_in;
+    size_t in_fs_r = in_fs;
+    if (sc && r.reduces()) {   // the reduction reads packed frames
+        sc->route = LANCZOS_SOURCE_PACKED;
+        if ((rc = rs_pack_source(st, d, sc->s, &in, &in_fs_r, frames, stream, last_hip)) != LANCZOS_OK) return rc;
+    }
     if (r.reduces()) {   // reducing_gap: reduce into context scratch, then resize the reduced frames
         int rb[4];
         const int32_t box[4] = {r.rb[0], r.rb[1], r.rb[2], r.rb[3]};
@@ -790,7 +853,7 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_r
         const size_t red_fs = (size_t)r.inner.in_w * r.inner.in_h * C;
         rc = rs_scratch(st, &st->reduced, (size_t)frames * red_fs, stream, stream_capturing(stream), last_hip);
         if (rc != LANCZOS_OK) return rc;
-        const hipError_t e = reduce_launch(in, (uint8_t*)st->reduced.p, d->in_w, C, r.fx, r.fy, rb, frames, in_fs, red_fs, stream);
+        const hipError_t e = reduce_launch(in, (uint8_t*)st->reduced.p, d->in_w, C, r.fx, r.fy, rb, frames, in_fs_r, red_fs, stream);
         if (e != hipSuccess) {
             *last_hip = (int)e;
             return LANCZOS_ERR_HIP;
@@ -798,7 +861,7 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_r
         return resize_inner(st, &r.inner, r.h, r.v, w, (const uint8_t*)st->reduced.p, (uint8_t*)d_out, frames, red_fs, out_fs,
                             stream, last_kernel, last_hip, tc);
     }
-    return resize_inner(st, d, r.h, r.v, w, in, (uint8_t*)d_out, frames, in_fs, out_fs, stream, last_kernel, last_hip, tc);
+    return resize_inner(st, d, r.h, r.v, w, in, (uint8_t*)d_out, frames, in_fs, out_fs, stream, last_kernel, last_hip, tc, sc);
 }
 
 // staging buffers of the host entry points (resize and reduce)
@@ -858,16 +921,16 @@ static int rs_staged_call(ResizeState* st, const void* in, size_t in_bytes, void
 }
 
 int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
-                const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip) {
+                const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip, RsSourceCall* sc) {
     const size_t B = (size_t)resize_bps(d);
     if ((((uintptr_t)in | (uintptr_t)out) & (B - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
     RsWindow w;
     const int rc = resize_window_resolve(d, win, &w);
     if (rc != LANCZOS_OK) return rc;
-    const size_t in_bytes = (size_t)d->in_w * d->in_h * d->channels * B * frames;
+    const size_t in_bytes = (sc ? sc->s.extent : (size_t)d->in_w * d->in_h * d->channels * B) * frames;
     const size_t out_bytes = (size_t)w.w * w.h * d->channels * B * frames;
     return rs_staged_call(st, in, in_bytes, out, out_bytes, {}, stream, last_hip, [&] {
-        return resize_device(st, d, o, win, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip);
+        return resize_device(st, d, o, win, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip, nullptr, sc);
     });
 }
 
@@ -875,7 +938,7 @@ int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_res
 // frames go up before they come back, so that the elements of `out` the strides leave out keep what they held.
 int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
                        const lanczos_resize_window* win, const RsTensorOut& t, const void* in, void* out, int frames,
-                       hipStream_t stream, int* last_kernel, int* last_hip, int* route, const int32_t* origins) {
+                       hipStream_t stream, int* last_kernel, int* last_hip, int* route, const int32_t* origins, RsSourceCall* sc) {
     if (((uintptr_t)out & (uintptr_t)(t.elem - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
     RsWindow w;
     const int wrc = resize_window_resolve(d, win, &w);
@@ -883,7 +946,7 @@ int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanc
     RsTensorCall tc;
     tc.t = t;
     tc.extent_bytes = tensor_extent_bytes(d, w, t);
-    const size_t in_bytes = (size_t)d->in_w * d->in_h * d->channels * frames;
+    const size_t in_bytes = (sc ? sc->s.extent : (size_t)d->in_w * d->in_h * d->channels) * frames;
     RsStagedExtra x;
     x.table = t.d_lut, x.table_at = (in_bytes + 255) & ~(size_t)255, x.table_bytes = (size_t)t.out_channels * 256 * t.elem;
     if (t.d_flip) x.flips = t.d_flip, x.flips_at = x.table_at + x.table_bytes, x.flips_bytes = (size_t)frames;
@@ -896,7 +959,7 @@ int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanc
         tc.t.d_lut = (const uint8_t*)st->stage_in + x.table_at;
         if (t.d_flip) tc.t.d_flip = (const uint8_t*)st->stage_in + x.flips_at;
         if (origins) tc.d_origin = (const int32_t*)((const uint8_t*)st->stage_in + x.origins_at);
-        const int rc = resize_device(st, d, o, win, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip, &tc);
+        const int rc = resize_device(st, d, o, win, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip, &tc, sc);
         *route = tc.route;
         return rc;
     });

@@ -4,7 +4,8 @@
 // samples in lanczos_resize_fused.hpp; the fused instances are compiled by lanczos_resize.hip (8-bit), lanczos_resize_tensor.hip
 // (8-bit into float tensors), lanczos_resize_tensor16.hip (8-bit into bfloat16 / float16 tensors), lanczos_resize_tensor_view.hip
 // and lanczos_resize_tensor16_view.hip (the same two through a channel map and flips), lanczos_resize_tensor_crops.hip and
-// lanczos_resize_tensor16_crops.hip (those with a crop origin per frame), lanczos_resize16.hip and
+// lanczos_resize_tensor16_crops.hip (those with a crop origin per frame), lanczos_resize_source.hip, lanczos_resize_source_tensor.hip
+// and lanczos_resize_source_tensor16.hip (those of a planar or oddly pitched source), lanczos_resize16.hip and
 // lanczos_resize32.hip.  The filter of a request (LANCZOS_RESIZE_FILTER)
 // only changes the tables; LANCZOS_FILTER_NEAREST has index tables and a kernel of its own (lanczos_resize_nearest.hip).
 #pragma once
@@ -112,13 +113,15 @@ struct RsFusedPlan {
     int K = 0, strips = 0, rows_per_chunk = 0, chunks = 0, ring_rows = 0, stage_rows = 0, stage_dw = 0;
     size_t lds = 0;
 };
-bool rs_fused_plan(const lanczos_resize_desc* d, const RsAxisView& H, const RsAxisView& V, int frames, RsFusedPlan* fp);
+// src_extent: the bytes of a source frame as the kernel addresses it, where that is not the packed frame (0)
+bool rs_fused_plan(const lanczos_resize_desc* d, const RsAxisView& H, const RsAxisView& V, int frames, RsFusedPlan* fp,
+                   size_t src_extent = 0);
 // The plan of a w x h window whose origin is only known when the kernel runs (lanczos_resize_crops).  H and V are the full
 // axes.  K, strips, rows_per_chunk and chunks depend on the window's size alone; stage_dw is the largest over every x origin
 // and ring_rows the largest over every y origin of what rs_fused_plan computes for the window there; stage_rows and lds follow
 // from those by its rule.  false where that does not fit, even if the window at some origins would
 bool rs_fused_plan_crops(const lanczos_resize_desc* d, const RsAxisView& H, const RsAxisView& V, int w, int h, int frames,
-                         RsFusedPlan* fp);
+                         RsFusedPlan* fp, size_t src_extent = 0);
 // crops: the plan of a request with a crop origin per frame (win is then NULL; mid_row0 / mid_rows are the whole output's,
 // which the converted route resizes)
 int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win, int frames,
@@ -157,6 +160,7 @@ struct ResizeState {
     Block scratch;                           // intermediate of the two-pass path (the rows the vertical taps read x out_w x C)
     Block reduced;                           // the reduced frames of a request with reducing_gap, tightly packed
     Block tensor_bytes;                      // the byte result of a tensor request on the converted route (k_rs_to_tensor reads it)
+    Block packed;                            // the tightly packed copy of a source on the PACKED route (k_rs_pack_source writes it)
     std::vector<void*> kept;                 // scratch blocks replaced while a graph may hold them: freed at destruction
     // staging of lanczos_resize_host
     void* stage_in = nullptr;
@@ -224,18 +228,43 @@ hipError_t rs_to_tensor_crops_launch(const uint8_t* src, size_t src_fs, size_t s
                                      size_t out_fs, int w, int h, int channels, const RsTensorOut& t, const int32_t* d_origin,
                                      int frames, hipStream_t stream);
 
+// A source layout (lanczos_resize_source), resolved by resize_source_resolve: sample (y, x, c) of a frame lies c * chan_stride +
+// y * row_stride + x * (planar ? 1 : C * B) bytes into it.  tight: interleaved with packed rows, the call without a source
+struct RsSource {
+    bool planar = false, tight = true;
+    size_t row_stride = 0, chan_stride = 0;   // bytes; chan_stride of an interleaved source is B
+    size_t extent = 0;                         // of one frame: in_h * row_stride, or channels * chan_stride
+};
+// src NULL: the tight interleaved layout.  Planar with one channel resolves to the interleaved shape
+int resize_source_resolve(const lanczos_resize_desc* d, const lanczos_resize_source* src, RsSource* s);
+// the source of a call and the route it took (LANCZOS_SOURCE_*); meaningful where the call returns LANCZOS_OK
+struct RsSourceCall {
+    RsSource s;
+    int route = 0;
+};
+// AUTO takes the planar instances of the fused kernel where they exist (false: PACKED, the instances by force only); the
+// measurements behind the choice are in DESIGN.md 4.5
+constexpr bool kRsPlanarAutoDirect = true;
+// k_rs_pack_source (lanczos_resize_source.hip): `frames` frames of w x h pixels of C samples of B bytes in layout s, in_fs
+// bytes apart at any byte address, to tightly packed interleaved frames out_fs bytes apart (out and out_fs dword multiples)
+hipError_t rs_pack_source_launch(const uint8_t* in, size_t in_fs, const RsSource& s, uint8_t* out, size_t out_fs, int w, int h,
+                                 int C, int B, int frames, hipStream_t stream);
+
 // The entry points (ctx->mu held, device set).  *last_kernel / *last_hip as in lanczos_ctx.  tc: a tensor request (NULL: bytes).
 // win: the window of the output that is computed and stored, tightly packed (NULL: the whole output)
 int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
                   const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream,
-                  int* last_kernel, int* last_hip, RsTensorCall* tc = nullptr);
+                  int* last_kernel, int* last_hip, RsTensorCall* tc = nullptr, RsSourceCall* sc = nullptr);
 // host table (t.d_lut), host flip array (t.d_flip, or NULL) and host buffers, element frames tensor_extent_bytes apart;
 // synchronous.  origins: NULL, or the host array of a lanczos_resize_crops request (win is then (0, 0, w, h))
 int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
                        const lanczos_resize_window* win, const RsTensorOut& t, const void* in, void* out, int frames,
-                       hipStream_t stream, int* last_kernel, int* last_hip, int* route, const int32_t* origins = nullptr);
+                       hipStream_t stream, int* last_kernel, int* last_hip, int* route, const int32_t* origins = nullptr,
+                       RsSourceCall* sc = nullptr);
+// sc: `in` holds the frames in that layout, its extent apart
 int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
-                const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip);
+                const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip,
+                RsSourceCall* sc = nullptr);
 
 // Reduce by whole factors (lanczos_reduce.hip): Pillow's Image.reduce over an integer box, 8-bit.  Arguments validated by
 // reduce_validate; the output rows are tightly packed.
@@ -261,12 +290,18 @@ struct RsFusedLaunch {
     int frames;
     const RsTensorCall* tc;   // TENSOR: `out` / `out_fs` are the element frames
     hipStream_t stream;
+    const RsSource* src = nullptr;   // NULL: packed interleaved rows.  A planar one runs the kRsPlanar instances
 };
 // TENSOR: bytes of a stored table element, 0 where the samples themselves are stored; + kRsMapped: through the channel map and
 // the flips of the request (RsTensorOut::mapped)
 constexpr int kRsMapped = 8;
 // + kRsCrops: a window origin per frame, read when the kernel runs (RsTensorCall::d_origin); the tables are the full axes'
 constexpr int kRsCrops = 16;
+// + kRsPlanar: the source is planar (RsSource::planar), staged through a byte transpose; with bytes out TENSOR is kRsPlanar alone
+constexpr int kRsPlanar = 32;
+// + kRsRowShift: LANCZOS_RESIZE_ALPHA over pitched interleaved rows whose pitch is no dword multiple: the staging shifts by the
+// residue of each row.  As for kRsPlanar, bytes out is the flag alone and a tensor request runs the mapped instance
+constexpr int kRsRowShift = 64;
 template <int BPS, int TENSOR>
 hipError_t rs_launch_fused(const RsFusedLaunch& c);
 

@@ -10,7 +10,9 @@
 //                   (8-bit, 16-bit elements out through a table: TENSOR = 2), lanczos_resize_tensor_view.hip and
 //                   lanczos_resize_tensor16_view.hip (the same two through a channel map and flips: TENSOR + kRsMapped),
 //                   lanczos_resize_tensor_crops.hip and lanczos_resize_tensor16_crops.hip (those with a crop origin per frame:
-//                   TENSOR + kRsMapped + kRsCrops), lanczos_resize16.hip and lanczos_resize32.hip.
+//                   TENSOR + kRsMapped + kRsCrops), lanczos_resize_source.hip, lanczos_resize_source_tensor.hip and
+//                   lanczos_resize_source_tensor16.hip (8-bit from a planar source: TENSOR with kRsPlanar, and ALPHA over rows
+//                   pitched off a dword: with kRsRowShift), lanczos_resize16.hip and lanczos_resize32.hip.
 #pragma once
 #include "lanczos_alpha.hpp"
 #include "lanczos_resize.hpp"
@@ -173,11 +175,44 @@ struct RsFusedTensorCrops : RsFusedTensorMap {
                                // kernel runs and clamped to [0, max_x0] x [0, max_y0]
     int max_x0, max_y0;        // the full output's size less the window's
 };
+// ... + kRsPlanar: the source is planar.  in_pitch is then the pitch of a plane row; behind the fields of the instance without it
+template <class Base>
+struct RsFusedPlanar : Base {
+    int chan_stride;      // bytes between the planes of a frame
+    unsigned src_bytes;   // from the frame's first byte to the last one the layout names, below 2^31
+};
 // the argument of k_rs_fused<..., TENSOR> for coefficients KT
 template <int TENSOR, class KT>
-using RsFusedArgs = std::conditional_t<
+using RsFusedArgsPacked = std::conditional_t<
     (TENSOR & kRsCrops) != 0, RsFusedTensorCrops,
     std::conditional_t<(TENSOR & kRsMapped) != 0, RsFusedTensorMap, std::conditional_t<TENSOR != 0, RsFusedTensor, RsFused<KT>>>>;
+template <int TENSOR, class KT>
+using RsFusedArgs = std::conditional_t<(TENSOR & kRsPlanar) != 0, RsFusedPlanar<RsFusedArgsPacked<(TENSOR & ~kRsPlanar), KT>>,
+                                       RsFusedArgsPacked<(TENSOR & ~kRsRowShift), KT>>;
+
+// The byte transpose of the planar staging and of k_rs_pack_source: p[c] holds bytes x .. x + 3 of plane c, o[] the C dwords of
+// those four pixels interleaved.  v_perm_b32 picks byte sel[k] of the eight bytes {a : b} (b the low four) for result byte k
+template <int C>
+__device__ __forceinline__ void rs_interleave4(const uint32_t (&p)[C], uint32_t (&o)[C]) {
+    static_assert(C == 3 || C == 4, "three or four planes");
+    if constexpr (C == 4) {
+        const uint32_t lo01 = __builtin_amdgcn_perm(p[1], p[0], 0x05010400u), hi01 = __builtin_amdgcn_perm(p[1], p[0], 0x07030602u);
+        const uint32_t lo23 = __builtin_amdgcn_perm(p[3], p[2], 0x05010400u), hi23 = __builtin_amdgcn_perm(p[3], p[2], 0x07030602u);
+        o[0] = __builtin_amdgcn_perm(lo23, lo01, 0x05040100u), o[1] = __builtin_amdgcn_perm(lo23, lo01, 0x07060302u);
+        o[2] = __builtin_amdgcn_perm(hi23, hi01, 0x05040100u), o[3] = __builtin_amdgcn_perm(hi23, hi01, 0x07060302u);
+    } else {   // R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
+        o[0] = __builtin_amdgcn_perm(p[2], __builtin_amdgcn_perm(p[1], p[0], 0x010c0400u), 0x03040100u);
+        o[1] = __builtin_amdgcn_perm(p[2], __builtin_amdgcn_perm(p[1], p[0], 0x06020c05u), 0x03020500u);
+        o[2] = __builtin_amdgcn_perm(p[2], __builtin_amdgcn_perm(p[1], p[0], 0x0c07030cu), 0x07020106u);
+    }
+}
+// the range of a planar frame's buffer resource: from its base rounded down to a dword to the last byte the layout names
+template <bool PLANAR, class Args>
+__device__ __forceinline__ unsigned rs_planar_range(const Args& g, int delta) {
+    if constexpr (PLANAR) return ((unsigned)delta + g.src_bytes + 3u) & ~3u;
+    else return 0u;
+}
+constexpr int kRsPlanarBatch = 4;   // groups of four pixels a thread of the planar staging has in flight: up to 2 C loads each
 
 template <int C, int BPS>
 struct RsStrip {
@@ -219,16 +254,34 @@ struct RsStrip {
 // crop lies inside the full output -- device memory cannot be validated, and the tables end there -- and moves its six table
 // pointers by it: from there on it is the kernel of the window at that origin.  The plan is the largest over every origin
 // (rs_fused_plan_crops), so staging rows and ring hold whichever the frame has.
+//
+// TENSOR with kRsPlanar (a planar source, 8-bit, C = 3 or 4; instances of their own once more, lanczos_resize_source*.hip): only
+// the staging loads differ.  A thread takes four pixels of a staged row: one dword from each of the C plane rows, transposed into
+// C interleaved dwords (rs_interleave4) and written to LDS as dwords.  A plane row starts at any byte, another residue per plane
+// and per row where the strides are odd, so each of those dwords is put together from the two aligned ones around it
+// (v_alignbyte, the second loaded only where the residue is not 0).  The staged rows then hold interleaved pixels from the
+// strip's first one on, premultiplied for ALPHA, and the horizontal pass reads its window unshifted, as it does for ALPHA.
+// Loads go through a buffer resource over [frame base rounded down to a dword, last named byte rounded up to one): nothing
+// outside it is read, and whatever lies in the padding of a row is only ever multiplied by a zero coefficient.
+//
+// TENSOR with kRsRowShift (ALPHA over interleaved rows whose pitch is no dword multiple; instances beside the planar ones): the
+// ALPHA staging shifts every pixel by the residue of its own row instead of the frame's.
 template <class S, int C, int K, bool ALPHA = false, int TENSOR = 0>
 __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
     RsFusedArgs<TENSOR, typename S::coeff_t> g) {
-    constexpr int EB = TENSOR & ~(kRsMapped | kRsCrops);   // bytes of a stored element
+    constexpr int EB = TENSOR & ~(kRsMapped | kRsCrops | kRsPlanar | kRsRowShift);   // bytes of a stored element
+    constexpr bool PLANAR = (TENSOR & kRsPlanar) != 0;
+    constexpr bool ROWSHIFT = (TENSOR & kRsRowShift) != 0;
+    static_assert(!ROWSHIFT || (ALPHA && !PLANAR && !(TENSOR & kRsCrops)), "a shift per row: the ALPHA staging of pitched rows");
+    static_assert(!PLANAR || (S::BPS == 1 && C >= 3 && !(TENSOR & kRsCrops)), "planar sources: 8-bit, 3 or 4 channels, no crops");
+    constexpr bool kPixelStage = ALPHA || PLANAR;         // a staged row starts at the strip's first pixel, whatever the address
+    constexpr bool kNoShift = kPixelStage && C == 4;      // ... and a staged dword is a pixel: the horizontal pass shifts nothing
     constexpr bool MAPPED = (TENSOR & kRsMapped) != 0;
     constexpr bool CROPS = (TENSOR & kRsCrops) != 0;
     static_assert((EB == 0 && !MAPPED) || EB == 2 || EB == 4, "bytes, 16-bit elements or floats out");
     static_assert(!CROPS || MAPPED, "a crop origin per frame comes with the mapped epilogue");
     static_assert(!ALPHA || C == 4, "alpha is the fourth of four channels");
-    static_assert((!ALPHA && !TENSOR) || S::BPS == 1, "alpha and tensor output are 8-bit");
+    static_assert((!ALPHA && !EB) || S::BPS == 1, "alpha and tensor output are 8-bit");
     using acc_t = typename S::acc_t;
     using word_t = typename S::word_t;
     using St = RsStrip<C, S::BPS>;
@@ -272,10 +325,11 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
     const int delta = kDwordSamples ? 0 : (int)((uintptr_t)fin & 3);
     const __amdgpu_buffer_rsrc_t irsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint8_t*>(fin - delta), 0,
-        kDwordSamples ? (unsigned)(g.in_h * g.in_pitch) : (unsigned)((delta + g.in_h * g.in_pitch + 3) & ~3), 0x00020000);
+        PLANAR          ? rs_planar_range<PLANAR>(g, delta)
+        : kDwordSamples ? (unsigned)(g.in_h * g.in_pitch) : (unsigned)((delta + g.in_h * g.in_pitch + 3) & ~3), 0x00020000);
     uint8_t* fout = g.out + blockIdx.y * g.out_fs;
     unsigned out_bytes = (unsigned)(g.out_h * g.out_pitch);
-    if constexpr (TENSOR) out_bytes = g.extent_bytes;
+    if constexpr (EB != 0) out_bytes = g.extent_bytes;
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(fout, 0, out_bytes, 0x00020000);
     const bool out_aligned = (((uintptr_t)fout | (unsigned)g.out_pitch | (unsigned)(x0 * CB)) & 3) == 0;
     const int valid_bytes = sw * (kDwordSamples ? C : CB);   // of the strip's row; dwords where a sample is one
@@ -301,10 +355,59 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
             const int nr = min(g.stage_rows, need - hi);
             // kRsLoadBatch loads in flight per thread before the first LDS write (one HBM latency per batch, not per dword)
             const int total = nr * g.stage_dw;
+            if constexpr (PLANAR) {
+                // a unit is four pixels of a staged row, C dwords of it; ngr of them cover a row
+                const int ngr = (g.stage_dw + C - 1) / C;
+                const int units = nr * ngr;
+                const float inv_ngr = 1.0f / (float)ngr;
+                for (int u0 = tid; u0 < units; u0 += kRsPlanarBatch * kRsThreads) {
+                    uint32_t pl[kRsPlanarBatch][C];
+#pragma unroll
+                    for (int b = 0; b < kRsPlanarBatch; b++) {
+                        const int u = u0 + b * kRsThreads;
+                        int r = (int)((float)u * inv_ngr);   // u / ngr, corrected below (u < 2^20)
+                        r -= r * ngr > u;
+                        r += (r + 1) * ngr <= u;
+                        const int off0 = delta + (hi + r) * g.in_pitch + xs + 4 * (u - r * ngr);
+#pragma unroll
+                        for (int c = 0; c < C; c++) {
+                            const int off = off0 + c * g.chan_stride;
+#ifdef LZ_RS_PLANAR_BYTE_LOADS   // the A/B of the aligned loads: four byte loads per plane dword (DESIGN.md 4.5 has both numbers)
+                            uint32_t bytes = 0u;
+#pragma unroll
+                            for (int k = 0; k < 4; k++)
+                                bytes |= (u < units ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(irsrc, off + k, 0, 0) : 0u) << (8 * k);
+                            pl[b][c] = bytes;
+                            continue;
+#endif
+                            const unsigned sh = (unsigned)off & 3u;
+                            const uint32_t lo = u < units ? __builtin_amdgcn_raw_buffer_load_b32(irsrc, off & ~3, 0, 0) : 0u;
+                            const uint32_t up = sh != 0 && u < units ? __builtin_amdgcn_raw_buffer_load_b32(irsrc, (off & ~3) + 4, 0, 0) : 0u;
+                            pl[b][c] = __builtin_amdgcn_alignbyte(up, lo, sh);
+                        }
+                    }
+#pragma unroll
+                    for (int b = 0; b < kRsPlanarBatch; b++) {
+                        const int u = u0 + b * kRsThreads;
+                        if (u < units) {
+                            int r = (int)((float)u * inv_ngr);
+                            r -= r * ngr > u;
+                            r += (r + 1) * ngr <= u;
+                            const int d0 = (u - r * ngr) * C;   // the unit's first dword of its row
+                            uint32_t px[C];
+                            rs_interleave4<C>(pl[b], px);
+#pragma unroll
+                            for (int c = 0; c < C; c++)
+                                if (d0 + c < g.stage_dw) stage[r * g.stage_dw + d0 + c] = ALPHA ? rs_premul_px(px[c]) : px[c];
+                        }
+                    }
+                }
+            } else
             for (int u0 = tid; u0 < total; u0 += kRsLoadBatch * kRsThreads) {
                 uint32_t v[kRsLoadBatch];
                 uint32_t vn[ALPHA ? kRsLoadBatch : 1];   // ALPHA, delta != 0: the dword behind v[b], the rest of its pixel
                 (void)vn;
+                [[maybe_unused]] unsigned rsh[ROWSHIFT ? kRsLoadBatch : 1];   // ROWSHIFT: the residue of the load's row
 #pragma unroll
                 for (int b = 0; b < kRsLoadBatch; b++) {
                     const int u = u0 + b * kRsThreads;
@@ -317,15 +420,20 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
                     } else {
                         const int off = delta + (hi + r) * g.in_pitch + xs * CB;
                         at = (off & ~3) + 4 * (u - r * g.stage_dw);
+                        if constexpr (ROWSHIFT) rsh[b] = (unsigned)off & 3u;
                     }
                     v[b] = u < total ? __builtin_amdgcn_raw_buffer_load_b32(irsrc, at, 0, 0) : 0u;
-                    if constexpr (ALPHA)
+                    if constexpr (ROWSHIFT)
+                        vn[b] = rsh[b] != 0 && u < total ? __builtin_amdgcn_raw_buffer_load_b32(irsrc, at + 4, 0, 0) : 0u;
+                    else if constexpr (ALPHA)
                         vn[b] = delta != 0 && u < total ? __builtin_amdgcn_raw_buffer_load_b32(irsrc, at + 4, 0, 0) : 0u;
                 }
 #pragma unroll
                 for (int b = 0; b < kRsLoadBatch; b++)
                     if (u0 + b * kRsThreads < total) {
-                        if constexpr (ALPHA)
+                        if constexpr (ROWSHIFT)
+                            stage[u0 + b * kRsThreads] = rs_premul_px(__builtin_amdgcn_alignbyte(vn[b], v[b], rsh[b]));
+                        else if constexpr (ALPHA)
                             stage[u0 + b * kRsThreads] = rs_premul_px(__builtin_amdgcn_alignbyte(vn[b], v[b], (unsigned)delta));
                         else
                             stage[u0 + b * kRsThreads] = v[b];
@@ -347,12 +455,12 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
                         }
                     }
                 } else {
-                    const int pos = (ALPHA ? 0 : (delta + (hi + j) * g.in_pitch + xs * CB) & 3) + hoff;
+                    const int pos = (kPixelStage ? 0 : (delta + (hi + j) * g.in_pitch + xs * CB) & 3) + hoff;
                     const uint32_t* srow = stage + j * g.stage_dw + (pos >> 2);
-                    const unsigned sh = ALPHA ? 0u : pos & 3;   // ALPHA: the staged dwords are pixels
+                    const unsigned sh = kNoShift ? 0u : pos & 3;   // ALPHA: the staged dwords are pixels
                     uint32_t dw[NE + 1];
 #pragma unroll
-                    for (int t = 0; t <= NE; t++) dw[t] = !ALPHA || t < NE ? srow[t] : 0u;
+                    for (int t = 0; t <= NE; t++) dw[t] = !kNoShift || t < NE ? srow[t] : 0u;
 #pragma unroll
                     for (int t = 0; t < NE; t++) {
                         const uint32_t e = __builtin_amdgcn_alignbyte(dw[t + 1], dw[t], sh);
@@ -394,7 +502,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
                 if (++slot == g.ring_rows) slot = 0;
             }
             const int b0 = kDwordSamples ? dcol : dcol * 4;   // the lane's place in the strip's row, as valid_bytes counts
-            if constexpr (TENSOR) {
+            if constexpr (EB != 0) {
                 // the dword is put together with v_perm_b32, not with shifts: followed by the exchange below, the shifted form
                 // is compiled to v_ashr_pk_u8_i32, whose 16-bit result leaves the upper half of its register as it was while
                 // the code behind it takes that half for zero (seen on the device: bytes 2 and 3 with bits of a0 in them)
@@ -479,7 +587,7 @@ template <class KT>
 void rs_fill_fused(RsFused<KT>* g, const RsFusedLaunch& c) {
     const lanczos_resize_desc* d = c.d;
     const RsWindow& w = c.win;   // the kernel's output is the window: its tables start at the window's first outputs
-    g->in_pitch = d->in_w * d->channels * resize_bps(d);
+    g->in_pitch = c.src ? (int)c.src->row_stride : d->in_w * d->channels * resize_bps(d);   // below 2^31 (the plan)
     g->out_pitch = w.w * d->channels * resize_bps(d);
     g->in_h = d->in_h, g->out_w = w.w, g->out_h = w.h;
     g->in_fs = c.in_fs, g->out_fs = c.out_fs;
@@ -495,9 +603,16 @@ hipError_t rs_launch_fused(const RsFusedLaunch& c) {
     using S = RsSample<BPS>;
     const bool alpha = (c.d->reserved[0] & LANCZOS_RESIZE_ALPHA) != 0;
     const RsFusedPlan& fp = *c.fp;
+    constexpr bool PLANAR = (TENSOR & kRsPlanar) != 0;
     RsFusedArgs<TENSOR, typename S::coeff_t> g{};
     rs_fill_fused(&g, c);
-    if constexpr (TENSOR != 0) {
+    constexpr bool ROWSHIFT = (TENSOR & kRsRowShift) != 0;
+    if ((c.src && c.src->planar) != PLANAR) return hipErrorInvalidValue;
+    if constexpr (PLANAR) {
+        g.chan_stride = (int)c.src->chan_stride;
+        g.src_bytes = (unsigned)((c.d->channels - 1) * c.src->chan_stride + (c.d->in_h - 1) * c.src->row_stride + c.d->in_w);
+    }
+    if constexpr ((TENSOR & ~(kRsPlanar | kRsRowShift)) != 0) {
         g.lut = (const uint32_t*)c.tc->t.d_lut;
         g.cs = (int)c.tc->t.chan_stride, g.rs = (int)c.tc->t.row_stride, g.ps = (int)c.tc->t.pix_stride;   // extent below 2^31 bytes
         g.extent_bytes = (unsigned)c.tc->extent_bytes;
@@ -513,7 +628,9 @@ hipError_t rs_launch_fused(const RsFusedLaunch& c) {
         const dim3 grid(fp.strips * fp.chunks, nf);
         bool launched = false;
         rs_dispatch_instance(c.d->channels, fp.K, alpha, [&](auto ch, auto k, auto a) {
-            if constexpr (!decltype(a)::value || BPS == 1) {   // alpha is 8-bit only (resize_validate)
+            // alpha is 8-bit only (resize_validate); a planar source of one channel is the interleaved one
+            if constexpr ((!decltype(a)::value || BPS == 1) && (!PLANAR || decltype(ch)::value >= 3) &&
+                          (!ROWSHIFT || decltype(a)::value)) {
                 hipLaunchKernelGGL((k_rs_fused<S, decltype(ch)::value, decltype(k)::value, decltype(a)::value, TENSOR>), grid,
                                    dim3(kRsThreads), fp.lds, c.stream, g);
                 launched = true;
@@ -533,6 +650,12 @@ extern template hipError_t rs_launch_fused<1, 4 + kRsMapped>(const RsFusedLaunch
 extern template hipError_t rs_launch_fused<1, 2 + kRsMapped>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<1, 4 + kRsMapped + kRsCrops>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<1, 2 + kRsMapped + kRsCrops>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<1, kRsPlanar>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<1, 4 + kRsMapped + kRsPlanar>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<1, 2 + kRsMapped + kRsPlanar>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<1, kRsRowShift>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<1, 4 + kRsMapped + kRsRowShift>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<1, 2 + kRsMapped + kRsRowShift>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<2, 0>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<4, 0>(const RsFusedLaunch&);
 

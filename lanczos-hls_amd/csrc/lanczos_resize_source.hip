@@ -1,0 +1,150 @@
+// lanczos_resize_source.hip -- a source layout beside the descriptor (lanczos_resize_source, include/lanczos_hip.h): planar
+// (CHW) and row-pitched frames without a repack.  Here: the layout's validation, the planar instances of the fused kernel that
+// store bytes (k_rs_fused<RsSample<1>, C, K, ALPHA, kRsPlanar> for every tap-count bucket x C = 3, 4 and alpha; the kernel is
+// lanczos_resize_fused.hpp's and only its staging loads differ), and k_rs_pack_source, the streaming gather of the PACKED
+// route.  The planar instances that store tensor elements are lanczos_resize_source_tensor.hip's and
+// lanczos_resize_source_tensor16.hip's; the routes are chosen in lanczos_resize.hip (resize_inner).
+#include "lanczos_resize_fused.hpp"
+
+namespace lz {
+
+template hipError_t rs_launch_fused<1, kRsPlanar>(const RsFusedLaunch&);
+// ... and the ALPHA instances of pitched interleaved rows whose pitch is no dword multiple (kRsRowShift)
+template hipError_t rs_launch_fused<1, kRsRowShift>(const RsFusedLaunch&);
+
+int resize_source_resolve(const lanczos_resize_desc* d, const lanczos_resize_source* src, RsSource* s) {
+    const long long C = d->channels, B = resize_bps(d);
+    const long long tight_row = (long long)d->in_w * C * B;
+    *s = RsSource{false, true, (size_t)tight_row, (size_t)B, (size_t)(d->in_h * tight_row)};
+    if (!src) return LANCZOS_OK;
+    for (int32_t r : src->reserved)
+        if (r != 0) return LANCZOS_ERR_BAD_ARG;
+    const long long rs = src->row_stride, cs = src->chan_stride, ps = src->pix_stride;
+    if (rs < 1 || cs < 1 || ps < 1 || rs % B != 0) return LANCZOS_ERR_BAD_ARG;
+    // a plane of in_h pitched rows: what chan_stride has to clear.  rs * in_h stays far below 2^63 only for a sane pitch
+    if (rs > ((long long)1 << 40)) return LANCZOS_ERR_BAD_ARG;
+    const long long plane = (d->in_h - 1) * rs + (long long)d->in_w * B;
+    const bool planar_shape = ps == B && rs >= (long long)d->in_w * B && cs >= plane && cs <= ((long long)1 << 56);
+    if (ps == C * B && cs == B && rs >= tight_row) {   // interleaved; with one channel this is every planar source as well
+        s->row_stride = (size_t)rs, s->tight = rs == tight_row, s->extent = (size_t)(d->in_h * rs);
+        return LANCZOS_OK;
+    }
+    if (!planar_shape) return LANCZOS_ERR_BAD_ARG;
+    if (C == 1) {   // one plane: the interleaved shape, whatever chan_stride says
+        s->row_stride = (size_t)rs, s->tight = rs == tight_row, s->extent = (size_t)(d->in_h * rs);
+        return LANCZOS_OK;
+    }
+    if (B != 1) return LANCZOS_ERR_UNSUPPORTED;   // planar wide samples: frames * C one-channel frames for the plain entries
+    s->planar = true, s->tight = false;
+    s->row_stride = (size_t)rs, s->chan_stride = (size_t)cs, s->extent = (size_t)(C * cs);
+    return LANCZOS_OK;
+}
+
+// ---- k_rs_pack_source ------------------------------------------------------------------------------------------------
+//
+// The source of the PACKED route -> tightly packed interleaved frames in context scratch, whose base and frame stride are dword
+// multiples.  Every store is a dword of the packed frame; 64-bit addresses throughout (a frame may exceed 4 GiB), plain global
+// loads.  A source dword at any byte address is put together from the two aligned dwords around it (the second loaded only
+// where the residue is not 0): both hold bytes the layout names, so nothing outside [frame base rounded down to a dword, frame
+// end rounded up to one) is read.
+struct RsPack {
+    const uint8_t* in;
+    uint8_t* out;
+    unsigned long long in_fs, out_fs, row_stride, chan_stride;
+    unsigned long long frame_bytes;   // of a packed frame
+    unsigned w, row_bytes;            // pixels and bytes of a packed row
+    unsigned npix;                    // w * h (planar: below 2^32)
+};
+
+__device__ __forceinline__ uint32_t rs_load_dword_at(const uint8_t* p) {
+    const unsigned sh = (unsigned)((uintptr_t)p & 3);
+    const uint32_t* q = (const uint32_t*)(p - sh);
+    const uint32_t lo = q[0];
+    const uint32_t up = sh != 0 ? q[1] : 0u;
+    return __builtin_amdgcn_alignbyte(up, lo, sh);
+}
+
+// planar, C = 3 or 4: a thread takes pixels q0 .. q0 + 3 of the frame in raster order (q0 a multiple of 4, so its C dwords of the
+// packed frame are aligned).  Where the four lie in one row: a dword per plane and the byte transpose of the fused staging;
+// across a row end: byte loads
+template <int C>
+__global__ __launch_bounds__(256) void k_rs_pack_source(RsPack p) {
+    const unsigned long long g = (unsigned long long)blockIdx.x * 256 + threadIdx.x;
+    if (g * 4 >= p.npix) return;
+    const unsigned q0 = (unsigned)(g * 4);
+    const uint8_t* fin = p.in + blockIdx.y * p.in_fs;
+    uint32_t* dst = (uint32_t*)(p.out + blockIdx.y * p.out_fs + (unsigned long long)q0 * C);
+    const unsigned y = q0 / p.w, x = q0 - y * p.w;
+    uint32_t o[C];
+    if (x + 4 <= p.w) {
+        uint32_t pl[C];
+#pragma unroll
+        for (int c = 0; c < C; c++) pl[c] = rs_load_dword_at(fin + c * p.chan_stride + y * p.row_stride + x);
+        rs_interleave4<C>(pl, o);
+    } else {
+#pragma unroll
+        for (int c = 0; c < C; c++) o[c] = 0u;
+        unsigned yy = y, xx = x;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (q0 + i < p.npix) {
+#pragma unroll
+                for (int c = 0; c < C; c++) {
+                    const int j = i * C + c;
+                    o[j >> 2] |= (uint32_t)fin[c * p.chan_stride + yy * p.row_stride + xx] << (8 * (j & 3));
+                }
+            }
+            if (++xx == p.w) xx = 0, yy++;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < C; c++)
+        if ((unsigned long long)q0 * C + 4 * c < p.frame_bytes) dst[c] = o[c];
+}
+
+// interleaved, pitched rows: a thread per dword of the packed frame (any sample width: the bytes are only moved)
+__global__ __launch_bounds__(256) void k_rs_pack_source_rows(RsPack p) {
+    const unsigned long long at = ((unsigned long long)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (at >= p.frame_bytes) return;
+    const uint8_t* fin = p.in + blockIdx.y * p.in_fs;
+    const unsigned long long y = at / p.row_bytes;
+    const unsigned xb = (unsigned)(at - y * p.row_bytes);
+    uint32_t v = 0u;
+    if (xb + 4 <= p.row_bytes) {
+        v = rs_load_dword_at(fin + y * p.row_stride + xb);
+    } else {
+        unsigned long long yy = y;
+        unsigned xx = xb;
+#pragma unroll
+        for (int b = 0; b < 4; b++) {
+            if (at + b < p.frame_bytes) v |= (uint32_t)fin[yy * p.row_stride + xx] << (8 * b);
+            if (++xx == p.row_bytes) xx = 0, yy++;
+        }
+    }
+    *(uint32_t*)(p.out + blockIdx.y * p.out_fs + at) = v;
+}
+
+hipError_t rs_pack_source_launch(const uint8_t* in, size_t in_fs, const RsSource& s, uint8_t* out, size_t out_fs, int w, int h,
+                                 int C, int B, int frames, hipStream_t stream) {
+    RsPack p{};
+    p.in_fs = in_fs, p.out_fs = out_fs, p.row_stride = s.row_stride, p.chan_stride = s.chan_stride;
+    p.w = (unsigned)w, p.row_bytes = (unsigned)(w * C * B);
+    p.frame_bytes = (unsigned long long)p.row_bytes * h;
+    p.npix = (unsigned)w * (unsigned)h;
+    if (s.planar && (B != 1 || (C != 3 && C != 4))) return hipErrorInvalidValue;
+    const unsigned long long threads = s.planar ? ((unsigned long long)p.npix + 3) / 4 : (p.frame_bytes + 3) / 4;
+    for (int f0 = 0; f0 < frames; f0 += 65535) {
+        const int nf = std::min(65535, frames - f0);
+        p.in = in + (size_t)f0 * in_fs;
+        p.out = out + (size_t)f0 * out_fs;
+        const dim3 grid((unsigned)((threads + 255) / 256), nf);
+        if (!s.planar) hipLaunchKernelGGL(k_rs_pack_source_rows, grid, dim3(256), 0, stream, p);
+        else if (C == 3) hipLaunchKernelGGL(k_rs_pack_source<3>, grid, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL(k_rs_pack_source<4>, grid, dim3(256), 0, stream, p);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace lz

@@ -104,6 +104,20 @@ frames), random 224x224 crops, float32.  Routes:
                    kernels, the floor
 Frame 0 of crops, crops_converted and full_gather are compared bit for bit before timing; a last line gives the ratios.
 
+SRC1, SRC1h, SRCP and SRCW are source-layout workloads (lanczos_resize_source: planar or row-pitched frames read as they lie;
+--only SRC1,SRC1h,SRCP,SRCW; a build with the entry), RGB8.  SRC1: 32 planar frames of 3840x2160 -> 1920x1080, bytes out; SRC1h:
+the same to normalised bfloat16 CHW; SRCP: 256 planar frames of 500x375 -> 341x256, the centre 224x224 window, normalised float32
+CHW; SRCW: 32 interleaved frames of 1920x1080 whose rows are pitched to a multiple of 256 bytes -> 3840x2160, bytes out.  SRCA
+and SRCAh (--only SRCA,SRCAh): 256 interleaved RGBA frames of 500x375 with LANCZOS_RESIZE_ALPHA and rows of 2006 bytes (no dword
+multiple: every row another residue) -> 341x256, bytes out and normalised bfloat16 CHW.  Routes:
+  direct        the call under RESIZE_FUSED: the fused kernel stages the caller's planes or pitched rows itself
+  packed        the call under RESIZE_CONVERT: k_rs_pack_source into context scratch, then the request as it always ran
+  auto          the call under RESIZE_AUTO (the summary line names the route it took)
+  torch_repack  what the call replaces: torch's permute(0, 2, 3, 1).contiguous() (SRCW: the slice's .contiguous()) on the same
+                stream, then the call without a source
+  floor         the call without a source alone, on frames that are already packed
+Frame 0 of all five is compared bit for bit before timing; a last line gives the ratios.
+
 --pillow adds Pillow's single-core time of one frame of each workload (if Pillow imports; else "not available"); for U1 and
 U4 that is the time of one I;16 plane (a frame has three), for F1 and F4 that of one F plane.
 """
@@ -774,6 +788,97 @@ def run_crops(name, args, ctx, torch):
     torch.cuda.empty_cache()
 
 
+SOURCE_WORKLOADS = {   # name: (in_w, in_h, out_w, out_h, frames, planar, row alignment or -padding (bytes), crop (w, h) from the centre, tensor dtype or None, channels, alpha)
+    "SRC1": (3840, 2160, 1920, 1080, 32, True, 1, None, None, 3, False),
+    "SRC1h": (3840, 2160, 1920, 1080, 32, True, 1, None, "bfloat16", 3, False),
+    "SRCP": (500, 375, 341, 256, 256, True, 1, (224, 224), "float32", 3, False),
+    "SRCW": (1920, 1080, 3840, 2160, 32, False, 256, None, None, 3, False),
+    "SRCA": (500, 375, 341, 256, 256, False, -6, None, None, 4, True),      # RGBA rows of 2006 bytes: the row-shift ALPHA instances
+    "SRCAh": (500, 375, 341, 256, 256, False, -6, None, "bfloat16", 4, True),
+}
+
+
+def run_source(name, args, ctx, torch):
+    """A source layout (lanczos_resize_source) against what it replaces: direct (the kernel reads the planar or pitched frames),
+    packed (the same request under RESIZE_CONVERT: k_rs_pack_source first), torch_repack (permute(0, 2, 3, 1).contiguous(), or
+    the slice's .contiguous(), then the call without a source) and floor (that call alone on frames already packed).  RGB8;
+    tensors are normalised CHW."""
+    iw, ih, ow, oh, f, planar, align, crop, dtype, c, alpha = SOURCE_WORKLOADS[name]
+    window = L.center_window(ow, oh, *crop) if crop else None
+    w, h = (window[2], window[3]) if window else (ow, oh)
+    d = L.resize_desc(iw, ih, ow, oh, c, alpha=alpha)
+    win = L.resize_window(d, window) if window else None
+    pitch = iw * c - align if align < 0 else -(-iw * c // align) * align
+    src = L.resize_source(d, "planar") if planar else L.resize_source(d, "interleaved", row_stride=pitch)
+    L.resize_source_validate(d, src)
+    src_fb = iw * ih * c if planar else ih * pitch          # bytes of a frame as the caller holds it
+    in_fb = iw * ih * c
+    elem = {None: 1, "float32": 4, "bfloat16": 2}[dtype]
+    out_fb = w * h * c
+    sets = max(2, -(-2 * 256 * 2 ** 20 // (f * src_fb)) + 1)
+    gen = torch.Generator(device="cuda").manual_seed(11)
+    xs = [torch.randint(0, 256, (f * src_fb,), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(sets)]
+    # the same frames already packed, for the floor
+    if planar:
+        packed = [x.view(f, c, ih, iw).permute(0, 2, 3, 1).contiguous() for x in xs]
+    else:
+        packed = [x.view(f, ih, pitch)[:, :, :iw * c].contiguous() for x in xs]
+    odt = {None: torch.uint8, "float32": torch.float32, "bfloat16": torch.bfloat16}[dtype]
+    ys = [torch.empty(f * out_fb, dtype=odt, device="cuda") for _ in range(sets)]
+    bits = {1: (lambda y: y), 4: (lambda y: y.view(torch.int32)), 2: (lambda y: y.view(torch.int16))}[elem]
+    d_lut = None
+    if dtype:
+        lut = L.normalize_lut(c, (IMAGENET_MEAN + (0.5,))[:c], (IMAGENET_STD + (0.25,))[:c], dtype=dtype)
+        d_lut = torch.from_numpy(lut.view(np.int16) if elem == 2 else lut).cuda()
+    st = L.tensor_strides("chw", w, h, c)
+    s = torch.cuda.current_stream().cuda_stream
+    seen = {}
+
+    def call(x_ptr, y, source):
+        if dtype:
+            ctx.resize_tensor_device(d, x_ptr, y.data_ptr(), f, d_lut.data_ptr(), st, stream=s, dtype=dtype, window=win, source=source)
+        else:
+            ctx.resize_device(d, x_ptr, y.data_ptr(), f, stream=s, window=win, source=source)
+
+    def with_source(path):
+        def step(i):
+            ctx.resize_force(path)
+            call(xs[i % sets].data_ptr(), ys[i % sets], src)
+            seen[path] = ctx.last_source_route()
+            return bits(ys[i % sets][:out_fb])
+        return step
+
+    def torch_repack(i):
+        ctx.resize_force(L.RESIZE_AUTO)
+        x = xs[i % sets]
+        t = x.view(f, c, ih, iw).permute(0, 2, 3, 1).contiguous() if planar else x.view(f, ih, pitch)[:, :, :iw * c].contiguous()
+        call(t.data_ptr(), ys[i % sets], None)
+        return bits(ys[i % sets][:out_fb])
+
+    def floor(i):
+        ctx.resize_force(L.RESIZE_AUTO)
+        call(packed[i % sets].data_ptr(), ys[i % sets], None)
+        return bits(ys[i % sets][:out_fb])
+
+    routes = {"direct": with_source(L.RESIZE_FUSED), "packed": with_source(L.RESIZE_CONVERT), "auto": with_source(L.RESIZE_AUTO),
+              "torch_repack": torch_repack, "floor": floor}
+    inb = {rn: f * in_fb for rn in routes}
+    outb = {rn: elem * f * out_fb for rn in routes}
+    us = run_routes(name, f"{iw}x{ih}->{ow}x{oh} C{c}{' alpha' if alpha else ''} {'planar' if planar else f'rows pitched to {pitch}'}" +
+                    (f" window {window}" if window else "") + (f" chw {dtype}" if dtype else " bytes"), f, routes, inb, outb, args,
+                    ctx, torch, check=(("direct", "packed"), ("direct", "torch_repack"), ("direct", "floor"), ("direct", "auto")))
+    ctx.resize_force(L.RESIZE_AUTO)
+    if (seen[L.RESIZE_FUSED], seen[L.RESIZE_CONVERT]) != (L.SOURCE_DIRECT, L.SOURCE_PACKED):
+        raise SystemExit(f"{name}: routes {seen}")
+    print(json.dumps({"workload": name, "auto_route": {L.SOURCE_DIRECT: "direct", L.SOURCE_PACKED: "packed"}[seen[L.RESIZE_AUTO]],
+                      "direct_over_packed": round(us["direct"] / us["packed"], 3),
+                      "direct_over_torch_repack": round(us["direct"] / us["torch_repack"], 3),
+                      "packed_over_torch_repack": round(us["packed"] / us["torch_repack"], 3),
+                      "direct_over_floor": round(us["direct"] / us["floor"], 3), "measured": True}), flush=True)
+    del xs, ys, packed
+    torch.cuda.empty_cache()
+
+
 def run_gap(name, args, ctx, torch):
     iw, ih, ow, oh, c, a, f = WORKLOADS["W5"]
     in_fb, out_fb = iw * ih * c, ow * oh * c
@@ -871,6 +976,8 @@ def main():
             run_window(name, args, ctx, torch, parent)
         elif name in CROPS_WORKLOADS:
             run_crops(name, args, ctx, torch)
+        elif name in SOURCE_WORKLOADS:
+            run_source(name, args, ctx, torch)
         elif name in VIEW_WORKLOADS:
             run_view(name, args, ctx, torch)
         elif name in TENSOR_WORKLOADS:
