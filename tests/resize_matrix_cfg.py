@@ -1,0 +1,473 @@
+"""The resize dispatcher over the cross product of its options (tests/test_resize_matrix_cfg.py, tests/test_resize_matrix_gpu.py):
+the case generator, the legality rules and resize_inner's decision tree restated in plain Python, and the CPU reference of every
+case.  No GPU is needed to import this module or to compute an expected array.
+
+A case is one value of every dimension: the sample kind, the geometry, the filter, the options (box / reducing_gap), the window,
+the output (bytes or one of the tensor forms), the source layout and the forced path.  cases() is the full product; legality()
+sorts it into requests that run (None), requests an entry refuses (the LANCZOS_ERR_* code) and combinations that are no request
+at all (NA: no entry takes them, or the value names nothing of its own for that kind).  predict() says which kernels a legal case
+launches, written from the conditions of resize_device / resize_inner (csrc/lanczos_resize.hip) -- it asks the host planners
+(resize_window_plan_host, resize_crops_plan_host) for `fused`, `pass_h`, `pass_v` and `fx` / `fy` and hard-codes none of them.
+
+Nothing in the reference comes from the code under test: the full bytes of a (kind, geometry, filter, options) are
+resize_filters_model.resize's, and everything else is numpy indexing on them with the models of the window, the tensor view, the
+crops and the source layout.  The tables are resize_tensor_model.identity_lut / resize_tensor16_model.identity_lut16: every
+(output channel, byte) has a word of its own that names both."""
+import collections
+import functools
+import itertools
+
+import numpy as np
+
+import lanczos_hls_amd as L
+import patterns as P
+import resize_crops_model as RC
+import resize_filters_model as F
+import resize_source_model as SM
+import resize_tensor16_model as T16
+import resize_tensor_model as T32
+import resize_tensor_view_model as V
+
+FRAMES = 3
+GUARD = 64          # sentinel elements in front of the first output frame and behind the last
+FRAME_GAP = 7       # sentinel elements between two output frames
+SENTINEL = 0xA5     # every byte of it
+NA = "n/a"
+
+Kind = collections.namedtuple("Kind", "channels bps alpha dtype")
+KINDS = collections.OrderedDict([
+    ("u8x1", Kind(1, 1, False, np.uint8)), ("u8x3", Kind(3, 1, False, np.uint8)), ("u8x4", Kind(4, 1, False, np.uint8)),
+    ("rgba", Kind(4, 1, True, np.uint8)),
+    ("u16x1", Kind(1, 2, False, np.uint16)), ("u16x3", Kind(3, 2, False, np.uint16)), ("u16x4", Kind(4, 2, False, np.uint16)),
+    ("f32x1", Kind(1, 4, False, np.float32)), ("f32x3", Kind(3, 4, False, np.float32)), ("f32x4", Kind(4, 4, False, np.float32))])
+U8_KINDS = ("u8x1", "u8x3", "u8x4", "rgba")
+
+# name -> (in_w, in_h, out_w, out_h)
+GEOMETRIES = collections.OrderedDict([
+    ("down", (61, 47, 37, 29)), ("up", (37, 29, 61, 47)), ("wideK", (90, 40, 20, 17)), ("strips", (523, 37, 300, 21)),
+    ("h", (61, 47, 37, 47)), ("v", (61, 47, 61, 29)), ("none", (61, 47, 61, 47))])
+FILTERS = ("lanczos", "bicubic", "nearest")
+OPTIONS = ("none", "fbox", "ibox", "gap")
+WINDOWS = ("whole", "sub")
+SOURCES = ("none", "pitched", "planar")
+FORCES = (L.RESIZE_AUTO, L.RESIZE_FUSED, L.RESIZE_TWO_PASS, L.RESIZE_CONVERT)
+FORCE_NAMES = {L.RESIZE_AUTO: "AUTO", L.RESIZE_FUSED: "FUSED", L.RESIZE_TWO_PASS: "TWO_PASS", L.RESIZE_CONVERT: "CONVERT"}
+
+# elem: bytes of a stored element, 0 = the samples themselves.  mapped: a channel map (channel_map()), per-frame flips D_FLIP and
+# the uniform `flip` XORed with them.  layout: "chw", "hwc", or "chwp", CHW with padded rows and planes.  crop: a crop origin per
+# frame (ORIGINS), the frame being crop_size().  The issue's four outputs are bytes, f32, bf16map_* and bf16crop_*; bf16, f32map
+# and f32crop are here because three of the fifteen fused families (<1, 2>, <1, 4 + mapped>, <1, 4 + mapped + crops>) have no
+# other way in.
+Output = collections.namedtuple("Output", "elem mapped layout flip crop")
+OUTPUTS = collections.OrderedDict([
+    ("bytes", Output(0, False, None, 0, False)),
+    ("f32", Output(4, False, "chw", 0, False)),
+    ("bf16", Output(2, False, "hwc", 0, False)),
+    ("f32map", Output(4, True, "chwp", 3, False)),
+    ("bf16map_hwc", Output(2, True, "hwc", 1, False)),
+    ("bf16map_chwp", Output(2, True, "chwp", 2, False)),
+    ("f32crop", Output(4, True, "hwc", 2, True)),
+    ("bf16crop_hwc", Output(2, True, "hwc", 3, True)),
+    ("bf16crop_chwp", Output(2, True, "chwp", 1, True))])
+D_FLIP = (0, 1, 2)
+
+Case = collections.namedtuple("Case", "kind geo filt opt win out src force")
+
+
+def describe(case):
+    return "/".join(str(v) for v in case[:-1]) + "/" + FORCE_NAMES[case.force]
+
+
+def cases(kinds=None, geos=None):
+    """the full product, in the order the GPU test walks it: the forced path changes fastest, then the source"""
+    for k, g in itertools.product(kinds or KINDS, geos or GEOMETRIES):
+        for rest in itertools.product(FILTERS, OPTIONS, WINDOWS, OUTPUTS, SOURCES, FORCES):
+            yield Case(k, g, *rest)
+
+
+# ---- the arguments of a case ------------------------------------------------------------------------------------------
+
+def box_of(case):
+    """the source box: a fractional one; an integer one over the full extent of one axis, the idle one where there is one"""
+    iw, ih, _, _ = GEOMETRIES[case.geo]
+    if case.opt == "fbox":
+        return (1.25, 2.5, iw - 3.75, ih - 1.125)
+    if case.opt == "ibox":
+        return (0, 3, iw, ih - 3) if case.geo == "v" else (3, 0, iw - 3, ih)
+    return None
+
+
+def gap_of(case):
+    return 2.0 if case.opt == "gap" else None
+
+
+def _odd(n):
+    return n if n % 2 else n - 1
+
+
+def window_size(geo):
+    """(w, h) of the sub-window, both odd; on `strips` still wider than one strip of any kind (the widest is 256 columns)"""
+    _, _, ow, oh = GEOMETRIES[geo]
+    return (271 if geo == "strips" else _odd(ow - 6)), _odd(oh - 8)
+
+
+def window_of(case):
+    """(x0, y0, w, h) with an odd origin and an odd size, or None"""
+    return (3, 5) + window_size(case.geo) if case.win == "sub" else None
+
+
+def crop_size(geo):
+    return window_size(geo)
+
+
+def origins_of(geo):
+    """the far corner, one the kernels must clamp on both axes, one odd interior origin"""
+    _, _, ow, oh = GEOMETRIES[geo]
+    w, h = crop_size(geo)
+    assert ow - w >= 2 and oh - h >= 4
+    return np.array([(ow - w, oh - h), (ow, -3), (1, 3)], dtype=np.int32)
+
+
+def channel_map(channels):
+    """a map that reorders; of four channels it also drops one"""
+    return {1: (0,), 3: (2, 0, 1), 4: (2, 0, 3)}[channels]
+
+
+def out_channels(case):
+    c = KINDS[case.kind].channels
+    return channel_map(c) if OUTPUTS[case.out].mapped else tuple(range(c))
+
+
+def flips_of(case):
+    """the flip of every frame as the kernels see it: the uniform one XOR the frame's byte"""
+    o = OUTPUTS[case.out]
+    return [o.flip ^ f for f in D_FLIP] if o.mapped else [0] * FRAMES
+
+
+def frame_size(case):
+    """(w, h) of a stored frame"""
+    _, _, ow, oh = GEOMETRIES[case.geo]
+    if OUTPUTS[case.out].crop:
+        return crop_size(case.geo)
+    return window_size(case.geo) if case.win == "sub" else (ow, oh)
+
+
+def tensor_strides(case):
+    """(chan_stride, row_stride, pix_stride) in elements"""
+    w, h = frame_size(case)
+    oc = len(out_channels(case))
+    lay = OUTPUTS[case.out].layout
+    if lay == "chwp":
+        return h * (w + 3) + 5, w + 3, 1
+    return V.strides(lay, w, h, oc)
+
+
+def out_geometry(case):
+    """(element bytes, elements of a frame's extent, frame stride in elements, elements of the whole buffer)"""
+    k, o = KINDS[case.kind], OUTPUTS[case.out]
+    w, h = frame_size(case)
+    if o.elem:
+        item, n = o.elem, V.extent(w, h, len(out_channels(case)), tensor_strides(case))
+    else:
+        item, n = k.bps, w * h * k.channels
+    fs = n + FRAME_GAP
+    return item, n, fs, GUARD + (FRAMES - 1) * fs + n + GUARD
+
+
+def lut_of(case):
+    o = OUTPUTS[case.out]
+    oc = len(out_channels(case))
+    return T32.identity_lut(oc) if o.elem == 4 else T16.identity_lut16(oc)
+
+
+# ---- contents ---------------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def frames_of(kind, geo):
+    """[FRAMES][in_h][in_w][C]: noise and gradient noise with a seed per frame; float frames are unit noise with one inf, one NaN
+    and one denormal near the centre, inside the support of the sub-window"""
+    k = KINDS[kind]
+    iw, ih, _, _ = GEOMETRIES[geo]
+    seed = 1000 * list(KINDS).index(kind) + 10 * list(GEOMETRIES).index(geo)
+    if k.dtype == np.float32:
+        x = np.random.default_rng(seed).standard_normal((FRAMES, ih, iw, k.channels)).astype(np.float32)
+        for f in range(FRAMES):
+            cy, cx = ih // 2 + f, iw // 2 - f
+            x[f, cy, cx, 0] = np.inf
+            x[f, cy - 5, cx + 7, k.channels - 1] = np.nan
+            x[f, cy + 4, cx - 6, 0] = np.float32(1e-41)
+    elif k.dtype == np.uint16:
+        x = np.stack([P.noise(ih, iw, k.channels, seed=seed + f, dtype=np.uint16) for f in range(FRAMES)])
+    else:
+        x = np.stack([(P.gradient_noise if f == 1 else P.noise)(ih, iw, k.channels, seed=seed + f) for f in range(FRAMES)])
+    x = np.ascontiguousarray(x)
+    x.setflags(write=False)
+    return x
+
+
+def source_of(kind, geo, src):
+    """the resize_source_model.Source of a layout, every byte it does not name noise.  pitched: rows 7 samples longer, the base 3
+    samples off a dword, the frame stride one sample past the extent (in bytes for 8-bit frames, where this is the row-shift
+    family of RGBA; wider samples keep their alignment).  planar: odd row and plane strides."""
+    k = KINDS[kind]
+    x = frames_of(kind, geo)
+    iw, ih, _, _ = GEOMETRIES[geo]
+    if src == "pitched":
+        rs = (iw * k.channels + 7) * k.bps
+        return SM.build(x, "interleaved", rs, base=(3 * k.bps) % 4, frame_stride=ih * rs + k.bps, seed=3)
+    assert src == "planar" and k.bps == 1 and k.channels > 1
+    rs = iw + 3 + (iw % 2)
+    cs = ih * rs + 1 + (ih * rs) % 2
+    assert rs % 2 and cs % 2
+    return SM.build(x, "planar", rs, cs, base=1, frame_stride=k.channels * cs + 1, seed=4)
+
+
+def source_struct(case, s=None):
+    """the ResizeSource of a case, written field by field (a refused layout has to reach the entry)"""
+    k = KINDS[case.kind]
+    iw, ih, _, _ = GEOMETRIES[case.geo]
+    r = L.ResizeSource()
+    if case.src == "pitched":
+        r.row_stride, r.chan_stride, r.pix_stride = s.row_stride if s else (iw * k.channels + 7) * k.bps, k.bps, k.channels * k.bps
+    else:
+        rs = s.row_stride if s else (iw + 3) * k.bps
+        r.row_stride, r.chan_stride, r.pix_stride = rs, s.chan_stride if s else ih * rs, k.bps
+    return r
+
+
+# ---- legality ---------------------------------------------------------------------------------------------------------
+
+def desc_of(case):
+    """the descriptor, its filter set without validation (a refused one has to reach the entry)"""
+    k = KINDS[case.kind]
+    iw, ih, ow, oh = GEOMETRIES[case.geo]
+    d = L.resize_desc(iw, ih, ow, oh, k.channels, 3, alpha=k.alpha, bits=16 if k.bps == 2 else 8, f32=k.bps == 4)
+    d.reserved[0] |= L.filter_code(case.filt) << 8
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def _plan(kind, geo, filt, opt, where):
+    """the host planners' answer for the whole output, the sub-window or the crop: (fused, pass_h, pass_v, reduces, K, strips,
+    chunks)"""
+    case = Case(kind, geo, filt, opt, "sub" if where == "sub" else "whole", "bytes", "none", L.RESIZE_AUTO)
+    d = desc_of(case)
+    if where == "crop":
+        p = L.resize_crops_plan_host(d, crop_size(geo), FRAMES, box=box_of(case), reducing_gap=gap_of(case))
+    else:
+        p = L.resize_window_plan_host(d, window_of(case), FRAMES, box=box_of(case), reducing_gap=gap_of(case))
+    return (bool(p.inner.fused), bool(p.pass_h), bool(p.pass_v), p.fx > 1 or p.fy > 1, p.inner.K, p.inner.strips, p.inner.chunks,
+            (p.fx, p.fy))
+
+
+Plan = collections.namedtuple("Plan", "fused pass_h pass_v reduces K strips chunks factors")
+
+
+def plan(case, where=None):
+    if where is None:
+        where = "crop" if OUTPUTS[case.out].crop else case.win
+    return Plan(*_plan(case.kind, case.geo, case.filt, case.opt, where))
+
+
+# The rules, in the order the entries apply them; the first that holds decides.  NA: no entry takes the combination, or the value
+# names nothing of its own there (one plane is a pitched source).
+RULES = (
+    ("a window together with crops is not a request", lambda c, k, o: o.crop and c.win != "whole", NA),
+    ("crops need a tensor output", lambda c, k, o: o.crop and not o.elem, NA),
+    ("a planar source needs 3 or 4 channels", lambda c, k, o: c.src == "planar" and k.channels == 1, NA),
+    ("nearest is refused for u16", lambda c, k, o: c.filt == "nearest" and k.bps == 2, L.ERR_UNSUPPORTED),
+    ("tensor outputs are 8-bit only", lambda c, k, o: o.elem and k.bps != 1, L.ERR_UNSUPPORTED),
+    ("planar sources are 8-bit only", lambda c, k, o: c.src == "planar" and k.bps != 1, L.ERR_UNSUPPORTED),
+    ("a gap is refused for alpha, u16, f32 and nearest",
+     lambda c, k, o: c.opt == "gap" and (k.alpha or k.bps != 1 or c.filt == "nearest"), L.ERR_BAD_ARG),
+    ("forced FUSED needs a plan", lambda c, k, o: c.force == L.RESIZE_FUSED and not plan(c).fused, L.ERR_UNSUPPORTED),
+)
+
+
+def legality(case):
+    """None: the case runs.  NA: it is no request.  Otherwise the code its entry returns."""
+    k, o = KINDS[case.kind], OUTPUTS[case.out]
+    for _, holds, verdict in RULES:
+        if holds(case, k, o):
+            return verdict
+    return None
+
+
+# ---- the dispatcher restated --------------------------------------------------------------------------------------------
+
+AUTO_PLANAR_DIRECT = True   # kRsPlanarAutoDirect: under AUTO the fused kernel reads planes as they lie
+Pred = collections.namedtuple("Pred", "main alpha reduce pack follower last_kernel tensor_route source_route")
+_FLAGS = ((8, "mapped"), (16, "crops"), (32, "planar"), (64, "rowshift"))
+
+
+def family(bps, tensor):
+    """the name of rs_launch_fused<bps, tensor>"""
+    return f"fused<{bps}, {' + '.join([str(tensor & 7)] + [n for b, n in _FLAGS if tensor & b])}>"
+
+
+FUSED_FAMILIES = tuple(family(b, t) for b, t in ((1, 0), (2, 0), (4, 0), (1, 4), (1, 2), (1, 12), (1, 10), (1, 28), (1, 26), (1, 32),
+                                                 (1, 44), (1, 42), (1, 64), (1, 76), (1, 74)))
+
+
+def predict(case):
+    """What a legal case launches: the main kernel (a fused family, nearest, copy, crop, pass_h_only, pass_v_only, two_pass, or
+    none where the crops gather reads the caller's frames), the alpha pass kernels with their `only`, whether k_reduce runs, the
+    pack kernel, the tensor follower, and the three values the context reports (source_route None: the call has no source and
+    leaves the last one)."""
+    k, o = KINDS[case.kind], OUTPUTS[case.out]
+    p = plan(case)
+    need_h, need_v = p.pass_h, p.pass_v
+    nearest = case.filt == "nearest" and (need_h or need_v)
+    force, tensor, crops = case.force, bool(o.elem), o.crop
+    pack_kernel = {"none": None, "pitched": "pack_rows", "planar": f"pack<{k.channels}>"}[case.src]
+    src, pack, route = (None if case.src == "none" else case.src), None, None
+    if src and p.reduces:                          # resize_device: the reduction reads packed frames
+        pack, route, src = pack_kernel, L.SOURCE_PACKED, None
+    had_source = src is not None
+    rowshift = src == "pitched" and k.alpha        # the pitch of source_of() is no dword multiple
+    if src and (force in (L.RESIZE_CONVERT, L.RESIZE_TWO_PASS) or (rowshift and crops) or
+                (src == "planar" and (crops or (force == L.RESIZE_AUTO and not AUTO_PLANAR_DIRECT)))):
+        src = None
+    fused_ok = p.fused and not nearest and need_h and need_v
+    assert not (force == L.RESIZE_FUSED and not fused_ok), "refused: legality() comes first"
+    fused = fused_ok and force != L.RESIZE_TWO_PASS
+    t_fused = tensor and fused and force != L.RESIZE_CONVERT
+    crops_gather = crops and not t_fused
+    if had_source:
+        if crops_gather or not fused:
+            src = None                             # the fused kernel alone reads a source as it lies
+        route = L.SOURCE_DIRECT if src else L.SOURCE_PACKED
+        if not src:
+            pack = pack_kernel
+    crops_direct = crops_gather and not nearest and not need_h and not need_v
+    whole = case.win == "whole"
+    if crops_gather:                               # the bytes of the whole output, by the plan of the whole output
+        whole = True
+        fused = plan(case, "whole").fused and not nearest and need_h and need_v and force != L.RESIZE_TWO_PASS
+    alpha = ()
+    if fused:
+        t = o.elem if t_fused else 0
+        if src == "planar":
+            t = (t + 8 if t else 0) + 32
+        elif src and rowshift:
+            t = (t + 8 if t else 0) + 64
+        elif t_fused and crops:
+            t += 8 + 16
+        elif t_fused and o.mapped:
+            t += 8
+        main, last = family(1 if (t or k.bps == 1) else k.bps, t), L.KERNEL_RESIZE_FUSED
+    elif nearest:
+        main, last = "nearest", L.KERNEL_RESIZE_NEAREST
+    elif not need_h and not need_v:
+        main, last = ("none" if crops_direct else "copy" if whole else "crop"), L.KERNEL_RESIZE_TWO_PASS
+    else:
+        main, last = ("two_pass" if need_h and need_v else "pass_h_only" if need_h else "pass_v_only"), L.KERNEL_RESIZE_TWO_PASS
+        if k.alpha:
+            alpha = tuple(f"{ax}_alpha<{'true' if only else 'false'}>" for ax, runs, only in
+                          (("h", need_h, not need_v), ("v", need_v, not need_h)) if runs)
+    follower = None
+    if tensor:
+        follower = ("crops_direct" if crops_direct else "crops_scratch" if crops_gather else
+                    None if t_fused else "to_tensor_map" if o.mapped else "to_tensor")
+    troute = 0 if not tensor else L.TENSOR_FUSED if t_fused else L.TENSOR_CONVERTED
+    return Pred(main, alpha, p.reduces, pack, follower, last, troute, route)
+
+
+MAINS = ("nearest", "copy", "crop", "pass_h_only", "pass_v_only", "two_pass", "none")
+ALPHA_LEAVES = ("h_alpha<true>", "h_alpha<false>", "v_alpha<true>", "v_alpha<false>")
+PACKS = ("pack<3>", "pack<4>", "pack_rows")
+FOLLOWERS = ("to_tensor", "to_tensor_map", "crops_scratch", "crops_direct")
+_WIDE = tuple(KINDS)
+_PLANAR = ("u8x3", "u8x4", "rgba")
+# leaf -> the kinds that can reach it (every one of them must)
+LEAVES = collections.OrderedDict(
+    [(family(1, 0), U8_KINDS), (family(2, 0), ("u16x1", "u16x3", "u16x4")), (family(4, 0), ("f32x1", "f32x3", "f32x4"))] +
+    [(family(1, t), U8_KINDS) for t in (4, 2, 12, 10, 28, 26)] +
+    [(family(1, t), _PLANAR) for t in (32, 44, 42)] + [(family(1, t), ("rgba",)) for t in (64, 76, 74)] +
+    [("nearest", tuple(n for n in KINDS if KINDS[n].bps != 2))] +
+    [(m, _WIDE) for m in ("copy", "crop", "pass_h_only", "pass_v_only", "two_pass")] + [("none", U8_KINDS)] +
+    [(a, ("rgba",)) for a in ALPHA_LEAVES] + [("reduce", ("u8x1", "u8x3", "u8x4"))] +
+    [("pack<3>", ("u8x3",)), ("pack<4>", ("u8x4", "rgba")), ("pack_rows", _WIDE)] + [(f, U8_KINDS) for f in FOLLOWERS])
+
+
+def leaves_of(pred):
+    """the names of LEAVES a prediction reaches"""
+    out = [pred.main] + list(pred.alpha)
+    if pred.reduce:
+        out.append("reduce")
+    if pred.pack:
+        out.append(pred.pack)
+    if pred.follower:
+        out.append(pred.follower)
+    return out
+
+
+# ---- the reference ----------------------------------------------------------------------------------------------------
+
+@functools.lru_cache(maxsize=None)
+def full_bytes(kind, geo, filt, opt):
+    """[FRAMES][out_h][out_w][C]: the whole output of every frame, by the numpy model of Pillow's resize"""
+    case = Case(kind, geo, filt, opt, "whole", "bytes", "none", L.RESIZE_AUTO)
+    _, _, ow, oh = GEOMETRIES[geo]
+    y = F.resize(frames_of(kind, geo), F.NAMES.index(filt), ow, oh, box_of(case), gap_of(case), a=3, alpha=KINDS[kind].alpha)
+    y = np.ascontiguousarray(y)
+    y.setflags(write=False)
+    return y
+
+
+def compose(full, window=None, crop=None, origins=None, lut=None, src=None, flips=None, strides=None, base=0,
+            frame_stride=None, out=None):
+    """The composition every expected array is made by, arguments spelled out (the fixture checks call it directly): the window
+    slice or the per-frame crops of `full`, then -- with a table -- the view's scatter into `out`, else the samples themselves."""
+    if crop is not None:
+        cut = RC.slices(full, crop[0], crop[1], origins)
+    elif window is not None:
+        x0, y0, w, h = window
+        cut = full[:, y0:y0 + h, x0:x0 + w]
+    else:
+        cut = full
+    if lut is None:
+        n = cut[0].size
+        for f in range(cut.shape[0]):
+            out[base + f * frame_stride:base + f * frame_stride + n] = np.ascontiguousarray(cut[f]).reshape(-1).view(out.dtype)
+        return cut.shape[0] * n
+    return V.scatter(out, base, cut, lut, src, flips, strides, frame_stride)
+
+
+@functools.lru_cache(maxsize=None)
+def _expected(kind, geo, filt, opt, win, out):
+    case = Case(kind, geo, filt, opt, win, out, "none", L.RESIZE_AUTO)
+    o = OUTPUTS[out]
+    item, n, fs, total = out_geometry(case)
+    want = np.full(total * item, SENTINEL, dtype=np.uint8).view({1: np.uint8, 2: np.uint16, 4: np.uint32}[item])
+    full = full_bytes(kind, geo, filt, opt)
+    w, h = frame_size(case)
+    if o.elem:
+        wrote = compose(full, window_of(case), crop_size(geo) if o.crop else None, origins_of(geo) if o.crop else None,
+                        lut_of(case), out_channels(case), flips_of(case), tensor_strides(case), GUARD, fs, want)
+        assert wrote == FRAMES * len(out_channels(case)) * w * h
+    else:
+        wrote = compose(full, window_of(case), base=GUARD, frame_stride=fs, out=want)
+        assert wrote == FRAMES * n
+    want.setflags(write=False)
+    return want
+
+
+def expected(case):
+    """the whole output buffer of a legal case as elements: sentinels in front, between the frames, behind, and at every element
+    of a tensor frame its strides do not name.  It depends on neither the source layout nor the forced path."""
+    return _expected(*case[:6])
+
+
+def first_difference(got, want, f32):
+    """None, or (index, got, want) of the first element that differs; float samples by the rule of resize32_model.same"""
+    if f32:
+        g, w = got.view(np.float32), want.view(np.float32)
+        gn, wn = np.isnan(g), np.isnan(w)
+        bad = (gn != wn) | (~gn & ~wn & (got != want))
+    else:
+        bad = got != want
+    if not bad.any():
+        return None
+    i = int(np.argmax(bad))
+    return i - GUARD, int(got[i]), int(want[i])

@@ -1,0 +1,286 @@
+"""CPU-only checks that keep tests/resize_matrix_cfg.py honest: its legality rules agree with the host validators both ways and
+with the error code, the planner facts the geometries were chosen for still hold, every leaf of the dispatcher is reached by a
+legal case of every kind that can reach it, and the composition that makes the expected arrays reproduces the committed Pillow
+fixtures.  No GPU needed."""
+import collections
+import ctypes
+import functools
+import importlib.util
+import os
+
+import numpy as np
+
+import lanczos_hls_amd as L
+import resize_filters_model as F
+import resize_matrix_cfg as M
+import resize_tensor16_model as T16
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+_DUMMY = (ctypes.c_int32 * 8)()   # a non-NULL, aligned address for the pointers the validators only test
+
+
+def _gen(name):
+    spec = importlib.util.spec_from_file_location(name, os.path.join(GOLDEN, name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def _view(case):
+    o = M.OUTPUTS[case.out]
+    return L.tensor_view(ctypes.addressof(_DUMMY), M.tensor_strides(case), o.elem, M.out_channels(case), o.flip if o.mapped else 0,
+                         ctypes.addressof(_DUMMY) if o.mapped else None)
+
+
+@functools.lru_cache(maxsize=None)
+def _validators(kind, geo, filt, opt, win, out, src):
+    """(the code of the first host validator that refuses, in the order the entries call them; the plan's `fused`)"""
+    case = M.Case(kind, geo, filt, opt, win, out, src, L.RESIZE_AUTO)
+    o = M.OUTPUTS[out]
+    lib, d = L._lib(), M.desc_of(case)
+    window = M.window_of(case)
+    rc = lib.lanczos_resize_validate(ctypes.byref(d))
+    if rc == L.OK and o.crop:
+        cr = L.resize_crops(*M.crop_size(geo), ctypes.addressof(_DUMMY))
+        rc = lib.lanczos_resize_crops_validate(ctypes.byref(d), ctypes.byref(cr))
+        if rc == L.OK:
+            rc = lib.lanczos_resize_tensor_crops_validate(ctypes.byref(d), ctypes.byref(cr), ctypes.byref(_view(case)))
+    elif rc == L.OK and o.elem:
+        wref = ctypes.byref(L.resize_window(d, window)) if window else None
+        rc = lib.lanczos_resize_tensor_view_validate(ctypes.byref(d), wref, ctypes.byref(_view(case)))
+        if not o.mapped:   # the plain tensor validators say the same
+            t = (L.tensor_out if o.elem == 4 else L.tensor16_out)(ctypes.addressof(_DUMMY), M.tensor_strides(case))
+            fn = {(4, False): lib.lanczos_resize_tensor_validate, (2, False): lib.lanczos_resize_tensor16_validate,
+                  (4, True): lib.lanczos_resize_tensor_window_validate, (2, True): lib.lanczos_resize_tensor16_window_validate}
+            args = (ctypes.byref(d), wref, ctypes.byref(t)) if window else (ctypes.byref(d), ctypes.byref(t))
+            assert fn[o.elem, bool(window)](*args) == rc, case
+    if rc == L.OK and src != "none":
+        rc = lib.lanczos_resize_source_validate(ctypes.byref(d), ctypes.byref(M.source_struct(case)))
+    fused = False
+    if rc == L.OK:
+        p = L.ResizePlanEx()
+        opts = L._opts_ref(d, M.box_of(case), M.gap_of(case), None)
+        if o.crop:
+            cr = L.resize_crops(*M.crop_size(geo), ctypes.addressof(_DUMMY))
+            rc = lib.lanczos_resize_crops_plan_host(ctypes.byref(d), opts, ctypes.byref(cr), M.FRAMES, ctypes.byref(p))
+        else:
+            wref = ctypes.byref(L.resize_window(d, window)) if window else None
+            rc = lib.lanczos_resize_window_plan_host(ctypes.byref(d), opts, wref, M.FRAMES, ctypes.byref(p))
+        fused = bool(p.inner.fused)
+    return rc, fused
+
+
+def test_the_legality_rules_are_the_validators():
+    """every case of the product that is a request: the rules refuse it exactly where a validator does, with its code"""
+    verdicts = collections.Counter()
+    for case in M.cases():
+        said = M.legality(case)
+        verdicts[said] += 1
+        if said == M.NA:
+            continue
+        rc, fused = _validators(*case[:7])
+        if rc == L.OK and case.force == L.RESIZE_FUSED and not fused:
+            rc = L.ERR_UNSUPPORTED
+        assert (said or L.OK) == rc, (M.describe(case), said, rc)
+    assert set(verdicts) == {None, M.NA, L.ERR_BAD_ARG, L.ERR_UNSUPPORTED}
+    assert verdicts[None] > 40000 and verdicts[L.ERR_UNSUPPORTED] > verdicts[L.ERR_BAD_ARG] > 1000, verdicts
+    # what NA stands for: one plane is a pitched source to the validator, and the Python entry refuses a window with crops
+    c = M.Case("u8x1", "down", "lanczos", "none", "whole", "bytes", "planar", L.RESIZE_AUTO)
+    d = M.desc_of(c)
+    s = L.ResizeSource()
+    s.row_stride, s.chan_stride, s.pix_stride = 64, 64 * 47, 1
+    assert M.legality(c) == M.NA and L._lib().lanczos_resize_source_validate(ctypes.byref(d), ctypes.byref(s)) == L.OK
+    assert M.legality(c._replace(out="f32crop", src="none", win="sub")) == M.NA
+
+
+def test_the_rules_name_each_reason():
+    """every rule decides at least one case of the product, except the one no value of the output dimension can break"""
+    hit = collections.Counter()
+    for case in M.cases():
+        k, o = M.KINDS[case.kind], M.OUTPUTS[case.out]
+        for name, holds, _ in M.RULES:
+            if holds(case, k, o):
+                hit[name] += 1
+                break
+    assert [n for n, _, _ in M.RULES if not hit[n]] == ["crops need a tensor output"], hit
+
+
+def _p(kind, geo, filt, opt="none", where="whole"):
+    return M.plan(M.Case(kind, geo, filt, opt, "whole", "bytes", "none", L.RESIZE_AUTO), where)
+
+
+def test_plan_facts():
+    """what the geometries were chosen for, asked of the planners: a planner change that empties a leaf fails here"""
+    for kind in M.KINDS:
+        for filt, ks in (("lanczos", (11, 7, 13)), ("bicubic", (9, 5, None))):
+            down, up, strips = (_p(kind, g, filt) for g in ("down", "up", "strips"))
+            assert down.fused and up.fused and strips.fused, (kind, filt)
+            assert down.K == ks[0] and up.K == ks[1] and up.chunks == 2, (kind, filt, down.K, up.K, up.chunks)
+            if ks[2]:
+                assert strips.K == ks[2], (kind, strips.K)
+            for g in ("down", "up", "strips"):      # the sub-window and the crop keep `fused`
+                assert _p(kind, g, filt, where="sub").fused and _p(kind, g, filt, where="crop").fused, (kind, g, filt)
+            for g in ("h", "v", "none"):
+                assert not _p(kind, g, filt).fused, (kind, g)
+            assert (_p(kind, "h", filt).pass_h, _p(kind, "h", filt).pass_v) == (True, False)
+            assert (_p(kind, "v", filt).pass_h, _p(kind, "v", filt).pass_v) == (False, True)
+            assert (_p(kind, "none", filt).pass_h, _p(kind, "none", filt).pass_v) == (False, False)
+            # the integer box keeps a one-axis request one-axis (and starts the axis of `none`); the fractional one runs both
+            assert (_p(kind, "h", filt, "ibox").pass_h, _p(kind, "h", filt, "ibox").pass_v) == (True, False)
+            assert (_p(kind, "v", filt, "ibox").pass_h, _p(kind, "v", filt, "ibox").pass_v) == (False, True)
+            assert (_p(kind, "none", filt, "ibox").pass_h, _p(kind, "none", filt, "ibox").pass_v) == (True, False)
+            for g in ("h", "v", "none"):
+                assert _p(kind, g, filt, "fbox").pass_h and _p(kind, g, filt, "fbox").pass_v, (kind, g)
+        assert not _p(kind, "wideK", "lanczos").fused and _p(kind, "wideK", "bicubic").fused and _p(kind, "wideK", "bicubic").K == 25
+        strips = {"u8x1": 2, "u8x3": 2, "u16x3": 3, "u8x4": 5, "rgba": 5, "u16x4": 5, "f32x3": 5, "f32x4": 5}
+        assert _p(kind, "strips", "lanczos").strips == strips.get(kind, 3), kind   # (one 16-bit or float channel: 128 columns)
+        assert _p(kind, "strips", "lanczos", where="sub").strips > 1, kind
+    for kind in ("u8x1", "u8x3", "u8x4"):           # the gap reduces wideK by 2 x 1, and what remains is fused
+        g = _p(kind, "wideK", "lanczos", "gap")
+        assert g.factors == (2, 1) and g.reduces and g.fused, (kind, g)
+        assert not _p(kind, "up", "lanczos", "gap").reduces
+    assert (3, 0, 58, 47) == M.box_of(M.Case("u8x3", "h", "lanczos", "ibox", "whole", "bytes", "none", 0))
+    # the sub-window: odd origin, odd size, inside the output; the origins: the far corner, one to clamp, one odd and inside
+    for geo, (_, _, ow, oh) in M.GEOMETRIES.items():
+        w, h = M.window_size(geo)
+        assert w % 2 and h % 2 and 3 + w <= ow and 5 + h <= oh, geo
+        org = M.origins_of(geo)
+        assert tuple(org[0]) == (ow - w, oh - h) and (org[1][0] > ow - w and org[1][1] < 0) and org[2][0] % 2 and org[2][1] % 2
+        assert 0 < org[2][0] < ow - w and 0 < org[2][1] < oh - h, geo
+    assert M.window_size("strips")[0] > 256
+
+
+def test_every_leaf_is_reached():
+    """every leaf of the written list by at least one legal case, and by every kind that can reach it -- and by no other"""
+    assert len(M.FUSED_FAMILIES) == len(set(M.FUSED_FAMILIES)) == 15
+    names = set(M.FUSED_FAMILIES) | set(M.MAINS) | set(M.ALPHA_LEAVES) | {"reduce"} | set(M.PACKS) | set(M.FOLLOWERS)
+    assert names == set(M.LEAVES) and len(M.MAINS) == 7 and len(M.PACKS) == 3 and len(M.FOLLOWERS) == 4
+    reached = collections.defaultdict(set)
+    reports = set()
+    for case in M.cases():
+        if M.legality(case) is None:
+            pred = M.predict(case)
+            for leaf in M.leaves_of(pred):
+                reached[leaf].add(case.kind)
+            reports.add((pred.last_kernel, pred.tensor_route, pred.source_route))
+    for leaf, kinds in M.LEAVES.items():
+        assert reached[leaf] == set(kinds), (leaf, sorted(reached[leaf]), sorted(kinds))
+    assert set(reached) == set(M.LEAVES)
+    assert {r[0] for r in reports} == {L.KERNEL_RESIZE_FUSED, L.KERNEL_RESIZE_TWO_PASS, L.KERNEL_RESIZE_NEAREST}
+    assert {r[1] for r in reports} == {0, L.TENSOR_FUSED, L.TENSOR_CONVERTED}
+    assert {r[2] for r in reports} == {None, L.SOURCE_DIRECT, L.SOURCE_PACKED}
+
+
+def test_the_dispatcher_cases_the_issue_names():
+    """the cases of resize_inner that are easy to get wrong, spelled out"""
+    c = M.Case("u8x3", "down", "lanczos", "none", "whole", "bytes", "pitched", L.RESIZE_AUTO)
+    assert M.predict(c)[:] == (M.family(1, 0), (), False, None, None, L.KERNEL_RESIZE_FUSED, 0, L.SOURCE_DIRECT)
+    for force in (L.RESIZE_CONVERT, L.RESIZE_TWO_PASS):   # both drop the source to PACKED, also for byte output
+        p = M.predict(c._replace(force=force))
+        assert (p.pack, p.source_route) == ("pack_rows", L.SOURCE_PACKED), force
+    assert M.predict(c._replace(force=L.RESIZE_CONVERT)).main == M.family(1, 0)
+    assert M.predict(c._replace(src="none")).source_route is None
+    p = M.predict(c._replace(src="planar", out="bf16crop_hwc"))                # planar with crops is PACKED
+    assert (p.main, p.pack, p.source_route) == (M.family(1, 26), "pack<3>", L.SOURCE_PACKED)
+    p = M.predict(c._replace(kind="rgba", out="bf16crop_hwc"))                 # ... and so is row-shift with crops
+    assert (p.main, p.pack, p.source_route) == (M.family(1, 26), "pack_rows", L.SOURCE_PACKED)
+    assert M.predict(c._replace(kind="rgba")).main == M.family(1, 64)
+    p = M.predict(c._replace(geo="wideK", opt="gap", src="planar"))            # a gap packs first and reduces from the packed frames
+    assert (p.reduce, p.pack, p.source_route, p.main) == (True, "pack<3>", L.SOURCE_PACKED, M.family(1, 0))
+    p = M.predict(c._replace(out="f32crop", force=L.RESIZE_CONVERT))           # crops_gather replans the whole output
+    assert (p.main, p.follower, p.tensor_route, p.source_route) == (M.family(1, 0), "crops_scratch", L.TENSOR_CONVERTED, L.SOURCE_PACKED)
+    p = M.predict(c._replace(geo="none", out="f32crop", src="none"))
+    assert (p.main, p.follower, p.last_kernel) == ("none", "crops_direct", L.KERNEL_RESIZE_TWO_PASS)
+    p = M.predict(c._replace(kind="rgba", geo="v", win="sub", out="bf16map_hwc", filt="bicubic"))
+    assert (p.main, p.alpha, p.pack, p.follower) == ("pass_v_only", ("v_alpha<true>",), "pack_rows", "to_tensor_map")
+    p = M.predict(c._replace(kind="f32x3", geo="v", win="sub", force=L.RESIZE_TWO_PASS))
+    assert (p.main, p.pack, p.source_route) == ("pass_v_only", "pack_rows", L.SOURCE_PACKED)
+
+
+def test_the_sources_name_what_the_issue_asks():
+    for kind, k in M.KINDS.items():
+        s = M.source_of(kind, "down", "pitched")
+        assert s.row_stride == (61 * k.channels + 7) * k.bps and s.at % 4 == (3 * k.bps) % 4 and s.frame_stride == s.extent + k.bps
+        assert np.array_equal(M.SM.unpack(s, M.frames_of(kind, "down").shape, k.dtype).view(np.uint8),
+                              M.frames_of(kind, "down").view(np.uint8))
+        assert M.source_struct(M.Case(kind, "down", "lanczos", "none", "whole", "bytes", "pitched", 0), s).row_stride == s.row_stride
+        if k.bps == 1 and k.channels > 1:
+            s = M.source_of(kind, "down", "planar")
+            assert s.row_stride % 2 and s.chan_stride % 2 and s.frame_stride > s.extent
+    assert M.source_of("rgba", "down", "pitched").row_stride % 4          # the row-shift family
+    x = M.frames_of("f32x3", "down")
+    assert np.isinf(x).sum() == np.isnan(x).sum() == M.FRAMES and ((x != 0) & (np.abs(x) < 1e-38)).sum() == M.FRAMES
+
+
+# ---- the composition against Pillow's fixtures ------------------------------------------------------------------------
+
+def _samples(cut_shape, dtype, full, **kw):
+    f = full.shape[0]
+    n = int(np.prod(cut_shape))
+    word = {1: np.uint8, 2: np.uint16, 4: np.uint32}[np.dtype(dtype).itemsize]
+    out = np.zeros(f * (n + 3), dtype=word)
+    assert M.compose(full, base=0, frame_stride=n + 3, out=out, **kw) == f * n
+    return np.stack([out[k * (n + 3):k * (n + 3) + n].view(dtype).reshape(cut_shape) for k in range(f)])
+
+
+def test_the_composition_reproduces_pillow():
+    """resize_pillow.npz and resize_pillow_alpha.npz (the whole output), resize_pillow_window.npz (the window) and
+    resize_pillow_crops.npz (crops, flips) for the filters the matrix uses: M.compose over the model's full bytes gives Pillow's"""
+    seen = 0
+    for fixture, alpha in (("resize_pillow.npz", False), ("resize_pillow_alpha.npz", True)):
+        z = np.load(os.path.join(GOLDEN, fixture))
+        for name in sorted(k[:-3] for k in z.files if k.endswith("_in")):
+            img, out = z[f"{name}_in"], z[f"{name}_out"]
+            img3, out3 = (img[..., None], out[..., None]) if img.ndim == 2 else (img, out)
+            full = F.resize(img3[None], F.LANCZOS, out3.shape[1], out3.shape[0], alpha=alpha)
+            assert np.array_equal(_samples(out3.shape, np.uint8, full)[0], out3), (fixture, name)
+            seen += 1
+    for name, (case, img, want) in _gen("make_resize_window_golden").load().items():
+        _, mode, filt, _, _, ow, oh, box, gap, window = case
+        if filt not in M.FILTERS:
+            continue
+        x = img[None, ..., None] if img.ndim == 2 else img[None]
+        full = F.resize(x, F.NAMES.index(filt), ow, oh, box, gap, alpha=mode == "RGBA")
+        w3 = want[..., None] if want.ndim == 2 else want
+        got = _samples(w3.shape, w3.dtype, full, window=window)[0]
+        assert F.same(got, w3), name
+        seen += 1
+    for name, (case, imgs, origins, flips, want) in _gen("make_resize_crops_golden").load().items():
+        _, mode, filt, _, _, ow, oh, box, gap, (w, h) = case
+        if filt not in M.FILTERS:
+            continue
+        x = imgs[..., None] if imgs.ndim == 3 else imgs
+        c = x.shape[-1]
+        full = F.resize(x, F.NAMES.index(filt), ow, oh, box, gap, alpha=mode == "RGBA")
+        st = M.V.strides("hwc", w, h, c)
+        n = M.V.extent(w, h, c, st)
+        out = np.zeros(len(x) * n, dtype=np.uint16)
+        assert M.compose(full, crop=(w, h), origins=origins, lut=T16.identity_lut16(c), src=tuple(range(c)), flips=flips, strides=st,
+                         base=0, frame_stride=n, out=out) == out.size
+        out = out.reshape(len(x), h, w, c)
+        assert np.array_equal(out >> 8, np.broadcast_to(np.arange(c, dtype=np.uint16), out.shape)), name
+        w4 = want[..., None] if want.ndim == 3 else want
+        assert np.array_equal((out & 255).astype(np.uint8), w4), name
+        seen += 1
+    assert seen >= 40, seen
+
+
+def test_expected_arrays_are_between_sentinels():
+    """the guard in front, the gap between the frames and the padding inside a padded tensor frame hold the sentinel"""
+    for out in M.OUTPUTS:
+        case = M.Case("rgba", "down", "bicubic", "fbox", "whole", out, "none", L.RESIZE_AUTO)
+        item, n, fs, total = M.out_geometry(case)
+        want = M.expected(case)
+        sent = int(np.full(1, M.SENTINEL, np.uint8).repeat(item).view(want.dtype)[0])
+        assert want.size == total and fs == n + 7 and (want[:M.GUARD] == sent).all() and (want[-M.GUARD:] == sent).all()
+        for f in range(M.FRAMES - 1):
+            assert (want[M.GUARD + f * fs + n:M.GUARD + (f + 1) * fs] == sent).all()
+        named = (want[M.GUARD:M.GUARD + n] != sent).sum()
+        w, h = M.frame_size(case)
+        if M.OUTPUTS[out].layout == "chwp":
+            assert named == len(M.out_channels(case)) * w * h < n
+        assert M.first_difference(want.copy(), want, False) is None
+        bad = want.copy()
+        bad[M.GUARD + 5] ^= 1
+        assert M.first_difference(bad, want, False)[0] == 5
