@@ -205,6 +205,14 @@ int lanczos_device_copy(int device, void* dst, const void* src, size_t bytes, in
  *   L(x) = sinc(x) sinc(x / a) on [-a, a), normalised to sum 1 and rounded to 22-bit fixed point (host, double);
  *   acc = 2^21 + sum(sample * coeff) in int32, result = clamp(acc >> 22, 0, 255).
  * The horizontal pass runs first into an 8-bit intermediate; a pass whose axis keeps its size is skipped (as Pillow does).
+ * The order is Pillow 12.2.0's (Image.resize), for every sample type, weighted filter and option below: where both passes
+ * run and the frame the resize reads -- the reduced one under a reducing_gap -- has in_h > 100 * in_w and out_h < in_h, the
+ * VERTICAL pass runs first, over the full width, into an intermediate of out_h rows stored in the same way, and the
+ * horizontal pass runs on that; with LANCZOS_RESIZE_ALPHA the first pass premultiplies and the last one divides alpha out,
+ * whichever axis it is.  Such a request never runs the fused kernel: lanczos_resize_plan_host and its _ex, window and crops
+ * forms report fused = 0, forced LANCZOS_RESIZE_FUSED is LANCZOS_ERR_UNSUPPORTED, lanczos_last_kernel reports
+ * LANCZOS_KERNEL_RESIZE_TWO_PASS, a tensor request takes LANCZOS_TENSOR_CONVERTED and a source layout LANCZOS_SOURCE_PACKED.
+ * Windows, tensor outputs, views, crops and sources stay slices and maps of that result.
  * Channels are independent: 8-bit interleaved samples, 1, 3 or 4 channels.  Four channels give Pillow's result on RGBX /
  * RGBa data.  With LANCZOS_RESIZE_ALPHA in the flag word they give Pillow's result in mode RGBA instead (channel 3 is
  * straight alpha), byte for byte, inside the same kernels -- no extra launch and no extra pass over memory:
@@ -395,7 +403,8 @@ int lanczos_resize_taps_f64_host_ex(const lanczos_resize_desc* d, const lanczos_
 /* Diagnostic: how a request with options resolves (the launch resolves with the same function).  fx = fy = 1: no reduction;
  * safe_box is then (0, 0, in_w, in_h), the reduced size the source's and inner_box the caller's box.  pass_h / pass_v: whether
  * the inner resize runs that pass.  mid_row0 / mid_rows: the rows of the (reduced) source the horizontal pass of the two-pass
- * path produces, which is what its scratch holds per frame (mid_rows x out_w pixels); 0 / 0 unless both passes run.  inner:
+ * path produces, which is what its scratch holds per frame (mid_rows x out_w pixels); 0 / 0 unless both passes run.  (A
+ * request that runs vertical first, see above, reads those source rows too, but its scratch holds out_h x reduced_w pixels.)  inner:
  * the plan of the inner resize, as lanczos_resize_plan_host reports it. */
 typedef struct lanczos_resize_plan_ex {
     int32_t fx, fy;

@@ -10,7 +10,9 @@
 //             ones are workgroup-uniform scalar loads.  This file compiles the 8-bit instances that store bytes.
 //   two-pass  k_rs_pass_h writes the intermediate (the rows the vertical taps read x out_w x C per frame) to context
 //             scratch, k_rs_pass_v reads it: any tap count, every sample width, all compiled here.  It also serves a resize
-//             that changes one axis only (one kernel) -- as Pillow, a pass whose axis keeps its size is skipped.
+//             that changes one axis only (one kernel) -- as Pillow, a pass whose axis keeps its size is skipped.  And it alone
+//             serves the frames Pillow resizes in the other order (rs_vertical_first: more than 100 times as tall as wide and
+//             shrinking in height): k_rs_pass_v first, over the full width, into scratch of out_h rows, then k_rs_pass_h.
 //
 // LANCZOS_RESIZE_ALPHA (four channels, Pillow's RGBA mode): both paths premultiply the colour samples by alpha where they
 // read the frame and divide alpha out where they write it (lanczos_alpha.hpp), the ALPHA instances of k_rs_fused and
@@ -347,6 +349,35 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_v_alpha(RsPass<int32_t> p) {
     rs_store_px(p.dst + blockIdx.z * p.dst_fs + o * p.dst_pitch + (size_t)x * 4, rs_unpremul_px(rs_clip_px(acc)));
 }
 
+// The other order (rs_vertical_first): the vertical pass runs first and premultiplies what it reads into an intermediate of
+// premultiplied pixels, the horizontal pass runs last and divides alpha out of what it writes.
+__global__ __launch_bounds__(kRsThreads) void k_rs_v_alpha_first(RsPass<int32_t> p) {
+    const int x = blockIdx.x * kRsThreads + threadIdx.x;   // pixel column
+    if (x * 4 >= p.n_cols) return;
+    const int o = blockIdx.y;
+    const int f = p.first[o], n = p.count[o];
+    const int32_t* k = p.coeffs + (size_t)o * p.ksize;
+    const uint8_t* src = p.src + blockIdx.z * p.src_fs + (size_t)f * p.src_pitch + (size_t)x * 4;
+    int acc[4] = {1 << (kResizePrecision - 1), 1 << (kResizePrecision - 1), 1 << (kResizePrecision - 1),
+                  1 << (kResizePrecision - 1)};
+#pragma unroll 4
+    for (int i = 0; i < n; i++) rs_mad_px(rs_premul_px(rs_load_px(src + (size_t)i * p.src_pitch)), k[i], acc);
+    rs_store_px(p.dst + blockIdx.z * p.dst_fs + o * p.dst_pitch + (size_t)x * 4, rs_clip_px(acc));
+}
+
+__global__ __launch_bounds__(kRsThreads) void k_rs_h_alpha_last(RsPass<int32_t> p) {
+    const int o = blockIdx.x * kRsThreads + threadIdx.x;   // output pixel of row blockIdx.y (n_cols counts samples)
+    if (o * 4 >= p.n_cols) return;
+    const int f = p.first[o], n = p.count[o];
+    const uint8_t* src = p.src + blockIdx.z * p.src_fs + blockIdx.y * p.src_pitch + (size_t)f * 4;
+    const int32_t* k = p.coeffs + (size_t)o * p.ksize;
+    int acc[4] = {1 << (kResizePrecision - 1), 1 << (kResizePrecision - 1), 1 << (kResizePrecision - 1),
+                  1 << (kResizePrecision - 1)};
+#pragma unroll 4
+    for (int i = 0; i < n; i++) rs_mad_px(rs_load_px(src + (size_t)i * 4), k[i], acc);
+    rs_store_px(p.dst + blockIdx.z * p.dst_fs + blockIdx.y * p.dst_pitch + (size_t)o * 4, rs_unpremul_px(rs_clip_px(acc)));
+}
+
 // the 8-bit instances of k_rs_fused that store bytes
 template hipError_t rs_launch_fused<1, 0>(const RsFusedLaunch&);
 
@@ -579,6 +610,7 @@ int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o,
         if (r.need_h) rs_mid_rows(rs_axis_view(V, w.y0, w.h), &out->mid_row0, &out->mid_rows);
     }
     if (!r.need_h || !r.need_v) return LANCZOS_OK;   // as resize_device: no table for an idle axis, nothing to fuse
+    if (rs_vertical_first(&r.inner, true, true)) return LANCZOS_OK;   // the pass kernels, vertical first: never fused
     if (!resize_build_axis(r.inner.in_w, r.inner.out_w, d->a, filter, r.h, &H, u16)) return LANCZOS_ERR_UNSUPPORTED;
     RsFusedPlan fp;
     if (crops ? !rs_fused_plan_crops(&r.inner, rs_axis_view(H, 0, H.out_n), rs_axis_view(V, 0, V.out_n), crops->w, crops->h, frames, &fp)
@@ -595,9 +627,10 @@ int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o,
 // One pass of the two-pass path over `rows` rows of `n_cols` samples of `bps` bytes; src / dst row pitches in samples, frame
 // strides in bytes.  alpha: the LANCZOS_RESIZE_ALPHA kernels (8-bit, a thread per pixel); `only`: the other pass does not run.
 // o0: the output of the axis the pass starts at (a window); the kernels count their outputs from it
+// v_first: both passes run, the vertical one first (rs_vertical_first); it only changes which alpha kernel a pass is
 static hipError_t rs_launch_pass(int bps, bool horizontal, const ResizeAxis* ax, int o0, int channels, const uint8_t* src, size_t src_fs,
                                  size_t src_pitch, uint8_t* dst, size_t dst_fs, size_t dst_pitch, int n_cols, int rows, int frames,
-                                 hipStream_t stream, bool alpha, bool only) {
+                                 hipStream_t stream, bool alpha, bool only, bool v_first = false) {
     if (alpha && bps != 1) return hipErrorInvalidValue;
     auto run = [&](auto sample) {
         using S = decltype(sample);
@@ -609,7 +642,8 @@ static hipError_t rs_launch_pass(int bps, bool horizontal, const ResizeAxis* ax,
         p.coeffs = ax->coeffs<typename S::coeff_t>() + (size_t)o0 * p.ksize;
         void (*kern)(RsPass<typename S::coeff_t>) = horizontal ? k_rs_pass_h<S> : k_rs_pass_v<S>;
         if constexpr (S::BPS == 1) {   // alpha is 8-bit only (checked above)
-            if (alpha && horizontal) kern = only ? k_rs_h_alpha<true> : k_rs_h_alpha<false>;
+            if (alpha && v_first) kern = horizontal ? k_rs_h_alpha_last : k_rs_v_alpha_first;
+            else if (alpha && horizontal) kern = only ? k_rs_h_alpha<true> : k_rs_h_alpha<false>;
             else if (alpha) kern = only ? k_rs_v_alpha<true> : k_rs_v_alpha<false>;
         }
         for (int f0 = 0; f0 < frames; f0 += 65535) {
@@ -674,6 +708,8 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     const int filter = resize_filter(d);
     // the gather reads both index tables, also that of an axis that keeps its size (the identity) -- unless both do
     const bool nearest = filter == LANCZOS_FILTER_NEAREST && (need_h || need_v);
+    // Pillow's order for a tall frame that shrinks: never the fused kernel, the pass kernels vertical first
+    const bool v_first = rs_vertical_first(d, need_h, need_v);
 
     ResizeAxis *H = nullptr, *V = nullptr;
     int rc;
@@ -696,7 +732,7 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
                 (src->planar && (crops || (st->force == LANCZOS_RESIZE_AUTO && !kRsPlanarAutoDirect)))))
         src = nullptr;
     auto plan = [&](size_t extent) {
-        return !nearest && need_h && need_v &&
+        return !nearest && need_h && need_v && !v_first &&
                (crops ? rs_fused_plan_crops(d, rs_axis_view(H->host, 0, d->out_w), rs_axis_view(V->host, 0, d->out_h), win.w, win.h,
                                             frames, &fp, extent)
                       : rs_fused_plan(d, rs_axis_view(H->host, win.x0, win.w), rs_axis_view(V->host, win.y0, win.h), frames, &fp,
@@ -721,7 +757,7 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     const bool crops_direct = crops_gather && !nearest && !need_h && !need_v;   // no pass runs: the caller's frames are the bytes
     if (crops_gather) {   // the bytes of the whole output, by the plan of the whole output
         win = RsWindow{0, 0, d->out_w, d->out_h};
-        fused_ok = !nearest && need_h && need_v &&
+        fused_ok = !nearest && need_h && need_v && !v_first &&
                    rs_fused_plan(d, rs_axis_view(H->host, 0, win.w), rs_axis_view(V->host, 0, win.h), frames, &fp);
         fused = fused_ok && st->force != LANCZOS_RESIZE_TWO_PASS;
     }
@@ -768,6 +804,21 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
         else
             e = rs_crop_launch(in + (size_t)win.y0 * in_pitch + (size_t)win.x0 * C * B, out, in_pitch, (size_t)win.w * C * B,
                                win.h, frames, in_fs, out_fs, stream);
+        *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
+    } else if (v_first) {
+        // The vertical pass turns the window's rows of the source's full width (Pillow's, and at most 655 pixels) into win.h
+        // rows of context scratch, stored as every intermediate is; the horizontal pass reads them through the window's slice
+        // of its table, whose `first` indexes that full width, and writes the output.
+        const int in_cols = d->in_w * C, out_cols = win.w * C;   // samples of a row
+        const size_t vmid_fs = (size_t)win.h * in_pitch;
+        rc = rs_scratch(st, &st->scratch, (size_t)frames * vmid_fs, stream, capturing, last_hip);
+        if (rc != LANCZOS_OK) return rc;
+        uint8_t* const vmid = (uint8_t*)st->scratch.p;
+        e = rs_launch_pass((int)B, false, V, win.y0, C, in, in_fs, in_cols, vmid, vmid_fs, in_cols, in_cols, win.h, frames, stream,
+                           alpha, false, true);
+        if (e == hipSuccess)
+            e = rs_launch_pass((int)B, true, H, win.x0, C, vmid, vmid_fs, in_cols, out, out_fs, out_cols, out_cols, win.h, frames,
+                               stream, alpha, false, true);
         *last_kernel = LANCZOS_KERNEL_RESIZE_TWO_PASS;
     } else {
         const int in_cols = d->in_w * C, out_cols = win.w * C;   // samples of a row

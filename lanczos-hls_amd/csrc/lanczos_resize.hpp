@@ -40,6 +40,13 @@ struct RsSpan {
 inline RsSpan rs_full_span(int in_n) { return RsSpan{0.0f, (float)in_n}; }
 // the pass rule: an axis runs its pass iff it changes size or its span is not the whole axis
 inline bool rs_axis_runs(int in_n, int out_n, RsSpan s) { return out_n != in_n || s.b0 != 0.0f || s.b1 != (float)in_n; }
+// The order rule, Pillow 12.2.0's Image.resize: a frame more than 100 times as tall as wide that shrinks in height runs the
+// vertical pass first, over the full width, and the horizontal pass on its result.  d is the request the resize runs on: the
+// reduced frame under a reducing_gap (RsResolved::inner).  It only matters where both passes run, and never for NEAREST
+inline bool rs_vertical_first(const lanczos_resize_desc* d, bool need_h, bool need_v) {
+    return need_h && need_v && LANCZOS_RESIZE_FILTER_OF(d->reserved[0]) != LANCZOS_FILTER_NEAREST && d->in_h > 100 * d->in_w &&
+           d->out_h < d->in_h;
+}
 // the filter of a request (LANCZOS_FILTER_*) and the support S of its weight function, which stands where Lanczos has a
 inline int resize_filter(const lanczos_resize_desc* d) { return LANCZOS_RESIZE_FILTER_OF(d->reserved[0]); }
 inline bool resize_nearest(const lanczos_resize_desc* d) { return resize_filter(d) == LANCZOS_FILTER_NEAREST; }

@@ -12,6 +12,8 @@ import math
 
 import numpy as np
 
+import resize_model as M
+
 
 def _filter(x, a):
     def sinc(v):
@@ -80,7 +82,7 @@ def pass_sums(x, axis, first, count, k):
     return np.moveaxis(out, 0, axis)
 
 
-def resize(img, out_w, out_h, a=3, saturate=False, stats=None):
+def resize(img, out_w, out_h, a=3, saturate=False, stats=None, order=None):
     """img: uint16 [H][W], [H][W][C] or [F][H][W][C] -> the resized image(s), same layout.  stats: an optional dict that
     receives the smallest and largest pre-store value met ("vmin", "vmax")."""
     img = np.asarray(img)
@@ -92,7 +94,9 @@ def resize(img, out_w, out_h, a=3, saturate=False, stats=None):
         x = x[None]
     in_h, in_w = x.shape[1], x.shape[2]
     y = x.astype(np.int64)
-    for axis, in_n, out_n in ((2, in_w, out_w), (1, in_h, out_h)):
+    sizes = {2: (in_w, out_w), 1: (in_h, out_h)}
+    for axis in M.pass_order(in_w, in_h, out_h, order):
+        in_n, out_n = sizes[axis]
         if in_n == out_n:
             continue
         f, c, k = axis_tables(in_n, out_n, a)

@@ -6,8 +6,8 @@ one pass is, per output sample,
     ss = 0.0; for i = 0 .. count - 1 ascending: ss = ss + (double)sample[first + i] * k[i]    (a multiply and an add)
     stored = (float)ss                                                                         (nearest even)
 with no clamp: a sum beyond FLT_MAX stores inf, a denormal stays a denormal, a tiny negative sum stores -0.0.  Exactly count
-taps are multiplied -- one whose weight is 0.0 too (inf * 0.0 = NaN), none outside the window.  The horizontal pass runs
-first into a float32 intermediate; a pass whose axis keeps its size with an idle box is skipped; no pass is a copy.
+taps are multiplied -- one whose weight is 0.0 too (inf * 0.0 = NaN), none outside the window.  The first pass (the
+horizontal one, unless resize_model.pillow_vertical_first) stores a float32 intermediate; a pass whose axis keeps its size with an idle box is skipped; no pass is a copy.
 numpy's float64 array arithmetic does not contract a multiply and an add, and does not flush denormals.
 
 The keyword switches of resize() are the near misses a fixture has to tell from the contract:
@@ -22,6 +22,7 @@ import numpy as np
 
 import resize16_model as M16
 import resize_box_model as MB
+import resize_model as M
 
 FUSED_K = (7, 9, 11, 13, 17, 25)
 FLT_MIN = np.float32(1.17549435e-38)
@@ -67,7 +68,8 @@ def one_pass(x, axis, first, count, k, acc32=False, flush=False, pad_to=None, sk
     return np.moveaxis(out, 0, axis)
 
 
-def resize(img, out_w, out_h, a=3, box=None, acc32=False, mid64=False, flush=False, pad_to=None, skip_zero_k=False):
+def resize(img, out_w, out_h, a=3, box=None, acc32=False, mid64=False, flush=False, pad_to=None, skip_zero_k=False,
+           order=None):
     """img: float32 [H][W], [H][W][C] or [F][H][W][C] -> the box (None = the whole frame) resized to out_h x out_w, same
     layout, every channel an independent plane."""
     img = np.asarray(img)
@@ -82,7 +84,9 @@ def resize(img, out_w, out_h, a=3, box=None, acc32=False, mid64=False, flush=Fal
     y = x
     ran = False
     with np.errstate(all="ignore"):
-        for axis, in_n, out_n, b0, b1 in ((2, in_w, out_w, x0, x1), (1, in_h, out_h, y0, y1)):
+        spans = {2: (in_w, out_w, x0, x1), 1: (in_h, out_h, y0, y1)}
+        for axis in M.pass_order(in_w, in_h, out_h, order):
+            in_n, out_n, b0, b1 = spans[axis]
             if not MB.axis_runs(in_n, out_n, b0, b1):
                 continue
             f, c, k = tables(in_n, out_n, a, b0, b1)

@@ -5,7 +5,8 @@ Written from the contract in include/lanczos_hip.h / DESIGN.md 4.5, not from the
 
   box     per axis (b0, b1): both rounded to float32, their difference taken in float32, scale = that / out in double,
           centre = b0f + (o + 0.5) * scale; first / count clipped to the whole source axis; the rest is resize_model's recipe.
-          A pass runs iff out != in or b0f != 0 or b1f != in.
+          A pass runs iff out != in or b0f != 0 or b1f != in.  Their order is resize_model.pass_order's, on the sizes of the
+          frame the resize reads (the reduced one under a gap).
   reduce  out = ((sum + d // 2) * (2^24 // d)) >> 24 in uint32, d = the source pixels the block really covers.
   gap     fx = int((x1 - x0) / out_w / g) or 1 (fy likewise) in double; safe box with s = a - 0.5; reduce over it; resize the
           reduced frame with the box shifted and divided (in double, float32 after).
@@ -89,7 +90,7 @@ def _like(img, y):
     return y
 
 
-def resize_box(img, out_w, out_h, box=None, a=3, alpha=False, float_box=True):
+def resize_box(img, out_w, out_h, box=None, a=3, alpha=False, float_box=True, order=None):
     """img: uint8 or uint16 [H][W], [H][W][C] or [F][H][W][C] -> the box resized to out_h x out_w, same layout.  alpha: the
     last of four channels is straight alpha (mode RGBA)."""
     x = _as4(img)
@@ -106,7 +107,9 @@ def resize_box(img, out_w, out_h, box=None, a=3, alpha=False, float_box=True):
         assert not u16 and x.shape[-1] == 4
         x = MA.premultiply(x)
     y = x.astype(np.int64)
-    for axis, run, in_n, out_n, b0, b1 in ((2, run_h, in_w, out_w, x0, x1), (1, run_v, in_h, out_h, y0, y1)):
+    spans = {2: (run_h, in_w, out_w, x0, x1), 1: (run_v, in_h, out_h, y0, y1)}
+    for axis in M.pass_order(in_w, in_h, out_h, order):
+        run, in_n, out_n, b0, b1 = spans[axis]
         if not run:
             continue
         f, c, k = axis_tables(in_n, out_n, a, b0, b1, f64=u16, float_box=float_box)
@@ -169,12 +172,12 @@ def gap_plan(in_w, in_h, out_w, out_h, box=None, gap=None, a=3):
     return fx, fy, rb, (rw, rh), inner
 
 
-def resize(img, out_w, out_h, box=None, reducing_gap=None, a=3, alpha=False):
+def resize(img, out_w, out_h, box=None, reducing_gap=None, a=3, alpha=False, order=None):
     """The whole call: Image.resize((out_w, out_h), LANCZOS, box, reducing_gap) on uint8 / uint16 frames."""
     x = _as4(img)
     in_h, in_w = x.shape[1], x.shape[2]
     fx, fy, rb, _, inner = gap_plan(in_w, in_h, out_w, out_h, box, reducing_gap, a)
     if fx == 1 and fy == 1:
-        return resize_box(img, out_w, out_h, box, a, alpha)
+        return resize_box(img, out_w, out_h, box, a, alpha, order=order)
     assert not alpha and x.dtype == np.uint8
-    return _like(img, resize_box(reduce(x, (fx, fy), rb), out_w, out_h, inner, a))
+    return _like(img, resize_box(reduce(x, (fx, fy), rb), out_w, out_h, inner, a, order=order))

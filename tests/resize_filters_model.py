@@ -16,6 +16,8 @@ The keyword switches are the near misses a fixture has to tell from the contract
     bicubic_a        another a of the bicubic (-0.75 is the other common one; Pillow's is -0.5)
     nearest_direct   idx[o] = int(b0f + (o + 0.5) * step) instead of the running sum
     nearest_premul   NEAREST on RGBA with the premultiply round trip of the weighted filters
+    order="h_first"  the horizontal pass first whatever the shape (Pillow runs a tall frame that shrinks vertical first:
+                     resize_model.pillow_vertical_first)
 """
 import math
 
@@ -144,7 +146,8 @@ def _resize_plain(x, filt, out_w, out_h, box, a, alpha, variant):
         y = src[:, iv][:, :, ih]
         return (MA.unpremultiply(y) if premul else y).astype(x.dtype)
     f32, u16 = x.dtype == np.float32, x.dtype == np.uint16
-    axes = ((2, run_h, in_w, out_w, x0, x1), (1, run_v, in_h, out_h, y0, y1))
+    spans = {2: (2, run_h, in_w, out_w, x0, x1), 1: (1, run_v, in_h, out_h, y0, y1)}
+    axes = [spans[axis] for axis in M.pass_order(in_w, in_h, out_h, variant.get("order"))]
     if f32:
         y = x
         with np.errstate(all="ignore"):

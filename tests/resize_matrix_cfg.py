@@ -45,7 +45,9 @@ U8_KINDS = ("u8x1", "u8x3", "u8x4", "rgba")
 # name -> (in_w, in_h, out_w, out_h)
 GEOMETRIES = collections.OrderedDict([
     ("down", (61, 47, 37, 29)), ("up", (37, 29, 61, 47)), ("wideK", (90, 40, 20, 17)), ("strips", (523, 37, 300, 21)),
-    ("h", (61, 47, 37, 47)), ("v", (61, 47, 61, 29)), ("none", (61, 47, 61, 47))])
+    ("h", (61, 47, 37, 47)), ("v", (61, 47, 61, 29)), ("none", (61, 47, 61, 47)),
+    # more than 100 times as tall as wide and shrinking in height: the pass kernels, vertical first (Pillow's order rule)
+    ("tall", (7, 750, 13, 77))])
 FILTERS = ("lanczos", "bicubic", "nearest")
 OPTIONS = ("none", "fbox", "ibox", "gap")
 WINDOWS = ("whole", "sub")
@@ -194,8 +196,8 @@ def frames_of(kind, geo):
         for f in range(FRAMES):
             cy, cx = ih // 2 + f, iw // 2 - f
             x[f, cy, cx, 0] = np.inf
-            x[f, cy - 5, cx + 7, k.channels - 1] = np.nan
-            x[f, cy + 4, cx - 6, 0] = np.float32(1e-41)
+            x[f, cy - 5, (cx + 7) % iw, k.channels - 1] = np.nan      # (the columns wrap on the 7 columns of `tall` alone)
+            x[f, cy + 4, (cx - 6) % iw, 0] = np.float32(1e-41)
     elif k.dtype == np.uint16:
         x = np.stack([P.noise(ih, iw, k.channels, seed=seed + f, dtype=np.uint16) for f in range(FRAMES)])
     else:
@@ -249,7 +251,7 @@ def desc_of(case):
 @functools.lru_cache(maxsize=None)
 def _plan(kind, geo, filt, opt, where):
     """the host planners' answer for the whole output, the sub-window or the crop: (fused, pass_h, pass_v, reduces, K, strips,
-    chunks)"""
+    chunks, factors, the size of the frame the resize reads)"""
     case = Case(kind, geo, filt, opt, "sub" if where == "sub" else "whole", "bytes", "none", L.RESIZE_AUTO)
     d = desc_of(case)
     if where == "crop":
@@ -257,10 +259,10 @@ def _plan(kind, geo, filt, opt, where):
     else:
         p = L.resize_window_plan_host(d, window_of(case), FRAMES, box=box_of(case), reducing_gap=gap_of(case))
     return (bool(p.inner.fused), bool(p.pass_h), bool(p.pass_v), p.fx > 1 or p.fy > 1, p.inner.K, p.inner.strips, p.inner.chunks,
-            (p.fx, p.fy))
+            (p.fx, p.fy), (p.reduced_w, p.reduced_h))
 
 
-Plan = collections.namedtuple("Plan", "fused pass_h pass_v reduces K strips chunks factors")
+Plan = collections.namedtuple("Plan", "fused pass_h pass_v reduces K strips chunks factors reduced")
 
 
 def plan(case, where=None):
@@ -310,8 +312,8 @@ FUSED_FAMILIES = tuple(family(b, t) for b, t in ((1, 0), (2, 0), (4, 0), (1, 4),
 
 
 def predict(case):
-    """What a legal case launches: the main kernel (a fused family, nearest, copy, crop, pass_h_only, pass_v_only, two_pass, or
-    none where the crops gather reads the caller's frames), the alpha pass kernels with their `only`, whether k_reduce runs, the
+    """What a legal case launches: the main kernel (a fused family, nearest, copy, crop, pass_h_only, pass_v_only, two_pass,
+    v_first -- the two passes in Pillow's order for a tall frame -- or none where the crops gather reads the caller's frames), the alpha pass kernels with their `only`, whether k_reduce runs, the
     pack kernel, the tensor follower, and the three values the context reports (source_route None: the call has no source and
     leaves the last one)."""
     k, o = KINDS[case.kind], OUTPUTS[case.out]
@@ -328,7 +330,11 @@ def predict(case):
     if src and (force in (L.RESIZE_CONVERT, L.RESIZE_TWO_PASS) or (rowshift and crops) or
                 (src == "planar" and (crops or (force == L.RESIZE_AUTO and not AUTO_PLANAR_DIRECT)))):
         src = None
-    fused_ok = p.fused and not nearest and need_h and need_v
+    # the order rule on the frame the resize reads (rs_vertical_first); the planners report fused = 0 for it
+    v_first = (need_h and need_v and case.filt != "nearest" and p.reduced[1] > 100 * p.reduced[0] and
+               GEOMETRIES[case.geo][3] < p.reduced[1])
+    assert not (v_first and p.fused)
+    fused_ok = p.fused and not nearest and need_h and need_v and not v_first
     assert not (force == L.RESIZE_FUSED and not fused_ok), "refused: legality() comes first"
     fused = fused_ok and force != L.RESIZE_TWO_PASS
     t_fused = tensor and fused and force != L.RESIZE_CONVERT
@@ -343,7 +349,8 @@ def predict(case):
     whole = case.win == "whole"
     if crops_gather:                               # the bytes of the whole output, by the plan of the whole output
         whole = True
-        fused = plan(case, "whole").fused and not nearest and need_h and need_v and force != L.RESIZE_TWO_PASS
+        fused = (plan(case, "whole").fused and not nearest and need_h and need_v and not v_first and
+                 force != L.RESIZE_TWO_PASS)
     alpha = ()
     if fused:
         t = o.elem if t_fused else 0
@@ -360,6 +367,10 @@ def predict(case):
         main, last = "nearest", L.KERNEL_RESIZE_NEAREST
     elif not need_h and not need_v:
         main, last = ("none" if crops_direct else "copy" if whole else "crop"), L.KERNEL_RESIZE_TWO_PASS
+    elif v_first:
+        main, last = "v_first", L.KERNEL_RESIZE_TWO_PASS
+        if k.alpha:
+            alpha = ("v_alpha_first", "h_alpha_last")
     else:
         main, last = ("two_pass" if need_h and need_v else "pass_h_only" if need_h else "pass_v_only"), L.KERNEL_RESIZE_TWO_PASS
         if k.alpha:
@@ -373,8 +384,8 @@ def predict(case):
     return Pred(main, alpha, p.reduces, pack, follower, last, troute, route)
 
 
-MAINS = ("nearest", "copy", "crop", "pass_h_only", "pass_v_only", "two_pass", "none")
-ALPHA_LEAVES = ("h_alpha<true>", "h_alpha<false>", "v_alpha<true>", "v_alpha<false>")
+MAINS = ("nearest", "copy", "crop", "pass_h_only", "pass_v_only", "two_pass", "v_first", "none")
+ALPHA_LEAVES = ("h_alpha<true>", "h_alpha<false>", "v_alpha<true>", "v_alpha<false>", "v_alpha_first", "h_alpha_last")
 PACKS = ("pack<3>", "pack<4>", "pack_rows")
 FOLLOWERS = ("to_tensor", "to_tensor_map", "crops_scratch", "crops_direct")
 _WIDE = tuple(KINDS)
@@ -385,7 +396,7 @@ LEAVES = collections.OrderedDict(
     [(family(1, t), U8_KINDS) for t in (4, 2, 12, 10, 28, 26)] +
     [(family(1, t), _PLANAR) for t in (32, 44, 42)] + [(family(1, t), ("rgba",)) for t in (64, 76, 74)] +
     [("nearest", tuple(n for n in KINDS if KINDS[n].bps != 2))] +
-    [(m, _WIDE) for m in ("copy", "crop", "pass_h_only", "pass_v_only", "two_pass")] + [("none", U8_KINDS)] +
+    [(m, _WIDE) for m in ("copy", "crop", "pass_h_only", "pass_v_only", "two_pass", "v_first")] + [("none", U8_KINDS)] +
     [(a, ("rgba",)) for a in ALPHA_LEAVES] + [("reduce", ("u8x1", "u8x3", "u8x4"))] +
     [("pack<3>", ("u8x3",)), ("pack<4>", ("u8x4", "rgba")), ("pack_rows", _WIDE)] + [(f, U8_KINDS) for f in FOLLOWERS])
 

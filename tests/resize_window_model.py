@@ -7,7 +7,7 @@ resize_filters_model.nearest_index), built for the whole axis.  The passes are t
 resize16_model.pass_sums + store, resize32_model.one_pass, resize_alpha_model.premultiply / unpremultiply), called with
 `first` shifted by the window's origin: int64 sums for 8-bit, one IEEE multiply and one IEEE add per tap in ascending order
 for the wide samples.  Horizontal first, into the intermediate Pillow stores, for the rows the chosen output rows read; then
-vertical.  An axis that keeps its size with an idle box is skipped (its chosen rows / columns are taken as they are), and a
+vertical -- or vertical first over the columns the chosen output columns read, where resize_model.pass_order says so.  An axis that keeps its size with an idle box is skipped (its chosen rows / columns are taken as they are), and a
 request that changes neither axis is a copy.
 
     fetch(y0, y1, x0, x1) -> ndarray [y1 - y0][x1 - x0][C] of the request's dtype: that rectangle of the source
@@ -91,8 +91,11 @@ def resize(fetch, in_w, in_h, out_w, out_h, channels, dtype, rows, cols, a=3, fi
         x = MA.premultiply(x)
     with np.errstate(all="ignore"):
         y = x if dtype == np.float32 else x.astype(np.int64)
-        y = _pass(y, 2, H, H.lo, dtype) if H.runs else gather_h(y)
-        y = _pass(y, 1, V, V.lo, dtype) if V.runs else gather_v(y)
+        for axis in M.pass_order(in_w, in_h, out_h):
+            if axis == 2:
+                y = _pass(y, 2, H, H.lo, dtype) if H.runs else gather_h(y)
+            else:
+                y = _pass(y, 1, V, V.lo, dtype) if V.runs else gather_v(y)
     y = y.astype(dtype)
     if alpha:
         y = MA.unpremultiply(y)

@@ -123,6 +123,12 @@ def test_plan_facts():
                 assert _p(kind, g, filt, where="sub").fused and _p(kind, g, filt, where="crop").fused, (kind, g, filt)
             for g in ("h", "v", "none"):
                 assert not _p(kind, g, filt).fused, (kind, g)
+            # `tall` runs both passes, vertical first: no fused plan for the whole output, the sub-window or the crop, with or
+            # without a box
+            for opt in ("none", "fbox", "ibox"):
+                for where in ("whole", "sub", "crop"):
+                    t = _p(kind, "tall", filt, opt, where)
+                    assert not t.fused and t.pass_h and t.pass_v and t.reduced == (7, 750), (kind, filt, opt, where)
             assert (_p(kind, "h", filt).pass_h, _p(kind, "h", filt).pass_v) == (True, False)
             assert (_p(kind, "v", filt).pass_h, _p(kind, "v", filt).pass_v) == (False, True)
             assert (_p(kind, "none", filt).pass_h, _p(kind, "none", filt).pass_v) == (False, False)
@@ -140,6 +146,8 @@ def test_plan_facts():
         g = _p(kind, "wideK", "lanczos", "gap")
         assert g.factors == (2, 1) and g.reduces and g.fused, (kind, g)
         assert not _p(kind, "up", "lanczos", "gap").reduces
+        t = _p(kind, "tall", "lanczos", "gap")      # ... and `tall` by 1 x 4 to 7 x 188, which is not tall and is fused
+        assert t.factors == (1, 4) and t.reduced == (7, 188) and t.fused, (kind, t)
     assert (3, 0, 58, 47) == M.box_of(M.Case("u8x3", "h", "lanczos", "ibox", "whole", "bytes", "none", 0))
     # the sub-window: odd origin, odd size, inside the output; the origins: the far corner, one to clamp, one odd and inside
     for geo, (_, _, ow, oh) in M.GEOMETRIES.items():
@@ -155,7 +163,7 @@ def test_every_leaf_is_reached():
     """every leaf of the written list by at least one legal case, and by every kind that can reach it -- and by no other"""
     assert len(M.FUSED_FAMILIES) == len(set(M.FUSED_FAMILIES)) == 15
     names = set(M.FUSED_FAMILIES) | set(M.MAINS) | set(M.ALPHA_LEAVES) | {"reduce"} | set(M.PACKS) | set(M.FOLLOWERS)
-    assert names == set(M.LEAVES) and len(M.MAINS) == 7 and len(M.PACKS) == 3 and len(M.FOLLOWERS) == 4
+    assert names == set(M.LEAVES) and len(M.MAINS) == 8 and len(M.PACKS) == 3 and len(M.FOLLOWERS) == 4
     reached = collections.defaultdict(set)
     reports = set()
     for case in M.cases():
@@ -196,6 +204,16 @@ def test_the_dispatcher_cases_the_issue_names():
     assert (p.main, p.alpha, p.pack, p.follower) == ("pass_v_only", ("v_alpha<true>",), "pack_rows", "to_tensor_map")
     p = M.predict(c._replace(kind="f32x3", geo="v", win="sub", force=L.RESIZE_TWO_PASS))
     assert (p.main, p.pack, p.source_route) == ("pass_v_only", "pack_rows", L.SOURCE_PACKED)
+    # a frame Pillow resizes vertical first: the pass kernels in that order, whatever else the request asks for
+    t = c._replace(geo="tall")
+    assert M.legality(t._replace(force=L.RESIZE_FUSED)) == L.ERR_UNSUPPORTED and M.legality(t) is None
+    assert M.predict(t._replace(kind="rgba"))[:] == ("v_first", ("v_alpha_first", "h_alpha_last"), False, "pack_rows", None,
+                                                     L.KERNEL_RESIZE_TWO_PASS, 0, L.SOURCE_PACKED)
+    assert M.predict(t._replace(src="planar", out="f32crop"))[:] == ("v_first", (), False, "pack<3>", "crops_scratch",
+                                                                     L.KERNEL_RESIZE_TWO_PASS, L.TENSOR_CONVERTED, L.SOURCE_PACKED)
+    assert M.predict(t._replace(src="none", win="sub", out="bf16map_hwc")).follower == "to_tensor_map"
+    assert M.predict(t._replace(src="none", filt="nearest")).main == "nearest"
+    assert M.predict(t._replace(src="none", opt="gap")).main == M.family(1, 0)     # reduced to 7 x 188, which is not tall
 
 
 def test_the_sources_name_what_the_issue_asks():

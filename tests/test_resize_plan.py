@@ -62,6 +62,8 @@ def two_pass_reasons(in_w, in_h, out_w, out_h, channels, a):
     reasons = []
     if in_w == out_w or in_h == out_h:
         return ["axis"]                       # one pass only (or a copy): nothing to fuse, and no table for that axis
+    if in_h > 100 * in_w and out_h < in_h:
+        reasons.append("order")               # Pillow runs such a frame vertical first: the pass kernels in that order
     if in_w * in_h * channels + 4 >= 2 ** 31 or out_w * out_h * channels >= 2 ** 31:
         reasons.append("bytes")               # 32-bit buffer offsets
     hf, hc, hks = tables(in_w, out_w, a)
@@ -138,19 +140,20 @@ def sweep_shapes():
 @pytest.mark.parametrize("a", [2, 3, 4])
 def test_plan_invariants_over_the_sweep(channels, a):
     """661 shapes (every SWEEP x SWEEP pair as the horizontal and as the vertical axis, and one frame of 2^31 bytes or more)
-    x frames in {1, 32}: 1322 plans per (channels, a).  How they plan (first reason that holds, in the order axis, bytes,
-    bucket, lds):
+    x frames in {1, 32}: 1322 plans per (channels, a).  How they plan (first reason that holds, in the order axis, order,
+    bytes, bucket, lds; `order` is a frame more than 100 times as tall as wide that shrinks in height, which runs the pass
+    kernels vertical first as Pillow does -- 1 x 160 .. 3840, 2 x 333 .. 3840, 3 x 333 .. 3840, ... in this sweep):
 
-        C a | fused  axis  bytes  bucket  lds
-        1 2 |   644   164      0     388  126
-        1 3 |   606   164      0     424  128
-        1 4 |   566   164      0     470  122
-        3 2 |   590   164      2     388  178
-        3 3 |   556   164      2     424  176
-        3 4 |   522   164      2     470  164
-        4 2 |   642   164      2     388  126
-        4 3 |   604   164      2     424  128
-        4 4 |   564   164      2     470  122
+        C a | fused  axis  order  bytes  bucket  lds
+        1 2 |   614   164     80      0     384   80
+        1 3 |   582   164     80      0     418   78
+        1 4 |   544   164     80      0     464   70
+        3 2 |   574   164     80      2     384  118
+        3 3 |   544   164     80      2     418  114
+        3 4 |   510   164     80      2     464  102
+        4 2 |   612   164     80      2     384   80
+        4 3 |   580   164     80      2     418   78
+        4 4 |   542   164     80      2     464   70
 
     (one channel: 65535 x 32768 stays below 2^31 bytes, so `bytes` does not occur there in this sweep.  It can occur: at
     65535 x 32769, which test_frames_at_the_2_gib_edge plans.)  Every outcome must occur, so that no branch of the planner
@@ -166,7 +169,7 @@ def test_plan_invariants_over_the_sweep(channels, a):
             r = check_plan(shape, channels, a, frames)
             counts[r] = counts.get(r, 0) + 1
     print(f"C={channels} a={a}: {counts}")
-    outcomes = {"fused", "axis", "bucket", "lds"} | ({"bytes"} if channels > 1 else set())
+    outcomes = {"fused", "axis", "order", "bucket", "lds"} | ({"bytes"} if channels > 1 else set())
     assert set(counts) == outcomes, counts
 
 

@@ -327,15 +327,18 @@ def test_output_frame_of_2_gib():
 
 
 def test_intermediate_of_2_gib_and_its_tensor():
-    """64 x 32769 -> 65535 x 8, one channel: the two-pass intermediate is 32769 rows of 65535 bytes, 2^31 + 32767 bytes of
+    """328 x 32769 -> 65535 x 8, one channel: the two-pass intermediate is 32769 rows of 65535 bytes, 2^31 + 32767 bytes of
     context scratch, which k_rs_pass_h writes and k_rs_pass_v reads above 2^31 (every output row's taps reach the last rows).
+    (328 columns, not fewer: a frame more than 100 times as tall as wide that shrinks in height runs vertical first, as Pillow
+    does, through an intermediate of 8 rows; 32769 <= 100 * 328 keeps this one horizontal first.)
     Compared: all 8 rows at the first, the middle and the last 64 columns and at 16 scattered columns (64 at first: cut down for
     the same reason as above); the other columns are not
     (the reference costs 32769 intermediate rows per column).  Then the same request through the tensor entry (identity table,
     CHW): the converted route, k_rs_to_tensor behind the two passes, on the same columns.  (The byte frame k_rs_to_tensor reads
     here is 512 KiB; one above 2^31 bytes would have a float frame of 8 GiB.)"""
     import torch
-    iw, ih, ow, oh = 64, 32769, 65535, 8
+    iw, ih, ow, oh = 328, 32769, 65535, 8
+    assert ih <= 100 * iw
     spec = ("u8c1", iw, ih, 1, {}, 1)
     p = L.resize_plan_host(L.resize_desc(iw, ih, ow, oh, 1), 1, box=(0, 0, iw, ih))
     assert not p.inner.fused and p.pass_h and p.pass_v and p.mid_rows * ow >= EDGE

@@ -12,7 +12,8 @@ import resize_window_model as W
 TYPES = {"u8c1": (np.uint8, 1, False), "u8c3": (np.uint8, 3, False), "u8c4": (np.uint8, 4, False),
          "rgba": (np.uint8, 4, True), "u16c3": (np.uint16, 3, False), "f32c3": (np.float32, 3, False)}
 # (in_w, in_h, out_w, out_h): both axes down, both up, mixed, one axis only (each way), neither
-SHAPES = [(120, 90, 37, 29), (40, 30, 117, 88), (117, 89, 61, 97), (119, 90, 119, 31), (120, 87, 43, 87), (64, 48, 64, 48)]
+SHAPES = [(120, 90, 37, 29), (40, 30, 117, 88), (117, 89, 61, 97), (119, 90, 119, 31), (120, 87, 43, 87), (64, 48, 64, 48),
+          (6, 640, 4, 77)]   # the last one runs vertical first (resize_model.pillow_vertical_first)
 
 
 def _frame(dtype, h, w, c, seed):
@@ -140,4 +141,4 @@ def test_the_wide_address_cases_stay_inside_their_frames():
             end, size = G.staged_end(spec, w, oh, corner_box(spec[1], spec[2]))
             assert end > size, (spec[0], w, end, size)
     check(("u8c1", 40, 30, 1, {}, 1), 65535, 32769, None)
-    check(("u8c1", 64, 32769, 1, {}, 1), 65535, 8, None)
+    check(("u8c1", 328, 32769, 1, {}, 1), 65535, 8, None)
