@@ -308,7 +308,8 @@ typedef struct lanczos_resize_desc {
                                       request whose float frame spans 2^31 bytes or more */
 #define LANCZOS_RESIZE_TWO_PASS 2
 #define LANCZOS_RESIZE_CONVERT 3   /* the resize as AUTO plans it; a source layout takes LANCZOS_SOURCE_PACKED (the A/B of the direct
-                                    * staging) and a tensor request takes the converted route (the A/B of the
+                                    * staging), a destination layout LANCZOS_DEST_UNPACKED (the A/B of the direct stores)
+                                    * and a tensor request takes the converted route (the A/B of the
                                       fused tensor epilogue); a byte request runs as under AUTO */
 
 /* host only, no GPU needed */
@@ -747,6 +748,64 @@ int lanczos_resize_tensor_source_host(lanczos_ctx* ctx, const lanczos_resize_des
                                       int frames);
 /* LANCZOS_SOURCE_DIRECT / LANCZOS_SOURCE_PACKED of the last call that had a source and returned LANCZOS_OK, 0 before any. */
 int lanczos_last_source_route(const lanczos_ctx* ctx);
+
+/* ---- resize into planar (CHW) and row-pitched destinations without a repack ----
+ * The byte, 16-bit-sample and float-sample entries above store `channels` interleaved samples with tightly packed rows.  A
+ * destination layout beside the descriptor says where the samples go instead, the mirror of lanczos_resize_source.  With (w, h)
+ * the window's extent (win NULL: the whole output), sample (y, x, c) of frame f goes to byte
+ *   f * out_frame_stride + c * chan_stride + y * row_stride + x * pix_stride
+ * of d_out (B = bytes per sample, C = channels).  Two shapes are accepted:
+ *   interleaved, pitched   pix_stride = C * B, chan_stride = B, row_stride >= w * C * B and a multiple of B.  Every sample type
+ *                          (8-bit, LANCZOS_RESIZE_ALPHA, _U16, _F32); floats keep their multiple-of-4 rule for base and strides,
+ *                          16-bit samples their multiple-of-2 rule.
+ *   planar                 pix_stride = 1, row_stride >= w, chan_stride >= (h - 1) * row_stride + w.  8-bit samples only,
+ *                          LANCZOS_RESIZE_ALPHA included; base, strides and frame stride may have any residue.  One channel,
+ *                          planar, is the interleaved shape.  Planar _U16 / _F32 is LANCZOS_ERR_UNSUPPORTED, for the reason the
+ *                          source gives: the caller already has frames * C one-channel frames.
+ * Everything else, and a non-zero reserved word, is LANCZOS_ERR_BAD_ARG.  out_frame_stride = 0 is the layout's own extent:
+ * h * row_stride (interleaved), C * chan_stride (planar); a non-zero stride below the last named byte + 1 is LANCZOS_ERR_BAD_ARG.
+ * dst NULL is exactly lanczos_resize_source_device; a tightly packed interleaved dst resolves to no destination, as a tight
+ * source does.
+ * THE CONTRACT: the named bytes are, byte for byte and word for word, what lanczos_resize_source_device stores for the same
+ * descriptor, options, window and source into a tightly packed interleaved frame.  EVERY BYTE THE LAYOUT DOES NOT NAME KEEPS ITS
+ * CONTENTS: row padding, plane padding, the gaps between frames and the bytes around the buffer.  The padding behind the last
+ * row need not be allocated.  Every dword store of the destination's own code goes to a dword-aligned address and covers named
+ * bytes only; the partial dwords at the ends of a row go out as bytes.
+ * Routes (lanczos_last_dest_route): LANCZOS_DEST_DIRECT, the resize kernel stored into the caller's layout itself -- the fused
+ * kernel, into pitched interleaved rows of every sample type (the pitch is an argument every instance already has) and into
+ * planes of 3 or 4 8-bit channels (planar-out instances of their own, lanczos_resize_dest*.hip), with a window and from an
+ * interleaved, pitched or planar source; a tightly packed interleaved destination is DIRECT on every route, being the call
+ * without one.  LANCZOS_DEST_UNPACKED, everything else: the two-pass kernels, one pass, LANCZOS_FILTER_NEAREST, the copies,
+ * reducing_gap, frames whose named span is 2^31 bytes or more, a planar destination from LANCZOS_RESIZE_ALPHA rows whose pitch
+ * is no multiple of 4, forced LANCZOS_RESIZE_TWO_PASS, and any destination that is not tightly packed under forced
+ * LANCZOS_RESIZE_CONVERT (the A/B of the direct stores).  The request then stores its tightly packed result in a scratch block of the context, and one streaming launch
+ * (k_rs_unpack_dest) scatters it.  The block lives as the other scratch of a context does.  There is no tensor form (a tensor
+ * view carries strides already), no channel map, no flips and no crop origins here. */
+typedef struct lanczos_resize_dest {
+    int64_t row_stride, chan_stride;   /* bytes */
+    int32_t pix_stride;                /* bytes */
+    int32_t reserved[3];               /* must be 0 */
+} lanczos_resize_dest;
+#define LANCZOS_DEST_INTERLEAVED 0
+#define LANCZOS_DEST_PLANAR 1
+#define LANCZOS_DEST_DIRECT 1     /* the resize kernel stored into the caller's layout itself */
+#define LANCZOS_DEST_UNPACKED 2   /* packed result in context scratch, then one scatter launch */
+/* Host only: the tight layout of that kind for the window's frame (win NULL: d's whole output). */
+int lanczos_resize_dest_init(lanczos_resize_dest* dst, const lanczos_resize_desc* d, const lanczos_resize_window* win, int layout);
+/* Host only.  NULL validates as the call without a destination does. */
+int lanczos_resize_dest_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_resize_dest* dst);
+/* lanczos_resize_source_device with a destination layout (dst NULL: exactly that call; src may be NULL). */
+int lanczos_resize_dest_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                               const lanczos_resize_window* win, const lanczos_resize_source* src, const lanczos_resize_dest* dst,
+                               const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride,
+                               void* stream);
+/* Host buffers; synchronous.  `out` holds `frames` frames the layout's own extent apart, the last one up to its last named byte;
+ * the bytes of `out` the layout does not name keep their contents. */
+int lanczos_resize_dest_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                             const lanczos_resize_window* win, const lanczos_resize_source* src, const lanczos_resize_dest* dst,
+                             const void* in, void* out, int frames);
+/* LANCZOS_DEST_DIRECT / LANCZOS_DEST_UNPACKED of the last call that had a destination and returned LANCZOS_OK, 0 before any. */
+int lanczos_last_dest_route(const lanczos_ctx* ctx);
 
 /* ---- reduce by whole factors (Pillow's Image.reduce((fx, fy), box), an exact integer box average) ----
  * 8-bit, 1, 3 or 4 independent interleaved channels.  box = (x0, y0, x1, y1), integers with 0 <= x0 < x1 <= in_w and the same

@@ -42,6 +42,8 @@ TENSOR_BF16, TENSOR_F16 = 1, 2          # the formats of lanczos_tensor_lut_conv
 _TENSOR16_FORMATS = {"bfloat16": TENSOR_BF16, "float16": TENSOR_F16}
 SOURCE_INTERLEAVED, SOURCE_PLANAR = 0, 1   # the layouts of lanczos_resize_source_init
 SOURCE_DIRECT, SOURCE_PACKED = 1, 2        # lanczos_last_source_route: who read the source of the last call that had one
+DEST_INTERLEAVED, DEST_PLANAR = 0, 1       # the layouts of lanczos_resize_dest_init
+DEST_DIRECT, DEST_UNPACKED = 1, 2          # lanczos_last_dest_route: who stored into the destination of the last call that had one
 
 # every symbol include/lanczos_hip.h declares (tests check the library exports exactly these)
 ABI_SYMBOLS = [
@@ -79,6 +81,8 @@ ABI_SYMBOLS = [
     "lanczos_resize_source_init", "lanczos_resize_source_validate", "lanczos_resize_source_device",
     "lanczos_resize_tensor_source_device", "lanczos_resize_source_host", "lanczos_resize_tensor_source_host",
     "lanczos_last_source_route",
+    "lanczos_resize_dest_init", "lanczos_resize_dest_validate", "lanczos_resize_dest_device", "lanczos_resize_dest_host",
+    "lanczos_last_dest_route",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
 
@@ -196,6 +200,13 @@ class ResizeCrops(ctypes.Structure):
 
 class ResizeSource(ctypes.Structure):
     """lanczos_resize_source -- where the samples of a source frame lie: sample (y, x, c) at byte c * chan_stride +
+    y * row_stride + x * pix_stride of its frame.  Interleaved with pitched rows, or planar (8-bit)."""
+    _fields_ = [("row_stride", ctypes.c_int64), ("chan_stride", ctypes.c_int64), ("pix_stride", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 3)]
+
+
+class ResizeDest(ctypes.Structure):
+    """lanczos_resize_dest -- where the samples of a result frame go: sample (y, x, c) to byte c * chan_stride +
     y * row_stride + x * pix_stride of its frame.  Interleaved with pitched rows, or planar (8-bit)."""
     _fields_ = [("row_stride", ctypes.c_int64), ("chan_stride", ctypes.c_int64), ("pix_stride", ctypes.c_int32),
                 ("reserved", ctypes.c_int32 * 3)]
@@ -361,6 +372,14 @@ def _lib():
             L.lanczos_resize_source_host.argtypes = [c_void_p, PRD, PRO, PRW, PRS, c_void_p, c_void_p, c_int]
             L.lanczos_resize_tensor_source_host.argtypes = [c_void_p, PRD, PRO, PRW, PRC, PRS, PTV, c_void_p, c_void_p, c_int]
             L.lanczos_last_source_route.argtypes = [c_void_p]
+        if hasattr(L, "lanczos_resize_dest_device"):   # (nor a destination layout)
+            PRT = ctypes.POINTER(ResizeDest)
+            L.lanczos_resize_dest_init.argtypes = [PRT, PRD, PRW, c_int]
+            L.lanczos_resize_dest_validate.argtypes = [PRD, PRW, PRT]
+            L.lanczos_resize_dest_device.argtypes = [c_void_p, PRD, PRO, PRW, PRS, PRT, c_void_p, c_void_p, c_int, c_size_t,
+                                                     c_size_t, c_void_p]
+            L.lanczos_resize_dest_host.argtypes = [c_void_p, PRD, PRO, PRW, PRS, PRT, c_void_p, c_void_p, c_int]
+            L.lanczos_last_dest_route.argtypes = [c_void_p]
         L.lanczos_strerror.restype = ctypes.c_char_p
         L.lanczos_version.argtypes = []
         L.lanczos_version.restype = ctypes.c_char_p
@@ -616,6 +635,33 @@ def resize_source_validate(desc, source):
     """lanczos_resize_source_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the layout is refused."""
     _check(_lib().lanczos_resize_source_validate(ctypes.byref(desc), ctypes.byref(source) if source is not None else None),
            "lanczos_resize_source_validate")
+
+
+def resize_dest(desc, layout="planar", row_stride=None, chan_stride=None, window=None):
+    """A ResizeDest for the result of `desc` (its window, where one is given): layout "planar" (N x C x H x W bytes, what a torch
+    stage takes) or "interleaved"; row_stride / chan_stride in bytes replace the tight layout's (pitched rows, padded planes).
+    Validated where it is used (resize_dest_validate); a ready ResizeDest is returned as it is."""
+    if isinstance(layout, ResizeDest):
+        return layout
+    kinds = {"interleaved": DEST_INTERLEAVED, "planar": DEST_PLANAR}
+    if layout not in kinds:
+        raise LanczosError(ERR_BAD_ARG, f"resize_dest: layout is 'planar' or 'interleaved', not {layout!r}")
+    t = ResizeDest()
+    _check(_lib().lanczos_resize_dest_init(ctypes.byref(t), ctypes.byref(desc), _window_ref(desc, window), kinds[layout]),
+           "lanczos_resize_dest_init")
+    if row_stride is not None:
+        if chan_stride is None and layout == "planar":   # the planes stay back to back
+            chan_stride = int(row_stride) * resize_window(desc, window).h
+        t.row_stride = int(row_stride)
+    if chan_stride is not None:
+        t.chan_stride = int(chan_stride)
+    return t
+
+
+def resize_dest_validate(desc, dest, window=None):
+    """lanczos_resize_dest_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the layout is refused."""
+    _check(_lib().lanczos_resize_dest_validate(ctypes.byref(desc), _window_ref(desc, window),
+                                               ctypes.byref(dest) if dest is not None else None), "lanczos_resize_dest_validate")
 
 
 def _planar_frames(img, what):
@@ -892,8 +938,11 @@ class Context:
 
     # -- resize to any size (Pillow's contract, lanczos_resize_*)
     def resize(self, img, out_w, out_h, a=3, alpha=False, box=None, reducing_gap=None, filter=FILTER_LANCZOS, window=None,
-               planar=False):
-        """planar=True: img is uint8 [C][H][W] or [F][C][H][W] (planes, as a decoder or a torch stage leaves them) and is read
+               planar=False, planar_out=False):
+        """planar_out=True (uint8, 3 or 4 channels): the result is planes, [C][h][w] or [F][C][h][w], stored that way by the
+        library (lanczos_resize_dest_host) -- the bytes of the same call without it moved to [C][h][w].  Combines with planar=True:
+        N x C x H x W in, N x C x h x w out.
+        planar=True: img is uint8 [C][H][W] or [F][C][H][W] (planes, as a decoder or a torch stage leaves them) and is read
         as it lies (lanczos_resize_source_host); the result is interleaved as ever, [h][w][C] or [F][h][w][C], the bytes of the
         same call on img moved to [H][W][C].
         window = (x0, y0, w, h) in output pixels: compute and return only that window of the out_h x out_w result, [h][w]
@@ -911,6 +960,25 @@ class Context:
         channels) by default, mode RGBA (straight alpha in the last channel, premultiplied inside the kernels) with
         alpha=True; alpha=True with any other channel count raises LanczosError(ERR_BAD_ARG).  uint16: every channel as
         Pillow resizes an I;16 plane (a sum above 65535 stores 0xFF00 | low byte, as Pillow does); not with alpha."""
+        if planar_out:
+            if planar:
+                x = _planar_frames(img, "resize")
+                f, c, h, w = x.shape
+            else:
+                x = np.ascontiguousarray(img)
+                if x.dtype != np.uint8 or x.ndim not in (3, 4) or x.shape[-1] not in (3, 4):
+                    raise LanczosError(ERR_BAD_ARG, "resize: planar_out=True takes uint8 frames of 3 or 4 channels")
+                x = x if x.ndim == 4 else x[None]
+                f, h, w, c = x.shape
+            d = resize_desc(w, h, out_w, out_h, c, a, alpha, filter=filter)
+            win = resize_window(d, window)
+            wref = ctypes.byref(win) if window is not None else None
+            out = np.empty((f, c, win.h, win.w), dtype=np.uint8)
+            _check(_lib().lanczos_resize_dest_host(self._h, ctypes.byref(d), _opts_ref(d, box, reducing_gap, None), wref,
+                                                   ctypes.byref(resize_source(d, "planar")) if planar else None,
+                                                   ctypes.byref(resize_dest(d, "planar", window=window)), x.ctypes.data,
+                                                   out.ctypes.data, f), "lanczos_resize_dest_host")
+            return out if np.ndim(img) == 4 else out[0]
         if planar:
             x = _planar_frames(img, "resize")
             f, c, h, w = x.shape
@@ -975,8 +1043,11 @@ class Context:
         return out if img.ndim == 4 else out[0]
 
     def resize_device(self, desc, d_in, d_out, frames, in_frame_stride=0, out_frame_stride=0, stream=None, box=None,
-                      reducing_gap=None, opts=None, filter=None, window=None, source=None):
-        """source: a ResizeSource (resize_source) saying where the samples of the frames at d_in lie -- planar, or interleaved
+                      reducing_gap=None, opts=None, filter=None, window=None, source=None, dest=None):
+        """dest: a ResizeDest (resize_dest) saying where the samples of the frames at d_out go -- planar, or interleaved with
+        pitched rows; out_frame_stride 0 is then that layout's extent, and every byte the layout does not name keeps its contents
+        (lanczos_resize_dest_device).
+        source: a ResizeSource (resize_source) saying where the samples of the frames at d_in lie -- planar, or interleaved
         with pitched rows; in_frame_stride 0 is then that layout's extent (lanczos_resize_source_device).
         Device pointers, asynchronous on `stream` (None = the default stream).  box / reducing_gap / opts as
         resize_taps_host.  The filter is the descriptor's (resize_desc(..., filter=)); filter= (a name or FILTER_*) runs
@@ -986,7 +1057,12 @@ class Context:
             d = ResizeDesc.from_buffer_copy(desc)
             d.reserved[0] = (d.reserved[0] & ~(15 << 8)) | (filter_code(filter) << 8)
             desc = d
-        if source is not None:
+        if dest is not None:
+            _check(_lib().lanczos_resize_dest_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
+                                                     _window_ref(desc, window), ctypes.byref(source) if source is not None else None,
+                                                     ctypes.byref(dest), d_in, d_out, frames, in_frame_stride, out_frame_stride,
+                                                     stream), "lanczos_resize_dest_device")
+        elif source is not None:
             _check(_lib().lanczos_resize_source_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
                                                        _window_ref(desc, window), ctypes.byref(source), d_in, d_out, frames,
                                                        in_frame_stride, out_frame_stride, stream), "lanczos_resize_source_device")
@@ -1207,6 +1283,11 @@ class Context:
         """TENSOR_FUSED (the resize kernel stored the floats), TENSOR_CONVERTED (bytes to scratch, then a conversion launch),
         or 0 if the last call on the context was no tensor call."""
         return _lib().lanczos_last_tensor_route(self._h)
+
+    def last_dest_route(self):
+        """DEST_DIRECT (the resize kernel stored into the destination itself), DEST_UNPACKED (the packed result went to context
+        scratch and one launch scattered it), of the last call on the context that had a destination layout; 0 before any."""
+        return _lib().lanczos_last_dest_route(self._h)
 
     def last_source_route(self):
         """SOURCE_DIRECT (the resize kernel read the source as it lies), SOURCE_PACKED (one launch gathered it tightly packed

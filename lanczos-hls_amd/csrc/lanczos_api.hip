@@ -69,6 +69,7 @@ struct lanczos_ctx {
     int last_kernel = LANCZOS_KERNEL_NONE;
     int last_tensor_route = 0;   // lanczos_last_tensor_route: LANCZOS_TENSOR_* of the last call, 0 unless it was a tensor call
     int last_source_route = 0;   // lanczos_last_source_route: LANCZOS_SOURCE_* of the last call that had a source layout
+    int last_dest_route = 0;     // lanczos_last_dest_route: LANCZOS_DEST_* of the last call that had a destination layout
     int last_route = 0;      // lanczos_last_route: main kernel, prefix route and launch count of the last upscale call
     int route_launches = 0;  // launches of the call in flight (reset by the entry points, counted where a launch is issued)
     int route_seen = 0;      // prefix routes of those launches, one bit each
@@ -1633,6 +1634,82 @@ int lanczos_resize_tensor_source_host(lanczos_ctx* ctx, const lanczos_resize_des
 }
 
 int lanczos_last_source_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_source_route : 0; }
+
+// ---- a destination layout beside the descriptor (lanczos_resize_dest.hip) ------------------------------------------------
+int lanczos_resize_dest_init(lanczos_resize_dest* dst, const lanczos_resize_desc* d, const lanczos_resize_window* win, int layout) {
+    if (!dst || (layout != LANCZOS_DEST_INTERLEAVED && layout != LANCZOS_DEST_PLANAR)) return LANCZOS_ERR_BAD_ARG;
+    int rc = lz::resize_validate(d);
+    lz::RsWindow w;
+    if (rc == LANCZOS_OK) rc = lz::resize_window_resolve(d, win, &w);
+    if (rc != LANCZOS_OK) return rc;
+    const int64_t B = lz::resize_bps(d);
+    *dst = lanczos_resize_dest{};
+    if (layout == LANCZOS_DEST_PLANAR) {
+        if (B != 1) return LANCZOS_ERR_UNSUPPORTED;
+        dst->row_stride = w.w, dst->chan_stride = (int64_t)w.w * w.h, dst->pix_stride = 1;
+    } else {
+        dst->row_stride = (int64_t)w.w * d->channels * B, dst->chan_stride = B, dst->pix_stride = (int32_t)(d->channels * B);
+    }
+    return LANCZOS_OK;
+}
+
+int lanczos_resize_dest_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_resize_dest* dst) {
+    int rc = lz::resize_validate(d);
+    lz::RsWindow w;
+    if (rc == LANCZOS_OK) rc = lz::resize_window_resolve(d, win, &w);
+    if (rc != LANCZOS_OK) return rc;
+    lz::RsDest s;
+    return lz::resize_dest_resolve(d, w, dst, &s);
+}
+
+extern "C++" {
+// what the two entries with a destination share: everything validated and resolved, then `run` under the context's lock
+template <class F>
+static int dest_call(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_resize_source* src,
+                     const lanczos_resize_dest* dst, bool host, F&& run) {
+    int rc = lz::resize_validate(d);
+    lz::RsWindow w;
+    lz::RsSourceCall sc;
+    lz::RsDestCall dc;
+    if (rc == LANCZOS_OK) rc = lz::resize_window_resolve(d, win, &w);
+    if (rc == LANCZOS_OK) rc = lz::resize_source_resolve(d, src, &sc.s);
+    if (rc == LANCZOS_OK) rc = lz::resize_dest_resolve(d, w, dst, &dc.s);
+    if (rc != LANCZOS_OK) return rc;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    if (host && !ctx->stream) return LANCZOS_ERR_HIP;
+    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
+    route_begin(ctx);
+    rc = run(src ? &sc : nullptr, &dc);
+    if (rc == LANCZOS_OK && src && sc.route) ctx->last_source_route = sc.route;   // a refused or failed call leaves them
+    if (rc == LANCZOS_OK && dc.route) ctx->last_dest_route = dc.route;
+    return rc;
+}
+}   // extern "C++"
+
+int lanczos_resize_dest_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
+                               const lanczos_resize_window* win, const lanczos_resize_source* src, const lanczos_resize_dest* dst,
+                               const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride,
+                               void* stream) {
+    if (!dst) return lanczos_resize_source_device(ctx, d, o, win, src, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    return dest_call(ctx, d, win, src, dst, false, [&](lz::RsSourceCall* sc, lz::RsDestCall* dc) {
+        return lz::resize_device(ctx->resize, d, o, win, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
+                                 &ctx->last_kernel, &ctx->last_hip, nullptr, sc, dc);
+    });
+}
+
+int lanczos_resize_dest_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
+                             const lanczos_resize_window* win, const lanczos_resize_source* src, const lanczos_resize_dest* dst,
+                             const void* in, void* out, int frames) {
+    if (!dst) return lanczos_resize_source_host(ctx, d, o, win, src, in, out, frames);
+    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    return dest_call(ctx, d, win, src, dst, true, [&](lz::RsSourceCall* sc, lz::RsDestCall* dc) {
+        return lz::resize_host(ctx->resize, d, o, win, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip, sc, dc);
+    });
+}
+
+int lanczos_last_dest_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_dest_route : 0; }
 
 int lanczos_reduce_size(int in_w, int in_h, int fx, int fy, const int32_t* box, int* out_w, int* out_h) {
     if (!out_w || !out_h) return LANCZOS_ERR_BAD_ARG;

@@ -41,6 +41,11 @@
 // instances of their own, lanczos_resize_source*.hip), every other route gets them packed into context scratch by
 // k_rs_pack_source first (lanczos_resize_source.hip).
 //
+// A destination layout (lanczos_resize_dest: planar frames, pitched rows) changes where a result byte is stored and nothing
+// else: the fused kernel stores pitched interleaved rows itself (a pitch is one of its arguments) and planes through an epilogue
+// and instances of their own (lanczos_resize_dest*.hip), every other route stores the packed result in context scratch and
+// k_rs_unpack_dest scatters it (lanczos_resize_dest.hip).
+//
 // The arithmetic is Pillow's and exact by construction; RsSample<BPS> says how for each width.
 #include "lanczos_resize.hpp"
 
@@ -419,6 +424,7 @@ ResizeState::~ResizeState() {   // the owner has drained the device
     if (reduced.p) (void)hipFree(reduced.p);
     if (tensor_bytes.p) (void)hipFree(tensor_bytes.p);
     if (packed.p) (void)hipFree(packed.p);
+    if (unpacked.p) (void)hipFree(unpacked.p);
     if (stage_in) (void)hipFree(stage_in);
     if (stage_out) (void)hipFree(stage_out);
     if (upload) (void)hipStreamDestroy(upload);
@@ -673,9 +679,12 @@ static hipError_t rs_launch_pass(int bps, bool horizontal, const ResizeAxis* ax,
 // sc: the frames at `in` lie in that layout, which is not the tight one (the tight one is no source at all).  Where the fused
 // kernel runs and has the staging for it, it reads them as they lie (LANCZOS_SOURCE_DIRECT); everything else gets them packed
 // into context scratch first (rs_pack_source) and is then the request it always was
+// dc: the window is stored in that layout, which is not the tight one (never with tc).  Where the fused kernel runs it stores
+// pitched rows and planes itself (LANCZOS_DEST_DIRECT); everything else stores the tightly packed window in context scratch, as
+// the request it always was, and k_rs_unpack_dest scatters it (LANCZOS_DEST_UNPACKED)
 static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh, RsSpan sv, const RsWindow& win_in,
                         const uint8_t* in, uint8_t* out, int frames, size_t in_fs, size_t out_fs, hipStream_t stream,
-                        int* last_kernel, int* last_hip, RsTensorCall* tc, RsSourceCall* sc = nullptr);
+                        int* last_kernel, int* last_hip, RsTensorCall* tc, RsSourceCall* sc = nullptr, RsDestCall* dc = nullptr);
 
 // the PACKED route of a source: `frames` frames at *in, in layout s, gathered tightly packed into the context's block; *in and
 // *in_fs then name that block
@@ -696,7 +705,7 @@ static int rs_pack_source(ResizeState* st, const lanczos_resize_desc* d, const R
 
 static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh, RsSpan sv, const RsWindow& win_in,
                         const uint8_t* in, uint8_t* out, int frames, size_t in_fs, size_t out_fs, hipStream_t stream,
-                        int* last_kernel, int* last_hip, RsTensorCall* tc, RsSourceCall* sc) {
+                        int* last_kernel, int* last_hip, RsTensorCall* tc, RsSourceCall* sc, RsDestCall* dc) {
     const int C = d->channels;
     const size_t B = (size_t)resize_bps(d);   // bytes per sample
     const bool f32 = B == 4;
@@ -767,6 +776,24 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
         if (rc != LANCZOS_OK) return rc;
         out = (uint8_t*)st->tensor_bytes.p, out_fs = bytes_fs;
     }
+    // 32-bit buffer offsets into the pitched frame, whose range the kernel takes as rows x pitch
+    uint8_t* const d_out = out;
+    const size_t d_fs = out_fs;
+    // a planar destination has instances of its own (8-bit, three or four channels), none of them with the row shift of an ALPHA
+    // source pitched off a dword: that one keeps its direct staging and is unpacked
+    const bool dst_direct = dc && fused && !dc->unpack_only && st->force != LANCZOS_RESIZE_CONVERT &&
+                            std::max(dc->s.named, (size_t)win.h * dc->s.row_stride) < ((size_t)1 << 31) &&
+                            (!dc->s.planar || ((st->force != LANCZOS_RESIZE_AUTO || kRsPlanarOutAutoDirect) && !(src && rowshift)));
+    if (dc) {
+        if (tc) return LANCZOS_ERR_BAD_ARG;
+        dc->route = dst_direct ? LANCZOS_DEST_DIRECT : LANCZOS_DEST_UNPACKED;
+        if (!dst_direct) {   // the packed window, readable a few dwords past its end (k_rs_unpack_dest)
+            const size_t bytes_fs = ((size_t)win.w * win.h * C * B + 3) & ~(size_t)3;
+            rc = rs_scratch(st, &st->unpacked, (size_t)frames * bytes_fs + 32, stream, capturing, last_hip);
+            if (rc != LANCZOS_OK) return rc;
+            out = (uint8_t*)st->unpacked.p, out_fs = bytes_fs;
+        }
+    }
     // two passes: the horizontal one produces the rows the vertical taps read and no others, mid_rows of them from source
     // row mid_row0 on, and the scratch holds exactly those; the vertical pass indexes it through a base mid_row0 rows in
     // front of it, which it never dereferences below the block (its first tap is row mid_row0)
@@ -777,8 +804,10 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
     const size_t in_pitch = (size_t)d->in_w * C * B;
     hipError_t e = hipSuccess;
     if (fused) {
-        const RsFusedLaunch c{d, win, &fp, H, V, in, out, in_fs, out_fs, frames, tc, stream, src};
-        e = src && src->planar ? (!t_fused           ? rs_launch_fused<1, kRsPlanar>(c)
+        const RsFusedLaunch c{d, win, &fp, H, V, in, out, in_fs, out_fs, frames, tc, stream, src, dst_direct ? &dc->s : nullptr};
+        e = dst_direct && dc->s.planar ? (src && src->planar ? rs_launch_fused<1, kRsPlanar + kRsPlanarOut>(c)
+                                                             : rs_launch_fused<1, kRsPlanarOut>(c))
+            : src && src->planar ? (!t_fused           ? rs_launch_fused<1, kRsPlanar>(c)
                                   : tc->t.elem == 2 ? rs_launch_fused<1, 2 + kRsMapped + kRsPlanar>(c)
                                                     : rs_launch_fused<1, 4 + kRsMapped + kRsPlanar>(c))
             : src && rowshift  ? (!t_fused           ? rs_launch_fused<1, kRsRowShift>(c)
@@ -854,6 +883,8 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
             e = rs_to_tensor_launch(out, out_fs, t_out, t_fs, win.w, win.h, C, tc->t, frames, stream);
         tc->route = t_fused ? LANCZOS_TENSOR_FUSED : LANCZOS_TENSOR_CONVERTED;
     }
+    if (dc && !dst_direct && e == hipSuccess)
+        e = rs_unpack_dest_launch(out, out_fs, d_out, d_fs, dc->s, win.w, win.h, C, (int)B, frames, stream);
     if (capturing) {   // a live graph may name these tables: they stay until the context goes
         for (ResizeAxis* ax : {H, V})
             if (ax) {
@@ -875,7 +906,7 @@ static int resize_inner(ResizeState* st, const lanczos_resize_desc* d, RsSpan sh
 
 int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
                   const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream,
-                  int* last_kernel, int* last_hip, RsTensorCall* tc, RsSourceCall* sc) {
+                  int* last_kernel, int* last_hip, RsTensorCall* tc, RsSourceCall* sc, RsDestCall* dc) {
     RsResolved r;
     RsWindow w;
     int rc = resize_resolve(d, o, &r);
@@ -885,10 +916,12 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_r
     const size_t B = (size_t)resize_bps(d);   // bytes per sample
     if (sc && sc->s.tight) sc->route = LANCZOS_SOURCE_DIRECT, sc = nullptr;   // the call without a source
     const size_t in_frame = sc ? sc->s.extent : (size_t)d->in_w * d->in_h * C * B;
-    const size_t out_frame = tc ? tc->extent_bytes : (size_t)w.w * w.h * C * B;
+    if (dc && dc->s.tight) dc->route = LANCZOS_DEST_DIRECT, dc = nullptr;     // the call without a destination
+    const size_t out_frame = tc ? tc->extent_bytes : dc ? dc->s.extent : (size_t)w.w * w.h * C * B;
     const size_t in_fs = in_frame_stride ? in_frame_stride : in_frame;
     const size_t out_fs = out_frame_stride ? out_frame_stride : out_frame;
-    if (in_fs < in_frame || out_fs < out_frame) return LANCZOS_ERR_BAD_ARG;
+    // a destination's frames may overlap each other's padding: the stride has to clear the named bytes only
+    if (in_fs < in_frame || out_fs < (dc ? dc->s.named : out_frame)) return LANCZOS_ERR_BAD_ARG;
     if ((((uintptr_t)d_in | (uintptr_t)d_out | in_fs | out_fs) & (B - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
     if (tc && (((uintptr_t)d_out | out_fs) & (size_t)(tc->t.elem - 1)) != 0) return LANCZOS_ERR_BAD_ARG;   // element frames
     const uint8_t* in = (const uint8_t*)d_in;
@@ -897,6 +930,7 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_r
         sc->route = LANCZOS_SOURCE_PACKED;
         if ((rc = rs_pack_source(st, d, sc->s, &in, &in_fs_r, frames, stream, last_hip)) != LANCZOS_OK) return rc;
     }
+    if (dc && r.reduces()) dc->unpack_only = true;   // as a source is packed for the reduction, whatever resizes the reduced frames
     if (r.reduces()) {   // reducing_gap: reduce into context scratch, then resize the reduced frames
         int rb[4];
         const int32_t box[4] = {r.rb[0], r.rb[1], r.rb[2], r.rb[3]};
@@ -910,9 +944,9 @@ int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_r
             return LANCZOS_ERR_HIP;
         }
         return resize_inner(st, &r.inner, r.h, r.v, w, (const uint8_t*)st->reduced.p, (uint8_t*)d_out, frames, red_fs, out_fs,
-                            stream, last_kernel, last_hip, tc);
+                            stream, last_kernel, last_hip, tc, nullptr, dc);   // (dc->unpack_only: set above)
     }
-    return resize_inner(st, d, r.h, r.v, w, in, (uint8_t*)d_out, frames, in_fs, out_fs, stream, last_kernel, last_hip, tc, sc);
+    return resize_inner(st, d, r.h, r.v, w, in, (uint8_t*)d_out, frames, in_fs, out_fs, stream, last_kernel, last_hip, tc, sc, dc);
 }
 
 // staging buffers of the host entry points (resize and reduce)
@@ -972,16 +1006,19 @@ static int rs_staged_call(ResizeState* st, const void* in, size_t in_bytes, void
 }
 
 int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
-                const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip, RsSourceCall* sc) {
+                const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip, RsSourceCall* sc,
+                RsDestCall* dc) {
     const size_t B = (size_t)resize_bps(d);
     if ((((uintptr_t)in | (uintptr_t)out) & (B - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
     RsWindow w;
     const int rc = resize_window_resolve(d, win, &w);
     if (rc != LANCZOS_OK) return rc;
     const size_t in_bytes = (sc ? sc->s.extent : (size_t)d->in_w * d->in_h * d->channels * B) * frames;
-    const size_t out_bytes = (size_t)w.w * w.h * d->channels * B * frames;
-    return rs_staged_call(st, in, in_bytes, out, out_bytes, {}, stream, last_hip, [&] {
-        return resize_device(st, d, o, win, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip, nullptr, sc);
+    const size_t out_bytes = dc ? dc->s.extent * (frames - 1) + dc->s.named : (size_t)w.w * w.h * d->channels * B * frames;
+    RsStagedExtra x;
+    x.out_up = dc != nullptr;   // the bytes the layout does not name keep what they held
+    return rs_staged_call(st, in, in_bytes, out, out_bytes, x, stream, last_hip, [&] {
+        return resize_device(st, d, o, win, st->stage_in, st->stage_out, frames, 0, 0, stream, last_kernel, last_hip, nullptr, sc, dc);
     });
 }
 

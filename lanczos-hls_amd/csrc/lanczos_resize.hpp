@@ -5,8 +5,8 @@
 // (8-bit into float tensors), lanczos_resize_tensor16.hip (8-bit into bfloat16 / float16 tensors), lanczos_resize_tensor_view.hip
 // and lanczos_resize_tensor16_view.hip (the same two through a channel map and flips), lanczos_resize_tensor_crops.hip and
 // lanczos_resize_tensor16_crops.hip (those with a crop origin per frame), lanczos_resize_source.hip, lanczos_resize_source_tensor.hip
-// and lanczos_resize_source_tensor16.hip (those of a planar or oddly pitched source), lanczos_resize16.hip and
-// lanczos_resize32.hip.  The filter of a request (LANCZOS_RESIZE_FILTER)
+// and lanczos_resize_source_tensor16.hip (those of a planar or oddly pitched source), lanczos_resize_dest.hip and
+// lanczos_resize_dest_source.hip (8-bit into a planar destination), lanczos_resize16.hip and lanczos_resize32.hip.  The filter of a request (LANCZOS_RESIZE_FILTER)
 // only changes the tables; LANCZOS_FILTER_NEAREST has index tables and a kernel of its own (lanczos_resize_nearest.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -168,6 +168,7 @@ struct ResizeState {
     Block reduced;                           // the reduced frames of a request with reducing_gap, tightly packed
     Block tensor_bytes;                      // the byte result of a tensor request on the converted route (k_rs_to_tensor reads it)
     Block packed;                            // the tightly packed copy of a source on the PACKED route (k_rs_pack_source writes it)
+    Block unpacked;                          // the tightly packed result of a destination on the UNPACKED route (k_rs_unpack_dest reads it)
     std::vector<void*> kept;                 // scratch blocks replaced while a graph may hold them: freed at destruction
     // staging of lanczos_resize_host
     void* stage_in = nullptr;
@@ -257,11 +258,39 @@ constexpr bool kRsPlanarAutoDirect = true;
 hipError_t rs_pack_source_launch(const uint8_t* in, size_t in_fs, const RsSource& s, uint8_t* out, size_t out_fs, int w, int h,
                                  int C, int B, int frames, hipStream_t stream);
 
+// A destination layout (lanczos_resize_dest), resolved by resize_dest_resolve for a w x h window: sample (y, x, c) of a frame goes
+// c * chan_stride + y * row_stride + x * (planar ? 1 : C * B) bytes into it.  tight: interleaved with packed rows, the call
+// without a destination
+struct RsDest {
+    bool planar = false, tight = true;
+    size_t row_stride = 0, chan_stride = 0;   // bytes; chan_stride of an interleaved destination is B
+    size_t extent = 0;                         // of one frame, the default frame stride: h * row_stride, or channels * chan_stride
+    size_t named = 0;                          // from a frame's first byte to the last one the layout names, + 1
+};
+// dst NULL: the tight interleaved layout.  Planar with one channel resolves to the interleaved shape
+int resize_dest_resolve(const lanczos_resize_desc* d, const RsWindow& w, const lanczos_resize_dest* dst, RsDest* s);
+// the destination of a call and the route it took (LANCZOS_DEST_*); meaningful where the call returns LANCZOS_OK
+struct RsDestCall {
+    RsDest s;
+    int route = 0;
+    bool unpack_only = false;   // set by resize_device: a request with a reducing gap is UNPACKED whatever resizes the reduced frames
+};
+// AUTO takes the planar-out instances of the fused kernel where they exist (false: UNPACKED, the instances by force only); the
+// measurements behind the choice are in DESIGN.md 4.5
+constexpr bool kRsPlanarOutAutoDirect = true;
+// k_rs_unpack_dest (lanczos_resize_dest.hip): `frames` tightly packed interleaved frames of w x h pixels of C samples of B bytes,
+// in_fs bytes apart (in and in_fs dword multiples, readable 32 bytes past the last frame), scattered into layout s at any byte
+// address, frames out_fs bytes apart.  Only bytes the layout names are written
+hipError_t rs_unpack_dest_launch(const uint8_t* in, size_t in_fs, uint8_t* out, size_t out_fs, const RsDest& s, int w, int h,
+                                 int C, int B, int frames, hipStream_t stream);
+
 // The entry points (ctx->mu held, device set).  *last_kernel / *last_hip as in lanczos_ctx.  tc: a tensor request (NULL: bytes).
 // win: the window of the output that is computed and stored, tightly packed (NULL: the whole output)
+// dc: the window is stored in that layout instead (bytes out only: never with tc)
 int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
                   const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream,
-                  int* last_kernel, int* last_hip, RsTensorCall* tc = nullptr, RsSourceCall* sc = nullptr);
+                  int* last_kernel, int* last_hip, RsTensorCall* tc = nullptr, RsSourceCall* sc = nullptr,
+                  RsDestCall* dc = nullptr);
 // host table (t.d_lut), host flip array (t.d_flip, or NULL) and host buffers, element frames tensor_extent_bytes apart;
 // synchronous.  origins: NULL, or the host array of a lanczos_resize_crops request (win is then (0, 0, w, h))
 int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
@@ -269,9 +298,11 @@ int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanc
                        hipStream_t stream, int* last_kernel, int* last_hip, int* route, const int32_t* origins = nullptr,
                        RsSourceCall* sc = nullptr);
 // sc: `in` holds the frames in that layout, its extent apart
+// dc: `out` holds the frames in that layout, its extent apart, the last one up to its last named byte; it goes up before it
+// comes back, so that the bytes the layout does not name keep what they held
 int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
                 const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip,
-                RsSourceCall* sc = nullptr);
+                RsSourceCall* sc = nullptr, RsDestCall* dc = nullptr);
 
 // Reduce by whole factors (lanczos_reduce.hip): Pillow's Image.reduce over an integer box, 8-bit.  Arguments validated by
 // reduce_validate; the output rows are tightly packed.
@@ -298,6 +329,8 @@ struct RsFusedLaunch {
     const RsTensorCall* tc;   // TENSOR: `out` / `out_fs` are the element frames
     hipStream_t stream;
     const RsSource* src = nullptr;   // NULL: packed interleaved rows.  A planar one runs the kRsPlanar instances
+    const RsDest* dst = nullptr;     // NULL: packed output rows; else rows row_stride bytes apart.  A planar one runs the
+                                     // kRsPlanarOut instances
 };
 // TENSOR: bytes of a stored table element, 0 where the samples themselves are stored; + kRsMapped: through the channel map and
 // the flips of the request (RsTensorOut::mapped)
@@ -309,6 +342,8 @@ constexpr int kRsPlanar = 32;
 // + kRsRowShift: LANCZOS_RESIZE_ALPHA over pitched interleaved rows whose pitch is no dword multiple: the staging shifts by the
 // residue of each row.  As for kRsPlanar, bytes out is the flag alone and a tensor request runs the mapped instance
 constexpr int kRsRowShift = 64;
+// + kRsPlanarOut: the destination is planar (RsDest::planar, bytes out): the vertical pass stores one dword per plane
+constexpr int kRsPlanarOut = 128;
 template <int BPS, int TENSOR>
 hipError_t rs_launch_fused(const RsFusedLaunch& c);
 

@@ -1,0 +1,119 @@
+// lanczos_resize_dest.hip -- a destination layout beside the descriptor (lanczos_resize_dest, include/lanczos_hip.h): planar
+// (CHW) and row-pitched result frames without a repack by the caller.  Here: the layout's validation, the planar-out instances of
+// the fused kernel over an interleaved source (the kernel is lanczos_resize_fused.hpp's and only its epilogue differs), and
+// k_rs_unpack_dest, the streaming scatter of the UNPACKED route.  Pitched interleaved rows need no kernel code (RsFused::out_pitch);
+// the routes are chosen in lanczos_resize.hip (resize_inner).
+#include "lanczos_resize_fused.hpp"
+
+namespace lz {
+
+// the instances of the fused kernel that store planes from an interleaved source (k_rs_fused<RsSample<1>, C, K, ALPHA,
+// kRsPlanarOut> for every tap-count bucket x C = 3, 4 and alpha); those of a planar source are lanczos_resize_dest_source.hip's
+template hipError_t rs_launch_fused<1, kRsPlanarOut>(const RsFusedLaunch&);
+
+int resize_dest_resolve(const lanczos_resize_desc* d, const RsWindow& w, const lanczos_resize_dest* dst, RsDest* s) {
+    const long long C = d->channels, B = resize_bps(d);
+    const long long tight_row = (long long)w.w * C * B;
+    *s = RsDest{false, true, (size_t)tight_row, (size_t)B, (size_t)(w.h * tight_row), (size_t)(w.h * tight_row)};
+    if (!dst) return LANCZOS_OK;
+    for (int32_t r : dst->reserved)
+        if (r != 0) return LANCZOS_ERR_BAD_ARG;
+    const long long rs = dst->row_stride, cs = dst->chan_stride, ps = dst->pix_stride;
+    if (rs < 1 || cs < 1 || ps < 1 || rs % B != 0) return LANCZOS_ERR_BAD_ARG;
+    // a plane of h pitched rows: what chan_stride has to clear.  rs * h stays far below 2^63 only for a sane pitch
+    if (rs > ((long long)1 << 40)) return LANCZOS_ERR_BAD_ARG;
+    const long long plane = (w.h - 1) * rs + (long long)w.w * B;
+    const bool planar_shape = ps == B && rs >= (long long)w.w * B && cs >= plane && cs <= ((long long)1 << 56);
+    const auto interleaved = [&] {
+        s->row_stride = (size_t)rs, s->tight = rs == tight_row;
+        s->extent = (size_t)(w.h * rs), s->named = (size_t)((w.h - 1) * rs + tight_row);
+        return LANCZOS_OK;
+    };
+    if (ps == C * B && cs == B && rs >= tight_row) return interleaved();   // with one channel: every planar destination as well
+    if (!planar_shape) return LANCZOS_ERR_BAD_ARG;
+    if (C == 1) return interleaved();             // one plane: the interleaved shape, whatever chan_stride says
+    if (B != 1) return LANCZOS_ERR_UNSUPPORTED;   // planar wide samples: frames * C one-channel frames for the plain entries
+    s->planar = true, s->tight = false;
+    s->row_stride = (size_t)rs, s->chan_stride = (size_t)cs;
+    s->extent = (size_t)(C * cs), s->named = (size_t)((C - 1) * cs + plane);
+    return LANCZOS_OK;
+}
+
+// ---- k_rs_unpack_dest --------------------------------------------------------------------------------------------------
+//
+// Tightly packed interleaved frames in context scratch (base and frame stride dword multiples) -> the destination of the UNPACKED
+// route.  A wave serves 64 groups of four bytes (or pixels) of one row of one frame (blockIdx.y), the four waves of a workgroup
+// four such runs, so that narrow rows fill workgroups too; 64-bit addresses throughout, plain global accesses.
+// A thread's dwords of the packed row are put together from the aligned ones around them (rs_load_dword_at: a packed row starts
+// at any byte); the block is readable past its last frame for that.
+struct RsUnpack {
+    const uint8_t* in;
+    uint8_t* out;
+    unsigned long long in_fs, out_fs, row_stride, chan_stride;
+    unsigned w, row_bytes;   // pixels and bytes of a packed row
+    unsigned h, runs;        // rows, and runs of 64 groups per row
+};
+// this lane's row and group of four: wave blockIdx.x * 4 + threadIdx.x / 64 is run (y, k) in raster order; false: past the frame
+__device__ __forceinline__ bool rs_unpack_place(const RsUnpack& p, unsigned long long* y, unsigned* i) {
+    const unsigned run = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const unsigned row = run / p.runs;
+    *y = row, *i = (run - row * p.runs) * 64 + (threadIdx.x & 63);
+    return row < p.h;
+}
+
+// planar, C = 3 or 4: a thread takes pixels 4 i .. 4 i + 3 of the row as C interleaved dwords and writes one dword per plane
+template <int C>
+__global__ __launch_bounds__(256) void k_rs_unpack_dest(RsUnpack p) {
+    unsigned i;
+    unsigned long long y;
+    const bool have = rs_unpack_place(p, &y, &i) && 4ull * i < p.w;
+    const uint8_t* src = p.in + blockIdx.y * p.in_fs + y * p.row_bytes + 4ull * i * C;
+    uint8_t* fout = p.out + blockIdx.y * p.out_fs + y * p.row_stride;
+    uint32_t o[C];
+#pragma unroll
+    for (int c = 0; c < C; c++) o[c] = have ? rs_load_dword_at(src + 4 * c) : 0u;
+#pragma unroll
+    for (int c = 0; c < C; c++) {
+        uint32_t pl = 0u;   // byte k: sample c of pixel 4 i + k, byte k * C + c of the C dwords
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int j = k * C + c;
+            pl |= ((o[j >> 2] >> (8 * (j & 3))) & 255u) << (8 * k);
+        }
+        rs_store_segment<1>(fout + c * p.chan_stride, i, p.w, pl, have);
+    }
+}
+
+// interleaved, pitched rows: a thread per dword of the packed row (any sample width: the bytes are only moved)
+__global__ __launch_bounds__(256) void k_rs_unpack_dest_rows(RsUnpack p) {
+    unsigned i;
+    unsigned long long y;
+    const bool have = rs_unpack_place(p, &y, &i) && 4ull * i < p.row_bytes;
+    const uint8_t* src = p.in + blockIdx.y * p.in_fs + y * p.row_bytes + 4ull * i;
+    const uint32_t v = have ? rs_load_dword_at(src) : 0u;
+    rs_store_segment<1>(p.out + blockIdx.y * p.out_fs + y * p.row_stride, i, p.row_bytes, v, have);
+}
+
+hipError_t rs_unpack_dest_launch(const uint8_t* in, size_t in_fs, uint8_t* out, size_t out_fs, const RsDest& s, int w, int h,
+                                 int C, int B, int frames, hipStream_t stream) {
+    RsUnpack p{};
+    p.in_fs = in_fs, p.out_fs = out_fs, p.row_stride = s.row_stride, p.chan_stride = s.chan_stride;
+    p.w = (unsigned)w, p.row_bytes = (unsigned)(w * C * B);
+    if (s.planar && (B != 1 || (C != 3 && C != 4))) return hipErrorInvalidValue;
+    const unsigned groups = ((s.planar ? p.w : p.row_bytes) + 3) / 4;
+    p.h = (unsigned)h, p.runs = (groups + 63) / 64;   // h * runs < 2^16 * 2^13
+    for (int f0 = 0; f0 < frames; f0 += 65535) {
+        const int nf = std::min(65535, frames - f0);
+        p.in = in + (size_t)f0 * in_fs;
+        p.out = out + (size_t)f0 * out_fs;
+        const dim3 grid((p.h * p.runs + 3) / 4, nf);
+        if (!s.planar) hipLaunchKernelGGL(k_rs_unpack_dest_rows, grid, dim3(256), 0, stream, p);
+        else if (C == 3) hipLaunchKernelGGL(k_rs_unpack_dest<3>, grid, dim3(256), 0, stream, p);
+        else hipLaunchKernelGGL(k_rs_unpack_dest<4>, grid, dim3(256), 0, stream, p);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+}  // namespace lz

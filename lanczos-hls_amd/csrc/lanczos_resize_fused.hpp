@@ -12,7 +12,9 @@
 //                   lanczos_resize_tensor_crops.hip and lanczos_resize_tensor16_crops.hip (those with a crop origin per frame:
 //                   TENSOR + kRsMapped + kRsCrops), lanczos_resize_source.hip, lanczos_resize_source_tensor.hip and
 //                   lanczos_resize_source_tensor16.hip (8-bit from a planar source: TENSOR with kRsPlanar, and ALPHA over rows
-//                   pitched off a dword: with kRsRowShift), lanczos_resize16.hip and lanczos_resize32.hip.
+//                   pitched off a dword: with kRsRowShift), lanczos_resize_dest.hip and lanczos_resize_dest_source.hip (8-bit
+//                   into a planar destination: kRsPlanarOut, the second with kRsPlanar), lanczos_resize16.hip and
+//                   lanczos_resize32.hip.
 #pragma once
 #include "lanczos_alpha.hpp"
 #include "lanczos_resize.hpp"
@@ -181,14 +183,24 @@ struct RsFusedPlanar : Base {
     int chan_stride;      // bytes between the planes of a frame
     unsigned src_bytes;   // from the frame's first byte to the last one the layout names, below 2^31
 };
+// ... + kRsPlanarOut: the destination is planar (RsDest::planar).  out_pitch is then the pitch of a plane row; behind the fields of
+// the instance without it, for the reason RsFusedTensorMap gives
+template <class Base>
+struct RsFusedPlanarOut : Base {
+    int out_chan_stride;   // bytes between the planes of a frame
+    unsigned dst_bytes;    // from the frame's first byte to the last one the layout names + 1, below 2^31
+};
 // the argument of k_rs_fused<..., TENSOR> for coefficients KT
 template <int TENSOR, class KT>
 using RsFusedArgsPacked = std::conditional_t<
     (TENSOR & kRsCrops) != 0, RsFusedTensorCrops,
     std::conditional_t<(TENSOR & kRsMapped) != 0, RsFusedTensorMap, std::conditional_t<TENSOR != 0, RsFusedTensor, RsFused<KT>>>>;
 template <int TENSOR, class KT>
-using RsFusedArgs = std::conditional_t<(TENSOR & kRsPlanar) != 0, RsFusedPlanar<RsFusedArgsPacked<(TENSOR & ~kRsPlanar), KT>>,
-                                       RsFusedArgsPacked<(TENSOR & ~kRsRowShift), KT>>;
+using RsFusedArgsIn = std::conditional_t<(TENSOR & kRsPlanar) != 0, RsFusedPlanar<RsFusedArgsPacked<(TENSOR & ~kRsPlanar), KT>>,
+                                         RsFusedArgsPacked<(TENSOR & ~kRsRowShift), KT>>;
+template <int TENSOR, class KT>
+using RsFusedArgs = std::conditional_t<(TENSOR & kRsPlanarOut) != 0, RsFusedPlanarOut<RsFusedArgsIn<(TENSOR & ~kRsPlanarOut), KT>>,
+                                       RsFusedArgsIn<TENSOR, KT>>;
 
 // The byte transpose of the planar staging and of k_rs_pack_source: p[c] holds bytes x .. x + 3 of plane c, o[] the C dwords of
 // those four pixels interleaved.  v_perm_b32 picks byte sel[k] of the eight bytes {a : b} (b the low four) for result byte k
@@ -205,6 +217,53 @@ __device__ __forceinline__ void rs_interleave4(const uint32_t (&p)[C], uint32_t 
         o[1] = __builtin_amdgcn_perm(p[2], __builtin_amdgcn_perm(p[1], p[0], 0x06020c05u), 0x03020500u);
         o[2] = __builtin_amdgcn_perm(p[2], __builtin_amdgcn_perm(p[1], p[0], 0x0c07030cu), 0x07020106u);
     }
+}
+// the dword at any byte address, put together from the two aligned ones around it (k_rs_pack_source, k_rs_unpack_dest)
+__device__ __forceinline__ uint32_t rs_load_dword_at(const uint8_t* p) {
+    const unsigned sh = (unsigned)((uintptr_t)p & 3);
+    const uint32_t* q = (const uint32_t*)(p - sh);
+    const uint32_t lo = q[0];
+    const uint32_t up = sh != 0 ? q[1] : 0u;
+    return __builtin_amdgcn_alignbyte(up, lo, sh);
+}
+// One row segment of a destination: n bytes from `row` on, which starts at any byte.  A lane holds bytes 4 i .. 4 i + 3 of it in v
+// (those below n; `have`: there is at least one); the lane LS below it holds group i - 1 and the lane LS above group i + 1, NL
+// lanes of the wave taking part (LS = 1: neighbouring lanes; LS = C: the lanes of one plane where the planes alternate lane by
+// lane).  Every lane of the wave calls.  Dwords are stored at dword-aligned addresses only and cover bytes of the segment only:
+// where the segment starts r bytes into a dword, a lane stores the aligned dword that ends inside its group, put together from
+// the previous group's upper r bytes and its own lower 4 - r (v_alignbyte).  What that leaves goes out as bytes: the lower bytes
+// of the chain's first group, the upper r bytes of the chain's or the segment's last group, and a dword that would cross the
+// segment's end.
+template <int LS, int NL = 64>
+__device__ __forceinline__ void rs_store_segment(uint8_t* row, unsigned i, unsigned n, uint32_t v, bool have) {
+    const unsigned r = (unsigned)((uintptr_t)row & 3);
+    const unsigned lane = threadIdx.x & 63;
+    const uint32_t prev = (uint32_t)__shfl_up((int)v, LS, 64);
+    if (!have) return;
+    const unsigned p0 = 4 * i;
+    if (r == 0) {
+        if (p0 + 4 <= n) {
+            *(uint32_t*)(row + p0) = v;
+        } else {
+            for (unsigned j = 0; p0 + j < n; j++) row[p0 + j] = (uint8_t)(v >> (8 * j));
+        }
+        return;
+    }
+    // bytes p0 - r .. p0 - r + 3 of the segment: byte j is the previous group's byte 4 - r + j for j < r, this group's j - r beyond
+    const uint32_t m = __builtin_amdgcn_alignbyte(v, prev, 4 - r);
+    uint8_t* const at = row + p0 - r;   // dword-aligned
+    const bool first = lane < LS;       // no previous group in this wave: the lane that holds it stores those bytes itself, below
+    if (!first && p0 + 4 <= n + r) {
+        *(uint32_t*)at = m;
+    } else {   // ... or a dword across the segment's end, cut there
+        for (unsigned j = first ? r : 0u; j < 4; j++)
+            if (p0 + j < n + r) at[j] = (uint8_t)(m >> (8 * j));
+    }
+    // this group's upper r bytes ride in the next group's dword; without a next group in this wave: bytes
+    const bool next_has = lane + LS < NL && p0 + 4 < n;
+    if (!next_has)
+        for (unsigned j = 4 - r; j < 4; j++)
+            if (p0 + j < n) row[p0 + j] = (uint8_t)(v >> (8 * j));
 }
 // the range of a planar frame's buffer resource: from its base rounded down to a dword to the last byte the layout names
 template <bool PLANAR, class Args>
@@ -266,12 +325,34 @@ struct RsStrip {
 //
 // TENSOR with kRsRowShift (ALPHA over interleaved rows whose pitch is no dword multiple; instances beside the planar ones): the
 // ALPHA staging shifts every pixel by the residue of its own row instead of the frame's.
+//
+// TENSOR with kRsPlanarOut (a planar destination, bytes out, 8-bit, C = 3 or 4; instances of their own, lanczos_resize_dest*.hip):
+// only the epilogue differs.  The wave's 64 dwords are exchanged as the tensor epilogue exchanges them, so that in round r lane i
+// has sample 64 r + i of the wave's 256, and every sample goes out as one byte store to c * chan_stride + y * row_stride + x of
+// the frame: every C-th lane continues one plane row, and only bytes the layout names are ever stored.  The other form, one
+// dword store per lane, is built by LZ_RS_PLANAR_OUT_DWORDS: the lane's dword is exchanged so that a lane holds four pixels of
+// ONE plane (C = 4: within the quad; C = 3: the row goes out in four slots of 16 groups, 48 lanes each), and rs_store_segment
+// stores it -- dwords at dword-aligned addresses only, realigned with the neighbouring group's dword where the plane row
+// starts off one, bytes at the ends of the strip's segment.  It measured slower than the byte stores on every workload.
 template <class S, int C, int K, bool ALPHA = false, int TENSOR = 0>
 __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
     RsFusedArgs<TENSOR, typename S::coeff_t> g) {
-    constexpr int EB = TENSOR & ~(kRsMapped | kRsCrops | kRsPlanar | kRsRowShift);   // bytes of a stored element
+    constexpr int EB = TENSOR & ~(kRsMapped | kRsCrops | kRsPlanar | kRsRowShift | kRsPlanarOut);   // bytes of a stored element
     constexpr bool PLANAR = (TENSOR & kRsPlanar) != 0;
     constexpr bool ROWSHIFT = (TENSOR & kRsRowShift) != 0;
+    constexpr bool PLANAR_OUT = (TENSOR & kRsPlanarOut) != 0;
+    static_assert(!PLANAR_OUT || (EB == 0 && S::BPS == 1 && C >= 3 && !ROWSHIFT && TENSOR < 2 * kRsPlanarOut),
+                  "planar destinations: bytes out, 3 or 4 channels");
+    // The planar epilogue has two forms: the tensor epilogue's exchange with a byte store per sample, and one dword store per
+    // lane (C = 4: after a transpose within the quad; C = 3: the row walked in four slots of 16 groups of four pixels, 48 lanes,
+    // instead of three waves, so that no group straddles a wave).  The byte form measured faster on every workload and is what
+    // is built; the dword form stays for the A/B (DESIGN.md 4.5 has both numbers)
+#ifdef LZ_RS_PLANAR_OUT_DWORDS
+    constexpr bool kPlanarOutBytes = false;
+#else
+    constexpr bool kPlanarOutBytes = true;
+#endif
+    constexpr bool kSlots = PLANAR_OUT && C == 3 && !kPlanarOutBytes;
     static_assert(!ROWSHIFT || (ALPHA && !PLANAR && !(TENSOR & kRsCrops)), "a shift per row: the ALPHA staging of pitched rows");
     static_assert(!PLANAR || (S::BPS == 1 && C >= 3 && !(TENSOR & kRsCrops)), "planar sources: 8-bit, 3 or 4 channels, no crops");
     constexpr bool kPixelStage = ALPHA || PLANAR;         // a staged row starts at the strip's first pixel, whatever the address
@@ -330,6 +411,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
     uint8_t* fout = g.out + blockIdx.y * g.out_fs;
     unsigned out_bytes = (unsigned)(g.out_h * g.out_pitch);
     if constexpr (EB != 0) out_bytes = g.extent_bytes;
+    if constexpr (PLANAR_OUT) out_bytes = g.dst_bytes;
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(fout, 0, out_bytes, 0x00020000);
     const bool out_aligned = (((uintptr_t)fout | (unsigned)g.out_pitch | (unsigned)(x0 * CB)) & 3) == 0;
     const int valid_bytes = sw * (kDwordSamples ? C : CB);   // of the strip's row; dwords where a sample is one
@@ -479,10 +561,13 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
             hi += nr;
         }
         // vertical: one output row per wave (WPR waves per row), coefficients uniform, SPD samples per lane
-        for (int q = wave; q < nob * WPR; q += kRsThreads / 64) {
-            const int r = q / WPR;
+        constexpr int VPR = kSlots ? 4 : WPR;   // wave iterations per output row
+        for (int q = wave; q < nob * VPR; q += kRsThreads / 64) {
+            const int r = q / VPR;
             const int o = o0 + r;
-            const int dcol = (q - r * WPR) * 64 + lane;
+            int dcol;
+            if constexpr (kSlots) dcol = (q - r * VPR) * 48 + min(lane, 47);   // lanes 48 .. 63 idle along with lane 47
+            else dcol = (q - r * WPR) * 64 + lane;
             const int f = g.vf[o], n = g.vc[o];
             const typename S::coeff_t* kv = g.vk + (size_t)o * g.vks;
             int slot = f % g.ring_rows;
@@ -536,6 +621,47 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
                         }
                     }
                 }
+            } else if constexpr (PLANAR_OUT) {
+                // (packed with v_perm_b32 for the reason above: an exchange follows)
+                uint32_t packed = __builtin_amdgcn_perm(S::store(a1), S::store(a0), 0x0c0c0400u) |
+                                  __builtin_amdgcn_perm(S::store(a3), S::store(a2), 0x04000c0cu);
+                if constexpr (ALPHA) packed = rs_unpremul_px(packed);
+                if constexpr (kPlanarOutBytes) {
+                    const int wb = b0 - lane * 4;   // the wave's first sample of the strip's row
+#pragma unroll
+                    for (int rr = 0; rr < 4; rr++) {
+                        const uint32_t w = (uint32_t)__shfl((int)packed, 16 * rr + (lane >> 2), 64);
+                        const int j = wb + 64 * rr + lane;
+                        if (j < valid_bytes) {
+                            const int xo = j / C, c = j - xo * C;
+                            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(w >> (8 * (lane & 3))), orsrc,
+                                                                 c * g.out_chan_stride + o * g.out_pitch + x0 + xo, 0, 0);
+                        }
+                    }
+                } else if constexpr (C == 4) {
+                    // a lane is a pixel: the quad transposes its 4 x 4 bytes, and lane 4 i + c has plane c of pixels 4 i .. 4 i + 3
+                    const int c = lane & 3;
+                    uint32_t pl = 0u;
+#pragma unroll
+                    for (int k = 0; k < 4; k++)
+                        pl |= (((uint32_t)__shfl((int)packed, (lane & ~3) + k, 64) >> (8 * c)) & 255u) << (8 * k);
+                    uint8_t* const row = fout + (size_t)c * (size_t)g.out_chan_stride + (size_t)o * (size_t)g.out_pitch + x0;
+                    rs_store_segment<4>(row, (unsigned)(lane >> 2), (unsigned)sw, pl, (lane & ~3) < sw);
+                } else {
+                    // three lanes are four pixels (R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3): lane 3 j + c gets plane c of them
+                    const int l = min(lane, 47), j3 = l / 3, c = l - 3 * j3;
+                    const uint32_t d0 = (uint32_t)__shfl((int)packed, 3 * j3, 64), d1 = (uint32_t)__shfl((int)packed, 3 * j3 + 1, 64),
+                                   d2 = (uint32_t)__shfl((int)packed, 3 * j3 + 2, 64);
+                    const int f0 = 8 * c, f1 = 8 * ((c + 3) & 3), f2 = 8 * ((c + 2) & 3), f3 = 8 * ((c + 1) & 3);
+                    // sample c of pixel k is byte 3 k + c of the twelve: pixel 0 in d0; pixel 1 in d0 (c = 0) or d1; pixel 2 in d1
+                    // (c < 2) or d2; pixel 3 in d2
+                    const uint32_t p1 = c == 0 ? d0 : d1, p2 = c < 2 ? d1 : d2;
+                    const uint32_t pl = ((d0 >> f0) & 255u) | (((p1 >> f1) & 255u) << 8) | (((p2 >> f2) & 255u) << 16) |
+                                        (((d2 >> f3) & 255u) << 24);
+                    const unsigned grp = (unsigned)((q - r * VPR) * 16 + j3);   // the group of four pixels in the strip
+                    uint8_t* const row = fout + (size_t)c * (size_t)g.out_chan_stride + (size_t)o * (size_t)g.out_pitch + x0;
+                    rs_store_segment<3, 48>(row, grp, (unsigned)sw, pl, lane < 48 && (int)(4 * grp) < sw);
+                }
             } else if (b0 < valid_bytes) {
                 const int row_off = o * g.out_pitch + (kDwordSamples ? 4 * (x0 * C + dcol) : x0 * CB + b0);
                 uint32_t packed;   // the dword of the lane's stored samples
@@ -588,7 +714,7 @@ void rs_fill_fused(RsFused<KT>* g, const RsFusedLaunch& c) {
     const lanczos_resize_desc* d = c.d;
     const RsWindow& w = c.win;   // the kernel's output is the window: its tables start at the window's first outputs
     g->in_pitch = c.src ? (int)c.src->row_stride : d->in_w * d->channels * resize_bps(d);   // below 2^31 (the plan)
-    g->out_pitch = w.w * d->channels * resize_bps(d);
+    g->out_pitch = c.dst ? (int)c.dst->row_stride : w.w * d->channels * resize_bps(d);   // below 2^31 (resize_inner)
     g->in_h = d->in_h, g->out_w = w.w, g->out_h = w.h;
     g->in_fs = c.in_fs, g->out_fs = c.out_fs;
     g->hks = c.H->host.ksize, g->vks = c.V->host.ksize;
@@ -607,12 +733,15 @@ hipError_t rs_launch_fused(const RsFusedLaunch& c) {
     RsFusedArgs<TENSOR, typename S::coeff_t> g{};
     rs_fill_fused(&g, c);
     constexpr bool ROWSHIFT = (TENSOR & kRsRowShift) != 0;
+    constexpr bool PLANAR_OUT = (TENSOR & kRsPlanarOut) != 0;
     if ((c.src && c.src->planar) != PLANAR) return hipErrorInvalidValue;
+    if ((c.dst && c.dst->planar) != PLANAR_OUT) return hipErrorInvalidValue;
+    if constexpr (PLANAR_OUT) g.out_chan_stride = (int)c.dst->chan_stride, g.dst_bytes = (unsigned)c.dst->named;
     if constexpr (PLANAR) {
         g.chan_stride = (int)c.src->chan_stride;
         g.src_bytes = (unsigned)((c.d->channels - 1) * c.src->chan_stride + (c.d->in_h - 1) * c.src->row_stride + c.d->in_w);
     }
-    if constexpr ((TENSOR & ~(kRsPlanar | kRsRowShift)) != 0) {
+    if constexpr ((TENSOR & ~(kRsPlanar | kRsRowShift | kRsPlanarOut)) != 0) {
         g.lut = (const uint32_t*)c.tc->t.d_lut;
         g.cs = (int)c.tc->t.chan_stride, g.rs = (int)c.tc->t.row_stride, g.ps = (int)c.tc->t.pix_stride;   // extent below 2^31 bytes
         g.extent_bytes = (unsigned)c.tc->extent_bytes;
@@ -629,7 +758,7 @@ hipError_t rs_launch_fused(const RsFusedLaunch& c) {
         bool launched = false;
         rs_dispatch_instance(c.d->channels, fp.K, alpha, [&](auto ch, auto k, auto a) {
             // alpha is 8-bit only (resize_validate); a planar source of one channel is the interleaved one
-            if constexpr ((!decltype(a)::value || BPS == 1) && (!PLANAR || decltype(ch)::value >= 3) &&
+            if constexpr ((!decltype(a)::value || BPS == 1) && (!(PLANAR || PLANAR_OUT) || decltype(ch)::value >= 3) &&
                           (!ROWSHIFT || decltype(a)::value)) {
                 hipLaunchKernelGGL((k_rs_fused<S, decltype(ch)::value, decltype(k)::value, decltype(a)::value, TENSOR>), grid,
                                    dim3(kRsThreads), fp.lds, c.stream, g);
@@ -656,6 +785,8 @@ extern template hipError_t rs_launch_fused<1, 2 + kRsMapped + kRsPlanar>(const R
 extern template hipError_t rs_launch_fused<1, kRsRowShift>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<1, 4 + kRsMapped + kRsRowShift>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<1, 2 + kRsMapped + kRsRowShift>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<1, kRsPlanarOut>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<1, kRsPlanar + kRsPlanarOut>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<2, 0>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<4, 0>(const RsFusedLaunch&);
 

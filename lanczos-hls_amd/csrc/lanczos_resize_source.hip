@@ -56,14 +56,6 @@ struct RsPack {
     unsigned npix;                    // w * h (planar: below 2^32)
 };
 
-__device__ __forceinline__ uint32_t rs_load_dword_at(const uint8_t* p) {
-    const unsigned sh = (unsigned)((uintptr_t)p & 3);
-    const uint32_t* q = (const uint32_t*)(p - sh);
-    const uint32_t lo = q[0];
-    const uint32_t up = sh != 0 ? q[1] : 0u;
-    return __builtin_amdgcn_alignbyte(up, lo, sh);
-}
-
 // planar, C = 3 or 4: a thread takes pixels q0 .. q0 + 3 of the frame in raster order (q0 a multiple of 4, so its C dwords of the
 // packed frame are aligned).  Where the four lie in one row: a dword per plane and the byte transpose of the fused staging;
 // across a row end: byte loads

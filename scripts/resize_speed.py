@@ -118,6 +118,14 @@ multiple: every row another residue) -> 341x256, bytes out and normalised bfloat
   floor         the call without a source alone, on frames that are already packed
 Frame 0 of all five is compared bit for bit before timing; a last line gives the ratios.
 
+DST1, DSTP, DSTPW and DSTW are destination-layout workloads (lanczos_resize_dest: planes or pitched rows stored by the library;
+--only DST1,DSTP,DSTPW,DSTW; a build with the entry), RGB8, bytes out.  DST1: 32 interleaved frames of 3840x2160 -> 1920x1080 into
+planes; DSTP: 256 planar frames of 500x375 -> 341x256 into planes (an odd width: three plane rows in four start off a dword);
+DSTPW: the same with the centre 224x224 window; DSTW: 32 frames of 1920x1080 -> 3840x2160 into rows pitched to a multiple of 256
+bytes that is not the tight pitch (11776); DSTA and DST4 (--only DSTA,DST4): DSTP with four channels and alpha, DST1 with four
+channels.  Routes: direct, unpacked, auto, torch_repack and floor (run_dest); the dword form of the planar epilogue is the direct
+route of a library built with EXTRA=-DLZ_RS_PLANAR_OUT_DWORDS and loaded through LANCZOS_LIB.
+
 --pillow adds Pillow's single-core time of one frame of each workload (if Pillow imports; else "not available"); for U1 and
 U4 that is the time of one I;16 plane (a frame has three), for F1 and F4 that of one F plane.
 """
@@ -879,6 +887,94 @@ def run_source(name, args, ctx, torch):
     torch.cuda.empty_cache()
 
 
+DEST_WORKLOADS = {   # name: (in_w, in_h, out_w, out_h, frames, planar source, planar destination, row alignment (bytes), crop (w, h) from the centre, channels, alpha)
+    "DST1": (3840, 2160, 1920, 1080, 32, False, True, 1, None, 3, False),
+    "DSTP": (500, 375, 341, 256, 256, True, True, 1, None, 3, False),          # an odd width: three plane rows in four start off a dword
+    "DSTPW": (500, 375, 341, 256, 256, True, True, 1, (224, 224), 3, False),
+    "DSTW": (1920, 1080, 3840, 2160, 32, False, False, 256, None, 3, False),   # interleaved rows pitched to a multiple of 256 bytes
+    "DSTA": (500, 375, 341, 256, 256, True, True, 1, None, 4, True),           # DSTP with four channels and LANCZOS_RESIZE_ALPHA
+    "DST4": (3840, 2160, 1920, 1080, 32, False, True, 1, None, 4, False),      # DST1 with four channels
+}
+
+
+def run_dest(name, args, ctx, torch):
+    """A destination layout (lanczos_resize_dest) against what it replaces: direct (the fused kernel stores the planes or pitched
+    rows itself; with a library built with -DLZ_RS_PLANAR_OUT_DWORDS, loaded through LANCZOS_LIB, this is the dword form of the
+    planar epilogue), unpacked (the same request under RESIZE_CONVERT: k_rs_unpack_dest last), auto, torch_repack
+    (the call without a destination, then permute(0, 3, 1, 2).contiguous(), or the copy into the pitched rows) and floor (that
+    call alone).  RGB8, bytes out."""
+    iw, ih, ow, oh, f, planar_in, planar_out, align, crop, c, alpha = DEST_WORKLOADS[name]
+    window = L.center_window(ow, oh, *crop) if crop else None
+    w, h = (window[2], window[3]) if window else (ow, oh)
+    d = L.resize_desc(iw, ih, ow, oh, c, alpha=alpha)
+    win = L.resize_window(d, window) if window else None
+    pitch = -(-w * c // align) * align
+    if not planar_out and pitch == w * c:     # already a multiple: one more unit, or the destination would be the tight one
+        pitch += align
+    dst = L.resize_dest(d, "planar", window=window) if planar_out else L.resize_dest(d, "interleaved", row_stride=pitch, window=window)
+    L.resize_dest_validate(d, dst, window=window)
+    src = L.resize_source(d, "planar") if planar_in else None
+    in_fb, out_fb = iw * ih * c, w * h * c
+    dst_fb = out_fb if planar_out else h * pitch            # bytes of a frame as the caller holds it
+    sets = max(2, -(-2 * 256 * 2 ** 20 // (f * in_fb)) + 1)
+    gen = torch.Generator(device="cuda").manual_seed(12)
+    xs = [torch.randint(0, 256, (f * in_fb,), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(sets)]
+    if planar_in:   # the same frames interleaved, for the call without a layout
+        packed = [x.view(f, c, ih, iw).permute(0, 2, 3, 1).contiguous() for x in xs]
+    else:
+        packed = xs
+    ys = [torch.zeros(f * dst_fb, dtype=torch.uint8, device="cuda") for _ in range(sets)]
+    tmp = torch.empty(f * out_fb, dtype=torch.uint8, device="cuda")
+    s = torch.cuda.current_stream().cuda_stream
+    seen = {}
+
+    def named(y):   # the bytes of frame 0 in one order, whatever the layout
+        if planar_out:
+            return y[:out_fb].view(c, h, w).permute(1, 2, 0).contiguous()
+        return y[:dst_fb].view(h, pitch)[:, :w * c].contiguous().view(h, w, c)
+
+    def with_dest(path):
+        def step(i):
+            ctx.resize_force(path)
+            ctx.resize_device(d, xs[i % sets].data_ptr(), ys[i % sets].data_ptr(), f, stream=s, window=win, source=src, dest=dst)
+            seen[path] = ctx.last_dest_route()
+            return named(ys[i % sets])
+        return step
+
+    def torch_repack(i):
+        ctx.resize_force(L.RESIZE_AUTO)
+        ctx.resize_device(d, xs[i % sets].data_ptr(), tmp.data_ptr(), f, stream=s, window=win, source=src)
+        y = ys[i % sets]
+        if planar_out:
+            y.view(f, c, h, w).copy_(tmp.view(f, h, w, c).permute(0, 3, 1, 2))
+        else:
+            y.view(f, h, pitch)[:, :, :w * c].copy_(tmp.view(f, h, w * c))
+        return named(y)
+
+    def floor(i):
+        ctx.resize_force(L.RESIZE_AUTO)
+        ctx.resize_device(d, packed[i % sets].data_ptr(), tmp.data_ptr(), f, stream=s, window=win)
+        return tmp[:out_fb].view(h, w, c)
+
+    routes = {"direct": with_dest(L.RESIZE_FUSED), "unpacked": with_dest(L.RESIZE_CONVERT), "auto": with_dest(L.RESIZE_AUTO),
+              "torch_repack": torch_repack, "floor": floor}
+    inb = {rn: f * in_fb for rn in routes}
+    outb = {rn: f * out_fb for rn in routes}
+    us = run_routes(name, f"{iw}x{ih}->{ow}x{oh} C{c}{' alpha' if alpha else ''} {'planar' if planar_in else 'interleaved'} in, " +
+                    ("planar out" if planar_out else f"rows pitched to {pitch} out") + (f" window {window}" if window else ""), f, routes,
+                    inb, outb, args, ctx, torch, check=(("direct", "unpacked"), ("direct", "torch_repack"), ("direct", "floor"), ("direct", "auto")))
+    ctx.resize_force(L.RESIZE_AUTO)
+    if (seen[L.RESIZE_FUSED], seen[L.RESIZE_CONVERT]) != (L.DEST_DIRECT, L.DEST_UNPACKED):
+        raise SystemExit(f"{name}: routes {seen}")
+    print(json.dumps({"workload": name, "auto_route": {L.DEST_DIRECT: "direct", L.DEST_UNPACKED: "unpacked"}[seen[L.RESIZE_AUTO]],
+                      "direct_over_unpacked": round(us["direct"] / us["unpacked"], 3),
+                      "direct_over_torch_repack": round(us["direct"] / us["torch_repack"], 3),
+                      "unpacked_over_torch_repack": round(us["unpacked"] / us["torch_repack"], 3),
+                      "direct_over_floor": round(us["direct"] / us["floor"], 3), "measured": True}), flush=True)
+    del xs, ys, packed, tmp
+    torch.cuda.empty_cache()
+
+
 def run_gap(name, args, ctx, torch):
     iw, ih, ow, oh, c, a, f = WORKLOADS["W5"]
     in_fb, out_fb = iw * ih * c, ow * oh * c
@@ -978,6 +1074,8 @@ def main():
             run_crops(name, args, ctx, torch)
         elif name in SOURCE_WORKLOADS:
             run_source(name, args, ctx, torch)
+        elif name in DEST_WORKLOADS:
+            run_dest(name, args, ctx, torch)
         elif name in VIEW_WORKLOADS:
             run_view(name, args, ctx, torch)
         elif name in TENSOR_WORKLOADS:
