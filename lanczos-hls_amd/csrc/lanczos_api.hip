@@ -1196,7 +1196,7 @@ int lanczos_resize_window_plan_host(const lanczos_resize_desc* d, const lanczos_
     int rc = lz::resize_validate(d);
     if (rc != LANCZOS_OK) return rc;
     if (frames < 1 || !out) return LANCZOS_ERR_BAD_ARG;
-    return lz::resize_plan_host(d, o, win, frames, out);
+    return lz::resize_plan_host(d, o, win, frames, out, nullptr);
 }
 
 int lanczos_resize_plan_host_ex(const lanczos_resize_desc* d, const lanczos_resize_opts* o, int frames,
@@ -1242,19 +1242,106 @@ static int resize_state(lanczos_ctx* ctx) {
     return ctx->resize ? LANCZOS_OK : LANCZOS_ERR_NOMEM;
 }
 
+// Every lanczos_resize_*_device / _host entry is: null checks, its validators, fill the request, resize_run.
+extern "C++" {
+// the buffers of an entry.  Device: NULL stream = the legacy default stream, as lanczos_resample_device.  Host: the context's
+struct ResizeBufs {
+    const void* in;
+    void* out;
+    int frames;
+    size_t in_frame_stride, out_frame_stride;
+    void* stream;
+    bool host;
+    bool null() const { return !in || !out || frames <= 0; }
+};
+static ResizeBufs host_bufs(const void* in, void* out, int frames) { return ResizeBufs{in, out, frames, 0, 0, nullptr, true}; }
+
+static lz::RsRequest resize_request(const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                                    const ResizeBufs& b) {
+    lz::RsRequest q;
+    q.d = d, q.o = o, q.win = win;
+    q.in = b.in, q.out = b.out, q.frames = b.frames;
+    q.in_frame_stride = b.in_frame_stride, q.out_frame_stride = b.out_frame_stride, q.stream = (hipStream_t)b.stream;
+    return q;
+}
+
+// what follows the validation of every resize: the context's lock, its device, its state, the call, the routes it took
+static int resize_run(lanczos_ctx* ctx, lz::RsRequest& q, bool host) {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    if (host && !ctx->stream) return LANCZOS_ERR_HIP;
+    int rc = resize_state(ctx);
+    if (rc != LANCZOS_OK) return rc;
+    route_begin(ctx);
+    if (host) q.stream = ctx->stream;
+    q.last_kernel = &ctx->last_kernel, q.last_hip = &ctx->last_hip;
+    rc = host ? lz::resize_host(ctx->resize, q) : lz::resize_device(ctx->resize, q);
+    if (q.tensor) ctx->last_tensor_route = q.tc.route;   // also of a call that failed once its launches were out
+    if (rc == LANCZOS_OK && q.source && q.sc.route) ctx->last_source_route = q.sc.route;   // a refused or failed call leaves them
+    if (rc == LANCZOS_OK && q.dest && q.dc.route) ctx->last_dest_route = q.dc.route;
+    return rc;
+}
+
+// bytes out.  src / dst NULL: the entry without that parameter
+static int resize_bytes(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                        const lanczos_resize_source* src, const lanczos_resize_dest* dst, const ResizeBufs& b) {
+    if (!ctx || b.null()) return LANCZOS_ERR_BAD_ARG;
+    lz::RsRequest q = resize_request(d, o, win, b);
+    q.source = src != nullptr, q.dest = dst != nullptr;
+    int rc = lz::resize_validate(d);
+    lz::RsWindow w;   // a destination is resolved for the window
+    if (rc == LANCZOS_OK && dst) rc = lz::resize_window_resolve(d, win, &w);
+    if (rc == LANCZOS_OK && src) rc = lz::resize_source_resolve(d, src, &q.sc.s);
+    if (rc == LANCZOS_OK && dst) rc = lz::resize_dest_resolve(d, w, dst, &q.dc.s);
+    return rc != LANCZOS_OK ? rc : resize_run(ctx, q, b.host);
+}
+
+// The float and the 16-bit tensor entries are one request (lz::RsTensorOut) with another element width
+template <class T>
+static int resize_tensor(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                         const T* t, int elem, const ResizeBufs& b) {
+    if (!ctx || b.null()) return LANCZOS_ERR_BAD_ARG;
+    lz::RsRequest q = resize_request(d, o, win, b);
+    q.tensor = true;
+    const int rc = lz::tensor_validate(d, win, t, elem, &q.tc.t);
+    return rc != LANCZOS_OK ? rc : resize_run(ctx, q, b.host);
+}
+
+// a crops request is a view whose frame is the window (0, 0, w, h): validated as one, *win filled
+static int tensor_crops_validate(const lanczos_resize_desc* d, const lanczos_resize_crops* crops, const lanczos_tensor_view* v,
+                                 lanczos_resize_window* win, lz::RsTensorOut* lay) {
+    const int rc = lz::resize_crops_validate(d, crops);
+    if (rc != LANCZOS_OK) return rc;
+    *win = lanczos_resize_window{0, 0, crops->w, crops->h, {0, 0, 0, 0}};
+    return lz::tensor_view_validate(d, win, v, lay);
+}
+
+// ... and so are the entries of a view, with a window or with crops (not both), with or without a source.  cropped: the entry
+// takes crops (NULL is then refused), not a window
+static int resize_view(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                       const lanczos_resize_crops* crops, bool cropped, const lanczos_resize_source* src, const lanczos_tensor_view* v,
+                       const ResizeBufs& b) {
+    if (win && crops) return LANCZOS_ERR_BAD_ARG;
+    if (!ctx || b.null()) return LANCZOS_ERR_BAD_ARG;
+    lanczos_resize_window cw;
+    lz::RsRequest q = resize_request(d, o, cropped ? &cw : win, b);
+    q.tensor = true, q.source = src != nullptr;
+    int rc = cropped ? tensor_crops_validate(d, crops, v, &cw, &q.tc.t) : lz::tensor_view_validate(d, win, v, &q.tc.t);
+    if (rc == LANCZOS_OK && src) rc = lz::resize_source_resolve(d, src, &q.sc.s);
+    if (rc != LANCZOS_OK) return rc;
+    if (crops) q.tc.d_origin = crops->d_origin;
+    for (int f = 0; crops && b.host && f < b.frames; f++) {   // a host array can be validated: nothing is clamped here
+        const int32_t x0 = crops->d_origin[2 * f], y0 = crops->d_origin[2 * f + 1];
+        if (x0 < 0 || x0 > d->out_w - crops->w || y0 < 0 || y0 > d->out_h - crops->h) return LANCZOS_ERR_BAD_ARG;
+    }
+    return resize_run(ctx, q, b.host);
+}
+}   // extern "C++"
+
 int lanczos_resize_window_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
                                  const lanczos_resize_window* win, const void* d_in, void* d_out, int frames,
                                  size_t in_frame_stride, size_t out_frame_stride, void* stream) {
-    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    int rc = lz::resize_validate(d);
-    if (rc != LANCZOS_OK) return rc;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    LZ_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
-    route_begin(ctx);
-    // NULL = the legacy default stream, as lanczos_resample_device
-    return lz::resize_device(ctx->resize, d, o, win, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
-                             &ctx->last_kernel, &ctx->last_hip);
+    return resize_bytes(ctx, d, o, win, nullptr, nullptr, {d_in, d_out, frames, in_frame_stride, out_frame_stride, stream, false});
 }
 
 int lanczos_resize_device_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* d_in,
@@ -1269,15 +1356,7 @@ int lanczos_resize_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const 
 
 int lanczos_resize_window_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
                                const lanczos_resize_window* win, const void* in, void* out, int frames) {
-    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    int rc = lz::resize_validate(d);
-    if (rc != LANCZOS_OK) return rc;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    LZ_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->stream) return LANCZOS_ERR_HIP;
-    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
-    route_begin(ctx);
-    return lz::resize_host(ctx->resize, d, o, win, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip);
+    return resize_bytes(ctx, d, o, win, nullptr, nullptr, host_bufs(in, out, frames));
 }
 
 int lanczos_resize_host_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const void* in,
@@ -1288,65 +1367,6 @@ int lanczos_resize_host_ex(lanczos_ctx* ctx, const lanczos_resize_desc* d, const
 int lanczos_resize_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const void* in, void* out, int frames) {
     return lanczos_resize_host_ex(ctx, d, nullptr, in, out, frames);
 }
-
-// The float and the 16-bit tensor entries are one request (lz::RsTensorOut) with another element width
-extern "C++" {
-// what follows the validation of a device request (tc.t filled)
-static int tensor_device_run(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
-                             const lanczos_resize_window* win, lz::RsTensorCall& tc, const void* d_in, void* d_out, int frames,
-                             size_t in_frame_stride, size_t out_frame_stride, void* stream, lz::RsSourceCall* sc = nullptr) {
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    LZ_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = resize_state(ctx);
-    if (rc != LANCZOS_OK) return rc;
-    route_begin(ctx);
-    lz::RsWindow w;
-    (void)lz::resize_window_resolve(d, win, &w);   // validated by the caller
-    tc.extent_bytes = lz::tensor_extent_bytes(d, w, tc.t);
-    rc = lz::resize_device(ctx->resize, d, opts, win, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
-                           &ctx->last_kernel, &ctx->last_hip, &tc, sc);
-    ctx->last_tensor_route = tc.route;
-    if (rc == LANCZOS_OK && sc && sc->route) ctx->last_source_route = sc->route;   // a refused or failed call leaves it
-    return rc;
-}
-
-template <class T>
-static int tensor_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
-                         const lanczos_resize_window* win, const T* t, int elem, const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
-    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    lz::RsTensorCall tc;
-    const int rc = lz::tensor_validate(d, win, t, elem, &tc.t);
-    if (rc != LANCZOS_OK) return rc;
-    return tensor_device_run(ctx, d, opts, win, tc, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
-}
-
-// ... and of a host request (lay filled)
-static int tensor_host_run(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
-                           const lanczos_resize_window* win, const lz::RsTensorOut& lay, const void* in, void* out, int frames,
-                           const int32_t* origins = nullptr, lz::RsSourceCall* sc = nullptr) {
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    LZ_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->stream) return LANCZOS_ERR_HIP;
-    int rc = resize_state(ctx);
-    if (rc != LANCZOS_OK) return rc;
-    route_begin(ctx);
-    rc = lz::resize_tensor_host(ctx->resize, d, opts, win, lay, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip,
-                                &ctx->last_tensor_route, origins, sc);
-    if (rc == LANCZOS_OK && sc && sc->route) ctx->last_source_route = sc->route;   // a refused or failed call leaves it
-    return rc;
-}
-
-template <class T>
-static int tensor_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
-                       const lanczos_resize_window* win, const T* t, int elem, const void* in, void* out, int frames) {
-    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    lz::RsTensorOut lay;
-    const int rc = lz::tensor_validate(d, win, t, elem, &lay);
-    if (rc != LANCZOS_OK) return rc;
-    return tensor_host_run(ctx, d, opts, win, lay, in, out, frames);
-}
-
-}   // extern "C++"
 
 int lanczos_resize_tensor_window_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win,
                                           const lanczos_tensor_out* t) {
@@ -1367,24 +1387,24 @@ int lanczos_tensor_lut_normalize(int channels, const float* mean, const float* s
 int lanczos_resize_tensor_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                  const lanczos_tensor_out* t, const void* d_in, void* d_out, int frames,
                                  size_t in_frame_stride, size_t out_frame_stride, void* stream) {
-    return tensor_device(ctx, d, opts, nullptr, t, 4, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+    return resize_tensor(ctx, d, opts, nullptr, t, 4, {d_in, d_out, frames, in_frame_stride, out_frame_stride, stream, false});
 }
 
 int lanczos_resize_tensor_window_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                         const lanczos_resize_window* win, const lanczos_tensor_out* t, const void* d_in,
                                         void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
-    return tensor_device(ctx, d, opts, win, t, 4, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+    return resize_tensor(ctx, d, opts, win, t, 4, {d_in, d_out, frames, in_frame_stride, out_frame_stride, stream, false});
 }
 
 int lanczos_resize_tensor_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                const lanczos_tensor_out* t, const void* in, void* out, int frames) {
-    return tensor_host(ctx, d, opts, nullptr, t, 4, in, out, frames);
+    return resize_tensor(ctx, d, opts, nullptr, t, 4, host_bufs(in, out, frames));
 }
 
 int lanczos_resize_tensor_window_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                       const lanczos_resize_window* win, const lanczos_tensor_out* t, const void* in, void* out,
                                       int frames) {
-    return tensor_host(ctx, d, opts, win, t, 4, in, out, frames);
+    return resize_tensor(ctx, d, opts, win, t, 4, host_bufs(in, out, frames));
 }
 
 int lanczos_resize_tensor16_window_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win,
@@ -1411,25 +1431,25 @@ int lanczos_tensor16_lut_normalize(int channels, const float* mean, const float*
 int lanczos_resize_tensor16_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                    const lanczos_tensor16_out* t, const void* d_in, void* d_out, int frames,
                                    size_t in_frame_stride, size_t out_frame_stride, void* stream) {
-    return tensor_device(ctx, d, opts, nullptr, t, 2, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+    return resize_tensor(ctx, d, opts, nullptr, t, 2, {d_in, d_out, frames, in_frame_stride, out_frame_stride, stream, false});
 }
 
 int lanczos_resize_tensor16_window_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                           const lanczos_resize_window* win, const lanczos_tensor16_out* t, const void* d_in,
                                           void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride,
                                           void* stream) {
-    return tensor_device(ctx, d, opts, win, t, 2, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+    return resize_tensor(ctx, d, opts, win, t, 2, {d_in, d_out, frames, in_frame_stride, out_frame_stride, stream, false});
 }
 
 int lanczos_resize_tensor16_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                  const lanczos_tensor16_out* t, const void* in, void* out, int frames) {
-    return tensor_host(ctx, d, opts, nullptr, t, 2, in, out, frames);
+    return resize_tensor(ctx, d, opts, nullptr, t, 2, host_bufs(in, out, frames));
 }
 
 int lanczos_resize_tensor16_window_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                         const lanczos_resize_window* win, const lanczos_tensor16_out* t, const void* in,
                                         void* out, int frames) {
-    return tensor_host(ctx, d, opts, win, t, 2, in, out, frames);
+    return resize_tensor(ctx, d, opts, win, t, 2, host_bufs(in, out, frames));
 }
 
 int lanczos_tensor_view_init(lanczos_tensor_view* v, const lanczos_resize_desc* d, int elem_bytes) {
@@ -1452,21 +1472,13 @@ int lanczos_resize_tensor_view_validate(const lanczos_resize_desc* d, const lanc
 int lanczos_resize_tensor_view_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                       const lanczos_resize_window* win, const lanczos_tensor_view* v, const void* d_in,
                                       void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
-    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    lz::RsTensorCall tc;
-    const int rc = lz::tensor_view_validate(d, win, v, &tc.t);
-    if (rc != LANCZOS_OK) return rc;
-    return tensor_device_run(ctx, d, opts, win, tc, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+    return resize_view(ctx, d, opts, win, nullptr, false, nullptr, v, {d_in, d_out, frames, in_frame_stride, out_frame_stride, stream, false});
 }
 
 int lanczos_resize_tensor_view_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                     const lanczos_resize_window* win, const lanczos_tensor_view* v, const void* in, void* out,
                                     int frames) {
-    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    lz::RsTensorOut lay;
-    const int rc = lz::tensor_view_validate(d, win, v, &lay);
-    if (rc != LANCZOS_OK) return rc;
-    return tensor_host_run(ctx, d, opts, win, lay, in, out, frames);
+    return resize_view(ctx, d, opts, win, nullptr, false, nullptr, v, host_bufs(in, out, frames));
 }
 
 int lanczos_resize_crops_validate(const lanczos_resize_desc* d, const lanczos_resize_crops* crops) {
@@ -1481,17 +1493,6 @@ int lanczos_resize_crops_plan_host(const lanczos_resize_desc* d, const lanczos_r
     return lz::resize_plan_host(d, o, nullptr, frames, out, crops);
 }
 
-extern "C++" {
-// a crops request is a view whose frame is the window (0, 0, w, h): validated as one, *win filled
-static int tensor_crops_validate(const lanczos_resize_desc* d, const lanczos_resize_crops* crops, const lanczos_tensor_view* v,
-                                 lanczos_resize_window* win, lz::RsTensorOut* lay) {
-    const int rc = lz::resize_crops_validate(d, crops);
-    if (rc != LANCZOS_OK) return rc;
-    *win = lanczos_resize_window{0, 0, crops->w, crops->h, {0, 0, 0, 0}};
-    return lz::tensor_view_validate(d, win, v, lay);
-}
-}   // extern "C++"
-
 int lanczos_resize_tensor_crops_validate(const lanczos_resize_desc* d, const lanczos_resize_crops* crops,
                                          const lanczos_tensor_view* v) {
     lanczos_resize_window win;
@@ -1502,28 +1503,13 @@ int lanczos_resize_tensor_crops_validate(const lanczos_resize_desc* d, const lan
 int lanczos_resize_tensor_crops_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                        const lanczos_resize_crops* crops, const lanczos_tensor_view* v, const void* d_in,
                                        void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
-    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    lanczos_resize_window win;
-    lz::RsTensorCall tc;
-    const int rc = tensor_crops_validate(d, crops, v, &win, &tc.t);
-    if (rc != LANCZOS_OK) return rc;
-    tc.d_origin = crops->d_origin;
-    return tensor_device_run(ctx, d, opts, &win, tc, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
+    return resize_view(ctx, d, opts, nullptr, crops, true, nullptr, v, {d_in, d_out, frames, in_frame_stride, out_frame_stride, stream, false});
 }
 
 int lanczos_resize_tensor_crops_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                      const lanczos_resize_crops* crops, const lanczos_tensor_view* v, const void* in, void* out,
                                      int frames) {
-    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    lanczos_resize_window win;
-    lz::RsTensorOut lay;
-    const int rc = tensor_crops_validate(d, crops, v, &win, &lay);
-    if (rc != LANCZOS_OK) return rc;
-    for (int f = 0; f < frames; f++) {   // a host array can be validated: nothing is clamped here
-        const int32_t x0 = crops->d_origin[2 * f], y0 = crops->d_origin[2 * f + 1];
-        if (x0 < 0 || x0 > d->out_w - crops->w || y0 < 0 || y0 > d->out_h - crops->h) return LANCZOS_ERR_BAD_ARG;
-    }
-    return tensor_host_run(ctx, d, opts, &win, lay, in, out, frames, crops->d_origin);
+    return resize_view(ctx, d, opts, nullptr, crops, true, nullptr, v, host_bufs(in, out, frames));
 }
 
 int lanczos_last_tensor_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_tensor_route : 0; }
@@ -1554,83 +1540,27 @@ int lanczos_resize_source_validate(const lanczos_resize_desc* d, const lanczos_r
 int lanczos_resize_source_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
                                  const lanczos_resize_window* win, const lanczos_resize_source* src, const void* d_in,
                                  void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
-    if (!src) return lanczos_resize_window_device(ctx, d, o, win, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
-    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    int rc = lz::resize_validate(d);
-    lz::RsSourceCall sc;
-    if (rc == LANCZOS_OK) rc = lz::resize_source_resolve(d, src, &sc.s);
-    if (rc != LANCZOS_OK) return rc;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    LZ_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
-    route_begin(ctx);
-    rc = lz::resize_device(ctx->resize, d, o, win, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
-                           &ctx->last_kernel, &ctx->last_hip, nullptr, &sc);
-    if (rc == LANCZOS_OK && sc.route) ctx->last_source_route = sc.route;   // a refused or failed call leaves it
-    return rc;
+    return resize_bytes(ctx, d, o, win, src, nullptr, {d_in, d_out, frames, in_frame_stride, out_frame_stride, stream, false});
 }
 
 int lanczos_resize_source_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
                                const lanczos_resize_window* win, const lanczos_resize_source* src, const void* in, void* out,
                                int frames) {
-    if (!src) return lanczos_resize_window_host(ctx, d, o, win, in, out, frames);
-    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    int rc = lz::resize_validate(d);
-    lz::RsSourceCall sc;
-    if (rc == LANCZOS_OK) rc = lz::resize_source_resolve(d, src, &sc.s);
-    if (rc != LANCZOS_OK) return rc;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    LZ_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->stream) return LANCZOS_ERR_HIP;
-    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
-    route_begin(ctx);
-    rc = lz::resize_host(ctx->resize, d, o, win, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip, &sc);
-    if (rc == LANCZOS_OK && sc.route) ctx->last_source_route = sc.route;   // a refused or failed call leaves it
-    return rc;
+    return resize_bytes(ctx, d, o, win, src, nullptr, host_bufs(in, out, frames));
 }
 
 int lanczos_resize_tensor_source_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                         const lanczos_resize_window* win, const lanczos_resize_crops* crops,
                                         const lanczos_resize_source* src, const lanczos_tensor_view* v, const void* d_in,
                                         void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, void* stream) {
-    if (win && crops) return LANCZOS_ERR_BAD_ARG;
-    if (!src)
-        return crops ? lanczos_resize_tensor_crops_device(ctx, d, opts, crops, v, d_in, d_out, frames, in_frame_stride,
-                                                          out_frame_stride, stream)
-                     : lanczos_resize_tensor_view_device(ctx, d, opts, win, v, d_in, d_out, frames, in_frame_stride,
-                                                         out_frame_stride, stream);
-    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    lanczos_resize_window cw;
-    lz::RsTensorCall tc;
-    lz::RsSourceCall sc;
-    int rc = crops ? tensor_crops_validate(d, crops, v, &cw, &tc.t) : lz::tensor_view_validate(d, win, v, &tc.t);
-    if (rc == LANCZOS_OK) rc = lz::resize_source_resolve(d, src, &sc.s);
-    if (rc != LANCZOS_OK) return rc;
-    if (crops) tc.d_origin = crops->d_origin;
-    return tensor_device_run(ctx, d, opts, crops ? &cw : win, tc, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream, &sc);
+    return resize_view(ctx, d, opts, win, crops, crops != nullptr, src, v, {d_in, d_out, frames, in_frame_stride, out_frame_stride, stream, false});
 }
 
 int lanczos_resize_tensor_source_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                                       const lanczos_resize_window* win, const lanczos_resize_crops* crops,
                                       const lanczos_resize_source* src, const lanczos_tensor_view* v, const void* in, void* out,
                                       int frames) {
-    if (win && crops) return LANCZOS_ERR_BAD_ARG;
-    if (!src)
-        return crops ? lanczos_resize_tensor_crops_host(ctx, d, opts, crops, v, in, out, frames)
-                     : lanczos_resize_tensor_view_host(ctx, d, opts, win, v, in, out, frames);
-    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    lanczos_resize_window cw;
-    lz::RsTensorOut lay;
-    lz::RsSourceCall sc;
-    int rc = crops ? tensor_crops_validate(d, crops, v, &cw, &lay) : lz::tensor_view_validate(d, win, v, &lay);
-    if (rc == LANCZOS_OK) rc = lz::resize_source_resolve(d, src, &sc.s);
-    if (rc != LANCZOS_OK) return rc;
-    if (crops)
-        for (int f = 0; f < frames; f++) {   // as lanczos_resize_tensor_crops_host: a host array is validated, not clamped
-            const int32_t x0 = crops->d_origin[2 * f], y0 = crops->d_origin[2 * f + 1];
-            if (x0 < 0 || x0 > d->out_w - crops->w || y0 < 0 || y0 > d->out_h - crops->h) return LANCZOS_ERR_BAD_ARG;
-        }
-    return tensor_host_run(ctx, d, opts, crops ? &cw : win, lay, in, out, frames, crops ? crops->d_origin : nullptr, &sc);
+    return resize_view(ctx, d, opts, win, crops, crops != nullptr, src, v, host_bufs(in, out, frames));
 }
 
 int lanczos_last_source_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_source_route : 0; }
@@ -1662,51 +1592,17 @@ int lanczos_resize_dest_validate(const lanczos_resize_desc* d, const lanczos_res
     return lz::resize_dest_resolve(d, w, dst, &s);
 }
 
-extern "C++" {
-// what the two entries with a destination share: everything validated and resolved, then `run` under the context's lock
-template <class F>
-static int dest_call(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_resize_source* src,
-                     const lanczos_resize_dest* dst, bool host, F&& run) {
-    int rc = lz::resize_validate(d);
-    lz::RsWindow w;
-    lz::RsSourceCall sc;
-    lz::RsDestCall dc;
-    if (rc == LANCZOS_OK) rc = lz::resize_window_resolve(d, win, &w);
-    if (rc == LANCZOS_OK) rc = lz::resize_source_resolve(d, src, &sc.s);
-    if (rc == LANCZOS_OK) rc = lz::resize_dest_resolve(d, w, dst, &dc.s);
-    if (rc != LANCZOS_OK) return rc;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    LZ_HIP(ctx, hipSetDevice(ctx->device));
-    if (host && !ctx->stream) return LANCZOS_ERR_HIP;
-    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
-    route_begin(ctx);
-    rc = run(src ? &sc : nullptr, &dc);
-    if (rc == LANCZOS_OK && src && sc.route) ctx->last_source_route = sc.route;   // a refused or failed call leaves them
-    if (rc == LANCZOS_OK && dc.route) ctx->last_dest_route = dc.route;
-    return rc;
-}
-}   // extern "C++"
-
 int lanczos_resize_dest_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
                                const lanczos_resize_window* win, const lanczos_resize_source* src, const lanczos_resize_dest* dst,
                                const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride,
                                void* stream) {
-    if (!dst) return lanczos_resize_source_device(ctx, d, o, win, src, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream);
-    if (!ctx || !d_in || !d_out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    return dest_call(ctx, d, win, src, dst, false, [&](lz::RsSourceCall* sc, lz::RsDestCall* dc) {
-        return lz::resize_device(ctx->resize, d, o, win, d_in, d_out, frames, in_frame_stride, out_frame_stride, (hipStream_t)stream,
-                                 &ctx->last_kernel, &ctx->last_hip, nullptr, sc, dc);
-    });
+    return resize_bytes(ctx, d, o, win, src, dst, {d_in, d_out, frames, in_frame_stride, out_frame_stride, stream, false});
 }
 
 int lanczos_resize_dest_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
                              const lanczos_resize_window* win, const lanczos_resize_source* src, const lanczos_resize_dest* dst,
                              const void* in, void* out, int frames) {
-    if (!dst) return lanczos_resize_source_host(ctx, d, o, win, src, in, out, frames);
-    if (!ctx || !in || !out || frames <= 0) return LANCZOS_ERR_BAD_ARG;
-    return dest_call(ctx, d, win, src, dst, true, [&](lz::RsSourceCall* sc, lz::RsDestCall* dc) {
-        return lz::resize_host(ctx->resize, d, o, win, in, out, frames, ctx->stream, &ctx->last_kernel, &ctx->last_hip, sc, dc);
-    });
+    return resize_bytes(ctx, d, o, win, src, dst, host_bufs(in, out, frames));
 }
 
 int lanczos_last_dest_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_dest_route : 0; }

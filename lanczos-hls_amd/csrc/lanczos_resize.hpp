@@ -1,5 +1,7 @@
 // lanczos_resize.hpp -- resize to any size with Pillow's contract (include/lanczos_hip.h, lanczos_resize_*): host tap tables,
-// their per-context cache, and the entry points lanczos_api.hip forwards to.  Tables, cache, planning and dispatch are in
+// their per-context cache, and the entry points lanczos_api.hip forwards to.  What needs no device is in lanczos_resize_route.cpp:
+// validation, tables, resolution, planning and rs_route, the one decision of what a request launches.  The table cache, the
+// scratch, the executor of a route (resize_device), the staging of the host entries and the alpha pass kernels are in
 // lanczos_resize.hip.  The kernels are written once for 8-bit, 16-bit (LANCZOS_RESIZE_U16) and float (LANCZOS_RESIZE_F32)
 // samples in lanczos_resize_fused.hpp; the fused instances are compiled by lanczos_resize.hip (8-bit), lanczos_resize_tensor.hip
 // (8-bit into float tensors), lanczos_resize_tensor16.hip (8-bit into bfloat16 / float16 tensors), lanczos_resize_tensor_view.hip
@@ -107,6 +109,14 @@ inline int resize_bps(const lanczos_resize_desc* d) { return resize_f32(d) ? 4 :
 constexpr int kRsThreads = 256;
 constexpr int kRsOB = 8;             // output rows per march step of the fused kernels
 constexpr int kRsLoadBatch = 16;     // staging loads in flight per thread
+constexpr int kRsFusedMaxLds = 80 * 1024;   // at least two fused workgroups per CU (160 KiB of LDS)
+constexpr int kRsRowsPerChunkMin = 4 * kRsOB;
+constexpr int kRsTargetWgs = 2048;
+// horizontal tap counts with a fused instance (a request runs on the smallest one >= its ksize, zero-padded), for every
+// sample width.  3 and 5 serve the upscales of the short filters (box and bilinear: ksize 3, bicubic: 5) and only them: a
+// Lanczos request keeps the instance it always had (a = 2 upscales, ksize 5, run on 7).  LANCZOS_RS_NO_SMALL_BUCKETS=1 pads
+// the short filters to 7 too
+#define LZ_RS_BUCKETS(X) X(3) X(5) X(7) X(9) X(11) X(13) X(17) X(25)
 // output pixels per strip of the fused kernels by channels and bytes per sample: ring rows of 256 / 768 / 256 bytes (8-bit),
 // 256 / 768 / 512 bytes (16-bit), 512 / 768 / 1024 bytes (float)
 constexpr int rs_strip_width(int channels, int bps) {
@@ -132,7 +142,7 @@ bool rs_fused_plan_crops(const lanczos_resize_desc* d, const RsAxisView& H, cons
 // crops: the plan of a request with a crop origin per frame (win is then NULL; mid_row0 / mid_rows are the whole output's,
 // which the converted route resizes)
 int resize_plan_host(const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win, int frames,
-                     lanczos_resize_plan_ex* out, const lanczos_resize_crops* crops = nullptr);
+                     lanczos_resize_plan_ex* out, const lanczos_resize_crops* crops);
 // a crop size per request: 1..out_w x 1..out_h, origins given, reserved words 0
 int resize_crops_validate(const lanczos_resize_desc* d, const lanczos_resize_crops* c);
 
@@ -199,11 +209,11 @@ struct RsTensorOut {
         return dst;
     }
 };
-// A tensor request (lanczos_resize_tensor.hip): d_out and out_frame_stride of resize_device are then those of the element
-// frames.  route: out, LANCZOS_TENSOR_FUSED or LANCZOS_TENSOR_CONVERTED once the launches are out.
+// The tensor part of a request (lanczos_resize_tensor.hip): `out` and out_frame_stride of the request are then those of the
+// element frames.  route: out, LANCZOS_TENSOR_FUSED or LANCZOS_TENSOR_CONVERTED once the launches are out.
 struct RsTensorCall {
     RsTensorOut t;             // validated (tensor_validate)
-    size_t extent_bytes = 0;   // of one element frame: from its first element to its last
+    size_t extent_bytes = 0;   // of one element frame: from its first element to its last (set by resize_device)
     int route = 0;
     // lanczos_resize_crops: a pair (x0, y0) per frame, read and clamped when the kernels run.  The window of the call is then
     // (0, 0, w, h), the size of every frame's crop
@@ -273,7 +283,6 @@ int resize_dest_resolve(const lanczos_resize_desc* d, const RsWindow& w, const l
 struct RsDestCall {
     RsDest s;
     int route = 0;
-    bool unpack_only = false;   // set by resize_device: a request with a reducing gap is UNPACKED whatever resizes the reduced frames
 };
 // AUTO takes the planar-out instances of the fused kernel where they exist (false: UNPACKED, the instances by force only); the
 // measurements behind the choice are in DESIGN.md 4.5
@@ -284,25 +293,72 @@ constexpr bool kRsPlanarOutAutoDirect = true;
 hipError_t rs_unpack_dest_launch(const uint8_t* in, size_t in_fs, uint8_t* out, size_t out_fs, const RsDest& s, int w, int h,
                                  int C, int B, int frames, hipStream_t stream);
 
-// The entry points (ctx->mu held, device set).  *last_kernel / *last_hip as in lanczos_ctx.  tc: a tensor request (NULL: bytes).
-// win: the window of the output that is computed and stored, tightly packed (NULL: the whole output)
-// dc: the window is stored in that layout instead (bytes out only: never with tc)
-int resize_device(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
-                  const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream,
-                  int* last_kernel, int* last_hip, RsTensorCall* tc = nullptr, RsSourceCall* sc = nullptr,
-                  RsDestCall* dc = nullptr);
-// host table (t.d_lut), host flip array (t.d_flip, or NULL) and host buffers, element frames tensor_extent_bytes apart;
-// synchronous.  origins: NULL, or the host array of a lanczos_resize_crops request (win is then (0, 0, w, h))
-int resize_tensor_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o,
-                       const lanczos_resize_window* win, const RsTensorOut& t, const void* in, void* out, int frames,
-                       hipStream_t stream, int* last_kernel, int* last_hip, int* route, const int32_t* origins = nullptr,
-                       RsSourceCall* sc = nullptr);
-// sc: `in` holds the frames in that layout, its extent apart
-// dc: `out` holds the frames in that layout, its extent apart, the last one up to its last named byte; it goes up before it
-// comes back, so that the bytes the layout does not name keep what they held
-int resize_host(ResizeState* st, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
-                const void* in, void* out, int frames, hipStream_t stream, int* last_kernel, int* last_hip,
-                RsSourceCall* sc = nullptr, RsDestCall* dc = nullptr);
+// One resize request, as every entry of lanczos_api.hip fills it in and the entry points below take it.
+struct RsRequest {
+    const lanczos_resize_desc* d = nullptr;        // validated (resize_validate)
+    const lanczos_resize_opts* o = nullptr;        // NULL: the full box, no gap
+    const lanczos_resize_window* win = nullptr;    // the window of the output that is computed and stored (NULL: all of it)
+    const void* in = nullptr;
+    void* out = nullptr;
+    int frames = 0;
+    size_t in_frame_stride = 0, out_frame_stride = 0;   // bytes; 0: the frames lie back to back
+    hipStream_t stream = nullptr;
+    int *last_kernel = nullptr, *last_hip = nullptr;     // as in lanczos_ctx
+    // the optional parts, each read only where its flag is set and its `route` written once the launches are out
+    bool tensor = false;   // tc: `out` holds element frames.  Crops: win is (0, 0, w, h) and tc.d_origin the origins
+    bool source = false;   // sc: the frames at `in` lie in that layout
+    bool dest = false;     // dc: the window is stored in that layout instead of tightly packed (bytes out only: never with tc)
+    RsTensorCall tc;
+    RsSourceCall sc;
+    RsDestCall dc;
+};
+
+// What rs_route is asked: a request resolved, nothing of it on a device
+struct RsRouteQuery {
+    const lanczos_resize_desc* d = nullptr;   // the caller's descriptor
+    const RsResolved* r = nullptr;
+    RsWindow win;                             // the frame that is stored; of a crops request (0, 0, w, h)
+    int frames = 1;
+    int force = LANCZOS_RESIZE_AUTO;
+    bool tensor = false, mapped = false, crops = false;
+    int elem = 0;                             // bytes of a tensor element
+    size_t extent_bytes = 0;                  // of one element frame
+    const RsSource* src = nullptr;            // NULL: the call has no source
+    const RsDest* dst = nullptr;              // NULL: the call has no destination
+    const ResizeAxisHost *H = nullptr, *V = nullptr;   // the tables of r->inner's axes; read where both passes run
+};
+enum RsMain { kRsMainFused, kRsMainNearest, kRsMainCopy, kRsMainCrop, kRsMainNone, kRsMainPassH, kRsMainPassV, kRsMainTwoPass,
+              kRsMainVFirst };
+enum RsFollower { kRsFollowNone, kRsFollowToTensor, kRsFollowCropsScratch, kRsFollowCropsDirect };
+// Everything a call does, in the order it does it: pack, reduce, main, follower, unpack.  A scratch block of ResizeState that
+// the call uses has its frame stride and size here; 0 bytes: not used
+struct RsRoute {
+    int err = LANCZOS_OK;   // the refusal; nothing else is set then
+    bool reduce = false;    // k_reduce in front: r->fx x r->fy over r->rb into `reduced`, which the resize then reads
+    bool pack = false;      // k_rs_pack_source in front of everything: the source gathered into `packed`
+    RsMain main = kRsMainNone;
+    int bps = 1, flags = 0;        // kRsMainFused: the instance rs_launch_fused<bps, flags>
+    bool src_direct = false;       // ... reads the source as it lies
+    bool dst_direct = false;       // ... stores the destination's layout itself
+    RsWindow win;                  // the window the main step computes: the request's, or the whole output in front of a crops gather
+    RsFusedPlan fp;                // kRsMainFused: its plan
+    int mid_row0 = 0, mid_rows = 0;   // both passes run: the rows of the source the vertical taps of the window read
+    RsFollower follower = kRsFollowNone;
+    int tensor_route = 0, source_route = 0, dest_route = 0, kernel = 0;   // LANCZOS_TENSOR_* / SOURCE_* / DEST_* / KERNEL_*; 0: no such part
+    struct Block {
+        size_t fs = 0, bytes = 0;
+    } packed, reduced, tensor_bytes, unpacked, scratch;
+};
+// The one decision.  Pure host code: no HIP call, no device state, no ResizeState
+RsRoute rs_route(const RsRouteQuery& q);
+
+// The entry points (ctx->mu held, device set).  resize_device resolves the request, asks rs_route and issues what it says.
+int resize_device(ResizeState* st, RsRequest& q);
+// host buffers, and for a tensor request a host table (tc.t.d_lut), host flips (tc.t.d_flip, or NULL) and host origins
+// (tc.d_origin, or NULL); frames back to back (a source's or destination's extent, an element frame's tensor_extent_bytes
+// apart); synchronous.  Element frames and a destination's go up before they come back, so that what the layout does not
+// name keeps what it held.  q.in / q.out are left naming the staging blocks
+int resize_host(ResizeState* st, RsRequest& q);
 
 // Reduce by whole factors (lanczos_reduce.hip): Pillow's Image.reduce over an integer box, 8-bit.  Arguments validated by
 // reduce_validate; the output rows are tightly packed.

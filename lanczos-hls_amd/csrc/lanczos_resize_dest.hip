@@ -1,8 +1,8 @@
 // lanczos_resize_dest.hip -- a destination layout beside the descriptor (lanczos_resize_dest, include/lanczos_hip.h): planar
-// (CHW) and row-pitched result frames without a repack by the caller.  Here: the layout's validation, the planar-out instances of
+// (CHW) and row-pitched result frames without a repack by the caller.  Here: the planar-out instances of
 // the fused kernel over an interleaved source (the kernel is lanczos_resize_fused.hpp's and only its epilogue differs), and
 // k_rs_unpack_dest, the streaming scatter of the UNPACKED route.  Pitched interleaved rows need no kernel code (RsFused::out_pitch);
-// the routes are chosen in lanczos_resize.hip (resize_inner).
+// the layout is validated and the routes are chosen in lanczos_resize_route.cpp (resize_dest_resolve, rs_route).
 #include "lanczos_resize_fused.hpp"
 
 namespace lz {
@@ -10,34 +10,6 @@ namespace lz {
 // the instances of the fused kernel that store planes from an interleaved source (k_rs_fused<RsSample<1>, C, K, ALPHA,
 // kRsPlanarOut> for every tap-count bucket x C = 3, 4 and alpha); those of a planar source are lanczos_resize_dest_source.hip's
 template hipError_t rs_launch_fused<1, kRsPlanarOut>(const RsFusedLaunch&);
-
-int resize_dest_resolve(const lanczos_resize_desc* d, const RsWindow& w, const lanczos_resize_dest* dst, RsDest* s) {
-    const long long C = d->channels, B = resize_bps(d);
-    const long long tight_row = (long long)w.w * C * B;
-    *s = RsDest{false, true, (size_t)tight_row, (size_t)B, (size_t)(w.h * tight_row), (size_t)(w.h * tight_row)};
-    if (!dst) return LANCZOS_OK;
-    for (int32_t r : dst->reserved)
-        if (r != 0) return LANCZOS_ERR_BAD_ARG;
-    const long long rs = dst->row_stride, cs = dst->chan_stride, ps = dst->pix_stride;
-    if (rs < 1 || cs < 1 || ps < 1 || rs % B != 0) return LANCZOS_ERR_BAD_ARG;
-    // a plane of h pitched rows: what chan_stride has to clear.  rs * h stays far below 2^63 only for a sane pitch
-    if (rs > ((long long)1 << 40)) return LANCZOS_ERR_BAD_ARG;
-    const long long plane = (w.h - 1) * rs + (long long)w.w * B;
-    const bool planar_shape = ps == B && rs >= (long long)w.w * B && cs >= plane && cs <= ((long long)1 << 56);
-    const auto interleaved = [&] {
-        s->row_stride = (size_t)rs, s->tight = rs == tight_row;
-        s->extent = (size_t)(w.h * rs), s->named = (size_t)((w.h - 1) * rs + tight_row);
-        return LANCZOS_OK;
-    };
-    if (ps == C * B && cs == B && rs >= tight_row) return interleaved();   // with one channel: every planar destination as well
-    if (!planar_shape) return LANCZOS_ERR_BAD_ARG;
-    if (C == 1) return interleaved();             // one plane: the interleaved shape, whatever chan_stride says
-    if (B != 1) return LANCZOS_ERR_UNSUPPORTED;   // planar wide samples: frames * C one-channel frames for the plain entries
-    s->planar = true, s->tight = false;
-    s->row_stride = (size_t)rs, s->chan_stride = (size_t)cs;
-    s->extent = (size_t)(C * cs), s->named = (size_t)((C - 1) * cs + plane);
-    return LANCZOS_OK;
-}
 
 // ---- k_rs_unpack_dest --------------------------------------------------------------------------------------------------
 //

@@ -683,12 +683,6 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
     }
 }
 
-// horizontal tap counts with a fused instance (a request runs on the smallest one >= its ksize, zero-padded), for every
-// sample width.  3 and 5 serve the upscales of the short filters (box and bilinear: ksize 3, bicubic: 5) and only them: a
-// Lanczos request keeps the instance it always had (a = 2 upscales, ksize 5, run on 7).  LANCZOS_RS_NO_SMALL_BUCKETS=1 pads
-// the short filters to 7 too
-#define LZ_RS_BUCKETS(X) X(3) X(5) X(7) X(9) X(11) X(13) X(17) X(25)
-
 // f(C, K, ALPHA) as std::integral_constants for the instance of a request; false: there is none
 template <class F>
 bool rs_dispatch_instance(int channels, int K, bool alpha, F&& f) {
@@ -714,7 +708,7 @@ void rs_fill_fused(RsFused<KT>* g, const RsFusedLaunch& c) {
     const lanczos_resize_desc* d = c.d;
     const RsWindow& w = c.win;   // the kernel's output is the window: its tables start at the window's first outputs
     g->in_pitch = c.src ? (int)c.src->row_stride : d->in_w * d->channels * resize_bps(d);   // below 2^31 (the plan)
-    g->out_pitch = c.dst ? (int)c.dst->row_stride : w.w * d->channels * resize_bps(d);   // below 2^31 (resize_inner)
+    g->out_pitch = c.dst ? (int)c.dst->row_stride : w.w * d->channels * resize_bps(d);   // below 2^31 (rs_route)
     g->in_h = d->in_h, g->out_w = w.w, g->out_h = w.h;
     g->in_fs = c.in_fs, g->out_fs = c.out_fs;
     g->hks = c.H->host.ksize, g->vks = c.V->host.ksize;

@@ -1,9 +1,10 @@
 // lanczos_resize_source.hip -- a source layout beside the descriptor (lanczos_resize_source, include/lanczos_hip.h): planar
-// (CHW) and row-pitched frames without a repack.  Here: the layout's validation, the planar instances of the fused kernel that
+// (CHW) and row-pitched frames without a repack.  Here: the planar instances of the fused kernel that
 // store bytes (k_rs_fused<RsSample<1>, C, K, ALPHA, kRsPlanar> for every tap-count bucket x C = 3, 4 and alpha; the kernel is
 // lanczos_resize_fused.hpp's and only its staging loads differ), and k_rs_pack_source, the streaming gather of the PACKED
 // route.  The planar instances that store tensor elements are lanczos_resize_source_tensor.hip's and
-// lanczos_resize_source_tensor16.hip's; the routes are chosen in lanczos_resize.hip (resize_inner).
+// lanczos_resize_source_tensor16.hip's; the layout is validated and the routes are chosen in
+// lanczos_resize_route.cpp (resize_source_resolve, rs_route).
 #include "lanczos_resize_fused.hpp"
 
 namespace lz {
@@ -11,34 +12,6 @@ namespace lz {
 template hipError_t rs_launch_fused<1, kRsPlanar>(const RsFusedLaunch&);
 // ... and the ALPHA instances of pitched interleaved rows whose pitch is no dword multiple (kRsRowShift)
 template hipError_t rs_launch_fused<1, kRsRowShift>(const RsFusedLaunch&);
-
-int resize_source_resolve(const lanczos_resize_desc* d, const lanczos_resize_source* src, RsSource* s) {
-    const long long C = d->channels, B = resize_bps(d);
-    const long long tight_row = (long long)d->in_w * C * B;
-    *s = RsSource{false, true, (size_t)tight_row, (size_t)B, (size_t)(d->in_h * tight_row)};
-    if (!src) return LANCZOS_OK;
-    for (int32_t r : src->reserved)
-        if (r != 0) return LANCZOS_ERR_BAD_ARG;
-    const long long rs = src->row_stride, cs = src->chan_stride, ps = src->pix_stride;
-    if (rs < 1 || cs < 1 || ps < 1 || rs % B != 0) return LANCZOS_ERR_BAD_ARG;
-    // a plane of in_h pitched rows: what chan_stride has to clear.  rs * in_h stays far below 2^63 only for a sane pitch
-    if (rs > ((long long)1 << 40)) return LANCZOS_ERR_BAD_ARG;
-    const long long plane = (d->in_h - 1) * rs + (long long)d->in_w * B;
-    const bool planar_shape = ps == B && rs >= (long long)d->in_w * B && cs >= plane && cs <= ((long long)1 << 56);
-    if (ps == C * B && cs == B && rs >= tight_row) {   // interleaved; with one channel this is every planar source as well
-        s->row_stride = (size_t)rs, s->tight = rs == tight_row, s->extent = (size_t)(d->in_h * rs);
-        return LANCZOS_OK;
-    }
-    if (!planar_shape) return LANCZOS_ERR_BAD_ARG;
-    if (C == 1) {   // one plane: the interleaved shape, whatever chan_stride says
-        s->row_stride = (size_t)rs, s->tight = rs == tight_row, s->extent = (size_t)(d->in_h * rs);
-        return LANCZOS_OK;
-    }
-    if (B != 1) return LANCZOS_ERR_UNSUPPORTED;   // planar wide samples: frames * C one-channel frames for the plain entries
-    s->planar = true, s->tight = false;
-    s->row_stride = (size_t)rs, s->chan_stride = (size_t)cs, s->extent = (size_t)(C * cs);
-    return LANCZOS_OK;
-}
 
 // ---- k_rs_pack_source ------------------------------------------------------------------------------------------------
 //

@@ -13,7 +13,8 @@
 //              elements (k_rs_to_tensor<C, uint16_t> is the k_rs_to_tensor16 of the documents; k_rs_to_tensor_map is the
 //              form with a channel map and flips).
 //
-// The validation of a request, the table of ToTensor + Normalize and its rounding to 16 bits are here as well.
+// The table of ToTensor + Normalize and its rounding to 16 bits are here as well; the validation of a request is
+// lanczos_resize_route.cpp's (tensor_validate).
 #include "lanczos_resize_fused.hpp"
 
 #include <algorithm>
@@ -21,72 +22,7 @@
 
 namespace lz {
 
-// ---- host: validation, the normalisation table --------------------------------------------------------------------
-
-size_t tensor_extent_bytes(const lanczos_resize_desc* d, const RsWindow& win, const RsTensorOut& t) {
-    const int oc = t.out_channels ? t.out_channels : d->channels;
-    return (size_t)((oc - 1) * t.chan_stride + (win.h - 1) * t.row_stride + (win.w - 1) * t.pix_stride + 1) *
-           (size_t)t.elem;
-}
-
-int tensor_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, RsTensorOut* t, const int32_t* reserved) {
-    int rc = resize_validate(d);
-    if (rc != LANCZOS_OK) return rc;
-    RsWindow w;   // the frame the strides describe
-    if ((rc = resize_window_resolve(d, win, &w)) != LANCZOS_OK) return rc;
-    if (!t || !t->d_lut) return LANCZOS_ERR_BAD_ARG;
-    for (int i = 0; i < 4; i++)
-        if (reserved[i] != 0) return LANCZOS_ERR_BAD_ARG;
-    // the channel map: out_channels 0 is every channel in its place.  Injective, and nothing set behind out_channels
-    if (t->elem != 2 && t->elem != 4) return LANCZOS_ERR_BAD_ARG;
-    if (t->out_channels == 0) {
-        t->out_channels = d->channels;
-        for (int c = 0; c < 4; c++) t->src_channel[c] = c < d->channels ? c : 0;
-    }
-    if (t->out_channels < 1 || t->out_channels > d->channels || (t->flip & ~3) != 0) return LANCZOS_ERR_BAD_ARG;
-    bool identity = t->out_channels == d->channels;
-    for (int oc = 0; oc < 4; oc++) {
-        const int sc = t->src_channel[oc];
-        if (oc >= t->out_channels ? sc != 0 : (sc < 0 || sc >= d->channels)) return LANCZOS_ERR_BAD_ARG;
-        for (int k = 0; k < oc && oc < t->out_channels; k++)
-            if (t->src_channel[k] == sc) return LANCZOS_ERR_BAD_ARG;
-        if (oc < t->out_channels && sc != oc) identity = false;
-    }
-    t->mapped = !identity || t->flip != 0 || t->d_flip != nullptr;
-    // a table per 16-bit value and float inputs are out of scope
-    if (d->reserved[0] & (LANCZOS_RESIZE_U16 | LANCZOS_RESIZE_F32)) return LANCZOS_ERR_UNSUPPORTED;
-    struct Dim {
-        int64_t stride, extent;
-    } dims[3] = {{t->chan_stride, t->out_channels}, {t->row_stride, w.h}, {t->pix_stride, w.w}};
-    constexpr int64_t kMaxStride = (int64_t)1 << 40;   // stride x extent stays far inside int64
-    for (const Dim& m : dims)
-        if (m.stride <= 0 || m.stride > kMaxStride) return LANCZOS_ERR_BAD_ARG;
-    // no two (c, y, x) share an address: by rising stride, each stride covers the whole extent of the one before.  An axis of
-    // extent 1 never moves, so its stride takes no part
-    std::sort(dims, dims + 3, [](const Dim& a, const Dim& b) { return a.stride < b.stride; });
-    int64_t covered = 1;   // elements the axes so far span
-    for (const Dim& m : dims) {
-        if (m.extent == 1) continue;
-        if (m.stride < covered) return LANCZOS_ERR_BAD_ARG;
-        covered = m.stride * m.extent;
-    }
-    return LANCZOS_OK;
-}
-
-int tensor_view_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_tensor_view* v,
-                         RsTensorOut* lay) {
-    if (v) {
-        *lay = RsTensorOut{v->d_lut, v->chan_stride, v->row_stride, v->pix_stride, v->elem_bytes, v->out_channels};
-        for (int c = 0; c < 4; c++) lay->src_channel[c] = v->src_channel[c];
-        lay->flip = v->flip, lay->d_flip = v->d_flip;
-        // 0 channels is no view (and stands for "all of them" inside): refused here, once the descriptor has been looked at
-        if (v->out_channels == 0) {
-            const int rc = resize_validate(d);
-            return rc != LANCZOS_OK ? rc : LANCZOS_ERR_BAD_ARG;
-        }
-    }
-    return tensor_validate(d, win, v ? lay : nullptr, v ? v->reserved : nullptr);
-}
+// ---- host: the normalisation table --------------------------------------------------------------------------------
 
 // ToTensor() then Normalize(mean, std), operation for operation in float: this translation unit is built with
 // -ffp-contract=off, and the divisions are IEEE divisions (no reciprocal)

@@ -270,8 +270,8 @@ def plan_ex(job):
 
 
 def scratch(job):
-    """kind -> bytes of context scratch the job needs on a context forced to the two-pass path (csrc/lanczos_resize.hip
-    resize_inner / resize_device, csrc/lanczos_api.hip): what makes a block of that kind grow"""
+    """kind -> bytes of context scratch the job needs on a context forced to the two-pass path (the blocks of rs_route,
+    csrc/lanczos_resize_route.cpp, that resize_device grows, csrc/lanczos_resize.hip): what makes a block of that kind grow"""
     k, f = job["kind"], job["frames"]
     if k == "planar":
         return {"planar": f * job["w"] * job["h"] * job["c"] * (1 + job["sn"] * job["sn"])}

@@ -1,12 +1,13 @@
 """The resize dispatcher over the cross product of its options (tests/test_resize_matrix_cfg.py, tests/test_resize_matrix_gpu.py):
-the case generator, the legality rules and resize_inner's decision tree restated in plain Python, and the CPU reference of every
+the case generator, the legality rules and the route decision (rs_route) restated in plain Python, and the CPU reference of every
 case.  No GPU is needed to import this module or to compute an expected array.
 
 A case is one value of every dimension: the sample kind, the geometry, the filter, the options (box / reducing_gap), the window,
 the output (bytes or one of the tensor forms), the source layout and the forced path.  cases() is the full product; legality()
 sorts it into requests that run (None), requests an entry refuses (the LANCZOS_ERR_* code) and combinations that are no request
 at all (NA: no entry takes them, or the value names nothing of its own for that kind).  predict() says which kernels a legal case
-launches, written from the conditions of resize_device / resize_inner (csrc/lanczos_resize.hip) -- it asks the host planners
+launches, written from the conditions of rs_route (csrc/lanczos_resize_route.cpp), against which tests/test_resize_matrix_cfg.py
+holds it case by case on the host; predict_dest() says the same of a destination layout.  predict() asks the host planners
 (resize_window_plan_host, resize_crops_plan_host) for `fused`, `pass_h`, `pass_v` and `fx` / `fy` and hard-codes none of them.
 
 Nothing in the reference comes from the code under test: the full bytes of a (kind, geometry, filter, options) are
@@ -213,15 +214,23 @@ def source_of(kind, geo, src):
     family of RGBA; wider samples keep their alignment).  planar: odd row and plane strides."""
     k = KINDS[kind]
     x = frames_of(kind, geo)
-    iw, ih, _, _ = GEOMETRIES[geo]
+    ih = GEOMETRIES[geo][1]
+    rs, cs, _ = source_strides(kind, geo, src)
     if src == "pitched":
-        rs = (iw * k.channels + 7) * k.bps
         return SM.build(x, "interleaved", rs, base=(3 * k.bps) % 4, frame_stride=ih * rs + k.bps, seed=3)
     assert src == "planar" and k.bps == 1 and k.channels > 1
-    rs = iw + 3 + (iw % 2)
-    cs = ih * rs + 1 + (ih * rs) % 2
     assert rs % 2 and cs % 2
     return SM.build(x, "planar", rs, cs, base=1, frame_stride=k.channels * cs + 1, seed=4)
+
+
+def source_strides(kind, geo, src):
+    """(row_stride, chan_stride, pix_stride) in bytes of source_of()'s layout, without building its frames"""
+    k = KINDS[kind]
+    iw, ih, _, _ = GEOMETRIES[geo]
+    if src == "pitched":
+        return (iw * k.channels + 7) * k.bps, k.bps, k.channels * k.bps
+    rs = iw + 3 + (iw % 2)
+    return rs, ih * rs + 1 + (ih * rs) % 2, k.bps
 
 
 def source_struct(case, s=None):
@@ -323,7 +332,7 @@ def predict(case):
     force, tensor, crops = case.force, bool(o.elem), o.crop
     pack_kernel = {"none": None, "pitched": "pack_rows", "planar": f"pack<{k.channels}>"}[case.src]
     src, pack, route = (None if case.src == "none" else case.src), None, None
-    if src and p.reduces:                          # resize_device: the reduction reads packed frames
+    if src and p.reduces:                          # the reduction reads packed frames
         pack, route, src = pack_kernel, L.SOURCE_PACKED, None
     had_source = src is not None
     rowshift = src == "pitched" and k.alpha        # the pitch of source_of() is no dword multiple
@@ -382,6 +391,47 @@ def predict(case):
                     None if t_fused else "to_tensor_map" if o.mapped else "to_tensor")
     troute = 0 if not tensor else L.TENSOR_FUSED if t_fused else L.TENSOR_CONVERTED
     return Pred(main, alpha, p.reduces, pack, follower, last, troute, route)
+
+
+DESTS = ("pitched", "planar")
+PLANAR_OUT = 128    # kRsPlanarOut in the flag word of a fused instance
+
+
+def dest_strides(case, dest):
+    """(row_stride, chan_stride, pix_stride) in bytes of a destination for the frame of a bytes-out case: pitched rows whose pitch
+    is no dword multiple, or planes with padded rows and a padded plane stride"""
+    k = KINDS[case.kind]
+    w, h = frame_size(case)
+    if dest == "pitched":
+        rs = w * k.channels * k.bps + k.bps
+        return rs + (k.bps if rs % 4 == 0 else 0), k.bps, k.channels * k.bps
+    return (w + 3) * k.bps, (h * (w + 3) + 5) * k.bps, k.bps
+
+
+def predict_dest(case, dest):
+    """The destination route of a legal bytes-out case, from the contract of lanczos_resize_dest (include/lanczos_hip.h): DIRECT
+    where the fused kernel runs, except behind a reducing gap, under forced CONVERT (forced TWO_PASS runs no fused kernel), and
+    into planes from RGBA rows it reads as they lie off a dword pitch; UNPACKED everything else.  (No frame here names 2^31 bytes.)"""
+    p = predict(case)
+    rowshift_direct = KINDS[case.kind].alpha and case.src == "pitched" and p.source_route == L.SOURCE_DIRECT
+    direct = (p.main.startswith("fused<") and not p.reduce and case.force != L.RESIZE_CONVERT and
+              not (dest == "planar" and rowshift_direct))
+    return L.DEST_DIRECT if direct else L.DEST_UNPACKED
+
+
+def route_line(case, dest=None):
+    """the request of a case as tests/native/resize_route_check.hip reads it"""
+    k, o = KINDS[case.kind], OUTPUTS[case.out]
+    d = desc_of(case)
+    box, win = box_of(case), window_of(case)
+    iw, ih, _, _ = GEOMETRIES[case.geo]
+    f = [d.in_w, d.in_h, d.out_w, d.out_h, d.channels, d.a, d.reserved[0]]
+    f += [int(case.opt != "none")] + [repr(float(v)) for v in (box or (0, 0, iw, ih))] + [repr(gap_of(case) or 0.0)]
+    f += [1, 0, 0, *crop_size(case.geo), 1] if o.crop else [1, *win, 0] if win else [0, 0, 0, 0, 0, 0]
+    f += [o.elem, int(o.mapped), *tensor_strides(case), len(out_channels(case))] if o.elem else [0, 0, 0, 0, 0, 0]
+    f += [1, *source_strides(case.kind, case.geo, case.src)] if case.src != "none" else [0, 0, 0, 0]
+    f += [1, *dest_strides(case, dest)] if dest else [0, 0, 0, 0]
+    return " ".join(str(v) for v in f + [case.force, FRAMES])
 
 
 MAINS = ("nearest", "copy", "crop", "pass_h_only", "pass_v_only", "two_pass", "v_first", "none")

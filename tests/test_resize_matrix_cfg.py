@@ -1,14 +1,18 @@
 """CPU-only checks that keep tests/resize_matrix_cfg.py honest: its legality rules agree with the host validators both ways and
 with the error code, the planner facts the geometries were chosen for still hold, every leaf of the dispatcher is reached by a
-legal case of every kind that can reach it, and the composition that makes the expected arrays reproduces the committed Pillow
-fixtures.  No GPU needed."""
+legal case of every kind that can reach it, the library's own route decision (rs_route, run on the host by
+tests/native/resize_route_check.hip) is the prediction for every legal case, and the composition that makes the expected arrays
+reproduces the committed Pillow fixtures.  No GPU needed."""
 import collections
 import ctypes
 import functools
 import importlib.util
 import os
+import shutil
+import subprocess
 
 import numpy as np
+import pytest
 
 import lanczos_hls_amd as L
 import resize_filters_model as F
@@ -181,7 +185,7 @@ def test_every_leaf_is_reached():
 
 
 def test_the_dispatcher_cases_the_issue_names():
-    """the cases of resize_inner that are easy to get wrong, spelled out"""
+    """the cases of the route decision (rs_route) that are easy to get wrong, spelled out"""
     c = M.Case("u8x3", "down", "lanczos", "none", "whole", "bytes", "pitched", L.RESIZE_AUTO)
     assert M.predict(c)[:] == (M.family(1, 0), (), False, None, None, L.KERNEL_RESIZE_FUSED, 0, L.SOURCE_DIRECT)
     for force in (L.RESIZE_CONVERT, L.RESIZE_TWO_PASS):   # both drop the source to PACKED, also for byte output
@@ -214,6 +218,101 @@ def test_the_dispatcher_cases_the_issue_names():
     assert M.predict(t._replace(src="none", win="sub", out="bf16map_hwc")).follower == "to_tensor_map"
     assert M.predict(t._replace(src="none", filt="nearest")).main == "nearest"
     assert M.predict(t._replace(src="none", opt="gap")).main == M.family(1, 0)     # reduced to 7 x 188, which is not tall
+
+
+@pytest.fixture(scope="module")
+def route_exe(tmp_path_factory):
+    """tests/native/resize_route_check.hip with the library's host-only translation unit: no library load, no kernel, no GPU"""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    csrc = os.path.join(ROOT, "lanczos-hls_amd", "csrc")
+    path = str(tmp_path_factory.mktemp("resize_route") / "resize_route_check")
+    subprocess.run([hipcc, "-O1", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-Wno-unused-function", "-I" + csrc,
+                    os.path.join(ROOT, "tests", "native", "resize_route_check.hip"), os.path.join(csrc, "lanczos_resize_route.cpp"),
+                    "-o", path], check=True, timeout=600)
+    return path
+
+
+Route = collections.namedtuple("Route", "err reduce pack main bps flags follower tensor_route source_route dest_route last_kernel")
+
+
+def _routes(exe, tmp_path, lines):
+    """rs_route's answer to every line, from one run of the program"""
+    path = str(tmp_path / "requests.txt")
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    r = subprocess.run([exe, path], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    out = r.stdout.split("\n")
+    assert out[len(lines)] == "done %d" % len(lines), out[-3:]
+    routes = []
+    for i, text in enumerate(out[:len(lines)]):
+        w = text.split()
+        assert w[0] == "ROUTE" and int(w[1]) == i, text
+        routes.append(Route(*(v if k in (5, 8) else int(v) for k, v in enumerate(w) if k >= 2)))
+    return routes
+
+
+def test_the_route_is_the_prediction(route_exe, tmp_path):
+    """rs_route (csrc/lanczos_resize_route.cpp), asked on the host for every legal case of the product, launches what predict()
+    says; a case refused only because FUSED is forced is refused by the route, with that code"""
+    legal, forced = [], []
+    for case in M.cases():
+        said = M.legality(case)
+        if said is None:
+            legal.append(case)
+        elif said == L.ERR_UNSUPPORTED and case.force == L.RESIZE_FUSED and M.legality(case._replace(force=L.RESIZE_AUTO)) is None:
+            forced.append(case)
+    assert len(legal) > 40000 and forced
+    routes = _routes(route_exe, tmp_path, [M.route_line(c) for c in legal + forced])
+    compared = 0
+    for case, rt in zip(legal, routes):
+        p = M.predict(case)
+        assert rt.err == L.OK, (M.describe(case), rt)
+        main = M.family(rt.bps, rt.flags) if rt.main == "fused" else rt.main
+        follower = {"none": None, "to_tensor": "to_tensor"}.get(rt.follower, rt.follower)
+        want_follower = "to_tensor" if p.follower == "to_tensor_map" else p.follower
+        assert (main, bool(rt.reduce), bool(rt.pack), follower, rt.last_kernel, rt.tensor_route, rt.source_route or None) == \
+            (p.main, p.reduce, p.pack is not None, want_follower, p.last_kernel, p.tensor_route, p.source_route), (M.describe(case), rt, p)
+        assert rt.dest_route == 0, (M.describe(case), rt)
+        compared += 1
+    assert compared == len(legal)
+    for case, rt in zip(forced, routes[len(legal):]):
+        assert rt.err == L.ERR_UNSUPPORTED, (M.describe(case), rt)
+
+
+def test_the_destination_route(route_exe, tmp_path):
+    """every legal bytes-out case of three kinds on three geometries, into pitched rows and -- where the validator takes them --
+    into planes: the route's destination is predict_dest's, and the fused instance is a planar-out one exactly where planes are
+    stored DIRECT"""
+    todo = []
+    for case in M.cases(kinds=("u8x3", "rgba", "u16x3"), geos=("down", "h", "tall")):
+        if case.out != "bytes" or M.legality(case) is not None:
+            continue
+        d = M.desc_of(case)
+        win = M.window_of(case)
+        for dest in M.DESTS:
+            s = L.ResizeDest()
+            s.row_stride, s.chan_stride, s.pix_stride = M.dest_strides(case, dest)
+            rc = L._lib().lanczos_resize_dest_validate(ctypes.byref(d), ctypes.byref(L.resize_window(d, win)) if win else None,
+                                                       ctypes.byref(s))
+            assert rc == (L.ERR_UNSUPPORTED if dest == "planar" and M.KINDS[case.kind].bps != 1 else L.OK), (M.describe(case), dest)
+            if rc == L.OK:
+                todo.append((case, dest))
+            if dest == "pitched":
+                assert s.row_stride % 4, (M.describe(case), s.row_stride)
+    assert len(todo) > 2000 and {dest for _, dest in todo} == set(M.DESTS)
+    routes = _routes(route_exe, tmp_path, [M.route_line(c, dest) for c, dest in todo])
+    seen = collections.Counter()
+    for (case, dest), rt in zip(todo, routes):
+        want = M.predict_dest(case, dest)
+        assert rt.err == L.OK and rt.dest_route == want, (M.describe(case), dest, rt, want)
+        planar_out = rt.main == "fused" and bool(rt.flags & M.PLANAR_OUT)
+        assert planar_out == (dest == "planar" and want == L.DEST_DIRECT), (M.describe(case), dest, rt)
+        p = M.predict(case)   # a destination changes nothing in front of the store
+        assert (rt.main == "fused", bool(rt.reduce), bool(rt.pack), rt.source_route or None) == \
+            (p.main.startswith("fused<"), p.reduce, p.pack is not None, p.source_route), (M.describe(case), dest, rt, p)
+        seen[dest, want] += 1
+    assert len(seen) == 4 and min(seen.values()) > 50, seen
 
 
 def test_the_sources_name_what_the_issue_asks():
