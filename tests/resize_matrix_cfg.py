@@ -9,6 +9,10 @@ at all (NA: no entry takes them, or the value names nothing of its own for that 
 launches, written from the conditions of rs_route (csrc/lanczos_resize_route.cpp), against which tests/test_resize_matrix_cfg.py
 holds it case by case on the host; predict_dest() says the same of a destination layout.  predict() asks the host planners
 (resize_window_plan_host, resize_crops_plan_host) for `fused`, `pass_h`, `pass_v` and `fx` / `fy` and hard-codes none of them.
+A destination layout is one more dimension, kept beside the Case tuple: dest_cases() pairs every bytes-out request with pitched
+rows and with planes, dest_legality() / DEST_RULES sort the pairs, dest_layout() is the buffer and expected_dest() what a legal
+pair leaves in it.  The host entries (tests/test_resize_matrix_host_gpu.py) take the same cases on tight buffers: expected_host(),
+host_out_bytes(), host_origins_of(), host_source_of().
 
 Nothing in the reference comes from the code under test: the full bytes of a (kind, geometry, filter, options) are
 resize_filters_model.resize's, and everything else is numpy indexing on them with the models of the window, the tensor view, the
@@ -23,6 +27,7 @@ import numpy as np
 import lanczos_hls_amd as L
 import patterns as P
 import resize_crops_model as RC
+import resize_dest_model as DM
 import resize_filters_model as F
 import resize_source_model as SM
 import resize_tensor16_model as T16
@@ -306,9 +311,10 @@ def legality(case):
 
 # ---- the dispatcher restated --------------------------------------------------------------------------------------------
 
+PLANAR_OUT = 128            # kRsPlanarOut in the flag word of a fused instance
 AUTO_PLANAR_DIRECT = True   # kRsPlanarAutoDirect: under AUTO the fused kernel reads planes as they lie
 Pred = collections.namedtuple("Pred", "main alpha reduce pack follower last_kernel tensor_route source_route")
-_FLAGS = ((8, "mapped"), (16, "crops"), (32, "planar"), (64, "rowshift"))
+_FLAGS = ((8, "mapped"), (16, "crops"), (32, "planar"), (64, "rowshift"), (PLANAR_OUT, "planar_out"))
 
 
 def family(bps, tensor):
@@ -394,7 +400,7 @@ def predict(case):
 
 
 DESTS = ("pitched", "planar")
-PLANAR_OUT = 128    # kRsPlanarOut in the flag word of a fused instance
+DEST_DIM = ("none",) + DESTS   # the destination dimension; "none" is the case itself, as cases() yields it
 
 
 def dest_strides(case, dest):
@@ -408,6 +414,67 @@ def dest_strides(case, dest):
     return (w + 3) * k.bps, (h * (w + 3) + 5) * k.bps, k.bps
 
 
+def dest_cases(kinds=None, geos=None):
+    """The destination dimension as (case, dest) pairs, dest in DESTS, over every bytes-out case that is a request, legal or
+    refused, in the order of cases() with the destination changing fastest.  A destination with a tensor output is NA (no entry
+    takes it), so the Case tuple and the product of cases() stay what they are."""
+    for case in cases(kinds, geos):
+        if case.out == "bytes" and legality(case) != NA:
+            for dest in DESTS:
+                yield case, dest
+
+
+# The rules of a case with a destination, in the order the entry applies them (resize_bytes: the descriptor, the source, the
+# destination; then the options and the route inside resize_device): RULES with one row behind the source's.  One plane is the
+# pitched shape whatever the sample width (resize_dest_resolve looks at the channel count first, as tests/test_resize_dest_host.py
+# holds it to), so planes of wide samples are refused only where there are three or four of them.
+_DEST_AFTER = "planar sources are 8-bit only"
+DEST_RULES = tuple(
+    row for name, holds, verdict in RULES for row in
+    [(name, (lambda c, k, o, dest, holds=holds: holds(c, k, o)), verdict)] +
+    ([("planar destinations are 8-bit only", lambda c, k, o, dest: dest == "planar" and k.bps != 1 and k.channels > 1,
+       L.ERR_UNSUPPORTED)] if name == _DEST_AFTER else []))
+assert len(DEST_RULES) == len(RULES) + 1
+
+
+def dest_legality(case, dest):
+    """legality() of a bytes-out case with a destination"""
+    assert case.out == "bytes" and dest in DESTS
+    k, o = KINDS[case.kind], OUTPUTS[case.out]
+    for _, holds, verdict in DEST_RULES:
+        if holds(case, k, o, dest):
+            return verdict
+    return None
+
+
+def dest_shape(case, dest):
+    """"planar" or "interleaved": the shape the library resolves a destination to.  One plane is pitched rows."""
+    return "planar" if dest == "planar" and KINDS[case.kind].channels > 1 else "interleaved"
+
+
+def dest_layout(case, dest, tight=False):
+    """The buffer of a destination as a resize_dest_model.Dest full of sentinels: dest_strides(), the first byte of frame 0 at
+    residue (3 * bps) % 4 behind GUARD elements, the frames FRAME_GAP elements further apart than the layout's own extent, GUARD
+    elements behind the last named byte of the last frame (the padding behind the last row is not part of the buffer).  tight: as
+    the host entry takes it, which has no frame stride: the frames at the layout's own extent, no guard, the first byte at 0."""
+    k = KINDS[case.kind]
+    w, h = frame_size(case)
+    rs, cs, _ = dest_strides(case, dest)
+    shape = dest_shape(case, dest)
+    rs, cs, ps, extent, named = DM.strides((FRAMES, h, w, k.channels), k.bps, shape, rs, cs if shape == "planar" else None)
+    at = 0 if tight else GUARD * k.bps + (3 * k.bps) % 4
+    fs = extent if tight else extent + FRAME_GAP * k.bps
+    total = at + (FRAMES - 1) * fs + named + (0 if tight else GUARD * k.bps)
+    return DM.Dest(np.full(total, SENTINEL, dtype=np.uint8), at, shape, rs, cs, ps, fs, extent, named)
+
+
+def dest_struct(case, dest):
+    """the ResizeDest of a case, written field by field (a refused layout has to reach the entry)"""
+    r = L.ResizeDest()
+    r.row_stride, r.chan_stride, r.pix_stride = dest_strides(case, dest)
+    return r
+
+
 def predict_dest(case, dest):
     """The destination route of a legal bytes-out case, from the contract of lanczos_resize_dest (include/lanczos_hip.h): DIRECT
     where the fused kernel runs, except behind a reducing gap, under forced CONVERT (forced TWO_PASS runs no fused kernel), and
@@ -417,6 +484,22 @@ def predict_dest(case, dest):
     direct = (p.main.startswith("fused<") and not p.reduce and case.force != L.RESIZE_CONVERT and
               not (dest == "planar" and rowshift_direct))
     return L.DEST_DIRECT if direct else L.DEST_UNPACKED
+
+
+def predict_dest_main(case, dest):
+    """(the main kernel, the unpack kernel or None) of a legal bytes-out case with a destination.  A destination changes nothing in
+    front of the store: the main kernel is predict()'s, except that planes stored DIRECT take the planar-out instance of the
+    fused kernel, which exists over an interleaved source (pitched rows included) and over a planar one.  UNPACKED: k_rs_unpack_dest
+    of the channel count for planes, k_rs_unpack_dest_rows for every pitched shape."""
+    k = KINDS[case.kind]
+    p = predict(case)
+    planes = dest_shape(case, dest) == "planar"
+    if predict_dest(case, dest) == L.DEST_UNPACKED:
+        return p.main, f"unpack<{k.channels}>" if planes else "unpack_rows"
+    if not planes:
+        return p.main, None
+    assert p.main in (family(1, 0), family(1, 32)), (describe(case), dest, p.main)
+    return family(1, PLANAR_OUT + (32 if p.main == family(1, 32) else 0)), None
 
 
 def route_line(case, dest=None):
@@ -448,7 +531,19 @@ LEAVES = collections.OrderedDict(
     [("nearest", tuple(n for n in KINDS if KINDS[n].bps != 2))] +
     [(m, _WIDE) for m in ("copy", "crop", "pass_h_only", "pass_v_only", "two_pass", "v_first")] + [("none", U8_KINDS)] +
     [(a, ("rgba",)) for a in ALPHA_LEAVES] + [("reduce", ("u8x1", "u8x3", "u8x4"))] +
-    [("pack<3>", ("u8x3",)), ("pack<4>", ("u8x4", "rgba")), ("pack_rows", _WIDE)] + [(f, U8_KINDS) for f in FOLLOWERS])
+    [("pack<3>", ("u8x3",)), ("pack<4>", ("u8x4", "rgba")), ("pack_rows", _WIDE)] + [(f, U8_KINDS) for f in FOLLOWERS] +
+    # what a destination adds (dest_cases()): the scatter kernels of the UNPACKED route and the planar-out fused families
+    [("unpack<3>", ("u8x3",)), ("unpack<4>", ("u8x4", "rgba")), ("unpack_rows", _WIDE)] +
+    [(family(1, PLANAR_OUT), _PLANAR), (family(1, PLANAR_OUT + 32), _PLANAR)])
+UNPACKS = ("unpack<3>", "unpack<4>", "unpack_rows")
+PLANAR_OUT_FAMILIES = (family(1, PLANAR_OUT), family(1, PLANAR_OUT + 32))
+DEST_LEAVES = UNPACKS + PLANAR_OUT_FAMILIES
+
+
+def dest_pairs(kind):
+    """the (dest, route) pairs a kind can reach: both routes of pitched rows, and of planes where the validator takes them"""
+    k = KINDS[kind]
+    return {(d, r) for d in DESTS for r in (L.DEST_DIRECT, L.DEST_UNPACKED) if d == "pitched" or k.bps == 1 or k.channels == 1}
 
 
 def leaves_of(pred):
@@ -476,17 +571,21 @@ def full_bytes(kind, geo, filt, opt):
     return y
 
 
+def cut_of(full, window=None, crop=None, origins=None):
+    """the frames a call stores, [FRAMES][h][w][C]: the window slice or the per-frame crops of `full`, or `full`"""
+    if crop is not None:
+        return RC.slices(full, crop[0], crop[1], origins)
+    if window is not None:
+        x0, y0, w, h = window
+        return full[:, y0:y0 + h, x0:x0 + w]
+    return full
+
+
 def compose(full, window=None, crop=None, origins=None, lut=None, src=None, flips=None, strides=None, base=0,
             frame_stride=None, out=None):
     """The composition every expected array is made by, arguments spelled out (the fixture checks call it directly): the window
     slice or the per-frame crops of `full`, then -- with a table -- the view's scatter into `out`, else the samples themselves."""
-    if crop is not None:
-        cut = RC.slices(full, crop[0], crop[1], origins)
-    elif window is not None:
-        x0, y0, w, h = window
-        cut = full[:, y0:y0 + h, x0:x0 + w]
-    else:
-        cut = full
+    cut = cut_of(full, window, crop, origins)
     if lut is None:
         n = cut[0].size
         for f in range(cut.shape[0]):
@@ -495,29 +594,104 @@ def compose(full, window=None, crop=None, origins=None, lut=None, src=None, flip
     return V.scatter(out, base, cut, lut, src, flips, strides, frame_stride)
 
 
-@functools.lru_cache(maxsize=None)
-def _expected(kind, geo, filt, opt, win, out):
-    case = Case(kind, geo, filt, opt, win, out, "none", L.RESIZE_AUTO)
-    o = OUTPUTS[out]
-    item, n, fs, total = out_geometry(case)
+def _compose_case(case, base, fs, total, origins):
+    """the output buffer of a legal case without a destination: `total` elements of sentinels, the frames `fs` elements apart from
+    element `base` on"""
+    o = OUTPUTS[case.out]
+    item, n, _, _ = out_geometry(case)
     want = np.full(total * item, SENTINEL, dtype=np.uint8).view({1: np.uint8, 2: np.uint16, 4: np.uint32}[item])
-    full = full_bytes(kind, geo, filt, opt)
+    full = full_bytes(case.kind, case.geo, case.filt, case.opt)
     w, h = frame_size(case)
     if o.elem:
-        wrote = compose(full, window_of(case), crop_size(geo) if o.crop else None, origins_of(geo) if o.crop else None,
-                        lut_of(case), out_channels(case), flips_of(case), tensor_strides(case), GUARD, fs, want)
+        wrote = compose(full, window_of(case), crop_size(case.geo) if o.crop else None, origins if o.crop else None,
+                        lut_of(case), out_channels(case), flips_of(case), tensor_strides(case), base, fs, want)
         assert wrote == FRAMES * len(out_channels(case)) * w * h
     else:
-        wrote = compose(full, window_of(case), base=GUARD, frame_stride=fs, out=want)
+        wrote = compose(full, window_of(case), base=base, frame_stride=fs, out=want)
         assert wrote == FRAMES * n
     want.setflags(write=False)
     return want
+
+
+@functools.lru_cache(maxsize=None)
+def _expected(kind, geo, filt, opt, win, out):
+    case = Case(kind, geo, filt, opt, win, out, "none", L.RESIZE_AUTO)
+    _, _, fs, total = out_geometry(case)
+    return _compose_case(case, GUARD, fs, total, origins_of(geo))
 
 
 def expected(case):
     """the whole output buffer of a legal case as elements: sentinels in front, between the frames, behind, and at every element
     of a tensor frame its strides do not name.  It depends on neither the source layout nor the forced path."""
     return _expected(*case[:6])
+
+
+@functools.lru_cache(maxsize=None)
+def _expected_dest(kind, geo, filt, opt, win, dest, tight):
+    case = Case(kind, geo, filt, opt, win, "bytes", "none", L.RESIZE_AUTO)
+    t = dest_layout(case, dest, tight)
+    want = DM.pack(t, cut_of(full_bytes(kind, geo, filt, opt), window_of(case)))
+    want.setflags(write=False)
+    return want
+
+
+def expected_dest(case, dest):
+    """The whole buffer of dest_layout() as bytes after a legal bytes-out case: sentinels, with the frames compose() stores for the
+    case put where the formula of tests/resize_dest_model.py names (its offsets, not restated here).  The guard, the frame gaps,
+    row padding and plane padding keep the sentinel."""
+    return _expected_dest(*case[:5], dest, False)
+
+
+# ---- the host entries ---------------------------------------------------------------------------------------------------
+#
+# lanczos_resize_dest_host takes every bytes-out case, lanczos_resize_tensor_source_host every tensor case.  A host entry has no
+# frame stride: the frames lie the layout's own extent apart, and the buffers are exactly as long as include/lanczos_hip.h says:
+# extent * FRAMES elements of a tensor, extent * (FRAMES - 1) + named bytes of a destination, w * h * C * bps * FRAMES otherwise.
+# The origins rule: the host entry validates its origin array and refuses an origin outside the output with ERR_BAD_ARG, where
+# the device entries clamp.  The host walk therefore passes origins_of() after the clamp (host_origins_of(): the same windows,
+# so the same expected frames) and keeps origins_of() itself as one refused request per crop output.
+
+def host_origins_of(geo):
+    """origins_of() as the kernels clamp them: every origin inside the output, the same crops"""
+    _, _, ow, oh = GEOMETRIES[geo]
+    w, h = crop_size(geo)
+    inside = RC.clamp(origins_of(geo), ow, oh, w, h).astype(np.int32)
+    assert not np.array_equal(inside, origins_of(geo))
+    return np.ascontiguousarray(inside)
+
+
+def host_out_bytes(case, dest=None):
+    """the size of `out` as the header states it"""
+    if dest:
+        t = dest_layout(case, dest, tight=True)
+        return t.extent * (FRAMES - 1) + t.named
+    item, n, _, _ = out_geometry(case)
+    return item * n * FRAMES
+
+
+@functools.lru_cache(maxsize=None)
+def _expected_host(kind, geo, filt, opt, win, out):
+    case = Case(kind, geo, filt, opt, win, out, "none", L.RESIZE_AUTO)
+    _, n, _, _ = out_geometry(case)
+    return _compose_case(case, 0, n, n * FRAMES, origins_of(geo)).view(np.uint8)
+
+
+def expected_host(case, dest=None):
+    """the bytes of `out` after a legal case through its host entry: the composition of expected() / expected_dest() on the tight
+    strides.  What the strides do not name -- padded tensor rows and planes, destination padding -- holds the sentinel."""
+    if dest:
+        return _expected_dest(*case[:5], dest, True)
+    return _expected_host(*case[:6])
+
+
+@functools.lru_cache(maxsize=None)
+def host_source_of(kind, geo, src):
+    """source_of()'s frames and strides re-laid as the host entry reads them: the layout's own extent apart, the first byte on a
+    dword"""
+    k = KINDS[kind]
+    rs, cs, _ = source_strides(kind, geo, src)
+    return SM.build(frames_of(kind, geo), "interleaved" if src == "pitched" else "planar", rs, cs if src == "planar" else None,
+                    base=0, seed=5)
 
 
 def first_difference(got, want, f32):

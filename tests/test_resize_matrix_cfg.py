@@ -2,7 +2,10 @@
 with the error code, the planner facts the geometries were chosen for still hold, every leaf of the dispatcher is reached by a
 legal case of every kind that can reach it, the library's own route decision (rs_route, run on the host by
 tests/native/resize_route_check.hip) is the prediction for every legal case, and the composition that makes the expected arrays
-reproduces the committed Pillow fixtures.  No GPU needed."""
+reproduces the committed Pillow fixtures.  The destination dimension has the same checks: DEST_RULES against the validators,
+rs_route's destination route and fused instance against predict_dest() / predict_dest_main() for every legal pair, every
+(dest, route) pair and every leaf of a destination reached, expected_dest() between its sentinels; and the tight buffers of the
+host walk are what the header says.  No GPU needed."""
 import collections
 import ctypes
 import functools
@@ -164,10 +167,15 @@ def test_plan_facts():
 
 
 def test_every_leaf_is_reached():
-    """every leaf of the written list by at least one legal case, and by every kind that can reach it -- and by no other"""
+    """every leaf of the written list by at least one legal case, and by every kind that can reach it -- and by no other; the
+    leaves of a destination (the unpack kernels, the planar-out families) by the destination cases, and every (dest, route) pair
+    by every kind that can reach it"""
     assert len(M.FUSED_FAMILIES) == len(set(M.FUSED_FAMILIES)) == 15
     names = set(M.FUSED_FAMILIES) | set(M.MAINS) | set(M.ALPHA_LEAVES) | {"reduce"} | set(M.PACKS) | set(M.FOLLOWERS)
+    assert len(names) + len(M.DEST_LEAVES) == len(M.LEAVES) and not names & set(M.DEST_LEAVES)
+    names |= set(M.DEST_LEAVES)
     assert names == set(M.LEAVES) and len(M.MAINS) == 8 and len(M.PACKS) == 3 and len(M.FOLLOWERS) == 4
+    assert len(M.UNPACKS) == 3 and M.PLANAR_OUT_FAMILIES == ("fused<1, 0 + planar_out>", "fused<1, 0 + planar + planar_out>")
     reached = collections.defaultdict(set)
     reports = set()
     for case in M.cases():
@@ -176,9 +184,27 @@ def test_every_leaf_is_reached():
             for leaf in M.leaves_of(pred):
                 reached[leaf].add(case.kind)
             reports.add((pred.last_kernel, pred.tensor_route, pred.source_route))
+    assert not set(reached) & set(M.DEST_LEAVES)     # no case without a destination reaches a leaf of one
+    pairs = collections.defaultdict(set)
+    dest_mains = collections.defaultdict(set)
+    for case, dest in M.dest_cases():
+        if M.dest_legality(case, dest) is None:
+            main, unpack = M.predict_dest_main(case, dest)
+            for leaf in (main, unpack):
+                if leaf in M.DEST_LEAVES:
+                    reached[leaf].add(case.kind)
+            dest_mains[case.kind].add(main)
+            pairs[case.kind].add((dest, M.predict_dest(case, dest)))
     for leaf, kinds in M.LEAVES.items():
         assert reached[leaf] == set(kinds), (leaf, sorted(reached[leaf]), sorted(kinds))
     assert set(reached) == set(M.LEAVES)
+    for kind, k in M.KINDS.items():
+        assert pairs[kind] == M.dest_pairs(kind), (kind, pairs[kind])
+        assert len(M.dest_pairs(kind)) == (2 if k.bps != 1 and k.channels > 1 else 4)
+        # every main kernel that stores bytes also stores them in front of a destination
+        assert dest_mains[kind] - set(M.PLANAR_OUT_FAMILIES) == {m for m in M.MAINS + M.FUSED_FAMILIES
+                                                                 if m != "none" and kind in M.LEAVES[m] and
+                                                                 (m in M.MAINS or m in (M.family(k.bps, 0), M.family(1, 32), M.family(1, 64)))}, kind
     assert {r[0] for r in reports} == {L.KERNEL_RESIZE_FUSED, L.KERNEL_RESIZE_TWO_PASS, L.KERNEL_RESIZE_NEAREST}
     assert {r[1] for r in reports} == {0, L.TENSOR_FUSED, L.TENSOR_CONVERTED}
     assert {r[2] for r in reports} == {None, L.SOURCE_DIRECT, L.SOURCE_PACKED}
@@ -280,39 +306,148 @@ def test_the_route_is_the_prediction(route_exe, tmp_path):
         assert rt.err == L.ERR_UNSUPPORTED, (M.describe(case), rt)
 
 
+@functools.lru_cache(maxsize=None)
+def _dest_validator(kind, geo, win, dest):
+    case = M.Case(kind, geo, "lanczos", "none", win, "bytes", "none", L.RESIZE_AUTO)
+    d = M.desc_of(case)
+    window = M.window_of(case)
+    s = M.dest_struct(case, dest)
+    return L._lib().lanczos_resize_dest_validate(ctypes.byref(d), ctypes.byref(L.resize_window(d, window)) if window else None,
+                                                 ctypes.byref(s))
+
+
+def test_the_destination_rules_are_the_validators():
+    """every (case, dest) pair: DEST_RULES refuse it exactly where the validators do in the order lanczos_resize_dest_device calls
+    them (descriptor, source, destination, then the options and the plan), with that code; and nothing but the one new row tells
+    a pair from its case"""
+    verdicts = collections.Counter()
+    for case, dest in M.dest_cases():
+        said = M.dest_legality(case, dest)
+        verdicts[said] += 1
+        assert said != M.NA
+        lib, d = L._lib(), M.desc_of(case)
+        rc = lib.lanczos_resize_validate(ctypes.byref(d))
+        if rc == L.OK and case.src != "none":
+            rc = lib.lanczos_resize_source_validate(ctypes.byref(d), ctypes.byref(M.source_struct(case)))
+        if rc == L.OK:
+            rc = _dest_validator(case.kind, case.geo, case.win, dest)
+        if rc == L.OK:
+            rc, fused = _validators(*case[:7])
+            if rc == L.OK and case.force == L.RESIZE_FUSED and not fused:
+                rc = L.ERR_UNSUPPORTED
+        assert (said or L.OK) == rc, (M.describe(case), dest, said, rc)
+        k = M.KINDS[case.kind]
+        wide_planes = dest == "planar" and k.bps != 1 and k.channels > 1
+        if not wide_planes:
+            assert said == M.legality(case), (M.describe(case), dest)
+        elif M.legality(case) is None:
+            assert said == L.ERR_UNSUPPORTED, (M.describe(case), dest)
+    bytes_out = [c for c in M.cases() if c.out == "bytes" and M.legality(c) != M.NA]
+    assert sum(verdicts.values()) == 2 * len(bytes_out)
+    assert verdicts[None] > 19000 and verdicts[L.ERR_UNSUPPORTED] > verdicts[L.ERR_BAD_ARG] > 1000, verdicts
+    names = [n for n, _, _ in M.DEST_RULES]
+    assert names.index("planar destinations are 8-bit only") == names.index("planar sources are 8-bit only") + 1
+    # one plane is the pitched shape, of wide samples too; a pitch off a dword wherever the sample width leaves one
+    for kind, k in M.KINDS.items():
+        c = M.Case(kind, "down", "lanczos", "none", "sub", "bytes", "none", L.RESIZE_AUTO)
+        assert M.dest_legality(c, "planar") == (L.ERR_UNSUPPORTED if k.bps != 1 and k.channels > 1 else None)
+        assert M.dest_shape(c, "planar") == ("planar" if k.channels > 1 else "interleaved")
+        assert (M.dest_strides(c, "pitched")[0] % 4 != 0) == (k.bps != 4), kind
+
+
 def test_the_destination_route(route_exe, tmp_path):
-    """every legal bytes-out case of three kinds on three geometries, into pitched rows and -- where the validator takes them --
-    into planes: the route's destination is predict_dest's, and the fused instance is a planar-out one exactly where planes are
-    stored DIRECT"""
-    todo = []
-    for case in M.cases(kinds=("u8x3", "rgba", "u16x3"), geos=("down", "h", "tall")):
-        if case.out != "bytes" or M.legality(case) is not None:
-            continue
-        d = M.desc_of(case)
-        win = M.window_of(case)
-        for dest in M.DESTS:
-            s = L.ResizeDest()
-            s.row_stride, s.chan_stride, s.pix_stride = M.dest_strides(case, dest)
-            rc = L._lib().lanczos_resize_dest_validate(ctypes.byref(d), ctypes.byref(L.resize_window(d, win)) if win else None,
-                                                       ctypes.byref(s))
-            assert rc == (L.ERR_UNSUPPORTED if dest == "planar" and M.KINDS[case.kind].bps != 1 else L.OK), (M.describe(case), dest)
-            if rc == L.OK:
-                todo.append((case, dest))
-            if dest == "pitched":
-                assert s.row_stride % 4, (M.describe(case), s.row_stride)
-    assert len(todo) > 2000 and {dest for _, dest in todo} == set(M.DESTS)
+    """every legal (case, dest) pair of every kind on every geometry, into pitched rows and -- where the validator takes them --
+    into planes: the route's destination is predict_dest's, the fused instance is predict_dest_main's (a planar-out one exactly
+    where planes are stored DIRECT), and nothing in front of the store differs from the case without a destination"""
+    todo = [(case, dest) for case, dest in M.dest_cases() if M.dest_legality(case, dest) is None]
+    assert len(todo) > 19000 and {dest for _, dest in todo} == set(M.DESTS)
     routes = _routes(route_exe, tmp_path, [M.route_line(c, dest) for c, dest in todo])
     seen = collections.Counter()
     for (case, dest), rt in zip(todo, routes):
         want = M.predict_dest(case, dest)
         assert rt.err == L.OK and rt.dest_route == want, (M.describe(case), dest, rt, want)
         planar_out = rt.main == "fused" and bool(rt.flags & M.PLANAR_OUT)
-        assert planar_out == (dest == "planar" and want == L.DEST_DIRECT), (M.describe(case), dest, rt)
+        assert planar_out == (M.dest_shape(case, dest) == "planar" and want == L.DEST_DIRECT), (M.describe(case), dest, rt)
+        main = M.family(rt.bps, rt.flags) if rt.main == "fused" else rt.main
+        assert main == M.predict_dest_main(case, dest)[0], (M.describe(case), dest, rt)
         p = M.predict(case)   # a destination changes nothing in front of the store
-        assert (rt.main == "fused", bool(rt.reduce), bool(rt.pack), rt.source_route or None) == \
-            (p.main.startswith("fused<"), p.reduce, p.pack is not None, p.source_route), (M.describe(case), dest, rt, p)
-        seen[dest, want] += 1
-    assert len(seen) == 4 and min(seen.values()) > 50, seen
+        assert (rt.main == "fused", bool(rt.reduce), bool(rt.pack), rt.source_route or None, rt.last_kernel, rt.tensor_route) == \
+            (p.main.startswith("fused<"), p.reduce, p.pack is not None, p.source_route, p.last_kernel, 0), (M.describe(case), dest, rt, p)
+        seen[case.kind, dest, want] += 1
+    for kind in M.KINDS:
+        assert {(d, r) for k, d, r in seen if k == kind} == M.dest_pairs(kind), kind
+    assert min(seen.values()) > 50, seen
+
+
+def test_expected_dest_arrays_are_between_sentinels():
+    """the guard, the gap between the frames, row padding and plane padding of expected_dest hold the sentinel, the named bytes are
+    frames * w * h * C * bps of them and hold the frames of expected(); the buffer ends GUARD elements behind the last named byte"""
+    import resize_dest_model as DM
+    for kind, geo, win in (("rgba", "down", "whole"), ("u8x3", "strips", "sub"), ("u8x1", "tall", "sub"), ("u16x3", "down", "sub"),
+                           ("u16x1", "up", "whole"), ("f32x4", "wideK", "whole"), ("f32x1", "h", "sub")):
+        k = M.KINDS[kind]
+        case = M.Case(kind, geo, "bicubic", "fbox", win, "bytes", "none", L.RESIZE_AUTO)
+        w, h = M.frame_size(case)
+        shape = (M.FRAMES, h, w, k.channels)
+        _, n, fs, _ = M.out_geometry(case)
+        plain = M.expected(case)
+        frames = np.stack([plain[M.GUARD + f * fs:M.GUARD + f * fs + n].reshape(h, w, k.channels) for f in range(M.FRAMES)])
+        for dest in M.DESTS:
+            if M.dest_legality(case, dest) is not None:
+                continue
+            t = M.dest_layout(case, dest)
+            want = M.expected_dest(case, dest)
+            named = DM.named_mask(t, shape, k.bps)
+            assert int(named.sum()) == M.FRAMES * w * h * k.channels * k.bps
+            assert want.dtype == np.uint8 and want.size == t.buf.size and (want[~named] == M.SENTINEL).all()
+            assert (t.buf == M.SENTINEL).all()
+            assert np.array_equal(DM.unpack(t, shape, frames.dtype, buf=want), frames)
+            # the layout: residue, frame stride, guards, a buffer that ends behind the last named byte
+            g = M.GUARD * k.bps
+            assert t.at == g + (3 * k.bps) % 4 and t.frame_stride == t.extent + M.FRAME_GAP * k.bps
+            first, last = int(np.argmax(named)), named.size - 1 - int(np.argmax(named[::-1]))
+            assert first == t.at and last + 1 + g == named.size and t.at + 2 * t.frame_stride + t.named == last + 1
+            assert t.named < t.extent                       # the padding behind the last row is not in the buffer
+            for f in range(M.FRAMES - 1):
+                assert not named[t.at + f * t.frame_stride + t.named:t.at + (f + 1) * t.frame_stride].any()
+            rows = named[t.at:t.at + t.row_stride]
+            assert rows[:w * k.bps].all() and not rows.all()   # row padding
+            if t.layout == "planar":
+                assert t.chan_stride > (h - 1) * t.row_stride + w + 3 and not named[t.at + t.chan_stride - 5:t.at + t.chan_stride].any()
+            # the tight form of the host entry: the same frames, the layout's own extent apart, as long as the header says
+            tt = M.dest_layout(case, dest, tight=True)
+            host = M.expected_host(case, dest)
+            assert (tt.at, tt.frame_stride) == (0, tt.extent) and host.size == M.host_out_bytes(case, dest) == 2 * tt.extent + tt.named
+            assert np.array_equal(DM.unpack(tt, shape, frames.dtype, buf=host), frames)
+            assert (host[~DM.named_mask(tt, shape, k.bps)] == M.SENTINEL).all()
+
+
+def test_expected_host_arrays():
+    """the tight buffers of the host walk: as long as the header says, the frames of expected() one extent apart, the sentinel
+    wherever the strides name nothing; the origins of the host walk are those of the device walk after the clamp"""
+    for out in M.OUTPUTS:
+        case = M.Case("rgba", "down", "bicubic", "fbox", "whole", out, "none", L.RESIZE_AUTO)
+        item, n, fs, _ = M.out_geometry(case)
+        want, host = M.expected(case).view(np.uint8), M.expected_host(case)
+        assert host.dtype == np.uint8 and host.size == M.host_out_bytes(case) == M.FRAMES * n * item
+        for f in range(M.FRAMES):
+            assert np.array_equal(host[f * n * item:(f + 1) * n * item], want[(M.GUARD + f * fs) * item:(M.GUARD + f * fs + n) * item])
+        if M.OUTPUTS[out].layout == "chwp":
+            assert (host.reshape(-1, item) == M.SENTINEL).all(axis=1).sum() > M.FRAMES * 5
+    for geo, (_, _, ow, oh) in M.GEOMETRIES.items():
+        w, h = M.crop_size(geo)
+        org, inside = M.origins_of(geo), M.host_origins_of(geo)
+        assert inside.dtype == np.int32 and (inside >= 0).all() and (inside[:, 0] <= ow - w).all() and (inside[:, 1] <= oh - h).all()
+        assert tuple(inside[1]) == (ow - w, 0) and np.array_equal(inside[[0, 2]], org[[0, 2]])
+    for kind, k in M.KINDS.items():
+        for src in ("pitched", "planar"):
+            if src == "planar" and (k.bps != 1 or k.channels == 1):
+                continue
+            s = M.host_source_of(kind, "down", src)
+            assert s.frame_stride == s.extent and s.at % 4 == 0
+            assert (s.row_stride, s.chan_stride, s.pix_stride) == M.source_strides(kind, "down", src)
+            assert np.array_equal(M.SM.unpack(s, M.frames_of(kind, "down").shape, k.dtype).view(np.uint8),
+                                  M.frames_of(kind, "down").view(np.uint8))
 
 
 def test_the_sources_name_what_the_issue_asks():

@@ -3,7 +3,13 @@ output, source layout and forced path that is a request goes through the device 
 sentinels.  A legal case is compared element for element with the numpy models composed on the CPU (float samples by the rule of
 resize32_model.same), and the kernel, tensor route and source route the context reports with cfg.predict; a refused case must
 return its code and leave every sentinel, and the legal case after it on the same context must still be right.  One test per
-(kind, geometry); the reference of a case is computed once and shared by its sources and forced paths."""
+(kind, geometry); the reference of a case is computed once and shared by its sources and forced paths.
+The same test then walks the pair's destination cases (cfg.dest_cases: every bytes-out request into pitched rows and into planes)
+through lanczos_resize_dest_device with the same context, stream and sentinels: the whole buffer -- named bytes, row and plane
+padding, frame gaps and guards in one comparison -- against cfg.expected_dest, and the kernel, source route and destination route
+the context reports against cfg.predict / cfg.predict_dest."""
+import collections
+
 import numpy as np
 import pytest
 
@@ -146,6 +152,86 @@ def _run(ctx, kind, geo):
     return legal, refused, failures
 
 
+def _run_dest(ctx, kind, geo):
+    """every destination case of (kind, geo), once, as _run walks the cases without one; returns (legal, refused, failures, the
+    count of every (dest, reported route) of a legal case, the leaves of cfg.DEST_LEAVES whose case ran and reported as predicted)"""
+    import torch
+    dev = _Device(kind, geo)
+    k = M.KINDS[kind]
+    todo = list(M.dest_cases((kind,), (geo,)))
+    biggest = max(M.dest_layout(c, d).buf.size for c, d in todo)
+    out = torch.empty((biggest + 3) // 4 * 4 + 64, dtype=torch.uint8, device="cuda")
+    assert out.data_ptr() % 4 == 0
+    side = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    legal = refused = 0
+    failures = []
+    seen = collections.Counter()
+    leaves = set()
+    source_route, dest_route = ctx.last_source_route(), ctx.last_dest_route()
+    after_refusal = ""
+    try:
+        with torch.cuda.stream(side):
+            for case, dest in todo:
+                verdict = M.dest_legality(case, dest)
+                what = f"{M.describe(case)} -> {dest}"
+                t = M.dest_layout(case, dest)
+                d_in, in_fs, source = dev.input(case)
+                out.fill_(M.SENTINEL)
+                ctx.resize_force(case.force)
+
+                def call():
+                    ctx.resize_device(M.desc_of(case), d_in, out.data_ptr() + t.at, M.FRAMES, in_frame_stride=in_fs,
+                                      out_frame_stride=t.frame_stride, stream=side.cuda_stream, box=M.box_of(case),
+                                      reducing_gap=M.gap_of(case), window=M.window_of(case), source=source,
+                                      dest=M.dest_struct(case, dest))
+                if verdict is not None:
+                    refused += 1
+                    try:
+                        call()
+                        code = L.OK
+                    except L.LanczosError as e:
+                        code = e.code
+                    if code != verdict:
+                        failures.append(f"{what}: returned {code}, not {verdict}")
+                    if bool((out != M.SENTINEL).any()):
+                        failures.append(f"{what}: a refused call wrote to the output")
+                    if (ctx.last_source_route(), ctx.last_dest_route()) != (source_route, dest_route):
+                        failures.append(f"{what}: a refused call changed the source or the destination route")
+                        source_route, dest_route = ctx.last_source_route(), ctx.last_dest_route()
+                    after_refusal = " (after a refusal)"
+                    continue
+                legal += 1
+                call()
+                got = out.cpu().numpy()
+                want = M.expected_dest(case, dest)
+                pred, want_route = M.predict(case), M.predict_dest(case, dest)
+                word = np.uint32 if k.bps == 4 else np.uint8        # whole floats, by the rule of resize32_model.same
+                diff = M.first_difference(got[:want.size].view(word), want.view(word), k.bps == 4)
+                if diff is not None:
+                    failures.append(f"{what}{after_refusal}: first difference at {'word' if k.bps == 4 else 'byte'} "
+                                    f"{diff[0] + M.GUARD} of the buffer (frame 0 starts at byte {t.at}): {diff[1]:#x} != {diff[2]:#x}; "
+                                    f"predicted {tuple(pred)}, destination route {want_route}")
+                if not (got[want.size:] == M.SENTINEL).all():
+                    failures.append(f"{what}: a byte behind the buffer was written")
+                if pred.source_route is not None:
+                    source_route = pred.source_route
+                dest_route = want_route
+                report = (ctx.last_kernel(), ctx.last_source_route(), ctx.last_dest_route())
+                seen[dest, report[2]] += 1
+                if report != (pred.last_kernel, source_route, dest_route):
+                    failures.append(f"{what}: reported (kernel, source route, destination route) {report}, predicted "
+                                    f"{(pred.last_kernel, source_route, dest_route)}")
+                    source_route, dest_route = report[1:]
+                elif diff is None:
+                    leaves.update(leaf for leaf in M.predict_dest_main(case, dest) if leaf in M.DEST_LEAVES)
+                after_refusal = ""
+    finally:
+        ctx.resize_force(L.RESIZE_AUTO)
+        torch.cuda.synchronize()
+    return legal, refused, failures, seen, leaves
+
+
 @pytest.mark.parametrize("geo", list(M.GEOMETRIES))
 @pytest.mark.parametrize("kind", list(M.KINDS))
 def test_matrix(ctx, kind, geo):
@@ -153,3 +239,22 @@ def test_matrix(ctx, kind, geo):
     assert not failures, f"{len(failures)} failures in {legal} legal and {refused} refused cases, the first: {failures[0]}"
     want = [M.legality(c) for c in M.cases((kind,), (geo,))]
     assert legal == sum(v is None for v in want) > 0 and refused == sum(v not in (None, M.NA) for v in want)
+    # ... and the same requests with a destination, where they store bytes
+    legal, refused, failures, seen, leaves = _run_dest(ctx, kind, geo)
+    assert not failures, (f"{len(failures)} failures in {legal} legal and {refused} refused cases with a destination, the first: "
+                          f"{failures[0]}")
+    pairs = list(M.dest_cases((kind,), (geo,)))
+    want = [M.dest_legality(c, d) for c, d in pairs]
+    assert M.NA not in want and len(pairs) == 2 * sum(c.out == "bytes" and v != M.NA for c, v in
+                                                       ((c, M.legality(c)) for c in M.cases((kind,), (geo,))))
+    assert legal == sum(v is None for v in want) > 0 and refused == sum(v is not None for v in want) > 0
+    # what the context reported, counted: every (dest, route) pair the rules predict for this geometry; where a fused plan
+    # exists that is every pair the kind can reach -- all four for 8-bit samples, both routes of pitched rows for wide ones
+    predicted = collections.Counter((d, M.predict_dest(c, d)) for (c, d), v in zip(pairs, want) if v is None)
+    assert seen == predicted, (seen, predicted)
+    k = M.KINDS[kind]
+    if geo in ("down", "up", "wideK", "strips"):
+        assert set(seen) == M.dest_pairs(kind) and len(seen) == (2 if k.bps != 1 and k.channels > 1 else 4), seen
+        assert leaves == {leaf for leaf in M.DEST_LEAVES if kind in M.LEAVES[leaf]}, leaves
+    else:   # no fused plan without a box: the pass kernels, the gather and the copies, every one of them unpacked
+        assert leaves >= {leaf for leaf in M.UNPACKS if kind in M.LEAVES[leaf]}, leaves
