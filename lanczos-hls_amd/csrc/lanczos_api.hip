@@ -14,6 +14,7 @@
 #include <map>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/lanczos_hip.h"
@@ -27,6 +28,7 @@
 #include "lanczos_resize.hpp"
 #include "lanczos_kernels_common.hpp"
 #include "lanczos_taps.hpp"
+#include "lanczos_upscale.hpp"
 
 namespace {
 
@@ -103,9 +105,6 @@ struct lanczos_ctx {
 static constexpr size_t kStampBytes = 16384 * 8 * 6 * 8;
 #endif
 static constexpr size_t kMaxPlans = 32;
-#ifndef LZ_SPLIT_RULE
-#define LZ_SPLIT_RULE 1
-#endif
 
 namespace {
 
@@ -128,6 +127,17 @@ void route_launch(lanczos_ctx* ctx, int main_kernel, int prefix_route) {
     if (ctx->route_launches < 0x7fff) ctx->route_launches++;
     ctx->route_seen |= 1 << prefix_route;
     ctx->last_route = main_kernel | prefix_route << 4 | ctx->route_seen << 8 | ctx->route_launches << 16;
+}
+
+// a scratch block of the context, grown to `bytes` (never shrunk; the old block is freed first)
+int grow_block(lanczos_ctx* ctx, void** block, size_t* have, size_t bytes) {
+    if (*have >= bytes) return LANCZOS_OK;
+    if (*block) (void)hipFree(*block);
+    *block = nullptr;
+    *have = 0;
+    LZ_HIP(ctx, hipMalloc(block, bytes));
+    *have = bytes;
+    return LANCZOS_OK;
 }
 
 void free_plan(Plan* p) {   // nothing in flight reads it any more
@@ -227,27 +237,24 @@ int get_plan(lanczos_ctx* ctx, const lanczos_desc* d, hipStream_t stream, Plan**
         delete p;
         return LANCZOS_ERR_HIP;
     }
-    struct HostView {   // (the sections below were written against a std::vector; same two members)
-        uint8_t* b;
-        uint8_t* data() const { return b; }
-    } host{(uint8_t*)p->host_block};
-    memset(host.data(), 0, total);
+    uint8_t* const host = (uint8_t*)p->host_block;
+    memset(host, 0, total);
     if (p->rat.ok) {
-        memcpy(host.data() + off_hwf, p->rat.h_wf.data(), p->rat.h_wf.size() * 4);
-        memcpy(host.data() + off_vwf, p->rat.v_wf.data(), p->rat.v_wf.size() * 4);
-        memcpy(host.data() + off_hint, p->rat.h_int.data(), p->rat.h_int.size());
-        memcpy(host.data() + off_vint, p->rat.v_int.data(), p->rat.v_int.size());
+        memcpy(host + off_hwf, p->rat.h_wf.data(), p->rat.h_wf.size() * 4);
+        memcpy(host + off_vwf, p->rat.v_wf.data(), p->rat.v_wf.size() * 4);
+        memcpy(host + off_hint, p->rat.h_int.data(), p->rat.h_int.size());
+        memcpy(host + off_vint, p->rat.v_int.data(), p->rat.v_int.size());
     }
-    if (p->ratp.ok) memcpy(host.data() + off_pw, p->ratp.phase_w, sizeof(p->ratp.phase_w));
+    if (p->ratp.ok) memcpy(host + off_pw, p->ratp.phase_w, sizeof(p->ratp.phase_w));
     if (p->fast_ok) {  // row 0: integer phase, row ph: phase ph
-        memcpy(host.data() + off_xw, p->fast.wi, lz::kMaxTaps * 8);
+        memcpy(host + off_xw, p->fast.wi, lz::kMaxTaps * 8);
         for (int ph = 1; ph < lz::kFastMaxS; ph++)
-            memcpy(host.data() + off_xw + (size_t)ph * lz::kMaxTaps * 8, p->fast.wd[ph], lz::kMaxTaps * 8);
+            memcpy(host + off_xw + (size_t)ph * lz::kMaxTaps * 8, p->fast.wd[ph], lz::kMaxTaps * 8);
     }
-    memcpy(host.data() + off_hf, p->H.first.data(), (size_t)d->out_w * 4);
-    memcpy(host.data() + off_vf, p->V.first.data(), (size_t)d->out_h * 4);
-    memcpy(host.data() + off_hw, p->H.w.data(), (size_t)d->out_w * taps * 8);
-    memcpy(host.data() + off_vw, p->V.w.data(), (size_t)d->out_h * taps * 8);
+    memcpy(host + off_hf, p->H.first.data(), (size_t)d->out_w * 4);
+    memcpy(host + off_vf, p->V.first.data(), (size_t)d->out_h * 4);
+    memcpy(host + off_hw, p->H.w.data(), (size_t)d->out_w * taps * 8);
+    memcpy(host + off_vw, p->V.w.data(), (size_t)d->out_h * taps * 8);
     const bool capturing = lz::stream_capturing(stream);   // hipStreamIsCapturing: the upload below must not become a graph node
     hipStream_t up = stream;
     e = hipMalloc(&p->dev_block, total);
@@ -302,28 +309,6 @@ int get_plan(lanczos_ctx* ctx, const lanczos_desc* d, hipStream_t stream, Plan**
     ctx->plan_order.touch(key);
     *out = p;
     return LANCZOS_OK;
-}
-
-int whole_or_strip(const lanczos_desc* d, int* row0, int* rows) {
-    if (d->out_rows == 0) {
-        *row0 = 0;
-        *rows = d->out_h;
-    } else {
-        *row0 = d->out_row0;
-        *rows = d->out_rows;
-    }
-    return LANCZOS_OK;
-}
-
-void strip_input_rows(const lz::AxisTaps& V, int a, int in_h, int row0, int rows, const lz::PrefixInfo& pi,
-                      int* in_row0, int* in_rows) {
-    int lo = V.first[row0];
-    int hi = V.first[row0 + rows - 1] + 2 * a - 1;
-    if (row0 < pi.K && pi.M2 - 1 > hi) hi = pi.M2 - 1;  // the in-place prefix reads a little deeper
-    if (lo < 0) lo = 0;
-    if (hi > in_h - 1) hi = in_h - 1;
-    *in_row0 = lo;
-    *in_rows = hi - lo + 1;
 }
 
 }  // namespace
@@ -388,11 +373,11 @@ int lanczos_strip_input_rows(const lanczos_desc* d, int out_row0, int out_rows, 
     lz::AxisTaps V;
     if (d->mode == LANCZOS_MODE_HLS) {
         lz::build_axis_hls(d->in_h, d->out_h, d->scale_n, d->scale_d, d->a, &V, d->reserved[0]);  // (the fixed-point stepper moves the window)
-        strip_input_rows(V, d->a, d->in_h, out_row0, out_rows, lz::PrefixInfo(), in_row0, in_rows);
+        lz::strip_input_rows(V.first.data(), d->a, d->in_h, out_row0, out_rows, lz::PrefixInfo(), in_row0, in_rows);
         return LANCZOS_OK;
     }
     lz::build_axis(d->in_h, d->out_h, d->scale_n, d->scale_d, d->a, &V);
-    strip_input_rows(V, d->a, d->in_h, out_row0, out_rows, lz::prefix_info(V), in_row0, in_rows);
+    lz::strip_input_rows(V.first.data(), d->a, d->in_h, out_row0, out_rows, lz::prefix_info(V), in_row0, in_rows);
     return LANCZOS_OK;
 }
 
@@ -643,22 +628,24 @@ int lanczos_force_kernel(lanczos_ctx* ctx, int family) {
     return LANCZOS_OK;
 }
 
+// (bytes per sample, a) -> <T, TAPS>: the instance ladder of k_rat, k_prefix and k_prefix_stream.  f(T(), integral_constant<TAPS>())
+extern "C++" {
+template <typename F>
+static void with_sample_taps(int bytes_per_sample, int a, F&& f) {
+    auto taps = [&](auto t) {
+        if (a == 2) f(t, std::integral_constant<int, 4>());
+        else if (a == 3) f(t, std::integral_constant<int, 6>());
+        else f(t, std::integral_constant<int, 8>());
+    };
+    if (bytes_per_sample == 1) taps(uint8_t());
+    else taps(uint16_t());
+}
+}
+
 // In-place prefix rows of an integer scale as a register-only kernel (k_prefix_reg) on `stream`, in FRONT of the marching kernel
 // (5 us by events of a 210 us step).  A fork / join onto a side stream so that it overlaps the march was measured and dropped
-// (the two event dependencies cost 14 us per step).  hipErrorNotSupported: no instance for this (sample type, scale, a) -- the
-// caller falls back to the general k_prefix behind the main kernel.
+// (the two event dependencies cost 14 us per step).  up_route sends a launch here only where prefix_reg_supports.
 static hipError_t launch_prefix_front(const lanczos_desc* d, const lz::FrameGeom& g, const Plan* p, hipStream_t stream) {
-#define LZ_PREFIX_REG_CONFIGS(X)                                                                                        \
-    X(uint8_t, 2, 2) X(uint8_t, 2, 3) X(uint8_t, 2, 4) X(uint8_t, 3, 2) X(uint8_t, 3, 3) X(uint8_t, 3, 4) X(uint8_t, 4, 2) \
-    X(uint8_t, 4, 3) X(uint8_t, 4, 4) X(uint16_t, 2, 3) X(uint16_t, 2, 4) X(uint16_t, 3, 3) X(uint16_t, 3, 4)
-    bool have = false;
-#define X(T, S, A)                                                                                                    \
-    if (d->bytes_per_sample == (int)sizeof(T) && d->scale_n == S && d->a == A && p->prefix.K == lz::prefix_K(S, A) && \
-        p->prefix.M == lz::prefix_M(S, A) && p->prefix.M2 == lz::prefix_M2(S, A))                                    \
-        have = true;
-    LZ_PREFIX_REG_CONFIGS(X)
-#undef X
-    if (!have) return hipErrorNotSupported;
     const int samples_w = d->out_w * d->channels;
     dim3 grid((samples_w + 127) / 128, g.frames);
 #define X(T, S, A)                                                                                  \
@@ -669,48 +656,166 @@ static hipError_t launch_prefix_front(const lanczos_desc* d, const lz::FrameGeom
     return hipGetLastError();
 }
 
-// the resample proper; ctx->mu is held by the caller
+// The event triple (start, middle, end) around one launch of a call, where timing is on.  begin() reserves it -- only once
+// nothing but a HIP failure can stop the call -- and records the start; commit() records the end and counts the triple
+// (ev_used += 3) after all three records succeeded, so timing_flush never meets an unrecorded event.
+struct LaunchTimer {
+    lanczos_ctx* ctx;
+    hipStream_t stream;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    int begin() {
+        if (!ctx->timing) return LANCZOS_OK;
+        if (ctx->ev_used + 3 > 3 * 4096) {
+            const int rc = timing_flush(ctx);
+            if (rc != LANCZOS_OK) return rc;
+        }
+        while ((int)ctx->ev.size() < ctx->ev_used + 3) {
+            hipEvent_t e;
+            LZ_HIP(ctx, hipEventCreate(&e));
+            ctx->ev.push_back(e);
+        }
+        ctx->ev_prefix_first.resize(ctx->ev.size() / 3 + 1, 0);
+        LZ_HIP(ctx, hipEventRecord(ctx->ev[ctx->ev_used], stream));
+        for (int i = 0; i < 3; i++) ev[i] = ctx->ev[ctx->ev_used + i];
+        return LANCZOS_OK;
+    }
+    int middle() {   // start..middle: the main kernel, or the prefix kernel that went in front of it
+        if (ev[0]) LZ_HIP(ctx, hipEventRecord(ev[1], stream));
+        return LANCZOS_OK;
+    }
+    int commit(bool prefix_first) {
+        if (!ev[0]) return LANCZOS_OK;
+        LZ_HIP(ctx, hipEventRecord(ev[2], stream));
+        ctx->ev_prefix_first[ctx->ev_used / 3] = prefix_first ? 1 : 0;
+        ctx->ev_used += 3;
+        return LANCZOS_OK;
+    }
+};
+
+// one launch of a route: the prefix rows in front, the main kernel, the prefix rows behind it, as the route lists them
+static int issue_launch(lanczos_ctx* ctx, const lanczos_desc* d, const Plan* p, const lz::UpRoute& rt, const lz::UpLaunch& launch,
+                        const lz::MarchFacts& facts, const lz::FrameGeom& g, hipStream_t stream) {
+    const int rows = rt.strip.rows, frames = launch.frames;
+    const bool front = launch.prefix == LANCZOS_ROUTE_PREFIX_FRONT;
+    LaunchTimer timer{ctx, stream};
+    int rc = timer.begin();
+    if (rc != LANCZOS_OK) return rc;
+    if (front) {
+        LZ_HIP(ctx, launch_prefix_front(d, g, p, stream));
+        if ((rc = timer.middle()) != LANCZOS_OK) return rc;
+    }
+    switch (rt.main) {
+        case LANCZOS_ROUTE_MAIN_HLS: {
+            const int tiles_x = (d->out_w + lz::kHlsTileW - 1) / lz::kHlsTileW;
+            const int tiles_y = (rows + lz::kHlsTileH - 1) / lz::kHlsTileH;
+            dim3 grid(tiles_x * tiles_y, frames);
+            if (d->bytes_per_sample == 1)
+                hipLaunchKernelGGL(lz::k_hls<uint8_t>, grid, dim3(lz::kHlsThreads), 0, stream, g, p->dev);
+            else
+                hipLaunchKernelGGL(lz::k_hls<uint16_t>, grid, dim3(lz::kHlsThreads), 0, stream, g, p->dev);
+            LZ_HIP(ctx, hipGetLastError());
+            break;
+        }
+        case LANCZOS_ROUTE_MAIN_MARCH: {
+            lz::FrameGeom gm = g;
+            const bool riding = launch.prefix == LANCZOS_ROUTE_PREFIX_RIDING;
+            if (riding) gm.prefix_K = p->prefix.K, gm.prefix_M = p->prefix.M, gm.prefix_M2 = p->prefix.M2;
+            LZ_HIP(ctx, lz::march_issue(*d, gm, p->dev, p->fast, stream, riding, facts, &ctx->wg_tabs));
+            break;
+        }
+        case LANCZOS_ROUTE_MAIN_NONE: break;   // a strip that ends inside the prefix rows: nothing marches
+        case LANCZOS_ROUTE_MAIN_TILE: LZ_HIP(ctx, lz::fast_launch(*d, g, p->dev, p->fast, stream)); break;
+        case LANCZOS_ROUTE_MAIN_RATP: LZ_HIP(ctx, lz::ratp_launch(*d, g, p->dev, p->ratp_dev, p->ratp_w_dev, stream)); break;
+        case LANCZOS_ROUTE_MAIN_RAT: {
+            const int row_bytes = d->out_w * d->channels * d->bytes_per_sample;
+            const int tiles_x = (row_bytes + lz::kRatTileRowBytes - 1) / lz::kRatTileRowBytes;
+            const int tiles_y = (rows + lz::kRatTileH - 1) / lz::kRatTileH;
+            dim3 grid(tiles_x * tiles_y, frames);
+            const bool ex = d->mode == LANCZOS_MODE_EXACT;
+            with_sample_taps(d->bytes_per_sample, d->a, [&](auto t, auto taps) {
+                using T = decltype(t);
+                constexpr int TAPS = decltype(taps)::value;
+                if (ex) hipLaunchKernelGGL((lz::k_rat<T, TAPS, true>), grid, dim3(lz::kRatThreads), 0, stream, g, p->dev, p->rat_dev);
+                else hipLaunchKernelGGL((lz::k_rat<T, TAPS, false>), grid, dim3(lz::kRatThreads), 0, stream, g, p->dev, p->rat_dev);
+            });
+            LZ_HIP(ctx, hipGetLastError());
+            break;
+        }
+        default: {
+            const int samples_w = d->out_w * d->channels;
+            const int tiles_x = (samples_w + lz::kGenTileW - 1) / lz::kGenTileW;
+            const int tiles_y = (rows + lz::kGenTileH - 1) / lz::kGenTileH;
+            dim3 grid(tiles_x * tiles_y, frames);
+            if (d->bytes_per_sample == 1)
+                hipLaunchKernelGGL(lz::k_generic<uint8_t>, grid, dim3(lz::kGenTileW), 0, stream, g, p->dev);
+            else
+                hipLaunchKernelGGL(lz::k_generic<uint16_t>, grid, dim3(lz::kGenTileW), 0, stream, g, p->dev);
+            LZ_HIP(ctx, hipGetLastError());
+        }
+    }
+    ctx->last_kernel = rt.kernel;
+    if (!front && (rc = timer.middle()) != LANCZOS_OK) return rc;
+    if (launch.prefix == LANCZOS_ROUTE_PREFIX_BEHIND || launch.prefix == LANCZOS_ROUTE_PREFIX_STREAMED) {
+        const int samples_w = d->out_w * d->channels, bw = rt.bw;
+        dim3 grid((samples_w + bw - 1) / bw, frames);
+        const int K = p->prefix.K, M = p->prefix.M, M2 = p->prefix.M2;
+        with_sample_taps(d->bytes_per_sample, d->a, [&](auto t, auto taps) {
+            using T = decltype(t);
+            constexpr int TAPS = decltype(taps)::value;
+            if (launch.prefix == LANCZOS_ROUTE_PREFIX_STREAMED)
+                hipLaunchKernelGGL((lz::k_prefix_stream<T, TAPS>), grid, dim3(128), 0, stream, g, p->dev, K, M);
+            else
+                hipLaunchKernelGGL((lz::k_prefix<T, TAPS>), grid, dim3(bw), rt.prefix_lds, stream, g, p->dev, K, M, M2);
+        });
+        LZ_HIP(ctx, hipGetLastError());
+    }
+    route_launch(ctx, rt.main, launch.prefix);
+    return timer.commit(front);
+}
+
+// the resample proper; ctx->mu is held by the caller.  The plan's facts and the marching instance's go to up_route
+// (lanczos_upscale.hpp), which decides everything the call does; what it lists is issued here.
 static int resample_device_locked(lanczos_ctx* ctx, const lanczos_desc* d, const void* d_in, void* d_out, int frames,
-                                  size_t in_frame_stride, size_t out_frame_stride, void* stream_v, bool in_split = false) {
-    int rc;
+                                  size_t in_frame_stride, size_t out_frame_stride, void* stream_v) {
     LZ_HIP(ctx, hipSetDevice(ctx->device));
     // NULL is the NULL (legacy default) stream -- NOT the context's private stream: a caller whose producers run
     // on the default stream (torch's default stream is handle 0) must be ordered behind them
     hipStream_t stream = (hipStream_t)stream_v;
     Plan* p = nullptr;
-    rc = get_plan(ctx, d, stream, &p);
+    const int rc = get_plan(ctx, d, stream, &p);
     if (rc != LANCZOS_OK) return rc;
+    lz::MarchFacts facts{};
+    const hipError_t fe = p->fast_ok ? lz::march_facts(*d, &facts) : hipErrorNotSupported;
+    if (fe != hipSuccess && fe != hipErrorNotSupported) LZ_HIP(ctx, fe);
 
-    int row0, rows;
-    whole_or_strip(d, &row0, &rows);
-    int in_row0, in_rows;
-    strip_input_rows(p->V, d->a, d->in_h, row0, rows, p->prefix, &in_row0, &in_rows);
-    const bool has_prefix = row0 < p->prefix.K;
-    if (has_prefix) {
-        // the prefix recurrence needs rows [0,M) of the output and [0,M2) of the H pass in one place
-        if (row0 != 0) return LANCZOS_ERR_UNSUPPORTED;
-        // (any depth runs: prefixes too deep for k_prefix's row arrays take the streaming form of the recurrence, k_prefix_stream)
-    }
+    lz::UpQuery q;
+    q.d = d, q.frames = frames;
+    q.in_frame_stride = in_frame_stride, q.out_frame_stride = out_frame_stride;
+    q.in = (uintptr_t)d_in, q.out = (uintptr_t)d_out;
+    q.force = ctx->force;
+    q.fast_ok = p->fast_ok, q.rat_ok = p->rat.ok, q.ratp_ok = p->ratp.ok;
+    q.prefix = p->prefix, q.v_first = p->V.first.data();
+    q.tile_kernel = lz::env().tile_kernel, q.separate_prefix = lz::env().separate_prefix, q.no_ratp = lz::env().no_ratp;
+    q.facts = fe == hipSuccess ? &facts : nullptr;
+    const lz::UpRoute rt = lz::up_route(q);
+    if (rt.err != LANCZOS_OK) return rt.err;
 
     lz::FrameGeom g{};
-    g.in = (const uint8_t*)d_in;
-    g.out = (uint8_t*)d_out;
     g.in_pitch = d->in_w * d->channels * d->bytes_per_sample;
     g.out_pitch = d->out_w * d->channels * d->bytes_per_sample;
-    g.in_frame_stride = in_frame_stride ? in_frame_stride : (size_t)g.in_pitch * in_rows;
-    g.out_frame_stride = out_frame_stride ? out_frame_stride : (size_t)g.out_pitch * rows;
+    g.in_frame_stride = rt.in_frame_stride;
+    g.out_frame_stride = rt.out_frame_stride;
     g.in_w = d->in_w;
     g.in_h = d->in_h;
     g.out_w = d->out_w;
     g.out_h = d->out_h;
     g.channels = d->channels;
     g.a = d->a;
-    g.in_row0 = in_row0;
-    g.in_rows = in_rows;
-    g.out_row0 = row0;
-    g.out_rows = rows;
-    g.skip_rows = has_prefix ? p->prefix.K : 0;
-    g.frames = frames;
+    g.in_row0 = rt.strip.in_row0;
+    g.in_rows = rt.strip.in_rows;
+    g.out_row0 = rt.strip.row0;
+    g.out_rows = rt.strip.rows;
+    g.skip_rows = rt.strip.row0 < p->prefix.K ? p->prefix.K : 0;
     g.hls_bp = d->mode == LANCZOS_MODE_HLS ? d->reserved[0] : 0;
     g.debug_skip = 0;
     g.stamps = nullptr;
@@ -723,206 +828,15 @@ static int resample_device_locked(lanczos_ctx* ctx, const lanczos_desc* d, const
         g.stamps = (unsigned long long*)ctx->stamp_buf;
     }
 #endif
-    if (d->mode == LANCZOS_MODE_HLS) {
-        if (ctx->force == LANCZOS_KERNEL_FAST || ctx->force == LANCZOS_KERNEL_GENERIC) return LANCZOS_ERR_UNSUPPORTED;
-        if (d->channels > 4 || 2 * d->a > 2 * lz::kMaxA) return LANCZOS_ERR_UNSUPPORTED;
-        if (frames > 65535) return LANCZOS_ERR_UNSUPPORTED;
-    }
-    bool prefix_fused = false;
-    bool use_fast = p->fast_ok && ctx->force != LANCZOS_KERNEL_GENERIC &&
-                    lz::fast_supports(*d, g);
-    const bool use_rat = !use_fast && p->rat.ok && ctx->force != LANCZOS_KERNEL_GENERIC && lz::rat_supports(*d, g);
-    if (ctx->force == LANCZOS_KERNEL_FAST && !use_fast && !use_rat) return LANCZOS_ERR_UNSUPPORTED;
-
-    // Events are reserved only once nothing but a HIP failure can stop the call; a triple is committed (ev_used += 3)
-    // after all three records succeeded, so timing_flush never meets an unrecorded event.
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-    if (ctx->timing) {
-        if (ctx->ev_used + 3 > 3 * 4096) {
-            rc = timing_flush(ctx);
-            if (rc != LANCZOS_OK) return rc;
-        }
-        while ((int)ctx->ev.size() < ctx->ev_used + 3) {
-            hipEvent_t e;
-            LZ_HIP(ctx, hipEventCreate(&e));
-            ctx->ev.push_back(e);
-        }
-        ctx->ev_prefix_first.resize(ctx->ev.size() / 3 + 1, 0);
-        ev0 = ctx->ev[ctx->ev_used];
-        ev1 = ctx->ev[ctx->ev_used + 1];
-        ev2 = ctx->ev[ctx->ev_used + 2];
-        LZ_HIP(ctx, hipEventRecord(ev0, stream));
-    }
-    if (d->mode == LANCZOS_MODE_HLS) {
-        const int tiles_x = (d->out_w + lz::kHlsTileW - 1) / lz::kHlsTileW;
-        const int tiles_y = (rows + lz::kHlsTileH - 1) / lz::kHlsTileH;
-        dim3 grid(tiles_x * tiles_y, frames);
-        if (d->bytes_per_sample == 1)
-            hipLaunchKernelGGL(lz::k_hls<uint8_t>, grid, dim3(lz::kHlsThreads), 0, stream, g, p->dev);
-        else
-            hipLaunchKernelGGL(lz::k_hls<uint16_t>, grid, dim3(lz::kHlsThreads), 0, stream, g, p->dev);
-        LZ_HIP(ctx, hipGetLastError());
-        ctx->last_kernel = LANCZOS_KERNEL_HLS;
-        route_launch(ctx, LANCZOS_ROUTE_MAIN_HLS, LANCZOS_ROUTE_PREFIX_NONE);
-        if (ev0) {  // one kernel: all of it is "main"
-            LZ_HIP(ctx, hipEventRecord(ev1, stream));
-            LZ_HIP(ctx, hipEventRecord(ev2, stream));
-            ctx->ev_prefix_first[ctx->ev_used / 3] = 0;
-            ctx->ev_used += 3;
-        }
-        return LANCZOS_OK;
-    }
-    bool prefix_front = false;  // the prefix rows went out on this stream in FRONT of the main kernel (register-only kernel)
-    int route_main = LANCZOS_ROUTE_MAIN_NONE;   // what lanczos_last_route reports: set where each launch is issued
-    if (use_fast) {
-        hipError_t e;
-        if (lz::env().tile_kernel || !lz::march_supports(g)) {  // LANCZOS_TILE_KERNEL=1: the tile-per-workgroup kernel (A/B measurements)
-            e = lz::fast_launch(*d, g, p->dev, p->fast, stream);
-            route_main = LANCZOS_ROUTE_MAIN_TILE;
-        } else {
-            lz::FrameGeom gm = g;
-            if (!in_split) {   // (with timing on, every sub-launch commits its own event triple: what is timed is what is shipped)
-                // A batch of twice the kernel's preferred size or more goes out as launches of that size (two chunks per (strip,
-                // frame) pair, rank-aware shares: the fastest shape this kernel has) followed by the rest.  The four-workgroups-per-CU
-                // instances already split at one and a half times that size: their one-workgroup-per-slot table degrades quickly
-                // (config 2, 48 frames: 400 us in one launch, 333 us as 32 + 16; 40 frames: 289 us either way), that of the
-                // two-workgroups-per-CU instances does not (config 3, 40 frames: 251 us in one launch, 272 us as 24 + 16) --
-                // profiles/round4y_ab_oversized_batch_split_rule.txt.
-                bool dummy = false;
-                e = lz::march_launch(*d, gm, p->dev, p->fast, stream, &dummy, &ctx->wg_tabs, /*query_only=*/true);
-                const int pf = ctx->wg_tabs.pref_frames;
-                const bool split = frames >= 2 * pf || (LZ_SPLIT_RULE && ctx->wg_tabs.wg_per_cu >= 4 && frames >= pf + pf / 2);
-                if (e == hipSuccess && pf >= 8 && split) {
-                    for (int f0 = 0; f0 < frames; f0 += pf) {
-                        const int nf = frames - f0 < pf ? frames - f0 : pf;
-                        rc = resample_device_locked(ctx, d, (const uint8_t*)d_in + (size_t)f0 * g.in_frame_stride,
-                                                    (uint8_t*)d_out + (size_t)f0 * g.out_frame_stride, nf, g.in_frame_stride,
-                                                    g.out_frame_stride, stream_v, /*in_split=*/true);
-                        if (rc != LANCZOS_OK) return rc;
-                    }
-                    return LANCZOS_OK;
-                }
-            }
-            if (has_prefix) {  // ask the marching launch to carry the prefix rows too (no separate k_prefix launch)
-                gm.prefix_K = p->prefix.K;
-                gm.prefix_M = p->prefix.M;
-                gm.prefix_M2 = p->prefix.M2;
-                e = lz::march_launch(*d, gm, p->dev, p->fast, stream, &prefix_fused, &ctx->wg_tabs, /*query_only=*/true);
-                if (e == hipSuccess && !prefix_fused) {
-                    // Large batch: the prefix rows do not ride (960 extra workgroups crowd the march: measured) -- the
-                    // register-only kernel goes out first, on the same stream
-                    gm.prefix_K = gm.prefix_M = gm.prefix_M2 = 0;
-                    if (!lz::env().separate_prefix && d->scale_d == 1 && d->in_h >= p->prefix.M2) {
-                        hipError_t pe = launch_prefix_front(d, g, p, stream);
-                        if (pe == hipSuccess) {
-                            prefix_front = true;
-                            if (ev1) LZ_HIP(ctx, hipEventRecord(ev1, stream));  // start..middle = the prefix kernel
-                        } else if (pe != hipErrorNotSupported) e = pe;
-                    }
-                }
-            } else {
-                e = hipSuccess;
-            }
-            if (e == hipSuccess) e = lz::march_launch(*d, gm, p->dev, p->fast, stream, &prefix_fused, &ctx->wg_tabs);
-            // (march_launch issues nothing for a strip that ends inside the prefix rows: its y_lo >= y_hi)
-            route_main = row0 + rows <= g.skip_rows ? LANCZOS_ROUTE_MAIN_NONE : LANCZOS_ROUTE_MAIN_MARCH;
-        }
-        if (e != hipSuccess) {
-            ctx->last_hip = (int)e;
-            return LANCZOS_ERR_HIP;
-        }
-        ctx->last_kernel = LANCZOS_KERNEL_FAST;
-    } else if (use_rat && p->ratp.ok && !lz::env().no_ratp) {
-        hipError_t e = lz::ratp_launch(*d, g, p->dev, p->ratp_dev, p->ratp_w_dev, stream);
-        if (e != hipSuccess) {
-            ctx->last_hip = (int)e;
-            return LANCZOS_ERR_HIP;
-        }
-        ctx->last_kernel = LANCZOS_KERNEL_FAST;
-        route_main = LANCZOS_ROUTE_MAIN_RATP;
-    } else if (use_rat) {
-        const int row_bytes = d->out_w * d->channels * d->bytes_per_sample;
-        const int tiles_x = (row_bytes + lz::kRatTileRowBytes - 1) / lz::kRatTileRowBytes;
-        const int tiles_y = (rows + lz::kRatTileH - 1) / lz::kRatTileH;
-        dim3 grid(tiles_x * tiles_y, frames);
-        const bool ex = d->mode == LANCZOS_MODE_EXACT;
-#define LZ_RAT(T, TAPS)                                                                                                  \
-    do {                                                                                                                 \
-        if (ex) hipLaunchKernelGGL((lz::k_rat<T, TAPS, true>), grid, dim3(lz::kRatThreads), 0, stream, g, p->dev, p->rat_dev);  \
-        else hipLaunchKernelGGL((lz::k_rat<T, TAPS, false>), grid, dim3(lz::kRatThreads), 0, stream, g, p->dev, p->rat_dev);    \
-    } while (0)
-        if (d->bytes_per_sample == 1) {
-            if (d->a == 2) LZ_RAT(uint8_t, 4);
-            else if (d->a == 3) LZ_RAT(uint8_t, 6);
-            else LZ_RAT(uint8_t, 8);
-        } else {
-            if (d->a == 2) LZ_RAT(uint16_t, 4);
-            else if (d->a == 3) LZ_RAT(uint16_t, 6);
-            else LZ_RAT(uint16_t, 8);
-        }
-#undef LZ_RAT
-        LZ_HIP(ctx, hipGetLastError());
-        ctx->last_kernel = LANCZOS_KERNEL_FAST;
-        route_main = LANCZOS_ROUTE_MAIN_RAT;
-    } else {
-        const int samples_w = d->out_w * d->channels;
-        const int tiles_x = (samples_w + lz::kGenTileW - 1) / lz::kGenTileW;
-        const int tiles_y = (rows + lz::kGenTileH - 1) / lz::kGenTileH;
-        dim3 grid(tiles_x * tiles_y, frames);
-        if (d->bytes_per_sample == 1)
-            hipLaunchKernelGGL(lz::k_generic<uint8_t>, grid, dim3(lz::kGenTileW), 0, stream, g, p->dev);
-        else
-            hipLaunchKernelGGL(lz::k_generic<uint16_t>, grid, dim3(lz::kGenTileW), 0, stream, g, p->dev);
-        LZ_HIP(ctx, hipGetLastError());
-        ctx->last_kernel = LANCZOS_KERNEL_GENERIC;
-        route_main = LANCZOS_ROUTE_MAIN_GENERIC;
-    }
-    int route_prefix = prefix_fused ? LANCZOS_ROUTE_PREFIX_RIDING : (prefix_front ? LANCZOS_ROUTE_PREFIX_FRONT : LANCZOS_ROUTE_PREFIX_NONE);
-    if (ev1 && !prefix_front) LZ_HIP(ctx, hipEventRecord(ev1, stream));  // start..middle = the main kernel
-
-    if (has_prefix && !prefix_fused && !prefix_front) {
-        const int samples_w = d->out_w * d->channels;
-        // columns per block: the row arrays (M + M2 rows) must fit 60 KB of LDS; deep prefixes (scales close to 1) get fewer
-        int bw = 128;
-        while (bw > 32 && (size_t)(p->prefix.M + p->prefix.M2) * bw * d->bytes_per_sample > 60 * 1024) bw >>= 1;
-        const bool streamed = (size_t)(p->prefix.M + p->prefix.M2) * bw * d->bytes_per_sample > 60 * 1024;
-        if (streamed) bw = 128;   // deep prefix (S = 1: the whole frame; S -> 1): rings of 24 rows instead of M + M2 row arrays
-        dim3 grid((samples_w + bw - 1) / bw, frames);
-#define LZ_PREFIX_STREAM(T, TAPS) \
-    hipLaunchKernelGGL((lz::k_prefix_stream<T, TAPS>), grid, dim3(128), 0, stream, g, p->dev, p->prefix.K, p->prefix.M)
-        route_prefix = streamed ? LANCZOS_ROUTE_PREFIX_STREAMED : LANCZOS_ROUTE_PREFIX_BEHIND;
-        if (streamed) {
-            if (d->bytes_per_sample == 1) {
-                if (d->a == 2) LZ_PREFIX_STREAM(uint8_t, 4);
-                else if (d->a == 3) LZ_PREFIX_STREAM(uint8_t, 6);
-                else LZ_PREFIX_STREAM(uint8_t, 8);
-            } else {
-                if (d->a == 2) LZ_PREFIX_STREAM(uint16_t, 4);
-                else if (d->a == 3) LZ_PREFIX_STREAM(uint16_t, 6);
-                else LZ_PREFIX_STREAM(uint16_t, 8);
-            }
-        } else
-#define LZ_PREFIX(T, TAPS)                                                                                       \
-    hipLaunchKernelGGL((lz::k_prefix<T, TAPS>), grid, dim3(bw), (size_t)(p->prefix.M + p->prefix.M2) * bw * sizeof(T), stream, g, \
-                       p->dev, p->prefix.K, p->prefix.M, p->prefix.M2)
-        if (d->bytes_per_sample == 1) {
-            if (d->a == 2) LZ_PREFIX(uint8_t, 4);
-            else if (d->a == 3) LZ_PREFIX(uint8_t, 6);
-            else LZ_PREFIX(uint8_t, 8);
-        } else {
-            if (d->a == 2) LZ_PREFIX(uint16_t, 4);
-            else if (d->a == 3) LZ_PREFIX(uint16_t, 6);
-            else LZ_PREFIX(uint16_t, 8);
-        }
-#undef LZ_PREFIX
-#undef LZ_PREFIX_STREAM
-        LZ_HIP(ctx, hipGetLastError());
-    }
-    route_launch(ctx, route_main, route_prefix);
-    if (ev2) {
-        LZ_HIP(ctx, hipEventRecord(ev2, stream));
-        ctx->ev_prefix_first[ctx->ev_used / 3] = prefix_front ? 1 : 0;
-        ctx->ev_used += 3;
+    // (with timing on, every launch of a split batch commits its own event triple: what is timed is what is shipped)
+    for (int i = 0, f0 = 0; i < rt.n_launches; i++) {
+        const lz::UpLaunch launch = rt.launch(i);
+        g.in = (const uint8_t*)d_in + (size_t)f0 * g.in_frame_stride;
+        g.out = (uint8_t*)d_out + (size_t)f0 * g.out_frame_stride;
+        g.frames = launch.frames;
+        const int lrc = issue_launch(ctx, d, p, rt, launch, facts, g, stream);
+        if (lrc != LANCZOS_OK) return lrc;
+        f0 += launch.frames;
     }
     return LANCZOS_OK;
 }
@@ -965,26 +879,11 @@ int lanczos_resample_host(lanczos_ctx* ctx, const lanczos_desc* d, const void* i
     Plan* p = nullptr;
     rc = get_plan(ctx, d, ctx->stream, &p);   // (the pipeline's resample calls run on the context's stream)
     if (rc != LANCZOS_OK) return rc;
-    int row0, rows, in_row0, in_rows;
-    whole_or_strip(d, &row0, &rows);
-    strip_input_rows(p->V, d->a, d->in_h, row0, rows, p->prefix, &in_row0, &in_rows);
-    const size_t in_frame = (size_t)d->in_w * d->channels * d->bytes_per_sample * in_rows;
-    const size_t out_frame = (size_t)d->out_w * d->channels * d->bytes_per_sample * rows;
-    const size_t in_bytes = in_frame * frames, out_bytes = out_frame * frames;
-    if (ctx->stage_in_bytes < in_bytes) {
-        if (ctx->stage_in) (void)hipFree(ctx->stage_in);
-        ctx->stage_in = nullptr;
-        ctx->stage_in_bytes = 0;
-        LZ_HIP(ctx, hipMalloc(&ctx->stage_in, in_bytes));
-        ctx->stage_in_bytes = in_bytes;
-    }
-    if (ctx->stage_out_bytes < out_bytes) {
-        if (ctx->stage_out) (void)hipFree(ctx->stage_out);
-        ctx->stage_out = nullptr;
-        ctx->stage_out_bytes = 0;
-        LZ_HIP(ctx, hipMalloc(&ctx->stage_out, out_bytes));
-        ctx->stage_out_bytes = out_bytes;
-    }
+    const lz::UpStrip strip = lz::up_strip(*d, p->V.first.data(), p->prefix);
+    const size_t in_frame = (size_t)d->in_w * d->channels * d->bytes_per_sample * strip.in_rows;
+    const size_t out_frame = (size_t)d->out_w * d->channels * d->bytes_per_sample * strip.rows;
+    if ((rc = grow_block(ctx, &ctx->stage_in, &ctx->stage_in_bytes, in_frame * frames)) != LANCZOS_OK) return rc;
+    if ((rc = grow_block(ctx, &ctx->stage_out, &ctx->stage_out_bytes, out_frame * frames)) != LANCZOS_OK) return rc;
     if (!ctx->copy_in) LZ_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_in, hipStreamNonBlocking));
     if (!ctx->copy_out) LZ_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_out, hipStreamNonBlocking));
     // groups of at most 4 frames, at most 64 groups in flight per call
@@ -1078,20 +977,8 @@ int lanczos_resample_planar_device(lanczos_ctx* ctx, const lanczos_desc* d, cons
     std::lock_guard<std::mutex> lock(ctx->mu);
     LZ_HIP(ctx, hipSetDevice(ctx->device));
     route_begin(ctx);
-    if (ctx->planar_in_bytes < in_bytes) {
-        if (ctx->planar_in) (void)hipFree(ctx->planar_in);
-        ctx->planar_in = nullptr;
-        ctx->planar_in_bytes = 0;
-        LZ_HIP(ctx, hipMalloc(&ctx->planar_in, in_bytes));
-        ctx->planar_in_bytes = in_bytes;
-    }
-    if (ctx->planar_out_bytes < out_bytes) {
-        if (ctx->planar_out) (void)hipFree(ctx->planar_out);
-        ctx->planar_out = nullptr;
-        ctx->planar_out_bytes = 0;
-        LZ_HIP(ctx, hipMalloc(&ctx->planar_out, out_bytes));
-        ctx->planar_out_bytes = out_bytes;
-    }
+    if ((rc = grow_block(ctx, &ctx->planar_in, &ctx->planar_in_bytes, in_bytes)) != LANCZOS_OK) return rc;
+    if ((rc = grow_block(ctx, &ctx->planar_out, &ctx->planar_out_bytes, out_bytes)) != LANCZOS_OK) return rc;
     LZ_HIP(ctx, lz::layout_launch(true, d_in_planar, ctx->planar_in, d->in_w, d->in_h, d->channels, d->bytes_per_sample, frames,
                                   (hipStream_t)stream));
     lanczos_desc whole = *d;

@@ -151,17 +151,7 @@ struct WgTabCacheT {
         note_stream(it->streams, stream);
         return hipSuccess;
     }
-    // set by every march_launch (query or launch): the batch size this kernel instance runs best at for this frame width -- the
-    // largest one whose (strip, frame) pairs, cut in two chunks each, fill ONE resident round of workgroups with rank-aware
-    // shares (config 2: 32 frames = 960 workgroups on 1 024 slots).  Larger batches are faster as several launches of this size
-    // (64 frames: 2 x 207 us against 502 us in one launch, profiles/round3g_bench_default.json); 0: no preference
-    int pref_frames = 0;
-    // the largest batch that still is ONE resident round of two chunks per (strip, frame) pair (config 2: 34 frames): beyond it a
-    // single launch falls back to one workgroup per slot with shares across pairs (48 frames: 399 us) and is slower than a launch of
-    // pref_frames followed by the rest (32 + 16 frames: 207 + 113 us)
-    int max_one_round_frames = 0;
-    int wg_per_cu = 0;   // resident marching workgroups per CU of the instance the last query was about
-    // lanczos_last_march_table: the shape of the last k_march launch (march_launch_t notes it where it launches, the entry points
+    // lanczos_last_march_table: the shape of the last k_march launch (march_issue_t notes it where it launches, the entry points
     // clear it when a call begins).  A key, not a pointer: items move on every insert.
     long long last_key[8] = {};
     bool last_valid = false;

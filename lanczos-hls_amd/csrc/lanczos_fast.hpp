@@ -28,6 +28,7 @@
 
 #include "lanczos_kernels_common.hpp"
 #include "lanczos_taps.hpp"
+#include "lanczos_upscale.hpp"
 
 namespace lz {
 
@@ -641,33 +642,7 @@ inline hipError_t fast_launch_t(const lanczos_desc& d, const FrameGeom& g, const
     return hipGetLastError();
 }
 
-// The instantiated configurations: (sample type, channels, scale, a) -- every integer scale 2..4 of the reference's params.h
-// space (lanczos.h:9-31: NUM_CHANNELS 1 / 3 / 4, LANCZOS_A 2..4) for 8-bit samples, scales 2 and 3 with a = 3, 4 for 16-bit ones.
-// Four groups = four translation units (csrc/lanczos_inst.hip compiled with -DLZ_INST_GROUP=0..3, in parallel).
-#define LZ_FAST_CONFIGS_G0(X) /* 8-bit, 2x */ \
-    X(uint8_t, 3, 2, 3) X(uint8_t, 3, 2, 2) X(uint8_t, 3, 2, 4) X(uint8_t, 4, 2, 2) X(uint8_t, 4, 2, 3) X(uint8_t, 4, 2, 4) \
-    X(uint8_t, 1, 2, 2) X(uint8_t, 1, 2, 3) X(uint8_t, 1, 2, 4)
-#define LZ_FAST_CONFIGS_G1(X) /* 8-bit, 3x */ \
-    X(uint8_t, 3, 3, 3) X(uint8_t, 3, 3, 2) X(uint8_t, 3, 3, 4) X(uint8_t, 4, 3, 2) X(uint8_t, 4, 3, 3) X(uint8_t, 4, 3, 4) \
-    X(uint8_t, 1, 3, 2) X(uint8_t, 1, 3, 3) X(uint8_t, 1, 3, 4)
-#define LZ_FAST_CONFIGS_G2(X) /* 8-bit, 4x */ \
-    X(uint8_t, 3, 4, 3) X(uint8_t, 3, 4, 2) X(uint8_t, 3, 4, 4) X(uint8_t, 4, 4, 2) X(uint8_t, 4, 4, 3) X(uint8_t, 4, 4, 4) \
-    X(uint8_t, 1, 4, 2) X(uint8_t, 1, 4, 3) X(uint8_t, 1, 4, 4)
-#define LZ_FAST_CONFIGS_G3(X) /* 16-bit */ \
-    X(uint16_t, 4, 2, 4) X(uint16_t, 3, 2, 3) X(uint16_t, 4, 2, 3) X(uint16_t, 3, 2, 4) \
-    X(uint16_t, 3, 3, 3) X(uint16_t, 3, 3, 4) X(uint16_t, 4, 3, 3) X(uint16_t, 4, 3, 4)
-#define LZ_FAST_CONFIGS(X) LZ_FAST_CONFIGS_G0(X) LZ_FAST_CONFIGS_G1(X) LZ_FAST_CONFIGS_G2(X) LZ_FAST_CONFIGS_G3(X)
-
-inline bool fast_supports(const lanczos_desc& d, const FrameGeom& g) {
-    if (d.scale_d != 1) return false;
-    if (g.out_pitch % 4 != 0 || (((uintptr_t)g.out) & 3) != 0 || (g.out_frame_stride & 3) != 0) return false;
-    if ((size_t)g.out_pitch * g.out_rows >= (1ull << 31) || (size_t)g.in_pitch >= (1ull << 30)) return false;
-#define X(T, C, S, A) \
-    if (d.bytes_per_sample == (int)sizeof(T) && d.channels == C && d.scale_n == S && d.a == A) return true;
-    LZ_FAST_CONFIGS(X)
-#undef X
-    return false;
-}
+// (the instantiated configurations LZ_FAST_CONFIGS_G0..3 and fast_supports: lanczos_upscale.hpp)
 
 // one dispatcher per group, defined in lanczos_inst.hip (hipErrorNotSupported: not one of the group's configurations)
 #define LZ_DECLARE_FAST_GROUP(G)                                                                                         \

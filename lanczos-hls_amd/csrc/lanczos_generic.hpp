@@ -15,6 +15,7 @@
 #pragma once
 #include "lanczos_kernels_common.hpp"
 #include "lanczos_taps.hpp"
+#include "lanczos_upscale.hpp"
 
 namespace lz {
 
@@ -249,25 +250,7 @@ __global__ __launch_bounds__(128) void k_prefix_stream(FrameGeom g, TapTables t,
 // and < 80 VGPRs these workgroups fit on a CU BESIDE four resident marching workgroups (which own all 160 KiB of LDS), so
 // launched on a second stream just before the marching kernel they run inside its first microseconds instead of as a
 // serial 8.5 us kernel + 2.5 us gap behind it (profiles/README.md, round 2).
-constexpr int prefix_last_tap(int o, int S, int A) { return o / S + A; }
-constexpr int prefix_K(int S, int A) {
-    int k = 0;
-    for (int o = 0; o < 4 * A * S + 8; o++)
-        if (prefix_last_tap(o, S, A) > o) k = o + 1;
-    return k;
-}
-constexpr int prefix_M(int S, int A) {
-    int m = prefix_K(S, A);
-    for (int o = 0; o < prefix_K(S, A); o++)
-        if (prefix_last_tap(o, S, A) + 1 > m) m = prefix_last_tap(o, S, A) + 1;
-    return m;
-}
-constexpr int prefix_M2(int S, int A) {
-    int m2 = 0;
-    for (int o = 0; o < prefix_M(S, A); o++)
-        if (prefix_last_tap(o, S, A) + 1 > m2) m2 = prefix_last_tap(o, S, A) + 1;
-    return m2;
-}
+// (prefix_K / prefix_M / prefix_M2 of (S, A) and the instance list LZ_PREFIX_REG_CONFIGS: lanczos_upscale.hpp)
 
 template <typename T, int S, int A>
 __global__ __launch_bounds__(128) void k_prefix_reg(FrameGeom g, TapTables t) {

@@ -1,5 +1,5 @@
 // lanczos_inst.hip -- one group of instantiated configurations of the integer-scale kernels (k_march, k_fast).
-// Compiled once per group (-DLZ_INST_GROUP=0..3, see lanczos_fast.hpp: LZ_FAST_CONFIGS_G*) so that the 35 configurations of
+// Compiled once per group (-DLZ_INST_GROUP=0..3, see lanczos_upscale.hpp: LZ_FAST_CONFIGS_G*) so that the 35 configurations of
 // the reference's params.h space (lanczos.h:9-31) build in parallel translation units instead of one ten-minute one.
 #include <hip/hip_runtime.h>
 
@@ -15,11 +15,20 @@
 
 namespace lz {
 
-hipError_t LZ_CAT(march_launch_g, LZ_INST_GROUP)(const lanczos_desc& d, const FrameGeom& g, const TapTables& t, const FastConsts& fc,
-                                                 hipStream_t stream, bool* prefix_fused, WgTabCache* cache, bool query_only) {
+hipError_t LZ_CAT(march_facts_g, LZ_INST_GROUP)(const lanczos_desc& d, MarchFacts* out) {
 #define X(T, C, S, A)                                                                               \
     if (d.bytes_per_sample == (int)sizeof(T) && d.channels == C && d.scale_n == S && d.a == A)      \
-        return march_launch_t<T, C, S, A>(d, g, t, fc, stream, prefix_fused, query_only, cache);
+        return march_facts_t<T, C, S, A>(d, out);
+    LZ_GROUP_CONFIGS(X)
+#undef X
+    return hipErrorNotSupported;
+}
+
+hipError_t LZ_CAT(march_issue_g, LZ_INST_GROUP)(const lanczos_desc& d, const FrameGeom& g, const TapTables& t, const FastConsts& fc,
+                                                hipStream_t stream, bool riding, const MarchFacts& facts, WgTabCache* cache) {
+#define X(T, C, S, A)                                                                               \
+    if (d.bytes_per_sample == (int)sizeof(T) && d.channels == C && d.scale_n == S && d.a == A)      \
+        return march_issue_t<T, C, S, A>(d, g, t, fc, stream, riding, facts, cache);
     LZ_GROUP_CONFIGS(X)
 #undef X
     return hipErrorNotSupported;

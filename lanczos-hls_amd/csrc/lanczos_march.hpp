@@ -189,7 +189,7 @@ struct MarchCfg {
 #ifndef LZ_MARCH_AUTO_MIN_WAVES   // A/B builds only (1): EVERY instance is told to leave room for the workgroups its LDS footprint allows
 #define LZ_MARCH_AUTO_MIN_WAVES 0
 #endif
-    // waves per SIMD that nb resident workgroups need (uneven landing: see march_launch_t), and the largest nb the LDS allows
+    // waves per SIMD that nb resident workgroups need (uneven landing: see march_facts_t), and the largest nb the LDS allows
     // whose need the register files can meet at all (8 waves per SIMD; 7 under the 96-SGPR cap, 6 without it)
     static constexpr int need_waves(int nb) { return NWAVES % 4 == 0 ? nb * NWAVES / 4 : (nb * NWAVES + 3) / 4 + 1; }
     static constexpr int auto_min_waves() {
@@ -1175,11 +1175,7 @@ inline void march_kernel_launch(dim3 grid, dim3 block, size_t lds, hipStream_t s
     else hipLaunchKernelGGL((k_march<T, C, S, A, EXACT, STAMP, RIDE>), grid, block, lds, stream, g, t, fc);
 }
 
-// the marching kernel moves whole 16-byte chunks: rows, frames and the base must be 16-byte multiples
-inline bool march_supports(const FrameGeom& g) {
-    return g.in_pitch % 16 == 0 && (((uintptr_t)g.in) & 15) == 0 && (g.in_frame_stride & 15) == 0 &&
-           (size_t)g.in_pitch * g.in_rows < (1ull << 30);  // (the hoisted load offsets' out-of-range markers need the two top bits)
-}
+// (march_supports: lanczos_upscale.hpp)
 
 // Chunk height: ONE resident round of workgroups.  With more workgroups than the chip holds at once the second
 // round runs part-empty and the launch takes two wave lifetimes; so the (strip, frame) pairs are cut into
@@ -1430,30 +1426,20 @@ inline int march_build_table(std::vector<WgEntry>& tab, int* segs_out, int strip
 // retire lists and the table cache: lanczos_cache.hpp (host-only, tested without a GPU)
 using WgTabCache = WgTabCacheT<WgEntry>;
 
+// What up_route (lanczos_upscale.hpp) needs to know of this instance on the current device: its workgroup size, LDS and strip
+// width, the workgroups a CU holds at once and the CU count.  Measured once per (instance, exact, device); the dynamic LDS size
+// of the kernels is set on the way.
 template <typename T, int C, int S, int A>
-inline hipError_t march_launch_t(const lanczos_desc& d, const FrameGeom& g_in, const TapTables& t,
-                                 const FastConsts& fc, hipStream_t stream, bool* prefix_fused, bool query_only, WgTabCache* cache) {
+inline hipError_t march_facts_t(const lanczos_desc& d, MarchFacts* out) {
     using K = MarchCfg<T, C, S, A>;
     using F = typename K::F;
-    FrameGeom g = g_in;
-    // g.prefix_K > 0 asks for the in-place prefix rows to ride on this launch (extra workgroups behind the marching
-    // ones); that needs a main launch at all and the row arrays to fit the workgroup's LDS -- otherwise the caller
-    // launches k_prefix
-    if (g.prefix_K > 0 &&
-        (env().separate_prefix || (size_t)(g.prefix_M + g.prefix_M2) * K::NT * sizeof(T) > (size_t)K::LDS_BYTES ||
-         g.out_row0 + g.out_rows <= (g.out_row0 > g.skip_rows ? g.out_row0 : g.skip_rows)))
-        g.prefix_K = g.prefix_M = g.prefix_M2 = 0;
-    *prefix_fused = g.prefix_K > 0;
-    const int strips = (g.out_w + F::TWP_OUT - 1) / F::TWP_OUT;
-    const int y_lo = g.out_row0 > g.skip_rows ? g.out_row0 : g.skip_rows;
-    const int y_hi = g.out_row0 + g.out_rows;
     const bool exact = d.mode == LANCZOS_MODE_EXACT;
     int dev = 0;
     (void)hipGetDevice(&dev);
     dev &= 63;
     int nb = 1, cus = 256;
-    {   // process-wide facts about this kernel instance on this device.  The lock covers only these arrays: the table cache below
-        // belongs to the context, whose calls are serialised by its own mutex.
+    {   // process-wide facts about this kernel instance on this device.  The lock covers only these arrays: the table cache of
+        // march_issue_t belongs to the context, whose calls are serialised by its own mutex.
         std::lock_guard<std::mutex> cache_lock(launch_cache_mutex());
         static int slots[2][64] = {};
         static int cus_of[64] = {};
@@ -1507,23 +1493,29 @@ inline hipError_t march_launch_t(const lanczos_desc& d, const FrameGeom& g_in, c
         cus = cus_of[dev];
         nb = slots[exact][dev] / cus > 0 ? slots[exact][dev] / cus : 1;
     }
-    {
-        int pf = (nb * cus) / (2 * strips);
-        cache->max_one_round_frames = pf;
-        cache->wg_per_cu = nb;
-        while (pf > 0 && (2 * strips * pf) % 16 != 0) pf--;   // every XCD gets whole pairs of chunks (march_build_table: balanced)
-        cache->pref_frames = pf;
-    }
-    // Measured (config 2, ms per step riding / separate): 1 frame 0.0198 / 0.0253, 2: 0.0281 / 0.0335, 4: 0.0464 / 0.0525,
-    // 8: 0.0687 / 0.0729, 16: 0.117-0.120 / 0.114-0.116, 32: 0.232 / 0.218 -- past about one prefix workgroup per CU they slow
-    // the march down more than the launch they replace (profiles/round3a_ab_prefix_riding_and_ldsdma_placement.txt).
-    g.prefix_blocks_per_frame = g.prefix_K > 0 ? (g.out_w * C + K::NT - 1) / K::NT : 0;
-    if (g.prefix_blocks_per_frame * g.frames > cus) {
-        g.prefix_K = g.prefix_M = g.prefix_M2 = g.prefix_blocks_per_frame = 0;
-        *prefix_fused = false;
-    }
-    // a pure query (the caller wants *prefix_fused and pref_frames) touches neither the table cache nor the stream
-    if (query_only || y_lo >= y_hi) return hipSuccess;
+    *out = MarchFacts{K::NT, K::LDS_BYTES, F::TWP_OUT, nb, cus};
+    return hipSuccess;
+}
+
+// Builds or finds the workgroup table of the launch and issues it.  It decides nothing: `riding` (up_route's) says whether the
+// in-place prefix rows ride on this launch as extra workgroups behind the marching ones, with g.prefix_K / _M / _M2 set (zero
+// otherwise); `facts` are march_facts_t's.  Nothing is issued for a strip that ends inside the prefix rows.
+template <typename T, int C, int S, int A>
+inline hipError_t march_issue_t(const lanczos_desc& d, const FrameGeom& g_in, const TapTables& t, const FastConsts& fc,
+                                hipStream_t stream, bool riding, const MarchFacts& facts, WgTabCache* cache) {
+    using K = MarchCfg<T, C, S, A>;
+    using F = typename K::F;
+    FrameGeom g = g_in;
+    const int strips = (g.out_w + F::TWP_OUT - 1) / F::TWP_OUT;
+    const int y_lo = g.out_row0 > g.skip_rows ? g.out_row0 : g.skip_rows;
+    const int y_hi = g.out_row0 + g.out_rows;
+    if (y_lo >= y_hi) return hipSuccess;
+    const bool exact = d.mode == LANCZOS_MODE_EXACT;
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    dev &= 63;
+    const int nb = facts.wg_per_cu, cus = facts.cus;
+    g.prefix_blocks_per_frame = riding ? (g.out_w * C + K::NT - 1) / K::NT : 0;
     // the workgroup table of this launch shape (built once per context and shape)
     const int m_lo = y_lo / S, m_hi = (y_hi - 1) / S + 1;
     const long long key[8] = {(long long)sizeof(T) | ((long long)C << 8) | ((long long)S << 16) | ((long long)A << 24) | ((long long)exact << 32),
@@ -1551,7 +1543,7 @@ inline hipError_t march_launch_t(const lanczos_desc& d, const FrameGeom& g_in, c
     g.wg_per_frame = 0;
     g.n_main = item->n;
     dim3 grid(g.n_main + g.prefix_blocks_per_frame * g.frames);
-    if (*prefix_fused) {
+    if (riding) {
         if (exact) march_kernel_launch<T, C, S, A, true, false, true>(grid, dim3(K::NT), K::LDS_BYTES, stream, g, t, fc);
         else march_kernel_launch<T, C, S, A, false, false, true>(grid, dim3(K::NT), K::LDS_BYTES, stream, g, t, fc);
         return hipGetLastError();
@@ -1568,22 +1560,33 @@ inline hipError_t march_launch_t(const lanczos_desc& d, const FrameGeom& g_in, c
     return hipGetLastError();
 }
 
-#define LZ_DECLARE_MARCH_GROUP(G)                                                                                                  \
-    hipError_t march_launch_g##G(const lanczos_desc& d, const FrameGeom& g, const TapTables& t, const FastConsts& fc, hipStream_t stream, \
-                                 bool* prefix_fused, WgTabCache* cache, bool query_only);
+// one pair of dispatchers per group, defined in lanczos_inst.hip (hipErrorNotSupported: not one of the group's configurations)
+#define LZ_DECLARE_MARCH_GROUP(G)                                                                                                    \
+    hipError_t march_facts_g##G(const lanczos_desc& d, MarchFacts* out);                                                             \
+    hipError_t march_issue_g##G(const lanczos_desc& d, const FrameGeom& g, const TapTables& t, const FastConsts& fc, hipStream_t stream, \
+                                bool riding, const MarchFacts& facts, WgTabCache* cache);
 LZ_DECLARE_MARCH_GROUP(0)
 LZ_DECLARE_MARCH_GROUP(1)
 LZ_DECLARE_MARCH_GROUP(2)
 LZ_DECLARE_MARCH_GROUP(3)
 #undef LZ_DECLARE_MARCH_GROUP
 
-inline hipError_t march_launch(const lanczos_desc& d, const FrameGeom& g, const TapTables& t, const FastConsts& fc,
-                               hipStream_t stream, bool* prefix_fused, WgTabCache* cache, bool query_only = false) {
-    *prefix_fused = false;
-    if (d.bytes_per_sample == 2) return march_launch_g3(d, g, t, fc, stream, prefix_fused, cache, query_only);
-    if (d.scale_n == 2) return march_launch_g0(d, g, t, fc, stream, prefix_fused, cache, query_only);
-    if (d.scale_n == 3) return march_launch_g1(d, g, t, fc, stream, prefix_fused, cache, query_only);
-    if (d.scale_n == 4) return march_launch_g2(d, g, t, fc, stream, prefix_fused, cache, query_only);
+// hipErrorNotSupported: the descriptor has no marching instance
+inline hipError_t march_facts(const lanczos_desc& d, MarchFacts* out) {
+    if (d.scale_d != 1) return hipErrorNotSupported;
+    if (d.bytes_per_sample == 2) return march_facts_g3(d, out);
+    if (d.scale_n == 2) return march_facts_g0(d, out);
+    if (d.scale_n == 3) return march_facts_g1(d, out);
+    if (d.scale_n == 4) return march_facts_g2(d, out);
+    return hipErrorNotSupported;
+}
+
+inline hipError_t march_issue(const lanczos_desc& d, const FrameGeom& g, const TapTables& t, const FastConsts& fc,
+                              hipStream_t stream, bool riding, const MarchFacts& facts, WgTabCache* cache) {
+    if (d.bytes_per_sample == 2) return march_issue_g3(d, g, t, fc, stream, riding, facts, cache);
+    if (d.scale_n == 2) return march_issue_g0(d, g, t, fc, stream, riding, facts, cache);
+    if (d.scale_n == 3) return march_issue_g1(d, g, t, fc, stream, riding, facts, cache);
+    if (d.scale_n == 4) return march_issue_g2(d, g, t, fc, stream, riding, facts, cache);
     return hipErrorNotSupported;
 }
 

@@ -293,15 +293,7 @@ inline void rat_prepare(const lanczos_desc& d, const AxisTaps& H, const AxisTaps
     r->ok = true;
 }
 
-inline bool rat_supports(const lanczos_desc& d, const FrameGeom& g) {
-    if (d.scale_d == 1) return false;                       // integer scales: the marching / tile kernels
-    if (d.scale_n >= 2 * d.scale_d + d.scale_d) {}          // (any ratio > 1 is fine)
-    if (g.out_pitch % 4 != 0 || (((uintptr_t)g.out) & 3) != 0 || (g.out_frame_stride & 3) != 0) return false;
-    // tile window bounds assume scale > 1: input span of a tile <= its output span + 2a
-    return d.scale_n > d.scale_d && g.frames <= 65535;
-}
-
-
+// (rat_supports: lanczos_upscale.hpp)
 
 // ======================================================================================================================
 // k_ratp -- the same job for the rational scales that are exactly PERIODIC in this frame: the host has checked, index by

@@ -80,8 +80,9 @@ def inst_id(i):
 
 
 def header_text():
-    with open(HEADER) as f:
-        return f.read()
+    """lanczos_upscale.hpp (the instance lists LZ_FAST_CONFIGS_G0..G3) followed by lanczos_fast.hpp (the shapes)"""
+    with open(os.path.join(os.path.dirname(HEADER), "lanczos_upscale.hpp")) as f, open(HEADER) as g:
+        return f.read() + g.read()
 
 
 def header_instances(text=None):
@@ -90,7 +91,7 @@ def header_instances(text=None):
     out = []
     for g in range(4):
         m = re.search(r"#define LZ_FAST_CONFIGS_G%d\(X\)[^\n]*\\\n((?:[^\n]*\\\n)*[^\n]*)\n" % g, text)
-        assert m, "LZ_FAST_CONFIGS_G%d not found in lanczos_fast.hpp" % g
+        assert m, "LZ_FAST_CONFIGS_G%d not found in lanczos_upscale.hpp" % g
         found = re.findall(r"X\((\w+),\s*(\d+),\s*(\d+),\s*(\d+)\)", m.group(1))
         assert found, "LZ_FAST_CONFIGS_G%d has no entries" % g
         out += [({"uint8_t": 1, "uint16_t": 2}[t], int(c), int(s), int(a)) for t, c, s, a in found]

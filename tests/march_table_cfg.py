@@ -8,7 +8,7 @@ list.  tests/test_march_table_cfg.py proves without a GPU (on the host-built tab
 nb; tests/test_march_table_gpu.py takes the first candidate that serves the device.
 
 Everything about the table is restated here from the library's sources, not read from them: strips(), rows(), single_launch()
-(the split rule of lanczos_api.hip: resample_device_locked), partition_errors() and the goal predicates.
+(the split rule of lanczos_upscale_route.cpp: up_route), partition_errors() and the goal predicates.
 """
 import collections
 
@@ -51,7 +51,7 @@ def prefix_rows(s, a):
 
 
 def rows(inst, in_h, out_row0=0, out_rows=0):
-    """[m_lo, m_hi) of a launch (march_launch_t): the input rows m = y // s of the output rows k_march stores, which start behind
+    """[m_lo, m_hi) of a launch (march_issue_t): the input rows m = y // s of the output rows k_march stores, which start behind
     the in-place prefix rows [0, K)."""
     bps, c, s, a = inst
     y_lo = max(out_row0, prefix_rows(s, a) if out_row0 < prefix_rows(s, a) else 0)
@@ -67,7 +67,7 @@ def preferred_frames(nb, cus, n_strips):
 
 
 def single_launch(nb, cus, n_strips, frames):
-    """resample_device_locked's split rule: a batch of twice the preferred size pf goes out as launches of pf frames, one of one
+    """up_route's split rule (csrc/lanczos_upscale_route.cpp): a batch of twice the preferred size pf goes out as launches of pf frames, one of one
     and a half times pf already where four workgroups are resident per CU; batches are split only where pf >= 8."""
     pf = preferred_frames(nb, cus, n_strips)
     return not (pf >= 8 and (frames >= 2 * pf or (nb >= 4 and frames >= pf + pf // 2)))

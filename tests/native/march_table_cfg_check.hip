@@ -14,7 +14,7 @@ template <typename T, int C, int S, int A>
 static int emit(int line, int in_w, int m_lo, int m_hi, int frames, int nb, int cus) {
     using K = MarchCfg<T, C, S, A>;
     const int twp_out = K::F::TWP_OUT;
-    const int strips = (in_w * S + twp_out - 1) / twp_out;   // march_launch_t
+    const int strips = (in_w * S + twp_out - 1) / twp_out;   // march_issue_t
     std::vector<WgEntry> tab;
     int segs = 0;
     bool balanced = false, mode_a = false;

@@ -29,6 +29,7 @@ import lanczos_hls_amd as L
 import oracle_lib as O
 import patterns as P
 from test_parity_gpu import _cmp
+from upscale_route_cfg import _prefix_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -37,24 +38,13 @@ NONE, RIDING, FRONT, BEHIND, STREAMED = (L.ROUTE_PREFIX_NONE, L.ROUTE_PREFIX_RID
                                          L.ROUTE_PREFIX_STREAMED)
 MODES = (L.MODE_EXACT, L.MODE_LSB1)
 
-# the 13 instances of k_prefix_reg (lanczos_api.hip LZ_PREFIX_REG_CONFIGS) with the channel counts the integer-scale kernels have
+# the 13 instances of k_prefix_reg (lanczos_upscale.hpp LZ_PREFIX_REG_CONFIGS) with the channel counts the integer-scale kernels have
 INSTANCES = [(np.uint8, s, a) for s in (2, 3, 4) for a in (2, 3, 4)] + [(np.uint16, s, a) for s in (2, 3) for a in (3, 4)]
 _IDS = [f"{np.dtype(dt).name}-{s}x-a{a}" for (dt, s, a) in INSTANCES]
 
 
 def _channels(dt):
     return (1, 3, 4) if dt == np.uint8 else (3, 4)
-
-
-def _prefix_rows(s, a):
-    """K, M, M2 of an integer scale on a frame tall enough that no tap is clipped (csrc/lanczos_generic.hpp prefix_K / _M / _M2
-    restated): output row o reads rows up to o // s + a; K = rows that read a row below themselves, M = output rows the
-    recurrence holds, M2 = H-pass rows it reads -- the smallest input height the front kernel admits."""
-    last = lambda o: o // s + a
-    K = max(o + 1 for o in range(4 * a * s + 8) if last(o) > o)
-    M = max([K] + [last(o) + 1 for o in range(K)])
-    M2 = max(last(o) + 1 for o in range(M))
-    return K, M, M2
 
 
 def _width(c, bps, s, marching, block_multiple=None, near=160):
