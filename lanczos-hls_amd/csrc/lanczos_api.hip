@@ -34,21 +34,12 @@ namespace {
 
 struct PlanKey {
     int in_w, in_h, out_w, out_h, channels, bps, sn, sd, a, hls;
-    bool operator<(const PlanKey& o) const { return memcmp(this, &o, sizeof(PlanKey)) < 0; }
 };
 
 struct Plan {
-    PlanKey key;
-    std::vector<hipStream_t> streams;  // streams this plan's tables were used on (retirement)
     lz::AxisTaps H, V;
     lz::PrefixInfo prefix;
-    lz::TapTables dev{};       // device copies
-    void* dev_block = nullptr;  // one allocation behind `dev`
-    void* host_block = nullptr; // page-locked source of the asynchronous upload (alive as long as the plan: a captured graph replays the copy)
-    hipEvent_t uploaded = nullptr;       // recorded behind the upload ...
-    hipStream_t upload_stream = nullptr; // ... on this stream (the stream of the plan's first call); neither where that stream
-                                         // was being captured: the upload was eager and is complete
-    bool captured = false;               // a captured call has used the tables: a live graph may name them
+    lz::TapTables dev{};       // device copies: pointers into the cache item's one block
     lz::FastConsts fast{};      // phase weights etc. for the specialised kernels
     bool fast_ok = false;
     lz::RatHost rat;            // rational scales: per-index f32 weights, integer-phase flags (k_rat)
@@ -57,16 +48,18 @@ struct Plan {
     lz::RatTables ratp_dev{};
     const float* ratp_w_dev = nullptr;
 };
+using PlanCache = lz::UploadCache<PlanKey, Plan>;
 
 }  // namespace
+
+static constexpr size_t kMaxPlans = 32;
 
 struct lanczos_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    std::map<PlanKey, Plan*> plans;
-    lz::LruOrder<PlanKey> plan_order;  // the cache is bounded (kMaxPlans): the least recently used plan is retired
-    lz::RetireList retired_plans;
-    std::vector<void*> kept_dev, kept_host;   // blocks of evicted plans a live graph may still name: freed by lanczos_destroy
+    lz::Lifetime life;                    // where every replaced device block of the context goes (lanczos_cache.hpp)
+    PlanCache plans{&life, kMaxPlans};    // tap tables, one block per shape
+    lz::WgTabCache wg_tabs{&life};        // k_march's workgroup tables, one per launch shape
     std::mutex mu;
     int last_kernel = LANCZOS_KERNEL_NONE;
     int last_tensor_route = 0;   // lanczos_last_tensor_route: LANCZOS_TENSOR_* of the last call, 0 unless it was a tensor call
@@ -77,10 +70,7 @@ struct lanczos_ctx {
     int route_seen = 0;      // prefix routes of those launches, one bit each
     int last_hip = 0;
     int force = LANCZOS_KERNEL_NONE;
-    // staging for lanczos_resample_host
-    void* stage_in = nullptr;
-    void* stage_out = nullptr;
-    size_t stage_in_bytes = 0, stage_out_bytes = 0;
+    lz::ScratchBlock stage_in, stage_out;   // staging for lanczos_resample_host
     // timing: event triples (start, middle, end) around a call's kernels; ev_prefix_first[i]: the in-place prefix kernel ran
     // in FRONT of the main kernel (start..middle = prefix, middle..end = main) instead of behind it
     bool timing = false;
@@ -92,19 +82,14 @@ struct lanczos_ctx {
 #ifdef LZ_PROFILE_BITS
     void* stamp_buf = nullptr;   // diagnostic builds: per-wave cycle sums + residency census of k_march (lanczos_diag_report)
 #endif
-    lz::WgTabCache wg_tabs;  // k_march's workgroup tables (device copies), one per launch shape
     hipStream_t copy_in = nullptr, copy_out = nullptr;  // lanczos_resample_host pipeline
     std::vector<hipEvent_t> pipe_ev;
-    // interleaved scratch frames of lanczos_resample_planar_device
-    void* planar_in = nullptr;
-    void* planar_out = nullptr;
-    size_t planar_in_bytes = 0, planar_out_bytes = 0;
+    lz::ScratchBlock planar_in, planar_out;   // interleaved scratch frames of lanczos_resample_planar_device
     lz::ResizeState* resize = nullptr;   // lanczos_resize_* (lanczos_resize.hip), created on first use
 };
 #ifdef LZ_PROFILE_BITS
 static constexpr size_t kStampBytes = 16384 * 8 * 6 * 8;
 #endif
-static constexpr size_t kMaxPlans = 32;
 
 namespace {
 
@@ -129,76 +114,21 @@ void route_launch(lanczos_ctx* ctx, int main_kernel, int prefix_route) {
     ctx->last_route = main_kernel | prefix_route << 4 | ctx->route_seen << 8 | ctx->route_launches << 16;
 }
 
-// a scratch block of the context, grown to `bytes` (never shrunk; the old block is freed first)
-int grow_block(lanczos_ctx* ctx, void** block, size_t* have, size_t bytes) {
-    if (*have >= bytes) return LANCZOS_OK;
-    if (*block) (void)hipFree(*block);
-    *block = nullptr;
-    *have = 0;
-    LZ_HIP(ctx, hipMalloc(block, bytes));
-    *have = bytes;
-    return LANCZOS_OK;
-}
-
-void free_plan(Plan* p) {   // nothing in flight reads it any more
-    if (p->dev_block) (void)hipFree(p->dev_block);
-    if (p->host_block) (void)hipHostFree(p->host_block);
-    if (p->uploaded) (void)hipEventDestroy(p->uploaded);
-    delete p;
-}
-
-// The plan of a shape: tap tables built on the host, uploaded ONCE, asynchronously, on the stream of the first call that needs
-// them (page-locked source, no device-wide wait: the entry points stay asynchronous on the caller's stream; calls on other
-// streams wait for the upload by event).  A stream that is being captured into a graph (relaxed capture mode: the first call
-// allocates) would turn the copy and the event into graph nodes that run only when the graph is replayed, perhaps never, while
-// the plan is cached as valid: there the upload is eager instead -- a copy on the context's private upload stream and a wait
-// for it, no event -- so an eager call of the shape before any replay reads complete tables.  Nothing is recorded on, queried
-// from or waited for on a capturing stream.  Tables a captured call has used are not freed when the LRU evicts their plan
-// (the graph may be replayed later): they move to kept_* until lanczos_destroy.
+// The plan of a shape: tap tables built on the host and uploaded ONCE, on the stream of the first call that needs them (the
+// entry points stay asynchronous on the caller's stream).  Upload, ordering of other streams, capture, eviction and release are
+// the upload cache's (lanczos_cache.hpp); here are the key, the host-side preparation and the layout of the block.
 int get_plan(lanczos_ctx* ctx, const lanczos_desc* d, hipStream_t stream, Plan** out) {
     PlanKey key;
     memset(&key, 0, sizeof(key));
     const bool hls = d->mode == LANCZOS_MODE_HLS;
     key = PlanKey{d->in_w, d->in_h, d->out_w, d->out_h, d->channels, d->bytes_per_sample,
                   d->scale_n, d->scale_d, d->a, hls ? 1 + d->reserved[0] : 0};
-    auto it = ctx->plans.find(key);
-    if (it != ctx->plans.end()) {
-        Plan* p = it->second;
-        ctx->plan_order.touch(key);
-        if (lz::stream_capturing(stream)) {
-            // (an upload still in flight on another stream is waited for here: the graph gets no node for it)
-            if (p->uploaded && hipEventQuery(p->uploaded) != hipSuccess) LZ_HIP(ctx, hipEventSynchronize(p->uploaded));
-            p->captured = true;
-        } else {
-            if (p->uploaded && stream != p->upload_stream && hipEventQuery(p->uploaded) != hipSuccess)
-                LZ_HIP(ctx, hipStreamWaitEvent(stream, p->uploaded, 0));  // another stream: behind the upload
-            lz::note_stream(p->streams, stream);
-        }
-        *out = p;
+    if (PlanCache::Item* it = ctx->plans.find(key)) {
+        LZ_HIP(ctx, ctx->plans.use(it, stream));
+        *out = it;
         return LANCZOS_OK;
     }
-    ctx->retired_plans.reap(false);
-    if (ctx->plans.size() >= kMaxPlans && !ctx->plan_order.empty()) {
-        // bounded: a caller that cycles through many shapes does not grow device memory without limit.  The least recently used
-        // plan's tables are freed once the launches that read them have drained (events on the streams it was used on).
-        const PlanKey old = ctx->plan_order.pop_oldest();
-        auto io = ctx->plans.find(old);
-        if (io != ctx->plans.end()) {
-            Plan* q = io->second;
-            if (q->captured) {
-                ctx->kept_dev.push_back(q->dev_block);
-                ctx->kept_host.push_back(q->host_block);
-            } else {
-                ctx->retired_plans.retire({q->dev_block}, {q->host_block}, q->streams);
-            }
-            if (q->uploaded) (void)hipEventDestroy(q->uploaded);
-            delete q;
-            ctx->plans.erase(io);
-        }
-    }
-    Plan* p = new (std::nothrow) Plan();
-    if (!p) return LANCZOS_ERR_NOMEM;
-    p->key = key;
+    Plan plan, *p = &plan;
     if (hls) {  // ROM weights, exact stepping, no in-place prefix (lanczos_hls.hpp)
         lz::build_axis_hls(d->in_w, d->out_w, d->scale_n, d->scale_d, d->a, &p->H, d->reserved[0]);
         lz::build_axis_hls(d->in_h, d->out_h, d->scale_n, d->scale_d, d->a, &p->V, d->reserved[0]);
@@ -231,14 +161,8 @@ int get_plan(lanczos_ctx* ctx, const lanczos_desc* d, hipStream_t stream, Plan**
         off_pw = total;
         total += sizeof(p->ratp.phase_w);
     }
-    hipError_t e = hipHostMalloc(&p->host_block, total, hipHostMallocDefault);
-    if (e != hipSuccess) {
-        ctx->last_hip = (int)e;
-        delete p;
-        return LANCZOS_ERR_HIP;
-    }
-    uint8_t* const host = (uint8_t*)p->host_block;
-    memset(host, 0, total);
+    std::vector<uint8_t> block(total, 0);
+    uint8_t* const host = block.data();
     if (p->rat.ok) {
         memcpy(host + off_hwf, p->rat.h_wf.data(), p->rat.h_wf.size() * 4);
         memcpy(host + off_vwf, p->rat.v_wf.data(), p->rat.v_wf.size() * 4);
@@ -255,33 +179,14 @@ int get_plan(lanczos_ctx* ctx, const lanczos_desc* d, hipStream_t stream, Plan**
     memcpy(host + off_vf, p->V.first.data(), (size_t)d->out_h * 4);
     memcpy(host + off_hw, p->H.w.data(), (size_t)d->out_w * taps * 8);
     memcpy(host + off_vw, p->V.w.data(), (size_t)d->out_h * taps * 8);
-    const bool capturing = lz::stream_capturing(stream);   // hipStreamIsCapturing: the upload below must not become a graph node
-    hipStream_t up = stream;
-    e = hipMalloc(&p->dev_block, total);
-    if (e == hipSuccess && capturing) e = ctx->wg_tabs.eager_stream(&up);
-    if (e == hipSuccess && !capturing) e = hipEventCreateWithFlags(&p->uploaded, hipEventDisableTiming);
-    if (e != hipSuccess) {
+    hipError_t e = hipSuccess;
+    PlanCache::Item* const it = ctx->plans.insert(key, std::move(plan), host, total, stream, lz::Upload::on_stream, &e);
+    if (!it) {
         ctx->last_hip = (int)e;
-        free_plan(p);
         return LANCZOS_ERR_HIP;
     }
-    e = hipMemcpyAsync(p->dev_block, p->host_block, total, hipMemcpyHostToDevice, up);  // stream-ordered in front of the first launch
-    if (e == hipSuccess) e = capturing ? hipStreamSynchronize(up) : hipEventRecord(p->uploaded, stream);
-    if (e != hipSuccess) {
-        // the copy may have been queued: its two blocks go through the retire list, not straight back to the allocator
-        ctx->last_hip = (int)e;
-        ctx->retired_plans.retire({p->dev_block}, {p->host_block}, {up});
-        if (p->uploaded) (void)hipEventDestroy(p->uploaded);
-        delete p;
-        return LANCZOS_ERR_HIP;
-    }
-    if (capturing) {
-        p->captured = true;   // complete: no event, no upload stream to stay behind
-    } else {
-        p->upload_stream = stream;
-        p->streams.push_back(stream);
-    }
-    uint8_t* b = (uint8_t*)p->dev_block;
+    p = it;   // the payload has moved into the item: what follows points its tables into the item's block
+    uint8_t* b = (uint8_t*)it->dev_block;
     p->dev.h_first = (const int32_t*)(b + off_hf);
     p->dev.v_first = (const int32_t*)(b + off_vf);
     p->dev.h_w = (const double*)(b + off_hw);
@@ -305,8 +210,6 @@ int get_plan(lanczos_ctx* ctx, const lanczos_desc* d, hipStream_t stream, Plan**
         p->ratp_dev.near2 = p->ratp.near2;
         p->ratp_w_dev = (const float*)(b + off_pw);
     }
-    ctx->plans[key] = p;
-    ctx->plan_order.touch(key);
     *out = p;
     return LANCZOS_OK;
 }
@@ -532,13 +435,10 @@ int lanczos_destroy(lanczos_ctx* ctx) {
     // Launches of this context may still be running on the caller's streams: the device is drained before anything they read
     // is freed (the only device-wide wait of the library, at the one point where it is owed).
     (void)hipDeviceSynchronize();
-    ctx->retired_plans.reap(true);
+    ctx->plans.release_all();
     ctx->wg_tabs.release_all();
-    for (auto& kv : ctx->plans) free_plan(kv.second);
-    ctx->plans.clear();
-    for (void* p : ctx->kept_dev) (void)hipFree(p);
-    for (void* p : ctx->kept_host) (void)hipHostFree(p);
     delete ctx->resize;
+    ctx->life.release_all();   // (before the context's streams go; the scratch blocks free themselves with the context)
 #ifdef LZ_PROFILE_BITS
     if (ctx->stamp_buf) {
         diag_report(ctx, stderr);
@@ -549,10 +449,6 @@ int lanczos_destroy(lanczos_ctx* ctx) {
     for (hipEvent_t e : ctx->pipe_ev) (void)hipEventDestroy(e);
     if (ctx->copy_in) (void)hipStreamDestroy(ctx->copy_in);
     if (ctx->copy_out) (void)hipStreamDestroy(ctx->copy_out);
-    if (ctx->planar_in) (void)hipFree(ctx->planar_in);
-    if (ctx->planar_out) (void)hipFree(ctx->planar_out);
-    if (ctx->stage_in) (void)hipFree(ctx->stage_in);
-    if (ctx->stage_out) (void)hipFree(ctx->stage_out);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return LANCZOS_OK;
@@ -610,13 +506,14 @@ int lanczos_last_march_table(const lanczos_ctx* ctx, lanczos_march_table_info* i
     info->segs = it->segs;
     info->mode = it->mode_a ? LANCZOS_MARCH_TABLE_A : LANCZOS_MARCH_TABLE_B;
     info->rank_aware = it->balanced ? 1 : 0;
-    info->strips = (int32_t)it->key[1], info->frames = (int32_t)it->key[2];
-    info->m_lo = (int32_t)it->key[3], info->m_hi = (int32_t)it->key[4];
-    info->wg_per_cu = (int32_t)it->key[5], info->cus = (int32_t)it->key[6];
+    const long long* const k = it->key.k;
+    info->strips = (int32_t)k[1], info->frames = (int32_t)k[2];
+    info->m_lo = (int32_t)k[3], info->m_hi = (int32_t)k[4];
+    info->wg_per_cu = (int32_t)k[5], info->cus = (int32_t)k[6];
     const int total = it->n * it->segs;
     if (entries) {
         static_assert(sizeof(lz::WgEntry) == 4 * sizeof(int32_t), "a table entry is four int32");
-        memcpy(entries, it->host, sizeof(lz::WgEntry) * (size_t)(capacity < total ? capacity : total));
+        memcpy(entries, it->host_block, sizeof(lz::WgEntry) * (size_t)(capacity < total ? capacity : total));
     }
     return total;
 }
@@ -882,10 +779,12 @@ int lanczos_resample_host(lanczos_ctx* ctx, const lanczos_desc* d, const void* i
     const lz::UpStrip strip = lz::up_strip(*d, p->V.first.data(), p->prefix);
     const size_t in_frame = (size_t)d->in_w * d->channels * d->bytes_per_sample * strip.in_rows;
     const size_t out_frame = (size_t)d->out_w * d->channels * d->bytes_per_sample * strip.rows;
-    if ((rc = grow_block(ctx, &ctx->stage_in, &ctx->stage_in_bytes, in_frame * frames)) != LANCZOS_OK) return rc;
-    if ((rc = grow_block(ctx, &ctx->stage_out, &ctx->stage_out_bytes, out_frame * frames)) != LANCZOS_OK) return rc;
     if (!ctx->copy_in) LZ_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_in, hipStreamNonBlocking));
     if (!ctx->copy_out) LZ_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_out, hipStreamNonBlocking));
+    // (the context's own streams: never captured.  The copy streams touch one block each, the kernels both)
+    LZ_HIP(ctx, ctx->stage_in.reserve(&ctx->life, in_frame * frames, ctx->copy_in, false));
+    LZ_HIP(ctx, ctx->stage_out.reserve(&ctx->life, out_frame * frames, ctx->copy_out, false));
+    ctx->stage_in.note(ctx->stream, false), ctx->stage_out.note(ctx->stream, false);
     // groups of at most 4 frames, at most 64 groups in flight per call
     int group = frames >= 8 ? 4 : (frames >= 2 ? (frames + 1) / 2 : 1);
     if ((frames + group - 1) / group > 64) group = (frames + 63) / 64;
@@ -901,8 +800,8 @@ int lanczos_resample_host(lanczos_ctx* ctx, const lanczos_desc* d, const void* i
         for (int gi = 0; gi < ngroups; gi++) {
             const int f0 = gi * group, nf = (f0 + group <= frames) ? group : frames - f0;
             const uint8_t* hin = (const uint8_t*)in + (size_t)f0 * in_frame;
-            uint8_t* din = (uint8_t*)ctx->stage_in + (size_t)f0 * in_frame;
-            uint8_t* dout = (uint8_t*)ctx->stage_out + (size_t)f0 * out_frame;
+            uint8_t* din = (uint8_t*)ctx->stage_in.p + (size_t)f0 * in_frame;
+            uint8_t* dout = (uint8_t*)ctx->stage_out.p + (size_t)f0 * out_frame;
             uint8_t* hout = (uint8_t*)out + (size_t)f0 * out_frame;
             LZ_HIP(ctx, hipMemcpyAsync(din, hin, in_frame * nf, hipMemcpyHostToDevice, ctx->copy_in));
             LZ_HIP(ctx, hipEventRecord(ctx->pipe_ev[2 * gi], ctx->copy_in));
@@ -977,17 +876,18 @@ int lanczos_resample_planar_device(lanczos_ctx* ctx, const lanczos_desc* d, cons
     std::lock_guard<std::mutex> lock(ctx->mu);
     LZ_HIP(ctx, hipSetDevice(ctx->device));
     route_begin(ctx);
-    if ((rc = grow_block(ctx, &ctx->planar_in, &ctx->planar_in_bytes, in_bytes)) != LANCZOS_OK) return rc;
-    if ((rc = grow_block(ctx, &ctx->planar_out, &ctx->planar_out_bytes, out_bytes)) != LANCZOS_OK) return rc;
-    LZ_HIP(ctx, lz::layout_launch(true, d_in_planar, ctx->planar_in, d->in_w, d->in_h, d->channels, d->bytes_per_sample, frames,
+    const bool capturing = lz::stream_capturing((hipStream_t)stream);
+    LZ_HIP(ctx, ctx->planar_in.reserve(&ctx->life, in_bytes, (hipStream_t)stream, capturing));
+    LZ_HIP(ctx, ctx->planar_out.reserve(&ctx->life, out_bytes, (hipStream_t)stream, capturing));
+    LZ_HIP(ctx, lz::layout_launch(true, d_in_planar, ctx->planar_in.p, d->in_w, d->in_h, d->channels, d->bytes_per_sample, frames,
                                   (hipStream_t)stream));
     lanczos_desc whole = *d;
     whole.out_row0 = 0;
     whole.out_rows = 0;
-    rc = resample_device_locked(ctx, &whole, ctx->planar_in, ctx->planar_out, frames, 0, 0, stream);
+    rc = resample_device_locked(ctx, &whole, ctx->planar_in.p, ctx->planar_out.p, frames, 0, 0, stream);
     if (rc != LANCZOS_OK) return rc;
     // (the report of the call is that of its resample: the layout launches add nothing to it)
-    const hipError_t e = lz::layout_launch(false, ctx->planar_out, d_out_planar, d->out_w, d->out_h, d->channels, d->bytes_per_sample,
+    const hipError_t e = lz::layout_launch(false, ctx->planar_out.p, d_out_planar, d->out_w, d->out_h, d->channels, d->bytes_per_sample,
                                            frames, (hipStream_t)stream);
     if (e != hipSuccess) {
         route_begin(ctx);
@@ -1125,7 +1025,7 @@ int lanczos_resize_plan_host(const lanczos_resize_desc* d, int frames, lanczos_r
 }
 
 static int resize_state(lanczos_ctx* ctx) {
-    if (!ctx->resize) ctx->resize = new (std::nothrow) lz::ResizeState();
+    if (!ctx->resize) ctx->resize = new (std::nothrow) lz::ResizeState(&ctx->life);
     return ctx->resize ? LANCZOS_OK : LANCZOS_ERR_NOMEM;
 }
 

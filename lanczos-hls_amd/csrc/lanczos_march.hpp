@@ -1423,8 +1423,25 @@ inline int march_build_table(std::vector<WgEntry>& tab, int* segs_out, int strip
     return n;
 }
 
-// retire lists and the table cache: lanczos_cache.hpp (host-only, tested without a GPU)
-using WgTabCache = WgTabCacheT<WgEntry>;
+// Device copies of the workgroup tables a context has used, one per launch shape: an upload cache (lanczos_cache.hpp, host-only,
+// tested without a GPU) of 64 shapes, each uploaded on the stream of its first launch.
+struct WgTabKey {
+    long long k[8];   // instance, strips, frames, m_lo, m_hi, workgroups per CU, CUs, device
+};
+struct WgTabInfo {
+    int n = 0, segs = 1;
+    bool balanced = false;
+    bool mode_a = false;   // march_build_table's branch: one workgroup per CU slot (A) or whole chunks (B)
+};
+struct WgTabCache : UploadCache<WgTabKey, WgTabInfo> {
+    explicit WgTabCache(Lifetime* life) : UploadCache(life, 64) {}
+    // lanczos_last_march_table: the shape of the last k_march launch (march_issue_t notes it where it launches, the entry points
+    // clear it when a call begins).  A key, not a pointer: the item may have been evicted since.
+    WgTabKey last_key = {};
+    bool last_valid = false;
+    void note_last(const WgTabKey& key) { last_key = key, last_valid = true; }
+    const Item* last() const { return last_valid ? peek(last_key) : nullptr; }
+};
 
 // What up_route (lanczos_upscale.hpp) needs to know of this instance on the current device: its workgroup size, LDS and strip
 // width, the workgroups a CU holds at once and the CU count.  Measured once per (instance, exact, device); the dynamic LDS size
@@ -1518,8 +1535,8 @@ inline hipError_t march_issue_t(const lanczos_desc& d, const FrameGeom& g_in, co
     g.prefix_blocks_per_frame = riding ? (g.out_w * C + K::NT - 1) / K::NT : 0;
     // the workgroup table of this launch shape (built once per context and shape)
     const int m_lo = y_lo / S, m_hi = (y_hi - 1) / S + 1;
-    const long long key[8] = {(long long)sizeof(T) | ((long long)C << 8) | ((long long)S << 16) | ((long long)A << 24) | ((long long)exact << 32),
-                              strips, g.frames, m_lo, m_hi, nb, cus, dev};
+    const WgTabKey key{{(long long)sizeof(T) | ((long long)C << 8) | ((long long)S << 16) | ((long long)A << 24) | ((long long)exact << 32),
+                        strips, g.frames, m_lo, m_hi, nb, cus, dev}};
     WgTabCache::Item* item = cache->find(key);
     if (!item) {
         std::vector<WgEntry> tab;
@@ -1527,7 +1544,7 @@ inline hipError_t march_issue_t(const lanczos_desc& d, const FrameGeom& g_in, co
         bool balanced = false, mode_a = false;
         const int n = march_build_table(tab, &segs, strips, g.frames, m_lo, m_hi, K::MS, K::TAPS, nb, cus, K::NWAVES, &balanced, &mode_a);
         hipError_t e = hipSuccess;
-        item = cache->insert(key, tab, n, segs, balanced, stream, &e, mode_a);
+        item = cache->insert(key, WgTabInfo{n, segs, balanced, mode_a}, tab.data(), sizeof(WgEntry) * tab.size(), stream, Upload::on_stream, &e);
         if (!item) return e;
         if (env().verbose)
             fprintf(stderr, "lanczos: k_march table: mode %c, %d workgroups x %d segment(s) for %d strips x %d frames, rows [%d, %d): %s shares\n",
@@ -1538,7 +1555,7 @@ inline hipError_t march_issue_t(const lanczos_desc& d, const FrameGeom& g_in, co
         const hipError_t e = cache->use(item, stream);   // behind the upload
         if (e != hipSuccess) return e;
     }
-    g.wg_tab = item->dev;
+    g.wg_tab = (const WgEntry*)item->dev_block;
     g.wg_segs = item->segs;
     g.wg_per_frame = 0;
     g.n_main = item->n;

@@ -150,114 +150,35 @@ template hipError_t rs_launch_fused<1, 0>(const RsFusedLaunch&);
 
 // ---- host side: cache, planning, launch ---------------------------------------------------------------------------
 
-// a block that launches on `streams` may still read: freed by a later call once they have drained.  A stream that is being
-// captured gets no event (it would become a graph node): such a block waits for the final reap behind a device-wide sync.
-static void rs_retire(RetireList& rl, void* p, const std::vector<hipStream_t>& streams) {
-    std::vector<hipStream_t> live;
-    bool captured = false;
-    for (hipStream_t s : streams) {
-        if (stream_capturing(s)) captured = true;
-        else live.push_back(s);
-    }
-    rl.retire({p}, {}, live);
-    if (captured) rl.list.back().unrecorded = true;
-}
-
-ResizeState::~ResizeState() {   // the owner has drained the device
-    retired.reap(true);
-    for (ResizeAxis* a : axes) {
-        (void)hipFree(a->dev);
-        delete a;
-    }
-    for (void* p : kept) (void)hipFree(p);
-    if (scratch.p) (void)hipFree(scratch.p);
-    if (reduced.p) (void)hipFree(reduced.p);
-    if (tensor_bytes.p) (void)hipFree(tensor_bytes.p);
-    if (packed.p) (void)hipFree(packed.p);
-    if (unpacked.p) (void)hipFree(unpacked.p);
-    if (stage_in) (void)hipFree(stage_in);
-    if (stage_out) (void)hipFree(stage_out);
-    if (upload) (void)hipStreamDestroy(upload);
-}
-
-// The tables of one axis shape, built and uploaded on first use.  The upload is eager: a copy on the private stream and a
-// wait for it, so an entry is valid from the moment it is cached -- also when the caller's stream is being captured
-// (a copy queued on it would only run when the graph is replayed, perhaps never).
-static int rs_axis(ResizeState* st, int in_n, int out_n, int a, int filter, RsSpan span, bool f64, ResizeAxis** out,
-                   int* last_hip) {
-    uint32_t bits[2];
-    memcpy(&bits[0], &span.b0, 4);
-    memcpy(&bits[1], &span.b1, 4);
-    for (size_t i = 0; i < st->axes.size(); i++) {
-        ResizeAxis* ax = st->axes[i];
-        if (ax->key[0] == in_n && ax->key[1] == out_n && ax->key[2] == a && ax->key[3] == (int)f64 &&
-            ax->key[4] == filter && ax->span_bits[0] == bits[0] && ax->span_bits[1] == bits[1]) {
-            st->axes.erase(st->axes.begin() + i);
-            st->axes.push_back(ax);   // most recent last
-            *out = ax;
-            return LANCZOS_OK;
-        }
-    }
-    st->retired.reap(false);
-    ResizeAxis* ax = new (std::nothrow) ResizeAxis();
-    if (!ax) return LANCZOS_ERR_NOMEM;
-    ax->key[0] = in_n, ax->key[1] = out_n, ax->key[2] = a, ax->key[3] = (int)f64, ax->key[4] = filter;
-    ax->span_bits[0] = bits[0], ax->span_bits[1] = bits[1];
-    if (!resize_build_axis(in_n, out_n, a, filter, span, &ax->host, f64)) {
-        delete ax;
-        return LANCZOS_ERR_UNSUPPORTED;
-    }
-    const ResizeAxisHost& h = ax->host;
-    std::vector<int32_t> block((size_t)2 * h.out_n + h.coeffs.size() + 2 * h.coeffs64.size());
-    memcpy(block.data(), h.first.data(), (size_t)h.out_n * 4);
-    memcpy(block.data() + h.out_n, h.count.data(), (size_t)h.out_n * 4);
-    if (f64) memcpy(block.data() + 2 * (size_t)h.out_n, h.coeffs64.data(), h.coeffs64.size() * 8);
-    else memcpy(block.data() + 2 * (size_t)h.out_n, h.coeffs.data(), h.coeffs.size() * 4);
-    hipError_t e = hipSuccess;
-    if (!st->upload) e = hipStreamCreateWithFlags(&st->upload, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void**)&ax->dev, block.size() * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(ax->dev, block.data(), block.size() * 4, hipMemcpyHostToDevice, st->upload);
-    if (e == hipSuccess) e = hipStreamSynchronize(st->upload);
-    if (e != hipSuccess) {
-        *last_hip = (int)e;
-        if (ax->dev) (void)hipFree(ax->dev);   // nothing else has seen the block
-        delete ax;
-        return LANCZOS_ERR_HIP;
-    }
-    if (st->axes.size() >= ResizeState::kMaxAxes) {   // bounded: the least recently used shape goes once its launches drained
-        ResizeAxis* old = st->axes.front();
-        rs_retire(st->retired, old->dev, old->streams);
-        delete old;
-        st->axes.erase(st->axes.begin());
-    }
-    st->axes.push_back(ax);
-    *out = ax;
-    return LANCZOS_OK;
-}
-
-// context scratch of at least `bytes`.  A block a captured launch used may still be named by a live graph: it is kept until
-// the context goes instead of being freed when a larger one replaces it.
-static int rs_scratch(ResizeState* st, ResizeState::Block* blk, size_t bytes, hipStream_t stream, bool capturing,
-                      int* last_hip) {
-    if (blk->bytes < bytes) {
-        if (blk->p) {
-            if (blk->captured) st->kept.push_back(blk->p);
-            else rs_retire(st->retired, blk->p, blk->streams);
-        }
-        blk->p = nullptr;
-        blk->bytes = 0;
-        blk->captured = false;
-        blk->streams.clear();
-        hipError_t e = hipMalloc(&blk->p, bytes);
-        if (e != hipSuccess) {
+// The tables of one axis shape, built and uploaded on first use: first | count | coeffs in one block.  The upload is eager, so
+// an entry is valid from the moment it is cached.  The call's use of the tables on `stream` is noted on the entry.
+static int rs_axis(ResizeState* st, int in_n, int out_n, int a, int filter, RsSpan span, bool f64, hipStream_t stream,
+                   bool capturing, ResizeAxis** out, int* last_hip) {
+    ResizeAxisKey key;
+    memset(&key, 0, sizeof(key));
+    key.in_n = in_n, key.out_n = out_n, key.a = a, key.f64 = (int)f64, key.filter = filter;
+    memcpy(&key.span_bits[0], &span.b0, 4);
+    memcpy(&key.span_bits[1], &span.b1, 4);
+    ResizeState::AxisCache::Item* it = st->axes.find(key);
+    if (!it) {
+        ResizeAxis ax;
+        if (!resize_build_axis(in_n, out_n, a, filter, span, &ax.host, f64)) return LANCZOS_ERR_UNSUPPORTED;
+        const ResizeAxisHost& h = ax.host;
+        std::vector<int32_t> block((size_t)2 * h.out_n + h.coeffs.size() + 2 * h.coeffs64.size());
+        memcpy(block.data(), h.first.data(), (size_t)h.out_n * 4);
+        memcpy(block.data() + h.out_n, h.count.data(), (size_t)h.out_n * 4);
+        if (f64) memcpy(block.data() + 2 * (size_t)h.out_n, h.coeffs64.data(), h.coeffs64.size() * 8);
+        else memcpy(block.data() + 2 * (size_t)h.out_n, h.coeffs.data(), h.coeffs.size() * 4);
+        hipError_t e = hipSuccess;
+        it = st->axes.insert(key, std::move(ax), block.data(), block.size() * 4, stream, Upload::eager, &e);
+        if (!it) {
             *last_hip = (int)e;
-            blk->p = nullptr;
             return LANCZOS_ERR_HIP;
         }
-        blk->bytes = bytes;
+        it->dev = (const int32_t*)it->dev_block;
     }
-    if (capturing) blk->captured = true;
-    else note_stream(blk->streams, stream);
+    (void)st->axes.use(it, stream, capturing);   // (an eager entry has no upload to wait for: nothing here can fail)
+    *out = it;
     return LANCZOS_OK;
 }
 
@@ -342,12 +263,12 @@ int resize_device(ResizeState* st, RsRequest& q) {
     const bool tables_of_both = filter == LANCZOS_FILTER_NEAREST && (r.need_h || r.need_v);
     const bool capturing = stream_capturing(stream);
     ResizeAxis *H = nullptr, *V = nullptr;
-    if ((r.need_h || tables_of_both) && (rc = rs_axis(st, d->in_w, d->out_w, d->a, filter, r.h, B > 1, &H, q.last_hip)) != LANCZOS_OK)
+    if ((r.need_h || tables_of_both) &&
+        (rc = rs_axis(st, d->in_w, d->out_w, d->a, filter, r.h, B > 1, stream, capturing, &H, q.last_hip)) != LANCZOS_OK)
         return rc;
-    if ((r.need_v || tables_of_both) && (rc = rs_axis(st, d->in_h, d->out_h, d->a, filter, r.v, B > 1, &V, q.last_hip)) != LANCZOS_OK)
+    if ((r.need_v || tables_of_both) &&
+        (rc = rs_axis(st, d->in_h, d->out_h, d->a, filter, r.v, B > 1, stream, capturing, &V, q.last_hip)) != LANCZOS_OK)
         return rc;
-    for (ResizeAxis* ax : {H, V})
-        if (ax && !capturing) note_stream(ax->streams, stream);
 
     RsRouteQuery rq;
     rq.d = d0, rq.r = &r, rq.win = w, rq.frames = frames, rq.force = st->force;
@@ -361,12 +282,17 @@ int resize_device(ResizeState* st, RsRequest& q) {
     const int32_t box[4] = {r.rb[0], r.rb[1], r.rb[2], r.rb[3]};
     if (rt.reduce && (rc = reduce_validate(d0->in_w, d0->in_h, C, r.fx, r.fy, box, rb)) != LANCZOS_OK) return rc;
     const struct {
-        ResizeState::Block* blk;
+        ScratchBlock* blk;
         size_t bytes;
     } blocks[5] = {{&st->packed, rt.packed.bytes},     {&st->reduced, rt.reduced.bytes}, {&st->tensor_bytes, rt.tensor_bytes.bytes},
                    {&st->unpacked, rt.unpacked.bytes}, {&st->scratch, rt.scratch.bytes}};
-    for (const auto& b : blocks)
-        if (b.bytes && (rc = rs_scratch(st, b.blk, b.bytes, stream, capturing, q.last_hip)) != LANCZOS_OK) return rc;
+    for (const auto& b : blocks) {
+        const hipError_t ge = b.bytes ? b.blk->reserve(st->life, b.bytes, stream, capturing) : hipSuccess;
+        if (ge != hipSuccess) {
+            *q.last_hip = (int)ge;
+            return LANCZOS_ERR_HIP;
+        }
+    }
 
     const uint8_t* in = (const uint8_t*)q.in;
     hipError_t e = hipSuccess;
@@ -460,18 +386,6 @@ int resize_device(ResizeState* st, RsRequest& q) {
         e = rs_unpack_dest_launch(out, step_fs, (uint8_t*)q.out, out_fs, q.dc.s, win.w, win.h, C, (int)B, frames, stream);
     *q.last_kernel = rt.kernel;
     q.tc.route = rt.tensor_route, q.sc.route = rt.source_route, q.dc.route = rt.dest_route;
-    if (capturing) {   // a live graph may name these tables: they stay until the context goes
-        for (ResizeAxis* ax : {H, V})
-            if (ax) {
-                auto it = std::find(st->axes.begin(), st->axes.end(), ax);
-                if (it != st->axes.end()) {
-                    st->kept.push_back(ax->dev);
-                    ax->dev = nullptr;
-                    st->axes.erase(it);
-                    delete ax;
-                }
-            }
-    }
     if (e != hipSuccess) {
         *q.last_hip = (int)e;
         return LANCZOS_ERR_HIP;
@@ -479,20 +393,6 @@ int resize_device(ResizeState* st, RsRequest& q) {
     return LANCZOS_OK;
 }
 
-
-// staging buffers of the host entry points (resize and reduce)
-static hipError_t rs_grow_stage(ResizeState* st, void** p, size_t* have, size_t need, hipStream_t stream) {
-    if (*have >= need) return hipSuccess;
-    if (*p) {
-        rs_retire(st->retired, *p, {stream});
-        *p = nullptr;
-        *have = 0;
-    }
-    const hipError_t e = hipMalloc(p, need);
-    if (e == hipSuccess) *have = need;
-    else *p = nullptr;
-    return e;
-}
 
 // What the host entry points share: both staging blocks grown, the input copied up, `call` (the device entry on the staged
 // blocks; it returns a LANCZOS_ status), the output copied down and the stream drained.  A tensor request has more to upload:
@@ -511,20 +411,20 @@ template <class F>
 static int rs_staged_call(ResizeState* st, const void* in, size_t in_bytes, void* out, size_t out_bytes, const RsStagedExtra& x,
                           hipStream_t stream, int* last_hip, F&& call) {
     const size_t in_need = std::max({in_bytes, x.table_at + x.table_bytes, x.flips_at + x.flips_bytes, x.origins_at + x.origins_bytes});
-    hipError_t e = rs_grow_stage(st, &st->stage_in, &st->stage_in_bytes, in_need, stream);
-    if (e == hipSuccess) e = rs_grow_stage(st, &st->stage_out, &st->stage_out_bytes, out_bytes, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(st->stage_in, in, in_bytes, hipMemcpyHostToDevice, stream);
+    hipError_t e = st->stage_in.reserve(st->life, in_need, stream, false);   // (the context's own stream: never captured)
+    if (e == hipSuccess) e = st->stage_out.reserve(st->life, out_bytes, stream, false);
+    if (e == hipSuccess) e = hipMemcpyAsync(st->stage_in.p, in, in_bytes, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess && x.table)
-        e = hipMemcpyAsync((uint8_t*)st->stage_in + x.table_at, x.table, x.table_bytes, hipMemcpyHostToDevice, stream);
+        e = hipMemcpyAsync((uint8_t*)st->stage_in.p + x.table_at, x.table, x.table_bytes, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess && x.flips)
-        e = hipMemcpyAsync((uint8_t*)st->stage_in + x.flips_at, x.flips, x.flips_bytes, hipMemcpyHostToDevice, stream);
+        e = hipMemcpyAsync((uint8_t*)st->stage_in.p + x.flips_at, x.flips, x.flips_bytes, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess && x.origins)
-        e = hipMemcpyAsync((uint8_t*)st->stage_in + x.origins_at, x.origins, x.origins_bytes, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess && x.out_up) e = hipMemcpyAsync(st->stage_out, out, out_bytes, hipMemcpyHostToDevice, stream);
+        e = hipMemcpyAsync((uint8_t*)st->stage_in.p + x.origins_at, x.origins, x.origins_bytes, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && x.out_up) e = hipMemcpyAsync(st->stage_out.p, out, out_bytes, hipMemcpyHostToDevice, stream);
     int rc = LANCZOS_OK;
     if (e == hipSuccess) {
         rc = call();
-        if (rc == LANCZOS_OK) e = hipMemcpyAsync(out, st->stage_out, out_bytes, hipMemcpyDeviceToHost, stream);
+        if (rc == LANCZOS_OK) e = hipMemcpyAsync(out, st->stage_out.p, out_bytes, hipMemcpyDeviceToHost, stream);
     }
     const hipError_t es = hipStreamSynchronize(stream);   // nothing stays in flight on the caller's buffers
     if (rc != LANCZOS_OK) return rc;
@@ -562,8 +462,8 @@ int resize_host(ResizeState* st, RsRequest& q) {
         }
     }
     return rs_staged_call(st, q.in, in_bytes, q.out, out_bytes, x, q.stream, q.last_hip, [&] {
-        const uint8_t* up = (const uint8_t*)st->stage_in;
-        q.in = st->stage_in, q.out = st->stage_out, q.in_frame_stride = q.out_frame_stride = 0;
+        const uint8_t* up = (const uint8_t*)st->stage_in.p;
+        q.in = st->stage_in.p, q.out = st->stage_out.p, q.in_frame_stride = q.out_frame_stride = 0;
         if (q.tensor) q.tc.t.d_lut = up + x.table_at;
         if (x.flips) q.tc.t.d_flip = up + x.flips_at;
         if (x.origins) q.tc.d_origin = (const int32_t*)(up + x.origins_at);
@@ -600,7 +500,7 @@ int reduce_host(ResizeState* st, int in_w, int in_h, int channels, int fx, int f
     const size_t in_bytes = (size_t)in_w * in_h * channels * frames;
     const size_t out_bytes = (size_t)((rb[2] - rb[0] + fx - 1) / fx) * ((rb[3] - rb[1] + fy - 1) / fy) * channels * frames;
     return rs_staged_call(st, in, in_bytes, out, out_bytes, {}, stream, last_hip, [&] {
-        return reduce_device(st, in_w, in_h, channels, fx, fy, box, st->stage_in, st->stage_out, frames, 0, 0, stream, last_hip);
+        return reduce_device(st, in_w, in_h, channels, fx, fy, box, st->stage_in.p, st->stage_out.p, frames, 0, 0, stream, last_hip);
     });
 }
 

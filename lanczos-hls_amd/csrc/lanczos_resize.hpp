@@ -148,43 +148,33 @@ int resize_crops_validate(const lanczos_resize_desc* d, const lanczos_resize_cro
 
 // One axis shape on the device: first | count | coeffs in one block (int32 coefficients, or double ones for 16-bit samples:
 // the two int32 arrays in front of them keep those 8-byte aligned).
+struct ResizeAxisKey {
+    int in_n, out_n, a, f64, filter;   // f64: double coefficients
+    uint32_t span_bits[2];             // the bit patterns of the span's two floats: two boxes over one (in, out, a) are two entries
+};
 struct ResizeAxis {
-    int key[5] = {0, 0, 0, 0, 0};   // in, out, a, double coefficients, filter
-    uint32_t span_bits[2] = {0, 0};   // the bit patterns of the span's two floats: two boxes over one (in, out, a) are two entries
     ResizeAxisHost host;
-    int32_t* dev = nullptr;
+    const int32_t* dev = nullptr;   // the cache item's block
     const int32_t* first() const { return dev; }
     const int32_t* count() const { return dev + host.out_n; }
-    template <class KT>   // int32_t, or double for the tables of samples wider than a byte (key[3])
+    template <class KT>   // int32_t, or double for the tables of samples wider than a byte
     const KT* coeffs() const { return (const KT*)(dev + 2 * (size_t)host.out_n); }
-    std::vector<hipStream_t> streams;   // streams whose launches read this block (retirement)
 };
 
 // What a context keeps for its resizes.  Callers serialise per context (ctx->mu).
 struct ResizeState {
-    static constexpr size_t kMaxAxes = 32;   // bounded: the least recently used axis shape is retired at the 33rd
-    std::vector<ResizeAxis*> axes;           // least recently used first
-    RetireList retired;
-    hipStream_t upload = nullptr;            // private stream of the eager table uploads
+    Lifetime* const life;                    // the context's
+    // 32 axis shapes, uploaded eagerly: an entry is complete from the moment it is cached
+    using AxisCache = UploadCache<ResizeAxisKey, ResizeAxis>;
+    AxisCache axes;
     int force = LANCZOS_RESIZE_AUTO;
-    // a block of context scratch that grows on demand
-    struct Block {
-        void* p = nullptr;
-        size_t bytes = 0;
-        bool captured = false;               // used by a captured launch: a live graph may still hold it
-        std::vector<hipStream_t> streams;
-    };
-    Block scratch;                           // intermediate of the two-pass path (the rows the vertical taps read x out_w x C)
-    Block reduced;                           // the reduced frames of a request with reducing_gap, tightly packed
-    Block tensor_bytes;                      // the byte result of a tensor request on the converted route (k_rs_to_tensor reads it)
-    Block packed;                            // the tightly packed copy of a source on the PACKED route (k_rs_pack_source writes it)
-    Block unpacked;                          // the tightly packed result of a destination on the UNPACKED route (k_rs_unpack_dest reads it)
-    std::vector<void*> kept;                 // scratch blocks replaced while a graph may hold them: freed at destruction
-    // staging of lanczos_resize_host
-    void* stage_in = nullptr;
-    void* stage_out = nullptr;
-    size_t stage_in_bytes = 0, stage_out_bytes = 0;
-    ~ResizeState();
+    ScratchBlock scratch;                    // intermediate of the two-pass path (the rows the vertical taps read x out_w x C)
+    ScratchBlock reduced;                    // the reduced frames of a request with reducing_gap, tightly packed
+    ScratchBlock tensor_bytes;               // the byte result of a tensor request on the converted route (k_rs_to_tensor reads it)
+    ScratchBlock packed;                     // the tightly packed copy of a source on the PACKED route (k_rs_pack_source writes it)
+    ScratchBlock unpacked;                   // the tightly packed result of a destination on the UNPACKED route (k_rs_unpack_dest reads it)
+    ScratchBlock stage_in, stage_out;        // staging of lanczos_resize_host
+    explicit ResizeState(Lifetime* l) : life(l), axes(l, 32) {}
 };
 
 // The table and the layout of a tensor request, whatever its element: lanczos_tensor_out (elem 4, floats),

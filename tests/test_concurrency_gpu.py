@@ -3,7 +3,7 @@
 Every other GPU test makes one call at a time from one host thread.  What exists only for concurrent use is exercised here:
 
   two streams, one context   a plan or a workgroup table whose upload is still pending on the stream of its first call, used from a
-                             second stream (the event wait of get_plan / WgTabCacheT::use), from a stream that is being captured
+                             second stream (the event wait of UploadCache::use, lanczos_cache.hpp), from a stream that is being captured
                              (the host-side wait: the graph gets no node for the upload), evicted while two streams are in flight
                              (retirement by events on every stream), and context scratch handed from stream to stream by the
                              caller's own events while its block is replaced.  Only the upscale device entry is promised to work

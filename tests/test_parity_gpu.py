@@ -842,6 +842,35 @@ def test_first_use_of_a_shape_inside_stream_capture():
         c.close()
 
 
+def test_planar_scratch_grows_after_capture():
+    """lanczos_resample_planar_device captured at 32 x 16, then called eagerly at 64 x 48: both interleaved scratch frames of the
+    context grow, and the blocks the graph names must stay (kept, not freed) -- the replay still gives the oracle's frame."""
+    import torch
+    c = L.Context(0)
+    try:
+        small, big = P.gradient_noise(16, 32, 1, seed=21), P.noise(48, 64, 1, seed=22)   # HWC with one channel: planar as it lies
+        ds, db = L.make_desc(32, 16, 1, 2, 1, 3, 1, L.MODE_EXACT), L.make_desc(64, 48, 1, 2, 1, 3, 1, L.MODE_EXACT)
+        xs, xb = torch.from_numpy(small).cuda(), torch.from_numpy(big).cuda()
+        ys = torch.zeros((32, 64, 1), dtype=torch.uint8, device="cuda")
+        yb = torch.zeros((96, 128, 1), dtype=torch.uint8, device="cuda")
+        g = torch.cuda.CUDAGraph()
+        s = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        with torch.cuda.graph(g, stream=s, capture_error_mode="relaxed"):
+            c.resample_planar_device(ds, xs.data_ptr(), ys.data_ptr(), 1, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        assert int(ys.max()) == 0                             # captured, not run
+        c.resample_planar_device(db, xb.data_ptr(), yb.data_ptr(), 1, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        _cmp(yb.cpu().numpy(), _oracle(big, 2, 1, 3), L.MODE_EXACT, "eager call at the larger size")
+        g.replay()
+        torch.cuda.synchronize()
+        _cmp(ys.cpu().numpy(), _oracle(small, 2, 1, 3), L.MODE_EXACT, "replay after the scratch frames grew")
+        del g
+    finally:
+        c.close()
+
+
 @pytest.mark.parametrize("mode", [L.MODE_EXACT, L.MODE_LSB1])
 @pytest.mark.parametrize("sn,sd", [(2, 1), (3, 2)])
 def test_first_use_inside_capture_then_eager_before_replay(sn, sd, mode):

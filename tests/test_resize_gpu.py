@@ -474,6 +474,41 @@ def test_captured_tables_survive_axis_evictions(path):
 
 
 @pytest.mark.parametrize("path", [L.RESIZE_FUSED, L.RESIZE_TWO_PASS])
+def test_one_shape_captured_into_two_graphs(path):
+    """One shape captured into two graphs of one context (the second capture finds the tables the first one cached), 80 other
+    axis shapes afterwards, then both replays and an eager call of the shape."""
+    import torch
+    c = L.Context(0)
+    try:
+        c.resize_force(path)
+        ih, iw, oh, ow = 77, 119, 43, 67
+        img = P.gradient_noise(ih, iw, 3, seed=16)
+        want = M.resize(img, ow, oh, 3)
+        d = L.resize_desc(iw, ih, ow, oh, 3, 3)
+        x = torch.from_numpy(img).cuda()
+        ys = [torch.zeros((oh, ow, 3), dtype=torch.uint8, device="cuda") for _ in range(2)]
+        graphs = [torch.cuda.CUDAGraph() for _ in range(2)]
+        s = torch.cuda.Stream()
+        for g, y in zip(graphs, ys):
+            torch.cuda.synchronize()
+            with torch.cuda.graph(g, stream=s, capture_error_mode="relaxed"):
+                c.resize_device(d, x.data_ptr(), y.data_ptr(), 1, stream=torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        for jw, jh, kw, kh in _axis_shapes(40):
+            other = P.noise(jh, jw, 3, seed=jw)
+            _eq(c.resize(other, kw, kh, 3), M.resize(other, kw, kh, 3), f"{jw}x{jh}->{kw}x{kh}")
+        assert int(ys[0].max()) == 0 and int(ys[1].max()) == 0
+        for k, (g, y) in enumerate(zip(graphs, ys)):
+            g.replay()
+            torch.cuda.synchronize()
+            _eq(y.cpu().numpy(), want, f"replay of graph {k} after 80 other axis shapes")
+        _eq(c.resize(img, ow, oh, 3), want, "the captured shape, eagerly")
+        del graphs
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("path", [L.RESIZE_FUSED, L.RESIZE_TWO_PASS])
 def test_square_shape_first_used_inside_capture(path):
     """in_w == in_h and out_w == out_h: both axes are one cache entry.  Capture, eager call before any replay, replay."""
     import torch

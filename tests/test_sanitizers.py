@@ -31,9 +31,9 @@ def test_host_image_io_under_asan_ubsan(tmp_path):
 
 
 def test_cache_lifetime_under_asan_ubsan(tmp_path):
-    """create -> many shapes -> destroy of the host-only parts (table cache, retire lists, plan-cache recency order) against a model of
-    streams in which queued copies complete only when the test says so (tests/native/cache_lifetime_check.cpp; round-3 harness
-    crash)."""
+    """create -> many shapes -> destroy of the host-only parts (retire list, upload cache in both modes, scratch block) against a
+    model of streams in which queued copies complete only when the test says so (tests/native/cache_lifetime_check.cpp; round-3
+    harness crash)."""
     exe = str(tmp_path / "cache_lifetime_check")
     subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                     "-I" + os.path.join(ROOT, "lanczos-hls_amd", "csrc"), os.path.join(ROOT, "tests", "native", "cache_lifetime_check.cpp"),
