@@ -452,7 +452,7 @@ typedef struct lanczos_tensor_out {
 /* LANCZOS_ERR_BAD_ARG: what lanczos_resize_validate refuses, a null t or table, a stride <= 0 (or above 2^40), non-zero
  * reserved words, strides under which two (c, y, x) share an address -- sorted by stride, each stride must be at least the
  * previous stride times its extent (an axis of extent 1 takes no part).  LANCZOS_ERR_UNSUPPORTED: LANCZOS_RESIZE_U16 or
- * LANCZOS_RESIZE_F32 (a table per 16-bit value and float inputs are out of scope). */
+ * LANCZOS_RESIZE_F32 (no table per 16-bit value or for a float: those frames have lanczos_resize_tensor_norm_* below). */
 int lanczos_resize_tensor_validate(const lanczos_resize_desc* d, const lanczos_tensor_out* t);
 /* Host only: lut[c * 256 + v] = ((float)v / 255.0f - mean[c]) / std[c], in float with IEEE division and no contraction --
  * bit for bit torch's uint8.to(float32).div(255).sub(mean).div(std).  mean == NULL is 0 and std == NULL is 1, so NULL, NULL is
@@ -619,7 +619,7 @@ int lanczos_tensor_view_init(lanczos_tensor_view* v, const lanczos_resize_desc* 
 /* Host only.  LANCZOS_ERR_BAD_ARG: everything lanczos_resize_tensor_window_validate refuses (the overlap rule under the
  * out_channels extents), elem_bytes other than 2 or 4, out_channels outside 1 .. channels, a src_channel out of range, a
  * duplicate or a non-zero one beyond out_channels, flip outside 0 .. 3, non-zero reserved words.  LANCZOS_ERR_UNSUPPORTED:
- * LANCZOS_RESIZE_U16 or LANCZOS_RESIZE_F32. */
+ * LANCZOS_RESIZE_U16 or LANCZOS_RESIZE_F32 (those frames have lanczos_resize_tensor_norm_* below). */
 int lanczos_resize_tensor_view_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win,
                                         const lanczos_tensor_view* v);
 /* As lanczos_resize_tensor_window_device (opts and win may be NULL): d_lut and d_flip are device pointers.  Further
@@ -806,6 +806,66 @@ int lanczos_resize_dest_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, con
                              const void* in, void* out, int frames);
 /* LANCZOS_DEST_DIRECT / LANCZOS_DEST_UNPACKED of the last call that had a destination and returned LANCZOS_OK, 0 before any. */
 int lanczos_last_dest_route(const lanczos_ctx* ctx);
+
+/* ---- resize 16-bit and float frames straight into normalised tensors ----
+ * The tensor entries above are 8-bit only: their table has an entry per sample value.  LANCZOS_RESIZE_U16 (Pillow's I;16) and
+ * LANCZOS_RESIZE_F32 (mode F) frames have this entry instead, which computes the normalisation where the sample is stored.  With
+ * P(f, y, x, c) the sample lanczos_resize_window_device stores for the same descriptor, options and window (a uint16 or a float),
+ * (w, h) the window's extent and m_f = (flip ^ d_flip[f]) & 3:
+ *   out[f][oc * chan_stride + Y * row_stride + X * pix_stride] =
+ *       cvt( ((float)P(f, y, x, src_channel[oc]) / div[oc] - mean[oc]) / std[oc] )
+ *   X = (m_f & 1) ? w - 1 - x : x        Y = (m_f & 2) ? h - 1 - y : y
+ * (float)P is exact for a 16-bit sample and the identity for a float one.  The division, the subtraction and the division are
+ * three separately rounded IEEE binary32 operations, round to nearest, denormals kept: no fused multiply-add, no reciprocal, no
+ * folded scale -- those differ from the three operations on most 16-bit values.  cvt is the identity for LANCZOS_TENSOR_F32 and
+ * what lanczos_tensor_lut_convert16 computes for LANCZOS_TENSOR_BF16 / _F16: round to nearest even, float16 subnormals kept,
+ * overflow to +-inf, a NaN to some NaN.  With `resized` Pillow's own output this is, bit for bit, torch's
+ * torch.from_numpy(resized).permute(...).float().div(div).sub(mean).div(std)[.to(dtype)] on the CPU.
+ * div, mean and std are indexed by the OUTPUT channel and passed by value: a captured call bakes them in.  They are not
+ * inspected -- the arithmetic is defined for every float.  The channel map, the flips, the strides (in elements), the overlap
+ * rule, the extent, the minimum out_frame_stride and d_flip's lifetime are lanczos_tensor_view's; elements the strides do not
+ * name are not written.
+ * opts: a box; a reducing_gap stays refused for wide samples.  win: optional.  src: optional, a row-pitched interleaved source;
+ * a planar source of wide samples stays LANCZOS_ERR_UNSUPPORTED.  No crop origins.  LANCZOS_FILTER_NEAREST with _U16 stays
+ * LANCZOS_ERR_UNSUPPORTED.
+ * Routes (lanczos_last_tensor_route): LANCZOS_TENSOR_FUSED exactly when lanczos_resize_window_plan_host says the sample request
+ * is fused and one element frame spans less than 2^31 bytes: the fused kernel's vertical pass applies the operations to the sum
+ * it holds and stores the element.  Everything else (two passes, one pass, tall frames, LANCZOS_FILTER_NEAREST on floats, the
+ * plain copy, forced LANCZOS_RESIZE_TWO_PASS / _CONVERT, larger element frames) is LANCZOS_TENSOR_CONVERTED: the samples go
+ * tightly packed to context scratch and one streaming launch (k_rs_to_tensor_norm) follows; a request that changes neither axis
+ * and has no window converts straight from the caller's frames.  lanczos_last_kernel and lanczos_resize_force apply as for the
+ * other tensor entries. */
+#define LANCZOS_TENSOR_F32 3   /* an element format beside LANCZOS_TENSOR_BF16 / LANCZOS_TENSOR_F16 */
+#define LANCZOS_TENSOR_CHW 0   /* the layouts of lanczos_tensor_norm_init */
+#define LANCZOS_TENSOR_HWC 1
+typedef struct lanczos_tensor_norm {
+    float div[4], mean[4], std[4];                 /* per output channel; entries beyond out_channels are not read */
+    int64_t chan_stride, row_stride, pix_stride;   /* in elements, each > 0 */
+    int32_t format;           /* LANCZOS_TENSOR_F32, LANCZOS_TENSOR_BF16 or LANCZOS_TENSOR_F16 */
+    int32_t out_channels;     /* 1 .. d->channels */
+    int32_t src_channel[4];   /* as lanczos_tensor_view */
+    int32_t flip;             /* bit 0: mirror x, bit 1: mirror y -- applied to every frame */
+    const uint8_t* d_flip;    /* NULL, or one byte per frame (same bits), XORed with `flip`; read when the kernels run */
+    int32_t reserved[4];      /* must be 0 */
+} lanczos_tensor_norm;
+/* Host only: the identity over every channel, the tight LANCZOS_TENSOR_CHW or _HWC strides of d's whole output, no flips,
+ * div = 1, mean = 0, std = 1.  LANCZOS_ERR_BAD_ARG: a null n, what lanczos_resize_validate refuses, an unknown format or layout. */
+int lanczos_tensor_norm_init(lanczos_tensor_norm* n, const lanczos_resize_desc* d, int format, int layout);
+/* Host only.  LANCZOS_ERR_UNSUPPORTED: an 8-bit descriptor (the table entries above serve those).  LANCZOS_ERR_BAD_ARG: an
+ * unknown format and everything lanczos_resize_tensor_view_validate refuses, the table pointer aside. */
+int lanczos_resize_tensor_norm_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win,
+                                        const lanczos_tensor_norm* n);
+/* Device buffers, asynchronous on `stream`: d_in and in_frame_stride are multiples of the sample width, d_out and
+ * out_frame_stride (bytes; 0 = the frame's extent) multiples of the element width. */
+int lanczos_resize_tensor_norm_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                      const lanczos_resize_window* win, const lanczos_resize_source* src,
+                                      const lanczos_tensor_norm* n, const void* d_in, void* d_out, int frames,
+                                      size_t in_frame_stride, size_t out_frame_stride, void* stream);
+/* Host buffers and a HOST flip array (`frames` bytes, or NULL); source frames the layout's extent apart, element frames one
+ * extent apart; synchronous.  Elements of `out` the strides do not name keep their contents. */
+int lanczos_resize_tensor_norm_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                    const lanczos_resize_window* win, const lanczos_resize_source* src,
+                                    const lanczos_tensor_norm* n, const void* in, void* out, int frames);
 
 /* ---- reduce by whole factors (Pillow's Image.reduce((fx, fy), box), an exact integer box average) ----
  * 8-bit, 1, 3 or 4 independent interleaved channels.  box = (x0, y0, x1, y1), integers with 0 <= x0 < x1 <= in_w and the same

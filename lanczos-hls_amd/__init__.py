@@ -40,6 +40,9 @@ FILTER_NAMES = ("lanczos", "box", "bilinear", "hamming", "bicubic", "nearest")
 TENSOR_FUSED, TENSOR_CONVERTED = 1, 2   # lanczos_last_tensor_route: who wrote the floats of the last tensor call
 TENSOR_BF16, TENSOR_F16 = 1, 2          # the formats of lanczos_tensor_lut_convert16 / lanczos_tensor16_lut_normalize
 _TENSOR16_FORMATS = {"bfloat16": TENSOR_BF16, "float16": TENSOR_F16}
+TENSOR_F32 = 3                          # ... and the third element format of lanczos_tensor_norm
+TENSOR_CHW, TENSOR_HWC = 0, 1           # the layouts of lanczos_tensor_norm_init
+_TENSOR_NORM_FORMATS = {"float32": TENSOR_F32, "bfloat16": TENSOR_BF16, "float16": TENSOR_F16}
 SOURCE_INTERLEAVED, SOURCE_PLANAR = 0, 1   # the layouts of lanczos_resize_source_init
 SOURCE_DIRECT, SOURCE_PACKED = 1, 2        # lanczos_last_source_route: who read the source of the last call that had one
 DEST_INTERLEAVED, DEST_PLANAR = 0, 1       # the layouts of lanczos_resize_dest_init
@@ -83,6 +86,8 @@ ABI_SYMBOLS = [
     "lanczos_last_source_route",
     "lanczos_resize_dest_init", "lanczos_resize_dest_validate", "lanczos_resize_dest_device", "lanczos_resize_dest_host",
     "lanczos_last_dest_route",
+    "lanczos_tensor_norm_init", "lanczos_resize_tensor_norm_validate", "lanczos_resize_tensor_norm_device",
+    "lanczos_resize_tensor_norm_host",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
 
@@ -190,6 +195,16 @@ class TensorView(ctypes.Structure):
                 ("pix_stride", ctypes.c_int64), ("elem_bytes", ctypes.c_int32), ("out_channels", ctypes.c_int32),
                 ("src_channel", ctypes.c_int32 * 4), ("flip", ctypes.c_int32), ("d_flip", ctypes.c_void_p),
                 ("reserved", ctypes.c_int32 * 4)]
+
+
+class TensorNorm(ctypes.Structure):
+    """lanczos_tensor_norm -- a tensor request of 16-bit or float samples: out[oc * chan_stride + Y * row_stride +
+    X * pix_stride] = cvt(((float)sample of source channel src_channel[oc] / div[oc] - mean[oc]) / std[oc]), three IEEE float
+    operations, X and Y mirrored per frame as in TensorView; format TENSOR_F32 / TENSOR_BF16 / TENSOR_F16."""
+    _fields_ = [("div", ctypes.c_float * 4), ("mean", ctypes.c_float * 4), ("std", ctypes.c_float * 4),
+                ("chan_stride", ctypes.c_int64), ("row_stride", ctypes.c_int64), ("pix_stride", ctypes.c_int64),
+                ("format", ctypes.c_int32), ("out_channels", ctypes.c_int32), ("src_channel", ctypes.c_int32 * 4),
+                ("flip", ctypes.c_int32), ("d_flip", ctypes.c_void_p), ("reserved", ctypes.c_int32 * 4)]
 
 
 class ResizeCrops(ctypes.Structure):
@@ -380,6 +395,13 @@ def _lib():
                                                      c_size_t, c_void_p]
             L.lanczos_resize_dest_host.argtypes = [c_void_p, PRD, PRO, PRW, PRS, PRT, c_void_p, c_void_p, c_int]
             L.lanczos_last_dest_route.argtypes = [c_void_p]
+        if hasattr(L, "lanczos_resize_tensor_norm_device"):   # (nor 16-bit and float samples into tensors)
+            PTN = ctypes.POINTER(TensorNorm)
+            L.lanczos_tensor_norm_init.argtypes = [PTN, PRD, c_int, c_int]
+            L.lanczos_resize_tensor_norm_validate.argtypes = [PRD, PRW, PTN]
+            L.lanczos_resize_tensor_norm_device.argtypes = [c_void_p, PRD, PRO, PRW, PRS, PTN, c_void_p, c_void_p, c_int, c_size_t,
+                                                            c_size_t, c_void_p]
+            L.lanczos_resize_tensor_norm_host.argtypes = [c_void_p, PRD, PRO, PRW, PRS, PTN, c_void_p, c_void_p, c_int]
         L.lanczos_strerror.restype = ctypes.c_char_p
         L.lanczos_version.argtypes = []
         L.lanczos_version.restype = ctypes.c_char_p
@@ -782,6 +804,52 @@ def tensor_view(d_lut, strides, elem_bytes=4, channels_out=(0, 1, 2), flip=0, d_
     v.flip = _FLIP_NAMES[flip] if flip in _FLIP_NAMES else int(flip)
     v.d_flip = d_flip
     return v
+
+
+def tensor_norm_init(desc, dtype="float32", layout="chw"):
+    """lanczos_tensor_norm_init: the identity over every channel, the tight "chw" or "hwc" strides of the whole output, no
+    flips, div = 1, mean = 0, std = 1."""
+    n = TensorNorm()
+    if dtype not in _TENSOR_NORM_FORMATS or layout not in ("chw", "hwc"):
+        raise LanczosError(ERR_BAD_ARG, f"tensor_norm_init: dtype float32 / bfloat16 / float16 and layout chw / hwc, not {dtype!r}, {layout!r}")
+    _check(_lib().lanczos_tensor_norm_init(ctypes.byref(n), ctypes.byref(desc), _TENSOR_NORM_FORMATS[dtype],
+                                           TENSOR_CHW if layout == "chw" else TENSOR_HWC), "lanczos_tensor_norm_init")
+    return n
+
+
+def tensor_norm(strides, div=1.0, mean=0.0, std=1.0, dtype="float32", channels_out=(0, 1, 2), flip=0, d_flip=None):
+    """A TensorNorm: strides = (chan_stride, row_stride, pix_stride) in elements; div / mean / std one value or one per OUTPUT
+    channel (float32: they are used as given, torch's .div(div).sub(mean).div(std)); dtype "float32", "bfloat16" or "float16";
+    channels_out, flip and d_flip as tensor_view.  Validated where it is used (resize_tensor_norm_validate)."""
+    n = TensorNorm()
+    if dtype not in _TENSOR_NORM_FORMATS:
+        raise LanczosError(ERR_BAD_ARG, f"tensor_norm: dtype is 'float32', 'bfloat16' or 'float16', not {dtype!r}")
+    src = [int(c) for c in channels_out]
+    if not 1 <= len(src) <= 4:
+        raise LanczosError(ERR_BAD_ARG, "tensor_norm: one to four output channels")
+    for name, v in (("div", div), ("mean", mean), ("std", std)):
+        a = np.asarray(v, dtype=np.float32)
+        if a.shape not in ((), (len(src),)):
+            raise LanczosError(ERR_BAD_ARG, f"tensor_norm: {name} is one value, or one per output channel")
+        a = np.broadcast_to(a, (len(src),))
+        for oc in range(len(src)):
+            getattr(n, name)[oc] = a[oc]
+    n.chan_stride, n.row_stride, n.pix_stride = (int(x) for x in strides)
+    n.format = _TENSOR_NORM_FORMATS[dtype]
+    n.out_channels = len(src)
+    for oc, sc in enumerate(src):
+        n.src_channel[oc] = sc
+    n.flip = _FLIP_NAMES[flip] if flip in _FLIP_NAMES else int(flip)
+    n.d_flip = d_flip
+    return n
+
+
+def resize_tensor_norm_validate(desc, n, window=None):
+    """lanczos_resize_tensor_norm_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the request is refused.
+    window: the strides describe that window's frame."""
+    _check(_lib().lanczos_resize_tensor_norm_validate(ctypes.byref(desc), _window_ref(desc, window),
+                                                      ctypes.byref(n) if n is not None else None),
+           "lanczos_resize_tensor_norm_validate")
 
 
 def resize_tensor_view_validate(desc, v, window=None):
@@ -1278,6 +1346,63 @@ class Context:
             _check(_lib().lanczos_resize_tensor_window_device(self._h, ctypes.byref(desc), oref, wref, ctypes.byref(t), d_in,
                                                               d_out, frames, in_frame_stride, out_frame_stride, stream),
                    "lanczos_resize_tensor_window_device")
+
+    # -- 16-bit and float frames straight into normalised tensors (lanczos_resize_tensor_norm_*)
+    def resize_tensor_norm(self, img, out_w, out_h, div=None, mean=None, std=None, dtype="float32", layout="chw", a=3, box=None,
+                           filter=FILTER_LANCZOS, window=None, channels_out=None, flip=None):
+        """img: uint16 or float32 [H][W], [H][W][C] or [F][H][W][C] as Context.resize / Context.resize_f32 take it -> elements
+        [F][C][H][W] (layout="chw") or [F][H][W][C] ("hwc"), the frame axis dropped as resize drops it:
+        ((float(P) / div - mean) / std) of the samples P those calls return for the same arguments, three IEEE float operations
+        -- bit for bit torch.from_numpy(P).permute(2, 0, 1).float().div(div).sub(mean).div(std) on the CPU, followed by
+        .to(dtype) for dtype "bfloat16" (returned as np.uint16 patterns) or "float16" (np.float16).  div=None is 65535 for
+        uint16 and 1 for float32; mean=None is 0, std=None is 1; each one value or one per channel of the result.  box, filter,
+        window, channels_out and flip as Context.resize_tensor.  No reducing_gap, no alpha, no crop origins."""
+        img = np.ascontiguousarray(img)
+        if img.dtype not in (np.uint16, np.float32) or img.ndim not in (2, 3, 4):
+            raise LanczosError(ERR_BAD_ARG, "resize_tensor_norm: expected a uint16 or float32 [H][W], [H][W][C] or [F][H][W][C] array")
+        if dtype not in _TENSOR_NORM_FORMATS:
+            raise LanczosError(ERR_BAD_ARG, f"resize_tensor_norm: dtype is 'float32', 'bfloat16' or 'float16', not {dtype!r}")
+        x = img.reshape(img.shape + (1,)) if img.ndim == 2 else img
+        x = x if x.ndim == 4 else x[None]
+        f, h, w, c = x.shape
+        u16 = img.dtype == np.uint16
+        d = resize_desc(w, h, out_w, out_h, c, a, bits=16 if u16 else 8, f32=not u16, filter=filter)
+        src = tuple(int(v) for v in channels_out) if channels_out is not None else tuple(range(c))
+        if not 1 <= len(src) <= c:
+            raise LanczosError(ERR_BAD_ARG, f"resize_tensor_norm: channels_out names 1 to {c} source channels")
+        c = len(src)
+        flips = None
+        if flip is not None and not isinstance(flip, str):
+            flips = np.ascontiguousarray(flip)
+            if flips.shape != (f,) or flips.dtype.kind not in "iub" or ((flips < 0) | (flips > 3)).any():
+                raise LanczosError(ERR_BAD_ARG, f"resize_tensor_norm: flip is 'h', 'v', 'hv' or {f} integers 0 .. 3, one per frame")
+            flips = flips.astype(np.uint8)
+        elif flip not in _FLIP_NAMES:
+            raise LanczosError(ERR_BAD_ARG, f"resize_tensor_norm: flip is 'h', 'v', 'hv' or one integer per frame, not {flip!r}")
+        win = resize_window(d, window)
+        n = tensor_norm(tensor_strides(layout, win.w, win.h, c), (65535.0 if u16 else 1.0) if div is None else div,
+                        0.0 if mean is None else mean, 1.0 if std is None else std, dtype, src,
+                        0 if flips is not None else flip, flips.ctypes.data if flips is not None else None)
+        out = np.empty((f, c, win.h, win.w) if layout == "chw" else (f, win.h, win.w, c),
+                       dtype=np.float32 if dtype == "float32" else np.uint16)
+        _check(_lib().lanczos_resize_tensor_norm_host(self._h, ctypes.byref(d), _opts_ref(d, box, None, None),
+                                                      ctypes.byref(win) if window is not None else None, None, ctypes.byref(n),
+                                                      x.ctypes.data, out.ctypes.data, f), "lanczos_resize_tensor_norm_host")
+        out = out if dtype == "float32" else _tensor16_array(out, dtype)
+        return out if img.ndim == 4 else out[0]
+
+    def resize_tensor_norm_device(self, desc, d_in, d_out, frames, norm, in_frame_stride=0, out_frame_stride=0, stream=None,
+                                  box=None, opts=None, window=None, source=None):
+        """Device pointers, asynchronous on `stream`: uint16 (resize_desc(..., bits=16)) or float32 (f32=True) frames at d_in
+        -> element frames at d_out as `norm`, a TensorNorm (tensor_norm / tensor_norm_init), describes them; its div / mean /
+        std travel by value.  out_frame_stride in BYTES (0 = one frame's extent).  box / opts as resize_device; window =
+        (x0, y0, w, h) or a ResizeWindow: the strides describe that window's frame; source: a ResizeSource of pitched
+        interleaved rows for the frames at d_in."""
+        _check(_lib().lanczos_resize_tensor_norm_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, None, opts),
+                                                        _window_ref(desc, window),
+                                                        ctypes.byref(source) if source is not None else None, ctypes.byref(norm),
+                                                        d_in, d_out, frames, in_frame_stride, out_frame_stride, stream),
+               "lanczos_resize_tensor_norm_device")
 
     def last_tensor_route(self):
         """TENSOR_FUSED (the resize kernel stored the floats), TENSOR_CONVERTED (bytes to scratch, then a conversion launch),

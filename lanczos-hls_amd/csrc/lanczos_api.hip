@@ -1301,6 +1301,53 @@ int lanczos_resize_tensor_crops_host(lanczos_ctx* ctx, const lanczos_resize_desc
 
 int lanczos_last_tensor_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_tensor_route : 0; }
 
+// ---- 16-bit and float frames into normalised tensors (lanczos_resize_tensor_norm.hip) -----------------------------------
+
+int lanczos_tensor_norm_init(lanczos_tensor_norm* n, const lanczos_resize_desc* d, int format, int layout) {
+    if (!n || (format != LANCZOS_TENSOR_F32 && format != LANCZOS_TENSOR_BF16 && format != LANCZOS_TENSOR_F16)) return LANCZOS_ERR_BAD_ARG;
+    if (layout != LANCZOS_TENSOR_CHW && layout != LANCZOS_TENSOR_HWC) return LANCZOS_ERR_BAD_ARG;
+    const int rc = lz::resize_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    *n = lanczos_tensor_norm{};
+    for (int c = 0; c < 4; c++) n->div[c] = 1.0f, n->std[c] = 1.0f;
+    if (layout == LANCZOS_TENSOR_CHW) n->chan_stride = (int64_t)d->out_h * d->out_w, n->row_stride = d->out_w, n->pix_stride = 1;
+    else n->chan_stride = 1, n->row_stride = (int64_t)d->out_w * d->channels, n->pix_stride = d->channels;
+    n->format = format, n->out_channels = d->channels;
+    for (int c = 0; c < d->channels; c++) n->src_channel[c] = c;
+    return LANCZOS_OK;
+}
+
+int lanczos_resize_tensor_norm_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win,
+                                        const lanczos_tensor_norm* n) {
+    lz::RsTensorOut lay;
+    return lz::tensor_norm_validate(d, win, n, &lay);
+}
+
+extern "C++" {
+static int resize_norm(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                       const lanczos_resize_source* src, const lanczos_tensor_norm* n, const ResizeBufs& b) {
+    if (!ctx || b.null()) return LANCZOS_ERR_BAD_ARG;
+    lz::RsRequest q = resize_request(d, o, win, b);
+    q.tensor = true, q.source = src != nullptr;
+    int rc = lz::tensor_norm_validate(d, win, n, &q.tc.t);
+    if (rc == LANCZOS_OK && src) rc = lz::resize_source_resolve(d, src, &q.sc.s);
+    return rc != LANCZOS_OK ? rc : resize_run(ctx, q, b.host);
+}
+}   // extern "C++"
+
+int lanczos_resize_tensor_norm_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                      const lanczos_resize_window* win, const lanczos_resize_source* src,
+                                      const lanczos_tensor_norm* n, const void* d_in, void* d_out, int frames,
+                                      size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+    return resize_norm(ctx, d, opts, win, src, n, {d_in, d_out, frames, in_frame_stride, out_frame_stride, stream, false});
+}
+
+int lanczos_resize_tensor_norm_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                    const lanczos_resize_window* win, const lanczos_resize_source* src,
+                                    const lanczos_tensor_norm* n, const void* in, void* out, int frames) {
+    return resize_norm(ctx, d, opts, win, src, n, host_bufs(in, out, frames));
+}
+
 // ---- a source layout beside the descriptor (lanczos_resize_source.hip) -------------------------------------------------
 int lanczos_resize_source_init(lanczos_resize_source* src, const lanczos_resize_desc* d, int layout) {
     if (!src || (layout != LANCZOS_SOURCE_INTERLEAVED && layout != LANCZOS_SOURCE_PLANAR)) return LANCZOS_ERR_BAD_ARG;

@@ -229,7 +229,7 @@ static hipError_t rs_launch_fused_any(int bps, int flags, const RsFusedLaunch& c
         X(1, 4 + kRsMapped + kRsCrops) X(1, 2 + kRsMapped + kRsCrops)
         X(1, kRsPlanar) X(1, 4 + kRsMapped + kRsPlanar) X(1, 2 + kRsMapped + kRsPlanar)
         X(1, kRsRowShift) X(1, 4 + kRsMapped + kRsRowShift) X(1, 2 + kRsMapped + kRsRowShift)
-        X(1, kRsPlanarOut) X(1, kRsPlanar + kRsPlanarOut) X(2, 0) X(4, 0)
+        X(1, kRsPlanarOut) X(1, kRsPlanar + kRsPlanarOut) X(2, 0) X(4, 0) X(2, kRsNorm) X(4, kRsNorm)
 #undef X
         default: return hipErrorInvalidValue;
     }
@@ -254,8 +254,9 @@ int resize_device(ResizeState* st, RsRequest& q) {
     const size_t out_fs = q.out_frame_stride ? q.out_frame_stride : out_frame;
     // a destination's frames may overlap each other's padding: the stride has to clear the named bytes only
     if (in_fs < in_frame || out_fs < (q.dest ? q.dc.s.named : out_frame)) return LANCZOS_ERR_BAD_ARG;
-    if ((((uintptr_t)q.in | (uintptr_t)q.out | in_fs | out_fs) & (B - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
-    if (q.tensor && (((uintptr_t)q.out | out_fs) & (size_t)(q.tc.t.elem - 1)) != 0) return LANCZOS_ERR_BAD_ARG;   // element frames
+    // samples lie on multiples of their width; the frames of a tensor request hold elements, which lie on multiples of theirs
+    if ((((uintptr_t)q.in | in_fs) & (B - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
+    if ((((uintptr_t)q.out | out_fs) & (q.tensor ? (size_t)(q.tc.t.elem - 1) : B - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
 
     // the tables: of an axis that runs, and both index tables of the gather
     const lanczos_resize_desc* const d = &r.inner;   // the frames the resize reads: the caller's, or the reduced ones
@@ -273,7 +274,7 @@ int resize_device(ResizeState* st, RsRequest& q) {
     RsRouteQuery rq;
     rq.d = d0, rq.r = &r, rq.win = w, rq.frames = frames, rq.force = st->force;
     rq.tensor = q.tensor, rq.mapped = q.tc.t.mapped, rq.crops = q.tensor && q.tc.d_origin, rq.elem = q.tc.t.elem;
-    rq.extent_bytes = q.tc.extent_bytes;
+    rq.extent_bytes = q.tc.extent_bytes, rq.norm = q.tensor && q.tc.t.norm;
     rq.src = q.source ? &q.sc.s : nullptr, rq.dst = q.dest ? &q.dc.s : nullptr;
     rq.H = H ? &H->host : nullptr, rq.V = V ? &V->host : nullptr;
     const RsRoute rt = rs_route(rq);
@@ -373,6 +374,10 @@ int resize_device(ResizeState* st, RsRequest& q) {
             case kRsFollowToTensor:
                 e = rs_to_tensor_launch(out, step_fs, (uint8_t*)q.out, out_fs, win.w, win.h, C, q.tc.t, frames, stream);
                 break;
+            case kRsFollowToTensorNorm:   // from the scratch the main step filled, or from the frames no step had to touch
+                e = rs_to_tensor_norm_launch(rt.follow_src ? in : out, rt.follow_src ? in_fs : step_fs, (uint8_t*)q.out, out_fs, win.w,
+                                             win.h, C, (int)B, q.tc.t, frames, stream);
+                break;
             case kRsFollowCropsScratch:
                 e = rs_to_tensor_crops_launch(out, step_fs, (size_t)win.w * C, win.w, win.h, (uint8_t*)q.out, out_fs, w.w, w.h, C,
                                               q.tc.t, q.tc.d_origin, frames, stream);
@@ -441,8 +446,8 @@ static int rs_staged_call(ResizeState* st, const void* in, size_t in_bytes, void
 int resize_host(ResizeState* st, RsRequest& q) {
     const lanczos_resize_desc* d = q.d;
     const size_t B = (size_t)resize_bps(d), frames = (size_t)q.frames;
-    if ((((uintptr_t)q.in | (uintptr_t)q.out) & (B - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
-    if (q.tensor && ((uintptr_t)q.out & (uintptr_t)(q.tc.t.elem - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
+    if (((uintptr_t)q.in & (B - 1)) != 0) return LANCZOS_ERR_BAD_ARG;
+    if (((uintptr_t)q.out & (q.tensor ? (uintptr_t)(q.tc.t.elem - 1) : (uintptr_t)(B - 1))) != 0) return LANCZOS_ERR_BAD_ARG;
     RsWindow w;
     const int rc = resize_window_resolve(d, q.win, &w);
     if (rc != LANCZOS_OK) return rc;
@@ -454,7 +459,8 @@ int resize_host(ResizeState* st, RsRequest& q) {
     x.out_up = q.tensor || q.dest;   // what the layout does not name keeps what it held
     if (q.tensor) {
         const RsTensorOut& t = q.tc.t;
-        x.table = t.d_lut, x.table_at = (in_bytes + 255) & ~(size_t)255, x.table_bytes = (size_t)t.out_channels * 256 * t.elem;
+        x.table = t.d_lut, x.table_at = (in_bytes + 255) & ~(size_t)255;
+        x.table_bytes = t.norm ? 0 : (size_t)t.out_channels * 256 * t.elem;   // (a norm request has no table: d_lut is NULL)
         if (t.d_flip) x.flips = t.d_flip, x.flips_at = x.table_at + x.table_bytes, x.flips_bytes = frames;
         if (q.tc.d_origin) {
             x.origins = q.tc.d_origin, x.origins_bytes = frames * 8;
@@ -464,7 +470,7 @@ int resize_host(ResizeState* st, RsRequest& q) {
     return rs_staged_call(st, q.in, in_bytes, q.out, out_bytes, x, q.stream, q.last_hip, [&] {
         const uint8_t* up = (const uint8_t*)st->stage_in.p;
         q.in = st->stage_in.p, q.out = st->stage_out.p, q.in_frame_stride = q.out_frame_stride = 0;
-        if (q.tensor) q.tc.t.d_lut = up + x.table_at;
+        if (q.tensor && x.table) q.tc.t.d_lut = up + x.table_at;
         if (x.flips) q.tc.t.d_flip = up + x.flips_at;
         if (x.origins) q.tc.d_origin = (const int32_t*)(up + x.origins_at);
         return resize_device(st, q);

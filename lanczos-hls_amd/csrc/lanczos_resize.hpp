@@ -8,7 +8,9 @@
 // and lanczos_resize_tensor16_view.hip (the same two through a channel map and flips), lanczos_resize_tensor_crops.hip and
 // lanczos_resize_tensor16_crops.hip (those with a crop origin per frame), lanczos_resize_source.hip, lanczos_resize_source_tensor.hip
 // and lanczos_resize_source_tensor16.hip (those of a planar or oddly pitched source), lanczos_resize_dest.hip and
-// lanczos_resize_dest_source.hip (8-bit into a planar destination), lanczos_resize16.hip and lanczos_resize32.hip.  The filter of a request (LANCZOS_RESIZE_FILTER)
+// lanczos_resize_dest_source.hip (8-bit into a planar destination), lanczos_resize16.hip and lanczos_resize32.hip, and
+// lanczos_resize_tensor_norm16.hip and lanczos_resize_tensor_norm32.hip (16-bit and float samples into normalised tensor elements,
+// lanczos_tensor_norm; their converter is in lanczos_resize_tensor_norm.hip).  The filter of a request (LANCZOS_RESIZE_FILTER)
 // only changes the tables; LANCZOS_FILTER_NEAREST has index tables and a kernel of its own (lanczos_resize_nearest.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -170,7 +172,7 @@ struct ResizeState {
     int force = LANCZOS_RESIZE_AUTO;
     ScratchBlock scratch;                    // intermediate of the two-pass path (the rows the vertical taps read x out_w x C)
     ScratchBlock reduced;                    // the reduced frames of a request with reducing_gap, tightly packed
-    ScratchBlock tensor_bytes;               // the byte result of a tensor request on the converted route (k_rs_to_tensor reads it)
+    ScratchBlock tensor_bytes;               // the sample result of a tensor request on the converted route (k_rs_to_tensor[_norm] reads it)
     ScratchBlock packed;                     // the tightly packed copy of a source on the PACKED route (k_rs_pack_source writes it)
     ScratchBlock unpacked;                   // the tightly packed result of a destination on the UNPACKED route (k_rs_unpack_dest reads it)
     ScratchBlock stage_in, stage_out;        // staging of lanczos_resize_host
@@ -192,6 +194,11 @@ struct RsTensorOut {
     const uint8_t* d_flip = nullptr;   // one byte per frame, XORed with flip; read when the kernels run
     // set by tensor_validate: false where the view is the identity without flips, which runs the kernels without a map
     bool mapped = false;
+    // lanczos_tensor_norm (16-bit and float samples): no table; the element is computed from the sample, cvt(((float)P / div -
+    // mean) / std) per OUTPUT channel.  format: LANCZOS_TENSOR_F32 / _BF16 / _F16, elem its width
+    bool norm = false;
+    int format = 0;
+    float div[4] = {1, 1, 1, 1}, mean[4] = {0, 0, 0, 0}, std[4] = {1, 1, 1, 1};
     // dst[c] in byte c: the output channel source channel c goes to, 255 where none does
     unsigned dst_of_src() const {
         unsigned dst = 0xffffffffu;
@@ -221,6 +228,9 @@ int tensor_validate(const lanczos_resize_desc* d, const lanczos_resize_window* w
 // ... and of lanczos_tensor_view
 int tensor_view_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_tensor_view* v,
                          RsTensorOut* lay);
+// ... and of lanczos_tensor_norm: the view's rules without a table, for wide samples only
+int tensor_norm_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_tensor_norm* n,
+                         RsTensorOut* lay);
 size_t tensor_extent_bytes(const lanczos_resize_desc* d, const RsWindow& win, const RsTensorOut& t);
 void tensor_lut_normalize(int channels, const float* mean, const float* std, float* lut);
 // float32 -> bfloat16 (LANCZOS_TENSOR_BF16) or float16 (LANCZOS_TENSOR_F16) words, round to nearest even; false: no such format
@@ -230,6 +240,10 @@ bool tensor_lut_convert16(const float* in, int n, int format, uint16_t* out);
 // (t.mapped: through the channel map and the frames' flips)
 hipError_t rs_to_tensor_launch(const uint8_t* src, size_t src_fs, uint8_t* out, size_t out_fs, int w, int h, int channels,
                                const RsTensorOut& t, int frames, hipStream_t stream);
+// k_rs_to_tensor_norm (lanczos_resize_tensor_norm.hip): tightly packed interleaved samples of `bps` bytes (2 or 4; frames `src_fs`
+// apart at any multiple of bps, nothing read outside a frame) -> strided elements computed from them, through the map and flips
+hipError_t rs_to_tensor_norm_launch(const uint8_t* src, size_t src_fs, uint8_t* out, size_t out_fs, int w, int h, int channels,
+                                    int bps, const RsTensorOut& t, int frames, hipStream_t stream);
 // k_rs_to_tensor_crops (lanczos_resize_tensor_crops.hip): frame f's w x h window at its clamped origin of interleaved byte frames
 // of src_w x src_h pixels (rows src_pitch bytes apart, any alignment) -> strided elements through the map, flips and table
 hipError_t rs_to_tensor_crops_launch(const uint8_t* src, size_t src_fs, size_t src_pitch, int src_w, int src_h, uint8_t* out,
@@ -316,10 +330,11 @@ struct RsRouteQuery {
     const RsSource* src = nullptr;            // NULL: the call has no source
     const RsDest* dst = nullptr;              // NULL: the call has no destination
     const ResizeAxisHost *H = nullptr, *V = nullptr;   // the tables of r->inner's axes; read where both passes run
+    bool norm = false;                        // a lanczos_tensor_norm request: wide samples, elements computed (tensor is set too)
 };
 enum RsMain { kRsMainFused, kRsMainNearest, kRsMainCopy, kRsMainCrop, kRsMainNone, kRsMainPassH, kRsMainPassV, kRsMainTwoPass,
               kRsMainVFirst };
-enum RsFollower { kRsFollowNone, kRsFollowToTensor, kRsFollowCropsScratch, kRsFollowCropsDirect };
+enum RsFollower { kRsFollowNone, kRsFollowToTensor, kRsFollowCropsScratch, kRsFollowCropsDirect, kRsFollowToTensorNorm };
 // Everything a call does, in the order it does it: pack, reduce, main, follower, unpack.  A scratch block of ResizeState that
 // the call uses has its frame stride and size here; 0 bytes: not used
 struct RsRoute {
@@ -338,6 +353,7 @@ struct RsRoute {
     struct Block {
         size_t fs = 0, bytes = 0;
     } packed, reduced, tensor_bytes, unpacked, scratch;
+    bool follow_src = false;   // kRsFollowToTensorNorm behind kRsMainNone: the follower reads the source frames themselves
 };
 // The one decision.  Pure host code: no HIP call, no device state, no ResizeState
 RsRoute rs_route(const RsRouteQuery& q);
@@ -390,6 +406,8 @@ constexpr int kRsPlanar = 32;
 constexpr int kRsRowShift = 64;
 // + kRsPlanarOut: the destination is planar (RsDest::planar, bytes out): the vertical pass stores one dword per plane
 constexpr int kRsPlanarOut = 128;
+// kRsNorm alone: wide samples (BPS 2 or 4) into computed elements, lanczos_tensor_norm; the element format is an argument
+constexpr int kRsNorm = 256;
 template <int BPS, int TENSOR>
 hipError_t rs_launch_fused(const RsFusedLaunch& c);
 

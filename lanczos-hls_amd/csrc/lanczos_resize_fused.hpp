@@ -14,7 +14,8 @@
 //                   lanczos_resize_source_tensor16.hip (8-bit from a planar source: TENSOR with kRsPlanar, and ALPHA over rows
 //                   pitched off a dword: with kRsRowShift), lanczos_resize_dest.hip and lanczos_resize_dest_source.hip (8-bit
 //                   into a planar destination: kRsPlanarOut, the second with kRsPlanar), lanczos_resize16.hip and
-//                   lanczos_resize32.hip.
+//                   lanczos_resize32.hip, lanczos_resize_tensor_norm16.hip and lanczos_resize_tensor_norm32.hip (16-bit and float
+//                   samples into computed elements: kRsNorm).
 #pragma once
 #include "lanczos_alpha.hpp"
 #include "lanczos_resize.hpp"
@@ -94,6 +95,33 @@ struct RsSample<4> {
     }
     static __device__ __forceinline__ uint32_t store(double ss) { return __float_as_uint(__double2float_rn(ss)); }
 };
+
+// ---- the element of a lanczos_tensor_norm request -----------------------------------------------------------------------
+//
+// cvt(((float)P / div - mean) / std) for one stored sample, in the words of `format` (LANCZOS_TENSOR_*; uniform over a launch).
+// Three IEEE operations, each rounded on its own: the build passes -ffp-contract=off and no fast-math flag, so `/` is the
+// correctly rounded division (v_div_scale / v_div_fmas / v_div_fixup) and nothing is folded, and the kernel mode keeps
+// denormals.  bfloat16 is rounded on the bits as tensor_lut_convert16 rounds it; float16 by the conversion instruction, which is
+// round to nearest even with subnormals kept and overflow to inf, as that function is.
+__device__ __forceinline__ uint32_t rs_norm_elem(float v, float div, float mean, float std, int format) {
+    const float e = ((v / div) - mean) / std;
+    const uint32_t b = __float_as_uint(e);
+    if (format == LANCZOS_TENSOR_F32) return b;
+    if (format == LANCZOS_TENSOR_BF16) {
+        if ((b & 0x7fffffffu) > 0x7f800000u) return (b >> 16) | 0x7fc0u;
+        return (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;
+    }
+    const _Float16 h = (_Float16)e;
+    return (uint32_t)__builtin_bit_cast(unsigned short, h);
+}
+// one of four launch arguments by a lane's channel
+__device__ __forceinline__ float rs_norm_pick(const float (&p)[4], int c) { return c == 0 ? p[0] : c == 1 ? p[1] : c == 2 ? p[2] : p[3]; }
+// the float a stored sample is: exact for 16 bits, the sample itself for a float
+template <int BPS>
+__device__ __forceinline__ float rs_norm_sample(uint32_t stored) {
+    if constexpr (BPS == 4) return __uint_as_float(stored);
+    else return (float)stored;
+}
 
 // ---- two-pass path ---------------------------------------------------------------------------------------------------
 
@@ -177,6 +205,17 @@ struct RsFusedTensorCrops : RsFusedTensorMap {
                                // kernel runs and clamped to [0, max_x0] x [0, max_y0]
     int max_x0, max_y0;        // the full output's size less the window's
 };
+// kRsNorm (wide samples into computed elements, lanczos_tensor_norm): `out` / `out_fs` are the element frames; always mapped
+template <class KT>
+struct RsFusedNorm : RsFused<KT> {
+    int cs, rs, ps;          // channel, row and pixel strides in elements
+    unsigned extent_bytes;   // of one element frame, below 2^31
+    unsigned dst;            // byte c: the output channel of source channel c, 255 where it is dropped
+    int flip;                // bit 0: mirror x, bit 1: mirror y
+    const uint8_t* d_flip;   // NULL, or one byte per frame of the launch, XORed with flip; read when the kernel runs
+    int format;              // LANCZOS_TENSOR_F32 / _BF16 / _F16
+    float div[4], mean[4], std[4];   // by SOURCE channel: those of the output channel it goes to
+};
 // ... + kRsPlanar: the source is planar.  in_pitch is then the pitch of a plane row; behind the fields of the instance without it
 template <class Base>
 struct RsFusedPlanar : Base {
@@ -193,8 +232,10 @@ struct RsFusedPlanarOut : Base {
 // the argument of k_rs_fused<..., TENSOR> for coefficients KT
 template <int TENSOR, class KT>
 using RsFusedArgsPacked = std::conditional_t<
+    (TENSOR & kRsNorm) != 0, RsFusedNorm<KT>,
+    std::conditional_t<
     (TENSOR & kRsCrops) != 0, RsFusedTensorCrops,
-    std::conditional_t<(TENSOR & kRsMapped) != 0, RsFusedTensorMap, std::conditional_t<TENSOR != 0, RsFusedTensor, RsFused<KT>>>>;
+    std::conditional_t<(TENSOR & kRsMapped) != 0, RsFusedTensorMap, std::conditional_t<TENSOR != 0, RsFusedTensor, RsFused<KT>>>>>;
 template <int TENSOR, class KT>
 using RsFusedArgsIn = std::conditional_t<(TENSOR & kRsPlanar) != 0, RsFusedPlanar<RsFusedArgsPacked<(TENSOR & ~kRsPlanar), KT>>,
                                          RsFusedArgsPacked<(TENSOR & ~kRsRowShift), KT>>;
@@ -314,6 +355,13 @@ struct RsStrip {
 // pointers by it: from there on it is the kernel of the window at that origin.  The plan is the largest over every origin
 // (rs_fused_plan_crops), so staging rows and ring hold whichever the frame has.
 //
+// TENSOR = kRsNorm (lanczos_tensor_norm, 16-bit and float samples; instances of their own, lanczos_resize_tensor_norm16/32.hip,
+// the wide instances that store samples are as they were): only the epilogue differs.  After the vertical chain a lane holds
+// SPD sums of consecutive samples of the strip's row; each is turned into the sample Pillow stores (S::store), then into the
+// element by three float operations and a rounding (rs_norm_elem), and stored at oc * cs + y * rs + x * ps through the channel
+// map and the flips, which every instance has (the identity view runs the identity map).  The element format is a launch
+// argument, uniform over the wave, not a template parameter: one instance per (width, C, K) and a third of the build.
+//
 // TENSOR with kRsPlanar (a planar source, 8-bit, C = 3 or 4; instances of their own once more, lanczos_resize_source*.hip): only
 // the staging loads differ.  A thread takes four pixels of a staged row: one dword from each of the C plane rows, transposed into
 // C interleaved dwords (rs_interleave4) and written to LDS as dwords.  A plane row starts at any byte, another residue per plane
@@ -337,7 +385,9 @@ struct RsStrip {
 template <class S, int C, int K, bool ALPHA = false, int TENSOR = 0>
 __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
     RsFusedArgs<TENSOR, typename S::coeff_t> g) {
-    constexpr int EB = TENSOR & ~(kRsMapped | kRsCrops | kRsPlanar | kRsRowShift | kRsPlanarOut);   // bytes of a stored element
+    constexpr int EB = TENSOR & ~(kRsMapped | kRsCrops | kRsPlanar | kRsRowShift | kRsPlanarOut | kRsNorm);   // bytes of a stored table element
+    constexpr bool NORM = (TENSOR & kRsNorm) != 0;   // wide samples into computed elements: its own epilogue, nothing else differs
+    static_assert(!NORM || (TENSOR == kRsNorm && S::BPS > 1), "norm: 16-bit or float samples, no other flag");
     constexpr bool PLANAR = (TENSOR & kRsPlanar) != 0;
     constexpr bool ROWSHIFT = (TENSOR & kRsRowShift) != 0;
     constexpr bool PLANAR_OUT = (TENSOR & kRsPlanarOut) != 0;
@@ -412,12 +462,13 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
     unsigned out_bytes = (unsigned)(g.out_h * g.out_pitch);
     if constexpr (EB != 0) out_bytes = g.extent_bytes;
     if constexpr (PLANAR_OUT) out_bytes = g.dst_bytes;
+    if constexpr (NORM) out_bytes = g.extent_bytes;
     const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(fout, 0, out_bytes, 0x00020000);
     const bool out_aligned = (((uintptr_t)fout | (unsigned)g.out_pitch | (unsigned)(x0 * CB)) & 3) == 0;
     const int valid_bytes = sw * (kDwordSamples ? C : CB);   // of the strip's row; dwords where a sample is one
     // MAPPED: the frame's flips turned into a base and two signed strides (elements)
     [[maybe_unused]] int t_base = 0, t_rs = 0, t_ps = 0;
-    if constexpr (MAPPED) {
+    if constexpr (MAPPED || NORM) {
         const int m = g.flip ^ (g.d_flip ? __builtin_amdgcn_readfirstlane((int)g.d_flip[blockIdx.y]) : 0);
         t_rs = (m & 2) ? -g.rs : g.rs, t_ps = (m & 1) ? -g.ps : g.ps;
         t_base = ((m & 2) ? (g.out_h - 1) * g.rs : 0) + ((m & 1) ? (g.out_w - 1) * g.ps : 0);
@@ -587,7 +638,25 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
                 if (++slot == g.ring_rows) slot = 0;
             }
             const int b0 = kDwordSamples ? dcol : dcol * 4;   // the lane's place in the strip's row, as valid_bytes counts
-            if constexpr (EB != 0) {
+            if constexpr (NORM) {
+                // the lane's SPD sums are consecutive samples of the strip's row: each becomes the sample Pillow stores, then the
+                // element, and goes out on its own -- no exchange, a lane already holds whole samples
+#pragma unroll
+                for (int s = 0; s < SPD; s++) {
+                    const int j = dcol * SPD + s;
+                    if (j < sw * C) {
+                        const int xo = j / C, c = j - xo * C;
+                        const int oc = (int)((g.dst >> (8 * c)) & 255u);
+                        if (oc < 4) {
+                            const float v = rs_norm_sample<BPS>(S::store(s == 0 ? a0 : a1));
+                            const uint32_t e = rs_norm_elem(v, rs_norm_pick(g.div, c), rs_norm_pick(g.mean, c), rs_norm_pick(g.std, c), g.format);
+                            const int to = t_base + oc * g.cs + o * t_rs + (x0 + xo) * t_ps;
+                            if (g.format == LANCZOS_TENSOR_F32) __builtin_amdgcn_raw_buffer_store_b32(e, orsrc, to * 4, 0, 0);
+                            else __builtin_amdgcn_raw_buffer_store_b16((uint16_t)e, orsrc, to * 2, 0, 0);
+                        }
+                    }
+                }
+            } else if constexpr (EB != 0) {
                 // the dword is put together with v_perm_b32, not with shifts: followed by the exchange below, the shifted form
                 // is compiled to v_ashr_pk_u8_i32, whose 16-bit result leaves the upper half of its register as it was while
                 // the code behind it takes that half for zero (seen on the device: bytes 2 and 3 with bits of a0 in them)
@@ -735,7 +804,18 @@ hipError_t rs_launch_fused(const RsFusedLaunch& c) {
         g.chan_stride = (int)c.src->chan_stride;
         g.src_bytes = (unsigned)((c.d->channels - 1) * c.src->chan_stride + (c.d->in_h - 1) * c.src->row_stride + c.d->in_w);
     }
-    if constexpr ((TENSOR & ~(kRsPlanar | kRsRowShift | kRsPlanarOut)) != 0) {
+    constexpr bool NORM = (TENSOR & kRsNorm) != 0;
+    if constexpr (NORM) {
+        const RsTensorOut& t = c.tc->t;
+        g.cs = (int)t.chan_stride, g.rs = (int)t.row_stride, g.ps = (int)t.pix_stride;   // extent below 2^31 bytes
+        g.extent_bytes = (unsigned)c.tc->extent_bytes;
+        g.dst = t.dst_of_src(), g.flip = t.flip & 3, g.format = t.format;
+        for (int oc = 0; oc < t.out_channels; oc++) {
+            const int sc = t.src_channel[oc];
+            g.div[sc] = t.div[oc], g.mean[sc] = t.mean[oc], g.std[sc] = t.std[oc];
+        }
+    }
+    if constexpr ((TENSOR & ~(kRsPlanar | kRsRowShift | kRsPlanarOut | kRsNorm)) != 0) {
         g.lut = (const uint32_t*)c.tc->t.d_lut;
         g.cs = (int)c.tc->t.chan_stride, g.rs = (int)c.tc->t.row_stride, g.ps = (int)c.tc->t.pix_stride;   // extent below 2^31 bytes
         g.extent_bytes = (unsigned)c.tc->extent_bytes;
@@ -746,7 +826,7 @@ hipError_t rs_launch_fused(const RsFusedLaunch& c) {
         const int nf = std::min(65535, c.frames - f0);
         g.in = c.in + (size_t)f0 * c.in_fs;
         g.out = c.out + (size_t)f0 * c.out_fs;
-        if constexpr ((TENSOR & kRsMapped) != 0) g.d_flip = c.tc->t.d_flip ? c.tc->t.d_flip + f0 : nullptr;   // a byte per frame
+        if constexpr ((TENSOR & kRsMapped) != 0 || NORM) g.d_flip = c.tc->t.d_flip ? c.tc->t.d_flip + f0 : nullptr;   // a byte per frame
         if constexpr ((TENSOR & kRsCrops) != 0) g.d_origin = c.tc->d_origin + 2 * (size_t)f0;                  // a pair per frame
         const dim3 grid(fp.strips * fp.chunks, nf);
         bool launched = false;
@@ -783,5 +863,7 @@ extern template hipError_t rs_launch_fused<1, kRsPlanarOut>(const RsFusedLaunch&
 extern template hipError_t rs_launch_fused<1, kRsPlanar + kRsPlanarOut>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<2, 0>(const RsFusedLaunch&);
 extern template hipError_t rs_launch_fused<4, 0>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<2, kRsNorm>(const RsFusedLaunch&);
+extern template hipError_t rs_launch_fused<4, kRsNorm>(const RsFusedLaunch&);
 
 }  // namespace lz

@@ -261,7 +261,7 @@ int tensor_validate(const lanczos_resize_desc* d, const lanczos_resize_window* w
     if (rc != LANCZOS_OK) return rc;
     RsWindow w;   // the frame the strides describe
     if ((rc = resize_window_resolve(d, win, &w)) != LANCZOS_OK) return rc;
-    if (!t || !t->d_lut) return LANCZOS_ERR_BAD_ARG;
+    if (!t || (!t->d_lut && !t->norm)) return LANCZOS_ERR_BAD_ARG;   // (a norm request has no table)
     for (int i = 0; i < 4; i++)
         if (reserved[i] != 0) return LANCZOS_ERR_BAD_ARG;
     // the channel map: out_channels 0 is every channel in its place.  Injective, and nothing set behind out_channels
@@ -280,8 +280,9 @@ int tensor_validate(const lanczos_resize_desc* d, const lanczos_resize_window* w
         if (oc < t->out_channels && sc != oc) identity = false;
     }
     t->mapped = !identity || t->flip != 0 || t->d_flip != nullptr;
-    // a table per 16-bit value and float inputs are out of scope
-    if (d->reserved[0] & (LANCZOS_RESIZE_U16 | LANCZOS_RESIZE_F32)) return LANCZOS_ERR_UNSUPPORTED;
+    // a table serves 8-bit samples and no others; 16-bit and float samples have the request that computes its elements
+    // (lanczos_tensor_norm, tensor_norm_validate), which in turn takes no 8-bit ones
+    if (((d->reserved[0] & (LANCZOS_RESIZE_U16 | LANCZOS_RESIZE_F32)) != 0) != t->norm) return LANCZOS_ERR_UNSUPPORTED;
     struct Dim {
         int64_t stride, extent;
     } dims[3] = {{t->chan_stride, t->out_channels}, {t->row_stride, w.h}, {t->pix_stride, w.w}};
@@ -313,6 +314,24 @@ int tensor_view_validate(const lanczos_resize_desc* d, const lanczos_resize_wind
         }
     }
     return tensor_validate(d, win, v ? lay : nullptr, v ? v->reserved : nullptr);
+}
+
+int tensor_norm_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_tensor_norm* n,
+                         RsTensorOut* lay) {
+    if (n) {
+        const bool known = n->format == LANCZOS_TENSOR_F32 || n->format == LANCZOS_TENSOR_BF16 || n->format == LANCZOS_TENSOR_F16;
+        *lay = RsTensorOut{nullptr, n->chan_stride, n->row_stride, n->pix_stride, n->format == LANCZOS_TENSOR_F32 ? 4 : 2, n->out_channels};
+        for (int c = 0; c < 4; c++)
+            lay->src_channel[c] = n->src_channel[c], lay->div[c] = n->div[c], lay->mean[c] = n->mean[c], lay->std[c] = n->std[c];
+        lay->flip = n->flip, lay->d_flip = n->d_flip;
+        lay->norm = true, lay->format = n->format;
+        // an unknown format and 0 channels (no view, as above) are refused once the descriptor has been looked at
+        if (!known || n->out_channels == 0) {
+            const int rc = resize_validate(d);
+            return rc != LANCZOS_OK ? rc : LANCZOS_ERR_BAD_ARG;
+        }
+    }
+    return tensor_validate(d, win, n ? lay : nullptr, n ? n->reserved : nullptr);
 }
 
 int resize_source_resolve(const lanczos_resize_desc* d, const lanczos_resize_source* src, RsSource* s) {
@@ -475,6 +494,8 @@ int resize_crops_validate(const lanczos_resize_desc* d, const lanczos_resize_cro
 // the tables are those of its full axes: a window changes which slice of them the plan and every launch see, nothing else.
 //   tensor   where the fused kernel runs it stores the elements itself (LANCZOS_TENSOR_FUSED); everything else writes its bytes
 //            to context scratch and k_rs_to_tensor follows
+//   norm     a tensor request of wide samples: the same rule with the kRsNorm instances and k_rs_to_tensor_norm, which reads the
+//            caller's frames where no pass runs and there is no window
 //   crops    q.win is (0, 0, w, h).  The fused kernel runs on the plan that holds for every origin; everything else resizes the
 //            whole output into context scratch and k_rs_to_tensor_crops gathers each frame's window from it -- or from the
 //            caller's frames where no pass runs
@@ -554,9 +575,12 @@ RsRoute rs_route(const RsRouteQuery& q) {
     const RsWindow& win = rt.win;
     if (q.tensor) {
         rt.tensor_route = t_fused ? LANCZOS_TENSOR_FUSED : LANCZOS_TENSOR_CONVERTED;
-        rt.follower = crops_direct ? kRsFollowCropsDirect : crops_gather ? kRsFollowCropsScratch : t_fused ? kRsFollowNone : kRsFollowToTensor;
-        if (!t_fused && !crops_direct) {
-            rt.tensor_bytes.fs = ((size_t)win.w * win.h * C + 3) & ~(size_t)3;
+        rt.follower = crops_direct ? kRsFollowCropsDirect : crops_gather ? kRsFollowCropsScratch : t_fused ? kRsFollowNone
+                      : q.norm     ? kRsFollowToTensorNorm : kRsFollowToTensor;
+        // a norm request that changes neither axis and has no window: the caller's frames are the samples, read where they lie
+        rt.follow_src = q.norm && !t_fused && !nearest && !need_h && !need_v && win.whole(d);
+        if (!t_fused && !crops_direct && !rt.follow_src) {
+            rt.tensor_bytes.fs = ((size_t)win.w * win.h * C * (q.norm ? B : 1) + 3) & ~(size_t)3;
             rt.tensor_bytes.bytes = (size_t)frames * rt.tensor_bytes.fs;
         }
     }
@@ -581,17 +605,18 @@ RsRoute rs_route(const RsRouteQuery& q) {
     if (fused) {
         const int t = t_fused ? q.elem : 0, tm = t_fused ? q.elem + kRsMapped : 0;
         rt.main = kRsMainFused, rt.kernel = LANCZOS_KERNEL_RESIZE_FUSED;
-        rt.flags = rt.dst_direct && dst->planar ? kRsPlanarOut + (src && src->planar ? kRsPlanar : 0)
+        rt.flags = t_fused && q.norm           ? kRsNorm
+                   : rt.dst_direct && dst->planar ? kRsPlanarOut + (src && src->planar ? kRsPlanar : 0)
                    : src && src->planar      ? tm + kRsPlanar
                    : src && rowshift         ? tm + kRsRowShift
                    : t_fused && crops        ? tm + kRsCrops
                    : t_fused && q.mapped     ? tm
                                              : t;
-        rt.bps = rt.flags ? 1 : (int)B;   // every instance with a flag is an 8-bit one
+        rt.bps = rt.flags && rt.flags != kRsNorm ? 1 : (int)B;   // every instance with another flag is an 8-bit one
     } else if (nearest) {
         rt.main = kRsMainNearest, rt.kernel = LANCZOS_KERNEL_RESIZE_NEAREST;
     } else if (!need_h && !need_v) {   // Pillow returns a copy (also of RGBA: no premultiply round trip); a window crops it
-        rt.main = crops_direct ? kRsMainNone : win.whole(d) ? kRsMainCopy : kRsMainCrop;
+        rt.main = crops_direct || rt.follow_src ? kRsMainNone : win.whole(d) ? kRsMainCopy : kRsMainCrop;
     } else if (v_first) {   // win.h rows of the source's full width in between
         rt.main = kRsMainVFirst;
         rt.scratch.fs = (size_t)win.h * d->in_w * C * B;

@@ -65,6 +65,19 @@ T1h, T2h, T4h and TPh are T1, T2, T4 and TP to bfloat16 (lanczos_resize_tensor16
   f32           the float32 tensor call alone
 Frame 0 of fused, converted and f32_cast are compared bit for bit before timing; a last line gives the ratios.
 
+N16, N16h, N32 and NP16 are normalised-tensor workloads of wide samples (lanczos_resize_tensor_norm_device: uint16 or float32
+frames resized straight into normalised tensors; --only N16,N16h,N32,NP16; a build with the entry).  N16: 32 frames of
+3840x2160 -> 1920x1080, three 16-bit channels, to CHW float32; N16h the same to bfloat16; N32 the same shape with float samples;
+NP16: 256 one-channel 16-bit frames of 512x512 -> 224x224 to float32.  Routes, alternating region by region:
+  fused          the call under RESIZE_AUTO: the fused kernel computes and stores the elements
+  converted      the same call under RESIZE_CONVERT: the same sample resize into context scratch, then k_rs_to_tensor_norm
+  samples_torch  the sample resize, then .permute().float().div(div).sub(mean).div(std)[.to(bfloat16)] with torch on the same
+                 stream, div / mean / std given as tensors so that torch divides
+  samples        the sample resize alone
+  parent_samples the sample resize alone on another build of the library (--parent-lib PATH: the parent commit's)
+  copy           a device-to-device copy of one step's element output
+Frame 0 of fused, converted and samples_torch are compared bit for bit before timing; a last line gives the ratios.
+
 WIN1, WIN1h, WIN2 and WINC are resize-and-crop workloads (a window of the output, lanczos_resize_window_device; --only
 WIN1,WIN1h,WIN2,WINC; a build with the entry).  WIN1: 256 frames of 500x375 RGB8 -> 341x256, window center_window(341, 256, 224, 224), bytes out.  WIN1h:
 the same into normalised bfloat16 CHW.  WIN2: 32 frames of 3840x2160 -> 1920x1080, window the centre 1280x720.  WINC: 256 frames of 341x256 at their own size (neither
@@ -541,6 +554,89 @@ def run_tensor16(name, args, ctx, torch):
                       "fused_over_converted": round(us["fused"] / us["converted"], 3),
                       "fused_over_f32": round(us["fused"] / us["f32"], 3), "measured": True}), flush=True)
     del xs, ys, wide
+    torch.cuda.empty_cache()
+
+
+NORM_WORKLOADS = {   # name: (in_w, in_h, out_w, out_h, channels, frames, sample bits, element dtype)
+    "N16": (3840, 2160, 1920, 1080, 3, 32, 16, "float32"),
+    "N16h": (3840, 2160, 1920, 1080, 3, 32, 16, "bfloat16"),
+    "N32": (3840, 2160, 1920, 1080, 3, 32, 32, "float32"),
+    "NP16": (512, 512, 224, 224, 1, 256, 16, "float32"),
+}
+
+
+def run_norm(name, args, ctx, torch, parent):
+    iw, ih, ow, oh, c, f, bits, dtype = NORM_WORKLOADS[name]
+    B, E = bits // 8, 4 if dtype == "float32" else 2
+    in_fb, out_fb = iw * ih * c, ow * oh * c   # samples / elements of a frame
+    sets = max(2, -(-2 * 256 * 2 ** 20 // (f * in_fb * B)) + 1)
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    if bits == 16:   # every 16-bit pattern, held as int16 and read as uint16
+        xs = [torch.randint(-32768, 32768, (f * in_fb,), dtype=torch.int16, device="cuda", generator=gen) for _ in range(sets)]
+    else:
+        xs = [torch.rand(f * in_fb, dtype=torch.float32, device="cuda", generator=gen) for _ in range(sets)]
+    edt = torch.float32 if E == 4 else torch.bfloat16
+    bits_t = torch.int32 if E == 4 else torch.int16
+    ys = [torch.empty(f * out_fb, dtype=edt, device="cuda") for _ in range(sets)]
+    tmp = torch.empty(f * out_fb, dtype=torch.uint16 if bits == 16 else torch.float32, device="cuda")
+    d = L.resize_desc(iw, ih, ow, oh, c, bits=16 if bits == 16 else 8, f32=bits == 32)
+    div = (65535.0,) * c if bits == 16 else (1.0,) * c
+    mean_v, std_v = IMAGENET_MEAN[:c], IMAGENET_STD[:c]
+    nrm = L.tensor_norm(L.tensor_strides("chw", ow, oh, c), div, mean_v, std_v, dtype, tuple(range(c)))
+    shape = (1, c, 1, 1)
+    t_div = torch.tensor(div, device="cuda").view(shape)
+    t_mean = torch.tensor(mean_v, device="cuda").view(shape)
+    t_std = torch.tensor(std_v, device="cuda").view(shape)
+    s = torch.cuda.current_stream().cuda_stream
+    seen = {}
+
+    def norm(path):
+        def step(i):
+            ctx.resize_force(path)
+            ctx.resize_tensor_norm_device(d, xs[i % sets].data_ptr(), ys[i % sets].data_ptr(), f, nrm, stream=s)
+            seen[path] = ctx.last_tensor_route()
+            return ys[i % sets][:out_fb].view(bits_t)
+        return step
+
+    def samples(i):
+        ctx.resize_force(L.RESIZE_AUTO)
+        ctx.resize_device(d, xs[i % sets].data_ptr(), tmp.data_ptr(), f, 0, 0, s)
+        return tmp[:out_fb].view(torch.int16 if bits == 16 else torch.int32)
+
+    def samples_torch(i):
+        samples(i)
+        t = tmp.view(f, oh, ow, c).permute(0, 3, 1, 2).float().div(t_div).sub(t_mean).div(t_std)
+        t = t if E == 4 else t.to(torch.bfloat16)
+        return t.contiguous().view(-1)[:out_fb].view(bits_t)
+
+    def parent_samples(i):
+        parent.resize_device(d, xs[i % sets].data_ptr(), tmp.data_ptr(), f, s)
+        return tmp[:out_fb].view(torch.int16 if bits == 16 else torch.int32)
+
+    def copy(i):
+        ys[(i + 1) % sets].copy_(ys[i % sets], non_blocking=True)
+        return ys[(i + 1) % sets][:out_fb].view(bits_t)
+
+    routes = {"fused": norm(L.RESIZE_AUTO), "converted": norm(L.RESIZE_CONVERT), "samples_torch": samples_torch, "samples": samples}
+    if parent is not None:
+        routes["parent_samples"] = parent_samples
+    routes["copy"] = copy
+    inb = {rn: B * f * in_fb for rn in routes}
+    outb = {rn: E * f * out_fb for rn in routes}
+    outb["samples"] = outb["parent_samples"] = B * f * out_fb
+    inb["copy"] = E * f * out_fb
+    us = run_routes(name, f"{iw}x{ih}->{ow}x{oh} C{c} {'u16' if bits == 16 else 'f32'} -> {dtype} chw", f, routes, inb, outb, args, ctx, torch,
+                    check=(("fused", "converted"), ("fused", "samples_torch")))
+    ctx.resize_force(L.RESIZE_AUTO)
+    if (seen[L.RESIZE_AUTO], seen[L.RESIZE_CONVERT]) != (L.TENSOR_FUSED, L.TENSOR_CONVERTED):
+        raise SystemExit(f"{name}: routes {seen}")
+    base = us.get("parent_samples", us["samples"])
+    print(json.dumps({"workload": name, "fused_over_converted": round(us["fused"] / us["converted"], 3),
+                      "fused_over_samples_torch": round(us["fused"] / us["samples_torch"], 3),
+                      "fused_minus_sample_resize_us": round(us["fused"] - base, 2), "sample_resize": "parent" if parent else "this build",
+                      "torch_stages_us": round(us["samples_torch"] - us["samples"], 2),
+                      "copy_of_element_output_us": round(us["copy"], 2), "measured": True}), flush=True)
+    del xs, ys, tmp
     torch.cuda.empty_cache()
 
 
@@ -1060,7 +1156,7 @@ def main():
     ap.add_argument("--routes", default=",".join(ROUTES))
     ap.add_argument("--pillow", action="store_true")
     ap.add_argument("--parent-lib", default=None,
-                    help="another build of liblanczos_hip.so for the parent_bytes route of T* and the parent_full route of WIN*")
+                    help="another build of liblanczos_hip.so for the parent_bytes route of T*, the parent_samples route of N* and the parent_full route of WIN*")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -1068,7 +1164,9 @@ def main():
     ctx = L.Context(0)
     parent = ParentLib(args.parent_lib) if args.parent_lib else None
     for name in args.only.split(","):
-        if name in WINDOW_WORKLOADS:
+        if name in NORM_WORKLOADS:
+            run_norm(name, args, ctx, torch, parent)
+        elif name in WINDOW_WORKLOADS:
             run_window(name, args, ctx, torch, parent)
         elif name in CROPS_WORKLOADS:
             run_crops(name, args, ctx, torch)
