@@ -867,6 +867,93 @@ int lanczos_resize_tensor_norm_host(lanczos_ctx* ctx, const lanczos_resize_desc*
                                     const lanczos_resize_window* win, const lanczos_resize_source* src,
                                     const lanczos_tensor_norm* n, const void* in, void* out, int frames);
 
+/* ---- resize YCbCr frames (I420, 4:2:2, 4:4:4 planes, NV12, NV21) straight into RGB bytes and tensors ----
+ * A frame holds in_w x in_h luma samples and two chroma planes subsampled by 2^sub_x x 2^sub_y (sub_x, sub_y 0 or 1) of
+ * cw x ch samples, cw = (in_w + sub_x) >> sub_x, ch = (in_h + sub_y) >> sub_y: centre siting (JPEG, MPEG-1), the full chroma
+ * plane covers the full luma plane, odd sizes included.  THE CONTRACT is a composition of Pillow calls, byte for byte:
+ *   Yo  = Image.fromarray(Y,  "L").resize((out_w, out_h), filt, box=bl, reducing_gap=g)
+ *   Cbo = Image.fromarray(Cb, "L").resize((out_w, out_h), filt, box=bc, reducing_gap=g)
+ *   Cro = Image.fromarray(Cr, "L").resize((out_w, out_h), filt, box=bc, reducing_gap=g)
+ *   rgb = Image.merge("YCbCr", (Yo, Cbo, Cro)).convert("RGB")
+ * bl is the request's box in luma pixels (opts NULL: the whole frame) and bc is bl with x times 2^-sub_x and y times 2^-sub_y,
+ * computed on the doubles of bl, so exactly.  Every plane obeys the rules of a one-channel resize on its own: an axis of a plane
+ * that keeps its size over the whole axis skips its pass (4:2:0 with out == in copies luma and still resizes chroma), and a
+ * reducing_gap reduces each plane as Pillow would reduce that plane.  The window is the same output rectangle for the three
+ * planes.  Left-sited chroma (MPEG-2) would need a negative box offset, which Pillow refuses: it is not expressed here.
+ * The descriptor describes the RGB result: channels = 3, in_w x in_h the luma size, every filter (LANCZOS_FILTER_NEAREST
+ * included) and every a.  LANCZOS_RESIZE_ALPHA, _U16 or _F32 in its flag word is LANCZOS_ERR_UNSUPPORTED (no wide chroma:
+ * P010 / P016 are not built).  There is no crop origin per frame and no lanczos_resize_dest on these entries.
+ * The colour conversion is a table the caller passes, int32 t[3][3][256]:
+ *   out[c] = clip8((t[c][0][y] + t[c][1][cb] + t[c][2][cr]) >> 6)           (>> arithmetic, clip8 to 0 .. 255)
+ * Its indices are bytes, so no content can address out of bounds; entries must keep the sum inside int32.  lanczos_ycc_table fills
+ * it for three standards.  LANCZOS_YCC_JFIF is Pillow's convert("RGB") exactly: t[c][0][y] = 64 y and
+ * T(k, i) = (int)(k * (i - 128) * 64 + 0.5) (double, truncation toward zero) with k = 1.402 (R from Cr), -0.34414 and -0.71414
+ * (G from Cb, Cr), 1.772 (B from Cb).  LANCZOS_YCC_BT601 / _BT709 are the limited-range matrices: ky = 255/219, kc = 255/224,
+ * (Kr, Kb) = (0.299, 0.114) / (0.2126, 0.0722), Kg = 1 - Kr - Kb; luma entries (int)(ky (i - 16) 64 + 0.5) + 32 (the shift
+ * then rounds), chroma entries (int)(k (i - 128) 64 + 0.5) with k = 2 (1 - Kr) kc (R from Cr), -2 (1 - Kb) Kb / Kg kc and
+ * -2 (1 - Kr) Kr / Kg kc (G from Cb, Cr), 2 (1 - Kb) kc (B from Cb).  Their result is within 1 of the float64 matrix result
+ * rounded to nearest and clipped.  Any other matrix or channel order (full-range BT.709, BGR rows) is the caller's own table.
+ * Routes: the planes are resized by the one-channel requests of lanczos_resize_source_device (same routes, same kernels:
+ * lanczos_resize_window_plan_host of the one-channel request of a plane says which) into context scratch, and one streaming
+ * launch (k_rs_ycc_merge) converts the three planes into RGB bytes or tensor elements.  The chroma of a planar layout takes two
+ * resize calls; the interleaved chroma of NV12 / NV21 is split into planes by one streaming launch (k_rs_ycc_split) and then
+ * takes one.  lanczos_resize_force applies to every plane.  The scratch lives as the other scratch of a context does: one stream
+ * at a time per context, a captured launch pins its block, a captured graph must not outlive its context. */
+#define LANCZOS_YCC_PLANAR 0   /* three planes: Y at the frame base, Cb at cb_offset, Cr at cr_offset */
+#define LANCZOS_YCC_NV12 1     /* Y plane, then one plane of interleaved (Cb, Cr) pairs at cb_offset; sub_x must be 1 */
+#define LANCZOS_YCC_NV21 2     /* ... of (Cr, Cb) pairs */
+#define LANCZOS_YCC_JFIF 0     /* the standards of lanczos_ycc_table */
+#define LANCZOS_YCC_BT601 1
+#define LANCZOS_YCC_BT709 2
+typedef struct lanczos_ycc_source {
+    int64_t y_row_stride, c_row_stride;   /* bytes; of NV12 / NV21 c_row_stride is that of the interleaved rows (>= 2 cw) */
+    int64_t cb_offset, cr_offset;         /* bytes from the frame base to the first chroma sample; NV12 / NV21: both the same */
+    int32_t layout, sub_x, sub_y;
+    int32_t reserved[5];                  /* must be 0 */
+} lanczos_ycc_source;
+/* Host only: the tight layout -- Y, then Cb, then Cr (or the interleaved plane), rows packed.  LANCZOS_ERR_BAD_ARG as validate. */
+int lanczos_ycc_source_init(lanczos_ycc_source* src, const lanczos_resize_desc* d, int layout, int sub_x, int sub_y);
+/* Host only.  LANCZOS_ERR_UNSUPPORTED: LANCZOS_RESIZE_ALPHA, _U16 or _F32 in d.  LANCZOS_ERR_BAD_ARG: a null pointer, what
+ * lanczos_resize_validate refuses, channels other than 3, an unknown layout, a subsampling other than 0 or 1, NV12 / NV21 with
+ * sub_x != 1 or with two different offsets, a row stride below a plane's row (or above 2^40), a negative offset, planes that
+ * overlap (a plane is its rows times its row stride: every plane must hold its full pitched rows), a non-zero reserved word.
+ * The frame's extent is the end of its last plane: in_frame_stride 0 stands for it, a smaller one is LANCZOS_ERR_BAD_ARG. */
+int lanczos_ycc_source_validate(const lanczos_resize_desc* d, const lanczos_ycc_source* src);
+/* Host only: t[3][3][256] of a standard (above).  LANCZOS_ERR_BAD_ARG: a null t, an unknown standard. */
+int lanczos_ycc_table(int standard, int32_t* t);
+/* Device buffers, asynchronous on `stream`.  d_table: device, 3 * 3 * 256 int32, read WHEN THE KERNELS RUN.  d_in: any byte
+ * address, frames in_frame_stride bytes apart (any residue).  d_out: tightly packed interleaved RGB bytes of the window (win NULL:
+ * the whole output), w * h * 3 per frame; d_out and out_frame_stride (0 = w * h * 3 rounded up to a multiple of 4) must be
+ * multiples of 4, else LANCZOS_ERR_BAD_ARG.  Nothing is written past a frame's w * h * 3 bytes.  opts and win may be NULL. */
+int lanczos_resize_ycc_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                              const lanczos_resize_window* win, const lanczos_ycc_source* src, const int32_t* d_table,
+                              const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride,
+                              void* stream);
+/* ... into tensor elements: with (R, G, B) the bytes above as source channels 0, 1, 2, everything is lanczos_tensor_view's
+ * contract and lanczos_resize_tensor_view_device's rules (table by output channel, strides in elements, channel map, flip and
+ * d_flip, the overlap rule, the extent, elements the strides do not name left untouched). */
+int lanczos_resize_ycc_tensor_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                     const lanczos_resize_window* win, const lanczos_ycc_source* src, const int32_t* d_table,
+                                     const lanczos_tensor_view* v, const void* d_in, void* d_out, int frames,
+                                     size_t in_frame_stride, size_t out_frame_stride, void* stream);
+/* Host buffers, a HOST table (and for the tensor form a HOST element table and HOST flips in v); synchronous.  Frames lie back
+ * to back: the source's extent apart, w * h * 3 bytes apart (no padding), element frames one extent apart.  Elements of `out` the
+ * strides do not name keep their contents. */
+int lanczos_resize_ycc_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                            const lanczos_resize_window* win, const lanczos_ycc_source* src, const int32_t* table, const void* in,
+                            void* out, int frames);
+int lanczos_resize_ycc_tensor_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                   const lanczos_resize_window* win, const lanczos_ycc_source* src, const int32_t* table,
+                                   const lanczos_tensor_view* v, const void* in, void* out, int frames);
+/* What the last successful lanczos_resize_ycc_* call on the context launched: the LANCZOS_KERNEL_* of the luma resize and of
+ * the chroma resize (LANCZOS_KERNEL_NONE: a plain copy), whether k_rs_ycc_split ran, and the number of launches (resize
+ * kernels, copies, split and merge).  All zero before any.  LANCZOS_ERR_BAD_ARG: a null pointer. */
+typedef struct lanczos_ycc_info {
+    int32_t luma_kernel, chroma_kernel, split, launches;
+    int32_t reserved[4];
+} lanczos_ycc_info;
+int lanczos_last_ycc_info(const lanczos_ctx* ctx, lanczos_ycc_info* info);
+
 /* ---- reduce by whole factors (Pillow's Image.reduce((fx, fy), box), an exact integer box average) ----
  * 8-bit, 1, 3 or 4 independent interleaved channels.  box = (x0, y0, x1, y1), integers with 0 <= x0 < x1 <= in_w and the same
  * for y; NULL = the whole frame.  The output is ceil((x1 - x0) / fx) x ceil((y1 - y0) / fy) pixels, tightly packed rows.

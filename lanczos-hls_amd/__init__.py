@@ -88,8 +88,16 @@ ABI_SYMBOLS = [
     "lanczos_last_dest_route",
     "lanczos_tensor_norm_init", "lanczos_resize_tensor_norm_validate", "lanczos_resize_tensor_norm_device",
     "lanczos_resize_tensor_norm_host",
+    "lanczos_ycc_source_init", "lanczos_ycc_source_validate", "lanczos_ycc_table", "lanczos_resize_ycc_device",
+    "lanczos_resize_ycc_tensor_device", "lanczos_resize_ycc_host", "lanczos_resize_ycc_tensor_host", "lanczos_last_ycc_info",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
+YCC_PLANAR, YCC_NV12, YCC_NV21 = 0, 1, 2   # lanczos_ycc_source.layout
+YCC_JFIF, YCC_BT601, YCC_BT709 = 0, 1, 2   # the standards of lanczos_ycc_table
+YCC_STANDARDS = {"jfif": YCC_JFIF, "bt601": YCC_BT601, "bt709": YCC_BT709}
+# the frame layouts Context.resize_ycc knows by name: (layout, sub_x, sub_y)
+YCC_LAYOUTS = {"nv12": (YCC_NV12, 1, 1), "nv21": (YCC_NV21, 1, 1), "i420": (YCC_PLANAR, 1, 1), "i422": (YCC_PLANAR, 1, 0),
+               "i444": (YCC_PLANAR, 0, 0)}
 
 
 class Route(collections.namedtuple("Route", "main prefix launches prefix_seen")):
@@ -225,6 +233,24 @@ class ResizeDest(ctypes.Structure):
     y * row_stride + x * pix_stride of its frame.  Interleaved with pitched rows, or planar (8-bit)."""
     _fields_ = [("row_stride", ctypes.c_int64), ("chan_stride", ctypes.c_int64), ("pix_stride", ctypes.c_int32),
                 ("reserved", ctypes.c_int32 * 3)]
+
+
+class YccSource(ctypes.Structure):
+    """lanczos_ycc_source -- where the planes of a YCbCr frame lie: in_w x in_h luma samples at the frame base, rows
+    y_row_stride bytes apart, and chroma subsampled by 2^sub_x x 2^sub_y at cb_offset / cr_offset, rows c_row_stride bytes apart
+    (YCC_PLANAR), or interleaved in one plane at cb_offset == cr_offset (YCC_NV12: Cb first, YCC_NV21: Cr first)."""
+    _fields_ = [("y_row_stride", ctypes.c_int64), ("c_row_stride", ctypes.c_int64), ("cb_offset", ctypes.c_int64),
+                ("cr_offset", ctypes.c_int64), ("layout", ctypes.c_int32), ("sub_x", ctypes.c_int32), ("sub_y", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 5)]
+
+
+class YccInfoC(ctypes.Structure):   # include/lanczos_hip.h: lanczos_ycc_info
+    _fields_ = [(n, ctypes.c_int32) for n in ("luma_kernel", "chroma_kernel", "split", "launches")] + [("reserved", ctypes.c_int32 * 4)]
+
+
+class YccInfo(collections.namedtuple("YccInfo", "luma_kernel chroma_kernel split launches")):
+    """lanczos_last_ycc_info: KERNEL_* of the luma and of the chroma resize of the last resize_ycc call (KERNEL_NONE: a copy),
+    whether the interleaved chroma was split into planes first, and the number of launches of the call."""
 
 
 FLIP_H, FLIP_V = 1, 2   # the bits of lanczos_tensor_view.flip and of a d_flip byte
@@ -402,6 +428,18 @@ def _lib():
             L.lanczos_resize_tensor_norm_device.argtypes = [c_void_p, PRD, PRO, PRW, PRS, PTN, c_void_p, c_void_p, c_int, c_size_t,
                                                             c_size_t, c_void_p]
             L.lanczos_resize_tensor_norm_host.argtypes = [c_void_p, PRD, PRO, PRW, PRS, PTN, c_void_p, c_void_p, c_int]
+        if hasattr(L, "lanczos_resize_ycc_device"):   # (nor YCbCr frames)
+            PYS = ctypes.POINTER(YccSource)
+            L.lanczos_ycc_source_init.argtypes = [PYS, PRD, c_int, c_int, c_int]
+            L.lanczos_ycc_source_validate.argtypes = [PRD, PYS]
+            L.lanczos_ycc_table.argtypes = [c_int, c_void_p]
+            L.lanczos_resize_ycc_device.argtypes = [c_void_p, PRD, PRO, PRW, PYS, c_void_p, c_void_p, c_void_p, c_int, c_size_t,
+                                                    c_size_t, c_void_p]
+            L.lanczos_resize_ycc_tensor_device.argtypes = [c_void_p, PRD, PRO, PRW, PYS, c_void_p, PTV, c_void_p, c_void_p, c_int,
+                                                           c_size_t, c_size_t, c_void_p]
+            L.lanczos_resize_ycc_host.argtypes = [c_void_p, PRD, PRO, PRW, PYS, c_void_p, c_void_p, c_void_p, c_int]
+            L.lanczos_resize_ycc_tensor_host.argtypes = [c_void_p, PRD, PRO, PRW, PYS, c_void_p, PTV, c_void_p, c_void_p, c_int]
+            L.lanczos_last_ycc_info.argtypes = [c_void_p, ctypes.POINTER(YccInfoC)]
         L.lanczos_strerror.restype = ctypes.c_char_p
         L.lanczos_version.argtypes = []
         L.lanczos_version.restype = ctypes.c_char_p
@@ -684,6 +722,68 @@ def resize_dest_validate(desc, dest, window=None):
     """lanczos_resize_dest_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the layout is refused."""
     _check(_lib().lanczos_resize_dest_validate(ctypes.byref(desc), _window_ref(desc, window),
                                                ctypes.byref(dest) if dest is not None else None), "lanczos_resize_dest_validate")
+
+
+def ycc_source(desc, layout="nv12", sub_x=None, sub_y=None, y_row_stride=None, c_row_stride=None, cb_offset=None, cr_offset=None):
+    """A validated YccSource for the frames `desc` resizes (desc: three channels, in_w x in_h the luma size).  layout: a name
+    of YCC_LAYOUTS ("nv12", "nv21", "i420", "i422", "i444"), or YCC_PLANAR / YCC_NV12 / YCC_NV21 with sub_x and sub_y given.
+    The defaults are the tight layout (Y, then Cb, then Cr or the interleaved plane, rows packed); strides and offsets in
+    bytes replace them one by one.  ycc_frame_bytes gives the frame's extent."""
+    if isinstance(layout, str):
+        if layout.lower() not in YCC_LAYOUTS:
+            raise LanczosError(ERR_BAD_ARG, f"ycc_source: layout is one of {', '.join(YCC_LAYOUTS)}, not {layout!r}")
+        code, sx, sy = YCC_LAYOUTS[layout.lower()]
+        sub_x, sub_y = (sx if sub_x is None else sub_x), (sy if sub_y is None else sub_y)
+    else:
+        code = int(layout)
+        if sub_x is None or sub_y is None:
+            raise LanczosError(ERR_BAD_ARG, "ycc_source: a layout given by its code needs sub_x and sub_y")
+    s = YccSource()
+    _check(_lib().lanczos_ycc_source_init(ctypes.byref(s), ctypes.byref(desc), code, int(sub_x), int(sub_y)), "lanczos_ycc_source_init")
+    for name, v in (("y_row_stride", y_row_stride), ("c_row_stride", c_row_stride), ("cb_offset", cb_offset), ("cr_offset", cr_offset)):
+        if v is not None:
+            setattr(s, name, int(v))
+    if code != YCC_PLANAR and cb_offset is not None and cr_offset is None:
+        s.cr_offset = s.cb_offset
+    _check(_lib().lanczos_ycc_source_validate(ctypes.byref(desc), ctypes.byref(s)), "lanczos_ycc_source_validate")
+    return s
+
+
+def ycc_source_validate(desc, source):
+    _check(_lib().lanczos_ycc_source_validate(ctypes.byref(desc), ctypes.byref(source) if source is not None else None),
+           "lanczos_ycc_source_validate")
+
+
+def ycc_chroma_size(desc, source):
+    """(cw, ch): the size of the chroma planes"""
+    return (desc.in_w + source.sub_x) >> source.sub_x, (desc.in_h + source.sub_y) >> source.sub_y
+
+
+def ycc_frame_bytes(desc, source):
+    """The extent of one frame in `source`'s layout: the end of its last plane, every plane holding its full pitched rows."""
+    cw, ch = ycc_chroma_size(desc, source)
+    return max(desc.in_h * source.y_row_stride, source.cb_offset + ch * source.c_row_stride, source.cr_offset + ch * source.c_row_stride)
+
+
+def ycc_table(standard="jfif"):
+    """int32 [3][3][256], t[c][k][v]: out[c] = clip8((t[c][0][y] + t[c][1][cb] + t[c][2][cr]) >> 6).  "jfif" is Pillow's
+    convert("RGB") exactly; "bt601" and "bt709" are the limited-range matrices (lanczos_ycc_table).  Any other matrix or
+    channel order is an array of this shape built by the caller."""
+    code = YCC_STANDARDS.get(standard.lower()) if isinstance(standard, str) else int(standard)
+    if code is None:
+        raise LanczosError(ERR_BAD_ARG, f"ycc_table: standard is one of {', '.join(YCC_STANDARDS)}, not {standard!r}")
+    t = np.empty((3, 3, 256), dtype=np.int32)
+    _check(_lib().lanczos_ycc_table(code, t.ctypes.data), "lanczos_ycc_table")
+    return t
+
+
+def _ycc_table_arg(standard, table, what):
+    if table is None:
+        return ycc_table(standard)
+    table = np.ascontiguousarray(table)
+    if table.dtype != np.int32 or table.shape != (3, 3, 256):
+        raise LanczosError(ERR_BAD_ARG, f"{what}: the colour table is int32 [3][3][256]")
+    return table
 
 
 def _planar_frames(img, what):
@@ -1403,6 +1503,116 @@ class Context:
                                                         ctypes.byref(source) if source is not None else None, ctypes.byref(norm),
                                                         d_in, d_out, frames, in_frame_stride, out_frame_stride, stream),
                "lanczos_resize_tensor_norm_device")
+
+    def _ycc_host_args(self, frames, in_w, in_h, out_w, out_h, layout, filter, a, source, what):
+        d = resize_desc(in_w, in_h, out_w, out_h, 3, a, filter=filter)
+        src = source if source is not None else ycc_source(d, layout)
+        ycc_source_validate(d, src)
+        x = np.ascontiguousarray(frames)
+        n = ycc_frame_bytes(d, src)
+        if x.dtype != np.uint8 or x.ndim not in (1, 2) or x.shape[-1] != n:
+            raise LanczosError(ERR_BAD_ARG, f"{what}: expected uint8 [{n}] or [N][{n}], the frames as they lie in memory")
+        return d, src, x, (x if x.ndim == 2 else x[None])
+
+    def resize_ycc(self, frames, in_w, in_h, out_w, out_h, layout="nv12", standard="jfif", filter=FILTER_LANCZOS, a=3, box=None,
+                   reducing_gap=None, window=None, table=None, source=None):
+        """YCbCr frames -> uint8 [N][h][w][3] (RGB under the standard tables), byte for byte Pillow's three "L" resizes (chroma
+        with the box scaled to its plane), Image.merge("YCbCr", ...) and convert("RGB") under standard="jfif".
+        frames: uint8 [N][B] or [B], each frame its B bytes as they lie in memory: the tight layout of `layout` ("nv12", "nv21",
+        "i420", "i422", "i444": Y, then Cb and Cr planes or the interleaved plane), or whatever `source` (ycc_source)
+        describes.  in_w x in_h: the luma size; chroma planes are ceil(in_w / 2) x ceil(in_h / 2) under 4:2:0, centre-sited.
+        box in luma pixels, reducing_gap, filter, a and window = (x0, y0, w, h) as Context.resize.  table: an int32 [3][3][256]
+        of the caller's instead of ycc_table(standard)."""
+        d, src, x0, x = self._ycc_host_args(frames, in_w, in_h, out_w, out_h, layout, filter, a, source, "resize_ycc")
+        t = _ycc_table_arg(standard, table, "resize_ycc")
+        win = resize_window(d, window)
+        out = np.empty((x.shape[0], win.h, win.w, 3), dtype=np.uint8)
+        _check(_lib().lanczos_resize_ycc_host(self._h, ctypes.byref(d), _opts_ref(d, box, reducing_gap, None),
+                                              ctypes.byref(win) if window is not None else None, ctypes.byref(src), t.ctypes.data,
+                                              x.ctypes.data, out.ctypes.data, x.shape[0]), "lanczos_resize_ycc_host")
+        return out if x0.ndim == 2 else out[0]
+
+    def resize_ycc_tensor(self, frames, in_w, in_h, out_w, out_h, layout="nv12", standard="jfif", mean=None, std=None, lut=None,
+                          dtype="float32", tensor_layout="chw", channels_out=None, flip=None, filter=FILTER_LANCZOS, a=3, box=None,
+                          reducing_gap=None, window=None, table=None, source=None):
+        """As resize_ycc, into a normalised tensor: lut[oc][byte] of the RGB bytes resize_ycc returns, float32 [N][C][h][w]
+        (tensor_layout="chw") or [N][h][w][C] ("hwc"); dtype, mean / std or lut, channels_out and flip as Context.resize_tensor
+        takes them (bfloat16 comes back as uint16 patterns)."""
+        d, src, x0, x = self._ycc_host_args(frames, in_w, in_h, out_w, out_h, layout, filter, a, source, "resize_ycc_tensor")
+        t = _ycc_table_arg(standard, table, "resize_ycc_tensor")
+        wide = dtype == "float32"
+        if not wide:
+            _tensor16_format(dtype, "resize_ycc_tensor")
+        f = x.shape[0]
+        channels_out = tuple(int(v) for v in channels_out) if channels_out is not None else (0, 1, 2)
+        c = len(channels_out)
+        if not 1 <= c <= 3:
+            raise LanczosError(ERR_BAD_ARG, "resize_ycc_tensor: channels_out names 1 to 3 source channels")
+        if lut is None:
+            if c == 2:
+                m, s = (None if v is None else np.broadcast_to(np.asarray(v, dtype=np.float32), (2,)) for v in (mean, std))
+                lut = np.concatenate([normalize_lut(1, None if m is None else m[k], None if s is None else s[k], dtype)
+                                      for k in range(2)])
+            else:
+                lut = normalize_lut(c, mean, std, dtype)
+        elif mean is not None or std is not None:
+            raise LanczosError(ERR_BAD_ARG, "resize_ycc_tensor: a table or mean / std, not both")
+        lut = np.ascontiguousarray(lut)
+        if lut.dtype not in ((np.float32,) if wide else (np.uint16, np.float16)) or lut.size != c * 256:
+            raise LanczosError(ERR_BAD_ARG, f"resize_ycc_tensor: the table is {'float32' if wide else 'uint16 or float16'} [{c}][256]")
+        flips = None
+        if flip is not None and not isinstance(flip, str):
+            flips = np.ascontiguousarray(flip)
+            if flips.shape != (f,) or flips.dtype.kind not in "iub" or ((flips < 0) | (flips > 3)).any():
+                raise LanczosError(ERR_BAD_ARG, f"resize_ycc_tensor: flip is 'h', 'v', 'hv' or {f} integers 0 .. 3, one per frame")
+            flips = flips.astype(np.uint8)
+        elif flip not in _FLIP_NAMES:
+            raise LanczosError(ERR_BAD_ARG, f"resize_ycc_tensor: flip is 'h', 'v', 'hv' or one integer per frame, not {flip!r}")
+        win = resize_window(d, window)
+        v = tensor_view(lut.ctypes.data, tensor_strides(tensor_layout, win.w, win.h, c), 4 if wide else 2, channels_out,
+                        0 if flips is not None else flip, flips.ctypes.data if flips is not None else None)
+        shape = (f, c, win.h, win.w) if tensor_layout == "chw" else (f, win.h, win.w, c)
+        out = np.empty(shape, dtype=np.float32 if wide else np.uint16)
+        _check(_lib().lanczos_resize_ycc_tensor_host(self._h, ctypes.byref(d), _opts_ref(d, box, reducing_gap, None),
+                                                     ctypes.byref(win) if window is not None else None, ctypes.byref(src),
+                                                     t.ctypes.data, ctypes.byref(v), x.ctypes.data, out.ctypes.data, f),
+               "lanczos_resize_ycc_tensor_host")
+        out = out if wide else _tensor16_array(out, dtype)
+        return out if x0.ndim == 2 else out[0]
+
+    def resize_ycc_device(self, desc, source, d_table, d_in, d_out, frames, in_frame_stride=0, out_frame_stride=0, stream=None,
+                          box=None, reducing_gap=None, opts=None, window=None):
+        """Device pointers, asynchronous on `stream`: YCbCr frames at d_in in `source`'s layout (any byte address, frames
+        in_frame_stride bytes apart, 0 = the layout's extent) -> tightly packed RGB bytes of the window at d_out.  d_out and
+        out_frame_stride (0 = w * h * 3 rounded up to a multiple of 4) are multiples of 4.  d_table: device, int32 [3][3][256]
+        (ycc_table), read when the kernels run."""
+        _check(_lib().lanczos_resize_ycc_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
+                                                _window_ref(desc, window), ctypes.byref(source) if source is not None else None,
+                                                d_table, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream),
+               "lanczos_resize_ycc_device")
+
+    def resize_ycc_tensor_device(self, desc, source, d_table, d_in, d_out, frames, d_lut, strides, in_frame_stride=0,
+                                 out_frame_stride=0, stream=None, box=None, reducing_gap=None, opts=None, dtype="float32",
+                                 window=None, channels_out=None, flip=None, d_flip=None):
+        """... -> tensor elements at d_out: strides (or a ready TensorView), d_lut, dtype, channels_out, flip and d_flip as
+        Context.resize_tensor_device takes them, over the RGB bytes resize_ycc_device stores as source channels 0, 1, 2."""
+        if isinstance(strides, TensorView):
+            v = strides
+        else:
+            if dtype != "float32":
+                _tensor16_format(dtype, "resize_ycc_tensor_device")
+            v = tensor_view(d_lut, strides, 4 if dtype == "float32" else 2, channels_out if channels_out is not None else (0, 1, 2),
+                            flip or 0, d_flip)
+        _check(_lib().lanczos_resize_ycc_tensor_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
+                                                       _window_ref(desc, window), ctypes.byref(source) if source is not None else None,
+                                                       d_table, ctypes.byref(v), d_in, d_out, frames, in_frame_stride,
+                                                       out_frame_stride, stream), "lanczos_resize_ycc_tensor_device")
+
+    def last_ycc_info(self):
+        """YccInfo of the last successful resize_ycc* call on the context (all zero before any)."""
+        info = YccInfoC()
+        _check(_lib().lanczos_last_ycc_info(self._h, ctypes.byref(info)), "lanczos_last_ycc_info")
+        return YccInfo(info.luma_kernel, info.chroma_kernel, bool(info.split), info.launches)
 
     def last_tensor_route(self):
         """TENSOR_FUSED (the resize kernel stored the floats), TENSOR_CONVERTED (bytes to scratch, then a conversion launch),

@@ -65,6 +65,7 @@ struct lanczos_ctx {
     int last_tensor_route = 0;   // lanczos_last_tensor_route: LANCZOS_TENSOR_* of the last call, 0 unless it was a tensor call
     int last_source_route = 0;   // lanczos_last_source_route: LANCZOS_SOURCE_* of the last call that had a source layout
     int last_dest_route = 0;     // lanczos_last_dest_route: LANCZOS_DEST_* of the last call that had a destination layout
+    lanczos_ycc_info last_ycc{};  // lanczos_last_ycc_info: what the last successful lanczos_resize_ycc_* call launched
     int last_route = 0;      // lanczos_last_route: main kernel, prefix route and launch count of the last upscale call
     int route_launches = 0;  // launches of the call in flight (reset by the entry points, counted where a launch is issued)
     int route_seen = 0;      // prefix routes of those launches, one bit each
@@ -1440,6 +1441,90 @@ int lanczos_resize_dest_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, con
 }
 
 int lanczos_last_dest_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_dest_route : 0; }
+
+// ---- YCbCr frames into RGB bytes and tensors (lanczos_resize_ycc.hip) ------------------------------------------------------
+int lanczos_ycc_source_init(lanczos_ycc_source* src, const lanczos_resize_desc* d, int layout, int sub_x, int sub_y) {
+    if (!src) return LANCZOS_ERR_BAD_ARG;
+    const int rc = lz::ycc_desc_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    if ((sub_x | sub_y) & ~1) return LANCZOS_ERR_BAD_ARG;
+    const int64_t cw = (d->in_w + sub_x) >> sub_x, ch = (d->in_h + sub_y) >> sub_y, luma = (int64_t)d->in_w * d->in_h;
+    *src = lanczos_ycc_source{};
+    src->layout = layout, src->sub_x = sub_x, src->sub_y = sub_y;
+    src->y_row_stride = d->in_w, src->cb_offset = luma;
+    if (layout == LANCZOS_YCC_PLANAR) src->c_row_stride = cw, src->cr_offset = luma + cw * ch;
+    else src->c_row_stride = 2 * cw, src->cr_offset = luma;
+    lz::YccSource s;
+    return lz::ycc_source_resolve(d, src, &s);
+}
+
+int lanczos_ycc_source_validate(const lanczos_resize_desc* d, const lanczos_ycc_source* src) {
+    const int rc = lz::ycc_desc_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    lz::YccSource s;
+    return lz::ycc_source_resolve(d, src, &s);
+}
+
+int lanczos_ycc_table(int standard, int32_t* t) { return t && lz::ycc_table(standard, t) ? LANCZOS_OK : LANCZOS_ERR_BAD_ARG; }
+
+int lanczos_last_ycc_info(const lanczos_ctx* ctx, lanczos_ycc_info* info) {
+    if (!ctx || !info) return LANCZOS_ERR_BAD_ARG;
+    *info = ctx->last_ycc;
+    return LANCZOS_OK;
+}
+
+extern "C++" {
+// every lanczos_resize_ycc_* entry: v NULL stores RGB bytes
+static int resize_ycc(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                      const lanczos_ycc_source* src, const int32_t* table, const lanczos_tensor_view* v, bool tensor,
+                      const ResizeBufs& b) {
+    if (!ctx || b.null() || !table) return LANCZOS_ERR_BAD_ARG;
+    lz::YccRequest q;
+    q.d = d, q.o = o, q.win = win, q.table = table, q.tensor = tensor;
+    q.in = b.in, q.out = b.out, q.frames = b.frames;
+    q.in_frame_stride = b.in_frame_stride, q.out_frame_stride = b.out_frame_stride, q.stream = (hipStream_t)b.stream;
+    int rc = lz::ycc_desc_validate(d);
+    if (rc == LANCZOS_OK) rc = lz::ycc_source_resolve(d, src, &q.s);
+    if (rc == LANCZOS_OK && tensor) rc = lz::tensor_view_validate(d, win, v, &q.t);
+    if (rc != LANCZOS_OK) return rc;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    if (b.host && !ctx->stream) return LANCZOS_ERR_HIP;
+    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
+    route_begin(ctx);
+    if (b.host) q.stream = ctx->stream;
+    q.last_hip = &ctx->last_hip;
+    rc = b.host ? lz::resize_ycc_host(ctx->resize, q) : lz::resize_ycc_device(ctx->resize, q);
+    if (rc == LANCZOS_OK) ctx->last_ycc = q.info, ctx->last_kernel = q.info.luma_kernel;
+    return rc;
+}
+}   // extern "C++"
+
+int lanczos_resize_ycc_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                              const lanczos_resize_window* win, const lanczos_ycc_source* src, const int32_t* d_table,
+                              const void* d_in, void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride,
+                              void* stream) {
+    return resize_ycc(ctx, d, opts, win, src, d_table, nullptr, false, {d_in, d_out, frames, in_frame_stride, out_frame_stride, stream, false});
+}
+
+int lanczos_resize_ycc_tensor_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                     const lanczos_resize_window* win, const lanczos_ycc_source* src, const int32_t* d_table,
+                                     const lanczos_tensor_view* v, const void* d_in, void* d_out, int frames,
+                                     size_t in_frame_stride, size_t out_frame_stride, void* stream) {
+    return resize_ycc(ctx, d, opts, win, src, d_table, v, true, {d_in, d_out, frames, in_frame_stride, out_frame_stride, stream, false});
+}
+
+int lanczos_resize_ycc_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                            const lanczos_resize_window* win, const lanczos_ycc_source* src, const int32_t* table, const void* in,
+                            void* out, int frames) {
+    return resize_ycc(ctx, d, opts, win, src, table, nullptr, false, host_bufs(in, out, frames));
+}
+
+int lanczos_resize_ycc_tensor_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
+                                   const lanczos_resize_window* win, const lanczos_ycc_source* src, const int32_t* table,
+                                   const lanczos_tensor_view* v, const void* in, void* out, int frames) {
+    return resize_ycc(ctx, d, opts, win, src, table, v, true, host_bufs(in, out, frames));
+}
 
 int lanczos_reduce_size(int in_w, int in_h, int fx, int fy, const int32_t* box, int* out_w, int* out_h) {
     if (!out_w || !out_h) return LANCZOS_ERR_BAD_ARG;

@@ -389,6 +389,12 @@ int resize_device(ResizeState* st, RsRequest& q) {
         }
     if (rt.unpacked.bytes && e == hipSuccess)
         e = rs_unpack_dest_launch(out, step_fs, (uint8_t*)q.out, out_fs, q.dc.s, win.w, win.h, C, (int)B, frames, stream);
+    {   // the launches that went out, for the callers that report them (frames go 65535 per launch)
+        const int groups = (frames + 65534) / 65535;
+        const int main_n = rt.main == kRsMainNone ? 0 : rt.main == kRsMainCopy ? 1
+                           : (rt.main == kRsMainTwoPass || rt.main == kRsMainVFirst) ? 2 * groups : groups;
+        q.launches = main_n + groups * ((int)rt.pack + (int)rt.reduce + (int)(rt.follower != kRsFollowNone) + (int)(rt.unpacked.bytes != 0));
+    }
     *q.last_kernel = rt.kernel;
     q.tc.route = rt.tensor_route, q.sc.route = rt.source_route, q.dc.route = rt.dest_route;
     if (e != hipSuccess) {

@@ -10,7 +10,8 @@
 // and lanczos_resize_source_tensor16.hip (those of a planar or oddly pitched source), lanczos_resize_dest.hip and
 // lanczos_resize_dest_source.hip (8-bit into a planar destination), lanczos_resize16.hip and lanczos_resize32.hip, and
 // lanczos_resize_tensor_norm16.hip and lanczos_resize_tensor_norm32.hip (16-bit and float samples into normalised tensor elements,
-// lanczos_tensor_norm; their converter is in lanczos_resize_tensor_norm.hip).  The filter of a request (LANCZOS_RESIZE_FILTER)
+// lanczos_tensor_norm; their converter is in lanczos_resize_tensor_norm.hip).  YCbCr frames (lanczos_resize_ycc_*) are three
+// one-channel requests through resize_device with a split in front and a merge behind, in lanczos_resize_ycc.hip.  The filter of a request (LANCZOS_RESIZE_FILTER)
 // only changes the tables; LANCZOS_FILTER_NEAREST has index tables and a kernel of its own (lanczos_resize_nearest.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -176,6 +177,8 @@ struct ResizeState {
     ScratchBlock packed;                     // the tightly packed copy of a source on the PACKED route (k_rs_pack_source writes it)
     ScratchBlock unpacked;                   // the tightly packed result of a destination on the UNPACKED route (k_rs_unpack_dest reads it)
     ScratchBlock stage_in, stage_out;        // staging of lanczos_resize_host
+    ScratchBlock ycc_in;                     // the Cb and Cr planes k_rs_ycc_split makes of interleaved chroma (lanczos_resize_ycc.hip)
+    ScratchBlock ycc_planes;                 // the resized Y, Cb and Cr planes k_rs_ycc_merge reads
     explicit ResizeState(Lifetime* l) : life(l), axes(l, 32) {}
 };
 
@@ -308,6 +311,7 @@ struct RsRequest {
     size_t in_frame_stride = 0, out_frame_stride = 0;   // bytes; 0: the frames lie back to back
     hipStream_t stream = nullptr;
     int *last_kernel = nullptr, *last_hip = nullptr;     // as in lanczos_ctx
+    int launches = 0;      // out: the launches (kernels and copies) resize_device issued for the request
     // the optional parts, each read only where its flag is set and its `route` written once the launches are out
     bool tensor = false;   // tc: `out` holds element frames.  Crops: win is (0, 0, w, h) and tc.d_origin the origins
     bool source = false;   // sc: the frames at `in` lie in that layout
@@ -420,5 +424,41 @@ hipError_t rs_nearest_launch(const uint8_t* in, uint8_t* out, int in_w, int out_
 // (the window's first byte; rows in_pitch bytes apart) to tightly packed rows at `out`, every frame in one launch.
 hipError_t rs_crop_launch(const uint8_t* in, uint8_t* out, size_t in_pitch, size_t row_bytes, int rows, int frames,
                           size_t in_fs, size_t out_fs, hipStream_t stream);
+
+// ---- YCbCr frames (lanczos_resize_ycc.hip): three one-channel requests through resize_device, a split in front of interleaved
+// chroma and the merge through the colour table behind them.  A lanczos_ycc_source resolved by ycc_source_resolve:
+struct YccSource {
+    int layout = 0, sx = 0, sy = 0;
+    int cw = 0, ch = 0;                     // the chroma planes' size
+    size_t y_rs = 0, c_rs = 0;              // row strides (bytes); c_rs of NV12 / NV21 is the interleaved rows'
+    size_t cb_off = 0, cr_off = 0;          // NV12 / NV21: both the interleaved plane's
+    size_t extent = 0;                      // of one frame: the end of its last plane
+    bool interleaved() const { return layout != LANCZOS_YCC_PLANAR; }
+};
+// d validated for these entries (three channels, 8-bit, no alpha) by ycc_desc_validate
+int ycc_desc_validate(const lanczos_resize_desc* d);
+int ycc_source_resolve(const lanczos_resize_desc* d, const lanczos_ycc_source* src, YccSource* s);
+bool ycc_table(int standard, int32_t* t);
+// One call of the lanczos_resize_ycc_* entries, filled in by lanczos_api.hip
+struct YccRequest {
+    const lanczos_resize_desc* d = nullptr;       // validated (ycc_desc_validate)
+    const lanczos_resize_opts* o = nullptr;
+    const lanczos_resize_window* win = nullptr;
+    YccSource s;                                  // resolved
+    const int32_t* table = nullptr;               // [3][3][256]
+    const void* in = nullptr;
+    void* out = nullptr;
+    int frames = 0;
+    size_t in_frame_stride = 0, out_frame_stride = 0;
+    hipStream_t stream = nullptr;
+    int* last_hip = nullptr;
+    bool tensor = false;
+    RsTensorOut t;                                // validated (tensor_view_validate) where tensor is set
+    lanczos_ycc_info info{};                      // out, on LANCZOS_OK
+};
+// ctx->mu held, device set: device pointers, asynchronous
+int resize_ycc_device(ResizeState* st, YccRequest& q);
+// host buffers, a host colour table, and of a tensor request a host element table and host flips; synchronous
+int resize_ycc_host(ResizeState* st, YccRequest& q);
 
 }  // namespace lz

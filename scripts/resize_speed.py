@@ -141,6 +141,13 @@ route of a library built with EXTRA=-DLZ_RS_PLANAR_OUT_DWORDS and loaded through
 
 --pillow adds Pillow's single-core time of one frame of each workload (if Pillow imports; else "not available"); for U1 and
 U4 that is the time of one I;16 plane (a frame has three), for F1 and F4 that of one F plane.
+
+YC1, YC2 and YC3 (--only YC1,YC2,YC3) are YCbCr frames (lanczos_resize_ycc_*): 32 NV12 frames 3840x2160 -> 1920x1080 to
+normalised bfloat16 CHW, 256 I420 frames 500x375 -> 341x256 with the centre 224x224 window to float32 CHW, 32 NV12 frames
+1920x1080 -> 3840x2160 to RGB bytes.  Routes, alternating region by region: `ycc`, the one call; `torch_convert`, what it
+replaces (repeat_interleave of the chroma, the float matrix, round, clamp, cast, repack, then the existing RGB call);
+`rgb_floor`, the existing RGB call alone on frames converted beforehand (--parent-lib: on that build); `luma_only`, the luma
+plane's one-channel resize alone.  A summary line carries the ratios, the kernels and the launch count of the call.
 """
 import argparse
 import json
@@ -432,6 +439,17 @@ class ParentLib:
                                                d_out, frames, 0, 0, stream)
         if rc != 0:
             raise SystemExit(f"parent lanczos_resize_device_ex: {rc}")
+
+    def window_device(self, entry, d, window, t, d_in, d_out, frames, in_fs, out_fs, stream):
+        """lanczos_resize_window_device (t None) or lanczos_resize_tensor[16]_window_device of the other build"""
+        import ctypes
+        fn = getattr(self.lib, entry)
+        fn.argtypes = [ctypes.c_void_p] * (6 if t is None else 7) + [ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+        win = self.byref(L.resize_window(d, window)) if window is not None else None
+        head = (self.h, self.byref(d), None, win) + (() if t is None else (self.byref(t),))
+        rc = fn(*head, d_in, d_out, frames, in_fs, out_fs, stream)
+        if rc != 0:
+            raise SystemExit(f"parent {entry}: {rc}")
 
     def close(self):
         self.lib.lanczos_destroy(self.h)
@@ -1147,6 +1165,111 @@ def run_box(name, out, args, ctx, torch):
     torch.cuda.empty_cache()
 
 
+YCC_WORKLOADS = {   # name: (in_w, in_h, out_w, out_h, frames, layout, crop (w, h) from the centre or None, tensor dtype or None)
+    "YC1": (3840, 2160, 1920, 1080, 32, "nv12", None, "bfloat16"),
+    "YC2": (500, 375, 341, 256, 256, "i420", (224, 224), "float32"),
+    "YC3": (1920, 1080, 3840, 2160, 32, "nv12", None, None),
+}
+
+
+def run_ycc(name, args, ctx, torch, parent):
+    """YCbCr frames: (a) `ycc`, the one call; (b) `torch_convert`, what it replaces -- chroma replicated to luma size
+    (repeat_interleave), the float matrix, round, clamp, cast and repack in torch, then the existing RGB call; (c) `rgb_floor`, the
+    existing RGB call alone on frames converted beforehand, on the parent's build where --parent-lib is given.  `luma_only` is the
+    luma plane's resize on its own (a one-channel call into scratch-sized memory): what (a) spends beyond it is chroma, the
+    split and the merge.  (b)'s chroma is nearest-replicated and its matrix is float, so its numbers differ from (a)'s by design:
+    only (a) is Pillow's composition; no route is checked against another."""
+    iw, ih, ow, oh, f, layout, crop, dtype = YCC_WORKLOADS[name]
+    d = L.resize_desc(iw, ih, ow, oh, 3)
+    src = L.ycc_source(d, layout)
+    in_fb = L.ycc_frame_bytes(d, src)
+    cw, chh = L.ycc_chroma_size(d, src)
+    win = L.center_window(ow, oh, *crop) if crop else None
+    w, h = (win[2], win[3]) if win else (ow, oh)
+    elem = {None: 1, "float32": 4, "bfloat16": 2}[dtype]
+    rgb_fs = (w * h * 3 + 3) // 4 * 4
+    out_fb = rgb_fs if dtype is None else w * h * 3 * elem
+    sets = max(2, -(-2 * 256 * 2 ** 20 // (f * in_fb)) + 1)
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    xs = [torch.randint(0, 256, (f, in_fb), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(sets)]
+    ys = [torch.empty(f * out_fb, dtype=torch.uint8, device="cuda") for _ in range(sets)]
+    table = torch.from_numpy(L.ycc_table("jfif")).cuda()
+    s = torch.cuda.current_stream().cuda_stream
+    st = L.tensor_strides("chw", w, h, 3)
+    lut = None if dtype is None else torch.from_numpy(
+        L.normalize_lut(3, IMAGENET_MEAN, IMAGENET_STD, dtype).view(np.int32 if elem == 4 else np.int16)).cuda()
+
+    def to_rgb(x):
+        yy = x[:, :iw * ih].view(f, ih, iw).float()
+        if layout == "nv12":
+            c2 = x[:, iw * ih:].view(f, chh, cw, 2)
+            cb, cr = c2[..., 0], c2[..., 1]
+        else:
+            cb = x[:, iw * ih:iw * ih + cw * chh].view(f, chh, cw)
+            cr = x[:, iw * ih + cw * chh:].view(f, chh, cw)
+        up = lambda p: p.repeat_interleave(2, 1).repeat_interleave(2, 2)[:, :ih, :iw].float().sub(128.0)
+        u, v = up(cb), up(cr)
+        rgb = torch.stack([yy + 1.402 * v, yy - 0.34414 * u - 0.71414 * v, yy + 1.772 * u], -1)
+        return rgb.round().clamp(0, 255).to(torch.uint8).contiguous()
+
+    rgbs = [to_rgb(xs[k]) for k in range(min(sets, 2))]           # (c)'s inputs, converted beforehand
+    tmp1 = torch.empty(f * ((w * h + 3) // 4 * 4), dtype=torch.uint8, device="cuda")
+    d1 = L.resize_desc(iw, ih, ow, oh, 1)
+
+    def rgb_call(c, x_ptr, y):
+        if dtype is None:
+            c.resize_device(d, x_ptr, y.data_ptr(), f, 0, rgb_fs, s, window=win)
+        else:
+            c.resize_tensor_device(d, x_ptr, y.data_ptr(), f, lut.data_ptr(), st, stream=s, dtype=dtype, window=win)
+
+    def ycc(i):
+        y = ys[i % sets]
+        if dtype is None:
+            ctx.resize_ycc_device(d, src, table.data_ptr(), xs[i % sets].data_ptr(), y.data_ptr(), f, stream=s, window=win)
+        else:
+            ctx.resize_ycc_tensor_device(d, src, table.data_ptr(), xs[i % sets].data_ptr(), y.data_ptr(), f, lut.data_ptr(), st,
+                                         stream=s, dtype=dtype, window=win)
+        return y[:out_fb]
+
+    def torch_convert(i):
+        rgb = to_rgb(xs[i % sets])
+        rgb_call(ctx, rgb.data_ptr(), ys[i % sets])
+        return ys[i % sets][:out_fb]
+
+    def rgb_floor(i):
+        y = ys[i % sets]
+        x_ptr = rgbs[i % len(rgbs)].data_ptr()
+        if parent is None:
+            rgb_call(ctx, x_ptr, y)
+        elif dtype is None:
+            parent.window_device("lanczos_resize_window_device", d, win, None, x_ptr, y.data_ptr(), f, 0, rgb_fs, s)
+        else:
+            t = L.tensor_out(lut.data_ptr(), st) if elem == 4 else L.tensor16_out(lut.data_ptr(), st)
+            parent.window_device("lanczos_resize_tensor_window_device" if elem == 4 else "lanczos_resize_tensor16_window_device",
+                                 d, win, t, x_ptr, y.data_ptr(), f, 0, 0, s)
+        return y[:out_fb]
+
+    def luma_only(i):
+        ctx.resize_device(d1, xs[i % sets].data_ptr(), tmp1.data_ptr(), f, in_fb, tmp1.numel() // f, s, window=win)
+        return tmp1[:w * h]
+
+    ycc(0)
+    info = ctx.last_ycc_info()
+    routes = {"ycc": ycc, "torch_convert": torch_convert, "rgb_floor": rgb_floor, "luma_only": luma_only}
+    inb = {"ycc": f * in_fb, "torch_convert": f * in_fb, "rgb_floor": f * iw * ih * 3, "luma_only": f * iw * ih}
+    outb = {rn: f * w * h * 3 * elem for rn in routes}
+    outb["luma_only"] = f * w * h
+    us = run_routes(name, f"{layout} {iw}x{ih}->{ow}x{oh}" + (f" window {win}" if win else "") + f" {dtype or 'rgb bytes'}", f,
+                    routes, inb, outb, args, ctx, torch)
+    print(json.dumps({"workload": name, "ycc_over_torch_convert": round(us["ycc"] / us["torch_convert"], 3),
+                      "ycc_over_rgb_floor": round(us["ycc"] / us["rgb_floor"], 3), "rgb_floor": "parent" if parent else "this build",
+                      "ycc_minus_luma_only_us": round(us["ycc"] - us["luma_only"], 2), "luma_kernel": info.luma_kernel,
+                      "chroma_kernel": info.chroma_kernel, "split": info.split, "launches": info.launches,
+                      "scratch_round_trip_bytes": 2 * 3 * f * w * h, "measured": True}), flush=True)
+    del xs, ys, rgbs, tmp1
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -1156,7 +1279,7 @@ def main():
     ap.add_argument("--routes", default=",".join(ROUTES))
     ap.add_argument("--pillow", action="store_true")
     ap.add_argument("--parent-lib", default=None,
-                    help="another build of liblanczos_hip.so for the parent_bytes route of T*, the parent_samples route of N* and the parent_full route of WIN*")
+                    help="another build of liblanczos_hip.so for the parent_bytes route of T*, the parent_samples route of N*, the parent_full route of WIN* and the rgb_floor route of YC*")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -1164,7 +1287,9 @@ def main():
     ctx = L.Context(0)
     parent = ParentLib(args.parent_lib) if args.parent_lib else None
     for name in args.only.split(","):
-        if name in NORM_WORKLOADS:
+        if name in YCC_WORKLOADS:
+            run_ycc(name, args, ctx, torch, parent)
+        elif name in NORM_WORKLOADS:
             run_norm(name, args, ctx, torch, parent)
         elif name in WINDOW_WORKLOADS:
             run_window(name, args, ctx, torch, parent)
