@@ -14,6 +14,7 @@ import collections
 import ctypes
 import os
 import subprocess
+from functools import cached_property as _cached_property
 
 import numpy as np
 
@@ -256,6 +257,126 @@ class YccInfo(collections.namedtuple("YccInfo", "luma_kernel chroma_kernel split
 FLIP_H, FLIP_V = 1, 2   # the bits of lanczos_tensor_view.flip and of a d_flip byte
 _FLIP_NAMES = {None: 0, "": 0, "h": FLIP_H, "v": FLIP_V, "hv": FLIP_H | FLIP_V, "vh": FLIP_H | FLIP_V}
 
+
+class Xfer(ctypes.Structure):
+    """lanczos_xfer -- one message of the root exchange (lanczos_multi_exchange_plan)."""
+    _fields_ = [("src", ctypes.c_int), ("dst", ctypes.c_int), ("src_off", ctypes.c_size_t), ("dst_off", ctypes.c_size_t),
+                ("bytes", ctypes.c_size_t)]
+
+
+# -- the signatures of include/lanczos_hip.h: _lib() sets them on the symbols the loaded library has
+_I, _P, _Z, _F = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double
+_PI, _PF, _PP = ctypes.POINTER(_I), ctypes.POINTER(_F), ctypes.POINTER(_P)
+_PD, _PRD, _PRO, _PRW, _PRC, _PRS, _PRT, _PYS = (ctypes.POINTER(t) for t in (Desc, ResizeDesc, ResizeOpts, ResizeWindow, ResizeCrops,
+                                                                           ResizeSource, ResizeDest, YccSource))
+_PTO, _PTO16, _PTV, _PTN = (ctypes.POINTER(t) for t in (TensorOut, TensorOut16, TensorView, TensorNorm))
+_PLAN, _PLANX = ctypes.POINTER(ResizePlan), ctypes.POINTER(ResizePlanEx)
+
+# every entry that comes as a pair (ctx, <head>, in, out, frames[, in_frame_stride, out_frame_stride, stream]):
+# (the device entry, the host entry, <head>)
+_ENTRY_PAIRS = [
+    ("lanczos_resample_device", "lanczos_resample_host", [_PD]),
+    ("lanczos_resize_device", "lanczos_resize_host", [_PRD]),
+    ("lanczos_resize_device_ex", "lanczos_resize_host_ex", [_PRD, _PRO]),
+    ("lanczos_reduce_device", "lanczos_reduce_host", [_I] * 5 + [_P]),
+    ("lanczos_resize_tensor_device", "lanczos_resize_tensor_host", [_PRD, _PRO, _PTO]),
+    ("lanczos_resize_tensor16_device", "lanczos_resize_tensor16_host", [_PRD, _PRO, _PTO16]),
+    ("lanczos_resize_window_device", "lanczos_resize_window_host", [_PRD, _PRO, _PRW]),
+    ("lanczos_resize_tensor_window_device", "lanczos_resize_tensor_window_host", [_PRD, _PRO, _PRW, _PTO]),
+    ("lanczos_resize_tensor16_window_device", "lanczos_resize_tensor16_window_host", [_PRD, _PRO, _PRW, _PTO16]),
+    ("lanczos_resize_tensor_view_device", "lanczos_resize_tensor_view_host", [_PRD, _PRO, _PRW, _PTV]),
+    ("lanczos_resize_tensor_crops_device", "lanczos_resize_tensor_crops_host", [_PRD, _PRO, _PRC, _PTV]),
+    ("lanczos_resize_source_device", "lanczos_resize_source_host", [_PRD, _PRO, _PRW, _PRS]),
+    ("lanczos_resize_tensor_source_device", "lanczos_resize_tensor_source_host", [_PRD, _PRO, _PRW, _PRC, _PRS, _PTV]),
+    ("lanczos_resize_dest_device", "lanczos_resize_dest_host", [_PRD, _PRO, _PRW, _PRS, _PRT]),
+    ("lanczos_resize_tensor_norm_device", "lanczos_resize_tensor_norm_host", [_PRD, _PRO, _PRW, _PRS, _PTN]),
+    ("lanczos_resize_ycc_device", "lanczos_resize_ycc_host", [_PRD, _PRO, _PRW, _PYS, _P]),
+    ("lanczos_resize_ycc_tensor_device", "lanczos_resize_ycc_tensor_host", [_PRD, _PRO, _PRW, _PYS, _P, _PTV]),
+]
+# name -> (argtypes, restype; None = int)
+_SIGNATURES = {
+    "lanczos_desc_init": ([_PD] + [_I] * 7, None),
+    "lanczos_validate": ([_PD], None),
+    "lanczos_inplace_rows": ([_PD], None),
+    "lanczos_strip_input_rows": ([_PD, _I, _I, _PI, _PI], None),
+    "lanczos_in_frame_bytes": ([_PD], _Z),
+    "lanczos_out_frame_bytes": ([_PD], _Z),
+    "lanczos_kernel": ([_F, _I], _F),
+    "lanczos_kernel_idx": ([_I] * 5, _F),
+    "lanczos_taps_host": ([_PD, _I, _P, _P], None),
+    "lanczos_create": ([_PP, _I], None),
+    "lanczos_destroy": ([_P], None),
+    "lanczos_host_alloc": ([_PP, _Z], None),
+    "lanczos_host_free": ([_P], None),
+    "lanczos_planar_to_interleaved_device": ([_P, _P, _P] + [_I] * 5 + [_P], None),
+    "lanczos_interleaved_to_planar_device": ([_P, _P, _P] + [_I] * 5 + [_P], None),
+    "lanczos_resample_planar_device": ([_P, _PD, _P, _P, _I, _P], None),
+    "lanczos_u8": ([_P, _P, _I, _I, _I, _P, _I, _I, _I], None),
+    "lanczos_timing_enable": ([_P, _I], None),
+    "lanczos_timing_read": ([_P, _PI, _PF, _PF], None),
+    "lanczos_last_kernel": ([_P], None),
+    "lanczos_last_hip_error": ([_P], None),
+    "lanczos_last_route": ([_P], None),
+    "lanczos_last_march_table": ([_P, ctypes.POINTER(MarchTableInfoC), ctypes.POINTER(ctypes.c_int32), _I], None),
+    "lanczos_force_kernel": ([_P, _I], None),
+    "lanczos_strerror": ([_I], ctypes.c_char_p),
+    "lanczos_version": ([], ctypes.c_char_p),
+    "lanczos_partition_frames": ([_I, _I, _I, _PI, _PI], None),
+    "lanczos_partition_rows": ([_PD, _I, _I, _PI, _PI, _PI, _PI], None),
+    "lanczos_multi_create": ([_PP, _PI, _I], None),
+    "lanczos_multi_destroy": ([_P], None),
+    "lanczos_multi_devices": ([_P], None),
+    "lanczos_resample_multi_host": ([_P, _PD, _P, _P, _I, _I], None),
+    "lanczos_resample_multi_root": ([_P, _PD, _P, _P, _I, _I, _PF, _PF], None),
+    "lanczos_multi_exchange_plan": ([_PD, _I, _I, _I, _I, ctypes.POINTER(Xfer), _I], None),
+    "lanczos_multi_exchange_selftest": ([_P, _I, _Z, _I], None),
+    "lanczos_resize_desc_init": ([_PRD] + [_I] * 6, None),
+    "lanczos_resize_desc_init_ex": ([_PRD] + [_I] * 7, None),
+    "lanczos_resize_desc_init_filter": ([_PRD] + [_I] * 7, None),
+    "lanczos_resize_validate": ([_PRD], None),
+    "lanczos_resize_taps_host": ([_PRD, _I, _P, _P, _P, _PI], None),
+    "lanczos_resize_taps_f64_host": ([_PRD, _I, _P, _P, _P, _PI], None),
+    "lanczos_resize_force": ([_P, _I], None),
+    "lanczos_resize_plan_host": ([_PRD, _I, _PLAN], None),
+    "lanczos_resize_opts_init": ([_PRO, _PRD], None),
+    "lanczos_resize_taps_host_ex": ([_PRD, _PRO, _I, _P, _P, _P, _PI], None),
+    "lanczos_resize_taps_f64_host_ex": ([_PRD, _PRO, _I, _P, _P, _P, _PI], None),
+    "lanczos_resize_plan_host_ex": ([_PRD, _PRO, _I, _PLANX], None),
+    "lanczos_reduce_size": ([_I] * 4 + [_P, _PI, _PI], None),
+    "lanczos_resize_tensor_validate": ([_PRD, _PTO], None),
+    "lanczos_tensor_lut_normalize": ([_I, _P, _P, _P], None),
+    "lanczos_last_tensor_route": ([_P], None),
+    "lanczos_resize_tensor16_validate": ([_PRD, _PTO16], None),
+    "lanczos_tensor_lut_convert16": ([_P, _I, _I, _P], None),
+    "lanczos_tensor16_lut_normalize": ([_I, _P, _P, _I, _P], None),
+    "lanczos_resize_window_init": ([_PRW, _PRD], None),
+    "lanczos_resize_window_validate": ([_PRD, _PRW], None),
+    "lanczos_resize_window_source": ([_PRD, _PRO, _PRW, _P], None),
+    "lanczos_resize_window_plan_host": ([_PRD, _PRO, _PRW, _I, _PLANX], None),
+    "lanczos_resize_tensor_window_validate": ([_PRD, _PRW, _PTO], None),
+    "lanczos_resize_tensor16_window_validate": ([_PRD, _PRW, _PTO16], None),
+    "lanczos_tensor_view_init": ([_PTV, _PRD, _I], None),
+    "lanczos_resize_tensor_view_validate": ([_PRD, _PRW, _PTV], None),
+    "lanczos_resize_crops_validate": ([_PRD, _PRC], None),
+    "lanczos_resize_crops_plan_host": ([_PRD, _PRO, _PRC, _I, _PLANX], None),
+    "lanczos_resize_tensor_crops_validate": ([_PRD, _PRC, _PTV], None),
+    "lanczos_resize_source_init": ([_PRS, _PRD, _I], None),
+    "lanczos_resize_source_validate": ([_PRD, _PRS], None),
+    "lanczos_last_source_route": ([_P], None),
+    "lanczos_resize_dest_init": ([_PRT, _PRD, _PRW, _I], None),
+    "lanczos_resize_dest_validate": ([_PRD, _PRW, _PRT], None),
+    "lanczos_last_dest_route": ([_P], None),
+    "lanczos_tensor_norm_init": ([_PTN, _PRD, _I, _I], None),
+    "lanczos_resize_tensor_norm_validate": ([_PRD, _PRW, _PTN], None),
+    "lanczos_ycc_source_init": ([_PYS, _PRD, _I, _I, _I], None),
+    "lanczos_ycc_source_validate": ([_PRD, _PYS], None),
+    "lanczos_ycc_table": ([_I, _P], None),
+    "lanczos_last_ycc_info": ([_P, ctypes.POINTER(YccInfoC)], None),
+}
+for _device, _host, _head in _ENTRY_PAIRS:
+    _SIGNATURES[_host] = ([_P] + _head + [_P, _P, _I], None)
+    _SIGNATURES[_device] = (_SIGNATURES[_host][0] + [_Z, _Z, _P], None)
+
 _LIB = None
 
 
@@ -280,169 +401,12 @@ def _lib():
                 f"{LIB_PATH} is missing: build it with `make -C lanczos-hls_amd` "
                 "(or __graft_entry__.build()); there is no CPU fallback")
         L = ctypes.CDLL(LIB_PATH)
-        PD = ctypes.POINTER(Desc)
-        c_int, c_void_p, c_size_t, c_double = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double
-        PI = ctypes.POINTER(c_int)
-        L.lanczos_desc_init.argtypes = [PD] + [c_int] * 7
-        L.lanczos_validate.argtypes = [PD]
-        L.lanczos_inplace_rows.argtypes = [PD]
-        L.lanczos_strip_input_rows.argtypes = [PD, c_int, c_int, PI, PI]
-        L.lanczos_in_frame_bytes.argtypes = [PD]
-        L.lanczos_in_frame_bytes.restype = c_size_t
-        L.lanczos_out_frame_bytes.argtypes = [PD]
-        L.lanczos_out_frame_bytes.restype = c_size_t
-        L.lanczos_kernel.argtypes = [c_double, c_int]
-        L.lanczos_kernel.restype = c_double
-        L.lanczos_kernel_idx.argtypes = [c_int] * 5
-        L.lanczos_kernel_idx.restype = c_double
-        L.lanczos_taps_host.argtypes = [PD, c_int, c_void_p, c_void_p]
-        L.lanczos_create.argtypes = [ctypes.POINTER(c_void_p), c_int]
-        L.lanczos_destroy.argtypes = [c_void_p]
-        L.lanczos_host_alloc.argtypes = [ctypes.POINTER(c_void_p), c_size_t]
-        L.lanczos_host_free.argtypes = [c_void_p]
-        L.lanczos_resample_host.argtypes = [c_void_p, PD, c_void_p, c_void_p, c_int]
-        L.lanczos_resample_device.argtypes = [c_void_p, PD, c_void_p, c_void_p, c_int, c_size_t, c_size_t,
-                                              c_void_p]
-        L.lanczos_planar_to_interleaved_device.argtypes = [c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]
-        L.lanczos_interleaved_to_planar_device.argtypes = [c_void_p, c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]
-        L.lanczos_resample_planar_device.argtypes = [c_void_p, PD, c_void_p, c_void_p, c_int, c_void_p]
-        L.lanczos_u8.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int]
-        L.lanczos_timing_enable.argtypes = [c_void_p, c_int]
-        L.lanczos_timing_read.argtypes = [c_void_p, PI, ctypes.POINTER(c_double), ctypes.POINTER(c_double)]
-        L.lanczos_last_kernel.argtypes = [c_void_p]
-        L.lanczos_last_hip_error.argtypes = [c_void_p]
-        if hasattr(L, "lanczos_last_route"):   # (an older build loaded through LANCZOS_LIB has none)
-            L.lanczos_last_route.argtypes = [c_void_p]
-        if hasattr(L, "lanczos_last_march_table"):
-            L.lanczos_last_march_table.argtypes = [c_void_p, ctypes.POINTER(MarchTableInfoC), ctypes.POINTER(ctypes.c_int32), c_int]
-        L.lanczos_force_kernel.argtypes = [c_void_p, c_int]
-        L.lanczos_strerror.argtypes = [c_int]
-        L.lanczos_partition_frames.argtypes = [c_int, c_int, c_int, PI, PI]
-        L.lanczos_partition_rows.argtypes = [PD, c_int, c_int, PI, PI, PI, PI]
-        L.lanczos_multi_create.argtypes = [ctypes.POINTER(c_void_p), PI, c_int]
-        L.lanczos_multi_destroy.argtypes = [c_void_p]
-        L.lanczos_multi_devices.argtypes = [c_void_p]
-        L.lanczos_resample_multi_host.argtypes = [c_void_p, PD, c_void_p, c_void_p, c_int, c_int]
-        L.lanczos_resample_multi_root.argtypes = [c_void_p, PD, c_void_p, c_void_p, c_int, c_int,
-                                                  ctypes.POINTER(c_double), ctypes.POINTER(c_double)]
-        PRD = ctypes.POINTER(ResizeDesc)
-        L.lanczos_resize_desc_init.argtypes = [PRD] + [c_int] * 6
-        L.lanczos_resize_desc_init_ex.argtypes = [PRD] + [c_int] * 7
-        L.lanczos_resize_validate.argtypes = [PRD]
-        L.lanczos_resize_taps_host.argtypes = [PRD, c_int, c_void_p, c_void_p, c_void_p, PI]
-        L.lanczos_resize_taps_f64_host.argtypes = [PRD, c_int, c_void_p, c_void_p, c_void_p, PI]
-        L.lanczos_resize_device.argtypes = [c_void_p, PRD, c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p]
-        L.lanczos_resize_host.argtypes = [c_void_p, PRD, c_void_p, c_void_p, c_int]
-        L.lanczos_resize_force.argtypes = [c_void_p, c_int]
-        L.lanczos_resize_plan_host.argtypes = [PRD, c_int, ctypes.POINTER(ResizePlan)]
-        PRO = ctypes.POINTER(ResizeOpts)
-        L.lanczos_strerror.restype = ctypes.c_char_p
-        L.lanczos_version.argtypes = []
-        L.lanczos_version.restype = ctypes.c_char_p
-        if os.environ.get("LANCZOS_LIB") and not hasattr(L, "lanczos_resize_opts_init"):
-            _LIB = L   # an older build of the ABI (A/B runs): everything up to here is there, box / gap / reduce are not
-            return _LIB
-        L.lanczos_resize_opts_init.argtypes = [PRO, PRD]
-        L.lanczos_resize_taps_host_ex.argtypes = [PRD, PRO, c_int, c_void_p, c_void_p, c_void_p, PI]
-        L.lanczos_resize_taps_f64_host_ex.argtypes = [PRD, PRO, c_int, c_void_p, c_void_p, c_void_p, PI]
-        L.lanczos_resize_plan_host_ex.argtypes = [PRD, PRO, c_int, ctypes.POINTER(ResizePlanEx)]
-        L.lanczos_resize_device_ex.argtypes = [c_void_p, PRD, PRO, c_void_p, c_void_p, c_int, c_size_t, c_size_t, c_void_p]
-        L.lanczos_resize_host_ex.argtypes = [c_void_p, PRD, PRO, c_void_p, c_void_p, c_int]
-        L.lanczos_reduce_size.argtypes = [c_int] * 4 + [c_void_p, PI, PI]
-        L.lanczos_reduce_device.argtypes = [c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_int, c_size_t,
-                                                                      c_size_t, c_void_p]
-        L.lanczos_reduce_host.argtypes = [c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_void_p, c_int]
-        if hasattr(L, "lanczos_resize_desc_init_filter"):   # (an older build loaded through LANCZOS_LIB has only Lanczos)
-            L.lanczos_resize_desc_init_filter.argtypes = [PRD] + [c_int] * 7
-        if hasattr(L, "lanczos_resize_tensor_device"):   # (nor has it the tensor entry)
-            PTO = ctypes.POINTER(TensorOut)
-            L.lanczos_resize_tensor_validate.argtypes = [PRD, PTO]
-            L.lanczos_tensor_lut_normalize.argtypes = [c_int, c_void_p, c_void_p, c_void_p]
-            L.lanczos_resize_tensor_device.argtypes = [c_void_p, PRD, PRO, PTO, c_void_p, c_void_p, c_int, c_size_t, c_size_t,
-                                                       c_void_p]
-            L.lanczos_resize_tensor_host.argtypes = [c_void_p, PRD, PRO, PTO, c_void_p, c_void_p, c_int]
-            L.lanczos_last_tensor_route.argtypes = [c_void_p]
-        if hasattr(L, "lanczos_resize_tensor16_device"):   # (nor the 16-bit one)
-            PTO16 = ctypes.POINTER(TensorOut16)
-            L.lanczos_resize_tensor16_validate.argtypes = [PRD, PTO16]
-            L.lanczos_tensor_lut_convert16.argtypes = [c_void_p, c_int, c_int, c_void_p]
-            L.lanczos_tensor16_lut_normalize.argtypes = [c_int, c_void_p, c_void_p, c_int, c_void_p]
-            L.lanczos_resize_tensor16_device.argtypes = [c_void_p, PRD, PRO, PTO16, c_void_p, c_void_p, c_int, c_size_t,
-                                                         c_size_t, c_void_p]
-            L.lanczos_resize_tensor16_host.argtypes = [c_void_p, PRD, PRO, PTO16, c_void_p, c_void_p, c_int]
-        if hasattr(L, "lanczos_resize_window_device"):   # (nor the window of the output)
-            PRW = ctypes.POINTER(ResizeWindow)
-            L.lanczos_resize_window_init.argtypes = [PRW, PRD]
-            L.lanczos_resize_window_validate.argtypes = [PRD, PRW]
-            L.lanczos_resize_window_source.argtypes = [PRD, PRO, PRW, c_void_p]
-            L.lanczos_resize_window_plan_host.argtypes = [PRD, PRO, PRW, c_int, ctypes.POINTER(ResizePlanEx)]
-            L.lanczos_resize_window_device.argtypes = [c_void_p, PRD, PRO, PRW, c_void_p, c_void_p, c_int, c_size_t, c_size_t,
-                                                       c_void_p]
-            L.lanczos_resize_window_host.argtypes = [c_void_p, PRD, PRO, PRW, c_void_p, c_void_p, c_int]
-            L.lanczos_resize_tensor_window_validate.argtypes = [PRD, PRW, PTO]
-            L.lanczos_resize_tensor16_window_validate.argtypes = [PRD, PRW, PTO16]
-            L.lanczos_resize_tensor_window_device.argtypes = [c_void_p, PRD, PRO, PRW, PTO, c_void_p, c_void_p, c_int, c_size_t,
-                                                              c_size_t, c_void_p]
-            L.lanczos_resize_tensor_window_host.argtypes = [c_void_p, PRD, PRO, PRW, PTO, c_void_p, c_void_p, c_int]
-            L.lanczos_resize_tensor16_window_device.argtypes = [c_void_p, PRD, PRO, PRW, PTO16, c_void_p, c_void_p, c_int,
-                                                                c_size_t, c_size_t, c_void_p]
-            L.lanczos_resize_tensor16_window_host.argtypes = [c_void_p, PRD, PRO, PRW, PTO16, c_void_p, c_void_p, c_int]
-        if hasattr(L, "lanczos_resize_tensor_view_device"):   # (nor the view)
-            PTV = ctypes.POINTER(TensorView)
-            L.lanczos_tensor_view_init.argtypes = [PTV, PRD, c_int]
-            L.lanczos_resize_tensor_view_validate.argtypes = [PRD, PRW, PTV]
-            L.lanczos_resize_tensor_view_device.argtypes = [c_void_p, PRD, PRO, PRW, PTV, c_void_p, c_void_p, c_int, c_size_t,
-                                                            c_size_t, c_void_p]
-            L.lanczos_resize_tensor_view_host.argtypes = [c_void_p, PRD, PRO, PRW, PTV, c_void_p, c_void_p, c_int]
-        if hasattr(L, "lanczos_resize_tensor_crops_device"):   # (nor a crop origin per frame)
-            PRC = ctypes.POINTER(ResizeCrops)
-            L.lanczos_resize_crops_validate.argtypes = [PRD, PRC]
-            L.lanczos_resize_crops_plan_host.argtypes = [PRD, PRO, PRC, c_int, ctypes.POINTER(ResizePlanEx)]
-            L.lanczos_resize_tensor_crops_validate.argtypes = [PRD, PRC, PTV]
-            L.lanczos_resize_tensor_crops_device.argtypes = [c_void_p, PRD, PRO, PRC, PTV, c_void_p, c_void_p, c_int, c_size_t,
-                                                             c_size_t, c_void_p]
-            L.lanczos_resize_tensor_crops_host.argtypes = [c_void_p, PRD, PRO, PRC, PTV, c_void_p, c_void_p, c_int]
-        if hasattr(L, "lanczos_resize_source_device"):   # (nor a source layout)
-            PRS = ctypes.POINTER(ResizeSource)
-            L.lanczos_resize_source_init.argtypes = [PRS, PRD, c_int]
-            L.lanczos_resize_source_validate.argtypes = [PRD, PRS]
-            L.lanczos_resize_source_device.argtypes = [c_void_p, PRD, PRO, PRW, PRS, c_void_p, c_void_p, c_int, c_size_t, c_size_t,
-                                                       c_void_p]
-            L.lanczos_resize_tensor_source_device.argtypes = [c_void_p, PRD, PRO, PRW, PRC, PRS, PTV, c_void_p, c_void_p, c_int,
-                                                              c_size_t, c_size_t, c_void_p]
-            L.lanczos_resize_source_host.argtypes = [c_void_p, PRD, PRO, PRW, PRS, c_void_p, c_void_p, c_int]
-            L.lanczos_resize_tensor_source_host.argtypes = [c_void_p, PRD, PRO, PRW, PRC, PRS, PTV, c_void_p, c_void_p, c_int]
-            L.lanczos_last_source_route.argtypes = [c_void_p]
-        if hasattr(L, "lanczos_resize_dest_device"):   # (nor a destination layout)
-            PRT = ctypes.POINTER(ResizeDest)
-            L.lanczos_resize_dest_init.argtypes = [PRT, PRD, PRW, c_int]
-            L.lanczos_resize_dest_validate.argtypes = [PRD, PRW, PRT]
-            L.lanczos_resize_dest_device.argtypes = [c_void_p, PRD, PRO, PRW, PRS, PRT, c_void_p, c_void_p, c_int, c_size_t,
-                                                     c_size_t, c_void_p]
-            L.lanczos_resize_dest_host.argtypes = [c_void_p, PRD, PRO, PRW, PRS, PRT, c_void_p, c_void_p, c_int]
-            L.lanczos_last_dest_route.argtypes = [c_void_p]
-        if hasattr(L, "lanczos_resize_tensor_norm_device"):   # (nor 16-bit and float samples into tensors)
-            PTN = ctypes.POINTER(TensorNorm)
-            L.lanczos_tensor_norm_init.argtypes = [PTN, PRD, c_int, c_int]
-            L.lanczos_resize_tensor_norm_validate.argtypes = [PRD, PRW, PTN]
-            L.lanczos_resize_tensor_norm_device.argtypes = [c_void_p, PRD, PRO, PRW, PRS, PTN, c_void_p, c_void_p, c_int, c_size_t,
-                                                            c_size_t, c_void_p]
-            L.lanczos_resize_tensor_norm_host.argtypes = [c_void_p, PRD, PRO, PRW, PRS, PTN, c_void_p, c_void_p, c_int]
-        if hasattr(L, "lanczos_resize_ycc_device"):   # (nor YCbCr frames)
-            PYS = ctypes.POINTER(YccSource)
-            L.lanczos_ycc_source_init.argtypes = [PYS, PRD, c_int, c_int, c_int]
-            L.lanczos_ycc_source_validate.argtypes = [PRD, PYS]
-            L.lanczos_ycc_table.argtypes = [c_int, c_void_p]
-            L.lanczos_resize_ycc_device.argtypes = [c_void_p, PRD, PRO, PRW, PYS, c_void_p, c_void_p, c_void_p, c_int, c_size_t,
-                                                    c_size_t, c_void_p]
-            L.lanczos_resize_ycc_tensor_device.argtypes = [c_void_p, PRD, PRO, PRW, PYS, c_void_p, PTV, c_void_p, c_void_p, c_int,
-                                                           c_size_t, c_size_t, c_void_p]
-            L.lanczos_resize_ycc_host.argtypes = [c_void_p, PRD, PRO, PRW, PYS, c_void_p, c_void_p, c_void_p, c_int]
-            L.lanczos_resize_ycc_tensor_host.argtypes = [c_void_p, PRD, PRO, PRW, PYS, c_void_p, PTV, c_void_p, c_void_p, c_int]
-            L.lanczos_last_ycc_info.argtypes = [c_void_p, ctypes.POINTER(YccInfoC)]
-        L.lanczos_strerror.restype = ctypes.c_char_p
-        L.lanczos_version.argtypes = []
-        L.lanczos_version.restype = ctypes.c_char_p
+        for name, (argtypes, restype) in _SIGNATURES.items():
+            fn = getattr(L, name, None)   # an older build of the ABI loaded through LANCZOS_LIB (A/B runs) lacks the later entries
+            if fn is not None:
+                fn.argtypes = argtypes
+                if restype is not None:
+                    fn.restype = restype
         _LIB = L
     return _LIB
 
@@ -450,6 +414,11 @@ def _lib():
 def _check(rc, what):
     if rc != OK:
         raise LanczosError(rc, what)
+
+
+def _ref(struct):
+    """byref, or NULL for None"""
+    return ctypes.byref(struct) if struct is not None else None
 
 
 def make_desc(in_w, in_h, channels, scale_n, scale_d, a, bytes_per_sample=1, mode=MODE_LSB1,
@@ -546,43 +515,36 @@ def resize_opts(desc, box=None, reducing_gap=None):
 def _opts_ref(desc, box, reducing_gap, opts):
     if opts is None and (box is not None or reducing_gap is not None):
         opts = resize_opts(desc, box, reducing_gap)
-    return ctypes.byref(opts) if opts is not None else None
+    return _ref(opts)
+
+
+def _resize_taps(entry, coeff_dtype, desc, axis, box, reducing_gap, opts):
+    """the body of resize_taps_host / resize_taps_f64_host: `entry`, or `entry`_ex with options, asked for ksize, then for the tables"""
+    ks = ctypes.c_int()
+    if box is None and reducing_gap is None and opts is None:
+        fn = lambda *a: getattr(_lib(), entry)(ctypes.byref(desc), axis, *a)
+    else:
+        ref = _opts_ref(desc, box, reducing_gap, opts)
+        fn = lambda *a: getattr(_lib(), entry + "_ex")(ctypes.byref(desc), ref, axis, *a)
+    _check(fn(None, None, None, ctypes.byref(ks)), entry)
+    n = desc.out_w if axis == 0 else desc.out_h
+    first = np.empty(n, dtype=np.int32)
+    count = np.empty(n, dtype=np.int32)
+    coeffs = np.empty((n, ks.value), dtype=coeff_dtype)
+    _check(fn(first.ctypes.data, count.ctypes.data, coeffs.ctypes.data, ctypes.byref(ks)), entry)
+    return first, count, coeffs
 
 
 def resize_taps_host(desc, axis, box=None, reducing_gap=None, opts=None):
     """Fixed-point tables of one axis (0 = horizontal, 1 = vertical): (first[out], count[out], coeffs[out][ksize]) int32.
     With a box and / or a gap (or a ready ResizeOpts) the tables of the resize that remains: lanczos_resize_taps_host_ex."""
-    ks = ctypes.c_int()
-    if box is None and reducing_gap is None and opts is None:
-        fn = lambda *a: _lib().lanczos_resize_taps_host(ctypes.byref(desc), axis, *a)
-    else:
-        ref = _opts_ref(desc, box, reducing_gap, opts)
-        fn = lambda *a: _lib().lanczos_resize_taps_host_ex(ctypes.byref(desc), ref, axis, *a)
-    _check(fn(None, None, None, ctypes.byref(ks)), "lanczos_resize_taps_host")
-    n = desc.out_w if axis == 0 else desc.out_h
-    first = np.empty(n, dtype=np.int32)
-    count = np.empty(n, dtype=np.int32)
-    coeffs = np.empty((n, ks.value), dtype=np.int32)
-    _check(fn(first.ctypes.data, count.ctypes.data, coeffs.ctypes.data, ctypes.byref(ks)), "lanczos_resize_taps_host")
-    return first, count, coeffs
+    return _resize_taps("lanczos_resize_taps_host", np.int32, desc, axis, box, reducing_gap, opts)
 
 
 def resize_taps_f64_host(desc, axis, box=None, reducing_gap=None, opts=None):
     """Double tables of one axis, what 16-bit and float requests run on: (first[out] int32, count[out] int32, coeffs[out][ksize]
     float64); first and count are those of resize_taps_host.  box / reducing_gap / opts as resize_taps_host."""
-    ks = ctypes.c_int()
-    if box is None and reducing_gap is None and opts is None:
-        fn = lambda *a: _lib().lanczos_resize_taps_f64_host(ctypes.byref(desc), axis, *a)
-    else:
-        ref = _opts_ref(desc, box, reducing_gap, opts)
-        fn = lambda *a: _lib().lanczos_resize_taps_f64_host_ex(ctypes.byref(desc), ref, axis, *a)
-    _check(fn(None, None, None, ctypes.byref(ks)), "lanczos_resize_taps_f64_host")
-    n = desc.out_w if axis == 0 else desc.out_h
-    first = np.empty(n, dtype=np.int32)
-    count = np.empty(n, dtype=np.int32)
-    coeffs = np.empty((n, ks.value), dtype=np.float64)
-    _check(fn(first.ctypes.data, count.ctypes.data, coeffs.ctypes.data, ctypes.byref(ks)), "lanczos_resize_taps_f64_host")
-    return first, count, coeffs
+    return _resize_taps("lanczos_resize_taps_f64_host", np.float64, desc, axis, box, reducing_gap, opts)
 
 
 def resize_plan_host(desc, frames=1, box=None, reducing_gap=None, opts=None):
@@ -650,7 +612,7 @@ def resize_crops(w, h, d_origin):
 def resize_crops_validate(desc, crops, view=None):
     """lanczos_resize_crops_validate, or with a TensorView lanczos_resize_tensor_crops_validate (the view's strides describe the
     w x h frame): raises LanczosError where the request is refused."""
-    cp = ctypes.byref(crops) if crops is not None else None
+    cp = _ref(crops)
     if view is None:
         _check(_lib().lanczos_resize_crops_validate(ctypes.byref(desc), cp), "lanczos_resize_crops_validate")
     else:
@@ -671,29 +633,35 @@ def resize_crops_plan_host(desc, crops, frames=1, box=None, reducing_gap=None, o
     return p
 
 
-def resize_source(desc, layout="planar", row_stride=None, chan_stride=None):
-    """A ResizeSource for `desc`: layout "planar" (N x C x H x W bytes, what torchvision.io.decode_jpeg(device=) returns) or
-    "interleaved"; row_stride / chan_stride in bytes replace the tight layout's (pitched rows, padded planes).  Validated where it
-    is used (resize_source_validate); a ready ResizeSource is returned as it is."""
-    if isinstance(layout, ResizeSource):
+def _layout_struct(cls, what, layout, row_stride, chan_stride, init, rows):
+    """the body of resize_source / resize_dest: init(struct, code) fills the tight layout, rows() is the height of one plane"""
+    if isinstance(layout, cls):
         return layout
-    kinds = {"interleaved": SOURCE_INTERLEAVED, "planar": SOURCE_PLANAR}
+    kinds = {"interleaved": SOURCE_INTERLEAVED, "planar": SOURCE_PLANAR}   # DEST_* are the same codes
     if layout not in kinds:
-        raise LanczosError(ERR_BAD_ARG, f"resize_source: layout is 'planar' or 'interleaved', not {layout!r}")
-    s = ResizeSource()
-    _check(_lib().lanczos_resize_source_init(ctypes.byref(s), ctypes.byref(desc), kinds[layout]), "lanczos_resize_source_init")
+        raise LanczosError(ERR_BAD_ARG, f"{what}: layout is 'planar' or 'interleaved', not {layout!r}")
+    s = cls()
+    _check(init(ctypes.byref(s), kinds[layout]), f"lanczos_{what}_init")
     if row_stride is not None:
         if chan_stride is None and layout == "planar":   # the planes stay back to back
-            chan_stride = int(row_stride) * desc.in_h
+            chan_stride = int(row_stride) * rows()
         s.row_stride = int(row_stride)
     if chan_stride is not None:
         s.chan_stride = int(chan_stride)
     return s
 
 
+def resize_source(desc, layout="planar", row_stride=None, chan_stride=None):
+    """A ResizeSource for `desc`: layout "planar" (N x C x H x W bytes, what torchvision.io.decode_jpeg(device=) returns) or
+    "interleaved"; row_stride / chan_stride in bytes replace the tight layout's (pitched rows, padded planes).  Validated where it
+    is used (resize_source_validate); a ready ResizeSource is returned as it is."""
+    return _layout_struct(ResizeSource, "resize_source", layout, row_stride, chan_stride,
+                          lambda s, kind: _lib().lanczos_resize_source_init(s, ctypes.byref(desc), kind), lambda: desc.in_h)
+
+
 def resize_source_validate(desc, source):
     """lanczos_resize_source_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the layout is refused."""
-    _check(_lib().lanczos_resize_source_validate(ctypes.byref(desc), ctypes.byref(source) if source is not None else None),
+    _check(_lib().lanczos_resize_source_validate(ctypes.byref(desc), _ref(source)),
            "lanczos_resize_source_validate")
 
 
@@ -701,27 +669,15 @@ def resize_dest(desc, layout="planar", row_stride=None, chan_stride=None, window
     """A ResizeDest for the result of `desc` (its window, where one is given): layout "planar" (N x C x H x W bytes, what a torch
     stage takes) or "interleaved"; row_stride / chan_stride in bytes replace the tight layout's (pitched rows, padded planes).
     Validated where it is used (resize_dest_validate); a ready ResizeDest is returned as it is."""
-    if isinstance(layout, ResizeDest):
-        return layout
-    kinds = {"interleaved": DEST_INTERLEAVED, "planar": DEST_PLANAR}
-    if layout not in kinds:
-        raise LanczosError(ERR_BAD_ARG, f"resize_dest: layout is 'planar' or 'interleaved', not {layout!r}")
-    t = ResizeDest()
-    _check(_lib().lanczos_resize_dest_init(ctypes.byref(t), ctypes.byref(desc), _window_ref(desc, window), kinds[layout]),
-           "lanczos_resize_dest_init")
-    if row_stride is not None:
-        if chan_stride is None and layout == "planar":   # the planes stay back to back
-            chan_stride = int(row_stride) * resize_window(desc, window).h
-        t.row_stride = int(row_stride)
-    if chan_stride is not None:
-        t.chan_stride = int(chan_stride)
-    return t
+    return _layout_struct(ResizeDest, "resize_dest", layout, row_stride, chan_stride,
+                          lambda t, kind: _lib().lanczos_resize_dest_init(t, ctypes.byref(desc), _window_ref(desc, window), kind),
+                          lambda: resize_window(desc, window).h)
 
 
 def resize_dest_validate(desc, dest, window=None):
     """lanczos_resize_dest_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the layout is refused."""
     _check(_lib().lanczos_resize_dest_validate(ctypes.byref(desc), _window_ref(desc, window),
-                                               ctypes.byref(dest) if dest is not None else None), "lanczos_resize_dest_validate")
+                                               _ref(dest)), "lanczos_resize_dest_validate")
 
 
 def ycc_source(desc, layout="nv12", sub_x=None, sub_y=None, y_row_stride=None, c_row_stride=None, cb_offset=None, cr_offset=None):
@@ -750,7 +706,7 @@ def ycc_source(desc, layout="nv12", sub_x=None, sub_y=None, y_row_stride=None, c
 
 
 def ycc_source_validate(desc, source):
-    _check(_lib().lanczos_ycc_source_validate(ctypes.byref(desc), ctypes.byref(source) if source is not None else None),
+    _check(_lib().lanczos_ycc_source_validate(ctypes.byref(desc), _ref(source)),
            "lanczos_ycc_source_validate")
 
 
@@ -786,12 +742,26 @@ def _ycc_table_arg(standard, table, what):
     return table
 
 
-def _planar_frames(img, what):
-    """uint8 (C, H, W) or (N, C, H, W) -> a contiguous (N, C, H, W) array"""
+def _frames(img, dtypes, what, planar=False):
+    """An image as the host wrappers take it -- [H][W], [H][W][C] or [F][H][W][C], with planar [C][H][W] or [F][C][H][W] -- of
+    one of `dtypes`: (the contiguous 4-D array, (f, h, w, c), back), where back(out) gives a 4-D result the axes img had;
+    back(out, True) keeps the channel axis of a 2-D image, as the tensor calls do."""
     img = np.ascontiguousarray(img)
-    if img.dtype != np.uint8 or img.ndim not in (3, 4):
-        raise LanczosError(ERR_BAD_ARG, f"{what}: planar=True takes a uint8 [C][H][W] or [F][C][H][W] array")
-    return img if img.ndim == 4 else img[None]
+    if img.dtype not in dtypes or img.ndim not in ((3, 4) if planar else (2, 3, 4)):
+        names = " or ".join(np.dtype(t).name for t in dtypes)
+        if planar:
+            raise LanczosError(ERR_BAD_ARG, f"{what}: planar=True takes a {names} [C][H][W] or [F][C][H][W] array")
+        raise LanczosError(ERR_BAD_ARG, f"{what}: expected a {names} [H][W], [H][W][C] or [F][H][W][C] array")
+    ndim = img.ndim
+    x = img.reshape(img.shape + (1,)) if ndim == 2 else img
+    x = x if x.ndim == 4 else x[None]
+    f, h, w, c = (x.shape[0], x.shape[2], x.shape[3], x.shape[1]) if planar else x.shape
+
+    def back(out, keep_channels=False):
+        if ndim == 2 and not keep_channels:
+            return out[0, :, :, 0]
+        return out if ndim == 4 else out[0]
+    return x, (f, h, w, c), back
 
 
 def center_window(out_w, out_h, w, h):
@@ -860,22 +830,65 @@ def tensor_strides(layout, out_w, out_h, channels):
     raise LanczosError(ERR_BAD_ARG, f"unknown layout {layout!r}: chw or hwc")
 
 
-def tensor_out(d_lut, strides):
-    """A TensorOut: d_lut a pointer to channels * 256 floats (device memory for the device entry), strides =
-    (chan_stride, row_stride, pix_stride) in floats.  Validated where it is used (resize_tensor_validate)."""
-    t = TensorOut()
+def _flip_arg(flip, frames, what):
+    """The flip of a host tensor call, None / "h" / "v" / "hv" or one integer per frame: (the bits for every frame, the uint8
+    array of one entry per frame or None)."""
+    if flip is not None and not isinstance(flip, str):
+        flips = np.ascontiguousarray(flip)
+        if flips.shape != (frames,) or flips.dtype.kind not in "iub" or ((flips < 0) | (flips > 3)).any():
+            raise LanczosError(ERR_BAD_ARG, f"{what}: flip is 'h', 'v', 'hv' or {frames} integers 0 .. 3, one per frame")
+        return 0, flips.astype(np.uint8)
+    if flip not in _FLIP_NAMES:
+        raise LanczosError(ERR_BAD_ARG, f"{what}: flip is 'h', 'v', 'hv' or one integer per frame, not {flip!r}")
+    return _FLIP_NAMES[flip], None
+
+
+def _lut_arg(lut, mean, std, c, dtype, what):
+    """The table of a host tensor call for c output channels, contiguous: the caller's, or normalize_lut(c, mean, std, dtype)."""
+    wide = dtype == "float32"
+    if lut is None:
+        if c == 2:   # lanczos_tensor_lut_normalize builds 1, 3 or 4 channels: two rows of one
+            m, s = (None if v is None else np.broadcast_to(np.asarray(v, dtype=np.float32), (2,)) for v in (mean, std))
+            lut = np.concatenate([normalize_lut(1, None if m is None else m[k], None if s is None else s[k], dtype)
+                                  for k in range(2)])
+        else:
+            lut = normalize_lut(c, mean, std, dtype)
+    elif mean is not None or std is not None:
+        raise LanczosError(ERR_BAD_ARG, f"{what}: a table or mean / std, not both")
+    lut = np.ascontiguousarray(lut)
+    if lut.dtype not in ((np.float32,) if wide else (np.uint16, np.float16)) or lut.size != c * 256:
+        raise LanczosError(ERR_BAD_ARG, f"{what}: the table is {'float32' if wide else 'uint16 or float16'} [{c}][256]")
+    return lut
+
+
+def _tensor_out(cls, d_lut, strides):
+    t = cls()
     t.d_lut = d_lut
     t.chan_stride, t.row_stride, t.pix_stride = (int(v) for v in strides)
     return t
+
+
+def _fill_view(s, strides, src, flip, d_flip):
+    """what TensorView and TensorNorm share: the strides, the channel map and the flips"""
+    s.chan_stride, s.row_stride, s.pix_stride = (int(x) for x in strides)
+    s.out_channels = len(src)
+    for oc, sc in enumerate(src):
+        s.src_channel[oc] = sc
+    s.flip = _FLIP_NAMES[flip] if flip in _FLIP_NAMES else int(flip)
+    s.d_flip = d_flip
+    return s
+
+
+def tensor_out(d_lut, strides):
+    """A TensorOut: d_lut a pointer to channels * 256 floats (device memory for the device entry), strides =
+    (chan_stride, row_stride, pix_stride) in floats.  Validated where it is used (resize_tensor_validate)."""
+    return _tensor_out(TensorOut, d_lut, strides)
 
 
 def tensor16_out(d_lut, strides):
     """A TensorOut16: d_lut a pointer to channels * 256 16-bit words (device memory for the device entry), strides =
     (chan_stride, row_stride, pix_stride) in elements.  Validated where it is used (resize_tensor16_validate)."""
-    t = TensorOut16()
-    t.d_lut = d_lut
-    t.chan_stride, t.row_stride, t.pix_stride = (int(v) for v in strides)
-    return t
+    return _tensor_out(TensorOut16, d_lut, strides)
 
 
 def tensor_view_init(desc, elem_bytes=4):
@@ -893,17 +906,11 @@ def tensor_view(d_lut, strides, elem_bytes=4, channels_out=(0, 1, 2), flip=0, d_
     device memory for the device entry.  Validated where it is used (resize_tensor_view_validate)."""
     v = TensorView()
     v.d_lut = d_lut
-    v.chan_stride, v.row_stride, v.pix_stride = (int(x) for x in strides)
     v.elem_bytes = int(elem_bytes)
     src = [int(c) for c in channels_out]
     if len(src) > 4:
         raise LanczosError(ERR_BAD_ARG, "tensor_view: at most four output channels")
-    v.out_channels = len(src)
-    for oc, sc in enumerate(src):
-        v.src_channel[oc] = sc
-    v.flip = _FLIP_NAMES[flip] if flip in _FLIP_NAMES else int(flip)
-    v.d_flip = d_flip
-    return v
+    return _fill_view(v, strides, src, flip, d_flip)
 
 
 def tensor_norm_init(desc, dtype="float32", layout="chw"):
@@ -934,21 +941,15 @@ def tensor_norm(strides, div=1.0, mean=0.0, std=1.0, dtype="float32", channels_o
         a = np.broadcast_to(a, (len(src),))
         for oc in range(len(src)):
             getattr(n, name)[oc] = a[oc]
-    n.chan_stride, n.row_stride, n.pix_stride = (int(x) for x in strides)
     n.format = _TENSOR_NORM_FORMATS[dtype]
-    n.out_channels = len(src)
-    for oc, sc in enumerate(src):
-        n.src_channel[oc] = sc
-    n.flip = _FLIP_NAMES[flip] if flip in _FLIP_NAMES else int(flip)
-    n.d_flip = d_flip
-    return n
+    return _fill_view(n, strides, src, flip, d_flip)
 
 
 def resize_tensor_norm_validate(desc, n, window=None):
     """lanczos_resize_tensor_norm_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the request is refused.
     window: the strides describe that window's frame."""
     _check(_lib().lanczos_resize_tensor_norm_validate(ctypes.byref(desc), _window_ref(desc, window),
-                                                      ctypes.byref(n) if n is not None else None),
+                                                      _ref(n)),
            "lanczos_resize_tensor_norm_validate")
 
 
@@ -956,30 +957,29 @@ def resize_tensor_view_validate(desc, v, window=None):
     """lanczos_resize_tensor_view_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the view is refused.
     window: the strides describe that window's frame."""
     _check(_lib().lanczos_resize_tensor_view_validate(ctypes.byref(desc), _window_ref(desc, window),
-                                                      ctypes.byref(v) if v is not None else None),
+                                                      _ref(v)),
            "lanczos_resize_tensor_view_validate")
+
+
+def _tensor_validate(kind, desc, t, window):
+    """the body of resize_tensor_validate ("tensor") / resize_tensor16_validate ("tensor16")"""
+    if window is None:
+        name, args = f"lanczos_resize_{kind}_validate", (_ref(t),)
+    else:
+        name, args = f"lanczos_resize_{kind}_window_validate", (_window_ref(desc, window), _ref(t))
+    _check(getattr(_lib(), name)(ctypes.byref(desc), *args), name)
 
 
 def resize_tensor16_validate(desc, t, window=None):
     """lanczos_resize_tensor16_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the request is refused.
     window: the strides describe that window's frame (lanczos_resize_tensor16_window_validate)."""
-    tp = ctypes.byref(t) if t is not None else None
-    if window is None:
-        _check(_lib().lanczos_resize_tensor16_validate(ctypes.byref(desc), tp), "lanczos_resize_tensor16_validate")
-    else:
-        _check(_lib().lanczos_resize_tensor16_window_validate(ctypes.byref(desc), _window_ref(desc, window), tp),
-               "lanczos_resize_tensor16_window_validate")
+    _tensor_validate("tensor16", desc, t, window)
 
 
 def resize_tensor_validate(desc, t, window=None):
     """lanczos_resize_tensor_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the request is refused.
     window: the strides describe that window's frame (lanczos_resize_tensor_window_validate)."""
-    tp = ctypes.byref(t) if t is not None else None
-    if window is None:
-        _check(_lib().lanczos_resize_tensor_validate(ctypes.byref(desc), tp), "lanczos_resize_tensor_validate")
-    else:
-        _check(_lib().lanczos_resize_tensor_window_validate(ctypes.byref(desc), _window_ref(desc, window), tp),
-               "lanczos_resize_tensor_window_validate")
+    _tensor_validate("tensor", desc, t, window)
 
 
 def _factor_pair(factor):
@@ -1022,6 +1022,101 @@ class PinnedArray:
             pass
 
 
+# -- which entry a request takes, one function per family.  side is "device" or "host"; has[p] says whether the request has
+# argument p ("opts": a box, a gap or ready options; "window"; and the family's own .params); the result is the entry's name and
+# its arguments between (ctx, desc) and (in, out, frames).  A request keeps the narrowest entry that can carry it: an older
+# build of the library has only those, and LanczosError names the entry.
+def _bytes_entry(side, has):
+    """bytes out: dest > source > window > opts > plain"""
+    if has["dest"]:
+        return "lanczos_resize_dest_" + side, ("opts", "window", "source", "dest")
+    if has["source"]:
+        return "lanczos_resize_source_" + side, ("opts", "window", "source")
+    if has["window"]:
+        return "lanczos_resize_window_" + side, ("opts", "window")
+    if has["opts"]:
+        return "lanczos_resize_" + side + "_ex", ("opts",)
+    return "lanczos_resize_" + side, ()
+
+
+def _tensor_entry(side, has):
+    """tensor out: source > crops > view > {float32, 16-bit} x {window, none}; has["t"] is the class of the tensor struct, a
+    TensorView (which a source and crops need), a TensorOut or a TensorOut16"""
+    if has["source"]:
+        return "lanczos_resize_tensor_source_" + side, ("opts", "window", "crops", "source", "t")
+    if has["crops"]:
+        return "lanczos_resize_tensor_crops_" + side, ("opts", "crops", "t")
+    if has["t"] is TensorView:
+        return "lanczos_resize_tensor_view_" + side, ("opts", "window", "t")
+    stem = "lanczos_resize_tensor16_" if has["t"] is TensorOut16 else "lanczos_resize_tensor_"
+    if has["window"]:
+        return stem + "window_" + side, ("opts", "window", "t")
+    return stem + side, ("opts", "t")
+
+
+def _norm_entry(side, has):
+    return "lanczos_resize_tensor_norm_" + side, ("opts", "window", "source", "norm")
+
+
+def _ycc_entry(side, has):
+    """RGB bytes, or with a TensorView tensor elements"""
+    if has["view"]:
+        return "lanczos_resize_ycc_tensor_" + side, ("opts", "window", "source", "table", "view")
+    return "lanczos_resize_ycc_" + side, ("opts", "window", "source", "table")
+
+
+_bytes_entry.params = ("source", "dest")
+_tensor_entry.params = ("crops", "source", "t")
+_norm_entry.params = ("source", "norm")
+_ycc_entry.params = ("source", "table", "view")
+
+
+class _Bound(dict):
+    """The resize entries of one context, resolved once per request shape so that a call costs no more than the call itself:
+    bound[chooser, side, has opts, has window, *(one flag per chooser.params)] is a function
+    issue(desc, box, reducing_gap, opts, window, *params, in, out, frames[, in_frame_stride, out_frame_stride, stream]) that
+    passes the entry the chooser picked exactly the arguments that shape has -- a struct by reference, a missing one as NULL,
+    options and window resolved by _opts_ref / _window_ref, the colour table as it is -- and raises LanczosError(code, entry)
+    on any code but OK.  The function is compiled from the chooser's answer the first time the shape is seen."""
+
+    def __init__(self, handle):
+        self.handle = handle
+
+    def __missing__(self, key):
+        chooser, side, *flags = key
+        params = ("opts", "window") + chooser.params
+        has = dict(zip(params, flags))
+        name, middle = chooser(side, has)
+        forms = {"opts": "_opts_ref(desc, box, reducing_gap, opts)", "window": "_window_ref(desc, window)", "table": "table"}
+        args = ", ".join(["byref(desc)"] + [forms.get(p, f"byref({p})") if has[p] else "None" for p in middle])
+        tail = "d_in, d_out, frames" + (", in_frame_stride, out_frame_stride, stream" if side == "device" else "")
+        scope = {"entry": getattr(_lib(), name), "handle": self.handle, "name": name, "byref": ctypes.byref, "_opts_ref": _opts_ref,
+                 "_window_ref": _window_ref, "LanczosError": LanczosError}
+        exec(f"def issue(desc, box, reducing_gap, {', '.join(params)}, {tail}):\n"
+             f"    rc = entry(handle, {args}, {tail})\n"
+             f"    if rc:\n"
+             f"        raise LanczosError(rc, name)\n", scope)
+        self[key] = scope["issue"]
+        return scope["issue"]
+
+
+def _reduce_entry(side, in_w, in_h, channels, factor, box):
+    fx, fy = _factor_pair(factor)
+    b = (ctypes.c_int32 * 4)(*[int(v) for v in box]) if box is not None else None
+    return "lanczos_reduce_" + side, in_w, in_h, channels, fx, fy, b
+
+
+def _tensor_view_arg(strides, d_lut, dtype, channels_out, channels, flip, d_flip, what):
+    """the view of a device tensor call: a ready TensorView, or one of strides, d_lut, dtype and the map (None = the identity
+    over `channels` channels)"""
+    if isinstance(strides, TensorView):
+        return strides
+    if dtype != "float32":
+        _tensor16_format(dtype, what)
+    return tensor_view(d_lut, strides, 4 if dtype == "float32" else 2,
+                       channels_out if channels_out is not None else tuple(range(channels)), flip or 0, d_flip)
+
+
 class Context:
     """One lanczos_ctx: a device, a stream, resident tap tables.  Not shared between threads."""
 
@@ -1029,10 +1124,18 @@ class Context:
         self._h = ctypes.c_void_p()
         _check(_lib().lanczos_create(ctypes.byref(self._h), device), "lanczos_create")
 
+    @_cached_property
+    def _bound(self):
+        return _Bound(self._h)
+
+    def _call(self, name, *args):
+        """entry `name` on this context; any code but OK raises LanczosError(code, name)"""
+        _check(getattr(_lib(), name)(self._h, *args), name)
+
     def close(self):
         if self._h:
             _lib().lanczos_destroy(self._h)
-            self._h = ctypes.c_void_p()
+            self._h.value = None   # in place: the bound entries hold this object
 
     def __del__(self):
         try:
@@ -1057,8 +1160,7 @@ class Context:
             if out.dtype != x.dtype or out.size != f * d.out_h * d.out_w * c or not out.flags["C_CONTIGUOUS"]:
                 raise LanczosError(ERR_BAD_ARG, "resample: `out` has the wrong size/dtype/layout")
             out = out.reshape((f, d.out_h, d.out_w, c))
-        _check(_lib().lanczos_resample_host(self._h, ctypes.byref(d), x.ctypes.data, out.ctypes.data, f),
-               "lanczos_resample_host")
+        self._call("lanczos_resample_host", ctypes.byref(d), x.ctypes.data, out.ctypes.data, f)
         return out if batched else out[0]
 
     def resample_strip(self, strip_in, desc):
@@ -1070,8 +1172,7 @@ class Context:
             raise LanczosError(ERR_BAD_ARG, f"resample_strip: expected [{need}][{desc.in_w}][{desc.channels}] samples of "
                                             f"{desc.bytes_per_sample} byte(s), got {strip_in.shape} {strip_in.dtype}")
         out = np.empty((desc.out_rows, desc.out_w, desc.channels), dtype=strip_in.dtype)
-        _check(_lib().lanczos_resample_host(self._h, ctypes.byref(desc), strip_in.ctypes.data,
-                                            out.ctypes.data, 1), "lanczos_resample_host")
+        self._call("lanczos_resample_host", ctypes.byref(desc), strip_in.ctypes.data, out.ctypes.data, 1)
         return out
 
     def u8(self, img, out_w, out_h, a):
@@ -1079,30 +1180,22 @@ class Context:
         img = np.ascontiguousarray(img, dtype=np.uint8)
         h, w, c = img.shape
         out = np.empty((out_h, out_w, c), dtype=np.uint8)
-        _check(_lib().lanczos_u8(self._h, img.ctypes.data, w, h, c, out.ctypes.data, out_w, out_h, a),
-               "lanczos_u8")
+        self._call("lanczos_u8", img.ctypes.data, w, h, c, out.ctypes.data, out_w, out_h, a)
         return out
 
     # -- device buffers (raw pointers, e.g. torch tensors' data_ptr()), asynchronous
     def resample_device(self, desc, d_in, d_out, frames, in_frame_stride=0, out_frame_stride=0, stream=None):
-        _check(_lib().lanczos_resample_device(self._h, ctypes.byref(desc), d_in, d_out, frames,
-                                              in_frame_stride, out_frame_stride, stream),
-               "lanczos_resample_device")
+        self._call("lanczos_resample_device", ctypes.byref(desc), d_in, d_out, frames, in_frame_stride, out_frame_stride, stream)
 
     # -- planar frames [C][H][W] (the reference's img_in / img_out_ex arrays, full_TB.h:20-21), device pointers
     def planar_to_interleaved_device(self, d_planar, d_inter, w, h, channels, bytes_per_sample, frames, stream=None):
-        _check(_lib().lanczos_planar_to_interleaved_device(self._h, d_planar, d_inter, w, h, channels,
-                                                           bytes_per_sample, frames, stream),
-               "lanczos_planar_to_interleaved_device")
+        self._call("lanczos_planar_to_interleaved_device", d_planar, d_inter, w, h, channels, bytes_per_sample, frames, stream)
 
     def interleaved_to_planar_device(self, d_inter, d_planar, w, h, channels, bytes_per_sample, frames, stream=None):
-        _check(_lib().lanczos_interleaved_to_planar_device(self._h, d_inter, d_planar, w, h, channels,
-                                                           bytes_per_sample, frames, stream),
-               "lanczos_interleaved_to_planar_device")
+        self._call("lanczos_interleaved_to_planar_device", d_inter, d_planar, w, h, channels, bytes_per_sample, frames, stream)
 
     def resample_planar_device(self, desc, d_in_planar, d_out_planar, frames, stream=None):
-        _check(_lib().lanczos_resample_planar_device(self._h, ctypes.byref(desc), d_in_planar, d_out_planar, frames,
-                                                     stream), "lanczos_resample_planar_device")
+        self._call("lanczos_resample_planar_device", ctypes.byref(desc), d_in_planar, d_out_planar, frames, stream)
 
     # -- resize to any size (Pillow's contract, lanczos_resize_*)
     def resize(self, img, out_w, out_h, a=3, alpha=False, box=None, reducing_gap=None, filter=FILTER_LANCZOS, window=None,
@@ -1128,58 +1221,25 @@ class Context:
         channels) by default, mode RGBA (straight alpha in the last channel, premultiplied inside the kernels) with
         alpha=True; alpha=True with any other channel count raises LanczosError(ERR_BAD_ARG).  uint16: every channel as
         Pillow resizes an I;16 plane (a sum above 65535 stores 0xFF00 | low byte, as Pillow does); not with alpha."""
-        if planar_out:
-            if planar:
-                x = _planar_frames(img, "resize")
-                f, c, h, w = x.shape
-            else:
-                x = np.ascontiguousarray(img)
-                if x.dtype != np.uint8 or x.ndim not in (3, 4) or x.shape[-1] not in (3, 4):
-                    raise LanczosError(ERR_BAD_ARG, "resize: planar_out=True takes uint8 frames of 3 or 4 channels")
-                x = x if x.ndim == 4 else x[None]
-                f, h, w, c = x.shape
-            d = resize_desc(w, h, out_w, out_h, c, a, alpha, filter=filter)
-            win = resize_window(d, window)
-            wref = ctypes.byref(win) if window is not None else None
-            out = np.empty((f, c, win.h, win.w), dtype=np.uint8)
-            _check(_lib().lanczos_resize_dest_host(self._h, ctypes.byref(d), _opts_ref(d, box, reducing_gap, None), wref,
-                                                   ctypes.byref(resize_source(d, "planar")) if planar else None,
-                                                   ctypes.byref(resize_dest(d, "planar", window=window)), x.ctypes.data,
-                                                   out.ctypes.data, f), "lanczos_resize_dest_host")
-            return out if np.ndim(img) == 4 else out[0]
-        if planar:
-            x = _planar_frames(img, "resize")
-            f, c, h, w = x.shape
-            d = resize_desc(w, h, out_w, out_h, c, a, alpha, filter=filter)
-            win = resize_window(d, window)
-            out = np.empty((f, win.h, win.w, c), dtype=np.uint8)
-            _check(_lib().lanczos_resize_source_host(self._h, ctypes.byref(d), _opts_ref(d, box, reducing_gap, None),
-                                                     ctypes.byref(win) if window is not None else None,
-                                                     ctypes.byref(resize_source(d, "planar")), x.ctypes.data, out.ctypes.data, f),
-                   "lanczos_resize_source_host")
-            return out if np.ndim(img) == 4 else out[0]
-        img = np.ascontiguousarray(img)
-        if img.dtype not in (np.uint8, np.uint16) or img.ndim not in (2, 3, 4):
-            raise LanczosError(ERR_BAD_ARG, "resize: expected a uint8 or uint16 [H][W], [H][W][C] or [F][H][W][C] array")
-        x = img.reshape(img.shape + (1,)) if img.ndim == 2 else img
-        x = x if x.ndim == 4 else x[None]
-        f, h, w, c = x.shape
-        d = resize_desc(w, h, out_w, out_h, c, a, alpha, 8 * img.dtype.itemsize, filter=filter)
+        if planar_out and not planar:
+            img = np.asarray(img)
+            if img.dtype != np.uint8 or img.ndim not in (3, 4) or img.shape[-1] not in (3, 4):
+                raise LanczosError(ERR_BAD_ARG, "resize: planar_out=True takes uint8 frames of 3 or 4 channels")
+        return self._resize_host("resize", img, (np.uint8,) if planar or planar_out else (np.uint8, np.uint16), out_w, out_h, a,
+                                 alpha, box, reducing_gap, filter, window, planar, planar_out)
+
+    def _resize_host(self, what, img, dtypes, out_w, out_h, a, alpha, box, reducing_gap, filter, window, planar=False,
+                     planar_out=False):
+        """the body of resize and resize_f32: frames of one of `dtypes` in, the same dtype out"""
+        x, (f, h, w, c), back = _frames(img, dtypes, what, planar)
+        d = resize_desc(w, h, out_w, out_h, c, a, alpha, 16 if x.dtype == np.uint16 else 8, x.dtype == np.float32, filter)
         win = resize_window(d, window)
-        out = np.empty((f, win.h, win.w, c), dtype=img.dtype)
-        if window is not None:
-            _check(_lib().lanczos_resize_window_host(self._h, ctypes.byref(d), _opts_ref(d, box, reducing_gap, None),
-                                                     ctypes.byref(win), x.ctypes.data, out.ctypes.data, f),
-                   "lanczos_resize_window_host")
-        elif box is None and reducing_gap is None:
-            _check(_lib().lanczos_resize_host(self._h, ctypes.byref(d), x.ctypes.data, out.ctypes.data, f),
-                   "lanczos_resize_host")
-        else:
-            _check(_lib().lanczos_resize_host_ex(self._h, ctypes.byref(d), _opts_ref(d, box, reducing_gap, None),
-                                                 x.ctypes.data, out.ctypes.data, f), "lanczos_resize_host_ex")
-        if img.ndim == 2:
-            return out[0, :, :, 0]
-        return out if img.ndim == 4 else out[0]
+        source = resize_source(d, "planar") if planar else None
+        dest = resize_dest(d, "planar", window=window) if planar_out else None
+        out = np.empty((f, c, win.h, win.w) if planar_out else (f, win.h, win.w, c), dtype=x.dtype)
+        self._bound[_bytes_entry, "host", box is not None or reducing_gap is not None, window is not None, bool(planar), bool(planar_out)](
+            d, box, reducing_gap, None, win if window is not None else None, source, dest, x.ctypes.data, out.ctypes.data, f)
+        return back(out)
 
     def resize_f32(self, img, out_w, out_h, a=3, box=None, filter=FILTER_LANCZOS, window=None):
         """filter and window as Context.resize.
@@ -1187,28 +1247,7 @@ class Context:
         bit for bit what Pillow's Image.resize((out_w, out_h), Image.LANCZOS, box) gives for it as a mode F plane (a = 3):
         double accumulation over exactly the window's taps, stored as float -- no clamp, inf on overflow, denormals kept, NaN
         where Pillow has NaN.  box as Context.resize.  No alpha and no reducing_gap for floats."""
-        img = np.ascontiguousarray(img)
-        if img.dtype != np.float32 or img.ndim not in (2, 3, 4):
-            raise LanczosError(ERR_BAD_ARG, "resize_f32: expected a float32 [H][W], [H][W][C] or [F][H][W][C] array")
-        x = img.reshape(img.shape + (1,)) if img.ndim == 2 else img
-        x = x if x.ndim == 4 else x[None]
-        f, h, w, c = x.shape
-        d = resize_desc(w, h, out_w, out_h, c, a, f32=True, filter=filter)
-        win = resize_window(d, window)
-        out = np.empty((f, win.h, win.w, c), dtype=np.float32)
-        if window is not None:
-            _check(_lib().lanczos_resize_window_host(self._h, ctypes.byref(d), _opts_ref(d, box, None, None),
-                                                     ctypes.byref(win), x.ctypes.data, out.ctypes.data, f),
-                   "lanczos_resize_window_host")
-        elif box is None:
-            _check(_lib().lanczos_resize_host(self._h, ctypes.byref(d), x.ctypes.data, out.ctypes.data, f),
-                   "lanczos_resize_host")
-        else:
-            _check(_lib().lanczos_resize_host_ex(self._h, ctypes.byref(d), _opts_ref(d, box, None, None),
-                                                 x.ctypes.data, out.ctypes.data, f), "lanczos_resize_host_ex")
-        if img.ndim == 2:
-            return out[0, :, :, 0]
-        return out if img.ndim == 4 else out[0]
+        return self._resize_host("resize_f32", img, (np.float32,), out_w, out_h, a, False, box, None, filter, window)
 
     def resize_device(self, desc, d_in, d_out, frames, in_frame_stride=0, out_frame_stride=0, stream=None, box=None,
                       reducing_gap=None, opts=None, filter=None, window=None, source=None, dest=None):
@@ -1225,26 +1264,9 @@ class Context:
             d = ResizeDesc.from_buffer_copy(desc)
             d.reserved[0] = (d.reserved[0] & ~(15 << 8)) | (filter_code(filter) << 8)
             desc = d
-        if dest is not None:
-            _check(_lib().lanczos_resize_dest_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
-                                                     _window_ref(desc, window), ctypes.byref(source) if source is not None else None,
-                                                     ctypes.byref(dest), d_in, d_out, frames, in_frame_stride, out_frame_stride,
-                                                     stream), "lanczos_resize_dest_device")
-        elif source is not None:
-            _check(_lib().lanczos_resize_source_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
-                                                       _window_ref(desc, window), ctypes.byref(source), d_in, d_out, frames,
-                                                       in_frame_stride, out_frame_stride, stream), "lanczos_resize_source_device")
-        elif window is not None:
-            _check(_lib().lanczos_resize_window_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
-                                                       _window_ref(desc, window), d_in, d_out, frames, in_frame_stride,
-                                                       out_frame_stride, stream), "lanczos_resize_window_device")
-        elif box is None and reducing_gap is None and opts is None:
-            _check(_lib().lanczos_resize_device(self._h, ctypes.byref(desc), d_in, d_out, frames, in_frame_stride,
-                                                out_frame_stride, stream), "lanczos_resize_device")
-        else:
-            _check(_lib().lanczos_resize_device_ex(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
-                                                   d_in, d_out, frames, in_frame_stride, out_frame_stride, stream),
-                   "lanczos_resize_device_ex")
+        self._bound[_bytes_entry, "device", box is not None or reducing_gap is not None or opts is not None, window is not None,
+                    source is not None, dest is not None](
+            desc, box, reducing_gap, opts, window, source, dest, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream)
 
     # -- resize straight into a float tensor (PIL.Image.resize -> ToTensor() -> Normalize(), lanczos_resize_tensor_*)
     def resize_tensor(self, img, out_w, out_h, mean=None, std=None, lut=None, layout="chw", a=3, alpha=False, box=None,
@@ -1273,102 +1295,39 @@ class Context:
         wide = dtype == "float32"
         if not wide:
             _tensor16_format(dtype, "resize_tensor")
-        if planar:
-            x = _planar_frames(img, "resize_tensor")
-            f, c, h, w = x.shape
-            img = x if np.ndim(img) == 4 else x[0]
-        else:
-            img = np.ascontiguousarray(img)
-            if img.dtype != np.uint8 or img.ndim not in (2, 3, 4):
-                raise LanczosError(ERR_BAD_ARG, "resize_tensor: expected a uint8 [H][W], [H][W][C] or [F][H][W][C] array")
-            x = img.reshape(img.shape + (1,)) if img.ndim == 2 else img
-            x = x if x.ndim == 4 else x[None]
-            f, h, w, c = x.shape
+        x, (f, h, w, c), back = _frames(img, (np.uint8,), "resize_tensor", planar)
         d = resize_desc(w, h, out_w, out_h, c, a, alpha, filter=filter)
-        view = planar or channels_out is not None or flip is not None
+        view = planar or channels_out is not None or flip is not None or crop is not None
         if channels_out is not None:
             channels_out = tuple(int(v) for v in channels_out)
             if not 1 <= len(channels_out) <= c:
                 raise LanczosError(ERR_BAD_ARG, f"resize_tensor: channels_out names 1 to {c} source channels")
             c = len(channels_out)
-        if lut is None:
-            if c == 2:   # lanczos_tensor_lut_normalize builds 1, 3 or 4 channels: two rows of one
-                m, s = (None if v is None else np.broadcast_to(np.asarray(v, dtype=np.float32), (2,)) for v in (mean, std))
-                lut = np.concatenate([normalize_lut(1, None if m is None else m[k], None if s is None else s[k], dtype)
-                                      for k in range(2)])
-            else:
-                lut = normalize_lut(c, mean, std, dtype)
-        elif mean is not None or std is not None:
-            raise LanczosError(ERR_BAD_ARG, "resize_tensor: a table or mean / std, not both")
-        lut = np.ascontiguousarray(lut)
-        if lut.dtype not in ((np.float32,) if wide else (np.uint16, np.float16)) or lut.size != c * 256:
-            raise LanczosError(ERR_BAD_ARG, f"resize_tensor: the table is {'float32' if wide else 'uint16 or float16'} [{c}][256]")
+        lut = _lut_arg(lut, mean, std, c, dtype, "resize_tensor")
         if (crop is None) != (origins is None) or (crop is not None and window is not None):
             raise LanczosError(ERR_BAD_ARG, "resize_tensor: crop= and origins= come together, and not with window=")
-        org = None
         if crop is not None:
             org = np.ascontiguousarray(origins)
             if len(crop) != 2 or org.shape != (f, 2) or org.dtype.kind not in "iu":
                 raise LanczosError(ERR_BAD_ARG, f"resize_tensor: crop is (w, h) and origins {f} integer pairs (x0, y0)")
             org = org.astype(np.int32)
             window = (0, 0, int(crop[0]), int(crop[1]))   # the frame the strides describe
-            view = True
         win = resize_window(d, window)
         strides = tensor_strides(layout, win.w, win.h, c)
         shape = (f, c, win.h, win.w) if layout == "chw" else (f, win.h, win.w, c)
-        opts = _opts_ref(d, box, reducing_gap, None)
-        wref = ctypes.byref(win) if window is not None else None
+        cr = resize_crops(win.w, win.h, org.ctypes.data) if crop is not None else None   # (the window is then no argument)
         if view:
-            flips = None
-            if flip is not None and not isinstance(flip, str):
-                flips = np.ascontiguousarray(flip)
-                if flips.shape != (f,) or flips.dtype.kind not in "iub" or ((flips < 0) | (flips > 3)).any():
-                    raise LanczosError(ERR_BAD_ARG, f"resize_tensor: flip is 'h', 'v', 'hv' or {f} integers 0 .. 3, one per frame")
-                flips = flips.astype(np.uint8)
-            elif flip not in _FLIP_NAMES:
-                raise LanczosError(ERR_BAD_ARG, f"resize_tensor: flip is 'h', 'v', 'hv' or one integer per frame, not {flip!r}")
-            v = tensor_view(lut.ctypes.data, strides, 4 if wide else 2,
-                            channels_out if channels_out is not None else tuple(range(c)),
-                            0 if flips is not None else flip, flips.ctypes.data if flips is not None else None)
-            out = np.empty(shape, dtype=np.float32 if wide else np.uint16)
-            if planar:
-                cr = resize_crops(win.w, win.h, org.ctypes.data) if org is not None else None
-                _check(_lib().lanczos_resize_tensor_source_host(self._h, ctypes.byref(d), opts, None if cr is not None else wref,
-                                                                ctypes.byref(cr) if cr is not None else None,
-                                                                ctypes.byref(resize_source(d, "planar")), ctypes.byref(v),
-                                                                x.ctypes.data, out.ctypes.data, f),
-                       "lanczos_resize_tensor_source_host")
-            elif org is not None:
-                cr = resize_crops(win.w, win.h, org.ctypes.data)
-                _check(_lib().lanczos_resize_tensor_crops_host(self._h, ctypes.byref(d), opts, ctypes.byref(cr), ctypes.byref(v),
-                                                               x.ctypes.data, out.ctypes.data, f),
-                       "lanczos_resize_tensor_crops_host")
-            else:
-                _check(_lib().lanczos_resize_tensor_view_host(self._h, ctypes.byref(d), opts, wref, ctypes.byref(v), x.ctypes.data,
-                                                              out.ctypes.data, f), "lanczos_resize_tensor_view_host")
-            out = out if wide else _tensor16_array(out, dtype)
-        elif wide:
-            t = tensor_out(lut.ctypes.data, strides)
-            out = np.empty(shape, dtype=np.float32)
-            if wref is None:
-                _check(_lib().lanczos_resize_tensor_host(self._h, ctypes.byref(d), opts, ctypes.byref(t), x.ctypes.data,
-                                                         out.ctypes.data, f), "lanczos_resize_tensor_host")
-            else:
-                _check(_lib().lanczos_resize_tensor_window_host(self._h, ctypes.byref(d), opts, wref, ctypes.byref(t),
-                                                                x.ctypes.data, out.ctypes.data, f),
-                       "lanczos_resize_tensor_window_host")
+            bits, flips = _flip_arg(flip, f, "resize_tensor")
+            t = tensor_view(lut.ctypes.data, strides, 4 if wide else 2, channels_out if channels_out is not None else tuple(range(c)),
+                            bits, flips.ctypes.data if flips is not None else None)
         else:
-            t = tensor16_out(lut.ctypes.data, strides)
-            out = np.empty(shape, dtype=np.uint16)
-            if wref is None:
-                _check(_lib().lanczos_resize_tensor16_host(self._h, ctypes.byref(d), opts, ctypes.byref(t), x.ctypes.data,
-                                                           out.ctypes.data, f), "lanczos_resize_tensor16_host")
-            else:
-                _check(_lib().lanczos_resize_tensor16_window_host(self._h, ctypes.byref(d), opts, wref, ctypes.byref(t),
-                                                                  x.ctypes.data, out.ctypes.data, f),
-                       "lanczos_resize_tensor16_window_host")
-            out = _tensor16_array(out, dtype)
-        return out if img.ndim == 4 else out[0]
+            t = (tensor_out if wide else tensor16_out)(lut.ctypes.data, strides)
+        source = resize_source(d, "planar") if planar else None
+        out = np.empty(shape, dtype=np.float32 if wide else np.uint16)
+        win = win if window is not None and cr is None else None
+        self._bound[_tensor_entry, "host", box is not None or reducing_gap is not None, win is not None, cr is not None, bool(planar),
+                    t.__class__](d, box, reducing_gap, None, win, cr, source, t, x.ctypes.data, out.ctypes.data, f)
+        return back(out if wide else _tensor16_array(out, dtype), True)
 
     def resize_tensor_device(self, desc, d_in, d_out, frames, d_lut, strides, in_frame_stride=0, out_frame_stride=0,
                              stream=None, box=None, reducing_gap=None, opts=None, dtype="float32", window=None,
@@ -1389,63 +1348,28 @@ class Context:
         dtype="bfloat16" / "float16" (or a ready TensorOut16): 16-bit elements at d_out and in the table, strides in
         elements, d_out and out_frame_stride multiples of 2.  window = (x0, y0, w, h) or a ResizeWindow: the element frames
         are that window of the output, and the strides describe its C x h x w frame (tensor_strides(layout, w, h, C))."""
-        oref = _opts_ref(desc, box, reducing_gap, opts)
         if crop is not None and window is not None:
             raise LanczosError(ERR_BAD_ARG, "resize_tensor_device: crop= or window=, not both")
         if (crop is None or not isinstance(crop, ResizeCrops)) and (crop is None) != (d_origin is None):
             raise LanczosError(ERR_BAD_ARG, "resize_tensor_device: crop=(w, h) and d_origin= come together")
-        wref = _window_ref(desc, window)
-        if source is not None and isinstance(strides, (TensorOut, TensorOut16)):   # the same request as a view
-            t = strides
-            strides = tensor_view(t.d_lut, (t.chan_stride, t.row_stride, t.pix_stride), 2 if isinstance(t, TensorOut16) else 4,
-                                  tuple(range(desc.channels)))
-        if source is not None or crop is not None or isinstance(strides, TensorView) or channels_out is not None or flip is not None or d_flip is not None:
-            if isinstance(strides, TensorView):
-                v = strides
-            else:
-                if dtype != "float32":
-                    _tensor16_format(dtype, "resize_tensor_device")
-                v = tensor_view(d_lut, strides, 4 if dtype == "float32" else 2,
-                                channels_out if channels_out is not None else tuple(range(desc.channels)), flip or 0, d_flip)
-            if source is not None:
-                cr = None if crop is None else crop if isinstance(crop, ResizeCrops) else resize_crops(crop[0], crop[1], d_origin)
-                _check(_lib().lanczos_resize_tensor_source_device(self._h, ctypes.byref(desc), oref, wref,
-                                                                  ctypes.byref(cr) if cr is not None else None, ctypes.byref(source),
-                                                                  ctypes.byref(v), d_in, d_out, frames, in_frame_stride,
-                                                                  out_frame_stride, stream), "lanczos_resize_tensor_source_device")
-                return
-            if crop is not None:
-                cr = crop if isinstance(crop, ResizeCrops) else resize_crops(crop[0], crop[1], d_origin)
-                _check(_lib().lanczos_resize_tensor_crops_device(self._h, ctypes.byref(desc), oref, ctypes.byref(cr), ctypes.byref(v),
-                                                                 d_in, d_out, frames, in_frame_stride, out_frame_stride, stream),
-                       "lanczos_resize_tensor_crops_device")
-                return
-            _check(_lib().lanczos_resize_tensor_view_device(self._h, ctypes.byref(desc), oref, wref, ctypes.byref(v), d_in,
-                                                            d_out, frames, in_frame_stride, out_frame_stride, stream),
-                   "lanczos_resize_tensor_view_device")
-            return
-        if isinstance(strides, TensorOut16) or dtype != "float32":
-            if not isinstance(strides, TensorOut16):
+        t = strides
+        if source is not None and isinstance(t, (TensorOut, TensorOut16)):   # the same request as a view
+            t = tensor_view(t.d_lut, (t.chan_stride, t.row_stride, t.pix_stride), 2 if isinstance(t, TensorOut16) else 4,
+                            tuple(range(desc.channels)))
+        if isinstance(t, TensorView):
+            pass
+        elif source is not None or crop is not None or channels_out is not None or flip is not None or d_flip is not None:
+            t = _tensor_view_arg(t, d_lut, dtype, channels_out, desc.channels, flip, d_flip, "resize_tensor_device")
+        elif isinstance(t, TensorOut16) or dtype != "float32":
+            if not isinstance(t, TensorOut16):
                 _tensor16_format(dtype, "resize_tensor_device")
-            t = strides if isinstance(strides, TensorOut16) else tensor16_out(d_lut, strides)
-            if wref is None:
-                _check(_lib().lanczos_resize_tensor16_device(self._h, ctypes.byref(desc), oref, ctypes.byref(t), d_in, d_out,
-                                                             frames, in_frame_stride, out_frame_stride, stream),
-                       "lanczos_resize_tensor16_device")
-            else:
-                _check(_lib().lanczos_resize_tensor16_window_device(self._h, ctypes.byref(desc), oref, wref, ctypes.byref(t),
-                                                                    d_in, d_out, frames, in_frame_stride, out_frame_stride,
-                                                                    stream), "lanczos_resize_tensor16_window_device")
-            return
-        t = strides if isinstance(strides, TensorOut) else tensor_out(d_lut, strides)
-        if wref is None:
-            _check(_lib().lanczos_resize_tensor_device(self._h, ctypes.byref(desc), oref, ctypes.byref(t), d_in, d_out, frames,
-                                                       in_frame_stride, out_frame_stride, stream),
-                   "lanczos_resize_tensor_device")
-        else:
-            _check(_lib().lanczos_resize_tensor_window_device(self._h, ctypes.byref(desc), oref, wref, ctypes.byref(t), d_in,
-                                                              d_out, frames, in_frame_stride, out_frame_stride, stream),
-                   "lanczos_resize_tensor_window_device")
+                t = tensor16_out(d_lut, t)
+        elif not isinstance(t, TensorOut):
+            t = tensor_out(d_lut, t)
+        cr = crop if crop is None or isinstance(crop, ResizeCrops) else resize_crops(crop[0], crop[1], d_origin)
+        self._bound[_tensor_entry, "device", box is not None or reducing_gap is not None or opts is not None, window is not None,
+                    cr is not None, source is not None, t.__class__](
+            desc, box, reducing_gap, opts, window, cr, source, t, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream)
 
     # -- 16-bit and float frames straight into normalised tensors (lanczos_resize_tensor_norm_*)
     def resize_tensor_norm(self, img, out_w, out_h, div=None, mean=None, std=None, dtype="float32", layout="chw", a=3, box=None,
@@ -1457,39 +1381,25 @@ class Context:
         .to(dtype) for dtype "bfloat16" (returned as np.uint16 patterns) or "float16" (np.float16).  div=None is 65535 for
         uint16 and 1 for float32; mean=None is 0, std=None is 1; each one value or one per channel of the result.  box, filter,
         window, channels_out and flip as Context.resize_tensor.  No reducing_gap, no alpha, no crop origins."""
-        img = np.ascontiguousarray(img)
-        if img.dtype not in (np.uint16, np.float32) or img.ndim not in (2, 3, 4):
-            raise LanczosError(ERR_BAD_ARG, "resize_tensor_norm: expected a uint16 or float32 [H][W], [H][W][C] or [F][H][W][C] array")
+        x, (f, h, w, c), back = _frames(img, (np.uint16, np.float32), "resize_tensor_norm")
         if dtype not in _TENSOR_NORM_FORMATS:
             raise LanczosError(ERR_BAD_ARG, f"resize_tensor_norm: dtype is 'float32', 'bfloat16' or 'float16', not {dtype!r}")
-        x = img.reshape(img.shape + (1,)) if img.ndim == 2 else img
-        x = x if x.ndim == 4 else x[None]
-        f, h, w, c = x.shape
-        u16 = img.dtype == np.uint16
+        u16 = x.dtype == np.uint16
         d = resize_desc(w, h, out_w, out_h, c, a, bits=16 if u16 else 8, f32=not u16, filter=filter)
         src = tuple(int(v) for v in channels_out) if channels_out is not None else tuple(range(c))
         if not 1 <= len(src) <= c:
             raise LanczosError(ERR_BAD_ARG, f"resize_tensor_norm: channels_out names 1 to {c} source channels")
         c = len(src)
-        flips = None
-        if flip is not None and not isinstance(flip, str):
-            flips = np.ascontiguousarray(flip)
-            if flips.shape != (f,) or flips.dtype.kind not in "iub" or ((flips < 0) | (flips > 3)).any():
-                raise LanczosError(ERR_BAD_ARG, f"resize_tensor_norm: flip is 'h', 'v', 'hv' or {f} integers 0 .. 3, one per frame")
-            flips = flips.astype(np.uint8)
-        elif flip not in _FLIP_NAMES:
-            raise LanczosError(ERR_BAD_ARG, f"resize_tensor_norm: flip is 'h', 'v', 'hv' or one integer per frame, not {flip!r}")
+        bits, flips = _flip_arg(flip, f, "resize_tensor_norm")
         win = resize_window(d, window)
         n = tensor_norm(tensor_strides(layout, win.w, win.h, c), (65535.0 if u16 else 1.0) if div is None else div,
                         0.0 if mean is None else mean, 1.0 if std is None else std, dtype, src,
-                        0 if flips is not None else flip, flips.ctypes.data if flips is not None else None)
+                        bits, flips.ctypes.data if flips is not None else None)
         out = np.empty((f, c, win.h, win.w) if layout == "chw" else (f, win.h, win.w, c),
                        dtype=np.float32 if dtype == "float32" else np.uint16)
-        _check(_lib().lanczos_resize_tensor_norm_host(self._h, ctypes.byref(d), _opts_ref(d, box, None, None),
-                                                      ctypes.byref(win) if window is not None else None, None, ctypes.byref(n),
-                                                      x.ctypes.data, out.ctypes.data, f), "lanczos_resize_tensor_norm_host")
-        out = out if dtype == "float32" else _tensor16_array(out, dtype)
-        return out if img.ndim == 4 else out[0]
+        self._bound[_norm_entry, "host", box is not None, window is not None, False, True](
+            d, box, None, None, win if window is not None else None, None, n, x.ctypes.data, out.ctypes.data, f)
+        return back(out if dtype == "float32" else _tensor16_array(out, dtype), True)
 
     def resize_tensor_norm_device(self, desc, d_in, d_out, frames, norm, in_frame_stride=0, out_frame_stride=0, stream=None,
                                   box=None, opts=None, window=None, source=None):
@@ -1498,11 +1408,8 @@ class Context:
         std travel by value.  out_frame_stride in BYTES (0 = one frame's extent).  box / opts as resize_device; window =
         (x0, y0, w, h) or a ResizeWindow: the strides describe that window's frame; source: a ResizeSource of pitched
         interleaved rows for the frames at d_in."""
-        _check(_lib().lanczos_resize_tensor_norm_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, None, opts),
-                                                        _window_ref(desc, window),
-                                                        ctypes.byref(source) if source is not None else None, ctypes.byref(norm),
-                                                        d_in, d_out, frames, in_frame_stride, out_frame_stride, stream),
-               "lanczos_resize_tensor_norm_device")
+        self._bound[_norm_entry, "device", box is not None or opts is not None, window is not None, source is not None, True](
+            desc, box, None, opts, window, source, norm, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream)
 
     def _ycc_host_args(self, frames, in_w, in_h, out_w, out_h, layout, filter, a, source, what):
         d = resize_desc(in_w, in_h, out_w, out_h, 3, a, filter=filter)
@@ -1527,9 +1434,9 @@ class Context:
         t = _ycc_table_arg(standard, table, "resize_ycc")
         win = resize_window(d, window)
         out = np.empty((x.shape[0], win.h, win.w, 3), dtype=np.uint8)
-        _check(_lib().lanczos_resize_ycc_host(self._h, ctypes.byref(d), _opts_ref(d, box, reducing_gap, None),
-                                              ctypes.byref(win) if window is not None else None, ctypes.byref(src), t.ctypes.data,
-                                              x.ctypes.data, out.ctypes.data, x.shape[0]), "lanczos_resize_ycc_host")
+        self._bound[_ycc_entry, "host", box is not None or reducing_gap is not None, window is not None, True, True, False](
+            d, box, reducing_gap, None, win if window is not None else None, src, t.ctypes.data, None, x.ctypes.data, out.ctypes.data,
+            x.shape[0])
         return out if x0.ndim == 2 else out[0]
 
     def resize_ycc_tensor(self, frames, in_w, in_h, out_w, out_h, layout="nv12", standard="jfif", mean=None, std=None, lut=None,
@@ -1548,35 +1455,15 @@ class Context:
         c = len(channels_out)
         if not 1 <= c <= 3:
             raise LanczosError(ERR_BAD_ARG, "resize_ycc_tensor: channels_out names 1 to 3 source channels")
-        if lut is None:
-            if c == 2:
-                m, s = (None if v is None else np.broadcast_to(np.asarray(v, dtype=np.float32), (2,)) for v in (mean, std))
-                lut = np.concatenate([normalize_lut(1, None if m is None else m[k], None if s is None else s[k], dtype)
-                                      for k in range(2)])
-            else:
-                lut = normalize_lut(c, mean, std, dtype)
-        elif mean is not None or std is not None:
-            raise LanczosError(ERR_BAD_ARG, "resize_ycc_tensor: a table or mean / std, not both")
-        lut = np.ascontiguousarray(lut)
-        if lut.dtype not in ((np.float32,) if wide else (np.uint16, np.float16)) or lut.size != c * 256:
-            raise LanczosError(ERR_BAD_ARG, f"resize_ycc_tensor: the table is {'float32' if wide else 'uint16 or float16'} [{c}][256]")
-        flips = None
-        if flip is not None and not isinstance(flip, str):
-            flips = np.ascontiguousarray(flip)
-            if flips.shape != (f,) or flips.dtype.kind not in "iub" or ((flips < 0) | (flips > 3)).any():
-                raise LanczosError(ERR_BAD_ARG, f"resize_ycc_tensor: flip is 'h', 'v', 'hv' or {f} integers 0 .. 3, one per frame")
-            flips = flips.astype(np.uint8)
-        elif flip not in _FLIP_NAMES:
-            raise LanczosError(ERR_BAD_ARG, f"resize_ycc_tensor: flip is 'h', 'v', 'hv' or one integer per frame, not {flip!r}")
+        lut = _lut_arg(lut, mean, std, c, dtype, "resize_ycc_tensor")
+        bits, flips = _flip_arg(flip, f, "resize_ycc_tensor")
         win = resize_window(d, window)
         v = tensor_view(lut.ctypes.data, tensor_strides(tensor_layout, win.w, win.h, c), 4 if wide else 2, channels_out,
-                        0 if flips is not None else flip, flips.ctypes.data if flips is not None else None)
+                        bits, flips.ctypes.data if flips is not None else None)
         shape = (f, c, win.h, win.w) if tensor_layout == "chw" else (f, win.h, win.w, c)
         out = np.empty(shape, dtype=np.float32 if wide else np.uint16)
-        _check(_lib().lanczos_resize_ycc_tensor_host(self._h, ctypes.byref(d), _opts_ref(d, box, reducing_gap, None),
-                                                     ctypes.byref(win) if window is not None else None, ctypes.byref(src),
-                                                     t.ctypes.data, ctypes.byref(v), x.ctypes.data, out.ctypes.data, f),
-               "lanczos_resize_ycc_tensor_host")
+        self._bound[_ycc_entry, "host", box is not None or reducing_gap is not None, window is not None, True, True, True](
+            d, box, reducing_gap, None, win if window is not None else None, src, t.ctypes.data, v, x.ctypes.data, out.ctypes.data, f)
         out = out if wide else _tensor16_array(out, dtype)
         return out if x0.ndim == 2 else out[0]
 
@@ -1586,32 +1473,24 @@ class Context:
         in_frame_stride bytes apart, 0 = the layout's extent) -> tightly packed RGB bytes of the window at d_out.  d_out and
         out_frame_stride (0 = w * h * 3 rounded up to a multiple of 4) are multiples of 4.  d_table: device, int32 [3][3][256]
         (ycc_table), read when the kernels run."""
-        _check(_lib().lanczos_resize_ycc_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
-                                                _window_ref(desc, window), ctypes.byref(source) if source is not None else None,
-                                                d_table, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream),
-               "lanczos_resize_ycc_device")
+        self._bound[_ycc_entry, "device", box is not None or reducing_gap is not None or opts is not None, window is not None,
+                    source is not None, True, False](
+            desc, box, reducing_gap, opts, window, source, d_table, None, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream)
 
     def resize_ycc_tensor_device(self, desc, source, d_table, d_in, d_out, frames, d_lut, strides, in_frame_stride=0,
                                  out_frame_stride=0, stream=None, box=None, reducing_gap=None, opts=None, dtype="float32",
                                  window=None, channels_out=None, flip=None, d_flip=None):
         """... -> tensor elements at d_out: strides (or a ready TensorView), d_lut, dtype, channels_out, flip and d_flip as
         Context.resize_tensor_device takes them, over the RGB bytes resize_ycc_device stores as source channels 0, 1, 2."""
-        if isinstance(strides, TensorView):
-            v = strides
-        else:
-            if dtype != "float32":
-                _tensor16_format(dtype, "resize_ycc_tensor_device")
-            v = tensor_view(d_lut, strides, 4 if dtype == "float32" else 2, channels_out if channels_out is not None else (0, 1, 2),
-                            flip or 0, d_flip)
-        _check(_lib().lanczos_resize_ycc_tensor_device(self._h, ctypes.byref(desc), _opts_ref(desc, box, reducing_gap, opts),
-                                                       _window_ref(desc, window), ctypes.byref(source) if source is not None else None,
-                                                       d_table, ctypes.byref(v), d_in, d_out, frames, in_frame_stride,
-                                                       out_frame_stride, stream), "lanczos_resize_ycc_tensor_device")
+        v = _tensor_view_arg(strides, d_lut, dtype, channels_out, 3, flip, d_flip, "resize_ycc_tensor_device")
+        self._bound[_ycc_entry, "device", box is not None or reducing_gap is not None or opts is not None, window is not None,
+                    source is not None, True, True](
+            desc, box, reducing_gap, opts, window, source, d_table, v, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream)
 
     def last_ycc_info(self):
         """YccInfo of the last successful resize_ycc* call on the context (all zero before any)."""
         info = YccInfoC()
-        _check(_lib().lanczos_last_ycc_info(self._h, ctypes.byref(info)), "lanczos_last_ycc_info")
+        self._call("lanczos_last_ycc_info", ctypes.byref(info))
         return YccInfo(info.luma_kernel, info.chroma_kernel, bool(info.split), info.launches)
 
     def last_tensor_route(self):
@@ -1633,44 +1512,32 @@ class Context:
     def reduce(self, img, factor, box=None):
         """img: uint8 [H][W], [H][W][C] or [F][H][W][C] -> the same layout reduced by `factor` (an int or (fx, fy)) over the
         integer box (x0, y0, x1, y1) (None = the whole frame): bytes identical to Pillow's Image.reduce(factor, box)."""
-        img = np.ascontiguousarray(img)
-        if img.dtype == np.uint16:
+        if np.asarray(img).dtype == np.uint16:
             raise LanczosError(ERR_BAD_ARG, "reduce: 8-bit samples only (Pillow refuses I;16 as well)")
-        if img.dtype != np.uint8 or img.ndim not in (2, 3, 4):
-            raise LanczosError(ERR_BAD_ARG, "reduce: expected a uint8 [H][W], [H][W][C] or [F][H][W][C] array")
-        x = img.reshape(img.shape + (1,)) if img.ndim == 2 else img
-        x = x if x.ndim == 4 else x[None]
-        f, h, w, c = x.shape
-        fx, fy = _factor_pair(factor)
-        ow, oh = reduce_size(w, h, (fx, fy), box)
-        b = (ctypes.c_int32 * 4)(*[int(v) for v in box]) if box is not None else None
+        x, (f, h, w, c), back = _frames(img, (np.uint8,), "reduce")
+        ow, oh = reduce_size(w, h, factor, box)
+        entry = _reduce_entry("host", w, h, c, factor, box)
         out = np.empty((f, oh, ow, c), dtype=np.uint8)
-        _check(_lib().lanczos_reduce_host(self._h, w, h, c, fx, fy, b, x.ctypes.data, out.ctypes.data, f),
-               "lanczos_reduce_host")
-        if img.ndim == 2:
-            return out[0, :, :, 0]
-        return out if img.ndim == 4 else out[0]
+        self._call(*entry, x.ctypes.data, out.ctypes.data, f)
+        return back(out)
 
     def reduce_device(self, in_w, in_h, channels, factor, d_in, d_out, frames, box=None, in_frame_stride=0,
                       out_frame_stride=0, stream=None):
         """Device pointers, asynchronous on `stream`; the output is reduce_size(in_w, in_h, factor, box) pixels per frame."""
-        fx, fy = _factor_pair(factor)
-        b = (ctypes.c_int32 * 4)(*[int(v) for v in box]) if box is not None else None
-        _check(_lib().lanczos_reduce_device(self._h, in_w, in_h, channels, fx, fy, b, d_in, d_out, frames, in_frame_stride,
-                                            out_frame_stride, stream), "lanczos_reduce_device")
+        entry = _reduce_entry("device", in_w, in_h, channels, factor, box)
+        self._call(*entry, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream)
 
     def resize_force(self, path):
         """RESIZE_AUTO / RESIZE_FUSED / RESIZE_TWO_PASS (tests and A/B runs); RESIZE_CONVERT: as AUTO, but a tensor request takes
         the converted route."""
-        _check(_lib().lanczos_resize_force(self._h, path), "lanczos_resize_force")
+        self._call("lanczos_resize_force", path)
 
     def timing_enable(self, on=True):
-        _check(_lib().lanczos_timing_enable(self._h, 1 if on else 0), "lanczos_timing_enable")
+        self._call("lanczos_timing_enable", 1 if on else 0)
 
     def timing_read(self):
         n, a, b = ctypes.c_int(), ctypes.c_double(), ctypes.c_double()
-        _check(_lib().lanczos_timing_read(self._h, ctypes.byref(n), ctypes.byref(a), ctypes.byref(b)),
-               "lanczos_timing_read")
+        self._call("lanczos_timing_read", ctypes.byref(n), ctypes.byref(a), ctypes.byref(b))
         return n.value, a.value, b.value
 
     def last_kernel(self):
@@ -1697,7 +1564,7 @@ class Context:
         return MarchTableInfo(*(getattr(info, f) for f in MarchTableInfo._fields)), tab
 
     def force_kernel(self, family):
-        _check(_lib().lanczos_force_kernel(self._h, family), "lanczos_force_kernel")
+        self._call("lanczos_force_kernel", family)
 
 
 def partition_frames(frames, parts, part):
@@ -1712,18 +1579,10 @@ def partition_rows(desc, parts, part):
     return tuple(x.value for x in v)   # out_row0, out_rows, in_row0, in_rows
 
 
-class Xfer(ctypes.Structure):
-    """lanczos_xfer -- one message of the root exchange (lanczos_multi_exchange_plan)."""
-    _fields_ = [("src", ctypes.c_int), ("dst", ctypes.c_int), ("src_off", ctypes.c_size_t), ("dst_off", ctypes.c_size_t),
-                ("bytes", ctypes.c_size_t)]
-
-
 def exchange_plan(desc, frames, split, n_devices, phase):
     """The scatter (phase 0) / gather (phase 1) of lanczos_resample_multi_root as a list of (src, dst, src_off, dst_off, bytes).
     Host only: no GPU, no RCCL."""
     fn = _lib().lanczos_multi_exchange_plan
-    fn.restype = ctypes.c_int
-    fn.argtypes = [ctypes.POINTER(Desc), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(Xfer), ctypes.c_int]
     n = fn(ctypes.byref(desc), frames, split, n_devices, phase, None, 0)
     if n < 0:
         raise LanczosError(-n, "lanczos_multi_exchange_plan")
@@ -1773,7 +1632,6 @@ class MultiContext:
         """The RCCL exchange machinery on one rank (lanczos_multi_exchange_selftest): returns the C status code and, for
         ERR_RCCL, (rccl_error, message index) from lanczos_multi_last_error."""
         lib = _lib()
-        lib.lanczos_multi_exchange_selftest.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int]
         rc = lib.lanczos_multi_exchange_selftest(self._h, messages, nbytes, fail_at)
         he, re_, at = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         lib.lanczos_multi_last_error(self._h, ctypes.byref(he), ctypes.byref(re_), ctypes.byref(at))
