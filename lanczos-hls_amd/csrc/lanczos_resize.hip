@@ -394,6 +394,7 @@ int resize_device(ResizeState* st, RsRequest& q) {
         const int main_n = rt.main == kRsMainNone ? 0 : rt.main == kRsMainCopy ? 1
                            : (rt.main == kRsMainTwoPass || rt.main == kRsMainVFirst) ? 2 * groups : groups;
         q.launches = main_n + groups * ((int)rt.pack + (int)rt.reduce + (int)(rt.follower != kRsFollowNone) + (int)(rt.unpacked.bytes != 0));
+        q.copied = !rt.reduce && (rt.main == kRsMainNone || rt.main == kRsMainCopy || rt.main == kRsMainCrop);
     }
     *q.last_kernel = rt.kernel;
     q.tc.route = rt.tensor_route, q.sc.route = rt.source_route, q.dc.route = rt.dest_route;

@@ -312,6 +312,7 @@ struct RsRequest {
     hipStream_t stream = nullptr;
     int *last_kernel = nullptr, *last_hip = nullptr;     // as in lanczos_ctx
     int launches = 0;      // out: the launches (kernels and copies) resize_device issued for the request
+    bool copied = false;   // out: no resize kernel ran, the request was the plain copy (of a window: its crop)
     // the optional parts, each read only where its flag is set and its `route` written once the launches are out
     bool tensor = false;   // tc: `out` holds element frames.  Crops: win is (0, 0, w, h) and tc.d_origin the origins
     bool source = false;   // sc: the frames at `in` lie in that layout

@@ -320,6 +320,7 @@ static int ycc_plane(ResizeState* st, YccRequest& q, const lanczos_resize_desc* 
     int rc = resize_source_resolve(d1, &src, &r.sc.s);
     if (rc == LANCZOS_OK) rc = resize_device(st, r);
     q.info.launches += r.launches;
+    if (rc == LANCZOS_OK && r.copied) *kernel = LANCZOS_KERNEL_NONE;   // lanczos_ycc_info: a plain copy is no kernel
     return rc;
 }
 

@@ -85,6 +85,90 @@ def pillow_recipe(y, cb, cr):
     return np.clip(np.stack([r, g, b], -1), 0, 255).astype(np.uint8)
 
 
+def all_triples():
+    """a 4096 x 4096 image holding every (y, cb, cr) once: pixel i = y << 16 | cb << 8 | cr"""
+    i = np.arange(1 << 24, dtype=np.uint32).reshape(4096, 4096)
+    return (i >> 16).astype(np.uint8), ((i >> 8) & 255).astype(np.uint8), (i & 255).astype(np.uint8)
+
+
+def passthrough_table():
+    """R = cb, G = y, B = cr: entries 64 i where a channel reads its plane, 0 elsewhere, so that the shift gives i back"""
+    t = np.zeros((3, 3, 256), dtype=np.int32)
+    t[0, 1] = t[1, 0] = t[2, 2] = 64 * np.arange(256)
+    return t
+
+
+INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
+# where clip8(sum >> 6) changes its behaviour: the ends of int32, the shift's steps around 0, the last sums that give 254 and
+# 255 unclamped (16319 / 16320, 16383) and the first ones the clamp holds (16384 ...), and one full step beyond either end
+BOUNDARY_SUMS = (INT32_MIN, -16384, -65, -64, -63, -1, 0, 1, 63, 64, 65, 16319, 16320, 16383, 16384, 16447, 16448, INT32_MAX)
+
+
+def boundary_table(seed=7):
+    """A caller's table at the edge of what the contract allows ("entries must keep the sum inside int32"): luma entries lie in
+    [-2^30, 2^30 - 1] and chroma entries in [-2^29, 2^29], so no sum leaves int32 and both of its ends are reached.  For every
+    channel and every v of BOUNDARY_SUMS one (y, cb, cr) is planted whose three entries add up to v, each of them large; the
+    triples differ from channel to channel.  The other entries are half small (sums around the shift's range) and half wide."""
+    rng = np.random.default_rng(seed)
+    t = np.zeros((3, 3, 256), dtype=np.int64)
+    n = len(BOUNDARY_SUMS)
+    for c in range(3):
+        small = rng.integers(-20000, 20001, (3, 256))
+        wide = np.stack([rng.integers(-(1 << 30), 1 << 30, 256), rng.integers(-(1 << 29), (1 << 29) + 1, 256),
+                         rng.integers(-(1 << 29), (1 << 29) + 1, 256)])
+        t[c] = np.where(rng.integers(0, 2, (3, 256)) == 1, small, wide)
+        iy, ib, ir = (rng.permutation(256)[:n] for _ in range(3))
+        for k, v in enumerate(BOUNDARY_SUMS):
+            if v == INT32_MIN:
+                p, q = -(1 << 29), -(1 << 29)
+            elif v == INT32_MAX:
+                p, q = 1 << 29, 1 << 29
+            else:
+                p, q = (int(x) for x in rng.integers(-(1 << 29) + (1 << 15), (1 << 29) - (1 << 15), 2))
+            t[c, 1, ib[k]], t[c, 2, ir[k]], t[c, 0, iy[k]] = p, q, v - p - q
+    assert (np.abs(t[:, 0] + 0.5) < (1 << 30)).all() and (np.abs(t[:, 1:]) <= (1 << 29)).all()
+    return t.astype(np.int32)
+
+
+def wide_table(seed=8):
+    """seeded entries in +-7e8: three of them add up to at most 2.1e9 < 2^31 - 1, so sums range over nearly all of int32"""
+    return np.random.default_rng(seed).integers(-700_000_000, 700_000_001, (3, 3, 256)).astype(np.int32)
+
+
+def table_sums(t, c):
+    """int64 [256][256][256]: the sum of channel c for every (y, cb, cr), in the order of all_triples()"""
+    t = np.asarray(t).astype(np.int64)
+    return t[c, 0][:, None, None] + t[c, 1][None, :, None] + t[c, 2][None, None, :]
+
+
+def chw_words(rgb, lut, src, flip):
+    """the words of one tight CHW frame under the view contract (resize_tensor_view_model.view for one frame), plane by plane
+    and without index arrays, for frames as large as all_triples(): [OC][h][w] of the table's word"""
+    lb = np.ascontiguousarray(lut)
+    lb = lb.view({4: np.uint32, 2: np.uint16}[lb.dtype.itemsize]).reshape(len(src), 256)
+    b = rgb[::-1] if flip & 2 else rgb
+    b = b[:, ::-1] if flip & 1 else b
+    return np.stack([lb[oc][b[..., s]] for oc, s in enumerate(src)])
+
+
+# ---- the row cover of the chroma split ------------------------------------------------------------------------------------------
+SPLIT_THREADS = 256
+
+
+def split_cover(addr, cw):
+    """Who moves the 2 cw bytes of an interleaved chroma row at byte address `addr`, as the split's contract words it: the
+    dwords at dword-aligned addresses inside the row, one per work item, then the `head` bytes in front of the first of them
+    and the `rest` bytes behind the last, one per work item, SPLIT_THREADS items to a workgroup.  Returns (head, nd, rest) and
+    the set of (kind, workgroup) pairs that have work, kind "dword" or "byte"."""
+    n = 2 * cw
+    head = min(-addr & 3, n)
+    nd = (n - head) >> 2
+    rest = n - head - 4 * nd
+    assert 0 <= rest < 4 and head + 4 * nd + rest == n
+    who = {("dword", k // SPLIT_THREADS) for k in range(nd)} | {("byte", k // SPLIT_THREADS) for k in range(nd, nd + head + rest)}
+    return (head, nd, rest), who
+
+
 def filter_code(filt):
     return F.NAMES.index(filt) if isinstance(filt, str) else int(filt)
 
@@ -155,18 +239,22 @@ Frames = collections.namedtuple("Frames", "buf at frame_stride y_row_stride c_ro
 MARGIN = 64
 
 
-def build(y, cb, cr, layout=PLANAR, y_row_stride=None, c_row_stride=None, base=0, gap=0, frame_gap=0, seed=1):
+def build(y, cb, cr, layout=PLANAR, y_row_stride=None, c_row_stride=None, base=0, gap=0, frame_gap=0, seed=1, cr_first=False):
     """The planes [F][h][w] laid out as frames: Y rows y_row_stride apart, `gap` bytes, then the chroma planes (PLANAR: Cb, gap,
-    Cr) or the interleaved plane (NV12: Cb first, NV21: Cr first), rows c_row_stride apart; frames frame_gap bytes past the
-    extent apart; the first frame MARGIN + base bytes into the buffer.  Every byte the layout does not name is noise."""
+    Cr; with cr_first Cr, gap, Cb, which is YV12) or the interleaved plane (NV12: Cb first, NV21: Cr first), rows c_row_stride
+    apart; frames frame_gap bytes past the extent apart; the first frame MARGIN + base bytes into the buffer.  Every byte the
+    layout does not name is noise."""
     f, h, w = y.shape
     _, ch, cw = cb.shape
     crow = cw if layout == PLANAR else 2 * cw
     yrs = w if y_row_stride is None else y_row_stride
     crs = crow if c_row_stride is None else c_row_stride
+    assert not cr_first or layout == PLANAR
     cb_off = h * yrs + gap
     cr_off = cb_off + ch * crs + gap if layout == PLANAR else cb_off
     extent = cr_off + ch * crs
+    if cr_first:
+        cb_off, cr_off = cr_off, cb_off
     fs = extent + frame_gap
     rng = np.random.default_rng(seed)
     buf = rng.integers(0, 256, MARGIN + base + (f - 1) * fs + extent + MARGIN, dtype=np.uint8)
@@ -190,3 +278,33 @@ def tight(y, cb, cr, layout=PLANAR):
     """[F][B] uint8: the frames back to back in the tight layout, as Context.resize_ycc takes them"""
     s = build(y, cb, cr, layout)
     return s.buf[s.at:s.at + y.shape[0] * s.frame_stride].reshape(y.shape[0], s.frame_stride).copy()
+
+
+# ---- the shapes of tests/test_resize_ycc_edges_gpu.py, each pinned to the installed Pillow by tests/test_resize_ycc_host.py ------
+Shape = collections.namedtuple("Shape", "sx sy in_w in_h out_w out_h filt")
+SPLIT_WIDE_CW = (511, 512, 513, 516, 1030)                  # chroma pairs per row around one, two and three workgroups' worth
+SPLIT_ODD_WIDE = Shape(1, 1, 1031, 3, 516, 2, "lanczos")    # cw = 516 from an odd width: the chroma pass runs
+MERGE_ONLY = ((1, 1500), (2500, 1), (1100, 3))              # 4:4:4 frames that keep their size: w == 1, one long row, rem0 != 0
+MANY_FRAMES = Shape(1, 1, 4, 2, 3, 2, "lanczos")
+
+
+def split_alone_shape(cw):
+    """NV12 / NV21 frames of 2 cw x 4 halved: the chroma box is the chroma plane, so chroma is a copy of what the split wrote"""
+    return Shape(1, 1, 2 * cw, 4, cw, 2, "lanczos")
+
+
+def narrow_shapes(subs=((1, 1),), outs=((3, 2), None)):
+    """in_w 1 .. 9 x in_h 1 .. 3 (cw 1 .. 5: rows shorter than the way to the next dword), to every size of outs (None: same)"""
+    return [Shape(sx, sy, w, h, *(o if o is not None else (w, h)), "lanczos")
+            for sx, sy in subs for w in range(1, 10) for h in range(1, 4) for o in outs]
+
+
+def noise_planes(shape, frames=1, seed=0):
+    """seeded noise planes (Y, Cb, Cr) of a Shape, [F][h][w] each"""
+    rng = np.random.default_rng([9300, shape.in_w, shape.in_h, shape.sx, shape.sy, seed])
+    cw, ch = chroma_size(shape.in_w, shape.in_h, shape.sx, shape.sy)
+    return tuple(rng.integers(0, 256, s, dtype=np.uint8) for s in ((frames, shape.in_h, shape.in_w), (frames, ch, cw), (frames, ch, cw)))
+
+
+def compose_shape(shape, y, cb, cr, **kw):
+    return compose(y, cb, cr, shape.sx, shape.sy, shape.out_w, shape.out_h, shape.filt, **kw)

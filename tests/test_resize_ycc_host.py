@@ -147,15 +147,9 @@ def test_table_refusals():
         L.ycc_table("bt2020")
 
 
-def _all_triples():
-    """a 4096 x 4096 image holding every (y, cb, cr) once"""
-    i = np.arange(1 << 24, dtype=np.uint32).reshape(4096, 4096)
-    return (i >> 16).astype(np.uint8), ((i >> 8) & 255).astype(np.uint8), (i & 255).astype(np.uint8)
-
-
 def test_jfif_table_is_pillows_convert_over_all_triples():
     from PIL import Image
-    y, cb, cr = _all_triples()
+    y, cb, cr = Y.all_triples()
     t = L.ycc_table("jfif")
     assert np.array_equal(t, Y.table(Y.JFIF))
     want = np.asarray(Image.merge("YCbCr", [Image.fromarray(p, "L") for p in (y, cb, cr)]).convert("RGB"))
@@ -174,7 +168,7 @@ def test_limited_range_tables(name, std):
     assert np.array_equal(t, Y.table(std))                                  # the restated formula, exactly
     assert np.array_equal(t, L.ycc_table(std))
     assert not t[0, 1].any() and not t[2, 2].any()                          # R does not read cb, B does not read cr
-    y, cb, cr = _all_triples()
+    y, cb, cr = Y.all_triples()
     worst = 0
     for r0 in range(0, 4096, 512):                                          # (in slabs: float64 over 2^24 triples at once is 400 MB)
         s = slice(r0, r0 + 512)
@@ -214,3 +208,155 @@ def test_chroma_box_is_exact():
     assert Y.chroma_box(None, 37, 23, 1, 0) == (0.0, 0.0, 18.5, 23.0)
     assert Y.chroma_box((3.5, 2.25, 33.75, 20.5), 37, 23, 1, 1) == (1.75, 1.125, 16.875, 10.25)
     assert Y.chroma_box((3.5, 2.25, 33.75, 20.5), 37, 23, 0, 0) == (3.5, 2.25, 33.75, 20.5)
+
+
+# ---- the yardsticks of tests/test_resize_ycc_edges_gpu.py, pinned without a GPU ------------------------------------------------
+def _pillow(shape, y, cb, cr):
+    """the header's recipe on one frame with the installed Pillow: three "L" resizes, chroma with box = Y.chroma_box(...)"""
+    from PIL import Image
+    filt = {"lanczos": Image.Resampling.LANCZOS, "bicubic": Image.Resampling.BICUBIC}[shape.filt]
+    size = (shape.out_w, shape.out_h)
+    bl = (0.0, 0.0, float(shape.in_w), float(shape.in_h))
+    bc = Y.chroma_box(None, shape.in_w, shape.in_h, shape.sx, shape.sy)
+    planes = [Image.fromarray(p).resize(size, filt, box=b) for p, b in ((y, bl), (cb, bc), (cr, bc))]
+    assert all(p.mode == "L" for p in planes)
+    return np.asarray(Image.merge("YCbCr", planes).convert("RGB"))
+
+
+def _pillow_cases():
+    shapes = Y.narrow_shapes(subs=((1, 1), (1, 0)), outs=((3, 2), (1, 1), None))
+    assert len(shapes) == 162
+    shapes += [Y.split_alone_shape(cw) for cw in Y.SPLIT_WIDE_CW] + [Y.SPLIT_ODD_WIDE, Y.MANY_FRAMES]
+    shapes += [Y.Shape(0, 0, w, h, w, h, "lanczos") for w, h in Y.MERGE_ONLY]
+    return shapes
+
+
+def test_model_equals_installed_pillow_on_the_edge_shapes():
+    """every shape class the GPU edge tests compare with Y.compose: narrow frames (rows of 1 .. 5 chroma pairs), the wide rows
+    of the split, the odd wide one, the frames of the 65 537-frame batch and the frames that keep their size"""
+    for shape in _pillow_cases():
+        frames = 12 if shape == Y.MANY_FRAMES else 1
+        y, cb, cr = Y.noise_planes(shape, frames, seed=1)
+        got = Y.compose_shape(shape, y, cb, cr)
+        for f in range(frames):
+            want = _pillow(shape, y[f], cb[f], cr[f])
+            assert got[f].shape == want.shape and np.array_equal(got[f], want), (shape, f)
+        if (shape.sx, shape.sy, shape.out_w, shape.out_h) == (0, 0, shape.in_w, shape.in_h):   # nothing resizes: the conversion alone
+            assert np.array_equal(got, Y.convert(Y.table(Y.JFIF), y, cb, cr)), shape
+
+
+def test_yv12_and_nv16_builders_lay_the_planes_out_as_named():
+    """Y.build's plane-order switch (YV12) and NV12 / NV21 with sub_y = 0 (NV16 / NV61): the offsets pass the validator and the
+    bytes at them are the planes"""
+    case = Y.CASE["i420_down"]
+    y, cb, cr = Y.make_planes(case, 2)
+    d = L.resize_desc(case.in_w, case.in_h, case.out_w, case.out_h, 3)
+    s = Y.build(y, cb, cr, Y.PLANAR, c_row_stride=21, gap=3, base=1, cr_first=True)
+    assert s.cr_offset < s.cb_offset
+    src = L.ycc_source(d, "i420", y_row_stride=s.y_row_stride, c_row_stride=21, cb_offset=s.cb_offset, cr_offset=s.cr_offset)
+    assert _code(d, src) == L.OK and L.ycc_frame_bytes(d, src) <= s.frame_stride
+    for f in range(2):
+        o = s.at + f * s.frame_stride
+        for r in range(12):
+            assert np.array_equal(s.buf[o + s.cb_offset + 21 * r:][:19], cb[f, r]) and np.array_equal(s.buf[o + s.cr_offset + 21 * r:][:19], cr[f, r])
+    plain = Y.build(y, cb, cr, Y.PLANAR, c_row_stride=21, gap=3, base=1)
+    assert (plain.cb_offset, plain.cr_offset) == (s.cr_offset, s.cb_offset) and plain.frame_stride == s.frame_stride
+    case = Y.CASE["i422_down"]
+    y, cb, cr = Y.make_planes(case, 2)
+    assert cb.shape == (2, case.in_h, 17)
+    d = L.resize_desc(case.in_w, case.in_h, case.out_w, case.out_h, 3)
+    for layout, code, first in ((Y.NV12, L.YCC_NV12, cb), (Y.NV21, L.YCC_NV21, cr)):
+        s = Y.build(y, cb, cr, layout, c_row_stride=37, base=2)
+        src = L.ycc_source(d, code, 1, 0, c_row_stride=37, cb_offset=s.cb_offset)
+        assert _code(d, src) == L.OK and (src.sub_x, src.sub_y, src.cr_offset) == (1, 0, s.cb_offset)
+        assert L.ycc_frame_bytes(d, src) == s.frame_stride == case.in_w * case.in_h + 37 * case.in_h
+        assert np.array_equal(s.buf[s.at + s.cb_offset + 37 * 30:][:34:2], first[0, 30])
+        src.cr_offset += 1                                                  # two offsets for one plane, also at sub_y = 0
+        assert _code(d, src) == L.ERR_BAD_ARG
+
+
+def test_passthrough_table_hands_the_planes_through():
+    t = Y.passthrough_table()
+    assert t.dtype == np.int32 and t.shape == (3, 3, 256) and np.count_nonzero(t) == 3 * 255
+    v = np.arange(256, dtype=np.uint8)
+    y, cb, cr = np.meshgrid(v, v[::5], v[::7], indexing="ij")
+    out = Y.convert(t, y, cb, cr)
+    assert np.array_equal(out[..., 0], cb) and np.array_equal(out[..., 1], y) and np.array_equal(out[..., 2], cr)
+
+
+@pytest.mark.parametrize("name", ["boundary", "wide"])
+def test_hostile_tables_keep_the_contracts_condition(name):
+    """in int64 over all 2^24 triples: no sum leaves int32 (the header's condition on a caller's table); the boundary table's
+    sums take every value of Y.BOUNDARY_SUMS in every channel; the wide table's reach both halves of int32's range"""
+    t = Y.boundary_table() if name == "boundary" else Y.wide_table()
+    assert t.dtype == np.int32 and t.shape == (3, 3, 256)
+    assert np.array_equal(t, Y.boundary_table() if name == "boundary" else Y.wide_table())       # seeded: the same every time
+    for c in range(3):
+        s = Y.table_sums(t, c)
+        assert s.dtype == np.int64 and s.shape == (256, 256, 256)
+        lo, hi = int(s.min()), int(s.max())
+        assert Y.INT32_MIN <= lo and hi <= Y.INT32_MAX, (c, lo, hi)
+        if name == "boundary":
+            hit = np.isin(np.asarray(Y.BOUNDARY_SUMS, dtype=np.int64), s)
+            assert hit.all(), (c, [v for v, h in zip(Y.BOUNDARY_SUMS, hit) if not h])
+            assert (lo, hi) == (Y.INT32_MIN, Y.INT32_MAX)
+        else:
+            assert np.abs(t[c].astype(np.int64)).max() <= 700_000_000
+            assert lo < -(1 << 30) and hi > (1 << 30), (c, lo, hi)
+        if name == "boundary":                                              # its small entries: every byte value out of every channel
+            assert len(np.unique(s[(s >= 0) & (s <= 16383)] >> 6)) == 256, c
+
+
+@pytest.mark.parametrize("std", [Y.JFIF, Y.BT601, Y.BT709])
+def test_standard_tables_clip_at_both_ends_in_every_channel(std):
+    t = Y.table(std)
+    for c in range(3):
+        s = Y.table_sums(t, c)
+        assert Y.INT32_MIN <= int(s.min()) and int(s.max()) <= Y.INT32_MAX
+        assert int(s.min()) < 0 and int(s.max()) > 16383                    # the clamp works at both ends ...
+    y, cb, cr = (p[::8] for p in Y.all_triples())
+    out = Y.convert(t, y, cb, cr)
+    assert all((out[..., c] == 0).any() and (out[..., c] == 255).any() for c in range(3))   # ... and outputs 0 and 255
+
+
+def test_convert_over_all_triples_is_the_table_sums():
+    """Y.convert on the all-triples image, the yardstick of the GPU merge tests, against the sums restated on the cube"""
+    t = Y.boundary_table()
+    y, cb, cr = Y.all_triples()
+    got = Y.convert(t, y, cb, cr)
+    for c in range(3):
+        assert np.array_equal(got[..., c].reshape(256, 256, 256), np.clip(Y.table_sums(t, c) >> 6, 0, 255).astype(np.uint8)), c
+
+
+def test_chw_words_is_the_view_model():
+    """Y.chw_words, which the all-triples tensor case compares with, equals resize_tensor_view_model.view"""
+    import resize_tensor16_model as T16
+    import resize_tensor_model as T32
+    import resize_tensor_view_model as V
+    rgb = np.random.default_rng(3).integers(0, 256, (7, 5, 3), dtype=np.uint8)
+    for lut in (T32.identity_lut(3), T16.identity_lut16(3), T32.identity_lut(2)):
+        for src in ((2, 1, 0), (0, 1, 2), (2, 0)):
+            if len(src) != lut.shape[0]:
+                continue
+            for flip in range(4):
+                assert np.array_equal(Y.chw_words(rgb, lut, src, flip), V.view(rgb, lut, src, flip, "chw")), (src, flip)
+
+
+def test_split_cover_names_every_workgroup_the_wide_rows_use():
+    """the row cover as k_rs_ycc_split's contract words it, in plain arithmetic: which widths and residues give a dword or a
+    tail byte to the second workgroup, and work to the third"""
+    (head, nd, rest), who = Y.split_cover(0, 511)                           # 1022 bytes: 255 dwords, the two tail bytes are items 255, 256
+    assert (head, nd, rest) == (0, 255, 2) and who == {("dword", 0), ("byte", 0), ("byte", 1)}
+    (head, nd, rest), who = Y.split_cover(1, 512)                           # 3 + 4 * 255 + 1
+    assert (head, nd, rest) == (3, 255, 1) and who == {("dword", 0), ("byte", 0), ("byte", 1)}
+    assert Y.split_cover(0, 512) == ((0, 256, 0), {("dword", 0)})           # exactly one workgroup of dwords
+    assert Y.split_cover(0, 513) == ((0, 256, 2), {("dword", 0), ("byte", 1)})
+    assert Y.split_cover(0, 516) == ((0, 258, 0), {("dword", 0), ("dword", 1)})
+    assert Y.split_cover(2, 1030)[1] == {("dword", 0), ("dword", 1), ("dword", 2), ("byte", 2)}
+    for addr in range(4):                                                   # rows shorter than the way to the next dword
+        (head, nd, rest), who = Y.split_cover(addr, 1)
+        assert (head, nd, rest) == ((0, 0, 2), (2, 0, 0), (2, 0, 0), (1, 0, 1))[addr] and who == {("byte", 0)}
+    for addr in range(8):
+        for cw in range(1, 40):
+            (head, nd, rest), _ = Y.split_cover(addr, cw)
+            assert head + 4 * nd + rest == 2 * cw and (nd == 0 or (addr + head) % 4 == 0) and head < 4 and rest < 4
