@@ -954,6 +954,98 @@ typedef struct lanczos_ycc_info {
 } lanczos_ycc_info;
 int lanczos_last_ycc_info(const lanczos_ctx* ctx, lanczos_ycc_info* info);
 
+/* ---- resize INTO YCbCr frames (I420, 4:2:2, 4:4:4 planes, NV12, NV21) from YCbCr frames or from packed RGB bytes ----
+ * The mirror of the section above: a lanczos_ycc_dest says where the planes of a result frame go.  The stored frame is the
+ * window (win NULL: the whole output) of w x h luma samples; its chroma planes hold ocw x och samples, ocw = (w + sub_x) >> sub_x,
+ * och = (h + sub_y) >> sub_y, with the destination's subsampling.  THE CONTRACT is a composition of Pillow calls, byte for byte.
+ * FROM YCbCr (src given): no colour conversion and no table, the planes are resized plane by plane,
+ *   Yo  = Image.fromarray(Y,  "L").resize((out_w, out_h), filt, box=bl, reducing_gap=g)
+ *   Cbo = Image.fromarray(Cb, "L").resize((OCW, OCH), filt, box=bc, reducing_gap=g)             (Cr likewise)
+ * with OCW = (out_w + sub_x) >> sub_x, OCH = (out_h + sub_y) >> sub_y the full output's chroma size under the DESTINATION's
+ * subsampling, and bl, bc the boxes of the section above: bc is bl scaled by the SOURCE's subsampling on the doubles.  Source and
+ * destination subsampling and layout are independent (4:2:0 -> 4:4:4, NV12 -> I420, NV21 -> NV12 are all requests).  Every plane
+ * obeys the one-channel rules on its own: an axis that keeps its size over its whole span is not filtered, so NV12 -> I420 at the
+ * same size is a pure re-layout.  A window (x0, y0, w, h) is in luma output pixels; x0 must be a multiple of 2^sub_x and y0 of
+ * 2^sub_y of the destination, else LANCZOS_ERR_BAD_ARG; the chroma window is (x0 >> sub_x, y0 >> sub_y, ocw, och), which then lies
+ * inside the full chroma plane for every w and h.
+ * FROM RGB (src NULL): the frames at `in` are tightly packed interleaved 8-bit RGB, as lanczos_resize_window_device takes them,
+ *   rgb = Image.fromarray(x, "RGB").resize((out_w, out_h), filt, box=b, reducing_gap=g)[.crop(window)]
+ *   Y, Cb, Cr = rgb.convert("YCbCr").split()
+ *   Cb, Cr = Cb.reduce((1 << sub_x, 1 << sub_y)), Cr.reduce((1 << sub_x, 1 << sub_y))          (only where sub_x or sub_y is 1)
+ * The window is cut first, so any origin is legal, and the chroma blocks are those of the windowed frame.  The conversion is a
+ * table the caller passes, of the form of the table above, int32 t[3][3][256]:
+ *   out[c] = clip8((t[c][0][R] + t[c][1][G] + t[c][2][B]) >> 6),  c = Y, Cb, Cr        (>> arithmetic, clip8 to 0 .. 255)
+ * and the chroma average is lanczos_reduce_*'s rule, ((sum + d / 2) * floor(2^24 / d)) >> 24, where d counts the 1, 2 or 4
+ * converted bytes a block really holds: the last column and row of blocks of an odd frame are ragged.
+ * lanczos_ycc_table_forward fills the table for the standards.  LANCZOS_YCC_JFIF is Pillow's convert("YCbCr") exactly: entries
+ * (int)(k * i * 64 + 0.5) (double, truncation toward zero) with k = 0.299, 0.587, 0.114 (Y), -0.16874, -0.33126, 0.5 (Cb),
+ * 0.5, -0.41869, -0.08131 (Cr), and 128 * 64 added to the R entry of Cb and of Cr (+ 128 behind the shift).  LANCZOS_YCC_BT601 /
+ * _BT709 are the limited-range forward matrices with the same entry rule: Y rows k = K * 219/255, chroma rows
+ * -Kr/(2(1-Kb)), -Kg/(2(1-Kb)), 1/2 (Cb) and 1/2, -Kg/(2(1-Kr)), -Kb/(2(1-Kr)) (Cr) times 224/255; the offsets 16 * 64 + 32 (Y)
+ * and 128 * 64 + 32 (Cb, Cr) are folded into the R entries, so the shift rounds.  Their result is within 1 of the float64 matrix
+ * result rounded to nearest and clipped.
+ * A request that resizes nothing (out == in, no box, no gap, no window) is a colour conversion: k_rs_ycc_encode reads the caller's
+ * frames, nothing copies them.
+ * UNNAMED BYTES: every byte of the destination that the layout does not name -- row padding, gaps between planes and frames,
+ * bytes around the buffer -- keeps its contents, in device and in host memory.
+ * Routes.  From YCbCr, luma and planar chroma are the one-channel requests of lanczos_resize_dest_device with a pitched source and
+ * a pitched destination: where the plan is fused the kernel stores into the caller's planes (LANCZOS_DEST_DIRECT), no scratch
+ * and no extra pass.  For NV12 / NV21 out the two chroma planes go tight into context scratch and one streaming launch
+ * (k_rs_ycc_join) interleaves them into the pitched rows; interleaved chroma in is split as above.  Fused 4:2:0 planar -> planar
+ * is three launches, NV -> NV four (luma, split, one chroma call of 2 * frames frames, join).  From RGB, the resize stores tight RGB into context scratch and one
+ * launch (k_rs_ycc_encode) converts, averages and stores the planes or the interleaved rows.  lanczos_resize_force applies to every
+ * plane; the scratch lives as the other scratch of a context does. */
+typedef struct lanczos_ycc_dest {
+    int64_t y_row_stride, c_row_stride;   /* bytes; of NV12 / NV21 c_row_stride is that of the interleaved rows (>= 2 ocw) */
+    int64_t cb_offset, cr_offset;         /* bytes from the frame base to the first chroma sample; NV12 / NV21: both the same */
+    int32_t layout, sub_x, sub_y;         /* LANCZOS_YCC_PLANAR / _NV12 / _NV21; 0 or 1 */
+    int32_t reserved[5];                  /* must be 0 */
+} lanczos_ycc_dest;
+/* Host only: the tight layout of the stored frame (win NULL: the whole output) -- Y, then Cb, then Cr (or the interleaved
+ * plane), rows packed.  Only the window's size is read, not its origin.  LANCZOS_ERR_BAD_ARG as validate otherwise. */
+int lanczos_ycc_dest_init(lanczos_ycc_dest* dst, const lanczos_resize_desc* d, const lanczos_resize_window* win, int layout,
+                          int sub_x, int sub_y);
+/* Host only: the rules of lanczos_ycc_source_validate, mirrored.  LANCZOS_ERR_UNSUPPORTED: LANCZOS_RESIZE_ALPHA, _U16 or _F32
+ * in d.  LANCZOS_ERR_BAD_ARG: a null pointer, what lanczos_resize_validate or lanczos_resize_window_validate refuses, channels
+ * other than 3, an unknown layout, a subsampling other than 0 or 1, NV12 / NV21 with sub_x != 1 or with two different offsets, a
+ * row stride below a plane's row (or above 2^40), a negative offset, planes that overlap (a plane is its rows times its row
+ * stride), a window origin that is no multiple of the subsampling (the rule of a YCbCr source; lanczos_resize_ycc_out does not
+ * apply it to RGB frames), a non-zero reserved word.  Planes may lie at any byte address with any pitch.  The frame's extent is
+ * the end of its last plane: out_frame_stride 0 stands for it; a stride need only clear the last byte the layout names. */
+int lanczos_ycc_dest_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_ycc_dest* dst);
+/* Host only: the forward table t[3][3][256] of a standard (above).  LANCZOS_ERR_BAD_ARG: a null t, an unknown standard. */
+int lanczos_ycc_table_forward(int standard, int32_t* t);
+#define LANCZOS_MEM_DEVICE 0   /* in, out and table are device pointers; asynchronous on `stream` */
+#define LANCZOS_MEM_HOST 1     /* ... host pointers; synchronous; frames lie one extent apart (the frame strides must be 0) */
+typedef struct lanczos_ycc_out_request {
+    const lanczos_resize_desc* d;      /* channels = 3; in_w x in_h the luma or RGB size.  _ALPHA, _U16, _F32: UNSUPPORTED */
+    const lanczos_resize_opts* opts;   /* may be NULL */
+    const lanczos_resize_window* win;  /* may be NULL */
+    const lanczos_ycc_source* src;     /* NULL: the frames at `in` are packed RGB */
+    const lanczos_ycc_dest* dst;
+    const int32_t* table;              /* from RGB: the forward table, read WHEN THE KERNELS RUN; from YCbCr it must be NULL */
+    const void* in;                    /* any byte address */
+    void* out;                         /* any byte address */
+    int32_t frames;
+    int32_t memory;                    /* LANCZOS_MEM_DEVICE or LANCZOS_MEM_HOST */
+    size_t in_frame_stride;            /* bytes, any residue; 0: the source's extent, or in_w * in_h * 3 */
+    size_t out_frame_stride;           /* bytes, any residue; 0: the destination's extent */
+    void* stream;                      /* LANCZOS_MEM_DEVICE only */
+    int32_t reserved[4];               /* must be 0 */
+} lanczos_ycc_out_request;
+/* The one launching entry.  LANCZOS_ERR_BAD_ARG: a null request, d, dst, in or out, frames < 1, an unknown memory, a table with
+ * src or none without, a table off a dword, what the validations above refuse, frame strides below the layouts' needs. */
+int lanczos_resize_ycc_out(lanczos_ctx* ctx, const lanczos_ycc_out_request* rq);
+/* What the last successful lanczos_resize_ycc_out on the context launched.  From YCbCr: the LANCZOS_KERNEL_* of the luma and of
+ * the chroma resize (LANCZOS_KERNEL_NONE: a copy), whether k_rs_ycc_split and k_rs_ycc_join ran; from RGB: luma_kernel is the
+ * kernel of the RGB resize (LANCZOS_KERNEL_NONE: a copy, a crop, or nothing at all), chroma_kernel LANCZOS_KERNEL_NONE, encode 1.
+ * launches counts everything: resize kernels, copies, split, join, encode.  All zero before any call. */
+typedef struct lanczos_ycc_out_info {
+    int32_t luma_kernel, chroma_kernel, split, join, encode, launches;
+    int32_t reserved[2];
+} lanczos_ycc_out_info;
+int lanczos_last_ycc_out_info(const lanczos_ctx* ctx, lanczos_ycc_out_info* info);
+
 /* ---- reduce by whole factors (Pillow's Image.reduce((fx, fy), box), an exact integer box average) ----
  * 8-bit, 1, 3 or 4 independent interleaved channels.  box = (x0, y0, x1, y1), integers with 0 <= x0 < x1 <= in_w and the same
  * for y; NULL = the whole frame.  The output is ceil((x1 - x0) / fx) x ceil((y1 - y0) / fy) pixels, tightly packed rows.

@@ -91,10 +91,13 @@ ABI_SYMBOLS = [
     "lanczos_resize_tensor_norm_host",
     "lanczos_ycc_source_init", "lanczos_ycc_source_validate", "lanczos_ycc_table", "lanczos_resize_ycc_device",
     "lanczos_resize_ycc_tensor_device", "lanczos_resize_ycc_host", "lanczos_resize_ycc_tensor_host", "lanczos_last_ycc_info",
+    "lanczos_ycc_dest_init", "lanczos_ycc_dest_validate", "lanczos_ycc_table_forward", "lanczos_resize_ycc_out",
+    "lanczos_last_ycc_out_info",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
 YCC_PLANAR, YCC_NV12, YCC_NV21 = 0, 1, 2   # lanczos_ycc_source.layout
 YCC_JFIF, YCC_BT601, YCC_BT709 = 0, 1, 2   # the standards of lanczos_ycc_table
+MEM_DEVICE, MEM_HOST = 0, 1                 # lanczos_ycc_out_request.memory
 YCC_STANDARDS = {"jfif": YCC_JFIF, "bt601": YCC_BT601, "bt709": YCC_BT709}
 # the frame layouts Context.resize_ycc knows by name: (layout, sub_x, sub_y)
 YCC_LAYOUTS = {"nv12": (YCC_NV12, 1, 1), "nv21": (YCC_NV21, 1, 1), "i420": (YCC_PLANAR, 1, 1), "i422": (YCC_PLANAR, 1, 0),
@@ -254,6 +257,32 @@ class YccInfo(collections.namedtuple("YccInfo", "luma_kernel chroma_kernel split
     whether the interleaved chroma was split into planes first, and the number of launches of the call."""
 
 
+class YccDest(ctypes.Structure):
+    """lanczos_ycc_dest -- where the planes of a YCbCr result frame go: the fields of YccSource, for the stored frame (the
+    window) of w x h luma samples and chroma planes of ((w + sub_x) >> sub_x) x ((h + sub_y) >> sub_y) samples."""
+    _fields_ = YccSource._fields_
+
+
+class YccOutRequest(ctypes.Structure):
+    """lanczos_ycc_out_request -- one call of lanczos_resize_ycc_out.  The pointer fields are addresses: whoever fills them in
+    keeps the structs they name alive (ycc_out_request does, on the request itself)."""
+    _fields_ = [("d", ctypes.c_void_p), ("opts", ctypes.c_void_p), ("win", ctypes.c_void_p), ("src", ctypes.c_void_p),
+                ("dst", ctypes.c_void_p), ("table", ctypes.c_void_p), ("in_", ctypes.c_void_p), ("out", ctypes.c_void_p),
+                ("frames", ctypes.c_int32), ("memory", ctypes.c_int32), ("in_frame_stride", ctypes.c_size_t),
+                ("out_frame_stride", ctypes.c_size_t), ("stream", ctypes.c_void_p), ("reserved", ctypes.c_int32 * 4)]
+
+
+class YccOutInfoC(ctypes.Structure):   # include/lanczos_hip.h: lanczos_ycc_out_info
+    _fields_ = [(n, ctypes.c_int32) for n in ("luma_kernel", "chroma_kernel", "split", "join", "encode", "launches")] + [
+        ("reserved", ctypes.c_int32 * 2)]
+
+
+class YccOutInfo(collections.namedtuple("YccOutInfo", "luma_kernel chroma_kernel split join encode launches")):
+    """lanczos_last_ycc_out_info: KERNEL_* of the luma and of the chroma resize of the last resize_*_to_ycc call (KERNEL_NONE: a
+    copy; from RGB luma_kernel is the RGB resize's), whether k_rs_ycc_split, k_rs_ycc_join and k_rs_ycc_encode ran, and the
+    number of launches of the call."""
+
+
 FLIP_H, FLIP_V = 1, 2   # the bits of lanczos_tensor_view.flip and of a d_flip byte
 _FLIP_NAMES = {None: 0, "": 0, "h": FLIP_H, "v": FLIP_V, "hv": FLIP_H | FLIP_V, "vh": FLIP_H | FLIP_V}
 
@@ -269,6 +298,7 @@ _I, _P, _Z, _F = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_double
 _PI, _PF, _PP = ctypes.POINTER(_I), ctypes.POINTER(_F), ctypes.POINTER(_P)
 _PD, _PRD, _PRO, _PRW, _PRC, _PRS, _PRT, _PYS = (ctypes.POINTER(t) for t in (Desc, ResizeDesc, ResizeOpts, ResizeWindow, ResizeCrops,
                                                                            ResizeSource, ResizeDest, YccSource))
+_PYD = ctypes.POINTER(YccDest)
 _PTO, _PTO16, _PTV, _PTN = (ctypes.POINTER(t) for t in (TensorOut, TensorOut16, TensorView, TensorNorm))
 _PLAN, _PLANX = ctypes.POINTER(ResizePlan), ctypes.POINTER(ResizePlanEx)
 
@@ -372,6 +402,11 @@ _SIGNATURES = {
     "lanczos_ycc_source_validate": ([_PRD, _PYS], None),
     "lanczos_ycc_table": ([_I, _P], None),
     "lanczos_last_ycc_info": ([_P, ctypes.POINTER(YccInfoC)], None),
+    "lanczos_ycc_dest_init": ([_PYD, _PRD, _PRW, _I, _I, _I], None),
+    "lanczos_ycc_dest_validate": ([_PRD, _PRW, _PYD], None),
+    "lanczos_ycc_table_forward": ([_I, _P], None),
+    "lanczos_resize_ycc_out": ([_P, ctypes.POINTER(YccOutRequest)], None),
+    "lanczos_last_ycc_out_info": ([_P, ctypes.POINTER(YccOutInfoC)], None),
 }
 for _device, _host, _head in _ENTRY_PAIRS:
     _SIGNATURES[_host] = ([_P] + _head + [_P, _P, _I], None)
@@ -733,9 +768,83 @@ def ycc_table(standard="jfif"):
     return t
 
 
-def _ycc_table_arg(standard, table, what):
+def _ycc_layout_arg(layout, sub_x, sub_y, what):
+    """(code, sub_x, sub_y) of a layout given by a name of YCC_LAYOUTS or by its code with both subsamplings"""
+    if isinstance(layout, str):
+        if layout.lower() not in YCC_LAYOUTS:
+            raise LanczosError(ERR_BAD_ARG, f"{what}: layout is one of {', '.join(YCC_LAYOUTS)}, not {layout!r}")
+        code, sx, sy = YCC_LAYOUTS[layout.lower()]
+        return code, (sx if sub_x is None else int(sub_x)), (sy if sub_y is None else int(sub_y))
+    if sub_x is None or sub_y is None:
+        raise LanczosError(ERR_BAD_ARG, f"{what}: a layout given by its code needs sub_x and sub_y")
+    return int(layout), int(sub_x), int(sub_y)
+
+
+def ycc_dest(desc, layout="nv12", window=None, sub_x=None, sub_y=None, y_row_stride=None, c_row_stride=None, cb_offset=None,
+             cr_offset=None, aligned=True):
+    """A validated YccDest for the frame a call with `desc` stores: its whole output, or `window` = (x0, y0, w, h) of it.
+    layout as ycc_source takes it.  The defaults are the tight layout (Y, then Cb, then Cr or the interleaved plane, rows
+    packed); strides and offsets in bytes replace them one by one.  aligned=False: the window origin is not checked against the
+    subsampling (RGB frames may be cut anywhere).  ycc_dest_frame_bytes gives the frame's extent."""
+    code, sx, sy = _ycc_layout_arg(layout, sub_x, sub_y, "ycc_dest")
+    win = resize_window(desc, window)
+    t = YccDest()
+    _check(_lib().lanczos_ycc_dest_init(ctypes.byref(t), ctypes.byref(desc), ctypes.byref(win), code, sx, sy), "lanczos_ycc_dest_init")
+    for name, v in (("y_row_stride", y_row_stride), ("c_row_stride", c_row_stride), ("cb_offset", cb_offset), ("cr_offset", cr_offset)):
+        if v is not None:
+            setattr(t, name, int(v))
+    if code != YCC_PLANAR and cb_offset is not None and cr_offset is None:
+        t.cr_offset = t.cb_offset
+    if not aligned:   # validated at the window's size: the layout's rules without the origin's
+        win = resize_window(desc, (0, 0, win.w, win.h))
+    _check(_lib().lanczos_ycc_dest_validate(ctypes.byref(desc), ctypes.byref(win), ctypes.byref(t)), "lanczos_ycc_dest_validate")
+    return t
+
+
+def ycc_dest_validate(desc, dest, window=None):
+    """lanczos_ycc_dest_validate: raises LanczosError (ERR_BAD_ARG / ERR_UNSUPPORTED) where the layout is refused."""
+    _check(_lib().lanczos_ycc_dest_validate(ctypes.byref(desc), _window_ref(desc, window), _ref(dest)), "lanczos_ycc_dest_validate")
+
+
+def ycc_dest_chroma_size(desc, dest, window=None):
+    """(ocw, och): the size of the stored chroma planes"""
+    win = resize_window(desc, window)
+    return (win.w + dest.sub_x) >> dest.sub_x, (win.h + dest.sub_y) >> dest.sub_y
+
+
+def ycc_dest_frame_bytes(desc, dest, window=None):
+    """The extent of one frame in `dest`'s layout: the end of its last plane, every plane holding its full pitched rows."""
+    win = resize_window(desc, window)
+    ch = (win.h + dest.sub_y) >> dest.sub_y
+    return max(win.h * dest.y_row_stride, dest.cb_offset + ch * dest.c_row_stride, dest.cr_offset + ch * dest.c_row_stride)
+
+
+def ycc_table_forward(standard="jfif"):
+    """int32 [3][3][256], t[c][k][v]: out[c] = clip8((t[c][0][R] + t[c][1][G] + t[c][2][B]) >> 6), c = Y, Cb, Cr.  "jfif" is
+    Pillow's convert("YCbCr") exactly; "bt601" and "bt709" are the limited-range matrices (lanczos_ycc_table_forward)."""
+    code = YCC_STANDARDS.get(standard.lower()) if isinstance(standard, str) else int(standard)
+    if code is None:
+        raise LanczosError(ERR_BAD_ARG, f"ycc_table_forward: standard is one of {', '.join(YCC_STANDARDS)}, not {standard!r}")
+    t = np.empty((3, 3, 256), dtype=np.int32)
+    _check(_lib().lanczos_ycc_table_forward(code, t.ctypes.data), "lanczos_ycc_table_forward")
+    return t
+
+
+def ycc_out_request(desc, dest, in_ptr, out_ptr, frames, source=None, table=None, opts=None, window=None, memory=MEM_DEVICE,
+                    in_frame_stride=0, out_frame_stride=0, stream=None):
+    """A YccOutRequest over ready structs (None: NULL) and addresses; the structs stay alive with it."""
+    rq = YccOutRequest()
+    rq._keep = (desc, dest, source, opts, window)
+    for name, v in (("d", desc), ("opts", opts), ("win", window), ("src", source), ("dst", dest)):
+        setattr(rq, name, ctypes.addressof(v) if v is not None else None)
+    rq.table, rq.in_, rq.out, rq.frames, rq.memory = table, in_ptr, out_ptr, int(frames), int(memory)
+    rq.in_frame_stride, rq.out_frame_stride, rq.stream = int(in_frame_stride), int(out_frame_stride), stream
+    return rq
+
+
+def _ycc_table_arg(standard, table, what, forward=False):
     if table is None:
-        return ycc_table(standard)
+        return ycc_table_forward(standard) if forward else ycc_table(standard)
     table = np.ascontiguousarray(table)
     if table.dtype != np.int32 or table.shape != (3, 3, 256):
         raise LanczosError(ERR_BAD_ARG, f"{what}: the colour table is int32 [3][3][256]")
@@ -1486,6 +1595,74 @@ class Context:
         self._bound[_ycc_entry, "device", box is not None or reducing_gap is not None or opts is not None, window is not None,
                     source is not None, True, True](
             desc, box, reducing_gap, opts, window, source, d_table, v, d_in, d_out, frames, in_frame_stride, out_frame_stride, stream)
+
+    def _ycc_out(self, d, dest, in_ptr, out_ptr, frames, source, table, box, reducing_gap, opts, window, memory, in_fs=0, out_fs=0,
+                 stream=None):
+        if opts is None and (box is not None or reducing_gap is not None):
+            opts = resize_opts(d, box, reducing_gap)
+        if window is not None and not isinstance(window, ResizeWindow):
+            window = resize_window(d, window)
+        rq = ycc_out_request(d, dest, in_ptr, out_ptr, frames, source, table, opts, window, memory, in_fs, out_fs, stream)
+        self._call("lanczos_resize_ycc_out", ctypes.byref(rq))
+
+    def _ycc_out_host(self, d, x, dest, out_layout, source, table, box, reducing_gap, window, rgb, out):
+        """the host side of resize_ycc_to_ycc / resize_rgb_to_ycc: x is [N][bytes of a frame]; out: a caller's buffer [N][extent]"""
+        t = dest if dest is not None else ycc_dest(d, out_layout, window, aligned=not rgb)
+        n = ycc_dest_frame_bytes(d, t, window)
+        if out is None:
+            out = np.zeros((x.shape[0], n), dtype=np.uint8)
+        elif out.dtype != np.uint8 or not out.flags.c_contiguous or out.shape != (x.shape[0], n):
+            raise LanczosError(ERR_BAD_ARG, f"out: expected a contiguous uint8 [{x.shape[0]}][{n}]")
+        self._ycc_out(d, t, x.ctypes.data, out.ctypes.data, x.shape[0], source, table.ctypes.data if table is not None else None,
+                      box, reducing_gap, None, window, MEM_HOST)
+        return out
+
+    def resize_ycc_to_ycc(self, frames, in_w, in_h, out_w, out_h, layout="nv12", out_layout="nv12", filter=FILTER_LANCZOS, a=3,
+                          box=None, reducing_gap=None, window=None, source=None, dest=None, out=None):
+        """YCbCr frames -> YCbCr frames, uint8 [N][B'] (or [B'] for one frame [B]), each frame its bytes as `out_layout`
+        ("nv12", "nv21", "i420", "i422", "i444": tight) or `dest` (ycc_dest) lays them out: byte for byte Pillow's "L" resize
+        of every plane, luma to out_w x out_h and chroma to the destination's chroma size with the box scaled to its plane, no
+        colour conversion.  frames, layout / source, box, reducing_gap, filter and a as Context.resize_ycc; window =
+        (x0, y0, w, h) in luma output pixels, the origin a multiple of the destination's subsampling.  Bytes of the result
+        that the layout does not name are zero, or keep what the caller's `out` ([N][extent]) held."""
+        d, src, x0, x = self._ycc_host_args(frames, in_w, in_h, out_w, out_h, layout, filter, a, source, "resize_ycc_to_ycc")
+        res = self._ycc_out_host(d, x, dest, out_layout, src, None, box, reducing_gap, window, False, out)
+        return res if x0.ndim == 2 else res[0]
+
+    def resize_rgb_to_ycc(self, img, out_w, out_h, out_layout="nv12", standard="jfif", table=None, filter=FILTER_LANCZOS, a=3,
+                          box=None, reducing_gap=None, window=None, dest=None, out=None):
+        """RGB images, uint8 [H][W][3] or [N][H][W][3] -> YCbCr frames as resize_ycc_to_ycc returns them: Pillow's resize of the
+        RGB image (cut to `window`, any origin), convert("YCbCr") under standard="jfif" and Image.reduce of the chroma planes
+        where the layout subsamples them.  table: an int32 [3][3][256] of the caller's instead of ycc_table_forward(standard)."""
+        x = np.ascontiguousarray(img)
+        if x.dtype != np.uint8 or x.ndim not in (3, 4) or x.shape[-1] != 3:
+            raise LanczosError(ERR_BAD_ARG, "resize_rgb_to_ycc: expected uint8 [H][W][3] or [N][H][W][3]")
+        x4 = x if x.ndim == 4 else x[None]
+        d = resize_desc(x4.shape[2], x4.shape[1], out_w, out_h, 3, a, filter=filter)
+        t = _ycc_table_arg(standard, table, "resize_rgb_to_ycc", forward=True)
+        res = self._ycc_out_host(d, x4.reshape(x4.shape[0], -1), dest, out_layout, None, t, box, reducing_gap, window, True, out)
+        return res if x.ndim == 4 else res[0]
+
+    def resize_ycc_to_ycc_device(self, desc, source, dest, d_in, d_out, frames, in_frame_stride=0, out_frame_stride=0, stream=None,
+                                 box=None, reducing_gap=None, opts=None, window=None):
+        """Device pointers, asynchronous on `stream`: YCbCr frames at d_in in `source`'s layout -> YCbCr frames at d_out in
+        `dest`'s (ycc_dest, of `window` where one is given), any byte addresses, frames in_frame_stride / out_frame_stride bytes
+        apart (0 = the layouts' extents).  Bytes the destination does not name keep their contents."""
+        self._ycc_out(desc, dest, d_in, d_out, frames, source, None, box, reducing_gap, opts, window, MEM_DEVICE, in_frame_stride,
+                      out_frame_stride, stream)
+
+    def resize_rgb_to_ycc_device(self, desc, dest, d_table, d_in, d_out, frames, in_frame_stride=0, out_frame_stride=0, stream=None,
+                                 box=None, reducing_gap=None, opts=None, window=None):
+        """... tightly packed RGB frames at d_in (in_frame_stride 0 = in_w * in_h * 3) -> YCbCr frames at d_out.  d_table:
+        device, int32 [3][3][256] (ycc_table_forward), read when the kernels run."""
+        self._ycc_out(desc, dest, d_in, d_out, frames, None, d_table, box, reducing_gap, opts, window, MEM_DEVICE, in_frame_stride,
+                      out_frame_stride, stream)
+
+    def last_ycc_out_info(self):
+        """YccOutInfo of the last successful resize_*_to_ycc* call on the context (all zero before any)."""
+        info = YccOutInfoC()
+        self._call("lanczos_last_ycc_out_info", ctypes.byref(info))
+        return YccOutInfo(info.luma_kernel, info.chroma_kernel, bool(info.split), bool(info.join), bool(info.encode), info.launches)
 
     def last_ycc_info(self):
         """YccInfo of the last successful resize_ycc* call on the context (all zero before any)."""

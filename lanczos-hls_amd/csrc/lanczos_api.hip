@@ -66,6 +66,7 @@ struct lanczos_ctx {
     int last_source_route = 0;   // lanczos_last_source_route: LANCZOS_SOURCE_* of the last call that had a source layout
     int last_dest_route = 0;     // lanczos_last_dest_route: LANCZOS_DEST_* of the last call that had a destination layout
     lanczos_ycc_info last_ycc{};  // lanczos_last_ycc_info: what the last successful lanczos_resize_ycc_* call launched
+    lanczos_ycc_out_info last_ycc_out{};  // lanczos_last_ycc_out_info: ... lanczos_resize_ycc_out call launched
     int last_route = 0;      // lanczos_last_route: main kernel, prefix route and launch count of the last upscale call
     int route_launches = 0;  // launches of the call in flight (reset by the entry points, counted where a launch is issued)
     int route_seen = 0;      // prefix routes of those launches, one bit each
@@ -1524,6 +1525,70 @@ int lanczos_resize_ycc_tensor_host(lanczos_ctx* ctx, const lanczos_resize_desc* 
                                    const lanczos_resize_window* win, const lanczos_ycc_source* src, const int32_t* table,
                                    const lanczos_tensor_view* v, const void* in, void* out, int frames) {
     return resize_ycc(ctx, d, opts, win, src, table, v, true, host_bufs(in, out, frames));
+}
+
+// ---- into YCbCr frames (lanczos_resize_ycc_out.hip) ----------------------------------------------------------------------
+int lanczos_ycc_dest_init(lanczos_ycc_dest* dst, const lanczos_resize_desc* d, const lanczos_resize_window* win, int layout,
+                          int sub_x, int sub_y) {
+    if (!dst) return LANCZOS_ERR_BAD_ARG;
+    int rc = lz::ycc_desc_validate(d);
+    lz::RsWindow w;
+    if (rc == LANCZOS_OK) rc = lz::resize_window_resolve(d, win, &w);
+    if (rc != LANCZOS_OK) return rc;
+    if ((sub_x | sub_y) & ~1) return LANCZOS_ERR_BAD_ARG;
+    const int64_t cw = (w.w + sub_x) >> sub_x, ch = (w.h + sub_y) >> sub_y, luma = (int64_t)w.w * w.h;
+    *dst = lanczos_ycc_dest{};
+    dst->layout = layout, dst->sub_x = sub_x, dst->sub_y = sub_y;
+    dst->y_row_stride = w.w, dst->cb_offset = luma;
+    if (layout == LANCZOS_YCC_PLANAR) dst->c_row_stride = cw, dst->cr_offset = luma + cw * ch;
+    else dst->c_row_stride = 2 * cw, dst->cr_offset = luma;
+    lz::YccDest s;
+    return lz::ycc_dest_resolve(w, dst, false, &s);
+}
+
+int lanczos_ycc_dest_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_ycc_dest* dst) {
+    int rc = lz::ycc_desc_validate(d);
+    lz::RsWindow w;
+    if (rc == LANCZOS_OK) rc = lz::resize_window_resolve(d, win, &w);
+    if (rc != LANCZOS_OK) return rc;
+    lz::YccDest s;
+    return lz::ycc_dest_resolve(w, dst, true, &s);
+}
+
+int lanczos_ycc_table_forward(int standard, int32_t* t) {
+    return t && lz::ycc_table_forward(standard, t) ? LANCZOS_OK : LANCZOS_ERR_BAD_ARG;
+}
+
+int lanczos_last_ycc_out_info(const lanczos_ctx* ctx, lanczos_ycc_out_info* info) {
+    if (!ctx || !info) return LANCZOS_ERR_BAD_ARG;
+    *info = ctx->last_ycc_out;
+    return LANCZOS_OK;
+}
+
+int lanczos_resize_ycc_out(lanczos_ctx* ctx, const lanczos_ycc_out_request* rq) {
+    if (!ctx || !rq || !rq->in || !rq->out || !rq->dst || rq->frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    if (rq->memory != LANCZOS_MEM_DEVICE && rq->memory != LANCZOS_MEM_HOST) return LANCZOS_ERR_BAD_ARG;
+    for (int32_t r : rq->reserved)
+        if (r != 0) return LANCZOS_ERR_BAD_ARG;
+    const bool host = rq->memory == LANCZOS_MEM_HOST;
+    lz::YccOutRequest q;
+    q.d = rq->d, q.o = rq->opts, q.win = rq->win, q.from_rgb = rq->src == nullptr, q.dst = rq->dst, q.table = rq->table;
+    q.in = rq->in, q.out = rq->out, q.frames = rq->frames;
+    q.in_frame_stride = rq->in_frame_stride, q.out_frame_stride = rq->out_frame_stride, q.stream = (hipStream_t)rq->stream;
+    int rc = lz::ycc_desc_validate(rq->d);
+    if (rc != LANCZOS_OK) return rc;
+    if (q.from_rgb ? !rq->table : rq->table != nullptr) return LANCZOS_ERR_BAD_ARG;   // the table belongs to RGB frames, and only to them
+    if (!q.from_rgb && (rc = lz::ycc_source_resolve(rq->d, rq->src, &q.s)) != LANCZOS_OK) return rc;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    if (host && !ctx->stream) return LANCZOS_ERR_HIP;
+    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
+    route_begin(ctx);
+    if (host) q.stream = ctx->stream;
+    q.last_kernel = &ctx->last_kernel, q.last_hip = &ctx->last_hip;
+    rc = host ? lz::resize_ycc_out_host(ctx->resize, q) : lz::resize_ycc_out_device(ctx->resize, q);
+    if (rc == LANCZOS_OK) ctx->last_ycc_out = q.info, ctx->last_kernel = q.info.luma_kernel;
+    return rc;
 }
 
 int lanczos_reduce_size(int in_w, int in_h, int fx, int fy, const int32_t* box, int* out_w, int* out_h) {

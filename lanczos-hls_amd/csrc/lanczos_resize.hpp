@@ -11,7 +11,8 @@
 // lanczos_resize_dest_source.hip (8-bit into a planar destination), lanczos_resize16.hip and lanczos_resize32.hip, and
 // lanczos_resize_tensor_norm16.hip and lanczos_resize_tensor_norm32.hip (16-bit and float samples into normalised tensor elements,
 // lanczos_tensor_norm; their converter is in lanczos_resize_tensor_norm.hip).  YCbCr frames (lanczos_resize_ycc_*) are three
-// one-channel requests through resize_device with a split in front and a merge behind, in lanczos_resize_ycc.hip.  The filter of a request (LANCZOS_RESIZE_FILTER)
+// one-channel requests through resize_device with a split in front and a merge behind, in lanczos_resize_ycc.hip; the way back
+// (lanczos_resize_ycc_out: planes with a pitched destination and a join, or RGB frames and an encode) is in lanczos_resize_ycc_out.hip.  The filter of a request (LANCZOS_RESIZE_FILTER)
 // only changes the tables; LANCZOS_FILTER_NEAREST has index tables and a kernel of its own (lanczos_resize_nearest.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -179,6 +180,8 @@ struct ResizeState {
     ScratchBlock stage_in, stage_out;        // staging of lanczos_resize_host
     ScratchBlock ycc_in;                     // the Cb and Cr planes k_rs_ycc_split makes of interleaved chroma (lanczos_resize_ycc.hip)
     ScratchBlock ycc_planes;                 // the resized Y, Cb and Cr planes k_rs_ycc_merge reads
+    ScratchBlock ycc_out;                    // the tight Cb and Cr planes k_rs_ycc_join interleaves (lanczos_resize_ycc_out.hip)
+    ScratchBlock ycc_rgb;                    // the tight resized RGB frames k_rs_ycc_encode reads
     explicit ResizeState(Lifetime* l) : life(l), axes(l, 32) {}
 };
 
@@ -440,6 +443,10 @@ struct YccSource {
 int ycc_desc_validate(const lanczos_resize_desc* d);
 int ycc_source_resolve(const lanczos_resize_desc* d, const lanczos_ycc_source* src, YccSource* s);
 bool ycc_table(int standard, int32_t* t);
+// clip8(sum >> 6) with the clamp in front of the shift: the sum held to [0, 255 * 64 + 63] and then shifted is the same byte.
+// (Shift first and clamp after compiles, two pixels at a time, into v_ashr_pk_u8_i32, and on an MI355X the dword that
+// instruction leaves did not have a clean upper half: OR-ed with pixels 2 and 3 it turned them into 255.)
+__device__ __forceinline__ uint32_t ycc_clip8_shift6(int sum) { return (uint32_t)(sum < 0 ? 0 : sum > 16383 ? 16383 : sum) >> 6; }
 // One call of the lanczos_resize_ycc_* entries, filled in by lanczos_api.hip
 struct YccRequest {
     const lanczos_resize_desc* d = nullptr;       // validated (ycc_desc_validate)
@@ -461,5 +468,44 @@ struct YccRequest {
 int resize_ycc_device(ResizeState* st, YccRequest& q);
 // host buffers, a host colour table, and of a tensor request a host element table and host flips; synchronous
 int resize_ycc_host(ResizeState* st, YccRequest& q);
+
+// ---- into YCbCr frames (lanczos_resize_ycc_out.hip): from a YCbCr source three one-channel requests with a pitched source and a
+// pitched destination, a split in front of interleaved chroma and a join behind it; from RGB bytes the three-channel request into
+// context scratch and k_rs_ycc_encode behind it.  A lanczos_ycc_dest resolved by ycc_dest_resolve for a w x h window:
+struct YccDest {
+    int layout = 0, sx = 0, sy = 0;
+    int cw = 0, ch = 0;                     // the stored chroma planes' size
+    size_t y_rs = 0, c_rs = 0;              // row strides (bytes); c_rs of NV12 / NV21 is the interleaved rows'
+    size_t cb_off = 0, cr_off = 0;          // NV12 / NV21: both the interleaved plane's
+    size_t extent = 0;                      // of one frame, the default frame stride: the end of its last plane
+    size_t named = 0;                       // from a frame's first byte to the last one the layout names, + 1
+    bool interleaved() const { return layout != LANCZOS_YCC_PLANAR; }
+};
+// aligned_origin: refuse a window origin that is no multiple of the subsampling (the rule of a YCbCr source)
+int ycc_dest_resolve(const RsWindow& w, const lanczos_ycc_dest* dst, bool aligned_origin, YccDest* s);
+bool ycc_table_forward(int standard, int32_t* t);
+// k_rs_ycc_split: shared with the composition above
+hipError_t ycc_split_launch(const uint8_t* in, size_t in_fs, const YccSource& s, uint8_t* out, size_t plane_bytes, int frames,
+                            hipStream_t stream);
+// One call of lanczos_resize_ycc_out, filled in by lanczos_api.hip
+struct YccOutRequest {
+    const lanczos_resize_desc* d = nullptr;       // validated (ycc_desc_validate)
+    const lanczos_resize_opts* o = nullptr;
+    const lanczos_resize_window* win = nullptr;
+    bool from_rgb = false;
+    YccSource s;                                  // resolved, where the frames are YCbCr
+    const lanczos_ycc_dest* dst = nullptr;        // resolved by the entry points, which know the window
+    const int32_t* table = nullptr;               // from RGB: the forward table [3][3][256]
+    const void* in = nullptr;
+    void* out = nullptr;
+    int frames = 0;
+    size_t in_frame_stride = 0, out_frame_stride = 0;
+    hipStream_t stream = nullptr;
+    int *last_kernel = nullptr, *last_hip = nullptr;
+    lanczos_ycc_out_info info{};                  // out, on LANCZOS_OK
+};
+int resize_ycc_out_device(ResizeState* st, YccOutRequest& q);
+// host buffers and a host table; frames one extent apart; synchronous.  The destination goes up before it comes back
+int resize_ycc_out_host(ResizeState* st, YccOutRequest& q);
 
 }  // namespace lz

@@ -129,8 +129,8 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_ycc_split(RsYccSplit g) {
     }
 }
 
-static hipError_t ycc_split_launch(const uint8_t* in, size_t in_fs, const YccSource& s, uint8_t* out, size_t plane_bytes, int frames,
-                                   hipStream_t stream) {
+hipError_t ycc_split_launch(const uint8_t* in, size_t in_fs, const YccSource& s, uint8_t* out, size_t plane_bytes, int frames,
+                            hipStream_t stream) {
     RsYccSplit g{};
     g.in_fs = in_fs, g.c_rs = s.c_rs, g.plane_bytes = plane_bytes, g.cw = s.cw, g.second_first = s.layout == LANCZOS_YCC_NV21;
     const unsigned items = (2u * (unsigned)s.cw) / 4u + 6u;   // dwords, and at most three bytes at either end
@@ -164,10 +164,7 @@ struct RsYccMerge {
 
 constexpr int kYccBlock = 4 * kRsThreads;   // pixels per workgroup: one dword of each plane per thread
 
-// clip8(sum >> 6) with the clamp in front of the shift: the sum held to [0, 255 * 64 + 63] and then shifted is the same byte.
-// (Shift first and clamp after compiles, two pixels at a time, into v_ashr_pk_u8_i32, and on an MI355X the dword that
-// instruction leaves did not have a clean upper half: OR-ed with pixels 2 and 3 it turned them into 255.)
-__device__ __forceinline__ uint32_t ycc_clip8_shift6(int sum) { return (uint32_t)(sum < 0 ? 0 : sum > 16383 ? 16383 : sum) >> 6; }
+// (ycc_clip8_shift6, the clamp in front of the shift, is in lanczos_resize.hpp: k_rs_ycc_encode shares it)
 
 // The 9 KiB table goes to LDS once per workgroup; -DLZ_YCC_TABLE_GLOBAL reads it through the caches instead (the A/B of
 // DESIGN.md 4.5).  Returns the pointer the conversions index

@@ -148,6 +148,12 @@ normalised bfloat16 CHW, 256 I420 frames 500x375 -> 341x256 with the centre 224x
 replaces (repeat_interleave of the chroma, the float matrix, round, clamp, cast, repack, then the existing RGB call);
 `rgb_floor`, the existing RGB call alone on frames converted beforehand (--parent-lib: on that build); `luma_only`, the luma
 plane's one-channel resize alone.  A summary line carries the ratios, the kernels and the launch count of the call.
+
+YO1, YO2 and YO3 (--only YO1,YO2,YO3) resize INTO YCbCr frames (lanczos_resize_ycc_out): 32 NV12 frames 3840x2160 -> 1920x1080
+NV12; 32 RGB frames 1920x1080 kept at size -> NV12 under BT.709; 32 RGB frames 3840x2160 -> 1280x720 I420.  Routes: `ycc_out`,
+the one call; `pipeline`, what it replaces (from NV12 the chroma split in torch, three one-channel resize calls and the
+re-interleave in torch; from RGB the RGB resize, then the float matrix, avg_pool2d, round, clamp, cast and repack in torch);
+`floor`, the luma call alone, or the RGB resize alone (--parent-lib: on that build).
 """
 import argparse
 import json
@@ -1270,6 +1276,115 @@ def run_ycc(name, args, ctx, torch, parent):
     torch.cuda.empty_cache()
 
 
+YCC_OUT_WORKLOADS = {   # name: (in_w, in_h, out_w, out_h, frames, source layout or None for RGB frames, destination layout, standard)
+    "YO1": (3840, 2160, 1920, 1080, 32, "nv12", "nv12", None),
+    "YO2": (1920, 1080, 1920, 1080, 32, None, "nv12", "bt709"),
+    "YO3": (3840, 2160, 1280, 720, 32, None, "i420", "jfif"),
+}
+
+
+def run_ycc_out(name, args, ctx, torch, parent):
+    """Into YCbCr frames (lanczos_resize_ycc_out): (a) `ycc_out`, the one call; (b) `pipeline`, what it replaces, built from the
+    other entries and torch -- from NV12: the chroma split in torch, three one-channel resize calls (luma straight into the
+    result's luma plane), the re-interleave in torch; from RGB: the RGB resize, then the float matrix, avg_pool2d, round, clamp,
+    cast and repack in torch; (c) `floor`: the luma call alone, or the RGB resize alone (--parent-lib: on that build).  (b)'s
+    matrix and average are float, so its bytes differ from (a)'s by design from RGB; from NV12 they are checked to agree."""
+    iw, ih, ow, oh, f, layout, out_layout, standard = YCC_OUT_WORKLOADS[name]
+    d = L.resize_desc(iw, ih, ow, oh, 3)
+    dst = L.ycc_dest(d, out_layout)
+    out_fb = L.ycc_dest_frame_bytes(d, dst)
+    ocw, och = L.ycc_dest_chroma_size(d, dst)
+    src = L.ycc_source(d, layout) if layout else None
+    in_fb = L.ycc_frame_bytes(d, src) if layout else iw * ih * 3
+    sets = max(2, -(-2 * 256 * 2 ** 20 // (f * in_fb)) + 1)
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    xs = [torch.randint(0, 256, (f, in_fb), dtype=torch.uint8, device="cuda", generator=gen) for _ in range(sets)]
+    ys = [torch.empty((f, out_fb), dtype=torch.uint8, device="cuda") for _ in range(sets)]
+    s = torch.cuda.current_stream().cuda_stream
+    table = torch.from_numpy(L.ycc_table_forward(standard)).cuda() if standard else None
+    d1 = L.resize_desc(iw, ih, ow, oh, 1)
+
+    def ycc_out(i):
+        y = ys[i % sets]
+        if layout:
+            ctx.resize_ycc_to_ycc_device(d, src, dst, xs[i % sets].data_ptr(), y.data_ptr(), f, stream=s)
+        else:
+            ctx.resize_rgb_to_ycc_device(d, dst, table.data_ptr(), xs[i % sets].data_ptr(), y.data_ptr(), f, stream=s)
+        return y[0]
+
+    def put_chroma(y, cb, cr):
+        if out_layout == "nv12":
+            c2 = y[:, ow * oh:].view(f, och, ocw, 2)
+            c2[..., 0], c2[..., 1] = cb, cr
+        else:
+            y[:, ow * oh:ow * oh + ocw * och] = cb.reshape(f, -1)
+            y[:, ow * oh + ocw * och:] = cr.reshape(f, -1)
+
+    if layout:
+        cw, chh = L.ycc_chroma_size(d, src)
+        dc = L.resize_desc(cw, chh, ocw, och, 1)
+        tmp = torch.empty((2, f, och, ocw), dtype=torch.uint8, device="cuda")
+
+        def pipeline(i):
+            x, y = xs[i % sets], ys[i % sets]
+            c2 = x[:, iw * ih:].view(f, chh, cw, 2)
+            cb, cr = c2[..., 0].contiguous(), c2[..., 1].contiguous()
+            ctx.resize_device(d1, x.data_ptr(), y.data_ptr(), f, in_fb, out_fb, s)
+            ctx.resize_device(dc, cb.data_ptr(), tmp[0].data_ptr(), f, 0, 0, s)
+            ctx.resize_device(dc, cr.data_ptr(), tmp[1].data_ptr(), f, 0, 0, s)
+            put_chroma(y, tmp[0], tmp[1])
+            return y[0]
+
+        def floor(i):
+            ctx.resize_device(d1, xs[i % sets].data_ptr(), ys[i % sets].data_ptr(), f, in_fb, out_fb, s)
+            return ys[i % sets][0, :ow * oh]
+        floor_in, floor_out = f * iw * ih, f * ow * oh
+    else:
+        rgb = torch.empty((f, oh, ow, 3), dtype=torch.uint8, device="cuda")
+        kr, kb = (0.299, 0.114) if standard != "bt709" else (0.2126, 0.0722)
+        kg = 1.0 - kr - kb
+        sy, sc, y0 = (1.0, 1.0, 0.0) if standard == "jfif" else (219.0 / 255.0, 224.0 / 255.0, 16.0)
+        m = torch.tensor([[kr * sy, kg * sy, kb * sy], [-kr / (2 * (1 - kb)) * sc, -kg / (2 * (1 - kb)) * sc, 0.5 * sc],
+                          [0.5 * sc, -kg / (2 * (1 - kr)) * sc, -kb / (2 * (1 - kr)) * sc]], dtype=torch.float32, device="cuda")
+        off = torch.tensor([y0, 128.0, 128.0], dtype=torch.float32, device="cuda")
+        q = lambda p: p.round().clamp(0, 255).to(torch.uint8)
+
+        def rgb_resize(c, i):
+            if c is None:
+                ctx.resize_device(d, xs[i % sets].data_ptr(), rgb.data_ptr(), f, 0, 0, s)
+            else:
+                c.resize_device(d, xs[i % sets].data_ptr(), rgb.data_ptr(), f, s)
+
+        def pipeline(i):
+            y = ys[i % sets]
+            rgb_resize(None, i)
+            ycc = rgb.float() @ m.t() + off
+            y[:, :ow * oh] = q(ycc[..., 0]).view(f, -1)
+            c = torch.nn.functional.avg_pool2d(ycc[..., 1:].permute(0, 3, 1, 2), 2)
+            put_chroma(y, q(c[:, 0]), q(c[:, 1]))
+            return y[0]
+
+        def floor(i):
+            rgb_resize(parent, i)
+            return rgb[0]
+        floor_in, floor_out = f * in_fb, f * ow * oh * 3
+
+    ycc_out(0)
+    info = ctx.last_ycc_out_info()
+    routes = {"ycc_out": ycc_out, "pipeline": pipeline, "floor": floor}
+    inb = {"ycc_out": f * in_fb, "pipeline": f * in_fb, "floor": floor_in}
+    outb = {"ycc_out": f * out_fb, "pipeline": f * out_fb, "floor": floor_out}
+    us = run_routes(name, f"{layout or 'rgb'} {iw}x{ih}->{ow}x{oh} {out_layout}" + (f" {standard}" if standard else ""), f, routes, inb,
+                    outb, args, ctx, torch, check=(("ycc_out", "pipeline"),) if layout else ())
+    print(json.dumps({"workload": name, "ycc_out_over_pipeline": round(us["ycc_out"] / us["pipeline"], 3),
+                      "ycc_out_over_floor": round(us["ycc_out"] / us["floor"], 3),
+                      "floor": ("luma call" if layout else "rgb resize") + (", parent" if parent and not layout else ", this build"),
+                      "luma_kernel": info.luma_kernel, "chroma_kernel": info.chroma_kernel, "split": info.split, "join": info.join,
+                      "encode": info.encode, "launches": info.launches, "measured": True}), flush=True)
+    del xs, ys
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -1287,7 +1402,9 @@ def main():
     ctx = L.Context(0)
     parent = ParentLib(args.parent_lib) if args.parent_lib else None
     for name in args.only.split(","):
-        if name in YCC_WORKLOADS:
+        if name in YCC_OUT_WORKLOADS:
+            run_ycc_out(name, args, ctx, torch, parent)
+        elif name in YCC_WORKLOADS:
             run_ycc(name, args, ctx, torch, parent)
         elif name in NORM_WORKLOADS:
             run_norm(name, args, ctx, torch, parent)
