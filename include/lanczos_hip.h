@@ -707,7 +707,7 @@ int lanczos_resize_tensor_crops_host(lanczos_ctx* ctx, const lanczos_resize_desc
  * reach a result).
  * Routes (lanczos_last_source_route): LANCZOS_SOURCE_DIRECT, the resize kernel reads the caller's memory -- the fused kernel,
  * for a pitched interleaved source of any sample type (with a window, a view or crops) and for a planar 8-bit source of 3 or 4
- * channels (bytes out or a tensor; planar instances of their own, lanczos_resize_source*.hip); a tightly packed interleaved
+ * channels (bytes out or a tensor; planar instances of their own); a tightly packed interleaved
  * source is DIRECT on every route, being the call without a source.  LANCZOS_SOURCE_PACKED, everything else: the two-pass
  * kernels, one pass, LANCZOS_FILTER_NEAREST, the copies, reducing_gap, oversize frames, a planar source with crops (and a
  * LANCZOS_RESIZE_ALPHA one whose row pitch is no multiple of 4 with crops), forced LANCZOS_RESIZE_TWO_PASS, and any source that
@@ -773,7 +773,7 @@ int lanczos_last_source_route(const lanczos_ctx* ctx);
  * bytes only; the partial dwords at the ends of a row go out as bytes.
  * Routes (lanczos_last_dest_route): LANCZOS_DEST_DIRECT, the resize kernel stored into the caller's layout itself -- the fused
  * kernel, into pitched interleaved rows of every sample type (the pitch is an argument every instance already has) and into
- * planes of 3 or 4 8-bit channels (planar-out instances of their own, lanczos_resize_dest*.hip), with a window and from an
+ * planes of 3 or 4 8-bit channels (planar-out instances of their own), with a window and from an
  * interleaved, pitched or planar source; a tightly packed interleaved destination is DIRECT on every route, being the call
  * without one.  LANCZOS_DEST_UNPACKED, everything else: the two-pass kernels, one pass, LANCZOS_FILTER_NEAREST, the copies,
  * reducing_gap, frames whose named span is 2^31 bytes or more, a planar destination from LANCZOS_RESIZE_ALPHA rows whose pitch

@@ -175,7 +175,7 @@ int reduce_validate(int in_w, int in_h, int channels, int fx, int fy, const int3
 }
 
 hipError_t reduce_launch(const uint8_t* in, uint8_t* out, int in_w, int channels, int fx, int fy, const int rb[4], int frames,
-                         size_t in_fs, size_t out_fs, hipStream_t stream) {
+                         size_t in_fs, size_t out_fs, RsIssue& is) {
     RdArgs g{};
     g.in_fs = in_fs, g.out_fs = out_fs;
     g.in_pitch = in_w * channels;
@@ -192,25 +192,14 @@ hipError_t reduce_launch(const uint8_t* in, uint8_t* out, int in_w, int channels
     const bool wide = fx * channels > kRdSpan;
     g.tile_ow = wide ? 1 : kRdSpan / (fx * channels);
     const int tiles = wide ? g.ow : (g.ow + g.tile_ow - 1) / g.tile_ow;
-    for (int f0 = 0; f0 < frames; f0 += 65535) {
-        const int nf = std::min(65535, frames - f0);
+    void (*kern)(RdArgs);
+    if (wide) kern = channels == 1 ? k_reduce_wide<1> : channels == 3 ? k_reduce_wide<3> : k_reduce_wide<4>;
+    else kern = channels == 1 ? k_reduce<1> : channels == 3 ? k_reduce<3> : k_reduce<4>;
+    return rs_for_frame_groups(is, frames, [&](int f0, int nf) {
         g.in = in + (size_t)f0 * in_fs;
         g.out = out + (size_t)f0 * out_fs;
-        const dim3 grid(tiles, g.oh, nf);
-#define LZ_RD_LAUNCH(KERNEL)                                                                          \
-    if (channels == 1) hipLaunchKernelGGL(KERNEL<1>, grid, dim3(kRsThreads), 0, stream, g);           \
-    else if (channels == 3) hipLaunchKernelGGL(KERNEL<3>, grid, dim3(kRsThreads), 0, stream, g);      \
-    else hipLaunchKernelGGL(KERNEL<4>, grid, dim3(kRsThreads), 0, stream, g);
-        if (wide) {
-            LZ_RD_LAUNCH(k_reduce_wide)
-        } else {
-            LZ_RD_LAUNCH(k_reduce)
-        }
-#undef LZ_RD_LAUNCH
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        hipLaunchKernelGGL(kern, dim3(tiles, g.oh, nf), dim3(kRsThreads), 0, is.stream, g);
+    });
 }
 
 }  // namespace lz

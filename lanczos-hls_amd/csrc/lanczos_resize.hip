@@ -8,7 +8,7 @@
 //             in LDS (buffer loads, range-checked zero fill), the horizontal pass turns them into rows of an LDS ring, stored
 //             as Pillow stores its intermediate, and the vertical pass reads the ring and stores the block's output rows.
 //             Horizontal coefficients stay in registers for the whole march (a thread keeps one output column); vertical
-//             ones are workgroup-uniform scalar loads.  This file compiles the 8-bit instances that store bytes.
+//             ones are workgroup-uniform scalar loads.
 //   two-pass  k_rs_pass_h writes the intermediate (the rows the vertical taps read x out_w x C per frame) to context
 //             scratch, k_rs_pass_v reads it: any tap count, every sample width, all compiled here.  It also serves a resize
 //             that changes one axis only (one kernel) -- as Pillow, a pass whose axis keeps its size is skipped.  And it alone
@@ -21,7 +21,7 @@
 //
 // LANCZOS_RESIZE_U16 (16-bit samples, Pillow's I;16) and LANCZOS_RESIZE_F32 (float samples, Pillow's mode F): the same tap
 // geometry with double coefficients (one set of tables and cache entries for both) and Pillow's double accumulation; a u16 or
-// float intermediate.  Their fused instances are compiled by lanczos_resize16.hip and lanczos_resize32.hip.
+// float intermediate.
 //
 // A source box (lanczos_resize_opts) only changes the tables: an axis is built over a span of the source given as two floats,
 // `first` still indexes the whole axis, and the kernels are the ones above.  reducing_gap puts lanczos_reduce.hip in front:
@@ -39,12 +39,12 @@
 //
 // A source layout (lanczos_resize_source: planar frames, pitched rows) changes where a source byte is fetched from and nothing
 // else: the fused kernel reads such frames as they lie (a pitch is one of its arguments; planar frames have staging loads and
-// instances of their own, lanczos_resize_source*.hip), every other route gets them packed into context scratch by
+// instances of their own), every other route gets them packed into context scratch by
 // k_rs_pack_source first (lanczos_resize_source.hip).
 //
 // A destination layout (lanczos_resize_dest: planar frames, pitched rows) changes where a result byte is stored and nothing
 // else: the fused kernel stores pitched interleaved rows itself (a pitch is one of its arguments) and planes through an epilogue
-// and instances of their own (lanczos_resize_dest*.hip), every other route stores the packed result in context scratch and
+// and instances of their own, every other route stores the packed result in context scratch and
 // k_rs_unpack_dest scatters it (lanczos_resize_dest.hip).
 //
 // The arithmetic is Pillow's and exact by construction; RsSample<BPS> says how for each width.
@@ -145,9 +145,6 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_h_alpha_last(RsPass<int32_t> 
     rs_store_px(p.dst + blockIdx.z * p.dst_fs + blockIdx.y * p.dst_pitch + (size_t)o * 4, rs_unpremul_px(rs_clip_px(acc)));
 }
 
-// the 8-bit instances of k_rs_fused that store bytes
-template hipError_t rs_launch_fused<1, 0>(const RsFusedLaunch&);
-
 // ---- host side: cache, planning, launch ---------------------------------------------------------------------------
 
 // The tables of one axis shape, built and uploaded on first use: first | count | coeffs in one block.  The upload is eager, so
@@ -189,7 +186,7 @@ static int rs_axis(ResizeState* st, int in_n, int out_n, int a, int filter, RsSp
 // v_first: both passes run, the vertical one first (rs_vertical_first); it only changes which alpha kernel a pass is
 static hipError_t rs_launch_pass(int bps, bool horizontal, const ResizeAxis* ax, int o0, int channels, const uint8_t* src, size_t src_fs,
                                  size_t src_pitch, uint8_t* dst, size_t dst_fs, size_t dst_pitch, int n_cols, int rows, int frames,
-                                 hipStream_t stream, bool alpha, bool only, bool v_first = false) {
+                                 RsIssue& is, bool alpha, bool only, bool v_first = false) {
     if (alpha && bps != 1) return hipErrorInvalidValue;
     auto run = [&](auto sample) {
         using S = decltype(sample);
@@ -205,31 +202,22 @@ static hipError_t rs_launch_pass(int bps, bool horizontal, const ResizeAxis* ax,
             else if (alpha && horizontal) kern = only ? k_rs_h_alpha<true> : k_rs_h_alpha<false>;
             else if (alpha) kern = only ? k_rs_v_alpha<true> : k_rs_v_alpha<false>;
         }
-        for (int f0 = 0; f0 < frames; f0 += 65535) {
-            const int nf = std::min(65535, frames - f0);
+        return rs_for_frame_groups(is, frames, [&](int f0, int nf) {
             p.src = src + (size_t)f0 * src_fs;
             p.dst = dst + (size_t)f0 * dst_fs;
             const int n_threads = alpha ? n_cols / 4 : n_cols;
-            const dim3 grid((n_threads + kRsThreads - 1) / kRsThreads, rows, nf);
-            hipLaunchKernelGGL(kern, grid, dim3(kRsThreads), 0, stream, p);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) return e;
-        }
-        return hipSuccess;
+            hipLaunchKernelGGL(kern, dim3((n_threads + kRsThreads - 1) / kRsThreads, rows, nf), dim3(kRsThreads), 0, is.stream, p);
+        });
     };
     return bps == 4 ? run(RsSample<4>()) : bps == 2 ? run(RsSample<2>()) : run(RsSample<1>());
 }
 
-// the instance of the fused kernel a route names: the cases are the instantiations lanczos_resize_fused.hpp declares
+// the instance of the fused kernel a route names: a case per entry of LZ_RS_FUSED_INSTANCES
 static hipError_t rs_launch_fused_any(int bps, int flags, const RsFusedLaunch& c) {
-    switch (bps << 8 | flags) {
-#define X(BPS, TENSOR) \
-    case (BPS) << 8 | (TENSOR): return rs_launch_fused<BPS, TENSOR>(c);
-        X(1, 0) X(1, 4) X(1, 2) X(1, 4 + kRsMapped) X(1, 2 + kRsMapped)
-        X(1, 4 + kRsMapped + kRsCrops) X(1, 2 + kRsMapped + kRsCrops)
-        X(1, kRsPlanar) X(1, 4 + kRsMapped + kRsPlanar) X(1, 2 + kRsMapped + kRsPlanar)
-        X(1, kRsRowShift) X(1, 4 + kRsMapped + kRsRowShift) X(1, 2 + kRsMapped + kRsRowShift)
-        X(1, kRsPlanarOut) X(1, kRsPlanar + kRsPlanarOut) X(2, 0) X(4, 0) X(2, kRsNorm) X(4, kRsNorm)
+    switch (bps << 12 | flags) {
+#define X(I, BPS, FLAGS) \
+    case (BPS) << 12 | (FLAGS): return rs_launch_fused<BPS, FLAGS>(c);
+        LZ_RS_FUSED_INSTANCES(X)
 #undef X
         default: return hipErrorInvalidValue;
     }
@@ -297,15 +285,17 @@ int resize_device(ResizeState* st, RsRequest& q) {
 
     const uint8_t* in = (const uint8_t*)q.in;
     hipError_t e = hipSuccess;
+    RsIssue is{stream};   // every launch below goes out through it and is counted where it does
     if (rt.pack) {
-        e = rs_pack_source_launch(in, in_fs, q.sc.s, (uint8_t*)st->packed.p, rt.packed.fs, d0->in_w, d0->in_h, C, (int)B, frames, stream);
+        e = rs_pack_source_launch(in, in_fs, q.sc.s, (uint8_t*)st->packed.p, rt.packed.fs, d0->in_w, d0->in_h, C, (int)B, frames, is);
         in = (const uint8_t*)st->packed.p, in_fs = rt.packed.fs;
     }
     if (rt.reduce && e == hipSuccess) {   // reducing_gap: reduce into context scratch, then resize the reduced frames
-        e = reduce_launch(in, (uint8_t*)st->reduced.p, d0->in_w, C, r.fx, r.fy, rb, frames, in_fs, rt.reduced.fs, stream);
+        e = reduce_launch(in, (uint8_t*)st->reduced.p, d0->in_w, C, r.fx, r.fy, rb, frames, in_fs, rt.reduced.fs, is);
         in = (const uint8_t*)st->reduced.p, in_fs = rt.reduced.fs;
     }
     if (e != hipSuccess) {
+        q.launches = is.launches;
         *q.last_hip = (int)e;
         return LANCZOS_ERR_HIP;
     }
@@ -321,81 +311,77 @@ int resize_device(ResizeState* st, RsRequest& q) {
     uint8_t* const mid = (uint8_t*)st->scratch.p;            // the intermediate of two passes
     switch (rt.main) {
         case kRsMainFused: {
-            const RsFusedLaunch c{d, win, &rt.fp, H, V, in, out, in_fs, step_fs, frames, q.tensor ? &q.tc : nullptr, stream,
+            const RsFusedLaunch c{d, win, &rt.fp, H, V, in, out, in_fs, step_fs, frames, q.tensor ? &q.tc : nullptr, is,
                                   rt.src_direct ? &q.sc.s : nullptr, rt.dst_direct ? &q.dc.s : nullptr};
             e = rs_launch_fused_any(rt.bps, rt.flags, c);
             break;
         }
         case kRsMainNearest:
             e = rs_nearest_launch(in, out, d->in_w, win.w, win.h, C, (int)B, H->first() + win.x0, V->first() + win.y0, frames, in_fs,
-                                  step_fs, stream);
+                                  step_fs, is);
             break;
         case kRsMainNone: break;   // nothing to copy: the gather below reads the caller's frames
         case kRsMainCopy:
             e = hipMemcpy2DAsync(out, step_fs, in, in_fs, (size_t)d->in_h * in_pitch, frames, hipMemcpyDeviceToDevice, stream);
+            if (e == hipSuccess) is.launches++;
             break;
         case kRsMainCrop:
             e = rs_crop_launch(in + (size_t)win.y0 * in_pitch + (size_t)win.x0 * px, out, in_pitch, (size_t)win.w * px, win.h, frames,
-                               in_fs, step_fs, stream);
+                               in_fs, step_fs, is);
             break;
         case kRsMainVFirst:
             // The vertical pass turns the window's rows of the source's full width (Pillow's, and at most 655 pixels) into win.h
             // rows of context scratch, stored as every intermediate is; the horizontal pass reads them through the window's slice
             // of its table, whose `first` indexes that full width, and writes the output.
             e = rs_launch_pass((int)B, false, V, win.y0, C, in, in_fs, in_cols, mid, rt.scratch.fs, in_cols, in_cols, win.h, frames,
-                               stream, alpha, false, true);
+                               is, alpha, false, true);
             if (e == hipSuccess)
                 e = rs_launch_pass((int)B, true, H, win.x0, C, mid, rt.scratch.fs, in_cols, out, step_fs, out_cols, out_cols, win.h,
-                                   frames, stream, alpha, false, true);
+                                   frames, is, alpha, false, true);
             break;
         case kRsMainPassH:   // the window's rows, which are the source's
             e = rs_launch_pass((int)B, true, H, win.x0, C, in + (size_t)win.y0 * in_pitch, in_fs, in_cols, out, step_fs, out_cols,
-                               out_cols, win.h, frames, stream, alpha, true);
+                               out_cols, win.h, frames, is, alpha, true);
             break;
         case kRsMainPassV:   // the window's columns of the source's full rows
             e = rs_launch_pass((int)B, false, V, win.y0, C, in + (size_t)win.x0 * px, in_fs, in_cols, out, step_fs, out_cols, out_cols,
-                               win.h, frames, stream, alpha, true);
+                               win.h, frames, is, alpha, true);
             break;
         case kRsMainTwoPass: {
             // the scratch holds rows mid_row0 .. mid_row0 + mid_rows of the horizontal pass's result; the vertical pass indexes it
             // through a base mid_row0 rows in front of it, which it never dereferences below the block (its first tap is mid_row0)
             const size_t mid_pitch = (size_t)win.w * px;
             e = rs_launch_pass((int)B, true, H, win.x0, C, in + (size_t)rt.mid_row0 * in_pitch, in_fs, in_cols, mid, rt.scratch.fs,
-                               out_cols, out_cols, rt.mid_rows, frames, stream, alpha, false);
+                               out_cols, out_cols, rt.mid_rows, frames, is, alpha, false);
             if (e == hipSuccess)
                 e = rs_launch_pass((int)B, false, V, win.y0, C,
                                    (const uint8_t*)((uintptr_t)mid - (uintptr_t)((size_t)rt.mid_row0 * mid_pitch)), rt.scratch.fs,
-                                   out_cols, out, step_fs, out_cols, out_cols, win.h, frames, stream, alpha, false);
+                                   out_cols, out, step_fs, out_cols, out_cols, win.h, frames, is, alpha, false);
             break;
         }
     }
     if (e == hipSuccess) switch (rt.follower) {
             case kRsFollowNone: break;
             case kRsFollowToTensor:
-                e = rs_to_tensor_launch(out, step_fs, (uint8_t*)q.out, out_fs, win.w, win.h, C, q.tc.t, frames, stream);
+                e = rs_to_tensor_launch(out, step_fs, (uint8_t*)q.out, out_fs, win.w, win.h, C, q.tc.t, frames, is);
                 break;
             case kRsFollowToTensorNorm:   // from the scratch the main step filled, or from the frames no step had to touch
                 e = rs_to_tensor_norm_launch(rt.follow_src ? in : out, rt.follow_src ? in_fs : step_fs, (uint8_t*)q.out, out_fs, win.w,
-                                             win.h, C, (int)B, q.tc.t, frames, stream);
+                                             win.h, C, (int)B, q.tc.t, frames, is);
                 break;
             case kRsFollowCropsScratch:
                 e = rs_to_tensor_crops_launch(out, step_fs, (size_t)win.w * C, win.w, win.h, (uint8_t*)q.out, out_fs, w.w, w.h, C,
-                                              q.tc.t, q.tc.d_origin, frames, stream);
+                                              q.tc.t, q.tc.d_origin, frames, is);
                 break;
             case kRsFollowCropsDirect:
                 e = rs_to_tensor_crops_launch(in, in_fs, in_pitch, d->in_w, d->in_h, (uint8_t*)q.out, out_fs, w.w, w.h, C, q.tc.t,
-                                              q.tc.d_origin, frames, stream);
+                                              q.tc.d_origin, frames, is);
                 break;
         }
     if (rt.unpacked.bytes && e == hipSuccess)
-        e = rs_unpack_dest_launch(out, step_fs, (uint8_t*)q.out, out_fs, q.dc.s, win.w, win.h, C, (int)B, frames, stream);
-    {   // the launches that went out, for the callers that report them (frames go 65535 per launch)
-        const int groups = (frames + 65534) / 65535;
-        const int main_n = rt.main == kRsMainNone ? 0 : rt.main == kRsMainCopy ? 1
-                           : (rt.main == kRsMainTwoPass || rt.main == kRsMainVFirst) ? 2 * groups : groups;
-        q.launches = main_n + groups * ((int)rt.pack + (int)rt.reduce + (int)(rt.follower != kRsFollowNone) + (int)(rt.unpacked.bytes != 0));
-        q.copied = !rt.reduce && (rt.main == kRsMainNone || rt.main == kRsMainCopy || rt.main == kRsMainCrop);
-    }
+        e = rs_unpack_dest_launch(out, step_fs, (uint8_t*)q.out, out_fs, q.dc.s, win.w, win.h, C, (int)B, frames, is);
+    q.launches = is.launches;
+    q.copied = !rt.reduce && (rt.main == kRsMainNone || rt.main == kRsMainCopy || rt.main == kRsMainCrop);
     *q.last_kernel = rt.kernel;
     q.tc.route = rt.tensor_route, q.sc.route = rt.source_route, q.dc.route = rt.dest_route;
     if (e != hipSuccess) {
@@ -496,8 +482,8 @@ int reduce_device(ResizeState* st, int in_w, int in_h, int channels, int fx, int
     const size_t in_fs = in_frame_stride ? in_frame_stride : in_frame;
     const size_t out_fs = out_frame_stride ? out_frame_stride : out_frame;
     if (in_fs < in_frame || out_fs < out_frame) return LANCZOS_ERR_BAD_ARG;
-    const hipError_t e = reduce_launch((const uint8_t*)d_in, (uint8_t*)d_out, in_w, channels, fx, fy, rb, frames, in_fs, out_fs,
-                                       stream);
+    RsIssue is{stream};
+    const hipError_t e = reduce_launch((const uint8_t*)d_in, (uint8_t*)d_out, in_w, channels, fx, fy, rb, frames, in_fs, out_fs, is);
     if (e != hipSuccess) {
         *last_hip = (int)e;
         return LANCZOS_ERR_HIP;

@@ -3,14 +3,8 @@
 // validation, tables, resolution, planning and rs_route, the one decision of what a request launches.  The table cache, the
 // scratch, the executor of a route (resize_device), the staging of the host entries and the alpha pass kernels are in
 // lanczos_resize.hip.  The kernels are written once for 8-bit, 16-bit (LANCZOS_RESIZE_U16) and float (LANCZOS_RESIZE_F32)
-// samples in lanczos_resize_fused.hpp; the fused instances are compiled by lanczos_resize.hip (8-bit), lanczos_resize_tensor.hip
-// (8-bit into float tensors), lanczos_resize_tensor16.hip (8-bit into bfloat16 / float16 tensors), lanczos_resize_tensor_view.hip
-// and lanczos_resize_tensor16_view.hip (the same two through a channel map and flips), lanczos_resize_tensor_crops.hip and
-// lanczos_resize_tensor16_crops.hip (those with a crop origin per frame), lanczos_resize_source.hip, lanczos_resize_source_tensor.hip
-// and lanczos_resize_source_tensor16.hip (those of a planar or oddly pitched source), lanczos_resize_dest.hip and
-// lanczos_resize_dest_source.hip (8-bit into a planar destination), lanczos_resize16.hip and lanczos_resize32.hip, and
-// lanczos_resize_tensor_norm16.hip and lanczos_resize_tensor_norm32.hip (16-bit and float samples into normalised tensor elements,
-// lanczos_tensor_norm; their converter is in lanczos_resize_tensor_norm.hip).  YCbCr frames (lanczos_resize_ycc_*) are three
+// samples in lanczos_resize_fused.hpp; LZ_RS_FUSED_INSTANCES below lists the fused instances and says which unit compiles what
+// (the converter of lanczos_tensor_norm is in lanczos_resize_tensor_norm.hip).  YCbCr frames (lanczos_resize_ycc_*) are three
 // one-channel requests through resize_device with a split in front and a merge behind, in lanczos_resize_ycc.hip; the way back
 // (lanczos_resize_ycc_out: planes with a pitched destination and a join, or RGB frames and an encode) is in lanczos_resize_ycc_out.hip.  The filter of a request (LANCZOS_RESIZE_FILTER)
 // only changes the tables; LANCZOS_FILTER_NEAREST has index tables and a kernel of its own (lanczos_resize_nearest.hip).
@@ -116,6 +110,25 @@ constexpr int kRsLoadBatch = 16;     // staging loads in flight per thread
 constexpr int kRsFusedMaxLds = 80 * 1024;   // at least two fused workgroups per CU (160 KiB of LDS)
 constexpr int kRsRowsPerChunkMin = 4 * kRsOB;
 constexpr int kRsTargetWgs = 2048;
+// Where a launcher issues and what it has issued: the stream, and the launches (kernels and copies) that went out on it, counted
+// where each goes out.  Every launcher below takes one in place of a stream
+struct RsIssue {
+    hipStream_t stream = nullptr;
+    int launches = 0;
+};
+// A grid dimension holds at most 65535 frames, so a batch goes out in groups of that many: launch(f0, nf) issues exactly one
+// launch for the nf frames from f0 on
+constexpr int kRsMaxGridFrames = 65535;
+template <class F>
+hipError_t rs_for_frame_groups(RsIssue& is, int frames, F&& launch) {
+    for (int f0 = 0; f0 < frames; f0 += kRsMaxGridFrames) {
+        launch(f0, frames - f0 < kRsMaxGridFrames ? frames - f0 : kRsMaxGridFrames);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        is.launches++;
+    }
+    return hipSuccess;
+}
 // horizontal tap counts with a fused instance (a request runs on the smallest one >= its ksize, zero-padded), for every
 // sample width.  3 and 5 serve the upscales of the short filters (box and bilinear: ksize 3, bicubic: 5) and only them: a
 // Lanczos request keeps the instance it always had (a = 2 upscales, ksize 5, run on 7).  LANCZOS_RS_NO_SMALL_BUCKETS=1 pads
@@ -245,16 +258,16 @@ bool tensor_lut_convert16(const float* in, int n, int format, uint16_t* out);
 // next dword multiple behind each frame) -> strided elements through the table
 // (t.mapped: through the channel map and the frames' flips)
 hipError_t rs_to_tensor_launch(const uint8_t* src, size_t src_fs, uint8_t* out, size_t out_fs, int w, int h, int channels,
-                               const RsTensorOut& t, int frames, hipStream_t stream);
+                               const RsTensorOut& t, int frames, RsIssue& is);
 // k_rs_to_tensor_norm (lanczos_resize_tensor_norm.hip): tightly packed interleaved samples of `bps` bytes (2 or 4; frames `src_fs`
 // apart at any multiple of bps, nothing read outside a frame) -> strided elements computed from them, through the map and flips
 hipError_t rs_to_tensor_norm_launch(const uint8_t* src, size_t src_fs, uint8_t* out, size_t out_fs, int w, int h, int channels,
-                                    int bps, const RsTensorOut& t, int frames, hipStream_t stream);
+                                    int bps, const RsTensorOut& t, int frames, RsIssue& is);
 // k_rs_to_tensor_crops (lanczos_resize_tensor_crops.hip): frame f's w x h window at its clamped origin of interleaved byte frames
 // of src_w x src_h pixels (rows src_pitch bytes apart, any alignment) -> strided elements through the map, flips and table
 hipError_t rs_to_tensor_crops_launch(const uint8_t* src, size_t src_fs, size_t src_pitch, int src_w, int src_h, uint8_t* out,
                                      size_t out_fs, int w, int h, int channels, const RsTensorOut& t, const int32_t* d_origin,
-                                     int frames, hipStream_t stream);
+                                     int frames, RsIssue& is);
 
 // A source layout (lanczos_resize_source), resolved by resize_source_resolve: sample (y, x, c) of a frame lies c * chan_stride +
 // y * row_stride + x * (planar ? 1 : C * B) bytes into it.  tight: interleaved with packed rows, the call without a source
@@ -276,7 +289,7 @@ constexpr bool kRsPlanarAutoDirect = true;
 // k_rs_pack_source (lanczos_resize_source.hip): `frames` frames of w x h pixels of C samples of B bytes in layout s, in_fs
 // bytes apart at any byte address, to tightly packed interleaved frames out_fs bytes apart (out and out_fs dword multiples)
 hipError_t rs_pack_source_launch(const uint8_t* in, size_t in_fs, const RsSource& s, uint8_t* out, size_t out_fs, int w, int h,
-                                 int C, int B, int frames, hipStream_t stream);
+                                 int C, int B, int frames, RsIssue& is);
 
 // A destination layout (lanczos_resize_dest), resolved by resize_dest_resolve for a w x h window: sample (y, x, c) of a frame goes
 // c * chan_stride + y * row_stride + x * (planar ? 1 : C * B) bytes into it.  tight: interleaved with packed rows, the call
@@ -301,7 +314,7 @@ constexpr bool kRsPlanarOutAutoDirect = true;
 // in_fs bytes apart (in and in_fs dword multiples, readable 32 bytes past the last frame), scattered into layout s at any byte
 // address, frames out_fs bytes apart.  Only bytes the layout names are written
 hipError_t rs_unpack_dest_launch(const uint8_t* in, size_t in_fs, uint8_t* out, size_t out_fs, const RsDest& s, int w, int h,
-                                 int C, int B, int frames, hipStream_t stream);
+                                 int C, int B, int frames, RsIssue& is);
 
 // One resize request, as every entry of lanczos_api.hip fills it in and the entry points below take it.
 struct RsRequest {
@@ -378,13 +391,13 @@ int resize_host(ResizeState* st, RsRequest& q);
 // reduce_validate; the output rows are tightly packed.
 int reduce_validate(int in_w, int in_h, int channels, int fx, int fy, const int32_t* box, int rb[4]);
 hipError_t reduce_launch(const uint8_t* in, uint8_t* out, int in_w, int channels, int fx, int fy, const int rb[4], int frames,
-                         size_t in_fs, size_t out_fs, hipStream_t stream);
+                         size_t in_fs, size_t out_fs, RsIssue& is);
 int reduce_device(ResizeState* st, int in_w, int in_h, int channels, int fx, int fy, const int32_t* box, const void* d_in,
                   void* d_out, int frames, size_t in_frame_stride, size_t out_frame_stride, hipStream_t stream, int* last_hip);
 int reduce_host(ResizeState* st, int in_w, int in_h, int channels, int fx, int fy, const int32_t* box, const void* in,
                 void* out, int frames, hipStream_t stream, int* last_hip);
 
-// One request for the fused kernel, k_rs_fused<RsSample<BPS>, C, K, ALPHA, TENSOR> (lanczos_resize_fused.hpp): the instance
+// One request for the fused kernel, k_rs_fused<RsSample<BPS>, C, K, ALPHA, FLAGS> (lanczos_resize_fused.hpp): the instance
 // is that of d's channels and alpha flag and of the plan's K.  Frame strides in bytes.  The kernel gets the tables from the
 // window's first outputs on and the window's extent as its output size; the plan is that of the window.
 struct RsFusedLaunch {
@@ -396,18 +409,19 @@ struct RsFusedLaunch {
     uint8_t* out;
     size_t in_fs, out_fs;
     int frames;
-    const RsTensorCall* tc;   // TENSOR: `out` / `out_fs` are the element frames
-    hipStream_t stream;
+    const RsTensorCall* tc;   // a tensor request: `out` / `out_fs` are the element frames
+    RsIssue& is;             // the stream, and the count the launches add to
     const RsSource* src = nullptr;   // NULL: packed interleaved rows.  A planar one runs the kRsPlanar instances
     const RsDest* dst = nullptr;     // NULL: packed output rows; else rows row_stride bytes apart.  A planar one runs the
                                      // kRsPlanarOut instances
 };
-// TENSOR: bytes of a stored table element, 0 where the samples themselves are stored; + kRsMapped: through the channel map and
-// the flips of the request (RsTensorOut::mapped)
+// FLAGS of an instance.  Its low bits (kRsElemMask): bytes of a stored table element, 2 or 4; 0 where the samples themselves
+// are stored.  + kRsMapped: through the channel map and the flips of the request (RsTensorOut::mapped)
+constexpr int kRsElemMask = 7;
 constexpr int kRsMapped = 8;
 // + kRsCrops: a window origin per frame, read when the kernel runs (RsTensorCall::d_origin); the tables are the full axes'
 constexpr int kRsCrops = 16;
-// + kRsPlanar: the source is planar (RsSource::planar), staged through a byte transpose; with bytes out TENSOR is kRsPlanar alone
+// + kRsPlanar: the source is planar (RsSource::planar), staged through a byte transpose; with bytes out FLAGS is kRsPlanar alone
 constexpr int kRsPlanar = 32;
 // + kRsRowShift: LANCZOS_RESIZE_ALPHA over pitched interleaved rows whose pitch is no dword multiple: the staging shifts by the
 // residue of each row.  As for kRsPlanar, bytes out is the flag alone and a tensor request runs the mapped instance
@@ -416,18 +430,44 @@ constexpr int kRsRowShift = 64;
 constexpr int kRsPlanarOut = 128;
 // kRsNorm alone: wide samples (BPS 2 or 4) into computed elements, lanczos_tensor_norm; the element format is an argument
 constexpr int kRsNorm = 256;
-template <int BPS, int TENSOR>
+// The instances of rs_launch_fused<BPS, FLAGS> (each with its k_rs_fused kernels for every channel count, tap bucket and ALPHA),
+// X(index, BPS, FLAGS).  This is the one list: the declarations, the cases of rs_launch_fused_any and rs_fused_instance_exists
+// come from it, and lanczos_resize_fused_inst.hip is compiled once per index (-DLZ_RS_INST=<index>, the Makefile's RS_INSTS) into
+// the instance of that entry and nothing else.  A new instance is a line here and one more index there.
+//    0      8-bit, bytes out                          1, 2    8-bit into float / 16-bit elements through a table
+//    3, 4   ... through a channel map and flips       5, 6    ... with a crop origin per frame
+//    7..9   8-bit from a planar source: bytes, floats, 16-bit elements
+//   10..12  ALPHA over rows pitched off a dword: the same three
+//   13, 14  8-bit into a planar destination, from an interleaved and from a planar source
+//   15, 16  16-bit and float samples                 17, 18   ... into computed elements (lanczos_tensor_norm)
+#define LZ_RS_FUSED_INSTANCES(X)                                                             \
+    X(0, 1, 0) X(1, 1, 4) X(2, 1, 2) X(3, 1, 4 + kRsMapped) X(4, 1, 2 + kRsMapped)           \
+    X(5, 1, 4 + kRsMapped + kRsCrops) X(6, 1, 2 + kRsMapped + kRsCrops)                      \
+    X(7, 1, kRsPlanar) X(8, 1, 4 + kRsMapped + kRsPlanar) X(9, 1, 2 + kRsMapped + kRsPlanar) \
+    X(10, 1, kRsRowShift) X(11, 1, 4 + kRsMapped + kRsRowShift) X(12, 1, 2 + kRsMapped + kRsRowShift) \
+    X(13, 1, kRsPlanarOut) X(14, 1, kRsPlanar + kRsPlanarOut)                                \
+    X(15, 2, 0) X(16, 4, 0) X(17, 2, kRsNorm) X(18, 4, kRsNorm)
+#define X(I, BPS, FLAGS) +1
+constexpr int kRsFusedInstances = 0 LZ_RS_FUSED_INSTANCES(X);
+#undef X
+// whether rs_launch_fused<bps, flags> is one of them: what a route's (bps, flags) has to satisfy
+constexpr bool rs_fused_instance_exists(int bps, int flags) {
+#define X(I, BPS, FLAGS) || (bps == (BPS) && flags == (FLAGS))
+    return false LZ_RS_FUSED_INSTANCES(X);
+#undef X
+}
+template <int BPS, int FLAGS>
 hipError_t rs_launch_fused(const RsFusedLaunch& c);
 
 // LANCZOS_FILTER_NEAREST (lanczos_resize_nearest.hip): out[y][x] = in[vidx[y]][hidx[x]] for pixels of `channels` samples of
 // `bps` bytes (1 or 4), one launch.  hidx / vidx are device tables of out_w / out_h source indices, all inside the source.
 hipError_t rs_nearest_launch(const uint8_t* in, uint8_t* out, int in_w, int out_w, int out_h, int channels, int bps,
                              const int32_t* hidx, const int32_t* vidx, int frames, size_t in_fs, size_t out_fs,
-                             hipStream_t stream);
+                             RsIssue& is);
 // The crop of a resize that changes neither axis (k_rs_crop, beside the gather): `rows` rows of `row_bytes` bytes from `in`
 // (the window's first byte; rows in_pitch bytes apart) to tightly packed rows at `out`, every frame in one launch.
 hipError_t rs_crop_launch(const uint8_t* in, uint8_t* out, size_t in_pitch, size_t row_bytes, int rows, int frames,
-                          size_t in_fs, size_t out_fs, hipStream_t stream);
+                          size_t in_fs, size_t out_fs, RsIssue& is);
 
 // ---- YCbCr frames (lanczos_resize_ycc.hip): three one-channel requests through resize_device, a split in front of interleaved
 // chroma and the merge through the colour table behind them.  A lanczos_ycc_source resolved by ycc_source_resolve:
@@ -486,7 +526,7 @@ int ycc_dest_resolve(const RsWindow& w, const lanczos_ycc_dest* dst, bool aligne
 bool ycc_table_forward(int standard, int32_t* t);
 // k_rs_ycc_split: shared with the composition above
 hipError_t ycc_split_launch(const uint8_t* in, size_t in_fs, const YccSource& s, uint8_t* out, size_t plane_bytes, int frames,
-                            hipStream_t stream);
+                            RsIssue& is);
 // One call of lanczos_resize_ycc_out, filled in by lanczos_api.hip
 struct YccOutRequest {
     const lanczos_resize_desc* d = nullptr;       // validated (ycc_desc_validate)

@@ -1,15 +1,10 @@
 // lanczos_resize_dest.hip -- a destination layout beside the descriptor (lanczos_resize_dest, include/lanczos_hip.h): planar
-// (CHW) and row-pitched result frames without a repack by the caller.  Here: the planar-out instances of
-// the fused kernel over an interleaved source (the kernel is lanczos_resize_fused.hpp's and only its epilogue differs), and
-// k_rs_unpack_dest, the streaming scatter of the UNPACKED route.  Pitched interleaved rows need no kernel code (RsFused::out_pitch);
+// (CHW) and row-pitched result frames without a repack by the caller.  Here: k_rs_unpack_dest, the streaming scatter of the
+// UNPACKED route (planes stored DIRECT are the kRsPlanarOut instances of the fused kernel, whose epilogue alone differs).  Pitched interleaved rows need no kernel code (RsFused::out_pitch);
 // the layout is validated and the routes are chosen in lanczos_resize_route.cpp (resize_dest_resolve, rs_route).
 #include "lanczos_resize_fused.hpp"
 
 namespace lz {
-
-// the instances of the fused kernel that store planes from an interleaved source (k_rs_fused<RsSample<1>, C, K, ALPHA,
-// kRsPlanarOut> for every tap-count bucket x C = 3, 4 and alpha); those of a planar source are lanczos_resize_dest_source.hip's
-template hipError_t rs_launch_fused<1, kRsPlanarOut>(const RsFusedLaunch&);
 
 // ---- k_rs_unpack_dest --------------------------------------------------------------------------------------------------
 //
@@ -67,25 +62,19 @@ __global__ __launch_bounds__(256) void k_rs_unpack_dest_rows(RsUnpack p) {
 }
 
 hipError_t rs_unpack_dest_launch(const uint8_t* in, size_t in_fs, uint8_t* out, size_t out_fs, const RsDest& s, int w, int h,
-                                 int C, int B, int frames, hipStream_t stream) {
+                                 int C, int B, int frames, RsIssue& is) {
     RsUnpack p{};
     p.in_fs = in_fs, p.out_fs = out_fs, p.row_stride = s.row_stride, p.chan_stride = s.chan_stride;
     p.w = (unsigned)w, p.row_bytes = (unsigned)(w * C * B);
     if (s.planar && (B != 1 || (C != 3 && C != 4))) return hipErrorInvalidValue;
     const unsigned groups = ((s.planar ? p.w : p.row_bytes) + 3) / 4;
     p.h = (unsigned)h, p.runs = (groups + 63) / 64;   // h * runs < 2^16 * 2^13
-    for (int f0 = 0; f0 < frames; f0 += 65535) {
-        const int nf = std::min(65535, frames - f0);
+    void (*const kern)(RsUnpack) = !s.planar ? k_rs_unpack_dest_rows : C == 3 ? k_rs_unpack_dest<3> : k_rs_unpack_dest<4>;
+    return rs_for_frame_groups(is, frames, [&](int f0, int nf) {
         p.in = in + (size_t)f0 * in_fs;
         p.out = out + (size_t)f0 * out_fs;
-        const dim3 grid((p.h * p.runs + 3) / 4, nf);
-        if (!s.planar) hipLaunchKernelGGL(k_rs_unpack_dest_rows, grid, dim3(256), 0, stream, p);
-        else if (C == 3) hipLaunchKernelGGL(k_rs_unpack_dest<3>, grid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL(k_rs_unpack_dest<4>, grid, dim3(256), 0, stream, p);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        hipLaunchKernelGGL(kern, dim3((p.h * p.runs + 3) / 4, nf), dim3(256), 0, is.stream, p);
+    });
 }
 
 }  // namespace lz

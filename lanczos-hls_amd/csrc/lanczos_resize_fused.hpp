@@ -4,18 +4,8 @@
 //   RsSample<BPS>   what a sample width brings: its types, Pillow's multiply-add and store.  These are the specification of
 //                   the bytes; everything below only moves samples around.
 //   k_rs_pass_h/_v  the two-pass kernels, one thread per output sample (instantiated in lanczos_resize.hip).
-//   k_rs_fused      the fused kernel, and rs_launch_fused, which fills its arguments and picks the instance.  Seven
-//                   translation units instantiate them side by side: lanczos_resize.hip (8-bit, bytes out),
-//                   lanczos_resize_tensor.hip (8-bit, floats out through a table: TENSOR = 4), lanczos_resize_tensor16.hip
-//                   (8-bit, 16-bit elements out through a table: TENSOR = 2), lanczos_resize_tensor_view.hip and
-//                   lanczos_resize_tensor16_view.hip (the same two through a channel map and flips: TENSOR + kRsMapped),
-//                   lanczos_resize_tensor_crops.hip and lanczos_resize_tensor16_crops.hip (those with a crop origin per frame:
-//                   TENSOR + kRsMapped + kRsCrops), lanczos_resize_source.hip, lanczos_resize_source_tensor.hip and
-//                   lanczos_resize_source_tensor16.hip (8-bit from a planar source: TENSOR with kRsPlanar, and ALPHA over rows
-//                   pitched off a dword: with kRsRowShift), lanczos_resize_dest.hip and lanczos_resize_dest_source.hip (8-bit
-//                   into a planar destination: kRsPlanarOut, the second with kRsPlanar), lanczos_resize16.hip and
-//                   lanczos_resize32.hip, lanczos_resize_tensor_norm16.hip and lanczos_resize_tensor_norm32.hip (16-bit and float
-//                   samples into computed elements: kRsNorm).
+//   k_rs_fused      the fused kernel, and rs_launch_fused, which fills its arguments and picks the instance.  The instances
+//                   are those of LZ_RS_FUSED_INSTANCES (lanczos_resize.hpp), which also says which unit compiles them.
 #pragma once
 #include "lanczos_alpha.hpp"
 #include "lanczos_resize.hpp"
@@ -185,9 +175,9 @@ struct RsFused {
     int strips, rows_per_chunk;   // grid.x = strips * chunks, grid.y = frames
     int ring_rows, stage_rows, stage_dw;
 };
-// TENSOR instances: `out` / `out_fs` of RsFused are the element frames and their stride in bytes
+// tensor instances: `out` / `out_fs` of RsFused are the element frames and their stride in bytes
 struct RsFusedTensor : RsFused<int32_t> {
-    const uint32_t* lut;     // [C][256] words of TENSOR bytes each, read when the kernel runs
+    const uint32_t* lut;     // [C][256] words of EB bytes each, read when the kernel runs
     int cs, rs, ps;          // channel, row and pixel strides in elements
     unsigned extent_bytes;   // of one element frame, below 2^31
 };
@@ -229,19 +219,19 @@ struct RsFusedPlanarOut : Base {
     int out_chan_stride;   // bytes between the planes of a frame
     unsigned dst_bytes;    // from the frame's first byte to the last one the layout names + 1, below 2^31
 };
-// the argument of k_rs_fused<..., TENSOR> for coefficients KT
-template <int TENSOR, class KT>
+// the argument of k_rs_fused<..., FLAGS> for coefficients KT
+template <int FLAGS, class KT>
 using RsFusedArgsPacked = std::conditional_t<
-    (TENSOR & kRsNorm) != 0, RsFusedNorm<KT>,
+    (FLAGS & kRsNorm) != 0, RsFusedNorm<KT>,
     std::conditional_t<
-    (TENSOR & kRsCrops) != 0, RsFusedTensorCrops,
-    std::conditional_t<(TENSOR & kRsMapped) != 0, RsFusedTensorMap, std::conditional_t<TENSOR != 0, RsFusedTensor, RsFused<KT>>>>>;
-template <int TENSOR, class KT>
-using RsFusedArgsIn = std::conditional_t<(TENSOR & kRsPlanar) != 0, RsFusedPlanar<RsFusedArgsPacked<(TENSOR & ~kRsPlanar), KT>>,
-                                         RsFusedArgsPacked<(TENSOR & ~kRsRowShift), KT>>;
-template <int TENSOR, class KT>
-using RsFusedArgs = std::conditional_t<(TENSOR & kRsPlanarOut) != 0, RsFusedPlanarOut<RsFusedArgsIn<(TENSOR & ~kRsPlanarOut), KT>>,
-                                       RsFusedArgsIn<TENSOR, KT>>;
+    (FLAGS & kRsCrops) != 0, RsFusedTensorCrops,
+    std::conditional_t<(FLAGS & kRsMapped) != 0, RsFusedTensorMap, std::conditional_t<FLAGS != 0, RsFusedTensor, RsFused<KT>>>>>;
+template <int FLAGS, class KT>
+using RsFusedArgsIn = std::conditional_t<(FLAGS & kRsPlanar) != 0, RsFusedPlanar<RsFusedArgsPacked<(FLAGS & ~kRsPlanar), KT>>,
+                                         RsFusedArgsPacked<(FLAGS & ~kRsRowShift), KT>>;
+template <int FLAGS, class KT>
+using RsFusedArgs = std::conditional_t<(FLAGS & kRsPlanarOut) != 0, RsFusedPlanarOut<RsFusedArgsIn<(FLAGS & ~kRsPlanarOut), KT>>,
+                                       RsFusedArgsIn<FLAGS, KT>>;
 
 // The byte transpose of the planar staging and of k_rs_pack_source: p[c] holds bytes x .. x + 3 of plane c, o[] the C dwords of
 // those four pixels interleaved.  v_perm_b32 picks byte sel[k] of the eight bytes {a : b} (b the low four) for result byte k
@@ -335,34 +325,34 @@ struct RsStrip {
 // that the staged dwords are pixels: a frame base that is no dword multiple (every row then starts `delta` bytes into a
 // dword, the row pitch being one) is shifted out while staging, and the horizontal pass reads its window unshifted.
 //
-// TENSOR (lanczos_tensor_out, 8-bit): the vertical pass stores lut[c][byte] as a float at c * cs + y * rs + x * ps of the float
+// A table element (FLAGS & kRsElemMask; lanczos_tensor_out, 8-bit): the vertical pass stores lut[c][byte] as a float at c * cs + y * rs + x * ps of the float
 // frame instead of the byte.  A lane holds four consecutive samples of the interleaved row, so a store of them as they lie would
 // put 16 bytes between neighbouring lanes; the wave's 64 dwords are exchanged instead (four ds_bpermute) so that in round r
 // lane i has sample 64 r + i of the wave's 256: neighbouring lanes store neighbouring samples, whole 256-byte runs where the
 // layout is interleaved or has one channel, runs of every C-th lane per plane where it is planar.  The table is read from
 // global memory through the vector cache (1 to 4 KiB, resident after the first rows): LDS and the plan stay the byte kernel's.
-// TENSOR is the width of the stored element in bytes: 4 (floats, lanczos_tensor_out), 2 (bfloat16 or float16 words,
+// Those bits are the width of the stored element in bytes: 4 (floats, lanczos_tensor_out), 2 (bfloat16 or float16 words,
 // lanczos_tensor16_out: the table is of 16-bit words and the store a 16-bit one, everything else the same), 0: bytes out.
 //
-// TENSOR + kRsMapped (lanczos_tensor_view with a channel map or flips; instances of their own, the ones above are as they
+// + kRsMapped (lanczos_tensor_view with a channel map or flips; instances of their own, the ones above are as they
 // were): the lane's channel c becomes dst[c], four byte fields of one scalar, and a channel no output names stores nothing.  A
 // flip negates a stride and moves the base to the matching corner of the frame -- both computed once per workgroup from one
 // uniform byte load -- so every offset stays inside [0, extent) and the buffer resource is the same.
 //
-// TENSOR + kRsMapped + kRsCrops (lanczos_resize_crops; instances of their own again): out_w x out_h is the crop every frame
+// + kRsMapped + kRsCrops (lanczos_resize_crops; instances of their own again): out_w x out_h is the crop every frame
 // stores and the tables are the full axes'.  A workgroup loads its frame's origin with two uniform loads, clamps it so that the
 // crop lies inside the full output -- device memory cannot be validated, and the tables end there -- and moves its six table
 // pointers by it: from there on it is the kernel of the window at that origin.  The plan is the largest over every origin
 // (rs_fused_plan_crops), so staging rows and ring hold whichever the frame has.
 //
-// TENSOR = kRsNorm (lanczos_tensor_norm, 16-bit and float samples; instances of their own, lanczos_resize_tensor_norm16/32.hip,
+// FLAGS = kRsNorm (lanczos_tensor_norm, 16-bit and float samples; instances of their own,
 // the wide instances that store samples are as they were): only the epilogue differs.  After the vertical chain a lane holds
 // SPD sums of consecutive samples of the strip's row; each is turned into the sample Pillow stores (S::store), then into the
 // element by three float operations and a rounding (rs_norm_elem), and stored at oc * cs + y * rs + x * ps through the channel
 // map and the flips, which every instance has (the identity view runs the identity map).  The element format is a launch
 // argument, uniform over the wave, not a template parameter: one instance per (width, C, K) and a third of the build.
 //
-// TENSOR with kRsPlanar (a planar source, 8-bit, C = 3 or 4; instances of their own once more, lanczos_resize_source*.hip): only
+// FLAGS with kRsPlanar (a planar source, 8-bit, C = 3 or 4; instances of their own once more): only
 // the staging loads differ.  A thread takes four pixels of a staged row: one dword from each of the C plane rows, transposed into
 // C interleaved dwords (rs_interleave4) and written to LDS as dwords.  A plane row starts at any byte, another residue per plane
 // and per row where the strides are odd, so each of those dwords is put together from the two aligned ones around it
@@ -371,10 +361,10 @@ struct RsStrip {
 // Loads go through a buffer resource over [frame base rounded down to a dword, last named byte rounded up to one): nothing
 // outside it is read, and whatever lies in the padding of a row is only ever multiplied by a zero coefficient.
 //
-// TENSOR with kRsRowShift (ALPHA over interleaved rows whose pitch is no dword multiple; instances beside the planar ones): the
+// FLAGS with kRsRowShift (ALPHA over interleaved rows whose pitch is no dword multiple; instances beside the planar ones): the
 // ALPHA staging shifts every pixel by the residue of its own row instead of the frame's.
 //
-// TENSOR with kRsPlanarOut (a planar destination, bytes out, 8-bit, C = 3 or 4; instances of their own, lanczos_resize_dest*.hip):
+// FLAGS with kRsPlanarOut (a planar destination, bytes out, 8-bit, C = 3 or 4; instances of their own):
 // only the epilogue differs.  The wave's 64 dwords are exchanged as the tensor epilogue exchanges them, so that in round r lane i
 // has sample 64 r + i of the wave's 256, and every sample goes out as one byte store to c * chan_stride + y * row_stride + x of
 // the frame: every C-th lane continues one plane row, and only bytes the layout names are ever stored.  The other form, one
@@ -382,16 +372,16 @@ struct RsStrip {
 // ONE plane (C = 4: within the quad; C = 3: the row goes out in four slots of 16 groups, 48 lanes each), and rs_store_segment
 // stores it -- dwords at dword-aligned addresses only, realigned with the neighbouring group's dword where the plane row
 // starts off one, bytes at the ends of the strip's segment.  It measured slower than the byte stores on every workload.
-template <class S, int C, int K, bool ALPHA = false, int TENSOR = 0>
+template <class S, int C, int K, bool ALPHA = false, int FLAGS = 0>
 __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
-    RsFusedArgs<TENSOR, typename S::coeff_t> g) {
-    constexpr int EB = TENSOR & ~(kRsMapped | kRsCrops | kRsPlanar | kRsRowShift | kRsPlanarOut | kRsNorm);   // bytes of a stored table element
-    constexpr bool NORM = (TENSOR & kRsNorm) != 0;   // wide samples into computed elements: its own epilogue, nothing else differs
-    static_assert(!NORM || (TENSOR == kRsNorm && S::BPS > 1), "norm: 16-bit or float samples, no other flag");
-    constexpr bool PLANAR = (TENSOR & kRsPlanar) != 0;
-    constexpr bool ROWSHIFT = (TENSOR & kRsRowShift) != 0;
-    constexpr bool PLANAR_OUT = (TENSOR & kRsPlanarOut) != 0;
-    static_assert(!PLANAR_OUT || (EB == 0 && S::BPS == 1 && C >= 3 && !ROWSHIFT && TENSOR < 2 * kRsPlanarOut),
+    RsFusedArgs<FLAGS, typename S::coeff_t> g) {
+    constexpr int EB = FLAGS & kRsElemMask;         // bytes of a stored table element
+    constexpr bool NORM = (FLAGS & kRsNorm) != 0;   // wide samples into computed elements: its own epilogue, nothing else differs
+    static_assert(!NORM || (FLAGS == kRsNorm && S::BPS > 1), "norm: 16-bit or float samples, no other flag");
+    constexpr bool PLANAR = (FLAGS & kRsPlanar) != 0;
+    constexpr bool ROWSHIFT = (FLAGS & kRsRowShift) != 0;
+    constexpr bool PLANAR_OUT = (FLAGS & kRsPlanarOut) != 0;
+    static_assert(!PLANAR_OUT || (EB == 0 && S::BPS == 1 && C >= 3 && !ROWSHIFT && FLAGS < 2 * kRsPlanarOut),
                   "planar destinations: bytes out, 3 or 4 channels");
     // The planar epilogue has two forms: the tensor epilogue's exchange with a byte store per sample, and one dword store per
     // lane (C = 4: after a transpose within the quad; C = 3: the row walked in four slots of 16 groups of four pixels, 48 lanes,
@@ -403,12 +393,12 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
     constexpr bool kPlanarOutBytes = true;
 #endif
     constexpr bool kSlots = PLANAR_OUT && C == 3 && !kPlanarOutBytes;
-    static_assert(!ROWSHIFT || (ALPHA && !PLANAR && !(TENSOR & kRsCrops)), "a shift per row: the ALPHA staging of pitched rows");
-    static_assert(!PLANAR || (S::BPS == 1 && C >= 3 && !(TENSOR & kRsCrops)), "planar sources: 8-bit, 3 or 4 channels, no crops");
+    static_assert(!ROWSHIFT || (ALPHA && !PLANAR && !(FLAGS & kRsCrops)), "a shift per row: the ALPHA staging of pitched rows");
+    static_assert(!PLANAR || (S::BPS == 1 && C >= 3 && !(FLAGS & kRsCrops)), "planar sources: 8-bit, 3 or 4 channels, no crops");
     constexpr bool kPixelStage = ALPHA || PLANAR;         // a staged row starts at the strip's first pixel, whatever the address
     constexpr bool kNoShift = kPixelStage && C == 4;      // ... and a staged dword is a pixel: the horizontal pass shifts nothing
-    constexpr bool MAPPED = (TENSOR & kRsMapped) != 0;
-    constexpr bool CROPS = (TENSOR & kRsCrops) != 0;
+    constexpr bool MAPPED = (FLAGS & kRsMapped) != 0;
+    constexpr bool CROPS = (FLAGS & kRsCrops) != 0;
     static_assert((EB == 0 && !MAPPED) || EB == 2 || EB == 4, "bytes, 16-bit elements or floats out");
     static_assert(!CROPS || MAPPED, "a crop origin per frame comes with the mapped epilogue");
     static_assert(!ALPHA || C == 4, "alpha is the fourth of four channels");
@@ -624,7 +614,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_fused(
             int slot = f % g.ring_rows;
             // SPD of the four sums are used.  Named sums and the packing below written out per width, not an array and
             // loops over it: from those the compiler orders the sums' registers otherwise, and for 8-bit it then packs with
-            // the v_ashr_pk_u8_i32 that the TENSOR branch speaks of.  With the array, and the 8-bit pack kept from that
+            // the v_ashr_pk_u8_i32 that the table-element branch speaks of.  With the array, and the 8-bit pack kept from that
             // instruction by hand, every instance had the same registers and occupancy but another schedule, and the 4K
             // workloads measured 0.25 to 0.5 % slower (8-bit and float, three channels, halving and doubling)
             [[maybe_unused]] acc_t a0 = S::kAcc0, a1 = a0, a2 = a0, a3 = a0;
@@ -787,16 +777,16 @@ void rs_fill_fused(RsFused<KT>* g, const RsFusedLaunch& c) {
     g->ring_rows = c.fp->ring_rows, g->stage_rows = c.fp->stage_rows, g->stage_dw = c.fp->stage_dw;
 }
 
-template <int BPS, int TENSOR>
+template <int BPS, int FLAGS>
 hipError_t rs_launch_fused(const RsFusedLaunch& c) {
     using S = RsSample<BPS>;
     const bool alpha = (c.d->reserved[0] & LANCZOS_RESIZE_ALPHA) != 0;
     const RsFusedPlan& fp = *c.fp;
-    constexpr bool PLANAR = (TENSOR & kRsPlanar) != 0;
-    RsFusedArgs<TENSOR, typename S::coeff_t> g{};
+    constexpr bool PLANAR = (FLAGS & kRsPlanar) != 0;
+    RsFusedArgs<FLAGS, typename S::coeff_t> g{};
     rs_fill_fused(&g, c);
-    constexpr bool ROWSHIFT = (TENSOR & kRsRowShift) != 0;
-    constexpr bool PLANAR_OUT = (TENSOR & kRsPlanarOut) != 0;
+    constexpr bool ROWSHIFT = (FLAGS & kRsRowShift) != 0;
+    constexpr bool PLANAR_OUT = (FLAGS & kRsPlanarOut) != 0;
     if ((c.src && c.src->planar) != PLANAR) return hipErrorInvalidValue;
     if ((c.dst && c.dst->planar) != PLANAR_OUT) return hipErrorInvalidValue;
     if constexpr (PLANAR_OUT) g.out_chan_stride = (int)c.dst->chan_stride, g.dst_bytes = (unsigned)c.dst->named;
@@ -804,7 +794,7 @@ hipError_t rs_launch_fused(const RsFusedLaunch& c) {
         g.chan_stride = (int)c.src->chan_stride;
         g.src_bytes = (unsigned)((c.d->channels - 1) * c.src->chan_stride + (c.d->in_h - 1) * c.src->row_stride + c.d->in_w);
     }
-    constexpr bool NORM = (TENSOR & kRsNorm) != 0;
+    constexpr bool NORM = (FLAGS & kRsNorm) != 0;
     if constexpr (NORM) {
         const RsTensorOut& t = c.tc->t;
         g.cs = (int)t.chan_stride, g.rs = (int)t.row_stride, g.ps = (int)t.pix_stride;   // extent below 2^31 bytes
@@ -815,55 +805,32 @@ hipError_t rs_launch_fused(const RsFusedLaunch& c) {
             g.div[sc] = t.div[oc], g.mean[sc] = t.mean[oc], g.std[sc] = t.std[oc];
         }
     }
-    if constexpr ((TENSOR & ~(kRsPlanar | kRsRowShift | kRsPlanarOut | kRsNorm)) != 0) {
+    if constexpr ((FLAGS & kRsElemMask) != 0) {
         g.lut = (const uint32_t*)c.tc->t.d_lut;
         g.cs = (int)c.tc->t.chan_stride, g.rs = (int)c.tc->t.row_stride, g.ps = (int)c.tc->t.pix_stride;   // extent below 2^31 bytes
         g.extent_bytes = (unsigned)c.tc->extent_bytes;
     }
-    if constexpr ((TENSOR & kRsMapped) != 0) g.dst = c.tc->t.dst_of_src(), g.flip = c.tc->t.flip & 3;
-    if constexpr ((TENSOR & kRsCrops) != 0) g.max_x0 = c.d->out_w - c.win.w, g.max_y0 = c.d->out_h - c.win.h;
-    for (int f0 = 0; f0 < c.frames; f0 += 65535) {
-        const int nf = std::min(65535, c.frames - f0);
+    if constexpr ((FLAGS & kRsMapped) != 0) g.dst = c.tc->t.dst_of_src(), g.flip = c.tc->t.flip & 3;
+    if constexpr ((FLAGS & kRsCrops) != 0) g.max_x0 = c.d->out_w - c.win.w, g.max_y0 = c.d->out_h - c.win.h;
+    void (*kern)(decltype(g)) = nullptr;
+    rs_dispatch_instance(c.d->channels, fp.K, alpha, [&](auto ch, auto k, auto a) {
+        // alpha is 8-bit only (resize_validate); a planar source of one channel is the interleaved one
+        if constexpr ((!decltype(a)::value || BPS == 1) && (!(PLANAR || PLANAR_OUT) || decltype(ch)::value >= 3) &&
+                      (!ROWSHIFT || decltype(a)::value))
+            kern = k_rs_fused<S, decltype(ch)::value, decltype(k)::value, decltype(a)::value, FLAGS>;
+    });
+    if (!kern) return c.frames > 0 ? hipErrorInvalidValue : hipSuccess;   // no frame, no launch to miss
+    return rs_for_frame_groups(c.is, c.frames, [&](int f0, int nf) {
         g.in = c.in + (size_t)f0 * c.in_fs;
         g.out = c.out + (size_t)f0 * c.out_fs;
-        if constexpr ((TENSOR & kRsMapped) != 0 || NORM) g.d_flip = c.tc->t.d_flip ? c.tc->t.d_flip + f0 : nullptr;   // a byte per frame
-        if constexpr ((TENSOR & kRsCrops) != 0) g.d_origin = c.tc->d_origin + 2 * (size_t)f0;                  // a pair per frame
-        const dim3 grid(fp.strips * fp.chunks, nf);
-        bool launched = false;
-        rs_dispatch_instance(c.d->channels, fp.K, alpha, [&](auto ch, auto k, auto a) {
-            // alpha is 8-bit only (resize_validate); a planar source of one channel is the interleaved one
-            if constexpr ((!decltype(a)::value || BPS == 1) && (!(PLANAR || PLANAR_OUT) || decltype(ch)::value >= 3) &&
-                          (!ROWSHIFT || decltype(a)::value)) {
-                hipLaunchKernelGGL((k_rs_fused<S, decltype(ch)::value, decltype(k)::value, decltype(a)::value, TENSOR>), grid,
-                                   dim3(kRsThreads), fp.lds, c.stream, g);
-                launched = true;
-            }
-        });
-        if (!launched) return hipErrorInvalidValue;
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        if constexpr ((FLAGS & kRsMapped) != 0 || NORM) g.d_flip = c.tc->t.d_flip ? c.tc->t.d_flip + f0 : nullptr;   // a byte per frame
+        if constexpr ((FLAGS & kRsCrops) != 0) g.d_origin = c.tc->d_origin + 2 * (size_t)f0;                  // a pair per frame
+        hipLaunchKernelGGL(kern, dim3(fp.strips * fp.chunks, nf), dim3(kRsThreads), fp.lds, c.is.stream, g);
+    });
 }
-// each is instantiated, with its kernels, by the translation unit named at the head of this file
-extern template hipError_t rs_launch_fused<1, 0>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<1, 4>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<1, 2>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<1, 4 + kRsMapped>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<1, 2 + kRsMapped>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<1, 4 + kRsMapped + kRsCrops>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<1, 2 + kRsMapped + kRsCrops>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<1, kRsPlanar>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<1, 4 + kRsMapped + kRsPlanar>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<1, 2 + kRsMapped + kRsPlanar>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<1, kRsRowShift>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<1, 4 + kRsMapped + kRsRowShift>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<1, 2 + kRsMapped + kRsRowShift>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<1, kRsPlanarOut>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<1, kRsPlanar + kRsPlanarOut>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<2, 0>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<4, 0>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<2, kRsNorm>(const RsFusedLaunch&);
-extern template hipError_t rs_launch_fused<4, kRsNorm>(const RsFusedLaunch&);
+// each is instantiated, with its kernels, by lanczos_resize_fused_inst.hip
+#define X(I, BPS, FLAGS) extern template hipError_t rs_launch_fused<BPS, FLAGS>(const RsFusedLaunch&);
+LZ_RS_FUSED_INSTANCES(X)
+#undef X
 
 }  // namespace lz

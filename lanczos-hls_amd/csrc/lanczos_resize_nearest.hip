@@ -74,7 +74,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_nearest(NnArgs g) {
 
 hipError_t rs_nearest_launch(const uint8_t* in, uint8_t* out, int in_w, int out_w, int out_h, int channels, int bps,
                              const int32_t* hidx, const int32_t* vidx, int frames, size_t in_fs, size_t out_fs,
-                             hipStream_t stream) {
+                             RsIssue& is) {
     NnArgs g{};
     g.in_fs = in_fs, g.out_fs = out_fs;
     g.in_pitch = (unsigned)in_w * channels * bps, g.out_pitch = (unsigned)out_w * channels * bps;
@@ -82,27 +82,15 @@ hipError_t rs_nearest_launch(const uint8_t* in, uint8_t* out, int in_w, int out_
     g.hidx = hidx, g.vidx = vidx;
     const int spd = 4 / bps;
     const int ndw = (g.n_samples + 2 * (spd - 1)) / spd;   // dwords of the address grid a row can touch, misaligned start included
-    for (int f0 = 0; f0 < frames; f0 += 65535) {
-        const int nf = std::min(65535, frames - f0);
+    void (*kern)(NnArgs);
+    if (bps == 1) kern = channels == 1 ? k_rs_nearest<1, 1> : channels == 3 ? k_rs_nearest<1, 3> : k_rs_nearest<1, 4>;
+    else if (bps == 4) kern = channels == 1 ? k_rs_nearest<4, 1> : channels == 3 ? k_rs_nearest<4, 3> : k_rs_nearest<4, 4>;
+    else return hipErrorInvalidValue;
+    return rs_for_frame_groups(is, frames, [&](int f0, int nf) {
         g.in = in + (size_t)f0 * in_fs;
         g.out = out + (size_t)f0 * out_fs;
-        const dim3 grid((ndw + kRsThreads - 1) / kRsThreads, out_h, nf);
-#define LZ_NN_LAUNCH(BB)                                                                                  \
-    if (channels == 1) hipLaunchKernelGGL((k_rs_nearest<BB, 1>), grid, dim3(kRsThreads), 0, stream, g);      \
-    else if (channels == 3) hipLaunchKernelGGL((k_rs_nearest<BB, 3>), grid, dim3(kRsThreads), 0, stream, g); \
-    else hipLaunchKernelGGL((k_rs_nearest<BB, 4>), grid, dim3(kRsThreads), 0, stream, g);
-        if (bps == 1) {
-            LZ_NN_LAUNCH(1)
-        } else if (bps == 4) {
-            LZ_NN_LAUNCH(4)
-        } else {
-            return hipErrorInvalidValue;
-        }
-#undef LZ_NN_LAUNCH
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        hipLaunchKernelGGL(kern, dim3((ndw + kRsThreads - 1) / kRsThreads, out_h, nf), dim3(kRsThreads), 0, is.stream, g);
+    });
 }
 
 struct CropArgs {
@@ -136,16 +124,19 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_crop(CropArgs g) {
 }
 
 hipError_t rs_crop_launch(const uint8_t* in, uint8_t* out, size_t in_pitch, size_t row_bytes, int rows, int frames,
-                          size_t in_fs, size_t out_fs, hipStream_t stream) {
+                          size_t in_fs, size_t out_fs, RsIssue& is) {
     CropArgs g{};
     g.in = in, g.out = out;
     g.in_fs = in_fs, g.out_fs = out_fs;
     g.in_pitch = in_pitch, g.out_pitch = row_bytes;
     g.row_bytes = (int)row_bytes, g.frames = frames;
     const int ndw = ((int)row_bytes + 6) / 4;   // dwords of the address grid a row can touch, a misaligned start included
-    const dim3 grid((ndw + kRsThreads - 1) / kRsThreads, rows, std::min(frames, 65535));
-    hipLaunchKernelGGL(k_rs_crop, grid, dim3(kRsThreads), 0, stream, g);
-    return hipGetLastError();
+    // one launch whatever the batch: the kernel strides over the frames with gridDim.z
+    const dim3 grid((ndw + kRsThreads - 1) / kRsThreads, rows, std::min(frames, kRsMaxGridFrames));
+    hipLaunchKernelGGL(k_rs_crop, grid, dim3(kRsThreads), 0, is.stream, g);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) is.launches++;
+    return e;
 }
 
 }  // namespace lz

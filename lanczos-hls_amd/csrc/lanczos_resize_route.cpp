@@ -8,6 +8,7 @@
 #include "lanczos_env.hpp"
 
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstring>
 
@@ -613,6 +614,7 @@ RsRoute rs_route(const RsRouteQuery& q) {
                    : t_fused && q.mapped     ? tm
                                              : t;
         rt.bps = rt.flags && rt.flags != kRsNorm ? 1 : (int)B;   // every instance with another flag is an 8-bit one
+        assert(rs_fused_instance_exists(rt.bps, rt.flags));     // an entry of LZ_RS_FUSED_INSTANCES, not rs_launch_fused_any's default
     } else if (nearest) {
         rt.main = kRsMainNearest, rt.kernel = LANCZOS_KERNEL_RESIZE_NEAREST;
     } else if (!need_h && !need_v) {   // Pillow returns a copy (also of RGBA: no premultiply round trip); a window crops it

@@ -1,17 +1,10 @@
 // lanczos_resize_source.hip -- a source layout beside the descriptor (lanczos_resize_source, include/lanczos_hip.h): planar
-// (CHW) and row-pitched frames without a repack.  Here: the planar instances of the fused kernel that
-// store bytes (k_rs_fused<RsSample<1>, C, K, ALPHA, kRsPlanar> for every tap-count bucket x C = 3, 4 and alpha; the kernel is
-// lanczos_resize_fused.hpp's and only its staging loads differ), and k_rs_pack_source, the streaming gather of the PACKED
-// route.  The planar instances that store tensor elements are lanczos_resize_source_tensor.hip's and
-// lanczos_resize_source_tensor16.hip's; the layout is validated and the routes are chosen in
-// lanczos_resize_route.cpp (resize_source_resolve, rs_route).
+// (CHW) and row-pitched frames without a repack.  Here: k_rs_pack_source, the streaming gather of the PACKED route (planes read
+// DIRECT are the kRsPlanar instances of the fused kernel, whose staging loads alone differ).  The layout is validated and the
+// routes are chosen in lanczos_resize_route.cpp (resize_source_resolve, rs_route).
 #include "lanczos_resize_fused.hpp"
 
 namespace lz {
-
-template hipError_t rs_launch_fused<1, kRsPlanar>(const RsFusedLaunch&);
-// ... and the ALPHA instances of pitched interleaved rows whose pitch is no dword multiple (kRsRowShift)
-template hipError_t rs_launch_fused<1, kRsRowShift>(const RsFusedLaunch&);
 
 // ---- k_rs_pack_source ------------------------------------------------------------------------------------------------
 //
@@ -90,7 +83,7 @@ __global__ __launch_bounds__(256) void k_rs_pack_source_rows(RsPack p) {
 }
 
 hipError_t rs_pack_source_launch(const uint8_t* in, size_t in_fs, const RsSource& s, uint8_t* out, size_t out_fs, int w, int h,
-                                 int C, int B, int frames, hipStream_t stream) {
+                                 int C, int B, int frames, RsIssue& is) {
     RsPack p{};
     p.in_fs = in_fs, p.out_fs = out_fs, p.row_stride = s.row_stride, p.chan_stride = s.chan_stride;
     p.w = (unsigned)w, p.row_bytes = (unsigned)(w * C * B);
@@ -98,18 +91,12 @@ hipError_t rs_pack_source_launch(const uint8_t* in, size_t in_fs, const RsSource
     p.npix = (unsigned)w * (unsigned)h;
     if (s.planar && (B != 1 || (C != 3 && C != 4))) return hipErrorInvalidValue;
     const unsigned long long threads = s.planar ? ((unsigned long long)p.npix + 3) / 4 : (p.frame_bytes + 3) / 4;
-    for (int f0 = 0; f0 < frames; f0 += 65535) {
-        const int nf = std::min(65535, frames - f0);
+    void (*const kern)(RsPack) = !s.planar ? k_rs_pack_source_rows : C == 3 ? k_rs_pack_source<3> : k_rs_pack_source<4>;
+    return rs_for_frame_groups(is, frames, [&](int f0, int nf) {
         p.in = in + (size_t)f0 * in_fs;
         p.out = out + (size_t)f0 * out_fs;
-        const dim3 grid((unsigned)((threads + 255) / 256), nf);
-        if (!s.planar) hipLaunchKernelGGL(k_rs_pack_source_rows, grid, dim3(256), 0, stream, p);
-        else if (C == 3) hipLaunchKernelGGL(k_rs_pack_source<3>, grid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL(k_rs_pack_source<4>, grid, dim3(256), 0, stream, p);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        hipLaunchKernelGGL(kern, dim3((unsigned)((threads + 255) / 256), nf), dim3(256), 0, is.stream, p);
+    });
 }
 
 }  // namespace lz

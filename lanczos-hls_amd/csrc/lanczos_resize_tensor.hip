@@ -2,12 +2,9 @@
 // lanczos_tensor_out, lanczos_tensor16_out and lanczos_tensor_view): out[c * cs + y * rs + x * ps] =
 // lut[c][P(y, x, c)], P the byte lanczos_resize_device_ex stores; a view also maps the channels and mirrors frames.  The table entries are moved as 32-bit or 16-bit words, never computed on.  Two kernels:
 //
-//   fused      the TENSOR instances of k_rs_fused (lanczos_resize_fused.hpp): the vertical pass stores the elements itself.  A
-//              tensor request runs them exactly where the byte request runs the fused kernel, on the same plan.  Those that
-//              store floats are instantiated here, those that store 16-bit elements in lanczos_resize_tensor16.hip, those of
-//              a view with a map or flips in lanczos_resize_tensor_view.hip and lanczos_resize_tensor16_view.hip, those of a
-//              request with a crop origin per frame in lanczos_resize_tensor_crops.hip and lanczos_resize_tensor16_crops.hip
-//              (with their converter, k_rs_to_tensor_crops).
+//   fused      the tensor instances of k_rs_fused (lanczos_resize_fused.hpp): the vertical pass stores the elements itself.  A
+//              tensor request runs them exactly where the byte request runs the fused kernel, on the same plan.  (The converter
+//              of a request with a crop origin per frame, k_rs_to_tensor_crops, is in lanczos_resize_tensor_crops.hip.)
 //   converted  k_rs_to_tensor behind any other resize (two passes, one pass, nearest, the plain copy, an element frame of 2^31
 //              bytes or more): the bytes go to context scratch, tightly packed, and one streaming launch turns them into
 //              elements (k_rs_to_tensor<C, uint16_t> is the k_rs_to_tensor16 of the documents; k_rs_to_tensor_map is the
@@ -167,7 +164,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_to_tensor_map(RsToTensorMap g
 }
 
 hipError_t rs_to_tensor_launch(const uint8_t* src, size_t src_fs, uint8_t* out, size_t out_fs, int w, int h, int channels,
-                               const RsTensorOut& t, int frames, hipStream_t stream) {
+                               const RsTensorOut& t, int frames, RsIssue& is) {
     RsToTensorMap g{};
     g.src_fs = src_fs, g.out_fs = out_fs;
     g.frame_bytes = (unsigned long long)w * h * channels;
@@ -182,21 +179,14 @@ hipError_t rs_to_tensor_launch(const uint8_t* src, size_t src_fs, uint8_t* out, 
     void (*kern_map)(RsToTensorMap);
     if (t.elem == 2) kern_map = channels == 1 ? k_rs_to_tensor_map<1, uint16_t> : channels == 3 ? k_rs_to_tensor_map<3, uint16_t> : k_rs_to_tensor_map<4, uint16_t>;
     else kern_map = channels == 1 ? k_rs_to_tensor_map<1, uint32_t> : channels == 3 ? k_rs_to_tensor_map<3, uint32_t> : k_rs_to_tensor_map<4, uint32_t>;
-    for (int f0 = 0; f0 < frames; f0 += 65535) {
-        const int nf = std::min(65535, frames - f0);
+    return rs_for_frame_groups(is, frames, [&](int f0, int nf) {
         g.src = src + (size_t)f0 * src_fs;
         g.out = out + (size_t)f0 * out_fs;
         g.d_flip = t.d_flip ? t.d_flip + f0 : nullptr;   // a byte per frame
         const dim3 grid(blocks, nf);
-        if (t.mapped) hipLaunchKernelGGL(kern_map, grid, dim3(kRsThreads), 0, stream, g);
-        else hipLaunchKernelGGL(kern, grid, dim3(kRsThreads), 0, stream, static_cast<const RsToTensor&>(g));
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        if (t.mapped) hipLaunchKernelGGL(kern_map, grid, dim3(kRsThreads), 0, is.stream, g);
+        else hipLaunchKernelGGL(kern, grid, dim3(kRsThreads), 0, is.stream, static_cast<const RsToTensor&>(g));
+    });
 }
-
-// the instances of k_rs_fused that store floats: every tap-count bucket x C = 1, 3, 4 and alpha
-template hipError_t rs_launch_fused<1, 4>(const RsFusedLaunch&);
 
 }  // namespace lz

@@ -3,8 +3,7 @@
 // and clamped when the kernels run.  Two kernels:
 //
 //   fused      k_rs_fused<RsSample<1>, C, K, ALPHA, 4 + kRsMapped + kRsCrops> for every tap-count bucket x C = 1, 3, 4 and alpha
-//              (lanczos_resize_fused.hpp), instantiated here so that they compile beside the others; those that store 16-bit
-//              elements are in lanczos_resize_tensor16_crops.hip.
+//              (lanczos_resize_fused.hpp), and the same with 16-bit elements.
 //   converted  k_rs_to_tensor_crops<C, E> behind every other resize, which then computes the bytes of the whole output into
 //              context scratch -- or behind none, where the request changes neither axis: it reads the caller's frames.
 #include "lanczos_resize_fused.hpp"
@@ -70,7 +69,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_to_tensor_crops(RsToTensorCro
 
 hipError_t rs_to_tensor_crops_launch(const uint8_t* src, size_t src_fs, size_t src_pitch, int src_w, int src_h, uint8_t* out,
                                      size_t out_fs, int w, int h, int channels, const RsTensorOut& t, const int32_t* d_origin,
-                                     int frames, hipStream_t stream) {
+                                     int frames, RsIssue& is) {
     RsToTensorCrops g{};
     g.src_fs = src_fs, g.out_fs = out_fs, g.src_pitch = src_pitch;
     g.w = w, g.h = h, g.max_x0 = src_w - w, g.max_y0 = src_h - h;
@@ -83,21 +82,13 @@ hipError_t rs_to_tensor_crops_launch(const uint8_t* src, size_t src_fs, size_t s
         kern = channels == 1 ? k_rs_to_tensor_crops<1, uint16_t> : channels == 3 ? k_rs_to_tensor_crops<3, uint16_t> : k_rs_to_tensor_crops<4, uint16_t>;
     else
         kern = channels == 1 ? k_rs_to_tensor_crops<1, uint32_t> : channels == 3 ? k_rs_to_tensor_crops<3, uint32_t> : k_rs_to_tensor_crops<4, uint32_t>;
-    for (int f0 = 0; f0 < frames; f0 += 65535) {
-        const int nf = std::min(65535, frames - f0);
+    return rs_for_frame_groups(is, frames, [&](int f0, int nf) {
         g.src = src + (size_t)f0 * src_fs;
         g.out = out + (size_t)f0 * out_fs;
         g.d_flip = t.d_flip ? t.d_flip + f0 : nullptr;   // a byte per frame
         g.d_origin = d_origin + 2 * (size_t)f0;          // a pair per frame
-        const dim3 grid((row_bytes + kCropsRowBlock - 1) / kCropsRowBlock, h, nf);
-        hipLaunchKernelGGL(kern, grid, dim3(kRsThreads), 0, stream, g);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        hipLaunchKernelGGL(kern, dim3((row_bytes + kCropsRowBlock - 1) / kCropsRowBlock, h, nf), dim3(kRsThreads), 0, is.stream, g);
+    });
 }
-
-// the instances of k_rs_fused that store floats with a crop origin per frame: every tap-count bucket x C = 1, 3, 4 and alpha
-template hipError_t rs_launch_fused<1, 4 + kRsMapped + kRsCrops>(const RsFusedLaunch&);
 
 }  // namespace lz

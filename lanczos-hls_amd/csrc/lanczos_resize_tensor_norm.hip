@@ -5,7 +5,7 @@
 // (rs_norm_elem, lanczos_resize_fused.hpp).  Two kernels:
 //
 //   fused      the kRsNorm instances of k_rs_fused: the vertical pass turns the sum it holds into the stored sample and that
-//              into the element.  Instantiated in lanczos_resize_tensor_norm16.hip and lanczos_resize_tensor_norm32.hip.
+//              into the element.
 //   converted  k_rs_to_tensor_norm, here, behind any other resize: the samples go to context scratch, tightly packed, and one
 //              streaming launch turns them into elements.  A request that changes neither axis and has no window runs it on the
 //              caller's frames.
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_to_tensor_norm(RsToTensorNorm
 }
 
 hipError_t rs_to_tensor_norm_launch(const uint8_t* src, size_t src_fs, uint8_t* out, size_t out_fs, int w, int h, int channels,
-                                    int bps, const RsTensorOut& t, int frames, hipStream_t stream) {
+                                    int bps, const RsTensorOut& t, int frames, RsIssue& is) {
     RsToTensorNorm g{};
     g.src_fs = src_fs, g.out_fs = out_fs;
     g.samples = (unsigned long long)w * h * channels;
@@ -99,16 +99,12 @@ hipError_t rs_to_tensor_norm_launch(const uint8_t* src, size_t src_fs, uint8_t* 
     if (bps == 2) kern = channels == 1 ? k_rs_to_tensor_norm<2, 1> : channels == 3 ? k_rs_to_tensor_norm<2, 3> : k_rs_to_tensor_norm<2, 4>;
     else if (bps == 4) kern = channels == 1 ? k_rs_to_tensor_norm<4, 1> : channels == 3 ? k_rs_to_tensor_norm<4, 3> : k_rs_to_tensor_norm<4, 4>;
     else return hipErrorInvalidValue;
-    for (int f0 = 0; f0 < frames; f0 += 65535) {
-        const int nf = std::min(65535, frames - f0);
+    return rs_for_frame_groups(is, frames, [&](int f0, int nf) {
         g.src = src + (size_t)f0 * src_fs;
         g.out = out + (size_t)f0 * out_fs;
         g.d_flip = t.d_flip ? t.d_flip + f0 : nullptr;   // a byte per frame
-        hipLaunchKernelGGL(kern, dim3(blocks, nf), dim3(kRsThreads), 0, stream, g);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        hipLaunchKernelGGL(kern, dim3(blocks, nf), dim3(kRsThreads), 0, is.stream, g);
+    });
 }
 
 }  // namespace lz

@@ -130,18 +130,14 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_ycc_split(RsYccSplit g) {
 }
 
 hipError_t ycc_split_launch(const uint8_t* in, size_t in_fs, const YccSource& s, uint8_t* out, size_t plane_bytes, int frames,
-                            hipStream_t stream) {
+                            RsIssue& is) {
     RsYccSplit g{};
     g.in_fs = in_fs, g.c_rs = s.c_rs, g.plane_bytes = plane_bytes, g.cw = s.cw, g.second_first = s.layout == LANCZOS_YCC_NV21;
     const unsigned items = (2u * (unsigned)s.cw) / 4u + 6u;   // dwords, and at most three bytes at either end
-    for (int f0 = 0; f0 < frames; f0 += 65535) {
-        const int nf = std::min(65535, frames - f0);
+    return rs_for_frame_groups(is, frames, [&](int f0, int nf) {
         g.in = in + (size_t)f0 * in_fs, g.out = out + (size_t)f0 * 2 * plane_bytes;
-        hipLaunchKernelGGL(k_rs_ycc_split, dim3((items + kRsThreads - 1) / kRsThreads, s.ch, nf), dim3(kRsThreads), 0, stream, g);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        hipLaunchKernelGGL(k_rs_ycc_split, dim3((items + kRsThreads - 1) / kRsThreads, s.ch, nf), dim3(kRsThreads), 0, is.stream, g);
+    });
 }
 
 // ---- k_rs_ycc_merge ----------------------------------------------------------------------------------------------------------
@@ -273,7 +269,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_ycc_merge_tensor(RsYccMerge g
 }
 
 static hipError_t ycc_merge_launch(const uint8_t* planes, size_t plane_bytes, uint8_t* out, size_t out_fs, int w, int h,
-                                   const int32_t* table, const RsTensorOut* t, int frames, hipStream_t stream) {
+                                   const int32_t* table, const RsTensorOut* t, int frames, RsIssue& is) {
     RsYccMerge g{};
     g.y_fs = plane_bytes, g.c_fs = 2 * plane_bytes, g.plane_bytes = plane_bytes;
     g.out_fs = out_fs, g.n = (unsigned long long)w * h, g.table = table, g.w = w, g.h = h;
@@ -284,17 +280,13 @@ static hipError_t ycc_merge_launch(const uint8_t* planes, size_t plane_bytes, ui
         kern = t->elem == 2 ? k_rs_ycc_merge_tensor<uint16_t> : k_rs_ycc_merge_tensor<uint32_t>;
     }
     const unsigned blocks = (unsigned)((g.n + kYccBlock - 1) / kYccBlock);   // at most 2^22
-    for (int f0 = 0; f0 < frames; f0 += 65535) {
-        const int nf = std::min(65535, frames - f0);
+    return rs_for_frame_groups(is, frames, [&](int f0, int nf) {
         g.y = planes + (size_t)f0 * plane_bytes;
         g.c = planes + (size_t)frames * plane_bytes + (size_t)f0 * 2 * plane_bytes;
         g.out = out + (size_t)f0 * out_fs;
         g.d_flip = t && t->d_flip ? t->d_flip + f0 : nullptr;
-        hipLaunchKernelGGL(kern, dim3(blocks, nf), dim3(kRsThreads), 0, stream, g);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        hipLaunchKernelGGL(kern, dim3(blocks, nf), dim3(kRsThreads), 0, is.stream, g);
+    });
 }
 
 // ---- the composition ---------------------------------------------------------------------------------------------------------
@@ -338,6 +330,7 @@ int resize_ycc_device(ResizeState* st, YccRequest& q) {
     if ((uintptr_t)q.table & 3) return LANCZOS_ERR_BAD_ARG;
 
     const hipStream_t stream = q.stream;
+    RsIssue is{stream};   // the split and the merge; the planes' launches come back in RsRequest::launches
     const bool capturing = stream_capturing(stream);
     const size_t c_plane = ((size_t)s.cw * s.ch + 3) & ~(size_t)3;
     hipError_t e = st->ycc_planes.reserve(st->life, (size_t)frames * 3 * plane, stream, capturing);
@@ -366,16 +359,18 @@ int resize_ycc_device(ResizeState* st, YccRequest& q) {
     if (rc != LANCZOS_OK) return rc;
     if (s.interleaved()) {
         uint8_t* const split = (uint8_t*)st->ycc_in.p;
-        if ((rc = ycc_hip(q, ycc_split_launch(in + s.cb_off, in_fs, s, split, c_plane, frames, stream))) != LANCZOS_OK) return rc;
-        q.info.split = 1, q.info.launches += (frames + 65534) / 65535;
+        rc = ycc_hip(q, ycc_split_launch(in + s.cb_off, in_fs, s, split, c_plane, frames, is));
+        q.info.launches += is.launches, is.launches = 0;   // counted as issued, like the planes': a later failure keeps it
+        if (rc != LANCZOS_OK) return rc;
+        q.info.split = 1;
         rc = ycc_plane(st, q, &dc, &oc, (size_t)s.cw, split, c_plane, co, plane, 2 * frames, &k_chroma);
     } else {
         rc = ycc_plane(st, q, &dc, &oc, s.c_rs, in + s.cb_off, in_fs, co, 2 * plane, frames, &k_chroma);
         if (rc == LANCZOS_OK) rc = ycc_plane(st, q, &dc, &oc, s.c_rs, in + s.cr_off, in_fs, co + plane, 2 * plane, frames, &k_chroma);
     }
     if (rc != LANCZOS_OK) return rc;
-    rc = ycc_hip(q, ycc_merge_launch(yo, plane, (uint8_t*)q.out, out_fs, w.w, w.h, q.table, q.tensor ? &q.t : nullptr, frames, stream));
-    q.info.launches += (frames + 65534) / 65535;
+    rc = ycc_hip(q, ycc_merge_launch(yo, plane, (uint8_t*)q.out, out_fs, w.w, w.h, q.table, q.tensor ? &q.t : nullptr, frames, is));
+    q.info.launches += is.launches;
     q.info.luma_kernel = k_luma, q.info.chroma_kernel = k_chroma;
     return rc;
 }

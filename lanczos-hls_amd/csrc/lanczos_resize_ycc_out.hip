@@ -122,18 +122,14 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_ycc_join(RsYccJoin g) {
 }
 
 static hipError_t ycc_join_launch(const uint8_t* in, size_t plane_bytes, uint8_t* out, size_t out_fs, const YccDest& t, int frames,
-                                  hipStream_t stream) {
+                                  RsIssue& is) {
     RsYccJoin g{};
     g.out_fs = out_fs, g.c_rs = t.c_rs, g.plane_bytes = plane_bytes, g.cw = t.cw, g.second_first = t.layout == LANCZOS_YCC_NV21;
     const unsigned items = (2u * (unsigned)t.cw) / 4u + 6u;   // dwords, and at most three bytes at either end
-    for (int f0 = 0; f0 < frames; f0 += 65535) {
-        const int nf = std::min(65535, frames - f0);
+    return rs_for_frame_groups(is, frames, [&](int f0, int nf) {
         g.in = in + (size_t)f0 * 2 * plane_bytes, g.out = out + (size_t)f0 * out_fs;
-        hipLaunchKernelGGL(k_rs_ycc_join, dim3((items + kRsThreads - 1) / kRsThreads, t.ch, nf), dim3(kRsThreads), 0, stream, g);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        hipLaunchKernelGGL(k_rs_ycc_join, dim3((items + kRsThreads - 1) / kRsThreads, t.ch, nf), dim3(kRsThreads), 0, is.stream, g);
+    });
 }
 
 // ---- k_rs_ycc_encode ---------------------------------------------------------------------------------------------------------
@@ -251,7 +247,7 @@ __global__ __launch_bounds__(kRsThreads) void k_rs_ycc_encode(RsYccEncode g) {
 }
 
 static hipError_t ycc_encode_launch(const uint8_t* in, size_t in_fs, uint8_t* out, size_t out_fs, const YccDest& t, int w, int h,
-                                    const int32_t* table, int frames, hipStream_t stream) {
+                                    const int32_t* table, int frames, RsIssue& is) {
     RsYccEncode g{};
     g.in_fs = in_fs, g.out_fs = out_fs, g.y_rs = t.y_rs, g.c_rs = t.c_rs, g.cb_off = t.cb_off, g.cr_off = t.cr_off;
     g.w = w, g.h = h, g.ch = t.ch, g.table = table;
@@ -260,14 +256,10 @@ static hipError_t ycc_encode_launch(const uint8_t* in, size_t in_fs, uint8_t* ou
                                      : (t.sy ? k_rs_ycc_encode<0, 1> : k_rs_ycc_encode<0, 0>);
     const unsigned groups = ((unsigned)w + 3u) / 4u;
     const dim3 grid((groups + kRsThreads - 1) / kRsThreads, (t.ch + kYccEncRows - 1) / kYccEncRows, 1);   // at most 64 x 16384
-    for (int f0 = 0; f0 < frames; f0 += 65535) {
-        const int nf = std::min(65535, frames - f0);
+    return rs_for_frame_groups(is, frames, [&](int f0, int nf) {
         g.in = in + (size_t)f0 * in_fs, g.out = out + (size_t)f0 * out_fs;
-        hipLaunchKernelGGL(kern, dim3(grid.x, grid.y, nf), dim3(kRsThreads), 0, stream, g);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        hipLaunchKernelGGL(kern, dim3(grid.x, grid.y, nf), dim3(kRsThreads), 0, is.stream, g);
+    });
 }
 
 // ---- the composition ---------------------------------------------------------------------------------------------------------
@@ -306,6 +298,7 @@ static int ycc_out_from_ycc(ResizeState* st, YccOutRequest& q, const RsWindow& w
     const size_t in_fs = q.in_frame_stride ? q.in_frame_stride : s.extent;
     if (in_fs < s.extent) return LANCZOS_ERR_BAD_ARG;
     const hipStream_t stream = q.stream;
+    RsIssue is{stream};   // the split and the join; the planes' launches come back in RsRequest::launches
     const bool capturing = stream_capturing(stream);
     const size_t in_plane = ((size_t)s.cw * s.ch + 3) & ~(size_t)3, out_plane = ((size_t)t.cw * t.ch + 3) & ~(size_t)3;
     hipError_t e = hipSuccess;
@@ -339,8 +332,10 @@ static int ycc_out_from_ycc(ResizeState* st, YccOutRequest& q, const RsWindow& w
     size_t c_in_rs = s.c_rs, c_in_fs = in_fs;
     if (s.interleaved()) {
         uint8_t* const split = (uint8_t*)st->ycc_in.p;
-        if ((rc = ycc_out_hip(q, ycc_split_launch(in + s.cb_off, in_fs, s, split, in_plane, frames, stream))) != LANCZOS_OK) return rc;
-        q.info.split = 1, q.info.launches += (frames + 65534) / 65535;
+        rc = ycc_out_hip(q, ycc_split_launch(in + s.cb_off, in_fs, s, split, in_plane, frames, is));
+        q.info.launches += is.launches, is.launches = 0;   // counted as issued, like the planes': a later failure keeps it
+        if (rc != LANCZOS_OK) return rc;
+        q.info.split = 1;
         cb_in = split, cr_in = split + in_plane, c_in_rs = (size_t)s.cw, c_in_fs = 2 * in_plane;
     }
     // ... and stored: the caller's, or the tight pairs the join reads
@@ -355,9 +350,10 @@ static int ycc_out_from_ycc(ResizeState* st, YccOutRequest& q, const RsWindow& w
     }
     if (rc != LANCZOS_OK) return rc;
     if (t.interleaved()) {
-        rc = ycc_out_hip(q, ycc_join_launch((const uint8_t*)st->ycc_out.p, out_plane, out + t.cb_off, out_fs, t, frames, stream));
-        q.info.join = 1, q.info.launches += (frames + 65534) / 65535;
+        rc = ycc_out_hip(q, ycc_join_launch((const uint8_t*)st->ycc_out.p, out_plane, out + t.cb_off, out_fs, t, frames, is));
+        q.info.join = 1;
     }
+    q.info.launches += is.launches;
     q.info.luma_kernel = k_luma, q.info.chroma_kernel = k_chroma;
     return rc;
 }
@@ -389,8 +385,9 @@ static int ycc_out_from_rgb(ResizeState* st, YccOutRequest& q, const RsWindow& w
         if (rr.copied) k_rgb = LANCZOS_KERNEL_NONE;
         rgb = (const uint8_t*)st->ycc_rgb.p, rgb_fs = fs;
     }
-    rc = ycc_out_hip(q, ycc_encode_launch(rgb, rgb_fs, (uint8_t*)q.out, out_fs, t, w.w, w.h, q.table, frames, q.stream));
-    q.info.encode = 1, q.info.launches += (frames + 65534) / 65535;
+    RsIssue is{q.stream};
+    rc = ycc_out_hip(q, ycc_encode_launch(rgb, rgb_fs, (uint8_t*)q.out, out_fs, t, w.w, w.h, q.table, frames, is));
+    q.info.encode = 1, q.info.launches += is.launches;
     q.info.luma_kernel = k_rgb, q.info.chroma_kernel = LANCZOS_KERNEL_NONE;
     return rc;
 }

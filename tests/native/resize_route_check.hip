@@ -6,18 +6,22 @@
 //   in_w in_h out_w out_h channels a reserved0                 the descriptor (sample width, alpha and filter in reserved0)
 //   has_opts box0 box1 box2 box3 gap                           lanczos_resize_opts
 //   has_win x0 y0 w h  crops                                   the window; crops = 1: (w, h) is the crop size, x0 = y0 = 0
-//   elem mapped chan_stride row_stride pix_stride out_channels the tensor part (elem 0: bytes out)
+//   elem mapped chan_stride row_stride pix_stride out_channels the tensor part (elem 0: bytes out); mapped bit 1: the request is a
+//                                                              lanczos_tensor_norm one (wide samples, no map)
 //   has_src row_stride chan_stride pix_stride                  lanczos_resize_source
 //   has_dst row_stride chan_stride pix_stride                  lanczos_resize_dest
 //   force frames
 // Output per line: ROUTE <line> <err> <reduce> <pack> <main> <bps> <flags> <follower> <tensor> <source> <dest> <kernel>
+// and behind them the list this program was compiled with, INSTANCE <index> <bps> <flags> per entry of LZ_RS_FUSED_INSTANCES.  A
+// fused route that names no entry (rs_fused_instance_exists) prints BAD and the exit status is 1.
 #include <cstdio>
 
 #include "lanczos_resize.hpp"
 using namespace lz;
 
 static const char* const kMain[] = {"fused", "nearest", "copy", "crop", "none", "pass_h_only", "pass_v_only", "two_pass", "v_first"};
-static const char* const kFollower[] = {"none", "to_tensor", "crops_scratch", "crops_direct"};
+static const char* const kFollower[] = {"none", "to_tensor", "crops_scratch", "crops_direct", "to_tensor_norm"};
+static_assert(rs_fused_instance_exists(1, 0) && !rs_fused_instance_exists(2, 4), "the predicate is the list's, at compile time");
 
 int main(int argc, char** argv) {
     FILE* f = argc > 1 ? fopen(argv[1], "r") : nullptr;
@@ -63,16 +67,23 @@ int main(int argc, char** argv) {
         q.d = &d, q.r = &r, q.frames = frames, q.force = force, q.H = &H, q.V = &V;
         if (elem) {
             RsTensorOut lay{nullptr, tcs, trs, tps, elem, oc};
-            q.tensor = true, q.mapped = mapped != 0, q.crops = crops != 0, q.elem = elem;
+            q.tensor = true, q.mapped = (mapped & 1) != 0, q.norm = (mapped & 2) != 0, q.crops = crops != 0, q.elem = elem;
             q.extent_bytes = tensor_extent_bytes(&d, q.win, lay);
         }
         q.src = has_src ? &rs : nullptr, q.dst = has_dst ? &rd : nullptr;
         const RsRoute rt = rs_route(q);
         printf("ROUTE %d %d %d %d %s %d %d %s %d %d %d %d\n", line, rt.err, (int)rt.reduce, (int)rt.pack, kMain[rt.main], rt.bps, rt.flags,
                kFollower[rt.follower], rt.tensor_route, rt.source_route, rt.dest_route, rt.kernel);
+        if (rt.err == LANCZOS_OK && rt.main == kRsMainFused && !rs_fused_instance_exists(rt.bps, rt.flags)) {
+            printf("BAD line %d: no fused instance <%d, %d>\n", line, rt.bps, rt.flags);
+            return 1;
+        }
         line++;
     }
     fclose(f);
     printf("done %d\n", line);
+#define X(I, BPS, FLAGS) printf("INSTANCE %d %d %d\n", I, BPS, FLAGS);
+    LZ_RS_FUSED_INSTANCES(X)
+#undef X
     return 0;
 }

@@ -312,6 +312,7 @@ def legality(case):
 # ---- the dispatcher restated --------------------------------------------------------------------------------------------
 
 PLANAR_OUT = 128            # kRsPlanarOut in the flag word of a fused instance
+NORM = 256                  # kRsNorm: the flag word of the lanczos_tensor_norm instances
 AUTO_PLANAR_DIRECT = True   # kRsPlanarAutoDirect: under AUTO the fused kernel reads planes as they lie
 Pred = collections.namedtuple("Pred", "main alpha reduce pack follower last_kernel tensor_route source_route")
 _FLAGS = ((8, "mapped"), (16, "crops"), (32, "planar"), (64, "rowshift"), (PLANAR_OUT, "planar_out"))

@@ -262,7 +262,8 @@ Route = collections.namedtuple("Route", "err reduce pack main bps flags follower
 
 
 def _routes(exe, tmp_path, lines):
-    """rs_route's answer to every line, from one run of the program"""
+    """rs_route's answer to every line, from one run of the program, and the (bps, flags) of every entry of
+    LZ_RS_FUSED_INSTANCES the program was compiled with; every fused route names one of them"""
     path = str(tmp_path / "requests.txt")
     with open(path, "w") as f:
         f.write("\n".join(lines) + "\n")
@@ -270,17 +271,24 @@ def _routes(exe, tmp_path, lines):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     out = r.stdout.split("\n")
     assert out[len(lines)] == "done %d" % len(lines), out[-3:]
+    inst = [text.split() for text in out[len(lines) + 1:] if text]
+    assert inst and [w[:2] for w in inst] == [["INSTANCE", str(i)] for i in range(len(inst))], inst   # the indices are dense
+    listed = {(int(w[2]), int(w[3])) for w in inst}
+    assert len(listed) == len(inst), inst   # and no entry is there twice
     routes = []
     for i, text in enumerate(out[:len(lines)]):
         w = text.split()
         assert w[0] == "ROUTE" and int(w[1]) == i, text
-        routes.append(Route(*(v if k in (5, 8) else int(v) for k, v in enumerate(w) if k >= 2)))
-    return routes
+        rt = Route(*(v if k in (5, 8) else int(v) for k, v in enumerate(w) if k >= 2))
+        assert rt.main != "fused" or (rt.bps, rt.flags) in listed, (lines[i], rt, sorted(listed))
+        routes.append(rt)
+    return routes, listed
 
 
-def test_the_route_is_the_prediction(route_exe, tmp_path):
-    """rs_route (csrc/lanczos_resize_route.cpp), asked on the host for every legal case of the product, launches what predict()
-    says; a case refused only because FUSED is forced is refused by the route, with that code"""
+@pytest.fixture(scope="module")
+def product_routes(route_exe, tmp_path_factory):
+    """the walk over the cross product: its legal cases, those refused only because FUSED is forced, rs_route's answer to each
+    (legal ones first), and the instance list"""
     legal, forced = [], []
     for case in M.cases():
         said = M.legality(case)
@@ -288,8 +296,23 @@ def test_the_route_is_the_prediction(route_exe, tmp_path):
             legal.append(case)
         elif said == L.ERR_UNSUPPORTED and case.force == L.RESIZE_FUSED and M.legality(case._replace(force=L.RESIZE_AUTO)) is None:
             forced.append(case)
+    routes, listed = _routes(route_exe, tmp_path_factory.mktemp("product"), [M.route_line(c) for c in legal + forced])
+    return legal, forced, routes, listed
+
+
+@pytest.fixture(scope="module")
+def dest_routes(route_exe, tmp_path_factory):
+    """the walk over the destinations: every legal (case, dest) pair, rs_route's answer to each, and the instance list"""
+    todo = [(case, dest) for case, dest in M.dest_cases() if M.dest_legality(case, dest) is None]
+    routes, listed = _routes(route_exe, tmp_path_factory.mktemp("dest"), [M.route_line(c, dest) for c, dest in todo])
+    return todo, routes, listed
+
+
+def test_the_route_is_the_prediction(product_routes):
+    """rs_route (csrc/lanczos_resize_route.cpp), asked on the host for every legal case of the product, launches what predict()
+    says; a case refused only because FUSED is forced is refused by the route, with that code"""
+    legal, forced, routes, _ = product_routes
     assert len(legal) > 40000 and forced
-    routes = _routes(route_exe, tmp_path, [M.route_line(c) for c in legal + forced])
     compared = 0
     for case, rt in zip(legal, routes):
         p = M.predict(case)
@@ -355,13 +378,12 @@ def test_the_destination_rules_are_the_validators():
         assert (M.dest_strides(c, "pitched")[0] % 4 != 0) == (k.bps != 4), kind
 
 
-def test_the_destination_route(route_exe, tmp_path):
+def test_the_destination_route(dest_routes):
     """every legal (case, dest) pair of every kind on every geometry, into pitched rows and -- where the validator takes them --
     into planes: the route's destination is predict_dest's, the fused instance is predict_dest_main's (a planar-out one exactly
     where planes are stored DIRECT), and nothing in front of the store differs from the case without a destination"""
-    todo = [(case, dest) for case, dest in M.dest_cases() if M.dest_legality(case, dest) is None]
+    todo, routes, _ = dest_routes
     assert len(todo) > 19000 and {dest for _, dest in todo} == set(M.DESTS)
-    routes = _routes(route_exe, tmp_path, [M.route_line(c, dest) for c, dest in todo])
     seen = collections.Counter()
     for (case, dest), rt in zip(todo, routes):
         want = M.predict_dest(case, dest)
@@ -377,6 +399,30 @@ def test_the_destination_route(route_exe, tmp_path):
     for kind in M.KINDS:
         assert {(d, r) for k, d, r in seen if k == kind} == M.dest_pairs(kind), kind
     assert min(seen.values()) > 50, seen
+
+
+def test_every_listed_instance_is_named(route_exe, tmp_path, product_routes, dest_routes):
+    """every entry of LZ_RS_FUSED_INSTANCES is the instance of at least one route: of the two walks, and -- the matrix has no
+    lanczos_tensor_norm output -- of the smallest case of that kind for the kRsNorm entries: three 16-bit or float channels,
+    halved, into tight CHW float32 elements"""
+    listed = product_routes[3]
+    assert dest_routes[2] == listed
+    walked = {(rt.bps, rt.flags) for rt in product_routes[2] + dest_routes[1] if rt.main == "fused"}
+    lines = []
+    for kind in ("u16x3", "f32x3"):
+        case = M.Case(kind, "down", "lanczos", "none", "whole", "bytes", "none", L.RESIZE_AUTO)
+        f = M.route_line(case).split()
+        w, h = M.frame_size(case)
+        f[19:25] = [str(v) for v in (4, 2, w * h, w, 1, 3)]   # elem, mapped = 2: a norm request, the strides, out_channels
+        lines.append(" ".join(f))
+    norm, again = _routes(route_exe, tmp_path, lines)
+    assert again == listed
+    assert [(rt.err, rt.main, rt.bps, rt.flags, rt.tensor_route) for rt in norm] == \
+        [(L.OK, "fused", 2, M.NORM, L.TENSOR_FUSED), (L.OK, "fused", 4, M.NORM, L.TENSOR_FUSED)], norm
+    named = walked | {(rt.bps, rt.flags) for rt in norm}
+    assert named == listed, (sorted(listed - named), sorted(named - listed))
+    # the cross product alone reaches every entry but the kRsNorm ones
+    assert listed - walked == {i for i in listed if i[1] == M.NORM}, sorted(listed - walked)
 
 
 def test_expected_dest_arrays_are_between_sentinels():

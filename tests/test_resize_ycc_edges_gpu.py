@@ -429,6 +429,33 @@ def test_more_than_65535_frames_in_one_call(ctx, tables, layout):
                              f"{int(got[bad[0]]):#x} != {int(want[bad[0]]):#x}")
 
 
+def test_more_than_65535_frames_cropped_in_one_call(ctx, tables):
+    """65 537 frames of a 4 x 2 4:4:4 source kept at size, of which the window 2 x 2 at (2, 0) is stored: no pass runs and the
+    window is not the frame, so every plane is rs_route's kRsMainCrop, and k_rs_crop takes the whole batch in ONE launch (it
+    strides over the frames with gridDim.z) where every other step goes out once per 65 535 frames.  Every frame is compared
+    with the slice of its source, and the count is the launches that went out: one per plane and the merge in two groups"""
+    shape, F, win = Y.Shape(0, 0, 4, 2, 4, 2, "lanczos"), 65537, (2, 0, 2, 2)
+    case = _case(shape)
+    p = L.resize_window_plan_host(L.resize_desc(4, 2, 4, 2, 1), win, F, box=(0, 0, 4, 2))
+    assert not (p.pass_h or p.pass_v)                           # a copy of a window: the crop
+    y, cb, cr = Y.noise_planes(shape, 12, seed=9)
+    ref12 = Y.convert(Y.table(Y.JFIF), y, cb, cr)[:, win[1]:win[1] + win[3], win[0]:win[0] + win[2]]
+    assert len({r.tobytes() for r in ref12}) == 12
+    idx = np.arange(F) % 8
+    idx[[0, 65534, 65535, 65536]] = [8, 9, 10, 11]
+    tight = Y.tight(y, cb, cr, Y.PLANAR)
+    assert tight.shape == (12, 24)
+    rng = np.random.default_rng(10)
+    buf = np.concatenate([rng.integers(0, 256, Y.MARGIN + 1, dtype=np.uint8), tight[idx].ravel(),
+                          rng.integers(0, 256, Y.MARGIN, dtype=np.uint8)])
+    s = Y.Frames(buf, Y.MARGIN + 1, 24, 4, 4, 8, 16, Y.PLANAR)
+    got = _bytes(ctx, case, s, F, tables["jfif"][1], window=win)
+    info = ctx.last_ycc_info()
+    _eq(got, ref12[idx], "65537 cropped frames")
+    assert info.luma_kernel == info.chroma_kernel == L.KERNEL_NONE and not info.split, info
+    assert _groups(F) == 2 and info.launches == 3 * 1 + _groups(F), info
+
+
 # ---- refusals --------------------------------------------------------------------------------------------------------------------
 def test_refusals_not_yet_exercised(ctx, tables):
     """a d_table off a dword, and an interleaved 4:2:2 layout with two different offsets: ERR_BAD_ARG from both device entries,
