@@ -881,8 +881,9 @@ int lanczos_resize_tensor_norm_host(lanczos_ctx* ctx, const lanczos_resize_desc*
  * reducing_gap reduces each plane as Pillow would reduce that plane.  The window is the same output rectangle for the three
  * planes.  Left-sited chroma (MPEG-2) would need a negative box offset, which Pillow refuses: it is not expressed here.
  * The descriptor describes the RGB result: channels = 3, in_w x in_h the luma size, every filter (LANCZOS_FILTER_NEAREST
- * included) and every a.  LANCZOS_RESIZE_ALPHA, _U16 or _F32 in its flag word is LANCZOS_ERR_UNSUPPORTED (no wide chroma:
- * P010 / P016 are not built).  There is no crop origin per frame and no lanczos_resize_dest on these entries.
+ * included) and every a.  LANCZOS_RESIZE_ALPHA, _U16 or _F32 in its flag word is LANCZOS_ERR_UNSUPPORTED (wide chroma, P010 /
+ * P016 and planes of 16-bit words, has an entry of its own: lanczos_resize_ycc16, below).  There is no crop origin per frame
+ * and no lanczos_resize_dest on these entries.
  * The colour conversion is a table the caller passes, int32 t[3][3][256]:
  *   out[c] = clip8((t[c][0][y] + t[c][1][cb] + t[c][2][cr]) >> 6)           (>> arithmetic, clip8 to 0 .. 255)
  * Its indices are bytes, so no content can address out of bounds; entries must keep the sum inside int32.  lanczos_ycc_table fills
@@ -1045,6 +1046,110 @@ typedef struct lanczos_ycc_out_info {
     int32_t reserved[2];
 } lanczos_ycc_out_info;
 int lanczos_last_ycc_out_info(const lanczos_ctx* ctx, lanczos_ycc_out_info* info);
+
+/* ---- resize YCbCr frames of 16-bit words (P010, P016, P210, planar 10 / 12 / 16-bit) into YCbCr, RGB words and tensors ----
+ * The two sections above are 8-bit.  This one entry serves frames whose samples are uint16 words holding any depth from 8 to 16
+ * bits, LSB-aligned (yuv420p10le) or MSB-aligned (P010): 4:2:0, 4:2:2 and 4:4:4 planes, and interleaved chroma of word pairs in
+ * either order.  The descriptor has channels = 3 and LANCZOS_RESIZE_U16; in_w x in_h is the luma size.  THE CONTRACT for the
+ * planes is Pillow's mode I;16 on the raw words, plane by plane:
+ *   Yo  = Image.fromarray(Y,  "I;16").resize((out_w, out_h), filt, box=bl)
+ *   Cbo = Image.fromarray(Cb, "I;16").resize((CW, CH), filt, box=bc)                            (Cr likewise)
+ * bl is the request's box in luma pixels and bc is bl scaled by the SOURCE's subsampling on its doubles (centre siting, odd sizes
+ * included), the rule of the 8-bit entries.  (CW, CH) is (out_w, out_h) for RGB and tensor output and the full output's chroma
+ * size under the DESTINATION's subsampling for YCbCr output, whose window rule is lanczos_ycc_dest_validate's: origins are
+ * multiples of the destination's subsampling.  An axis that keeps its size over its whole span is not filtered: P010 -> planar at
+ * the same even size is a pure re-layout and runs no resize kernel.
+ * THE I;16 STORE IS PART OF THE CONTRACT: a rounded sum below 0 stores 0, and one above 65535 stores 0xFF00 | low byte -- not
+ * 65535.  MSB-aligned full-range content (words near 65535 beside words near 0) hits this at every hard edge, exactly as Pillow
+ * does; limited-range and LSB-aligned content stays clear of it.
+ * What wide requests refuse stays refused: a reducing_gap is LANCZOS_ERR_BAD_ARG (Pillow's reduce refuses I;16) and
+ * LANCZOS_FILTER_NEAREST is LANCZOS_ERR_UNSUPPORTED.
+ * THE OUTPUT KIND is decided by which pointers of the request are set:
+ *   dst alone          wide YCbCr frames in dst's layout; no colour conversion.
+ *   matrix alone       packed RGB of 16-bit samples, w * h * 3 words per frame (the window's; win NULL: the whole output); `out`
+ *                      and out_frame_stride (0 = w * h * 6 rounded up to a multiple of 4) must be multiples of 4.
+ *   matrix and norm    tensor elements: cvt(((float)RGB16[src_channel[oc]] / div[oc] - mean[oc]) / std[oc]), lanczos_tensor_norm's
+ *                      contract with (R, G, B) the words above as source channels 0, 1, 2 -- the channel map, flips, d_flip,
+ *                      strides (in elements), the overlap rule and the extent all apply; elements the strides do not name are
+ *                      left untouched.
+ * Every other combination is LANCZOS_ERR_BAD_ARG.
+ * THE COLOUR CONVERSION is an integer matrix passed by value (a table over words would hold 3 * 3 * 65536 entries):
+ *   out[c] = clamp((k[c][0] * (y - sub[0]) + k[c][1] * (cb - sub[1]) + k[c][2] * (cr - sub[2]) + rnd) >> shift, 0, max)
+ * with the sum in int64, >> an arithmetic shift and rnd = shift ? 1 << (shift - 1) : 0.  |k| < 2^24, sub and max in 0 .. 65535,
+ * shift in 0 .. 30: within these bounds no content can overflow the sum.  lanczos_ycc16_matrix_init fills it for a standard
+ * (LANCZOS_YCC_JFIF and _BT601: the BT.601 constants; _BT709; _BT2020: Kr 0.2627, Kb 0.0593), a depth of 8 .. 16 bits, either
+ * alignment and either range, scaled to max = 65535: with unit = 2^(16 - depth) for MSB-aligned words and 1 otherwise,
+ *   ky = 65535 / (luma range in words),    luma range   = (full ? 2^depth - 1 : 219 << (depth - 8)) * unit
+ *   kc = 65535 / (chroma range in words),  chroma range = (full ? 2^depth - 1 : 224 << (depth - 8)) * unit
+ *   sub = ((full ? 0 : 16 << (depth - 8)) * unit, 2^(depth - 1) * unit, 2^(depth - 1) * unit)
+ *   R = ky y' + 2 (1 - Kr) kc cr',  G = ky y' - 2 (1 - Kb) Kb / Kg kc cb' - 2 (1 - Kr) Kr / Kg kc cr',  B = ky y' + 2 (1 - Kb) kc cb'
+ * shift is the largest value <= 30 for which every entry, rounded to nearest, stays below 2^23 in magnitude, and k the real
+ * coefficient times 2^shift rounded to nearest.  The unrounded integer sum then differs from the real one by at most
+ * sum_j 0.5 |v_j - sub_j| / 2^shift < 0.5, so results are within 1 of the float64 matrix rounded to nearest.  Any other matrix (a
+ * full-range BT.709 to 10-bit RGB, BGR rows, a pass-through) is the caller's own struct.
+ * LAYOUTS are lanczos_ycc_source and lanczos_ycc_dest with every stride and offset in BYTES, validated by the functions below,
+ * which mirror the 8-bit rules with these differences: the descriptor must have LANCZOS_RESIZE_U16 (else
+ * LANCZOS_ERR_UNSUPPORTED; _ALPHA and _F32 too); a luma or planar chroma row is 2 w bytes, an interleaved row 4 cw bytes; every
+ * stride, offset, base pointer and frame stride must be a multiple of 2, else LANCZOS_ERR_BAD_ARG.  Bytes of a destination the
+ * layout does not name keep their contents, in device and in host memory.
+ * Routes.  The planes are one-channel LANCZOS_RESIZE_U16 requests of lanczos_resize_dest_device with a pitched source, for YCbCr
+ * output with a pitched destination too, so a fused plan stores into the caller's planes.  Interleaved chroma in is split into
+ * two tight word planes by one streaming launch (k_rs_ycc_split16); interleaved chroma out is joined from two tight planes by one
+ * (k_rs_ycc_join16); RGB words and elements come from one launch over the three resized planes (k_rs_ycc16_merge).  Fused 4:2:0
+ * planar -> planar is 3 launches; P010 -> P010 is 4 (luma, split, one chroma call of 2 * frames frames, join); P010 -> tensor is 4
+ * (luma, split, chroma, merge).  lanczos_resize_force applies to every plane; the scratch lives as the other scratch of a
+ * context does.  Not here: RGB words into wide YCbCr, crop origins per frame, left-sited chroma. */
+#define LANCZOS_YCC_BT2020 3   /* a standard of lanczos_ycc16_matrix_init beside LANCZOS_YCC_JFIF / _BT601 / _BT709 */
+typedef struct lanczos_ycc16_matrix {
+    int32_t k[3][3];      /* |k| < 2^24; rows R, G, B over (y, cb, cr) */
+    int32_t sub[3];       /* 0 .. 65535, subtracted from (y, cb, cr) */
+    int32_t shift;        /* 0 .. 30 */
+    int32_t max;          /* 0 .. 65535 */
+    int32_t reserved[4];  /* must be 0 */
+} lanczos_ycc16_matrix;
+/* Host only.  LANCZOS_ERR_BAD_ARG: a null m, an unknown standard, a depth outside 8 .. 16. */
+int lanczos_ycc16_matrix_init(lanczos_ycc16_matrix* m, int standard, int depth, int msb_aligned, int full_range);
+/* Host only.  LANCZOS_ERR_BAD_ARG: a null m, |k| >= 2^24, a sub, shift or max outside its range, a non-zero reserved word. */
+int lanczos_ycc16_matrix_validate(const lanczos_ycc16_matrix* m);
+/* Host only: the tight layouts in bytes, as lanczos_ycc_source_init / lanczos_ycc_dest_init give them for 8-bit frames. */
+int lanczos_ycc16_source_init(lanczos_ycc_source* src, const lanczos_resize_desc* d, int layout, int sub_x, int sub_y);
+int lanczos_ycc16_dest_init(lanczos_ycc_dest* dst, const lanczos_resize_desc* d, const lanczos_resize_window* win, int layout,
+                            int sub_x, int sub_y);
+/* Host only: the rules of lanczos_ycc_source_validate / lanczos_ycc_dest_validate with the differences above. */
+int lanczos_ycc16_source_validate(const lanczos_resize_desc* d, const lanczos_ycc_source* src);
+int lanczos_ycc16_dest_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_ycc_dest* dst);
+typedef struct lanczos_ycc16_request {
+    const lanczos_resize_desc* d;        /* channels = 3 with LANCZOS_RESIZE_U16; in_w x in_h the luma size */
+    const lanczos_resize_opts* opts;     /* may be NULL; a box only */
+    const lanczos_resize_window* win;    /* may be NULL */
+    const lanczos_ycc_source* src;       /* required */
+    const lanczos_ycc_dest* dst;         /* wide YCbCr out */
+    const lanczos_ycc16_matrix* matrix;  /* RGB words or, with norm, tensor elements out; read when the call is made */
+    const lanczos_tensor_norm* norm;     /* LANCZOS_MEM_HOST: d_flip is a host array */
+    const void* in;                      /* a multiple of 2 */
+    void* out;                           /* a multiple of 2 (YCbCr), of 4 (RGB words), of the element (tensor) */
+    int32_t frames;
+    int32_t memory;                      /* LANCZOS_MEM_DEVICE or LANCZOS_MEM_HOST */
+    size_t in_frame_stride;              /* bytes, a multiple of 2; 0: the source's extent */
+    size_t out_frame_stride;             /* bytes; 0: the destination's extent, w * h * 6 rounded up to 4, the elements' extent */
+    void* stream;                        /* LANCZOS_MEM_DEVICE only */
+    int32_t reserved[4];                 /* must be 0 */
+} lanczos_ycc16_request;
+/* Host only: everything lanczos_resize_ycc16 refuses from the request alone, by the code it would return -- a null request, d,
+ * src, in or out, frames < 1, an unknown memory, a non-zero reserved word, an illegal combination of dst / matrix / norm, what the
+ * validations above and lanczos_resize_tensor_norm_validate refuse, a reducing_gap, a base or frame stride off its multiple, a
+ * frame stride with LANCZOS_MEM_HOST. */
+int lanczos_ycc16_request_validate(const lanczos_ycc16_request* rq);
+/* The one launching entry.  LANCZOS_MEM_HOST: synchronous, frames one extent apart (RGB words back to back). */
+int lanczos_resize_ycc16(lanczos_ctx* ctx, const lanczos_ycc16_request* rq);
+/* What the last successful lanczos_resize_ycc16 on the context launched: the LANCZOS_KERNEL_* of the luma and of the chroma
+ * resize (LANCZOS_KERNEL_NONE: a copy), whether k_rs_ycc_split16, k_rs_ycc_join16 and k_rs_ycc16_merge ran, and the number of
+ * launches (resize kernels, copies, split, join, merge).  All zero before any call. */
+typedef struct lanczos_ycc16_info {
+    int32_t luma_kernel, chroma_kernel, split, join, merge, launches;
+    int32_t reserved[2];
+} lanczos_ycc16_info;
+int lanczos_last_ycc16_info(const lanczos_ctx* ctx, lanczos_ycc16_info* info);
 
 /* ---- reduce by whole factors (Pillow's Image.reduce((fx, fy), box), an exact integer box average) ----
  * 8-bit, 1, 3 or 4 independent interleaved channels.  box = (x0, y0, x1, y1), integers with 0 <= x0 < x1 <= in_w and the same

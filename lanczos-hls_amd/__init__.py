@@ -93,6 +93,9 @@ ABI_SYMBOLS = [
     "lanczos_resize_ycc_tensor_device", "lanczos_resize_ycc_host", "lanczos_resize_ycc_tensor_host", "lanczos_last_ycc_info",
     "lanczos_ycc_dest_init", "lanczos_ycc_dest_validate", "lanczos_ycc_table_forward", "lanczos_resize_ycc_out",
     "lanczos_last_ycc_out_info",
+    "lanczos_ycc16_matrix_init", "lanczos_ycc16_matrix_validate", "lanczos_ycc16_source_init", "lanczos_ycc16_source_validate",
+    "lanczos_ycc16_dest_init", "lanczos_ycc16_dest_validate", "lanczos_ycc16_request_validate", "lanczos_resize_ycc16",
+    "lanczos_last_ycc16_info",
 ]
 SPLIT_FRAMES, SPLIT_ROWS = 0, 1
 YCC_PLANAR, YCC_NV12, YCC_NV21 = 0, 1, 2   # lanczos_ycc_source.layout
@@ -102,6 +105,12 @@ YCC_STANDARDS = {"jfif": YCC_JFIF, "bt601": YCC_BT601, "bt709": YCC_BT709}
 # the frame layouts Context.resize_ycc knows by name: (layout, sub_x, sub_y)
 YCC_LAYOUTS = {"nv12": (YCC_NV12, 1, 1), "nv21": (YCC_NV21, 1, 1), "i420": (YCC_PLANAR, 1, 1), "i422": (YCC_PLANAR, 1, 0),
                "i444": (YCC_PLANAR, 0, 0)}
+# ... and what the 16-bit entry (lanczos_resize_ycc16) adds: a fourth standard for ycc16_matrix, and the names of the frames of
+# word pairs -- "p010" / "p016" have the nv12 shape, "p210" / "p216" (and "nv16") the 4:2:2 one
+YCC_BT2020 = 3
+YCC16_STANDARDS = dict(YCC_STANDARDS, bt2020=YCC_BT2020)
+YCC16_LAYOUTS = dict(YCC_LAYOUTS, p010=(YCC_NV12, 1, 1), p016=(YCC_NV12, 1, 1), nv16=(YCC_NV12, 1, 0), p210=(YCC_NV12, 1, 0),
+                     p216=(YCC_NV12, 1, 0))
 
 
 class Route(collections.namedtuple("Route", "main prefix launches prefix_seen")):
@@ -283,6 +292,35 @@ class YccOutInfo(collections.namedtuple("YccOutInfo", "luma_kernel chroma_kernel
     number of launches of the call."""
 
 
+class Ycc16Matrix(ctypes.Structure):
+    """lanczos_ycc16_matrix -- the colour conversion of 16-bit YCbCr words, passed by value:
+    out[c] = clamp((k[c][0] * (y - sub[0]) + k[c][1] * (cb - sub[1]) + k[c][2] * (cr - sub[2]) + rnd) >> shift, 0, max), the sum
+    in int64, rnd = 1 << (shift - 1) (0 for shift 0).  |k| < 2^24, sub and max in 0 .. 65535, shift in 0 .. 30."""
+    _fields_ = [("k", (ctypes.c_int32 * 3) * 3), ("sub", ctypes.c_int32 * 3), ("shift", ctypes.c_int32), ("max", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 4)]
+
+
+class Ycc16Request(ctypes.Structure):
+    """lanczos_ycc16_request -- one call of lanczos_resize_ycc16.  The pointer fields are addresses: whoever fills them in keeps
+    the structs they name alive (ycc16_request does, on the request itself).  dst alone: wide YCbCr out; matrix alone: packed
+    RGB words; matrix and norm: tensor elements."""
+    _fields_ = [("d", ctypes.c_void_p), ("opts", ctypes.c_void_p), ("win", ctypes.c_void_p), ("src", ctypes.c_void_p),
+                ("dst", ctypes.c_void_p), ("matrix", ctypes.c_void_p), ("norm", ctypes.c_void_p), ("in_", ctypes.c_void_p),
+                ("out", ctypes.c_void_p), ("frames", ctypes.c_int32), ("memory", ctypes.c_int32),
+                ("in_frame_stride", ctypes.c_size_t), ("out_frame_stride", ctypes.c_size_t), ("stream", ctypes.c_void_p),
+                ("reserved", ctypes.c_int32 * 4)]
+
+
+class Ycc16InfoC(ctypes.Structure):   # include/lanczos_hip.h: lanczos_ycc16_info
+    _fields_ = [(n, ctypes.c_int32) for n in ("luma_kernel", "chroma_kernel", "split", "join", "merge", "launches")] + [
+        ("reserved", ctypes.c_int32 * 2)]
+
+
+class Ycc16Info(collections.namedtuple("Ycc16Info", "luma_kernel chroma_kernel split join merge launches")):
+    """lanczos_last_ycc16_info: KERNEL_* of the luma and of the chroma resize of the last resize_ycc16* call (KERNEL_NONE: a
+    copy), whether k_rs_ycc_split16, k_rs_ycc_join16 and k_rs_ycc16_merge ran, and the number of launches of the call."""
+
+
 FLIP_H, FLIP_V = 1, 2   # the bits of lanczos_tensor_view.flip and of a d_flip byte
 _FLIP_NAMES = {None: 0, "": 0, "h": FLIP_H, "v": FLIP_V, "hv": FLIP_H | FLIP_V, "vh": FLIP_H | FLIP_V}
 
@@ -407,6 +445,15 @@ _SIGNATURES = {
     "lanczos_ycc_table_forward": ([_I, _P], None),
     "lanczos_resize_ycc_out": ([_P, ctypes.POINTER(YccOutRequest)], None),
     "lanczos_last_ycc_out_info": ([_P, ctypes.POINTER(YccOutInfoC)], None),
+    "lanczos_ycc16_matrix_init": ([ctypes.POINTER(Ycc16Matrix), _I, _I, _I, _I], None),
+    "lanczos_ycc16_matrix_validate": ([ctypes.POINTER(Ycc16Matrix)], None),
+    "lanczos_ycc16_source_init": ([_PYS, _PRD, _I, _I, _I], None),
+    "lanczos_ycc16_source_validate": ([_PRD, _PYS], None),
+    "lanczos_ycc16_dest_init": ([_PYD, _PRD, _PRW, _I, _I, _I], None),
+    "lanczos_ycc16_dest_validate": ([_PRD, _PRW, _PYD], None),
+    "lanczos_ycc16_request_validate": ([ctypes.POINTER(Ycc16Request)], None),
+    "lanczos_resize_ycc16": ([_P, ctypes.POINTER(Ycc16Request)], None),
+    "lanczos_last_ycc16_info": ([_P, ctypes.POINTER(Ycc16InfoC)], None),
 }
 for _device, _host, _head in _ENTRY_PAIRS:
     _SIGNATURES[_host] = ([_P] + _head + [_P, _P, _I], None)
@@ -768,12 +815,12 @@ def ycc_table(standard="jfif"):
     return t
 
 
-def _ycc_layout_arg(layout, sub_x, sub_y, what):
+def _ycc_layout_arg(layout, sub_x, sub_y, what, layouts=YCC_LAYOUTS):
     """(code, sub_x, sub_y) of a layout given by a name of YCC_LAYOUTS or by its code with both subsamplings"""
     if isinstance(layout, str):
-        if layout.lower() not in YCC_LAYOUTS:
-            raise LanczosError(ERR_BAD_ARG, f"{what}: layout is one of {', '.join(YCC_LAYOUTS)}, not {layout!r}")
-        code, sx, sy = YCC_LAYOUTS[layout.lower()]
+        if layout.lower() not in layouts:
+            raise LanczosError(ERR_BAD_ARG, f"{what}: layout is one of {', '.join(layouts)}, not {layout!r}")
+        code, sx, sy = layouts[layout.lower()]
         return code, (sx if sub_x is None else int(sub_x)), (sy if sub_y is None else int(sub_y))
     if sub_x is None or sub_y is None:
         raise LanczosError(ERR_BAD_ARG, f"{what}: a layout given by its code needs sub_x and sub_y")
@@ -840,6 +887,82 @@ def ycc_out_request(desc, dest, in_ptr, out_ptr, frames, source=None, table=None
     rq.table, rq.in_, rq.out, rq.frames, rq.memory = table, in_ptr, out_ptr, int(frames), int(memory)
     rq.in_frame_stride, rq.out_frame_stride, rq.stream = int(in_frame_stride), int(out_frame_stride), stream
     return rq
+
+
+def ycc16_matrix(standard="bt709", depth=10, msb_aligned=True, full_range=False):
+    """A Ycc16Matrix of a standard ("jfif" and "bt601": the BT.601 constants; "bt709"; "bt2020") for words that hold `depth`
+    bits (8 .. 16), MSB-aligned as in P010 or LSB-aligned as in yuv420p10le, limited or full range, scaled to RGB words of
+    0 .. 65535 (lanczos_ycc16_matrix_init).  Any other matrix is a Ycc16Matrix the caller fills in."""
+    code = YCC16_STANDARDS.get(standard.lower()) if isinstance(standard, str) else int(standard)
+    if code is None:
+        raise LanczosError(ERR_BAD_ARG, f"ycc16_matrix: standard is one of {', '.join(YCC16_STANDARDS)}, not {standard!r}")
+    m = Ycc16Matrix()
+    _check(_lib().lanczos_ycc16_matrix_init(ctypes.byref(m), code, int(depth), int(bool(msb_aligned)), int(bool(full_range))),
+           "lanczos_ycc16_matrix_init")
+    return m
+
+
+def ycc16_matrix_validate(matrix):
+    _check(_lib().lanczos_ycc16_matrix_validate(_ref(matrix)), "lanczos_ycc16_matrix_validate")
+
+
+def _ycc16_fill(s, layout_code, y_row_stride, c_row_stride, cb_offset, cr_offset):
+    for name, v in (("y_row_stride", y_row_stride), ("c_row_stride", c_row_stride), ("cb_offset", cb_offset), ("cr_offset", cr_offset)):
+        if v is not None:
+            setattr(s, name, int(v))
+    if layout_code != YCC_PLANAR and cb_offset is not None and cr_offset is None:
+        s.cr_offset = s.cb_offset
+
+
+def ycc16_source(desc, layout="p010", sub_x=None, sub_y=None, y_row_stride=None, c_row_stride=None, cb_offset=None, cr_offset=None):
+    """A validated YccSource for frames of 16-bit words (desc: resize_desc(..., 3, bits=16), in_w x in_h the luma size).  layout: a
+    name of YCC16_LAYOUTS (those of ycc_source, "p010" / "p016" for the nv12 shape, "p210" / "p216" / "nv16" for 4:2:2 pairs) or a
+    code with sub_x and sub_y.  Strides and offsets are BYTES, multiples of 2; the defaults are the tight layout."""
+    code, sx, sy = _ycc_layout_arg(layout, sub_x, sub_y, "ycc16_source", YCC16_LAYOUTS)
+    s = YccSource()
+    _check(_lib().lanczos_ycc16_source_init(ctypes.byref(s), ctypes.byref(desc), code, sx, sy), "lanczos_ycc16_source_init")
+    _ycc16_fill(s, code, y_row_stride, c_row_stride, cb_offset, cr_offset)
+    _check(_lib().lanczos_ycc16_source_validate(ctypes.byref(desc), ctypes.byref(s)), "lanczos_ycc16_source_validate")
+    return s
+
+
+def ycc16_source_validate(desc, source):
+    _check(_lib().lanczos_ycc16_source_validate(ctypes.byref(desc), _ref(source)), "lanczos_ycc16_source_validate")
+
+
+def ycc16_dest(desc, layout="p010", window=None, sub_x=None, sub_y=None, y_row_stride=None, c_row_stride=None, cb_offset=None,
+               cr_offset=None):
+    """A validated YccDest for the frame of 16-bit words a call with `desc` stores: its whole output, or `window` = (x0, y0, w, h)
+    of it, the origin a multiple of the subsampling.  layout as ycc16_source takes it; strides and offsets in BYTES, multiples of
+    2.  ycc_dest_frame_bytes gives the frame's extent."""
+    code, sx, sy = _ycc_layout_arg(layout, sub_x, sub_y, "ycc16_dest", YCC16_LAYOUTS)
+    win = resize_window(desc, window)
+    t = YccDest()
+    _check(_lib().lanczos_ycc16_dest_init(ctypes.byref(t), ctypes.byref(desc), ctypes.byref(win), code, sx, sy), "lanczos_ycc16_dest_init")
+    _ycc16_fill(t, code, y_row_stride, c_row_stride, cb_offset, cr_offset)
+    _check(_lib().lanczos_ycc16_dest_validate(ctypes.byref(desc), ctypes.byref(win), ctypes.byref(t)), "lanczos_ycc16_dest_validate")
+    return t
+
+
+def ycc16_dest_validate(desc, dest, window=None):
+    _check(_lib().lanczos_ycc16_dest_validate(ctypes.byref(desc), _window_ref(desc, window), _ref(dest)), "lanczos_ycc16_dest_validate")
+
+
+def ycc16_request(desc, source, in_ptr, out_ptr, frames, dest=None, matrix=None, norm=None, opts=None, window=None, memory=MEM_DEVICE,
+                  in_frame_stride=0, out_frame_stride=0, stream=None):
+    """A Ycc16Request over ready structs (None: NULL) and addresses; the structs stay alive with it."""
+    rq = Ycc16Request()
+    rq._keep = (desc, source, dest, matrix, norm, opts, window)
+    for name, v in (("d", desc), ("opts", opts), ("win", window), ("src", source), ("dst", dest), ("matrix", matrix), ("norm", norm)):
+        setattr(rq, name, ctypes.addressof(v) if v is not None else None)
+    rq.in_, rq.out, rq.frames, rq.memory = in_ptr, out_ptr, int(frames), int(memory)
+    rq.in_frame_stride, rq.out_frame_stride, rq.stream = int(in_frame_stride), int(out_frame_stride), stream
+    return rq
+
+
+def ycc16_request_validate(rq):
+    """lanczos_ycc16_request_validate: raises LanczosError with the code lanczos_resize_ycc16 would refuse the request with"""
+    _check(_lib().lanczos_ycc16_request_validate(_ref(rq)), "lanczos_ycc16_request_validate")
 
 
 def _ycc_table_arg(standard, table, what, forward=False):
@@ -1663,6 +1786,110 @@ class Context:
         info = YccOutInfoC()
         self._call("lanczos_last_ycc_out_info", ctypes.byref(info))
         return YccOutInfo(info.luma_kernel, info.chroma_kernel, bool(info.split), bool(info.join), bool(info.encode), info.launches)
+
+    def _ycc16(self, d, source, in_ptr, out_ptr, frames, dest, matrix, norm, box, opts, window, memory, in_fs=0, out_fs=0, stream=None):
+        if opts is None and box is not None:
+            opts = resize_opts(d, box, None)
+        if window is not None and not isinstance(window, ResizeWindow):
+            window = resize_window(d, window)
+        rq = ycc16_request(d, source, in_ptr, out_ptr, frames, dest, matrix, norm, opts, window, memory, in_fs, out_fs, stream)
+        self._call("lanczos_resize_ycc16", ctypes.byref(rq))
+
+    def _ycc16_host_args(self, frames, in_w, in_h, out_w, out_h, layout, filter, a, source, what):
+        d = resize_desc(in_w, in_h, out_w, out_h, 3, a, bits=16, filter=filter)
+        src = source if source is not None else ycc16_source(d, layout)
+        ycc16_source_validate(d, src)
+        x = np.ascontiguousarray(frames)
+        n = ycc_frame_bytes(d, src) // 2
+        if x.dtype != np.uint16 or x.ndim not in (1, 2) or x.shape[-1] != n:
+            raise LanczosError(ERR_BAD_ARG, f"{what}: expected uint16 [{n}] or [N][{n}], the words of the frames as they lie in memory")
+        return d, src, x, (x if x.ndim == 2 else x[None])
+
+    def resize_ycc16_to_ycc(self, frames, in_w, in_h, out_w, out_h, layout="p010", out_layout="p010", filter=FILTER_LANCZOS, a=3,
+                            box=None, window=None, source=None, dest=None, out=None):
+        """YCbCr frames of 16-bit words -> YCbCr frames of 16-bit words, uint16 [N][W'] (or [W'] for one frame [W]): word for word
+        Pillow's "I;16" resize of every plane on the raw words, luma to out_w x out_h and chroma to the destination's chroma size
+        with the box scaled to its plane; no colour conversion.  frames: uint16 [N][W] or [W], each frame its words as they lie
+        in memory in the tight layout of `layout` (a name of YCC16_LAYOUTS: "p010", "p016", "p210", "p216", "nv12", "nv21",
+        "nv16", "i420", "i422", "i444") or as `source` (ycc16_source) describes.  The words may hold any depth, LSB- or
+        MSB-aligned: sums above 65535 store 0xFF00 | low byte, as Pillow's do.  box in luma pixels, filter (not "nearest") and
+        a as Context.resize; no reducing_gap.  window = (x0, y0, w, h) in luma output pixels, the origin a multiple of the
+        destination's subsampling.  Words of the result the layout does not name are zero, or keep what `out` held."""
+        d, src, x0, x = self._ycc16_host_args(frames, in_w, in_h, out_w, out_h, layout, filter, a, source, "resize_ycc16_to_ycc")
+        t = dest if dest is not None else ycc16_dest(d, out_layout, window)
+        n = ycc_dest_frame_bytes(d, t, window) // 2
+        if out is None:
+            out = np.zeros((x.shape[0], n), dtype=np.uint16)
+        elif out.dtype != np.uint16 or not out.flags.c_contiguous or out.shape != (x.shape[0], n):
+            raise LanczosError(ERR_BAD_ARG, f"out: expected a contiguous uint16 [{x.shape[0]}][{n}]")
+        self._ycc16(d, src, x.ctypes.data, out.ctypes.data, x.shape[0], t, None, None, box, None, window, MEM_HOST)
+        return out if x0.ndim == 2 else out[0]
+
+    def resize_ycc16_rgb(self, frames, in_w, in_h, out_w, out_h, layout="p010", matrix=None, filter=FILTER_LANCZOS, a=3, box=None,
+                         window=None, source=None):
+        """YCbCr frames of 16-bit words -> uint16 [N][h][w][3]: the planes resized as resize_ycc16_to_ycc resizes them (chroma to
+        the luma size) and converted through `matrix`, a Ycc16Matrix (None: ycc16_matrix(), BT.709 for limited-range 10-bit
+        words, MSB-aligned, to RGB words of 0 .. 65535)."""
+        d, src, x0, x = self._ycc16_host_args(frames, in_w, in_h, out_w, out_h, layout, filter, a, source, "resize_ycc16_rgb")
+        m = matrix if matrix is not None else ycc16_matrix()
+        win = resize_window(d, window)
+        out = np.empty((x.shape[0], win.h, win.w, 3), dtype=np.uint16)
+        self._ycc16(d, src, x.ctypes.data, out.ctypes.data, x.shape[0], None, m, None, box, None, window, MEM_HOST)
+        return out if x0.ndim == 2 else out[0]
+
+    def resize_ycc16_tensor(self, frames, in_w, in_h, out_w, out_h, layout="p010", matrix=None, mean=None, std=None, div=65535.0,
+                            dtype="float32", tensor_layout="chw", channels_out=None, flip=None, filter=FILTER_LANCZOS, a=3, box=None,
+                            window=None, source=None):
+        """As resize_ycc16_rgb, into a normalised tensor: ((float(P) / div - mean) / std) of the RGB words P that call returns,
+        three IEEE float operations as Context.resize_tensor_norm computes them, float32 [N][C][h][w] (tensor_layout="chw") or
+        [N][h][w][C] ("hwc"); dtype "bfloat16" comes back as uint16 patterns, "float16" as np.float16.  div, mean and std one
+        value or one per channel of the result; channels_out and flip as Context.resize_tensor."""
+        d, src, x0, x = self._ycc16_host_args(frames, in_w, in_h, out_w, out_h, layout, filter, a, source, "resize_ycc16_tensor")
+        if dtype not in _TENSOR_NORM_FORMATS:
+            raise LanczosError(ERR_BAD_ARG, f"resize_ycc16_tensor: dtype is 'float32', 'bfloat16' or 'float16', not {dtype!r}")
+        m = matrix if matrix is not None else ycc16_matrix()
+        f = x.shape[0]
+        ch = tuple(int(v) for v in channels_out) if channels_out is not None else (0, 1, 2)
+        c = len(ch)
+        if not 1 <= c <= 3:
+            raise LanczosError(ERR_BAD_ARG, "resize_ycc16_tensor: channels_out names 1 to 3 source channels")
+        bits, flips = _flip_arg(flip, f, "resize_ycc16_tensor")
+        win = resize_window(d, window)
+        n = tensor_norm(tensor_strides(tensor_layout, win.w, win.h, c), div, 0.0 if mean is None else mean, 1.0 if std is None else std,
+                        dtype, ch, bits, flips.ctypes.data if flips is not None else None)
+        out = np.empty((f, c, win.h, win.w) if tensor_layout == "chw" else (f, win.h, win.w, c),
+                       dtype=np.float32 if dtype == "float32" else np.uint16)
+        self._ycc16(d, src, x.ctypes.data, out.ctypes.data, f, None, m, n, box, None, window, MEM_HOST)
+        out = out if dtype == "float32" else _tensor16_array(out, dtype)
+        return out if x0.ndim == 2 else out[0]
+
+    def resize_ycc16_to_ycc_device(self, desc, source, dest, d_in, d_out, frames, in_frame_stride=0, out_frame_stride=0, stream=None,
+                                   box=None, opts=None, window=None):
+        """Device pointers, asynchronous on `stream`: frames of 16-bit words at d_in in `source`'s layout (ycc16_source) -> frames
+        at d_out in `dest`'s (ycc16_dest, of `window` where one is given).  Addresses and frame strides (bytes; 0 = the layouts'
+        extents) are multiples of 2.  Bytes the destination does not name keep their contents."""
+        self._ycc16(desc, source, d_in, d_out, frames, dest, None, None, box, opts, window, MEM_DEVICE, in_frame_stride, out_frame_stride,
+                    stream)
+
+    def resize_ycc16_rgb_device(self, desc, source, matrix, d_in, d_out, frames, in_frame_stride=0, out_frame_stride=0, stream=None,
+                                box=None, opts=None, window=None):
+        """... -> tightly packed RGB words of the window at d_out, w * h * 3 per frame; d_out and out_frame_stride (0 = w * h * 6
+        rounded up to a multiple of 4) are multiples of 4.  matrix: a Ycc16Matrix, passed by value."""
+        self._ycc16(desc, source, d_in, d_out, frames, None, matrix, None, box, opts, window, MEM_DEVICE, in_frame_stride,
+                    out_frame_stride, stream)
+
+    def resize_ycc16_tensor_device(self, desc, source, matrix, norm, d_in, d_out, frames, in_frame_stride=0, out_frame_stride=0,
+                                   stream=None, box=None, opts=None, window=None):
+        """... -> tensor elements at d_out as `norm`, a TensorNorm (tensor_norm), describes them over the RGB words as source
+        channels 0, 1, 2; its div / mean / std travel by value, its d_flip is a device array read when the kernels run."""
+        self._ycc16(desc, source, d_in, d_out, frames, None, matrix, norm, box, opts, window, MEM_DEVICE, in_frame_stride,
+                    out_frame_stride, stream)
+
+    def last_ycc16_info(self):
+        """Ycc16Info of the last successful resize_ycc16* call on the context (all zero before any)."""
+        info = Ycc16InfoC()
+        self._call("lanczos_last_ycc16_info", ctypes.byref(info))
+        return Ycc16Info(info.luma_kernel, info.chroma_kernel, bool(info.split), bool(info.join), bool(info.merge), info.launches)
 
     def last_ycc_info(self):
         """YccInfo of the last successful resize_ycc* call on the context (all zero before any)."""

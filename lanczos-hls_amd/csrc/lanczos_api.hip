@@ -67,6 +67,7 @@ struct lanczos_ctx {
     int last_dest_route = 0;     // lanczos_last_dest_route: LANCZOS_DEST_* of the last call that had a destination layout
     lanczos_ycc_info last_ycc{};  // lanczos_last_ycc_info: what the last successful lanczos_resize_ycc_* call launched
     lanczos_ycc_out_info last_ycc_out{};  // lanczos_last_ycc_out_info: ... lanczos_resize_ycc_out call launched
+    lanczos_ycc16_info last_ycc16{};  // lanczos_last_ycc16_info: ... lanczos_resize_ycc16 call launched
     int last_route = 0;      // lanczos_last_route: main kernel, prefix route and launch count of the last upscale call
     int route_launches = 0;  // launches of the call in flight (reset by the entry points, counted where a launch is issued)
     int route_seen = 0;      // prefix routes of those launches, one bit each
@@ -1588,6 +1589,127 @@ int lanczos_resize_ycc_out(lanczos_ctx* ctx, const lanczos_ycc_out_request* rq) 
     q.last_kernel = &ctx->last_kernel, q.last_hip = &ctx->last_hip;
     rc = host ? lz::resize_ycc_out_host(ctx->resize, q) : lz::resize_ycc_out_device(ctx->resize, q);
     if (rc == LANCZOS_OK) ctx->last_ycc_out = q.info, ctx->last_kernel = q.info.luma_kernel;
+    return rc;
+}
+
+// ---- YCbCr frames of 16-bit words (lanczos_resize_ycc16.hip) --------------------------------------------------------------
+int lanczos_ycc16_matrix_init(lanczos_ycc16_matrix* m, int standard, int depth, int msb_aligned, int full_range) {
+    return m && lz::ycc16_matrix_init(m, standard, depth, msb_aligned != 0, full_range != 0) ? LANCZOS_OK : LANCZOS_ERR_BAD_ARG;
+}
+
+int lanczos_ycc16_matrix_validate(const lanczos_ycc16_matrix* m) { return lz::ycc16_matrix_validate(m); }
+
+int lanczos_ycc16_source_init(lanczos_ycc_source* src, const lanczos_resize_desc* d, int layout, int sub_x, int sub_y) {
+    if (!src) return LANCZOS_ERR_BAD_ARG;
+    const int rc = lz::ycc16_desc_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    if ((sub_x | sub_y) & ~1) return LANCZOS_ERR_BAD_ARG;
+    const int64_t cw = (d->in_w + sub_x) >> sub_x, ch = (d->in_h + sub_y) >> sub_y, luma = (int64_t)d->in_w * d->in_h * 2;
+    *src = lanczos_ycc_source{};
+    src->layout = layout, src->sub_x = sub_x, src->sub_y = sub_y;
+    src->y_row_stride = 2 * (int64_t)d->in_w, src->cb_offset = luma;
+    if (layout == LANCZOS_YCC_PLANAR) src->c_row_stride = 2 * cw, src->cr_offset = luma + 2 * cw * ch;
+    else src->c_row_stride = 4 * cw, src->cr_offset = luma;
+    lz::YccSource s;
+    return lz::ycc16_source_resolve(d, src, &s);
+}
+
+int lanczos_ycc16_source_validate(const lanczos_resize_desc* d, const lanczos_ycc_source* src) {
+    const int rc = lz::ycc16_desc_validate(d);
+    if (rc != LANCZOS_OK) return rc;
+    lz::YccSource s;
+    return lz::ycc16_source_resolve(d, src, &s);
+}
+
+int lanczos_ycc16_dest_init(lanczos_ycc_dest* dst, const lanczos_resize_desc* d, const lanczos_resize_window* win, int layout,
+                            int sub_x, int sub_y) {
+    if (!dst) return LANCZOS_ERR_BAD_ARG;
+    int rc = lz::ycc16_desc_validate(d);
+    lz::RsWindow w;
+    if (rc == LANCZOS_OK) rc = lz::resize_window_resolve(d, win, &w);
+    if (rc != LANCZOS_OK) return rc;
+    if ((sub_x | sub_y) & ~1) return LANCZOS_ERR_BAD_ARG;
+    const int64_t cw = (w.w + sub_x) >> sub_x, ch = (w.h + sub_y) >> sub_y, luma = (int64_t)w.w * w.h * 2;
+    *dst = lanczos_ycc_dest{};
+    dst->layout = layout, dst->sub_x = sub_x, dst->sub_y = sub_y;
+    dst->y_row_stride = 2 * (int64_t)w.w, dst->cb_offset = luma;
+    if (layout == LANCZOS_YCC_PLANAR) dst->c_row_stride = 2 * cw, dst->cr_offset = luma + 2 * cw * ch;
+    else dst->c_row_stride = 4 * cw, dst->cr_offset = luma;
+    lz::YccDest s;
+    return lz::ycc16_dest_resolve(w, dst, false, &s);
+}
+
+int lanczos_ycc16_dest_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_ycc_dest* dst) {
+    int rc = lz::ycc16_desc_validate(d);
+    lz::RsWindow w;
+    if (rc == LANCZOS_OK) rc = lz::resize_window_resolve(d, win, &w);
+    if (rc != LANCZOS_OK) return rc;
+    lz::YccDest s;
+    return lz::ycc16_dest_resolve(w, dst, true, &s);
+}
+
+int lanczos_last_ycc16_info(const lanczos_ctx* ctx, lanczos_ycc16_info* info) {
+    if (!ctx || !info) return LANCZOS_ERR_BAD_ARG;
+    *info = ctx->last_ycc16;
+    return LANCZOS_OK;
+}
+
+extern "C++" {
+// everything lanczos_resize_ycc16 refuses from the request alone; on LANCZOS_OK q holds the request, resolved
+static int ycc16_request_resolve(const lanczos_ycc16_request* rq, lz::Ycc16Request& q) {
+    if (!rq || !rq->in || !rq->out || !rq->src || rq->frames <= 0) return LANCZOS_ERR_BAD_ARG;
+    if (rq->memory != LANCZOS_MEM_DEVICE && rq->memory != LANCZOS_MEM_HOST) return LANCZOS_ERR_BAD_ARG;
+    for (int32_t r : rq->reserved)
+        if (r != 0) return LANCZOS_ERR_BAD_ARG;
+    const bool host = rq->memory == LANCZOS_MEM_HOST;
+    q.d = rq->d, q.o = rq->opts, q.win = rq->win, q.dst = rq->dst, q.rgb = rq->matrix != nullptr, q.tensor = rq->norm != nullptr;
+    q.in = rq->in, q.out = rq->out, q.frames = rq->frames;
+    q.in_frame_stride = rq->in_frame_stride, q.out_frame_stride = rq->out_frame_stride, q.stream = (hipStream_t)rq->stream;
+    int rc = lz::ycc16_desc_validate(rq->d);
+    if (rc != LANCZOS_OK) return rc;
+    // the output kind: dst alone, matrix alone, or matrix and norm
+    if ((rq->dst != nullptr) == (rq->matrix != nullptr) || (rq->norm && !rq->matrix)) return LANCZOS_ERR_BAD_ARG;
+    if ((rc = lz::ycc16_source_resolve(rq->d, rq->src, &q.s)) != LANCZOS_OK) return rc;
+    lz::RsResolved r;
+    lz::RsWindow w;
+    if ((rc = lz::resize_resolve(rq->d, rq->opts, &r)) != LANCZOS_OK) return rc;   // (a reducing_gap on words: LANCZOS_ERR_BAD_ARG)
+    if ((rc = lz::resize_window_resolve(rq->d, rq->win, &w)) != LANCZOS_OK) return rc;
+    lz::YccDest t;
+    if (rq->dst && (rc = lz::ycc16_dest_resolve(w, rq->dst, true, &t)) != LANCZOS_OK) return rc;
+    if (rq->matrix) {
+        if ((rc = lz::ycc16_matrix_validate(rq->matrix)) != LANCZOS_OK) return rc;
+        q.m = *rq->matrix;
+    }
+    if (rq->norm && (rc = lz::tensor_norm_validate(rq->d, rq->win, rq->norm, &q.t)) != LANCZOS_OK) return rc;
+    // bases and frame strides: words on words, RGB frames on dwords, elements on elements
+    const size_t out_mask = rq->dst ? 1 : rq->norm ? (size_t)(q.t.elem - 1) : host ? 1 : 3;
+    if ((((uintptr_t)rq->in | rq->in_frame_stride) & 1) != 0 || (((uintptr_t)rq->out | rq->out_frame_stride) & out_mask) != 0)
+        return LANCZOS_ERR_BAD_ARG;
+    if (host && (rq->in_frame_stride || rq->out_frame_stride)) return LANCZOS_ERR_BAD_ARG;
+    return LANCZOS_OK;
+}
+}   // extern "C++"
+
+int lanczos_ycc16_request_validate(const lanczos_ycc16_request* rq) {
+    lz::Ycc16Request q;
+    return ycc16_request_resolve(rq, q);
+}
+
+int lanczos_resize_ycc16(lanczos_ctx* ctx, const lanczos_ycc16_request* rq) {
+    if (!ctx) return LANCZOS_ERR_BAD_ARG;
+    lz::Ycc16Request q;
+    int rc = ycc16_request_resolve(rq, q);
+    if (rc != LANCZOS_OK) return rc;
+    const bool host = rq->memory == LANCZOS_MEM_HOST;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    if (host && !ctx->stream) return LANCZOS_ERR_HIP;
+    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
+    route_begin(ctx);
+    if (host) q.stream = ctx->stream;
+    q.last_hip = &ctx->last_hip;
+    rc = host ? lz::resize_ycc16_host(ctx->resize, q) : lz::resize_ycc16_device(ctx->resize, q);
+    if (rc == LANCZOS_OK) ctx->last_ycc16 = q.info, ctx->last_kernel = q.info.luma_kernel;
     return rc;
 }
 

@@ -548,4 +548,37 @@ int resize_ycc_out_device(ResizeState* st, YccOutRequest& q);
 // host buffers and a host table; frames one extent apart; synchronous.  The destination goes up before it comes back
 int resize_ycc_out_host(ResizeState* st, YccOutRequest& q);
 
+// ---- YCbCr frames of 16-bit words (lanczos_resize_ycc16.hip; lanczos_resize_ycc16): the compositions above on one-channel
+// LANCZOS_RESIZE_U16 requests, with a split and a join of word pairs and a merge through an integer matrix.  YccSource and YccDest
+// hold bytes here too; the 16-bit validators resolve them
+int ycc16_desc_validate(const lanczos_resize_desc* d);
+int ycc16_source_resolve(const lanczos_resize_desc* d, const lanczos_ycc_source* src, YccSource* s);
+int ycc16_dest_resolve(const RsWindow& w, const lanczos_ycc_dest* dst, bool aligned_origin, YccDest* s);
+int ycc16_matrix_validate(const lanczos_ycc16_matrix* m);
+bool ycc16_matrix_init(lanczos_ycc16_matrix* m, int standard, int depth, bool msb_aligned, bool full_range);
+// One call of lanczos_resize_ycc16, filled in by lanczos_api.hip
+struct Ycc16Request {
+    const lanczos_resize_desc* d = nullptr;       // validated (ycc16_desc_validate)
+    const lanczos_resize_opts* o = nullptr;
+    const lanczos_resize_window* win = nullptr;
+    YccSource s;                                  // resolved
+    const lanczos_ycc_dest* dst = nullptr;        // YCbCr out: resolved by the entry points, which know the window
+    bool rgb = false;                             // RGB words or elements out: m is validated
+    lanczos_ycc16_matrix m{};
+    bool tensor = false;
+    RsTensorOut t;                                // validated (tensor_norm_validate) where tensor is set
+    const void* in = nullptr;
+    void* out = nullptr;
+    int frames = 0;
+    size_t in_frame_stride = 0, out_frame_stride = 0;
+    hipStream_t stream = nullptr;
+    int* last_hip = nullptr;
+    lanczos_ycc16_info info{};                    // out, on LANCZOS_OK
+};
+// ctx->mu held, device set: device pointers, asynchronous
+int resize_ycc16_device(ResizeState* st, Ycc16Request& q);
+// host buffers and, of a tensor request, host flips; frames one extent apart; synchronous.  A destination's and a tensor's
+// frames go up before they come back
+int resize_ycc16_host(ResizeState* st, Ycc16Request& q);
+
 }  // namespace lz

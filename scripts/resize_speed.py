@@ -1385,6 +1385,143 @@ def run_ycc_out(name, args, ctx, torch, parent):
     torch.cuda.empty_cache()
 
 
+YCC16_WORKLOADS = {   # name: (in_w, in_h, out_w, out_h, frames, layout, crop (w, h) from the centre or None, tensor dtype or None: YCbCr out)
+    "YW1": (3840, 2160, 1920, 1080, 32, "p010", None, None),
+    "YW2": (3840, 2160, 1920, 1080, 32, "p010", None, "bfloat16"),
+    "YW3": (500, 375, 341, 256, 256, "i420", (224, 224), "float32"),
+}
+
+
+def run_ycc16(name, args, ctx, torch, parent):
+    """YCbCr frames of 16-bit words (lanczos_resize_ycc16), 10-bit samples: MSB-aligned in P010, LSB-aligned in planes.
+    YW1, P010 -> P010: (a) `ycc16`, the one call; (b) `pipeline`, what it replaces -- torch's split of the chroma pairs, three
+    one-channel uint16 calls (luma straight into the result), torch's re-interleave; (c) `floor`, the luma call alone.  (a) and
+    (b) are checked to agree.  YW2 / YW3, into normalised tensors under BT.2020: (b) `pipeline` is torch's chroma replication,
+    float matrix, round, clamp and cast to RGB words, then resize_tensor_norm; (c) `floor` is resize_tensor_norm alone on frames
+    converted beforehand (--parent-lib: on that build); `luma_only` the luma plane's call.  (b) replicates chroma and its matrix
+    is float, so only (a) is Pillow's composition there and no route is checked against another."""
+    import ctypes
+    iw, ih, ow, oh, f, layout, crop, dtype = YCC16_WORKLOADS[name]
+    msb = layout == "p010"
+    d = L.resize_desc(iw, ih, ow, oh, 3, bits=16)
+    src = L.ycc16_source(d, layout)
+    in_fb = L.ycc_frame_bytes(d, src)
+    cw, chh = L.ycc_chroma_size(d, src)
+    win = L.center_window(ow, oh, *crop) if crop else None
+    w, h = (win[2], win[3]) if win else (ow, oh)
+    s = torch.cuda.current_stream().cuda_stream
+    sets = max(2, -(-2 * 256 * 2 ** 20 // (f * in_fb)) + 1)
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    words = lambda n: (torch.randint(64, 941, (f, n), dtype=torch.int32, device="cuda", generator=gen) << (6 if msb else 0)).to(torch.int16)
+    xs = [words(in_fb // 2) for _ in range(sets)]
+    d1 = L.resize_desc(iw, ih, ow, oh, 1, bits=16)
+    unsigned = lambda t: t.to(torch.int32) & 0xFFFF
+
+    def split(x):
+        if layout == "p010":
+            c2 = x[:, iw * ih:].view(f, chh, cw, 2)
+            return c2[..., 0], c2[..., 1]
+        return x[:, iw * ih:iw * ih + cw * chh].view(f, chh, cw), x[:, iw * ih + cw * chh:].view(f, chh, cw)
+
+    if dtype is None:
+        dst = L.ycc16_dest(d, layout)
+        out_fb = L.ycc_dest_frame_bytes(d, dst)
+        ocw, och = L.ycc_dest_chroma_size(d, dst)
+        ys = [torch.empty((f, out_fb // 2), dtype=torch.int16, device="cuda") for _ in range(sets)]
+        dc = L.resize_desc(cw, chh, ocw, och, 1, bits=16)
+        tmp = torch.empty((2, f, och, ocw), dtype=torch.int16, device="cuda")
+
+        def ycc16(i):
+            ctx.resize_ycc16_to_ycc_device(d, src, dst, xs[i % sets].data_ptr(), ys[i % sets].data_ptr(), f, stream=s)
+            return ys[i % sets][0]
+
+        def pipeline(i):
+            x, y = xs[i % sets], ys[i % sets]
+            cb, cr = (p.contiguous() for p in split(x))
+            ctx.resize_device(d1, x.data_ptr(), y.data_ptr(), f, in_fb, out_fb, s)
+            ctx.resize_device(dc, cb.data_ptr(), tmp[0].data_ptr(), f, 0, 0, s)
+            ctx.resize_device(dc, cr.data_ptr(), tmp[1].data_ptr(), f, 0, 0, s)
+            c2 = y[:, ow * oh:].view(f, och, ocw, 2)
+            c2[..., 0], c2[..., 1] = tmp[0], tmp[1]
+            return y[0]
+
+        def floor(i):
+            ctx.resize_device(d1, xs[i % sets].data_ptr(), ys[i % sets].data_ptr(), f, in_fb, out_fb, s)
+            return ys[i % sets][0, :ow * oh]
+        routes = {"ycc16": ycc16, "pipeline": pipeline, "floor": floor}
+        inb = {"ycc16": f * in_fb, "pipeline": f * in_fb, "floor": f * iw * ih * 2}
+        outb = {"ycc16": f * out_fb, "pipeline": f * out_fb, "floor": f * ow * oh * 2}
+        check, floor_on = (("ycc16", "pipeline"),), "luma call, this build"
+    else:
+        elem = 4 if dtype == "float32" else 2
+        m = L.ycc16_matrix("bt2020", 10, msb, False)
+        st = L.tensor_strides("chw", w, h, 3)
+        n = L.tensor_norm(st, 65535.0, IMAGENET_MEAN, IMAGENET_STD, dtype)
+        ys = [torch.empty(f * w * h * 3 * elem, dtype=torch.uint8, device="cuda") for _ in range(sets)]
+        d3 = L.resize_desc(iw, ih, ow, oh, 3, bits=16)
+        kr, kb = 0.2627, 0.0593
+        kg, unit = 1.0 - kr - kb, (64.0 if msb else 1.0)
+        ky, kc = 65535.0 / (876.0 * unit), 65535.0 / (896.0 * unit)
+
+        def to_rgb(x):
+            yy = (unsigned(x[:, :iw * ih]).view(f, ih, iw).float() - 64.0 * unit) * ky
+            up = lambda p: (unsigned(p).repeat_interleave(2, 1).repeat_interleave(2, 2)[:, :ih, :iw].float() - 512.0 * unit) * kc
+            cb, cr = split(x)
+            u, v = up(cb), up(cr)
+            rgb = torch.stack([yy + 2 * (1 - kr) * v, yy - 2 * (1 - kb) * kb / kg * u - 2 * (1 - kr) * kr / kg * v, yy + 2 * (1 - kb) * u], -1)
+            return rgb.round().clamp(0, 65535).to(torch.int32).to(torch.int16).contiguous()
+
+        rgbs = [to_rgb(xs[k]) for k in range(min(sets, 2))]           # the floor's inputs, converted beforehand
+        tmp1 = torch.empty(f * w * h + 1, dtype=torch.int16, device="cuda")
+
+        def ycc16(i):
+            y = ys[i % sets]
+            ctx.resize_ycc16_tensor_device(d, src, m, n, xs[i % sets].data_ptr(), y.data_ptr(), f, stream=s, window=win)
+            return y[:w * h * 3 * elem]
+
+        def pipeline(i):
+            y = ys[i % sets]
+            rgb = to_rgb(xs[i % sets])
+            ctx.resize_tensor_norm_device(d3, rgb.data_ptr(), y.data_ptr(), f, n, stream=s, window=win)
+            return y[:w * h * 3 * elem]
+
+        if parent is not None:
+            fn = parent.lib.lanczos_resize_tensor_norm_device
+            fn.argtypes = [ctypes.c_void_p] * 8 + [ctypes.c_int, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_void_p]
+            pwin = L.resize_window(d3, win) if win else None
+
+        def floor(i):
+            y, x_ptr = ys[i % sets], rgbs[i % len(rgbs)].data_ptr()
+            if parent is None:
+                ctx.resize_tensor_norm_device(d3, x_ptr, y.data_ptr(), f, n, stream=s, window=win)
+            else:
+                rc = fn(parent.h, ctypes.byref(d3), None, ctypes.byref(pwin) if pwin is not None else None, None, ctypes.byref(n), x_ptr,
+                        y.data_ptr(), f, 0, 0, s)
+                if rc != 0:
+                    raise SystemExit(f"parent lanczos_resize_tensor_norm_device: {rc}")
+            return y[:w * h * 3 * elem]
+
+        def luma_only(i):
+            ctx.resize_device(d1, xs[i % sets].data_ptr(), tmp1.data_ptr(), f, in_fb, 2 * w * h, s, window=win)
+            return tmp1[:w * h]
+        routes = {"ycc16": ycc16, "pipeline": pipeline, "floor": floor, "luma_only": luma_only}
+        inb = {"ycc16": f * in_fb, "pipeline": f * in_fb, "floor": f * iw * ih * 6, "luma_only": f * iw * ih * 2}
+        outb = {rn: f * w * h * 3 * elem for rn in routes}
+        outb["luma_only"] = f * w * h * 2
+        check, floor_on = (), "resize_tensor_norm on RGB words, " + ("parent" if parent else "this build")
+
+    ycc16(0)
+    info = ctx.last_ycc16_info()
+    us = run_routes(name, f"{layout} {iw}x{ih}->{ow}x{oh}" + (f" window {win}" if win else "") + f" {dtype or layout}", f, routes, inb,
+                    outb, args, ctx, torch, check=check)
+    print(json.dumps({"workload": name, "ycc16_over_pipeline": round(us["ycc16"] / us["pipeline"], 3),
+                      "ycc16_over_floor": round(us["ycc16"] / us["floor"], 3), "floor": floor_on,
+                      "luma_kernel": info.luma_kernel, "chroma_kernel": info.chroma_kernel, "split": info.split, "join": info.join,
+                      "merge": info.merge, "launches": info.launches, "measured": True}), flush=True)
+    del xs, ys
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -1402,7 +1539,9 @@ def main():
     ctx = L.Context(0)
     parent = ParentLib(args.parent_lib) if args.parent_lib else None
     for name in args.only.split(","):
-        if name in YCC_OUT_WORKLOADS:
+        if name in YCC16_WORKLOADS:
+            run_ycc16(name, args, ctx, torch, parent)
+        elif name in YCC_OUT_WORKLOADS:
             run_ycc_out(name, args, ctx, torch, parent)
         elif name in YCC_WORKLOADS:
             run_ycc(name, args, ctx, torch, parent)
