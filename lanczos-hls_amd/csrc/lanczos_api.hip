@@ -1444,27 +1444,83 @@ int lanczos_resize_dest_host(lanczos_ctx* ctx, const lanczos_resize_desc* d, con
 
 int lanczos_last_dest_route(const lanczos_ctx* ctx) { return ctx ? ctx->last_dest_route : 0; }
 
-// ---- YCbCr frames into RGB bytes and tensors (lanczos_resize_ycc.hip) ------------------------------------------------------
-int lanczos_ycc_source_init(lanczos_ycc_source* src, const lanczos_resize_desc* d, int layout, int sub_x, int sub_y) {
+// ---- YCbCr frames (lanczos_resize_ycc.hip): lanczos_resize_ycc_*, lanczos_resize_ycc_out and lanczos_resize_ycc16 fill one ----
+// request, lz::YccRequest, with the bytes of a sample (B: 1, or 2 for the ycc16 entries) and what is stored
+extern "C++" {
+static int ycc_source_init(lanczos_ycc_source* src, const lanczos_resize_desc* d, int B, int layout, int sub_x, int sub_y) {
     if (!src) return LANCZOS_ERR_BAD_ARG;
-    const int rc = lz::ycc_desc_validate(d);
+    const int rc = lz::ycc_desc_validate(d, B);
     if (rc != LANCZOS_OK) return rc;
-    if ((sub_x | sub_y) & ~1) return LANCZOS_ERR_BAD_ARG;
-    const int64_t cw = (d->in_w + sub_x) >> sub_x, ch = (d->in_h + sub_y) >> sub_y, luma = (int64_t)d->in_w * d->in_h;
-    *src = lanczos_ycc_source{};
-    src->layout = layout, src->sub_x = sub_x, src->sub_y = sub_y;
-    src->y_row_stride = d->in_w, src->cb_offset = luma;
-    if (layout == LANCZOS_YCC_PLANAR) src->c_row_stride = cw, src->cr_offset = luma + cw * ch;
-    else src->c_row_stride = 2 * cw, src->cr_offset = luma;
-    lz::YccSource s;
-    return lz::ycc_source_resolve(d, src, &s);
+    return lz::ycc_layout_init(src, d->in_w, d->in_h, B, layout, sub_x, sub_y);
+}
+
+static int ycc_source_resolve(const lanczos_resize_desc* d, const lanczos_ycc_source* src, int B, lz::YccLayout* s) {
+    const int rc = lz::ycc_desc_validate(d, B);
+    if (rc != LANCZOS_OK) return rc;
+    return lz::ycc_layout_resolve(src, d->in_w, d->in_h, B, false, 0, 0, s);
+}
+
+static int ycc_dest_init(lanczos_ycc_dest* dst, const lanczos_resize_desc* d, const lanczos_resize_window* win, int B, int layout,
+                         int sub_x, int sub_y) {
+    if (!dst) return LANCZOS_ERR_BAD_ARG;
+    int rc = lz::ycc_desc_validate(d, B);
+    lz::RsWindow w;
+    if (rc == LANCZOS_OK) rc = lz::resize_window_resolve(d, win, &w);
+    if (rc != LANCZOS_OK) return rc;
+    return lz::ycc_layout_init(dst, w.w, w.h, B, layout, sub_x, sub_y);
+}
+
+static int ycc_dest_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_ycc_dest* dst, int B) {
+    int rc = lz::ycc_desc_validate(d, B);
+    lz::RsWindow w;
+    if (rc == LANCZOS_OK) rc = lz::resize_window_resolve(d, win, &w);
+    if (rc != LANCZOS_OK) return rc;
+    lz::YccLayout s;
+    return lz::ycc_layout_resolve(dst, w.w, w.h, B, true, w.x0, w.y0, &s);
+}
+
+// What the launching entries share once q is resolved: the lock, the device, the resize state, the context's stream for host
+// buffers, the call, and on LANCZOS_OK last_kernel and `store`, which copies q.info into the entry's public info struct
+template <class Store>
+static int ycc_run(lanczos_ctx* ctx, lz::YccRequest& q, bool host, Store&& store) {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    LZ_HIP(ctx, hipSetDevice(ctx->device));
+    if (host && !ctx->stream) return LANCZOS_ERR_HIP;
+    int rc = resize_state(ctx);
+    if (rc != LANCZOS_OK) return rc;
+    route_begin(ctx);
+    if (host) q.stream = ctx->stream;
+    q.last_hip = &ctx->last_hip;
+    rc = host ? lz::resize_ycc_host(ctx->resize, q) : lz::resize_ycc_device(ctx->resize, q);
+    if (rc == LANCZOS_OK) ctx->last_kernel = q.info.luma_kernel, store(q.info);
+    return rc;
+}
+
+// every lanczos_resize_ycc_* entry: v NULL stores RGB bytes
+static int resize_ycc(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
+                      const lanczos_ycc_source* src, const int32_t* table, const lanczos_tensor_view* v, bool tensor,
+                      const ResizeBufs& b) {
+    if (!ctx || b.null() || !table) return LANCZOS_ERR_BAD_ARG;
+    lz::YccRequest q;
+    q.d = d, q.o = o, q.win = win, q.table = table, q.B = 1, q.kind = tensor ? lz::kYccOutElems : lz::kYccOutRgb;
+    q.in = b.in, q.out = b.out, q.frames = b.frames;
+    q.in_frame_stride = b.in_frame_stride, q.out_frame_stride = b.out_frame_stride, q.stream = (hipStream_t)b.stream;
+    int rc = ycc_source_resolve(d, src, 1, &q.s);
+    if (rc == LANCZOS_OK && tensor) rc = lz::tensor_view_validate(d, win, v, &q.t);
+    if (rc != LANCZOS_OK) return rc;
+    return ycc_run(ctx, q, b.host, [&](const lz::YccInfo& i) {
+        ctx->last_ycc = lanczos_ycc_info{i.luma_kernel, i.chroma_kernel, i.split, i.launches, {}};
+    });
+}
+}   // extern "C++"
+
+int lanczos_ycc_source_init(lanczos_ycc_source* src, const lanczos_resize_desc* d, int layout, int sub_x, int sub_y) {
+    return ycc_source_init(src, d, 1, layout, sub_x, sub_y);
 }
 
 int lanczos_ycc_source_validate(const lanczos_resize_desc* d, const lanczos_ycc_source* src) {
-    const int rc = lz::ycc_desc_validate(d);
-    if (rc != LANCZOS_OK) return rc;
-    lz::YccSource s;
-    return lz::ycc_source_resolve(d, src, &s);
+    lz::YccLayout s;
+    return ycc_source_resolve(d, src, 1, &s);
 }
 
 int lanczos_ycc_table(int standard, int32_t* t) { return t && lz::ycc_table(standard, t) ? LANCZOS_OK : LANCZOS_ERR_BAD_ARG; }
@@ -1474,33 +1530,6 @@ int lanczos_last_ycc_info(const lanczos_ctx* ctx, lanczos_ycc_info* info) {
     *info = ctx->last_ycc;
     return LANCZOS_OK;
 }
-
-extern "C++" {
-// every lanczos_resize_ycc_* entry: v NULL stores RGB bytes
-static int resize_ycc(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* o, const lanczos_resize_window* win,
-                      const lanczos_ycc_source* src, const int32_t* table, const lanczos_tensor_view* v, bool tensor,
-                      const ResizeBufs& b) {
-    if (!ctx || b.null() || !table) return LANCZOS_ERR_BAD_ARG;
-    lz::YccRequest q;
-    q.d = d, q.o = o, q.win = win, q.table = table, q.tensor = tensor;
-    q.in = b.in, q.out = b.out, q.frames = b.frames;
-    q.in_frame_stride = b.in_frame_stride, q.out_frame_stride = b.out_frame_stride, q.stream = (hipStream_t)b.stream;
-    int rc = lz::ycc_desc_validate(d);
-    if (rc == LANCZOS_OK) rc = lz::ycc_source_resolve(d, src, &q.s);
-    if (rc == LANCZOS_OK && tensor) rc = lz::tensor_view_validate(d, win, v, &q.t);
-    if (rc != LANCZOS_OK) return rc;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    LZ_HIP(ctx, hipSetDevice(ctx->device));
-    if (b.host && !ctx->stream) return LANCZOS_ERR_HIP;
-    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
-    route_begin(ctx);
-    if (b.host) q.stream = ctx->stream;
-    q.last_hip = &ctx->last_hip;
-    rc = b.host ? lz::resize_ycc_host(ctx->resize, q) : lz::resize_ycc_device(ctx->resize, q);
-    if (rc == LANCZOS_OK) ctx->last_ycc = q.info, ctx->last_kernel = q.info.luma_kernel;
-    return rc;
-}
-}   // extern "C++"
 
 int lanczos_resize_ycc_device(lanczos_ctx* ctx, const lanczos_resize_desc* d, const lanczos_resize_opts* opts,
                               const lanczos_resize_window* win, const lanczos_ycc_source* src, const int32_t* d_table,
@@ -1528,32 +1557,14 @@ int lanczos_resize_ycc_tensor_host(lanczos_ctx* ctx, const lanczos_resize_desc* 
     return resize_ycc(ctx, d, opts, win, src, table, v, true, host_bufs(in, out, frames));
 }
 
-// ---- into YCbCr frames (lanczos_resize_ycc_out.hip) ----------------------------------------------------------------------
+// ---- into YCbCr frames -------------------------------------------------------------------------------------------------------
 int lanczos_ycc_dest_init(lanczos_ycc_dest* dst, const lanczos_resize_desc* d, const lanczos_resize_window* win, int layout,
                           int sub_x, int sub_y) {
-    if (!dst) return LANCZOS_ERR_BAD_ARG;
-    int rc = lz::ycc_desc_validate(d);
-    lz::RsWindow w;
-    if (rc == LANCZOS_OK) rc = lz::resize_window_resolve(d, win, &w);
-    if (rc != LANCZOS_OK) return rc;
-    if ((sub_x | sub_y) & ~1) return LANCZOS_ERR_BAD_ARG;
-    const int64_t cw = (w.w + sub_x) >> sub_x, ch = (w.h + sub_y) >> sub_y, luma = (int64_t)w.w * w.h;
-    *dst = lanczos_ycc_dest{};
-    dst->layout = layout, dst->sub_x = sub_x, dst->sub_y = sub_y;
-    dst->y_row_stride = w.w, dst->cb_offset = luma;
-    if (layout == LANCZOS_YCC_PLANAR) dst->c_row_stride = cw, dst->cr_offset = luma + cw * ch;
-    else dst->c_row_stride = 2 * cw, dst->cr_offset = luma;
-    lz::YccDest s;
-    return lz::ycc_dest_resolve(w, dst, false, &s);
+    return ycc_dest_init(dst, d, win, 1, layout, sub_x, sub_y);
 }
 
 int lanczos_ycc_dest_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_ycc_dest* dst) {
-    int rc = lz::ycc_desc_validate(d);
-    lz::RsWindow w;
-    if (rc == LANCZOS_OK) rc = lz::resize_window_resolve(d, win, &w);
-    if (rc != LANCZOS_OK) return rc;
-    lz::YccDest s;
-    return lz::ycc_dest_resolve(w, dst, true, &s);
+    return ycc_dest_validate(d, win, dst, 1);
 }
 
 int lanczos_ycc_table_forward(int standard, int32_t* t) {
@@ -1571,28 +1582,22 @@ int lanczos_resize_ycc_out(lanczos_ctx* ctx, const lanczos_ycc_out_request* rq) 
     if (rq->memory != LANCZOS_MEM_DEVICE && rq->memory != LANCZOS_MEM_HOST) return LANCZOS_ERR_BAD_ARG;
     for (int32_t r : rq->reserved)
         if (r != 0) return LANCZOS_ERR_BAD_ARG;
-    const bool host = rq->memory == LANCZOS_MEM_HOST;
-    lz::YccOutRequest q;
-    q.d = rq->d, q.o = rq->opts, q.win = rq->win, q.from_rgb = rq->src == nullptr, q.dst = rq->dst, q.table = rq->table;
+    const bool from_rgb = rq->src == nullptr;
+    lz::YccRequest q;
+    q.d = rq->d, q.o = rq->opts, q.win = rq->win, q.dst = rq->dst, q.table = rq->table;
+    q.B = 1, q.kind = from_rgb ? lz::kYccOutYccFromRgb : lz::kYccOutYcc;
     q.in = rq->in, q.out = rq->out, q.frames = rq->frames;
     q.in_frame_stride = rq->in_frame_stride, q.out_frame_stride = rq->out_frame_stride, q.stream = (hipStream_t)rq->stream;
-    int rc = lz::ycc_desc_validate(rq->d);
+    int rc = lz::ycc_desc_validate(rq->d, 1);
     if (rc != LANCZOS_OK) return rc;
-    if (q.from_rgb ? !rq->table : rq->table != nullptr) return LANCZOS_ERR_BAD_ARG;   // the table belongs to RGB frames, and only to them
-    if (!q.from_rgb && (rc = lz::ycc_source_resolve(rq->d, rq->src, &q.s)) != LANCZOS_OK) return rc;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    LZ_HIP(ctx, hipSetDevice(ctx->device));
-    if (host && !ctx->stream) return LANCZOS_ERR_HIP;
-    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
-    route_begin(ctx);
-    if (host) q.stream = ctx->stream;
-    q.last_kernel = &ctx->last_kernel, q.last_hip = &ctx->last_hip;
-    rc = host ? lz::resize_ycc_out_host(ctx->resize, q) : lz::resize_ycc_out_device(ctx->resize, q);
-    if (rc == LANCZOS_OK) ctx->last_ycc_out = q.info, ctx->last_kernel = q.info.luma_kernel;
-    return rc;
+    if (from_rgb ? !rq->table : rq->table != nullptr) return LANCZOS_ERR_BAD_ARG;   // the table belongs to RGB frames, and only to them
+    if (!from_rgb && (rc = ycc_source_resolve(rq->d, rq->src, 1, &q.s)) != LANCZOS_OK) return rc;
+    return ycc_run(ctx, q, rq->memory == LANCZOS_MEM_HOST, [&](const lz::YccInfo& i) {
+        ctx->last_ycc_out = lanczos_ycc_out_info{i.luma_kernel, i.chroma_kernel, i.split, i.join, i.encode, i.launches, {}};
+    });
 }
 
-// ---- YCbCr frames of 16-bit words (lanczos_resize_ycc16.hip) --------------------------------------------------------------
+// ---- YCbCr frames of 16-bit words --------------------------------------------------------------------------------------------
 int lanczos_ycc16_matrix_init(lanczos_ycc16_matrix* m, int standard, int depth, int msb_aligned, int full_range) {
     return m && lz::ycc16_matrix_init(m, standard, depth, msb_aligned != 0, full_range != 0) ? LANCZOS_OK : LANCZOS_ERR_BAD_ARG;
 }
@@ -1600,52 +1605,21 @@ int lanczos_ycc16_matrix_init(lanczos_ycc16_matrix* m, int standard, int depth, 
 int lanczos_ycc16_matrix_validate(const lanczos_ycc16_matrix* m) { return lz::ycc16_matrix_validate(m); }
 
 int lanczos_ycc16_source_init(lanczos_ycc_source* src, const lanczos_resize_desc* d, int layout, int sub_x, int sub_y) {
-    if (!src) return LANCZOS_ERR_BAD_ARG;
-    const int rc = lz::ycc16_desc_validate(d);
-    if (rc != LANCZOS_OK) return rc;
-    if ((sub_x | sub_y) & ~1) return LANCZOS_ERR_BAD_ARG;
-    const int64_t cw = (d->in_w + sub_x) >> sub_x, ch = (d->in_h + sub_y) >> sub_y, luma = (int64_t)d->in_w * d->in_h * 2;
-    *src = lanczos_ycc_source{};
-    src->layout = layout, src->sub_x = sub_x, src->sub_y = sub_y;
-    src->y_row_stride = 2 * (int64_t)d->in_w, src->cb_offset = luma;
-    if (layout == LANCZOS_YCC_PLANAR) src->c_row_stride = 2 * cw, src->cr_offset = luma + 2 * cw * ch;
-    else src->c_row_stride = 4 * cw, src->cr_offset = luma;
-    lz::YccSource s;
-    return lz::ycc16_source_resolve(d, src, &s);
+    return ycc_source_init(src, d, 2, layout, sub_x, sub_y);
 }
 
 int lanczos_ycc16_source_validate(const lanczos_resize_desc* d, const lanczos_ycc_source* src) {
-    const int rc = lz::ycc16_desc_validate(d);
-    if (rc != LANCZOS_OK) return rc;
-    lz::YccSource s;
-    return lz::ycc16_source_resolve(d, src, &s);
+    lz::YccLayout s;
+    return ycc_source_resolve(d, src, 2, &s);
 }
 
 int lanczos_ycc16_dest_init(lanczos_ycc_dest* dst, const lanczos_resize_desc* d, const lanczos_resize_window* win, int layout,
                             int sub_x, int sub_y) {
-    if (!dst) return LANCZOS_ERR_BAD_ARG;
-    int rc = lz::ycc16_desc_validate(d);
-    lz::RsWindow w;
-    if (rc == LANCZOS_OK) rc = lz::resize_window_resolve(d, win, &w);
-    if (rc != LANCZOS_OK) return rc;
-    if ((sub_x | sub_y) & ~1) return LANCZOS_ERR_BAD_ARG;
-    const int64_t cw = (w.w + sub_x) >> sub_x, ch = (w.h + sub_y) >> sub_y, luma = (int64_t)w.w * w.h * 2;
-    *dst = lanczos_ycc_dest{};
-    dst->layout = layout, dst->sub_x = sub_x, dst->sub_y = sub_y;
-    dst->y_row_stride = 2 * (int64_t)w.w, dst->cb_offset = luma;
-    if (layout == LANCZOS_YCC_PLANAR) dst->c_row_stride = 2 * cw, dst->cr_offset = luma + 2 * cw * ch;
-    else dst->c_row_stride = 4 * cw, dst->cr_offset = luma;
-    lz::YccDest s;
-    return lz::ycc16_dest_resolve(w, dst, false, &s);
+    return ycc_dest_init(dst, d, win, 2, layout, sub_x, sub_y);
 }
 
 int lanczos_ycc16_dest_validate(const lanczos_resize_desc* d, const lanczos_resize_window* win, const lanczos_ycc_dest* dst) {
-    int rc = lz::ycc16_desc_validate(d);
-    lz::RsWindow w;
-    if (rc == LANCZOS_OK) rc = lz::resize_window_resolve(d, win, &w);
-    if (rc != LANCZOS_OK) return rc;
-    lz::YccDest s;
-    return lz::ycc16_dest_resolve(w, dst, true, &s);
+    return ycc_dest_validate(d, win, dst, 2);
 }
 
 int lanczos_last_ycc16_info(const lanczos_ctx* ctx, lanczos_ycc16_info* info) {
@@ -1656,26 +1630,27 @@ int lanczos_last_ycc16_info(const lanczos_ctx* ctx, lanczos_ycc16_info* info) {
 
 extern "C++" {
 // everything lanczos_resize_ycc16 refuses from the request alone; on LANCZOS_OK q holds the request, resolved
-static int ycc16_request_resolve(const lanczos_ycc16_request* rq, lz::Ycc16Request& q) {
+static int ycc16_request_resolve(const lanczos_ycc16_request* rq, lz::YccRequest& q) {
     if (!rq || !rq->in || !rq->out || !rq->src || rq->frames <= 0) return LANCZOS_ERR_BAD_ARG;
     if (rq->memory != LANCZOS_MEM_DEVICE && rq->memory != LANCZOS_MEM_HOST) return LANCZOS_ERR_BAD_ARG;
     for (int32_t r : rq->reserved)
         if (r != 0) return LANCZOS_ERR_BAD_ARG;
     const bool host = rq->memory == LANCZOS_MEM_HOST;
-    q.d = rq->d, q.o = rq->opts, q.win = rq->win, q.dst = rq->dst, q.rgb = rq->matrix != nullptr, q.tensor = rq->norm != nullptr;
+    q.d = rq->d, q.o = rq->opts, q.win = rq->win, q.dst = rq->dst, q.B = 2;
+    q.kind = rq->dst ? lz::kYccOutYcc : rq->norm ? lz::kYccOutElems : lz::kYccOutRgb;
     q.in = rq->in, q.out = rq->out, q.frames = rq->frames;
     q.in_frame_stride = rq->in_frame_stride, q.out_frame_stride = rq->out_frame_stride, q.stream = (hipStream_t)rq->stream;
-    int rc = lz::ycc16_desc_validate(rq->d);
+    int rc = lz::ycc_desc_validate(rq->d, 2);
     if (rc != LANCZOS_OK) return rc;
     // the output kind: dst alone, matrix alone, or matrix and norm
     if ((rq->dst != nullptr) == (rq->matrix != nullptr) || (rq->norm && !rq->matrix)) return LANCZOS_ERR_BAD_ARG;
-    if ((rc = lz::ycc16_source_resolve(rq->d, rq->src, &q.s)) != LANCZOS_OK) return rc;
+    if ((rc = ycc_source_resolve(rq->d, rq->src, 2, &q.s)) != LANCZOS_OK) return rc;
     lz::RsResolved r;
     lz::RsWindow w;
     if ((rc = lz::resize_resolve(rq->d, rq->opts, &r)) != LANCZOS_OK) return rc;   // (a reducing_gap on words: LANCZOS_ERR_BAD_ARG)
     if ((rc = lz::resize_window_resolve(rq->d, rq->win, &w)) != LANCZOS_OK) return rc;
-    lz::YccDest t;
-    if (rq->dst && (rc = lz::ycc16_dest_resolve(w, rq->dst, true, &t)) != LANCZOS_OK) return rc;
+    lz::YccLayout t;
+    if (rq->dst && (rc = lz::ycc_layout_resolve(rq->dst, w.w, w.h, 2, true, w.x0, w.y0, &t)) != LANCZOS_OK) return rc;
     if (rq->matrix) {
         if ((rc = lz::ycc16_matrix_validate(rq->matrix)) != LANCZOS_OK) return rc;
         q.m = *rq->matrix;
@@ -1691,26 +1666,18 @@ static int ycc16_request_resolve(const lanczos_ycc16_request* rq, lz::Ycc16Reque
 }   // extern "C++"
 
 int lanczos_ycc16_request_validate(const lanczos_ycc16_request* rq) {
-    lz::Ycc16Request q;
+    lz::YccRequest q;
     return ycc16_request_resolve(rq, q);
 }
 
 int lanczos_resize_ycc16(lanczos_ctx* ctx, const lanczos_ycc16_request* rq) {
     if (!ctx) return LANCZOS_ERR_BAD_ARG;
-    lz::Ycc16Request q;
-    int rc = ycc16_request_resolve(rq, q);
+    lz::YccRequest q;
+    const int rc = ycc16_request_resolve(rq, q);
     if (rc != LANCZOS_OK) return rc;
-    const bool host = rq->memory == LANCZOS_MEM_HOST;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    LZ_HIP(ctx, hipSetDevice(ctx->device));
-    if (host && !ctx->stream) return LANCZOS_ERR_HIP;
-    if ((rc = resize_state(ctx)) != LANCZOS_OK) return rc;
-    route_begin(ctx);
-    if (host) q.stream = ctx->stream;
-    q.last_hip = &ctx->last_hip;
-    rc = host ? lz::resize_ycc16_host(ctx->resize, q) : lz::resize_ycc16_device(ctx->resize, q);
-    if (rc == LANCZOS_OK) ctx->last_ycc16 = q.info, ctx->last_kernel = q.info.luma_kernel;
-    return rc;
+    return ycc_run(ctx, q, rq->memory == LANCZOS_MEM_HOST, [&](const lz::YccInfo& i) {
+        ctx->last_ycc16 = lanczos_ycc16_info{i.luma_kernel, i.chroma_kernel, i.split, i.join, i.merge, i.launches, {}};
+    });
 }
 
 int lanczos_reduce_size(int in_w, int in_h, int fx, int fy, const int32_t* box, int* out_w, int* out_h) {

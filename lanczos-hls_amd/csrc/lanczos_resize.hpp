@@ -4,9 +4,10 @@
 // scratch, the executor of a route (resize_device), the staging of the host entries and the alpha pass kernels are in
 // lanczos_resize.hip.  The kernels are written once for 8-bit, 16-bit (LANCZOS_RESIZE_U16) and float (LANCZOS_RESIZE_F32)
 // samples in lanczos_resize_fused.hpp; LZ_RS_FUSED_INSTANCES below lists the fused instances and says which unit compiles what
-// (the converter of lanczos_tensor_norm is in lanczos_resize_tensor_norm.hip).  YCbCr frames (lanczos_resize_ycc_*) are three
-// one-channel requests through resize_device with a split in front and a merge behind, in lanczos_resize_ycc.hip; the way back
-// (lanczos_resize_ycc_out: planes with a pitched destination and a join, or RGB frames and an encode) is in lanczos_resize_ycc_out.hip.  The filter of a request (LANCZOS_RESIZE_FILTER)
+// (the converter of lanczos_tensor_norm is in lanczos_resize_tensor_norm.hip).  YCbCr frames (lanczos_resize_ycc_*,
+// lanczos_resize_ycc_out, lanczos_resize_ycc16) are one-channel requests through resize_device with a split in front and a join
+// or a merge behind, one composition for the three families in lanczos_resize_ycc.hip; their host-only part is
+// lanczos_resize_ycc_layout.cpp (the section at the end of this file).  The filter of a request (LANCZOS_RESIZE_FILTER)
 // only changes the tables; LANCZOS_FILTER_NEAREST has index tables and a kernel of its own (lanczos_resize_nearest.hip).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -191,9 +192,9 @@ struct ResizeState {
     ScratchBlock packed;                     // the tightly packed copy of a source on the PACKED route (k_rs_pack_source writes it)
     ScratchBlock unpacked;                   // the tightly packed result of a destination on the UNPACKED route (k_rs_unpack_dest reads it)
     ScratchBlock stage_in, stage_out;        // staging of lanczos_resize_host
-    ScratchBlock ycc_in;                     // the Cb and Cr planes k_rs_ycc_split makes of interleaved chroma (lanczos_resize_ycc.hip)
-    ScratchBlock ycc_planes;                 // the resized Y, Cb and Cr planes k_rs_ycc_merge reads
-    ScratchBlock ycc_out;                    // the tight Cb and Cr planes k_rs_ycc_join interleaves (lanczos_resize_ycc_out.hip)
+    ScratchBlock ycc_in;                     // the Cb and Cr planes k_rs_ycc_split[16] makes of interleaved chroma (lanczos_resize_ycc.hip)
+    ScratchBlock ycc_planes;                 // the resized Y, Cb and Cr planes k_rs_ycc_merge / k_rs_ycc16_merge reads
+    ScratchBlock ycc_out;                    // the tight Cb and Cr planes k_rs_ycc_join[16] interleaves
     ScratchBlock ycc_rgb;                    // the tight resized RGB frames k_rs_ycc_encode reads
     explicit ResizeState(Lifetime* l) : life(l), axes(l, 32) {}
 };
@@ -469,116 +470,82 @@ hipError_t rs_nearest_launch(const uint8_t* in, uint8_t* out, int in_w, int out_
 hipError_t rs_crop_launch(const uint8_t* in, uint8_t* out, size_t in_pitch, size_t row_bytes, int rows, int frames,
                           size_t in_fs, size_t out_fs, RsIssue& is);
 
-// ---- YCbCr frames (lanczos_resize_ycc.hip): three one-channel requests through resize_device, a split in front of interleaved
-// chroma and the merge through the colour table behind them.  A lanczos_ycc_source resolved by ycc_source_resolve:
-struct YccSource {
+// ---- YCbCr frames: lanczos_resize_ycc_* (8-bit frames into RGB bytes and tensor elements), lanczos_resize_ycc_out
+// (into 8-bit YCbCr frames, from YCbCr or from RGB) and lanczos_resize_ycc16 (frames of 16-bit words into any of these) are one
+// request and one composition.  Nothing of it resizes: every plane is a one-channel request of B-byte samples through
+// resize_device with a pitched source and a pitched destination, a split in front of interleaved chroma, a join behind
+// interleaved chroma out, and behind the planes the merge into RGB or elements (lanczos_resize_ycc.hip; the merge of words in
+// lanczos_resize_ycc16.hip).  From RGB bytes it is the three-channel request into context scratch and k_rs_ycc_encode behind it
+// (lanczos_resize_ycc_out.hip).  What needs no device -- the layouts, the descriptor check, the standard tables and matrices --
+// is in lanczos_resize_ycc_layout.cpp and lanczos_resize_route.cpp.
+// A lanczos_ycc_source or lanczos_ycc_dest resolved by ycc_layout_resolve for a w x h luma frame of B-byte samples; everything in
+// bytes:
+struct YccLayout {
     int layout = 0, sx = 0, sy = 0;
     int cw = 0, ch = 0;                     // the chroma planes' size
-    size_t y_rs = 0, c_rs = 0;              // row strides (bytes); c_rs of NV12 / NV21 is the interleaved rows'
-    size_t cb_off = 0, cr_off = 0;          // NV12 / NV21: both the interleaved plane's
-    size_t extent = 0;                      // of one frame: the end of its last plane
-    bool interleaved() const { return layout != LANCZOS_YCC_PLANAR; }
-};
-// d validated for these entries (three channels, 8-bit, no alpha) by ycc_desc_validate
-int ycc_desc_validate(const lanczos_resize_desc* d);
-int ycc_source_resolve(const lanczos_resize_desc* d, const lanczos_ycc_source* src, YccSource* s);
-bool ycc_table(int standard, int32_t* t);
-// clip8(sum >> 6) with the clamp in front of the shift: the sum held to [0, 255 * 64 + 63] and then shifted is the same byte.
-// (Shift first and clamp after compiles, two pixels at a time, into v_ashr_pk_u8_i32, and on an MI355X the dword that
-// instruction leaves did not have a clean upper half: OR-ed with pixels 2 and 3 it turned them into 255.)
-__device__ __forceinline__ uint32_t ycc_clip8_shift6(int sum) { return (uint32_t)(sum < 0 ? 0 : sum > 16383 ? 16383 : sum) >> 6; }
-// One call of the lanczos_resize_ycc_* entries, filled in by lanczos_api.hip
-struct YccRequest {
-    const lanczos_resize_desc* d = nullptr;       // validated (ycc_desc_validate)
-    const lanczos_resize_opts* o = nullptr;
-    const lanczos_resize_window* win = nullptr;
-    YccSource s;                                  // resolved
-    const int32_t* table = nullptr;               // [3][3][256]
-    const void* in = nullptr;
-    void* out = nullptr;
-    int frames = 0;
-    size_t in_frame_stride = 0, out_frame_stride = 0;
-    hipStream_t stream = nullptr;
-    int* last_hip = nullptr;
-    bool tensor = false;
-    RsTensorOut t;                                // validated (tensor_view_validate) where tensor is set
-    lanczos_ycc_info info{};                      // out, on LANCZOS_OK
-};
-// ctx->mu held, device set: device pointers, asynchronous
-int resize_ycc_device(ResizeState* st, YccRequest& q);
-// host buffers, a host colour table, and of a tensor request a host element table and host flips; synchronous
-int resize_ycc_host(ResizeState* st, YccRequest& q);
-
-// ---- into YCbCr frames (lanczos_resize_ycc_out.hip): from a YCbCr source three one-channel requests with a pitched source and a
-// pitched destination, a split in front of interleaved chroma and a join behind it; from RGB bytes the three-channel request into
-// context scratch and k_rs_ycc_encode behind it.  A lanczos_ycc_dest resolved by ycc_dest_resolve for a w x h window:
-struct YccDest {
-    int layout = 0, sx = 0, sy = 0;
-    int cw = 0, ch = 0;                     // the stored chroma planes' size
-    size_t y_rs = 0, c_rs = 0;              // row strides (bytes); c_rs of NV12 / NV21 is the interleaved rows'
+    size_t y_rs = 0, c_rs = 0;              // row strides; c_rs of NV12 / NV21 is the interleaved rows'
     size_t cb_off = 0, cr_off = 0;          // NV12 / NV21: both the interleaved plane's
     size_t extent = 0;                      // of one frame, the default frame stride: the end of its last plane
     size_t named = 0;                       // from a frame's first byte to the last one the layout names, + 1
     bool interleaved() const { return layout != LANCZOS_YCC_PLANAR; }
 };
-// aligned_origin: refuse a window origin that is no multiple of the subsampling (the rule of a YCbCr source)
-int ycc_dest_resolve(const RsWindow& w, const lanczos_ycc_dest* dst, bool aligned_origin, YccDest* s);
+// d validated for these entries: three channels, samples of B bytes (1 or 2), no alpha (lanczos_resize_route.cpp)
+int ycc_desc_validate(const lanczos_resize_desc* d, int B);
+// L: lanczos_ycc_source or lanczos_ycc_dest.  aligned_origin: refuse a window origin (x0, y0) that is no multiple of the
+// subsampling (the rule of a destination filled from YCbCr frames).  Every refusal is LANCZOS_ERR_BAD_ARG
+template <class L>
+int ycc_layout_resolve(const L* l, int w, int h, int B, bool aligned_origin, int x0, int y0, YccLayout* s);
+// the tight layout -- Y, then Cb, then Cr (or the interleaved plane), rows packed -- and its resolution: what the *_init entries do
+template <class L>
+int ycc_layout_init(L* l, int w, int h, int B, int layout, int sub_x, int sub_y);
+bool ycc_table(int standard, int32_t* t);
 bool ycc_table_forward(int standard, int32_t* t);
-// k_rs_ycc_split: shared with the composition above
-hipError_t ycc_split_launch(const uint8_t* in, size_t in_fs, const YccSource& s, uint8_t* out, size_t plane_bytes, int frames,
-                            RsIssue& is);
-// One call of lanczos_resize_ycc_out, filled in by lanczos_api.hip
-struct YccOutRequest {
-    const lanczos_resize_desc* d = nullptr;       // validated (ycc_desc_validate)
-    const lanczos_resize_opts* o = nullptr;
-    const lanczos_resize_window* win = nullptr;
-    bool from_rgb = false;
-    YccSource s;                                  // resolved, where the frames are YCbCr
-    const lanczos_ycc_dest* dst = nullptr;        // resolved by the entry points, which know the window
-    const int32_t* table = nullptr;               // from RGB: the forward table [3][3][256]
-    const void* in = nullptr;
-    void* out = nullptr;
-    int frames = 0;
-    size_t in_frame_stride = 0, out_frame_stride = 0;
-    hipStream_t stream = nullptr;
-    int *last_kernel = nullptr, *last_hip = nullptr;
-    lanczos_ycc_out_info info{};                  // out, on LANCZOS_OK
-};
-int resize_ycc_out_device(ResizeState* st, YccOutRequest& q);
-// host buffers and a host table; frames one extent apart; synchronous.  The destination goes up before it comes back
-int resize_ycc_out_host(ResizeState* st, YccOutRequest& q);
-
-// ---- YCbCr frames of 16-bit words (lanczos_resize_ycc16.hip; lanczos_resize_ycc16): the compositions above on one-channel
-// LANCZOS_RESIZE_U16 requests, with a split and a join of word pairs and a merge through an integer matrix.  YccSource and YccDest
-// hold bytes here too; the 16-bit validators resolve them
-int ycc16_desc_validate(const lanczos_resize_desc* d);
-int ycc16_source_resolve(const lanczos_resize_desc* d, const lanczos_ycc_source* src, YccSource* s);
-int ycc16_dest_resolve(const RsWindow& w, const lanczos_ycc_dest* dst, bool aligned_origin, YccDest* s);
 int ycc16_matrix_validate(const lanczos_ycc16_matrix* m);
 bool ycc16_matrix_init(lanczos_ycc16_matrix* m, int standard, int depth, bool msb_aligned, bool full_range);
-// One call of lanczos_resize_ycc16, filled in by lanczos_api.hip
-struct Ycc16Request {
-    const lanczos_resize_desc* d = nullptr;       // validated (ycc16_desc_validate)
+// clip8(sum >> 6) with the clamp in front of the shift: the sum held to [0, 255 * 64 + 63] and then shifted is the same byte.
+// (Shift first and clamp after compiles, two pixels at a time, into v_ashr_pk_u8_i32, and on an MI355X the dword that
+// instruction leaves did not have a clean upper half: OR-ed with pixels 2 and 3 it turned them into 255.)
+__device__ __forceinline__ uint32_t ycc_clip8_shift6(int sum) { return (uint32_t)(sum < 0 ? 0 : sum > 16383 ? 16383 : sum) >> 6; }
+// What a call stores, and what it launched: the superset of lanczos_ycc_info, lanczos_ycc_out_info and lanczos_ycc16_info
+enum YccOut { kYccOutRgb, kYccOutElems, kYccOutYcc, kYccOutYccFromRgb };
+struct YccInfo {
+    int luma_kernel = 0, chroma_kernel = 0, split = 0, join = 0, merge = 0, encode = 0, launches = 0;
+};
+// One call of any of the three families, filled in by lanczos_api.hip
+struct YccRequest {
+    const lanczos_resize_desc* d = nullptr;       // validated (ycc_desc_validate with B)
     const lanczos_resize_opts* o = nullptr;
     const lanczos_resize_window* win = nullptr;
-    YccSource s;                                  // resolved
-    const lanczos_ycc_dest* dst = nullptr;        // YCbCr out: resolved by the entry points, which know the window
-    bool rgb = false;                             // RGB words or elements out: m is validated
-    lanczos_ycc16_matrix m{};
-    bool tensor = false;
-    RsTensorOut t;                                // validated (tensor_norm_validate) where tensor is set
+    int B = 1;                                    // bytes of a sample
+    YccOut kind = kYccOutRgb;
+    YccLayout s;                                  // resolved, where the frames are YCbCr (every kind but kYccOutYccFromRgb)
+    const lanczos_ycc_dest* dst = nullptr;        // the YCbCr kinds: resolved by the entry points, which know the window
+    const int32_t* table = nullptr;               // 8-bit RGB, elements and from RGB: [3][3][256], inverse or forward
+    lanczos_ycc16_matrix m{};                     // 16-bit RGB and elements: validated
+    RsTensorOut t;                                // kYccOutElems: validated (tensor_view_validate, of words tensor_norm_validate)
     const void* in = nullptr;
     void* out = nullptr;
     int frames = 0;
     size_t in_frame_stride = 0, out_frame_stride = 0;
     hipStream_t stream = nullptr;
     int* last_hip = nullptr;
-    lanczos_ycc16_info info{};                    // out, on LANCZOS_OK
+    YccInfo info;                                 // out, on LANCZOS_OK
+    bool tensor() const { return kind == kYccOutElems; }
+    bool to_ycc() const { return kind == kYccOutYcc || kind == kYccOutYccFromRgb; }
 };
 // ctx->mu held, device set: device pointers, asynchronous
-int resize_ycc16_device(ResizeState* st, Ycc16Request& q);
-// host buffers and, of a tensor request, host flips; frames one extent apart; synchronous.  A destination's and a tensor's
-// frames go up before they come back
-int resize_ycc16_host(ResizeState* st, Ycc16Request& q);
+int resize_ycc_device(ResizeState* st, YccRequest& q);
+// host buffers, a host table, and of an element request a host element table and host flips; frames back to back (a layout's
+// extent, w * h * 3 samples, an element frame's extent apart: the frame strides must be 0); synchronous.  A destination's and a
+// tensor's frames go up before they come back, so that what the layout does not name keeps what it held
+int resize_ycc_host(ResizeState* st, YccRequest& q);
+// the launchers the composition calls across units: the merges behind the three planes (`planes`: frames luma planes, then
+// frames pairs Cb | Cr, every plane plane_bytes long) and the encode behind the RGB resize
+hipError_t ycc_merge_launch(const uint8_t* planes, size_t plane_bytes, uint8_t* out, size_t out_fs, int w, int h,
+                            const int32_t* table, const RsTensorOut* t, int frames, RsIssue& is);
+hipError_t ycc16_merge_launch(const uint8_t* planes, size_t plane_bytes, uint8_t* out, size_t out_fs, int w, int h,
+                              const lanczos_ycc16_matrix& m, const RsTensorOut* t, int frames, RsIssue& is);
+hipError_t ycc_encode_launch(const uint8_t* in, size_t in_fs, uint8_t* out, size_t out_fs, const YccLayout& t, int w, int h,
+                             const int32_t* table, int frames, RsIssue& is);
 
 }  // namespace lz

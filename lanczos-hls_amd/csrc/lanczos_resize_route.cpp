@@ -36,6 +36,16 @@ int resize_validate(const lanczos_resize_desc* d) {
     return LANCZOS_OK;
 }
 
+// the descriptor of a YCbCr request: three channels of B-byte samples (1, or 2 with LANCZOS_RESIZE_U16), nothing else
+int ycc_desc_validate(const lanczos_resize_desc* d, int B) {
+    if (!d) return LANCZOS_ERR_BAD_ARG;
+    const int wide = B == 2 ? LANCZOS_RESIZE_U16 : 0;
+    if ((d->reserved[0] & (LANCZOS_RESIZE_ALPHA | LANCZOS_RESIZE_U16 | LANCZOS_RESIZE_F32)) != wide) return LANCZOS_ERR_UNSUPPORTED;
+    const int rc = resize_validate(d);   // (LANCZOS_FILTER_NEAREST on words: LANCZOS_ERR_UNSUPPORTED)
+    if (rc != LANCZOS_OK) return rc;
+    return d->channels == 3 ? LANCZOS_OK : LANCZOS_ERR_BAD_ARG;
+}
+
 // Pillow's sinc_filter / lanczos_filter with a as a parameter (libm sin, double)
 static double rs_sinc(double x) {
     if (x == 0.0) return 1.0;

@@ -4,10 +4,13 @@ build of the library (LANCZOS_LIB=PATH names another one, e.g. the parent commit
 
     python scripts/resize_host_time.py [--calls 5000] [--rounds 5]
 
-Three requests, one frame each, 16 x 16 -> 8 x 8, AUTO:
+Six requests, one frame each, 16 x 16 -> 8 x 8, AUTO:
   bytes    lanczos_resize_device, RGB
   crops    lanczos_resize_tensor_crops_device, RGB into a 4 x 4 float32 CHW crop
   planar   lanczos_resize_dest_device, RGB planes in, RGB planes out
+  ycc      lanczos_resize_ycc_device, NV12 into RGB bytes (four launches a call)
+  ycc_out  lanczos_resize_ycc_out, NV12 into NV12 (four launches)
+  ycc16    lanczos_resize_ycc16, P010 into P010 (four launches)
 Every round issues --calls calls on one stream through the ctypes function itself (no wrapper in between) and synchronises once
 at the end.  One JSON line: microseconds per call of every round, and their median, per request."""
 import argparse
@@ -45,6 +48,17 @@ def main():
         "crops": lambda: lib.lanczos_resize_tensor_crops_device(h, pd, None, ctypes.byref(crops), ctypes.byref(view), px, py, 1, 0, 0, s),
         "planar": lambda: lib.lanczos_resize_dest_device(h, pd, None, None, ctypes.byref(src), ctypes.byref(dst), px, py, 1, 0, 0, s),
     }
+    # one call of each YCbCr entry: luma, split, one chroma call, then merge or join
+    table = torch.from_numpy(L.ycc_table("jfif")).cuda()
+    nv12, nv12_out = L.ycc_source(d, "nv12"), L.ycc_dest(d, "nv12")
+    d16 = L.resize_desc(16, 16, 8, 8, 3, 3, bits=16)
+    rq_out = L.ycc_out_request(d, nv12_out, px, py, 1, source=nv12, stream=stream.cuda_stream)
+    rq16 = L.ycc16_request(d16, L.ycc16_source(d16, "p010"), px, py, 1, dest=L.ycc16_dest(d16, "p010"), stream=stream.cuda_stream)
+    requests.update({
+        "ycc": lambda: lib.lanczos_resize_ycc_device(h, pd, None, None, ctypes.byref(nv12), table.data_ptr(), px, py, 1, 0, 0, s),
+        "ycc_out": lambda: lib.lanczos_resize_ycc_out(h, ctypes.byref(rq_out)),
+        "ycc16": lambda: lib.lanczos_resize_ycc16(h, ctypes.byref(rq16)),
+    })
     out = {"lib": L.LIB_PATH, "calls": args.calls}
     for name, call in requests.items():
         rounds = []
